@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- BA iterations/sec of the MI355X bundle-adjustment path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-per-call] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes runs of its own: the
+first solve on a fresh handle, the J-free companion, the residual+Jacobian kernel without its point sums, per-call
+least_squares() timings and the scipy CPU baseline.  `--dump-outputs DIR` writes what the last timed solve returned
+(x, its residual vector and gradient, cost, rmse, optimality) as DIR/<name>.npy.
 
 A *step* is one outer (trust-region) iteration of the solver that replaces the reference's
 ``least_squares`` call (/root/reference/sfm_lite/sfm.py:266-268): Jacobian sweep, normal-equation
@@ -35,6 +41,25 @@ for p in (ROOT, os.path.join(ROOT, "sfm-python_amd")):
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+DUMP_BYTES = 64 << 20          # --dump-outputs writes at most this much in all
+DUMP_ELEMS = 1 << 21           # ... and at most this many entries per array
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every array as <out_dir>/<name>.npy in float64.  An array of more than DUMP_ELEMS entries is written as the
+    entries at a fixed, seeded sample of its indices (numpy default_rng(0), sorted): the same for every run of the same
+    arguments, so two builds compare entry for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, v in arrays.items():
+        v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+        if v.size > DUMP_ELEMS:
+            print(f"[bench] {name}: {v.size} entries, writing a seeded sample of {DUMP_ELEMS}", file=sys.stderr, flush=True)
+            v = v[np.sort(np.random.default_rng(0).choice(v.size, DUMP_ELEMS, replace=False))]
+        total += v.nbytes
+        if total > DUMP_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_BYTES} bytes")
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def k1_bytes_f32(C, P, N):
@@ -147,7 +172,12 @@ def main():
                     help="N = 1 only: run rank 0's share of the workload sharded G ways (all cameras, 1/G of the points and "
                          "observations) instead of the whole problem -- with --force-exchange the per-rank critical path "
                          "of a G-GPU strong-scaling run, measured on one GPU (DESIGN.md section 9)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own after the timed steps: first solve on a fresh handle, "
+                         "J-free companion, residual+Jacobian kernel without its point sums, per-call timings, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve returned as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the scipy CPU baseline")
     ap.add_argument("--settle", type=float, default=0.5,
                     help="seconds of untimed solves before the warm-up steps (start-up transient of the GPU queue)")
     ap.add_argument("--force-exchange", action="store_true",
@@ -163,11 +193,14 @@ def main():
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N > 1 only.  strong (default): one problem of the workload's size sharded over the ranks; "
                          "weak: one workload-sized shard per rank")
-    ap.add_argument("--no-per-call", action="store_true", help="skip the end-to-end least_squares() call timings")
+    ap.add_argument("--no-per-call", action="store_true",
+                    help="with --full: skip the end-to-end least_squares() call timings")
     ap.add_argument("--no-direct", action="store_true",
                     help="do not map the peers' staging buffers: every collective goes through --exchange "
                          "(default: the direct xGMI all-reduce kernel serves them, --exchange is the fallback)")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -247,12 +280,17 @@ def main():
         opt.ftol, opt.xtol, opt.gtol = 1e-10, 1e-8, 1e-8           # the reference's ftol, scipy defaults
         opt.profile = 1
 
+        last = {}                  # --dump-outputs: what the last solve of the latest run_iterations() returned
+
         def run_iterations(k):
             """exactly k outer iterations from back-to-back solves; returns per-solve results"""
             results, left = [], k
             while left > 0:
                 opt.max_iter = left
-                _, res, _, _ = be.solve(pb.x0, opt, want_fun=False, want_grad=False)
+                x, res, _, _ = be.solve(pb.x0, opt, want_fun=False, want_grad=False)
+                if a.dump_outputs and res.iterations >= left:
+                    last.update(x=x, res=res)
+                del x              # no result array is held across the next solve
                 if res.iterations <= 0:
                     raise RuntimeError("solver made no progress")
                 results.append((int(res.iterations), float(res.rmse), float(res.rmse0), float(res.resjac_avg_us),
@@ -313,14 +351,20 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         n_launch1, n_coll1 = be.counters()
+        outputs = None
+        if a.dump_outputs and rank == 0:   # the last timed solve's residual vector and gradient, before `be` runs anything else
+            fun, grad = be.fetch_fun_grad(True, True)
+            res = last["res"]
+            outputs = {"x": last["x"], "fun": fun, "grad": grad, "cost": [res.cost], "rmse": [res.rmse],
+                       "optimality": [res.optimality]}
         # outside the timed region: the same residual+Jacobian kernel compiled WITHOUT the point-block sums (another
         # symbol, so its launches do not mix with the solver's in a rocprofv3 trace of this command), back to back
-        k1_plain_us = be.time_kernel(pb.x0, 7, 50) if world == 1 else None
+        k1_plain_us = be.time_kernel(pb.x0, 7, 50) if world == 1 and a.full else None
         # `value` comes from back-to-back solves of the same x0, which replay the previous solve's per-iteration PCG
         # counts (no spare launch, never a miss).  The other end: the FIRST solve of a fresh handle (no record: one spare
         # PCG launch per iteration, counts guessed from the previous iteration), same problem resident, x0 crossing PCIe
         first_solve = None
-        if world == 1:
+        if world == 1 and a.full:
             fb = sfmba.Backend(local_rank)
             fb.set_precision(a.storage_bits)
             fb.set_problem(*pb.args)
@@ -338,7 +382,7 @@ def main():
         # bitwise the same result in fp64 storage).  NOT the default and not `value`: the judged residual+Jacobian kernel
         # writes its blocks.  Outside the timed region.
         j_free = None
-        if world == 1 and a.shard_of <= 1 and Cl <= 1000:
+        if world == 1 and a.full and a.shard_of <= 1 and Cl <= 1000:
             jb = sfmba.Backend(local_rank)
             jb.set_precision(a.storage_bits)
             jb.debug_option("jfree", 1)
@@ -385,7 +429,7 @@ def main():
             "unit": "iterations/s" if strong else "shard-iterations/s (one workload-sized shard per GPU, summed over GPUs)",
             "n_gpus": world, "steps": steps, "warmup": a.warmup,
             "ms_per_step": 1e3 * elapsed / steps,
-            "settle_s": a.settle,
+            "settle_s": a.settle, "full": a.full,
             "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
             "dtype": "f64" if a.storage_bits == 64 else "f64 arithmetic, f32 storage", "data": "synthetic",
             "transport": None if td is None else (f"direct xGMI all-reduce kernel ({be.p2p_calls()} collectives; "
@@ -432,11 +476,13 @@ def main():
                              "achieved": (kb(Cl, Pl, Nl) - 72 * Pl) / (k1_plain_us * 1e-6) / 1e9,
                              "frac": (kb(Cl, Pl, Nl) - 72 * Pl) / (k1_plain_us * 1e-6) / 1e9 / HBM_PEAK_GBS})},
         }
-        if world == 1 and not a.no_per_call:
+        if world == 1 and a.full and not a.no_per_call:
             line["per_call_ms"] = per_call_times(a.workload, a.storage_bits)
-        if not a.no_cpu_baseline and world == 1:     # the CPU baseline is timed on rank 0 at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:     # the CPU baseline is timed on rank 0 at N = 1 only
             line["cpu_baseline"] = cpu_baseline((C, P, N))
             line["speedup_vs_cpu_baseline"] = (steps / elapsed) / line["cpu_baseline"]["value"]
+        if outputs is not None:
+            dump_outputs(a.dump_outputs, outputs)
         print(json.dumps(line), flush=True)
     if td is not None:
         td.barrier()

@@ -10,11 +10,11 @@ TAG=${1:-r04}
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py 2> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench_line.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -- python3 $R/bench.py --no-cpu-baseline --no-per-call 2> $OUT/${TAG}_stats.err | tail -1 > $OUT/${TAG}_bench_under_rocprof.json
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_pmc_fetch -- python3 $R/bench.py --no-cpu-baseline --no-per-call --steps 10 --warmup 5 --settle 0.1 > $OUT/${TAG}_pmc_fetch.json 2> $OUT/${TAG}_pmc_fetch.err
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/${TAG}_pmc_write -- python3 $R/bench.py --no-cpu-baseline --no-per-call --steps 10 --warmup 5 --settle 0.1 > $OUT/${TAG}_pmc_write.json 2> $OUT/${TAG}_pmc_write.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats_cfg2 -- python3 $R/bench.py --workload cfg2 --no-cpu-baseline --no-per-call 2> $OUT/${TAG}_stats_cfg2.err | tail -1 > $OUT/${TAG}_bench_cfg2.json
+python3 $R/bench.py --full 2> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench_line.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -- python3 $R/bench.py --full --no-cpu-baseline --no-per-call 2> $OUT/${TAG}_stats.err | tail -1 > $OUT/${TAG}_bench_under_rocprof.json
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_pmc_fetch -- python3 $R/bench.py --full --no-cpu-baseline --no-per-call --steps 10 --warmup 5 --settle 0.1 > $OUT/${TAG}_pmc_fetch.json 2> $OUT/${TAG}_pmc_fetch.err
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/${TAG}_pmc_write -- python3 $R/bench.py --full --no-cpu-baseline --no-per-call --steps 10 --warmup 5 --settle 0.1 > $OUT/${TAG}_pmc_write.json 2> $OUT/${TAG}_pmc_write.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats_cfg2 -- python3 $R/bench.py --full --workload cfg2 --no-cpu-baseline --no-per-call 2> $OUT/${TAG}_stats_cfg2.err | tail -1 > $OUT/${TAG}_bench_cfg2.json
 # (SFMBA_HIP_RUNTIME=system: this tool does not import torch, and with the wheel's ROCm 7.0 runtime under the 7.2 tracer the
 # 24 MB copies of the trial point to its host mirror run as blit kernels beside K1 instead of on the SDMA engines -- K1 then
 # reads 750 us in the trace; untraced, and in bench.py with either runtime, they do not)
@@ -26,9 +26,9 @@ for W in cfg4 cfg5; do
   rocprofv3 --pmc TA_BUSY_avr GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_WR --output-format csv -d $OUT/${TAG}_k1c_b_$W -- python3 $R/tools/time_kernels.py $W 0 $B > /dev/null 2>> $OUT/${TAG}_k1c.err
 done
 cd $R
-python3 bench.py --workload cfg3 --no-cpu-baseline --no-per-call 2>> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench_cfg3.json
-python3 bench.py --workload cfg5 --storage-bits 32 --no-cpu-baseline --no-per-call --steps 10 2>> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench_cfg5_f32.json
-python3 bench.py --workload cfg5 --no-cpu-baseline --no-per-call --steps 10 2>> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench_cfg5_f64.json
+python3 bench.py --full --workload cfg3 --no-cpu-baseline --no-per-call 2>> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench_cfg3.json
+python3 bench.py --full --workload cfg5 --storage-bits 32 --no-cpu-baseline --no-per-call --steps 10 2>> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench_cfg5_f32.json
+python3 bench.py --full --workload cfg5 --no-cpu-baseline --no-per-call --steps 10 2>> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench_cfg5_f64.json
 python3 tools/profile_summary.py stats $OUT/${TAG}_stats $OUT/${TAG}_bench_kernel_stats.md > /dev/null
 python3 tools/profile_summary.py stats $OUT/${TAG}_stats_cfg2 $OUT/${TAG}_bench_cfg2_kernel_stats.md > /dev/null
 python3 tools/profile_summary.py stats $OUT/${TAG}_stats_cfg5 $OUT/${TAG}_cfg5_f32_kernel_stats.md > /dev/null

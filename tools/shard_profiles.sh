@@ -14,9 +14,9 @@ cd /tmp && export TMPDIR=/tmp
 for W in cfg4 cfg5; do
   B=64; [ $W = cfg5 ] && B=32
   S=20; [ $W = cfg5 ] && S=10
-  python3 $R/bench.py --workload $W --storage-bits $B --shard-of 8 --steps $S --no-cpu-baseline --no-per-call > $OUT/${TAG}_shard8_${W}_local.json 2>> $OUT/${TAG}_shard.err
-  python3 $R/bench.py --workload $W --storage-bits $B --shard-of 8 --steps $S --no-cpu-baseline --no-per-call --force-exchange > $OUT/${TAG}_shard8_${W}_sharded.json 2>> $OUT/${TAG}_shard.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_shard8_${W} -- python3 $R/bench.py --workload $W --storage-bits $B --shard-of 8 --steps $S --no-cpu-baseline --no-per-call --force-exchange > $OUT/${TAG}_shard8_${W}_sharded_under_rocprof.json 2>> $OUT/${TAG}_shard.err
+  python3 $R/bench.py --full --workload $W --storage-bits $B --shard-of 8 --steps $S --no-cpu-baseline --no-per-call > $OUT/${TAG}_shard8_${W}_local.json 2>> $OUT/${TAG}_shard.err
+  python3 $R/bench.py --full --workload $W --storage-bits $B --shard-of 8 --steps $S --no-cpu-baseline --no-per-call --force-exchange > $OUT/${TAG}_shard8_${W}_sharded.json 2>> $OUT/${TAG}_shard.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_shard8_${W} -- python3 $R/bench.py --full --workload $W --storage-bits $B --shard-of 8 --steps $S --no-cpu-baseline --no-per-call --force-exchange > $OUT/${TAG}_shard8_${W}_sharded_under_rocprof.json 2>> $OUT/${TAG}_shard.err
   python3 $R/tools/profile_summary.py stats $OUT/${TAG}_shard8_${W} $OUT/${TAG}_shard8_${W}_sharded_kernel_stats.md > /dev/null
   rm -rf $OUT/${TAG}_shard8_${W}
   for f in local sharded; do python3 - <<PY
