@@ -485,6 +485,7 @@ def trf_schur(x0, n_cameras, n_points, camera_indices, point_indices, points_2d,
     gh2_prev = None                     # |g_h|^2 of the previous solved iterate (adaptive forcing term)
     step_norm = None
     actual_reduction = None
+    x_norm = None                       # |x| of the iterate the last step was taken from (the xtol test's operand)
     history = []
     info = {}
     while True:                                                                # :450
@@ -493,7 +494,7 @@ def trf_schur(x0, n_cameras, n_points, camera_indices, point_indices, points_2d,
         if g_norm < gtol:
             status = 1
         history.append(dict(iteration=iteration, nfev=nfev, cost=cost, reduction=actual_reduction,
-                            step_norm=step_norm, optimality=g_norm,
+                            step_norm=step_norm, x_norm=x_norm, optimality=g_norm,
                             pcg_iters=info.get("pcg_iters", 0)))
         if verbose:
             print(f"{iteration:6d} {nfev:6d} {cost:16.8e} "

@@ -195,3 +195,69 @@ def test_cfg5_full_size_fp32_storage(cfg5):
             assert abs(np.sum(x64) - ck["sum"]) <= 1e-8 * ck["abs_sum"]
     finally:
         be.close()
+
+
+# ---- the sharded forms at 5000 cameras: rank 0's share of an 8-way sharding, a world of one ---------------------------
+
+def _check_fp32_against_record(be, pb, rec, measured):
+    """fp32 storage against the recorded fp64 oracle run: counts and PCG history equal, cost 1e-8 relative, rmse 1e-8 --
+    the bounds test_cfg5_full_size_fp32_storage states for the same comparison."""
+    opt = be.default_options()
+    opt.ftol = rec["config"]["ftol"]
+    x, res, _, _ = be.solve(pb.x0, opt, want_fun=False, want_grad=False)
+    measured.update(status=int(res.status), nfev=int(res.nfev), njev=int(res.njev), pcg=be.pcg_history(),
+                    cost_rel=abs(res.cost - rec["cost"]) / rec["cost"], rmse_abs=abs(res.rmse - rec["rmse"]))
+    print("measured against the record:", measured)
+    assert (int(res.status), int(res.nfev), int(res.njev)) == (rec["status"], rec["nfev"], rec["njev"])
+    assert be.pcg_history() == rec["pcg_iterations"] and int(res.pcg_iterations) == sum(rec["pcg_iterations"])
+    assert abs(res.cost - rec["cost"]) <= 1e-8 * rec["cost"] and abs(res.rmse - rec["rmse"]) <= 1e-8
+    return x, res
+
+
+def test_cfg5_shard_of_8_sharded_forms_world_of_one_vs_recorded_oracle_and_blocks(cfg5):
+    """Rank 0's share of an 8-way sharding of cfg5 (5000 / 125089 / 1250002: what one of eight GPUs holds) on a handle
+    sharded with a world of one (test_gpu_fullsize.sharded_world_of_one).  At 5000 cameras the sharded iteration takes
+    forms no small test reaches together: pass A's table in global memory, the PCG update a kernel of its own, with
+    fp32 storage the mixed-precision product, and the per-camera exchange inside K3 / the right-hand-side pass / pass B.
+    Held to the oracle's recorded fp64 run of the SAME shard (oracle_cfg5_shard8.json, ``tools/gen_golden.py --shard
+    cfg5 8``; tests/test_oracle_golden.py asserts that none of its decisions is near a tie), each with the in-kernel
+    exchange and with the collectives as launches of their own (pcg_inline = 0):
+    * fp32 storage, mixed product as shipped: counts and PCG history equal, cost 1e-8 relative, rmse 1e-8;
+    * fp64 storage: the same and the checksums, cost 1e-9.
+    The same shard on a plain handle: counts and history equal, cost within 1e-9 (fp64; fp32 storage against fp32
+    storage: the 1e-8 of that mode).  The exchanged quantities at x0 against the oracle's blocks of the shard:
+    [U | g_c], V, g_p (recomputed in fp64 in both storage modes) 1e-11 / 1e-10, S v 1e-9 in fp64 and behind
+    pcg_mixed = 0, the mixed product inside (1e-12, 1e-6) and symmetric to 1e-6.
+    Sharded against plain: the in-kernel form equals the plain handle's solve to the BIT in both storage modes (asserted);
+    the form with the collectives as launches orders the four per-camera PCG scalar sums differently (pcg_tail_camera:
+    one thread, index order; pass B's tail: a wave reduction) -- cost 3.3e-16 (fp64) / 6.6e-16 (fp32) apart, x 4.8e-12 /
+    1.3e-6 (fp32-stored blocks in the step).
+    Measured on an MI355X: fp32 storage cost 1.2e-15 (bound 1e-8), rmse 2.2e-16 (1e-8); fp64 storage cost0 2.1e-16 (1e-12),
+    cost 1.2e-15 (1e-9), rmse 2.2e-16 (1e-9), checksums 0 (1e-8); 181 vs 220 launches per solve in both modes; U 1.3e-15,
+    V 3.9e-16 (1e-11), g_c 1.9e-15, g_p 5.6e-15 (1e-10); S v 1.8e-15 in fp64 and behind pcg_mixed = 0 (1e-9), symmetric
+    to 0 (1e-10); the mixed product 1.1e-7 (inside 1e-12 ... 1e-6), symmetric to 4.1e-9 (1e-6).
+    Wall time: 2 s of the 25 s the sharded-form tests add to ``pytest -m gpu`` (test_gpu_fullsize.py has the account)."""
+    from oracle import ba_oracle as orc
+    from test_gpu_fullsize import (exchanged_quantities_against_oracle, plain_solve, rank0_shard,
+                                   sharded_solves_against_record, sharded_world_of_one)
+    with open(os.path.join(GOLDEN, "oracle_cfg5_shard8.json")) as f:
+        rec = json.load(f)
+    pb = rank0_shard(cfg5, 8)
+    assert (pb.n_cameras, pb.n_points, pb.n_obs) == (rec["config"]["n_cameras"], rec["shard"]["n_points"], rec["shard"]["n_obs"])
+    for bits, check, tol in ((32, _check_fp32_against_record, 1e-8), (64, None, 1e-9)):
+        runs = sharded_solves_against_record(pb, rec, bits=bits, check=check)
+        xp, rp, hp = plain_solve(pb, rec, bits=bits)
+        for form, (x, res) in runs.items():
+            same = np.array_equal(x, xp) and res.cost == rp.cost
+            print(f"fp{bits} {form} vs plain handle: cost differs by {abs(res.cost - rp.cost) / rp.cost:.3e}, x by {np.abs(x - xp).max():.3e}, "
+                  f"bitwise equal: {same}")
+            assert (int(res.status), int(res.nfev), int(res.njev)) == (int(rp.status), int(rp.nfev), int(rp.njev))
+            assert hp == rec["pcg_iterations"]
+            assert abs(res.cost - rp.cost) <= tol * rp.cost
+            assert same or form != "inline"              # the in-kernel form IS the plain handle's, to the bit
+    r_o, Jc_o, Jp_o = orc.jacobian_blocks(pb.x0, *pb.args)
+    nb = orc.normal_blocks(r_o, Jc_o, Jp_o, pb.n_cameras, pb.n_points, pb.camera_indices, pb.point_indices)
+    del r_o, Jc_o, Jp_o
+    for bits, debug, mixed in ((64, (), False), (32, (), True), (32, (("pcg_mixed", 0),), False)):
+        with sharded_world_of_one(pb, bits=bits, debug=debug) as handle:
+            exchanged_quantities_against_oracle(handle, pb, nb, mixed=mixed)

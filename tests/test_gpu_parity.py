@@ -815,7 +815,7 @@ def test_exchange_path_world1_nccl(dbg):
 
 # ---- a REAL two-rank run of the C++ solver: both ranks share the one GPU, collectives over gloo ------------
 
-def _two_rank_worker(rank, world, port, q, direct=False, dims=(11, 3000, 10000, 0, 0.01), debug=()):
+def _two_rank_worker(rank, world, port, q, direct=False, dims=(11, 3000, 10000, 0, 0.01), debug=(), blocks=False):
     import torch
     import torch.distributed as td
     import sfmba
@@ -825,7 +825,7 @@ def _two_rank_worker(rank, world, port, q, direct=False, dims=(11, 3000, 10000, 
     torch.cuda.set_device(0)
     td.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        _two_rank_body(rank, world, q, direct, dims, debug, torch, td, sfmba, sdist)
+        _two_rank_body(rank, world, q, direct, dims, debug, torch, td, sfmba, sdist, blocks)
     except Exception as e:                                       # noqa: BLE001 -- the parent fails at once, with the text
         q.put(dict(error=f"rank {rank}: {type(e).__name__}: {e}"))
         raise
@@ -833,7 +833,15 @@ def _two_rank_worker(rank, world, port, q, direct=False, dims=(11, 3000, 10000, 
         td.destroy_process_group()
 
 
-def _two_rank_body(rank, world, q, direct, dims, debug, torch, td, sfmba, sdist):
+def _exchange_operands(n_cameras, n_points):
+    """The seeded operands of the kernel-level step of _two_rank_body: dc and v (the same on every rank) and the
+    full-length dp every rank cuts its own point range from -- the magnitudes of a damped solve of these problems
+    (about a thousandth of the diagonals of U, 1e9 ... 1e5, and of V, 1e6 ... 1e4)."""
+    rng = np.random.default_rng(4242)
+    return rng.uniform(1e5, 1e6, 6 * n_cameras), rng.uniform(1e2, 1e3, 3 * n_points), rng.normal(size=6 * n_cameras)
+
+
+def _two_rank_body(rank, world, q, direct, dims, debug, torch, td, sfmba, sdist, blocks=False):
     pb = sfmba.make_problem(dims[0], dims[1], dims[2], seed=dims[3], x0_noise=dims[4])
     shards = sdist.partition_points(pb.point_indices, pb.n_points, world)
     loc = sdist.shard_problem(pb, shards[rank])
@@ -854,6 +862,26 @@ def _two_rank_body(rank, world, q, direct, dims, debug, torch, td, sfmba, sdist)
         launches = be.counters()[0] - n0
         torch.cuda.synchronize()
         x2 = be.solve(loc.x0, opt)[0] if direct else x                    # staging buffers are reusable
+        n_coll = be.counters()[1]
+        hist = be.pcg_history()
+        extra = {}
+        if blocks:
+            # the exchanged quantities themselves, entry by entry: [U | g_c] (K3, with the in-kernel exchange where the
+            # solves had it) and S v (every rank's pass B over its own observations + the 6 C collective) at the start.
+            # K3 and the rhs pass own ONE slot set and rely on a grid-wide collective between two launches of either:
+            # outside a solve the barrier restores that separation
+            dc, dp, v = _exchange_operands(pb.n_cameras, pb.n_points)
+            s = shards[rank]
+            td.barrier()
+            U, _, gc, _ = be.normal_blocks(loc.x0)
+            td.barrier()
+            y = be.schur_matvec(loc.x0, dc, dp[3 * s.point_begin:3 * s.point_end], v)
+            torch.cuda.synchronize()
+            mine = (U, gc, y)
+            everyone = [None] * world
+            td.all_gather_object(everyone, mine)
+            extra = dict(U=U, gc=gc, y=y,
+                         blocks_equal=all(all(np.array_equal(a, b) for a, b in zip(e, mine)) for e in everyone))
     td.barrier()
     direct_calls = be.p2p_calls()
     if link is not None:
@@ -868,11 +896,12 @@ def _two_rank_body(rank, world, q, direct, dims, debug, torch, td, sfmba, sdist)
                    cams_equal=all(np.array_equal(xi[:6 * dims[0]], xs[0][:6 * dims[0]]) for xi in xs),
                    status=int(res.status), nfev=int(res.nfev), cost=float(res.cost), rmse=float(res.rmse),
                    calls=ex.n_calls, direct_calls=direct_calls, link_active=link_active, launches=int(launches),
-                   again=float(np.abs(x2 - x).max())))
+                   again=float(np.abs(x2 - x).max()), njev=int(res.njev), cost0=float(res.cost0), pcg_history=hist,
+                   collectives=int(n_coll), **extra))
     be.close()
 
 
-def _run_ranks(world, direct, dims=(11, 3000, 10000, 0, 0.01), debug=()):
+def _run_ranks(world, direct, dims=(11, 3000, 10000, 0, 0.01), debug=(), blocks=False):
     import socket
     import torch.multiprocessing as mp
     with socket.socket() as s:
@@ -880,7 +909,7 @@ def _run_ranks(world, direct, dims=(11, 3000, 10000, 0, 0.01), debug=()):
         port = s.getsockname()[1]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_two_rank_worker, args=(r, world, port, q, direct, dims, debug)) for r in range(world)]
+    procs = [ctx.Process(target=_two_rank_worker, args=(r, world, port, q, direct, dims, debug, blocks)) for r in range(world)]
     for p in procs:
         p.start()
     out = q.get(timeout=300)
@@ -951,6 +980,85 @@ def test_direct_allreduce_over_peer_mapped_memory(dbg):
     out = _run_ranks(2, direct=True, dims=(100, 1500, 12000, 4, 0.01), debug=(("cam_chunk", 16, 1),))
     assert out["link_active"] and out["calls"] == 0 and out["cams_equal"] and out["again"] == 0.0
     assert out["nfev"] == ref.nfev and abs(out["cost"] - ref.cost) <= 1e-9 * ref.cost
+
+
+def test_exchanged_quantities_on_real_ranks_against_the_oracle(orc):
+    """What the ranks exchange, compared ENTRY BY ENTRY with an independent reference instead of through a solve's cost:
+    after their solves, 2 and 3 processes that share the GPU each call normal_blocks (K3: [U | g_c] summed over the
+    ranks -- inside the kernel by cam_exchange_value at 100 and 60 cameras, by a collective launch at 300) and
+    schur_matvec (pass B over the rank's own observations + the 6 C collective) on their shards.  U, g_c and S v must be
+    the same on every rank to the bit, and equal the oracle's blocks of the FULL problem (1e-11 / 1e-10, the bounds of
+    every blocks test here) and the explicit U v + dc v - W (V + diag dp)^-1 W^T v of the full problem (1e-9).  A
+    rank-order or slot-offset error in the exchange, or a peer's value entering the sum twice, fails here directly;
+    the world-of-one tests (tests/test_gpu_fullsize.py) cannot see it: they have no peer.
+    Measured on an MI355X (worst of the three): U 7.8e-16 (bound 1e-11), g_c 1.1e-15 (1e-10), S v 1.2e-15 (1e-9); equal on
+    all ranks to the bit.  With rank 1's value entering cam_exchange_value's sum twice (checked by hand on a scratch copy):
+    U 0.53, g_c 0.53 at 100 cameras -- red -- while the world-of-one tests stay green."""
+    import sfmba
+    from test_gpu_fullsize import explicit_schur_product
+    for world, dims in ((2, (100, 1500, 12000, 4, 0.01)), (3, (60, 900, 8000, 6, 0.01)), (2, (300, 2000, 16000, 9, 0.01))):
+        pb = sfmba.make_problem(dims[0], dims[1], dims[2], seed=dims[3], x0_noise=dims[4])
+        r_o, Jc_o, Jp_o = orc.jacobian_blocks(pb.x0, *pb.args)
+        nb = orc.normal_blocks(r_o, Jc_o, Jp_o, pb.n_cameras, pb.n_points, pb.camera_indices, pb.point_indices)
+        dc, dp, v = _exchange_operands(pb.n_cameras, pb.n_points)
+        ref = explicit_schur_product(nb, pb.args, dc, dp, v)
+        out = _run_ranks(world, direct=True, dims=dims, blocks=True)
+        assert out["link_active"] and out["calls"] == 0 and out["cams_equal"] and out["again"] == 0.0
+        err = dict(U=_rel(out["U"], _upper(nb.U)), gc=_rel(out["gc"], nb.gc), y=_rel(out["y"], ref))
+        print(f"{world} ranks, {dims[0]} cameras: {err}, equal on all ranks: {out['blocks_equal']}")
+        assert out["blocks_equal"], "U, g_c or S v differ between the ranks"
+        assert err["U"] < 1e-11 and err["gc"] < 1e-10 and err["y"] < 1e-9, err
+
+
+def test_two_process_cfg4_on_one_device_equals_the_recorded_oracle_run():
+    """cfg4 (1000 / 100k / 1M) cut in two, one process per half on the one GPU, collectives over the direct link:
+    (ranks - 1) x cameras = 1000 > 128, so ranks that share a device take the collective LAUNCHES.
+    Held to the oracle's recorded run of the whole problem: nfev, njev and the PCG iterations of every outer iteration
+    equal, cost0 1e-12, cost 1e-9, rmse 1e-9, the merged parameters' checksums 1e-8 abs_sum; the status equal or both in
+    {2, 3, 4} (which of ftol and xtol the last, 13th-digit step satisfies is rounding noise between sum orders).
+    Measured on an MI355X: status 2 as recorded, cost0 1.3e-16 (bound 1e-12), cost 6.1e-16 (1e-9), rmse 3.3e-16 (1e-9),
+    checksums 0 and 4.8e-19 (1e-8); 174 launches and 113 collectives per solve."""
+    rec = json.load(open(os.path.join(GOLDEN, "oracle_cfg4.json")))
+    cfg = rec["config"]
+    out = _run_ranks(2, direct=True, dims=(cfg["n_cameras"], cfg["n_points"], cfg["n_obs"], cfg["seed"], 0.01))
+    ck = rec["x_checksum"]
+    C = cfg["n_cameras"]
+    print("2-process cfg4:", dict(status=out["status"], nfev=out["nfev"], njev=out["njev"], pcg=out["pcg_history"],
+                                  cost0_rel=abs(out["cost0"] - rec["cost0"]) / rec["cost0"], cost_rel=abs(out["cost"] - rec["cost"]) / rec["cost"],
+                                  rmse_abs=abs(out["rmse"] - rec["rmse"]), sum_rel=abs(np.sum(out["x"]) - ck["sum"]) / ck["abs_sum"],
+                                  cams_sum_rel=abs(np.sum(out["x"][:6 * C]) - ck["cams_sum"]) / ck["abs_sum"],
+                                  direct_calls=out["direct_calls"], collectives=out["collectives"], launches=out["launches"]))
+    assert out["link_active"], "peers could not be mapped or the self-test failed"
+    assert out["calls"] == 0 and out["direct_calls"] > 0 and out["collectives"] > 0
+    assert out["cams_equal"] and out["again"] == 0.0
+    assert (out["nfev"], out["njev"]) == (rec["nfev"], rec["njev"]) and out["pcg_history"] == rec["pcg_iterations"]
+    assert out["status"] == rec["status"] or {out["status"], rec["status"]} <= {2, 3, 4}
+    assert abs(out["cost0"] - rec["cost0"]) <= 1e-12 * rec["cost0"]
+    assert abs(out["cost"] - rec["cost"]) <= 1e-9 * rec["cost"] and abs(out["rmse"] - rec["rmse"]) <= 1e-9
+    assert abs(np.sum(out["x"]) - ck["sum"]) <= 1e-8 * ck["abs_sum"]
+    assert abs(np.sum(out["x"][:6 * C]) - ck["cams_sum"]) <= 1e-8 * ck["abs_sum"]
+
+
+def test_shared_device_rule_switches_between_128_and_129_cameras():
+    """kSharedDeviceCams: two ranks that share one GPU exchange inside the producing kernels while (ranks - 1) x cameras
+    <= 128 -- the waiting workgroups of the other rank then leave half of the 256 CUs alone -- and keep the collective
+    launches above.  At 128 cameras the default run must need FEWER launches than the run with pcg_inline = 0, at 129
+    it must not; both give the single-process solve (nfev equal, cost 1e-9).
+    Measured on an MI355X: 128 cameras 163 launches against 224, 129 cameras 246 against 246."""
+    import sfmba
+    for cams in (128, 129):
+        dims = (cams, 1800, 15000, 11, 0.01)
+        pb = sfmba.make_problem(dims[0], dims[1], dims[2], seed=dims[3], x0_noise=dims[4])
+        ref = sfmba.least_squares(sfmba.compute_residuals, pb.x0, x_scale="jac", ftol=1e-10, method="trf", args=pb.args)
+        out = _run_ranks(2, direct=True, dims=dims)
+        assert out["link_active"] and out["calls"] == 0 and out["cams_equal"] and out["again"] == 0.0
+        assert out["nfev"] == ref.nfev and (out["status"] == ref.status or {out["status"], ref.status} <= {2, 3, 4})
+        assert abs(out["cost"] - ref.cost) <= 1e-9 * ref.cost
+        off = _run_ranks(2, direct=True, dims=dims, debug=(("pcg_inline", 0),))
+        print(f"{cams} cameras: {out['launches']} launches, {off['launches']} with pcg_inline = 0")
+        assert off["link_active"] and off["calls"] == 0
+        assert off["nfev"] == out["nfev"] and abs(off["cost"] - out["cost"]) <= 1e-9 * out["cost"]
+        assert (out["launches"] < off["launches"]) == (cams == 128), (cams, out["launches"], off["launches"])
 
 
 def test_two_rank_solve_on_one_gpu_gloo(dbg):

@@ -300,3 +300,48 @@ def test_held_cameras_oracle_against_scipys_capture():
         assert o.status in (2, 3, 4) and o.cost <= float(g[pre + "summary"][3]) * (1 + 1e-9)
         free = orc.trf_schur(x0, *pb.args, ftol=1e-10, linear="dense")
         assert free.cost <= o.cost * (1 + 1e-9)                  # holding cameras can only cost
+
+
+def test_recorded_shard_runs_decide_nothing_near_a_tie():
+    """tests/golden/oracle_cfg4_shard8.json / oracle_cfg5_shard8.json (tools/gen_golden.py --shard NAME 8): the oracle's run
+    of rank 0's share of an 8-way sharding, which the GPU tests hold the sharded solver forms to COUNT FOR COUNT.  That is
+    only fair where none of the oracle's own stop / continue decisions is near a tie: every recorded ratio
+    actual_reduction / (ftol cost) and step_norm / (xtol (xtol + |x|)) -- the operands of the oracle's termination test,
+    which stops below 1 -- lies outside [0.5, 2] (nearest: ftol 2.35 / 0.35, xtol 9.7 / 0.10), and the decisions they
+    imply are the recorded status and iteration count.  From the files alone."""
+    want = {"cfg4": (1000, 12518, 125000, 4, 7, [1, 2, 5, 6, 6, 6]), "cfg5": (5000, 125089, 1250002, 2, 6, [1, 2, 5, 6, 6])}
+    for name, (C, P, N, status, nfev, pcg) in want.items():
+        with open(os.path.join(GOLDEN, f"oracle_{name}_shard8.json")) as f:
+            rec = json.load(f)
+        whole = json.load(open(os.path.join(GOLDEN, f"oracle_{name}.json")))
+        assert set(whole) <= set(rec) and rec["config"] == whole["config"] and rec["oracle_settings"] == whole["oracle_settings"]
+        assert rec["shard"] == dict(rank=0, world=8, n_points=P, n_obs=N) and rec["config"]["n_cameras"] == C
+        assert (rec["status"], rec["nfev"], rec["njev"], rec["pcg_iterations"]) == (status, nfev, nfev, pcg)
+        fr, xr = rec["ftol_ratio_per_iteration"], rec["xtol_ratio_per_iteration"]
+        assert len(fr) == len(xr) == len(pcg) == len(rec["cost_per_iteration"]) - 1
+        for r in fr + xr:
+            assert np.isfinite(r) and r >= 0 and not (0.5 <= r <= 2.0), (name, r)
+        assert all(f > 2.0 and x > 2.0 for f, x in zip(fr[:-1], xr[:-1]))          # every step but the last: continue
+        assert {(True, True): 4, (True, False): 2, (False, True): 3}[(fr[-1] < 0.5, xr[-1] < 0.5)] == status
+        # the ftol ratio again from the recorded costs (every step of these runs was accepted: nfev == njev)
+        cost = rec["cost_per_iteration"]
+        assert cost[0] == rec["cost0"] and cost[-1] == rec["cost"]
+        for k in range(len(fr) - 2):             # (the last steps' reductions are below the costs' last digits)
+            assert abs((cost[k] - cost[k + 1]) / (rec["config"]["ftol"] * cost[k]) - fr[k]) <= 1e-6 * fr[k]
+
+
+def test_oracle_history_carries_the_operands_of_its_termination_test():
+    """history[k] of trf_schur: `reduction`, `step_norm` and `x_norm` of the step INTO iterate k, cost of iterate k --
+    what tools/gen_golden.py --shard turns into the recorded ratios.  x_norm is |x| of the iterate the step was taken
+    from; the ratios of the last step reproduce the status."""
+    pb = make_problem(6, 60, 400, seed=12)
+    o = orc.trf_schur(pb.x0, *pb.args, ftol=1e-10, linear="pcg", pcg_tol=1e-2, pcg_tol_max=0.1, precond="schur")
+    h = o.history
+    assert h[0]["x_norm"] is None and h[0]["reduction"] is None
+    assert abs(h[1]["x_norm"] - np.linalg.norm(pb.x0)) <= 1e-14 * np.linalg.norm(pb.x0)
+    assert all(h[k]["x_norm"] > 0 for k in range(1, len(h)))
+    f_ok = h[-1]["reduction"] < 1e-10 * h[-2]["cost"]
+    x_ok = h[-1]["step_norm"] < 1e-8 * (1e-8 + h[-1]["x_norm"])
+    assert o.status == (4 if f_ok and x_ok else 2 if f_ok else 3 if x_ok else None)
+    for k in range(1, len(h) - 1):
+        assert not (h[k]["reduction"] < 1e-10 * h[k - 1]["cost"]) and not (h[k]["step_norm"] < 1e-8 * (1e-8 + h[k]["x_norm"]))

@@ -11,6 +11,8 @@ of /root/reference/sfm_lite/sfm.py:266-268).  No reference source is written any
     python tools/gen_golden.py --cfg2     # also the ~7 min scipy run on the SceauxCastle-scale synthetic
     python tools/gen_golden.py --full cfg4   # oracle.trf_schur with the shipped settings at BASELINE's full size
     python tools/gen_golden.py --full cfg5   #   (cfg4: ~1 min, cfg5: ~15 min and ~25 GB; build container only)
+    python tools/gen_golden.py --shard cfg4 8   # the same for rank 0's share of an 8-way sharding (cfg4: seconds,
+    python tools/gen_golden.py --shard cfg5 8   #   cfg5: under a minute)
     python tools/gen_golden.py --growing  # scipy + the reference residual on a 2 -> 11 camera growing reconstruction
     python tools/gen_golden.py --fixed    # scipy + the reference's pattern with fixed_camera_indices (seconds)
     python tools/gen_golden.py --params   # gauge-aligned parameter distance oracle <-> scipy on every stored scipy x
@@ -240,9 +242,18 @@ def oracle_full(name):
     What the GPU tests compare at sizes the oracle cannot be run at inside the suite: status, nfev, njev, cost,
     RMSE and the PCG iterations of every outer iteration."""
     sys.path.insert(0, ROOT)
-    from oracle import ba_oracle as orc
-    from sfmba.synthetic import CONFIGS, make_config
+    from sfmba.synthetic import make_config
     pb = make_config(name)
+    rec, o, dt = _oracle_record(pb, name)
+    with open(os.path.join(OUT, f"oracle_{name}.json"), "w") as f:
+        json.dump(rec, f, indent=1)
+    print(f"  oracle {name}: status {o.status} nfev {o.nfev} cost {o.cost!r} pcg {rec['pcg_iterations']} in {dt:.0f}s")
+
+
+def _oracle_record(pb, name):
+    """oracle.trf_schur on `pb` with the shipped settings -> (the record oracle_<name>.json holds, result, seconds)."""
+    from oracle import ba_oracle as orc
+    from sfmba.synthetic import CONFIGS
     t = time.time()
     o = orc.trf_schur(pb.x0, *pb.args, ftol=1e-10, linear="pcg", pcg_tol=1e-2, pcg_tol_max=0.1, precond="schur",
                       verbose=1)
@@ -258,9 +269,34 @@ def oracle_full(name):
                cost_per_iteration=[float(h["cost"]) for h in o.history],
                x_checksum=dict(sum=float(np.sum(o.x)), abs_sum=float(np.sum(np.abs(o.x))),
                                cams_sum=float(np.sum(o.x[:6 * pb.n_cameras]))))
-    with open(os.path.join(OUT, f"oracle_{name}.json"), "w") as f:
+    return rec, o, dt
+
+
+def oracle_shard(name, world):
+    """The same recorded run for RANK 0'S SHARE of a `world`-way observation sharding of a BASELINE.json configuration
+    (sfmba.dist.partition_points / shard_problem: all cameras, the rank's own points and observations, solved as a
+    problem of its own) -- what a handle that runs the sharded forms with a world of one must reproduce.  On top of
+    oracle_full's fields: the shard's own sizes, and per outer iteration the two ratios the oracle's termination test
+    compares with 1 (ba_oracle.trf_schur, check_termination): actual_reduction / (ftol * cost before the step) and
+    step_norm / (xtol * (xtol + |x|)).  A count-for-count comparison with another implementation is only fair where
+    none of them is near 1; tests/test_oracle_golden.py asserts that from the file."""
+    sys.path.insert(0, ROOT)
+    from sfmba.dist import partition_points, shard_problem
+    from sfmba.synthetic import make_config
+    pb = make_config(name)
+    pb = shard_problem(pb, partition_points(pb.point_indices, pb.n_points, world)[0])
+    rec, o, dt = _oracle_record(pb, name)
+    ftol, xtol = rec["config"]["ftol"], 1e-8                       # (xtol: trf_schur's default, as in oracle_full)
+    h = o.history
+    rec["shard"] = dict(rank=0, world=world, n_points=int(pb.n_points), n_obs=int(pb.n_obs))
+    rec["xtol"] = xtol
+    rec["ftol_ratio_per_iteration"] = [float(h[k]["reduction"] / (ftol * h[k - 1]["cost"])) for k in range(1, len(h))]
+    rec["xtol_ratio_per_iteration"] = [float(h[k]["step_norm"] / (xtol * (xtol + h[k]["x_norm"]))) for k in range(1, len(h))]
+    with open(os.path.join(OUT, f"oracle_{name}_shard{world}.json"), "w") as f:
         json.dump(rec, f, indent=1)
-    print(f"  oracle {name}: status {o.status} nfev {o.nfev} cost {o.cost!r} pcg {rec['pcg_iterations']} in {dt:.0f}s")
+    print(f"  oracle {name} shard 0 of {world} ({pb.n_cameras} / {pb.n_points} / {pb.n_obs}): status {o.status} nfev {o.nfev} "
+          f"cost {o.cost!r} pcg {rec['pcg_iterations']} in {dt:.0f}s\n    ftol ratios {rec['ftol_ratio_per_iteration']}\n"
+          f"    xtol ratios {rec['xtol_ratio_per_iteration']}")
 
 
 def lsq_growing(ba):
@@ -456,6 +492,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg2", action="store_true")
     ap.add_argument("--full", choices=("cfg3", "cfg4", "cfg5"))
+    ap.add_argument("--shard", nargs=2, metavar=("NAME", "G"), help="oracle run of rank 0's share of a G-way sharding")
     ap.add_argument("--growing", action="store_true")
     ap.add_argument("--fixed", action="store_true")
     ap.add_argument("--params", action="store_true")
@@ -463,6 +500,12 @@ def main():
     if a.full:                                   # oracle only: needs no reference
         os.makedirs(OUT, exist_ok=True)
         oracle_full(a.full)
+        return
+    if a.shard:
+        if a.shard[0] not in ("cfg3", "cfg4", "cfg5"):
+            ap.error("--shard NAME: one of cfg3, cfg4, cfg5")
+        os.makedirs(OUT, exist_ok=True)
+        oracle_shard(a.shard[0], int(a.shard[1]))
         return
     if a.growing:
         lsq_growing(load_ref())
