@@ -254,6 +254,17 @@ int  sfmba_tr2d_solve(const double* B3, const double* g2, double Delta, double* 
  *   "rhsrec"         P  1 / 0: the rhs + preconditioner pass gathers dedicated 128-byte point records whatever the size
  *   "cost_rider"        0: the trial cost is summed and posted by a k_finish launch of its own instead of riding with
  *                       the normal-block launch
+ *   "spec_scale"        0: k_update_scale (column scale, gradient, D^2 g and the partial sums of an accepted point) is
+ *                       launched after the host has accepted the trial point (default on one rank: enqueued behind the
+ *                       trial point's normal blocks before the verdict, into a second set of the three vectors which
+ *                       is swapped in on acceptance; with several ranks always the 0 form)
+ *   "start_handoff"     0: a solve starts with a blocking read-back of the cost and the scale sums, the camera table
+ *                       and the point records as two launches (default on one rank: the cost is posted by the
+ *                       normal-block launch and picked up behind the first k_jdot, the first radius is derived on the
+ *                       device by k_prep / k_tr_step and read at the first hand-off; needs "cost_rider")
+ *   "early_download"    0: the result is copied to the host behind the last launch of the solve (default: when a
+ *                       solve ends on an accepted step, x leaves on the copy stream as soon as the host has accepted
+ *                       it, beside the last kernels)
  *   "pcg_mixed"      P  1 / 0: fp32 operands with fp64 accumulation in the implicit Schur product (default: with fp32
  *                       storage, sfmba_set_precision); "pcg_mixed_b" 0: pass B keeps its fp64 point records
  *   "pcg_inline"        0: sharded solves over the direct link keep the all-reduces of the per-camera sums as launches

@@ -334,6 +334,14 @@ __global__ void k_cam_table(const double* __restrict__ xc, int C, double* __rest
     cam_table_row(prm, tab, C, c);
 }
 
+// Delta < 0 stands for "first iteration of a solve": the radius is |x0 * scale_inv| (SCIPY trf.py:428), 1 when that is
+// zero, from q2 of the point slice (slot 9) + q2 of the camera slice, in the host's operand order
+__device__ __forceinline__ double start_radius(const double* __restrict__ sc, double Delta) {
+    if (Delta >= 0.0) return Delta;
+    const double d = sqrt(sc[9] + sc[16 + 2]);
+    return d == 0.0 ? 1.0 : d;
+}
+
 // The first trust-region step of an outer iteration, decided on the device so that the host does not
 // have to read the model's scalars back before the trial point can be evaluated: one thread builds
 // the 2-D model from the (rank-reduced) exchange scalars and solves it for the radius the host passed.
@@ -352,6 +360,7 @@ __global__ void k_tr_step(double* __restrict__ sc, double Delta, const PcgCtrl* 
     if (ctrl != nullptr && ctrl->done == 0) { sc[30] = 1.0; return; }
     auto q = [&](int point_slot, int k) { return sc[point_slot] + sc[16 + k]; };   // points (reduced) + cameras
     const TrModel m = tr_build_model(sc[1], sc[2], sc[3], q(8, 1), q(4, 5), q(5, 6), q(11, 4), q(6, 7), q(7, 8));
+    Delta = start_radius(sc, Delta);     // (the host takes the radius of a solve's first iteration from slot 31)
     const TrStep st = tr_solve_step(m, Delta);
     sc[25] = st.c1; sc[26] = st.c2; sc[27] = st.predicted; sc[28] = st.step_h_norm; sc[29] = st.step_norm;
     sc[30] = 0.0; sc[31] = Delta;
@@ -402,6 +411,25 @@ __global__ void k_fill_rec(const double* __restrict__ pts, int P, double* __rest
     if (q >= 3 * P) return;
     const int p = q / 3;
     rec[(size_t)kRec * p + (q - 3 * p)] = pts[q];
+}
+
+// k_cam_table and k_fill_rec of a freshly uploaded parameter vector as ONE launch: blocks [0, bc) take one camera per
+// thread, the remaining blocks the point coordinates (the split of k_step_table)
+__global__ __launch_bounds__(256) void k_cam_table_rec(const double* __restrict__ x, int C, int P, int bc,
+                                                       double* __restrict__ tab, double* __restrict__ rec) {
+    if ((int)blockIdx.x < bc) {
+        const int c = blockIdx.x * blockDim.x + threadIdx.x;
+        if (c >= C) return;
+        double prm[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) prm[k] = x[6 * (size_t)c + k];
+        cam_table_row(prm, tab, C, c);
+        return;
+    }
+    const int q = ((int)blockIdx.x - bc) * blockDim.x + threadIdx.x;
+    if (q >= 3 * P) return;
+    const int p = q / 3;
+    rec[(size_t)kRec * p + (q - 3 * p)] = x[6 * (size_t)C + q];
 }
 
 // One observation: residual and (JAC) the 2x6 / 2x3 blocks.
@@ -1237,7 +1265,8 @@ __device__ __forceinline__ void write_partials(double (&q)[kNQ], double* __restr
 }
 
 // Column scale of x_scale='jac' (SCIPY common.py:598-610): si = |J col|_2 = sqrt(diag(J^T J)),
-// zeros -> 1 on the first call, running max afterwards; g = J^T f gathered from the blocks;
+// zeros -> 1 on the first call, running max afterwards (read from `si_old`, written to `si`: the same array, or the
+// other buffer set when the launch speculates on the acceptance of a trial point); g = J^T f gathered from the blocks;
 // sg = g / si^2 (= D^2 g); and, in the same pass, the partial sums q0..q4 of the new iterate.
 // Blocks [0, bc): the camera slice, one element per thread and trip.  Blocks [bc, grid): the point slice, one POINT per
 // thread and trip with every load of the trip issued before the first use -- V, g_p and x were written by other XCDs a
@@ -1248,9 +1277,10 @@ __global__ __launch_bounds__(256) void k_update_scale(const double* __restrict__
                                                       const double* __restrict__ V,
                                                       const double* __restrict__ gp,
                                                       const double* __restrict__ x, int C, int P,
-                                                      int first, int bc, double* __restrict__ si,
+                                                      int first, int bc, const double* si_old, double* si,
                                                       double* __restrict__ g, double* __restrict__ sg,
-                                                      double* __restrict__ part) {
+                                                      double* __restrict__ part, const double* __restrict__ skip) {
+    if (skip != nullptr && *skip != 0.0) return;   // speculative launch cancelled by k_tr_step (K3 wrote no blocks)
     const int n6 = 6 * C;
     double q[kNQ];
 #pragma unroll
@@ -1271,13 +1301,14 @@ __global__ __launch_bounds__(256) void k_update_scale(const double* __restrict__
             const int c = e / 6, k = e - 6 * c;
             const double d = Ugc[(size_t)c * 27 + diagU[k]], ge = Ugc[(size_t)c * 27 + 21 + k];
             double s, sge;
-            element(d, ge, first ? 0.0 : si[e], x[e], s, sge);
+            element(d, ge, first ? 0.0 : si_old[e], x[e], s, sge);
             si[e] = s; g[e] = ge; sg[e] = sge;
         }
     } else {
         const int nb = (int)gridDim.x - bc, b = (int)blockIdx.x - bc;
         const double* __restrict__ xp = x + n6;
-        double* __restrict__ sip = si + n6;
+        const double* sio = si_old + n6;
+        double* sip = si + n6;
         double* __restrict__ gpo = g + n6;
         double* __restrict__ sgp = sg + n6;
         for (int p0 = (b * kScalePts) * (int)blockDim.x + (int)threadIdx.x; p0 < P; p0 += nb * kScalePts * (int)blockDim.x) {
@@ -1291,7 +1322,7 @@ __global__ __launch_bounds__(256) void k_update_scale(const double* __restrict__
                 for (int k = 0; k < 3; ++k) {
                     ge[u][k] = gp[pp * 3 + k];
                     xe[u][k] = xp[pp * 3 + k];
-                    so[u][k] = first ? 0.0 : sip[pp * 3 + k];
+                    so[u][k] = first ? 0.0 : sio[pp * 3 + k];
                 }
             }
 #pragma unroll
@@ -1667,7 +1698,7 @@ __global__ __launch_bounds__(64) void k_prep(double* __restrict__ sc, double Del
     } else {
         G11 = sc[1];
     }
-    const double reg = reg_from_scalars(sc, G11, Delta, reg_min);
+    const double reg = reg_from_scalars(sc, G11, start_radius(sc, Delta), reg_min);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         sc[13] = reg;
         // forcing term of this iteration's PCG (slot 15) from the drop of the scaled gradient norm (slot 14 keeps the

@@ -263,6 +263,9 @@ struct sfmba_handle {
         int pcg_split = -1;                  // 1: the local form with its tail in a kernel of its own (k_pcg_tail) on a
                                              // single rank too; 0: sharded / multi-chunk solves keep the round-2 forms
                                              // (whole update in every workgroup of pass A, or k_pcg_update)
+        int spec_scale = -1;                 // 0: k_update_scale is launched after the host has accepted the trial point
+        int start_handoff = -1;              // 0: a solve starts with a blocking read-back of the cost and the scale sums
+        int early_download = -1;             // 0: the result is copied to the host behind the last launch of the solve
         int cam_chunk = 0;                   // > 0: chunk length of the camera-major kernels
         int pcg_guess_bias = 0;              // added to the number of speculatively enqueued PCG iterations
         int trace_pcg = 0, trace_stalls = 0, trace_timing = 0;   // stderr diagnostics
@@ -293,6 +296,8 @@ struct sfmba_handle {
     DevBuf V, Vinv, gp, e, recA, recB;       // rec: point records X Y Z | z (k_fill_rec), one per parameter vector
     DevBuf edge;                             // pieces of the point rows cut by K1's tiles (PointBlocksOut)
     DevBuf g, si, sg, p;                     // n-vectors; p = [dc | dp]
+    DevBuf g2, si2, sg2;                     // second set of g, si, sg: a speculative k_update_scale writes the trial
+                                             // point's there (see g_cur below)
     DevBuf Dc, Minv, vecs, vtmp, vcm;               // camera-sized, plane-major [k][C]; vecs = 2 sets x (x r p s u)
     DevBuf part, ctrl;
     DevBuf arena_own;
@@ -348,6 +353,7 @@ struct sfmba_handle {
     // DMA -- 145 us against 130-150 us for one copy + a four-thread staging copy: four blit launches, no gain.)
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_written = nullptr, ev_copied[2] = {nullptr, nullptr};
+    bool result_in_flight = false;           // a solve's early result copy (copy stream -> h_x) has not been waited for
     PinnedBuf mirror[2];
     unsigned long long mirror_tag[2] = {0, 0}, copy_count = 0, x_tag = 0;
     bool mirror_on = false;
@@ -384,6 +390,14 @@ struct sfmba_handle {
     double* tab_new = nullptr;
     double* rec = nullptr;                   // point records of x / x_new (swapped together with them)
     double* rec_new = nullptr;
+    // gradient, column scale and D^2 g of the ACCEPTED point (alias g / si / sg or g2 / si2 / sg2) and the set a
+    // speculative k_update_scale fills for the trial point; swapped where x / tab / rec are, on acceptance only
+    double* g_cur = nullptr;
+    double* si_cur = nullptr;
+    double* sg_cur = nullptr;
+    double* g_new = nullptr;
+    double* si_new = nullptr;
+    double* sg_new = nullptr;
 
     double* acc() const { return arena; }    // product of the implicit Schur complement / reduced rhs term (6C)
     double* sd() const { return arena + 6 * C; }       // diagonal blocks of W Vinv W^T (Schur-diagonal preconditioner)
@@ -588,6 +602,19 @@ void report_stall(const sfmba_handle* h, const char* where, double seconds) {   
     if (h->dbg.trace_stalls && seconds > 2e-3) fprintf(stderr, "sfmba: waited %.2f ms in %s\n", 1e3 * seconds, where);
 }
 
+int wait_event(sfmba_handle* h, hipEvent_t ev) {      // as wait_stream, for one event of the copy stream
+    const double t0 = now_s();
+    for (;;) {
+        const hipError_t e = hipEventQuery(ev);
+        if (e == hipSuccess) { report_stall(h, "wait_event", now_s() - t0); return 0; }
+        if (e != hipErrorNotReady) return fail(h, -3, "hipEventQuery failed: %s", hipGetErrorString(e));
+        if (now_s() - t0 > 0.05) break;
+    }
+    HIPCHK(h, hipEventSynchronize(ev));
+    report_stall(h, "wait_event (blocking)", now_s() - t0);
+    return 0;
+}
+
 int wait_stream(sfmba_handle* h) {
     const double t0 = now_s();
     for (;;) {
@@ -648,7 +675,14 @@ int wait_mailbox(sfmba_handle* h, unsigned long long seq) {
 // ---- kernel launch wrappers --------------------------------------------------------------------
 
 // camera table and point records of a freshly uploaded parameter vector
-int launch_cam_table(sfmba_handle* h, const double* x, double* tab, double* rec) {
+int launch_cam_table(sfmba_handle* h, const double* x, double* tab, double* rec, bool one_launch = false) {
+    if (one_launch) {
+        const int bc = (int)((h->C + 255) / 256);
+        hipLaunchKernelGGL(k_cam_table_rec, dim3((unsigned)(bc + (3 * h->P + 255) / 256)), dim3(256), 0, h->stream, x,
+                           (int)h->C, (int)h->P, bc, tab, rec);
+        LAUNCHED(h);
+        return 0;
+    }
     hipLaunchKernelGGL(k_cam_table, dim3((h->C + 255) / 256), dim3(256), 0, h->stream, x, (int)h->C, tab);
     LAUNCHED(h);
     hipLaunchKernelGGL(k_fill_rec, dim3((unsigned)((3 * h->P + 255) / 256)), dim3(256), 0, h->stream, x + 6 * h->C, (int)h->P, rec);
@@ -1070,7 +1104,7 @@ int schur_product_standalone(sfmba_handle* h, const double* v_planes) {
 // partials -> half B.  When k_update_scale's final sums are still pending they ride along (one extra workgroup).
 int launch_jdot(sfmba_handle* h, int* nparts) {
     const int grid = grid_1d(h->N, kSweepThreads, h->n_cu);
-    const double* sgc = h->sg.as<double>();
+    const double* sgc = h->sg_cur;
     const double* sgp = sgc + 6 * h->C;
     Piggyback pb{};
     if (h->pending_scale_sums) pb = slices_rider(h, 0, 4);
@@ -1113,7 +1147,7 @@ int launch_backsub(sfmba_handle* h, int* nparts) {
         CHK(set_lds(h, kern, lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, h->ranges.as<int2>(), h->n_ranges, obs_arrays(h),
                            h->vecs.as<double>(), dc, vinv_ptr(h), h->gp.as<double>(), h->t1.as<double>(), dp, h->partB(),
-                           (int)h->C, (const PcgCtrl*)nullptr, 0, h->g.as<double>(), h->si.as<double>(), h->sg.as<double>(), rc, FinalUpdate{});
+                           (int)h->C, (const PcgCtrl*)nullptr, 0, h->g_cur, h->si_cur, h->sg_cur, rc, FinalUpdate{});
     } else if (h->lds_vec) {
         const size_t lds = sizeof(double) * 6 * h->C;
         auto kern = k_backsub<true>;
@@ -1121,7 +1155,7 @@ int launch_backsub(sfmba_handle* h, int* nparts) {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, h->ranges.as<int2>(),
                            h->n_ranges, obs_arrays(h), h->vecs.as<double>(), dc, vinv_ptr(h),
                            h->gp.as<double>(), h->t1.as<double>(), dp, h->partB(), (int)h->C,
-                           ctrl2, h->pcg_L, h->g.as<double>(), h->si.as<double>(), h->sg.as<double>(), rc,
+                           ctrl2, h->pcg_L, h->g_cur, h->si_cur, h->sg_cur, rc,
                            h->pcg_a_owed ? FinalUpdate{h->pcg_part.as<double>(), h->vecs.as<double>(), h->ctrl.as<PcgCtrl>(), h->pcg_L - 1}
                                          : FinalUpdate{});
     } else {
@@ -1131,8 +1165,8 @@ int launch_backsub(sfmba_handle* h, int* nparts) {
         hipLaunchKernelGGL(k_backsub<false>, dim3(grid), dim3(kSweepThreads), 0, h->stream,
                            h->ranges.as<int2>(), h->n_ranges, obs_arrays(h), h->vecs.as<double>(), dc,
                            vinv_ptr(h), h->gp.as<double>(), h->t1.as<double>(), dp,
-                           h->partB(), (int)h->C, (const PcgCtrl*)nullptr, 0, h->g.as<double>(),
-                           h->si.as<double>(), h->sg.as<double>(), rc, FinalUpdate{});
+                           h->partB(), (int)h->C, (const PcgCtrl*)nullptr, 0, h->g_cur,
+                           h->si_cur, h->sg_cur, rc, FinalUpdate{});
     }
     LAUNCHED(h);
     *nparts = grid;
@@ -1141,16 +1175,29 @@ int launch_backsub(sfmba_handle* h, int* nparts) {
 
 // column scale + gradient + q0..q4 of the new iterate (after the normal blocks are complete)
 // `defer`: the final sums are left to ride with the next k_jdot launch (flush_scale_sums if none follows)
-int launch_update_scale(sfmba_handle* h, int first, bool defer = false) {
+// `speculative`: the trial point h->x_new, enqueued before the host has decided on it.  The accepted point's si, g, sg
+// are only read (the running maximum) and the results go to the second buffer set, which the host swaps in when it
+// accepts the step; on a rejection nothing is swapped and the next trial's launch overwrites them.  The launch
+// honours h->skip (k_tr_step cancelled the trial: K3 wrote no blocks).  The partial rows (half A) are NOT summed by
+// this launch: exchange slots 8..12 and kCamSlot + 0..4 always describe the ACCEPTED point when the host or k_prep
+// read them -- the sums run (riding with k_jdot, or flush_scale_sums) only after the host has accepted the point,
+// i.e. set pending_scale_sums; a rejected trial's rows are overwritten by the next K1 / k_update_scale.
+int launch_update_scale(sfmba_handle* h, int first, bool defer = false, bool speculative = false) {
+    const double* x = speculative ? h->x_new : h->x;
+    double* si = speculative ? h->si_new : h->si_cur;
+    double* g = speculative ? h->g_new : h->g_cur;
+    double* sg = speculative ? h->sg_new : h->sg_cur;
+    const double* skip = speculative ? h->skip : (const double*)nullptr;
     if (h->scale_pts == 2)
         hipLaunchKernelGGL(k_update_scale<2>, dim3(h->red_grid), dim3(256), 0, h->stream, h->Ugc(), h->V.as<double>(),
-                           h->gp.as<double>(), h->x, (int)h->C, (int)h->P, first, h->red_bc, h->si.as<double>(),
-                           h->g.as<double>(), h->sg.as<double>(), h->part.as<double>());
+                           h->gp.as<double>(), x, (int)h->C, (int)h->P, first, h->red_bc, (const double*)h->si_cur, si,
+                           g, sg, h->part.as<double>(), skip);
     else
         hipLaunchKernelGGL(k_update_scale<1>, dim3(h->red_grid), dim3(256), 0, h->stream, h->Ugc(), h->V.as<double>(),
-                           h->gp.as<double>(), h->x, (int)h->C, (int)h->P, first, h->red_bc, h->si.as<double>(),
-                           h->g.as<double>(), h->sg.as<double>(), h->part.as<double>());
+                           h->gp.as<double>(), x, (int)h->C, (int)h->P, first, h->red_bc, (const double*)h->si_cur, si,
+                           g, sg, h->part.as<double>(), skip);
     LAUNCHED(h);
+    if (speculative) return 0;
     if (defer) { h->pending_scale_sums = true; return 0; }
     return launch_finish_slices(h, 0, 4);
 }
@@ -1253,7 +1300,12 @@ int upload_x(sfmba_handle* h, const double* x_host) {
         h->origin = Origin{sx / (double)cnt, sy / (double)cnt, sz / (double)cnt};
         if (!std::isfinite(h->origin.x + h->origin.y + h->origin.z)) h->origin = Origin{0.0, 0.0, 0.0};
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));      // the staging buffer may still be in flight
+    // The staging buffer's readers and writers on the stream: every call waits for its own before it returns (the solve
+    // for a post behind its upload and for the result's copy); synchronising an idle stream costs about 1 us and is kept.
+    // The early result copy of a solve runs on the copy stream: only a solve that failed leaves one behind.
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->result_in_flight && h->copy_stream) HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    h->result_in_flight = false;
     const double t0 = now_s();
     hipError_t err = hipSuccess;
     staging_copy(h, h->h_x, x_host, sizeof(double) * h->n, [&](int, size_t off, size_t bytes) {
@@ -1582,6 +1634,9 @@ int sfmba_debug_option(sfmba_handle* h, const char* name, int64_t value) {
     else if (n == "packed_upload") h->dbg.packed_upload = v;
     else if (n == "pcg_mixed_b") h->dbg.pcg_mixed_b = v;
     else if (n == "cost_rider") h->dbg.cost_rider = v;
+    else if (n == "spec_scale") h->dbg.spec_scale = v;
+    else if (n == "start_handoff") h->dbg.start_handoff = v;
+    else if (n == "early_download") h->dbg.early_download = v;
     else if (n == "rhsrec") h->dbg.rhsrec = v;
     else if (n == "xcd_chunks") h->dbg.xcd_chunks = v;
     else if (n == "tab_lds") h->dbg.tab_lds = v;
@@ -2285,6 +2340,11 @@ static int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, co
     HIPCHK(h, h->g.ensure(sizeof(double) * h->n));
     HIPCHK(h, h->si.ensure(sizeof(double) * h->n));
     HIPCHK(h, h->sg.ensure(sizeof(double) * h->n));
+    HIPCHK(h, h->g2.ensure(sizeof(double) * h->n));
+    HIPCHK(h, h->si2.ensure(sizeof(double) * h->n));
+    HIPCHK(h, h->sg2.ensure(sizeof(double) * h->n));
+    h->g_cur = static_cast<double*>(h->g.p); h->si_cur = static_cast<double*>(h->si.p); h->sg_cur = static_cast<double*>(h->sg.p);
+    h->g_new = h->g2.as<double>(); h->si_new = h->si2.as<double>(); h->sg_new = h->sg2.as<double>();
     HIPCHK(h, h->p.ensure(sizeof(double) * h->n + 16));
     HIPCHK(h, h->Dc.ensure(sizeof(double) * 6 * C));
     HIPCHK(h, h->Minv.ensure(sizeof(double) * 21 * C));
@@ -2572,15 +2632,15 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
         CHK(launch_normal_blocks(h, h->x, h->tab, h->rec));
         CHK(launch_update_scale(h, 1));
         hipLaunchKernelGGL(k_point_prep, dim3((h->P + 255) / 256), dim3(256), 0, h->stream, h->V.as<double>(),
-                           h->gp.as<double>(), h->si.as<double>() + 6 * h->C, (const double*)nullptr, (int)h->P,
+                           h->gp.as<double>(), h->si_cur + 6 * h->C, (const double*)nullptr, (int)h->P,
                            1e-6, vinv_ptr(h), h->rec + 3, (const double*)(h->x + 6 * h->C),
                            h->use_rhsrec ? h->rhsrec.as<double>() : (double*)nullptr);
         LAUNCHED(h);
         CHK(launch_mixed_prep(h, h->x, h->tab));
         // v = the camera slice of the gradient, as plane-major planes (and camera-major when v is not staged in LDS)
         hipLaunchKernelGGL(k_transpose, dim3((unsigned)((6 * h->C + 255) / 256)), dim3(256), 0, h->stream,
-                           (const double*)h->g.as<double>(), (int)h->C, 6, h->vtmp.as<double>(), (const PcgCtrl*)nullptr, 0);
-        HIPCHK(h, hipMemcpyAsync(h->vcm.p, h->g.p, sizeof(double) * 6 * h->C, hipMemcpyDeviceToDevice, h->stream));
+                           (const double*)h->g_cur, (int)h->C, 6, h->vtmp.as<double>(), (const PcgCtrl*)nullptr, 0);
+        HIPCHK(h, hipMemcpyAsync(h->vcm.p, h->g_cur, sizeof(double) * 6 * h->C, hipMemcpyDeviceToDevice, h->stream));
         CHK(schur_product_standalone(h, h->vtmp.as<double>()));          // leaves a valid z for case 5
     }
     struct EventPair {                    // destroyed on every exit path
@@ -2691,8 +2751,15 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
         ~EventList() { for (auto& pr : *this) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); } }
     } evs;
     int np_cost = 0;                                                  // partial rows of the last K1 launch
+    // debug options of the hand-offs (default: on; single rank only -- with several ranks the cost and the scale sums
+    // pass through collectives between these launches, and the parent's order is kept)
+    const bool quick_start = !multi_rank(h) && h->dbg.start_handoff != 0 && h->dbg.cost_rider != 0;
+    const bool spec_scale = !multi_rank(h) && h->dbg.spec_scale != 0;
+    const bool early_download = h->copy_stream != nullptr && h->dbg.early_download != 0;
+    bool result_sent = false;                                         // x is already on its way to h_x (ev_copied[0])
+    double t_sent0 = 0.0, t_sent1 = 0.0, t_ws = 0.0;
     auto eval_jac = [&](const double* x, double* tab, bool table_ready, bool finish = true) -> int {   // K0 + K1, sum r^2 -> scalar 0
-        if (!table_ready) CHK(launch_cam_table(h, x, tab, h->rec));
+        if (!table_ready) CHK(launch_cam_table(h, x, tab, h->rec, quick_start));
         int& np = np_cost;
         if (opt.profile) {
             hipEvent_t a, b;
@@ -2720,17 +2787,35 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
     };
 
     // f0, J0 (least_squares.py:838, 903-912)
-    CHK(eval_jac(h->x, h->tab, false));
-    CHK(exchange(h, sc, 1, 0));                      // sum r^2
-    CHK(linearise(1));
-    CHK(fetch_scalars(h));
-    double cost = 0.5 * h->h_scal[0];
-    if (!std::isfinite(cost)) return fail(h, -2, "Residuals are not finite in the initial point.");
-    out->cost0 = cost;
-    out->rmse0 = std::sqrt(2.0 * cost / m_total);
+    double cost = 0.0, Delta = -1.0;
+    unsigned long long start_seq = 0;                // quick start: the post the host still has to wait for
+    auto start_values = [&]() -> int {               // cost0 is on the host
+        cost = 0.5 * h->h_scal[0];
+        if (!std::isfinite(cost)) return fail(h, -2, "Residuals are not finite in the initial point.");
+        out->cost0 = cost;
+        out->rmse0 = std::sqrt(2.0 * cost / m_total);
+        return 0;
+    };
+    if (quick_start) {
+        // No blocking hand-off: the launches take the form of a trial evaluation (the cost sum and its post ride with
+        // K3), k_update_scale's sums ride with the first k_jdot, and k_prep / k_tr_step derive the first radius from
+        // the exchange scalars themselves (Delta < 0).  The host picks the cost up behind the k_jdot launch below and
+        // the radius (slot 31) at the first regular hand-off.
+        CHK(eval_jac(h->x, h->tab, false, /*finish=*/false));
+        start_seq = ++h->mbox_seq;
+        CHK(launch_normal_blocks(h, h->x, h->tab, h->rec, np_cost,
+                                 Mailbox{h->mbox_dev, sc, nullptr, start_seq, p2p_error_word(h)}));
+        CHK(launch_update_scale(h, 1, /*defer=*/true));
+    } else {
+        CHK(eval_jac(h->x, h->tab, false));
+        CHK(exchange(h, sc, 1, 0));                      // sum r^2
+        CHK(linearise(1));
+        CHK(fetch_scalars(h));
+        CHK(start_values());
+        Delta = std::sqrt(qsum(h, 2));                          // |x0 * scale_inv|, trf.py:428
+        if (Delta == 0.0) Delta = 1.0;
+    }
     int64_t nfev = 1, njev = 1, iteration = 0, pcg_total = 0;
-    double Delta = std::sqrt(qsum(h, 2));                       // |x0 * scale_inv|, trf.py:428
-    if (Delta == 0.0) Delta = 1.0;
     int status = -1;
     double step_norm = 0.0, actual_reduction = 0.0, g_norm = 0.0, reg_term = 0.0;
     bool have_red = false;
@@ -2780,6 +2865,12 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
         int np = 0;
         const bool scale_sums_rode = h->pending_scale_sums;
         CHK(launch_jdot(h, &np));                               // t1 = J D^2 g, G11 = |t1|^2
+        if (start_seq != 0) {                                   // quick start: cost0 was posted by K3 a while ago
+            CHK(wait_mailbox(h, start_seq));
+            memcpy(h->h_scal, h->mbox, sizeof(double) * kScalSlots);
+            start_seq = 0;
+            CHK(start_values());
+        }
         if (!one_rank && h->p2p.ready) {
             // direct path: the collective's own workgroup first sums k_jdot's partials into slot 1, then reduces
             // slots 1..12 over the ranks when an accepted step left fresh q1..q4 (8..11, sums) and max|g| (12, a
@@ -2800,7 +2891,7 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
         {   // regularisation (trf.py:471-475), Vinv/e per point, Dc/Minv per camera, acc0 = 0: one launch
             const int bc = (int)((C + 63) / 64), bp = (int)((P + 63) / 64);
             hipLaunchKernelGGL(k_prep, dim3(bc + bp), dim3(64), 0, h->stream, sc, Delta, opt.reg_min, h->Ugc(),
-                               h->V.as<double>(), h->gp.as<double>(), h->si.as<double>(), (int)C, (int)P, bc,
+                               h->V.as<double>(), h->gp.as<double>(), h->si_cur, (int)C, (int)P, bc,
                                h->Dc.as<double>(), (h->dbg.precond == 0 ? h->Minv.as<double>() : (double*)nullptr),
                                vinv_ptr(h), h->rec + 3,
                                one_rank ? (const double*)h->partB() : (const double*)nullptr, np, opt.pcg_tol,
@@ -2850,7 +2941,7 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
         auto enqueue_trial = [&](const double* coef_dev, double c1, double c2) -> int {
             const int bc = (int)((C + 255) / 256);
             hipLaunchKernelGGL(k_step_table, dim3(bc + grid_1d(3 * P, 256, 2048)), dim3(256), 0, h->stream, h->x,
-                               h->sg.as<double>(), h->p.as<double>(), c1, c2, coef_dev, (int)C, n, bc, h->x_new,
+                               h->sg_cur, h->p.as<double>(), c1, c2, coef_dev, (int)C, n, bc, h->x_new,
                                h->tab_new, h->rec_new, h->skip);
             LAUNCHED(h);
             if (h->mirror_on) {                                 // x_new to its host mirror, beside the evaluation below
@@ -2907,6 +2998,8 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
             else CHK(launch_normal_blocks(h, h->x_new, h->tab_new, h->rec_new));
             trial_post_pending = false;
             nb_valid = false;
+            // ... and, behind them, scale, gradient and partial sums of the trial point into the second buffer set
+            if (spec_scale) CHK(launch_update_scale(h, 0, /*defer=*/true, /*speculative=*/true));
             CHK(wait_mailbox(h, h->mbox_seq));
             memcpy(h->h_scal, h->mbox, sizeof(double) * kScalSlots);
             if (with_ctrl) memcpy(&hc, h->mbox + kMboxCtrl, sizeof hc);
@@ -2947,6 +3040,7 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
         // zero when the very first step failed, in which case the 2-D model below degenerates to the
         // steepest-descent line, exactly scipy's fallback when gn_h adds nothing to span(g_h).
         if (hc.done == 3) ++pcg_breakdowns;
+        if (Delta < 0.0) Delta = h->h_scal[31];                 // quick start: the radius k_tr_step derived and used
 
         // ---- loop head of trf.py:450-459, evaluated now that the scalars are on the host -----------
         g_norm = std::max(h->h_scal[kMaxSlot], h->h_scal[kCamSlot + 0]);
@@ -3013,7 +3107,28 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
                                                                 // point are already there / in flight
             cost = cost_new;
             ++njev;
-            CHK(launch_update_scale(h, 0, /*defer=*/true));     // its final sums ride with the next k_jdot and
+            if (status != -1 && early_download && !h->mirror_on) {
+                // The solve ends on this point.  x was written by k_step_table, which the stream ran before the K1 / K3
+                // whose post the host has just read, and nothing from here on writes it: the result leaves on the copy
+                // stream now, beside what is left of K3, k_update_scale, the final sums and the last post.
+                CHK(ensure_h_x(h));
+                t_sent0 = now_s();
+                // (in ONE piece: two halves, the first half's pinned -> pageable copy beside the second half's transfer,
+                // measured 1.805-1.822 ms per cfg4 solve against 1.792-1.849 -- no gain, two blit launches)
+                HIPCHK(h, hipMemcpyAsync(h->h_x, h->x, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->copy_stream));
+                HIPCHK(h, hipEventRecord(h->ev_copied[0], h->copy_stream));
+                h->result_in_flight = true;
+                result_sent = true;
+                t_sent1 = now_s();
+            }
+            if (spec_scale) {                                   // already enqueued behind K3 (handoff): take its outputs
+                std::swap(h->g_cur, h->g_new);
+                std::swap(h->si_cur, h->si_new);
+                std::swap(h->sg_cur, h->sg_new);
+                h->pending_scale_sums = true;
+            } else {
+                CHK(launch_update_scale(h, 0, /*defer=*/true));
+            }                                                   // its final sums ride with the next k_jdot and
                                                                 // are read with the next hand-off
         } else {
             step_norm = 0.0;
@@ -3042,10 +3157,19 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
     const int xw = h->x == h->xa.as<double>() ? 0 : 1;
     const bool mirrored = h->mirror_on && h->x_tag != 0 && h->mirror_tag[xw] == h->x_tag;     // x is on the host already
     const size_t xbytes = sizeof(double) * (size_t)n;
-    if (!mirrored) HIPCHK(h, hipMemcpyAsync(h->h_x, h->x, xbytes, hipMemcpyDeviceToHost, h->stream));
+    if (!mirrored && !result_sent) {
+        HIPCHK(h, hipMemcpyAsync(h->h_x, h->x, xbytes, hipMemcpyDeviceToHost, h->stream));
+    }
     if (h->p2p.ready)                                           // did a direct all-reduce give up waiting for a peer?
         HIPCHK(h, hipMemcpyAsync(h->h_scal + 62, h->p2p.words + 1, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    // (result_sent: the last launch of the stream is the k_post whose post fetch_scalars has waited for; the query
+    // still lets the runtime retire the solve's launches while the copy is in flight)
     CHK(wait_stream(h));
+    t_ws = now_s();
+    if (result_sent) {
+        CHK(wait_event(h, h->ev_copied[0]));
+        h->result_in_flight = false;
+    }
     if (mirrored) HIPCHK(h, hipEventSynchronize(h->ev_copied[xw]));
     const double t_dl1 = now_s();
     if (h->p2p.ready) {
@@ -3056,6 +3180,9 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
     staging_copy(h, x_inout, mirrored ? h->mirror[xw].p : (const void*)h->h_x, xbytes);
     if (h->mirror_on) HIPCHK(h, hipStreamSynchronize(h->copy_stream));     // (a copy of a rejected last trial may still run)
     const double t_end = now_s();
+    if (h->dbg.trace_timing && result_sent)
+        fprintf(stderr, "sfmba: early result copy: enqueue %.1f us, then %.1f us to the last post, stream query %.1f us, copy event %.1f us\n",
+                1e6 * (t_sent1 - t_sent0), 1e6 * (t_dl0 - t_sent1), 1e6 * (t_ws - t_dl0), 1e6 * (t_dl1 - t_ws));
     if (h->dbg.trace_timing)
         fprintf(stderr, "sfmba: solve  %.3f ms total, upload %.1f us, result: copy + wait %.1f us, staging copy %.1f us\n", 1e3 * (t_end - t_begin),
                 1e6 * (t_dev0 - t_begin), 1e6 * (t_dl1 - t_dl0), 1e6 * (t_end - t_dl1));
@@ -3090,7 +3217,7 @@ int sfmba_get_fun_grad(sfmba_handle* h, double* fun_out, double* grad_out) {
     if (fun_out) CHK(download_residuals(h, fun_out));
     if (grad_out) {
         CHK(ensure_h_x(h));
-        HIPCHK(h, hipMemcpyAsync(h->h_x, h->g.p, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->h_x, h->g_cur, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
         CHK(wait_stream(h));
         memcpy(grad_out, h->h_x, sizeof(double) * h->n);
     }
