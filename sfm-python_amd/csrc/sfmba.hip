@@ -51,7 +51,14 @@ constexpr int kScalSlots = 32;
 // k_resjac) and B (k_jdot, k_backsub).  Consecutive producers alternate halves, so the final sums of one
 // producer can ride along with the NEXT producer's launch (Piggyback) without a race on the rows.
 constexpr int kPartRows = 2048;
+//   written by k_tr_step [25..31]: c1, c2, predicted reduction, |step_h|, |step| of the step it chose; its verdict
+//                              (non-zero: the trial launches behind it are void); the radius it used
+constexpr int kCostSlot = 0, kG11Slot = 1, kTailSlot = 2, kQ1Slot = 8;      // sum r^2 | G11 | G12, G22, q5..q8 | q1..q4
 constexpr int kMaxSlot = 12, kRegSlot = 13, kGhPrevSlot = 14, kEtaSlot = 15, kCamSlot = 16;
+constexpr int kStepSlot = 25, kSkipSlot = 30, kRadiusSlot = 31;
+// the pinned block h_scal (64 doubles): the scalars, then staging for small read-backs
+constexpr int kPinCtrl = 40;             // a PcgCtrl (pcg_read)
+constexpr int kPinP2pErr = 62;           // the error word of the direct link at the end of a solve
 constexpr int kPointSlot[9] = {12, 8, 9, 10, 11, 4, 5, 6, 7};     // slot of q0..q8 of the point slice
 
 struct DevBuf {
@@ -204,6 +211,86 @@ double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// test / diagnostic hooks, set through sfmba_debug_option only (nothing reads the environment)
+#define SFMBA_DEBUG_OPTIONS(X) \
+    X(pcg_fused, -1)      /* 0: two-kernel PCG although the fused launch would fit */ \
+    X(tab_lds, -1)        /* 0: camera table read from L2 although LDS would fit */ \
+    X(vec_lds, -1)        /* 0: camera vector read from L2 although LDS would fit */ \
+    X(sweep_rc, -1)       /* 0: pass A reads the stored Jacobian although the recomputing form would fit; 2: its table in global memory whatever the size */ \
+    X(dense, -1)          /* 0: PCG although the dense reduced-camera path would apply */ \
+    X(precond, -1)        /* 0: block-Jacobi preconditioner from U + Dc instead of the Schur diagonal */ \
+    X(pcg_local, -1)      /* 0: the fused PCG keeps its whole update in pass A's prologue */ \
+    X(xcd_chunks, -1)     /* 1 / 0: camera lists cut at the eight point-range boundaries (one chunk per XCD) whatever the size */ \
+    X(rhsrec, -1)         /* 1 / 0: the rhs + preconditioner pass gathers its own 128-byte records whatever the size */ \
+    X(cost_rider, -1)     /* 0: the trial cost is summed and posted by a k_finish launch of its own */ \
+    X(packed_upload, -1)  /* 0: the observation arrays are uploaded as int32 / fp64 although they would pack */ \
+    X(jfree, -1)          /* 1: the J-free iteration (measurement): K1 does not write the Jacobian, k_jdot and k_backsub recompute its blocks from the LDS camera table */ \
+    X(cm_device, -1)      /* 0: the camera-major order is sorted on the host and its permutation uploaded */ \
+    X(pcg_inline, -1)     /* 0: sharded solves keep the collective of the product as a launch of its own */ \
+    X(xcd_cam, -1)        /* 0: K3 and the rhs pass keep the one-chunk-per-camera table where pass B takes the XCD-aware one */ \
+    X(pcg_skip_last, -1)  /* 0: the pass B behind the launch the record says is the last one is enqueued all the same; 2: only that pass B is left out */ \
+    X(pcg_mixed_b, -1)    /* 0: pass B keeps fp64 point records although pass A runs on fp32 operands */ \
+    X(pcg_mixed, -1)      /* 1 / 0: fp32 operands in the implicit Schur product whatever the storage mode */ \
+    X(pcg_split, -1)      /* 1: the local form with its tail in a kernel of its own (k_pcg_tail) on a single rank too; 0: sharded / multi-chunk solves keep the round-2 forms (whole update in every workgroup of pass A, or k_pcg_update) */ \
+    X(spec_scale, -1)     /* 0: k_update_scale is launched after the host has accepted the trial point */ \
+    X(start_handoff, -1)  /* 0: a solve starts with a blocking read-back of the cost and the scale sums */ \
+    X(early_download, -1) /* 0: the result is copied to the host behind the last launch of the solve */ \
+    X(cam_chunk, 0)       /* > 0: chunk length of the camera-major kernels */ \
+    X(pcg_guess_bias, 0)  /* added to the number of speculatively enqueued PCG iterations */ \
+    X(trace_pcg, 0) X(trace_stalls, 0) X(trace_timing, 0)   /* stderr diagnostics */ \
+    X(wait_deadline_s, 120) /* a hand-off that does not arrive within this many seconds fails the solve (-3) */ \
+    X(p2p_delay_ms, 0)    /* test: sleep this long before the first collective of a solve */ \
+    X(p2p_timeout_ms, 0)  /* test: > 0 overrides both time-outs of the direct all-reduce */
+struct Debug {
+#define X(name, init) int name = init;
+    SFMBA_DEBUG_OPTIONS(X)
+#undef X
+};
+// name -> member, from the same list: an option cannot exist without a setter
+const struct { const char* name; int Debug::*member; } kDebugOptions[] = {
+#define X(name, init) {#name, &Debug::name},
+    SFMBA_DEBUG_OPTIONS(X)
+#undef X
+};
+
+// Which form of every kernel runs.  Two functions below the handle fill it and nothing else writes it:
+// decide_problem_forms (sfmba_set_problem) and decide_solve_forms (start of every compute call).
+struct Forms {
+    // ---- problem stage: frozen until the next sfmba_set_problem
+    bool packed_upload = false;              // observation arrays cross PCIe as uint16 / int16 (k_unpack_obs)
+    bool cm_device = false;                  // camera-major order sorted on the device
+    int64_t cam_chunk_len = 4096;            // chunk length of the camera-major kernels
+    bool lds_tab = true, lds_vec = true;     // camera table (K1, K2) / camera vector (sweeps) staged in LDS
+    bool sweep_rc = false;                   // pass A recomputes the blocks from an LDS table (k_point_sweep_rc)
+    bool sweep_rc_g = false;                 // ... from a table in global memory (more cameras than the LDS holds)
+    bool round_blocks = false;               // pass A applies stored fp32 blocks: the camera-major passes round theirs the same way
+    bool pcg_fused = false;                  // PCG update fused into the launch of pass A (v in LDS, C <= 1024)
+    // mixed-precision Schur product (ba_kernels.hpp: MixedPrep): fp32 operands, fp64 arithmetic
+    bool mixed = false;                      // pass A
+    bool mixed_b = false;                    // ... and pass B (fp32 point records)
+    bool jfree = false;                      // J-free iteration (needs the camera table in LDS)
+    bool dense = false;                      // reduced camera matrix formed and factorised (6 C <= kDenseMaxN) instead of PCG
+    bool xcd_b = false;                      // pass B takes the XCD-aware chunk table (every camera's list cut at eight point ranges)
+    bool use_rhsrec = false;                 // the rhs + preconditioner pass gathers its own 128-byte records (many points)
+    bool cam_multi = false;                  // some camera has more than one chunk: k_cam_combine runs
+    // ---- solve stage: from the above, the transport as it stands and the options read live
+    bool one_rank = true;                    // no transport: nothing is exchanged
+    bool dense_solve = false;                // dense, on one rank (sharded: the block pairs would need their own all-reduce)
+    bool precond = true;                     // Schur-diagonal preconditioner (false: block-Jacobi of U + Dc)
+    bool xcd_cam = false;                    // K3 and the rhs pass over the XCD-aware table too, one wave per chunk
+    bool cam_inline = false;                 // per-camera sums of K3 / the rhs pass all-reduced by the workgroup that forms them
+    bool own_inverse = false;                // the rhs pass inverts its camera's preconditioner block itself (RhsPrecond)
+    // where the product is reduced: inside pass B, camera by camera (CamExchange) / behind it, with the per-camera tail of
+    // the local form (k_p2p_pcg / k_pcg_tail); else by a collective and k_pcg_update or pass A's prologue
+    bool pcg_inline = false, pcg_split = false;
+    // per-camera bookkeeping in pass B or the tail: the fused form / the light update as a kernel of its own (> 1024 cameras)
+    bool pcg_local = false, pcg_local2 = false;
+    int skip_last = 0;                       // of the last speculative launch pair: 0 nothing is left out, 1 its pass B, 2 pass A too (FinalUpdate)
+    // hand-offs: no blocking one at the start; k_update_scale of the trial point enqueued before the verdict; (one rank) the
+    // trial cost and its post ride with K3; the result leaves on the copy stream as soon as the solve is decided
+    bool quick_start = false, spec_scale = false, cost_rider = true, early_download = false;
+};
+
 }  // namespace
 
 struct sfmba_handle {
@@ -225,54 +312,15 @@ struct sfmba_handle {
     bool f32_next = false;                   // takes effect at the next sfmba_set_problem
     std::vector<int64_t> fixed_next;         // sfmba_set_fixed_cameras: cameras held still from the next sfmba_set_problem on
     int64_t n_fixed = 0;                     // ... of the current problem
-    bool lds_tab = true, lds_vec = true;     // camera table (K1, K2) / camera vector (sweeps) staged in LDS
-    bool sweep_rc = false;                   // pass A recomputes the blocks from an LDS table (k_point_sweep_rc)
-    bool sweep_rc_g = false;                 // ... from a table in global memory (more cameras than the LDS holds)
+    Forms forms;                            // which kernel forms run (decide_problem_forms / decide_solve_forms)
     DevBuf rctab;                            // [C][18], k_rc_table
-    // mixed-precision Schur product (ba_kernels.hpp: MixedPrep): fp32 operands, fp64 arithmetic
-    bool jfree = false;                      // J-free iteration (debug option jfree; needs the camera table in LDS)
-    bool mixed = false;                      // pass A
-    bool mixed_b = false;                    // ... and pass B (fp32 point records)
     DevBuf rt32, rec32, rctab32, rtd;        // [C][12], [P][8], [C][20] floats; [C][12] doubles
     Origin origin{0.0, 0.0, 0.0};            // coordinates are rounded relative to it (set with every uploaded x)
-    bool dense = false;                      // reduced camera matrix formed and factorised (6 C <= kDenseMaxN) instead of PCG
     DevView cov_ptr, cov_pt, blk_ab;         // dense path: per block pair (a <= b) the points both cameras see
     DevBuf Sblk;
     DevBuf tables;                           // ranges | wsteps | steps | chunk table | chunk offsets | pair lists: ONE upload
     int n_blk = 0;
-    // test / diagnostic hooks, set through sfmba_debug_option only (nothing reads the environment)
-    struct Debug {
-        int pcg_fused = -1;                  // 0: two-kernel PCG although the fused launch would fit
-        int tab_lds = -1, vec_lds = -1;      // 0: camera table / camera vector read from L2 although LDS would fit
-        int sweep_rc = -1;                   // 0: pass A reads the stored Jacobian although the recomputing form would fit
-        int dense = -1;                      // 0: PCG although the dense reduced-camera path would apply
-        int precond = -1;                    // 0: block-Jacobi preconditioner from U + Dc instead of the Schur diagonal
-        int pcg_local = -1;                  // 0: the fused PCG keeps its whole update in pass A's prologue
-        int xcd_chunks = -1;                 // 1 / 0: camera lists cut at the eight point-range boundaries (one chunk per XCD) whatever the size
-        int rhsrec = -1;                     // 1 / 0: the rhs + preconditioner pass gathers its own 128-byte records whatever the size
-        int cost_rider = -1;                 // 0: the trial cost is summed and posted by a k_finish launch of its own
-        int packed_upload = -1;              // 0: the observation arrays are uploaded as int32 / fp64 although they would pack
-        int jfree = -1;                      // 1: the J-free iteration (measurement): K1 does not write the Jacobian, k_jdot and
-                                             // k_backsub recompute its blocks from the LDS camera table
-        int cm_device = -1;                  // 0: the camera-major order is sorted on the host and its permutation uploaded
-        int pcg_inline = -1;                 // 0: sharded solves keep the collective of the product as a launch of its own
-        int xcd_cam = -1;                    // 0: K3 and the rhs pass keep the one-chunk-per-camera table where pass B takes the XCD-aware one
-        int pcg_skip_last = -1;              // 0: the pass B behind the launch the record says is the last one is enqueued all the same
-        int pcg_mixed_b = -1;                // 0: pass B keeps fp64 point records although pass A runs on fp32 operands
-        int pcg_mixed = -1;                  // 1 / 0: fp32 operands in the implicit Schur product whatever the storage mode
-        int pcg_split = -1;                  // 1: the local form with its tail in a kernel of its own (k_pcg_tail) on a
-                                             // single rank too; 0: sharded / multi-chunk solves keep the round-2 forms
-                                             // (whole update in every workgroup of pass A, or k_pcg_update)
-        int spec_scale = -1;                 // 0: k_update_scale is launched after the host has accepted the trial point
-        int start_handoff = -1;              // 0: a solve starts with a blocking read-back of the cost and the scale sums
-        int early_download = -1;             // 0: the result is copied to the host behind the last launch of the solve
-        int cam_chunk = 0;                   // > 0: chunk length of the camera-major kernels
-        int pcg_guess_bias = 0;              // added to the number of speculatively enqueued PCG iterations
-        int trace_pcg = 0, trace_stalls = 0, trace_timing = 0;   // stderr diagnostics
-        int wait_deadline_s = 120;           // a hand-off that does not arrive within this many seconds fails the solve (-3)
-        int p2p_delay_ms = 0;                // test: sleep this long before the first collective of a solve
-        int p2p_timeout_ms = 0;              // test: > 0 overrides both time-outs of the direct all-reduce
-    } dbg;
+    Debug dbg;                               // test / diagnostic hooks (sfmba_debug_option)
 
     DevBuf cam_idx, pt_idx, pt_ptr, uv;
     DevView ranges, wsteps, steps;
@@ -287,10 +335,8 @@ struct sfmba_handle {
     // point-range boundaries, chunk 8 c + k on XCD k (see set_problem)
     DevView cam_chunks_b, cam_chunk_ptr_b;
     int n_chunks_b = 0;
-    bool xcd_b = false;
     std::vector<int4> host_chunks_b;
     std::vector<int> host_chunk_ptr_b;
-    bool cam_multi = false;                  // some camera has more than one chunk: k_cam_combine runs
     DevBuf xa, xb, tabA, tabB, r, J, t1;     // ONE Jacobian / residual buffer set
     DevBuf rhsrec;                           // [P][kRhsRec]: what k_cam_rhs_diag gathers (written by k_prep)
     DevBuf V, Vinv, gp, e, recA, recB;       // rec: point records X Y Z | z (k_fill_rec), one per parameter vector
@@ -359,15 +405,8 @@ struct sfmba_handle {
     bool mirror_on = false;
     const double* skip = nullptr;         // device flag gating speculative trial launches (sfmba_solve); else null
     double pcg_tol = 0.0; int pcg_cap = 0; // options of the running PCG (fused launch 0 writes the control block)
-    bool pcg_fused = false;               // PCG update fused into the launch of pass A (v in LDS, C <= 1024)
-    bool pcg_local = false;               // ... with the per-camera bookkeeping in pass B (one rank, single-chunk cameras)
-    bool pcg_local2 = false;              // the same bookkeeping with the light update as a kernel of its own (> 1024 cameras)
     bool pcg_b_owed = false;              // the pass B behind the last enqueued pass A was left out (pcg_enqueue)
     bool pcg_a_owed = false;              // ... and that pass A too: k_backsub does its update (FinalUpdate)
-    bool pcg_inline = false;              // sharded, direct link, single-chunk cameras: the product's all-reduce runs inside
-                                          // pass B, camera by camera (CamExchange), and the iteration is the local form
-    bool pcg_split = false;               // local form whose per-camera tail runs behind the reduction (k_p2p_pcg / k_pcg_tail)
-                                          // instead of inside pass B: sharded solves, cameras of several chunks
     DevBuf pcg_part;                      // [4][C] partial dot products of the local form
     int pcg_hint = 0;                     // largest PCG iteration count a solve on this handle has needed
     std::vector<int> pcg_hist;            // PCG iterations of outer iteration k in the previous solve on this handle: the
@@ -377,27 +416,19 @@ struct sfmba_handle {
     int64_t hist_C = 0, hist_P = 0, hist_N = 0;   // the problem pcg_hist was recorded on
     unsigned long long hist_sig = 0;         // ... and its content: problem generation + a checksum of the start vector
     unsigned long long problem_gen = 0;      // raised by every sfmba_set_problem whose arrays differ from the previous ones
-    bool use_rhsrec = false;                 // the rhs + preconditioner pass gathers its own 128-byte records (many points)
     bool solved = false;
     bool transport_dropped = false;          // sfmba_set_problem tore down an active transport: the next compute call
                                              // fails until one is set up again (or single-rank use is acknowledged)
     std::vector<const void*> lds_ready;      // kernels already opted in to 160 KiB dynamic LDS
     int last_pcg_iters = 0;
 
-    double* x = nullptr;                     // current / trial parameter vectors (alias xa/xb)
-    double* x_new = nullptr;
-    double* tab = nullptr;
-    double* tab_new = nullptr;
-    double* rec = nullptr;                   // point records of x / x_new (swapped together with them)
-    double* rec_new = nullptr;
+    double *x = nullptr, *x_new = nullptr;   // current / trial parameter vectors (alias xa/xb)
+    double *tab = nullptr, *tab_new = nullptr;
+    double *rec = nullptr, *rec_new = nullptr;   // point records of x / x_new (swapped together with them)
     // gradient, column scale and D^2 g of the ACCEPTED point (alias g / si / sg or g2 / si2 / sg2) and the set a
     // speculative k_update_scale fills for the trial point; swapped where x / tab / rec are, on acceptance only
-    double* g_cur = nullptr;
-    double* si_cur = nullptr;
-    double* sg_cur = nullptr;
-    double* g_new = nullptr;
-    double* si_new = nullptr;
-    double* sg_new = nullptr;
+    double *g_cur = nullptr, *si_cur = nullptr, *sg_cur = nullptr;
+    double *g_new = nullptr, *si_new = nullptr, *sg_new = nullptr;
 
     double* acc() const { return arena; }    // product of the implicit Schur complement / reduced rhs term (6C)
     double* sd() const { return arena + 6 * C; }       // diagonal blocks of W Vinv W^T (Schur-diagonal preconditioner)
@@ -460,27 +491,110 @@ const unsigned* p2p_error_word(const sfmba_handle* h) { return h->p2p.ready ? h-
 constexpr long long kP2pFirstTicks = 6000000000ll, kP2pSteadyTicks = 3000000000ll;      // 60 s, 30 s at 100 MHz
 constexpr size_t kP2pFlagBytes = sizeof(unsigned long long) * 2 * kP2pMaxRanks * kP2pFlagStride;
 
-void p2p_fill_args(sfmba_handle* h, P2pArgs& a) {
-    auto& p = h->p2p;
-    for (int q = 0; q < p.world; ++q) { a.data[q] = p.data[q]; a.flags[q] = p.flags[q]; }
-    a.rank = p.rank; a.world = p.world; a.stride = p.stride;
-    a.seq = reinterpret_cast<unsigned long long*>(p.words + 2);
-    a.ticket = p.words; a.error = p.words + 1;
+long long p2p_timeout(sfmba_handle* h) {
     // Ticks of the 100 MHz wall clock.  The FIRST collective of a solve is the rendezvous of ranks that entered
     // sfmba_solve at different times (Python skew, first-use code-object loads; no barrier is required before a solve):
     // it waits up to 60 s.  Steady state: 30 s -- the devices run in lockstep there, but a host thread that stalls between
     // two launches (a cold page of a runtime library on a fresh machine, a descheduled process) holds its peers up for as
     // long; the bound only decides how soon a dead peer is noticed (round 4: 3 s gave one spurious failure in a first solve
     // on a fresh box).
-    a.timeout = p.first_in_solve ? kP2pFirstTicks : kP2pSteadyTicks;
-    if (h->dbg.p2p_timeout_ms > 0) a.timeout = 100000ll * h->dbg.p2p_timeout_ms;       // test hook
-    p.first_in_solve = false;
+    const long long ticks = h->p2p.first_in_solve ? kP2pFirstTicks : kP2pSteadyTicks;
+    h->p2p.first_in_solve = false;
+    return h->dbg.p2p_timeout_ms > 0 ? 100000ll * h->dbg.p2p_timeout_ms : ticks;       // test hook
+}
+void p2p_fill_args(sfmba_handle* h, P2pArgs& a) {
+    auto& p = h->p2p;
+    for (int q = 0; q < p.world; ++q) { a.data[q] = p.data[q]; a.flags[q] = p.flags[q]; }
+    a.rank = p.rank; a.world = p.world; a.stride = p.stride;
+    a.seq = reinterpret_cast<unsigned long long*>(p.words + 2);
+    a.ticket = p.words; a.error = p.words + 1;
+    a.timeout = p2p_timeout(h);
 }
 
+// ==== the form decision =================================================================================================
+// Problem stage.  sfmba_set_problem calls it twice: once to plan the build of the tables, with the facts that only the
+// build can find assumed favourable, and once at its end with the facts as found; that result stays in h->forms.
+//   form                      | runs when                                                        | overriding option
+//   packed_upload             | N >= 65536, C <= 65535 and every pixel an int16 integer          | packed_upload = 1 / 0
+//   cm_device                 | N >= 65536 and the camera counters fit the LDS                   | cm_device = 1 / 0
+//   cam_chunk_len             | max(4096, N / (2 CUs))                                           | cam_chunk = length
+//   xcd_b (table of pass B)   | P >= 250000                                                      | xcd_chunks = 1 / 0
+//   lds_tab (K1, K2)          | the camera table fits the LDS                                    | tab_lds = 0
+//   lds_vec (sweeps)          | a camera vector fits the LDS                                     | vec_lds = 0
+//   pass A: sweep_rc          | C <= kRcMaxCams and its table fits the LDS: blocks recomputed    | sweep_rc = 0 (stored J), 2 (sweep_rc_g)
+//           sweep_rc_g        | else: blocks recomputed from a table in global memory            | sweep_rc = 0 (stored J)
+//           stored Jacobian   | on request only                                                  |
+//   round_blocks              | stored Jacobian in fp32 storage (passes B, K3, rhs round alike)  | --
+//   pass B                    | k_cam_schur_w over the XCD-aware table if xcd_b, else k_cam_schur over the chunk list; fp32 records
+//                             | if mixed_b, blocks rounded to fp32 if round_blocks, else fp64     | (those of xcd_b, mixed_b)
+//   pcg_fused                 | (lds_vec or sweep_rc) and C <= 1024: update in pass A's prologue | pcg_fused = 0
+//   mixed (pass A fp32 ops)   | fp32 storage and a recomputing pass A                            | pcg_mixed = 1 / 0
+//   mixed_b (pass B too)      | mixed                                                            | pcg_mixed_b = 0
+//   jfree                     | on request, with lds_tab                                         | jfree = 1
+//   dense                     | 6 C <= kDenseMaxN and at most 2^26 pair-list entries             | dense = 0
+//   use_rhsrec (rhs pass)     | P >= 250000                                                      | rhsrec = 1 / 0
+// So cfg4 (1000 cameras / 100k points / 1M observations, fp64): pass A k_point_sweep_rc<FUSED> (sweep_rc, pcg_fused), pass B
+// k_cam_schur over the chunk list; cfg5 in fp32 storage (5000 / 1M / 10M): pass A k_rc_table32 + k_point_sweep_rc32 (sweep_rc_g,
+// mixed), pass B k_cam_schur_w on fp32 records over the XCD-aware table + k_cam_combine_w (xcd_b, mixed_b), rhs pass from rhsrec.
+struct ProblemFacts {                    // what only the build of the tables can tell
+    bool pixels_int16 = true;            // every pixel coordinate is an int16 integer
+    bool cam_multi = false;              // some camera's list was cut into several chunks
+    int64_t pair_entries = 0;            // length of the pair lists of the dense path
+};
+Forms decide_problem_forms(int64_t C, int64_t P, int64_t N, bool f32, int n_cu, const ProblemFacts& facts, const Debug& dbg) {
+    const auto by_size = [](int option, bool fits) { return option == 1 || (option != 0 && fits); };     // 1 forces, 0 forbids
+    Forms f;
+    f.packed_upload = by_size(dbg.packed_upload, N >= 65536) && C <= 65535 && facts.pixels_int16;   // (small: two launches > the bytes)
+    // (from 64k observations on: below that the three launches cost more than the host's sort)
+    f.cm_device = by_size(dbg.cm_device, N >= 65536) && sizeof(int) * (size_t)C <= kLdsDynMax;
+    // a camera of up to 4096 observations is one workgroup (16 per lane) and needs no combine launch
+    f.cam_chunk_len = dbg.cam_chunk > 0 ? dbg.cam_chunk : std::max<int64_t>(4096, (N + 2 * n_cu - 1) / (2 * n_cu));
+    f.cam_multi = facts.cam_multi;
+    f.xcd_b = by_size(dbg.xcd_chunks, P >= 250000);
+    f.lds_tab = (size_t)C * kCamRow * sizeof(double) <= kLdsDynMax && dbg.tab_lds != 0;
+    f.lds_vec = (size_t)C * 6 * sizeof(double) <= kLdsDynMax && dbg.vec_lds != 0;
+    f.sweep_rc = C <= kRcMaxCams && (size_t)C * kRcRow * sizeof(double) <= kLdsDynMax && dbg.sweep_rc != 0 && dbg.sweep_rc != 2;
+    f.sweep_rc_g = !f.sweep_rc && dbg.sweep_rc != 0;
+    f.round_blocks = f32 && !f.sweep_rc && !f.sweep_rc_g;
+    f.pcg_fused = (f.lds_vec || f.sweep_rc) && C <= kSweepThreads && dbg.pcg_fused != 0;
+    // fp32 operands in the implicit Schur product: with fp32 storage (BASELINE config 5 names it), or on request
+    f.mixed = (f.sweep_rc || f.sweep_rc_g) && by_size(dbg.pcg_mixed, f32);
+    f.mixed_b = f.mixed && dbg.pcg_mixed_b != 0;
+    f.jfree = dbg.jfree == 1 && f.lds_tab;
+    f.dense = 6 * C <= kDenseMaxN && dbg.dense != 0 && facts.pair_entries <= ((int64_t)1 << 26);   // (very long tracks: the pair lists would not pay)
+    // One 128-byte gather record per point for k_cam_rhs_diag pays once the point tables no longer sit in the L2s
+    // (1M points: 432 -> 188 us); at 100k points the two 4.8 MB tables it replaces are L2-resident and k_prep's 11 MB of
+    // extra writes cost what the pass gains (DESIGN.md section 5)
+    f.use_rhsrec = by_size(dbg.rhsrec, P >= 250000);
+    return f;
+}
+
+// Solve stage, at the start of every compute call (begin_compute): the transport is attached between sfmba_set_problem
+// and the call, and these options are read live.  Nothing it reads changes inside a call: a direct link that fails is
+// closed by sfmba_solve_from only after the solve has returned.
+//   spread = several ranks, cam_multi or xcd_b: the sums of a camera come from several workgroups
+//   link   = direct link, single-chunk cameras on every rank, and few cameras where ranks share a GPU (note below)
+//   local  = pcg_local != 0, precond != 0 and a PCG form with per-camera bookkeeping (pcg_fused or sweep_rc_g)
+//   form                      | runs when                                                        | overriding option
+//   precond (Schur diagonal)  | always                                                           | precond = 0
+//   K3, rhs pass: xcd_cam     | xcd_b: XCD-aware table, one wave per chunk, sums by collective   | xcd_cam = 0
+//                 cam_inline  | link, single-chunk cameras, not xcd_cam: exchanged per camera    | pcg_inline = 0
+//                 own_inverse | single-chunk cameras and (one rank or cam_inline)                | --
+//   product reduced: pcg_inline, inside pass B camera by camera | link, local, not cam_multi / xcd_b | pcg_inline = 0, pcg_split = 1
+//     else pcg_split: k_p2p_pcg, or collective + k_pcg_tail     | local and spread                   | pcg_split = 0 (1: not spread too)
+//     else collective + k_pcg_update (fused: pass A's prologue) | spread; one rank: nothing to reduce |
+//   pcg_local, pcg_local2     | pcg_fused / sweep_rc_g without it; not spread, or split / inline | pcg_local = 0
+//   skip_last                 | pcg_fused and (one rank or pcg_inline): 2 if pcg_local, lds_vec and not jfree, else 1 | pcg_skip_last = 0, 2 (-> 1)
+//   dense_solve               | dense and one rank                                               | dense = 0
+//   quick_start, spec_scale, cost_rider | one rank                     | start_handoff = 0 or cost_rider = 0; spec_scale = 0; cost_rider = 0
+//   early_download            | the copy stream exists                                           | early_download = 0
+// So cfg4 on one rank: not spread, pcg_local -- pass B does the per-camera bookkeeping and nothing is reduced; cfg5: spread by
+// xcd_b, pcg_split with pcg_local2 -- k_pcg_tail behind k_cam_combine_w, then k_pcg_update_local; cfg4 / 8 over the direct link:
+// pcg_inline with pcg_local -- the product is summed over the ranks inside pass B, K3 and the rhs pass exchange per camera.
 // sharded over the direct link, every camera a single chunk: per-camera sums are all-reduced by the workgroup that
 // forms them (CamExchange) instead of by a collective launch behind the kernel
 // -- on EVERY rank (the chunking is a property of the shard; ranks that disagreed would wait for each other in different
-// kernels), and practically never between ranks that SHARE one GPU (p2p_inline_ok).  With a GPU per rank a waiting
+// kernels), and practically never between ranks that SHARE one GPU (`link` of decide_solve_forms).  With a GPU per rank a waiting
 // workgroup costs its own device a slot and nothing else.  On a shared device the ranks compete for the CUs: a camera
 // workgroup that waits for its peer holds registers on its CU, and the peer -- if it is one kernel behind, which two
 // processes drift apart by easily -- first has to run pass A, whose 1024-thread workgroups need the whole register file of
@@ -489,22 +603,41 @@ void p2p_fill_args(sfmba_handle* h, P2pArgs& a) {
 // they are one or a few workgroups).  So rehearsals on one device take the exchange inside the kernels only while the
 // waiting workgroups of all other ranks leave half the CUs alone -- small tests -- and the collective launches otherwise.
 constexpr int64_t kSharedDeviceCams = 128;         // (ranks - 1) x cameras: at most half of the 256 CUs hold a waiting workgroup
-bool p2p_inline_ok(const sfmba_handle* h) {
+void decide_solve_forms(sfmba_handle* h) {
+    Forms& f = h->forms;
+    const Debug& d = h->dbg;
     const auto& p = h->p2p;
-    return p.ready && !p.any_multi && !(p.shared_device > 1 && h->C * (p.shared_device - 1) > kSharedDeviceCams);
+    f.one_rank = !multi_rank(h);
+    const bool link = p.ready && !p.any_multi && !(p.shared_device > 1 && h->C * (p.shared_device - 1) > kSharedDeviceCams);
+    const bool spread = !f.one_rank || f.cam_multi || f.xcd_b;
+    const bool local = d.pcg_local != 0 && d.precond != 0 && (f.pcg_fused || f.sweep_rc_g);
+    f.precond = d.precond != 0;
+    f.xcd_cam = f.xcd_b && d.xcd_cam != 0;
+    f.cam_inline = link && !f.cam_multi && !f.xcd_cam && d.pcg_inline != 0;
+    f.own_inverse = !f.cam_multi && (f.one_rank || f.cam_inline);
+    f.pcg_inline = link && !f.cam_multi && !f.xcd_b && d.pcg_inline != 0 && local && d.pcg_split != 1;
+    f.pcg_split = !f.pcg_inline && local && (spread ? d.pcg_split != 0 : d.pcg_split == 1);
+    const bool own_cameras = !spread || f.pcg_split || f.pcg_inline;
+    f.pcg_local = f.pcg_fused && d.pcg_local != 0 && own_cameras;
+    f.pcg_local2 = !f.pcg_fused && f.sweep_rc_g && d.pcg_local != 0 && own_cameras;
+    // (several ranks: only where the product's exchange sits inside pass B -- every rank then takes the same
+    // decision from the same record, and a launch that is not enqueued exchanges nothing on any of them)
+    f.skip_last = !(f.pcg_fused && (f.one_rank || f.pcg_inline) && d.pcg_skip_last != 0) ? 0
+                  : (f.pcg_local && f.lds_vec && !f.jfree && d.pcg_skip_last != 2) ? 2 : 1;
+    f.dense_solve = f.dense && f.one_rank;
+    // (single rank only -- with several ranks the cost and the scale sums pass through collectives between these launches)
+    f.quick_start = f.one_rank && d.start_handoff != 0 && d.cost_rider != 0;
+    f.spec_scale = f.one_rank && d.spec_scale != 0;
+    f.cost_rider = d.cost_rider != 0;
+    f.early_download = h->copy_stream != nullptr && d.early_download != 0;
 }
-// K3 and the rhs pass over the XCD-aware chunk table, one wave per chunk (k_cam_blocks_w, k_cam_rhs_diag_w)
-bool xcd_cam(const sfmba_handle* h) { return h->xcd_b && h->dbg.xcd_cam != 0; }
-bool cam_inline(const sfmba_handle* h) { return p2p_inline_ok(h) && !h->cam_multi && !xcd_cam(h) && h->dbg.pcg_inline != 0; }
 
 CamExchange cam_exchange(sfmba_handle* h) {
     CamExchange cx{};
     auto& p = h->p2p;
     for (int q = 0; q < p.world; ++q) cx.data[q] = p.camdata[q];
     cx.rank = p.rank; cx.world = p.world; cx.C = (int)h->C; cx.error = p.words + 1;
-    cx.timeout = p.first_in_solve ? kP2pFirstTicks : kP2pSteadyTicks;      // (as p2p_fill_args)
-    if (h->dbg.p2p_timeout_ms > 0) cx.timeout = 100000ll * h->dbg.p2p_timeout_ms;
-    p.first_in_solve = false;
+    cx.timeout = p2p_timeout(h);
     return cx;
 }
 
@@ -567,12 +700,12 @@ int set_lds(sfmba_handle* h, Kern k, size_t bytes) {
 double* vinv_ptr(const sfmba_handle* h) { return kVinvInRec < 0 ? h->Vinv.as<double>() : h->rec + kVinvInRec; }
 
 MixedPrep mixed_prep(const sfmba_handle* h, const double* tab) {
-    if (!h->mixed) return MixedPrep{nullptr, nullptr, nullptr, nullptr, Origin{0.0, 0.0, 0.0}};
+    if (!h->forms.mixed) return MixedPrep{nullptr, nullptr, nullptr, nullptr, Origin{0.0, 0.0, 0.0}};
     return MixedPrep{tab, h->rt32.as<float>(), h->rec32.as<float>(), h->rtd.as<double>(), h->origin};
 }
 // fp32 operands of (x, tab) outside a solve (inside, k_prep writes them)
 int launch_mixed_prep(sfmba_handle* h, const double* x, const double* tab) {
-    if (!h->mixed) return 0;
+    if (!h->forms.mixed) return 0;
     const int bc = (int)((h->C + 255) / 256), bp = (int)((h->P + 255) / 256);
     hipLaunchKernelGGL(k_mixed_prep, dim3(bc + bp), dim3(256), 0, h->stream, mixed_prep(h, tab), x + 6 * h->C, (int)h->C, (int)h->P, bc);
     LAUNCHED(h);
@@ -602,29 +735,19 @@ void report_stall(const sfmba_handle* h, const char* where, double seconds) {   
     if (h->dbg.trace_stalls && seconds > 2e-3) fprintf(stderr, "sfmba: waited %.2f ms in %s\n", 1e3 * seconds, where);
 }
 
-int wait_event(sfmba_handle* h, hipEvent_t ev) {      // as wait_stream, for one event of the copy stream
+// `ev` null: the handle's stream; else one event of the copy stream
+int wait_stream(sfmba_handle* h, hipEvent_t ev = nullptr) {
+    const char* what = ev ? "hipEventQuery" : "hipStreamQuery";
     const double t0 = now_s();
     for (;;) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e == hipSuccess) { report_stall(h, "wait_event", now_s() - t0); return 0; }
-        if (e != hipErrorNotReady) return fail(h, -3, "hipEventQuery failed: %s", hipGetErrorString(e));
-        if (now_s() - t0 > 0.05) break;
-    }
-    HIPCHK(h, hipEventSynchronize(ev));
-    report_stall(h, "wait_event (blocking)", now_s() - t0);
-    return 0;
-}
-
-int wait_stream(sfmba_handle* h) {
-    const double t0 = now_s();
-    for (;;) {
-        const hipError_t e = hipStreamQuery(h->stream);
-        if (e == hipSuccess) { report_stall(h, "wait_stream", now_s() - t0); return 0; }
-        if (e != hipErrorNotReady) return fail(h, -3, "hipStreamQuery failed: %s", hipGetErrorString(e));
+        const hipError_t e = ev ? hipEventQuery(ev) : hipStreamQuery(h->stream);
+        if (e == hipSuccess) { report_stall(h, ev ? "wait_event" : "wait_stream", now_s() - t0); return 0; }
+        if (e != hipErrorNotReady) return fail(h, -3, "%s failed: %s", what, hipGetErrorString(e));
         if (now_s() - t0 > 0.05) break;          // long wait: stop burning the core
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    report_stall(h, "wait_stream (blocking)", now_s() - t0);
+    if (ev) HIPCHK(h, hipEventSynchronize(ev));
+    else HIPCHK(h, hipStreamSynchronize(h->stream));
+    report_stall(h, ev ? "wait_event (blocking)" : "wait_stream (blocking)", now_s() - t0);
     return 0;
 }
 
@@ -698,15 +821,31 @@ PointBlocksOut point_blocks_out(sfmba_handle* h) {
     return PointBlocksOut{h->V.as<double>(), h->gp.as<double>(), h->edge.as<double>()};
 }
 
-template <bool LDS, bool JAC, bool STORE_R, bool F32, bool BLOCKS>
-int launch_resjac_b(sfmba_handle* h, const double* x, const double* tab, int grid, size_t lds,
-                    hipEvent_t ev0, hipEvent_t ev1) {
-    const double* pts = x + 6 * h->C;
-    const PointBlocksOut pb = BLOCKS ? point_blocks_out(h) : PointBlocksOut{nullptr, nullptr, nullptr};
-    auto kern = k_resjac<LDS, JAC, STORE_R, F32, BLOCKS>;
-    if constexpr (JAC && BLOCKS && LDS && STORE_R) {           // J-free iteration: the blocks feed the point sums only
-        if (h->jfree) kern = k_resjac<LDS, JAC, STORE_R, F32, BLOCKS, false>;
+// the instantiation of K1: BLOCKS only with JAC, and without the Jacobian stores (J-free iteration: the blocks feed the
+// point sums only) only where that iteration can run
+template <bool LDS, bool JAC, bool STORE_R, bool F32>
+auto resjac_kernel(bool blocks, bool jfree) {
+    if constexpr (JAC) {
+        if constexpr (LDS && STORE_R) { if (blocks && jfree) return k_resjac<LDS, JAC, STORE_R, F32, true, false>; }
+        if (blocks) return k_resjac<LDS, JAC, STORE_R, F32, true>;
     }
+    return k_resjac<LDS, JAC, STORE_R, F32, false>;
+}
+
+// `blocks`: the Jacobian launch also leaves V_p, g_p of x (the point half of the normal equations; the camera half
+// and the pieces of runs cut by tile boundaries follow in launch_normal_blocks)
+template <bool JAC, bool STORE_R>
+int launch_resjac(sfmba_handle* h, const double* x, const double* tab, int* nparts,
+                  hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, bool blocks = JAC) {
+    const Forms& f = h->forms;
+    const int grid = grid_1d(h->N, kSweepThreads, h->n_cu);
+    *nparts = grid;
+    // the camera table staged in LDS, or its rows gathered through the LDS
+    const size_t lds = f.lds_tab ? (size_t)h->C * kCamRow * sizeof(double) : sizeof(double) * kRowSlabDoubles * kWavesPerSweepBlock;
+    auto kern = f.lds_tab ? (h->f32 ? resjac_kernel<true, JAC, STORE_R, true>(blocks, f.jfree) : resjac_kernel<true, JAC, STORE_R, false>(blocks, f.jfree))
+                          : (h->f32 ? resjac_kernel<false, JAC, STORE_R, true>(blocks, false) : resjac_kernel<false, JAC, STORE_R, false>(blocks, false));
+    const double* pts = x + 6 * h->C;
+    const PointBlocksOut pb = (JAC && blocks) ? point_blocks_out(h) : PointBlocksOut{nullptr, nullptr, nullptr};
     CHK(set_lds(h, kern, lds));
     if (ev0) {
         hipExtLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), (uint32_t)lds, h->stream, ev0, ev1, 0u, tab, pts,
@@ -722,346 +861,226 @@ int launch_resjac_b(sfmba_handle* h, const double* x, const double* tab, int gri
     LAUNCHED(h);
     return 0;
 }
-template <bool LDS, bool JAC, bool STORE_R, bool F32>
-int launch_resjac_v(sfmba_handle* h, const double* x, const double* tab, int grid, size_t lds,
-                    hipEvent_t ev0, hipEvent_t ev1, bool blocks) {
-    if constexpr (JAC) {
-        if (blocks) return launch_resjac_b<LDS, JAC, STORE_R, F32, true>(h, x, tab, grid, lds, ev0, ev1);
-    }
-    return launch_resjac_b<LDS, JAC, STORE_R, F32, false>(h, x, tab, grid, lds, ev0, ev1);
-}
 
-// `blocks`: the Jacobian launch also leaves V_p, g_p of x (the point half of the normal equations; the camera half
-// and the pieces of runs cut by tile boundaries follow in launch_normal_blocks)
-template <bool JAC, bool STORE_R>
-int launch_resjac(sfmba_handle* h, const double* x, const double* tab, int* nparts,
-                  hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, bool blocks = JAC) {
-    const int grid = grid_1d(h->N, kSweepThreads, h->n_cu);
-    *nparts = grid;
-    const size_t lds = (size_t)h->C * kCamRow * sizeof(double);
-    if (h->lds_tab)
-        return h->f32 ? launch_resjac_v<true, JAC, STORE_R, true>(h, x, tab, grid, lds, ev0, ev1, blocks)
-                      : launch_resjac_v<true, JAC, STORE_R, false>(h, x, tab, grid, lds, ev0, ev1, blocks);
-    const size_t slabs = sizeof(double) * kRowSlabDoubles * kWavesPerSweepBlock;       // rows gathered through the LDS
-    return h->f32 ? launch_resjac_v<false, JAC, STORE_R, true>(h, x, tab, grid, slabs, ev0, ev1, blocks)
-                  : launch_resjac_v<false, JAC, STORE_R, false>(h, x, tab, grid, slabs, ev0, ev1, blocks);
+// "sum the partial rows [0, n) of `part`, one column, into scalar s": as a rider workgroup of the launch behind the
+// producer (Piggyback), or as a k_finish launch of its own (launch_finish)
+Piggyback sum_rider(sfmba_handle* h, const double* part, int n, int s) {
+    Piggyback pb{part, h->scal(), FinishJob{}, 1, 1, 0};
+    pb.job.row0[0] = 0; pb.job.nrows[0] = n;
+    for (int k = 0; k < kFinishCols; ++k) { pb.job.slot[0][k] = k == 0 ? s : -1; pb.job.slot[1][k] = -1; }
+    return pb;
 }
-
-// sum of `nparts` partial rows of width nq into the exchange scalars starting at slot `slot`
-int launch_finish(sfmba_handle* h, const double* part, int nparts, int nq, int slot) {
-    FinishJob job{};
-    job.row0[0] = 0; job.nrows[0] = nparts;
-    for (int k = 0; k < kFinishCols; ++k) { job.slot[0][k] = slot + k; job.slot[1][k] = -1; }
-    hipLaunchKernelGGL(k_finish, dim3(1), dim3(64 * nq), 0, h->stream, part, job, nq, 0, h->scal(), h->skip,
-                       h->post);
+// the sums of a rider as a launch of their own: one workgroup per slice, one wave per quantity
+int launch_finish(sfmba_handle* h, const Piggyback& pb, const double* skip = nullptr, const Mailbox& post = Mailbox{}) {
+    hipLaunchKernelGGL(k_finish, dim3(pb.ny), dim3(64 * pb.nq), 0, h->stream, pb.part, pb.job, pb.nq, pb.first_sum, pb.out, skip, post);
     LAUNCHED(h);
     return 0;
 }
 
-// the two-slice (cameras | points) reduction of k_update_scale; the point slice
-// publishes only quantities [q_lo, q_hi] (the others keep their already rank-reduced values)
-FinishJob slices_job(const sfmba_handle* h, int q_lo, int q_hi) {
+// the two-slice (cameras | points) reduction of k_update_scale; the point slice publishes only q0..q4 (the
+// others keep their already rank-reduced values)
+FinishJob slices_job(const sfmba_handle* h) {
     FinishJob job{};
     job.row0[0] = 0;         job.nrows[0] = h->red_bc;
     job.row0[1] = h->red_bc; job.nrows[1] = h->red_grid - h->red_bc;
-    for (int k = 0; k < kFinishCols; ++k) { job.slot[0][k] = -1; job.slot[1][k] = -1; }
-    for (int k = 0; k < kNQ; ++k) {
-        job.slot[0][k] = kCamSlot + k;
-        job.slot[1][k] = (k >= q_lo && k <= q_hi) ? kPointSlot[k] : -1;
+    for (int k = 0; k < kFinishCols; ++k) {
+        job.slot[0][k] = k < kNQ ? kCamSlot + k : -1;
+        job.slot[1][k] = k <= 4 ? kPointSlot[k] : -1;
     }
     return job;
 }
-Piggyback slices_rider(sfmba_handle* h, int q_lo, int q_hi) {
-    return Piggyback{h->part.as<double>(), h->scal(), slices_job(h, q_lo, q_hi), 2, kNQ, 1};
-}
-
-int launch_finish_slices(sfmba_handle* h, int q_lo, int q_hi) {
-    const FinishJob job = slices_job(h, q_lo, q_hi);
-    hipLaunchKernelGGL(k_finish, dim3(2), dim3(64 * kNQ), 0, h->stream, h->part.as<double>(), job, kNQ, 1, h->scal(),
-                       (const double*)nullptr, Mailbox{});
-    LAUNCHED(h);
-    return 0;
-}
+Piggyback slices_rider(sfmba_handle* h) { return Piggyback{h->part.as<double>(), h->scal(), slices_job(h), 2, kNQ, 1}; }
 
 CamMajor cam_major(const sfmba_handle* h) {
     return CamMajor{h->cam_chunks.as<int4>(), h->cm_pt.as<int>(), h->cm_uv.as<double>()};
 }
+CamMajor cam_major_b(const sfmba_handle* h) {           // the XCD-aware table; its kernels take n_chunks_b / kWaveChunkCams workgroups
+    return CamMajor{h->cam_chunks_b.as<int4>(), h->cm_pt.as<int>(), h->cm_uv.as<double>()};
+}
 
 // chunk rows of cameras with several chunks -> out[c * cs + col * ks]
-int launch_cam_combine(sfmba_handle* h, int ncols, double* out, int cs, int ks, const double* skip, const int* done,
-                       bool table_b = false) {
-    if (!(table_b ? h->xcd_b : h->cam_multi)) return 0;
+int launch_cam_combine(sfmba_handle* h, int ncols, double* out, int cs, int ks, const double* skip, const int* done) {
+    if (!h->forms.cam_multi) return 0;
     hipLaunchKernelGGL(k_cam_combine, dim3((int)((h->C * ncols + 255) / 256)), dim3(256), 0, h->stream,
-                       (table_b ? h->cam_chunk_ptr_b : h->cam_chunk_ptr).as<int>(), h->cam_partial.as<double>(), (int)h->C, ncols,
-                       out, cs, ks, skip, done);
+                       h->cam_chunk_ptr.as<int>(), h->cam_partial.as<double>(), (int)h->C, ncols, out, cs, ks, skip, done);
+    LAUNCHED(h);
+    return 0;
+}
+// the same for the eight rows per camera of the XCD-aware table
+template <int NCOLS>
+int launch_cam_combine_w(sfmba_handle* h, double* out, int cs, int ks, const int* done, const double* skip) {
+    hipLaunchKernelGGL(k_cam_combine_w<NCOLS>, dim3((unsigned)((NCOLS * h->C + 255) / 256)), dim3(256), 0, h->stream,
+                       (const double*)h->cam_partial.as<double>(), (int)h->C, out, cs, ks, done, skip);
     LAUNCHED(h);
     return 0;
 }
 
-// K3 at (x, tab): [U_c | g_c] over the camera-major order, blocks recomputed from the camera table and the point
+// K3 at (tab, rec): [U_c | g_c] over the camera-major order, blocks recomputed from the camera table and the point
 // records.  V_p, g_p were left by the residual+Jacobian launch at the same x (launch_resjac with `blocks`), except
 // for the runs its 64-observation tiles cut: their pieces are added by a few extra workgroups of this launch.
 // `cost_parts` > 0: the launch also sums that many cost partials (left in `part` by the residual launch before it) into
 // scalar slot 0 and posts the hand-off `mb` (one more rider workgroup instead of a k_finish launch)
-template <bool F32>
-int launch_normal_blocks_v(sfmba_handle* h, const double* x, const double* tab, const double* rec, int cost_parts,
-                           const Mailbox& mb) {
-    (void)x;
+int launch_normal_blocks(sfmba_handle* h, const double* tab, const double* rec, int cost_parts = 0, const Mailbox& mb = Mailbox{}) {
+    const Forms& f = h->forms;
     const int tiles = (int)((h->N + 63) / 64);
-    const int riders = (tiles + kCamThreads - 1) / kCamThreads;
+    const int extra = (tiles + kCamThreads - 1) / kCamThreads + (cost_parts > 0 ? 1 : 0);
     CamExchange cx{};
-    if (cam_inline(h)) { cx = cam_exchange(h); ++h->p2p.calls; ++h->n_collectives; }
-    Piggyback fin{};
-    if (cost_parts > 0) {
-        fin = Piggyback{h->part.as<double>(), h->scal(), FinishJob{}, 1, 1, 0};
-        fin.job.row0[0] = 0; fin.job.nrows[0] = cost_parts;
-        for (int k = 0; k < kFinishCols; ++k) { fin.job.slot[0][k] = k; fin.job.slot[1][k] = -1; }
-    }
-    if (xcd_cam(h)) {                                           // many points: one wave per chunk of the XCD-aware table
-        const CamMajor cmb{h->cam_chunks_b.as<int4>(), h->cm_pt.as<int>(), h->cm_uv.as<double>()};
+    if (f.cam_inline) { cx = cam_exchange(h); ++h->p2p.calls; ++h->n_collectives; }
+    const Piggyback fin = cost_parts > 0 ? sum_rider(h, h->part.as<double>(), cost_parts, kCostSlot) : Piggyback{};
+    if (f.xcd_cam) {                                            // many points: one wave per chunk of the XCD-aware table
         const int wgrid = h->n_chunks_b / kWaveChunkCams;
-        hipLaunchKernelGGL((k_cam_blocks_w<F32>), dim3(wgrid + riders + (cost_parts > 0 ? 1 : 0)), dim3(kCamThreads), 0, h->stream,
-                           cmb, tab, rec, h->K, h->cam_partial.as<double>(), h->skip, wgrid,
+        hipLaunchKernelGGL(h->f32 ? k_cam_blocks_w<true> : k_cam_blocks_w<false>, dim3(wgrid + extra), dim3(kCamThreads), 0, h->stream,
+                           cam_major_b(h), tab, rec, h->K, h->cam_partial.as<double>(), h->skip, wgrid,
                            (const int*)h->pt_idx.as<int>(), (int)h->N, point_blocks_out(h), fin, mb);
         LAUNCHED(h);
-        hipLaunchKernelGGL(k_cam_combine_w<27>, dim3((unsigned)((27 * h->C + 255) / 256)), dim3(256), 0, h->stream,
-                           (const double*)h->cam_partial.as<double>(), (int)h->C, h->Ugc(), 27, 1, (const int*)nullptr,
-                           (const double*)h->skip);
-        LAUNCHED(h);
+        CHK(launch_cam_combine_w<27>(h, h->Ugc(), 27, 1, nullptr, h->skip));
         return exchange(h, h->Ugc(), 27 * h->C, 0);
     }
-    hipLaunchKernelGGL((k_cam_blocks<F32>), dim3(h->n_chunks + riders + (cost_parts > 0 ? 1 : 0)), dim3(kCamThreads), 0, h->stream,
+    hipLaunchKernelGGL(h->f32 ? k_cam_blocks<true> : k_cam_blocks<false>, dim3(h->n_chunks + extra), dim3(kCamThreads), 0, h->stream,
                        cam_major(h), tab, rec, h->K, h->Ugc(), h->cam_partial.as<double>(), h->skip, (int)h->n_chunks,
                        (const int*)h->pt_idx.as<int>(), (int)h->N, point_blocks_out(h), fin, mb, cx);
     LAUNCHED(h);
     CHK(launch_cam_combine(h, 27, h->Ugc(), 27, 1, h->skip, nullptr));
-    if (cx.world > 1 || cam_inline(h)) return 0;               // [U | g_c] was summed over the ranks camera by camera
+    if (f.cam_inline) return 0;                                 // [U | g_c] was summed over the ranks camera by camera
     return exchange(h, h->Ugc(), 27 * h->C, 0);
 }
-int launch_normal_blocks(sfmba_handle* h, const double* x, const double* tab, const double* rec, int cost_parts = 0,
-                         const Mailbox& mb = Mailbox{}) {
-    return h->f32 ? launch_normal_blocks_v<true>(h, x, tab, rec, cost_parts, mb)
-                  : launch_normal_blocks_v<false>(h, x, tab, rec, cost_parts, mb);
-}
 
-// Pass A of the implicit Schur product (z_p for every point).  Inside the two-kernel PCG: vin = base of the
-// vector sets, ctrl2 / L select the set on the device; standalone (test entry): vin = the vector itself,
+// Pass A of the implicit Schur product (z_p for every point).  FUSED: with the PCG update of the previous product in
+// its prologue (one launch; vin = base of the vector sets, ctrl2 = the control blocks).  Else inside the two-kernel
+// PCG the same vin / ctrl2, and L selects the set on the device; standalone (test entry): vin = the vector itself,
 // plane-major when it is staged in LDS, camera-major otherwise; ctrl2 = nullptr.
-int launch_point_sweep(sfmba_handle* h, const double* vin, const PcgCtrl* ctrl2, int L) {
-    const int grid = (h->n_ranges + kWavesPerSweepBlock - 1) / kWavesPerSweepBlock;
-    if (h->mixed && h->sweep_rc) {        // fp32 operands, table in LDS
-        const size_t lds = sizeof(float) * kRc32Row * (size_t)h->C;
-        auto kern = h->mixed_b ? k_point_sweep_rc32<false, false, false> : k_point_sweep_rc32<false, false, true>;
+template <bool FUSED>
+int launch_pass_a(sfmba_handle* h, const double* vin, const PcgCtrl* ctrl2, int L) {
+    const Forms& f = h->forms;
+    const dim3 grid((h->n_ranges + kWavesPerSweepBlock - 1) / kWavesPerSweepBlock), block(kSweepThreads);
+    const int C = (int)h->C;
+    const int *ci = h->cam_idx.as<int>(), *pi = h->pt_idx.as<int>();
+    const double *tab = h->tab, *pts = h->x + 6 * h->C, *vinv = vinv_ptr(h), *acc = h->acc();
+    const float* rt32 = h->rt32.as<float>();
+    PcgFused pf{};
+    if constexpr (FUSED)
+        pf = PcgFused{h->Dc.as<double>(), h->Minv.as<double>(), h->Ugc(), h->vecs.as<double>(), h->ctrl.as<PcgCtrl>(),
+                      h->pcg_tol, h->pcg_cap, (const double*)(h->scal() + kEtaSlot),
+                      f.pcg_local ? h->pcg_part.as<double>() : (double*)nullptr};
+    // the three families of pass A; `table`: the recomputing forms' table in global memory (null: built in LDS)
+    auto rc32 = [&](auto kern, size_t lds, const float* table) -> int {      // fp32 operands
         CHK(set_lds(h, kern, lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, step_table(h), (const int*)h->cam_idx.as<int>(),
-                           (const int*)h->pt_idx.as<int>(), (const double*)h->tab, (const float*)h->rt32.as<float>(), h->K, vin,
-                           (const double*)vinv_ptr(h), h->rec32.as<float>(), (const double*)h->acc(), (int)h->C, ctrl2, L,
-                           PcgFused{}, (const float*)nullptr, h->rec);
+        hipLaunchKernelGGL(kern, grid, block, lds, h->stream, step_table(h), ci, pi, tab, rt32, h->K, vin, vinv,
+                           h->rec32.as<float>(), acc, C, ctrl2, L, pf, table, h->rec);
         LAUNCHED(h);
         return 0;
-    }
-    if (h->mixed && h->sweep_rc_g) {      // fp32 operands, table in global memory
-        hipLaunchKernelGGL(k_rc_table32, dim3((unsigned)((h->C + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->tab,
-                           (const float*)h->rt32.as<float>(), vin, ctrl2, L, (int)h->C, h->rctab32.as<float>());
-        LAUNCHED(h);
-        const size_t slabs = sizeof(float) * kRow32SlabFloats * kWavesPerSweepBlock;
-        auto kern_g = h->mixed_b ? k_point_sweep_rc32<false, true, false> : k_point_sweep_rc32<false, true, true>;
-        CHK(set_lds(h, kern_g, slabs));
-        hipLaunchKernelGGL(kern_g, dim3(grid), dim3(kSweepThreads), slabs, h->stream, step_table(h),
-                           (const int*)h->cam_idx.as<int>(), (const int*)h->pt_idx.as<int>(), (const double*)h->tab,
-                           (const float*)h->rt32.as<float>(), h->K, vin, (const double*)vinv_ptr(h), h->rec32.as<float>(),
-                           (const double*)h->acc(), (int)h->C, ctrl2, L, PcgFused{}, (const float*)h->rctab32.as<float>(), h->rec);
-        LAUNCHED(h);
-        return 0;
-    }
-    if (h->sweep_rc) {                    // recomputing form: vin plane-major (or the base of the vector sets)
-        const size_t lds = sizeof(double) * kRcRow * (size_t)h->C;
-        auto kern = k_point_sweep_rc<false>;
+    };
+    auto rc = [&](auto kern, size_t lds, const double* table) -> int {       // blocks recomputed in fp64
         CHK(set_lds(h, kern, lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, step_table(h), (const int*)h->cam_idx.as<int>(),
-                           (const int*)h->pt_idx.as<int>(), (const double*)h->tab, (const double*)(h->x + 6 * h->C), h->K, vin,
-                           (const double*)vinv_ptr(h), h->rec, (const double*)h->acc(), (int)h->C, ctrl2, L,
-                           PcgFused{}, (const double*)nullptr);
+        hipLaunchKernelGGL(kern, grid, block, lds, h->stream, step_table(h), ci, pi, tab, pts, h->K, vin, vinv, h->rec, acc, C,
+                           ctrl2, L, pf, table);
         LAUNCHED(h);
         return 0;
-    }
-    if (h->sweep_rc_g) {                  // the same with its table in global memory: one small launch builds it
-        hipLaunchKernelGGL(k_rc_table, dim3((unsigned)((h->C + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->tab, vin,
-                           ctrl2, L, (int)h->C, h->rctab.as<double>());
-        LAUNCHED(h);
-        const size_t slabs = sizeof(double) * kRowSlabDoubles * kWavesPerSweepBlock;    // rows gathered through the LDS
-        auto kern_g = k_point_sweep_rc<false, true>;
-        CHK(set_lds(h, kern_g, slabs));
-        hipLaunchKernelGGL(kern_g, dim3(grid), dim3(kSweepThreads), slabs, h->stream, step_table(h),
-                           (const int*)h->cam_idx.as<int>(), (const int*)h->pt_idx.as<int>(), (const double*)h->tab,
-                           (const double*)(h->x + 6 * h->C), h->K, vin, (const double*)vinv_ptr(h), h->rec,
-                           (const double*)h->acc(), (int)h->C, ctrl2, L, PcgFused{}, (const double*)h->rctab.as<double>());
-        LAUNCHED(h);
-        return 0;
-    }
-    if (h->lds_vec) {
-        const size_t lds = sizeof(double) * 6 * (size_t)h->C;
-        auto kern = k_point_sweep<true, false>;
+    };
+    auto stored = [&](auto kern, size_t lds) -> int {                        // the stored Jacobian
         CHK(set_lds(h, kern, lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, step_table(h), obs_arrays(h), vin,
-                           vinv_ptr(h), h->rec, (const double*)h->acc(), (int)h->C, ctrl2, L, PcgFused{});
+        hipLaunchKernelGGL(kern, grid, block, lds, h->stream, step_table(h), obs_arrays(h), vin, vinv, h->rec, acc, C, ctrl2, L, pf);
+        LAUNCHED(h);
+        return 0;
+    };
+    if (f.mixed && f.sweep_rc)
+        return rc32(f.mixed_b ? k_point_sweep_rc32<FUSED, false, false> : k_point_sweep_rc32<FUSED, false, true>,
+                    sizeof(float) * kRc32Row * (size_t)C, nullptr);
+    if (f.sweep_rc) return rc(k_point_sweep_rc<FUSED>, sizeof(double) * kRcRow * (size_t)C, nullptr);
+    if constexpr (FUSED) {
+        return stored(k_point_sweep<true, true>, sizeof(double) * 6 * (size_t)C);
     } else {
-        hipLaunchKernelGGL((k_point_sweep<false, false>), dim3(grid), dim3(kSweepThreads), 0, h->stream, step_table(h),
-                           obs_arrays(h), vin, vinv_ptr(h), h->rec, (const double*)h->acc(),
-                           (int)h->C, ctrl2, L, PcgFused{});
+        if (f.mixed && f.sweep_rc_g) {        // table in global memory: one small launch builds it
+            hipLaunchKernelGGL(k_rc_table32, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, h->stream, tab, rt32, vin, ctrl2, L, C,
+                               h->rctab32.as<float>());
+            LAUNCHED(h);
+            return rc32(f.mixed_b ? k_point_sweep_rc32<false, true, false> : k_point_sweep_rc32<false, true, true>,
+                        sizeof(float) * kRow32SlabFloats * kWavesPerSweepBlock, h->rctab32.as<float>());
+        }
+        if (f.sweep_rc_g) {
+            hipLaunchKernelGGL(k_rc_table, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, h->stream, tab, vin, ctrl2, L, C,
+                               h->rctab.as<double>());
+            LAUNCHED(h);
+            return rc(k_point_sweep_rc<false, true>, sizeof(double) * kRowSlabDoubles * kWavesPerSweepBlock,    // rows gathered through the LDS
+                      h->rctab.as<double>());
+        }
+        return f.lds_vec ? stored(k_point_sweep<true, false>, sizeof(double) * 6 * (size_t)C) : stored(k_point_sweep<false, false>, 0);
     }
-    LAUNCHED(h);
-    return 0;
 }
-
-// pass A fused with the PCG update of the previous product (one launch)
-int launch_pcg_fused(sfmba_handle* h, int L) {
-    const int grid = (h->n_ranges + kWavesPerSweepBlock - 1) / kWavesPerSweepBlock;
-    PcgFused pf{h->Dc.as<double>(), h->Minv.as<double>(), h->Ugc(), h->vecs.as<double>(), h->ctrl.as<PcgCtrl>(),
-                h->pcg_tol, h->pcg_cap, (const double*)(h->scal() + kEtaSlot),
-                h->pcg_local ? h->pcg_part.as<double>() : (double*)nullptr};
-    if (h->mixed && h->sweep_rc) {
-        const size_t lds32 = sizeof(float) * kRc32Row * (size_t)h->C;
-        auto kern32 = h->mixed_b ? k_point_sweep_rc32<true, false, false> : k_point_sweep_rc32<true, false, true>;
-        CHK(set_lds(h, kern32, lds32));
-        hipLaunchKernelGGL(kern32, dim3(grid), dim3(kSweepThreads), lds32, h->stream, step_table(h),
-                           (const int*)h->cam_idx.as<int>(), (const int*)h->pt_idx.as<int>(), (const double*)h->tab,
-                           (const float*)h->rt32.as<float>(), h->K, (const double*)h->vecs.as<double>(),
-                           (const double*)vinv_ptr(h), h->rec32.as<float>(), (const double*)h->acc(), (int)h->C,
-                           (const PcgCtrl*)h->ctrl.as<PcgCtrl>(), L, pf, (const float*)nullptr, h->rec);
-        LAUNCHED(h);
-        return 0;
-    }
-    if (h->sweep_rc) {
-        const size_t lds_rc = sizeof(double) * kRcRow * (size_t)h->C;
-        auto kern_rc = k_point_sweep_rc<true>;
-        CHK(set_lds(h, kern_rc, lds_rc));
-        hipLaunchKernelGGL(kern_rc, dim3(grid), dim3(kSweepThreads), lds_rc, h->stream, step_table(h),
-                           (const int*)h->cam_idx.as<int>(), (const int*)h->pt_idx.as<int>(), (const double*)h->tab,
-                           (const double*)(h->x + 6 * h->C), h->K, (const double*)h->vecs.as<double>(),
-                           (const double*)vinv_ptr(h), h->rec, (const double*)h->acc(), (int)h->C,
-                           (const PcgCtrl*)h->ctrl.as<PcgCtrl>(), L, pf, (const double*)nullptr);
-        LAUNCHED(h);
-        return 0;
-    }
-    const size_t lds = sizeof(double) * 6 * (size_t)h->C;
-    auto kern = k_point_sweep<true, true>;
-    CHK(set_lds(h, kern, lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, step_table(h), obs_arrays(h),
-                       (const double*)h->vecs.as<double>(), vinv_ptr(h), h->rec,
-                       (const double*)h->acc(), (int)h->C, (const PcgCtrl*)h->ctrl.as<PcgCtrl>(), L, pf);
-    LAUNCHED(h);
-    return 0;
-}
-
 // Pass B (camera-major): MODE 0  acc = sum Jc^T (Jc v - Jp z) with z from pass A; MODE 1  acc = -sum Jc^T Jp e.
 // ctrl_done / set: see k_cam_schur.
 template <int MODE>
 int launch_cam_schur(sfmba_handle* h, const double* vin, const PcgCtrl* ctrl_done, int set, bool local = false,
                      bool inline_exchange = false) {
+    const Forms& f = h->forms;
     const PcgLocal pl{h->Dc.as<double>(), h->Minv.as<double>(), h->vecs.as<double>(),
                       local ? h->pcg_part.as<double>() : (double*)nullptr};
     CamExchange cx{};
     if (MODE == 0 && inline_exchange) { cx = cam_exchange(h); ++h->p2p.calls; ++h->n_collectives; }
-    // MODE 0 with the XCD-aware table: chunk 8 c + k runs on XCD k and gathers records of point range k only
-    const bool tb = MODE == 0 && h->xcd_b;
-    const CamMajor cm = tb ? CamMajor{h->cam_chunks_b.as<int4>(), h->cm_pt.as<int>(), h->cm_uv.as<double>()} : cam_major(h);
-    const int grid = tb ? h->n_chunks_b : h->n_chunks;
     const MixedB mxb{h->rtd.as<double>()};
-    if (tb) {                                       // one wave per chunk of the XCD-aware table
-        const bool round = h->f32 && !h->sweep_rc && !h->sweep_rc_g;
-        if (round) return fail(h, -1, "XCD-aware chunks need the recomputing form of pass A");
-        const int wgrid = h->n_chunks_b / kWaveChunkCams;
-        if (h->mixed_b)
-            hipLaunchKernelGGL((k_cam_schur_w<true>), dim3(wgrid), dim3(kCamThreads), 0, h->stream, cm, (const double*)h->tab,
-                               reinterpret_cast<const double*>(h->rec32.as<float>()), h->K, vin, (int)h->C,
-                               h->cam_partial.as<double>(), ctrl_done, set, mxb);
-        else
-            hipLaunchKernelGGL((k_cam_schur_w<false>), dim3(wgrid), dim3(kCamThreads), 0, h->stream, cm, (const double*)h->tab,
-                               (const double*)h->rec, h->K, vin, (int)h->C, h->cam_partial.as<double>(), ctrl_done, set, mxb);
+    // fp32 operands: the same rounded R, T - o, X - o, a', u_T as pass A
+    const bool mixed = MODE == 0 && f.mixed_b;
+    const double* rec = mixed ? reinterpret_cast<const double*>(h->rec32.as<float>()) : (const double*)h->rec;
+    const int* done = ctrl_done ? &ctrl_done->done : nullptr;
+    // MODE 0 with the XCD-aware table: chunk 8 c + k runs on XCD k and gathers records of point range k only, one wave per chunk
+    if (MODE == 0 && f.xcd_b) {
+        if (f.round_blocks) return fail(h, -1, "XCD-aware chunks need the recomputing form of pass A");
+        hipLaunchKernelGGL(mixed ? k_cam_schur_w<true> : k_cam_schur_w<false>, dim3(h->n_chunks_b / kWaveChunkCams), dim3(kCamThreads), 0,
+                           h->stream, cam_major_b(h), (const double*)h->tab, rec, h->K, vin, (int)h->C, h->cam_partial.as<double>(),
+                           ctrl_done, set, mxb);
         LAUNCHED(h);
-        hipLaunchKernelGGL(k_cam_combine_w<6>, dim3((unsigned)((6 * h->C + 255) / 256)), dim3(256), 0, h->stream,
-                           (const double*)h->cam_partial.as<double>(), (int)h->C, h->acc(), 1, (int)h->C,
-                           ctrl_done ? &ctrl_done->done : (const int*)nullptr, (const double*)nullptr);
-        LAUNCHED(h);
-        return 0;
+        return launch_cam_combine_w<6>(h, h->acc(), 1, (int)h->C, done, nullptr);
     }
-    if (h->f32 && !h->sweep_rc && !h->sweep_rc_g)   // pass A applies the stored fp32 blocks: pass B rounds its own the same way
-        hipLaunchKernelGGL((k_cam_schur<MODE, true>), dim3(grid), dim3(kCamThreads), 0, h->stream, cm,
-                           (const double*)h->tab, (const double*)h->rec, h->K, vin, (int)h->C, h->acc(),
-                           h->cam_partial.as<double>(), ctrl_done, set, pl, mxb, cx);
-    else if (MODE == 0 && h->mixed_b)               // fp32 operands: the same rounded R, T - o, X - o, a', u_T as pass A
-        hipLaunchKernelGGL((k_cam_schur<0, false, true>), dim3(grid), dim3(kCamThreads), 0, h->stream, cm,
-                           (const double*)h->tab, reinterpret_cast<const double*>(h->rec32.as<float>()), h->K, vin, (int)h->C,
-                           h->acc(), h->cam_partial.as<double>(), ctrl_done, set, pl, mxb, cx);
-    else
-        hipLaunchKernelGGL((k_cam_schur<MODE, false>), dim3(grid), dim3(kCamThreads), 0, h->stream, cm,
-                           (const double*)h->tab, (const double*)h->rec, h->K, vin, (int)h->C, h->acc(),
-                           h->cam_partial.as<double>(), ctrl_done, set, pl, mxb, cx);
+    // (round_blocks: pass A applies the stored fp32 blocks, pass B rounds its own the same way)
+    auto kern = f.round_blocks ? k_cam_schur<MODE, true> : mixed ? k_cam_schur<0, false, true> : k_cam_schur<MODE, false>;
+    hipLaunchKernelGGL(kern, dim3(h->n_chunks), dim3(kCamThreads), 0, h->stream, cam_major(h), (const double*)h->tab,
+                       rec, h->K, vin, (int)h->C, h->acc(), h->cam_partial.as<double>(),
+                       ctrl_done, set, pl, mxb, cx);
     LAUNCHED(h);
-    return launch_cam_combine(h, 6, h->acc(), 1, (int)h->C, nullptr, ctrl_done ? &ctrl_done->done : nullptr, tb);
+    return launch_cam_combine(h, 6, h->acc(), 1, (int)h->C, nullptr, done);
 }
 
-// The local form with its tail split off (k_p2p_pcg / k_pcg_tail): sharded solves and cameras of several chunks; on a
-// single rank with single-chunk cameras only on request (debug option, tests).
-bool pcg_split_mode(const sfmba_handle* h) {
-    if (h->dbg.pcg_local == 0 || h->dbg.precond == 0) return false;
-    if (!(h->pcg_fused || h->sweep_rc_g)) return false;         // (the forms that have a local prologue / k_pcg_update_local)
-    return (multi_rank(h) || h->cam_multi || h->xcd_b) ? h->dbg.pcg_split != 0 : h->dbg.pcg_split == 1;
+// all-reduced [U | g_c], acc | sd -> Dc-damped block inverses of the Schur-diagonal preconditioner
+int launch_cam_prep_schur(sfmba_handle* h) {
+    hipLaunchKernelGGL(k_cam_prep_schur, dim3((unsigned)((h->C + 63) / 64)), dim3(64), 0, h->stream, (const double*)h->Ugc(),
+                       (const double*)h->sd(), (int)h->C, h->Dc.as<double>(), h->Minv.as<double>());
+    LAUNCHED(h);
+    return 0;
 }
 
 // Reduced right-hand side term -> acc and, with the Schur-diagonal preconditioner, the diagonal blocks of
 // W Vinv W^T -> sd in the same pass; all-reduce; block inverses.  (k_prep has written e into the records and, for
 // the block-Jacobi-of-U form, Minv itself.)
 int launch_rhs_and_preconditioner(sfmba_handle* h) {
+    const Forms& f = h->forms;
     const int64_t C = h->C;
-    if (h->dbg.precond == 0) {
+    if (!f.precond) {
         CHK(launch_cam_schur<1>(h, nullptr, nullptr, 0));
         return exchange(h, h->acc(), 6 * C, 0);
     }
     // single-chunk cameras on one rank, or sharded with the sums exchanged camera by camera inside the pass
     // (CamExchange): every workgroup holds its camera's complete sums and inverts its own preconditioner block (RhsPrecond)
     CamExchange cx{};
-    if (cam_inline(h)) { cx = cam_exchange(h); ++h->p2p.calls; ++h->n_collectives; }
-    if (xcd_cam(h)) {
-        const CamMajor cmb{h->cam_chunks_b.as<int4>(), h->cm_pt.as<int>(), h->cm_uv.as<double>()};
-        const int wgrid = h->n_chunks_b / kWaveChunkCams;
-        const double* rr = h->use_rhsrec ? (const double*)h->rhsrec.as<double>() : (const double*)nullptr;
-        if (h->f32 && !h->sweep_rc && !h->sweep_rc_g)
-            hipLaunchKernelGGL((k_cam_rhs_diag_w<true>), dim3(wgrid), dim3(kCamThreads), 0, h->stream, cmb, (const double*)h->tab,
-                               (const double*)h->rec, (const double*)vinv_ptr(h), h->K, h->cam_partial.as<double>(), rr);
-        else
-            hipLaunchKernelGGL((k_cam_rhs_diag_w<false>), dim3(wgrid), dim3(kCamThreads), 0, h->stream, cmb, (const double*)h->tab,
-                               (const double*)h->rec, (const double*)vinv_ptr(h), h->K, h->cam_partial.as<double>(), rr);
+    if (f.cam_inline) { cx = cam_exchange(h); ++h->p2p.calls; ++h->n_collectives; }
+    const double* rr = f.use_rhsrec ? (const double*)h->rhsrec.as<double>() : (const double*)nullptr;
+    if (f.xcd_cam) {
+        hipLaunchKernelGGL(f.round_blocks ? k_cam_rhs_diag_w<true> : k_cam_rhs_diag_w<false>, dim3(h->n_chunks_b / kWaveChunkCams),
+                           dim3(kCamThreads), 0, h->stream, cam_major_b(h), (const double*)h->tab, (const double*)h->rec,
+                           (const double*)vinv_ptr(h), h->K, h->cam_partial.as<double>(), rr);
         LAUNCHED(h);
-        hipLaunchKernelGGL(k_cam_combine_w<27>, dim3((unsigned)((27 * C + 255) / 256)), dim3(256), 0, h->stream,
-                           (const double*)h->cam_partial.as<double>(), (int)C, h->acc(), 1, (int)C, (const int*)nullptr,
-                           (const double*)nullptr);
-        LAUNCHED(h);
+        CHK(launch_cam_combine_w<27>(h, h->acc(), 1, (int)C, nullptr, nullptr));
         CHK(exchange(h, h->acc(), 27 * C, 0));                  // acc | sd: one contiguous plane-major vector
-        hipLaunchKernelGGL(k_cam_prep_schur, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, h->stream, (const double*)h->Ugc(),
-                           (const double*)h->sd(), (int)C, h->Dc.as<double>(), h->Minv.as<double>());
-        LAUNCHED(h);
-        return 0;
+        return launch_cam_prep_schur(h);
     }
-    const bool own_inverse = !h->cam_multi && (!multi_rank(h) || cam_inline(h));
-    const RhsPrecond mp = own_inverse ? RhsPrecond{h->Ugc(), h->Dc.as<double>(), h->Minv.as<double>()} : RhsPrecond{nullptr, nullptr, nullptr};
-    if (h->f32 && !h->sweep_rc && !h->sweep_rc_g)
-        hipLaunchKernelGGL((k_cam_rhs_diag<true>), dim3(h->n_chunks), dim3(kRhsThreads), 0, h->stream, cam_major(h),
-                           (const double*)h->tab, (const double*)h->rec, (const double*)vinv_ptr(h), h->K, (int)C,
-                           h->acc(), h->cam_partial.as<double>(), mp, h->use_rhsrec ? (const double*)h->rhsrec.as<double>() : (const double*)nullptr, cx);
-    else
-        hipLaunchKernelGGL((k_cam_rhs_diag<false>), dim3(h->n_chunks), dim3(kRhsThreads), 0, h->stream, cam_major(h),
-                           (const double*)h->tab, (const double*)h->rec, (const double*)vinv_ptr(h), h->K, (int)C,
-                           h->acc(), h->cam_partial.as<double>(), mp, h->use_rhsrec ? (const double*)h->rhsrec.as<double>() : (const double*)nullptr, cx);
+    const RhsPrecond mp = f.own_inverse ? RhsPrecond{h->Ugc(), h->Dc.as<double>(), h->Minv.as<double>()} : RhsPrecond{nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(f.round_blocks ? k_cam_rhs_diag<true> : k_cam_rhs_diag<false>, dim3(h->n_chunks), dim3(kRhsThreads), 0, h->stream,
+                       cam_major(h), (const double*)h->tab, (const double*)h->rec, (const double*)vinv_ptr(h), h->K, (int)C,
+                       h->acc(), h->cam_partial.as<double>(), mp, rr, cx);
     LAUNCHED(h);
-    if (own_inverse) return 0;
+    if (f.own_inverse) return 0;
     CHK(launch_cam_combine(h, 27, h->acc(), 1, (int)C, nullptr, nullptr));
     CHK(exchange(h, h->acc(), 27 * C, 0));                  // acc | sd: one contiguous plane-major vector
-    hipLaunchKernelGGL(k_cam_prep_schur, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, h->stream, (const double*)h->Ugc(),
-                       (const double*)h->sd(), (int)C, h->Dc.as<double>(), h->Minv.as<double>());
-    LAUNCHED(h);
-    return 0;
+    return launch_cam_prep_schur(h);
 }
 
 // Few cameras: form the block pairs of W V^-1 W^T, then run the PCG on S = U + Dc - (...) inside one workgroup with
@@ -1091,13 +1110,13 @@ int launch_dense_solve(sfmba_handle* h, double tol, int max_iters, bool rhs) {
 // acc = (S - Dc) v for a plane-major vector v outside the PCG (test and timing entries): pass A, pass B
 int schur_product_standalone(sfmba_handle* h, const double* v_planes) {
     const double* va = v_planes;
-    if (!h->lds_vec && !h->sweep_rc && !h->sweep_rc_g) {    // pass A gathers v from a camera-major copy in L2
+    if (!h->forms.lds_vec && !h->forms.sweep_rc && !h->forms.sweep_rc_g) {    // pass A gathers v from a camera-major copy in L2
         hipLaunchKernelGGL(k_transpose, dim3((unsigned)((6 * h->C + 255) / 256)), dim3(256), 0, h->stream, v_planes,
                            6, (int)h->C, h->vcm.as<double>(), (const PcgCtrl*)nullptr, 0);
         LAUNCHED(h);
         va = h->vcm.as<double>();
     }
-    CHK(launch_point_sweep(h, va, nullptr, 0));
+    CHK(launch_pass_a<false>(h, va, nullptr, 0));
     return launch_cam_schur<0>(h, v_planes, nullptr, 0);
 }
 
@@ -1107,26 +1126,18 @@ int launch_jdot(sfmba_handle* h, int* nparts) {
     const double* sgc = h->sg_cur;
     const double* sgp = sgc + 6 * h->C;
     Piggyback pb{};
-    if (h->pending_scale_sums) pb = slices_rider(h, 0, 4);
+    if (h->pending_scale_sums) pb = slices_rider(h);
     const int launch_grid = grid + (pb.part != nullptr ? 1 : 0);
     const Recompute rc{h->tab, h->x + 6 * h->C, h->K};
-    if (h->jfree) {
-        const size_t lds = sizeof(double) * kCamRow * (size_t)h->C;
-        auto kern = k_jdot<false, true>;
+    auto run = [&](auto kern, size_t lds) -> int {
         CHK(set_lds(h, kern, lds));
         hipLaunchKernelGGL(kern, dim3(launch_grid), dim3(kSweepThreads), lds, h->stream, obs_arrays(h), sgc, sgp,
                            (int)h->N, (int)h->C, h->t1.as<double>(), h->partB(), pb, rc);
-    } else if (h->lds_vec) {
-        const size_t lds = sizeof(double) * 6 * h->C;
-        auto kern = k_jdot<true>;
-        CHK(set_lds(h, kern, lds));
-        hipLaunchKernelGGL(kern, dim3(launch_grid), dim3(kSweepThreads), lds, h->stream, obs_arrays(h), sgc, sgp,
-                           (int)h->N, (int)h->C, h->t1.as<double>(), h->partB(), pb, rc);
-    } else {
-        hipLaunchKernelGGL(k_jdot<false>, dim3(launch_grid), dim3(kSweepThreads), 0, h->stream, obs_arrays(h),
-                           sgc, sgp, (int)h->N, (int)h->C, h->t1.as<double>(), h->partB(), pb, rc);
-    }
-    LAUNCHED(h);
+        LAUNCHED(h);
+        return 0;
+    };
+    CHK(h->forms.jfree ? run(k_jdot<false, true>, sizeof(double) * kCamRow * (size_t)h->C)
+        : h->forms.lds_vec ? run(k_jdot<true>, sizeof(double) * 6 * (size_t)h->C) : run(k_jdot<false>, 0));
     h->pending_scale_sums = false;
     *nparts = grid;
     return 0;
@@ -1138,37 +1149,24 @@ int launch_backsub(sfmba_handle* h, int* nparts) {
     double* dp = dc + 6 * h->C;
     const PcgCtrl* ctrl2 = h->ctrl.as<PcgCtrl>();
     const Recompute rc{h->tab, h->x + 6 * h->C, h->K};
-    if (h->jfree) {
-        hipLaunchKernelGGL(k_transpose, dim3((6 * h->C + 255) / 256), dim3(256), 0, h->stream,
-                           (const double*)h->vecs.as<double>(), 6, (int)h->C, dc, ctrl2, h->pcg_L);
-        LAUNCHED(h);
-        const size_t lds = sizeof(double) * kCamRow * (size_t)h->C;
-        auto kern = k_backsub<false, true>;
+    // dc from the device-selected vector set: read from the LDS copy of the sets (`in_lds`), or transposed first
+    auto run = [&](auto kern, size_t lds, bool in_lds) -> int {
+        if (!in_lds) {
+            hipLaunchKernelGGL(k_transpose, dim3((6 * h->C + 255) / 256), dim3(256), 0, h->stream,
+                               (const double*)h->vecs.as<double>(), 6, (int)h->C, dc, ctrl2, h->pcg_L);
+            LAUNCHED(h);
+        }
         CHK(set_lds(h, kern, lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, h->ranges.as<int2>(), h->n_ranges, obs_arrays(h),
                            h->vecs.as<double>(), dc, vinv_ptr(h), h->gp.as<double>(), h->t1.as<double>(), dp, h->partB(),
-                           (int)h->C, (const PcgCtrl*)nullptr, 0, h->g_cur, h->si_cur, h->sg_cur, rc, FinalUpdate{});
-    } else if (h->lds_vec) {
-        const size_t lds = sizeof(double) * 6 * h->C;
-        auto kern = k_backsub<true>;
-        CHK(set_lds(h, kern, lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, h->ranges.as<int2>(),
-                           h->n_ranges, obs_arrays(h), h->vecs.as<double>(), dc, vinv_ptr(h),
-                           h->gp.as<double>(), h->t1.as<double>(), dp, h->partB(), (int)h->C,
-                           ctrl2, h->pcg_L, h->g_cur, h->si_cur, h->sg_cur, rc,
-                           h->pcg_a_owed ? FinalUpdate{h->pcg_part.as<double>(), h->vecs.as<double>(), h->ctrl.as<PcgCtrl>(), h->pcg_L - 1}
-                                         : FinalUpdate{});
-    } else {
-        hipLaunchKernelGGL(k_transpose, dim3((6 * h->C + 255) / 256), dim3(256), 0, h->stream,
-                           (const double*)h->vecs.as<double>(), 6, (int)h->C, dc, ctrl2, h->pcg_L);
+                           (int)h->C, in_lds ? ctrl2 : (const PcgCtrl*)nullptr, in_lds ? h->pcg_L : 0, h->g_cur, h->si_cur, h->sg_cur, rc,
+                           in_lds && h->pcg_a_owed ? FinalUpdate{h->pcg_part.as<double>(), h->vecs.as<double>(), h->ctrl.as<PcgCtrl>(), h->pcg_L - 1}
+                                                   : FinalUpdate{});
         LAUNCHED(h);
-        hipLaunchKernelGGL(k_backsub<false>, dim3(grid), dim3(kSweepThreads), 0, h->stream,
-                           h->ranges.as<int2>(), h->n_ranges, obs_arrays(h), h->vecs.as<double>(), dc,
-                           vinv_ptr(h), h->gp.as<double>(), h->t1.as<double>(), dp,
-                           h->partB(), (int)h->C, (const PcgCtrl*)nullptr, 0, h->g_cur,
-                           h->si_cur, h->sg_cur, rc, FinalUpdate{});
-    }
-    LAUNCHED(h);
+        return 0;
+    };
+    CHK(h->forms.jfree ? run(k_backsub<false, true>, sizeof(double) * kCamRow * (size_t)h->C, false)
+        : h->forms.lds_vec ? run(k_backsub<true>, sizeof(double) * 6 * (size_t)h->C, true) : run(k_backsub<false>, 0, false));
     *nparts = grid;
     return 0;
 }
@@ -1188,23 +1186,18 @@ int launch_update_scale(sfmba_handle* h, int first, bool defer = false, bool spe
     double* g = speculative ? h->g_new : h->g_cur;
     double* sg = speculative ? h->sg_new : h->sg_cur;
     const double* skip = speculative ? h->skip : (const double*)nullptr;
-    if (h->scale_pts == 2)
-        hipLaunchKernelGGL(k_update_scale<2>, dim3(h->red_grid), dim3(256), 0, h->stream, h->Ugc(), h->V.as<double>(),
-                           h->gp.as<double>(), x, (int)h->C, (int)h->P, first, h->red_bc, (const double*)h->si_cur, si,
-                           g, sg, h->part.as<double>(), skip);
-    else
-        hipLaunchKernelGGL(k_update_scale<1>, dim3(h->red_grid), dim3(256), 0, h->stream, h->Ugc(), h->V.as<double>(),
-                           h->gp.as<double>(), x, (int)h->C, (int)h->P, first, h->red_bc, (const double*)h->si_cur, si,
-                           g, sg, h->part.as<double>(), skip);
+    hipLaunchKernelGGL(h->scale_pts == 2 ? k_update_scale<2> : k_update_scale<1>, dim3(h->red_grid), dim3(256), 0, h->stream, h->Ugc(),
+                       h->V.as<double>(), h->gp.as<double>(), x, (int)h->C, (int)h->P, first, h->red_bc, (const double*)h->si_cur, si,
+                       g, sg, h->part.as<double>(), skip);
     LAUNCHED(h);
     if (speculative) return 0;
     if (defer) { h->pending_scale_sums = true; return 0; }
-    return launch_finish_slices(h, 0, 4);
+    return launch_finish(h, slices_rider(h));
 }
 
 // q0..q8 with the step vector p
 // Final sums of k_backsub's partial rows (half B, kBacksubCols wide): G12, G22 -> slots 2, 3; q5..q8 of the
-// point slice -> 4..7 (the run exchange_tail reduces over ranks); q5..q8 of the camera slice -> 21..24.
+// point slice -> 4..7 (the run the tail of the linear phase reduces over ranks); q5..q8 of the camera slice -> 21..24.
 Piggyback backsub_rider(sfmba_handle* h, int nparts) {
     Piggyback pb{h->partB(), h->scal(), FinishJob{}, 1, kBacksubCols, 0};
     pb.job.row0[0] = 0; pb.job.nrows[0] = nparts;
@@ -1213,28 +1206,18 @@ Piggyback backsub_rider(sfmba_handle* h, int nparts) {
     for (int k = 0; k < 4; ++k) pb.job.slot[0][6 + k] = kCamSlot + 5 + k;
     return pb;
 }
-int launch_finish_backsub(sfmba_handle* h, int nparts) {
-    const Piggyback pb = backsub_rider(h, nparts);
-    hipLaunchKernelGGL(k_finish, dim3(1), dim3(64 * kBacksubCols), 0, h->stream, pb.part, pb.job, kBacksubCols, 0,
-                       h->scal(), (const double*)nullptr, Mailbox{});
-    LAUNCHED(h);
-    return 0;
-}
 
 // all-reduce freshly written exchange scalars over ranks (no-op on one GPU); stays on the stream.
 // Only slots written since their last reduction may be included.
 int flush_scale_sums(sfmba_handle* h) {         // no k_jdot follows the last k_update_scale: finish on its own
     if (!h->pending_scale_sums) return 0;
     h->pending_scale_sums = false;
-    return launch_finish_slices(h, 0, 4);
+    return launch_finish(h, slices_rider(h));
 }
 int exchange_linearise(sfmba_handle* h) {       // q1..q4 and max|g| of the point slice
-    CHK(exchange(h, h->scal() + 8, 4, 0));
+    CHK(exchange(h, h->scal() + kQ1Slot, 4, 0));
     CHK(exchange(h, h->scal() + kMaxSlot, 1, 1));
     return 0;
-}
-int exchange_tail(sfmba_handle* h) {            // G12, G22, q5..q8
-    return exchange(h, h->scal() + 2, 6, 0);
 }
 
 // bring all 32 scalars to the host (h_scal) and wait: one small kernel posts them into the mailbox (no blit
@@ -1247,9 +1230,6 @@ int fetch_scalars(sfmba_handle* h) {
     memcpy(h->h_scal, h->mbox, sizeof(double) * kScalSlots);
     return 0;
 }
-
-// q_k summed over the camera slice and the (rank-reduced) point slice
-double qsum(const sfmba_handle* h, int q) { return h->h_scal[kPointSlot[q]] + h->h_scal[kCamSlot + q]; }
 
 // x crosses PCIe through a pinned staging buffer (an async copy from pageable memory is staged by the
 // runtime anyway, synchronously and in small pieces)
@@ -1291,7 +1271,7 @@ void staging_copy(sfmba_handle* h, void* dst, const void* src, size_t bytes) {
 
 int upload_x(sfmba_handle* h, const double* x_host) {
     CHK(ensure_h_x(h));
-    if (h->mixed) {                    // origin of the fp32 operands: mean of (a sample of) this vector's points
+    if (h->forms.mixed) {                    // origin of the fp32 operands: mean of (a sample of) this vector's points
         const double* pts = x_host + 6 * h->C;
         const int64_t stride = std::max<int64_t>(1, h->P / 1024);
         double sx = 0.0, sy = 0.0, sz = 0.0;
@@ -1336,13 +1316,15 @@ int download_residuals(sfmba_handle* h, double* r_out) {
     return 0;
 }
 
-int check_ready(sfmba_handle* h, const void* x) {
+// every compute entry: is the handle ready, and which forms does this call run (the solve stage of the decision)
+int begin_compute(sfmba_handle* h, const void* x) {
     if (!h->have_problem) return fail(h, -1, "sfmba_set_problem has not been called");
     if (h->transport_dropped)
         return fail(h, -1, "sfmba_set_problem removed this handle's multi-rank transport (direct link / RCCL communicator / "
                            "callback): set it up again for the new problem, or call sfmba_set_exchange(h, NULL, 0, NULL, NULL, 0) "
                            "to solve the shard on its own");
     if (!x) return fail(h, -1, "x is NULL");
+    decide_solve_forms(h);
     return 0;
 }
 
@@ -1355,20 +1337,12 @@ int pcg_start(sfmba_handle* h, const sfmba_options& opt) {
     h->pcg_L = 0;
     h->pcg_b_owed = false;
     h->pcg_a_owed = false;
-    // sharded over the direct link with single-chunk cameras: the local form itself, the all-reduce of the product inside
-    // pass B (CamExchange); else the local form with its tail behind the reduction (pcg_split), else the general forms
-    h->pcg_inline = p2p_inline_ok(h) && !h->cam_multi && !h->xcd_b && h->dbg.pcg_inline != 0 && h->dbg.pcg_local != 0 &&
-                    h->dbg.precond != 0 && h->dbg.pcg_split != 1 && (h->pcg_fused || h->sweep_rc_g);
-    h->pcg_split = !h->pcg_inline && pcg_split_mode(h);
-    const bool own_cameras = (!multi_rank(h) && !h->cam_multi && !h->xcd_b) || h->pcg_split || h->pcg_inline;
-    h->pcg_local = h->pcg_fused && h->dbg.pcg_local != 0 && own_cameras;
-    h->pcg_local2 = !h->pcg_fused && h->sweep_rc_g && h->dbg.pcg_local != 0 && own_cameras;
-    if (h->pcg_fused) {                   // launch 0 of the fused form initialises the solve itself
+    if (h->forms.pcg_fused) {                   // launch 0 of the fused form initialises the solve itself
         h->pcg_tol = opt.pcg_tol;
         h->pcg_cap = pcg_max_iters(h, opt);
         return 0;
     }
-    if (h->pcg_local2)                    // its update takes gamma from the iterate: no reduction at the start
+    if (h->forms.pcg_local2)                    // its update takes gamma from the iterate: no reduction at the start
         hipLaunchKernelGGL(k_pcg_init_local, dim3((unsigned)((h->C + 63) / 64)), dim3(64), 0, h->stream, (const double*)h->Ugc(),
                            (const double*)h->acc(), (const double*)h->Minv.as<double>(), (int)h->C, h->vecs.as<double>(),
                            (const double*)(h->scal() + kEtaSlot), pcg_max_iters(h, opt), h->ctrl.as<PcgCtrl>());
@@ -1415,9 +1389,9 @@ int launch_reduce_and_tail(sfmba_handle* h, const PcgCtrl* cd, int set) {
 // B, the z of pass A of launch L, all untouched since).
 int pcg_pass_b(sfmba_handle* h, int L) {
     const PcgCtrl* cd = h->ctrl.as<PcgCtrl>() + ((L + 1) & 1);
-    CHK(launch_cam_schur<0>(h, h->vecs.as<double>(), cd, L & 1, h->pcg_local && !h->pcg_split, h->pcg_inline));
-    if (h->pcg_split) CHK(launch_reduce_and_tail(h, cd, L & 1));
-    else if (!h->pcg_inline) CHK(exchange(h, h->acc(), 6 * h->C, 0, &cd->done));
+    CHK(launch_cam_schur<0>(h, h->vecs.as<double>(), cd, L & 1, h->forms.pcg_local && !h->forms.pcg_split, h->forms.pcg_inline));
+    if (h->forms.pcg_split) CHK(launch_reduce_and_tail(h, cd, L & 1));
+    else if (!h->forms.pcg_inline) CHK(exchange(h, h->acc(), 6 * h->C, 0, &cd->done));
     return 0;
 }
 
@@ -1426,7 +1400,7 @@ int pcg_enqueue(sfmba_handle* h, int count, bool speculative = false) {
     if (h->pcg_a_owed) {                                        // (k_backsub stood in for this launch and found work left)
         h->pcg_a_owed = false;
         h->pcg_b_owed = true;
-        CHK(launch_pcg_fused(h, h->pcg_L - 1));
+        CHK(launch_pass_a<true>(h, h->vecs.as<double>(), ctrl2, h->pcg_L - 1));
     }
     if (h->pcg_b_owed) {
         h->pcg_b_owed = false;
@@ -1434,18 +1408,16 @@ int pcg_enqueue(sfmba_handle* h, int count, bool speculative = false) {
     }
     for (int k = 0; k < count; ++k) {
         const int L = h->pcg_L;
-        if (h->pcg_fused) {
-            // (several ranks: only where the product's exchange sits inside pass B -- every rank then takes the same
-            // decision from the same record, and a launch that is not enqueued exchanges nothing on any of them)
-            const bool last = speculative && k == count - 1 && (!multi_rank(h) || h->pcg_inline) && h->dbg.pcg_skip_last != 0;
+        if (h->forms.pcg_fused) {
+            const bool last = speculative && k == count - 1 && h->forms.skip_last != 0;
             // ... and in the local form with the step vector in k_backsub's LDS not even that pass A: k_backsub's prologue
             // does its update (FinalUpdate)
-            if (last && L > 0 && h->pcg_local && h->lds_vec && !h->jfree && h->dbg.pcg_skip_last != 2) {
+            if (last && L > 0 && h->forms.skip_last == 2) {
                 h->pcg_L = L + 1;
                 h->pcg_a_owed = true;
                 break;
             }
-            CHK(launch_pcg_fused(h, L));
+            CHK(launch_pass_a<true>(h, h->vecs.as<double>(), ctrl2, L));
             // a launch that found the solve finished (or finished it) produced no z: its control block (written
             // to slot (L+1)&1) says so, and pass B and the collective behind it are void as well
             h->pcg_L = L + 1;
@@ -1454,10 +1426,10 @@ int pcg_enqueue(sfmba_handle* h, int count, bool speculative = false) {
             continue;
         }
         const PcgCtrl* cd = ctrl2 + (L & 1);                     // current until k_pcg_update writes the other one
-        CHK(launch_point_sweep(h, h->vecs.as<double>(), ctrl2, L));
-        CHK(launch_cam_schur<0>(h, h->vecs.as<double>(), cd, -1, h->pcg_local2 && !h->pcg_split, h->pcg_inline));
-        if (h->pcg_local2 && h->pcg_split) CHK(launch_reduce_and_tail(h, cd, -1));
-        if (h->pcg_local2) {                                    // pass B / the tail did the bookkeeping: the light update
+        CHK(launch_pass_a<false>(h, h->vecs.as<double>(), ctrl2, L));
+        CHK(launch_cam_schur<0>(h, h->vecs.as<double>(), cd, -1, h->forms.pcg_local2 && !h->forms.pcg_split, h->forms.pcg_inline));
+        if (h->forms.pcg_local2 && h->forms.pcg_split) CHK(launch_reduce_and_tail(h, cd, -1));
+        if (h->forms.pcg_local2) {                                    // pass B / the tail did the bookkeeping: the light update
             hipLaunchKernelGGL(k_pcg_update_local, dim3((unsigned)((h->C + 1023) / 1024)), dim3(1024), 0, h->stream,
                                h->vecs.as<double>(), (const double*)h->pcg_part.as<double>(), ctrl2, L, (int)h->C);
             LAUNCHED(h);
@@ -1475,10 +1447,10 @@ int pcg_enqueue(sfmba_handle* h, int count, bool speculative = false) {
 
 int pcg_read(sfmba_handle* h, PcgCtrl* hc) {
     static_assert(sizeof(PcgCtrl) <= 24 * sizeof(double), "PcgCtrl fits the pinned tail");
-    HIPCHK(h, hipMemcpyAsync(h->h_scal + 40, h->ctrl.as<PcgCtrl>() + (h->pcg_L & 1), sizeof *hc,
+    HIPCHK(h, hipMemcpyAsync(h->h_scal + kPinCtrl, h->ctrl.as<PcgCtrl>() + (h->pcg_L & 1), sizeof *hc,
                              hipMemcpyDeviceToHost, h->stream));
     CHK(wait_stream(h));
-    memcpy(hc, h->h_scal + 40, sizeof *hc);
+    memcpy(hc, h->h_scal + kPinCtrl, sizeof *hc);
     return 0;
 }
 
@@ -1617,40 +1589,9 @@ int sfmba_set_print(sfmba_handle* h, sfmba_print_fn fn, void* ctx) {
 int sfmba_debug_option(sfmba_handle* h, const char* name, int64_t value) {
     CHK(enter(h));
     if (!name) return fail(h, -1, "option name is NULL");
-    const std::string n(name);
-    const int v = (int)value;
-    if (n == "pcg_fused") h->dbg.pcg_fused = v;
-    else if (n == "sweep_rc") h->dbg.sweep_rc = v;
-    else if (n == "dense") h->dbg.dense = v;
-    else if (n == "precond") h->dbg.precond = v;
-    else if (n == "pcg_local") h->dbg.pcg_local = v;
-    else if (n == "pcg_split") h->dbg.pcg_split = v;
-    else if (n == "pcg_mixed") h->dbg.pcg_mixed = v;
-    else if (n == "pcg_inline") h->dbg.pcg_inline = v;
-    else if (n == "pcg_skip_last") h->dbg.pcg_skip_last = v;
-    else if (n == "xcd_cam") h->dbg.xcd_cam = v;
-    else if (n == "cm_device") h->dbg.cm_device = v;
-    else if (n == "jfree") h->dbg.jfree = v;
-    else if (n == "packed_upload") h->dbg.packed_upload = v;
-    else if (n == "pcg_mixed_b") h->dbg.pcg_mixed_b = v;
-    else if (n == "cost_rider") h->dbg.cost_rider = v;
-    else if (n == "spec_scale") h->dbg.spec_scale = v;
-    else if (n == "start_handoff") h->dbg.start_handoff = v;
-    else if (n == "early_download") h->dbg.early_download = v;
-    else if (n == "rhsrec") h->dbg.rhsrec = v;
-    else if (n == "xcd_chunks") h->dbg.xcd_chunks = v;
-    else if (n == "tab_lds") h->dbg.tab_lds = v;
-    else if (n == "vec_lds") h->dbg.vec_lds = v;
-    else if (n == "cam_chunk") h->dbg.cam_chunk = v;
-    else if (n == "pcg_guess_bias") h->dbg.pcg_guess_bias = v;
-    else if (n == "trace_pcg") h->dbg.trace_pcg = v;
-    else if (n == "trace_stalls") h->dbg.trace_stalls = v;
-    else if (n == "trace_timing") h->dbg.trace_timing = v;
-    else if (n == "wait_deadline_s") h->dbg.wait_deadline_s = v;
-    else if (n == "p2p_delay_ms") h->dbg.p2p_delay_ms = v;
-    else if (n == "p2p_timeout_ms") h->dbg.p2p_timeout_ms = v;
-    else return fail(h, -1, "unknown debug option '%s'", name);
-    return 0;
+    for (const auto& o : kDebugOptions)
+        if (strcmp(name, o.name) == 0) { h->dbg.*o.member = (int)value; return 0; }
+    return fail(h, -1, "unknown debug option '%s'", name);
 }
 
 int sfmba_set_precision(sfmba_handle* h, int32_t storage_bits) {
@@ -1835,7 +1776,7 @@ int sfmba_p2p_attach(sfmba_handle* h, const void* handles, int32_t rank, int32_t
         for (const char* c = bus; *c; ++c) id = (id ^ (unsigned char)*c) * 1099511628211ull;
         std::fill(v.begin(), v.begin() + world + 1, 0.0);
         v[(size_t)rank] = (double)(1 + (id >> 24));
-        v[(size_t)world] = (h->cam_multi || h->xcd_b) ? 1.0 : 0.0;
+        v[(size_t)world] = (h->forms.cam_multi || h->forms.xcd_b) ? 1.0 : 0.0;
         HIPCHK(h, hipMemcpyAsync(dev, v.data(), sizeof(double) * (world + 1), hipMemcpyHostToDevice, h->stream));
         CHK(p2p_allreduce(h, dev, world + 1, 0, nullptr));
         HIPCHK(h, hipMemcpyAsync(v.data(), dev, sizeof(double) * (world + 1), hipMemcpyDeviceToHost, h->stream));
@@ -1888,27 +1829,55 @@ int sfmba_get_counters(const sfmba_handle* h, int64_t* kernel_launches, int64_t*
     return 0;
 }
 
-static int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, const int64_t* cam, const int64_t* pt,
-                            const double* uv, const int64_t* uv_i64, const double* K);
+// ---- sfmba_set_problem ---------------------------------------------------------------------------------------------
+namespace {
+// What the phases of a sfmba_set_problem call share; run() is the call, the members below it are its phases in order.
+struct ProblemBuild {
+    sfmba_handle* const h;
+    const int64_t C, P, N;
+    const int64_t *const cam, *const pt;
+    const double* const uv;
+    const int64_t* const uv_i64;
+    const double* const K;
+    const int64_t ld = (N + 255) / 256 * 256;
+    const size_t ldz = (size_t)ld;
+    const bool f32 = h->f32_next;
+    Forms plan;                              // the forms with the facts of the tables still assumed favourable
+    ProblemFacts facts;                      // ... and those facts as the phases find them
+    std::vector<char> fixed;                 // [C] camera held still
+    int64_t n_cmp = 0, fdiff = 0;            // observations compared with / equal to the previous problem's
+    bool sorted = true;
+    const int parts = h->pool.parts_for(N);
+    const int64_t per = (N + parts - 1) / parts;
+    std::vector<int> hist;                   // [parts][C] camera counts, then scatter offsets
+    // what part t of the conversion pass found: first bad index, first changed observation, order broken, a pixel that is no int16
+    std::vector<int64_t> bad = std::vector<int64_t>((size_t)parts, -1), first_diff = std::vector<int64_t>((size_t)parts, N);
+    std::vector<char> unsorted = std::vector<char>((size_t)parts, 0), not16 = unsorted;
+    std::vector<int> cam_ptr, cov_ptr, cov_pt;
+    std::vector<int2> blk_ab;
+    // the converted arrays in pinned memory (h->stage)
+    double* uvs = nullptr; float* uvf = nullptr;
+    int *ci = nullptr, *pi = nullptr, *perm = nullptr, *ptr = nullptr;
+    unsigned short* ci16 = nullptr; short* uv16 = nullptr;
+    int64_t p_keep = 0;                      // run offsets that are unchanged on the device
+    size_t tables_bytes = 0;
 
-int sfmba_set_problem(sfmba_handle* h, int64_t C, int64_t P, int64_t N, const int64_t* cam, const int64_t* pt,
-                      const double* uv, const double* K) {
-    return set_problem_impl(h, C, P, N, cam, pt, uv, nullptr, K);
-}
+    int run();
+    // the phases, in order (the form decision sits between pair_lists and allocate)
+    int check_and_reset();
+    int convert_and_compare();      // ... and the point-major order
+    void convert(const int64_t* ord, int64_t n_compare, bool packed_prefix_ok);
+    void camera_major_sort();
+    void wave_ranges(), step_tables(), chunk_tables(), pair_lists();
+    int allocate(), upload_and_zero(), enqueue_camera_major();
+    hipError_t up(void* dst, const void* src, size_t elem, size_t from, size_t to) {
+        if (to <= from) return hipSuccess;
+        return hipMemcpyAsync(static_cast<char*>(dst) + elem * from, static_cast<const char*>(src) + elem * from,
+                              elem * (to - from), hipMemcpyHostToDevice, h->stream);
+    }
+};
 
-int sfmba_set_problem_i64(sfmba_handle* h, int64_t C, int64_t P, int64_t N, const int64_t* cam, const int64_t* pt,
-                          const int64_t* uv, const double* K) {
-    return set_problem_impl(h, C, P, N, cam, pt, nullptr, uv, K);
-}
-
-static int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, const int64_t* cam, const int64_t* pt,
-                            const double* uv, const int64_t* uv_i64, const double* K) {
-    CHK(enter(h));
-    const bool timing = h->dbg.trace_timing != 0;
-    const double tp0 = now_s();
-    double tp1 = tp0, tp2 = tp0, tp3 = tp0, ts1 = tp0, ts2 = tp0, ts3 = tp0;
-    h->have_problem = false;
-    h->solved = false;
+int ProblemBuild::check_and_reset() {
     if (C <= 0 || P <= 0 || N <= 0) return fail(h, -1, "n_cameras, n_points, n_obs must be positive");
     if (!cam || !pt || (!uv && !uv_i64) || !K) return fail(h, -1, "NULL array argument");
     if (N >= (int64_t)1 << 30 || 6 * C + 3 * P >= (int64_t)1 << 31)
@@ -1922,7 +1891,7 @@ static int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, co
     // U_c, g_c, the reduced right-hand side, the Schur-diagonal block, the product of pass B -- is empty for them,
     // exactly as for a camera nobody observes; the point-major sweeps keep the observations (residual, cost, V_p,
     // g_p) and only ever multiply the camera part of their Jacobian with a camera vector that stays zero.
-    std::vector<char> fixed((size_t)C, 0);
+    fixed.assign((size_t)C, 0);
     for (int64_t c : h->fixed_next) {
         if (c < 0 || c >= C) return fail(h, -1, "fixed camera index %lld out of range [0,%lld)", (long long)c, (long long)C);
         fixed[(size_t)c] = 1;
@@ -1934,27 +1903,60 @@ static int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, co
     // staging buffer of the direct link stays allocated until sfmba_p2p_detach / _export / _destroy, because
     // peers may still have it mapped.
     // The drop is not silent: the next compute call on this handle fails (-1) until a transport is attached again
-    // or single-rank operation is acknowledged (check_ready).
+    // or single-rank operation is acknowledged (begin_compute).
     const bool had_transport = multi_rank(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));                  // collectives in flight; a previous upload may still read the staging
     if (h->p2p.ready) p2p_close_peers(h);
     if (h->comm) { if (RcclApi* api = rccl_api()) (void)api->CommDestroy(h->comm); h->comm = nullptr; }
     if (had_transport) h->transport_dropped = true;
+    return 0;
+}
 
-    // ---- incremental re-use ---------------------------------------------------------
-    // The reference calls BA once per fused edge on a growing reconstruction (/root/reference/sfm_lite/sfm.py:59-71):
-    // once every camera is registered, a new edge only appends points and their observations, so the argument
-    // arrays of one call start with those of the previous call.  The converted arrays of the last problem stay in
-    // pinned host memory and in HBM; this call compares as it converts, finds the first observation that differs
-    // and uploads from there on only.  The structure tables are always rebuilt from the (complete) host arrays, by
-    // the same code whatever was re-used: results are bitwise those of a fresh handle.
+// pass 1 (parallel): range check, order check, conversion with comparison, camera histogram
+void ProblemBuild::convert(const int64_t* ord, int64_t n_compare, bool packed_prefix_ok) {
+    h->pool.run(parts, [&](int t) {
+        const int64_t b = std::min<int64_t>(N, t * per), e = std::min<int64_t>(N, (t + 1) * per);
+        int* hc = hist.data() + (size_t)t * (size_t)C;
+        for (int64_t c = 0; c < C; ++c) hc[c] = 0;
+        int64_t fd = N;
+        for (int64_t k = b; k < e; ++k) {
+            const int64_t s = ord ? ord[k] : k;
+            const int64_t cv = cam[s], pv = pt[s];
+            if (cv < 0 || cv >= C || pv < 0 || pv >= P) { if (bad[t] < 0) bad[t] = s; continue; }
+            if (!ord && k > 0 && pv < pt[k - 1]) unsorted[t] = 1;
+            double u0, u1;
+            if (uv) { u0 = uv[2 * s]; u1 = uv[2 * s + 1]; }
+            else { u0 = (double)uv_i64[2 * s]; u1 = (double)uv_i64[2 * s + 1]; }          // as numpy promotes
+            if (!fixed[(size_t)cv]) ++hc[cv];
+            const bool same = k < n_compare && ci[k] == (int)cv && pi[k] == (int)pv && uvs[2 * k] == u0 && uvs[2 * k + 1] == u1;
+            if (ci16 && !(same && packed_prefix_ok)) {     // (an unchanged entry is packed already, if the previous call packed)
+                const bool in = std::fabs(u0) < 32768.0 && std::fabs(u1) < 32768.0;
+                const short q0 = in ? (short)u0 : (short)0, q1 = in ? (short)u1 : (short)0;
+                if (!in || (double)q0 != u0 || (double)q1 != u1) not16[t] = 1;
+                ci16[k] = (unsigned short)cv; uv16[2 * k] = q0; uv16[2 * k + 1] = q1;
+            }
+            if (same) continue;
+            if (fd == N) fd = k;
+            ci[k] = (int)cv; pi[k] = (int)pv; uvs[2 * k] = u0; uvs[2 * k + 1] = u1;
+            if (uvf) { uvf[2 * k] = (float)u0; uvf[2 * k + 1] = (float)u1; }    // integer pixels up to 2^24 are exact
+        }
+        first_diff[t] = fd;
+    });
+}
+
+// ---- incremental re-use ---------------------------------------------------------
+// The reference calls BA once per fused edge on a growing reconstruction (/root/reference/sfm_lite/sfm.py:59-71):
+// once every camera is registered, a new edge only appends points and their observations, so the argument
+// arrays of one call start with those of the previous call.  The converted arrays of the last problem stay in
+// pinned host memory and in HBM; this call compares as it converts, finds the first observation that differs
+// and uploads from there on only.  The structure tables are always rebuilt from the (complete) host arrays, by
+// the same code whatever was re-used: results are bitwise those of a fresh handle.
+// Then the point-major order: any order is accepted, the kernels want point-major.
+int ProblemBuild::convert_and_compare() {
     auto& prev = h->prev;
-    const bool f32 = h->f32_next;
-    const int64_t ld = (N + 255) / 256 * 256;
-    const size_t ldz = (size_t)ld;
-    const int64_t n_cmp = (prev.valid && prev.f32 == f32) ? std::min(prev.N, N) : 0;
-    prev.valid = false;                                          // until this call has completed
     auto& sg = h->stage;
+    n_cmp = (prev.valid && prev.f32 == f32) ? std::min(prev.N, N) : 0;
+    prev.valid = false;                                          // until this call has completed
     const size_t keep_obs = (size_t)n_cmp;
     HIPCHK(h, sg.uv.ensure(sizeof(double) * 2 * ldz, sizeof(double) * 2 * keep_obs));
     HIPCHK(h, sg.ci.ensure(sizeof(int) * ldz, sizeof(int) * keep_obs));
@@ -1962,81 +1964,37 @@ static int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, co
     HIPCHK(h, sg.perm.ensure(sizeof(int) * ldz, 0));
     HIPCHK(h, sg.ptr.ensure(sizeof(int) * ((size_t)P + 1), 0));
     if (f32) HIPCHK(h, sg.uvf.ensure(sizeof(float) * 2 * ldz, sizeof(float) * 2 * keep_obs));
-    const bool try_pack = (h->dbg.packed_upload == 1 || (h->dbg.packed_upload != 0 && N >= 65536)) && C <= 65535;   // (small: two launches > the bytes)
+    const bool try_pack = plan.packed_upload;
     const bool packed_prefix_ok = try_pack && prev.packed && n_cmp > 0;      // the staged prefix holds valid packed entries
     if (try_pack) {
         HIPCHK(h, sg.ci16.ensure(sizeof(unsigned short) * ldz, sizeof(unsigned short) * keep_obs));
         HIPCHK(h, sg.uv16.ensure(sizeof(short) * 2 * ldz, sizeof(short) * 2 * keep_obs));
     }
-    unsigned short* ci16 = try_pack ? sg.ci16.as<unsigned short>() : nullptr;
-    short* uv16 = try_pack ? sg.uv16.as<short>() : nullptr;
-    std::vector<char> not16((size_t)h->pool.parts_for(N), 0);       // a pixel that is no int16 integer: no packing
-    double* uvs = sg.uv.as<double>();
-    float* uvf = f32 ? sg.uvf.as<float>() : nullptr;
-    int* ci = sg.ci.as<int>();
-    int* pi = sg.pi.as<int>();
-    int* perm = sg.perm.as<int>();
-    int* ptr = sg.ptr.as<int>();
+    ci16 = try_pack ? sg.ci16.as<unsigned short>() : nullptr;
+    uv16 = try_pack ? sg.uv16.as<short>() : nullptr;
+    uvs = sg.uv.as<double>();
+    uvf = f32 ? sg.uvf.as<float>() : nullptr;
+    ci = sg.ci.as<int>(); pi = sg.pi.as<int>(); perm = sg.perm.as<int>(); ptr = sg.ptr.as<int>();
 
-    // ---- pass 1 (parallel): range check, order check, conversion with comparison, camera histogram -------------
-    const int parts = h->pool.parts_for(N);
-    std::vector<int> hist((size_t)parts * (size_t)C, 0);
-    std::vector<int64_t> bad((size_t)parts, -1), first_diff((size_t)parts, N);
-    std::vector<char> unsorted((size_t)parts, 0);
-    const int64_t per = (N + parts - 1) / parts;
-    auto convert = [&](const int64_t* ord, int64_t n_compare) {
-        h->pool.run(parts, [&](int t) {
-            const int64_t b = std::min<int64_t>(N, t * per), e = std::min<int64_t>(N, (t + 1) * per);
-            int* hc = hist.data() + (size_t)t * (size_t)C;
-            for (int64_t c = 0; c < C; ++c) hc[c] = 0;
-            int64_t fd = N;
-            for (int64_t k = b; k < e; ++k) {
-                const int64_t s = ord ? ord[k] : k;
-                const int64_t cv = cam[s], pv = pt[s];
-                if (cv < 0 || cv >= C || pv < 0 || pv >= P) { if (bad[t] < 0) bad[t] = s; continue; }
-                if (!ord && k > 0 && pv < pt[k - 1]) unsorted[t] = 1;
-                double u0, u1;
-                if (uv) { u0 = uv[2 * s]; u1 = uv[2 * s + 1]; }
-                else { u0 = (double)uv_i64[2 * s]; u1 = (double)uv_i64[2 * s + 1]; }          // as numpy promotes
-                if (!fixed[(size_t)cv]) ++hc[cv];
-                const bool same = k < n_compare && ci[k] == (int)cv && pi[k] == (int)pv && uvs[2 * k] == u0 && uvs[2 * k + 1] == u1;
-                if (ci16 && !(same && packed_prefix_ok)) {     // (an unchanged entry is packed already, if the previous call packed)
-                    const bool in = std::fabs(u0) < 32768.0 && std::fabs(u1) < 32768.0;
-                    const short q0 = in ? (short)u0 : (short)0, q1 = in ? (short)u1 : (short)0;
-                    if (!in || (double)q0 != u0 || (double)q1 != u1) not16[t] = 1;
-                    ci16[k] = (unsigned short)cv; uv16[2 * k] = q0; uv16[2 * k + 1] = q1;
-                }
-                if (same) continue;
-                if (fd == N) fd = k;
-                ci[k] = (int)cv; pi[k] = (int)pv; uvs[2 * k] = u0; uvs[2 * k + 1] = u1;
-                if (uvf) { uvf[2 * k] = (float)u0; uvf[2 * k + 1] = (float)u1; }    // integer pixels up to 2^24 are exact
-            }
-            first_diff[t] = fd;
-        });
-    };
-    convert(nullptr, n_cmp);
-    auto report_bad = [&]() -> int {
-        for (int t = 0; t < parts; ++t) {
-            const int64_t i = bad[t];
-            if (i < 0) continue;
-            if (cam[i] < 0 || cam[i] >= C)
-                return fail(h, -1, "camera_indices[%lld]=%lld out of range [0,%lld)", (long long)i, (long long)cam[i], (long long)C);
-            return fail(h, -1, "point_indices[%lld]=%lld out of range [0,%lld)", (long long)i, (long long)pt[i], (long long)P);
-        }
-        return 0;
-    };
-    CHK(report_bad());                  // (numpy's fancy indexing would raise IndexError in the reference)
-    bool sorted = true;
+    hist.assign((size_t)parts * (size_t)C, 0);
+    convert(nullptr, n_cmp, packed_prefix_ok);
+    for (int t = 0; t < parts; ++t) {       // (numpy's fancy indexing would raise IndexError in the reference)
+        const int64_t i = bad[t];
+        if (i < 0) continue;
+        if (cam[i] < 0 || cam[i] >= C)
+            return fail(h, -1, "camera_indices[%lld]=%lld out of range [0,%lld)", (long long)i, (long long)cam[i], (long long)C);
+        return fail(h, -1, "point_indices[%lld]=%lld out of range [0,%lld)", (long long)i, (long long)pt[i], (long long)P);
+    }
     for (int t = 0; t < parts; ++t) sorted = sorted && !unsorted[t];
     h->permuted = !sorted;
     h->order.clear();
-    if (!sorted) {                       // any order is accepted; the kernels want point-major.  No re-use on this path.
+    if (!sorted) {                       // No re-use on this path.
         h->order.resize(N);
         std::iota(h->order.begin(), h->order.end(), (int64_t)0);
         std::stable_sort(h->order.begin(), h->order.end(), [&](int64_t a, int64_t b) { return pt[a] < pt[b]; });
-        convert(h->order.data(), 0);
+        convert(h->order.data(), 0, packed_prefix_ok);
     }
-    int64_t fdiff = N;
+    fdiff = N;
     for (int t = 0; t < parts; ++t) fdiff = std::min(fdiff, first_diff[t]);
     fdiff = std::min(fdiff, n_cmp);      // nothing beyond the compared prefix is on the device
     for (size_t k = (size_t)N; k < ldz; ++k) {                       // padding up to the next multiple of 256
@@ -2044,244 +2002,220 @@ static int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, co
         if (uvf) { uvf[2 * k] = 0.f; uvf[2 * k + 1] = 0.f; }
         if (ci16) { ci16[k] = 0; uv16[2 * k] = 0; uv16[2 * k + 1] = 0; }
     }
-    bool packed = try_pack;
-    for (char f : not16) packed = packed && !f;
-    tp1 = now_s();
+    for (char f : not16) facts.pixels_int16 = facts.pixels_int16 && !f;
+    return 0;
+}
 
-    // ---- camera-major order: stable counting sort of the positions by camera (per-part histograms, so that the
-    // parts scatter independently and the order inside a camera stays the point-major one) -----------------------
-    std::vector<int> cam_ptr((size_t)C + 1);
-    {
-        int run = 0;
-        for (int64_t c = 0; c < C; ++c) {
-            cam_ptr[c] = run;
-            for (int t = 0; t < parts; ++t) { int& v = hist[(size_t)t * (size_t)C + c]; const int n = v; v = run; run += n; }
-        }
-        cam_ptr[C] = run;
+// camera-major order: stable counting sort of the positions by camera (per-part histograms, so that the parts scatter
+// independently and the order inside a camera stays the point-major one), and the run offsets of the points
+void ProblemBuild::camera_major_sort() {
+    cam_ptr.resize((size_t)C + 1);
+    int run = 0;
+    for (int64_t c = 0; c < C; ++c) {
+        cam_ptr[c] = run;
+        for (int t = 0; t < parts; ++t) { int& v = hist[(size_t)t * (size_t)C + c]; const int n = v; v = run; run += n; }
     }
-    // ---- pass 2 (parallel): run offsets of the points, camera-major permutation ---------------------------------
-    // ptr[p] = first position whose point index is >= p (pi is non-decreasing): every run start k writes the
-    // entries (pi[k-1], pi[k]], so the parts touch disjoint pieces of ptr.
+    cam_ptr[C] = run;
+    // pass 2 (parallel): ptr[p] = first position whose point index is >= p (pi is non-decreasing): every run start k
+    // writes the entries (pi[k-1], pi[k]], so the parts touch disjoint pieces of ptr.
     // The camera-major order itself is sorted on the DEVICE (k_cam_hist / k_cam_offsets / k_cam_scatter: the same stable
     // order) unless the camera counters do not fit the LDS; the host then only needs the run offsets.
-    // (from 64k observations on: below that the three launches cost more than the host's sort)
-    const bool cm_device = (h->dbg.cm_device == 1 || (h->dbg.cm_device != 0 && N >= 65536)) && sizeof(int) * (size_t)C <= kLdsDynMax;
+    const bool on_host = !plan.cm_device;
     h->pool.run(parts, [&](int t) {
         const int64_t b = std::min<int64_t>(N, t * per), e = std::min<int64_t>(N, (t + 1) * per);
         int* off = hist.data() + (size_t)t * (size_t)C;
         for (int64_t k = b; k < e; ++k) {
             const int lo = k == 0 ? -1 : pi[k - 1];
             for (int q = lo + 1; q <= pi[k]; ++q) ptr[q] = (int)k;
-            if (!cm_device && !fixed[(size_t)ci[k]]) perm[off[ci[k]]++] = (int)k;
+            if (on_host && !fixed[(size_t)ci[k]]) perm[off[ci[k]]++] = (int)k;
         }
     });
     for (int64_t q = (int64_t)pi[N - 1] + 1; q <= P; ++q) ptr[q] = (int)N;
-    ts1 = now_s();
-    if (!cm_device)
+    if (on_host)
         for (size_t k = (size_t)cam_ptr[C]; k < ldz; ++k) perm[k] = 0;  // (shorter than N when cameras are held still)
+}
 
-    for (int k = 0; k < 9; ++k) h->K.k[k] = K[k];
-    h->f32 = f32;
-    h->C = C; h->P = P; h->N = N; h->n = 6 * C + 3 * P;
-    h->N_total = N;
-    h->ld = ld;
-    // wave ranges: cut at point boundaries, >= T observations each
+// wave ranges: cut at point boundaries, >= T observations each
+void ProblemBuild::wave_ranges() {
     const int64_t total_waves = (int64_t)h->n_cu * kWavesPerSweepBlock;
     const int64_t T = std::max<int64_t>(64, (N + total_waves - 1) / total_waves);
     std::vector<int2>& ranges = h->host_ranges;
     ranges.clear();
-    {
-        int64_t start = 0;
-        for (int64_t p = 0; p < P; ++p) {
-            const int64_t endp = ptr[p + 1];
-            if (endp - start >= T || (p == P - 1 && endp > start)) {
-                ranges.push_back(make_int2((int)start, (int)endp));
-                start = endp;
-            }
+    int64_t start = 0;
+    for (int64_t p = 0; p < P; ++p) {
+        const int64_t endp = ptr[p + 1];
+        if (endp - start >= T || (p == P - 1 && endp > start)) {
+            ranges.push_back(make_int2((int)start, (int)endp));
+            start = endp;
         }
     }
     h->n_ranges = (int)ranges.size();
-    ts2 = now_s();
-    // step table of the sweeps: per wave range, batches of <= 64 observations that end on a point
-    // boundary; a point with more than 64 observations is one step of its own
+}
+
+// step table of the sweeps: per wave range, batches of <= 64 observations that end on a point
+// boundary; a point with more than 64 observations is one step of its own
+void ProblemBuild::step_tables() {
+    const std::vector<int2>& ranges = h->host_ranges;
     std::vector<int2>& wsteps = h->host_wsteps;
     std::vector<int2>& steps = h->host_steps;
     wsteps.resize(ranges.size());
     steps.clear();
-    {   // the ranges are independent: every worker walks a slice of them into its own list (the walk is a chain of
-        // dependent reads of pi / ptr -- 1.2-1.4 ms of a 3.6 ms call at 1M observations when one thread did all of it),
-        // the lists are concatenated in range order afterwards
-        const int sparts = (int)std::max<size_t>(1, std::min<size_t>((size_t)parts, ranges.size() / 64));
-        std::vector<std::vector<int2>> local((size_t)sparts);
-        const size_t rper = (ranges.size() + (size_t)sparts - 1) / (size_t)sparts;
-        h->pool.run(sparts, [&](int t) {
-            std::vector<int2>& out = local[(size_t)t];
-            const size_t w0 = std::min(ranges.size(), (size_t)t * rper), w1 = std::min(ranges.size(), w0 + rper);
-            out.reserve((w1 - w0) * 6);
-            for (size_t w = w0; w < w1; ++w) {
-                const int first = (int)out.size();                       // (relative to the slice; rebased below)
-                int64_t pos = ranges[w].x;
-                const int64_t end = ranges[w].y;
-                while (pos < end) {
-                    const int64_t pfirst = pi[pos];
-                    if (ptr[pfirst + 1] - pos > 64) {                    // long run (pos is always a run start)
-                        out.push_back(make_int2((int)pos, (int)(ptr[pfirst + 1] - pos)));
-                        pos = ptr[pfirst + 1];
-                        continue;
-                    }
-                    // largest run boundary <= pos + 64
-                    int64_t lim = std::min<int64_t>(pos + 64, end), cut;
-                    if (lim == end) cut = end;
-                    else { const int64_t pl = pi[lim]; cut = (ptr[pl] == lim) ? lim : ptr[pl]; }   // lim inside a run -> its start
-                    out.push_back(make_int2((int)pos, (int)(cut - pos)));
-                    pos = cut;
+    // the ranges are independent: every worker walks a slice of them into its own list (the walk is a chain of
+    // dependent reads of pi / ptr -- 1.2-1.4 ms of a 3.6 ms call at 1M observations when one thread did all of it),
+    // the lists are concatenated in range order afterwards
+    const int sparts = (int)std::max<size_t>(1, std::min<size_t>((size_t)parts, ranges.size() / 64));
+    std::vector<std::vector<int2>> local((size_t)sparts);
+    const size_t rper = (ranges.size() + (size_t)sparts - 1) / (size_t)sparts;
+    h->pool.run(sparts, [&](int t) {
+        std::vector<int2>& out = local[(size_t)t];
+        const size_t w0 = std::min(ranges.size(), (size_t)t * rper), w1 = std::min(ranges.size(), w0 + rper);
+        out.reserve((w1 - w0) * 6);
+        for (size_t w = w0; w < w1; ++w) {
+            const int first = (int)out.size();                       // (relative to the slice; rebased below)
+            int64_t pos = ranges[w].x;
+            const int64_t end = ranges[w].y;
+            while (pos < end) {
+                const int64_t pfirst = pi[pos];
+                if (ptr[pfirst + 1] - pos > 64) {                    // long run (pos is always a run start)
+                    out.push_back(make_int2((int)pos, (int)(ptr[pfirst + 1] - pos)));
+                    pos = ptr[pfirst + 1];
+                    continue;
                 }
-                wsteps[w] = make_int2(first, (int)out.size() - first);
+                // largest run boundary <= pos + 64
+                int64_t lim = std::min<int64_t>(pos + 64, end), cut;
+                if (lim == end) cut = end;
+                else { const int64_t pl = pi[lim]; cut = (ptr[pl] == lim) ? lim : ptr[pl]; }   // lim inside a run -> its start
+                out.push_back(make_int2((int)pos, (int)(cut - pos)));
+                pos = cut;
             }
-        });
-        size_t total = 0;
-        for (auto& v : local) total += v.size();
-        steps.reserve(total);
-        for (int t = 0; t < sparts; ++t) {
-            const int base = (int)steps.size();
-            const size_t w0 = std::min(ranges.size(), (size_t)t * rper), w1 = std::min(ranges.size(), w0 + rper);
-            for (size_t w = w0; w < w1; ++w) wsteps[w].x += base;
-            steps.insert(steps.end(), local[(size_t)t].begin(), local[(size_t)t].end());
+            wsteps[w] = make_int2(first, (int)out.size() - first);
         }
+    });
+    size_t total = 0;
+    for (auto& v : local) total += v.size();
+    steps.reserve(total);
+    for (int t = 0; t < sparts; ++t) {
+        const int base = (int)steps.size();
+        const size_t w0 = std::min(ranges.size(), (size_t)t * rper), w1 = std::min(ranges.size(), w0 + rper);
+        for (size_t w = w0; w < w1; ++w) wsteps[w].x += base;
+        steps.insert(steps.end(), local[(size_t)t].begin(), local[(size_t)t].end());
     }
     h->n_steps = (int)steps.size();
-    ts3 = now_s();
-    // chunk table of the camera-major kernels: every camera gets at least one chunk (an empty one writes its
-    // zeros), runs longer than chunk_len are cut; one 256-thread workgroup per chunk
+}
+
+// chunk table of the camera-major kernels: every camera gets at least one chunk (an empty one writes its
+// zeros), runs longer than the chunk length are cut; one 256-thread workgroup per chunk
+void ProblemBuild::chunk_tables() {
     std::vector<int4>& chunks = h->host_chunks;
     std::vector<int>& chunk_ptr = h->host_chunk_ptr;
     chunks.clear();
     chunk_ptr.resize((size_t)C + 1);
-    {
-        // a camera of up to 4096 observations is one workgroup (16 per lane) and needs no combine launch
-        int64_t chunk_len = std::max<int64_t>(4096, (N + 2 * h->n_cu - 1) / (2 * h->n_cu));
-        if (h->dbg.cam_chunk > 0) chunk_len = h->dbg.cam_chunk;
-        h->cam_multi = false;
-        for (int64_t c = 0; c < C; ++c) {
-            chunk_ptr[c] = (int)chunks.size();
+    const int64_t chunk_len = plan.cam_chunk_len;
+    for (int64_t c = 0; c < C; ++c) {
+        chunk_ptr[c] = (int)chunks.size();
+        const int b = cam_ptr[c], e = cam_ptr[c + 1];
+        const int nch = std::max<int>(1, (int)((e - b + chunk_len - 1) / chunk_len));
+        if (nch > 1) facts.cam_multi = true;
+        for (int j = 0; j < nch; ++j)
+            chunks.push_back(make_int4((int)c, (int)std::min<int64_t>(e, b + j * chunk_len),
+                                       (int)std::min<int64_t>(e, b + (j + 1) * chunk_len), nch));
+    }
+    chunk_ptr[C] = (int)chunks.size();
+    h->n_chunks = (int)chunks.size();
+    // XCD-aware chunks for pass B of the Schur product (many points).  Every camera-major pass gathers one record
+    // per observation from a table of P x 48 bytes; workgroup i runs on XCD i mod 8 and each XCD has its own 4 MiB
+    // L2: with one chunk per camera every L2 sees the WHOLE table (48 MB at a million points).  A camera's list is
+    // ascending in the point index, so it is cut at the eight point-range boundaries P k / 8: chunk 8 c + k runs on
+    // XCD k and touches points of range k only, each L2 serves an eighth of the table (pass B at 5000 / 1M / 10M:
+    // 201 -> 134 us); the eight partial rows of a camera are added by k_cam_combine and the PCG tail runs behind
+    // it (k_pcg_tail).  Pass B only: the passes with 27 sums per workgroup (K3, rhs + preconditioner) lose more to
+    // eight times as many block reductions than they gain (208 -> 320 us, 188 -> 257 us).
+    std::vector<int4>& chunks_b = h->host_chunks_b;
+    chunks_b.clear();
+    h->host_chunk_ptr_b.clear();
+    if (plan.xcd_b) {
+        // row (8 g + k) 4 + j = camera 4 g + j, range k: the four waves of workgroup 8 g + k (XCD k) take the pieces of
+        // four cameras over the same point range (k_cam_schur_w); cameras behind the last one are padding (camera -1)
+        constexpr int kX = kWaveChunkRanges, kG = kWaveChunkCams;
+        static_assert(kX == 8, "one range per XCD");
+        const int64_t groups = (C + kG - 1) / kG;
+        chunks_b.assign((size_t)(groups * kX * kG), make_int4(-1, 0, 0, kX));
+        for (int64_t c = 0; c < C && !plan.cm_device; ++c) {       // (device-side sort: k_xcd_chunks fills the table)
             const int b = cam_ptr[c], e = cam_ptr[c + 1];
-            const int nch = std::max<int>(1, (int)((e - b + chunk_len - 1) / chunk_len));
-            if (nch > 1) h->cam_multi = true;
-            for (int j = 0; j < nch; ++j)
-                chunks.push_back(make_int4((int)c, (int)std::min<int64_t>(e, b + j * chunk_len),
-                                           (int)std::min<int64_t>(e, b + (j + 1) * chunk_len), nch));
-        }
-        chunk_ptr[C] = (int)chunks.size();
-        h->n_chunks = (int)chunks.size();
-        // XCD-aware chunks for pass B of the Schur product (many points).  Every camera-major pass gathers one record
-        // per observation from a table of P x 48 bytes; workgroup i runs on XCD i mod 8 and each XCD has its own 4 MiB
-        // L2: with one chunk per camera every L2 sees the WHOLE table (48 MB at a million points).  A camera's list is
-        // ascending in the point index, so it is cut at the eight point-range boundaries P k / 8: chunk 8 c + k runs on
-        // XCD k and touches points of range k only, each L2 serves an eighth of the table (pass B at 5000 / 1M / 10M:
-        // 201 -> 134 us); the eight partial rows of a camera are added by k_cam_combine and the PCG tail runs behind
-        // it (k_pcg_tail).  Pass B only: the passes with 27 sums per workgroup (K3, rhs + preconditioner) lose more to
-        // eight times as many block reductions than they gain (208 -> 320 us, 188 -> 257 us).
-        std::vector<int4>& chunks_b = h->host_chunks_b;
-        std::vector<int>& chunk_ptr_b = h->host_chunk_ptr_b;
-        chunks_b.clear();
-        chunk_ptr_b.clear();
-        h->xcd_b = h->dbg.xcd_chunks == 1 || (h->dbg.xcd_chunks != 0 && P >= 250000);
-        if (h->xcd_b) {
-            // row (8 g + k) 4 + j = camera 4 g + j, range k: the four waves of workgroup 8 g + k (XCD k) take the pieces of
-            // four cameras over the same point range (k_cam_schur_w); cameras behind the last one are padding (camera -1)
-            constexpr int kX = kWaveChunkRanges, kG = kWaveChunkCams;
-            static_assert(kX == 8, "one range per XCD");
-            const int64_t groups = (C + kG - 1) / kG;
-            chunks_b.assign((size_t)(groups * kX * kG), make_int4(-1, 0, 0, kX));
-            for (int64_t c = 0; c < C && !cm_device; ++c) {            // (device-side sort: k_xcd_chunks fills the table)
-                const int b = cam_ptr[c], e = cam_ptr[c + 1];
-                int prev = b;
-                for (int k = 0; k < kX; ++k) {
-                    int bound = e;
-                    if (k + 1 < kX) {
-                        const int64_t p_hi = P * (int64_t)(k + 1) / kX;          // first point of the next range
-                        int lo = prev, hi = e;                                   // lower bound over pi[perm[.]] (ascending)
-                        while (lo < hi) { const int mid = (lo + hi) >> 1; if (pi[perm[mid]] < p_hi) lo = mid + 1; else hi = mid; }
-                        bound = lo;
-                    }
-                    chunks_b[(size_t)(((c / kG) * kX + k) * kG + c % kG)] = make_int4((int)c, prev, bound, kX);
-                    prev = bound;
+            int prev = b;
+            for (int k = 0; k < kX; ++k) {
+                int bound = e;
+                if (k + 1 < kX) {
+                    const int64_t p_hi = P * (int64_t)(k + 1) / kX;          // first point of the next range
+                    int lo = prev, hi = e;                                   // lower bound over pi[perm[.]] (ascending)
+                    while (lo < hi) { const int mid = (lo + hi) >> 1; if (pi[perm[mid]] < p_hi) lo = mid + 1; else hi = mid; }
+                    bound = lo;
                 }
+                chunks_b[(size_t)(((c / kG) * kX + k) * kG + c % kG)] = make_int4((int)c, prev, bound, kX);
+                prev = bound;
             }
         }
-        h->n_chunks_b = (int)chunks_b.size();
     }
-    // few cameras: for every block pair (a <= b) the points seen by both cameras, with multiplicity (a point seen
-    // m_a, m_b times contributes m_a m_b times); two counting passes over the runs.  The diagonal pairs' workgroups
-    // also sum the reduced right-hand side of their camera, over the entries that pair an observation with itself.
-    h->dense = 6 * C <= kDenseMaxN && h->dbg.dense != 0;
-    std::vector<int> cov_ptr, cov_pt;
-    std::vector<int2> blk_ab;
-    if (h->dense) {
-        const int nblk = (int)(C * (C + 1) / 2);
-        cov_ptr.assign((size_t)nblk + 1, 0);
-        // (unordered pairs i <= j: a pair of different cameras is one entry of its block, two observations of the same
-        // camera by the same point are two, an observation with itself one -- what the ordered double loop counted)
-        // Two passes over the points, count and fill; from 32k points on split over a few threads by contiguous point
-        // ranges: per-part counts per block, then part t's entries of a block follow part t - 1's -- ascending point order
-        // inside a block, whatever the number of parts.  (Below that size waking the pool costs more than the passes:
-        // measured at the SceauxCastle scale, 0.10 ms single-threaded against 0.13 ms on four threads.)
-        const int pp = P >= 32768 ? 4 : 1;
-        std::vector<int> cnt((size_t)pp * (size_t)nblk, 0);
-        const int64_t pper = (P + pp - 1) / pp;
-        auto each_pair = [&](int t, auto&& visit) {
-            const int64_t p0 = std::min<int64_t>(P, t * pper), p1 = std::min<int64_t>(P, p0 + pper);
-            for (int64_t p = p0; p < p1; ++p)
-                for (int i = ptr[p]; i < ptr[p + 1]; ++i)
-                    for (int j = i; j < ptr[p + 1]; ++j) {
-                        const int a = std::min(ci[i], ci[j]), b = std::max(ci[i], ci[j]);
-                        if (fixed[(size_t)a] || fixed[(size_t)b]) continue;
-                        visit((int)p, dense_block_index(a, b, (int)C), i == j, a == b);
-                    }
-        };
-        h->pool.run(pp, [&](int t) {
-            int* ct = cnt.data() + (size_t)t * (size_t)nblk;
-            each_pair(t, [&](int, int blk, bool self, bool same_cam) { ct[blk] += (self || !same_cam) ? 1 : 2; });
-        });
-        int64_t total = 0;
-        for (int blk = 0; blk < nblk; ++blk) {
-            cov_ptr[(size_t)blk] = (int)std::min<int64_t>(total, INT32_MAX);
-            for (int t = 0; t < pp; ++t) { int& v = cnt[(size_t)t * (size_t)nblk + blk]; const int n_e = v; v = (int)std::min<int64_t>(total, INT32_MAX); total += n_e; }
-        }
-        cov_ptr[(size_t)nblk] = (int)std::min<int64_t>(total, INT32_MAX);
-        if (total > ((int64_t)1 << 26)) h->dense = false;      // very long tracks: the pair lists would not pay
-        else {
-            cov_pt.resize((size_t)std::max<int64_t>(1, total));
-            h->pool.run(pp, [&](int t) {
-                int* fill = cnt.data() + (size_t)t * (size_t)nblk;
-                each_pair(t, [&](int p, int blk, bool self, bool same_cam) {
-                    int& f = fill[blk];
-                    cov_pt[(size_t)f++] = self ? ~p : p;                       // (~p: the term of the right-hand side)
-                    if (!self && same_cam) cov_pt[(size_t)f++] = p;
-                });
-            });
-            blk_ab.resize((size_t)nblk);
-            for (int a = 0; a < (int)C; ++a)
-                for (int b = a; b < (int)C; ++b) blk_ab[(size_t)dense_block_index(a, b, (int)C)] = make_int2(a, b);
-            h->n_blk = nblk;
-        }
-    }
-    tp2 = now_s();
-    h->lds_tab = (size_t)C * kCamRow * sizeof(double) <= kLdsDynMax;
-    h->lds_vec = (size_t)C * 6 * sizeof(double) <= kLdsDynMax;
-    if (h->dbg.tab_lds == 0) h->lds_tab = false;               // test hooks (sfmba_debug_option): force the L2 placements
-    if (h->dbg.vec_lds == 0) h->lds_vec = false;
-    h->sweep_rc = C <= kRcMaxCams && (size_t)C * kRcRow * sizeof(double) <= kLdsDynMax && h->dbg.sweep_rc != 0 &&
-                  h->dbg.sweep_rc != 2;                        // (2: test hook -- the table in global memory whatever the size)
-    h->sweep_rc_g = !h->sweep_rc && h->dbg.sweep_rc != 0;      // too many cameras for the LDS: the table lives in L2
-    h->pcg_fused = (h->lds_vec || h->sweep_rc) && C <= kSweepThreads;
-    if (h->dbg.pcg_fused == 0) h->pcg_fused = false;
-    // fp32 operands in the implicit Schur product: with fp32 storage (BASELINE config 5 names it), or on request
-    h->mixed = (h->sweep_rc || h->sweep_rc_g) && (h->dbg.pcg_mixed == 1 || (h->dbg.pcg_mixed != 0 && f32));
-    h->mixed_b = h->mixed && h->dbg.pcg_mixed_b != 0;
-    h->jfree = h->dbg.jfree == 1 && h->lds_tab;
+    h->n_chunks_b = (int)chunks_b.size();
+}
 
-    // ---- device arrays: grow-only; the index / pixel arrays keep their re-used prefix when they grow -------------
+// few cameras: for every block pair (a <= b) the points seen by both cameras, with multiplicity (a point seen
+// m_a, m_b times contributes m_a m_b times); two counting passes over the runs.  The diagonal pairs' workgroups
+// also sum the reduced right-hand side of their camera, over the entries that pair an observation with itself.
+void ProblemBuild::pair_lists() {
+    if (!plan.dense) return;
+    const int nblk = (int)(C * (C + 1) / 2);
+    cov_ptr.assign((size_t)nblk + 1, 0);
+    // (unordered pairs i <= j: a pair of different cameras is one entry of its block, two observations of the same
+    // camera by the same point are two, an observation with itself one -- what the ordered double loop counted)
+    // Two passes over the points, count and fill; from 32k points on split over a few threads by contiguous point
+    // ranges: per-part counts per block, then part t's entries of a block follow part t - 1's -- ascending point order
+    // inside a block, whatever the number of parts.  (Below that size waking the pool costs more than the passes:
+    // measured at the SceauxCastle scale, 0.10 ms single-threaded against 0.13 ms on four threads.)
+    const int pp = P >= 32768 ? 4 : 1;
+    std::vector<int> cnt((size_t)pp * (size_t)nblk, 0);
+    const int64_t pper = (P + pp - 1) / pp;
+    auto each_pair = [&](int t, auto&& visit) {
+        const int64_t p0 = std::min<int64_t>(P, t * pper), p1 = std::min<int64_t>(P, p0 + pper);
+        for (int64_t p = p0; p < p1; ++p)
+            for (int i = ptr[p]; i < ptr[p + 1]; ++i)
+                for (int j = i; j < ptr[p + 1]; ++j) {
+                    const int a = std::min(ci[i], ci[j]), b = std::max(ci[i], ci[j]);
+                    if (fixed[(size_t)a] || fixed[(size_t)b]) continue;
+                    visit((int)p, dense_block_index(a, b, (int)C), i == j, a == b);
+                }
+    };
+    h->pool.run(pp, [&](int t) {
+        int* ct = cnt.data() + (size_t)t * (size_t)nblk;
+        each_pair(t, [&](int, int blk, bool self, bool same_cam) { ct[blk] += (self || !same_cam) ? 1 : 2; });
+    });
+    int64_t total = 0;
+    for (int blk = 0; blk < nblk; ++blk) {
+        cov_ptr[(size_t)blk] = (int)std::min<int64_t>(total, INT32_MAX);
+        for (int t = 0; t < pp; ++t) { int& v = cnt[(size_t)t * (size_t)nblk + blk]; const int n_e = v; v = (int)std::min<int64_t>(total, INT32_MAX); total += n_e; }
+    }
+    cov_ptr[(size_t)nblk] = (int)std::min<int64_t>(total, INT32_MAX);
+    facts.pair_entries = total;
+    if (total > ((int64_t)1 << 26)) return;                  // very long tracks: the pair lists would not pay (-> PCG)
+    cov_pt.resize((size_t)std::max<int64_t>(1, total));
+    h->pool.run(pp, [&](int t) {
+        int* fill = cnt.data() + (size_t)t * (size_t)nblk;
+        each_pair(t, [&](int p, int blk, bool self, bool same_cam) {
+            int& f = fill[blk];
+            cov_pt[(size_t)f++] = self ? ~p : p;                       // (~p: the term of the right-hand side)
+            if (!self && same_cam) cov_pt[(size_t)f++] = p;
+        });
+    });
+    blk_ab.resize((size_t)nblk);
+    for (int a = 0; a < (int)C; ++a)
+        for (int b = a; b < (int)C; ++b) blk_ab[(size_t)dense_block_index(a, b, (int)C)] = make_int2(a, b);
+    h->n_blk = nblk;
+}
+
+// device arrays: grow-only; the index / pixel arrays keep their re-used prefix when they grow
+int ProblemBuild::allocate() {
+    const Forms& f = h->forms;
+    auto& sg = h->stage;
     const size_t esz = f32 ? sizeof(float) : sizeof(double);     // element size of the per-observation streams
     const size_t keep = (size_t)fdiff;
     HIPCHK(h, h->cam_idx.ensure_keep(sizeof(int) * ldz, sizeof(int) * keep));
@@ -2289,21 +2223,23 @@ static int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, co
     HIPCHK(h, h->uv.ensure_keep(esz * 2 * ldz, esz * 2 * keep));
     // run offsets of the points before the first changed observation's point are unchanged
     // (entries up to the point of the last unchanged observation are determined by unchanged positions alone)
-    const int64_t p_keep = keep == 0 ? 0 : std::min<int64_t>(std::min<int64_t>(prev.P, P), (int64_t)pi[fdiff - 1] + 1);
+    p_keep = keep == 0 ? 0 : std::min<int64_t>(std::min<int64_t>(h->prev.P, P), (int64_t)pi[fdiff - 1] + 1);
     HIPCHK(h, h->pt_ptr.ensure_keep(sizeof(int) * ((size_t)P + 1), sizeof(int) * (size_t)p_keep));
     // the structure tables: one device buffer, one pinned staging buffer, one copy
     struct Piece { const void* src; size_t bytes; DevView* view; size_t off; };
     Piece pieces[11] = {
         {cam_ptr.data(), sizeof(int) * cam_ptr.size(), &h->cam_ptr_dev, 0},
-        {ranges.data(), sizeof(int2) * ranges.size(), &h->ranges, 0}, {wsteps.data(), sizeof(int2) * wsteps.size(), &h->wsteps, 0},
-        {steps.data(), sizeof(int2) * steps.size(), &h->steps, 0}, {chunks.data(), sizeof(int4) * chunks.size(), &h->cam_chunks, 0},
-        {chunk_ptr.data(), sizeof(int) * chunk_ptr.size(), &h->cam_chunk_ptr, 0},
-        {cov_ptr.data(), h->dense ? sizeof(int) * cov_ptr.size() : 0, &h->cov_ptr, 0},
-        {cov_pt.data(), h->dense ? sizeof(int) * cov_pt.size() : 0, &h->cov_pt, 0},
-        {blk_ab.data(), h->dense ? sizeof(int2) * blk_ab.size() : 0, &h->blk_ab, 0},
+        {h->host_ranges.data(), sizeof(int2) * h->host_ranges.size(), &h->ranges, 0},
+        {h->host_wsteps.data(), sizeof(int2) * h->host_wsteps.size(), &h->wsteps, 0},
+        {h->host_steps.data(), sizeof(int2) * h->host_steps.size(), &h->steps, 0},
+        {h->host_chunks.data(), sizeof(int4) * h->host_chunks.size(), &h->cam_chunks, 0},
+        {h->host_chunk_ptr.data(), sizeof(int) * h->host_chunk_ptr.size(), &h->cam_chunk_ptr, 0},
+        {cov_ptr.data(), f.dense ? sizeof(int) * cov_ptr.size() : 0, &h->cov_ptr, 0},
+        {cov_pt.data(), f.dense ? sizeof(int) * cov_pt.size() : 0, &h->cov_pt, 0},
+        {blk_ab.data(), f.dense ? sizeof(int2) * blk_ab.size() : 0, &h->blk_ab, 0},
         {h->host_chunks_b.data(), sizeof(int4) * h->host_chunks_b.size(), &h->cam_chunks_b, 0},
         {h->host_chunk_ptr_b.data(), sizeof(int) * h->host_chunk_ptr_b.size(), &h->cam_chunk_ptr_b, 0}};
-    size_t tables_bytes = 0;
+    tables_bytes = 0;
     for (auto& pc : pieces) { pc.off = tables_bytes; tables_bytes += (pc.bytes + 255) / 256 * 256; }
     HIPCHK(h, h->tables.ensure(tables_bytes + 256));
     HIPCHK(h, sg.tables.ensure(tables_bytes + 256, 0));
@@ -2311,75 +2247,48 @@ static int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, co
         if (pc.bytes) memcpy(sg.tables.as<char>() + pc.off, pc.src, pc.bytes);
         pc.view->p = h->tables.as<char>() + pc.off;
     }
-    HIPCHK(h, h->xa.ensure(sizeof(double) * h->n));
-    HIPCHK(h, h->xb.ensure(sizeof(double) * h->n));
-    HIPCHK(h, h->tabA.ensure(sizeof(double) * cam_table_doubles((int)C)));
-    HIPCHK(h, h->tabB.ensure(sizeof(double) * cam_table_doubles((int)C)));
-    HIPCHK(h, h->r.ensure(esz * 2 * ldz));
-    HIPCHK(h, h->J.ensure(esz * 12 * ldz));
-    HIPCHK(h, h->cm_perm.ensure(sizeof(int) * ldz));
-    HIPCHK(h, h->cm_pt.ensure(sizeof(int) * ldz));
-    HIPCHK(h, h->cm_uv.ensure(esz * 2 * ldz));
-    HIPCHK(h, h->cam_partial.ensure(sizeof(double) * std::max<size_t>(27 * chunks.size(), 27 * h->host_chunks_b.size())));
-    HIPCHK(h, h->recA.ensure(sizeof(double) * kRec * P));
-    HIPCHK(h, h->recB.ensure(sizeof(double) * kRec * P));
-    // One 128-byte gather record per point for k_cam_rhs_diag pays once the point tables no longer sit in the L2s
-    // (1M points: 432 -> 188 us); at 100k points the two 4.8 MB tables it replaces are L2-resident and k_prep's 11 MB of
-    // extra writes cost what the pass gains (DESIGN.md section 5)
-    h->use_rhsrec = h->dbg.rhsrec == 1 || (h->dbg.rhsrec != 0 && P >= 250000);
-    if (h->use_rhsrec) HIPCHK(h, h->rhsrec.ensure(sizeof(double) * kRhsRec * P));
-    if (h->dense) {
-        HIPCHK(h, h->Sblk.ensure(sizeof(double) * 36 * blk_ab.size()));
-    }
-    HIPCHK(h, h->t1.ensure(esz * 2 * ldz));
-    HIPCHK(h, h->V.ensure(sizeof(double) * 6 * P));
-    HIPCHK(h, h->Vinv.ensure(sizeof(double) * (kVinvInRec < 0 ? kVinvRow * P : 8)));
-    HIPCHK(h, h->gp.ensure(sizeof(double) * 3 * P + 16));      // (+16: zeroed in 16-byte units)
-    HIPCHK(h, h->edge.ensure(sizeof(double) * 2 * kEdgeRow * (size_t)((N + 63) / 64)));
-    HIPCHK(h, h->e.ensure(sizeof(double) * 3 * P));
-    HIPCHK(h, h->g.ensure(sizeof(double) * h->n));
-    HIPCHK(h, h->si.ensure(sizeof(double) * h->n));
-    HIPCHK(h, h->sg.ensure(sizeof(double) * h->n));
-    HIPCHK(h, h->g2.ensure(sizeof(double) * h->n));
-    HIPCHK(h, h->si2.ensure(sizeof(double) * h->n));
-    HIPCHK(h, h->sg2.ensure(sizeof(double) * h->n));
-    h->g_cur = static_cast<double*>(h->g.p); h->si_cur = static_cast<double*>(h->si.p); h->sg_cur = static_cast<double*>(h->sg.p);
+    const size_t n8 = sizeof(double) * (size_t)h->n, cam_tab = sizeof(double) * cam_table_doubles((int)C);
+    const struct { DevBuf* buf; size_t bytes; } sized[] = {
+        {&h->xa, n8}, {&h->xb, n8}, {&h->tabA, cam_tab}, {&h->tabB, cam_tab}, {&h->r, esz * 2 * ldz}, {&h->J, esz * 12 * ldz},
+        {&h->cm_perm, sizeof(int) * ldz}, {&h->cm_pt, sizeof(int) * ldz}, {&h->cm_uv, esz * 2 * ldz},
+        {&h->cam_partial, sizeof(double) * std::max<size_t>(27 * h->host_chunks.size(), 27 * h->host_chunks_b.size())},
+        {&h->recA, sizeof(double) * kRec * P}, {&h->recB, sizeof(double) * kRec * P},
+        {&h->rhsrec, f.use_rhsrec ? sizeof(double) * kRhsRec * P : 0}, {&h->Sblk, f.dense ? sizeof(double) * 36 * blk_ab.size() : 0},
+        {&h->t1, esz * 2 * ldz}, {&h->V, sizeof(double) * 6 * P}, {&h->Vinv, sizeof(double) * (kVinvInRec < 0 ? kVinvRow * P : 8)},
+        {&h->gp, sizeof(double) * 3 * P + 16},                  // (+16: zeroed in 16-byte units)
+        {&h->edge, sizeof(double) * 2 * kEdgeRow * (size_t)((N + 63) / 64)}, {&h->e, sizeof(double) * 3 * P},
+        {&h->g, n8}, {&h->si, n8}, {&h->sg, n8}, {&h->g2, n8}, {&h->si2, n8}, {&h->sg2, n8}, {&h->p, n8 + 16},
+        {&h->Dc, sizeof(double) * 6 * C}, {&h->Minv, sizeof(double) * 21 * C}, {&h->vecs, sizeof(double) * 2 * kPcgVecs * 6 * C},
+        {&h->vtmp, sizeof(double) * 6 * C}, {&h->vcm, sizeof(double) * 6 * C},
+        {&h->rctab, f.sweep_rc_g ? sizeof(double) * kRcRow * (size_t)C : 0},
+        {&h->rt32, f.mixed ? sizeof(float) * kRt32 * (size_t)C : 0}, {&h->rtd, f.mixed ? sizeof(double) * kRt32 * (size_t)C : 0},
+        {&h->rec32, f.mixed ? sizeof(float) * kRec32 * (size_t)P : 0},
+        {&h->rctab32, f.mixed && f.sweep_rc_g ? sizeof(float) * kRc32Row * (size_t)C : 0},
+        {&h->part, sizeof(double) * (size_t)(2 * kPartRows * kNQ)}, {&h->ctrl, 2 * sizeof(PcgCtrl)},
+        {&h->pcg_part, sizeof(double) * 4 * C}, {&h->arena_own, sizeof(double) * (size_t)sfmba_exchange_doubles(C)}};
+    for (const auto& b : sized)
+        if (b.bytes) HIPCHK(h, b.buf->ensure(b.bytes));         // (0: a form that is not taken needs no buffer)
+    h->g_cur = h->g.as<double>(); h->si_cur = h->si.as<double>(); h->sg_cur = h->sg.as<double>();
     h->g_new = h->g2.as<double>(); h->si_new = h->si2.as<double>(); h->sg_new = h->sg2.as<double>();
-    HIPCHK(h, h->p.ensure(sizeof(double) * h->n + 16));
-    HIPCHK(h, h->Dc.ensure(sizeof(double) * 6 * C));
-    HIPCHK(h, h->Minv.ensure(sizeof(double) * 21 * C));
-    HIPCHK(h, h->vecs.ensure(sizeof(double) * 2 * kPcgVecs * 6 * C));
-    HIPCHK(h, h->vtmp.ensure(sizeof(double) * 6 * C));
-    HIPCHK(h, h->vcm.ensure(sizeof(double) * 6 * C));
-    if (h->sweep_rc_g) HIPCHK(h, h->rctab.ensure(sizeof(double) * kRcRow * (size_t)C));
-    if (h->mixed) {
-        HIPCHK(h, h->rt32.ensure(sizeof(float) * kRt32 * (size_t)C));
-        HIPCHK(h, h->rtd.ensure(sizeof(double) * kRt32 * (size_t)C));
-        HIPCHK(h, h->rec32.ensure(sizeof(float) * kRec32 * (size_t)P));
-        if (h->sweep_rc_g) HIPCHK(h, h->rctab32.ensure(sizeof(float) * kRc32Row * (size_t)C));
-    }
     // k_update_scale: cameras one element per thread, points kScalePts points per thread (all loads of a thread in flight
     // together); at most 1024 partial rows, summed by k_jdot's rider workgroup
     h->scale_pts = P >= 65536 ? 2 : 1;
     h->red_bc = grid_1d(6 * C, 256, 32);
     h->red_grid = h->red_bc + grid_1d(P, 256 * h->scale_pts, 992);
-    HIPCHK(h, h->part.ensure(sizeof(double) * (size_t)(2 * kPartRows * kNQ)));
-    HIPCHK(h, h->ctrl.ensure(2 * sizeof(PcgCtrl)));
-    HIPCHK(h, h->pcg_part.ensure(sizeof(double) * 4 * C));
-    HIPCHK(h, h->arena_own.ensure(sizeof(double) * (size_t)sfmba_exchange_doubles(C)));
     h->arena = h->arena_own.as<double>();
     h->ar_fn = nullptr; h->ar_ctx = nullptr;
     h->x = h->xa.as<double>(); h->x_new = h->xb.as<double>();
     h->tab = h->tabA.as<double>(); h->tab_new = h->tabB.as<double>();
     h->rec = h->recA.as<double>(); h->rec_new = h->recB.as<double>();
+    return 0;
+}
 
-    // ---- uploads: observations from the first changed one on, run offsets from its point on, structure tables ----
-    auto up = [&](void* dst, const void* src, size_t elem, size_t from, size_t to) -> hipError_t {
-        if (to <= from) return hipSuccess;
-        return hipMemcpyAsync(static_cast<char*>(dst) + elem * from, static_cast<const char*>(src) + elem * from,
-                              elem * (to - from), hipMemcpyHostToDevice, h->stream);
-    };
-    if (packed) {
+// uploads: observations from the first changed one on, run offsets from its point on, structure tables; then every
+// zero-initialised array in ONE launch
+int ProblemBuild::upload_and_zero() {
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    const size_t keep = (size_t)fdiff;
+    if (h->forms.packed_upload) {
         HIPCHK(h, h->ci16_dev.ensure(sizeof(unsigned short) * ldz));
         HIPCHK(h, h->uv16_dev.ensure(sizeof(short) * 2 * ldz));
         HIPCHK(h, up(h->ci16_dev.p, ci16, sizeof(unsigned short), keep, ldz));
@@ -2390,77 +2299,109 @@ static int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, co
         HIPCHK(h, up(h->uv.p, f32 ? (const void*)uvf : (const void*)uvs, 2 * esz, keep, ldz));
     }
     HIPCHK(h, up(h->pt_ptr.p, ptr, sizeof(int), (size_t)p_keep, (size_t)P + 1));
-    if (packed) {
-        if (keep < ldz) {
-            hipLaunchKernelGGL(k_unpack_obs, dim3((unsigned)((ldz - keep + 255) / 256)), dim3(256), 0, h->stream,
-                               (const unsigned short*)h->ci16_dev.as<unsigned short>(), (const short2*)h->uv16_dev.as<short2>(),
-                               (int)keep, (int)ldz, f32 ? 1 : 0, h->cam_idx.as<int>(), h->uv.as<double>());
-            LAUNCHED(h);
-            hipLaunchKernelGGL(k_expand_pt_idx, dim3((unsigned)((P + 1 + 255) / 256)), dim3(256), 0, h->stream,
-                               (const int*)h->pt_ptr.as<int>(), (int)P, (int)N, (int)ld, h->pt_idx.as<int>());
-            LAUNCHED(h);
-        }
+    if (h->forms.packed_upload && keep < ldz) {
+        hipLaunchKernelGGL(k_unpack_obs, dim3((unsigned)((ldz - keep + 255) / 256)), dim3(256), 0, h->stream,
+                           (const unsigned short*)h->ci16_dev.as<unsigned short>(), (const short2*)h->uv16_dev.as<short2>(),
+                           (int)keep, (int)ldz, f32 ? 1 : 0, h->cam_idx.as<int>(), h->uv.as<double>());
+        LAUNCHED(h);
+        hipLaunchKernelGGL(k_expand_pt_idx, dim3((unsigned)((P + 1 + 255) / 256)), dim3(256), 0, h->stream,
+                           (const int*)h->pt_ptr.as<int>(), (int)P, (int)N, (int)ld, h->pt_idx.as<int>());
+        LAUNCHED(h);
     }
     h->obs_reused = fdiff;
     h->obs_uploaded = ld - fdiff;
-    if (!(fdiff == N && n_cmp == N && prev.N == N && prev.P == P && h->C == C)) ++h->problem_gen;
-    HIPCHK(h, hipMemcpyAsync(h->tables.p, sg.tables.p, tables_bytes, hipMemcpyHostToDevice, h->stream));
-    {   // every zero-initialised array in ONE launch: the exchange arena; V, g_p (points without observations are never
-        // written by the normal-block kernels: their blocks must be 0) and p (... and their step is 0); r; the point records
-        ZeroJob z{};
-        auto put = [&](int k, void* ptr_, size_t bytes) { z.p[k] = ptr_; z.n16[k] = (int64_t)(bytes / 16); };
-        put(0, h->arena, sizeof(double) * (size_t)sfmba_exchange_doubles(C));
-        put(1, h->V.p, sizeof(double) * 6 * P);
-        put(2, h->gp.p, (sizeof(double) * 3 * P + 15) / 16 * 16);
-        put(3, h->p.p, (sizeof(double) * h->n + 15) / 16 * 16);
-        put(4, h->r.p, esz * 2 * ldz);
-        put(5, h->recA.p, sizeof(double) * kRec * P);
-        put(6, h->recB.p, sizeof(double) * kRec * P);
-        int64_t most = 0;
-        for (int k = 0; k < 7; ++k) most = std::max(most, z.n16[k]);
-        hipLaunchKernelGGL(k_zero_many, dim3((unsigned)grid_1d(most, 256 * 4, 2048), 7), dim3(256), 0, h->stream, z);
-        LAUNCHED(h);
-    }
-    if (cm_device) {
-        const int B = (int)std::min<int64_t>(kSortSlices, (N + 63) / 64);
-        const int per_slice = (int)(((N + B - 1) / B + 63) / 64 * 64);
-        int key_bits = 0;
-        while (((int64_t)1 << key_bits) < C) ++key_bits;
-        HIPCHK(h, h->sort_hist.ensure(sizeof(int) * 2 * (size_t)B * (size_t)C));          // counts | offsets
-        int* sort_off = h->sort_hist.as<int>() + (size_t)B * (size_t)C;
-        const unsigned char* fixed_dev = nullptr;
-        if (h->n_fixed > 0) {
-            HIPCHK(h, h->fixed_dev.ensure((size_t)C));
-            HIPCHK(h, hipMemcpyAsync(h->fixed_dev.p, fixed.data(), (size_t)C, hipMemcpyHostToDevice, h->stream));
-            fixed_dev = h->fixed_dev.as<unsigned char>();
-        }
-        const size_t lds = sizeof(int) * (size_t)C;
-        CHK(set_lds(h, k_cam_hist, lds));
-        CHK(set_lds(h, k_cam_scatter, lds));
-        hipLaunchKernelGGL(k_cam_hist, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(), fixed_dev, (int)N, (int)C,
-                           per_slice, h->sort_hist.as<int>());
-        LAUNCHED(h);
-        hipLaunchKernelGGL(k_cam_offsets, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->sort_hist.as<int>(),
-                           (const int*)h->cam_ptr_dev.as<int>(), B, (int)C, sort_off);
-        LAUNCHED(h);
-        hipLaunchKernelGGL(k_cam_scatter, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(), fixed_dev,
-                           (const int*)h->pt_idx.as<int>(), (const double*)h->uv.as<double>(), f32 ? 1 : 0, (int)N, (int)C, per_slice,
-                           key_bits, (const int*)sort_off, h->cm_pt.as<int>(), h->cm_uv.as<double>());
-        LAUNCHED(h);
-        if (h->xcd_b) {
-            hipLaunchKernelGGL(k_xcd_chunks, dim3((unsigned)((h->n_chunks_b + 255) / 256)), dim3(256), 0, h->stream,
-                               (const int*)h->cam_ptr_dev.as<int>(), (const int*)h->cm_pt.as<int>(), (int)C, (int)P,
-                               h->cam_chunks_b.as<int4>());
-            LAUNCHED(h);
-        }
-    } else {
+    if (!(fdiff == N && n_cmp == N && h->prev.N == N && h->prev.P == P)) ++h->problem_gen;
+    HIPCHK(h, hipMemcpyAsync(h->tables.p, h->stage.tables.p, tables_bytes, hipMemcpyHostToDevice, h->stream));
+    // zeroed: the exchange arena; V, g_p (points without observations are never written by the normal-block kernels:
+    // their blocks must be 0) and p (... and their step is 0); r; the point records
+    ZeroJob z{};
+    auto put = [&](int k, void* ptr_, size_t bytes) { z.p[k] = ptr_; z.n16[k] = (int64_t)(bytes / 16); };
+    put(0, h->arena, sizeof(double) * (size_t)sfmba_exchange_doubles(C));
+    put(1, h->V.p, sizeof(double) * 6 * P);
+    put(2, h->gp.p, (sizeof(double) * 3 * P + 15) / 16 * 16);
+    put(3, h->p.p, (sizeof(double) * h->n + 15) / 16 * 16);
+    put(4, h->r.p, esz * 2 * ldz);
+    put(5, h->recA.p, sizeof(double) * kRec * P);
+    put(6, h->recB.p, sizeof(double) * kRec * P);
+    int64_t most = 0;
+    for (int k = 0; k < 7; ++k) most = std::max(most, z.n16[k]);
+    hipLaunchKernelGGL(k_zero_many, dim3((unsigned)grid_1d(most, 256 * 4, 2048), 7), dim3(256), 0, h->stream, z);
+    LAUNCHED(h);
+    return 0;
+}
+
+// the camera-major copies of point index and pixel: sorted on the device, or gathered through the host's permutation
+int ProblemBuild::enqueue_camera_major() {
+    if (!h->forms.cm_device) {
         HIPCHK(h, hipMemcpyAsync(h->cm_perm.p, perm, sizeof(int) * ldz, hipMemcpyHostToDevice, h->stream));
         hipLaunchKernelGGL(k_build_cam_major, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->cm_perm.as<int>(),
                            h->pt_idx.as<int>(), h->uv.as<double>(), f32 ? 1 : 0, (int)N, h->cm_pt.as<int>(),
                            h->cm_uv.as<double>());
         LAUNCHED(h);
+        return 0;
     }
-    tp3 = now_s();
+    const int B = (int)std::min<int64_t>(kSortSlices, (N + 63) / 64);
+    const int per_slice = (int)(((N + B - 1) / B + 63) / 64 * 64);
+    int key_bits = 0;
+    while (((int64_t)1 << key_bits) < C) ++key_bits;
+    HIPCHK(h, h->sort_hist.ensure(sizeof(int) * 2 * (size_t)B * (size_t)C));          // counts | offsets
+    int* sort_off = h->sort_hist.as<int>() + (size_t)B * (size_t)C;
+    const unsigned char* fixed_dev = nullptr;
+    if (h->n_fixed > 0) {
+        HIPCHK(h, h->fixed_dev.ensure((size_t)C));
+        HIPCHK(h, hipMemcpyAsync(h->fixed_dev.p, fixed.data(), (size_t)C, hipMemcpyHostToDevice, h->stream));
+        fixed_dev = h->fixed_dev.as<unsigned char>();
+    }
+    const size_t lds = sizeof(int) * (size_t)C;
+    CHK(set_lds(h, k_cam_hist, lds));
+    CHK(set_lds(h, k_cam_scatter, lds));
+    hipLaunchKernelGGL(k_cam_hist, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(), fixed_dev, (int)N, (int)C,
+                       per_slice, h->sort_hist.as<int>());
+    LAUNCHED(h);
+    hipLaunchKernelGGL(k_cam_offsets, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->sort_hist.as<int>(),
+                       (const int*)h->cam_ptr_dev.as<int>(), B, (int)C, sort_off);
+    LAUNCHED(h);
+    hipLaunchKernelGGL(k_cam_scatter, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(), fixed_dev,
+                       (const int*)h->pt_idx.as<int>(), (const double*)h->uv.as<double>(), f32 ? 1 : 0, (int)N, (int)C, per_slice,
+                       key_bits, (const int*)sort_off, h->cm_pt.as<int>(), h->cm_uv.as<double>());
+    LAUNCHED(h);
+    if (h->forms.xcd_b) {
+        hipLaunchKernelGGL(k_xcd_chunks, dim3((unsigned)((h->n_chunks_b + 255) / 256)), dim3(256), 0, h->stream,
+                           (const int*)h->cam_ptr_dev.as<int>(), (const int*)h->cm_pt.as<int>(), (int)C, (int)P,
+                           h->cam_chunks_b.as<int4>());
+        LAUNCHED(h);
+    }
+    return 0;
+}
+
+int ProblemBuild::run() {
+    const bool timing = h->dbg.trace_timing != 0;
+    const double tp0 = now_s();
+    h->have_problem = false;
+    h->solved = false;
+    CHK(check_and_reset());
+    plan = decide_problem_forms(C, P, N, f32, h->n_cu, ProblemFacts{}, h->dbg);
+    CHK(convert_and_compare());
+    const double tp1 = now_s();
+    camera_major_sort();
+    const double ts1 = now_s();
+    for (int k = 0; k < 9; ++k) h->K.k[k] = K[k];
+    h->f32 = f32;
+    h->C = C; h->P = P; h->N = N; h->n = 6 * C + 3 * P;
+    h->N_total = N;
+    h->ld = ld;
+    wave_ranges();
+    const double ts2 = now_s();
+    step_tables();
+    const double ts3 = now_s();
+    chunk_tables();
+    pair_lists();
+    const double tp2 = now_s();
+    h->forms = decide_problem_forms(C, P, N, f32, h->n_cu, facts, h->dbg);      // THE decision: the facts are in
+    CHK(allocate());
+    CHK(upload_and_zero());
+    CHK(enqueue_camera_major());
+    const double tp3 = now_s();
     HIPCHK(h, hipStreamSynchronize(h->stream));     // the host tables are rebuilt by the next call
     if (timing)
         fprintf(stderr, "sfmba: set_problem  structure = run offsets + camera-major permutation %.2f ms, wave ranges %.2f ms, step table %.2f ms, "
@@ -2469,15 +2410,52 @@ static int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, co
         fprintf(stderr, "sfmba: set_problem  convert+compare %.2f ms  structure %.2f ms  allocate+enqueue %.2f ms  upload wait %.2f ms"
                         "  (%lld of %lld observations re-used)\n",
                 1e3 * (tp1 - tp0), 1e3 * (tp2 - tp1), 1e3 * (tp3 - tp2), 1e3 * (now_s() - tp3), (long long)fdiff, (long long)N);
+    auto& prev = h->prev;
     if (sorted) { prev.valid = true; prev.f32 = f32; prev.N = N; prev.P = P; }
-    prev.packed = sorted && packed;
+    prev.packed = sorted && h->forms.packed_upload;
     h->have_problem = true;
     return 0;
 }
 
+int set_problem_impl(sfmba_handle* h, int64_t C, int64_t P, int64_t N, const int64_t* cam, const int64_t* pt,
+                     const double* uv, const int64_t* uv_i64, const double* K) {
+    CHK(enter(h));
+    ProblemBuild b{h, C, P, N, cam, pt, uv, uv_i64, K};
+    return b.run();
+}
+}  // namespace
+
+int sfmba_set_problem(sfmba_handle* h, int64_t C, int64_t P, int64_t N, const int64_t* cam, const int64_t* pt,
+                      const double* uv, const double* K) {
+    return set_problem_impl(h, C, P, N, cam, pt, uv, nullptr, K);
+}
+
+int sfmba_set_problem_i64(sfmba_handle* h, int64_t C, int64_t P, int64_t N, const int64_t* cam, const int64_t* pt,
+                          const int64_t* uv, const double* K) {
+    return set_problem_impl(h, C, P, N, cam, pt, nullptr, uv, K);
+}
+
+namespace {
+// test / timing entries: x on the device, its camera table and point records, residual + Jacobian, normal blocks
+int linearise_at(sfmba_handle* h, const double* x, bool blocks = true) {
+    CHK(upload_x(h, x));
+    CHK(launch_cam_table(h, h->x, h->tab, h->rec));
+    int np = 0;
+    CHK((launch_resjac<true, true>(h, h->x, h->tab, &np)));
+    return blocks ? launch_normal_blocks(h, h->tab, h->rec) : 0;
+}
+// k_point_prep: V_p^-1 and the point records' z half outside a solve (inside one, k_prep does this work)
+int launch_point_prep(sfmba_handle* h, const double* si_pts, const double* e_in, double reg, double* z_out, const double* pts, double* rhsrec) {
+    hipLaunchKernelGGL(k_point_prep, dim3((h->P + 255) / 256), dim3(256), 0, h->stream, h->V.as<double>(),
+                       h->gp.as<double>(), si_pts, e_in, (int)h->P, reg, vinv_ptr(h), z_out, pts, rhsrec);
+    LAUNCHED(h);
+    return 0;
+}
+}  // namespace
+
 int sfmba_residuals(sfmba_handle* h, const double* x, double* r_out) {
     CHK(enter(h));
-    CHK(check_ready(h, x));
+    CHK(begin_compute(h, x));
     if (!r_out) return fail(h, -1, "r_out is NULL");
     CHK(upload_x(h, x));
     CHK(launch_cam_table(h, h->x, h->tab, h->rec));
@@ -2488,7 +2466,7 @@ int sfmba_residuals(sfmba_handle* h, const double* x, double* r_out) {
 
 int sfmba_residual_jacobian(sfmba_handle* h, const double* x, double* r_out, double* Jc_out, double* Jp_out) {
     CHK(enter(h));
-    CHK(check_ready(h, x));
+    CHK(begin_compute(h, x));
     if (!r_out || !Jc_out || !Jp_out) return fail(h, -1, "NULL output");
     CHK(upload_x(h, x));
     CHK(launch_cam_table(h, h->x, h->tab, h->rec));
@@ -2515,12 +2493,8 @@ int sfmba_residual_jacobian(sfmba_handle* h, const double* x, double* r_out, dou
 
 int sfmba_normal_blocks(sfmba_handle* h, const double* x, double* U, double* V, double* gc, double* gp) {
     CHK(enter(h));
-    CHK(check_ready(h, x));
-    CHK(upload_x(h, x));
-    CHK(launch_cam_table(h, h->x, h->tab, h->rec));
-    int np = 0;
-    CHK((launch_resjac<true, true>(h, h->x, h->tab, &np)));
-    CHK(launch_normal_blocks(h, h->x, h->tab, h->rec));
+    CHK(begin_compute(h, x));
+    CHK(linearise_at(h, x));
     std::vector<double> ugc(27 * h->C);
     HIPCHK(h, hipMemcpyAsync(ugc.data(), h->Ugc(), sizeof(double) * 27 * h->C, hipMemcpyDeviceToHost, h->stream));
     if (V) HIPCHK(h, hipMemcpyAsync(V, h->V.p, sizeof(double) * 6 * h->P, hipMemcpyDeviceToHost, h->stream));
@@ -2535,13 +2509,9 @@ int sfmba_normal_blocks(sfmba_handle* h, const double* x, double* U, double* V, 
 
 int sfmba_schur_matvec(sfmba_handle* h, const double* x, const double* dc, const double* dp, const double* v, double* y) {
     CHK(enter(h));
-    CHK(check_ready(h, x));
+    CHK(begin_compute(h, x));
     if (!dc || !dp || !v || !y) return fail(h, -1, "NULL argument");
-    CHK(upload_x(h, x));
-    CHK(launch_cam_table(h, h->x, h->tab, h->rec));
-    int np = 0;
-    CHK((launch_resjac<true, true>(h, h->x, h->tab, &np)));
-    CHK(launch_normal_blocks(h, h->x, h->tab, h->rec));
+    CHK(linearise_at(h, x));
     // stage dp in e (as explicit diagonal), v in pk -- camera vectors are plane-major on the device
     const int64_t C = h->C;
     std::vector<double> vp(6 * C);
@@ -2549,10 +2519,7 @@ int sfmba_schur_matvec(sfmba_handle* h, const double* x, const double* dc, const
         for (int k = 0; k < 6; ++k) vp[k * C + c] = v[6 * c + k];
     HIPCHK(h, hipMemcpyAsync(h->e.p, dp, sizeof(double) * 3 * h->P, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->vtmp.p, vp.data(), sizeof(double) * 6 * C, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_point_prep, dim3((h->P + 255) / 256), dim3(256), 0, h->stream, h->V.as<double>(),
-                       h->gp.as<double>(), (const double*)nullptr, h->e.as<double>(), (int)h->P, 0.0,
-                       vinv_ptr(h), (double*)nullptr, (const double*)nullptr, (double*)nullptr);
-    LAUNCHED(h);
+    CHK(launch_point_prep(h, nullptr, h->e.as<double>(), 0.0, nullptr, nullptr, nullptr));
     CHK(launch_mixed_prep(h, h->x, h->tab));
     CHK(schur_product_standalone(h, h->vtmp.as<double>()));
     CHK(exchange(h, h->acc(), 6 * C, 0));
@@ -2568,15 +2535,11 @@ int sfmba_schur_matvec(sfmba_handle* h, const double* x, const double* dc, const
 int sfmba_dense_schur(sfmba_handle* h, const double* x, const double* dc, const double* dp, const double* rhs,
                       double* S_out, double* sol_out) {
     CHK(enter(h));
-    CHK(check_ready(h, x));
+    CHK(begin_compute(h, x));
     if (!dc || !dp || !rhs || !sol_out) return fail(h, -1, "NULL argument");
-    if (!h->dense) return fail(h, -1, "the dense reduced-camera path needs 6 * n_cameras <= %d", kDenseMaxN);
+    if (!h->forms.dense) return fail(h, -1, "the dense reduced-camera path needs 6 * n_cameras <= %d", kDenseMaxN);
     const int64_t C = h->C;
-    CHK(upload_x(h, x));
-    CHK(launch_cam_table(h, h->x, h->tab, h->rec));
-    int np = 0;
-    CHK((launch_resjac<true, true>(h, h->x, h->tab, &np)));
-    CHK(launch_normal_blocks(h, h->x, h->tab, h->rec));
+    CHK(linearise_at(h, x));
     std::vector<double> ugc(27 * C), planes(6 * C), accp(6 * C);
     HIPCHK(h, hipMemcpyAsync(ugc.data(), h->Ugc(), sizeof(double) * 27 * C, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2588,10 +2551,7 @@ int sfmba_dense_schur(sfmba_handle* h, const double* x, const double* dc, const 
     HIPCHK(h, hipMemcpyAsync(h->e.p, dp, sizeof(double) * 3 * h->P, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->Dc.p, planes.data(), sizeof(double) * 6 * C, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->acc(), accp.data(), sizeof(double) * 6 * C, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_point_prep, dim3((h->P + 255) / 256), dim3(256), 0, h->stream, h->V.as<double>(),
-                       h->gp.as<double>(), (const double*)nullptr, h->e.as<double>(), (int)h->P, 0.0,
-                       vinv_ptr(h), (double*)nullptr, (const double*)nullptr, (double*)nullptr);
-    LAUNCHED(h);
+    CHK(launch_point_prep(h, nullptr, h->e.as<double>(), 0.0, nullptr, nullptr, nullptr));
     CHK(launch_dense_solve(h, 1e-14, 40 * 6 * (int)C, /*rhs=*/false));   // (test entry: to the end, to be compared with a direct solve)
     std::vector<double> blk(36 * (size_t)h->n_blk), sol(6 * C);
     HIPCHK(h, hipMemcpyAsync(blk.data(), h->Sblk.p, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, h->stream));
@@ -2622,20 +2582,14 @@ int sfmba_dense_schur(sfmba_handle* h, const double* x, const double* dc, const 
 
 int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t reps, double* avg_us) {
     CHK(enter(h));
-    CHK(check_ready(h, x));
+    CHK(begin_compute(h, x));
     if (!avg_us || reps <= 0) return fail(h, -1, "bad reps / avg_us");
-    CHK(upload_x(h, x));
-    CHK(launch_cam_table(h, h->x, h->tab, h->rec));
     int np = 0;
-    CHK((launch_resjac<true, true>(h, h->x, h->tab, &np)));
+    CHK(linearise_at(h, x, which >= 2));
     if (which >= 2) {
-        CHK(launch_normal_blocks(h, h->x, h->tab, h->rec));
         CHK(launch_update_scale(h, 1));
-        hipLaunchKernelGGL(k_point_prep, dim3((h->P + 255) / 256), dim3(256), 0, h->stream, h->V.as<double>(),
-                           h->gp.as<double>(), h->si_cur + 6 * h->C, (const double*)nullptr, (int)h->P,
-                           1e-6, vinv_ptr(h), h->rec + 3, (const double*)(h->x + 6 * h->C),
-                           h->use_rhsrec ? h->rhsrec.as<double>() : (double*)nullptr);
-        LAUNCHED(h);
+        CHK(launch_point_prep(h, h->si_cur + 6 * h->C, nullptr, 1e-6, h->rec + 3, h->x + 6 * h->C,
+                              h->forms.use_rhsrec ? h->rhsrec.as<double>() : (double*)nullptr));
         CHK(launch_mixed_prep(h, h->x, h->tab));
         // v = the camera slice of the gradient, as plane-major planes (and camera-major when v is not staged in LDS)
         hipLaunchKernelGGL(k_transpose, dim3((unsigned)((6 * h->C + 255) / 256)), dim3(256), 0, h->stream,
@@ -2655,18 +2609,18 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
         switch (which) {
             case 0: CHK((launch_resjac<true, true>(h, h->x, h->tab, &np))); break;
             case 1: CHK((launch_resjac<false, false>(h, h->x, h->tab, &np))); break;
-            case 2: CHK(launch_normal_blocks(h, h->x, h->tab, h->rec)); break;
+            case 2: CHK(launch_normal_blocks(h, h->tab, h->rec)); break;
             case 3: CHK(schur_product_standalone(h, h->vtmp.as<double>())); break;
-            case 4: CHK(launch_point_sweep(h, (h->lds_vec || h->sweep_rc || h->sweep_rc_g) ? h->vtmp.as<double>() : h->vcm.as<double>(), nullptr, 0)); break;
+            case 4: CHK(launch_pass_a<false>(h, (h->forms.lds_vec || h->forms.sweep_rc || h->forms.sweep_rc_g) ? h->vtmp.as<double>() : h->vcm.as<double>(), nullptr, 0)); break;
             case 5: CHK(launch_cam_schur<0>(h, h->vtmp.as<double>(), nullptr, 0)); break;
             case 6: CHK(launch_cam_schur<1>(h, nullptr, nullptr, 0)); break;
             case 7: CHK((launch_resjac<true, true>(h, h->x, h->tab, &np, nullptr, nullptr, /*blocks=*/false))); break;
             case 8:    // reduced right-hand side + Schur-diagonal blocks (without the 6x6 inverses)
-                if (xcd_cam(h)) { CHK(launch_rhs_and_preconditioner(h)); break; }      // (wave-per-chunk form: with combine + inverses)
+                if (h->forms.xcd_cam) { CHK(launch_rhs_and_preconditioner(h)); break; }      // (wave-per-chunk form: with combine + inverses)
                 hipLaunchKernelGGL((k_cam_rhs_diag<false>), dim3(h->n_chunks), dim3(kRhsThreads), 0, h->stream, cam_major(h),
                                    (const double*)h->tab, (const double*)h->rec, (const double*)vinv_ptr(h), h->K, (int)h->C,
                                    h->acc(), h->cam_partial.as<double>(), RhsPrecond{nullptr, nullptr, nullptr},
-                                   h->use_rhsrec ? (const double*)h->rhsrec.as<double>() : (const double*)nullptr, CamExchange{});
+                                   h->forms.use_rhsrec ? (const double*)h->rhsrec.as<double>() : (const double*)nullptr, CamExchange{});
                 LAUNCHED(h);
                 break;
             case 10:   // streaming-store ceiling: fill the Jacobian planes, 16 B per lane, one stream
@@ -2685,50 +2639,110 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
     return 0;
 }
 
-static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, const sfmba_options* opt_in, sfmba_result* out);
+namespace {
+// One sfmba_solve call: the state its phases share, and the phases in the order run() goes through them.
+// Host/device hand-offs per outer iteration: ONE read-back after the whole linear phase
+// (Cauchy product, Schur PCG, back-substitution, Gram/dot reductions are enqueued without the
+// host seeing intermediate values: the regularisation term is computed by k_prep on the device
+// and the PCG stops itself through its device-side control block) and ONE per trial step.
+struct Solve {
+    sfmba_handle* const h;
+    const sfmba_options opt;
+    sfmba_result* const out;
+    const Forms& f = h->forms;
+    const int64_t C = h->C, P = h->P, n = h->n;
+    const int64_t max_nfev = opt.max_nfev > 0 ? opt.max_nfev : 100 * (6 * C + 3 * P);
+    const double m_total = 2.0 * (double)h->N_total;
+    double* const sc = h->scal();
+    const double* const hs = h->h_scal;                         // the scalars as last brought to the host
+    struct EventList : std::vector<std::pair<hipEvent_t, hipEvent_t>> {     // destroyed on every exit path
+        ~EventList() { for (auto& pr : *this) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); } }
+    } evs;                                                      // opt.profile: one pair per K1 launch
+    int np_cost = 0;                                            // partial rows of the last K1 launch
+    int np_tail = 0;                                            // ... of the last k_backsub launch
+    double cost = 0.0, Delta = -1.0;
+    unsigned long long start_seq = 0;                           // quick start: the post the host still has to wait for
+    int64_t nfev = 1, njev = 1, iteration = 0, pcg_total = 0, pcg_breakdowns = 0;
+    int status = -1;
+    double step_norm = 0.0, actual_reduction = 0.0, g_norm = 0.0, reg_term = 0.0, cost_new = 0.0;
+    bool have_red = false;
+    // the record of PCG counts and the guess taken from it
+    int pcg_guess = h->pcg_hint;                                // iterations to enqueue without reading back
+    bool guess_exact = false;                                   // pcg_guess comes from the record: no spare launch
+    bool hist_same = false;
+    unsigned long long sig = 0;
+    std::vector<int> pcg_hist_new;
+    int pcg_enqueued = 0;
+    bool missed = false;
+    PcgCtrl hc{};                                               // control block of this iteration's PCG, as handed off
+    bool nb_valid = true;                                       // V, g_p, [U|g_c] (and, single-buffered, J and r) belong to h->x
+    // Single-buffered Jacobian: the trial point is evaluated into the SAME J / r buffers the sweeps of
+    // this iteration have just read, so K1's stores land on lines that are still resident in the
+    // Infinity Cache instead of cold ones.  A rejected step leaves J / r describing the rejected point;
+    // nothing uses them before the next trial overwrites them, except the rare exits handled below.
+    Mailbox trial_post{};                                       // one rank: the post that rides with the trial point's K3
+    bool trial_post_pending = false;
+    bool result_sent = false;                                   // x is already on its way to h_x (ev_copied[0])
+    double t_begin = 0.0, t_dev0 = 0.0, t_sent0 = 0.0, t_sent1 = 0.0;
 
-int sfmba_solve(sfmba_handle* h, double* x_inout, const sfmba_options* opt_in, sfmba_result* out) {
-    return sfmba_solve_from(h, x_inout, x_inout, opt_in, out);
-}
-
-int sfmba_solve_from(sfmba_handle* h, const double* x0, double* x_out, const sfmba_options* opt_in, sfmba_result* out) {
-    const int rc = solve_impl(h, x0, x_out, opt_in, out);
-    if (rc != 0 && h) {
-        // Leave the handle reusable: drain what was enqueued (speculative launches may still be in flight) and,
-        // after a collective failure, unmap the peers -- sequence numbers no longer agree across ranks, so the
-        // direct link is dead; the transport registered before it (RCCL / callback) serves later solves.
-        const std::string msg = h->err;
-        h->skip = nullptr; h->post = Mailbox{};
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-        if (rc == -5 && h->p2p.ready) {
-            p2p_close_peers(h);
-            if (h->p2p.words) (void)hipMemset(h->p2p.words, 0, 4 * sizeof(unsigned));
-        }
-        h->err = msg;
+    int run(const double* x_start, double* x_out);
+    // the phases, in order, and what they share
+    int start(const double* x_start), start_values();
+    void recall_pcg_record(const double* x_start);
+    int linear_phase(), tail();
+    int device_trial();
+    void record_pcg_count();
+    int step_loop(), accept_or_reject(), terminate();
+    int deliver(double* x_out);
+    int eval_jac(const double* x, double* tab, bool table_ready, bool finish = true);
+    int enqueue_trial(const double* coef_dev, double c1, double c2), handoff(bool with_ctrl);
+    int fetch() {                                               // the scalars of a post that has arrived
+        CHK(wait_mailbox(h, h->mbox_seq));
+        memcpy(h->h_scal, h->mbox, sizeof(double) * kScalSlots);
+        return 0;
     }
-    return rc;
+    double qsum(int q) const { return hs[kPointSlot[q]] + hs[kCamSlot + q]; }   // camera slice + (rank-reduced) point slice
+    int guess_launches() const { return pcg_guess + (f.pcg_fused ? 1 : 0) + (guess_exact ? 0 : 1); }
+};
+
+// K0 + K1, sum r^2 -> the cost slot
+int Solve::eval_jac(const double* x, double* tab, bool table_ready, bool finish) {
+    if (!table_ready) CHK(launch_cam_table(h, x, tab, h->rec, f.quick_start));
+    if (opt.profile) {
+        hipEvent_t a, b;
+        // timing-only events (hip_runtime_api.h: hipEventDisableSystemFence): no system-scope cache write-back and
+        // invalidation when they are recorded, which otherwise lands inside the measured interval (+1.3 us)
+        // and delays the launches around the kernel
+        HIPCHK(h, hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
+        if (hipEventCreateWithFlags(&b, hipEventDisableSystemFence) != hipSuccess) {
+            (void)hipEventDestroy(a);
+            return fail(h, -3, "hipEventCreateWithFlags failed");
+        }
+        evs.emplace_back(a, b);
+        CHK((launch_resjac<true, true>(h, x, tab, &np_cost, a, b)));
+    } else {
+        CHK((launch_resjac<true, true>(h, x, tab, &np_cost)));
+    }
+    if (finish) CHK(launch_finish(h, sum_rider(h, h->part.as<double>(), np_cost, kCostSlot), h->skip, h->post));
+    return 0;
 }
 
-static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, const sfmba_options* opt_in, sfmba_result* out) {
-    CHK(enter(h));
-    CHK(check_ready(h, x_start));
-    if (!x_inout) return fail(h, -1, "x_out is NULL");
-    if (!out) return fail(h, -1, "result is NULL");
-    sfmba_options opt;
-    if (opt_in) opt = *opt_in; else sfmba_default_options(&opt);
-    memset(out, 0, sizeof *out);
+int Solve::start_values() {                                     // cost0 is on the host
+    cost = 0.5 * hs[kCostSlot];
+    if (!std::isfinite(cost)) return fail(h, -2, "Residuals are not finite in the initial point.");
+    out->cost0 = cost;
+    out->rmse0 = std::sqrt(2.0 * cost / m_total);
+    return 0;
+}
+
+// upload, f0, J0 (least_squares.py:838, 903-912)
+int Solve::start(const double* x_start) {
     h->solved = false;
     h->skip = nullptr; h->post = Mailbox{};
     h->pending_scale_sums = false;
     h->p2p.first_in_solve = true;
     if (h->dbg.p2p_delay_ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(h->dbg.p2p_delay_ms));
-    const double t_begin = now_s();
-    const int64_t C = h->C, P = h->P, n = h->n;
-    const int64_t max_nfev = opt.max_nfev > 0 ? opt.max_nfev : 100 * (6 * C + 3 * P);
-    const double m_total = 2.0 * (double)h->N_total;
-    double* sc = h->scal();
-
+    t_begin = now_s();
     h->x = h->xa.as<double>(); h->x_new = h->xb.as<double>();
     h->tab = h->tabA.as<double>(); h->tab_new = h->tabB.as<double>();
     h->rec = h->recA.as<double>(); h->rec_new = h->recB.as<double>();
@@ -2739,445 +2753,370 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
         HIPCHK(h, h->mirror[0].ensure(sizeof(double) * n, 0));
         HIPCHK(h, h->mirror[1].ensure(sizeof(double) * n, 0));
     }
-    HIPCHK(h, hipMemsetAsync(h->scal() + kGhPrevSlot, 0, 2 * sizeof(double), h->stream));   // forcing-term memory of k_prep
-    const double t_dev0 = now_s();
+    HIPCHK(h, hipMemsetAsync(sc + kGhPrevSlot, 0, 2 * sizeof(double), h->stream));   // forcing-term memory of k_prep
+    t_dev0 = now_s();
     report_stall(h, "upload_x", t_dev0 - t_begin);
-
-    // Host/device hand-offs per outer iteration: ONE read-back after the whole linear phase
-    // (Cauchy product, Schur PCG, back-substitution, Gram/dot reductions are enqueued without the
-    // host seeing intermediate values: the regularisation term is computed by k_prep on the device
-    // and the PCG stops itself through its device-side control block) and ONE per trial step.
-    struct EventList : std::vector<std::pair<hipEvent_t, hipEvent_t>> {     // destroyed on every exit path
-        ~EventList() { for (auto& pr : *this) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); } }
-    } evs;
-    int np_cost = 0;                                                  // partial rows of the last K1 launch
-    // debug options of the hand-offs (default: on; single rank only -- with several ranks the cost and the scale sums
-    // pass through collectives between these launches, and the parent's order is kept)
-    const bool quick_start = !multi_rank(h) && h->dbg.start_handoff != 0 && h->dbg.cost_rider != 0;
-    const bool spec_scale = !multi_rank(h) && h->dbg.spec_scale != 0;
-    const bool early_download = h->copy_stream != nullptr && h->dbg.early_download != 0;
-    bool result_sent = false;                                         // x is already on its way to h_x (ev_copied[0])
-    double t_sent0 = 0.0, t_sent1 = 0.0, t_ws = 0.0;
-    auto eval_jac = [&](const double* x, double* tab, bool table_ready, bool finish = true) -> int {   // K0 + K1, sum r^2 -> scalar 0
-        if (!table_ready) CHK(launch_cam_table(h, x, tab, h->rec, quick_start));
-        int& np = np_cost;
-        if (opt.profile) {
-            hipEvent_t a, b;
-            // timing-only events (hip_runtime_api.h: hipEventDisableSystemFence): no system-scope cache write-back and
-            // invalidation when they are recorded, which otherwise lands inside the measured interval (+1.3 us)
-            // and delays the launches around the kernel
-            HIPCHK(h, hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
-            if (hipEventCreateWithFlags(&b, hipEventDisableSystemFence) != hipSuccess) {
-                (void)hipEventDestroy(a);
-                return fail(h, -3, "hipEventCreateWithFlags failed");
-            }
-            evs.emplace_back(a, b);
-            CHK((launch_resjac<true, true>(h, x, tab, &np, a, b)));
-        } else {
-            CHK((launch_resjac<true, true>(h, x, tab, &np)));
-        }
-        if (finish) CHK(launch_finish(h, h->part.as<double>(), np, 1, 0));
-        return 0;
-    };
-    auto linearise = [&](int first) -> int {      // normal blocks, scale, gradient, q0..q4 at h->x
-        CHK(launch_normal_blocks(h, h->x, h->tab, h->rec));
-        CHK(launch_update_scale(h, first));
-        CHK(exchange_linearise(h));
-        return 0;
-    };
-
-    // f0, J0 (least_squares.py:838, 903-912)
-    double cost = 0.0, Delta = -1.0;
-    unsigned long long start_seq = 0;                // quick start: the post the host still has to wait for
-    auto start_values = [&]() -> int {               // cost0 is on the host
-        cost = 0.5 * h->h_scal[0];
-        if (!std::isfinite(cost)) return fail(h, -2, "Residuals are not finite in the initial point.");
-        out->cost0 = cost;
-        out->rmse0 = std::sqrt(2.0 * cost / m_total);
-        return 0;
-    };
-    if (quick_start) {
+    if (f.quick_start) {
         // No blocking hand-off: the launches take the form of a trial evaluation (the cost sum and its post ride with
         // K3), k_update_scale's sums ride with the first k_jdot, and k_prep / k_tr_step derive the first radius from
-        // the exchange scalars themselves (Delta < 0).  The host picks the cost up behind the k_jdot launch below and
-        // the radius (slot 31) at the first regular hand-off.
+        // the exchange scalars themselves (Delta < 0).  The host picks the cost up behind the k_jdot launch
+        // (linear_phase) and the radius at the first regular hand-off.
         CHK(eval_jac(h->x, h->tab, false, /*finish=*/false));
         start_seq = ++h->mbox_seq;
-        CHK(launch_normal_blocks(h, h->x, h->tab, h->rec, np_cost,
-                                 Mailbox{h->mbox_dev, sc, nullptr, start_seq, p2p_error_word(h)}));
-        CHK(launch_update_scale(h, 1, /*defer=*/true));
-    } else {
-        CHK(eval_jac(h->x, h->tab, false));
-        CHK(exchange(h, sc, 1, 0));                      // sum r^2
-        CHK(linearise(1));
-        CHK(fetch_scalars(h));
-        CHK(start_values());
-        Delta = std::sqrt(qsum(h, 2));                          // |x0 * scale_inv|, trf.py:428
-        if (Delta == 0.0) Delta = 1.0;
+        CHK(launch_normal_blocks(h, h->tab, h->rec, np_cost, Mailbox{h->mbox_dev, sc, nullptr, start_seq, p2p_error_word(h)}));
+        return launch_update_scale(h, 1, /*defer=*/true);
     }
-    int64_t nfev = 1, njev = 1, iteration = 0, pcg_total = 0;
-    int status = -1;
-    double step_norm = 0.0, actual_reduction = 0.0, g_norm = 0.0, reg_term = 0.0;
-    bool have_red = false;
-    int pcg_guess = h->pcg_hint;                                // iterations to enqueue without reading back
-    std::vector<int> pcg_hist_new;
-    bool guess_exact = false;                                   // pcg_guess comes from the record: no spare launch
-    // The record is trusted count for count only on the problem it was recorded on; on a neighbouring problem (the
-    // reference's growing reconstruction: a camera or a few hundred observations more) it is a guess with a spare
-    // launch; on an unrelated problem it is dropped together with the running hint.
-    // (content, not only sizes: the problem arrays' generation and a checksum of the start vector -- a different start on
-    // the same problem, or another problem of the same sizes, is a "neighbouring" one and gets the spare launch)
-    unsigned long long sig = h->problem_gen * 0x9E3779B97F4A7C15ull;
-    {
-        const int64_t stride = std::max<int64_t>(1, n / 509);
-        for (int64_t k = 0; k < n; k += stride) {
-            unsigned long long bits;
-            memcpy(&bits, x_start + k, sizeof bits);
-            sig = (sig ^ bits) * 0x100000001B3ull;
-        }
+    CHK(eval_jac(h->x, h->tab, false));
+    CHK(exchange(h, sc + kCostSlot, 1, 0));                     // sum r^2
+    CHK(launch_normal_blocks(h, h->tab, h->rec));               // normal blocks, scale, gradient, q0..q4 at h->x
+    CHK(launch_update_scale(h, 1));
+    CHK(exchange_linearise(h));
+    CHK(fetch_scalars(h));
+    CHK(start_values());
+    Delta = std::sqrt(qsum(2));                                 // |x0 * scale_inv|, trf.py:428
+    if (Delta == 0.0) Delta = 1.0;
+    return 0;
+}
+
+// The record is trusted count for count only on the problem it was recorded on; on a neighbouring problem (the
+// reference's growing reconstruction: a camera or a few hundred observations more) it is a guess with a spare
+// launch; on an unrelated problem it is dropped together with the running hint.
+// (content, not only sizes: the problem arrays' generation and a checksum of the start vector -- a different start on
+// the same problem, or another problem of the same sizes, is a "neighbouring" one and gets the spare launch)
+void Solve::recall_pcg_record(const double* x_start) {
+    sig = h->problem_gen * 0x9E3779B97F4A7C15ull;
+    const int64_t stride = std::max<int64_t>(1, n / 509);
+    for (int64_t k = 0; k < n; k += stride) {
+        unsigned long long bits;
+        memcpy(&bits, x_start + k, sizeof bits);
+        sig = (sig ^ bits) * 0x100000001B3ull;
     }
-    const bool hist_same = h->hist_C == C && h->hist_P == P && h->hist_N == h->N && h->hist_sig == sig;
+    hist_same = h->hist_C == C && h->hist_P == P && h->hist_N == h->N && h->hist_sig == sig;
     const bool hist_near = hist_same || (h->hist_N > 0 && std::llabs(h->hist_C - C) <= 1 && 2 * h->N >= h->hist_N && h->N <= 2 * h->hist_N);
     if (!hist_near) { h->pcg_hist.clear(); h->pcg_hint = 0; pcg_guess = 0; }
     if (!h->pcg_hist.empty() && h->pcg_hist[0] > 0) { pcg_guess = h->pcg_hist[0]; guess_exact = hist_same; }
-    int64_t pcg_breakdowns = 0;
-    bool nb_valid = true;                                       // V, g_p, [U|g_c] (and, single-buffered, J and r) belong to h->x
-    // Single-buffered Jacobian: the trial point is evaluated into the SAME J / r buffers the sweeps of
-    // this iteration have just read, so K1's stores land on lines that are still resident in the
-    // Infinity Cache instead of cold ones.  A rejected step leaves J / r describing the rejected point;
-    // nothing uses them before the next trial overwrites them, except the rare exits handled below.
-    const bool pcg_debug = h->dbg.trace_pcg != 0;
-    const int pcg_bias = h->dbg.pcg_guess_bias;                 // test hook (sfmba_debug_option)
-    if (opt.verbose >= 2) print_header(h);
+}
 
-    for (;;) {                                                  // trf.py:450
-        if (!nb_valid) {                                        // a rejected trial overwrote the blocks and no
-            CHK(eval_jac(h->x, h->tab, true));         // step was accepted afterwards
-            CHK(launch_normal_blocks(h, h->x, h->tab, h->rec));                       // (nfev limit)
-            nb_valid = true;
-        }
-        // ---- enqueue the whole linear phase ---------------------------------------------------
-        // Final sums of per-workgroup partials are not launches of their own where a neighbour can carry
-        // them: k_update_scale's ride with k_jdot; on a single rank k_jdot's are repeated by every workgroup
-        // of k_prep and k_backsub's are done by k_tr_step (with several
-        // ranks the all-reduce has to sit between producer and consumer, so those two stay launches).
-        const bool one_rank = !multi_rank(h);
-        int np = 0;
-        const bool scale_sums_rode = h->pending_scale_sums;
-        CHK(launch_jdot(h, &np));                               // t1 = J D^2 g, G11 = |t1|^2
-        if (start_seq != 0) {                                   // quick start: cost0 was posted by K3 a while ago
-            CHK(wait_mailbox(h, start_seq));
-            memcpy(h->h_scal, h->mbox, sizeof(double) * kScalSlots);
-            start_seq = 0;
-            CHK(start_values());
-        }
-        if (!one_rank && h->p2p.ready) {
-            // direct path: the collective's own workgroup first sums k_jdot's partials into slot 1, then reduces
-            // slots 1..12 over the ranks when an accepted step left fresh q1..q4 (8..11, sums) and max|g| (12, a
-            // maximum by the mask), G11 alone otherwise.  Slots 2..7 (G12, G22, q5..q8 of the previous iteration)
-            // are summed once more along the way; nothing reads them before k_backsub's sums rewrite them.
-            Piggyback pb{h->partB(), sc, FinishJob{}, 1, 1, 0};
-            pb.job.row0[0] = 0; pb.job.nrows[0] = np;
-            for (int k = 0; k < kNQ; ++k) { pb.job.slot[0][k] = 1 + k; pb.job.slot[1][k] = -1; }
-            static_assert(kMaxSlot == 12, "mask below assumes the maximum sits at the end of the run");
-            CHK(p2p_allreduce(h, sc + 1, scale_sums_rode ? kMaxSlot : 1, 0, nullptr,
-                              scale_sums_rode ? 1ull << (kMaxSlot - 1) : 0ull, &pb));
-            ++h->n_collectives;
-        } else if (!one_rank) {
-            CHK(launch_finish(h, h->partB(), np, 1, 1));
-            if (scale_sums_rode) CHK(exchange_linearise(h));        // q1..q4, max|g| of the accepted point
-            CHK(exchange(h, sc + 1, 1, 0));
-        }
-        {   // regularisation (trf.py:471-475), Vinv/e per point, Dc/Minv per camera, acc0 = 0: one launch
-            const int bc = (int)((C + 63) / 64), bp = (int)((P + 63) / 64);
-            hipLaunchKernelGGL(k_prep, dim3(bc + bp), dim3(64), 0, h->stream, sc, Delta, opt.reg_min, h->Ugc(),
-                               h->V.as<double>(), h->gp.as<double>(), h->si_cur, (int)C, (int)P, bc,
-                               h->Dc.as<double>(), (h->dbg.precond == 0 ? h->Minv.as<double>() : (double*)nullptr),
-                               vinv_ptr(h), h->rec + 3,
-                               one_rank ? (const double*)h->partB() : (const double*)nullptr, np, opt.pcg_tol,
-                               std::max(opt.pcg_tol, opt.pcg_tol_max), (const double*)(h->x + 6 * C),
-                               (h->use_rhsrec && !(h->dense && one_rank)) ? h->rhsrec.as<double>() : (double*)nullptr,   // (read by k_cam_rhs_diag only)
-                               (h->dense && one_rank) ? MixedPrep{nullptr, nullptr, nullptr, nullptr, Origin{0.0, 0.0, 0.0}} : mixed_prep(h, h->tab));
-            LAUNCHED(h);
-        }
-        const bool dense = h->dense && one_rank;               // (sharded: the block pairs would need their own all-reduce)
-        if (!dense) CHK(launch_rhs_and_preconditioner(h));      // reduced rhs term -> acc, preconditioner blocks
-                                                                // (few cameras: both inside launch_dense_solve)
-        if (!dense) CHK(pcg_start(h, opt));                     // replaces lsmr, trf.py:477-480
-        PcgCtrl hc{};
-        if (dense) {
-            // the same PCG inside one workgroup; an iteration there costs a twentieth of the two launches of the
-            // implicit product, so the forcing term is a decade tighter (cfg2: 5 outer iterations instead of 7)
-            CHK(launch_dense_solve(h, kDenseTolFactor * opt.pcg_tol, pcg_max_iters(h, opt), /*rhs=*/true));
-        } else if (pcg_guess > 0) {
-            // speculative: no read-back; surplus launches are no-ops.  Fused launches apply the update of
-            // iteration k in launch k + 1, so k iterations need k + 1 launches; one spare either way.
-            CHK(pcg_enqueue(h, pcg_guess + (h->pcg_fused ? 1 : 0) + (guess_exact ? 0 : 1), true));
-        } else {
-            CHK(pcg_finish_polling(h, opt, &hc));
-        }
-        // back-substitution + model products (all in k_backsub); `for_device_step`: k_tr_step follows and
-        // (single rank) sums k_backsub's partial rows itself
-        int np_tail = 0;
-        auto tail = [&](bool for_device_step) -> int {
-            CHK(launch_backsub(h, &np));
-            np_tail = np;
-            if (!one_rank && h->p2p.ready) {                    // the sums run inside the collective's workgroup
-                const Piggyback pb = backsub_rider(h, np);
-                CHK(p2p_allreduce(h, sc + 2, 6, 0, nullptr, 0, &pb));
-                ++h->n_collectives;
-                return 0;
-            }
-            if (!(for_device_step && one_rank)) CHK(launch_finish_backsub(h, np));
-            CHK(exchange_tail(h));
-            return 0;
-        };
-        CHK(tail(true));
-
-        Mailbox trial_post{};
-        bool trial_post_pending = false;
-        // ---- the first trial step is decided ON THE DEVICE (k_tr_step) and evaluated right away -------
-        // so that an outer iteration hands control to the host ONCE, after the trial cost is known.
-        auto enqueue_trial = [&](const double* coef_dev, double c1, double c2) -> int {
-            const int bc = (int)((C + 255) / 256);
-            hipLaunchKernelGGL(k_step_table, dim3(bc + grid_1d(3 * P, 256, 2048)), dim3(256), 0, h->stream, h->x,
-                               h->sg_cur, h->p.as<double>(), c1, c2, coef_dev, (int)C, n, bc, h->x_new,
-                               h->tab_new, h->rec_new, h->skip);
-            LAUNCHED(h);
-            if (h->mirror_on) {                                 // x_new to its host mirror, beside the evaluation below
-                const int w = h->x_new == h->xa.as<double>() ? 0 : 1;
-                HIPCHK(h, hipEventRecord(h->ev_written, h->stream));
-                HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_written, 0));
-                HIPCHK(h, hipMemcpyAsync(h->mirror[w].p, h->x_new, sizeof(double) * n, hipMemcpyDeviceToHost, h->copy_stream));
-                HIPCHK(h, hipEventRecord(h->ev_copied[w], h->copy_stream));
-                h->mirror_tag[w] = ++h->copy_count;
-            }
-            // the trial point is evaluated WITH its Jacobian, into the same buffers: when
-            // the step is accepted (the common case) nothing has to be recomputed
-            // The cost reduction that ends the evaluation also posts the hand-off (scalars + PCG control
-            // block) into the host mailbox; with several ranks the post follows the all-reduce of the cost.
-            const Mailbox mb{h->mbox_dev, sc, h->ctrl.as<PcgCtrl>() + (h->pcg_L & 1), ++h->mbox_seq, p2p_error_word(h)};
-            const bool ranks = multi_rank(h);
-            if (ranks && h->p2p.ready) {
-                // direct path: ONE single-workgroup launch sums K1's cost partials, reduces the cost over the
-                // ranks and posts the hand-off (or only posts, when k_tr_step cancelled the trial)
-                CHK(eval_jac(h->x_new, h->tab_new, true, /*finish=*/false));
-                Piggyback pb{h->part.as<double>(), sc, FinishJob{}, 1, 1, 0};
-                pb.job.row0[0] = 0; pb.job.nrows[0] = np_cost;
-                for (int k = 0; k < kNQ; ++k) { pb.job.slot[0][k] = k; pb.job.slot[1][k] = -1; }
-                CHK(p2p_allreduce(h, sc, 1, 0, nullptr, 0, &pb, &mb, h->skip));
-                ++h->n_collectives;
-                return 0;
-            }
-            if (!ranks && h->dbg.cost_rider == 0) {
-                h->post = mb;
-                const int rc = eval_jac(h->x_new, h->tab_new, true);
-                h->post = Mailbox{};
-                return rc;
-            }
-            if (!ranks) {
-                // single rank: the cost sum and the post ride with the launch that builds the trial point's blocks
-                // (handoff below), one launch less per iteration
-                CHK(eval_jac(h->x_new, h->tab_new, true, /*finish=*/false));
-                trial_post = mb;
-                trial_post_pending = true;
-                return 0;
-            }
-            CHK(eval_jac(h->x_new, h->tab_new, true));
-            CHK(exchange(h, sc, 1, 0));
-            hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->stream, mb);
-            LAUNCHED(h);
-            return 0;
-        };
-        auto handoff = [&](bool with_ctrl) -> int {
-            // While the host waits, the GPU already builds the normal-equation blocks of the trial point
-            // (speculating on acceptance, the common case).  They overwrite V / g_p / [U|g_c], which a
-            // rejected step does not need: a retry only re-solves the 2-D model (host scalars) and
-            // re-applies k_step_table to x, D^2 g and p, all untouched.
-            if (trial_post_pending) CHK(launch_normal_blocks(h, h->x_new, h->tab_new, h->rec_new, np_cost, trial_post));
-            else CHK(launch_normal_blocks(h, h->x_new, h->tab_new, h->rec_new));
-            trial_post_pending = false;
-            nb_valid = false;
-            // ... and, behind them, scale, gradient and partial sums of the trial point into the second buffer set
-            if (spec_scale) CHK(launch_update_scale(h, 0, /*defer=*/true, /*speculative=*/true));
-            CHK(wait_mailbox(h, h->mbox_seq));
-            memcpy(h->h_scal, h->mbox, sizeof(double) * kScalSlots);
-            if (with_ctrl) memcpy(&hc, h->mbox + kMboxCtrl, sizeof hc);
-            return 0;
-        };
-        const bool speculated = pcg_guess > 0 || dense;         // dense: the control block always says "finished"
-        const int pcg_enqueued = pcg_guess > 0 ? pcg_guess + (h->pcg_fused ? 1 : 0) + (guess_exact ? 0 : 1) : 0;
-        bool missed = false;
-        for (bool speculative = speculated;;) {
-            hipLaunchKernelGGL(k_tr_step, dim3(1), dim3(one_rank ? 1024 : 64), 0, h->stream, sc, Delta,
-                               speculative ? (const PcgCtrl*)(h->ctrl.as<PcgCtrl>() + (h->pcg_L & 1)) : (const PcgCtrl*)nullptr,
-                               one_rank ? backsub_rider(h, np_tail) : Piggyback{});
-            LAUNCHED(h);
-            h->skip = sc + 30;                                  // k_tr_step's verdict gates every launch below
-            int rc_trial = enqueue_trial(sc + 25, 0.0, 0.0);
-            if (rc_trial == 0) rc_trial = handoff(speculative); // THE hand-off of this iteration
-            h->skip = nullptr;
-            CHK(rc_trial);
-            if (!(speculative && hc.done == 0)) break;
-            // The PCG needed more iterations than were enqueued.  k_tr_step saw that on the device and
-            // cancelled the trial launches, so J, r and the normal blocks still describe x: finish the
-            // PCG (host-polled), redo the tail and decide the step on the device again -- the arithmetic of
-            // an iteration does not depend on whether its guess sufficed.
-            missed = true;
-            nb_valid = true;
-            if (opt.profile && !evs.empty()) {                  // the cancelled launch is not a K1 timing sample
-                (void)hipEventDestroy(evs.back().first);
-                (void)hipEventDestroy(evs.back().second);
-                evs.pop_back();
-            }
-            CHK(pcg_finish_polling(h, opt, &hc));
-            CHK(tail(true));
-            speculative = false;
-        }
-        bool first_trial_ready = true;
-        // hc.done == 3: the CG recurrences lost positive definiteness (rounding, typically on a converged
-        // system whose right-hand side is noise).  The iterate of the last good step is kept -- it is
-        // zero when the very first step failed, in which case the 2-D model below degenerates to the
-        // steepest-descent line, exactly scipy's fallback when gn_h adds nothing to span(g_h).
-        if (hc.done == 3) ++pcg_breakdowns;
-        if (Delta < 0.0) Delta = h->h_scal[31];                 // quick start: the radius k_tr_step derived and used
-
-        // ---- loop head of trf.py:450-459, evaluated now that the scalars are on the host -----------
-        g_norm = std::max(h->h_scal[kMaxSlot], h->h_scal[kCamSlot + 0]);
-        if (g_norm < opt.gtol) status = 1;
-        if (opt.verbose >= 2) print_iter(h, iteration, nfev, cost, have_red, actual_reduction, step_norm, g_norm);
-        if (status != -1 || nfev >= max_nfev || (opt.max_iter > 0 && iteration >= opt.max_iter)) break;
-        pcg_total += hc.iters;
-        if (pcg_debug && dense)
-            fprintf(stderr, "sfmba: iteration %lld: PCG in LDS, %d iterations, outcome %d, reg %.3e\n", (long long)iteration,
-                    hc.iters, hc.done, h->h_scal[kRegSlot]);
-        else if (pcg_debug)
-            fprintf(stderr, "sfmba: iteration %lld: PCG enqueued %d, needed %d%s\n", (long long)iteration,
-                    pcg_enqueued, hc.iters, missed ? " (miss)" : "");
-        // Next guess: the largest recent count, forgotten by one iteration per outer iteration.  A surplus
-        // iteration costs two empty launches (~10 us); a miss costs a hand-off per polled batch.
-        h->pcg_hint = std::max(hc.iters, h->pcg_hint - 1);
-        pcg_hist_new.push_back(hc.iters);
-        {
-            const int rec = (iteration + 1 < (int64_t)h->pcg_hist.size()) ? h->pcg_hist[iteration + 1] : 0;
-            guess_exact = rec > 0 && pcg_bias == 0 && hist_same;
-            pcg_guess = std::max(1, (guess_exact ? rec : h->pcg_hint) + pcg_bias);
-        }
-        reg_term = h->h_scal[kRegSlot];
-
-        const double x_norm = std::sqrt(qsum(h, 3));
-        const TrModel model = tr_build_model(h->h_scal[1], h->h_scal[2], h->h_scal[3], qsum(h, 1), qsum(h, 5),
-                                             qsum(h, 6), qsum(h, 4), qsum(h, 7), qsum(h, 8));
-
-        actual_reduction = -1.0;
-        double cost_new = cost;
-        while (actual_reduction <= 0.0 && nfev < max_nfev) {    // trf.py:488
-            TrStep st;
-            if (first_trial_ready) {                            // decided and evaluated on the device above
-                st.c1 = h->h_scal[25]; st.c2 = h->h_scal[26]; st.predicted = h->h_scal[27];
-                st.step_h_norm = h->h_scal[28]; st.step_norm = h->h_scal[29];
-                first_trial_ready = false;
-            } else {                                            // retry after a rejected step (or fallback)
-                st = tr_solve_step(model, Delta);
-                CHK(enqueue_trial(nullptr, st.c1, st.c2));
-                CHK(handoff(false));
-            }
-            ++nfev;
-            cost_new = 0.5 * h->h_scal[0];
-            if (!std::isfinite(cost_new)) {                     // trf.py:504-506
-                Delta = 0.25 * st.step_h_norm;
-                continue;
-            }
-            actual_reduction = cost - cost_new;
-            double ratio;
-            const double Delta_new = update_tr_radius(Delta, actual_reduction, st.predicted, st.step_h_norm,
-                                                      st.step_h_norm > 0.95 * Delta, &ratio);
-            step_norm = st.step_norm;
-            const int term = check_termination(actual_reduction, cost, step_norm, x_norm, ratio, opt.ftol, opt.xtol);
-            if (term != 0) { status = term; break; }
-            Delta = Delta_new;
-        }
-        have_red = true;
-        if (actual_reduction > 0.0) {                           // trf.py:528
-            std::swap(h->x, h->x_new);
-            std::swap(h->tab, h->tab_new);
-            std::swap(h->rec, h->rec_new);
-            h->x_tag = h->mirror_tag[h->x == h->xa.as<double>() ? 0 : 1];      // (0 when no mirror copy was made)
-            nb_valid = true;                                    // J, f and the normal blocks of the accepted
-                                                                // point are already there / in flight
-            cost = cost_new;
-            ++njev;
-            if (status != -1 && early_download && !h->mirror_on) {
-                // The solve ends on this point.  x was written by k_step_table, which the stream ran before the K1 / K3
-                // whose post the host has just read, and nothing from here on writes it: the result leaves on the copy
-                // stream now, beside what is left of K3, k_update_scale, the final sums and the last post.
-                CHK(ensure_h_x(h));
-                t_sent0 = now_s();
-                // (in ONE piece: two halves, the first half's pinned -> pageable copy beside the second half's transfer,
-                // measured 1.805-1.822 ms per cfg4 solve against 1.792-1.849 -- no gain, two blit launches)
-                HIPCHK(h, hipMemcpyAsync(h->h_x, h->x, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->copy_stream));
-                HIPCHK(h, hipEventRecord(h->ev_copied[0], h->copy_stream));
-                h->result_in_flight = true;
-                result_sent = true;
-                t_sent1 = now_s();
-            }
-            if (spec_scale) {                                   // already enqueued behind K3 (handoff): take its outputs
-                std::swap(h->g_cur, h->g_new);
-                std::swap(h->si_cur, h->si_new);
-                std::swap(h->sg_cur, h->sg_new);
-                h->pending_scale_sums = true;
-            } else {
-                CHK(launch_update_scale(h, 0, /*defer=*/true));
-            }                                                   // its final sums ride with the next k_jdot and
-                                                                // are read with the next hand-off
-        } else {
-            step_norm = 0.0;
-            actual_reduction = 0.0;
-        }
-        ++iteration;
-        if (status != -1) {                                     // terminated inside the step loop
-            if (h->pending_scale_sums) {                        // no k_jdot follows
-                CHK(flush_scale_sums(h));
-                CHK(exchange_linearise(h));
-            }
-            CHK(fetch_scalars(h));
-            g_norm = std::max(h->h_scal[kMaxSlot], h->h_scal[kCamSlot + 0]);
-            if (opt.verbose >= 2) print_iter(h, iteration, nfev, cost, have_red, actual_reduction, step_norm, g_norm);
-            break;
-        }
+// ---- enqueue the whole linear phase ---------------------------------------------------
+// Final sums of per-workgroup partials are not launches of their own where a neighbour can carry
+// them: k_update_scale's ride with k_jdot; on a single rank k_jdot's are repeated by every workgroup
+// of k_prep and k_backsub's are done by k_tr_step (with several
+// ranks the all-reduce has to sit between producer and consumer, so those two stay launches).
+int Solve::linear_phase() {
+    if (!nb_valid) {                                            // a rejected trial overwrote the blocks and no
+        CHK(eval_jac(h->x, h->tab, true));                      // step was accepted afterwards
+        CHK(launch_normal_blocks(h, h->tab, h->rec));           // (nfev limit)
+        nb_valid = true;
     }
-    if (status == -1) status = 0;
+    int np = 0;
+    const bool scale_sums_rode = h->pending_scale_sums;
+    CHK(launch_jdot(h, &np));                                   // t1 = J D^2 g, G11 = |t1|^2
+    if (start_seq != 0) {                                       // quick start: cost0 was posted by K3 a while ago
+        start_seq = 0;
+        CHK(fetch());
+        CHK(start_values());
+    }
+    if (!f.one_rank && h->p2p.ready) {
+        // direct path: the collective's own workgroup first sums k_jdot's partials into slot 1, then reduces
+        // slots 1..12 over the ranks when an accepted step left fresh q1..q4 (8..11, sums) and max|g| (12, a
+        // maximum by the mask), G11 alone otherwise.  Slots 2..7 (G12, G22, q5..q8 of the previous iteration)
+        // are summed once more along the way; nothing reads them before k_backsub's sums rewrite them.
+        const Piggyback pb = sum_rider(h, h->partB(), np, kG11Slot);
+        static_assert(kMaxSlot == 12 && kG11Slot == 1, "mask below assumes the maximum sits at the end of the run");
+        CHK(p2p_allreduce(h, sc + kG11Slot, scale_sums_rode ? kMaxSlot : 1, 0, nullptr,
+                          scale_sums_rode ? 1ull << (kMaxSlot - 1) : 0ull, &pb));
+        ++h->n_collectives;
+    } else if (!f.one_rank) {
+        CHK(launch_finish(h, sum_rider(h, h->partB(), np, kG11Slot), h->skip, h->post));
+        if (scale_sums_rode) CHK(exchange_linearise(h));        // q1..q4, max|g| of the accepted point
+        CHK(exchange(h, sc + kG11Slot, 1, 0));
+    }
+    {   // regularisation (trf.py:471-475), Vinv/e per point, Dc/Minv per camera, acc0 = 0: one launch
+        const int bc = (int)((C + 63) / 64), bp = (int)((P + 63) / 64);
+        hipLaunchKernelGGL(k_prep, dim3(bc + bp), dim3(64), 0, h->stream, sc, Delta, opt.reg_min, h->Ugc(),
+                           h->V.as<double>(), h->gp.as<double>(), h->si_cur, (int)C, (int)P, bc,
+                           h->Dc.as<double>(), (f.precond ? (double*)nullptr : h->Minv.as<double>()),
+                           vinv_ptr(h), h->rec + 3,
+                           f.one_rank ? (const double*)h->partB() : (const double*)nullptr, np, opt.pcg_tol,
+                           std::max(opt.pcg_tol, opt.pcg_tol_max), (const double*)(h->x + 6 * C),
+                           (f.use_rhsrec && !f.dense_solve) ? h->rhsrec.as<double>() : (double*)nullptr,   // (read by k_cam_rhs_diag only)
+                           f.dense_solve ? MixedPrep{nullptr, nullptr, nullptr, nullptr, Origin{0.0, 0.0, 0.0}} : mixed_prep(h, h->tab));
+        LAUNCHED(h);
+    }
+    hc = PcgCtrl{};
+    pcg_enqueued = 0;
+    if (f.dense_solve) {
+        // few cameras: the reduced rhs term and the preconditioner blocks are formed inside launch_dense_solve, and
+        // the same PCG runs inside one workgroup; an iteration there costs a twentieth of the two launches of the
+        // implicit product, so the forcing term is a decade tighter (cfg2: 5 outer iterations instead of 7)
+        CHK(launch_dense_solve(h, kDenseTolFactor * opt.pcg_tol, pcg_max_iters(h, opt), /*rhs=*/true));
+        return tail();
+    }
+    CHK(launch_rhs_and_preconditioner(h));                      // reduced rhs term -> acc, preconditioner blocks
+    CHK(pcg_start(h, opt));                                     // replaces lsmr, trf.py:477-480
+    if (pcg_guess > 0) {
+        // speculative: no read-back; surplus launches are no-ops.  Fused launches apply the update of
+        // iteration k in launch k + 1, so k iterations need k + 1 launches; one spare either way.
+        pcg_enqueued = guess_launches();
+        CHK(pcg_enqueue(h, pcg_enqueued, true));
+    } else {
+        CHK(pcg_finish_polling(h, opt, &hc));
+    }
+    return tail();
+}
+
+// back-substitution + model products (all in k_backsub); k_tr_step follows and (single rank) sums k_backsub's
+// partial rows itself
+int Solve::tail() {
+    CHK(launch_backsub(h, &np_tail));
+    if (!f.one_rank && h->p2p.ready) {                          // the sums run inside the collective's workgroup
+        const Piggyback pb = backsub_rider(h, np_tail);
+        CHK(p2p_allreduce(h, sc + kTailSlot, 6, 0, nullptr, 0, &pb));
+        ++h->n_collectives;
+        return 0;
+    }
+    if (!f.one_rank) CHK(launch_finish(h, backsub_rider(h, np_tail)));
+    return exchange(h, sc + kTailSlot, 6, 0);                   // G12, G22, q5..q8
+}
+
+// the trial point x + step (coefficients from the device, or c1, c2) and its evaluation
+int Solve::enqueue_trial(const double* coef_dev, double c1, double c2) {
+    const int bc = (int)((C + 255) / 256);
+    hipLaunchKernelGGL(k_step_table, dim3(bc + grid_1d(3 * P, 256, 2048)), dim3(256), 0, h->stream, h->x,
+                       h->sg_cur, h->p.as<double>(), c1, c2, coef_dev, (int)C, n, bc, h->x_new,
+                       h->tab_new, h->rec_new, h->skip);
+    LAUNCHED(h);
+    if (h->mirror_on) {                                         // x_new to its host mirror, beside the evaluation below
+        const int w = h->x_new == h->xa.as<double>() ? 0 : 1;
+        HIPCHK(h, hipEventRecord(h->ev_written, h->stream));
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_written, 0));
+        HIPCHK(h, hipMemcpyAsync(h->mirror[w].p, h->x_new, sizeof(double) * n, hipMemcpyDeviceToHost, h->copy_stream));
+        HIPCHK(h, hipEventRecord(h->ev_copied[w], h->copy_stream));
+        h->mirror_tag[w] = ++h->copy_count;
+    }
+    // the trial point is evaluated WITH its Jacobian, into the same buffers: when
+    // the step is accepted (the common case) nothing has to be recomputed
+    // The cost reduction that ends the evaluation also posts the hand-off (scalars + PCG control
+    // block) into the host mailbox; with several ranks the post follows the all-reduce of the cost.
+    const Mailbox mb{h->mbox_dev, sc, h->ctrl.as<PcgCtrl>() + (h->pcg_L & 1), ++h->mbox_seq, p2p_error_word(h)};
+    if (!f.one_rank && h->p2p.ready) {
+        // direct path: ONE single-workgroup launch sums K1's cost partials, reduces the cost over the
+        // ranks and posts the hand-off (or only posts, when k_tr_step cancelled the trial)
+        CHK(eval_jac(h->x_new, h->tab_new, true, /*finish=*/false));
+        const Piggyback pb = sum_rider(h, h->part.as<double>(), np_cost, kCostSlot);
+        CHK(p2p_allreduce(h, sc + kCostSlot, 1, 0, nullptr, 0, &pb, &mb, h->skip));
+        ++h->n_collectives;
+        return 0;
+    }
+    if (f.one_rank && !f.cost_rider) {
+        h->post = mb;
+        const int rc = eval_jac(h->x_new, h->tab_new, true);
+        h->post = Mailbox{};
+        return rc;
+    }
+    if (f.one_rank) {
+        // single rank: the cost sum and the post ride with the launch that builds the trial point's blocks
+        // (handoff), one launch less per iteration
+        CHK(eval_jac(h->x_new, h->tab_new, true, /*finish=*/false));
+        trial_post = mb;
+        trial_post_pending = true;
+        return 0;
+    }
+    CHK(eval_jac(h->x_new, h->tab_new, true));
+    CHK(exchange(h, sc + kCostSlot, 1, 0));
+    hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->stream, mb);
+    LAUNCHED(h);
+    return 0;
+}
+
+// While the host waits, the GPU already builds the normal-equation blocks of the trial point
+// (speculating on acceptance, the common case).  They overwrite V / g_p / [U|g_c], which a
+// rejected step does not need: a retry only re-solves the 2-D model (host scalars) and
+// re-applies k_step_table to x, D^2 g and p, all untouched.
+int Solve::handoff(bool with_ctrl) {
+    if (trial_post_pending) CHK(launch_normal_blocks(h, h->tab_new, h->rec_new, np_cost, trial_post));
+    else CHK(launch_normal_blocks(h, h->tab_new, h->rec_new));
+    trial_post_pending = false;
+    nb_valid = false;
+    // ... and, behind them, scale, gradient and partial sums of the trial point into the second buffer set
+    if (f.spec_scale) CHK(launch_update_scale(h, 0, /*defer=*/true, /*speculative=*/true));
+    CHK(fetch());
+    if (with_ctrl) memcpy(&hc, h->mbox + kMboxCtrl, sizeof hc);
+    return 0;
+}
+
+// ---- the first trial step is decided ON THE DEVICE (k_tr_step) and evaluated right away -------
+// so that an outer iteration hands control to the host ONCE, after the trial cost is known.
+int Solve::device_trial() {
+    missed = false;
+    for (bool speculative = pcg_guess > 0 || f.dense_solve;;) {        // dense: the control block always says "finished"
+        hipLaunchKernelGGL(k_tr_step, dim3(1), dim3(f.one_rank ? 1024 : 64), 0, h->stream, sc, Delta,
+                           speculative ? (const PcgCtrl*)(h->ctrl.as<PcgCtrl>() + (h->pcg_L & 1)) : (const PcgCtrl*)nullptr,
+                           f.one_rank ? backsub_rider(h, np_tail) : Piggyback{});
+        LAUNCHED(h);
+        h->skip = sc + kSkipSlot;                               // k_tr_step's verdict gates every launch below
+        int rc_trial = enqueue_trial(sc + kStepSlot, 0.0, 0.0);
+        if (rc_trial == 0) rc_trial = handoff(speculative);     // THE hand-off of this iteration
+        h->skip = nullptr;
+        CHK(rc_trial);
+        if (!(speculative && hc.done == 0)) break;
+        // The PCG needed more iterations than were enqueued.  k_tr_step saw that on the device and
+        // cancelled the trial launches, so J, r and the normal blocks still describe x: finish the
+        // PCG (host-polled), redo the tail and decide the step on the device again -- the arithmetic of
+        // an iteration does not depend on whether its guess sufficed.
+        missed = true;
+        nb_valid = true;
+        if (opt.profile && !evs.empty()) {                      // the cancelled launch is not a K1 timing sample
+            (void)hipEventDestroy(evs.back().first);
+            (void)hipEventDestroy(evs.back().second);
+            evs.pop_back();
+        }
+        CHK(pcg_finish_polling(h, opt, &hc));
+        CHK(tail());
+        speculative = false;
+    }
+    // hc.done == 3: the CG recurrences lost positive definiteness (rounding, typically on a converged
+    // system whose right-hand side is noise).  The iterate of the last good step is kept -- it is
+    // zero when the very first step failed, in which case the 2-D model degenerates to the
+    // steepest-descent line, exactly scipy's fallback when gn_h adds nothing to span(g_h).
+    if (hc.done == 3) ++pcg_breakdowns;
+    if (Delta < 0.0) Delta = hs[kRadiusSlot];                   // quick start: the radius k_tr_step derived and used
+    return 0;
+}
+
+// Next guess: the largest recent count, forgotten by one iteration per outer iteration.  A surplus
+// iteration costs two empty launches (~10 us); a miss costs a hand-off per polled batch.
+void Solve::record_pcg_count() {
+    pcg_total += hc.iters;
+    if (h->dbg.trace_pcg && f.dense_solve)
+        fprintf(stderr, "sfmba: iteration %lld: PCG in LDS, %d iterations, outcome %d, reg %.3e\n", (long long)iteration,
+                hc.iters, hc.done, hs[kRegSlot]);
+    else if (h->dbg.trace_pcg)
+        fprintf(stderr, "sfmba: iteration %lld: PCG enqueued %d, needed %d%s\n", (long long)iteration,
+                pcg_enqueued, hc.iters, missed ? " (miss)" : "");
+    h->pcg_hint = std::max(hc.iters, h->pcg_hint - 1);
+    pcg_hist_new.push_back(hc.iters);
+    const int bias = h->dbg.pcg_guess_bias;                     // test hook (sfmba_debug_option)
+    const int rec = (iteration + 1 < (int64_t)h->pcg_hist.size()) ? h->pcg_hist[iteration + 1] : 0;
+    guess_exact = rec > 0 && bias == 0 && hist_same;
+    pcg_guess = std::max(1, (guess_exact ? rec : h->pcg_hint) + bias);
+    reg_term = hs[kRegSlot];
+}
+
+// trf.py:488: the first trial was decided and evaluated on the device (device_trial); a retry after a rejected step
+// (or fallback) is solved on the host from the same 2-D model
+int Solve::step_loop() {
+    const double x_norm = std::sqrt(qsum(3));
+    const TrModel model = tr_build_model(hs[kG11Slot], hs[kTailSlot], hs[kTailSlot + 1], qsum(1), qsum(5), qsum(6), qsum(4),
+                                         qsum(7), qsum(8));
+    actual_reduction = -1.0;
+    cost_new = cost;
+    for (bool first = true; actual_reduction <= 0.0 && nfev < max_nfev; first = false) {
+        TrStep st;
+        if (first) {
+            st.c1 = hs[kStepSlot]; st.c2 = hs[kStepSlot + 1]; st.predicted = hs[kStepSlot + 2];
+            st.step_h_norm = hs[kStepSlot + 3]; st.step_norm = hs[kStepSlot + 4];
+        } else {
+            st = tr_solve_step(model, Delta);
+            CHK(enqueue_trial(nullptr, st.c1, st.c2));
+            CHK(handoff(false));
+        }
+        ++nfev;
+        cost_new = 0.5 * hs[kCostSlot];
+        if (!std::isfinite(cost_new)) {                         // trf.py:504-506
+            Delta = 0.25 * st.step_h_norm;
+            continue;
+        }
+        actual_reduction = cost - cost_new;
+        double ratio;
+        const double Delta_new = update_tr_radius(Delta, actual_reduction, st.predicted, st.step_h_norm,
+                                                  st.step_h_norm > 0.95 * Delta, &ratio);
+        step_norm = st.step_norm;
+        const int term = check_termination(actual_reduction, cost, step_norm, x_norm, ratio, opt.ftol, opt.xtol);
+        if (term != 0) { status = term; break; }
+        Delta = Delta_new;
+    }
+    have_red = true;
+    return 0;
+}
+
+int Solve::accept_or_reject() {
+    if (!(actual_reduction > 0.0)) {
+        step_norm = 0.0;
+        actual_reduction = 0.0;
+        return 0;
+    }
+    std::swap(h->x, h->x_new);                                  // trf.py:528
+    std::swap(h->tab, h->tab_new);
+    std::swap(h->rec, h->rec_new);
+    h->x_tag = h->mirror_tag[h->x == h->xa.as<double>() ? 0 : 1];      // (0 when no mirror copy was made)
+    nb_valid = true;                                            // J, f and the normal blocks of the accepted
+                                                                // point are already there / in flight
+    cost = cost_new;
+    ++njev;
+    if (status != -1 && f.early_download && !h->mirror_on) {
+        // The solve ends on this point.  x was written by k_step_table, which the stream ran before the K1 / K3
+        // whose post the host has just read, and nothing from here on writes it: the result leaves on the copy
+        // stream now, beside what is left of K3, k_update_scale, the final sums and the last post.
+        CHK(ensure_h_x(h));
+        t_sent0 = now_s();
+        // (in ONE piece: two halves, the first half's pinned -> pageable copy beside the second half's transfer,
+        // measured 1.805-1.822 ms per cfg4 solve against 1.792-1.849 -- no gain, two blit launches)
+        HIPCHK(h, hipMemcpyAsync(h->h_x, h->x, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->copy_stream));
+        HIPCHK(h, hipEventRecord(h->ev_copied[0], h->copy_stream));
+        h->result_in_flight = true;
+        result_sent = true;
+        t_sent1 = now_s();
+    }
+    if (!f.spec_scale) return launch_update_scale(h, 0, /*defer=*/true);
+    std::swap(h->g_cur, h->g_new);                              // already enqueued behind K3 (handoff): take its outputs
+    std::swap(h->si_cur, h->si_new);
+    std::swap(h->sg_cur, h->sg_new);
+    h->pending_scale_sums = true;                               // its final sums ride with the next k_jdot and
+    return 0;                                                   // are read with the next hand-off
+}
+
+int Solve::terminate() {                                        // terminated inside the step loop
+    if (h->pending_scale_sums) {                                // no k_jdot follows
+        CHK(flush_scale_sums(h));
+        CHK(exchange_linearise(h));
+    }
+    CHK(fetch_scalars(h));
+    g_norm = std::max(hs[kMaxSlot], hs[kCamSlot + 0]);
+    if (opt.verbose >= 2) print_iter(h, iteration, nfev, cost, have_red, actual_reduction, step_norm, g_norm);
+    return 0;
+}
+
+// the result vector into the caller's array, the record of this solve, the result struct
+int Solve::deliver(double* x_out) {
     if (!nb_valid) {                                            // last trial was not accepted: result.fun is f(x)
         int np = 0;
         CHK((launch_resjac<false, true>(h, h->x, h->tab, &np)));
     }
-
     CHK(ensure_h_x(h));
     const double t_dl0 = now_s();
     const int xw = h->x == h->xa.as<double>() ? 0 : 1;
     const bool mirrored = h->mirror_on && h->x_tag != 0 && h->mirror_tag[xw] == h->x_tag;     // x is on the host already
     const size_t xbytes = sizeof(double) * (size_t)n;
-    if (!mirrored && !result_sent) {
-        HIPCHK(h, hipMemcpyAsync(h->h_x, h->x, xbytes, hipMemcpyDeviceToHost, h->stream));
-    }
+    if (!mirrored && !result_sent) HIPCHK(h, hipMemcpyAsync(h->h_x, h->x, xbytes, hipMemcpyDeviceToHost, h->stream));
     if (h->p2p.ready)                                           // did a direct all-reduce give up waiting for a peer?
-        HIPCHK(h, hipMemcpyAsync(h->h_scal + 62, h->p2p.words + 1, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->h_scal + kPinP2pErr, h->p2p.words + 1, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     // (result_sent: the last launch of the stream is the k_post whose post fetch_scalars has waited for; the query
     // still lets the runtime retire the solve's launches while the copy is in flight)
     CHK(wait_stream(h));
-    t_ws = now_s();
+    const double t_ws = now_s();
     if (result_sent) {
-        CHK(wait_event(h, h->ev_copied[0]));
+        CHK(wait_stream(h, h->ev_copied[0]));
         h->result_in_flight = false;
     }
     if (mirrored) HIPCHK(h, hipEventSynchronize(h->ev_copied[xw]));
     const double t_dl1 = now_s();
     if (h->p2p.ready) {
         unsigned err = 0;
-        memcpy(&err, h->h_scal + 62, sizeof err);
+        memcpy(&err, h->h_scal + kPinP2pErr, sizeof err);
         if (err != 0) return p2p_timed_out(h, err);
     }
-    staging_copy(h, x_inout, mirrored ? h->mirror[xw].p : (const void*)h->h_x, xbytes);
+    staging_copy(h, x_out, mirrored ? h->mirror[xw].p : (const void*)h->h_x, xbytes);
     if (h->mirror_on) HIPCHK(h, hipStreamSynchronize(h->copy_stream));     // (a copy of a rejected last trial may still run)
     const double t_end = now_s();
     if (h->dbg.trace_timing && result_sent)
@@ -3201,7 +3140,7 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
     out->optimality = g_norm;
     out->rmse = std::sqrt(2.0 * cost / m_total);
     out->nfev = nfev; out->njev = njev; out->iterations = iteration; out->pcg_iterations = pcg_total;
-    out->status = status;
+    out->status = status == -1 ? 0 : status;
     out->seconds_total = t_end - t_begin;
     out->seconds_device = t_end - t_dev0;
     out->last_step_norm = step_norm;
@@ -3209,6 +3148,63 @@ static int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, c
     out->reserved = (int32_t)pcg_breakdowns;
     h->solved = true;
     return 0;
+}
+
+int Solve::run(const double* x_start, double* x_out) {
+    CHK(start(x_start));
+    recall_pcg_record(x_start);
+    if (opt.verbose >= 2) print_header(h);
+    for (;;) {                                                  // trf.py:450
+        CHK(linear_phase());
+        CHK(device_trial());
+        // ---- loop head of trf.py:450-459, evaluated now that the scalars are on the host -----------
+        g_norm = std::max(hs[kMaxSlot], hs[kCamSlot + 0]);
+        if (g_norm < opt.gtol) status = 1;
+        if (opt.verbose >= 2) print_iter(h, iteration, nfev, cost, have_red, actual_reduction, step_norm, g_norm);
+        if (status != -1 || nfev >= max_nfev || (opt.max_iter > 0 && iteration >= opt.max_iter)) break;
+        record_pcg_count();
+        CHK(step_loop());
+        CHK(accept_or_reject());
+        ++iteration;
+        if (status != -1) { CHK(terminate()); break; }
+    }
+    return deliver(x_out);
+}
+
+int solve_impl(sfmba_handle* h, const double* x_start, double* x_inout, const sfmba_options* opt_in, sfmba_result* out) {
+    CHK(enter(h));
+    CHK(begin_compute(h, x_start));
+    if (!x_inout) return fail(h, -1, "x_out is NULL");
+    if (!out) return fail(h, -1, "result is NULL");
+    sfmba_options opt;
+    if (opt_in) opt = *opt_in; else sfmba_default_options(&opt);
+    memset(out, 0, sizeof *out);
+    Solve s{h, opt, out};
+    return s.run(x_start, x_inout);
+}
+}  // namespace
+
+int sfmba_solve(sfmba_handle* h, double* x_inout, const sfmba_options* opt_in, sfmba_result* out) {
+    return sfmba_solve_from(h, x_inout, x_inout, opt_in, out);
+}
+
+int sfmba_solve_from(sfmba_handle* h, const double* x0, double* x_out, const sfmba_options* opt_in, sfmba_result* out) {
+    const int rc = solve_impl(h, x0, x_out, opt_in, out);
+    if (rc != 0 && h) {
+        // Leave the handle reusable: drain what was enqueued (speculative launches may still be in flight) and,
+        // after a collective failure, unmap the peers -- sequence numbers no longer agree across ranks, so the
+        // direct link is dead; the transport registered before it (RCCL / callback) serves later solves.
+        const std::string msg = h->err;
+        h->skip = nullptr; h->post = Mailbox{};
+        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
+        if (rc == -5 && h->p2p.ready) {
+            p2p_close_peers(h);
+            if (h->p2p.words) (void)hipMemset(h->p2p.words, 0, 4 * sizeof(unsigned));
+        }
+        h->err = msg;
+    }
+    return rc;
 }
 
 int sfmba_get_fun_grad(sfmba_handle* h, double* fun_out, double* grad_out) {
