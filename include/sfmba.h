@@ -186,6 +186,9 @@ int64_t sfmba_p2p_calls(const sfmba_handle* h);      /* collectives served by th
 /* Running totals since sfmba_create: kernel launches enqueued by the library and collectives performed (any
  * transport).  Differences around a solve give launches / collectives per outer iteration (bench.py). */
 int  sfmba_get_counters(const sfmba_handle* h, int64_t* kernel_launches, int64_t* collectives);
+/* Which kernel form the current problem runs (the problem stage of the forms table): value = 0 / 1 for name =
+ * "lds_tab", "lds_vec", "sweep_rc", "sweep_rc_g", "pcg_fused", "mixed", "jfree", "rc_cons", "dense". */
+int  sfmba_get_form(sfmba_handle* h, const char* name, int32_t* value);
 /* PCG iterations of every outer iteration of the last completed sfmba_solve on this handle (the record the next
  * solve's speculative launches are sized from); returns the number of outer iterations, writes min(that, cap)
  * entries.  What the full-size parity tests compare with the recorded oracle runs (tests/golden/oracle_cfg*.json). */
@@ -215,7 +218,8 @@ int  sfmba_get_fun_grad(sfmba_handle* h, double* fun_out, double* grad_out);
  *        2 the camera pass of the normal equations (U_c, g_c, and the point rows the sweep's tiles cut),
  *        3 one implicit Schur product (pass A + pass B), 4 pass A alone, 5 pass B alone, 6 the reduced
  *        right-hand-side pass, 7 the residual+Jacobian sweep with its point-block sums switched off,
- *        10 a streaming-store fill of the Jacobian buffer (ceiling probe).
+ *        10 a streaming-store fill of the Jacobian buffer (ceiling probe),
+ *        11 k_jdot and 12 k_backsub (without its PCG prologue) in the form the problem has selected ("rc_consumers").
  * avg_us: average duration of one repetition. */
 int  sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t reps, double* avg_us);
 /* Normal-equation blocks at x: U (C,21 upper triangle row-major), V (P,6 upper), gc (C,6), gp (P,3). */
@@ -224,6 +228,17 @@ int  sfmba_normal_blocks(sfmba_handle* h, const double* x, double* U, double* V,
 /* y = S v with S = U + diag(dc) - W (V + diag(dp))^-1 W^T at x (v, dc, y: 6C; dp: 3P). */
 int  sfmba_schur_matvec(sfmba_handle* h, const double* x, const double* dc, const double* dp,
                         const double* v, double* y);
+
+/* The two products of an outer iteration with the whole Jacobian, by the kernels the solver itself runs in the form the
+ * problem has selected ("rc_consumers"): k_jdot, t1 = J sg with sum |t1|^2, and k_backsub for the camera step dc:
+ * dp = (V + diag(dp_diag))^-1 (-g_p - sum Jp^T Jc dc) per point, t2 = J [dc; dp], and its ten sums
+ * (t1.t2, t2.t2; g.p, |p / scale|^2, (D^2 g).p, |p|^2 of the point slice; the same four of the camera slice), where g and
+ * the column scale are those of x, D^2 g of the cameras is sg, and D^2 g of the points is g_p * scale_p^2 as the solver has it.
+ * x, sg: 6C+3P; dc: 6C; dp_diag: 3P.  t1_out: 2N in the caller's observation order; dp_out: 3P; sums_out: 10;
+ * g_out, si_out (6C+3P, either may be NULL): the gradient and the inverse column scale the sums were formed with.
+ * Single rank, 64-bit storage. */
+int  sfmba_step_products(sfmba_handle* h, const double* x, const double* sg, const double* dc, const double* dp_diag,
+                         double* t1_out, double* g11_out, double* dp_out, double* sums_out, double* g_out, double* si_out);
 
 /* Few-camera path (6 n_cameras <= 128, the reference's own problem sizes): at x, with the diagonals dc (6C) and dp
  * (3P), form S = U + diag(dc) - W (V + diag(dp))^-1 W^T (S_out: (6C)^2 row-major, may be NULL) and solve S y = rhs
@@ -281,6 +296,10 @@ int  sfmba_tr2d_solve(const double* B3, const double* g2, double Delta, double* 
  *                       observations on); "packed_upload" P 1 / 0: observation arrays uploaded packed (same default)
  *   "jfree"          P  1: the J-free iteration (measurement): K1 does not write the Jacobian, k_jdot / k_backsub
  *                       recompute its blocks (needs the camera table in LDS)
+ *   "rc_consumers"   P  0: k_jdot and k_backsub read the stored Jacobian; 1: their row form wherever it is legal, whatever the
+ *                       size (default, -1: by the forms table -- the row form, which takes J (D^2 g) and J p from pass A's LDS
+ *                       camera rows and the point instead of the stored blocks, from 65536 observations on, with 64-bit
+ *                       storage, whenever pass A runs in its LDS row form)
  *   "pcg_guess_bias"    added to the number of speculatively enqueued PCG iterations (negative: force misses)
  *   "wait_deadline_s"   a hand-off not posted within this many seconds fails the solve with -3 (default 120)
  *   "p2p_delay_ms"      sleep before the first collective of a solve (late-peer test)

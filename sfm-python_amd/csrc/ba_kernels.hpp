@@ -3837,6 +3837,287 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub(
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_jdot and k_backsub in ROW FORM (Forms::rc_cons): the two products with the whole Jacobian, J (D^2 g) and J p, taken
+// the way pass A (k_point_sweep_rc) takes Jc u -- from the LDS table R | T | a' | u_T of the vector's camera slice and the
+// point, without the stored blocks (96 of the 120 bytes those kernels read per observation):
+//     j_k = row k of d r / d X (the same expressions as observe<true>: the same bits as the stored point block),
+//     (Jc u)_k = -j_k . (v x a' + u_T),       (J [u; w])_k = (Jc u)_k + j_k . w_p.
+// 64-bit storage only: with 32-bit storage the consumers have to apply the stored, rounded blocks.
+// ---------------------------------------------------------------------------------------------
+// a' and u_T of camera `cam` from its six entries u (put_au of pass A)
+__device__ __forceinline__ void rc_put_au(const double* __restrict__ wbc, int C, int cam, const double* u,
+                                          double* __restrict__ tab_lds) {
+    const double wx = wbc[cam], wy = wbc[(size_t)C + cam], wz = wbc[2 * (size_t)C + cam];
+    const double b = wbc[3 * (size_t)C + cam], cc = wbc[4 * (size_t)C + cam];
+    const double c0 = wy * u[2] - wz * u[1], c1 = wz * u[0] - wx * u[2], c2 = wx * u[1] - wy * u[0];   // w x u_w
+    const double d0 = wy * c2 - wz * c1, d1 = wz * c0 - wx * c2, d2 = wx * c1 - wy * c0;               // w x (w x u_w)
+    double* __restrict__ row = tab_lds + (size_t)kRcRow * cam;
+    row[12] = u[0] - b * c0 + cc * d0; row[13] = u[1] - b * c1 + cc * d1; row[14] = u[2] - b * c2 + cc * d2;
+    row[15] = u[3]; row[16] = u[4]; row[17] = u[5];
+}
+// R | T of every camera into the table: 6 x 16 bytes per camera, coalesced; ends with the barrier
+__device__ __forceinline__ void rc_stage_rt(const double* __restrict__ rt, int C, double* __restrict__ tab_lds) {
+    for (int e = threadIdx.x; e < C * (kCamRT / 2); e += blockDim.x) {
+        const int cam = e / (kCamRT / 2), k = e - cam * (kCamRT / 2);
+        reinterpret_cast<double2*>(tab_lds + (size_t)kRcRow * cam)[k] = reinterpret_cast<const double2*>(rt)[e];
+    }
+    __syncthreads();
+}
+// One observation from its camera's row (nine 16-byte pieces) and its point: j (2x3 row-major) and t_k = (Jc u)_k.
+// The arithmetic of `contrib` in k_point_sweep_rc.
+__device__ __forceinline__ void rc_row_products(const double2* __restrict__ row, const KMat& K, double X, double Y, double Z,
+                                                double* __restrict__ j, double* __restrict__ t) {
+    const double2 r01 = row[0], r23 = row[1], r45 = row[2], r67 = row[3], r8t = row[4], t12 = row[5];
+    const double2 a01 = row[6], a2u = row[7], u12 = row[8];
+    const double R0 = r01.x, R1 = r01.y, R2 = r23.x, R3 = r23.y, R4 = r45.x, R5 = r45.y, R6 = r67.x, R7 = r67.y,
+                 R8 = r8t.x;
+    const double vx = X - r8t.y, vy = Y - t12.x, vz = Z - t12.y;
+    const double qx = R0 * vx + R1 * vy + R2 * vz;
+    const double qy = R3 * vx + R4 * vy + R5 * vz;
+    const double qz = R6 * vx + R7 * vy + R8 * vz;
+    const double px = K.k[0] * qx + K.k[1] * qy + K.k[2] * qz;
+    const double py = K.k[3] * qx + K.k[4] * qy + K.k[5] * qz;
+    const double pz = K.k[6] * qx + K.k[7] * qy + K.k[8] * qz;
+    const double iz = 1.0 / pz;
+    const double ax = a01.x, ay = a01.y, az = a2u.x;
+    const double g0 = vy * az - vz * ay + a2u.y, g1 = vz * ax - vx * az + u12.x, g2 = vx * ay - vy * ax + u12.y;   // v x a' + u_T
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double pk = (k == 0 ? px : py) * iz;
+        const double b0 = (K.k[3 * k + 0] - pk * K.k[6]) * iz;
+        const double b1 = (K.k[3 * k + 1] - pk * K.k[7]) * iz;
+        const double b2 = (K.k[3 * k + 2] - pk * K.k[8]) * iz;
+        const double j0 = b0 * R0 + b1 * R3 + b2 * R6;            // row k of A R
+        const double j1 = b0 * R1 + b1 * R4 + b2 * R7;
+        const double j2 = b0 * R2 + b1 * R5 + b2 * R8;
+        j[3 * k + 0] = j0; j[3 * k + 1] = j1; j[3 * k + 2] = j2;
+        t[k] = -(j0 * g0 + j1 * g1 + j2 * g2);
+    }
+}
+
+// k_jdot in row form: t1 = J (D^2 g), sum |t1|^2.  Same grid, rider workgroup and part[block] as k_jdot.
+__global__ __launch_bounds__(kSweepThreads) void k_jdot_rc(
+    const int* __restrict__ cam_idx, const int* __restrict__ pt_idx, const double* __restrict__ camtab,
+    const double* __restrict__ pts, KMat K, const double* __restrict__ sgc, const double* __restrict__ sgp, int N, int C,
+    double* __restrict__ t1, double* __restrict__ part, Piggyback pb) {
+    extern __shared__ __align__(16) double smem[];
+    __shared__ double red[kWavesPerSweepBlock];
+    const int nwork = pb.part != nullptr ? (int)gridDim.x - 1 : (int)gridDim.x;
+    if ((int)blockIdx.x == nwork) { finish_in_block(pb); return; }      // rider block: another kernel's sums
+    const int stride = nwork * (int)blockDim.x;
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    int c = 0, p = 0;
+    if (i < N) { c = cam_idx[i]; p = pt_idx[i]; }                       // in flight under the prologue
+    for (int cam = threadIdx.x; cam < C; cam += blockDim.x) {           // sgc: camera-major, 48-byte rows
+        const double2* __restrict__ s2 = reinterpret_cast<const double2*>(sgc + 6 * (size_t)cam);
+        const double2 u01 = s2[0], u23 = s2[1], u45 = s2[2];
+        const double u[6] = {u01.x, u01.y, u23.x, u23.y, u45.x, u45.y};
+        rc_put_au(camtab + cam_wbc_offset(C), C, cam, u, smem);
+    }
+    rc_stage_rt(camtab + cam_rt_offset(C), C, smem);
+    double acc = 0.0;
+    while (i < N) {
+        const int in = i + stride;
+        int cn = 0, pn = 0;
+        if (in < N) { cn = cam_idx[in]; pn = pt_idx[in]; }              // the next trip's indices behind this one's work
+        const double* __restrict__ Xp = pts + 3 * (size_t)p;
+        const double* __restrict__ b = sgp + 3 * (size_t)p;
+        const double X = Xp[0], Y = Xp[1], Z = Xp[2], b0 = b[0], b1 = b[1], b2 = b[2];
+        double j[6], t[2];
+        rc_row_products(reinterpret_cast<const double2*>(smem + (size_t)kRcRow * c), K, X, Y, Z, j, t);
+        const double t0 = t[0] + (j[0] * b0 + j[1] * b1 + j[2] * b2);
+        const double t1v = t[1] + (j[3] * b0 + j[4] * b1 + j[5] * b2);
+        reinterpret_cast<double2*>(t1)[i] = make_double2(t0, t1v);
+        acc += t0 * t0 + t1v * t1v;
+        i = in; c = cn; p = pn;
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s += red[k];
+        part[blockIdx.x] = s;
+    }
+}
+
+// k_backsub in row form: everything k_backsub<true> does (the FinalUpdate prologue included; its comment applies), with the
+// finished camera step put into the LDS table as a' | u_T instead of as a 6 C vector.  The step's own entries are
+// therefore not in LDS: the camera dot products take them from where the prologue took them, by the same expression.
+__global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
+    const int2* __restrict__ ranges, int n_ranges, const int* __restrict__ cam_idx, const int* __restrict__ pt_idx,
+    const int* __restrict__ pt_ptr, const double* __restrict__ camtab, const double* __restrict__ pts, KMat K,
+    const double* __restrict__ dc_planes, double* __restrict__ dc, const double* __restrict__ Vinv,
+    const double* __restrict__ gp, const double* __restrict__ t1, double* __restrict__ dp, double* __restrict__ part, int C,
+    const PcgCtrl* __restrict__ ctrl2, int L, const double* __restrict__ gvec, const double* __restrict__ si,
+    const double* __restrict__ sg, FinalUpdate fu) {
+    extern __shared__ __align__(16) double smem[];
+    __shared__ double red[kBacksubCols * kWavesPerSweepBlock];
+    const double* __restrict__ wbc = camtab + cam_wbc_offset(C);
+    const int n6 = 6 * C;
+    const bool final_update = fu.part != nullptr;                         // grid-uniform
+    double alpha = 0.0;
+    bool add = false;
+    if (final_update) {
+        const int cam = threadIdx.x;
+        const PcgCtrl ci = fu.ctrl2[fu.L & 1];
+        PcgCtrl co = ci;
+        double xe[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, pe[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (cam < C) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                xe[k] = fu.vecs[kPcgX * n6 + (size_t)k * C + cam];
+                pe[k] = fu.vecs[kPcgP * n6 + (size_t)k * C + cam];
+            }
+        }
+        if (ci.done == 0) alpha = pcg_local_step(fu.part, C, ci, co);     // (else: finished earlier than the record says)
+        if (blockIdx.x == 0 && threadIdx.x == 0) fu.ctrl2[(fu.L + 1) & 1] = co;
+        if (co.done == 0) return;                                         // grid-uniform: the record was too short
+        add = ci.done == 0 && co.done != 3;                               // (3: x stays the last good iterate)
+        if (cam < C) {
+            double u[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                u[k] = add ? fma(alpha, pe[k], xe[k]) : xe[k];
+                if (blockIdx.x == 0) dc[6 * cam + k] = u[k];              // (the step vector only: see k_backsub)
+            }
+            rc_put_au(wbc, C, cam, u, smem);
+        }
+    } else {
+        if (ctrl2 != nullptr)                      // dc_planes = base of the PCG vector sets: take x of the final set
+            dc_planes += (size_t)((ctrl2[L & 1].iters & 1) * kPcgVecs + kPcgX) * n6;
+        for (int cam = threadIdx.x; cam < C; cam += blockDim.x) {
+            double u[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                u[k] = dc_planes[(size_t)k * C + cam];
+                if (blockIdx.x == 0) dc[6 * cam + k] = u[k];
+            }
+            rc_put_au(wbc, C, cam, u, smem);
+        }
+    }
+    rc_stage_rt(camtab + cam_rt_offset(C), C, smem);
+    const int wg = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    int pos = 0, end = 0;
+    if (wg < n_ranges) { const int2 rg = ranges[wg]; pos = rg.x; end = rg.y; }
+    double g12 = 0.0, g22 = 0.0;
+    double qs[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};       // q5..q8: [0..3] points, [4..7] cameras
+    auto products = [&](int j, double X, double Y, double Z, double* jp, double* t) {      // observation j, its point
+        rc_row_products(reinterpret_cast<const double2*>(smem + (size_t)kRcRow * cam_idx[j]), K, X, Y, Z, jp, t);
+    };
+    // point entries: g is g_p itself and D^2 g = g / s^2 exactly as k_update_scale formed it
+    auto point_dots = [&](int p, const double* s3, double z0, double z1, double z2) {
+        const double z[3] = {z0, z1, z2};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double s_ = s3[k], ge = gp[3 * (size_t)p + k], pe = z[k];
+            qs[0] += ge * pe; qs[1] += (pe * s_) * (pe * s_); qs[2] += (ge / (s_ * s_)) * pe; qs[3] += pe * pe;
+        }
+    };
+    auto solve_point = [&](int p, const double* y, double& z0, double& z1, double& z2) {
+        const double* vi = Vinv + kVinvRow * (size_t)p;
+        const double b0 = -gp[3 * (size_t)p] - y[0], b1 = -gp[3 * (size_t)p + 1] - y[1],
+                     b2 = -gp[3 * (size_t)p + 2] - y[2];
+        z0 = vi[0] * b0 + vi[1] * b1 + vi[2] * b2;
+        z1 = vi[1] * b0 + vi[3] * b1 + vi[4] * b2;
+        z2 = vi[2] * b0 + vi[4] * b1 + vi[5] * b2;
+        dp[3 * (size_t)p] = z0; dp[3 * (size_t)p + 1] = z1; dp[3 * (size_t)p + 2] = z2;
+    };
+    auto gram = [&](int i, const double* jp, const double* t, double z0, double z1, double z2) {
+        const double a0 = t[0] + jp[0] * z0 + jp[1] * z1 + jp[2] * z2;
+        const double a1 = t[1] + jp[3] * z0 + jp[4] * z1 + jp[5] * z2;
+        const double2 tt = reinterpret_cast<const double2*>(t1)[i];
+        g12 += tt.x * a0 + tt.y * a1;
+        g22 += a0 * a0 + a1 * a1;
+    };
+
+    while (pos < end) {
+        const int i = pos + lane;
+        const bool in = i < end;
+        const int p = in ? pt_idx[i] : pt_idx[pos];
+        const int sb = pt_ptr[p], se = pt_ptr[p + 1];
+        const bool complete = in && (se <= pos + 64);
+        const int n_take = __popcll(__ballot(complete));
+        double jp[6], t[2];
+        if (n_take == 0) {                             // one point with more observations than the window holds
+            const int run_end = __shfl(se, 0);
+            const int pp = __shfl(p, 0);
+            const double* __restrict__ Xp = pts + 3 * (size_t)pp;
+            const double X = Xp[0], Y = Xp[1], Z = Xp[2];
+            double y[3] = {0.0, 0.0, 0.0};
+            for (int j = pos + lane; j < run_end; j += 64) {
+                products(j, X, Y, Z, jp, t);
+                y[0] += jp[0] * t[0] + jp[3] * t[1]; y[1] += jp[1] * t[0] + jp[4] * t[1];
+                y[2] += jp[2] * t[0] + jp[5] * t[1];
+            }
+            y[0] = wave_sum(y[0]); y[1] = wave_sum(y[1]); y[2] = wave_sum(y[2]);
+            double z0, z1, z2;
+            solve_point(pp, y, z0, z1, z2);              // every lane writes the same values
+            if (lane == 0) point_dots(pp, si + 6 * (size_t)C + 3 * (size_t)pp, z0, z1, z2);
+            for (int j = pos + lane; j < run_end; j += 64) {
+                products(j, X, Y, Z, jp, t);
+                gram(j, jp, t, z0, z1, z2);
+            }
+            pos = run_end;
+            continue;
+        }
+        const bool act = lane < n_take;
+        double z0 = 0.0, z1 = 0.0, z2 = 0.0;
+        double y[3] = {0.0, 0.0, 0.0};
+        double s3[3] = {1.0, 1.0, 1.0};        // scale entries of the lane's point, requested with the point so
+        t[0] = 0.0; t[1] = 0.0;                // that the run head does not wait for them after the reduction
+        if (act) {
+            const double* __restrict__ Xp = pts + 3 * (size_t)p;
+            const double X = Xp[0], Y = Xp[1], Z = Xp[2];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s3[k] = si[6 * (size_t)C + 3 * (size_t)p + k];
+            products(i, X, Y, Z, jp, t);
+            y[0] = jp[0] * t[0] + jp[3] * t[1]; y[1] = jp[1] * t[0] + jp[4] * t[1];
+            y[2] = jp[2] * t[0] + jp[5] * t[1];
+        }
+        seg_reduce_serial<3>(y, act ? sb : -1 - lane, lane);
+        if (act && i == sb) { solve_point(p, y, z0, z1, z2); point_dots(p, s3, z0, z1, z2); }
+        const int head = act ? lane - (i - sb) : lane;
+        z0 = __shfl(z0, head); z1 = __shfl(z1, head); z2 = __shfl(z2, head);
+        if (act) gram(i, jp, t, z0, z1, z2);
+        pos += n_take;
+    }
+    {   // camera slice, a few elements per workgroup so that none straggles; after the sweep, so that its four sums
+        // are not live across it.  Element e = 6 cam + k of the step, formed as the prologue formed it.
+        const int per = (n6 + (int)gridDim.x - 1) / (int)gridDim.x;
+        const int e = (int)blockIdx.x * per + (int)threadIdx.x;
+        if ((int)threadIdx.x < per && e < n6) {
+            const int cam = e / 6, k = e - 6 * cam;
+            double pe;
+            if (final_update) {
+                const double xk = fu.vecs[kPcgX * n6 + (size_t)k * C + cam];
+                pe = add ? fma(alpha, fu.vecs[kPcgP * n6 + (size_t)k * C + cam], xk) : xk;
+            } else {
+                pe = dc_planes[(size_t)k * C + cam];
+            }
+            const double s = si[e];
+            qs[4] += gvec[e] * pe; qs[5] += (pe * s) * (pe * s); qs[6] += sg[e] * pe; qs[7] += pe * pe;
+        }
+    }
+    double row[kBacksubCols];
+    row[0] = wave_sum(g12);
+    row[1] = wave_sum(g22);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) row[2 + k] = wave_sum(qs[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < kBacksubCols; ++k) red[kBacksubCols * (threadIdx.x >> 6) + k] = row[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kBacksubCols) {                   // one thread per column, waves added in fixed order
+        double a = 0.0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) a += red[kBacksubCols * w + threadIdx.x];
+        part[(size_t)kBacksubCols * blockIdx.x + threadIdx.x] = a;
+    }
+}
+
 // out [cols][rows] <- in [rows][cols]; camera-major [C][6] <- plane-major [6][C] with rows = 6, cols = C.
 // ctrl2 != null: `in` is the base of the PCG vector sets, take x of the final set.
 __global__ void k_transpose(const double* __restrict__ in, int rows, int cols, double* __restrict__ out,

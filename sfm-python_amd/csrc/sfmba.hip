@@ -225,6 +225,7 @@ double now_s() {
     X(cost_rider, -1)     /* 0: the trial cost is summed and posted by a k_finish launch of its own */ \
     X(packed_upload, -1)  /* 0: the observation arrays are uploaded as int32 / fp64 although they would pack */ \
     X(jfree, -1)          /* 1: the J-free iteration (measurement): K1 does not write the Jacobian, k_jdot and k_backsub recompute its blocks from the LDS camera table */ \
+    X(rc_consumers, -1)   /* 0: k_jdot and k_backsub read the stored Jacobian although their row form would apply; 1: the row form wherever it is legal, whatever the size */ \
     X(cm_device, -1)      /* 0: the camera-major order is sorted on the host and its permutation uploaded */ \
     X(pcg_inline, -1)     /* 0: sharded solves keep the collective of the product as a launch of its own */ \
     X(xcd_cam, -1)        /* 0: K3 and the rhs pass keep the one-chunk-per-camera table where pass B takes the XCD-aware one */ \
@@ -269,6 +270,7 @@ struct Forms {
     bool mixed = false;                      // pass A
     bool mixed_b = false;                    // ... and pass B (fp32 point records)
     bool jfree = false;                      // J-free iteration (needs the camera table in LDS)
+    bool rc_cons = false;                    // k_jdot / k_backsub in row form (k_jdot_rc, k_backsub_rc): the stored Jacobian is not read
     bool dense = false;                      // reduced camera matrix formed and factorised (6 C <= kDenseMaxN) instead of PCG
     bool xcd_b = false;                      // pass B takes the XCD-aware chunk table (every camera's list cut at eight point ranges)
     bool use_rhsrec = false;                 // the rhs + preconditioner pass gathers its own 128-byte records (many points)
@@ -531,6 +533,8 @@ void p2p_fill_args(sfmba_handle* h, P2pArgs& a) {
 //   mixed (pass A fp32 ops)   | fp32 storage and a recomputing pass A                            | pcg_mixed = 1 / 0
 //   mixed_b (pass B too)      | mixed                                                            | pcg_mixed_b = 0
 //   jfree                     | on request, with lds_tab                                         | jfree = 1
+//   rc_cons (k_jdot, k_backsub in row form) | N >= 65536, 64-bit storage and sweep_rc (FinalUpdate needs a thread per camera: skip_last = 2 implies pcg_fused, C <= 1024) | rc_consumers = 0; 1 (whatever N)
+//           stored Jacobian   | else: fp32 storage (the stored, rounded blocks are the operator), more cameras than the LDS table takes, sweep_rc = 0 |
 //   dense                     | 6 C <= kDenseMaxN and at most 2^26 pair-list entries             | dense = 0
 //   use_rhsrec (rhs pass)     | P >= 250000                                                      | rhsrec = 1 / 0
 // So cfg4 (1000 cameras / 100k points / 1M observations, fp64): pass A k_point_sweep_rc<FUSED> (sweep_rc, pcg_fused), pass B
@@ -561,6 +565,9 @@ Forms decide_problem_forms(int64_t C, int64_t P, int64_t N, bool f32, int n_cu, 
     f.mixed = (f.sweep_rc || f.sweep_rc_g) && by_size(dbg.pcg_mixed, f32);
     f.mixed_b = f.mixed && dbg.pcg_mixed_b != 0;
     f.jfree = dbg.jfree == 1 && f.lds_tab;
+    // (the row form saves the 96 bytes of J per observation and pays a 144-byte table prologue per workgroup and a longer
+    // dependent chain per observation: even at 30k observations, 1 % ahead at 64k, 3-4 % of a solve from 100k on)
+    f.rc_cons = !f32 && f.sweep_rc && by_size(dbg.rc_consumers, N >= 65536);
     f.dense = 6 * C <= kDenseMaxN && dbg.dense != 0 && facts.pair_entries <= ((int64_t)1 << 26);   // (very long tracks: the pair lists would not pay)
     // One 128-byte gather record per point for k_cam_rhs_diag pays once the point tables no longer sit in the L2s
     // (1M points: 432 -> 188 us); at 100k points the two 4.8 MB tables it replaces are L2-resident and k_prep's 11 MB of
@@ -584,7 +591,7 @@ Forms decide_problem_forms(int64_t C, int64_t P, int64_t N, bool f32, int n_cu, 
 //     else pcg_split: k_p2p_pcg, or collective + k_pcg_tail     | local and spread                   | pcg_split = 0 (1: not spread too)
 //     else collective + k_pcg_update (fused: pass A's prologue) | spread; one rank: nothing to reduce |
 //   pcg_local, pcg_local2     | pcg_fused / sweep_rc_g without it; not spread, or split / inline | pcg_local = 0
-//   skip_last                 | pcg_fused and (one rank or pcg_inline): 2 if pcg_local, lds_vec and not jfree, else 1 | pcg_skip_last = 0, 2 (-> 1)
+//   skip_last                 | pcg_fused and (one rank or pcg_inline): 2 if pcg_local and (rc_cons, or lds_vec and not jfree), else 1 | pcg_skip_last = 0, 2 (-> 1)
 //   dense_solve               | dense and one rank                                               | dense = 0
 //   quick_start, spec_scale, cost_rider | one rank                     | start_handoff = 0 or cost_rider = 0; spec_scale = 0; cost_rider = 0
 //   early_download            | the copy stream exists                                           | early_download = 0
@@ -623,7 +630,7 @@ void decide_solve_forms(sfmba_handle* h) {
     // (several ranks: only where the product's exchange sits inside pass B -- every rank then takes the same
     // decision from the same record, and a launch that is not enqueued exchanges nothing on any of them)
     f.skip_last = !(f.pcg_fused && (f.one_rank || f.pcg_inline) && d.pcg_skip_last != 0) ? 0
-                  : (f.pcg_local && f.lds_vec && !f.jfree && d.pcg_skip_last != 2) ? 2 : 1;
+                  : (f.pcg_local && (f.rc_cons || (f.lds_vec && !f.jfree)) && d.pcg_skip_last != 2) ? 2 : 1;
     f.dense_solve = f.dense && f.one_rank;
     // (single rank only -- with several ranks the cost and the scale sums pass through collectives between these launches)
     f.quick_start = f.one_rank && d.start_handoff != 0 && d.cost_rider != 0;
@@ -1136,6 +1143,14 @@ int launch_jdot(sfmba_handle* h, int* nparts) {
         LAUNCHED(h);
         return 0;
     };
+    if (h->forms.rc_cons) {
+        const size_t lds = sizeof(double) * kRcRow * (size_t)h->C;
+        CHK(set_lds(h, k_jdot_rc, lds));
+        hipLaunchKernelGGL(k_jdot_rc, dim3(launch_grid), dim3(kSweepThreads), lds, h->stream, (const int*)h->cam_idx.as<int>(),
+                           (const int*)h->pt_idx.as<int>(), rc.camtab, rc.pts, h->K, sgc, sgp, (int)h->N, (int)h->C,
+                           h->t1.as<double>(), h->partB(), pb);
+        LAUNCHED(h);
+    } else
     CHK(h->forms.jfree ? run(k_jdot<false, true>, sizeof(double) * kCamRow * (size_t)h->C)
         : h->forms.lds_vec ? run(k_jdot<true>, sizeof(double) * 6 * (size_t)h->C) : run(k_jdot<false>, 0));
     h->pending_scale_sums = false;
@@ -1143,28 +1158,42 @@ int launch_jdot(sfmba_handle* h, int* nparts) {
     return 0;
 }
 
-int launch_backsub(sfmba_handle* h, int* nparts) {
+// `planes` (test and timing entries): the camera step as a plane-major vector of its own instead of x of the PCG's final set
+int launch_backsub(sfmba_handle* h, int* nparts, const double* planes = nullptr) {
     const int grid = (h->n_ranges + kWavesPerSweepBlock - 1) / kWavesPerSweepBlock;
     double* dc = h->p.as<double>();
     double* dp = dc + 6 * h->C;
-    const PcgCtrl* ctrl2 = h->ctrl.as<PcgCtrl>();
+    const PcgCtrl* ctrl2 = planes ? (const PcgCtrl*)nullptr : h->ctrl.as<PcgCtrl>();
+    const double* step_planes = planes ? planes : (const double*)h->vecs.as<double>();
     const Recompute rc{h->tab, h->x + 6 * h->C, h->K};
     // dc from the device-selected vector set: read from the LDS copy of the sets (`in_lds`), or transposed first
     auto run = [&](auto kern, size_t lds, bool in_lds) -> int {
         if (!in_lds) {
             hipLaunchKernelGGL(k_transpose, dim3((6 * h->C + 255) / 256), dim3(256), 0, h->stream,
-                               (const double*)h->vecs.as<double>(), 6, (int)h->C, dc, ctrl2, h->pcg_L);
+                               step_planes, 6, (int)h->C, dc, ctrl2, h->pcg_L);
             LAUNCHED(h);
         }
         CHK(set_lds(h, kern, lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, h->ranges.as<int2>(), h->n_ranges, obs_arrays(h),
-                           h->vecs.as<double>(), dc, vinv_ptr(h), h->gp.as<double>(), h->t1.as<double>(), dp, h->partB(),
+                           step_planes, dc, vinv_ptr(h), h->gp.as<double>(), h->t1.as<double>(), dp, h->partB(),
                            (int)h->C, in_lds ? ctrl2 : (const PcgCtrl*)nullptr, in_lds ? h->pcg_L : 0, h->g_cur, h->si_cur, h->sg_cur, rc,
-                           in_lds && h->pcg_a_owed ? FinalUpdate{h->pcg_part.as<double>(), h->vecs.as<double>(), h->ctrl.as<PcgCtrl>(), h->pcg_L - 1}
+                           in_lds && h->pcg_a_owed && !planes ? FinalUpdate{h->pcg_part.as<double>(), h->vecs.as<double>(), h->ctrl.as<PcgCtrl>(), h->pcg_L - 1}
                                                    : FinalUpdate{});
         LAUNCHED(h);
         return 0;
     };
+    if (h->forms.rc_cons) {
+        const size_t lds = sizeof(double) * kRcRow * (size_t)h->C;
+        CHK(set_lds(h, k_backsub_rc, lds));
+        hipLaunchKernelGGL(k_backsub_rc, dim3(grid), dim3(kSweepThreads), lds, h->stream, (const int2*)h->ranges.as<int2>(), h->n_ranges,
+                           (const int*)h->cam_idx.as<int>(), (const int*)h->pt_idx.as<int>(), (const int*)h->pt_ptr.as<int>(),
+                           rc.camtab, rc.pts, h->K, step_planes, dc, (const double*)vinv_ptr(h),
+                           (const double*)h->gp.as<double>(), (const double*)h->t1.as<double>(), dp, h->partB(), (int)h->C, ctrl2, h->pcg_L,
+                           (const double*)h->g_cur, (const double*)h->si_cur, (const double*)h->sg_cur,
+                           h->pcg_a_owed && !planes ? FinalUpdate{h->pcg_part.as<double>(), h->vecs.as<double>(), h->ctrl.as<PcgCtrl>(), h->pcg_L - 1}
+                                                    : FinalUpdate{});
+        LAUNCHED(h);
+    } else
     CHK(h->forms.jfree ? run(k_backsub<false, true>, sizeof(double) * kCamRow * (size_t)h->C, false)
         : h->forms.lds_vec ? run(k_backsub<true>, sizeof(double) * 6 * (size_t)h->C, true) : run(k_backsub<false>, 0, false));
     *nparts = grid;
@@ -1592,6 +1621,20 @@ int sfmba_debug_option(sfmba_handle* h, const char* name, int64_t value) {
     for (const auto& o : kDebugOptions)
         if (strcmp(name, o.name) == 0) { h->dbg.*o.member = (int)value; return 0; }
     return fail(h, -1, "unknown debug option '%s'", name);
+}
+
+int sfmba_get_form(sfmba_handle* h, const char* name, int32_t* value) {
+    CHK(enter(h));
+    if (!name || !value) return fail(h, -1, "NULL argument");
+    if (!h->have_problem) return fail(h, -1, "no problem set");
+    const Forms& f = h->forms;
+    const struct { const char* name; int value; } forms[] = {
+        {"lds_tab", f.lds_tab}, {"lds_vec", f.lds_vec}, {"sweep_rc", f.sweep_rc}, {"sweep_rc_g", f.sweep_rc_g},
+        {"pcg_fused", f.pcg_fused}, {"mixed", f.mixed}, {"jfree", f.jfree}, {"rc_cons", f.rc_cons}, {"dense", f.dense},
+    };
+    for (const auto& e : forms)
+        if (strcmp(name, e.name) == 0) { *value = e.value; return 0; }
+    return fail(h, -1, "unknown form '%s'", name);
 }
 
 int sfmba_set_precision(sfmba_handle* h, int32_t storage_bits) {
@@ -2532,6 +2575,48 @@ int sfmba_schur_matvec(sfmba_handle* h, const double* x, const double* dc, const
     return 0;
 }
 
+int sfmba_step_products(sfmba_handle* h, const double* x, const double* sg, const double* dc, const double* dp_diag,
+                        double* t1_out, double* g11_out, double* dp_out, double* sums_out, double* g_out, double* si_out) {
+    CHK(enter(h));
+    CHK(begin_compute(h, x));
+    if (!sg || !dc || !dp_diag || !t1_out || !g11_out || !dp_out || !sums_out) return fail(h, -1, "NULL argument");
+    if (h->f32) return fail(h, -1, "sfmba_step_products returns t1 as stored: 64-bit storage only");
+    if (!h->forms.one_rank) return fail(h, -1, "sfmba_step_products is a single-rank entry");
+    const int64_t C = h->C, P = h->P, N = h->N;
+    CHK(linearise_at(h, x));
+    CHK(launch_update_scale(h, 1));                             // s, g of the point (and D^2 g, replaced by the caller's below)
+    std::vector<double> planes(6 * C);
+    for (int64_t c = 0; c < C; ++c)
+        for (int k = 0; k < 6; ++k) planes[k * C + c] = dc[6 * c + k];
+    HIPCHK(h, hipMemcpyAsync(h->sg_cur, sg, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->e.p, dp_diag, sizeof(double) * 3 * P, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->vtmp.p, planes.data(), sizeof(double) * 6 * C, hipMemcpyHostToDevice, h->stream));
+    CHK(launch_point_prep(h, nullptr, h->e.as<double>(), 0.0, nullptr, nullptr, nullptr));
+    int np1 = 0, np2 = 0;
+    CHK(launch_jdot(h, &np1));
+    std::vector<double> part1((size_t)np1), t1((size_t)2 * N);
+    HIPCHK(h, hipMemcpyAsync(part1.data(), h->partB(), sizeof(double) * np1, hipMemcpyDeviceToHost, h->stream));
+    CHK(launch_backsub(h, &np2, h->vtmp.as<double>()));
+    std::vector<double> part2((size_t)np2 * kBacksubCols);
+    HIPCHK(h, hipMemcpyAsync(part2.data(), h->partB(), sizeof(double) * part2.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(t1.data(), h->t1.p, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dp_out, h->p.as<double>() + 6 * C, sizeof(double) * 3 * P, hipMemcpyDeviceToHost, h->stream));
+    if (g_out) HIPCHK(h, hipMemcpyAsync(g_out, h->g_cur, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    if (si_out) HIPCHK(h, hipMemcpyAsync(si_out, h->si_cur, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int64_t k = 0; k < N; ++k) {
+        const int64_t d = h->permuted ? h->order[k] : k;
+        t1_out[2 * d] = t1[2 * k]; t1_out[2 * d + 1] = t1[2 * k + 1];
+    }
+    *g11_out = 0.0;                                             // the partial rows in the order the device sums them
+    for (int b = 0; b < np1; ++b) *g11_out += part1[b];
+    for (int k = 0; k < kBacksubCols; ++k) {
+        sums_out[k] = 0.0;
+        for (int b = 0; b < np2; ++b) sums_out[k] += part2[(size_t)b * kBacksubCols + k];
+    }
+    return 0;
+}
+
 int sfmba_dense_schur(sfmba_handle* h, const double* x, const double* dc, const double* dp, const double* rhs,
                       double* S_out, double* sol_out) {
     CHK(enter(h));
@@ -2596,6 +2681,7 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
                            (const double*)h->g_cur, (int)h->C, 6, h->vtmp.as<double>(), (const PcgCtrl*)nullptr, 0);
         HIPCHK(h, hipMemcpyAsync(h->vcm.p, h->g_cur, sizeof(double) * 6 * h->C, hipMemcpyDeviceToDevice, h->stream));
         CHK(schur_product_standalone(h, h->vtmp.as<double>()));          // leaves a valid z for case 5
+        if (which == 12) CHK(launch_jdot(h, &np));
     }
     struct EventPair {                    // destroyed on every exit path
         hipEvent_t a = nullptr, b = nullptr;
@@ -2623,6 +2709,8 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
                                    h->forms.use_rhsrec ? (const double*)h->rhsrec.as<double>() : (const double*)nullptr, CamExchange{});
                 LAUNCHED(h);
                 break;
+            case 11: CHK(launch_jdot(h, &np)); break;                                   // the selected form (rc_consumers)
+            case 12: CHK(launch_backsub(h, &np, h->vtmp.as<double>())); break;         // after one k_jdot (below): t1 is valid
             case 10:   // streaming-store ceiling: fill the Jacobian planes, 16 B per lane, one stream
                 hipLaunchKernelGGL(k_fill16, dim3(h->n_cu * 2), dim3(1024), 0, h->stream, h->J.as<double>(),
                                    (int64_t)((h->f32 ? 3 : 6) * h->ld), 1.0);

@@ -20,7 +20,7 @@ SYMBOLS = (
     "sfmba_normal_blocks", "sfmba_schur_matvec", "sfmba_comm_get_unique_id", "sfmba_comm_init",
     "sfmba_comm_destroy", "sfmba_set_precision", "sfmba_p2p_export", "sfmba_p2p_attach", "sfmba_p2p_detach",
     "sfmba_p2p_calls", "sfmba_tr2d_solve", "sfmba_debug_option", "sfmba_set_print", "sfmba_get_counters", "sfmba_problem_reuse", "sfmba_dense_schur",
-    "sfmba_get_pcg_history", "sfmba_set_fixed_cameras",
+    "sfmba_get_pcg_history", "sfmba_set_fixed_cameras", "sfmba_step_products", "sfmba_get_form",
 )
 
 
@@ -112,6 +112,11 @@ def load():
     lib.sfmba_schur_matvec.argtypes = [P, P, P, P, P, P]
     lib.sfmba_dense_schur.argtypes = [P, P, P, P, P, P, P]
     lib.sfmba_dense_schur.restype = C.c_int
+    if hasattr(lib, "sfmba_step_products"):     # (an older build given through SFMBA_LIB for an A/B run has neither)
+        lib.sfmba_step_products.argtypes = [P] * 11
+        lib.sfmba_step_products.restype = C.c_int
+        lib.sfmba_get_form.argtypes = [P, C.c_char_p, C.POINTER(C.c_int32)]
+        lib.sfmba_get_form.restype = C.c_int
     lib.sfmba_tr2d_solve.argtypes = [P, P, C.c_double, P]
     lib.sfmba_comm_get_unique_id.argtypes = [P]
     lib.sfmba_comm_init.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int64]

@@ -213,6 +213,12 @@ class Backend:
         self._lib.sfmba_get_counters(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
+    def form(self, name: str) -> int:
+        """Whether the current problem runs the named kernel form (include/sfmba.h: sfmba_get_form)."""
+        v = C.c_int32()
+        self._check(self._lib.sfmba_get_form(self._h, name.encode(), C.byref(v)))
+        return int(v.value)
+
     def pcg_history(self):
         """PCG iterations of every outer iteration of the last solve on this handle."""
         n = int(self._lib.sfmba_get_pcg_history(self._h, None, 0))        # (returns the count, writes min(count, cap))
@@ -262,6 +268,24 @@ class Backend:
         self._check(self._lib.sfmba_schur_matvec(self._h, _capi.ptr(x), _capi.ptr(dc), _capi.ptr(dp),
                                                  _capi.ptr(v), _capi.ptr(y)))
         return y
+
+    def step_products(self, x, sg, dc, dp_diag):
+        """k_jdot and k_backsub in the selected form (include/sfmba.h: sfmba_step_products)
+        -> dict(t1 (N, 2), g11, dp (P, 3), sums (10), g, si)."""
+        self._flush_pending()
+        x = _f64(x, (self.n_params,), "x")
+        sg = _f64(sg, (self.n_params,), "sg")
+        dc, dp_diag = _f64(dc).reshape(-1), _f64(dp_diag).reshape(-1)
+        if dc.shape[0] != 6 * self.n_cameras or dp_diag.shape[0] != self.n_params - 6 * self.n_cameras:
+            raise ValueError("dc must hold 6 C and dp_diag 3 P entries")
+        t1 = np.empty((self.n_obs, 2))
+        g11 = C.c_double()
+        dp = np.empty((dp_diag.shape[0] // 3, 3))
+        sums, g, si = np.empty(10), np.empty(self.n_params), np.empty(self.n_params)
+        self._check(self._lib.sfmba_step_products(self._h, _capi.ptr(x), _capi.ptr(sg), _capi.ptr(dc), _capi.ptr(dp_diag),
+                                                  _capi.ptr(t1), C.byref(g11), _capi.ptr(dp), _capi.ptr(sums), _capi.ptr(g),
+                                                  _capi.ptr(si)))
+        return {"t1": t1, "g11": g11.value, "dp": dp, "sums": sums, "g": g, "si": si}
 
     def dense_schur(self, x, dc, dp, rhs):
         """(S, y): the formed reduced camera matrix and the solution of S y = rhs by the in-LDS PCG run to the end."""

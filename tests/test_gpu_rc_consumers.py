@@ -1,0 +1,405 @@
+"""k_jdot and k_backsub in row form (debug option rc_consumers; DESIGN.md sections 5 and 12): the two products with the whole
+Jacobian taken from pass A's LDS camera rows R | T | a' | u_T and the point instead of from the stored blocks.
+The forms table takes the row form from 65536 observations on; the problems here are smaller (tests stay quick), so
+they ask for it with rc_consumers = 1 -- "wherever it is legal" -- and check through the form query that it ran.
+Entry by entry against extended-precision numpy (both forms), whole solves against the stored-Jacobian form and the
+oracle, the FinalUpdate hand-over of replayed records, and the sharded forms on a world of one."""
+import math
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+LD = np.longdouble
+EPS = float(np.finfo(np.float64).eps)
+
+
+@pytest.fixture(scope="module")
+def orc():
+    from oracle import ba_oracle
+    return ba_oracle
+
+
+# ---- 1. entries against extended precision ---------------------------------------------------------------------------
+# Roundings on the longest path of an entry, counted from ba_kernels.hpp with every multiplication and addition as one
+# rounding (the compiler contracts some pairs into FMAs: fewer, never more).  The camera table R | T | w b c and the
+# fetched residuals are inputs of both forms, of K1 and of the reference alike and are not counted.
+#   row form (rc_row_products):  v = X - T 1;  q = R v 3;  p = K q 3;  iz 1;  pk 1;  b = (K - pk K) iz 3;  j = b R 3:  15 for j;
+#       a' (rc_put_au): w x u 2, w x (w x u) 2, u - b c + cc d 3, g = v x a' + u_T 3: 10 < 15;  t = -(j . g) 3:  18 for t
+#       t1 = t + j . w_p:  19
+#   stored form (k_jdot / k_backsub):  t = jc . u, six terms added to 0: 7;  t1 = nine terms: 10
+#   y_p = sum of jp^T t: 2 more, then the sum over the run: seg_reduce_serial 7 steps, or (run longer than the window)
+#       ceil(L / 64) serial additions and the 6 steps of wave_sum
+#   dp = Vinv (-g_p - y): 1 + 3, Vinv by chol3_inverse: 15 on its longest path (inv[0]), on V + diag (1), V and g_p summed
+#       over the run by K1 (products 1, the same run sums)
+#   t2 = t + jp . dp: 4 more than the later of t and dp
+#   sums: products 2, then one addition per window of the lane's range, 6 (wave_sum), 16 (waves of the workgroup), and the
+#       workgroups' partial rows
+# k is TWICE the count: the reference is formed from the fetched blocks, which carry K1's roundings of the same paths.
+T_ROUNDINGS = {0: 7, 1: 18}
+T1_ROUNDINGS = {0: 10, 1: 19}
+CHOL_ROUNDINGS = 15
+
+
+def _run_roundings(L):
+    return np.maximum(7, np.ceil(L / 64.0) + 6)
+
+
+def _cross_abs(a, b):
+    """|a x b| evaluated with absolute values: what bounds the rounding error of the cross product."""
+    return np.stack([a[:, 1] * b[:, 2] + a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] + a[:, 0] * b[:, 2],
+                     a[:, 0] * b[:, 1] + a[:, 1] * b[:, 0]], axis=1)
+
+
+def _row_form_abs(pb, x, u):
+    """The row form's expressions for j (N, 2, 3) and t = Jc u (N, 2) evaluated with every operand replaced by its absolute
+    value (and 1 / p_z by |1 / p_z| (sum |terms of p_z|) / |p_z|): gamma_n times this bounds the rounding error of n roundings."""
+    C, ci, pi = pb.n_cameras, np.asarray(pb.camera_indices), np.asarray(pb.point_indices)
+    K = np.abs(np.asarray(pb.K, dtype=LD))
+    cam, X = x[:6 * C].reshape(C, 6).astype(LD), x[6 * C:].reshape(-1, 3).astype(LD)
+    w, T = cam[:, :3], cam[:, 3:]
+    th2 = np.einsum("ci,ci->c", w, w)
+    th = np.sqrt(th2)
+    small = th < 1e-6
+    ths = np.where(small, 1.0, th)
+    a = np.where(small, 1.0, np.sin(ths) / ths)
+    b = np.where(small, 0.5, (1 - np.cos(ths)) / ths ** 2)
+    cc = np.where(small, 1.0 / 6, (ths - np.sin(ths)) / ths ** 3)
+    W = np.zeros((C, 3, 3), dtype=LD)
+    W[:, 0, 1], W[:, 0, 2], W[:, 1, 0], W[:, 1, 2], W[:, 2, 0], W[:, 2, 1] = -w[:, 2], w[:, 1], w[:, 2], -w[:, 0], -w[:, 1], w[:, 0]
+    R = np.eye(3, dtype=LD)[None] + a[:, None, None] * W + b[:, None, None] * np.einsum("cij,cjk->cik", W, W)
+    Ra = np.abs(R)[ci]
+    v, va = X[pi] - T[ci], np.abs(X[pi]) + np.abs(T[ci])
+    pz = np.einsum("nij,nj->ni", R[ci], v) @ np.asarray(pb.K, dtype=LD).T[:, 2]
+    pa = np.einsum("nij,nj->ni", Ra, va) @ K.T
+    iza = pa[:, 2] / pz ** 2
+    ja = np.empty((len(ci), 2, 3), dtype=LD)
+    for k in range(2):
+        pka = pa[:, k] * iza
+        ba = (K[k][None, :] + pka[:, None] * K[2][None, :]) * iza[:, None]
+        ja[:, k, :] = np.einsum("nm,nmi->ni", ba, Ra)
+    uw, uT, wa = np.abs(u[:, :3].astype(LD)), np.abs(u[:, 3:].astype(LD)), np.abs(w)
+    ca = _cross_abs(wa, uw)
+    aa = uw + np.abs(b)[:, None] * ca + np.abs(cc)[:, None] * _cross_abs(wa, ca)
+    ga = _cross_abs(va, aa[ci]) + uT[ci]
+    return ja, np.einsum("nki,ni->nk", ja, ga)
+
+
+def _inv3(A):
+    """(P, 3, 3) symmetric -> inverses, by cofactors in the arrays' own precision (numpy.linalg has no longdouble)."""
+    c = np.empty_like(A)
+    for i in range(3):
+        for j in range(3):
+            r, s = [k for k in range(3) if k != i], [k for k in range(3) if k != j]
+            c[:, j, i] = (-1) ** (i + j) * (A[:, r[0], s[0]] * A[:, r[1], s[1]] - A[:, r[0], s[1]] * A[:, r[1], s[0]])
+    det = np.einsum("pi,pi->p", A[:, 0, :], c[:, :, 0])
+    return c / det[:, None, None]
+
+
+class _Case:
+    """Reference values of sfmba_step_products in longdouble from the fetched blocks, and what bounds the entries' errors."""
+
+    def __init__(self, be, pb, seed=0):
+        C, P, N = pb.n_cameras, pb.n_points, len(pb.camera_indices)
+        ci, pi = np.asarray(pb.camera_indices), np.asarray(pb.point_indices)
+        rng = np.random.default_rng(seed)
+        self.pb, self.C, self.P, self.N, self.ci, self.pi = pb, C, P, N, ci, pi
+        self.sg = rng.normal(size=6 * C + 3 * P)
+        self.dc = 1e-2 * rng.normal(size=6 * C)
+        r, Jc, Jp = be.residual_jacobian(pb.x0)
+        r, Jc, Jp = r.reshape(N, 2).astype(LD), Jc.astype(LD), Jp.astype(LD)
+        V = np.zeros((P, 3, 3), dtype=LD)
+        np.add.at(V, pi, np.einsum("nki,nkj->nij", Jp, Jp))
+        # a diagonal of the size of V's own: V + diag is well conditioned, also for a point with one observation (V singular)
+        self.diag = np.asarray(np.einsum("pii->pi", V) + 1.0, dtype=np.float64).ravel() * rng.uniform(0.5, 2.0, size=3 * P)
+        self.L = np.bincount(pi, minlength=P)
+        self.seen = self.L > 0
+        sgc, sgp, dc = self.sg[:6 * C].reshape(C, 6).astype(LD), self.sg[6 * C:].reshape(P, 3).astype(LD), self.dc.reshape(C, 6).astype(LD)
+        aJc, aJp = np.abs(Jc), np.abs(Jp)
+        self.t1 = np.einsum("nki,ni->nk", Jc, sgc[ci]) + np.einsum("nki,ni->nk", Jp, sgp[pi])
+        t = np.einsum("nki,ni->nk", Jc, dc[ci])
+        ja1, ta1 = _row_form_abs(pb, pb.x0, sgc)
+        ja2, ta2 = _row_form_abs(pb, pb.x0, dc)
+        # sum |terms| of t1 and of t = Jc dc, per form
+        self.S_t1 = {0: np.einsum("nki,ni->nk", aJc, np.abs(sgc[ci])) + np.einsum("nki,ni->nk", aJp, np.abs(sgp[pi])),
+                     1: ta1 + np.einsum("nki,ni->nk", ja1, np.abs(sgp[pi]))}
+        S_t = {0: np.einsum("nki,ni->nk", aJc, np.abs(dc[ci])), 1: ta2}
+        aj = {0: aJp, 1: ja2}
+        gp, y = np.zeros((P, 3), dtype=LD), np.zeros((P, 3), dtype=LD)
+        np.add.at(gp, pi, np.einsum("nki,nk->ni", Jp, r))
+        np.add.at(y, pi, np.einsum("nki,nk->ni", Jp, t))
+        A = V + np.einsum("pi,ij->pij", self.diag.reshape(P, 3).astype(LD), np.eye(3, dtype=LD))
+        Ainv = _inv3(A)
+        self.dp = np.einsum("pij,pj->pi", Ainv, -gp - y)
+        aInv = np.abs(Ainv)
+        ga, aA = np.zeros((P, 3), dtype=LD), np.abs(A)
+        np.add.at(ga, pi, np.einsum("nki,nk->ni", aJp, np.abs(r)))
+        s_run = _run_roundings(self.L)
+        self.k_t1, self.B_t1, self.S_dp, self.k_dp, self.B_dp, self.B_t2 = {}, {}, {}, {}, {}, {}
+        self.t2 = t + np.einsum("nki,ni->nk", Jp, self.dp[pi])
+        for form in (0, 1):
+            self.k_t1[form] = 2 * T1_ROUNDINGS[form]
+            self.B_t1[form] = self.k_t1[form] * EPS * self.S_t1[form]
+            ya = np.zeros((P, 3), dtype=LD)
+            np.add.at(ya, pi, np.einsum("nki,nk->ni", aj[form], S_t[form]))
+            # sum |terms| of dp: |Vinv| (sum |jp r| + sum |jp t|), and the inverse's own error |Vinv| |V + diag| |Vinv| |b|
+            self.S_dp[form] = np.einsum("pij,pj->pi", aInv, ga + ya) + \
+                np.einsum("pij,pjk,pkl,pl->pi", aInv, aA, aInv, np.abs(gp) + np.abs(y))
+            self.k_dp[form] = 2 * (T_ROUNDINGS[form] + 2 + s_run + 4 + CHOL_ROUNDINGS + 2 + s_run)
+            self.B_dp[form] = self.k_dp[form][:, None] * EPS * self.S_dp[form]
+            self.B_t2[form] = 2 * (T_ROUNDINGS[form] + 4) * EPS * (S_t[form] + np.einsum("nki,ni->nk", aj[form], np.abs(self.dp[pi]))) + \
+                np.einsum("nki,ni->nk", aj[form], self.B_dp[form][pi])
+
+    def sums(self, out, form):
+        """-> (reference of g11 and the ten sums, their bounds) with the gradient and the scale the device formed them with."""
+        C, P, N = self.C, self.P, self.N
+        g, si = out["g"].astype(LD), out["si"].astype(LD)
+        gpt, spt = g[6 * C:].reshape(P, 3)[self.seen], si[6 * C:].reshape(P, 3)[self.seen]
+        dp, Bdp = self.dp[self.seen], self.B_dp[form][self.seen]
+        dc, gc, sc, sgc = self.dc.astype(LD), g[:6 * C], si[:6 * C], self.sg[:6 * C].astype(LD)
+        # additions on the way of a sum: one per window of a lane's range (ranges are cut at max(64, N / 4096) observations,
+        # a window completes at least one run), the run trips of the longest point, 6 + 16 in the workgroup, <= 256 partial rows
+        n_add = 2 + max(64, math.ceil(N / 4096)) + math.ceil(self.L.max() / 64) + 6 + 16 + min(256, math.ceil(N / 1024))
+        t1, t2, B1, B2 = self.t1, self.t2, self.B_t1[form], self.B_t2[form]
+        ref = [np.sum(t1 * t1), np.sum(t1 * t2), np.sum(t2 * t2),
+               np.sum(gpt * dp), np.sum((dp * spt) ** 2), np.sum(gpt / spt ** 2 * dp), np.sum(dp * dp),
+               np.sum(gc * dc), np.sum((dc * sc) ** 2), np.sum(sgc * dc), np.sum(dc * dc)]
+        e = 2 * n_add * EPS
+        bound = [np.sum((2 * np.abs(t1) + B1) * B1) + e * np.sum(t1 * t1),
+                 np.sum(B1 * np.abs(t2) + np.abs(t1) * B2 + B1 * B2) + e * np.sum(np.abs(t1 * t2)),
+                 np.sum((2 * np.abs(t2) + B2) * B2) + e * np.sum(t2 * t2),
+                 np.sum(np.abs(gpt) * Bdp) + e * np.sum(np.abs(gpt * dp)),
+                 np.sum(spt ** 2 * (2 * np.abs(dp) + Bdp) * Bdp) + (e + 4 * EPS) * np.sum((dp * spt) ** 2),
+                 np.sum(np.abs(gpt) / spt ** 2 * Bdp) + (e + 6 * EPS) * np.sum(np.abs(gpt / spt ** 2 * dp)),
+                 np.sum((2 * np.abs(dp) + Bdp) * Bdp) + e * np.sum(dp * dp),
+                 e * np.sum(np.abs(gc * dc)), (e + 4 * EPS) * np.sum((dc * sc) ** 2), e * np.sum(np.abs(sgc * dc)), e * np.sum(dc * dc)]
+        return np.array(ref, dtype=LD), np.array(bound, dtype=LD)
+
+
+def _check_entries(be, pb, form, case, tag):
+    out = be.step_products(pb.x0, case.sg, case.dc, case.diag)
+    seen = case.seen                                 # (an unobserved point has no run: nothing produces its dp)
+    err_t1 = np.abs(out["t1"].astype(LD) - case.t1)
+    err_dp = np.abs(out["dp"].astype(LD) - case.dp)[seen]
+    ref, bound = case.sums(out, form)
+    got = np.concatenate([[out["g11"]], out["sums"]]).astype(LD)
+    err_s = np.abs(got - ref)
+    print(f"{tag} form {form}: t1 err/bound {float((err_t1 / case.B_t1[form]).max()):.3f} (k = {case.k_t1[form]}), "
+          f"dp {float((err_dp / case.B_dp[form][seen]).max()):.3f} (k = {int(case.k_dp[form].min())}..{int(case.k_dp[form].max())}), "
+          f"sums {np.array2string(np.asarray(err_s / bound, dtype=np.float64), precision=3)}")
+    assert np.all(np.isfinite(out["t1"])) and np.all(np.isfinite(out["dp"][seen])) and np.all(np.isfinite(got.astype(np.float64)))
+    assert np.all(err_t1 <= case.B_t1[form]), tag
+    assert np.all(err_dp <= case.B_dp[form][seen]), tag
+    assert np.all(err_s <= bound), (tag, err_s / bound)
+    # the bounds mean something: they sit nine digits below all but a hundredth of the entries (and all of the sums)
+    assert np.mean(case.B_t1[form] < 1e-9 * np.abs(case.t1)) >= 0.99, tag
+    assert np.mean(case.B_dp[form][seen] < 1e-9 * np.abs(case.dp[seen])) >= 0.99, tag
+    assert np.all(bound < 1e-9 * np.abs(ref)), tag
+    return out
+
+
+def _both_forms(pb, tag, fixed=(), expect_row_form=1):
+    import sfmba
+    outs, case = {}, None
+    for rc in (0, 1):
+        be = sfmba.Backend(0)
+        try:
+            be.debug_option("dense", 0)
+            be.debug_option("rc_consumers", rc)
+            be.set_fixed_cameras(fixed)
+            be.set_problem(*pb.args)
+            assert be.form("rc_cons") == (expect_row_form if rc else 0), tag
+            case = case or _Case(be, pb)
+            outs[rc] = _check_entries(be, pb, be.form("rc_cons"), case, tag)
+        finally:
+            be.close()
+    return outs
+
+
+def _hand_built(orc):
+    """8 cameras, 40 points: 21 points of 3 observations (0..62), a run of 5 that starts on lane 63 of the first window, a
+    point with 200 observations (more than a window: the long-run path), 8 points with one observation, 9 with four."""
+    import sfmba
+    from sfmba.synthetic import BAProblem
+    base = sfmba.make_problem(8, 40, 400, seed=4)
+    counts = [3] * 21 + [5] + [200] + [1] * 8 + [4] * 9
+    pi = np.repeat(np.arange(40), counts)
+    ci = (np.arange(len(pi)) * 3 + pi) % 8
+    args = (8, 40, ci, pi, np.zeros((len(pi), 2)), base.K)
+    rng = np.random.default_rng(7)
+    uv = orc.compute_residuals(base.x_true, *args).reshape(-1, 2) + rng.normal(0.0, 0.5, (len(pi), 2))
+    return BAProblem(8, 40, ci, pi, uv, base.K, base.x0, base.x_true)
+
+
+CASES = ("tiny", "medium", "hand_built", "gaps", "held_camera")
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_entries_against_extended_precision(orc, name):
+    """t1, sum |t1|^2, dp and the ten sums of sfmba_step_products, stored-Jacobian form and row form, entry by entry within
+    k eps sum |terms| of the longdouble value (k and the terms: the comment at the top of this file)."""
+    import sfmba
+    if name == "tiny":
+        pb, fixed = sfmba.make_problem(6, 80, 500, seed=5), ()
+    elif name == "medium":
+        pb, fixed = sfmba.make_problem(60, 900, 9000, seed=12), ()
+    elif name == "hand_built":
+        pb, fixed = _hand_built(orc), ()
+        L = np.bincount(pb.point_indices, minlength=40)
+        assert L.max() == 200 and np.sum(L == 1) >= 3 and np.cumsum(L)[20] == 63 and L[21] > 1
+    elif name == "gaps":
+        pb, fixed = sfmba.drop_observations(sfmba.make_problem(6, 80, 500, seed=5), cameras=(3,), points=(7,)), ()
+    else:
+        pb, fixed = sfmba.make_problem(6, 80, 500, seed=5), (2,)
+    _both_forms(pb, name, fixed=fixed)
+
+
+def test_forms_table_at_its_size_and_storage_switches():
+    """The default (rc_consumers = -1): the row form from 65536 observations on, not below; never with fp32 storage; and
+    rc_consumers = 0 / 1 override the size, not the legality."""
+    import sfmba
+    be = sfmba.Backend(0)
+    try:
+        for n_obs, bits, rc, want in ((65535, 64, -1, 0), (65536, 64, -1, 1), (65536, 32, -1, 0), (65536, 32, 1, 0),
+                                      (65536, 64, 0, 0), (65535, 64, 1, 1)):
+            pb = sfmba.make_problem(40, 8000, n_obs, seed=2)
+            be.set_precision(bits)
+            be.debug_option("rc_consumers", rc)
+            be.set_problem(*pb.args)
+            assert be.form("rc_cons") == want, (n_obs, bits, rc)
+    finally:
+        be.close()
+
+
+def test_largest_camera_count_of_the_row_form_and_the_first_above(orc):
+    """1100 cameras is what pass A's LDS table takes (kRcMaxCams): the row form runs there; at 1101 the table decides for the
+    stored-Jacobian readers, whatever rc_consumers asks for, and the default equals rc_consumers = 0 to the bit."""
+    import sfmba
+    _both_forms(sfmba.make_problem(1100, 1500, 12000, seed=8), "1100 cameras")
+    pb = sfmba.make_problem(1101, 1500, 12000, seed=8)
+    rng = np.random.default_rng(3)
+    sg, dc, diag = rng.normal(size=pb.x0.shape[0]), 1e-2 * rng.normal(size=6 * 1101), rng.uniform(1.0, 2.0, size=3 * 1500)
+    outs = {}
+    for rc in (-1, 0, 1):
+        be = sfmba.Backend(0)
+        try:
+            be.debug_option("rc_consumers", rc)
+            be.set_problem(*pb.args)
+            assert be.form("rc_cons") == 0 and be.form("sweep_rc") == 0
+            outs[rc] = be.step_products(pb.x0, sg, dc, diag)
+        finally:
+            be.close()
+    for rc in (-1, 1):
+        assert all(np.array_equal(outs[rc][k], outs[0][k]) for k in ("t1", "dp", "sums")) and outs[rc]["g11"] == outs[0]["g11"]
+
+
+# ---- 2. whole solves ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", range(4))
+def test_whole_solves_row_form_against_stored_jacobian_form(orc, which):
+    """rc_consumers = 0 against the row form (1: these problems are below the size from which it is the default) on ONE
+    handle, held to the bounds between two forms of one algorithm (test_fused_pcg_launch_equals_sweep_plus_update); the
+    first two problems also against the oracle."""
+    import sfmba
+    pb = (lambda: sfmba.make_config("cfg2"), lambda: sfmba.make_problem(300, 4000, 30000, seed=3),
+          lambda: sfmba.make_problem(6, 80, 500, seed=5, x0_noise=0.2), lambda: sfmba.make_problem(1024, 3000, 20000, seed=8))[which]()
+    be = sfmba.Backend(0)
+    try:
+        be.debug_option("dense", 0)
+        runs = []
+        for rc in (0, 1):
+            be.debug_option("rc_consumers", rc)
+            be.set_problem(*pb.args)
+            assert be.form("rc_cons") == rc
+            opt = be.default_options()
+            opt.ftol = 1e-10
+            x, res, fun, _ = be.solve(pb.x0, opt)
+            runs.append((x, res, fun, be.pcg_history()))
+    finally:
+        be.close()
+    (xa, a, fa, _), (xb, b, fb, _) = runs
+    print(f"problem {which}: cost {a.cost!r} / {b.cost!r}, max |dx| {np.abs(xa - xb).max():.3e}, max |dfun| {np.abs(fa - fb).max():.3e}")
+    assert (a.nfev, a.pcg_iterations) == (b.nfev, b.pcg_iterations)
+    assert abs(a.njev - b.njev) <= 1 and {a.status, b.status} <= {2, 3, 4}
+    assert abs(a.cost - b.cost) <= 1e-12 * a.cost
+    assert np.abs(xa - xb).max() <= 1e-6 * np.abs(xa).max()
+    assert np.abs(fa - fb).max() <= 1e-6
+    if which < 2:
+        from test_gpu_parity import _oracle_kwargs
+        o = orc.trf_schur(pb.x0, *pb.args, ftol=1e-10, **_oracle_kwargs(False))
+        assert (b.status, b.nfev, b.njev) == (o.status, o.nfev, o.njev)
+        assert abs(b.cost - o.cost) <= 1e-9 * o.cost
+
+
+# ---- 3. the FinalUpdate hand-over --------------------------------------------------------------------------------------
+def test_final_update_in_the_row_form_prologue():
+    """Back-to-back solves on one handle replay the PCG record, and the launch of pass A that would only find the solve
+    finished is left to k_backsub_rc's prologue (pcg_skip_last at its default); with pcg_skip_last = 0 every launch is
+    enqueued.  Exact replays, a record made too short by a tighter pcg_tol and one that is too long: x, nfev, cost and
+    the PCG history are those of a fresh handle, to the bit."""
+    import sfmba
+    pb = sfmba.make_problem(60, 900, 9000, seed=12)
+    hist = {}
+    for tol in (1e-2, 1e-5):
+        fresh = sfmba.Backend(0)
+        fresh.debug_option("dense", 0)
+        fresh.debug_option("rc_consumers", 1)
+        fresh.set_problem(*pb.args)
+        assert fresh.form("rc_cons") == 1
+        opt = fresh.default_options()
+        opt.ftol = 1e-10
+        opt.pcg_tol = opt.pcg_tol_max = tol
+        x, res, _, _ = fresh.solve(pb.x0, opt)
+        hist[tol] = (x, res.nfev, res.cost, fresh.pcg_history())
+        fresh.close()
+    assert sum(hist[1e-5][3]) > sum(hist[1e-2][3]) + 5
+    be = sfmba.Backend(0)
+    try:
+        be.debug_option("dense", 0)
+        be.debug_option("rc_consumers", 1)
+        be.set_problem(*pb.args)
+        assert be.form("rc_cons") == 1
+        opt = be.default_options()
+        opt.ftol = 1e-10
+        launches = {}
+        for skip in (-1, 0):
+            be.debug_option("pcg_skip_last", skip)
+            for tol in (1e-2, 1e-2, 1e-5, 1e-5, 1e-2):
+                opt.pcg_tol = opt.pcg_tol_max = tol
+                l0 = be.counters()[0]
+                x, res, _, _ = be.solve(pb.x0, opt)
+                launches[skip, tol] = be.counters()[0] - l0        # (the last of each tolerance: an exact or too long replay)
+                assert np.array_equal(x, hist[tol][0]) and (res.nfev, res.cost) == hist[tol][1:3]
+                assert be.pcg_history() == hist[tol][3]
+        # the prologue really stood in for launches: two per outer iteration fewer than with every launch enqueued
+        assert launches[-1, 1e-5] < launches[0, 1e-5]
+    finally:
+        be.close()
+
+
+# ---- 4. the sharded forms on a world of one ------------------------------------------------------------------------------
+def test_world_of_one_sharded_path_with_row_form_consumers():
+    """The sharded forms of the iteration (collectives over the direct link, per-camera exchanges inside the kernels; the
+    non-FinalUpdate prologue of k_backsub_rc on x of the PCG's final set) give the counts of the local form, cost to 1e-9."""
+    import sfmba
+    from test_gpu_fullsize import sharded_world_of_one, solve_sharded
+    pb = sfmba.make_problem(100, 2000, 16000, seed=6)
+
+    def solve(be):
+        assert be.form("rc_cons") == 1
+        opt = be.default_options()
+        opt.ftol = 1e-10
+        x, res, _, _ = be.solve(pb.x0, opt, want_fun=False, want_grad=False)
+        return x, res, be.pcg_history()
+
+    local = sfmba.Backend(0)
+    try:
+        local.debug_option("rc_consumers", 1)
+        local.set_problem(*pb.args)
+        xl, rl, hl = solve(local)
+    finally:
+        local.close()
+    with sharded_world_of_one(pb, debug=(("rc_consumers", 1),)) as handle:
+        (xs, rs, hs), _ = solve_sharded(handle, solve)
+    assert (rs.status, rs.nfev, rs.njev, rs.pcg_iterations) == (rl.status, rl.nfev, rl.njev, rl.pcg_iterations) and hs == hl
+    assert abs(rs.cost - rl.cost) <= 1e-9 * rl.cost
