@@ -203,6 +203,60 @@ int  sfmba_residuals(sfmba_handle* h, const double* x, double* r_out);
 int  sfmba_residual_jacobian(sfmba_handle* h, const double* x, double* r_out, double* Jc_out,
                              double* Jp_out);
 
+/* ---- reprojection statistics and track filtering ----------------------------------------------- */
+/* What the reference evaluates around its BA call in Python loops or not at all: the mean reprojection error it prints
+ * after every fused edge (one calc_reproj_error call per observation, sfm.py:234-241), the depth test behind a camera
+ * (sfm.py:221-223), the angle between the rays to a point (sfm.py:146-157) -- and the masks that turn thresholds on
+ * them into a smaller problem (the reference never drops an observation).  One sweep per observation, one reduction
+ * per point, one per camera, at the parameter vector x (6C+3P) of the current problem.
+ *
+ * Per observation (N, the caller's observation order):
+ *   obs_err    sqrt(rx^2 + ry^2) in pixels, (rx, ry) the residual of sfmba_residuals at the same x, bit for bit
+ *   obs_depth  z of R(w_c) (X_p - T_c), the camera-frame coordinate the projection divides by
+ *   obs_keep   1 iff the observation passes its own test (err <= max_error_px, err finite, depth > min_depth) AND its
+ *              point is kept: the final mask.  "Kept observations" of a POINT below are those that pass their own test.
+ * Per point (P), over its observations in stored (point-major, else caller's) order:
+ *   pt_views          kept observations
+ *   pt_max_err        largest err among them (0 if none)
+ *   pt_sum_err2       sum of err^2 over them
+ *   pt_min_depth      smallest depth over ALL its observations, kept or not (+inf if it has none)
+ *   pt_max_angle_deg  widest angle between the rays X_p - T_a, X_p - T_b over all pairs of kept observations, as
+ *                     atan2(|a x b|, a . b) in degrees; 0 with fewer than two
+ *   pt_keep           1 iff pt_views >= min_views and pt_max_angle_deg >= min_angle_deg
+ * Per camera (C), over its finally kept observations (obs_keep = 1), cameras held still included:
+ *   cam_views, cam_sum_err, cam_max_err;  cam_behind counts ALL its observations with depth <= 0
+ * summary: observations in the problem, finally kept, points kept, observations with depth <= 0; sum of err, sum of
+ *   err^2 and largest err over the finally kept observations.
+ * With the default options (max_error_px = +inf, min_depth = -inf, min_angle_deg = 0, min_views = 0) everything with a
+ * finite err is kept: a pure statistics pass.
+ *
+ * Any output pointer may be NULL; an array that is not asked for is not downloaded, and the per-camera pass and its
+ * camera-major order (built at the first call of a problem that asks, at most 40448 cameras) run only when a per-camera
+ * array is asked for.  opt = NULL: the defaults.  Returns -1 when no problem is set, x is NULL, a threshold is NaN, or
+ * the handle waits for its transport (see sfmba_set_problem).  A non-finite x is no error: the observations it reaches
+ * report a non-finite err and are never kept.  The call works on buffers of its own: fun and grad of the last solve and
+ * the record the next solve starts from are as they were.  Same input, same bits: no atomics; sums run in a fixed order.
+ * On a sharded handle the call describes the LOCAL shard only: its observations and points; per-camera figures and the
+ * summary count this shard's observations (the caller adds or maximises over the ranks). */
+typedef struct sfmba_filter_options {
+    double  max_error_px;  /* an observation is kept when err <= this ...                          */
+    double  min_depth;     /* ... and depth > this                                                 */
+    double  min_angle_deg; /* a point is kept when its widest ray angle is >= this ...             */
+    int32_t min_views;     /* ... and it has at least this many kept observations                  */
+    int32_t reserved;
+} sfmba_filter_options;
+typedef struct sfmba_stats_summary {
+    int64_t n_obs, n_obs_kept, n_points_kept, n_behind;
+    double  sum_err, sum_err2, max_err;
+} sfmba_stats_summary;
+void sfmba_default_filter_options(sfmba_filter_options* opt);
+int  sfmba_reprojection_stats(sfmba_handle* h, const double* x, const sfmba_filter_options* opt,
+                              double* obs_err, double* obs_depth, uint8_t* obs_keep,
+                              int32_t* pt_views, double* pt_max_err, double* pt_sum_err2, double* pt_min_depth,
+                              double* pt_max_angle_deg, uint8_t* pt_keep,
+                              int32_t* cam_views, double* cam_sum_err, double* cam_max_err, int32_t* cam_behind,
+                              sfmba_stats_summary* summary);
+
 /* ---- least_squares(method='trf', x_scale='jac') (sfm.py:266-268) ---------------------------- */
 /* x_inout: x0 on entry, result.x on success (untouched on failure). */
 int  sfmba_solve(sfmba_handle* h, double* x_inout, const sfmba_options* opt, sfmba_result* out);
@@ -219,7 +273,8 @@ int  sfmba_get_fun_grad(sfmba_handle* h, double* fun_out, double* grad_out);
  *        3 one implicit Schur product (pass A + pass B), 4 pass A alone, 5 pass B alone, 6 the reduced
  *        right-hand-side pass, 7 the residual+Jacobian sweep with its point-block sums switched off,
  *        10 a streaming-store fill of the Jacobian buffer (ceiling probe),
- *        11 k_jdot and 12 k_backsub (without its PCG prologue) in the form the problem has selected ("rc_consumers").
+ *        11 k_jdot and 12 k_backsub (without its PCG prologue) in the form the problem has selected ("rc_consumers"),
+ *        13 the per-observation sweep and 14 the per-point reduction of sfmba_reprojection_stats (default options).
  * avg_us: average duration of one repetition. */
 int  sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t reps, double* avg_us);
 /* Normal-equation blocks at x: U (C,21 upper triangle row-major), V (P,6 upper), gc (C,6), gp (P,3). */

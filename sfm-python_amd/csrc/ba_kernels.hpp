@@ -4376,4 +4376,375 @@ __global__ __launch_bounds__(1024) void k_fill16(double* __restrict__ a, int64_t
         *reinterpret_cast<double2*>(a + 2 * e) = make_double2(v, v + 1.0);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Reprojection statistics and track filtering (sfmba_reprojection_stats).  Three sweeps over
+// buffers of their own -- nothing a solver form reads or writes is touched:
+//   k_obs_stats    per observation, point-major: err = |r|, depth = z of R (X - T), keep = the observation's own test
+//   k_point_stats  per point over its run: views, max err, sum err^2, min depth, widest ray angle, the point's verdict,
+//                  and the FINAL mask of its observations (own test and point kept); one row of partial sums per workgroup
+//   k_cam_stats    per camera over a camera-major permutation of ALL observations (cameras held still included,
+//                  which the solver's camera-major lists leave out): kept views, sum and max err, observations behind
+//   k_stats_summary  one workgroup adds the rows of k_point_stats in row order
+// No atomics: a point's sums run over its observations in stored order, a camera's and the summary's are added in a
+// fixed order; maxima, minima and counts do not depend on the order at all.
+// ---------------------------------------------------------------------------------------------
+struct StatsFilter { double max_err, min_depth, min_angle_deg; int min_views; };
+
+// The residual-only sweep (k_resjac<.., false, true, ..>) with other stores: same persistent workgroups, same camera
+// table in LDS (or rows gathered through the wave's slab), same pipeline -- indices two batches ahead, pixel and point
+// one batch ahead, so three observations per lane are in flight -- and the same observe<false>, so rx, ry are the
+// solver's residual bit for bit.  Per observation it reads 4 + 4 + 16 (8 in fp32 storage) bytes and the gathered point,
+// and writes err | depth as one 16-byte store and the mask byte.
+// A non-finite err fails the test whatever the threshold (+inf <= +inf would pass it).
+template <bool LDS_TAB, bool F32>
+__global__ __launch_bounds__(kSweepThreads) void k_obs_stats(
+    const double* __restrict__ camtab, const double* __restrict__ pts, const int* __restrict__ cam_idx,
+    const int* __restrict__ pt_idx, const double* __restrict__ uv, double* __restrict__ ed,
+    unsigned char* __restrict__ keep, int N, int C, KMat K, double max_err, double min_depth) {
+    extern __shared__ __align__(16) double smem[];
+    const int stride = gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    int c0 = 0, p0 = 0, c1 = 0, p1 = 0;
+    double2 uv0 = make_double2(0.0, 0.0);
+    double X0 = 0.0, Y0 = 0.0, Z0 = 0.0;
+    if (i < N) { c0 = cam_idx[i]; p0 = pt_idx[i]; uv0 = load_pair(uv, F32, i); }
+    if (i + stride < N) { c1 = cam_idx[i + stride]; p1 = pt_idx[i + stride]; }
+    if (i < N) { const double* __restrict__ Xp = pts + 3 * (size_t)p0; X0 = Xp[0]; Y0 = Xp[1]; Z0 = Xp[2]; }
+    if (LDS_TAB) {
+        const int n2 = (C * kCamRow) >> 1;
+        const double2* __restrict__ src = reinterpret_cast<const double2*>(camtab);
+        double2* __restrict__ dst = reinterpret_cast<double2*>(smem);
+        for (int k = threadIdx.x; k < n2; k += blockDim.x) dst[k] = src[k];
+        __syncthreads();
+    }
+    double* const slab = smem + (size_t)(threadIdx.x >> 6) * kRowSlabDoubles;
+    if (!LDS_TAB && i - lane < N) rows_request(camtab, c0, lane, slab);
+    while (i - lane < N) {                       // wave-uniform: rows_request shuffles over all 64 lanes
+        const bool on = i < N;
+        const int in = i + stride, in2 = in + stride;
+        double tl[kCamRow];
+        if (!LDS_TAB) rows_wait();
+        {
+            const double2* __restrict__ trow = reinterpret_cast<const double2*>(LDS_TAB ? smem + (size_t)c0 * kCamRow
+                                                                                         : slab + (size_t)lane * kCamRow);
+#pragma unroll
+            for (int k = 0; k < kCamRow / 2; ++k) { const double2 q = trow[k]; tl[2 * k] = q.x; tl[2 * k + 1] = q.y; }
+        }
+        if (!LDS_TAB) {
+            rows_read_done();
+            if (in - lane < N) rows_request(camtab, c1, lane, slab);
+        }
+        int c2 = 0, p2 = 0;
+        double2 uv1 = make_double2(0.0, 0.0);
+        double X1 = 0.0, Y1 = 0.0, Z1 = 0.0;
+        if (in2 < N) { c2 = cam_idx[in2]; p2 = pt_idx[in2]; }
+        if (in < N) {
+            uv1 = load_pair(uv, F32, in);
+            const double* __restrict__ Xp = pts + 3 * (size_t)p1;
+            X1 = Xp[0]; Y1 = Xp[1]; Z1 = Xp[2];
+        }
+        double jc[12], jp[6], rx, ry;
+        observe<false>(tl, X0, Y0, Z0, uv0.x, uv0.y, K, rx, ry, jc, jp);
+        const double depth = tl[6] * (X0 - tl[9]) + tl[7] * (Y0 - tl[10]) + tl[8] * (Z0 - tl[11]);
+        const double err = sqrt(rx * rx + ry * ry);
+        if (on) {
+            st16(ed + 2 * (size_t)i, err, depth);
+            keep[i] = (err <= max_err && err < INFINITY && depth > min_depth) ? 1 : 0;
+        }
+        i = in;
+        c0 = c1; p0 = p1; c1 = c2; p1 = p2;
+        uv0 = uv1; X0 = X1; Y0 = Y1; Z0 = Z1;
+    }
+}
+
+// One lane per point while the run is shorter than kStatsLongTrack: every pair of a run of n costs the lane two
+// dependent gathers (camera index, camera centre) and ~30 flops, n (n - 1) / 2 times, and the other 63 lanes of the wave
+// wait for the longest run among them.  From kStatsLongTrack on the WAVE takes the point after its lanes have finished
+// their short ones: the run is cut into blocks of 64 observations, every lane holds the ray of one observation of block
+// B and meets the rays of every block A <= B, handed round with v_readlane -- n^2 / 64 steps per lane instead of
+// n^2 / 2.  A wave-handled run of n <= 64 costs about n steps of the whole wave, a lane-handled one n^2 / 2 steps of a
+// wave whose other lanes may be idle: a lone long run gains from n = 2 on, 64 equally long ones only from n = 128 on;
+// 32 sits between (a lone run of 31 holds its wave for 465 steps, 64 runs of 32 cost 2048 instead of 496).
+// The widest angle is tracked as the pair (|a x b|, a . b) and compared by the sign of sin(theta1 - theta2) =
+// s1 d2 - d1 s2 (both angles in [0, pi]); atan2 is evaluated once per point (per lane in the wave form).
+constexpr int kStatsLongTrack = 32;
+constexpr int kStatsPtThreads = 256;
+constexpr int kStatsPart = 6;        // partial row of a workgroup: points kept, observations kept, behind, sum err, sum err^2, max err
+static_assert(kStatsLongTrack <= 32, "the lane form keeps the run's mask in 32 bits");
+
+__device__ __forceinline__ void widest_pair(double ax, double ay, double az, double bx, double by, double bz,
+                                            double& sb, double& db) {
+    const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+    const double s = sqrt(cx * cx + cy * cy + cz * cz), d = ax * bx + ay * by + az * bz;
+    if (s * db - d * sb > 0.0) { sb = s; db = d; }
+}
+__device__ __forceinline__ int wave_isum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+
+struct PointStatsOut {
+    int* __restrict__ views;
+    double* __restrict__ max_err;
+    double* __restrict__ sum_err2;
+    double* __restrict__ min_depth;
+    double* __restrict__ angle_deg;
+    unsigned char* __restrict__ keep;
+};
+
+__global__ __launch_bounds__(kStatsPtThreads) void k_point_stats(
+    const int* __restrict__ pt_ptr, const int* __restrict__ cam_idx, const double* __restrict__ camtab,
+    const double* __restrict__ pts, const double* __restrict__ ed, const unsigned char* __restrict__ keep, int P,
+    StatsFilter flt, PointStatsOut out, unsigned char* __restrict__ keep_final, double* __restrict__ part) {
+    __shared__ double red[(kStatsPtThreads / 64) * kStatsPart];
+    const int lane = threadIdx.x & 63;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const double2* __restrict__ ed2 = reinterpret_cast<const double2*>(ed);
+    constexpr double kDeg = 57.295779513082320877;
+    int b = 0, e = 0;
+    double X = 0.0, Y = 0.0, Z = 0.0;
+    if (p < P) { b = pt_ptr[p]; e = pt_ptr[p + 1]; X = pts[3 * (size_t)p]; Y = pts[3 * (size_t)p + 1]; Z = pts[3 * (size_t)p + 2]; }
+    const int n = e - b;
+    int views = 0, behind = 0;
+    double maxe = 0.0, s1 = 0.0, s2 = 0.0, mind = INFINITY, sb = 0.0, db = 1.0;
+    if (n < kStatsLongTrack) {
+        unsigned mask = 0u;
+        for (int k = 0; k < n; ++k) {
+            const double2 q = ed2[b + k];
+            mind = fmin(mind, q.y);
+            behind += q.y <= 0.0 ? 1 : 0;
+            if (keep[b + k]) {
+                mask |= 1u << k;
+                ++views;
+                maxe = fmax(maxe, q.x);
+                s2 += q.x * q.x;
+                s1 += q.x;
+            }
+        }
+        for (int a = 0; a + 1 < n; ++a) {
+            if (!((mask >> a) & 1u) || (mask >> (a + 1)) == 0u) continue;
+            const double* __restrict__ Ta = camtab + (size_t)cam_idx[b + a] * kCamRow + 9;
+            const double ax = X - Ta[0], ay = Y - Ta[1], az = Z - Ta[2];
+            for (int k = a + 1; k < n; ++k) {
+                if (!((mask >> k) & 1u)) continue;
+                const double* __restrict__ Tb = camtab + (size_t)cam_idx[b + k] * kCamRow + 9;
+                widest_pair(ax, ay, az, X - Tb[0], Y - Tb[1], Z - Tb[2], sb, db);
+            }
+        }
+    }
+    double ang = atan2(sb, db);
+    // the long runs among this wave's 64 points, one after the other, by the whole wave
+    unsigned long long todo = __ballot(n >= kStatsLongTrack);
+    while (todo) {
+        const int q = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int qb = __shfl(b, q), qe = __shfl(e, q);
+        const double qX = __shfl(X, q), qY = __shfl(Y, q), qZ = __shfl(Z, q);
+        int wv = 0, wbeh = 0;
+        double wmax = 0.0, wmin = INFINITY, ws1 = 0.0, ws2 = 0.0, wsb = 0.0, wdb = 1.0;
+        for (int B0 = qb; B0 < qe; B0 += 64) {
+            const int kb = B0 + lane;
+            double2 eb = make_double2(0.0, INFINITY);
+            bool fb = false;
+            double bx = 0.0, by = 0.0, bz = 0.0;
+            if (kb < qe) {
+                eb = ed2[kb];
+                fb = keep[kb] != 0;
+                const double* __restrict__ T = camtab + (size_t)cam_idx[kb] * kCamRow + 9;
+                bx = qX - T[0]; by = qY - T[1]; bz = qZ - T[2];
+                wmin = fmin(wmin, eb.y);
+                wbeh += eb.y <= 0.0 ? 1 : 0;
+            }
+            if (fb) { ++wv; wmax = fmax(wmax, eb.x); }
+            const unsigned long long mb = __ballot(fb);
+            for (unsigned long long m = mb; m; m &= m - 1) {       // the two sums in stored order, on every lane alike
+                const double v = readlane_double(eb.x, __ffsll((long long)m) - 1);
+                ws2 += v * v;
+                ws1 += v;
+            }
+            for (int A0 = qb; A0 <= B0; A0 += 64) {
+                double ax = bx, ay = by, az = bz;
+                bool fa = fb;
+                if (A0 != B0) {                                    // a full block: A0 + 63 < B0 <= qe - 1
+                    const int ka = A0 + lane;
+                    fa = keep[ka] != 0;
+                    const double* __restrict__ T = camtab + (size_t)cam_idx[ka] * kCamRow + 9;
+                    ax = qX - T[0]; ay = qY - T[1]; az = qZ - T[2];
+                }
+                for (unsigned long long m = __ballot(fa); m; m &= m - 1) {
+                    const int k = __ffsll((long long)m) - 1;
+                    const double rx = readlane_double(ax, k), ry = readlane_double(ay, k), rz = readlane_double(az, k);
+                    if (fb) widest_pair(rx, ry, rz, bx, by, bz, wsb, wdb);     // (a ray with itself: angle 0, never wider)
+                }
+            }
+        }
+        wv = wave_isum(wv);
+        wbeh = wave_isum(wbeh);
+        wmax = wave_max(wmax);
+        wmin = wave_min(wmin);
+        const double wang = wave_max(atan2(wsb, wdb));
+        const unsigned char qk = (wv >= flt.min_views && wang * kDeg >= flt.min_angle_deg) ? 1 : 0;
+        for (int k = qb + lane; k < qe; k += 64) keep_final[k] = keep[k] & qk;
+        if (lane == q) { views = wv; behind = wbeh; maxe = wmax; mind = wmin; s1 = ws1; s2 = ws2; ang = wang; }
+    }
+    const double deg = ang * kDeg;
+    const bool pk = p < P && views >= flt.min_views && deg >= flt.min_angle_deg;
+    if (p < P) {
+        out.views[p] = views; out.max_err[p] = maxe; out.sum_err2[p] = s2; out.min_depth[p] = mind;
+        out.angle_deg[p] = deg; out.keep[p] = pk ? 1 : 0;
+        if (n < kStatsLongTrack)
+            for (int k = 0; k < n; ++k) keep_final[b + k] = keep[b + k] & (pk ? 1 : 0);
+    }
+    // the workgroup's row: sums over its points in lane order inside a wave, wave by wave
+    double v[kStatsPart - 1] = {pk ? 1.0 : 0.0, pk ? (double)views : 0.0, (double)behind, pk ? s1 : 0.0, pk ? s2 : 0.0};
+    const double vmax = wave_max(pk ? maxe : 0.0);
+    block_sum<kStatsPart - 1>(v, red);
+    __shared__ double redmax[kStatsPtThreads / 64];
+    if (lane == 0) redmax[threadIdx.x >> 6] = vmax;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* __restrict__ row = part + (size_t)blockIdx.x * kStatsPart;
+#pragma unroll
+        for (int k = 0; k < kStatsPart - 1; ++k) row[k] = v[k];
+        double m = 0.0;
+        for (int k = 0; k < kStatsPtThreads / 64; ++k) m = fmax(m, redmax[k]);
+        row[kStatsPart - 1] = m;
+    }
+}
+
+// rows of k_point_stats -> out[0..5] (points kept, observations kept, behind, sum err, sum err^2, max err): every thread
+// adds rows tid, tid + 256, ... in that order, then the 256 sums are added in thread order
+__global__ __launch_bounds__(256) void k_stats_summary(const double* __restrict__ part, int rows, double* __restrict__ out) {
+    __shared__ double red[4 * kStatsPart];
+    double v[kStatsPart - 1] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double m = 0.0;
+    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
+        const double* __restrict__ row = part + (size_t)r * kStatsPart;
+#pragma unroll
+        for (int k = 0; k < kStatsPart - 1; ++k) v[k] += row[k];
+        m = fmax(m, row[kStatsPart - 1]);
+    }
+    m = wave_max(m);
+    block_sum<kStatsPart - 1>(v, red);
+    __shared__ double redmax[4];
+    if ((threadIdx.x & 63) == 0) redmax[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kStatsPart - 1; ++k) out[k] = v[k];
+        out[kStatsPart - 1] = fmax(fmax(redmax[0], redmax[1]), fmax(redmax[2], redmax[3]));
+    }
+}
+
+// One workgroup per camera over its slice of the permutation (camera-major position -> point-major position): thread t
+// takes entries t, t + 256, ... in that order (four gathers in flight), the 256 partial sums are added in thread order.
+__global__ __launch_bounds__(kCamThreads) void k_cam_stats(const int* __restrict__ cam_ptr, const int* __restrict__ perm,
+                                                           const double* __restrict__ ed, const unsigned char* __restrict__ keep_final,
+                                                           int* __restrict__ views, double* __restrict__ sum_err,
+                                                           double* __restrict__ max_err, int* __restrict__ n_behind) {
+    __shared__ double red[kCamWaves];
+    __shared__ double redmax[kCamWaves];
+    __shared__ int redi[2 * kCamWaves];
+    const int c = blockIdx.x;
+    const int b = cam_ptr[c], e = cam_ptr[c + 1];
+    const double2* __restrict__ ed2 = reinterpret_cast<const double2*>(ed);
+    int nv = 0, nb = 0;
+    double s = 0.0, m = 0.0;
+    for (int j0 = b + (int)threadIdx.x; j0 < e; j0 += kCamThreads * kCamUnroll) {
+        int idx[kCamUnroll];
+        double2 q[kCamUnroll];
+        unsigned char kf[kCamUnroll];
+#pragma unroll
+        for (int u = 0; u < kCamUnroll; ++u) { const int j = j0 + u * kCamThreads; idx[u] = j < e ? perm[j] : -1; }
+#pragma unroll
+        for (int u = 0; u < kCamUnroll; ++u) {
+            q[u] = make_double2(0.0, 1.0); kf[u] = 0;
+            if (idx[u] >= 0) { q[u] = ed2[idx[u]]; kf[u] = keep_final[idx[u]]; }
+        }
+#pragma unroll
+        for (int u = 0; u < kCamUnroll; ++u) {
+            if (idx[u] >= 0 && q[u].y <= 0.0) ++nb;
+            if (kf[u]) { ++nv; s += q[u].x; m = fmax(m, q[u].x); }
+        }
+    }
+    s = wave_sum(s); m = wave_max(m); nv = wave_isum(nv); nb = wave_isum(nb);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[w] = s; redmax[w] = m; redi[2 * w] = nv; redi[2 * w + 1] = nb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double ts = 0.0, tm = 0.0;
+        int tv = 0, tb = 0;
+        for (int k = 0; k < kCamWaves; ++k) { ts += red[k]; tm = fmax(tm, redmax[k]); tv += redi[2 * k]; tb += redi[2 * k + 1]; }
+        views[c] = tv; sum_err[c] = ts; max_err[c] = tm; n_behind[c] = tb;
+    }
+}
+
+// The permutation k_cam_stats walks: the stable counting sort of k_cam_hist / k_cam_offsets with no camera left out.
+//   k_stats_cam_count  hist[slice][C] -> cnt[c], one thread per camera
+//   k_stats_cam_scan   one workgroup: cam_ptr = exclusive prefix sums of cnt (every thread a contiguous piece)
+//   k_stats_cam_scatter  k_cam_scatter's walk, storing the point-major position itself
+__global__ __launch_bounds__(256) void k_stats_cam_count(const int* __restrict__ hist, int B, int C, int* __restrict__ cnt) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    int total = 0;
+    for (int b0 = 0; b0 < B; b0 += 16) {
+        int n[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) n[u] = b0 + u < B ? hist[(size_t)(b0 + u) * C + c] : 0;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) total += n[u];
+    }
+    cnt[c] = total;
+}
+__global__ __launch_bounds__(1024) void k_stats_cam_scan(const int* __restrict__ cnt, int C, int* __restrict__ cam_ptr) {
+    __shared__ int tot[1024];
+    const int per = (C + 1023) / 1024;
+    const int c0 = min(C, (int)threadIdx.x * per), c1 = min(C, c0 + per);
+    int s = 0;
+    for (int c = c0; c < c1; ++c) s += cnt[c];
+    tot[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {                       // inclusive scan of the 1024 piece totals
+        const int add = (int)threadIdx.x >= o ? tot[threadIdx.x - o] : 0;
+        __syncthreads();
+        tot[threadIdx.x] += add;
+        __syncthreads();
+    }
+    int run = tot[threadIdx.x] - s;
+    for (int c = c0; c < c1; ++c) { cam_ptr[c] = run; run += cnt[c]; }
+    if (threadIdx.x == 1023) cam_ptr[C] = tot[1023];
+}
+__global__ __launch_bounds__(64) void k_stats_cam_scatter(const int* __restrict__ cam_idx, int N, int C, int per, int key_bits,
+                                                          const int* __restrict__ off, int* __restrict__ perm) {
+    extern __shared__ int cur[];
+    for (int c = threadIdx.x; c < C; c += 64) cur[c] = off[(size_t)blockIdx.x * C + c];
+    __syncthreads();
+    const int lane = threadIdx.x;
+    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    const int b0 = blockIdx.x * per, b1 = min(N, b0 + per);
+    int cn = b0 + lane < b1 ? cam_idx[b0 + lane] : -1;
+    for (int k0 = b0; k0 < b1; k0 += 64) {
+        const int c = cn;
+        cn = k0 + 64 + lane < b1 ? cam_idx[k0 + 64 + lane] : -1;
+        const bool act = c >= 0;
+        unsigned long long eq = __ballot(act);                 // lanes with the same camera as this one
+        for (int bit = 0; bit < key_bits; ++bit) {
+            const unsigned long long m = __ballot(act && ((c >> bit) & 1));
+            eq &= ((c >> bit) & 1) ? m : ~m;
+        }
+        if (act) {
+            perm[cur[c] + __popcll(eq & lt)] = k0 + lane;
+            if ((eq >> lane) == 1ull) cur[c] += __popcll(eq);   // the highest lane of the group advances the offset
+        }
+        __builtin_amdgcn_wave_barrier();                         // (one wave: LDS operations execute in program order)
+    }
+}
+
 }  // namespace sfmba

@@ -441,6 +441,19 @@ struct sfmba_handle {
     int scale_pts = 1;                       // points per thread of k_update_scale
     double* partB() const { return part.as<double>() + (size_t)kPartRows * kNQ; }
     bool pending_scale_sums = false;         // k_update_scale ran, its final sums ride with the next k_jdot
+    // sfmba_reprojection_stats: a parameter vector, camera table and result arrays of its own (grow-only), so that the
+    // solver's buffers -- x, tab, rec, r, J, the normal blocks -- are as the last solve left them after a statistics call
+    struct Stats {
+        DevBuf x, tab;                       // the call's parameter vector and its camera table
+        DevBuf ed, keep, keep_final;         // [ld] err | depth pairs; [ld] own test; [ld] own test and point kept
+        DevBuf pt_views, pt_d, pt_keep;      // [P]; [4][P] max err, sum err^2, min depth, angle; [P]
+        DevBuf cam_i, cam_d;                 // [2][C] views, behind; [2][C] sum err, max err
+        DevBuf part, sum;                    // [point workgroups][kStatsPart]; [kStatsPart]
+        DevBuf perm, cam_ptr, hist, cnt;     // camera-major permutation of ALL observations, built at the first call of a problem
+        unsigned long long perm_gen = 0;     // ... for the problem of this generation and size (0: none)
+        int64_t perm_N = -1, perm_C = -1;
+        PinnedBuf host;                      // staging of the per-observation downloads
+    } stats;
 };
 
 namespace {
@@ -1298,9 +1311,11 @@ void staging_copy(sfmba_handle* h, void* dst, const void* src, size_t bytes) {
     staging_copy(h, dst, src, bytes, [](int, size_t, size_t) {});
 }
 
-int upload_x(sfmba_handle* h, const double* x_host) {
+// `dst` null: the solver's current parameter vector h->x; else a buffer of the caller's (sfmba_reprojection_stats), which
+// leaves h->x and the origin of the fp32 operands alone
+int upload_x(sfmba_handle* h, const double* x_host, double* dst = nullptr) {
     CHK(ensure_h_x(h));
-    if (h->forms.mixed) {                    // origin of the fp32 operands: mean of (a sample of) this vector's points
+    if (h->forms.mixed && !dst) {                    // origin of the fp32 operands: mean of (a sample of) this vector's points
         const double* pts = x_host + 6 * h->C;
         const int64_t stride = std::max<int64_t>(1, h->P / 1024);
         double sx = 0.0, sy = 0.0, sz = 0.0;
@@ -1319,7 +1334,7 @@ int upload_x(sfmba_handle* h, const double* x_host) {
     hipError_t err = hipSuccess;
     staging_copy(h, h->h_x, x_host, sizeof(double) * h->n, [&](int, size_t off, size_t bytes) {
         if (bytes == 0 || err != hipSuccess) return;
-        err = hipMemcpyAsync(reinterpret_cast<char*>(h->x) + off, reinterpret_cast<const char*>(h->h_x) + off, bytes,
+        err = hipMemcpyAsync(reinterpret_cast<char*>(dst ? dst : h->x) + off, reinterpret_cast<const char*>(h->h_x) + off, bytes,
                              hipMemcpyHostToDevice, h->stream);
     });
     HIPCHK(h, err);
@@ -2496,6 +2511,225 @@ int launch_point_prep(sfmba_handle* h, const double* si_pts, const double* e_in,
 }
 }  // namespace
 
+namespace {
+// ---- reprojection statistics (sfmba_reprojection_stats; kernels: ba_kernels.hpp, "Reprojection statistics") ------------
+int stats_allocate(sfmba_handle* h, int* pt_blocks) {
+    auto& s = h->stats;
+    const size_t ldz = (size_t)h->ld, P = (size_t)h->P, C = (size_t)h->C;
+    *pt_blocks = (int)std::max<size_t>(1, (P + kStatsPtThreads - 1) / kStatsPtThreads);
+    const struct { DevBuf* buf; size_t bytes; } sized[] = {
+        {&s.x, sizeof(double) * (size_t)h->n}, {&s.tab, sizeof(double) * cam_table_doubles((int)C)},
+        {&s.ed, sizeof(double) * 2 * ldz}, {&s.keep, ldz}, {&s.keep_final, ldz},
+        {&s.pt_views, sizeof(int) * P}, {&s.pt_d, sizeof(double) * 4 * P}, {&s.pt_keep, P},
+        {&s.cam_i, sizeof(int) * 2 * C}, {&s.cam_d, sizeof(double) * 2 * C},
+        {&s.part, sizeof(double) * kStatsPart * (size_t)*pt_blocks}, {&s.sum, sizeof(double) * kStatsPart}};
+    for (const auto& b : sized) HIPCHK(h, b.buf->ensure(b.bytes));
+    return 0;
+}
+
+// x into the call's own buffer, and its camera table
+int stats_prepare(sfmba_handle* h, const double* x) {
+    auto& s = h->stats;
+    CHK(upload_x(h, x, s.x.as<double>()));
+    hipLaunchKernelGGL(k_cam_table, dim3((unsigned)((h->C + 255) / 256)), dim3(256), 0, h->stream, (const double*)s.x.as<double>(),
+                       (int)h->C, s.tab.as<double>());
+    LAUNCHED(h);
+    return 0;
+}
+
+// the per-observation sweep: grid, workgroup and LDS of the residual-only sweep (launch_resjac)
+int launch_obs_stats(sfmba_handle* h, const StatsFilter& flt) {
+    auto& s = h->stats;
+    const bool lds_tab = h->forms.lds_tab;
+    const int grid = grid_1d(h->N, kSweepThreads, h->n_cu);
+    const size_t lds = lds_tab ? (size_t)h->C * kCamRow * sizeof(double) : sizeof(double) * kRowSlabDoubles * kWavesPerSweepBlock;
+    auto kern = lds_tab ? (h->f32 ? k_obs_stats<true, true> : k_obs_stats<true, false>)
+                        : (h->f32 ? k_obs_stats<false, true> : k_obs_stats<false, false>);
+    CHK(set_lds(h, kern, lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, (const double*)s.tab.as<double>(),
+                       (const double*)(s.x.as<double>() + 6 * h->C), (const int*)h->cam_idx.as<int>(),
+                       (const int*)h->pt_idx.as<int>(), (const double*)h->uv.as<double>(), s.ed.as<double>(),
+                       s.keep.as<unsigned char>(), (int)h->N, (int)h->C, h->K, flt.max_err, flt.min_depth);
+    LAUNCHED(h);
+    return 0;
+}
+
+int launch_point_stats(sfmba_handle* h, const StatsFilter& flt, int pt_blocks) {
+    auto& s = h->stats;
+    double* d = s.pt_d.as<double>();
+    const size_t P = (size_t)h->P;
+    const PointStatsOut out{s.pt_views.as<int>(), d, d + P, d + 2 * P, d + 3 * P, s.pt_keep.as<unsigned char>()};
+    hipLaunchKernelGGL(k_point_stats, dim3(pt_blocks), dim3(kStatsPtThreads), 0, h->stream, (const int*)h->pt_ptr.as<int>(),
+                       (const int*)h->cam_idx.as<int>(), (const double*)s.tab.as<double>(),
+                       (const double*)(s.x.as<double>() + 6 * h->C), (const double*)s.ed.as<double>(),
+                       (const unsigned char*)s.keep.as<unsigned char>(), (int)h->P, flt, out,
+                       s.keep_final.as<unsigned char>(), s.part.as<double>());
+    LAUNCHED(h);
+    return 0;
+}
+
+int launch_stats_summary(sfmba_handle* h, int pt_blocks) {
+    auto& s = h->stats;
+    hipLaunchKernelGGL(k_stats_summary, dim3(1), dim3(256), 0, h->stream, (const double*)s.part.as<double>(), pt_blocks,
+                       s.sum.as<double>());
+    LAUNCHED(h);
+    return 0;
+}
+
+// The camera-major permutation of all observations of the current problem: built at the first call that asks for
+// per-camera figures and kept until the problem's arrays change (the solver's own lists leave out cameras held still
+// and, sorted on the device, come without the permutation).
+int stats_cam_perm(sfmba_handle* h) {
+    auto& s = h->stats;
+    const int64_t N = h->N, C = h->C;
+    if (s.perm_gen != 0 && s.perm_gen == h->problem_gen && s.perm_N == N && s.perm_C == C) return 0;
+    const size_t lds = sizeof(int) * (size_t)C;
+    if (lds > kLdsDynMax)
+        return fail(h, -1, "per-camera statistics sort with one LDS counter per camera: at most %d cameras", (int)(kLdsDynMax / sizeof(int)));
+    const int B = (int)std::min<int64_t>(kSortSlices, (N + 63) / 64);
+    const int per_slice = (int)(((N + B - 1) / B + 63) / 64 * 64);
+    int key_bits = 0;
+    while (((int64_t)1 << key_bits) < C) ++key_bits;
+    HIPCHK(h, s.hist.ensure(sizeof(int) * 2 * (size_t)B * (size_t)C));                // counts | offsets
+    HIPCHK(h, s.cnt.ensure(sizeof(int) * (size_t)C));
+    HIPCHK(h, s.cam_ptr.ensure(sizeof(int) * ((size_t)C + 1)));
+    HIPCHK(h, s.perm.ensure(sizeof(int) * (size_t)h->ld));
+    int* off = s.hist.as<int>() + (size_t)B * (size_t)C;
+    const unsigned cblocks = (unsigned)((C + 255) / 256);
+    CHK(set_lds(h, k_cam_hist, lds));
+    CHK(set_lds(h, k_stats_cam_scatter, lds));
+    hipLaunchKernelGGL(k_cam_hist, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(),
+                       (const unsigned char*)nullptr, (int)N, (int)C, per_slice, s.hist.as<int>());
+    LAUNCHED(h);
+    hipLaunchKernelGGL(k_stats_cam_count, dim3(cblocks), dim3(256), 0, h->stream, (const int*)s.hist.as<int>(), B, (int)C,
+                       s.cnt.as<int>());
+    LAUNCHED(h);
+    hipLaunchKernelGGL(k_stats_cam_scan, dim3(1), dim3(1024), 0, h->stream, (const int*)s.cnt.as<int>(), (int)C, s.cam_ptr.as<int>());
+    LAUNCHED(h);
+    hipLaunchKernelGGL(k_cam_offsets, dim3(cblocks), dim3(256), 0, h->stream, (const int*)s.hist.as<int>(),
+                       (const int*)s.cam_ptr.as<int>(), B, (int)C, off);
+    LAUNCHED(h);
+    hipLaunchKernelGGL(k_stats_cam_scatter, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(), (int)N, (int)C,
+                       per_slice, key_bits, (const int*)off, s.perm.as<int>());
+    LAUNCHED(h);
+    s.perm_gen = h->problem_gen; s.perm_N = N; s.perm_C = C;
+    return 0;
+}
+
+int launch_cam_stats(sfmba_handle* h) {
+    auto& s = h->stats;
+    const size_t C = (size_t)h->C;
+    hipLaunchKernelGGL(k_cam_stats, dim3((unsigned)C), dim3(kCamThreads), 0, h->stream, (const int*)s.cam_ptr.as<int>(),
+                       (const int*)s.perm.as<int>(), (const double*)s.ed.as<double>(),
+                       (const unsigned char*)s.keep_final.as<unsigned char>(), s.cam_i.as<int>(), s.cam_d.as<double>(),
+                       s.cam_d.as<double>() + C, s.cam_i.as<int>() + C);
+    LAUNCHED(h);
+    return 0;
+}
+
+StatsFilter stats_filter(const sfmba_filter_options& o) {
+    return StatsFilter{o.max_error_px, o.min_depth, o.min_angle_deg, (int)o.min_views};
+}
+
+// sfmba_time_kernel, which = 13 / 14: the per-observation sweep / the per-point reduction at x, default thresholds
+int stats_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t reps, double* avg_us) {
+    sfmba_filter_options o;
+    sfmba_default_filter_options(&o);
+    const StatsFilter flt = stats_filter(o);
+    int pt_blocks = 1;
+    CHK(stats_allocate(h, &pt_blocks));
+    CHK(stats_prepare(h, x));
+    CHK(launch_obs_stats(h, flt));                      // (the reduction's input)
+    struct EventPair {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    HIPCHK(h, hipEventCreate(&ev.a));
+    HIPCHK(h, hipEventCreate(&ev.b));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventRecord(ev.a, h->stream));
+    for (int k = 0; k < reps; ++k) {
+        if (which == 13) CHK(launch_obs_stats(h, flt));
+        else CHK(launch_point_stats(h, flt, pt_blocks));
+    }
+    HIPCHK(h, hipEventRecord(ev.b, h->stream));
+    HIPCHK(h, hipEventSynchronize(ev.b));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, ev.a, ev.b));
+    *avg_us = 1e3 * (double)ms / reps;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+}  // namespace
+
+void sfmba_default_filter_options(sfmba_filter_options* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->max_error_px = INFINITY; o->min_depth = -INFINITY; o->min_angle_deg = 0.0; o->min_views = 0;
+}
+
+int sfmba_reprojection_stats(sfmba_handle* h, const double* x, const sfmba_filter_options* opt, double* obs_err,
+                             double* obs_depth, uint8_t* obs_keep, int32_t* pt_views, double* pt_max_err, double* pt_sum_err2,
+                             double* pt_min_depth, double* pt_max_angle_deg, uint8_t* pt_keep, int32_t* cam_views,
+                             double* cam_sum_err, double* cam_max_err, int32_t* cam_behind, sfmba_stats_summary* summary) {
+    CHK(enter(h));
+    CHK(begin_compute(h, x));
+    sfmba_filter_options o;
+    if (opt) o = *opt; else sfmba_default_filter_options(&o);
+    if (std::isnan(o.max_error_px) || std::isnan(o.min_depth) || std::isnan(o.min_angle_deg))
+        return fail(h, -1, "a threshold of the filter options is NaN");
+    const StatsFilter flt = stats_filter(o);
+    auto& s = h->stats;
+    const size_t N = (size_t)h->N, P = (size_t)h->P, C = (size_t)h->C;
+    const bool want_cam = cam_views || cam_sum_err || cam_max_err || cam_behind;
+    int pt_blocks = 1;
+    CHK(stats_allocate(h, &pt_blocks));
+    CHK(stats_prepare(h, x));
+    if (want_cam) CHK(stats_cam_perm(h));
+    CHK(launch_obs_stats(h, flt));
+    CHK(launch_point_stats(h, flt, pt_blocks));
+    if (summary) CHK(launch_stats_summary(h, pt_blocks));
+    if (want_cam) CHK(launch_cam_stats(h));
+    // downloads: only what was asked for; the per-observation arrays through pinned staging, then into the caller's order
+    const bool want_ed = obs_err || obs_depth;
+    if (want_ed || obs_keep) HIPCHK(h, s.host.ensure(17 * N + 64, 0));
+    double* const st_ed = s.host.as<double>();
+    unsigned char* const st_keep = s.host.as<unsigned char>() + 16 * N;
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+    };
+    if (want_ed) HIPCHK(h, down(st_ed, s.ed.p, 16 * N));
+    if (obs_keep) HIPCHK(h, down(st_keep, s.keep_final.p, N));
+    const double* pd = s.pt_d.as<double>();
+    HIPCHK(h, down(pt_views, s.pt_views.p, sizeof(int32_t) * P));
+    HIPCHK(h, down(pt_max_err, pd, sizeof(double) * P));
+    HIPCHK(h, down(pt_sum_err2, pd + P, sizeof(double) * P));
+    HIPCHK(h, down(pt_min_depth, pd + 2 * P, sizeof(double) * P));
+    HIPCHK(h, down(pt_max_angle_deg, pd + 3 * P, sizeof(double) * P));
+    HIPCHK(h, down(pt_keep, s.pt_keep.p, P));
+    HIPCHK(h, down(cam_views, s.cam_i.p, sizeof(int32_t) * C));
+    HIPCHK(h, down(cam_behind, s.cam_i.as<int>() + C, sizeof(int32_t) * C));
+    HIPCHK(h, down(cam_sum_err, s.cam_d.p, sizeof(double) * C));
+    HIPCHK(h, down(cam_max_err, s.cam_d.as<double>() + C, sizeof(double) * C));
+    double sums[kStatsPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (summary) HIPCHK(h, down(sums, s.sum.p, sizeof sums));
+    CHK(wait_stream(h));
+    if (want_ed || obs_keep) {
+        for (size_t k = 0; k < N; ++k) {
+            const size_t d = h->permuted ? (size_t)h->order[k] : k;
+            if (obs_err) obs_err[d] = st_ed[2 * k];
+            if (obs_depth) obs_depth[d] = st_ed[2 * k + 1];
+            if (obs_keep) obs_keep[d] = st_keep[k];
+        }
+    }
+    if (summary) {
+        summary->n_obs = h->N;
+        summary->n_points_kept = (int64_t)sums[0]; summary->n_obs_kept = (int64_t)sums[1]; summary->n_behind = (int64_t)sums[2];
+        summary->sum_err = sums[3]; summary->sum_err2 = sums[4]; summary->max_err = sums[5];
+    }
+    return 0;
+}
+
 int sfmba_residuals(sfmba_handle* h, const double* x, double* r_out) {
     CHK(enter(h));
     CHK(begin_compute(h, x));
@@ -2669,6 +2903,7 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
     CHK(enter(h));
     CHK(begin_compute(h, x));
     if (!avg_us || reps <= 0) return fail(h, -1, "bad reps / avg_us");
+    if (which == 13 || which == 14) return stats_time_kernel(h, x, which, reps, avg_us);
     int np = 0;
     CHK(linearise_at(h, x, which >= 2));
     if (which >= 2) {

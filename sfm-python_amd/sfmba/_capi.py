@@ -21,6 +21,7 @@ SYMBOLS = (
     "sfmba_comm_destroy", "sfmba_set_precision", "sfmba_p2p_export", "sfmba_p2p_attach", "sfmba_p2p_detach",
     "sfmba_p2p_calls", "sfmba_tr2d_solve", "sfmba_debug_option", "sfmba_set_print", "sfmba_get_counters", "sfmba_problem_reuse", "sfmba_dense_schur",
     "sfmba_get_pcg_history", "sfmba_set_fixed_cameras", "sfmba_step_products", "sfmba_get_form",
+    "sfmba_default_filter_options", "sfmba_reprojection_stats",
 )
 
 
@@ -39,6 +40,16 @@ class Result(C.Structure):
                 ("reserved", C.c_int32), ("seconds_total", C.c_double), ("seconds_device", C.c_double),
                 ("resjac_avg_us", C.c_double), ("resjac_launches", C.c_int64),
                 ("last_step_norm", C.c_double), ("last_reg", C.c_double)]
+
+
+class FilterOptions(C.Structure):
+    _fields_ = [("max_error_px", C.c_double), ("min_depth", C.c_double), ("min_angle_deg", C.c_double),
+                ("min_views", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StatsSummary(C.Structure):
+    _fields_ = [("n_obs", C.c_int64), ("n_obs_kept", C.c_int64), ("n_points_kept", C.c_int64),
+                ("n_behind", C.c_int64), ("sum_err", C.c_double), ("sum_err2", C.c_double), ("max_err", C.c_double)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -117,6 +128,11 @@ def load():
         lib.sfmba_step_products.restype = C.c_int
         lib.sfmba_get_form.argtypes = [P, C.c_char_p, C.POINTER(C.c_int32)]
         lib.sfmba_get_form.restype = C.c_int
+    if hasattr(lib, "sfmba_reprojection_stats"):     # (likewise)
+        lib.sfmba_default_filter_options.argtypes = [C.POINTER(FilterOptions)]
+        lib.sfmba_default_filter_options.restype = None
+        lib.sfmba_reprojection_stats.argtypes = [P, P, C.POINTER(FilterOptions)] + [P] * 13 + [C.POINTER(StatsSummary)]
+        lib.sfmba_reprojection_stats.restype = C.c_int
     lib.sfmba_tr2d_solve.argtypes = [P, P, C.c_double, P]
     lib.sfmba_comm_get_unique_id.argtypes = [P]
     lib.sfmba_comm_init.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int64]

@@ -21,6 +21,47 @@ def _f64(a, shape=None, name="array"):
     return a
 
 
+class ReprojectionStats:
+    """What `Backend.reprojection_stats` returns (include/sfmba.h: sfmba_reprojection_stats).  Arrays that were not asked
+    for are None.  ``obs_*`` (N) in the caller's observation order, ``pt_*`` (P), ``cam_*`` (C); the summary's fields
+    ``n_obs, n_obs_kept, n_points_kept, n_behind, sum_err, sum_err2, max_err`` run over the finally kept observations."""
+
+    _ARRAYS = ("obs_err", "obs_depth", "obs_keep", "pt_views", "pt_max_err", "pt_sum_err2", "pt_min_depth",
+               "pt_max_angle_deg", "pt_keep", "cam_views", "cam_sum_err", "cam_max_err", "cam_behind")
+    _SUMMARY = ("n_obs", "n_obs_kept", "n_points_kept", "n_behind", "sum_err", "sum_err2", "max_err")
+
+    def __init__(self, arrays, summary):
+        for name in self._ARRAYS:
+            setattr(self, name, arrays.get(name))
+        for name in self._SUMMARY:
+            v = getattr(summary, name)
+            setattr(self, name, float(v) if isinstance(v, float) else int(v))
+
+    @property
+    def mean_error_px(self):
+        """Mean reprojection error over the kept observations (0 when none is kept)."""
+        return self.sum_err / max(self.n_obs_kept, 1)
+
+    @property
+    def rms_error_px(self):
+        """sqrt(mean err^2) over the kept observations."""
+        return float(np.sqrt(self.sum_err2 / max(self.n_obs_kept, 1)))
+
+    @property
+    def cam_mean_err(self):
+        if self.cam_sum_err is None:
+            return None
+        return self.cam_sum_err / np.maximum(self.cam_views, 1)
+
+    def summary(self):
+        d = {name: getattr(self, name) for name in self._SUMMARY}
+        d["mean_error_px"], d["rms_error_px"] = self.mean_error_px, self.rms_error_px
+        return d
+
+    def __repr__(self):
+        return "ReprojectionStats(" + ", ".join(f"{k}={v!r}" for k, v in self.summary().items()) + ")"
+
+
 class Backend:
     """One MI355X.  Not thread-safe; use one Backend per thread (include/sfmba.h, Threading)."""
 
@@ -236,6 +277,40 @@ class Backend:
         out = np.empty(2 * self.n_obs)
         self._check(self._lib.sfmba_residuals(self._h, _capi.ptr(x), _capi.ptr(out)))
         return out
+
+    def reprojection_stats(self, x, max_error_px=np.inf, min_depth=-np.inf, min_angle_deg=0.0, min_views=0,
+                           want=("obs", "points", "cameras")):
+        """Reprojection error, depth and keep mask per observation, track statistics per point, error statistics per
+        camera and a summary at ``x``, in one sweep on the device (include/sfmba.h: sfmba_reprojection_stats).  An
+        observation is kept when ``err <= max_error_px`` and ``depth > min_depth`` and its point is kept; a point when
+        it has ``min_views`` such observations and their rays open at least ``min_angle_deg``.  The defaults keep
+        everything.  ``want``: which groups of arrays to download ("obs", "points", "cameras"); the summary always comes.
+        -> :class:`ReprojectionStats`."""
+        self._flush_pending()
+        x = _f64(x, (self.n_params,), "x")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        unknown = set(want) - {"obs", "points", "cameras"}
+        if unknown:
+            raise ValueError(f"unknown group(s) in `want`: {sorted(unknown)}")
+        opt = _capi.FilterOptions()
+        self._lib.sfmba_default_filter_options(C.byref(opt))
+        opt.max_error_px, opt.min_depth, opt.min_angle_deg = float(max_error_px), float(min_depth), float(min_angle_deg)
+        opt.min_views = int(min_views)
+        N, P, Cn = self.n_obs, self.n_points, self.n_cameras
+        spec = (("obs", "obs_err", N, np.float64), ("obs", "obs_depth", N, np.float64), ("obs", "obs_keep", N, np.uint8),
+                ("points", "pt_views", P, np.int32), ("points", "pt_max_err", P, np.float64),
+                ("points", "pt_sum_err2", P, np.float64), ("points", "pt_min_depth", P, np.float64),
+                ("points", "pt_max_angle_deg", P, np.float64), ("points", "pt_keep", P, np.uint8),
+                ("cameras", "cam_views", Cn, np.int32), ("cameras", "cam_sum_err", Cn, np.float64),
+                ("cameras", "cam_max_err", Cn, np.float64), ("cameras", "cam_behind", Cn, np.int32))
+        arrays = {name: np.empty(n, dtype=dt) for group, name, n, dt in spec if group in want}
+        ptrs = [_capi.ptr(arrays[name]) if name in arrays else None for _, name, _, _ in spec]
+        summary = _capi.StatsSummary()
+        self._check(self._lib.sfmba_reprojection_stats(self._h, _capi.ptr(x), C.byref(opt), *ptrs, C.byref(summary)))
+        for name in ("obs_keep", "pt_keep"):
+            if name in arrays:
+                arrays[name] = arrays[name].view(np.bool_)
+        return ReprojectionStats(arrays, summary)
 
     def residual_jacobian(self, x):
         self._flush_pending()

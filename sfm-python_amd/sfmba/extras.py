@@ -30,6 +30,112 @@ def calc_reproj_error(points3d, points2d, K, R, tvec, device=0):
     return float(np.linalg.norm(reproj_error(points3d, points2d, K, R, tvec, device=device), axis=1).mean())
 
 
+def _backend_with_problem(args, device, backend):
+    n_cameras, n_points, camera_indices, point_indices, points_2d, K = api._split_args(tuple(args))
+    be = backend if backend is not None else api.get_backend(device)
+    be.set_precision(64)
+    be.set_fixed_cameras(())
+    be.set_problem(n_cameras, n_points, camera_indices, point_indices, points_2d, K)
+    return be
+
+
+def reprojection_stats(x, args, max_error_px=np.inf, min_depth=-np.inf, min_angle_deg=0.0, min_views=0,
+                       want=("obs", "points", "cameras"), device=0, backend=None):
+    """`Backend.reprojection_stats` in one call on the reference's ``args`` tuple (sfm.py:268): per-observation
+    reprojection error, depth and keep mask, per-point track statistics, per-camera error statistics and a summary at
+    ``x``, evaluated by one sweep on the device.  ``backend``: a :class:`Backend` to run on instead of the calling
+    thread's own (``device`` is then ignored)."""
+    be = _backend_with_problem(args, device, backend)
+    return be.reprojection_stats(x, max_error_px=max_error_px, min_depth=min_depth, min_angle_deg=min_angle_deg,
+                                 min_views=min_views, want=want)
+
+
+def total_mean_reproj_error(x, args, device=0, backend=None):
+    """Mean L2 reprojection error over all observations at ``x``: the figure the reference accumulates after every fused
+    edge with one ``calc_reproj_error`` call per observation (sfm.py:234-241), here from one sweep.
+
+    Two things the reference does are documented, not imitated.  It divides the sum by the LAST LOOP INDEX ``n = N - 1``
+    (``enumerate`` starts at 0) and not by the number of observations; this function divides by ``N``, so the
+    reference's printed value is ``N / (N - 1)`` times larger.  And it reads a pose ``H`` as ``[R | t]`` with
+    ``x_cam = R X + t``, while the bundle-adjustment model -- and ``x`` here -- holds the camera
+    CENTRE, ``x_cam = R (X - T)``; pack poses with ``pack_cameras_points(..., pose_convention=...)`` accordingly."""
+    st = reprojection_stats(x, args, want=(), device=device, backend=backend)
+    return st.sum_err / max(st.n_obs, 1)
+
+
+def prune_problem(x, args, obs_keep, pt_keep):
+    """Remove dropped observations and dropped points from a problem -> ``(x2, args2, obs_index, point_index)``.
+
+    ``obs_keep`` (N) and ``pt_keep`` (P) are boolean masks, e.g. those of :func:`reprojection_stats`.  An observation
+    survives when it is kept AND its point is kept; a point survives when it is kept (an observation of a dropped point
+    goes with it).  Points are renumbered densely in their old order, observations keep their order, ALL cameras stay
+    (their indices remain valid; a camera left without observations is legal input to the solver).  ``obs_index`` and
+    ``point_index`` are the positions of the surviving rows in the original arrays: ``args2``'s pixels are
+    ``points_2d[obs_index]``, the points of ``x2`` are those of ``x`` at ``point_index``.  Pure numpy."""
+    n_cameras, n_points, camera_indices, point_indices, points_2d, K = api._split_args(tuple(args))
+    n_cameras, n_points = int(n_cameras), int(n_points)
+    ci = np.asarray(camera_indices).ravel()
+    pi = np.asarray(point_indices).ravel()
+    p2 = np.asarray(points_2d)
+    x = np.asarray(x, dtype=np.float64).ravel()
+    obs_keep = np.asarray(obs_keep).ravel()
+    pt_keep = np.asarray(pt_keep).ravel()
+    if obs_keep.shape[0] != ci.shape[0] or pi.shape[0] != ci.shape[0] or p2.shape[0] != ci.shape[0]:
+        raise ValueError(f"obs_keep has {obs_keep.shape[0]} entries, the problem {ci.shape[0]} observations")
+    if pt_keep.shape[0] != n_points:
+        raise ValueError(f"pt_keep has {pt_keep.shape[0]} entries, the problem {n_points} points")
+    if x.shape[0] != 6 * n_cameras + 3 * n_points:
+        raise ValueError(f"x has {x.shape[0]} entries, expected 6*n_cameras + 3*n_points = {6 * n_cameras + 3 * n_points}")
+    pt_keep = pt_keep.astype(bool)
+    obs_index = np.flatnonzero(obs_keep.astype(bool) & pt_keep[pi])
+    point_index = np.flatnonzero(pt_keep)
+    new_id = np.full(n_points, -1, dtype=np.int64)
+    new_id[point_index] = np.arange(point_index.shape[0], dtype=np.int64)
+    pts = x[6 * n_cameras:].reshape(n_points, 3)
+    x2 = np.concatenate([x[:6 * n_cameras], pts[point_index].ravel()])
+    args2 = (n_cameras, int(point_index.shape[0]), ci[obs_index], new_id[pi[obs_index]], p2[obs_index], K)
+    return x2, args2, obs_index, point_index
+
+
+def refine_reconstruction(x0, args, rounds=2, max_error_px=4.0, min_depth=0.0, min_angle_deg=2.0, min_views=2,
+                          device=0, backend=None, **least_squares_kwargs):
+    """The trim loop around bundle adjustment: solve, measure, drop, solve again.
+
+    Every round solves the current problem with :func:`sfmba.least_squares` (``least_squares_kwargs`` are passed on;
+    ``x_scale='jac'`` and ``method='trf'`` are the defaults), takes :func:`reprojection_stats` at the result with the
+    four thresholds and prunes what fails them (:func:`prune_problem`).  It stops after ``rounds`` solves, or as soon as
+    a round drops nothing.  -> ``(result, (x, args), (obs_index, point_index), summaries)``: the last solve's result; the
+    surviving problem with the parameters at the last solve's ``x``; the surviving rows' positions in the ORIGINAL
+    arrays, composed over all rounds; per round a dict with ``n_obs``, ``n_points`` (solved), ``n_obs_kept``,
+    ``n_points_kept``, ``mean_error_px``, ``rms_error_px``, ``max_error_px`` (over the kept set) and ``rmse`` (the
+    solve's, over everything it was given)."""
+    if rounds < 1:
+        raise ValueError("rounds must be at least 1")
+    kw = dict(x_scale="jac", method="trf")
+    kw.update(least_squares_kwargs)
+    be = backend if backend is not None else api.get_backend(device)
+    x = np.asarray(x0, dtype=np.float64).ravel()
+    args = api._split_args(tuple(args))
+    obs_index = np.arange(len(np.asarray(args[2]).ravel()), dtype=np.int64)
+    point_index = np.arange(int(args[1]), dtype=np.int64)
+    summaries = []
+    result = None
+    for _ in range(int(rounds)):
+        result = api.least_squares(api.compute_residuals, x, args=args, backend=be, **kw)
+        # (the handle holds exactly this problem: statistics straight on it, in the solve's storage precision)
+        st = be.reprojection_stats(result.x, max_error_px=max_error_px, min_depth=min_depth, min_angle_deg=min_angle_deg,
+                                   min_views=min_views, want=("obs", "points"))
+        summaries.append(dict(n_obs=st.n_obs, n_points=int(args[1]), n_obs_kept=st.n_obs_kept,
+                              n_points_kept=st.n_points_kept, mean_error_px=st.mean_error_px,
+                              rms_error_px=st.rms_error_px, max_error_px=st.max_err, rmse=float(result.rmse)))
+        x = result.x
+        if st.n_obs_kept == st.n_obs and st.n_points_kept == int(args[1]):
+            break
+        x, args, oi, pi = prune_problem(result.x, args, st.obs_keep, st.pt_keep)
+        obs_index, point_index = obs_index[oi], point_index[pi]
+    return result, (x, args), (obs_index, point_index), summaries
+
+
 def load_calibration_data(txt_path):
     """3x3 whitespace-separated text -> ndarray, /root/reference/sfm_lite/utils.py:24-35."""
     K = np.array([[float(v) for v in line.split()] for line in open(txt_path) if line.strip()])
