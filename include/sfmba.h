@@ -257,6 +257,60 @@ int  sfmba_reprojection_stats(sfmba_handle* h, const double* x, const sfmba_filt
                               int32_t* cam_views, double* cam_sum_err, double* cam_max_err, int32_t* cam_behind,
                               sfmba_stats_summary* summary);
 
+/* ---- triangulation: N-view DLT plus point refinement ------------------------------------------- */
+/* What creates the points bundle adjustment is given.  The reference calls cv2.triangulatePoints (sfm.py:140, 218), a
+ * two-view DLT over the first two views of a track, once; this call triangulates every selected point of the current
+ * problem from ALL its used observations, with the cameras of x[:6C], in one kernel (k_triangulate).  The points of x
+ * are read only to fill X_out where no new point is returned.
+ *
+ * Per selected point, over its used observations in stored (point-major) order:
+ *   linear stage  cv2.triangulatePoints extended to n views: rows u M3 - M1 and v M3 - M2 with M = K R [I | -T] in
+ *                 pixel units, A^T A accumulated as ten doubles, its smallest eigenvector v by cyclic Jacobi rotations,
+ *                 X = v[:3] / v[3].  The unknowns are neither translated nor rescaled (the homogeneous minimiser is
+ *                 not invariant to that): for two views the result is the reference's.
+ *   refinement    (max_iter > 0) Gauss-Newton on 1/2 sum |r|^2 over the three coordinates, r the residual of
+ *                 sfmba_residuals and its 2x3 block.  The damping (H + lambda diag H) starts at zero; a trial point that
+ *                 raises the cost is rejected and the damping raised (1e-3, then x10; x0.1 after an accepted step), so
+ *                 the refined point never has a higher cost than the linear one.  It stops when an accepted step has
+ *                 |d| <= xtol (|X| + xtol), when the step on offer is that small already (it is not taken: at rounding
+ *                 level a trial point no longer lowers the cost), when a trial is rejected whose predicted reduction
+ *                 was below 1e-12 of the cost (the rounding of the cost's own evaluation decides such trials), or after
+ *                 max_iter trial points.  The run is walked once for the linear
+ *                 stage, once at the linear point and once per trial point (pt_iters counts the trial points).
+ *   verdict       at the result, first match wins (pt_status):
+ *                   1 FEW_VIEWS    fewer used observations than max(2, min_views)
+ *                   2 AT_INFINITY  |v[3]| <= 1e-12 |v|, or anything non-finite
+ *                   3 BEHIND       a used observation has depth <= min_depth
+ *                   4 LOW_ANGLE    the widest ray angle over the used observations (as pt_max_angle_deg of
+ *                                  sfmba_reprojection_stats) is below min_angle_deg
+ *                   5 HIGH_ERROR   a used observation has err above max_error_px
+ *                   0 OK           otherwise;            -1: the point was not selected
+ * X_out (P,3): the new point for status 0, the point of x for every other status.  pt_views: used observations, for
+ * every selected point (else 0).  pt_iters, pt_rms_err = sqrt(sum err^2 / pt_views) in pixels and pt_angle_deg are
+ * those of the result for every point that got past AT_INFINITY; else 0, NaN, NaN.  n_ok: points with status 0.
+ *
+ * pt_select (P) and obs_use (N, the caller's observation order): nonzero = take part; NULL = all.  Any output pointer may
+ * be NULL; an array that is not asked for is not downloaded.  opt = NULL: the defaults.  Returns -1 when no problem is
+ * set, x is NULL, an option is NaN, or the handle waits for its transport.  As sfmba_reprojection_stats: on a sharded
+ * handle the call describes the LOCAL shard only; pixels are read as stored (fp64 or fp32); every buffer is the call's
+ * own (shared with the statistics call), so fun, grad, the PCG record and a following solve are exactly what a fresh
+ * handle gives; no atomics, sums in a fixed order: same input, same bits. */
+typedef struct sfmba_triangulate_options {
+    int32_t max_iter;      /* refinement iterations after the linear solution; 0 = linear only (default 10) */
+    int32_t min_views;     /* used observations a point needs; values < 2 count as 2 (default 2)            */
+    double  xtol;          /* refinement stops when an accepted step has |d| <= xtol (|X| + xtol) (1e-10)    */
+    double  min_angle_deg; /* widest ray angle over the used observations at the result (default 1.0)        */
+    double  min_depth;     /* every used observation must have depth > this at the result (default 0.0)      */
+    double  max_error_px;  /* ... and err <= this (default +inf)                                             */
+} sfmba_triangulate_options;
+void sfmba_default_triangulate_options(sfmba_triangulate_options* opt);
+int  sfmba_triangulate(sfmba_handle* h, const double* x, const uint8_t* pt_select /* P or NULL = all */,
+                       const uint8_t* obs_use /* N, caller's order, or NULL = all */,
+                       const sfmba_triangulate_options* opt,
+                       double* X_out /* (P,3) */, int32_t* pt_status /* P */, int32_t* pt_views /* P */,
+                       int32_t* pt_iters /* P */, double* pt_rms_err /* P */, double* pt_angle_deg /* P */,
+                       int64_t* n_ok);
+
 /* ---- least_squares(method='trf', x_scale='jac') (sfm.py:266-268) ---------------------------- */
 /* x_inout: x0 on entry, result.x on success (untouched on failure). */
 int  sfmba_solve(sfmba_handle* h, double* x_inout, const sfmba_options* opt, sfmba_result* out);
@@ -274,7 +328,8 @@ int  sfmba_get_fun_grad(sfmba_handle* h, double* fun_out, double* grad_out);
  *        right-hand-side pass, 7 the residual+Jacobian sweep with its point-block sums switched off,
  *        10 a streaming-store fill of the Jacobian buffer (ceiling probe),
  *        11 k_jdot and 12 k_backsub (without its PCG prologue) in the form the problem has selected ("rc_consumers"),
- *        13 the per-observation sweep and 14 the per-point reduction of sfmba_reprojection_stats (default options).
+ *        13 the per-observation sweep and 14 the per-point reduction of sfmba_reprojection_stats (default options),
+ *        15 k_triangulate of sfmba_triangulate over every point and observation (default options).
  * avg_us: average duration of one repetition. */
 int  sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t reps, double* avg_us);
 /* Normal-equation blocks at x: U (C,21 upper triangle row-major), V (P,6 upper), gc (C,6), gp (P,3). */

@@ -4747,4 +4747,348 @@ __global__ __launch_bounds__(64) void k_stats_cam_scatter(const int* __restrict_
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Triangulation (sfmba_triangulate): per selected point, over the used observations of its run,
+//   linear stage  the n-view DLT of cv2.triangulatePoints: rows u M3 - M1, v M3 - M2 with M = K R [I | -T], A^T A as ten
+//                 sums, its smallest eigenvector by cyclic Jacobi rotations, X = v[:3] / v[3] (unknowns neither
+//                 translated nor rescaled: for two views this is the reference's minimiser)
+//   refinement    damped Gauss-Newton on 1/2 sum |r|^2 over X, r and d r / d X from observe<> (the solver's residual);
+//                 one pass over the run per trial point, which yields its cost and the next linearisation
+//   verdict       at the result: depth and err of every used observation, the widest ray angle (widest_pair)
+// Runs are handled as in k_point_stats: a lane takes a run shorter than kStatsLongTrack, the wave the longer ones
+// afterwards, lanes striding the run and the sums combined by an xor butterfly, which leaves the same bits on every lane
+// -- so the wave's lanes take every decision alike.  Camera rows are the compact R | T rows of the table (six 16-byte
+// loads), staged in LDS by persistent workgroups when the table fits (forms.lds_tab), else read through L2.
+// No atomics; nothing of the solver's is read but the structure arrays and the pixels.
+// ---------------------------------------------------------------------------------------------
+constexpr int kTriThreads = 512;     // two waves per SIMD: the Jacobi state (26 doubles) and a linearisation stay in registers
+constexpr int kTriSweeps = 12;       // cap of the Jacobi sweeps (a 4x4 converges in 4..7)
+constexpr int kTriOk = 0, kTriFewViews = 1, kTriAtInfinity = 2, kTriBehind = 3, kTriLowAngle = 4, kTriHighError = 5,
+              kTriNotSelected = -1;
+struct TriOptions { int max_iter, min_views; double xtol, min_angle_deg, min_depth, max_err; };
+struct TriIn {
+    const int* __restrict__ pt_ptr;
+    const int* __restrict__ cam_idx;
+    const double* __restrict__ uv;
+    const unsigned char* __restrict__ use;       // [N] stored order, or null: every observation
+    const unsigned char* __restrict__ select;    // [P], or null: every point
+    const double* __restrict__ pts;              // the points of x
+};
+struct TriOut {
+    double* __restrict__ X;
+    int* __restrict__ status;
+    int* __restrict__ views;
+    int* __restrict__ iters;
+    double* __restrict__ rms;
+    double* __restrict__ angle_deg;
+    int* __restrict__ ok_part;                   // [workgroups] points with status OK
+};
+struct TriResult { int status, views, iters; double X, Y, Z, rms, ang; };
+
+// position of entry (i, j) of a symmetric 4x4 kept as its upper triangle, row by row
+__host__ __device__ constexpr int sym4(int i, int j) {
+    return i <= j ? 4 * i - i * (i - 1) / 2 + (j - i) : 4 * j - j * (j - 1) / 2 + (i - j);
+}
+
+// one Jacobi rotation in the (P, Q) plane: a <- G^T a G, v <- v G  (every index is a compile-time constant)
+template <int P, int Q>
+__device__ __forceinline__ void jacobi_rotate(double (&a)[10], double (&v)[16]) {
+    const double apq = a[sym4(P, Q)];
+    const double theta = (a[sym4(Q, Q)] - a[sym4(P, P)]) / (2.0 * apq);
+    // (theta^2 = inf: t = 0; a pair that is zero already: the identity, without a branch around 26 live doubles)
+    const double t = apq == 0.0 ? 0.0 : copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    a[sym4(P, P)] -= t * apq;
+    a[sym4(Q, Q)] += t * apq;
+    a[sym4(P, Q)] = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (r != P && r != Q) {
+            const double arp = a[sym4(r, P)], arq = a[sym4(r, Q)];
+            a[sym4(r, P)] = c * arp - s * arq;
+            a[sym4(r, Q)] = s * arp + c * arq;
+        }
+        const double vrp = v[4 * r + P], vrq = v[4 * r + Q];
+        v[4 * r + P] = c * vrp - s * vrq;
+        v[4 * r + Q] = s * vrp + c * vrq;
+    }
+}
+// eigenvector of the smallest eigenvalue of a (destroyed): cyclic sweeps until the off-diagonal part is 1e-40 of the
+// diagonal (a sweep squares that ratio) or has vanished
+__device__ __forceinline__ void smallest_eigenvector4(double (&a)[10], double& w0, double& w1, double& w2, double& w3) {
+    double v[16] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0};
+#pragma unroll 1
+    for (int sweep = 0; sweep < kTriSweeps; ++sweep) {
+        const double off = fabs(a[1]) + fabs(a[2]) + fabs(a[3]) + fabs(a[5]) + fabs(a[6]) + fabs(a[8]);
+        const double dia = fabs(a[0]) + fabs(a[4]) + fabs(a[7]) + fabs(a[9]);
+        if (!(off > 1e-40 * dia)) break;                         // (a NaN ends the loop too)
+        jacobi_rotate<0, 1>(a, v); jacobi_rotate<0, 2>(a, v); jacobi_rotate<0, 3>(a, v);
+        jacobi_rotate<1, 2>(a, v); jacobi_rotate<1, 3>(a, v); jacobi_rotate<2, 3>(a, v);
+    }
+    double lo = a[0];
+    w0 = v[0]; w1 = v[4]; w2 = v[8]; w3 = v[12];
+    if (a[4] < lo) { lo = a[4]; w0 = v[1]; w1 = v[5]; w2 = v[9]; w3 = v[13]; }
+    if (a[7] < lo) { lo = a[7]; w0 = v[2]; w1 = v[6]; w2 = v[10]; w3 = v[14]; }
+    if (a[9] < lo) { lo = a[9]; w0 = v[3]; w1 = v[7]; w2 = v[11]; w3 = v[15]; }
+}
+
+__device__ __forceinline__ double wave_butterfly_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+// R | T of camera c into the first twelve entries of an observe<> row (w, b, c are not needed for d r / d X)
+__device__ __forceinline__ void tri_load_row(const double* __restrict__ rt, int c, double* __restrict__ tl) {
+    const double2* __restrict__ row = reinterpret_cast<const double2*>(rt + (size_t)c * kCamRT);
+#pragma unroll
+    for (int k = 0; k < kCamRT / 2; ++k) { const double2 q = row[k]; tl[2 * k] = q.x; tl[2 * k + 1] = q.y; }
+#pragma unroll
+    for (int k = kCamRT; k < kCamRow; ++k) tl[k] = 0.0;
+}
+
+// the linear stage's pass: a += the two DLT rows of every used observation; used = their number
+template <bool F32, bool WAVE>
+__device__ __forceinline__ void tri_dlt_pass(const double* __restrict__ rt, const TriIn& in, int b, int e, int lane,
+                                             const KMat& K, double (&a)[10], int& used) {
+#pragma unroll
+    for (int q = 0; q < 10; ++q) a[q] = 0.0;
+    used = 0;
+#pragma unroll 1
+    for (int k = WAVE ? b + lane : b; k < e; k += WAVE ? 64 : 1) {
+        if (in.use != nullptr && !in.use[k]) continue;
+        double tl[kCamRow];
+        tri_load_row(rt, in.cam_idx[k], tl);
+        const double2 px = load_pair(in.uv, F32, k);
+        double m[12];                                            // M = K R [I | -T], row-major 3x4
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) m[4 * i + j] = K.k[3 * i] * tl[j] + K.k[3 * i + 1] * tl[3 + j] + K.k[3 * i + 2] * tl[6 + j];
+            m[4 * i + 3] = -(m[4 * i] * tl[9] + m[4 * i + 1] * tl[10] + m[4 * i + 2] * tl[11]);
+        }
+        double ru[4], rv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { ru[j] = px.x * m[8 + j] - m[j]; rv[j] = px.y * m[8 + j] - m[4 + j]; }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = i; j < 4; ++j) a[sym4(i, j)] += ru[i] * ru[j] + rv[i] * rv[j];
+        ++used;
+    }
+    if (WAVE) {
+#pragma unroll
+        for (int q = 0; q < 10; ++q) a[q] = wave_butterfly_sum(a[q]);
+        used = wave_isum(used);
+    }
+}
+
+// one pass at (X, Y, Z): s = sum |r|^2, g = sum Jp^T r (3), H = sum Jp^T Jp (6, upper); smallest depth, largest err
+template <bool F32, bool WAVE>
+__device__ __forceinline__ void tri_linearise(const double* __restrict__ rt, const TriIn& in, int b, int e, int lane,
+                                              const KMat& K, double X, double Y, double Z, double (&s)[10],
+                                              double& mind, double& maxe) {
+#pragma unroll
+    for (int q = 0; q < 10; ++q) s[q] = 0.0;
+    mind = INFINITY; maxe = 0.0;
+#pragma unroll 1
+    for (int k = WAVE ? b + lane : b; k < e; k += WAVE ? 64 : 1) {
+        if (in.use != nullptr && !in.use[k]) continue;
+        double tl[kCamRow];
+        tri_load_row(rt, in.cam_idx[k], tl);
+        const double2 px = load_pair(in.uv, F32, k);
+        double jc[12], jp[6], rx, ry;
+        observe<true>(tl, X, Y, Z, px.x, px.y, K, rx, ry, jc, jp);
+        const double depth = tl[6] * (X - tl[9]) + tl[7] * (Y - tl[10]) + tl[8] * (Z - tl[11]);
+        const double e2 = rx * rx + ry * ry;
+        s[0] += e2;
+        s[1] += jp[0] * rx + jp[3] * ry; s[2] += jp[1] * rx + jp[4] * ry; s[3] += jp[2] * rx + jp[5] * ry;
+        s[4] += jp[0] * jp[0] + jp[3] * jp[3]; s[5] += jp[0] * jp[1] + jp[3] * jp[4]; s[6] += jp[0] * jp[2] + jp[3] * jp[5];
+        s[7] += jp[1] * jp[1] + jp[4] * jp[4]; s[8] += jp[1] * jp[2] + jp[4] * jp[5];
+        s[9] += jp[2] * jp[2] + jp[5] * jp[5];
+        mind = fmin(mind, depth);
+        maxe = fmax(maxe, sqrt(e2));
+    }
+    if (WAVE) {
+#pragma unroll
+        for (int q = 0; q < 10; ++q) s[q] = wave_butterfly_sum(s[q]);
+        mind = wave_min(mind);
+        maxe = wave_max(maxe);
+    }
+}
+
+// widest angle (radians) between the rays X - T of the used observations of the run: all pairs by one lane, or -- as the
+// wave form of k_point_stats -- every lane the ray of one observation of block B against the rays of the blocks A <= B
+template <bool WAVE>
+__device__ __forceinline__ double tri_widest_angle(const double* __restrict__ rt, const TriIn& in, int b, int e, int lane,
+                                                   double X, double Y, double Z) {
+    double sb = 0.0, db = 1.0;
+    if (!WAVE) {
+        for (int i = b; i + 1 < e; ++i) {
+            if (in.use != nullptr && !in.use[i]) continue;
+            const double* __restrict__ Ta = rt + (size_t)in.cam_idx[i] * kCamRT + 9;
+            const double ax = X - Ta[0], ay = Y - Ta[1], az = Z - Ta[2];
+            for (int k = i + 1; k < e; ++k) {
+                if (in.use != nullptr && !in.use[k]) continue;
+                const double* __restrict__ Tb = rt + (size_t)in.cam_idx[k] * kCamRT + 9;
+                widest_pair(ax, ay, az, X - Tb[0], Y - Tb[1], Z - Tb[2], sb, db);
+            }
+        }
+        return atan2(sb, db);
+    }
+    for (int B0 = b; B0 < e; B0 += 64) {
+        const int kb = B0 + lane;
+        bool fb = false;
+        double bx = 0.0, by = 0.0, bz = 0.0;
+        if (kb < e) {
+            fb = in.use == nullptr || in.use[kb] != 0;
+            const double* __restrict__ T = rt + (size_t)in.cam_idx[kb] * kCamRT + 9;
+            bx = X - T[0]; by = Y - T[1]; bz = Z - T[2];
+        }
+        for (int A0 = b; A0 <= B0; A0 += 64) {
+            double ax = bx, ay = by, az = bz;
+            bool fa = fb;
+            if (A0 != B0) {                                      // a full block: A0 + 63 < B0 <= e - 1
+                const int ka = A0 + lane;
+                fa = in.use == nullptr || in.use[ka] != 0;
+                const double* __restrict__ T = rt + (size_t)in.cam_idx[ka] * kCamRT + 9;
+                ax = X - T[0]; ay = Y - T[1]; az = Z - T[2];
+            }
+            for (unsigned long long m = __ballot(fa); m; m &= m - 1) {
+                const int k = __ffsll((long long)m) - 1;
+                const double rx = readlane_double(ax, k), ry = readlane_double(ay, k), rz = readlane_double(az, k);
+                if (fb) widest_pair(rx, ry, rz, bx, by, bz, sb, db);
+            }
+        }
+    }
+    return wave_max(atan2(sb, db));
+}
+
+// One point.  WAVE: called by all 64 lanes with the same arguments; every lane leaves with the same result.
+// (X0, Y0, Z0): the point of x, handed back whenever the status is not OK.
+template <bool F32, bool WAVE>
+__device__ __forceinline__ void tri_point(const double* __restrict__ rt, const TriIn& in, int b, int e, int lane, const KMat& K,
+                                          const TriOptions& o, double X0, double Y0, double Z0, TriResult& r) {
+    constexpr double kDeg = 57.295779513082320877;
+    r.status = kTriFewViews; r.iters = 0;
+    r.X = X0; r.Y = Y0; r.Z = Z0;
+    r.rms = NAN; r.ang = NAN;
+    double X, Y, Z;
+    {
+        double a[10];
+        tri_dlt_pass<F32, WAVE>(rt, in, b, e, lane, K, a, r.views);
+        if (r.views < max(2, o.min_views)) return;
+        double w0, w1, w2, w3;
+        smallest_eigenvector4(a, w0, w1, w2, w3);
+        const double nw = sqrt(w0 * w0 + w1 * w1 + w2 * w2 + w3 * w3);
+        r.status = kTriAtInfinity;
+        if (!(fabs(w3) > 1e-12 * nw)) return;                    // (false for a NaN as well)
+        X = w0 / w3; Y = w1 / w3; Z = w2 / w3;
+    }
+    double s[10], mind, maxe;
+    tri_linearise<F32, WAVE>(rt, in, b, e, lane, K, X, Y, Z, s, mind, maxe);
+    if (!(fabs(s[0]) < INFINITY && fabs(X) + fabs(Y) + fabs(Z) < INFINITY)) return;
+    double lam = 0.0;
+    int it = 0;
+#pragma unroll 1
+    while (it < o.max_iter) {
+        const double hd[6] = {s[4] * (1.0 + lam), s[5], s[6], s[7] * (1.0 + lam), s[8], s[9] * (1.0 + lam)};
+        double inv[6];
+        chol3_inverse(hd, inv);
+        const double d0 = -(inv[0] * s[1] + inv[1] * s[2] + inv[2] * s[3]);
+        const double d1 = -(inv[1] * s[1] + inv[3] * s[2] + inv[4] * s[3]);
+        const double d2 = -(inv[2] * s[1] + inv[4] * s[2] + inv[5] * s[3]);
+        const double dn = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+        if (dn <= o.xtol * (sqrt(X * X + Y * Y + Z * Z) + o.xtol)) break;      // the step on offer is below the tolerance already
+        const double Xt = X + d0, Yt = Y + d1, Zt = Z + d2;
+        double st[10], mt, et;
+        tri_linearise<F32, WAVE>(rt, in, b, e, lane, K, Xt, Yt, Zt, st, mt, et);
+        ++it;
+        if (st[0] <= s[0]) {                                     // (a non-finite trial cost is a rejection)
+            X = Xt; Y = Yt; Z = Zt;
+#pragma unroll
+            for (int q = 0; q < 10; ++q) s[q] = st[q];
+            mind = mt; maxe = et;
+            lam = lam > 1e-6 ? 0.1 * lam : 0.0;
+            if (dn <= o.xtol * (sqrt(X * X + Y * Y + Z * Z) + o.xtol)) break;
+        } else {
+            // rejected although the model promised less than 1e-12 of the cost: rounding of the cost's own evaluation
+            // (residuals are differences of pixel coordinates ~1e3) decides such trials, and more damping changes nothing
+            const double gd = s[1] * d0 + s[2] * d1 + s[3] * d2;
+            const double dHd = d0 * (s[4] * d0 + s[5] * d1 + s[6] * d2) + d1 * (s[5] * d0 + s[7] * d1 + s[8] * d2) +
+                               d2 * (s[6] * d0 + s[8] * d1 + s[9] * d2);
+            if (-(gd + 0.5 * dHd) <= 1e-12 * 0.5 * s[0]) break;
+            lam = lam == 0.0 ? 1e-3 : 10.0 * lam;
+        }
+    }
+    r.iters = it;
+    r.rms = sqrt(s[0] / (double)r.views);
+    r.ang = kDeg * tri_widest_angle<WAVE>(rt, in, b, e, lane, X, Y, Z);
+    if (!(r.ang == r.ang)) return;
+    if (mind <= o.min_depth) { r.status = kTriBehind; return; }
+    if (r.ang < o.min_angle_deg) { r.status = kTriLowAngle; return; }
+    if (maxe > o.max_err) { r.status = kTriHighError; return; }
+    r.status = kTriOk;
+    r.X = X; r.Y = Y; r.Z = Z;
+}
+
+template <bool LDS_TAB, bool F32>
+__global__ __launch_bounds__(kTriThreads) void k_triangulate(const double* __restrict__ camtab, TriIn in, int P, int C, KMat K,
+                                                              TriOptions opt, TriOut out) {
+    extern __shared__ __align__(16) double smem[];
+    __shared__ int red[kTriThreads / 64];
+    const int lane = threadIdx.x & 63;
+    const double* __restrict__ rt_global = camtab + cam_rt_offset(C);
+    if (LDS_TAB) {
+        const int n2 = (C * kCamRT) >> 1;
+        const double2* __restrict__ src = reinterpret_cast<const double2*>(rt_global);
+        double2* __restrict__ dst = reinterpret_cast<double2*>(smem);
+        for (int k = threadIdx.x; k < n2; k += blockDim.x) dst[k] = src[k];
+        __syncthreads();
+    }
+    const double* __restrict__ rt = LDS_TAB ? smem : rt_global;
+    int n_ok = 0;
+    for (int base = blockIdx.x * kTriThreads; base < P; base += gridDim.x * kTriThreads) {     // uniform over the workgroup
+        const int p = base + (int)threadIdx.x;
+        int b = 0, e = 0;
+        double X0 = 0.0, Y0 = 0.0, Z0 = 0.0;
+        bool sel = false;
+        if (p < P) {
+            b = in.pt_ptr[p]; e = in.pt_ptr[p + 1];
+            X0 = in.pts[3 * (size_t)p]; Y0 = in.pts[3 * (size_t)p + 1]; Z0 = in.pts[3 * (size_t)p + 2];
+            sel = in.select == nullptr || in.select[p] != 0;
+        }
+        const int n = e - b;
+        TriResult r;
+        r.status = kTriNotSelected; r.views = 0; r.iters = 0;
+        r.X = X0; r.Y = Y0; r.Z = Z0; r.rms = NAN; r.ang = NAN;
+        if (sel && n < kStatsLongTrack) tri_point<F32, false>(rt, in, b, e, 0, K, opt, X0, Y0, Z0, r);
+        // the long runs among this wave's 64 points, one after the other, by the whole wave
+        unsigned long long todo = __ballot(sel && n >= kStatsLongTrack);
+        while (todo) {
+            const int q = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int qb = __shfl(b, q), qe = __shfl(e, q);
+            const double qX = __shfl(X0, q), qY = __shfl(Y0, q), qZ = __shfl(Z0, q);
+            TriResult w;
+            tri_point<F32, true>(rt, in, qb, qe, lane, K, opt, qX, qY, qZ, w);
+            if (lane == q) r = w;
+        }
+        if (p < P) {
+            out.X[3 * (size_t)p] = r.X; out.X[3 * (size_t)p + 1] = r.Y; out.X[3 * (size_t)p + 2] = r.Z;
+            out.status[p] = r.status; out.views[p] = r.views; out.iters[p] = r.iters;
+            out.rms[p] = r.rms; out.angle_deg[p] = r.ang;
+            n_ok += r.status == kTriOk ? 1 : 0;
+        }
+    }
+    // points with status OK of this workgroup: wave sums, added in wave order
+    n_ok = wave_isum(n_ok);
+    if (lane == 0) red[threadIdx.x >> 6] = n_ok;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int k = 0; k < kTriThreads / 64; ++k) t += red[k];
+        out.ok_part[blockIdx.x] = t;
+    }
+}
+
 }  // namespace sfmba

@@ -454,6 +454,13 @@ struct sfmba_handle {
         int64_t perm_N = -1, perm_C = -1;
         PinnedBuf host;                      // staging of the per-observation downloads
     } stats;
+    // sfmba_triangulate: works on stats.x / stats.tab (the parameter vector and camera table of a call outside the
+    // solver) and on result arrays of its own
+    struct Tri {
+        DevBuf use, select;                  // [ld] obs_use in stored order; [P]
+        DevBuf X, ints, dbl, ok_part;        // [P][3]; [3][P] status, views, iters; [2][P] rms err, angle; [workgroups]
+        PinnedBuf host;                      // staging of the two masks and of the workgroups' counts
+    } tri;
 };
 
 namespace {
@@ -2631,6 +2638,26 @@ StatsFilter stats_filter(const sfmba_filter_options& o) {
     return StatsFilter{o.max_error_px, o.min_depth, o.min_angle_deg, (int)o.min_views};
 }
 
+// `reps` back-to-back calls of `launch` on the handle's stream between two events -> average microseconds of one
+int time_reps(sfmba_handle* h, int32_t reps, double* avg_us, const std::function<int()>& launch) {
+    struct EventPair {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    HIPCHK(h, hipEventCreate(&ev.a));
+    HIPCHK(h, hipEventCreate(&ev.b));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventRecord(ev.a, h->stream));
+    for (int k = 0; k < reps; ++k) CHK(launch());
+    HIPCHK(h, hipEventRecord(ev.b, h->stream));
+    HIPCHK(h, hipEventSynchronize(ev.b));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, ev.a, ev.b));
+    *avg_us = 1e3 * (double)ms / reps;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 // sfmba_time_kernel, which = 13 / 14: the per-observation sweep / the per-point reduction at x, default thresholds
 int stats_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t reps, double* avg_us) {
     sfmba_filter_options o;
@@ -2640,27 +2667,112 @@ int stats_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
     CHK(stats_allocate(h, &pt_blocks));
     CHK(stats_prepare(h, x));
     CHK(launch_obs_stats(h, flt));                      // (the reduction's input)
-    struct EventPair {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    HIPCHK(h, hipEventCreate(&ev.a));
-    HIPCHK(h, hipEventCreate(&ev.b));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventRecord(ev.a, h->stream));
-    for (int k = 0; k < reps; ++k) {
-        if (which == 13) CHK(launch_obs_stats(h, flt));
-        else CHK(launch_point_stats(h, flt, pt_blocks));
-    }
-    HIPCHK(h, hipEventRecord(ev.b, h->stream));
-    HIPCHK(h, hipEventSynchronize(ev.b));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, ev.a, ev.b));
-    *avg_us = 1e3 * (double)ms / reps;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return time_reps(h, reps, avg_us, [&] { return which == 13 ? launch_obs_stats(h, flt) : launch_point_stats(h, flt, pt_blocks); });
+}
+
+// ---- triangulation (sfmba_triangulate; kernel: ba_kernels.hpp, "Triangulation") ------------------------------------------
+int tri_allocate(sfmba_handle* h, int* grid) {
+    auto& s = h->stats;
+    auto& t = h->tri;
+    const size_t ldz = (size_t)h->ld, P = (size_t)h->P;
+    *grid = grid_1d(h->P, kTriThreads, h->n_cu);
+    const struct { DevBuf* buf; size_t bytes; } sized[] = {
+        {&s.x, sizeof(double) * (size_t)h->n}, {&s.tab, sizeof(double) * cam_table_doubles((int)h->C)},
+        {&t.use, ldz}, {&t.select, P}, {&t.X, sizeof(double) * 3 * P}, {&t.ints, sizeof(int) * 3 * P},
+        {&t.dbl, sizeof(double) * 2 * P}, {&t.ok_part, sizeof(int) * (size_t)*grid}};
+    for (const auto& b : sized) HIPCHK(h, b.buf->ensure(b.bytes));
     return 0;
 }
+
+TriOptions tri_options(const sfmba_triangulate_options& o) {
+    return TriOptions{(int)o.max_iter, (int)o.min_views, o.xtol, o.min_angle_deg, o.min_depth, o.max_error_px};
+}
+
+// the table of stats_prepare(h, x) must be in place; use / select: the masks are on the device
+int launch_triangulate(sfmba_handle* h, const TriOptions& opt, bool use, bool select, int grid) {
+    auto& s = h->stats;
+    auto& t = h->tri;
+    const size_t P = (size_t)h->P;
+    const bool lds_tab = h->forms.lds_tab;
+    const size_t lds = lds_tab ? (size_t)h->C * kCamRT * sizeof(double) : 0;
+    auto kern = lds_tab ? (h->f32 ? k_triangulate<true, true> : k_triangulate<true, false>)
+                        : (h->f32 ? k_triangulate<false, true> : k_triangulate<false, false>);
+    CHK(set_lds(h, kern, lds));
+    const TriIn in{h->pt_ptr.as<int>(), h->cam_idx.as<int>(), h->uv.as<double>(),
+                   use ? t.use.as<unsigned char>() : nullptr, select ? t.select.as<unsigned char>() : nullptr,
+                   s.x.as<double>() + 6 * h->C};
+    const TriOut out{t.X.as<double>(), t.ints.as<int>(), t.ints.as<int>() + P, t.ints.as<int>() + 2 * P,
+                     t.dbl.as<double>(), t.dbl.as<double>() + P, t.ok_part.as<int>()};
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kTriThreads), lds, h->stream, (const double*)s.tab.as<double>(), in, (int)h->P,
+                       (int)h->C, h->K, opt, out);
+    LAUNCHED(h);
+    return 0;
+}
+
+// sfmba_time_kernel, which = 15: k_triangulate at x over every point and observation, default options
+int tri_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us) {
+    sfmba_triangulate_options o;
+    sfmba_default_triangulate_options(&o);
+    const TriOptions opt = tri_options(o);
+    int grid = 1;
+    CHK(tri_allocate(h, &grid));
+    CHK(stats_prepare(h, x));
+    return time_reps(h, reps, avg_us, [&] { return launch_triangulate(h, opt, false, false, grid); });
+}
 }  // namespace
+
+void sfmba_default_triangulate_options(sfmba_triangulate_options* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->max_iter = 10; o->min_views = 2; o->xtol = 1e-10; o->min_angle_deg = 1.0; o->min_depth = 0.0; o->max_error_px = INFINITY;
+}
+
+int sfmba_triangulate(sfmba_handle* h, const double* x, const uint8_t* pt_select, const uint8_t* obs_use,
+                      const sfmba_triangulate_options* opt, double* X_out, int32_t* pt_status, int32_t* pt_views,
+                      int32_t* pt_iters, double* pt_rms_err, double* pt_angle_deg, int64_t* n_ok) {
+    CHK(enter(h));
+    CHK(begin_compute(h, x));
+    sfmba_triangulate_options o;
+    if (opt) o = *opt; else sfmba_default_triangulate_options(&o);
+    if (std::isnan(o.xtol) || std::isnan(o.min_angle_deg) || std::isnan(o.min_depth) || std::isnan(o.max_error_px))
+        return fail(h, -1, "an option of sfmba_triangulate is NaN");
+    auto& t = h->tri;
+    const size_t N = (size_t)h->N, P = (size_t)h->P;
+    int grid = 1;
+    CHK(tri_allocate(h, &grid));
+    CHK(stats_prepare(h, x));
+    // the masks: obs_use into stored order (h->order: stored position -> caller's), both through pinned staging
+    const size_t off_sel = (N + 63) / 64 * 64, off_ok = off_sel + (P + 63) / 64 * 64;
+    HIPCHK(h, t.host.ensure(off_ok + sizeof(int) * (size_t)grid, 0));
+    unsigned char* const st = t.host.as<unsigned char>();
+    if (obs_use && N) {
+        for (size_t k = 0; k < N; ++k) st[k] = obs_use[h->permuted ? (size_t)h->order[k] : k] ? 1 : 0;
+        HIPCHK(h, hipMemcpyAsync(t.use.p, st, N, hipMemcpyHostToDevice, h->stream));
+    }
+    if (pt_select && P) {
+        for (size_t p = 0; p < P; ++p) st[off_sel + p] = pt_select[p] ? 1 : 0;
+        HIPCHK(h, hipMemcpyAsync(t.select.p, st + off_sel, P, hipMemcpyHostToDevice, h->stream));
+    }
+    CHK(launch_triangulate(h, tri_options(o), obs_use != nullptr, pt_select != nullptr, grid));
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+    };
+    const int* pi = t.ints.as<int>();
+    HIPCHK(h, down(X_out, t.X.p, sizeof(double) * 3 * P));
+    HIPCHK(h, down(pt_status, pi, sizeof(int32_t) * P));
+    HIPCHK(h, down(pt_views, pi + P, sizeof(int32_t) * P));
+    HIPCHK(h, down(pt_iters, pi + 2 * P, sizeof(int32_t) * P));
+    HIPCHK(h, down(pt_rms_err, t.dbl.p, sizeof(double) * P));
+    HIPCHK(h, down(pt_angle_deg, t.dbl.as<double>() + P, sizeof(double) * P));
+    int* const st_ok = reinterpret_cast<int*>(st + off_ok);
+    if (n_ok) HIPCHK(h, down(st_ok, t.ok_part.p, sizeof(int) * (size_t)grid));
+    CHK(wait_stream(h));
+    if (n_ok) {
+        *n_ok = 0;
+        for (int k = 0; k < grid; ++k) *n_ok += st_ok[k];
+    }
+    return 0;
+}
 
 void sfmba_default_filter_options(sfmba_filter_options* o) {
     if (!o) return;
@@ -2904,6 +3016,7 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
     CHK(begin_compute(h, x));
     if (!avg_us || reps <= 0) return fail(h, -1, "bad reps / avg_us");
     if (which == 13 || which == 14) return stats_time_kernel(h, x, which, reps, avg_us);
+    if (which == 15) return tri_time_kernel(h, x, reps, avg_us);
     int np = 0;
     CHK(linearise_at(h, x, which >= 2));
     if (which >= 2) {

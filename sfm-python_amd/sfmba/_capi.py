@@ -22,6 +22,7 @@ SYMBOLS = (
     "sfmba_p2p_calls", "sfmba_tr2d_solve", "sfmba_debug_option", "sfmba_set_print", "sfmba_get_counters", "sfmba_problem_reuse", "sfmba_dense_schur",
     "sfmba_get_pcg_history", "sfmba_set_fixed_cameras", "sfmba_step_products", "sfmba_get_form",
     "sfmba_default_filter_options", "sfmba_reprojection_stats",
+    "sfmba_default_triangulate_options", "sfmba_triangulate",
 )
 
 
@@ -50,6 +51,11 @@ class FilterOptions(C.Structure):
 class StatsSummary(C.Structure):
     _fields_ = [("n_obs", C.c_int64), ("n_obs_kept", C.c_int64), ("n_points_kept", C.c_int64),
                 ("n_behind", C.c_int64), ("sum_err", C.c_double), ("sum_err2", C.c_double), ("max_err", C.c_double)]
+
+
+class TriangulateOptions(C.Structure):
+    _fields_ = [("max_iter", C.c_int32), ("min_views", C.c_int32), ("xtol", C.c_double), ("min_angle_deg", C.c_double),
+                ("min_depth", C.c_double), ("max_error_px", C.c_double)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -133,6 +139,11 @@ def load():
         lib.sfmba_default_filter_options.restype = None
         lib.sfmba_reprojection_stats.argtypes = [P, P, C.POINTER(FilterOptions)] + [P] * 13 + [C.POINTER(StatsSummary)]
         lib.sfmba_reprojection_stats.restype = C.c_int
+    if hasattr(lib, "sfmba_triangulate"):            # (likewise)
+        lib.sfmba_default_triangulate_options.argtypes = [C.POINTER(TriangulateOptions)]
+        lib.sfmba_default_triangulate_options.restype = None
+        lib.sfmba_triangulate.argtypes = [P, P, P, P, C.POINTER(TriangulateOptions)] + [P] * 6 + [C.POINTER(C.c_int64)]
+        lib.sfmba_triangulate.restype = C.c_int
     lib.sfmba_tr2d_solve.argtypes = [P, P, C.c_double, P]
     lib.sfmba_comm_get_unique_id.argtypes = [P]
     lib.sfmba_comm_init.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int64]

@@ -62,6 +62,27 @@ class ReprojectionStats:
         return "ReprojectionStats(" + ", ".join(f"{k}={v!r}" for k, v in self.summary().items()) + ")"
 
 
+class Triangulation:
+    """What `Backend.triangulate` returns (include/sfmba.h: sfmba_triangulate).  ``points`` (P, 3): the new point where
+    ``status`` is 0, else the point of ``x``; ``status`` (P) one of the ``Triangulation.OK .. HIGH_ERROR`` codes, -1 for a
+    point that was not selected; ``views``, ``iters`` (P, int32); ``rms_err`` (pixels) and ``angle_deg`` (P), NaN where
+    the point did not get that far; ``n_ok`` the number of status-0 points."""
+
+    NOT_SELECTED, OK, FEW_VIEWS, AT_INFINITY, BEHIND, LOW_ANGLE, HIGH_ERROR = -1, 0, 1, 2, 3, 4, 5
+
+    def __init__(self, points, status, views, iters, rms_err, angle_deg, n_ok):
+        self.points, self.status, self.views, self.iters = points, status, views, iters
+        self.rms_err, self.angle_deg, self.n_ok = rms_err, angle_deg, int(n_ok)
+
+    @property
+    def ok(self):
+        """Boolean mask of the points that came back with a new position."""
+        return self.status == self.OK
+
+    def __repr__(self):
+        return f"Triangulation(n_points={len(self.status)}, n_ok={self.n_ok})"
+
+
 class Backend:
     """One MI355X.  Not thread-safe; use one Backend per thread (include/sfmba.h, Threading)."""
 
@@ -311,6 +332,42 @@ class Backend:
             if name in arrays:
                 arrays[name] = arrays[name].view(np.bool_)
         return ReprojectionStats(arrays, summary)
+
+    def triangulate(self, x, select=None, obs_use=None, **options):
+        """Triangulate the selected points of the current problem from their used observations and the cameras of ``x``:
+        n-view DLT, then Gauss-Newton on the reprojection error, then a verdict per point (include/sfmba.h:
+        sfmba_triangulate).  ``select`` (P) and ``obs_use`` (N, the caller's observation order): boolean masks, None = all.
+        ``options``: fields of ``sfmba_triangulate_options`` (max_iter, min_views, xtol, min_angle_deg, min_depth,
+        max_error_px).  -> :class:`Triangulation`."""
+        self._flush_pending()
+        x = _f64(x, (self.n_params,), "x")
+        opt = _capi.TriangulateOptions()
+        self._lib.sfmba_default_triangulate_options(C.byref(opt))
+        names = {f[0]: f[1] for f in _capi.TriangulateOptions._fields_}
+        for key, value in options.items():
+            if key not in names:
+                raise TypeError(f"unknown triangulation option {key!r} (known: {sorted(names)})")
+            setattr(opt, key, int(value) if names[key] is C.c_int32 else float(value))
+
+        def mask(a, n, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a).ravel() != 0, dtype=np.uint8)
+            if a.shape[0] != n:
+                raise ValueError(f"{name} has {a.shape[0]} entries, expected {n}")
+            return a
+
+        P = self.n_points
+        sel, use = mask(select, P, "select"), mask(obs_use, self.n_obs, "obs_use")
+        points = np.empty((P, 3))
+        status, views, iters = (np.empty(P, dtype=np.int32) for _ in range(3))
+        rms, ang = np.empty(P), np.empty(P)
+        n_ok = C.c_int64()
+        self._check(self._lib.sfmba_triangulate(
+            self._h, _capi.ptr(x), _capi.ptr(sel) if sel is not None else None,
+            _capi.ptr(use) if use is not None else None, C.byref(opt), _capi.ptr(points), _capi.ptr(status),
+            _capi.ptr(views), _capi.ptr(iters), _capi.ptr(rms), _capi.ptr(ang), C.byref(n_ok)))
+        return Triangulation(points, status, views, iters, rms, ang, n_ok.value)
 
     def residual_jacobian(self, x):
         self._flush_pending()

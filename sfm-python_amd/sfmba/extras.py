@@ -97,8 +97,56 @@ def prune_problem(x, args, obs_keep, pt_keep):
     return x2, args2, obs_index, point_index
 
 
+def triangulate_tracks(x, args, select=None, obs_use=None, device=0, backend=None, **options):
+    """`Backend.triangulate` in one call on the reference's ``args`` tuple (sfm.py:268): every selected point from all its
+    used observations and the cameras of ``x`` -- n-view DLT, Gauss-Newton on the reprojection error, a verdict per point
+    -- by one kernel on the device.  ``options``: the fields of ``sfmba_triangulate_options``.
+    -> :class:`sfmba.Triangulation`."""
+    be = _backend_with_problem(args, device, backend)
+    return be.triangulate(x, select=select, obs_use=obs_use, **options)
+
+
+def _cameras_from_projection(M, K):
+    """``[R | t] = K^-1 M`` -> (rotation vector, centre ``T = -R^T t``), the six camera parameters of the
+    bundle-adjustment model.  Raises ValueError when ``R`` is not a rotation to within 1e-6."""
+    M = np.asarray(M, dtype=np.float64)
+    if M.shape != (3, 4):
+        raise ValueError(f"a projection matrix has shape (3, 4), got {M.shape}")
+    Rt = np.linalg.solve(np.asarray(K, dtype=np.float64), M)
+    R, t = Rt[:, :3], Rt[:, 3]
+    if not (np.all(np.isfinite(R)) and np.abs(R.T @ R - np.eye(3)).max() <= 1e-6 and abs(np.linalg.det(R) - 1.0) <= 1e-6):
+        raise ValueError("K^-1 M[:, :3] is not a rotation to within 1e-6: M is not K [R | t] for this K")
+    return np.concatenate([api._rotvec_from_matrix(R), -R.T @ t])
+
+
+def triangulate_points(M1, M2, pts1, pts2, K, device=0, backend=None):
+    """``cv2.triangulatePoints(M1, M2, pts1, pts2)`` as the reference calls it (sfm.py:140, 218): ``(3, 4)`` projection
+    matrices ``K [R | t]`` and ``(2, N)`` pixels -> ``(4, N)`` homogeneous points with last row 1.  The linear stage of
+    :func:`triangulate_tracks` alone (no refinement, no angle, depth or error test) on a two-camera problem built from
+    ``[R | t] = K^-1 M``; a point at infinity comes back as a NaN column.  ``K`` is needed because the device model holds
+    rotations, not general 3x4 matrices."""
+    if np.shape(K) != (3, 3):
+        raise ValueError("K must be (3, 3)")
+    cams = np.concatenate([_cameras_from_projection(M1, K), _cameras_from_projection(M2, K)])
+    pts1, pts2 = np.asarray(pts1, dtype=np.float64), np.asarray(pts2, dtype=np.float64)
+    if pts1.ndim != 2 or pts1.shape[0] != 2 or pts1.shape != pts2.shape:
+        raise ValueError(f"pts1 and pts2 must both be (2, N), got {pts1.shape} and {pts2.shape}")
+    n = pts1.shape[1]
+    out = np.ones((4, n))
+    if n == 0:
+        return out
+    uv = np.stack([pts1.T, pts2.T], axis=1).reshape(2 * n, 2)            # point-major: (view 1, view 2) per point
+    ci = np.tile(np.array([0, 1], dtype=np.int64), n)
+    pi = np.repeat(np.arange(n, dtype=np.int64), 2)
+    be = _backend_with_problem((2, n, ci, pi, uv, K), device, backend)
+    tri = be.triangulate(np.concatenate([cams, np.zeros(3 * n)]), max_iter=0, min_views=2, min_angle_deg=-np.inf,
+                         min_depth=-np.inf, max_error_px=np.inf)
+    out[:3] = np.where(tri.ok[None, :], tri.points.T, np.nan)
+    return out
+
+
 def refine_reconstruction(x0, args, rounds=2, max_error_px=4.0, min_depth=0.0, min_angle_deg=2.0, min_views=2,
-                          device=0, backend=None, **least_squares_kwargs):
+                          device=0, backend=None, retriangulate=False, **least_squares_kwargs):
     """The trim loop around bundle adjustment: solve, measure, drop, solve again.
 
     Every round solves the current problem with :func:`sfmba.least_squares` (``least_squares_kwargs`` are passed on;
@@ -108,7 +156,15 @@ def refine_reconstruction(x0, args, rounds=2, max_error_px=4.0, min_depth=0.0, m
     surviving problem with the parameters at the last solve's ``x``; the surviving rows' positions in the ORIGINAL
     arrays, composed over all rounds; per round a dict with ``n_obs``, ``n_points`` (solved), ``n_obs_kept``,
     ``n_points_kept``, ``mean_error_px``, ``rms_error_px``, ``max_error_px`` (over the kept set) and ``rmse`` (the
-    solve's, over everything it was given)."""
+    solve's, over everything it was given).
+
+    ``retriangulate=True`` gives the points a round would drop a second chance before it drops them: every such point
+    with at least ``max(2, min_views)`` observations is triangulated anew (:meth:`Backend.triangulate`, same four
+    thresholds) from its observations that pass their own test -- from all its observations when fewer than
+    ``min_views`` pass, the case of a point that is itself misplaced while its pixels are fine.  A point that comes back
+    ``OK`` takes its new coordinates, the statistics are taken again at the updated ``x``, and the pruning follows those:
+    the point stays, observations of it that still fail are dropped.  Each summary then carries
+    ``n_points_retriangulated``, the points rescued in that round."""
     if rounds < 1:
         raise ValueError("rounds must be at least 1")
     kw = dict(x_scale="jac", method="trf")
@@ -125,13 +181,29 @@ def refine_reconstruction(x0, args, rounds=2, max_error_px=4.0, min_depth=0.0, m
         # (the handle holds exactly this problem: statistics straight on it, in the solve's storage precision)
         st = be.reprojection_stats(result.x, max_error_px=max_error_px, min_depth=min_depth, min_angle_deg=min_angle_deg,
                                    min_views=min_views, want=("obs", "points"))
+        x = result.x
+        n_retriangulated = 0
+        if retriangulate and st.n_points_kept < int(args[1]):
+            pidx = np.asarray(args[3]).ravel()
+            own = (st.obs_err <= max_error_px) & np.isfinite(st.obs_err) & (st.obs_depth > min_depth)
+            need = max(2, int(min_views))
+            cand = ~st.pt_keep & (np.bincount(pidx, minlength=int(args[1])) >= need)
+            if cand.any():
+                tri = be.triangulate(x, select=cand, obs_use=own | (st.pt_views < need)[pidx], min_views=min_views,
+                                     min_angle_deg=min_angle_deg, min_depth=min_depth, max_error_px=max_error_px)
+                n_retriangulated = tri.n_ok
+                if n_retriangulated:
+                    x = np.concatenate([x[:6 * int(args[0])], tri.points.ravel()])
+                    st = be.reprojection_stats(x, max_error_px=max_error_px, min_depth=min_depth,
+                                               min_angle_deg=min_angle_deg, min_views=min_views, want=("obs", "points"))
         summaries.append(dict(n_obs=st.n_obs, n_points=int(args[1]), n_obs_kept=st.n_obs_kept,
                               n_points_kept=st.n_points_kept, mean_error_px=st.mean_error_px,
                               rms_error_px=st.rms_error_px, max_error_px=st.max_err, rmse=float(result.rmse)))
-        x = result.x
+        if retriangulate:
+            summaries[-1]["n_points_retriangulated"] = int(n_retriangulated)
         if st.n_obs_kept == st.n_obs and st.n_points_kept == int(args[1]):
             break
-        x, args, oi, pi = prune_problem(result.x, args, st.obs_keep, st.pt_keep)
+        x, args, oi, pi = prune_problem(x, args, st.obs_keep, st.pt_keep)
         obs_index, point_index = obs_index[oi], point_index[pi]
     return result, (x, args), (obs_index, point_index), summaries
 

@@ -15,6 +15,8 @@ of /root/reference/sfm_lite/sfm.py:266-268).  No reference source is written any
     python tools/gen_golden.py --shard cfg5 8   #   cfg5: under a minute)
     python tools/gen_golden.py --growing  # scipy + the reference residual on a 2 -> 11 camera growing reconstruction
     python tools/gen_golden.py --fixed    # scipy + the reference's pattern with fixed_camera_indices (seconds)
+    python tools/gen_golden.py --triangulate   # the reference's two-view DLT on synthetic pixel pairs, and the bounds of
+                                          #   the triangulation tests (seconds)
     python tools/gen_golden.py --params   # gauge-aligned parameter distance oracle <-> scipy on every stored scipy x
                                           #   (re-runs the last growing stage with scipy: ~4 min)
 """
@@ -488,6 +490,73 @@ def param_bounds(ba):
                        scipy_version=__import__("scipy").__version__, rows=rows), f, indent=1)
 
 
+REF_TRI = "/root/reference/cv2_lite/triangulate_points.py"
+TRI_BOUND_FACTOR = 100.0       # fused multiply-adds, the Jacobi rotation order and summation order of the kernel
+
+
+def triangulate_cases():
+    """tests/golden/triangulate_cases.npz: K_SCEAUX, two synthetic camera matrices, 100 noisy pixel pairs and the output
+    of the reference's `triangulate_points_linear2` on them; tests/golden/triangulate_bounds.json: the distance of the
+    numpy restatement (tests/triangulate_ref.py) to the reference on that set, and to the SVD of the same rows on the
+    tracks of the GPU tests' problem, each with the bound (x TRI_BOUND_FACTOR) the kernel is held to.  Data only."""
+    spec = importlib.util.spec_from_file_location("ref_tri", REF_TRI)
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    for p in (ROOT, os.path.join(ROOT, "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import triangulate_ref as tr
+    from sfmba.synthetic import K_SCEAUX
+
+    rng = np.random.default_rng(2024)
+    n = 100
+    cams = np.array([[0.03, -0.12, 0.02, -0.6, 0.1, 0.2], [-0.05, 0.15, -0.04, 0.7, -0.2, -0.1]])
+    M = tr.projection_matrices(cams.ravel(), 2, K_SCEAUX)
+    X = rng.normal(0.0, 1.0, (n, 3)) + np.array([0.0, 0.0, 10.0])
+    Xh = np.hstack([X, np.ones((n, 1))])
+    pts = []
+    for k in range(2):
+        p = Xh @ M[k].T
+        pts.append((p[:, :2] / p[:, 2:3] + rng.normal(0.0, 0.5, (n, 2))).T.copy())
+    X_ref = ref.triangulate_points_linear2(M[0], M[1], pts[0], pts[1])
+    np.savez_compressed(os.path.join(OUT, "triangulate_cases.npz"), K=K_SCEAUX, M1=M[0], M2=M[1], pts1=pts[0],
+                        pts2=pts[1], X_ref=X_ref)
+
+    # the restatement on the fixture, through the same K^-1 M -> (rotation vector, centre) route the library takes
+    c2 = np.concatenate([tr.cameras_from_projection(M[0], K_SCEAUX), tr.cameras_from_projection(M[1], K_SCEAUX)])
+    uv = np.stack([pts[0].T, pts[1].T], axis=1).reshape(2 * n, 2)
+    args = (2, n, np.tile([0, 1], n), np.repeat(np.arange(n), 2), uv, K_SCEAUX)
+    lin = tr.triangulate(np.concatenate([c2, np.zeros(3 * n)]), args, max_iter=0, min_angle_deg=-np.inf,
+                         min_depth=-np.inf)["linear"]
+    d_fix = float(np.abs(lin - X_ref[:3].T).max())
+
+    # ... and on the tracks of the GPU tests' problem against the SVD of the same rows
+    pb = make_problem(6, 300, 1500, seed=3)
+    C, P, ci, pi, uv, K = pb.args
+    full = tr.triangulate(pb.x_true, pb.args, max_iter=0)
+    Mc = tr.projection_matrices(pb.x_true, C, K)
+    order, ptr = tr.stored_runs(pi, P)
+    cams = pb.x_true[:6 * C].reshape(C, 6)
+    d_pb, n_cmp, n_two = 0.0, 0, 0
+    for p in range(P):
+        idx = order[ptr[p]:ptr[p + 1]]
+        if len(idx) < 2:
+            continue
+        n_two += 1
+        Xs = tr.svd_point(tr.dlt_rows(Mc[ci[idx]], uv[idx]))
+        if tr.widest_angle_deg(Xs, cams[ci[idx], 3:]) < 2.0:
+            continue
+        n_cmp += 1
+        d_pb = max(d_pb, float(np.abs(full["linear"][p] - Xs).max() / max(1.0, np.abs(Xs).max())))
+    rec = dict(factor=TRI_BOUND_FACTOR,
+               fixture=dict(measured_abs=d_fix, bound_abs=TRI_BOUND_FACTOR * d_fix),
+               problem=dict(spec=[6, 300, 1500, 3], tracks_two_views=n_two, tracks_compared=n_cmp,
+                            measured_rel=d_pb, bound_rel=TRI_BOUND_FACTOR * d_pb))
+    with open(os.path.join(OUT, "triangulate_bounds.json"), "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg2", action="store_true")
@@ -496,7 +565,11 @@ def main():
     ap.add_argument("--growing", action="store_true")
     ap.add_argument("--fixed", action="store_true")
     ap.add_argument("--params", action="store_true")
+    ap.add_argument("--triangulate", action="store_true")
     a = ap.parse_args()
+    if a.triangulate:
+        triangulate_cases()
+        return
     if a.full:                                   # oracle only: needs no reference
         os.makedirs(OUT, exist_ok=True)
         oracle_full(a.full)
