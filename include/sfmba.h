@@ -311,6 +311,56 @@ int  sfmba_triangulate(sfmba_handle* h, const double* x, const uint8_t* pt_selec
                        int32_t* pt_iters /* P */, double* pt_rms_err /* P */, double* pt_angle_deg /* P */,
                        int64_t* n_ok);
 
+/* ---- resection: n-point DLT plus pose refinement ------------------------------------------------ */
+/* What registers a camera: its pose from its observations of known points.  The reference calls cv2.solvePnP per new
+ * camera (sfm.py:207-208; its teaching restatement is cv2_lite/solve_pnp.py); this call resects every selected camera
+ * of the current problem from ALL its used observations and the points of x[6C:], in one kernel (k_resect), one
+ * workgroup per camera.  The cameras of x are read only for start = 1 and to fill cam_out where no new pose is returned.
+ *
+ * Per selected camera, over its used observations in camera-major stored order:
+ *   linear stage  (start = 0) _solve_pnp_linear (solve_pnp.py:18-43): pixels normalised by K^-1, rows [P, 0, -u P] and
+ *                 [0, P, -v P] with P = (X, Y, Z, 1), nothing translated or rescaled; A^T A from forty sums, its smallest
+ *                 eigenvector h by cyclic Jacobi rotations on the 12x12 matrix (pairs (0,1), (0,2), .., (10,11), until
+ *                 the off-diagonal part is 1e-40 of the diagonal, at most 30 sweeps); h = [M | m], R = M (M^T M)^(-1/2)
+ *                 (the reference's U V^T), R and m negated when det M < 0.  Unlike the reference, which takes t = m of the
+ *                 unit-norm h, t = m / s with s the mean singular value of M: the reference's unscaled t is only a poor
+ *                 start.  T = -R^T t, omega from R through a quaternion.
+ *   refinement    (max_iter > 0) Gauss-Newton on 1/2 sum |r|^2 over the six parameters (omega, T), r the residual of
+ *                 sfmba_residuals and its 2x6 block.  Damping (H + lambda diag H, from zero; 1e-3, then x10 after a
+ *                 rejected trial, x0.1 after an accepted one), the rejection of a trial pose that raises the cost (a
+ *                 non-finite cost counts as raised) and the stops are those of sfmba_triangulate, with |p| the norm of
+ *                 the six parameters: the result never costs more than the start pose.  cam_iters counts trial poses.
+ *   verdict       at the result, first match wins (cam_status):
+ *                   1 FEW_VIEWS   fewer used observations than max(min_views, 6) (start = 0) / max(min_views, 3) (start = 1)
+ *                   2 DEGENERATE  anything non-finite, or (start = 0) the second-smallest eigenvalue of A^T A is at most
+ *                                 1e-12 of the largest (coplanar points: the null space has more than one dimension)
+ *                   3 BEHIND      a used observation has depth <= min_depth
+ *                   4 HIGH_ERROR  sqrt(sum |r|^2 / views) over the used observations is above max_rms_px
+ *                   0 OK          otherwise;            -1: the camera was not selected
+ * cam_out (C,6): the new pose for status 0, the camera of x for every other status.  cam_views: used observations, for
+ * every selected camera (else 0).  cam_iters and cam_rms_err are those of the result for every camera that got past
+ * DEGENERATE; else 0, NaN.  n_ok: cameras with status 0.
+ *
+ * cam_select (C) and obs_use (N, the caller's observation order): nonzero = take part; NULL = all.  Any output pointer may
+ * be NULL; an array that is not asked for is not downloaded.  opt = NULL: the defaults.  Returns -1 when no problem is
+ * set, x is NULL, an option is NaN, the handle waits for its transport, or the handle holds a shard (a camera's
+ * observations are spread over the ranks).  Pixels are read as stored (fp64 or fp32); every buffer is the call's own or
+ * the statistics call's, so fun, grad, the PCG record and a following solve are exactly what a fresh handle gives; no
+ * atomics, sums in a fixed order: same input, same bits. */
+typedef struct sfmba_resect_options {
+    int32_t max_iter;    /* refinement trials after the start pose; 0 = start pose only (default 20) */
+    int32_t min_views;   /* used observations a camera needs; below 6 counts as 6 when start = 0, below 3 as 3 when start = 1 (default 6) */
+    int32_t start;       /* 0 = linear stage (DLT), 1 = the camera's pose in x (pose-only refinement) */
+    double  xtol;        /* stop when a step has |d| <= xtol (|p| + xtol), p the six parameters (1e-10) */
+    double  min_depth;   /* every used observation must have depth > this at the result (0.0) */
+    double  max_rms_px;  /* rms reprojection error over the used observations at the result (default +inf) */
+} sfmba_resect_options;
+void sfmba_default_resect_options(sfmba_resect_options* opt);
+int  sfmba_resect(sfmba_handle* h, const double* x, const uint8_t* cam_select /* C or NULL = all */,
+                  const uint8_t* obs_use /* N, caller's order, or NULL = all */, const sfmba_resect_options* opt,
+                  double* cam_out /* (C,6): omega, centre T, the BA model's parameters */, int32_t* cam_status,
+                  int32_t* cam_views, int32_t* cam_iters, double* cam_rms_err, int64_t* n_ok);
+
 /* ---- least_squares(method='trf', x_scale='jac') (sfm.py:266-268) ---------------------------- */
 /* x_inout: x0 on entry, result.x on success (untouched on failure). */
 int  sfmba_solve(sfmba_handle* h, double* x_inout, const sfmba_options* opt, sfmba_result* out);
@@ -329,7 +379,8 @@ int  sfmba_get_fun_grad(sfmba_handle* h, double* fun_out, double* grad_out);
  *        10 a streaming-store fill of the Jacobian buffer (ceiling probe),
  *        11 k_jdot and 12 k_backsub (without its PCG prologue) in the form the problem has selected ("rc_consumers"),
  *        13 the per-observation sweep and 14 the per-point reduction of sfmba_reprojection_stats (default options),
- *        15 k_triangulate of sfmba_triangulate over every point and observation (default options).
+ *        15 k_triangulate of sfmba_triangulate over every point and observation (default options),
+ *        16 k_resect of sfmba_resect over every camera and observation (default options).
  * avg_us: average duration of one repetition. */
 int  sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t reps, double* avg_us);
 /* Normal-equation blocks at x: U (C,21 upper triangle row-major), V (P,6 upper), gc (C,6), gp (P,3). */

@@ -5091,4 +5091,475 @@ __global__ __launch_bounds__(kTriThreads) void k_triangulate(const double* __res
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Resection (sfmba_resect): per selected camera, over its used observations in camera-major stored
+// order (the permutation of stats_cam_perm),
+//   linear stage  the n-point DLT of the reference's _solve_pnp_linear: pixels normalised by K^-1, rows [P, 0, -u P],
+//                 [0, P, -v P] with P = (X, Y, Z, 1), A^T A from forty sums (S, S_u, S_v, S_w, each a symmetric 4x4), its
+//                 smallest eigenvector by cyclic Jacobi rotations on the 12x12 matrix in LDS (one wave, lane r owns row
+//                 r; pairs (0,1), (0,2), ..., (0,11), (1,2), ..., (10,11)), h = [M | m], R = M (M^T M)^(-1/2) by a 3x3
+//                 Jacobi, t = m / (mean singular value of M), both negated when det M < 0, T = -R^T t, omega through a
+//                 quaternion
+//   refinement    damped Gauss-Newton on 1/2 sum |r|^2 over (omega, T): r and the 2x6 block from observe<true>, the
+//                 trial pose's table row made by thread 0 (cam_row_values) and shared through LDS; one pass over the
+//                 slice per trial pose, which yields its cost and the next linearisation.  Damping, rejection and the
+//                 stops are k_triangulate's.
+//   verdict       at the result: used observations, finiteness / the gap of A^T A, smallest depth, rms error
+// One 256-thread workgroup per camera, on the shape of k_cam_stats: thread t takes entries t, t + 256, ... of the slice,
+// kResectUnroll gathers in flight (entry -> stored position -> pixel, point index -> point); partial sums are combined
+// by wave_sum and then over the waves in wave order (block_sum): same input, same bits.  Every decision is taken by
+// thread 0 and handed to the workgroup through LDS.  No atomics; nothing of the solver's is read but the structure
+// arrays and the pixels.
+// ---------------------------------------------------------------------------------------------
+constexpr int kResectUnroll = 4;
+constexpr int kResectSweeps = 30;    // cap of the Jacobi sweeps of the 12x12 matrix (it converges in 6..10)
+constexpr int kResOk = 0, kResFewViews = 1, kResDegenerate = 2, kResBehind = 3, kResHighError = 4, kResNotSelected = -1;
+struct ResectOptions { int max_iter, min_views, start; double xtol, min_depth, max_rms; };
+struct ResectIn {
+    const int* __restrict__ cam_ptr;             // [C + 1] slices of perm
+    const int* __restrict__ perm;                // camera-major position -> stored position
+    const int* __restrict__ pt_idx;              // [N] stored order
+    const double* __restrict__ uv;
+    const unsigned char* __restrict__ use;       // [N] stored order, or null: every observation
+    const unsigned char* __restrict__ select;    // [C], or null: every camera
+    const double* __restrict__ x;                // the parameter vector: 6C camera parameters, then the points
+};
+struct ResectOut {
+    double* __restrict__ cam;                    // [C][6]
+    int* __restrict__ status;
+    int* __restrict__ views;
+    int* __restrict__ iters;
+    double* __restrict__ rms;
+    int* __restrict__ ok_part;                   // [C] 1 where the status is OK
+};
+struct ResectObs { double X, Y, Z, u, v; bool on; };
+
+// entries j0, j0 + 256, ... of the slice [.., e): all index loads, then all pixel / point-index loads, then the points
+template <bool F32>
+__device__ __forceinline__ void resect_gather(const ResectIn& in, const double* __restrict__ pts, int j0, int e,
+                                              ResectObs (&o)[kResectUnroll]) {
+    int idx[kResectUnroll], p[kResectUnroll];
+#pragma unroll
+    for (int u = 0; u < kResectUnroll; ++u) { const int j = j0 + u * kCamThreads; idx[u] = j < e ? in.perm[j] : -1; }
+    if (in.use != nullptr) {
+        unsigned char f[kResectUnroll];
+#pragma unroll
+        for (int u = 0; u < kResectUnroll; ++u) f[u] = idx[u] >= 0 ? in.use[idx[u]] : 0;
+#pragma unroll
+        for (int u = 0; u < kResectUnroll; ++u) if (!f[u]) idx[u] = -1;
+    }
+#pragma unroll
+    for (int u = 0; u < kResectUnroll; ++u) {
+        o[u].on = idx[u] >= 0;
+        p[u] = 0; o[u].u = 0.0; o[u].v = 0.0;
+        if (o[u].on) { p[u] = in.pt_idx[idx[u]]; const double2 q = load_pair(in.uv, F32, idx[u]); o[u].u = q.x; o[u].v = q.y; }
+    }
+#pragma unroll
+    for (int u = 0; u < kResectUnroll; ++u) {
+        o[u].X = 0.0; o[u].Y = 0.0; o[u].Z = 1.0;
+        if (o[u].on) { const double* __restrict__ Xp = pts + 3 * (size_t)p[u]; o[u].X = Xp[0]; o[u].Y = Xp[1]; o[u].Z = Xp[2]; }
+    }
+}
+
+// the linear stage's pass: v = S (10) | S_u (10) | S_v (10) | S_w (10), upper triangles row by row; thread 0 leaves with
+// the workgroup's sums and the number of used observations
+template <bool F32>
+__device__ __forceinline__ void resect_dlt_pass(const ResectIn& in, const double* __restrict__ pts, int b, int e, const KMat& Kinv,
+                                                double (&v)[40], int& used, double* red, int* redi) {
+#pragma unroll
+    for (int q = 0; q < 40; ++q) v[q] = 0.0;
+    used = 0;
+#pragma unroll 1
+    for (int j0 = b + (int)threadIdx.x; j0 < e; j0 += kCamThreads * kResectUnroll) {
+        ResectObs o[kResectUnroll];
+        resect_gather<F32>(in, pts, j0, e, o);
+#pragma unroll
+        for (int u = 0; u < kResectUnroll; ++u) {
+            if (!o[u].on) continue;
+            const double un = Kinv.k[0] * o[u].u + Kinv.k[1] * o[u].v + Kinv.k[2];
+            const double vn = Kinv.k[3] * o[u].u + Kinv.k[4] * o[u].v + Kinv.k[5];
+            const double w2 = un * un + vn * vn;
+            const double P[4] = {o[u].X, o[u].Y, o[u].Z, 1.0};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = i; j < 4; ++j) {
+                    const double pp = P[i] * P[j];
+                    v[sym4(i, j)] += pp;
+                    v[10 + sym4(i, j)] += un * pp;
+                    v[20 + sym4(i, j)] += vn * pp;
+                    v[30 + sym4(i, j)] += w2 * pp;
+                }
+            ++used;
+        }
+    }
+    used = wave_isum(used);
+    if ((threadIdx.x & 63) == 0) redi[threadIdx.x >> 6] = used;
+    block_sum<40>(v, red);
+    if (threadIdx.x == 0) {
+        used = 0;
+        for (int k = 0; k < kCamWaves; ++k) used += redi[k];
+    }
+}
+
+// one pass at the pose of the table row tl: s[0] = sum |r|^2, s[1..6] = sum Jc^T r, s[7..27] = sum Jc^T Jc (upper, row by
+// row); thread 0 leaves with the workgroup's sums, the smallest depth and the number of used observations
+template <bool F32>
+__device__ __forceinline__ void resect_linearise(const ResectIn& in, const double* __restrict__ pts, int b, int e, const KMat& K,
+                                                 const double* __restrict__ tl, double (&s)[28], double& mind, int& used,
+                                                 double* red, double* redm, int* redi) {
+#pragma unroll
+    for (int q = 0; q < 28; ++q) s[q] = 0.0;
+    mind = INFINITY;
+    used = 0;
+#pragma unroll 1
+    for (int j0 = b + (int)threadIdx.x; j0 < e; j0 += kCamThreads * kResectUnroll) {
+        ResectObs o[kResectUnroll];
+        resect_gather<F32>(in, pts, j0, e, o);
+#pragma unroll
+        for (int u = 0; u < kResectUnroll; ++u) {
+            if (!o[u].on) continue;
+            double jc[12], jp[6], rx, ry;
+            observe<true>(tl, o[u].X, o[u].Y, o[u].Z, o[u].u, o[u].v, K, rx, ry, jc, jp);
+            const double depth = tl[6] * (o[u].X - tl[9]) + tl[7] * (o[u].Y - tl[10]) + tl[8] * (o[u].Z - tl[11]);
+            s[0] += rx * rx + ry * ry;
+            int n = 7;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                s[1 + a] += jc[a] * rx + jc[6 + a] * ry;
+#pragma unroll
+                for (int c = a; c < 6; ++c) s[n++] += jc[a] * jc[c] + jc[6 + a] * jc[6 + c];
+            }
+            mind = fmin(mind, depth);
+            ++used;
+        }
+    }
+    mind = wave_min(mind);
+    used = wave_isum(used);
+    if ((threadIdx.x & 63) == 0) { redm[threadIdx.x >> 6] = mind; redi[threadIdx.x >> 6] = used; }
+    block_sum<28>(s, red);
+    if (threadIdx.x == 0) {
+        used = 0; mind = INFINITY;
+        for (int k = 0; k < kCamWaves; ++k) { used += redi[k]; mind = fmin(mind, redm[k]); }
+    }
+}
+
+// Cyclic Jacobi on the symmetric 12x12 matrix A (full storage, LDS), eigenvectors in the columns of V, by ONE wave: lane
+// r < 12 owns row r of both.  The LDS operations of one wave execute in program order (volatile keeps the compiler to it):
+// within a rotation every lane reads before any lane writes.
+__device__ __forceinline__ void resect_jacobi12(volatile double* A, volatile double* V, int lane) {
+#pragma unroll 1
+    for (int sweep = 0; sweep < kResectSweeps; ++sweep) {
+        double off = 0.0, dia = 0.0;
+        if (lane < 12) {
+            for (int j = lane + 1; j < 12; ++j) off += fabs(A[12 * lane + j]);
+            dia = fabs(A[13 * lane]);
+        }
+        off = wave_sum(off);
+        dia = wave_sum(dia);
+        if (!(off > 1e-40 * dia)) break;                         // (a NaN ends the loop too)
+#pragma unroll 1
+        for (int p = 0; p < 11; ++p)
+#pragma unroll 1
+            for (int q = p + 1; q < 12; ++q) {
+                const double app = A[13 * p], aqq = A[13 * q], apq = A[12 * p + q];
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = apq == 0.0 ? 0.0 : copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                double arp = 0.0, arq = 0.0, vrp = 0.0, vrq = 0.0;
+                if (lane < 12) { arp = A[12 * lane + p]; arq = A[12 * lane + q]; vrp = V[12 * lane + p]; vrq = V[12 * lane + q]; }
+                if (lane < 12) {
+                    V[12 * lane + p] = c * vrp - s * vrq;
+                    V[12 * lane + q] = s * vrp + c * vrq;
+                    if (lane == p) { A[13 * p] = app - t * apq; A[12 * p + q] = 0.0; }
+                    else if (lane == q) { A[13 * q] = aqq + t * apq; A[12 * q + p] = 0.0; }
+                    else {
+                        const double n1 = c * arp - s * arq, n2 = s * arp + c * arq;
+                        A[12 * lane + p] = n1; A[12 * p + lane] = n1;
+                        A[12 * lane + q] = n2; A[12 * q + lane] = n2;
+                    }
+                }
+            }
+    }
+}
+
+__host__ __device__ constexpr int sym3(int i, int j) { return i <= j ? (i == 0 ? j : i + j + 1) : (j == 0 ? i : i + j + 1); }
+template <int P, int Q>
+__device__ __forceinline__ void jacobi3_rotate(double (&a)[6], double (&v)[9]) {
+    const double apq = a[sym3(P, Q)];
+    const double theta = (a[sym3(Q, Q)] - a[sym3(P, P)]) / (2.0 * apq);
+    const double t = apq == 0.0 ? 0.0 : copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    a[sym3(P, P)] -= t * apq;
+    a[sym3(Q, Q)] += t * apq;
+    a[sym3(P, Q)] = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        if (r != P && r != Q) {
+            const double arp = a[sym3(r, P)], arq = a[sym3(r, Q)];
+            a[sym3(r, P)] = c * arp - s * arq;
+            a[sym3(r, Q)] = s * arp + c * arq;
+        }
+        const double vrp = v[3 * r + P], vrq = v[3 * r + Q];
+        v[3 * r + P] = c * vrp - s * vrq;
+        v[3 * r + Q] = s * vrp + c * vrq;
+    }
+}
+
+// h = [M | m] (rows of 4) -> the six parameters (omega, T) of the pose R = M (M^T M)^(-1/2), t = m / s, T = -R^T t
+__device__ __forceinline__ void resect_pose_from_h(const double (&h)[12], double (&prm)[6]) {
+    double M[9], m[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) M[3 * i + j] = h[4 * i + j];
+        m[i] = h[4 * i + 3];
+    }
+    const double det = M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
+    if (det < 0.0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) M[k] = -M[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) m[k] = -m[k];
+    }
+    double a[6], w[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) a[sym3(i, j)] = M[i] * M[j] + M[3 + i] * M[3 + j] + M[6 + i] * M[6 + j];
+#pragma unroll 1
+    for (int sweep = 0; sweep < kTriSweeps; ++sweep) {
+        const double off = fabs(a[1]) + fabs(a[2]) + fabs(a[4]);
+        const double dia = fabs(a[0]) + fabs(a[3]) + fabs(a[5]);
+        if (!(off > 1e-40 * dia)) break;
+        jacobi3_rotate<0, 1>(a, w); jacobi3_rotate<0, 2>(a, w); jacobi3_rotate<1, 2>(a, w);
+    }
+    const double s0 = sqrt(a[0]), s1 = sqrt(a[3]), s2 = sqrt(a[5]);
+    const double i0 = 1.0 / s0, i1 = 1.0 / s1, i2 = 1.0 / s2;
+    const double scale = (s0 + s1 + s2) / 3.0;
+    double Bi[9];                                                // (M^T M)^(-1/2) = W diag(1 / sigma) W^T
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Bi[3 * i + j] = w[3 * i] * i0 * w[3 * j] + w[3 * i + 1] * i1 * w[3 * j + 1] + w[3 * i + 2] * i2 * w[3 * j + 2];
+    double R[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) R[3 * i + j] = M[3 * i] * Bi[j] + M[3 * i + 1] * Bi[3 + j] + M[3 * i + 2] * Bi[6 + j];
+    const double t0 = m[0] / scale, t1 = m[1] / scale, t2 = m[2] / scale;
+    prm[3] = -(R[0] * t0 + R[3] * t1 + R[6] * t2);
+    prm[4] = -(R[1] * t0 + R[4] * t1 + R[7] * t2);
+    prm[5] = -(R[2] * t0 + R[5] * t1 + R[8] * t2);
+    // rotation vector through the quaternion, the largest component first (angles near 0 and near pi are both safe)
+    const double tr = R[0] + R[4] + R[8];
+    double qw, qx, qy, qz;
+    if (tr > 0.0) {
+        const double s = sqrt(tr + 1.0) * 2.0;
+        qw = 0.25 * s; qx = (R[7] - R[5]) / s; qy = (R[2] - R[6]) / s; qz = (R[3] - R[1]) / s;
+    } else if (R[0] > R[4] && R[0] > R[8]) {
+        const double s = sqrt(1.0 + R[0] - R[4] - R[8]) * 2.0;
+        qw = (R[7] - R[5]) / s; qx = 0.25 * s; qy = (R[1] + R[3]) / s; qz = (R[2] + R[6]) / s;
+    } else if (R[4] > R[8]) {
+        const double s = sqrt(1.0 + R[4] - R[0] - R[8]) * 2.0;
+        qw = (R[2] - R[6]) / s; qx = (R[1] + R[3]) / s; qy = 0.25 * s; qz = (R[5] + R[7]) / s;
+    } else {
+        const double s = sqrt(1.0 + R[8] - R[0] - R[4]) * 2.0;
+        qw = (R[3] - R[1]) / s; qx = (R[2] + R[6]) / s; qy = (R[5] + R[7]) / s; qz = 0.25 * s;
+    }
+    if (qw < 0.0) { qw = -qw; qx = -qx; qy = -qy; qz = -qz; }
+    const double n = sqrt(qx * qx + qy * qy + qz * qz);
+    const double f = n < 1e-12 ? 2.0 : 2.0 * atan2(n, qw) / n;
+    prm[0] = qx * f; prm[1] = qy * f; prm[2] = qz * f;
+}
+
+template <bool F32>
+__global__ __launch_bounds__(kCamThreads) void k_resect(ResectIn in, int C, KMat K, KMat Kinv, ResectOptions opt, ResectOut out) {
+    __shared__ double red[kCamWaves * 40];
+    __shared__ double redm[kCamWaves];
+    __shared__ int redi[kCamWaves];
+    __shared__ __align__(16) double row[kCamRow];
+    __shared__ double jA[144], jV[144];
+    __shared__ int ctl;
+    __shared__ double s[28], p[6];                               // thread 0's: the accepted pose and its sums
+    const int c = blockIdx.x;
+    const int b = in.cam_ptr[c], e = in.cam_ptr[c + 1];
+    const double* __restrict__ pts = in.x + 6 * (size_t)C;
+    const bool first = threadIdx.x == 0;
+    if (first) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) p[k] = in.x[6 * (size_t)c + k];
+    }
+    // what thread 0 reports: the camera of x unless the status becomes OK
+    int status = kResNotSelected, views = 0, iters = 0;
+    double rms = NAN;
+    auto report = [&](bool ok) {
+        if (!first) return;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) out.cam[6 * (size_t)c + k] = ok ? p[k] : in.x[6 * (size_t)c + k];
+        out.status[c] = status; out.views[c] = views; out.iters[c] = iters; out.rms[c] = rms;
+        out.ok_part[c] = ok ? 1 : 0;
+    };
+    if (in.select != nullptr && !in.select[c]) { report(false); return; }          // (uniform over the workgroup)
+    const int need = max(opt.min_views, opt.start == 0 ? 6 : 3);
+    if (first) { row[kCamTab] = 0.0; ctl = 1; }
+    if (opt.start == 0) {
+        {
+            double v[40];
+            resect_dlt_pass<F32>(in, pts, b, e, Kinv, v, views, red, redi);
+            if (first) {
+                // A^T A = [[S, 0, -S_u], [0, S, -S_v], [-S_u, -S_v, S_w]], V = I
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int q = sym4(i, j);
+                        jA[12 * i + j] = v[q];           jA[12 * i + 4 + j] = 0.0;        jA[12 * i + 8 + j] = -v[10 + q];
+                        jA[12 * (4 + i) + j] = 0.0;      jA[12 * (4 + i) + 4 + j] = v[q]; jA[12 * (4 + i) + 8 + j] = -v[20 + q];
+                        jA[12 * (8 + i) + j] = -v[10 + q]; jA[12 * (8 + i) + 4 + j] = -v[20 + q]; jA[12 * (8 + i) + 8 + j] = v[30 + q];
+                    }
+                for (int k = 0; k < 144; ++k) jV[k] = (k % 13) == 0 ? 1.0 : 0.0;
+            }
+        }
+        if (threadIdx.x < 64) {                                  // wave 0: thread 0's stores above are its own
+            resect_jacobi12(jA, jV, (int)threadIdx.x);
+            if (first) {
+                status = kResFewViews;
+                bool go = views >= need;
+                if (go) {
+                    status = kResDegenerate;
+                    const volatile double* vA = jA;
+                    const volatile double* vV = jV;
+                    int lo = 0;
+                    double hi = vA[0];
+                    for (int k = 1; k < 12; ++k) { if (vA[13 * k] < vA[13 * lo]) lo = k; hi = fmax(hi, vA[13 * k]); }
+                    double second = INFINITY;
+                    for (int k = 0; k < 12; ++k) if (k != lo) second = fmin(second, vA[13 * k]);
+                    go = second > 1e-12 * hi;                    // (false for a NaN as well)
+                    double hv[12];
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) hv[k] = vV[12 * k + lo];
+                    resect_pose_from_h(hv, p);
+                    double sum = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) sum += fabs(p[k]);
+                    go = go && sum < INFINITY;
+                    if (go) cam_row_values(p, row);
+                }
+                ctl = go ? 1 : 0;
+            }
+        }
+    } else if (first) {
+        cam_row_values(p, row);
+    }
+    __syncthreads();
+    if (!ctl) { report(false); return; }
+    // refinement: thread 0 holds the accepted pose p, its sums s and smallest depth, the damping and the step on trial
+    // (the accepted sums live in LDS: with the trial's 28 in registers beside the 6x6 factorisation the kernel spilled)
+    double mind = INFINITY, lam = 0.0, d[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, dn = 0.0;
+    bool have = false;
+#pragma unroll 1
+    for (;;) {
+        double tl[kCamRow];
+        {
+            const double2* __restrict__ r2 = reinterpret_cast<const double2*>(row);
+#pragma unroll
+            for (int k = 0; k < kCamRow / 2; ++k) { const double2 q = r2[k]; tl[2 * k] = q.x; tl[2 * k + 1] = q.y; }
+        }
+        double st[28], mt;
+        int used;
+        resect_linearise<F32>(in, pts, b, e, K, tl, st, mt, used, red, redm, redi);
+        if (first) {
+            bool stop = false;
+            if (!have) {                                         // the start pose
+                have = true;
+                views = used;
+#pragma unroll
+                for (int q = 0; q < 28; ++q) s[q] = st[q];
+                mind = mt;
+                double sum = fabs(s[0]);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) sum += fabs(p[k]);
+                if (views < need) { status = kResFewViews; stop = true; }
+                else if (!(sum < INFINITY)) { status = kResDegenerate; stop = true; }
+                else status = kResOk;
+            } else {
+                ++iters;
+                if (st[0] <= s[0]) {                             // (a non-finite trial cost is a rejection)
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) p[k] += d[k];
+#pragma unroll
+                    for (int q = 0; q < 28; ++q) s[q] = st[q];
+                    mind = mt;
+                    lam = lam > 1e-6 ? 0.1 * lam : 0.0;
+                    double pn = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) pn += p[k] * p[k];
+                    if (dn <= opt.xtol * (sqrt(pn) + opt.xtol)) stop = true;
+                } else {
+                    // rejected although the model promised less than 1e-12 of the cost (see tri_point)
+                    double gd = 0.0, dHd = 0.0;
+                    int n = 7;
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) {
+                        gd += s[1 + a] * d[a];
+#pragma unroll
+                        for (int q = a; q < 6; ++q) { dHd += (q == a ? 1.0 : 2.0) * s[n] * d[a] * d[q]; ++n; }
+                    }
+                    if (-(gd + 0.5 * dHd) <= 1e-12 * 0.5 * s[0]) stop = true;
+                    lam = lam == 0.0 ? 1e-3 : 10.0 * lam;
+                }
+            }
+            if (!stop && iters >= opt.max_iter) stop = true;
+            if (!stop) {
+                double A[6][6], inv[21];
+                int n = 7;
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int q = a; q < 6; ++q) { A[a][q] = A[q][a] = q == a ? s[n] * (1.0 + lam) : s[n]; ++n; }
+                spd6_inverse(A, inv);
+                double full[6][6];
+                n = 0;
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int q = a; q < 6; ++q) { full[a][q] = full[q][a] = inv[n]; ++n; }
+                double pn = 0.0;
+                dn = 0.0;
+#pragma unroll
+                for (int a = 0; a < 6; ++a) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) t += full[a][q] * s[1 + q];
+                    d[a] = -t;
+                    dn += t * t;
+                    pn += p[a] * p[a];
+                }
+                dn = sqrt(dn);
+                if (dn <= opt.xtol * (sqrt(pn) + opt.xtol)) stop = true;       // the step on offer is below the tolerance already
+                else {
+                    double pt[6];
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) pt[k] = p[k] + d[k];
+                    cam_row_values(pt, row);
+                }
+            }
+            ctl = stop ? 0 : 1;
+        }
+        __syncthreads();
+        if (!ctl) break;
+    }
+    if (first && status == kResOk) {
+        rms = sqrt(s[0] / (double)views);
+        double sum = fabs(rms) + fabs(mind);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) sum += fabs(p[k]);
+        if (!(sum < INFINITY)) status = kResDegenerate;
+        else if (mind <= opt.min_depth) status = kResBehind;
+        else if (rms > opt.max_rms) status = kResHighError;
+    }
+    report(status == kResOk);
+}
+
 }  // namespace sfmba

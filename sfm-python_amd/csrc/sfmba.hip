@@ -461,6 +461,13 @@ struct sfmba_handle {
         DevBuf X, ints, dbl, ok_part;        // [P][3]; [3][P] status, views, iters; [2][P] rms err, angle; [workgroups]
         PinnedBuf host;                      // staging of the two masks and of the workgroups' counts
     } tri;
+    // sfmba_resect: works on stats.x (the parameter vector of a call outside the solver), the camera-major permutation
+    // of the statistics call, and on result arrays of its own
+    struct Resect {
+        DevBuf use, select;                  // [ld] obs_use in stored order; [C]
+        DevBuf cam, ints, rms;               // [C][6]; [4][C] status, views, iters, ok; [C]
+        PinnedBuf host;                      // staging of the two masks and of the cameras' counts
+    } resect;
 };
 
 namespace {
@@ -2774,6 +2781,123 @@ int sfmba_triangulate(sfmba_handle* h, const double* x, const uint8_t* pt_select
     return 0;
 }
 
+namespace {
+// ---- resection (sfmba_resect; kernel: ba_kernels.hpp, "Resection") ----------------------------------------------------------
+int resect_allocate(sfmba_handle* h) {
+    auto& r = h->resect;
+    const size_t ldz = (size_t)h->ld, C = (size_t)h->C;
+    const struct { DevBuf* buf; size_t bytes; } sized[] = {
+        {&h->stats.x, sizeof(double) * (size_t)h->n}, {&r.use, ldz}, {&r.select, C}, {&r.cam, sizeof(double) * 6 * C},
+        {&r.ints, sizeof(int) * 4 * C}, {&r.rms, sizeof(double) * C}};
+    for (const auto& b : sized) HIPCHK(h, b.buf->ensure(b.bytes));
+    return 0;
+}
+
+ResectOptions resect_options(const sfmba_resect_options& o) {
+    return ResectOptions{(int)o.max_iter, (int)o.min_views, o.start != 0 ? 1 : 0, o.xtol, o.min_depth, o.max_rms_px};
+}
+
+// K^-1 by the adjugate (the pixels of the linear stage are normalised with it)
+KMat inverse_k(const KMat& K) {
+    const double* k = K.k;
+    const double c00 = k[4] * k[8] - k[5] * k[7], c01 = k[5] * k[6] - k[3] * k[8], c02 = k[3] * k[7] - k[4] * k[6];
+    const double det = k[0] * c00 + k[1] * c01 + k[2] * c02;
+    KMat inv;
+    inv.k[0] = c00 / det; inv.k[1] = (k[2] * k[7] - k[1] * k[8]) / det; inv.k[2] = (k[1] * k[5] - k[2] * k[4]) / det;
+    inv.k[3] = c01 / det; inv.k[4] = (k[0] * k[8] - k[2] * k[6]) / det; inv.k[5] = (k[2] * k[3] - k[0] * k[5]) / det;
+    inv.k[6] = c02 / det; inv.k[7] = (k[1] * k[6] - k[0] * k[7]) / det; inv.k[8] = (k[0] * k[4] - k[1] * k[3]) / det;
+    return inv;
+}
+
+// x must be in stats.x and the permutation of stats_cam_perm(h) in place; use / select: the masks are on the device
+int launch_resect(sfmba_handle* h, const ResectOptions& opt, bool use, bool select) {
+    auto& s = h->stats;
+    auto& r = h->resect;
+    const size_t C = (size_t)h->C;
+    if (C == 0) return 0;
+    const ResectIn in{s.cam_ptr.as<int>(), s.perm.as<int>(), h->pt_idx.as<int>(), h->uv.as<double>(),
+                      use ? r.use.as<unsigned char>() : nullptr, select ? r.select.as<unsigned char>() : nullptr,
+                      s.x.as<double>()};
+    const ResectOut out{r.cam.as<double>(), r.ints.as<int>(), r.ints.as<int>() + C, r.ints.as<int>() + 2 * C,
+                        r.rms.as<double>(), r.ints.as<int>() + 3 * C};
+    auto kern = h->f32 ? k_resect<true> : k_resect<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)C), dim3(kCamThreads), 0, h->stream, in, (int)h->C, h->K, inverse_k(h->K), opt, out);
+    LAUNCHED(h);
+    return 0;
+}
+
+int resect_check_single(sfmba_handle* h) {
+    if (multi_rank(h) || h->N_total != h->N)
+        return fail(h, -1, "sfmba_resect needs every observation of a camera: this handle holds a shard of the problem");
+    return 0;
+}
+
+// sfmba_time_kernel, which = 16: k_resect at x over every camera and observation, default options
+int resect_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us) {
+    sfmba_resect_options o;
+    sfmba_default_resect_options(&o);
+    const ResectOptions opt = resect_options(o);
+    CHK(resect_check_single(h));
+    CHK(resect_allocate(h));
+    CHK(upload_x(h, x, h->stats.x.as<double>()));
+    CHK(stats_cam_perm(h));
+    return time_reps(h, reps, avg_us, [&] { return launch_resect(h, opt, false, false); });
+}
+}  // namespace
+
+void sfmba_default_resect_options(sfmba_resect_options* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->max_iter = 20; o->min_views = 6; o->start = 0; o->xtol = 1e-10; o->min_depth = 0.0; o->max_rms_px = INFINITY;
+}
+
+int sfmba_resect(sfmba_handle* h, const double* x, const uint8_t* cam_select, const uint8_t* obs_use,
+                 const sfmba_resect_options* opt, double* cam_out, int32_t* cam_status, int32_t* cam_views,
+                 int32_t* cam_iters, double* cam_rms_err, int64_t* n_ok) {
+    CHK(enter(h));
+    CHK(begin_compute(h, x));
+    sfmba_resect_options o;
+    if (opt) o = *opt; else sfmba_default_resect_options(&o);
+    if (std::isnan(o.xtol) || std::isnan(o.min_depth) || std::isnan(o.max_rms_px))
+        return fail(h, -1, "an option of sfmba_resect is NaN");
+    CHK(resect_check_single(h));
+    auto& r = h->resect;
+    const size_t N = (size_t)h->N, C = (size_t)h->C;
+    CHK(resect_allocate(h));
+    CHK(upload_x(h, x, h->stats.x.as<double>()));
+    CHK(stats_cam_perm(h));
+    // the masks: obs_use into stored order (h->order: stored position -> caller's), both through pinned staging
+    const size_t off_sel = (N + 63) / 64 * 64, off_ok = off_sel + (C + 63) / 64 * 64;
+    HIPCHK(h, r.host.ensure(off_ok + sizeof(int) * C, 0));
+    unsigned char* const st = r.host.as<unsigned char>();
+    if (obs_use && N) {
+        for (size_t k = 0; k < N; ++k) st[k] = obs_use[h->permuted ? (size_t)h->order[k] : k] ? 1 : 0;
+        HIPCHK(h, hipMemcpyAsync(r.use.p, st, N, hipMemcpyHostToDevice, h->stream));
+    }
+    if (cam_select && C) {
+        for (size_t c = 0; c < C; ++c) st[off_sel + c] = cam_select[c] ? 1 : 0;
+        HIPCHK(h, hipMemcpyAsync(r.select.p, st + off_sel, C, hipMemcpyHostToDevice, h->stream));
+    }
+    CHK(launch_resect(h, resect_options(o), obs_use != nullptr, cam_select != nullptr));
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+    };
+    const int* pi = r.ints.as<int>();
+    HIPCHK(h, down(cam_out, r.cam.p, sizeof(double) * 6 * C));
+    HIPCHK(h, down(cam_status, pi, sizeof(int32_t) * C));
+    HIPCHK(h, down(cam_views, pi + C, sizeof(int32_t) * C));
+    HIPCHK(h, down(cam_iters, pi + 2 * C, sizeof(int32_t) * C));
+    HIPCHK(h, down(cam_rms_err, r.rms.p, sizeof(double) * C));
+    int* const st_ok = reinterpret_cast<int*>(st + off_ok);
+    if (n_ok) HIPCHK(h, down(st_ok, pi + 3 * C, sizeof(int) * C));
+    CHK(wait_stream(h));
+    if (n_ok) {
+        *n_ok = 0;
+        for (size_t c = 0; c < C; ++c) *n_ok += st_ok[c];
+    }
+    return 0;
+}
+
 void sfmba_default_filter_options(sfmba_filter_options* o) {
     if (!o) return;
     memset(o, 0, sizeof *o);
@@ -3017,6 +3141,7 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
     if (!avg_us || reps <= 0) return fail(h, -1, "bad reps / avg_us");
     if (which == 13 || which == 14) return stats_time_kernel(h, x, which, reps, avg_us);
     if (which == 15) return tri_time_kernel(h, x, reps, avg_us);
+    if (which == 16) return resect_time_kernel(h, x, reps, avg_us);
     int np = 0;
     CHK(linearise_at(h, x, which >= 2));
     if (which >= 2) {

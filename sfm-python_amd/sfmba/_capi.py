@@ -23,6 +23,7 @@ SYMBOLS = (
     "sfmba_get_pcg_history", "sfmba_set_fixed_cameras", "sfmba_step_products", "sfmba_get_form",
     "sfmba_default_filter_options", "sfmba_reprojection_stats",
     "sfmba_default_triangulate_options", "sfmba_triangulate",
+    "sfmba_default_resect_options", "sfmba_resect",
 )
 
 
@@ -56,6 +57,11 @@ class StatsSummary(C.Structure):
 class TriangulateOptions(C.Structure):
     _fields_ = [("max_iter", C.c_int32), ("min_views", C.c_int32), ("xtol", C.c_double), ("min_angle_deg", C.c_double),
                 ("min_depth", C.c_double), ("max_error_px", C.c_double)]
+
+
+class ResectOptions(C.Structure):
+    _fields_ = [("max_iter", C.c_int32), ("min_views", C.c_int32), ("start", C.c_int32), ("xtol", C.c_double),
+                ("min_depth", C.c_double), ("max_rms_px", C.c_double)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -144,6 +150,11 @@ def load():
         lib.sfmba_default_triangulate_options.restype = None
         lib.sfmba_triangulate.argtypes = [P, P, P, P, C.POINTER(TriangulateOptions)] + [P] * 6 + [C.POINTER(C.c_int64)]
         lib.sfmba_triangulate.restype = C.c_int
+    if hasattr(lib, "sfmba_resect"):                 # (likewise)
+        lib.sfmba_default_resect_options.argtypes = [C.POINTER(ResectOptions)]
+        lib.sfmba_default_resect_options.restype = None
+        lib.sfmba_resect.argtypes = [P, P, P, P, C.POINTER(ResectOptions)] + [P] * 5 + [C.POINTER(C.c_int64)]
+        lib.sfmba_resect.restype = C.c_int
     lib.sfmba_tr2d_solve.argtypes = [P, P, C.c_double, P]
     lib.sfmba_comm_get_unique_id.argtypes = [P]
     lib.sfmba_comm_init.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int64]

@@ -83,6 +83,27 @@ class Triangulation:
         return f"Triangulation(n_points={len(self.status)}, n_ok={self.n_ok})"
 
 
+class Resection:
+    """What `Backend.resect` returns (include/sfmba.h: sfmba_resect).  ``cameras`` (C, 6): the new pose (rotation vector,
+    centre -- the bundle-adjustment model's parameters) where ``status`` is 0, else the camera of ``x``; ``status`` (C)
+    one of the ``Resection.OK .. HIGH_ERROR`` codes, -1 for a camera that was not selected; ``views``, ``iters`` (C,
+    int32); ``rms_err`` (pixels), NaN where the camera did not get that far; ``n_ok`` the number of status-0 cameras."""
+
+    NOT_SELECTED, OK, FEW_VIEWS, DEGENERATE, BEHIND, HIGH_ERROR = -1, 0, 1, 2, 3, 4
+
+    def __init__(self, cameras, status, views, iters, rms_err, n_ok):
+        self.cameras, self.status, self.views, self.iters = cameras, status, views, iters
+        self.rms_err, self.n_ok = rms_err, int(n_ok)
+
+    @property
+    def ok(self):
+        """Boolean mask of the cameras that came back with a new pose."""
+        return self.status == self.OK
+
+    def __repr__(self):
+        return f"Resection(n_cameras={len(self.status)}, n_ok={self.n_ok})"
+
+
 class Backend:
     """One MI355X.  Not thread-safe; use one Backend per thread (include/sfmba.h, Threading)."""
 
@@ -368,6 +389,42 @@ class Backend:
             _capi.ptr(use) if use is not None else None, C.byref(opt), _capi.ptr(points), _capi.ptr(status),
             _capi.ptr(views), _capi.ptr(iters), _capi.ptr(rms), _capi.ptr(ang), C.byref(n_ok)))
         return Triangulation(points, status, views, iters, rms, ang, n_ok.value)
+
+    def resect(self, x, select=None, obs_use=None, **options):
+        """Resect the selected cameras of the current problem from their used observations and the points of ``x``:
+        n-point DLT (or, ``start=1``, the camera's pose in ``x``), then Gauss-Newton on the reprojection error over the
+        six pose parameters, then a verdict per camera (include/sfmba.h: sfmba_resect).  ``select`` (C) and ``obs_use``
+        (N, the caller's observation order): boolean masks, None = all.  ``options``: fields of ``sfmba_resect_options``
+        (max_iter, min_views, start, xtol, min_depth, max_rms_px).  -> :class:`Resection`."""
+        self._flush_pending()
+        x = _f64(x, (self.n_params,), "x")
+        opt = _capi.ResectOptions()
+        self._lib.sfmba_default_resect_options(C.byref(opt))
+        names = {f[0]: f[1] for f in _capi.ResectOptions._fields_}
+        for key, value in options.items():
+            if key not in names:
+                raise TypeError(f"unknown resection option {key!r} (known: {sorted(names)})")
+            setattr(opt, key, int(value) if names[key] is C.c_int32 else float(value))
+
+        def mask(a, n, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a).ravel() != 0, dtype=np.uint8)
+            if a.shape[0] != n:
+                raise ValueError(f"{name} has {a.shape[0]} entries, expected {n}")
+            return a
+
+        Cn = self.n_cameras
+        sel, use = mask(select, Cn, "select"), mask(obs_use, self.n_obs, "obs_use")
+        cameras = np.empty((Cn, 6))
+        status, views, iters = (np.empty(Cn, dtype=np.int32) for _ in range(3))
+        rms = np.empty(Cn)
+        n_ok = C.c_int64()
+        self._check(self._lib.sfmba_resect(
+            self._h, _capi.ptr(x), _capi.ptr(sel) if sel is not None else None,
+            _capi.ptr(use) if use is not None else None, C.byref(opt), _capi.ptr(cameras), _capi.ptr(status),
+            _capi.ptr(views), _capi.ptr(iters), _capi.ptr(rms), C.byref(n_ok)))
+        return Resection(cameras, status, views, iters, rms, n_ok.value)
 
     def residual_jacobian(self, x):
         self._flush_pending()

@@ -106,6 +106,38 @@ def triangulate_tracks(x, args, select=None, obs_use=None, device=0, backend=Non
     return be.triangulate(x, select=select, obs_use=obs_use, **options)
 
 
+def resect_cameras(x, args, select=None, obs_use=None, device=0, backend=None, **options):
+    """`Backend.resect` in one call on the reference's ``args`` tuple (sfm.py:268): every selected camera from all its used
+    observations and the points of ``x`` -- n-point DLT, Gauss-Newton on the reprojection error over the pose, a verdict
+    per camera -- by one kernel on the device.  ``options``: the fields of ``sfmba_resect_options``.
+    -> :class:`sfmba.Resection`."""
+    be = _backend_with_problem(args, device, backend)
+    return be.resect(x, select=select, obs_use=obs_use, **options)
+
+
+def solve_pnp(point3ds, point2ds, K, dist=None, device=0, backend=None, **options):
+    """``cv2.solvePnP(point3ds, point2ds, K, dist)`` as the reference calls it (sfm.py:207-208): ``(N, 3)`` points and
+    ``(N, 2)`` pixels -> ``(success, rvec (3, 1), tvec (3, 1))`` in OpenCV's ``x_cam = R X + t`` convention.  A one-camera
+    problem through :func:`resect_cameras`: ``success`` is ``status == OK``, and a pose that is not OK comes back as NaN.
+    The device model has no lens distortion: a non-zero ``dist`` raises ValueError.  ``options``: the fields of
+    ``sfmba_resect_options`` (``max_iter=0`` gives the linear stage alone)."""
+    if dist is not None and np.any(np.asarray(dist, dtype=np.float64) != 0.0):
+        raise ValueError("solve_pnp supports no lens distortion: dist must be None or all zeros")
+    point3ds = np.ascontiguousarray(point3ds, dtype=np.float64)
+    point2ds = np.ascontiguousarray(point2ds, dtype=np.float64)
+    n = len(point3ds)
+    if point3ds.shape != (n, 3) or point2ds.shape != (n, 2) or np.shape(K) != (3, 3):
+        raise ValueError("expected point3ds (N,3), point2ds (N,2), K (3,3)")
+    x = np.concatenate([np.zeros(6), point3ds.ravel()])
+    res = resect_cameras(x, (1, n, np.zeros(n, dtype=np.int64), np.arange(n, dtype=np.int64), point2ds, K),
+                         device=device, backend=backend, **options)
+    if not res.ok[0]:
+        return False, np.full((3, 1), np.nan), np.full((3, 1), np.nan)
+    w, T = res.cameras[0, :3], res.cameras[0, 3:]
+    R = api._matrix_from_rotvec(w)
+    return True, w.reshape(3, 1).copy(), (-R @ T).reshape(3, 1)
+
+
 def _cameras_from_projection(M, K):
     """``[R | t] = K^-1 M`` -> (rotation vector, centre ``T = -R^T t``), the six camera parameters of the
     bundle-adjustment model.  Raises ValueError when ``R`` is not a rotation to within 1e-6."""
