@@ -121,11 +121,15 @@ __device__ __forceinline__ double quad_sum(double v) {        // sum over the fo
     v += dpp_double<0x4E>(v);                                  // quad_perm [2,3,0,1]
     return v;
 }
-__device__ __forceinline__ double wave_max(double v) {
+// The xor butterfly over the wave with any commutative operator: the same bits on every lane.  (A sum by it adds in
+// another order than wave_sum.)
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce_xor(T v, Op op) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
     return v;
 }
+__device__ __forceinline__ double wave_max(double v) { return wave_reduce_xor(v, [](double a, double b) { return fmax(a, b); }); }
 
 // Block-wide sum of NQ values per thread; result valid on thread 0.  `red` holds >= 16*NQ doubles.
 template <int NQ>
@@ -1369,12 +1373,16 @@ struct Recompute {
     const double* __restrict__ pts;      // [P][3]
     KMat K;
 };
-__device__ __forceinline__ void stage_cam_table(const double* __restrict__ camtab, int C, double* __restrict__ smem) {
-    const int n2 = (C * kCamRow) >> 1;
-    const double2* __restrict__ src = reinterpret_cast<const double2*>(camtab);
+// n doubles (n even, both ends 16-byte aligned) into LDS by the whole workgroup, 16 bytes per lane; ends with a barrier
+__device__ __forceinline__ void stage_table(const double* __restrict__ tab, int n, double* __restrict__ smem) {
+    const int n2 = n >> 1;
+    const double2* __restrict__ src = reinterpret_cast<const double2*>(tab);
     double2* __restrict__ dst = reinterpret_cast<double2*>(smem);
     for (int k = threadIdx.x; k < n2; k += blockDim.x) dst[k] = src[k];
     __syncthreads();
+}
+__device__ __forceinline__ void stage_cam_table(const double* __restrict__ camtab, int C, double* __restrict__ smem) {
+    stage_table(camtab, C * kCamRow, smem);
 }
 __device__ __forceinline__ void recompute_blocks(const Recompute& rc, const double* __restrict__ tab_lds, int c, int p,
                                                  double* jc, double* jp) {
@@ -4374,1192 +4382,6 @@ __global__ __launch_bounds__(256) void k_zero_many(ZeroJob z) {
 __global__ __launch_bounds__(1024) void k_fill16(double* __restrict__ a, int64_t n2, double v) {
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n2; e += (int64_t)gridDim.x * blockDim.x)
         *reinterpret_cast<double2*>(a + 2 * e) = make_double2(v, v + 1.0);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Reprojection statistics and track filtering (sfmba_reprojection_stats).  Three sweeps over
-// buffers of their own -- nothing a solver form reads or writes is touched:
-//   k_obs_stats    per observation, point-major: err = |r|, depth = z of R (X - T), keep = the observation's own test
-//   k_point_stats  per point over its run: views, max err, sum err^2, min depth, widest ray angle, the point's verdict,
-//                  and the FINAL mask of its observations (own test and point kept); one row of partial sums per workgroup
-//   k_cam_stats    per camera over a camera-major permutation of ALL observations (cameras held still included,
-//                  which the solver's camera-major lists leave out): kept views, sum and max err, observations behind
-//   k_stats_summary  one workgroup adds the rows of k_point_stats in row order
-// No atomics: a point's sums run over its observations in stored order, a camera's and the summary's are added in a
-// fixed order; maxima, minima and counts do not depend on the order at all.
-// ---------------------------------------------------------------------------------------------
-struct StatsFilter { double max_err, min_depth, min_angle_deg; int min_views; };
-
-// The residual-only sweep (k_resjac<.., false, true, ..>) with other stores: same persistent workgroups, same camera
-// table in LDS (or rows gathered through the wave's slab), same pipeline -- indices two batches ahead, pixel and point
-// one batch ahead, so three observations per lane are in flight -- and the same observe<false>, so rx, ry are the
-// solver's residual bit for bit.  Per observation it reads 4 + 4 + 16 (8 in fp32 storage) bytes and the gathered point,
-// and writes err | depth as one 16-byte store and the mask byte.
-// A non-finite err fails the test whatever the threshold (+inf <= +inf would pass it).
-template <bool LDS_TAB, bool F32>
-__global__ __launch_bounds__(kSweepThreads) void k_obs_stats(
-    const double* __restrict__ camtab, const double* __restrict__ pts, const int* __restrict__ cam_idx,
-    const int* __restrict__ pt_idx, const double* __restrict__ uv, double* __restrict__ ed,
-    unsigned char* __restrict__ keep, int N, int C, KMat K, double max_err, double min_depth) {
-    extern __shared__ __align__(16) double smem[];
-    const int stride = gridDim.x * blockDim.x;
-    const int lane = threadIdx.x & 63;
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    int c0 = 0, p0 = 0, c1 = 0, p1 = 0;
-    double2 uv0 = make_double2(0.0, 0.0);
-    double X0 = 0.0, Y0 = 0.0, Z0 = 0.0;
-    if (i < N) { c0 = cam_idx[i]; p0 = pt_idx[i]; uv0 = load_pair(uv, F32, i); }
-    if (i + stride < N) { c1 = cam_idx[i + stride]; p1 = pt_idx[i + stride]; }
-    if (i < N) { const double* __restrict__ Xp = pts + 3 * (size_t)p0; X0 = Xp[0]; Y0 = Xp[1]; Z0 = Xp[2]; }
-    if (LDS_TAB) {
-        const int n2 = (C * kCamRow) >> 1;
-        const double2* __restrict__ src = reinterpret_cast<const double2*>(camtab);
-        double2* __restrict__ dst = reinterpret_cast<double2*>(smem);
-        for (int k = threadIdx.x; k < n2; k += blockDim.x) dst[k] = src[k];
-        __syncthreads();
-    }
-    double* const slab = smem + (size_t)(threadIdx.x >> 6) * kRowSlabDoubles;
-    if (!LDS_TAB && i - lane < N) rows_request(camtab, c0, lane, slab);
-    while (i - lane < N) {                       // wave-uniform: rows_request shuffles over all 64 lanes
-        const bool on = i < N;
-        const int in = i + stride, in2 = in + stride;
-        double tl[kCamRow];
-        if (!LDS_TAB) rows_wait();
-        {
-            const double2* __restrict__ trow = reinterpret_cast<const double2*>(LDS_TAB ? smem + (size_t)c0 * kCamRow
-                                                                                         : slab + (size_t)lane * kCamRow);
-#pragma unroll
-            for (int k = 0; k < kCamRow / 2; ++k) { const double2 q = trow[k]; tl[2 * k] = q.x; tl[2 * k + 1] = q.y; }
-        }
-        if (!LDS_TAB) {
-            rows_read_done();
-            if (in - lane < N) rows_request(camtab, c1, lane, slab);
-        }
-        int c2 = 0, p2 = 0;
-        double2 uv1 = make_double2(0.0, 0.0);
-        double X1 = 0.0, Y1 = 0.0, Z1 = 0.0;
-        if (in2 < N) { c2 = cam_idx[in2]; p2 = pt_idx[in2]; }
-        if (in < N) {
-            uv1 = load_pair(uv, F32, in);
-            const double* __restrict__ Xp = pts + 3 * (size_t)p1;
-            X1 = Xp[0]; Y1 = Xp[1]; Z1 = Xp[2];
-        }
-        double jc[12], jp[6], rx, ry;
-        observe<false>(tl, X0, Y0, Z0, uv0.x, uv0.y, K, rx, ry, jc, jp);
-        const double depth = tl[6] * (X0 - tl[9]) + tl[7] * (Y0 - tl[10]) + tl[8] * (Z0 - tl[11]);
-        const double err = sqrt(rx * rx + ry * ry);
-        if (on) {
-            st16(ed + 2 * (size_t)i, err, depth);
-            keep[i] = (err <= max_err && err < INFINITY && depth > min_depth) ? 1 : 0;
-        }
-        i = in;
-        c0 = c1; p0 = p1; c1 = c2; p1 = p2;
-        uv0 = uv1; X0 = X1; Y0 = Y1; Z0 = Z1;
-    }
-}
-
-// One lane per point while the run is shorter than kStatsLongTrack: every pair of a run of n costs the lane two
-// dependent gathers (camera index, camera centre) and ~30 flops, n (n - 1) / 2 times, and the other 63 lanes of the wave
-// wait for the longest run among them.  From kStatsLongTrack on the WAVE takes the point after its lanes have finished
-// their short ones: the run is cut into blocks of 64 observations, every lane holds the ray of one observation of block
-// B and meets the rays of every block A <= B, handed round with v_readlane -- n^2 / 64 steps per lane instead of
-// n^2 / 2.  A wave-handled run of n <= 64 costs about n steps of the whole wave, a lane-handled one n^2 / 2 steps of a
-// wave whose other lanes may be idle: a lone long run gains from n = 2 on, 64 equally long ones only from n = 128 on;
-// 32 sits between (a lone run of 31 holds its wave for 465 steps, 64 runs of 32 cost 2048 instead of 496).
-// The widest angle is tracked as the pair (|a x b|, a . b) and compared by the sign of sin(theta1 - theta2) =
-// s1 d2 - d1 s2 (both angles in [0, pi]); atan2 is evaluated once per point (per lane in the wave form).
-constexpr int kStatsLongTrack = 32;
-constexpr int kStatsPtThreads = 256;
-constexpr int kStatsPart = 6;        // partial row of a workgroup: points kept, observations kept, behind, sum err, sum err^2, max err
-static_assert(kStatsLongTrack <= 32, "the lane form keeps the run's mask in 32 bits");
-
-__device__ __forceinline__ void widest_pair(double ax, double ay, double az, double bx, double by, double bz,
-                                            double& sb, double& db) {
-    const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
-    const double s = sqrt(cx * cx + cy * cy + cz * cz), d = ax * bx + ay * by + az * bz;
-    if (s * db - d * sb > 0.0) { sb = s; db = d; }
-}
-__device__ __forceinline__ int wave_isum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-    return v;
-}
-
-struct PointStatsOut {
-    int* __restrict__ views;
-    double* __restrict__ max_err;
-    double* __restrict__ sum_err2;
-    double* __restrict__ min_depth;
-    double* __restrict__ angle_deg;
-    unsigned char* __restrict__ keep;
-};
-
-__global__ __launch_bounds__(kStatsPtThreads) void k_point_stats(
-    const int* __restrict__ pt_ptr, const int* __restrict__ cam_idx, const double* __restrict__ camtab,
-    const double* __restrict__ pts, const double* __restrict__ ed, const unsigned char* __restrict__ keep, int P,
-    StatsFilter flt, PointStatsOut out, unsigned char* __restrict__ keep_final, double* __restrict__ part) {
-    __shared__ double red[(kStatsPtThreads / 64) * kStatsPart];
-    const int lane = threadIdx.x & 63;
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const double2* __restrict__ ed2 = reinterpret_cast<const double2*>(ed);
-    constexpr double kDeg = 57.295779513082320877;
-    int b = 0, e = 0;
-    double X = 0.0, Y = 0.0, Z = 0.0;
-    if (p < P) { b = pt_ptr[p]; e = pt_ptr[p + 1]; X = pts[3 * (size_t)p]; Y = pts[3 * (size_t)p + 1]; Z = pts[3 * (size_t)p + 2]; }
-    const int n = e - b;
-    int views = 0, behind = 0;
-    double maxe = 0.0, s1 = 0.0, s2 = 0.0, mind = INFINITY, sb = 0.0, db = 1.0;
-    if (n < kStatsLongTrack) {
-        unsigned mask = 0u;
-        for (int k = 0; k < n; ++k) {
-            const double2 q = ed2[b + k];
-            mind = fmin(mind, q.y);
-            behind += q.y <= 0.0 ? 1 : 0;
-            if (keep[b + k]) {
-                mask |= 1u << k;
-                ++views;
-                maxe = fmax(maxe, q.x);
-                s2 += q.x * q.x;
-                s1 += q.x;
-            }
-        }
-        for (int a = 0; a + 1 < n; ++a) {
-            if (!((mask >> a) & 1u) || (mask >> (a + 1)) == 0u) continue;
-            const double* __restrict__ Ta = camtab + (size_t)cam_idx[b + a] * kCamRow + 9;
-            const double ax = X - Ta[0], ay = Y - Ta[1], az = Z - Ta[2];
-            for (int k = a + 1; k < n; ++k) {
-                if (!((mask >> k) & 1u)) continue;
-                const double* __restrict__ Tb = camtab + (size_t)cam_idx[b + k] * kCamRow + 9;
-                widest_pair(ax, ay, az, X - Tb[0], Y - Tb[1], Z - Tb[2], sb, db);
-            }
-        }
-    }
-    double ang = atan2(sb, db);
-    // the long runs among this wave's 64 points, one after the other, by the whole wave
-    unsigned long long todo = __ballot(n >= kStatsLongTrack);
-    while (todo) {
-        const int q = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const int qb = __shfl(b, q), qe = __shfl(e, q);
-        const double qX = __shfl(X, q), qY = __shfl(Y, q), qZ = __shfl(Z, q);
-        int wv = 0, wbeh = 0;
-        double wmax = 0.0, wmin = INFINITY, ws1 = 0.0, ws2 = 0.0, wsb = 0.0, wdb = 1.0;
-        for (int B0 = qb; B0 < qe; B0 += 64) {
-            const int kb = B0 + lane;
-            double2 eb = make_double2(0.0, INFINITY);
-            bool fb = false;
-            double bx = 0.0, by = 0.0, bz = 0.0;
-            if (kb < qe) {
-                eb = ed2[kb];
-                fb = keep[kb] != 0;
-                const double* __restrict__ T = camtab + (size_t)cam_idx[kb] * kCamRow + 9;
-                bx = qX - T[0]; by = qY - T[1]; bz = qZ - T[2];
-                wmin = fmin(wmin, eb.y);
-                wbeh += eb.y <= 0.0 ? 1 : 0;
-            }
-            if (fb) { ++wv; wmax = fmax(wmax, eb.x); }
-            const unsigned long long mb = __ballot(fb);
-            for (unsigned long long m = mb; m; m &= m - 1) {       // the two sums in stored order, on every lane alike
-                const double v = readlane_double(eb.x, __ffsll((long long)m) - 1);
-                ws2 += v * v;
-                ws1 += v;
-            }
-            for (int A0 = qb; A0 <= B0; A0 += 64) {
-                double ax = bx, ay = by, az = bz;
-                bool fa = fb;
-                if (A0 != B0) {                                    // a full block: A0 + 63 < B0 <= qe - 1
-                    const int ka = A0 + lane;
-                    fa = keep[ka] != 0;
-                    const double* __restrict__ T = camtab + (size_t)cam_idx[ka] * kCamRow + 9;
-                    ax = qX - T[0]; ay = qY - T[1]; az = qZ - T[2];
-                }
-                for (unsigned long long m = __ballot(fa); m; m &= m - 1) {
-                    const int k = __ffsll((long long)m) - 1;
-                    const double rx = readlane_double(ax, k), ry = readlane_double(ay, k), rz = readlane_double(az, k);
-                    if (fb) widest_pair(rx, ry, rz, bx, by, bz, wsb, wdb);     // (a ray with itself: angle 0, never wider)
-                }
-            }
-        }
-        wv = wave_isum(wv);
-        wbeh = wave_isum(wbeh);
-        wmax = wave_max(wmax);
-        wmin = wave_min(wmin);
-        const double wang = wave_max(atan2(wsb, wdb));
-        const unsigned char qk = (wv >= flt.min_views && wang * kDeg >= flt.min_angle_deg) ? 1 : 0;
-        for (int k = qb + lane; k < qe; k += 64) keep_final[k] = keep[k] & qk;
-        if (lane == q) { views = wv; behind = wbeh; maxe = wmax; mind = wmin; s1 = ws1; s2 = ws2; ang = wang; }
-    }
-    const double deg = ang * kDeg;
-    const bool pk = p < P && views >= flt.min_views && deg >= flt.min_angle_deg;
-    if (p < P) {
-        out.views[p] = views; out.max_err[p] = maxe; out.sum_err2[p] = s2; out.min_depth[p] = mind;
-        out.angle_deg[p] = deg; out.keep[p] = pk ? 1 : 0;
-        if (n < kStatsLongTrack)
-            for (int k = 0; k < n; ++k) keep_final[b + k] = keep[b + k] & (pk ? 1 : 0);
-    }
-    // the workgroup's row: sums over its points in lane order inside a wave, wave by wave
-    double v[kStatsPart - 1] = {pk ? 1.0 : 0.0, pk ? (double)views : 0.0, (double)behind, pk ? s1 : 0.0, pk ? s2 : 0.0};
-    const double vmax = wave_max(pk ? maxe : 0.0);
-    block_sum<kStatsPart - 1>(v, red);
-    __shared__ double redmax[kStatsPtThreads / 64];
-    if (lane == 0) redmax[threadIdx.x >> 6] = vmax;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* __restrict__ row = part + (size_t)blockIdx.x * kStatsPart;
-#pragma unroll
-        for (int k = 0; k < kStatsPart - 1; ++k) row[k] = v[k];
-        double m = 0.0;
-        for (int k = 0; k < kStatsPtThreads / 64; ++k) m = fmax(m, redmax[k]);
-        row[kStatsPart - 1] = m;
-    }
-}
-
-// rows of k_point_stats -> out[0..5] (points kept, observations kept, behind, sum err, sum err^2, max err): every thread
-// adds rows tid, tid + 256, ... in that order, then the 256 sums are added in thread order
-__global__ __launch_bounds__(256) void k_stats_summary(const double* __restrict__ part, int rows, double* __restrict__ out) {
-    __shared__ double red[4 * kStatsPart];
-    double v[kStatsPart - 1] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    double m = 0.0;
-    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
-        const double* __restrict__ row = part + (size_t)r * kStatsPart;
-#pragma unroll
-        for (int k = 0; k < kStatsPart - 1; ++k) v[k] += row[k];
-        m = fmax(m, row[kStatsPart - 1]);
-    }
-    m = wave_max(m);
-    block_sum<kStatsPart - 1>(v, red);
-    __shared__ double redmax[4];
-    if ((threadIdx.x & 63) == 0) redmax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < kStatsPart - 1; ++k) out[k] = v[k];
-        out[kStatsPart - 1] = fmax(fmax(redmax[0], redmax[1]), fmax(redmax[2], redmax[3]));
-    }
-}
-
-// One workgroup per camera over its slice of the permutation (camera-major position -> point-major position): thread t
-// takes entries t, t + 256, ... in that order (four gathers in flight), the 256 partial sums are added in thread order.
-__global__ __launch_bounds__(kCamThreads) void k_cam_stats(const int* __restrict__ cam_ptr, const int* __restrict__ perm,
-                                                           const double* __restrict__ ed, const unsigned char* __restrict__ keep_final,
-                                                           int* __restrict__ views, double* __restrict__ sum_err,
-                                                           double* __restrict__ max_err, int* __restrict__ n_behind) {
-    __shared__ double red[kCamWaves];
-    __shared__ double redmax[kCamWaves];
-    __shared__ int redi[2 * kCamWaves];
-    const int c = blockIdx.x;
-    const int b = cam_ptr[c], e = cam_ptr[c + 1];
-    const double2* __restrict__ ed2 = reinterpret_cast<const double2*>(ed);
-    int nv = 0, nb = 0;
-    double s = 0.0, m = 0.0;
-    for (int j0 = b + (int)threadIdx.x; j0 < e; j0 += kCamThreads * kCamUnroll) {
-        int idx[kCamUnroll];
-        double2 q[kCamUnroll];
-        unsigned char kf[kCamUnroll];
-#pragma unroll
-        for (int u = 0; u < kCamUnroll; ++u) { const int j = j0 + u * kCamThreads; idx[u] = j < e ? perm[j] : -1; }
-#pragma unroll
-        for (int u = 0; u < kCamUnroll; ++u) {
-            q[u] = make_double2(0.0, 1.0); kf[u] = 0;
-            if (idx[u] >= 0) { q[u] = ed2[idx[u]]; kf[u] = keep_final[idx[u]]; }
-        }
-#pragma unroll
-        for (int u = 0; u < kCamUnroll; ++u) {
-            if (idx[u] >= 0 && q[u].y <= 0.0) ++nb;
-            if (kf[u]) { ++nv; s += q[u].x; m = fmax(m, q[u].x); }
-        }
-    }
-    s = wave_sum(s); m = wave_max(m); nv = wave_isum(nv); nb = wave_isum(nb);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[w] = s; redmax[w] = m; redi[2 * w] = nv; redi[2 * w + 1] = nb; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double ts = 0.0, tm = 0.0;
-        int tv = 0, tb = 0;
-        for (int k = 0; k < kCamWaves; ++k) { ts += red[k]; tm = fmax(tm, redmax[k]); tv += redi[2 * k]; tb += redi[2 * k + 1]; }
-        views[c] = tv; sum_err[c] = ts; max_err[c] = tm; n_behind[c] = tb;
-    }
-}
-
-// The permutation k_cam_stats walks: the stable counting sort of k_cam_hist / k_cam_offsets with no camera left out.
-//   k_stats_cam_count  hist[slice][C] -> cnt[c], one thread per camera
-//   k_stats_cam_scan   one workgroup: cam_ptr = exclusive prefix sums of cnt (every thread a contiguous piece)
-//   k_stats_cam_scatter  k_cam_scatter's walk, storing the point-major position itself
-__global__ __launch_bounds__(256) void k_stats_cam_count(const int* __restrict__ hist, int B, int C, int* __restrict__ cnt) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    int total = 0;
-    for (int b0 = 0; b0 < B; b0 += 16) {
-        int n[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) n[u] = b0 + u < B ? hist[(size_t)(b0 + u) * C + c] : 0;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) total += n[u];
-    }
-    cnt[c] = total;
-}
-__global__ __launch_bounds__(1024) void k_stats_cam_scan(const int* __restrict__ cnt, int C, int* __restrict__ cam_ptr) {
-    __shared__ int tot[1024];
-    const int per = (C + 1023) / 1024;
-    const int c0 = min(C, (int)threadIdx.x * per), c1 = min(C, c0 + per);
-    int s = 0;
-    for (int c = c0; c < c1; ++c) s += cnt[c];
-    tot[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {                       // inclusive scan of the 1024 piece totals
-        const int add = (int)threadIdx.x >= o ? tot[threadIdx.x - o] : 0;
-        __syncthreads();
-        tot[threadIdx.x] += add;
-        __syncthreads();
-    }
-    int run = tot[threadIdx.x] - s;
-    for (int c = c0; c < c1; ++c) { cam_ptr[c] = run; run += cnt[c]; }
-    if (threadIdx.x == 1023) cam_ptr[C] = tot[1023];
-}
-__global__ __launch_bounds__(64) void k_stats_cam_scatter(const int* __restrict__ cam_idx, int N, int C, int per, int key_bits,
-                                                          const int* __restrict__ off, int* __restrict__ perm) {
-    extern __shared__ int cur[];
-    for (int c = threadIdx.x; c < C; c += 64) cur[c] = off[(size_t)blockIdx.x * C + c];
-    __syncthreads();
-    const int lane = threadIdx.x;
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    const int b0 = blockIdx.x * per, b1 = min(N, b0 + per);
-    int cn = b0 + lane < b1 ? cam_idx[b0 + lane] : -1;
-    for (int k0 = b0; k0 < b1; k0 += 64) {
-        const int c = cn;
-        cn = k0 + 64 + lane < b1 ? cam_idx[k0 + 64 + lane] : -1;
-        const bool act = c >= 0;
-        unsigned long long eq = __ballot(act);                 // lanes with the same camera as this one
-        for (int bit = 0; bit < key_bits; ++bit) {
-            const unsigned long long m = __ballot(act && ((c >> bit) & 1));
-            eq &= ((c >> bit) & 1) ? m : ~m;
-        }
-        if (act) {
-            perm[cur[c] + __popcll(eq & lt)] = k0 + lane;
-            if ((eq >> lane) == 1ull) cur[c] += __popcll(eq);   // the highest lane of the group advances the offset
-        }
-        __builtin_amdgcn_wave_barrier();                         // (one wave: LDS operations execute in program order)
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Triangulation (sfmba_triangulate): per selected point, over the used observations of its run,
-//   linear stage  the n-view DLT of cv2.triangulatePoints: rows u M3 - M1, v M3 - M2 with M = K R [I | -T], A^T A as ten
-//                 sums, its smallest eigenvector by cyclic Jacobi rotations, X = v[:3] / v[3] (unknowns neither
-//                 translated nor rescaled: for two views this is the reference's minimiser)
-//   refinement    damped Gauss-Newton on 1/2 sum |r|^2 over X, r and d r / d X from observe<> (the solver's residual);
-//                 one pass over the run per trial point, which yields its cost and the next linearisation
-//   verdict       at the result: depth and err of every used observation, the widest ray angle (widest_pair)
-// Runs are handled as in k_point_stats: a lane takes a run shorter than kStatsLongTrack, the wave the longer ones
-// afterwards, lanes striding the run and the sums combined by an xor butterfly, which leaves the same bits on every lane
-// -- so the wave's lanes take every decision alike.  Camera rows are the compact R | T rows of the table (six 16-byte
-// loads), staged in LDS by persistent workgroups when the table fits (forms.lds_tab), else read through L2.
-// No atomics; nothing of the solver's is read but the structure arrays and the pixels.
-// ---------------------------------------------------------------------------------------------
-constexpr int kTriThreads = 512;     // two waves per SIMD: the Jacobi state (26 doubles) and a linearisation stay in registers
-constexpr int kTriSweeps = 12;       // cap of the Jacobi sweeps (a 4x4 converges in 4..7)
-constexpr int kTriOk = 0, kTriFewViews = 1, kTriAtInfinity = 2, kTriBehind = 3, kTriLowAngle = 4, kTriHighError = 5,
-              kTriNotSelected = -1;
-struct TriOptions { int max_iter, min_views; double xtol, min_angle_deg, min_depth, max_err; };
-struct TriIn {
-    const int* __restrict__ pt_ptr;
-    const int* __restrict__ cam_idx;
-    const double* __restrict__ uv;
-    const unsigned char* __restrict__ use;       // [N] stored order, or null: every observation
-    const unsigned char* __restrict__ select;    // [P], or null: every point
-    const double* __restrict__ pts;              // the points of x
-};
-struct TriOut {
-    double* __restrict__ X;
-    int* __restrict__ status;
-    int* __restrict__ views;
-    int* __restrict__ iters;
-    double* __restrict__ rms;
-    double* __restrict__ angle_deg;
-    int* __restrict__ ok_part;                   // [workgroups] points with status OK
-};
-struct TriResult { int status, views, iters; double X, Y, Z, rms, ang; };
-
-// position of entry (i, j) of a symmetric 4x4 kept as its upper triangle, row by row
-__host__ __device__ constexpr int sym4(int i, int j) {
-    return i <= j ? 4 * i - i * (i - 1) / 2 + (j - i) : 4 * j - j * (j - 1) / 2 + (i - j);
-}
-
-// one Jacobi rotation in the (P, Q) plane: a <- G^T a G, v <- v G  (every index is a compile-time constant)
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rotate(double (&a)[10], double (&v)[16]) {
-    const double apq = a[sym4(P, Q)];
-    const double theta = (a[sym4(Q, Q)] - a[sym4(P, P)]) / (2.0 * apq);
-    // (theta^2 = inf: t = 0; a pair that is zero already: the identity, without a branch around 26 live doubles)
-    const double t = apq == 0.0 ? 0.0 : copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    a[sym4(P, P)] -= t * apq;
-    a[sym4(Q, Q)] += t * apq;
-    a[sym4(P, Q)] = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        if (r != P && r != Q) {
-            const double arp = a[sym4(r, P)], arq = a[sym4(r, Q)];
-            a[sym4(r, P)] = c * arp - s * arq;
-            a[sym4(r, Q)] = s * arp + c * arq;
-        }
-        const double vrp = v[4 * r + P], vrq = v[4 * r + Q];
-        v[4 * r + P] = c * vrp - s * vrq;
-        v[4 * r + Q] = s * vrp + c * vrq;
-    }
-}
-// eigenvector of the smallest eigenvalue of a (destroyed): cyclic sweeps until the off-diagonal part is 1e-40 of the
-// diagonal (a sweep squares that ratio) or has vanished
-__device__ __forceinline__ void smallest_eigenvector4(double (&a)[10], double& w0, double& w1, double& w2, double& w3) {
-    double v[16] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0};
-#pragma unroll 1
-    for (int sweep = 0; sweep < kTriSweeps; ++sweep) {
-        const double off = fabs(a[1]) + fabs(a[2]) + fabs(a[3]) + fabs(a[5]) + fabs(a[6]) + fabs(a[8]);
-        const double dia = fabs(a[0]) + fabs(a[4]) + fabs(a[7]) + fabs(a[9]);
-        if (!(off > 1e-40 * dia)) break;                         // (a NaN ends the loop too)
-        jacobi_rotate<0, 1>(a, v); jacobi_rotate<0, 2>(a, v); jacobi_rotate<0, 3>(a, v);
-        jacobi_rotate<1, 2>(a, v); jacobi_rotate<1, 3>(a, v); jacobi_rotate<2, 3>(a, v);
-    }
-    double lo = a[0];
-    w0 = v[0]; w1 = v[4]; w2 = v[8]; w3 = v[12];
-    if (a[4] < lo) { lo = a[4]; w0 = v[1]; w1 = v[5]; w2 = v[9]; w3 = v[13]; }
-    if (a[7] < lo) { lo = a[7]; w0 = v[2]; w1 = v[6]; w2 = v[10]; w3 = v[14]; }
-    if (a[9] < lo) { lo = a[9]; w0 = v[3]; w1 = v[7]; w2 = v[11]; w3 = v[15]; }
-}
-
-__device__ __forceinline__ double wave_butterfly_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// R | T of camera c into the first twelve entries of an observe<> row (w, b, c are not needed for d r / d X)
-__device__ __forceinline__ void tri_load_row(const double* __restrict__ rt, int c, double* __restrict__ tl) {
-    const double2* __restrict__ row = reinterpret_cast<const double2*>(rt + (size_t)c * kCamRT);
-#pragma unroll
-    for (int k = 0; k < kCamRT / 2; ++k) { const double2 q = row[k]; tl[2 * k] = q.x; tl[2 * k + 1] = q.y; }
-#pragma unroll
-    for (int k = kCamRT; k < kCamRow; ++k) tl[k] = 0.0;
-}
-
-// the linear stage's pass: a += the two DLT rows of every used observation; used = their number
-template <bool F32, bool WAVE>
-__device__ __forceinline__ void tri_dlt_pass(const double* __restrict__ rt, const TriIn& in, int b, int e, int lane,
-                                             const KMat& K, double (&a)[10], int& used) {
-#pragma unroll
-    for (int q = 0; q < 10; ++q) a[q] = 0.0;
-    used = 0;
-#pragma unroll 1
-    for (int k = WAVE ? b + lane : b; k < e; k += WAVE ? 64 : 1) {
-        if (in.use != nullptr && !in.use[k]) continue;
-        double tl[kCamRow];
-        tri_load_row(rt, in.cam_idx[k], tl);
-        const double2 px = load_pair(in.uv, F32, k);
-        double m[12];                                            // M = K R [I | -T], row-major 3x4
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) m[4 * i + j] = K.k[3 * i] * tl[j] + K.k[3 * i + 1] * tl[3 + j] + K.k[3 * i + 2] * tl[6 + j];
-            m[4 * i + 3] = -(m[4 * i] * tl[9] + m[4 * i + 1] * tl[10] + m[4 * i + 2] * tl[11]);
-        }
-        double ru[4], rv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { ru[j] = px.x * m[8 + j] - m[j]; rv[j] = px.y * m[8 + j] - m[4 + j]; }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = i; j < 4; ++j) a[sym4(i, j)] += ru[i] * ru[j] + rv[i] * rv[j];
-        ++used;
-    }
-    if (WAVE) {
-#pragma unroll
-        for (int q = 0; q < 10; ++q) a[q] = wave_butterfly_sum(a[q]);
-        used = wave_isum(used);
-    }
-}
-
-// one pass at (X, Y, Z): s = sum |r|^2, g = sum Jp^T r (3), H = sum Jp^T Jp (6, upper); smallest depth, largest err
-template <bool F32, bool WAVE>
-__device__ __forceinline__ void tri_linearise(const double* __restrict__ rt, const TriIn& in, int b, int e, int lane,
-                                              const KMat& K, double X, double Y, double Z, double (&s)[10],
-                                              double& mind, double& maxe) {
-#pragma unroll
-    for (int q = 0; q < 10; ++q) s[q] = 0.0;
-    mind = INFINITY; maxe = 0.0;
-#pragma unroll 1
-    for (int k = WAVE ? b + lane : b; k < e; k += WAVE ? 64 : 1) {
-        if (in.use != nullptr && !in.use[k]) continue;
-        double tl[kCamRow];
-        tri_load_row(rt, in.cam_idx[k], tl);
-        const double2 px = load_pair(in.uv, F32, k);
-        double jc[12], jp[6], rx, ry;
-        observe<true>(tl, X, Y, Z, px.x, px.y, K, rx, ry, jc, jp);
-        const double depth = tl[6] * (X - tl[9]) + tl[7] * (Y - tl[10]) + tl[8] * (Z - tl[11]);
-        const double e2 = rx * rx + ry * ry;
-        s[0] += e2;
-        s[1] += jp[0] * rx + jp[3] * ry; s[2] += jp[1] * rx + jp[4] * ry; s[3] += jp[2] * rx + jp[5] * ry;
-        s[4] += jp[0] * jp[0] + jp[3] * jp[3]; s[5] += jp[0] * jp[1] + jp[3] * jp[4]; s[6] += jp[0] * jp[2] + jp[3] * jp[5];
-        s[7] += jp[1] * jp[1] + jp[4] * jp[4]; s[8] += jp[1] * jp[2] + jp[4] * jp[5];
-        s[9] += jp[2] * jp[2] + jp[5] * jp[5];
-        mind = fmin(mind, depth);
-        maxe = fmax(maxe, sqrt(e2));
-    }
-    if (WAVE) {
-#pragma unroll
-        for (int q = 0; q < 10; ++q) s[q] = wave_butterfly_sum(s[q]);
-        mind = wave_min(mind);
-        maxe = wave_max(maxe);
-    }
-}
-
-// widest angle (radians) between the rays X - T of the used observations of the run: all pairs by one lane, or -- as the
-// wave form of k_point_stats -- every lane the ray of one observation of block B against the rays of the blocks A <= B
-template <bool WAVE>
-__device__ __forceinline__ double tri_widest_angle(const double* __restrict__ rt, const TriIn& in, int b, int e, int lane,
-                                                   double X, double Y, double Z) {
-    double sb = 0.0, db = 1.0;
-    if (!WAVE) {
-        for (int i = b; i + 1 < e; ++i) {
-            if (in.use != nullptr && !in.use[i]) continue;
-            const double* __restrict__ Ta = rt + (size_t)in.cam_idx[i] * kCamRT + 9;
-            const double ax = X - Ta[0], ay = Y - Ta[1], az = Z - Ta[2];
-            for (int k = i + 1; k < e; ++k) {
-                if (in.use != nullptr && !in.use[k]) continue;
-                const double* __restrict__ Tb = rt + (size_t)in.cam_idx[k] * kCamRT + 9;
-                widest_pair(ax, ay, az, X - Tb[0], Y - Tb[1], Z - Tb[2], sb, db);
-            }
-        }
-        return atan2(sb, db);
-    }
-    for (int B0 = b; B0 < e; B0 += 64) {
-        const int kb = B0 + lane;
-        bool fb = false;
-        double bx = 0.0, by = 0.0, bz = 0.0;
-        if (kb < e) {
-            fb = in.use == nullptr || in.use[kb] != 0;
-            const double* __restrict__ T = rt + (size_t)in.cam_idx[kb] * kCamRT + 9;
-            bx = X - T[0]; by = Y - T[1]; bz = Z - T[2];
-        }
-        for (int A0 = b; A0 <= B0; A0 += 64) {
-            double ax = bx, ay = by, az = bz;
-            bool fa = fb;
-            if (A0 != B0) {                                      // a full block: A0 + 63 < B0 <= e - 1
-                const int ka = A0 + lane;
-                fa = in.use == nullptr || in.use[ka] != 0;
-                const double* __restrict__ T = rt + (size_t)in.cam_idx[ka] * kCamRT + 9;
-                ax = X - T[0]; ay = Y - T[1]; az = Z - T[2];
-            }
-            for (unsigned long long m = __ballot(fa); m; m &= m - 1) {
-                const int k = __ffsll((long long)m) - 1;
-                const double rx = readlane_double(ax, k), ry = readlane_double(ay, k), rz = readlane_double(az, k);
-                if (fb) widest_pair(rx, ry, rz, bx, by, bz, sb, db);
-            }
-        }
-    }
-    return wave_max(atan2(sb, db));
-}
-
-// One point.  WAVE: called by all 64 lanes with the same arguments; every lane leaves with the same result.
-// (X0, Y0, Z0): the point of x, handed back whenever the status is not OK.
-template <bool F32, bool WAVE>
-__device__ __forceinline__ void tri_point(const double* __restrict__ rt, const TriIn& in, int b, int e, int lane, const KMat& K,
-                                          const TriOptions& o, double X0, double Y0, double Z0, TriResult& r) {
-    constexpr double kDeg = 57.295779513082320877;
-    r.status = kTriFewViews; r.iters = 0;
-    r.X = X0; r.Y = Y0; r.Z = Z0;
-    r.rms = NAN; r.ang = NAN;
-    double X, Y, Z;
-    {
-        double a[10];
-        tri_dlt_pass<F32, WAVE>(rt, in, b, e, lane, K, a, r.views);
-        if (r.views < max(2, o.min_views)) return;
-        double w0, w1, w2, w3;
-        smallest_eigenvector4(a, w0, w1, w2, w3);
-        const double nw = sqrt(w0 * w0 + w1 * w1 + w2 * w2 + w3 * w3);
-        r.status = kTriAtInfinity;
-        if (!(fabs(w3) > 1e-12 * nw)) return;                    // (false for a NaN as well)
-        X = w0 / w3; Y = w1 / w3; Z = w2 / w3;
-    }
-    double s[10], mind, maxe;
-    tri_linearise<F32, WAVE>(rt, in, b, e, lane, K, X, Y, Z, s, mind, maxe);
-    if (!(fabs(s[0]) < INFINITY && fabs(X) + fabs(Y) + fabs(Z) < INFINITY)) return;
-    double lam = 0.0;
-    int it = 0;
-#pragma unroll 1
-    while (it < o.max_iter) {
-        const double hd[6] = {s[4] * (1.0 + lam), s[5], s[6], s[7] * (1.0 + lam), s[8], s[9] * (1.0 + lam)};
-        double inv[6];
-        chol3_inverse(hd, inv);
-        const double d0 = -(inv[0] * s[1] + inv[1] * s[2] + inv[2] * s[3]);
-        const double d1 = -(inv[1] * s[1] + inv[3] * s[2] + inv[4] * s[3]);
-        const double d2 = -(inv[2] * s[1] + inv[4] * s[2] + inv[5] * s[3]);
-        const double dn = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-        if (dn <= o.xtol * (sqrt(X * X + Y * Y + Z * Z) + o.xtol)) break;      // the step on offer is below the tolerance already
-        const double Xt = X + d0, Yt = Y + d1, Zt = Z + d2;
-        double st[10], mt, et;
-        tri_linearise<F32, WAVE>(rt, in, b, e, lane, K, Xt, Yt, Zt, st, mt, et);
-        ++it;
-        if (st[0] <= s[0]) {                                     // (a non-finite trial cost is a rejection)
-            X = Xt; Y = Yt; Z = Zt;
-#pragma unroll
-            for (int q = 0; q < 10; ++q) s[q] = st[q];
-            mind = mt; maxe = et;
-            lam = lam > 1e-6 ? 0.1 * lam : 0.0;
-            if (dn <= o.xtol * (sqrt(X * X + Y * Y + Z * Z) + o.xtol)) break;
-        } else {
-            // rejected although the model promised less than 1e-12 of the cost: rounding of the cost's own evaluation
-            // (residuals are differences of pixel coordinates ~1e3) decides such trials, and more damping changes nothing
-            const double gd = s[1] * d0 + s[2] * d1 + s[3] * d2;
-            const double dHd = d0 * (s[4] * d0 + s[5] * d1 + s[6] * d2) + d1 * (s[5] * d0 + s[7] * d1 + s[8] * d2) +
-                               d2 * (s[6] * d0 + s[8] * d1 + s[9] * d2);
-            if (-(gd + 0.5 * dHd) <= 1e-12 * 0.5 * s[0]) break;
-            lam = lam == 0.0 ? 1e-3 : 10.0 * lam;
-        }
-    }
-    r.iters = it;
-    r.rms = sqrt(s[0] / (double)r.views);
-    r.ang = kDeg * tri_widest_angle<WAVE>(rt, in, b, e, lane, X, Y, Z);
-    if (!(r.ang == r.ang)) return;
-    if (mind <= o.min_depth) { r.status = kTriBehind; return; }
-    if (r.ang < o.min_angle_deg) { r.status = kTriLowAngle; return; }
-    if (maxe > o.max_err) { r.status = kTriHighError; return; }
-    r.status = kTriOk;
-    r.X = X; r.Y = Y; r.Z = Z;
-}
-
-template <bool LDS_TAB, bool F32>
-__global__ __launch_bounds__(kTriThreads) void k_triangulate(const double* __restrict__ camtab, TriIn in, int P, int C, KMat K,
-                                                              TriOptions opt, TriOut out) {
-    extern __shared__ __align__(16) double smem[];
-    __shared__ int red[kTriThreads / 64];
-    const int lane = threadIdx.x & 63;
-    const double* __restrict__ rt_global = camtab + cam_rt_offset(C);
-    if (LDS_TAB) {
-        const int n2 = (C * kCamRT) >> 1;
-        const double2* __restrict__ src = reinterpret_cast<const double2*>(rt_global);
-        double2* __restrict__ dst = reinterpret_cast<double2*>(smem);
-        for (int k = threadIdx.x; k < n2; k += blockDim.x) dst[k] = src[k];
-        __syncthreads();
-    }
-    const double* __restrict__ rt = LDS_TAB ? smem : rt_global;
-    int n_ok = 0;
-    for (int base = blockIdx.x * kTriThreads; base < P; base += gridDim.x * kTriThreads) {     // uniform over the workgroup
-        const int p = base + (int)threadIdx.x;
-        int b = 0, e = 0;
-        double X0 = 0.0, Y0 = 0.0, Z0 = 0.0;
-        bool sel = false;
-        if (p < P) {
-            b = in.pt_ptr[p]; e = in.pt_ptr[p + 1];
-            X0 = in.pts[3 * (size_t)p]; Y0 = in.pts[3 * (size_t)p + 1]; Z0 = in.pts[3 * (size_t)p + 2];
-            sel = in.select == nullptr || in.select[p] != 0;
-        }
-        const int n = e - b;
-        TriResult r;
-        r.status = kTriNotSelected; r.views = 0; r.iters = 0;
-        r.X = X0; r.Y = Y0; r.Z = Z0; r.rms = NAN; r.ang = NAN;
-        if (sel && n < kStatsLongTrack) tri_point<F32, false>(rt, in, b, e, 0, K, opt, X0, Y0, Z0, r);
-        // the long runs among this wave's 64 points, one after the other, by the whole wave
-        unsigned long long todo = __ballot(sel && n >= kStatsLongTrack);
-        while (todo) {
-            const int q = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const int qb = __shfl(b, q), qe = __shfl(e, q);
-            const double qX = __shfl(X0, q), qY = __shfl(Y0, q), qZ = __shfl(Z0, q);
-            TriResult w;
-            tri_point<F32, true>(rt, in, qb, qe, lane, K, opt, qX, qY, qZ, w);
-            if (lane == q) r = w;
-        }
-        if (p < P) {
-            out.X[3 * (size_t)p] = r.X; out.X[3 * (size_t)p + 1] = r.Y; out.X[3 * (size_t)p + 2] = r.Z;
-            out.status[p] = r.status; out.views[p] = r.views; out.iters[p] = r.iters;
-            out.rms[p] = r.rms; out.angle_deg[p] = r.ang;
-            n_ok += r.status == kTriOk ? 1 : 0;
-        }
-    }
-    // points with status OK of this workgroup: wave sums, added in wave order
-    n_ok = wave_isum(n_ok);
-    if (lane == 0) red[threadIdx.x >> 6] = n_ok;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int k = 0; k < kTriThreads / 64; ++k) t += red[k];
-        out.ok_part[blockIdx.x] = t;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Resection (sfmba_resect): per selected camera, over its used observations in camera-major stored
-// order (the permutation of stats_cam_perm),
-//   linear stage  the n-point DLT of the reference's _solve_pnp_linear: pixels normalised by K^-1, rows [P, 0, -u P],
-//                 [0, P, -v P] with P = (X, Y, Z, 1), A^T A from forty sums (S, S_u, S_v, S_w, each a symmetric 4x4), its
-//                 smallest eigenvector by cyclic Jacobi rotations on the 12x12 matrix in LDS (one wave, lane r owns row
-//                 r; pairs (0,1), (0,2), ..., (0,11), (1,2), ..., (10,11)), h = [M | m], R = M (M^T M)^(-1/2) by a 3x3
-//                 Jacobi, t = m / (mean singular value of M), both negated when det M < 0, T = -R^T t, omega through a
-//                 quaternion
-//   refinement    damped Gauss-Newton on 1/2 sum |r|^2 over (omega, T): r and the 2x6 block from observe<true>, the
-//                 trial pose's table row made by thread 0 (cam_row_values) and shared through LDS; one pass over the
-//                 slice per trial pose, which yields its cost and the next linearisation.  Damping, rejection and the
-//                 stops are k_triangulate's.
-//   verdict       at the result: used observations, finiteness / the gap of A^T A, smallest depth, rms error
-// One 256-thread workgroup per camera, on the shape of k_cam_stats: thread t takes entries t, t + 256, ... of the slice,
-// kResectUnroll gathers in flight (entry -> stored position -> pixel, point index -> point); partial sums are combined
-// by wave_sum and then over the waves in wave order (block_sum): same input, same bits.  Every decision is taken by
-// thread 0 and handed to the workgroup through LDS.  No atomics; nothing of the solver's is read but the structure
-// arrays and the pixels.
-// ---------------------------------------------------------------------------------------------
-constexpr int kResectUnroll = 4;
-constexpr int kResectSweeps = 30;    // cap of the Jacobi sweeps of the 12x12 matrix (it converges in 6..10)
-constexpr int kResOk = 0, kResFewViews = 1, kResDegenerate = 2, kResBehind = 3, kResHighError = 4, kResNotSelected = -1;
-struct ResectOptions { int max_iter, min_views, start; double xtol, min_depth, max_rms; };
-struct ResectIn {
-    const int* __restrict__ cam_ptr;             // [C + 1] slices of perm
-    const int* __restrict__ perm;                // camera-major position -> stored position
-    const int* __restrict__ pt_idx;              // [N] stored order
-    const double* __restrict__ uv;
-    const unsigned char* __restrict__ use;       // [N] stored order, or null: every observation
-    const unsigned char* __restrict__ select;    // [C], or null: every camera
-    const double* __restrict__ x;                // the parameter vector: 6C camera parameters, then the points
-};
-struct ResectOut {
-    double* __restrict__ cam;                    // [C][6]
-    int* __restrict__ status;
-    int* __restrict__ views;
-    int* __restrict__ iters;
-    double* __restrict__ rms;
-    int* __restrict__ ok_part;                   // [C] 1 where the status is OK
-};
-struct ResectObs { double X, Y, Z, u, v; bool on; };
-
-// entries j0, j0 + 256, ... of the slice [.., e): all index loads, then all pixel / point-index loads, then the points
-template <bool F32>
-__device__ __forceinline__ void resect_gather(const ResectIn& in, const double* __restrict__ pts, int j0, int e,
-                                              ResectObs (&o)[kResectUnroll]) {
-    int idx[kResectUnroll], p[kResectUnroll];
-#pragma unroll
-    for (int u = 0; u < kResectUnroll; ++u) { const int j = j0 + u * kCamThreads; idx[u] = j < e ? in.perm[j] : -1; }
-    if (in.use != nullptr) {
-        unsigned char f[kResectUnroll];
-#pragma unroll
-        for (int u = 0; u < kResectUnroll; ++u) f[u] = idx[u] >= 0 ? in.use[idx[u]] : 0;
-#pragma unroll
-        for (int u = 0; u < kResectUnroll; ++u) if (!f[u]) idx[u] = -1;
-    }
-#pragma unroll
-    for (int u = 0; u < kResectUnroll; ++u) {
-        o[u].on = idx[u] >= 0;
-        p[u] = 0; o[u].u = 0.0; o[u].v = 0.0;
-        if (o[u].on) { p[u] = in.pt_idx[idx[u]]; const double2 q = load_pair(in.uv, F32, idx[u]); o[u].u = q.x; o[u].v = q.y; }
-    }
-#pragma unroll
-    for (int u = 0; u < kResectUnroll; ++u) {
-        o[u].X = 0.0; o[u].Y = 0.0; o[u].Z = 1.0;
-        if (o[u].on) { const double* __restrict__ Xp = pts + 3 * (size_t)p[u]; o[u].X = Xp[0]; o[u].Y = Xp[1]; o[u].Z = Xp[2]; }
-    }
-}
-
-// the linear stage's pass: v = S (10) | S_u (10) | S_v (10) | S_w (10), upper triangles row by row; thread 0 leaves with
-// the workgroup's sums and the number of used observations
-template <bool F32>
-__device__ __forceinline__ void resect_dlt_pass(const ResectIn& in, const double* __restrict__ pts, int b, int e, const KMat& Kinv,
-                                                double (&v)[40], int& used, double* red, int* redi) {
-#pragma unroll
-    for (int q = 0; q < 40; ++q) v[q] = 0.0;
-    used = 0;
-#pragma unroll 1
-    for (int j0 = b + (int)threadIdx.x; j0 < e; j0 += kCamThreads * kResectUnroll) {
-        ResectObs o[kResectUnroll];
-        resect_gather<F32>(in, pts, j0, e, o);
-#pragma unroll
-        for (int u = 0; u < kResectUnroll; ++u) {
-            if (!o[u].on) continue;
-            const double un = Kinv.k[0] * o[u].u + Kinv.k[1] * o[u].v + Kinv.k[2];
-            const double vn = Kinv.k[3] * o[u].u + Kinv.k[4] * o[u].v + Kinv.k[5];
-            const double w2 = un * un + vn * vn;
-            const double P[4] = {o[u].X, o[u].Y, o[u].Z, 1.0};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = i; j < 4; ++j) {
-                    const double pp = P[i] * P[j];
-                    v[sym4(i, j)] += pp;
-                    v[10 + sym4(i, j)] += un * pp;
-                    v[20 + sym4(i, j)] += vn * pp;
-                    v[30 + sym4(i, j)] += w2 * pp;
-                }
-            ++used;
-        }
-    }
-    used = wave_isum(used);
-    if ((threadIdx.x & 63) == 0) redi[threadIdx.x >> 6] = used;
-    block_sum<40>(v, red);
-    if (threadIdx.x == 0) {
-        used = 0;
-        for (int k = 0; k < kCamWaves; ++k) used += redi[k];
-    }
-}
-
-// one pass at the pose of the table row tl: s[0] = sum |r|^2, s[1..6] = sum Jc^T r, s[7..27] = sum Jc^T Jc (upper, row by
-// row); thread 0 leaves with the workgroup's sums, the smallest depth and the number of used observations
-template <bool F32>
-__device__ __forceinline__ void resect_linearise(const ResectIn& in, const double* __restrict__ pts, int b, int e, const KMat& K,
-                                                 const double* __restrict__ tl, double (&s)[28], double& mind, int& used,
-                                                 double* red, double* redm, int* redi) {
-#pragma unroll
-    for (int q = 0; q < 28; ++q) s[q] = 0.0;
-    mind = INFINITY;
-    used = 0;
-#pragma unroll 1
-    for (int j0 = b + (int)threadIdx.x; j0 < e; j0 += kCamThreads * kResectUnroll) {
-        ResectObs o[kResectUnroll];
-        resect_gather<F32>(in, pts, j0, e, o);
-#pragma unroll
-        for (int u = 0; u < kResectUnroll; ++u) {
-            if (!o[u].on) continue;
-            double jc[12], jp[6], rx, ry;
-            observe<true>(tl, o[u].X, o[u].Y, o[u].Z, o[u].u, o[u].v, K, rx, ry, jc, jp);
-            const double depth = tl[6] * (o[u].X - tl[9]) + tl[7] * (o[u].Y - tl[10]) + tl[8] * (o[u].Z - tl[11]);
-            s[0] += rx * rx + ry * ry;
-            int n = 7;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                s[1 + a] += jc[a] * rx + jc[6 + a] * ry;
-#pragma unroll
-                for (int c = a; c < 6; ++c) s[n++] += jc[a] * jc[c] + jc[6 + a] * jc[6 + c];
-            }
-            mind = fmin(mind, depth);
-            ++used;
-        }
-    }
-    mind = wave_min(mind);
-    used = wave_isum(used);
-    if ((threadIdx.x & 63) == 0) { redm[threadIdx.x >> 6] = mind; redi[threadIdx.x >> 6] = used; }
-    block_sum<28>(s, red);
-    if (threadIdx.x == 0) {
-        used = 0; mind = INFINITY;
-        for (int k = 0; k < kCamWaves; ++k) { used += redi[k]; mind = fmin(mind, redm[k]); }
-    }
-}
-
-// Cyclic Jacobi on the symmetric 12x12 matrix A (full storage, LDS), eigenvectors in the columns of V, by ONE wave: lane
-// r < 12 owns row r of both.  The LDS operations of one wave execute in program order (volatile keeps the compiler to it):
-// within a rotation every lane reads before any lane writes.
-__device__ __forceinline__ void resect_jacobi12(volatile double* A, volatile double* V, int lane) {
-#pragma unroll 1
-    for (int sweep = 0; sweep < kResectSweeps; ++sweep) {
-        double off = 0.0, dia = 0.0;
-        if (lane < 12) {
-            for (int j = lane + 1; j < 12; ++j) off += fabs(A[12 * lane + j]);
-            dia = fabs(A[13 * lane]);
-        }
-        off = wave_sum(off);
-        dia = wave_sum(dia);
-        if (!(off > 1e-40 * dia)) break;                         // (a NaN ends the loop too)
-#pragma unroll 1
-        for (int p = 0; p < 11; ++p)
-#pragma unroll 1
-            for (int q = p + 1; q < 12; ++q) {
-                const double app = A[13 * p], aqq = A[13 * q], apq = A[12 * p + q];
-                const double theta = (aqq - app) / (2.0 * apq);
-                const double t = apq == 0.0 ? 0.0 : copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                double arp = 0.0, arq = 0.0, vrp = 0.0, vrq = 0.0;
-                if (lane < 12) { arp = A[12 * lane + p]; arq = A[12 * lane + q]; vrp = V[12 * lane + p]; vrq = V[12 * lane + q]; }
-                if (lane < 12) {
-                    V[12 * lane + p] = c * vrp - s * vrq;
-                    V[12 * lane + q] = s * vrp + c * vrq;
-                    if (lane == p) { A[13 * p] = app - t * apq; A[12 * p + q] = 0.0; }
-                    else if (lane == q) { A[13 * q] = aqq + t * apq; A[12 * q + p] = 0.0; }
-                    else {
-                        const double n1 = c * arp - s * arq, n2 = s * arp + c * arq;
-                        A[12 * lane + p] = n1; A[12 * p + lane] = n1;
-                        A[12 * lane + q] = n2; A[12 * q + lane] = n2;
-                    }
-                }
-            }
-    }
-}
-
-__host__ __device__ constexpr int sym3(int i, int j) { return i <= j ? (i == 0 ? j : i + j + 1) : (j == 0 ? i : i + j + 1); }
-template <int P, int Q>
-__device__ __forceinline__ void jacobi3_rotate(double (&a)[6], double (&v)[9]) {
-    const double apq = a[sym3(P, Q)];
-    const double theta = (a[sym3(Q, Q)] - a[sym3(P, P)]) / (2.0 * apq);
-    const double t = apq == 0.0 ? 0.0 : copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    a[sym3(P, P)] -= t * apq;
-    a[sym3(Q, Q)] += t * apq;
-    a[sym3(P, Q)] = 0.0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        if (r != P && r != Q) {
-            const double arp = a[sym3(r, P)], arq = a[sym3(r, Q)];
-            a[sym3(r, P)] = c * arp - s * arq;
-            a[sym3(r, Q)] = s * arp + c * arq;
-        }
-        const double vrp = v[3 * r + P], vrq = v[3 * r + Q];
-        v[3 * r + P] = c * vrp - s * vrq;
-        v[3 * r + Q] = s * vrp + c * vrq;
-    }
-}
-
-// h = [M | m] (rows of 4) -> the six parameters (omega, T) of the pose R = M (M^T M)^(-1/2), t = m / s, T = -R^T t
-__device__ __forceinline__ void resect_pose_from_h(const double (&h)[12], double (&prm)[6]) {
-    double M[9], m[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) M[3 * i + j] = h[4 * i + j];
-        m[i] = h[4 * i + 3];
-    }
-    const double det = M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
-    if (det < 0.0) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) M[k] = -M[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) m[k] = -m[k];
-    }
-    double a[6], w[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = i; j < 3; ++j) a[sym3(i, j)] = M[i] * M[j] + M[3 + i] * M[3 + j] + M[6 + i] * M[6 + j];
-#pragma unroll 1
-    for (int sweep = 0; sweep < kTriSweeps; ++sweep) {
-        const double off = fabs(a[1]) + fabs(a[2]) + fabs(a[4]);
-        const double dia = fabs(a[0]) + fabs(a[3]) + fabs(a[5]);
-        if (!(off > 1e-40 * dia)) break;
-        jacobi3_rotate<0, 1>(a, w); jacobi3_rotate<0, 2>(a, w); jacobi3_rotate<1, 2>(a, w);
-    }
-    const double s0 = sqrt(a[0]), s1 = sqrt(a[3]), s2 = sqrt(a[5]);
-    const double i0 = 1.0 / s0, i1 = 1.0 / s1, i2 = 1.0 / s2;
-    const double scale = (s0 + s1 + s2) / 3.0;
-    double Bi[9];                                                // (M^T M)^(-1/2) = W diag(1 / sigma) W^T
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Bi[3 * i + j] = w[3 * i] * i0 * w[3 * j] + w[3 * i + 1] * i1 * w[3 * j + 1] + w[3 * i + 2] * i2 * w[3 * j + 2];
-    double R[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) R[3 * i + j] = M[3 * i] * Bi[j] + M[3 * i + 1] * Bi[3 + j] + M[3 * i + 2] * Bi[6 + j];
-    const double t0 = m[0] / scale, t1 = m[1] / scale, t2 = m[2] / scale;
-    prm[3] = -(R[0] * t0 + R[3] * t1 + R[6] * t2);
-    prm[4] = -(R[1] * t0 + R[4] * t1 + R[7] * t2);
-    prm[5] = -(R[2] * t0 + R[5] * t1 + R[8] * t2);
-    // rotation vector through the quaternion, the largest component first (angles near 0 and near pi are both safe)
-    const double tr = R[0] + R[4] + R[8];
-    double qw, qx, qy, qz;
-    if (tr > 0.0) {
-        const double s = sqrt(tr + 1.0) * 2.0;
-        qw = 0.25 * s; qx = (R[7] - R[5]) / s; qy = (R[2] - R[6]) / s; qz = (R[3] - R[1]) / s;
-    } else if (R[0] > R[4] && R[0] > R[8]) {
-        const double s = sqrt(1.0 + R[0] - R[4] - R[8]) * 2.0;
-        qw = (R[7] - R[5]) / s; qx = 0.25 * s; qy = (R[1] + R[3]) / s; qz = (R[2] + R[6]) / s;
-    } else if (R[4] > R[8]) {
-        const double s = sqrt(1.0 + R[4] - R[0] - R[8]) * 2.0;
-        qw = (R[2] - R[6]) / s; qx = (R[1] + R[3]) / s; qy = 0.25 * s; qz = (R[5] + R[7]) / s;
-    } else {
-        const double s = sqrt(1.0 + R[8] - R[0] - R[4]) * 2.0;
-        qw = (R[3] - R[1]) / s; qx = (R[2] + R[6]) / s; qy = (R[5] + R[7]) / s; qz = 0.25 * s;
-    }
-    if (qw < 0.0) { qw = -qw; qx = -qx; qy = -qy; qz = -qz; }
-    const double n = sqrt(qx * qx + qy * qy + qz * qz);
-    const double f = n < 1e-12 ? 2.0 : 2.0 * atan2(n, qw) / n;
-    prm[0] = qx * f; prm[1] = qy * f; prm[2] = qz * f;
-}
-
-template <bool F32>
-__global__ __launch_bounds__(kCamThreads) void k_resect(ResectIn in, int C, KMat K, KMat Kinv, ResectOptions opt, ResectOut out) {
-    __shared__ double red[kCamWaves * 40];
-    __shared__ double redm[kCamWaves];
-    __shared__ int redi[kCamWaves];
-    __shared__ __align__(16) double row[kCamRow];
-    __shared__ double jA[144], jV[144];
-    __shared__ int ctl;
-    __shared__ double s[28], p[6];                               // thread 0's: the accepted pose and its sums
-    const int c = blockIdx.x;
-    const int b = in.cam_ptr[c], e = in.cam_ptr[c + 1];
-    const double* __restrict__ pts = in.x + 6 * (size_t)C;
-    const bool first = threadIdx.x == 0;
-    if (first) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) p[k] = in.x[6 * (size_t)c + k];
-    }
-    // what thread 0 reports: the camera of x unless the status becomes OK
-    int status = kResNotSelected, views = 0, iters = 0;
-    double rms = NAN;
-    auto report = [&](bool ok) {
-        if (!first) return;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) out.cam[6 * (size_t)c + k] = ok ? p[k] : in.x[6 * (size_t)c + k];
-        out.status[c] = status; out.views[c] = views; out.iters[c] = iters; out.rms[c] = rms;
-        out.ok_part[c] = ok ? 1 : 0;
-    };
-    if (in.select != nullptr && !in.select[c]) { report(false); return; }          // (uniform over the workgroup)
-    const int need = max(opt.min_views, opt.start == 0 ? 6 : 3);
-    if (first) { row[kCamTab] = 0.0; ctl = 1; }
-    if (opt.start == 0) {
-        {
-            double v[40];
-            resect_dlt_pass<F32>(in, pts, b, e, Kinv, v, views, red, redi);
-            if (first) {
-                // A^T A = [[S, 0, -S_u], [0, S, -S_v], [-S_u, -S_v, S_w]], V = I
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int q = sym4(i, j);
-                        jA[12 * i + j] = v[q];           jA[12 * i + 4 + j] = 0.0;        jA[12 * i + 8 + j] = -v[10 + q];
-                        jA[12 * (4 + i) + j] = 0.0;      jA[12 * (4 + i) + 4 + j] = v[q]; jA[12 * (4 + i) + 8 + j] = -v[20 + q];
-                        jA[12 * (8 + i) + j] = -v[10 + q]; jA[12 * (8 + i) + 4 + j] = -v[20 + q]; jA[12 * (8 + i) + 8 + j] = v[30 + q];
-                    }
-                for (int k = 0; k < 144; ++k) jV[k] = (k % 13) == 0 ? 1.0 : 0.0;
-            }
-        }
-        if (threadIdx.x < 64) {                                  // wave 0: thread 0's stores above are its own
-            resect_jacobi12(jA, jV, (int)threadIdx.x);
-            if (first) {
-                status = kResFewViews;
-                bool go = views >= need;
-                if (go) {
-                    status = kResDegenerate;
-                    const volatile double* vA = jA;
-                    const volatile double* vV = jV;
-                    int lo = 0;
-                    double hi = vA[0];
-                    for (int k = 1; k < 12; ++k) { if (vA[13 * k] < vA[13 * lo]) lo = k; hi = fmax(hi, vA[13 * k]); }
-                    double second = INFINITY;
-                    for (int k = 0; k < 12; ++k) if (k != lo) second = fmin(second, vA[13 * k]);
-                    go = second > 1e-12 * hi;                    // (false for a NaN as well)
-                    double hv[12];
-#pragma unroll
-                    for (int k = 0; k < 12; ++k) hv[k] = vV[12 * k + lo];
-                    resect_pose_from_h(hv, p);
-                    double sum = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) sum += fabs(p[k]);
-                    go = go && sum < INFINITY;
-                    if (go) cam_row_values(p, row);
-                }
-                ctl = go ? 1 : 0;
-            }
-        }
-    } else if (first) {
-        cam_row_values(p, row);
-    }
-    __syncthreads();
-    if (!ctl) { report(false); return; }
-    // refinement: thread 0 holds the accepted pose p, its sums s and smallest depth, the damping and the step on trial
-    // (the accepted sums live in LDS: with the trial's 28 in registers beside the 6x6 factorisation the kernel spilled)
-    double mind = INFINITY, lam = 0.0, d[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, dn = 0.0;
-    bool have = false;
-#pragma unroll 1
-    for (;;) {
-        double tl[kCamRow];
-        {
-            const double2* __restrict__ r2 = reinterpret_cast<const double2*>(row);
-#pragma unroll
-            for (int k = 0; k < kCamRow / 2; ++k) { const double2 q = r2[k]; tl[2 * k] = q.x; tl[2 * k + 1] = q.y; }
-        }
-        double st[28], mt;
-        int used;
-        resect_linearise<F32>(in, pts, b, e, K, tl, st, mt, used, red, redm, redi);
-        if (first) {
-            bool stop = false;
-            if (!have) {                                         // the start pose
-                have = true;
-                views = used;
-#pragma unroll
-                for (int q = 0; q < 28; ++q) s[q] = st[q];
-                mind = mt;
-                double sum = fabs(s[0]);
-#pragma unroll
-                for (int k = 0; k < 6; ++k) sum += fabs(p[k]);
-                if (views < need) { status = kResFewViews; stop = true; }
-                else if (!(sum < INFINITY)) { status = kResDegenerate; stop = true; }
-                else status = kResOk;
-            } else {
-                ++iters;
-                if (st[0] <= s[0]) {                             // (a non-finite trial cost is a rejection)
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) p[k] += d[k];
-#pragma unroll
-                    for (int q = 0; q < 28; ++q) s[q] = st[q];
-                    mind = mt;
-                    lam = lam > 1e-6 ? 0.1 * lam : 0.0;
-                    double pn = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) pn += p[k] * p[k];
-                    if (dn <= opt.xtol * (sqrt(pn) + opt.xtol)) stop = true;
-                } else {
-                    // rejected although the model promised less than 1e-12 of the cost (see tri_point)
-                    double gd = 0.0, dHd = 0.0;
-                    int n = 7;
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) {
-                        gd += s[1 + a] * d[a];
-#pragma unroll
-                        for (int q = a; q < 6; ++q) { dHd += (q == a ? 1.0 : 2.0) * s[n] * d[a] * d[q]; ++n; }
-                    }
-                    if (-(gd + 0.5 * dHd) <= 1e-12 * 0.5 * s[0]) stop = true;
-                    lam = lam == 0.0 ? 1e-3 : 10.0 * lam;
-                }
-            }
-            if (!stop && iters >= opt.max_iter) stop = true;
-            if (!stop) {
-                double A[6][6], inv[21];
-                int n = 7;
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int q = a; q < 6; ++q) { A[a][q] = A[q][a] = q == a ? s[n] * (1.0 + lam) : s[n]; ++n; }
-                spd6_inverse(A, inv);
-                double full[6][6];
-                n = 0;
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int q = a; q < 6; ++q) { full[a][q] = full[q][a] = inv[n]; ++n; }
-                double pn = 0.0;
-                dn = 0.0;
-#pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int q = 0; q < 6; ++q) t += full[a][q] * s[1 + q];
-                    d[a] = -t;
-                    dn += t * t;
-                    pn += p[a] * p[a];
-                }
-                dn = sqrt(dn);
-                if (dn <= opt.xtol * (sqrt(pn) + opt.xtol)) stop = true;       // the step on offer is below the tolerance already
-                else {
-                    double pt[6];
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) pt[k] = p[k] + d[k];
-                    cam_row_values(pt, row);
-                }
-            }
-            ctl = stop ? 0 : 1;
-        }
-        __syncthreads();
-        if (!ctl) break;
-    }
-    if (first && status == kResOk) {
-        rms = sqrt(s[0] / (double)views);
-        double sum = fabs(rms) + fabs(mind);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) sum += fabs(p[k]);
-        if (!(sum < INFINITY)) status = kResDegenerate;
-        else if (mind <= opt.min_depth) status = kResBehind;
-        else if (rms > opt.max_rms) status = kResHighError;
-    }
-    report(status == kResOk);
 }
 
 }  // namespace sfmba

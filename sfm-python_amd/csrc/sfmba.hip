@@ -24,6 +24,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <numeric>
 #include <string>
@@ -31,6 +32,7 @@
 #include <vector>
 
 #include "ba_kernels.hpp"
+#include "consumer_kernels.hpp"
 #include "tr2d.hpp"
 
 using namespace sfmba;
@@ -453,20 +455,21 @@ struct sfmba_handle {
         unsigned long long perm_gen = 0;     // ... for the problem of this generation and size (0: none)
         int64_t perm_N = -1, perm_C = -1;
         PinnedBuf host;                      // staging of the per-observation downloads
+        // the masks of sfmba_triangulate / sfmba_resect (calls on a handle are serialised: one pair serves both)
+        DevBuf use;                          // [ld] obs_use in stored order
+        PinnedBuf mask_host;                 // staging of obs_use, of the select mask and of the OK counts
     } stats;
     // sfmba_triangulate: works on stats.x / stats.tab (the parameter vector and camera table of a call outside the
-    // solver) and on result arrays of its own
+    // solver), stats.use and on result arrays of its own
     struct Tri {
-        DevBuf use, select;                  // [ld] obs_use in stored order; [P]
+        DevBuf select;                       // [P]
         DevBuf X, ints, dbl, ok_part;        // [P][3]; [3][P] status, views, iters; [2][P] rms err, angle; [workgroups]
-        PinnedBuf host;                      // staging of the two masks and of the workgroups' counts
     } tri;
     // sfmba_resect: works on stats.x (the parameter vector of a call outside the solver), the camera-major permutation
-    // of the statistics call, and on result arrays of its own
+    // of the statistics call, stats.use and on result arrays of its own
     struct Resect {
-        DevBuf use, select;                  // [ld] obs_use in stored order; [C]
+        DevBuf select;                       // [C]
         DevBuf cam, ints, rms;               // [C][6]; [4][C] status, views, iters, ok; [C]
-        PinnedBuf host;                      // staging of the two masks and of the cameras' counts
     } resect;
 };
 
@@ -502,6 +505,19 @@ int fail(sfmba_handle* h, int code, const char* fmt, ...) {
         int rc_ = (expr);          \
         if (rc_ != 0) return rc_;  \
     } while (0)
+
+// every buffer of the list at (at least) its size; 0: a form that is not taken needs no buffer
+struct SizedBuf { DevBuf* buf; size_t bytes; };
+int ensure_all(sfmba_handle* h, std::initializer_list<SizedBuf> sized) {
+    for (const auto& b : sized)
+        if (b.bytes) HIPCHK(h, b.buf->ensure(b.bytes));
+    return 0;
+}
+
+// device -> host on the handle's stream; an array the caller did not ask for (null) is left out
+hipError_t download(sfmba_handle* h, void* dst, const void* src, size_t bytes) {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+}
 
 int enter(sfmba_handle* h) {
     if (!h) return -1;
@@ -2320,7 +2336,7 @@ int ProblemBuild::allocate() {
         pc.view->p = h->tables.as<char>() + pc.off;
     }
     const size_t n8 = sizeof(double) * (size_t)h->n, cam_tab = sizeof(double) * cam_table_doubles((int)C);
-    const struct { DevBuf* buf; size_t bytes; } sized[] = {
+    CHK(ensure_all(h, {
         {&h->xa, n8}, {&h->xb, n8}, {&h->tabA, cam_tab}, {&h->tabB, cam_tab}, {&h->r, esz * 2 * ldz}, {&h->J, esz * 12 * ldz},
         {&h->cm_perm, sizeof(int) * ldz}, {&h->cm_pt, sizeof(int) * ldz}, {&h->cm_uv, esz * 2 * ldz},
         {&h->cam_partial, sizeof(double) * std::max<size_t>(27 * h->host_chunks.size(), 27 * h->host_chunks_b.size())},
@@ -2337,9 +2353,7 @@ int ProblemBuild::allocate() {
         {&h->rec32, f.mixed ? sizeof(float) * kRec32 * (size_t)P : 0},
         {&h->rctab32, f.mixed && f.sweep_rc_g ? sizeof(float) * kRc32Row * (size_t)C : 0},
         {&h->part, sizeof(double) * (size_t)(2 * kPartRows * kNQ)}, {&h->ctrl, 2 * sizeof(PcgCtrl)},
-        {&h->pcg_part, sizeof(double) * 4 * C}, {&h->arena_own, sizeof(double) * (size_t)sfmba_exchange_doubles(C)}};
-    for (const auto& b : sized)
-        if (b.bytes) HIPCHK(h, b.buf->ensure(b.bytes));         // (0: a form that is not taken needs no buffer)
+        {&h->pcg_part, sizeof(double) * 4 * C}, {&h->arena_own, sizeof(double) * (size_t)sfmba_exchange_doubles(C)}}));
     h->g_cur = h->g.as<double>(); h->si_cur = h->si.as<double>(); h->sg_cur = h->sg.as<double>();
     h->g_new = h->g2.as<double>(); h->si_new = h->si2.as<double>(); h->sg_new = h->sg2.as<double>();
     // k_update_scale: cameras one element per thread, points kScalePts points per thread (all loads of a thread in flight
@@ -2526,19 +2540,17 @@ int launch_point_prep(sfmba_handle* h, const double* si_pts, const double* e_in,
 }  // namespace
 
 namespace {
-// ---- reprojection statistics (sfmba_reprojection_stats; kernels: ba_kernels.hpp, "Reprojection statistics") ------------
+// ---- reprojection statistics (sfmba_reprojection_stats; kernels: consumer_kernels.hpp, "Reprojection statistics") ------
 int stats_allocate(sfmba_handle* h, int* pt_blocks) {
     auto& s = h->stats;
     const size_t ldz = (size_t)h->ld, P = (size_t)h->P, C = (size_t)h->C;
     *pt_blocks = (int)std::max<size_t>(1, (P + kStatsPtThreads - 1) / kStatsPtThreads);
-    const struct { DevBuf* buf; size_t bytes; } sized[] = {
+    return ensure_all(h, {
         {&s.x, sizeof(double) * (size_t)h->n}, {&s.tab, sizeof(double) * cam_table_doubles((int)C)},
         {&s.ed, sizeof(double) * 2 * ldz}, {&s.keep, ldz}, {&s.keep_final, ldz},
         {&s.pt_views, sizeof(int) * P}, {&s.pt_d, sizeof(double) * 4 * P}, {&s.pt_keep, P},
         {&s.cam_i, sizeof(int) * 2 * C}, {&s.cam_d, sizeof(double) * 2 * C},
-        {&s.part, sizeof(double) * kStatsPart * (size_t)*pt_blocks}, {&s.sum, sizeof(double) * kStatsPart}};
-    for (const auto& b : sized) HIPCHK(h, b.buf->ensure(b.bytes));
-    return 0;
+        {&s.part, sizeof(double) * kStatsPart * (size_t)*pt_blocks}, {&s.sum, sizeof(double) * kStatsPart}});
 }
 
 // x into the call's own buffer, and its camera table
@@ -2604,10 +2616,9 @@ int stats_cam_perm(sfmba_handle* h) {
     const int per_slice = (int)(((N + B - 1) / B + 63) / 64 * 64);
     int key_bits = 0;
     while (((int64_t)1 << key_bits) < C) ++key_bits;
-    HIPCHK(h, s.hist.ensure(sizeof(int) * 2 * (size_t)B * (size_t)C));                // counts | offsets
-    HIPCHK(h, s.cnt.ensure(sizeof(int) * (size_t)C));
-    HIPCHK(h, s.cam_ptr.ensure(sizeof(int) * ((size_t)C + 1)));
-    HIPCHK(h, s.perm.ensure(sizeof(int) * (size_t)h->ld));
+    CHK(ensure_all(h, {{&s.hist, sizeof(int) * 2 * (size_t)B * (size_t)C},               // counts | offsets
+                       {&s.cnt, sizeof(int) * (size_t)C}, {&s.cam_ptr, sizeof(int) * ((size_t)C + 1)},
+                       {&s.perm, sizeof(int) * (size_t)h->ld}}));
     int* off = s.hist.as<int>() + (size_t)B * (size_t)C;
     const unsigned cblocks = (unsigned)((C + 255) / 256);
     CHK(set_lds(h, k_cam_hist, lds));
@@ -2677,18 +2688,51 @@ int stats_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
     return time_reps(h, reps, avg_us, [&] { return which == 13 ? launch_obs_stats(h, flt) : launch_point_stats(h, flt, pt_blocks); });
 }
 
-// ---- triangulation (sfmba_triangulate; kernel: ba_kernels.hpp, "Triangulation") ------------------------------------------
+// ---- what triangulation and resection share on the host ------------------------------------------------------------------
+// The masks of a call onto the device, both through pinned staging (stats.mask_host): obs_use [N] into stored order
+// (h->order: stored position -> caller's) -> stats.use, the select mask [n_sel] as it is -> select_dev; null: not
+// given.  *counts: room for n_counts ints behind them in the staging, for finish_with_ok_count.
+int stage_masks(sfmba_handle* h, const uint8_t* obs_use, const uint8_t* select, size_t n_sel, DevBuf& select_dev,
+                size_t n_counts, int** counts) {
+    auto& s = h->stats;
+    const size_t N = (size_t)h->N;
+    const size_t off_sel = (N + 63) / 64 * 64, off_ok = off_sel + (n_sel + 63) / 64 * 64;
+    HIPCHK(h, s.mask_host.ensure(off_ok + sizeof(int) * n_counts, 0));
+    unsigned char* const st = s.mask_host.as<unsigned char>();
+    if (obs_use && N) {
+        for (size_t k = 0; k < N; ++k) st[k] = obs_use[h->permuted ? (size_t)h->order[k] : k] ? 1 : 0;
+        HIPCHK(h, hipMemcpyAsync(s.use.p, st, N, hipMemcpyHostToDevice, h->stream));
+    }
+    if (select && n_sel) {
+        for (size_t k = 0; k < n_sel; ++k) st[off_sel + k] = select[k] ? 1 : 0;
+        HIPCHK(h, hipMemcpyAsync(select_dev.p, st + off_sel, n_sel, hipMemcpyHostToDevice, h->stream));
+    }
+    *counts = reinterpret_cast<int*>(st + off_ok);
+    return 0;
+}
+
+// the end of such a call: the n OK counts at src (device) through `counts` (stage_masks), the stream waited for, their
+// sum -> *n_ok (null: not asked for)
+int finish_with_ok_count(sfmba_handle* h, const int* src, size_t n, int* counts, int64_t* n_ok) {
+    if (n_ok) HIPCHK(h, download(h, counts, src, sizeof(int) * n));
+    CHK(wait_stream(h));
+    if (n_ok) {
+        *n_ok = 0;
+        for (size_t k = 0; k < n; ++k) *n_ok += counts[k];
+    }
+    return 0;
+}
+
+// ---- triangulation (sfmba_triangulate; kernel: consumer_kernels.hpp, "Triangulation") ------------------------------------
 int tri_allocate(sfmba_handle* h, int* grid) {
     auto& s = h->stats;
     auto& t = h->tri;
     const size_t ldz = (size_t)h->ld, P = (size_t)h->P;
     *grid = grid_1d(h->P, kTriThreads, h->n_cu);
-    const struct { DevBuf* buf; size_t bytes; } sized[] = {
+    return ensure_all(h, {
         {&s.x, sizeof(double) * (size_t)h->n}, {&s.tab, sizeof(double) * cam_table_doubles((int)h->C)},
-        {&t.use, ldz}, {&t.select, P}, {&t.X, sizeof(double) * 3 * P}, {&t.ints, sizeof(int) * 3 * P},
-        {&t.dbl, sizeof(double) * 2 * P}, {&t.ok_part, sizeof(int) * (size_t)*grid}};
-    for (const auto& b : sized) HIPCHK(h, b.buf->ensure(b.bytes));
-    return 0;
+        {&s.use, ldz}, {&t.select, P}, {&t.X, sizeof(double) * 3 * P}, {&t.ints, sizeof(int) * 3 * P},
+        {&t.dbl, sizeof(double) * 2 * P}, {&t.ok_part, sizeof(int) * (size_t)*grid}});
 }
 
 TriOptions tri_options(const sfmba_triangulate_options& o) {
@@ -2706,7 +2750,7 @@ int launch_triangulate(sfmba_handle* h, const TriOptions& opt, bool use, bool se
                         : (h->f32 ? k_triangulate<false, true> : k_triangulate<false, false>);
     CHK(set_lds(h, kern, lds));
     const TriIn in{h->pt_ptr.as<int>(), h->cam_idx.as<int>(), h->uv.as<double>(),
-                   use ? t.use.as<unsigned char>() : nullptr, select ? t.select.as<unsigned char>() : nullptr,
+                   use ? s.use.as<unsigned char>() : nullptr, select ? t.select.as<unsigned char>() : nullptr,
                    s.x.as<double>() + 6 * h->C};
     const TriOut out{t.X.as<double>(), t.ints.as<int>(), t.ints.as<int>() + P, t.ints.as<int>() + 2 * P,
                      t.dbl.as<double>(), t.dbl.as<double>() + P, t.ok_part.as<int>()};
@@ -2744,53 +2788,30 @@ int sfmba_triangulate(sfmba_handle* h, const double* x, const uint8_t* pt_select
     if (std::isnan(o.xtol) || std::isnan(o.min_angle_deg) || std::isnan(o.min_depth) || std::isnan(o.max_error_px))
         return fail(h, -1, "an option of sfmba_triangulate is NaN");
     auto& t = h->tri;
-    const size_t N = (size_t)h->N, P = (size_t)h->P;
-    int grid = 1;
+    const size_t P = (size_t)h->P;
+    int grid = 1, *counts = nullptr;
     CHK(tri_allocate(h, &grid));
     CHK(stats_prepare(h, x));
-    // the masks: obs_use into stored order (h->order: stored position -> caller's), both through pinned staging
-    const size_t off_sel = (N + 63) / 64 * 64, off_ok = off_sel + (P + 63) / 64 * 64;
-    HIPCHK(h, t.host.ensure(off_ok + sizeof(int) * (size_t)grid, 0));
-    unsigned char* const st = t.host.as<unsigned char>();
-    if (obs_use && N) {
-        for (size_t k = 0; k < N; ++k) st[k] = obs_use[h->permuted ? (size_t)h->order[k] : k] ? 1 : 0;
-        HIPCHK(h, hipMemcpyAsync(t.use.p, st, N, hipMemcpyHostToDevice, h->stream));
-    }
-    if (pt_select && P) {
-        for (size_t p = 0; p < P; ++p) st[off_sel + p] = pt_select[p] ? 1 : 0;
-        HIPCHK(h, hipMemcpyAsync(t.select.p, st + off_sel, P, hipMemcpyHostToDevice, h->stream));
-    }
+    CHK(stage_masks(h, obs_use, pt_select, P, t.select, (size_t)grid, &counts));
     CHK(launch_triangulate(h, tri_options(o), obs_use != nullptr, pt_select != nullptr, grid));
-    auto down = [&](void* dst, const void* src, size_t bytes) {
-        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-    };
     const int* pi = t.ints.as<int>();
-    HIPCHK(h, down(X_out, t.X.p, sizeof(double) * 3 * P));
-    HIPCHK(h, down(pt_status, pi, sizeof(int32_t) * P));
-    HIPCHK(h, down(pt_views, pi + P, sizeof(int32_t) * P));
-    HIPCHK(h, down(pt_iters, pi + 2 * P, sizeof(int32_t) * P));
-    HIPCHK(h, down(pt_rms_err, t.dbl.p, sizeof(double) * P));
-    HIPCHK(h, down(pt_angle_deg, t.dbl.as<double>() + P, sizeof(double) * P));
-    int* const st_ok = reinterpret_cast<int*>(st + off_ok);
-    if (n_ok) HIPCHK(h, down(st_ok, t.ok_part.p, sizeof(int) * (size_t)grid));
-    CHK(wait_stream(h));
-    if (n_ok) {
-        *n_ok = 0;
-        for (int k = 0; k < grid; ++k) *n_ok += st_ok[k];
-    }
-    return 0;
+    HIPCHK(h, download(h, X_out, t.X.p, sizeof(double) * 3 * P));
+    HIPCHK(h, download(h, pt_status, pi, sizeof(int32_t) * P));
+    HIPCHK(h, download(h, pt_views, pi + P, sizeof(int32_t) * P));
+    HIPCHK(h, download(h, pt_iters, pi + 2 * P, sizeof(int32_t) * P));
+    HIPCHK(h, download(h, pt_rms_err, t.dbl.p, sizeof(double) * P));
+    HIPCHK(h, download(h, pt_angle_deg, t.dbl.as<double>() + P, sizeof(double) * P));
+    return finish_with_ok_count(h, t.ok_part.as<int>(), (size_t)grid, counts, n_ok);
 }
 
 namespace {
-// ---- resection (sfmba_resect; kernel: ba_kernels.hpp, "Resection") ----------------------------------------------------------
+// ---- resection (sfmba_resect; kernel: consumer_kernels.hpp, "Resection") ----------------------------------------------------
 int resect_allocate(sfmba_handle* h) {
     auto& r = h->resect;
     const size_t ldz = (size_t)h->ld, C = (size_t)h->C;
-    const struct { DevBuf* buf; size_t bytes; } sized[] = {
-        {&h->stats.x, sizeof(double) * (size_t)h->n}, {&r.use, ldz}, {&r.select, C}, {&r.cam, sizeof(double) * 6 * C},
-        {&r.ints, sizeof(int) * 4 * C}, {&r.rms, sizeof(double) * C}};
-    for (const auto& b : sized) HIPCHK(h, b.buf->ensure(b.bytes));
-    return 0;
+    return ensure_all(h, {
+        {&h->stats.x, sizeof(double) * (size_t)h->n}, {&h->stats.use, ldz}, {&r.select, C}, {&r.cam, sizeof(double) * 6 * C},
+        {&r.ints, sizeof(int) * 4 * C}, {&r.rms, sizeof(double) * C}});
 }
 
 ResectOptions resect_options(const sfmba_resect_options& o) {
@@ -2816,7 +2837,7 @@ int launch_resect(sfmba_handle* h, const ResectOptions& opt, bool use, bool sele
     const size_t C = (size_t)h->C;
     if (C == 0) return 0;
     const ResectIn in{s.cam_ptr.as<int>(), s.perm.as<int>(), h->pt_idx.as<int>(), h->uv.as<double>(),
-                      use ? r.use.as<unsigned char>() : nullptr, select ? r.select.as<unsigned char>() : nullptr,
+                      use ? s.use.as<unsigned char>() : nullptr, select ? r.select.as<unsigned char>() : nullptr,
                       s.x.as<double>()};
     const ResectOut out{r.cam.as<double>(), r.ints.as<int>(), r.ints.as<int>() + C, r.ints.as<int>() + 2 * C,
                         r.rms.as<double>(), r.ints.as<int>() + 3 * C};
@@ -2862,40 +2883,20 @@ int sfmba_resect(sfmba_handle* h, const double* x, const uint8_t* cam_select, co
         return fail(h, -1, "an option of sfmba_resect is NaN");
     CHK(resect_check_single(h));
     auto& r = h->resect;
-    const size_t N = (size_t)h->N, C = (size_t)h->C;
+    const size_t C = (size_t)h->C;
+    int* counts = nullptr;
     CHK(resect_allocate(h));
     CHK(upload_x(h, x, h->stats.x.as<double>()));
     CHK(stats_cam_perm(h));
-    // the masks: obs_use into stored order (h->order: stored position -> caller's), both through pinned staging
-    const size_t off_sel = (N + 63) / 64 * 64, off_ok = off_sel + (C + 63) / 64 * 64;
-    HIPCHK(h, r.host.ensure(off_ok + sizeof(int) * C, 0));
-    unsigned char* const st = r.host.as<unsigned char>();
-    if (obs_use && N) {
-        for (size_t k = 0; k < N; ++k) st[k] = obs_use[h->permuted ? (size_t)h->order[k] : k] ? 1 : 0;
-        HIPCHK(h, hipMemcpyAsync(r.use.p, st, N, hipMemcpyHostToDevice, h->stream));
-    }
-    if (cam_select && C) {
-        for (size_t c = 0; c < C; ++c) st[off_sel + c] = cam_select[c] ? 1 : 0;
-        HIPCHK(h, hipMemcpyAsync(r.select.p, st + off_sel, C, hipMemcpyHostToDevice, h->stream));
-    }
+    CHK(stage_masks(h, obs_use, cam_select, C, r.select, C, &counts));
     CHK(launch_resect(h, resect_options(o), obs_use != nullptr, cam_select != nullptr));
-    auto down = [&](void* dst, const void* src, size_t bytes) {
-        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-    };
     const int* pi = r.ints.as<int>();
-    HIPCHK(h, down(cam_out, r.cam.p, sizeof(double) * 6 * C));
-    HIPCHK(h, down(cam_status, pi, sizeof(int32_t) * C));
-    HIPCHK(h, down(cam_views, pi + C, sizeof(int32_t) * C));
-    HIPCHK(h, down(cam_iters, pi + 2 * C, sizeof(int32_t) * C));
-    HIPCHK(h, down(cam_rms_err, r.rms.p, sizeof(double) * C));
-    int* const st_ok = reinterpret_cast<int*>(st + off_ok);
-    if (n_ok) HIPCHK(h, down(st_ok, pi + 3 * C, sizeof(int) * C));
-    CHK(wait_stream(h));
-    if (n_ok) {
-        *n_ok = 0;
-        for (size_t c = 0; c < C; ++c) *n_ok += st_ok[c];
-    }
-    return 0;
+    HIPCHK(h, download(h, cam_out, r.cam.p, sizeof(double) * 6 * C));
+    HIPCHK(h, download(h, cam_status, pi, sizeof(int32_t) * C));
+    HIPCHK(h, download(h, cam_views, pi + C, sizeof(int32_t) * C));
+    HIPCHK(h, download(h, cam_iters, pi + 2 * C, sizeof(int32_t) * C));
+    HIPCHK(h, download(h, cam_rms_err, r.rms.p, sizeof(double) * C));
+    return finish_with_ok_count(h, pi + 3 * C, C, counts, n_ok);
 }
 
 void sfmba_default_filter_options(sfmba_filter_options* o) {
@@ -2931,24 +2932,21 @@ int sfmba_reprojection_stats(sfmba_handle* h, const double* x, const sfmba_filte
     if (want_ed || obs_keep) HIPCHK(h, s.host.ensure(17 * N + 64, 0));
     double* const st_ed = s.host.as<double>();
     unsigned char* const st_keep = s.host.as<unsigned char>() + 16 * N;
-    auto down = [&](void* dst, const void* src, size_t bytes) {
-        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-    };
-    if (want_ed) HIPCHK(h, down(st_ed, s.ed.p, 16 * N));
-    if (obs_keep) HIPCHK(h, down(st_keep, s.keep_final.p, N));
+    if (want_ed) HIPCHK(h, download(h, st_ed, s.ed.p, 16 * N));
+    if (obs_keep) HIPCHK(h, download(h, st_keep, s.keep_final.p, N));
     const double* pd = s.pt_d.as<double>();
-    HIPCHK(h, down(pt_views, s.pt_views.p, sizeof(int32_t) * P));
-    HIPCHK(h, down(pt_max_err, pd, sizeof(double) * P));
-    HIPCHK(h, down(pt_sum_err2, pd + P, sizeof(double) * P));
-    HIPCHK(h, down(pt_min_depth, pd + 2 * P, sizeof(double) * P));
-    HIPCHK(h, down(pt_max_angle_deg, pd + 3 * P, sizeof(double) * P));
-    HIPCHK(h, down(pt_keep, s.pt_keep.p, P));
-    HIPCHK(h, down(cam_views, s.cam_i.p, sizeof(int32_t) * C));
-    HIPCHK(h, down(cam_behind, s.cam_i.as<int>() + C, sizeof(int32_t) * C));
-    HIPCHK(h, down(cam_sum_err, s.cam_d.p, sizeof(double) * C));
-    HIPCHK(h, down(cam_max_err, s.cam_d.as<double>() + C, sizeof(double) * C));
+    HIPCHK(h, download(h, pt_views, s.pt_views.p, sizeof(int32_t) * P));
+    HIPCHK(h, download(h, pt_max_err, pd, sizeof(double) * P));
+    HIPCHK(h, download(h, pt_sum_err2, pd + P, sizeof(double) * P));
+    HIPCHK(h, download(h, pt_min_depth, pd + 2 * P, sizeof(double) * P));
+    HIPCHK(h, download(h, pt_max_angle_deg, pd + 3 * P, sizeof(double) * P));
+    HIPCHK(h, download(h, pt_keep, s.pt_keep.p, P));
+    HIPCHK(h, download(h, cam_views, s.cam_i.p, sizeof(int32_t) * C));
+    HIPCHK(h, download(h, cam_behind, s.cam_i.as<int>() + C, sizeof(int32_t) * C));
+    HIPCHK(h, download(h, cam_sum_err, s.cam_d.p, sizeof(double) * C));
+    HIPCHK(h, download(h, cam_max_err, s.cam_d.as<double>() + C, sizeof(double) * C));
     double sums[kStatsPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (summary) HIPCHK(h, down(sums, s.sum.p, sizeof sums));
+    if (summary) HIPCHK(h, download(h, sums, s.sum.p, sizeof sums));
     CHK(wait_stream(h));
     if (want_ed || obs_keep) {
         for (size_t k = 0; k < N; ++k) {
@@ -3156,15 +3154,7 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
         CHK(schur_product_standalone(h, h->vtmp.as<double>()));          // leaves a valid z for case 5
         if (which == 12) CHK(launch_jdot(h, &np));
     }
-    struct EventPair {                    // destroyed on every exit path
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    HIPCHK(h, hipEventCreate(&ev.a));
-    HIPCHK(h, hipEventCreate(&ev.b));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventRecord(ev.a, h->stream));
-    for (int k = 0; k < reps; ++k) {
+    return time_reps(h, reps, avg_us, [&]() -> int {
         switch (which) {
             case 0: CHK((launch_resjac<true, true>(h, h->x, h->tab, &np))); break;
             case 1: CHK((launch_resjac<false, false>(h, h->x, h->tab, &np))); break;
@@ -3190,14 +3180,8 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
                 break;
             default: return fail(h, -1, "unknown kernel id %d", which);
         }
-    }
-    HIPCHK(h, hipEventRecord(ev.b, h->stream));
-    HIPCHK(h, hipEventSynchronize(ev.b));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, ev.a, ev.b));
-    *avg_us = 1e3 * (double)ms / reps;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
+        return 0;
+    });
 }
 
 namespace {

@@ -21,6 +21,25 @@ def _f64(a, shape=None, name="array"):
     return a
 
 
+def _mask(a, n, name):
+    """A boolean mask of n entries as contiguous uint8 (None stays None: every entry)."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(a).ravel() != 0, dtype=np.uint8)
+    if a.shape[0] != n:
+        raise ValueError(f"{name} has {a.shape[0]} entries, expected {n}")
+    return a
+
+
+def _fill_options(opt, options, what):
+    """Keyword options into the fields of the ctypes structure `opt`; `what` names the call in the error text."""
+    names = {f[0]: f[1] for f in type(opt)._fields_}
+    for key, value in options.items():
+        if key not in names:
+            raise TypeError(f"unknown {what} option {key!r} (known: {sorted(names)})")
+        setattr(opt, key, int(value) if names[key] is C.c_int32 else float(value))
+
+
 class ReprojectionStats:
     """What `Backend.reprojection_stats` returns (include/sfmba.h: sfmba_reprojection_stats).  Arrays that were not asked
     for are None.  ``obs_*`` (N) in the caller's observation order, ``pt_*`` (P), ``cam_*`` (C); the summary's fields
@@ -364,22 +383,9 @@ class Backend:
         x = _f64(x, (self.n_params,), "x")
         opt = _capi.TriangulateOptions()
         self._lib.sfmba_default_triangulate_options(C.byref(opt))
-        names = {f[0]: f[1] for f in _capi.TriangulateOptions._fields_}
-        for key, value in options.items():
-            if key not in names:
-                raise TypeError(f"unknown triangulation option {key!r} (known: {sorted(names)})")
-            setattr(opt, key, int(value) if names[key] is C.c_int32 else float(value))
-
-        def mask(a, n, name):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(np.asarray(a).ravel() != 0, dtype=np.uint8)
-            if a.shape[0] != n:
-                raise ValueError(f"{name} has {a.shape[0]} entries, expected {n}")
-            return a
-
+        _fill_options(opt, options, "triangulation")
         P = self.n_points
-        sel, use = mask(select, P, "select"), mask(obs_use, self.n_obs, "obs_use")
+        sel, use = _mask(select, P, "select"), _mask(obs_use, self.n_obs, "obs_use")
         points = np.empty((P, 3))
         status, views, iters = (np.empty(P, dtype=np.int32) for _ in range(3))
         rms, ang = np.empty(P), np.empty(P)
@@ -400,22 +406,9 @@ class Backend:
         x = _f64(x, (self.n_params,), "x")
         opt = _capi.ResectOptions()
         self._lib.sfmba_default_resect_options(C.byref(opt))
-        names = {f[0]: f[1] for f in _capi.ResectOptions._fields_}
-        for key, value in options.items():
-            if key not in names:
-                raise TypeError(f"unknown resection option {key!r} (known: {sorted(names)})")
-            setattr(opt, key, int(value) if names[key] is C.c_int32 else float(value))
-
-        def mask(a, n, name):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(np.asarray(a).ravel() != 0, dtype=np.uint8)
-            if a.shape[0] != n:
-                raise ValueError(f"{name} has {a.shape[0]} entries, expected {n}")
-            return a
-
+        _fill_options(opt, options, "resection")
         Cn = self.n_cameras
-        sel, use = mask(select, Cn, "select"), mask(obs_use, self.n_obs, "obs_use")
+        sel, use = _mask(select, Cn, "select"), _mask(obs_use, self.n_obs, "obs_use")
         cameras = np.empty((Cn, 6))
         status, views, iters = (np.empty(Cn, dtype=np.int32) for _ in range(3))
         rms = np.empty(Cn)

@@ -9,14 +9,14 @@ Gauss-Newton step is at most 100 xtol (|p| + xtol) -- one contraction of the ite
 oracle's and the kernel's Jacobian; two results that both satisfy it lie within 200 xtol (|p| + xtol) of each other."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 
 import resect_ref as rr
+from kernel_source import kernel_constant
 
 pytestmark = pytest.mark.gpu
 
@@ -32,11 +32,6 @@ def be():
     b = sfmba.Backend(0)
     yield b
     b.close()
-
-
-def _kernel_constant(name):
-    src = open(os.path.join(ROOT, "sfm-python_amd", "csrc", "ba_kernels.hpp")).read()
-    return int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
 
 
 def make_camera(rng, n, noise, w=None, T=None, coplanar=False):
@@ -168,7 +163,7 @@ def test_refinement_reaches_the_gauss_newton_fixed_point(be, four):
 def test_run_lengths_at_the_edges_of_the_loop(be):
     """Cameras with 0, 5, 6, 7, 255, 256, 257 and 256 unroll -+ 1 observations in one problem (nine cameras, 2834
     observations: the list of run lengths decides the size)."""
-    T, U = _kernel_constant("kCamThreads"), _kernel_constant("kResectUnroll")
+    T, U = kernel_constant("kCamThreads"), kernel_constant("kResectUnroll")
     assert T == 256 and U >= 2
     lengths = [0, 5, 6, 7, T - 1, T, T + 1, T * U - 1, T * U + 1]
     rng = np.random.default_rng(77)

@@ -1,13 +1,11 @@
 """GPU tests of the reprojection statistics (sfmba_reprojection_stats): the three sweeps against numpy on the oracle's
 residuals and camera-frame points.  Bounds are stated where used; the arithmetic is fp64 everywhere, pixels are read as
 stored (fp64 or fp32)."""
-import os
-import re
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import consumer_inputs
+from kernel_source import kernel_constant
 
 pytestmark = pytest.mark.gpu
 
@@ -24,11 +22,6 @@ def be():
 def orc():
     from oracle import ba_oracle
     return ba_oracle
-
-
-def _kernel_constant(name):
-    src = open(os.path.join(ROOT, "sfm-python_amd", "csrc", "ba_kernels.hpp")).read()
-    return int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
 
 
 class Ref:
@@ -228,32 +221,9 @@ def test_threshold_masks(be, orc, irregular):
 
 # ---- test 3: work-unit boundaries -------------------------------------------------------------------------------------
 
-def _boundary_problem(seed=11):
-    """A few thousand points of 2-3 views (runs that straddle the 64-observation tiles and the 1024-observation
-    workgroups of the per-observation sweep, and the 256-point workgroups of the reduction), three runs of exactly
-    L - 1, L and L + 1 views around the long-track switch-over L, in point-major order."""
-    L, tile, block = _kernel_constant("kStatsLongTrack"), 64, _kernel_constant("kSweepThreads")
-    rng = np.random.default_rng(seed)
-    C = L + 8
-    lens = rng.integers(2, 4, 4000)
-    for k, n in ((700, L - 1), (701, L), (2900, L + 1), (3999, L)):      # (701 follows 700 in one wave; 3999: the last point)
-        lens[k] = n
-    P = len(lens)
-    ptr = np.concatenate([[0], np.cumsum(lens)])
-    # runs must straddle tile and workgroup boundaries
-    inside = lambda m: np.any((ptr[:-1] % m != 0) & (ptr[:-1] // m != (ptr[1:] - 1) // m))
-    assert inside(tile) and inside(block)
-    pi = np.repeat(np.arange(P, dtype=np.int64), lens)
-    ci = np.concatenate([rng.permutation(C)[:n] for n in lens]).astype(np.int64)     # distinct cameras inside a run
-    w = rng.normal(0.0, 0.1, (C, 3))
-    T = rng.normal(0.0, 0.5, (C, 3))
-    X = rng.normal(0.0, 1.0, (P, 3)) + [0.0, 0.0, 10.0]
-    from sfmba import K_SCEAUX
-    from sfmba.synthetic import _rodrigues_batch
-    q = np.einsum("nij,nj->ni", _rodrigues_batch(w)[ci], X[pi] - T[ci]) @ K_SCEAUX.T
-    uv = q[:, :2] / q[:, 2:3] + rng.normal(0.0, 0.7, (len(ci), 2))
-    x = np.concatenate([np.hstack([w, T]).ravel(), X.ravel()])
-    return x, (C, P, ci, pi, uv, K_SCEAUX.copy()), L
+def _boundary_problem():
+    x, args = consumer_inputs.boundary_problem()
+    return x, args, kernel_constant("kStatsLongTrack")
 
 
 @pytest.mark.parametrize("bits", [64, 32])
@@ -281,10 +251,40 @@ def test_work_unit_boundaries(be, orc, bits):
         be.set_precision(64)
 
 
+def test_runs_longer_than_a_wave(be, orc):
+    """Runs of 63, 64, 65, 128 and 130 observations: the wave form of the per-point reduction with one, two and three
+    blocks, full and partial, a threshold that takes observations out of every block -- against numpy at the bounds of
+    test_work_unit_boundaries, and with the observations handed over in another order bit for bit."""
+    x, args = consumer_inputs.long_run_problem()
+    C, P, ci, pi, uv, K = args
+    special = consumer_inputs.LONG_RUNS
+    assert all(np.count_nonzero(pi == p) == n for p, n in special.items()) and np.all(np.diff(pi) >= 0)
+    thr = dict(max_error_px=1.0, min_depth=0.0, min_angle_deg=0.0, min_views=2)
+    ref = Ref(orc, x, args, 1.0, 0.0, 0.0, 2)
+    assert np.abs(ref.err - 1.0).min() > 1e-6                        # no decision within rounding of the threshold
+    for p, n in special.items():                                     # dropped and kept observations in every block
+        own = ref.own[pi == p]                                       # (but for the one or two of a last block)
+        for b0 in range(0, n - 2, 64):
+            assert 0 < np.count_nonzero(own[b0:b0 + 64]) < len(own[b0:b0 + 64]), (p, b0)
+    be.set_precision(64)
+    be.set_problem(*args)
+    st = be.reprojection_stats(x, **thr)
+    _check_parity(be, orc, x, args, ref, st)
+    perm = consumer_inputs.point_interleaved_order(pi)
+    assert np.any(np.diff(pi[perm]) < 0)
+    be.set_problem(C, P, ci[perm], pi[perm], uv[perm], K)
+    sh = be.reprojection_stats(x, **thr)
+    for name in st._ARRAYS:
+        a, b = getattr(st, name), getattr(sh, name)
+        assert (a[perm] if name.startswith("obs_") else a).tobytes() == b.tobytes(), name
+    for name in st._SUMMARY:
+        assert getattr(st, name) == getattr(sh, name), name
+
+
 def _large_case(which):
     from sfmba import make_problem
     if which == "grid_stride":      # more observations than one pass of the persistent workgroups (256 CUs x 1024 lanes) takes
-        return make_problem(300, 60000, 256 * _kernel_constant("kSweepThreads") * 2 + 777, seed=5), 40.0
+        return make_problem(300, 60000, 256 * kernel_constant("kSweepThreads") * 2 + 777, seed=5), 40.0
     return make_problem(1200, 800, 6000, seed=6), 40.0      # "many_cameras": the camera table does not fit the LDS
 
 
@@ -298,7 +298,7 @@ def test_other_forms_of_the_observation_sweep(be, orc, which):
     C, P, ci, pi, uv, K = args
     n = len(ci)
     if which == "many_cameras":
-        assert C * _kernel_constant("kCamRow") * 8 > 160 * 1024
+        assert C * kernel_constant("kCamRow") * 8 > 160 * 1024
     r = orc.compute_residuals(x, *args).reshape(-1, 2)
     err = np.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1])
     fin = err <= thr

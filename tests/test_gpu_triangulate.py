@@ -8,14 +8,15 @@ at the returned point the next Gauss-Newton step is at most 100 xtol (|X| + xtol
 the difference between the oracle's and the kernel's Jacobian."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 
+import consumer_inputs
 import triangulate_ref as tr
+from kernel_source import kernel_constant
 
 pytestmark = pytest.mark.gpu
 
@@ -30,11 +31,6 @@ def be():
     b = sfmba.Backend(0)
     yield b
     b.close()
-
-
-def _kernel_constant(name):
-    src = open(os.path.join(ROOT, "sfm-python_amd", "csrc", "ba_kernels.hpp")).read()
-    return int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
 
 
 class Tracks:
@@ -270,25 +266,10 @@ def test_errors(be, problem):
 def ring():
     """40 cameras on a ring; tracks of exactly 2, L-1, L, L+1 and 40 views (L = kStatsLongTrack) spread among 700
     three- and four-view tracks: lane- and wave-handled runs in the same waves, more than one workgroup."""
-    import sfmba
-    L = _kernel_constant("kStatsLongTrack")
-    assert L == 32 and _kernel_constant("kTriThreads") < 705
-    base = sfmba.make_ring_problem(40, 50, 400, seed=9)
-    C, K = 40, base.K
-    cams = base.x_true[:6 * C].reshape(C, 6)
-    rng = np.random.default_rng(17)
-    P = 705
-    lengths = np.where(np.arange(P) % 2 == 0, 3, 4)
+    L = kernel_constant("kStatsLongTrack")
+    assert L == 32 and kernel_constant("kTriThreads") < 705
     special = {5: 2, 70: L - 1, 71: L, 300: L + 1, 640: 40}
-    for p, n in special.items():
-        lengths[p] = n
-    pts = rng.normal(0.0, 1.0, (P, 3))
-    ci = np.concatenate([rng.permutation(C)[:n] for n in lengths]).astype(np.int64)
-    pi = np.repeat(np.arange(P, dtype=np.int64), lengths)
-    x = np.concatenate([cams.ravel(), pts.ravel()])
-    proj = tr.orc.compute_residuals(x, C, P, ci, pi, np.zeros((len(ci), 2)), K).reshape(-1, 2)
-    uv = proj + rng.normal(0.0, 0.5, proj.shape)
-    args = (C, P, ci, pi, uv, K)
+    x, args = consumer_inputs.ring_tracks(40, 705, special, cam_seed=9, seed=17)
     return x, args, special
 
 
@@ -333,8 +314,7 @@ def test_lane_and_wave_handled_runs(be, ring):
     _check_refined(tku, mu, lin_u.points, chk)
     # the same problem handed over in a non-point-major order (first observation of every point, then the second, ...:
     # the stored order inside a run is the caller's, so the sums run in the same order): same bits, masks permuted alike
-    pos = np.arange(len(ci)) - np.searchsorted(pi, pi)
-    perm = np.lexsort((pi, pos))
+    perm = consumer_inputs.point_interleaved_order(pi)
     assert np.any(np.diff(pi[perm]) < 0)
     be.set_problem(C, P, ci[perm], pi[perm], uv[perm], K)
     sh, shu = be.triangulate(x), be.triangulate(x, obs_use=use[perm])
@@ -343,11 +323,51 @@ def test_lane_and_wave_handled_runs(be, ring):
         assert getattr(shu, name).tobytes() == getattr(mu, name).tobytes(), name
 
 
+def _result_angles(tk, tri, which):
+    return np.array([tr.widest_angle_deg(tri.points[p], tk.cams[tk.ci[tk.runs[p]], 3:]) for p in which])
+
+
+def test_runs_longer_than_a_wave(be):
+    """Tracks of 63, 64, 65, 128 and 130 views: the wave form with one, two and three blocks of 64 observations, full and
+    partial -- the linear and refined checks of test_lane_and_wave_handled_runs, then again with observations taken out
+    of every block of the runs that have more than one."""
+    x, args = consumer_inputs.long_run_problem()
+    C, P, ci, pi, uv, K = args
+    special = consumer_inputs.LONG_RUNS
+    tk = Tracks(x, args)
+    sp = np.array(sorted(special))
+    assert np.array_equal(tk.views[sp], [special[p] for p in sp]) and tk.angle[sp].min() >= 2.0
+    be.set_precision(64)
+    be.set_problem(*args)
+    lin = be.triangulate(x, max_iter=0, min_angle_deg=2.0)
+    assert np.all(lin.status[sp] == lin.OK)
+    _check_linear(tk, lin.points, sp)
+    tri = be.triangulate(x)
+    assert np.all(tri.status[sp] == tri.OK)
+    _check_refined(tk, tri, lin.points, sp)
+    rms = _run_rms(be, tk, tri, sp)
+    assert np.all(np.abs(tri.rms_err[sp] - rms) <= 1e-12 * rms)
+    assert np.abs(tri.angle_deg[sp] - _result_angles(tk, tri, sp)).max() <= 1e-9
+    # obs_use: observations out of both blocks of the 65-view run and out of all of the 128- and the 130-view run's
+    use = np.ones(len(ci), dtype=bool)
+    for p, drop in ((90, (0, 7, 64)), (130, (3, 63, 64, 70, 127)), (204, (5, 40, 64, 100, 128, 129))):
+        assert special[p] > max(drop)
+        use[tk.runs[p][list(drop)]] = False
+    tku = Tracks(x, args, obs_use=use)
+    mu = be.triangulate(x, obs_use=use)
+    chk = np.array([90, 130, 204])
+    assert np.array_equal(mu.views, tku.views) and np.all(mu.status[chk] == mu.OK)
+    lin_u = be.triangulate(x, obs_use=use, max_iter=0)
+    _check_linear(tku, lin_u.points, chk)
+    _check_refined(tku, mu, lin_u.points, chk)
+    assert np.abs(mu.angle_deg[chk] - _result_angles(tku, mu, chk)).max() <= 1e-9
+
+
 def test_camera_table_too_large_for_the_lds(be):
     """More cameras than the LDS holds a table of: rows read through L2.  A selection of the points, against the SVD."""
     import sfmba
     pb = sfmba.make_problem(1200, 800, 6000, seed=6)
-    assert 1200 * _kernel_constant("kCamRow") * 8 > 160 * 1024
+    assert 1200 * kernel_constant("kCamRow") * 8 > 160 * 1024
     sel = np.zeros(800, dtype=bool)
     sel[::5] = True
     tk = Tracks(pb.x_true, pb.args)

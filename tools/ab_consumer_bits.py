@@ -1,0 +1,113 @@
+"""Bit identity of the three consumers (reprojection statistics, triangulation, resection) between two builds of the
+library.  Usage: python tools/ab_consumer_bits.py LIB_A LIB_B [--out DIR]
+
+One fresh child process per library (SFMBA_LIB), each under its own time limit; the tool stops at the first child that
+does not exit cleanly.  A child runs the three calls over inputs that reach every form of the kernels -- the long-run,
+ring and boundary problems of the tests, 1200 cameras (the camera table does not fit the LDS), camera slices at the edges
+of k_resect's strided loop -- in 64- and 32-bit storage, with and without select / obs_use, start 0 and 1, max_iter 0 and
+default, and writes every returned array to DIR/consumer_bits_<a|b>.npz (DIR: a fresh temporary folder unless --out names
+one).  The parent compares the two files byte for byte."""
+import os
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "sfm-python_amd"), os.path.join(ROOT, "tests")]
+import numpy as np
+
+CHILD_SECONDS = 240
+
+
+def inputs():
+    import consumer_inputs as ci
+    import sfmba
+    from kernel_source import kernel_constant
+    L = kernel_constant("kStatsLongTrack")
+    yield "long_runs", ci.long_run_problem()
+    yield "ring", ci.ring_tracks(40, 705, {5: 2, 70: L - 1, 71: L, 300: L + 1, 640: 40}, cam_seed=9, seed=17)
+    yield "boundary", ci.boundary_problem()
+    pb = sfmba.make_problem(1200, 800, 6000, seed=6)
+    yield "many_cameras", (pb.x0, pb.args)
+    yield "camera_slices", ci.camera_slices_problem([1, 255, 256, 257, 1024, 1025])
+
+
+def child(out_path):
+    import sfmba
+    from sfmba.backend import ReprojectionStats
+    be = sfmba.Backend(0)
+    out = {}
+    for name, (x, args) in inputs():
+        C, P, ci, pi, uv, K = args
+        rng = np.random.default_rng(5)
+        masks = (rng.random(len(ci)) < 0.85, rng.random(P) < 0.7, rng.random(C) < 0.7)
+        for bits in (64, 32):
+            be.set_precision(bits)
+            be.set_problem(*args)
+            for tag, kw in (("default", {}), ("filter", dict(max_error_px=1.0, min_depth=0.0, min_angle_deg=1.0, min_views=2))):
+                st = be.reprojection_stats(x, **kw)
+                for f in ReprojectionStats._ARRAYS:
+                    out[f"{name}/{bits}/stats/{tag}/{f}"] = getattr(st, f)
+                out[f"{name}/{bits}/stats/{tag}/summary"] = np.array([getattr(st, f) for f in ReprojectionStats._SUMMARY], dtype=np.float64)
+            for m, (use, psel, csel) in (("all", (None, None, None)), ("masked", masks)):
+                for it in ({"max_iter": 0}, {}):
+                    t = be.triangulate(x, select=psel, obs_use=use, **it)
+                    key = f"{name}/{bits}/tri/{m}/{'linear' if it else 'refined'}"
+                    for f in ("points", "status", "views", "iters", "rms_err", "angle_deg"):
+                        out[f"{key}/{f}"] = getattr(t, f)
+                    out[f"{key}/n_ok"] = np.array([t.n_ok])
+                    for start in (0, 1):
+                        r = be.resect(x, select=csel, obs_use=use, start=start, **it)
+                        key = f"{name}/{bits}/resect/{m}/start{start}/{'linear' if it else 'refined'}"
+                        for f in ("cameras", "status", "views", "iters", "rms_err"):
+                            out[f"{key}/{f}"] = getattr(r, f)
+                        out[f"{key}/n_ok"] = np.array([r.n_ok])
+    be.close()
+    np.savez(out_path, **{k.replace("/", "|"): v for k, v in out.items()})
+
+
+def main():
+    argv = sys.argv[1:]
+    if argv[:1] == ["--child"]:
+        return child(argv[1])
+    out_dir = None
+    if "--out" in argv:
+        k = argv.index("--out")
+        out_dir = argv[k + 1]
+        del argv[k:k + 2]
+    lib_a, lib_b = (os.path.abspath(p) for p in argv)
+    if out_dir is None:
+        out_dir = tempfile.mkdtemp(prefix="consumer_bits_")
+    os.makedirs(out_dir, exist_ok=True)
+    files = []
+    for tag, lib in (("a", lib_a), ("b", lib_b)):
+        path = os.path.join(out_dir, f"consumer_bits_{tag}.npz")
+        try:
+            rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path], env=dict(os.environ, SFMBA_LIB=lib),
+                                timeout=CHILD_SECONDS).returncode
+        except subprocess.TimeoutExpired:
+            rc = "time limit"
+        if rc != 0:
+            print(f"{lib}: the child ended with {rc}; stopping")
+            return 2
+        files.append(np.load(path))
+    a, b = files
+    print(f"A = {lib_a}\nB = {lib_b}")
+    differ = [k for k in a.files if k not in b.files or a[k].dtype != b[k].dtype or a[k].tobytes() != b[k].tobytes()]
+    differ += [k for k in b.files if k not in a.files]
+    groups = {}
+    for k in a.files:
+        g = "/".join(k.split("|")[:3])
+        n, bad = groups.get(g, (0, 0))
+        groups[g] = (n + 1, bad + (k in differ))
+    for g, (n, bad) in groups.items():
+        print(f"  {g:32s} {n:4d} arrays  {'identical' if not bad else '%d DIFFER' % bad}")
+    nbytes = sum(a[k].nbytes for k in a.files)
+    print(f"{len(a.files)} arrays, {nbytes} bytes: " + ("every array identical" if not differ else f"{len(differ)} arrays differ"))
+    for k in differ[:20]:
+        print("  differs:", k.replace("|", "/"))
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
