@@ -361,6 +361,93 @@ int  sfmba_resect(sfmba_handle* h, const double* x, const uint8_t* cam_select /*
                   double* cam_out /* (C,6): omega, centre T, the BA model's parameters */, int32_t* cam_status,
                   int32_t* cam_views, int32_t* cam_iters, double* cam_rms_err, int64_t* n_ok);
 
+/* ---- two-view geometry: F by RANSAC and pose recovery for a batch of edges (sfm.py:88-107, 120-180) -------------- */
+/* A batch of edges (image pairs) that is independent of the bundle-adjustment problem: neither call needs
+ * sfmba_set_problem, both ignore sfmba_set_precision (pairs are always fp64) and any transport, and both use buffers of
+ * their own, so fun, grad, the PCG record and a following solve are exactly what a fresh handle gives.  No atomics, sums
+ * in a fixed order: same input, same bits.
+ *   n_edges, edge_ptr (n_edges + 1, ascending, edge_ptr[0] = 0), pts1, pts2 ((M,2) with M = edge_ptr[n_edges]: the pixels
+ *   of pair k in image 1 and image 2), pair_use (M bytes, nonzero = take part; NULL = all).
+ * An edge's "used pairs" are its pairs with pair_use != 0 in stored order, numbered 0 .. n-1; a batch with a mask gives
+ * bit for bit what the batch with those pairs removed gives.
+ *
+ * sfmba_fundamental_ransac: the reference's estimate_fundamental_matrix_ransac (cv2_lite/fundamental_matrix_estimation.py)
+ * for every edge, H = max_iters hypotheses each, without early exit (the reference has none).
+ *   hypothesis  estimate_fundamental_matrix on eight used pairs: each image's eight points minus their column means, over
+ *               ONE scale, the standard deviation of all 16 coordinates together (np.std(pts) as the reference writes it;
+ *               neither per axis nor Hartley's sqrt 2); rows of construct_matrix_A; f = the eigenvector of the smallest
+ *               eigenvalue of A^T A (cyclic Jacobi on the 9x9 matrix, pairs (0,1), (0,2), .., (7,8), until the off-diagonal
+ *               part is 1e-40 of the diagonal, at most 30 sweeps); rank 2 by removing the smallest singular direction,
+ *               F <- F - (F v3) v3^T with v3 the smallest eigenvector of F^T F; then T2^T F T1.
+ *   score       THE REFERENCE'S RULE, NOT OpenCV's: the one-sided distance in image 2, |x2^T F x1| / sqrt(l0^2 + l1^2) with
+ *               l = F x1, is STRICTLY below threshold; a non-finite distance is no inlier.  (cv2.findFundamentalMat takes
+ *               the larger of the distances in both images.)
+ *   best        the largest inlier count, the lowest h among equals (Python's max keeps the first)
+ *   samples     given: (n_edges, H, 8) int32 positions among the used pairs; a position outside 0 .. n-1 makes the call
+ *               return -1, a sample with a repeated position is invalid: its count is -1.  NULL: drawn by a counter-based
+ *               rule, so that a result depends neither on the grid nor on the order of execution:
+ *                 mix(z): z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb; z ^= z >> 31
+ *                 key = mix(seed ^ mix(e << 32 | h)), e the edge's position in the batch
+ *                 draw j = 0..7: k = mix(key + (j + 1) 0x9e3779b97f4a7c15) mod (n - j); then, for every earlier choice c
+ *                 in ascending order of c, if (k >= c) ++k
+ *   refit = 1   F_refit: the same estimate_fundamental_matrix over ALL inliers of the best hypothesis (45 sums of A^T A
+ *               in a fixed order, the same Jacobi, rank 2, denormalised).  refit = 0: F_refit is a copy of F.
+ * F and F_refit (n_edges,9) have unit Frobenius norm and their entry of largest magnitude positive.  inlier_mask (M):
+ * the mask of the best hypothesis, 0 for pairs that took no part.  edge_inliers, edge_best: count and h of the best
+ * hypothesis.  edge_success: inliers / n >= confidence (the reference's `success`).  edge_status: 0 OK; 1 FEW_PAIRS
+ * (n < 8); 2 DEGENERATE (no hypothesis with a finite F and at least 8 inliers).  For a status other than 0, F and F_refit
+ * are zero; DEGENERATE still reports the count, h and mask of its best hypothesis (the reference returns that hypothesis
+ * whatever its count), FEW_PAIRS reports 0, -1 and an empty mask.  hyp_inliers (n_edges,H): the count of every hypothesis (-1:
+ * invalid sample, or FEW_PAIRS).  n_ok: edges with status 0.  kernel_us: with profile = 1 the HIP-event time of the call's
+ * launches, else 0.
+ *
+ * sfmba_recover_pose: the reference's recover_pose (cv2_lite/recover_pose.py) for every edge, E (n_edges,9) row-major, K (9).
+ *   decomposition  eigenvectors v1 v2 v3 of E^T E by a 3x3 Jacobi, by descending eigenvalue, v1 and v2 with their
+ *                  component of largest magnitude positive (the sign decides which rotation is R1), v3 flipped so that det V = +1;
+ *                  s_i = |E v_i|, u1 = E v1 / s1, u2 = E v2 / s2 made orthogonal to u1 and of unit length, u3 = u1 x u2; R1 = U W V^T,
+ *                  R2 = U W^T V^T with the W of decompose_essential_matrix (both determinants +1 by construction), t = u3;
+ *                  candidates in the order (R1,t), (R1,-t), (R2,t), (R2,-t)
+ *   choice         every used pair is triangulated against every candidate by the two-view DLT (the rows of
+ *                  triangulate_points_linear2 with M1 = K [I | 0], M2 = K [R | t]; smallest eigenvector of the 4x4 A^T A,
+ *                  unknowns neither translated nor rescaled).  A pair is in front when both depths are finite and
+ *                  > min_depth.  Most pairs in front wins, the earliest candidate among equals.  The reference refines the
+ *                  points before it counts; this call does not (sfmba_triangulate refines points).
+ * R (n_edges,9), t (n_edges,3): x2 = R x1 + t, |t| = 1.  front_mask (M), X (M,3; NaN for pairs that took no part),
+ * angle_deg (M): the angle between the rays X - O1 and X - O2 (O1 = 0, O2 = -R^T t) as atan2(|a x b|, a . b), NaN where
+ * the pair is not in front.  edge_front: the winner's count; edge_front_all (n_edges,4): every candidate's.
+ * edge_sum_err: the reference's reproj_err total (both images) over the used pairs.  edge_status, first match wins: 0 OK;
+ * 1 FEW_PAIRS (no used pair); 2 DEGENERATE (anything non-finite in E, or s2 <= 1e-12 s1; outputs zero / NaN); 3 TIE (the
+ * winner's count is not above the runner-up's; the winner is still returned).  n_ok, kernel_us as above.
+ *
+ * Every output pointer may be NULL, and an array that is not asked for is not downloaded.  opt = NULL: the defaults.
+ * Both return -1 for a malformed batch (edge_ptr not ascending from 0, NULL pixels), a NaN option or max_iters < 1. */
+typedef struct sfmba_ransac_options {
+    double   threshold;   /* pixels (default 1.0, the reference's; sfm.py passes 0.1) */
+    double   confidence;  /* edge_success = inliers / n >= confidence (0.99) */
+    uint64_t seed;        /* of the drawn samples (0) */
+    int32_t  max_iters;   /* hypotheses per edge, H, the same for all edges, at least 1 (1000) */
+    int32_t  refit;       /* 1 = F_refit over all inliers of the best hypothesis (0) */
+    int32_t  profile;     /* 1 = kernel_us is measured (0) */
+    int32_t  reserved;
+} sfmba_ransac_options;
+void sfmba_default_ransac_options(sfmba_ransac_options* opt);
+int  sfmba_fundamental_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edge_ptr, const double* pts1, const double* pts2,
+                              const uint8_t* pair_use /* M or NULL = all */, const int32_t* samples /* (n_edges,H,8) or NULL = drawn */,
+                              const sfmba_ransac_options* opt, double* F, double* F_refit, uint8_t* inlier_mask,
+                              int32_t* edge_inliers, int32_t* edge_best, uint8_t* edge_success, int32_t* edge_status,
+                              int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us);
+typedef struct sfmba_pose_options {
+    double  min_depth;   /* a pair is in front when both depths are above this (0.0) */
+    int32_t profile;     /* 1 = kernel_us is measured (0) */
+    int32_t reserved;
+} sfmba_pose_options;
+void sfmba_default_pose_options(sfmba_pose_options* opt);
+int  sfmba_recover_pose(sfmba_handle* h, int64_t n_edges, const int64_t* edge_ptr, const double* pts1, const double* pts2,
+                        const uint8_t* pair_use /* M or NULL = all */, const double* E, const double* K,
+                        const sfmba_pose_options* opt, double* R, double* t, uint8_t* front_mask, double* X, double* angle_deg,
+                        int32_t* edge_front, int32_t* edge_front_all, double* edge_sum_err, int32_t* edge_status,
+                        int64_t* n_ok, double* kernel_us);
+
 /* ---- least_squares(method='trf', x_scale='jac') (sfm.py:266-268) ---------------------------- */
 /* x_inout: x0 on entry, result.x on success (untouched on failure). */
 int  sfmba_solve(sfmba_handle* h, double* x_inout, const sfmba_options* opt, sfmba_result* out);

@@ -1170,4 +1170,659 @@ __global__ __launch_bounds__(kCamThreads) void k_resect(ResectIn in, int C, KMat
     report(status == kResOk);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Two-view geometry (sfmba_fundamental_ransac, sfmba_recover_pose).  A batch of edges (image
+// pairs), each a run of used pixel pairs x1 y1 x2 y2 (32 bytes, packed by the host in stored order); nothing of a
+// bundle-adjustment problem is read.
+//   k_fund_ransac   grid over (edge, slice of hypotheses); a wave takes one hypothesis at a time: eight sampled pairs ->
+//                   the reference's estimate_fundamental_matrix (one-scale normalisation, A^T A of the eight rows, its
+//                   smallest eigenvector by jacobi_lds<9>, rank 2 by a 3x3 Jacobi in registers, T2^T F T1), then the
+//                   lanes stride the edge's pairs and count |x2^T F x1| / |(F x1)_xy| < threshold by ballot / popcount.
+//                   A workgroup leaves the best (count, h, F) of its slice in a slot of its own.
+//   k_fund_finish   one workgroup per edge: best slot (largest count, lowest h), the mask of that F, the refit over all
+//                   its inliers (sums by block_sum, the 9x9 Jacobi by wave 0), unit norm and sign.
+//   k_recover_pose  one workgroup per edge: wave 0 decomposes E into the four (R, t), every pair is triangulated against
+//                   each (two-view DLT, smallest_eigenvector4) and counted in front; thread 0 decides; a second pass
+//                   writes the winner's points, mask, ray angles and the summed reprojection error.
+// No atomics; sums in a fixed order (wave_sum, then the waves in wave order); counts do not depend on the order.
+// ---------------------------------------------------------------------------------------------
+constexpr int kTwoViewThreads = 256;
+constexpr int kTwoViewWaves = 4;
+constexpr int kTwoViewLdsPairs = 4096;   // an edge of up to this many used pairs is staged in LDS (128 KiB of the 160)
+constexpr int kTwoViewMinSlice = 8;      // fewest hypotheses of a workgroup's slice (two per wave)
+constexpr int kTwoViewSlot = 12;         // doubles of a slot: count, h, F (9), unused
+constexpr int kJacobiLdsSweeps = 30;     // cap of the sweeps of jacobi_lds (a 9x9 converges in 5..9)
+constexpr int kFundOk = 0, kFundFewPairs = 1, kFundDegenerate = 2;
+constexpr int kPoseOk = 0, kPoseFewPairs = 1, kPoseDegenerate = 2, kPoseTie = 3;
+
+// resect_jacobi12 for any N <= 64: cyclic Jacobi on the symmetric N x N matrix A (full storage, LDS), eigenvectors in the
+// columns of V, by ONE wave, lane r < N owning row r of both.  (k_resect keeps resect_jacobi12 as it is written.)
+template <int N>
+__device__ __forceinline__ void jacobi_lds(volatile double* A, volatile double* V, int lane) {
+#pragma unroll 1
+    for (int sweep = 0; sweep < kJacobiLdsSweeps; ++sweep) {
+        double off = 0.0, dia = 0.0;
+        if (lane < N) {
+            for (int j = lane + 1; j < N; ++j) off += fabs(A[N * lane + j]);
+            dia = fabs(A[(N + 1) * lane]);
+        }
+        off = wave_sum(off);
+        dia = wave_sum(dia);
+        if (!(off > 1e-40 * dia)) break;                         // (a NaN ends the loop too)
+#pragma unroll 1
+        for (int p = 0; p < N - 1; ++p)
+#pragma unroll 1
+            for (int q = p + 1; q < N; ++q) {
+                const double app = A[(N + 1) * p], aqq = A[(N + 1) * q], apq = A[N * p + q];
+                double t, c, s;
+                jacobi_cs(app, aqq, apq, t, c, s);
+                double arp = 0.0, arq = 0.0, vrp = 0.0, vrq = 0.0;
+                if (lane < N) { arp = A[N * lane + p]; arq = A[N * lane + q]; vrp = V[N * lane + p]; vrq = V[N * lane + q]; }
+                if (lane < N) {
+                    V[N * lane + p] = c * vrp - s * vrq;
+                    V[N * lane + q] = s * vrp + c * vrq;
+                    if (lane == p) { A[(N + 1) * p] = app - t * apq; A[N * p + q] = 0.0; }
+                    else if (lane == q) { A[(N + 1) * q] = aqq + t * apq; A[N * q + p] = 0.0; }
+                    else {
+                        const double n1 = c * arp - s * arq, n2 = s * arp + c * arq;
+                        A[N * lane + p] = n1; A[N * p + lane] = n1;
+                        A[N * lane + q] = n2; A[N * q + lane] = n2;
+                    }
+                }
+            }
+    }
+}
+
+// the counter-based sample rule (include/sfmba.h): eight distinct positions among n >= 8, a function of (seed, e, h) alone
+__host__ __device__ __forceinline__ unsigned long long twoview_mix(unsigned long long z) {
+    z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
+    z ^= z >> 27; z *= 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    return z;
+}
+__device__ __forceinline__ void twoview_draw(unsigned long long seed, unsigned e, unsigned h, int n, int (&idx)[8]) {
+    const unsigned long long key = twoview_mix(seed ^ twoview_mix(((unsigned long long)e << 32) | (unsigned long long)h));
+    int srt[8];                                                  // the earlier choices, ascending
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        int k = (int)(twoview_mix(key + (unsigned long long)(j + 1) * 0x9e3779b97f4a7c15ull) % (unsigned long long)(n - j));
+#pragma unroll
+        for (int i = 0; i < j; ++i) if (k >= srt[i]) ++k;
+        idx[j] = k;
+        int v = k;
+#pragma unroll
+        for (int i = 0; i < j; ++i) if (v < srt[i]) { const int t = srt[i]; srt[i] = v; v = t; }
+        srt[j] = v;
+    }
+}
+
+// the row of construct_matrix_A of one normalised pair
+__device__ __forceinline__ void fund_row(double x1, double y1, double x2, double y2, double (&r)[9]) {
+    r[0] = x2 * x1; r[1] = x2 * y1; r[2] = x2; r[3] = y2 * x1; r[4] = y2 * y1; r[5] = y2; r[6] = x1; r[7] = y1; r[8] = 1.0;
+}
+// After jacobi_lds<9>: f = the eigenvector of the smallest eigenvalue, rank 2 forced by removing the smallest singular
+// direction (F <- F - (F v3) v3^T, v3 the smallest eigenvector of F^T F), then T2^T F T1 with T = [[1/s, 0, -mx/s],
+// [0, 1/s, -my/s], [0, 0, 1]].  Every lane of the calling wave leaves with the same F.
+__device__ __forceinline__ void fund_from_jacobi(const volatile double* A, const volatile double* V, double m1x, double m1y,
+                                                 double s1, double m2x, double m2y, double s2, double (&F)[9]) {
+    int lo = 0;
+    double least = A[0];
+#pragma unroll
+    for (int k = 1; k < 9; ++k) { const double d = A[10 * k]; if (d < least) { least = d; lo = k; } }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) F[k] = V[9 * k + lo];
+    double a[6], w[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) a[sym<3>(i, j)] = F[i] * F[j] + F[3 + i] * F[3 + j] + F[6 + i] * F[6 + j];
+    jacobi_sweeps<3>(a, w);
+    // (the columns as values behind an empty statement: without it the compiler selects an ADDRESS by the comparisons
+    // below and reads the column from scratch memory)
+    double w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4], w5 = w[5], w6 = w[6], w7 = w[7], w8 = w[8];
+    asm volatile("" : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3), "+v"(w4), "+v"(w5), "+v"(w6), "+v"(w7), "+v"(w8));
+    double l3 = a[0], v0 = w0, v1 = w3, v2 = w6;
+    if (a[3] < l3) { l3 = a[3]; v0 = w1; v1 = w4; v2 = w7; }
+    if (a[5] < l3) { l3 = a[5]; v0 = w2; v1 = w5; v2 = w8; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double fv = F[3 * i] * v0 + F[3 * i + 1] * v1 + F[3 * i + 2] * v2;
+        F[3 * i] -= fv * v0; F[3 * i + 1] -= fv * v1; F[3 * i + 2] -= fv * v2;
+    }
+    const double a1 = 1.0 / s1, b1 = -m1x / s1, c1 = -m1y / s1, a2 = 1.0 / s2, b2 = -m2x / s2, c2 = -m2y / s2;
+    double G[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        G[3 * i] = F[3 * i] * a1; G[3 * i + 1] = F[3 * i + 1] * a1;
+        G[3 * i + 2] = F[3 * i] * b1 + F[3 * i + 1] * c1 + F[3 * i + 2];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        F[j] = a2 * G[j]; F[3 + j] = a2 * G[3 + j];
+        F[6 + j] = b2 * G[j] + c2 * G[3 + j] + G[6 + j];
+    }
+}
+// the reference's score: the distance of x2 from the line F x1, one-sided, strictly below the threshold; a non-finite
+// distance is no inlier (NaN compares false; +inf < thr is false)
+__device__ __forceinline__ bool fund_inlier(const double (&F)[9], double x1, double y1, double x2, double y2, double thr) {
+    const double l0 = F[0] * x1 + F[1] * y1 + F[2], l1 = F[3] * x1 + F[4] * y1 + F[5], l2 = F[6] * x1 + F[7] * y1 + F[8];
+    const double d = fabs(x2 * l0 + y2 * l1 + l2) / sqrt(l0 * l0 + l1 * l1);
+    return d < thr && d < INFINITY;
+}
+// unit Frobenius norm, the entry of largest magnitude (the first of equals) positive
+__device__ __forceinline__ void fund_unit(double (&F)[9]) {
+    double ss = 0.0, big = 0.0, sgn = 1.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { ss += F[k] * F[k]; if (fabs(F[k]) > big) { big = fabs(F[k]); sgn = F[k] < 0.0 ? -1.0 : 1.0; } }
+    const double nrm = sqrt(ss) * sgn;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) F[k] = F[k] / nrm;
+}
+
+struct FundIn {
+    const double* __restrict__ pairs;            // [M_used][4] x1 y1 x2 y2
+    const int* __restrict__ uptr;                // [n_edges + 1] runs of used pairs
+    const int* __restrict__ samples;             // [n_edges][H][8] positions among the used pairs, or null: drawn
+};
+
+// the hypotheses h0 + w, h0 + w + 4, ... < h1 of edge e by wave w; P: the edge's pairs (LDS or global)
+__device__ __forceinline__ void fund_slice(const double* P, const FundIn& in, int e, int n, int H, int h0, int h1,
+                                           unsigned long long seed, double thr, volatile double* A, volatile double* V,
+                                           volatile double* R, int* __restrict__ hyp, int& bc, int& bh, double (&bF)[9]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const double2* __restrict__ P2 = reinterpret_cast<const double2*>(P);
+    bc = -1; bh = 0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) bF[k] = 0.0;
+#pragma unroll 1
+    for (int h = h0 + w; h < h1; h += kTwoViewWaves) {
+        int idx[8];
+        bool valid = true;
+        if (in.samples != nullptr) {
+            const int* __restrict__ sp = in.samples + ((size_t)e * (size_t)H + (size_t)h) * 8;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { idx[j] = sp[j]; valid = valid && idx[j] >= 0 && idx[j] < n; }
+#pragma unroll
+            for (int j = 1; j < 8; ++j)
+#pragma unroll
+                for (int i = 0; i < j; ++i) valid = valid && idx[i] != idx[j];
+        } else {
+            twoview_draw(seed, (unsigned)e, (unsigned)h, n, idx);
+        }
+        if (!valid) {                                            // (uniform over the wave)
+            if (lane == 0 && hyp != nullptr) hyp[(size_t)e * (size_t)H + (size_t)h] = -1;
+            continue;
+        }
+        double x1[8], y1[8], x2[8], y2[8];
+        double m1x = 0.0, m1y = 0.0, m2x = 0.0, m2y = 0.0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const double2 qa = P2[2 * idx[j]], qb = P2[2 * idx[j] + 1];
+            x1[j] = qa.x; y1[j] = qa.y; x2[j] = qb.x; y2[j] = qb.y;
+            m1x += qa.x; m1y += qa.y; m2x += qb.x; m2y += qb.y;
+        }
+        const double g1 = (m1x + m1y) / 16.0, g2 = (m2x + m2y) / 16.0;     // np.std: about the mean of all 16 coordinates
+        m1x /= 8.0; m1y /= 8.0; m2x /= 8.0; m2y /= 8.0;
+        double q1 = 0.0, q2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            q1 += (x1[j] - g1) * (x1[j] - g1) + (y1[j] - g1) * (y1[j] - g1);
+            q2 += (x2[j] - g2) * (x2[j] - g2) + (y2[j] - g2) * (y2[j] - g2);
+        }
+        const double s1 = sqrt(q1 / 16.0), s2 = sqrt(q2 / 16.0);
+        // the eight rows through LDS (lane 0 stores them), then lane i < 9 sums row i of A^T A over the rows 0..7
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            double r[9];
+            fund_row((x1[j] - m1x) / s1, (y1[j] - m1y) / s1, (x2[j] - m2x) / s2, (y2[j] - m2y) / s2, r);
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i) R[9 * j + i] = r[i];
+            }
+        }
+        if (lane < 9) {
+            double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const double ri = R[9 * j + lane];
+#pragma unroll
+                for (int c = 0; c < 9; ++c) acc[c] += ri * R[9 * j + c];
+            }
+#pragma unroll
+            for (int c = 0; c < 9; ++c) { A[9 * lane + c] = acc[c]; V[9 * lane + c] = c == lane ? 1.0 : 0.0; }
+        }
+        jacobi_lds<9>(A, V, lane);
+        double F[9];
+        fund_from_jacobi(A, V, m1x, m1y, s1, m2x, m2y, s2, F);
+        int cnt = 0;
+#pragma unroll 1
+        for (int k0 = 0; k0 < n; k0 += 64) {                     // uniform over the wave: the ballot needs every lane
+            const int k = k0 + lane;
+            bool inl = false;
+            if (k < n) { const double2 qa = P2[2 * k], qb = P2[2 * k + 1]; inl = fund_inlier(F, qa.x, qa.y, qb.x, qb.y, thr); }
+            cnt += __popcll(__ballot(inl));
+        }
+        if (lane == 0 && hyp != nullptr) hyp[(size_t)e * (size_t)H + (size_t)h] = cnt;
+        if (cnt > bc) {                                          // (h ascends: the lowest h of equal counts stays)
+            bc = cnt; bh = h;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) bF[k] = F[k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(kTwoViewThreads) void k_fund_ransac(FundIn in, int H, int hs, int n_slices, unsigned long long seed,
+                                                                 double thr, double* __restrict__ slots, int* __restrict__ hyp) {
+    extern __shared__ __align__(16) double smem[];
+    __shared__ double jA[kTwoViewWaves][81], jV[kTwoViewWaves][81], jR[kTwoViewWaves][72];
+    __shared__ double wbest[kTwoViewWaves][kTwoViewSlot];
+    const int e = blockIdx.x / n_slices, sl = blockIdx.x - e * n_slices;
+    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
+    const int h0 = sl * hs, h1 = min(H, h0 + hs);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    double* __restrict__ slot = slots + (size_t)blockIdx.x * kTwoViewSlot;
+    if (n < 8) {                                                 // (uniform over the workgroup) FEW_PAIRS: no hypothesis
+        if (hyp != nullptr)
+            for (int h = h0 + (int)threadIdx.x; h < h1; h += kTwoViewThreads) hyp[(size_t)e * (size_t)H + (size_t)h] = -1;
+        if (threadIdx.x == 0) {
+            slot[0] = -1.0; slot[1] = 0.0;
+#pragma unroll
+            for (int k = 2; k < kTwoViewSlot; ++k) slot[k] = 0.0;
+        }
+        return;
+    }
+    const double* __restrict__ gp = in.pairs + 4 * (size_t)b;
+    int bc, bh;
+    double bF[9];
+    if (n <= kTwoViewLdsPairs) {
+        stage_table(gp, 4 * n, smem);
+        fund_slice(smem, in, e, n, H, h0, h1, seed, thr, jA[w], jV[w], jR[w], hyp, bc, bh, bF);
+    } else {
+        fund_slice(gp, in, e, n, H, h0, h1, seed, thr, jA[w], jV[w], jR[w], hyp, bc, bh, bF);
+    }
+    if (lane == 0) {
+        wbest[w][0] = (double)bc; wbest[w][1] = (double)bh;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wbest[w][2 + k] = bF[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int best = 0;
+        for (int k = 1; k < kTwoViewWaves; ++k)
+            if (wbest[k][0] > wbest[best][0] || (wbest[k][0] == wbest[best][0] && wbest[k][1] < wbest[best][1])) best = k;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) slot[k] = wbest[best][k];
+        slot[11] = 0.0;
+    }
+}
+
+// rows I0 .. I1 - 1 of the upper triangle of A^T A over the pairs of the mask mk (its own stores), thread t taking pairs t, t + 256, ...; thread 0
+// stores them (and their mirror) into A
+template <int I0, int I1>
+__device__ __forceinline__ void fund_ata_rows(const double2* __restrict__ P2, int n, const unsigned char* mk, double m1x,
+                                              double m1y, double s1, double m2x, double m2y, double s2, double* red, double* A) {
+    constexpr int NS = sym<9>(I1 - 1, 8) - sym<9>(I0, I0) + 1, Q0 = sym<9>(I0, I0);
+    double s[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) s[q] = 0.0;
+#pragma unroll 1
+    for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+        const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+        if (!mk[k]) continue;
+        double r[9];
+        fund_row((qa.x - m1x) / s1, (qa.y - m1y) / s1, (qb.x - m2x) / s2, (qb.y - m2y) / s2, r);
+#pragma unroll
+        for (int i = I0; i < I1; ++i)
+#pragma unroll
+            for (int c = i; c < 9; ++c) s[sym<9>(i, c) - Q0] += r[i] * r[c];
+    }
+    block_sum<NS>(s, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = I0; i < I1; ++i)
+#pragma unroll
+            for (int c = i; c < 9; ++c) { A[9 * i + c] = s[sym<9>(i, c) - Q0]; A[9 * c + i] = s[sym<9>(i, c) - Q0]; }
+    }
+}
+
+struct FundOut {
+    double* __restrict__ F;                      // [E][9]
+    double* __restrict__ F_refit;                // [E][9]
+    unsigned char* __restrict__ mask;            // [M_used]
+    int* __restrict__ ints;                      // [E][4] inliers, best h, status, success
+};
+
+__global__ __launch_bounds__(kTwoViewThreads) void k_fund_finish(FundIn in, int n_slices, double thr, double confidence, int refit,
+                                                                 const double* __restrict__ slots, FundOut out) {
+    __shared__ double red[kTwoViewWaves * 18];
+    __shared__ double jA[81], jV[81];
+    __shared__ double sF[9], sm[9];
+    __shared__ int ctl[2];
+    const int e = blockIdx.x;
+    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
+    const bool first = threadIdx.x == 0;
+    const double2* __restrict__ P2 = reinterpret_cast<const double2*>(in.pairs + 4 * (size_t)b);
+    if (first) {
+        const double* __restrict__ sl = slots + (size_t)e * (size_t)n_slices * kTwoViewSlot;
+        int best = 0;
+        for (int k = 1; k < n_slices; ++k)                       // slots ascend in h: the first of equal counts has the lowest
+            if (sl[(size_t)k * kTwoViewSlot] > sl[(size_t)best * kTwoViewSlot]) best = k;
+        const double* __restrict__ bs = sl + (size_t)best * kTwoViewSlot;
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { sF[k] = bs[2 + k]; sum += fabs(bs[2 + k]); }
+        ctl[0] = n < 8 ? kFundFewPairs : (sum < INFINITY ? kFundOk : kFundDegenerate);
+        ctl[1] = bs[0] >= 0.0 ? (int)bs[1] : -1;                 // (-1: no valid sample in any slot)
+    }
+    __syncthreads();
+    const unsigned char* mk = out.mask + (size_t)b;              // a thread reads back only what it stored itself
+    if (ctl[0] == kFundFewPairs) {                               // (uniform over the workgroup)
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) out.mask[(size_t)b + k] = 0;
+        if (threadIdx.x < 9) { out.F[9 * (size_t)e + threadIdx.x] = 0.0; out.F_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
+        if (first) { int* __restrict__ oi = out.ints + 4 * (size_t)e; oi[0] = 0; oi[1] = -1; oi[2] = kFundFewPairs; oi[3] = 0; }
+        return;
+    }
+    // The mask of the best F, and the count FROM that mask: edge_inliers, edge_success, the status and the refit below all
+    // rest on this one evaluation (the count in the slot came from another copy of the expression, which the compiler may
+    // have contracted differently for a pair within an ulp of the threshold).
+    double F[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) F[k] = sF[k];
+    {
+        double c[1] = {0.0};
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+            const bool inl = ctl[1] >= 0 && fund_inlier(F, qa.x, qa.y, qb.x, qb.y, thr);
+            out.mask[(size_t)b + k] = inl ? 1 : 0;
+            c[0] += inl ? 1.0 : 0.0;
+        }
+        block_sum<1>(c, red);
+        if (first) {
+            const int cnt = (int)c[0];
+            if (ctl[0] == kFundOk && cnt < 8) ctl[0] = kFundDegenerate;
+            sm[8] = (double)cnt;
+            int* __restrict__ oi = out.ints + 4 * (size_t)e;
+            // (DEGENERATE still reports the count, h and mask of its best hypothesis; only F is withheld)
+            oi[0] = cnt; oi[1] = ctl[1]; oi[2] = ctl[0];
+            oi[3] = (ctl[1] >= 0 && (double)cnt / (double)n >= confidence) ? 1 : 0;
+        }
+        __syncthreads();
+    }
+    const int status = ctl[0], cnt = (int)sm[8];
+    if (status != kFundOk) {
+        if (threadIdx.x < 9) { out.F[9 * (size_t)e + threadIdx.x] = 0.0; out.F_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
+        return;
+    }
+    double Fu[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Fu[k] = F[k];
+    fund_unit(Fu);
+    if (first) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) out.F[9 * (size_t)e + k] = Fu[k];
+    }
+    if (!refit) {
+        if (first) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) out.F_refit[9 * (size_t)e + k] = Fu[k];
+        }
+        return;
+    }
+    // the reference's estimate_fundamental_matrix over the cnt >= 8 inliers: thread t takes pairs t, t + 256, ...
+    {
+        double v[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+            if (mk[k]) { v[0] += qa.x; v[1] += qa.y; v[2] += qb.x; v[3] += qb.y; }
+        }
+        block_sum<4>(v, red);
+        if (first) {
+            const double c = (double)cnt;
+            sm[0] = v[0] / c; sm[1] = v[1] / c; sm[2] = v[2] / c; sm[3] = v[3] / c;
+            sm[4] = (v[0] + v[1]) / (2.0 * c); sm[5] = (v[2] + v[3]) / (2.0 * c);
+        }
+        __syncthreads();
+    }
+    const double m1x = sm[0], m1y = sm[1], m2x = sm[2], m2y = sm[3];
+    {
+        const double g1 = sm[4], g2 = sm[5];
+        double v[2] = {0.0, 0.0};
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+            if (mk[k]) {
+                v[0] += (qa.x - g1) * (qa.x - g1) + (qa.y - g1) * (qa.y - g1);
+                v[1] += (qb.x - g2) * (qb.x - g2) + (qb.y - g2) * (qb.y - g2);
+            }
+        }
+        block_sum<2>(v, red);
+        if (first) { sm[6] = sqrt(v[0] / (2.0 * (double)cnt)); sm[7] = sqrt(v[1] / (2.0 * (double)cnt)); }
+        __syncthreads();
+    }
+    const double s1 = sm[6], s2 = sm[7];
+    // the 45 sums in three passes (rows 0-1, 2-4, 5-8 of the upper triangle): all of them at once in registers spilled
+    fund_ata_rows<0, 2>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
+    fund_ata_rows<2, 5>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
+    fund_ata_rows<5, 9>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
+    if (first)
+        for (int k = 0; k < 81; ++k) jV[k] = (k % 10) == 0 ? 1.0 : 0.0;
+    if (threadIdx.x < 64) {                                      // wave 0: thread 0's stores above are its own
+        jacobi_lds<9>(jA, jV, (int)threadIdx.x);
+        double Fr[9];
+        fund_from_jacobi(jA, jV, m1x, m1y, s1, m2x, m2y, s2, Fr);
+        fund_unit(Fr);
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) sum += fabs(Fr[k]);
+        if (first) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) out.F_refit[9 * (size_t)e + k] = sum < INFINITY ? Fr[k] : Fu[k];
+        }
+    }
+}
+
+// ---- sfmba_recover_pose ----
+struct PoseOut {
+    double* __restrict__ Rt;                     // [E][12] R (9), t (3)
+    double* __restrict__ sum_err;                // [E]
+    int* __restrict__ ints;                      // [E][6] front of the winner, front of the four candidates, status
+    unsigned char* __restrict__ front;           // [M_used]
+    double* __restrict__ X;                      // [M_used][3]
+    double* __restrict__ angle_deg;              // [M_used]
+};
+
+// The two-view DLT of one pair against M1 = [K | 0] and M2 (rows of 4): the rows of triangulate_points_linear2,
+// the smallest eigenvector of their A^T A, X = w[:3] / w[3]
+__device__ __forceinline__ void pose_dlt(const KMat& K, const double* __restrict__ M2, double x1, double y1, double x2, double y2,
+                                         double& X, double& Y, double& Z) {
+    double rows[4][4];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { rows[0][j] = x1 * K.k[6 + j] - K.k[j]; rows[1][j] = y1 * K.k[6 + j] - K.k[3 + j]; }
+    rows[0][3] = 0.0; rows[1][3] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { rows[2][j] = x2 * M2[8 + j] - M2[j]; rows[3][j] = y2 * M2[8 + j] - M2[4 + j]; }
+    double a[10];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = i; j < 4; ++j)
+            a[sym<4>(i, j)] = rows[0][i] * rows[0][j] + rows[1][i] * rows[1][j] + rows[2][i] * rows[2][j] + rows[3][i] * rows[3][j];
+    double w0, w1, w2, w3;
+    smallest_eigenvector4(a, w0, w1, w2, w3);
+    X = w0 / w3; Y = w1 / w3; Z = w2 / w3;
+}
+// candidate row c of LDS: R (9), t (3), M2 = K [R | t] (12)
+constexpr int kPoseCand = 24;
+__device__ __forceinline__ bool pose_in_front(const double* __restrict__ cd, double X, double Y, double Z, double min_depth) {
+    const double d2 = cd[6] * X + cd[7] * Y + cd[8] * Z + cd[11];
+    return Z > min_depth && d2 > min_depth && Z < INFINITY && d2 < INFINITY;
+}
+
+__global__ __launch_bounds__(kTwoViewThreads) void k_recover_pose(const double* __restrict__ pairs, const int* __restrict__ uptr,
+                                                                  const double* __restrict__ Emat, KMat K, double min_depth, PoseOut out) {
+    __shared__ double cand[4 * kPoseCand];
+    __shared__ double red[kTwoViewWaves];
+    __shared__ int redi[kTwoViewWaves][4];
+    __shared__ int ctl[2];
+    constexpr double kDeg = 57.295779513082320877;
+    const int e = blockIdx.x;
+    const int b = uptr[e], n = uptr[e + 1] - b;
+    const bool first = threadIdx.x == 0;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const double2* __restrict__ P2 = reinterpret_cast<const double2*>(pairs + 4 * (size_t)b);
+    if (threadIdx.x < 64) {                                      // wave 0, every lane alike; lane 0 stores
+        double E[9], sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { E[k] = Emat[9 * (size_t)e + k]; sum += fabs(E[k]); }
+        double a[6], v[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = i; j < 3; ++j) a[sym<3>(i, j)] = E[i] * E[j] + E[3 + i] * E[3 + j] + E[6 + i] * E[6 + j];
+        jacobi_sweeps<3>(a, v);
+        // eigenpairs by descending eigenvalue (the first of equals first)
+        double l0 = a[0], l1 = a[3], l2 = a[5];
+        double c0[3] = {v[0], v[3], v[6]}, c1[3] = {v[1], v[4], v[7]}, c2[3] = {v[2], v[5], v[8]};
+        auto order = [](double& la, double& lb, double (&ca)[3], double (&cb)[3]) {
+            if (lb > la) {
+                const double t = la; la = lb; lb = t;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { const double u = ca[k]; ca[k] = cb[k]; cb[k] = u; }
+            }
+        };
+        order(l0, l1, c0, c1); order(l1, l2, c1, c2); order(l0, l1, c0, c1);
+        // the sign of an eigenvector is the solver's accident, and flipping v1 swaps R1 with R2 and t with -t: v1 and v2
+        // get their component of largest magnitude (the first of equals) positive, v3 follows from det V = +1
+        auto positive = [](double (&c)[3]) {
+            double big = fabs(c[0]), sg = c[0];
+            if (fabs(c[1]) > big) { big = fabs(c[1]); sg = c[1]; }
+            if (fabs(c[2]) > big) { big = fabs(c[2]); sg = c[2]; }
+            if (sg < 0.0) { c[0] = -c[0]; c[1] = -c[1]; c[2] = -c[2]; }
+        };
+        positive(c0); positive(c1);
+        const double det = c0[0] * (c1[1] * c2[2] - c1[2] * c2[1]) - c0[1] * (c1[0] * c2[2] - c1[2] * c2[0]) +
+                           c0[2] * (c1[0] * c2[1] - c1[1] * c2[0]);
+        if (det < 0.0) { c2[0] = -c2[0]; c2[1] = -c2[1]; c2[2] = -c2[2]; }
+        // s_i = |E v_i|, not sqrt(lambda_i): an eigenvalue of E^T E carries eps s1^2 of rounding, so its root cannot tell an
+        // s2 below 1e-8 s1 from zero, while |E v2| is good to a few eps s1
+        double u1[3], u2[3], u3[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            u1[i] = E[3 * i] * c0[0] + E[3 * i + 1] * c0[1] + E[3 * i + 2] * c0[2];
+            u2[i] = E[3 * i] * c1[0] + E[3 * i + 1] * c1[1] + E[3 * i + 2] * c1[2];
+        }
+        const double sg1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]), sg2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+        const bool good = sum < INFINITY && sg2 > 1e-12 * sg1;   // (false for a NaN as well)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { u1[i] /= sg1; u2[i] /= sg2; }
+        const double d12 = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) u2[i] -= d12 * u1[i];
+        const double n2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) u2[i] /= n2;
+        u3[0] = u1[1] * u2[2] - u1[2] * u2[1]; u3[1] = u1[2] * u2[0] - u1[0] * u2[2]; u3[2] = u1[0] * u2[1] - u1[1] * u2[0];
+        if (first) {
+            ctl[0] = n < 1 ? kPoseFewPairs : (good ? kPoseOk : kPoseDegenerate);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                double* __restrict__ cd = cand + c * kPoseCand;
+                const double sr = c < 2 ? 1.0 : -1.0, st = (c & 1) ? -1.0 : 1.0;
+                // R1 = U W V^T = u2 v1^T - u1 v2^T + u3 v3^T, R2 = U W^T V^T = -u2 v1^T + u1 v2^T + u3 v3^T
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) cd[3 * i + j] = sr * (u2[i] * c0[j] - u1[i] * c1[j]) + u3[i] * c2[j];
+                    cd[9 + i] = st * u3[i];
+                }
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) cd[12 + 4 * i + j] = K.k[3 * i] * cd[j] + K.k[3 * i + 1] * cd[3 + j] + K.k[3 * i + 2] * cd[6 + j];
+                    cd[12 + 4 * i + 3] = K.k[3 * i] * cd[9] + K.k[3 * i + 1] * cd[10] + K.k[3 * i + 2] * cd[11];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (ctl[0] != kPoseOk) {                                     // (uniform over the workgroup)
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            out.front[(size_t)b + k] = 0;
+            out.X[3 * ((size_t)b + k)] = NAN; out.X[3 * ((size_t)b + k) + 1] = NAN; out.X[3 * ((size_t)b + k) + 2] = NAN;
+            out.angle_deg[(size_t)b + k] = NAN;
+        }
+        if (first) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) out.Rt[12 * (size_t)e + k] = 0.0;
+            out.sum_err[e] = NAN;
+            int* __restrict__ oi = out.ints + 6 * (size_t)e;
+            oi[0] = 0; oi[1] = 0; oi[2] = 0; oi[3] = 0; oi[4] = 0; oi[5] = ctl[0];
+        }
+        return;
+    }
+    // pass 1: pairs in front of each candidate
+    int cnt[4] = {0, 0, 0, 0};
+#pragma unroll 1
+    for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+        const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+#pragma unroll 1
+        for (int c = 0; c < 4; ++c) {
+            const double* __restrict__ cd = cand + c * kPoseCand;
+            double X, Y, Z;
+            pose_dlt(K, cd + 12, qa.x, qa.y, qb.x, qb.y, X, Y, Z);
+            const int f = pose_in_front(cd, X, Y, Z, min_depth) ? 1 : 0;
+            cnt[0] += c == 0 ? f : 0; cnt[1] += c == 1 ? f : 0; cnt[2] += c == 2 ? f : 0; cnt[3] += c == 3 ? f : 0;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) cnt[c] = wave_isum(cnt[c]);
+    if (lane == 0) { redi[w][0] = cnt[0]; redi[w][1] = cnt[1]; redi[w][2] = cnt[2]; redi[w][3] = cnt[3]; }
+    __syncthreads();
+    if (first) {
+        int tot[4], win = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { tot[c] = 0; for (int k = 0; k < kTwoViewWaves; ++k) tot[c] += redi[k][c]; }
+#pragma unroll
+        for (int c = 1; c < 4; ++c) if (tot[c] > tot[win]) win = c;            // the earliest of equal counts
+        int second = -1;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) if (c != win && tot[c] > second) second = tot[c];
+        ctl[1] = win;
+        int* __restrict__ oi = out.ints + 6 * (size_t)e;
+        oi[0] = tot[win]; oi[1] = tot[0]; oi[2] = tot[1]; oi[3] = tot[2]; oi[4] = tot[3];
+        oi[5] = tot[win] > second ? kPoseOk : kPoseTie;
+    }
+    __syncthreads();
+    // pass 2: the winner's points, mask, ray angles and the reference's reproj_err total
+    const double* __restrict__ cd = cand + ctl[1] * kPoseCand;
+    const double O2x = -(cd[0] * cd[9] + cd[3] * cd[10] + cd[6] * cd[11]), O2y = -(cd[1] * cd[9] + cd[4] * cd[10] + cd[7] * cd[11]),
+                 O2z = -(cd[2] * cd[9] + cd[5] * cd[10] + cd[8] * cd[11]);
+    double err[1] = {0.0};
+#pragma unroll 1
+    for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+        const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+        double X, Y, Z;
+        pose_dlt(K, cd + 12, qa.x, qa.y, qb.x, qb.y, X, Y, Z);
+        const bool f = pose_in_front(cd, X, Y, Z, min_depth);
+        const double bx = X - O2x, by = Y - O2y, bz = Z - O2z;
+        const double cx = Y * bz - Z * by, cy = Z * bx - X * bz, cz = X * by - Y * bx;
+        const double ang = kDeg * atan2(sqrt(cx * cx + cy * cy + cz * cz), X * bx + Y * by + Z * bz);
+        const double p1w = K.k[6] * X + K.k[7] * Y + K.k[8] * Z;
+        const double e1x = qa.x - (K.k[0] * X + K.k[1] * Y + K.k[2] * Z) / p1w, e1y = qa.y - (K.k[3] * X + K.k[4] * Y + K.k[5] * Z) / p1w;
+        const double* __restrict__ M2 = cd + 12;
+        const double p2w = M2[8] * X + M2[9] * Y + M2[10] * Z + M2[11];
+        const double e2x = qb.x - (M2[0] * X + M2[1] * Y + M2[2] * Z + M2[3]) / p2w, e2y = qb.y - (M2[4] * X + M2[5] * Y + M2[6] * Z + M2[7]) / p2w;
+        err[0] += sqrt(e1x * e1x + e1y * e1y) + sqrt(e2x * e2x + e2y * e2y);
+        const size_t o = (size_t)b + k;
+        out.front[o] = f ? 1 : 0;
+        out.X[3 * o] = X; out.X[3 * o + 1] = Y; out.X[3 * o + 2] = Z;
+        out.angle_deg[o] = f ? ang : NAN;
+    }
+    block_sum<1>(err, red);
+    if (first) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) out.Rt[12 * (size_t)e + k] = cd[k];
+        out.sum_err[e] = err[0];
+    }
+}
+
 }  // namespace sfmba

@@ -471,6 +471,16 @@ struct sfmba_handle {
         DevBuf select;                       // [C]
         DevBuf cam, ints, rms;               // [C][6]; [4][C] status, views, iters, ok; [C]
     } resect;
+    // sfmba_fundamental_ransac / sfmba_recover_pose: a batch of edges that has nothing to do with the problem; every
+    // buffer is the two calls' own
+    struct TwoView {
+        DevBuf pairs, uptr, samples, E;      // [M_used][4] x1 y1 x2 y2; [n_edges + 1]; [n_edges][H][8]; [n_edges][9]
+        DevBuf slots, hyp;                   // [n_edges][slices][kTwoViewSlot]; [n_edges][H]
+        DevBuf F, ints, mask;                // [2][n_edges][9] F, F_refit; [n_edges][4]; [M_used]
+        DevBuf Rt, err, pose_ints, X, ang;   // [n_edges][12]; [n_edges]; [n_edges][6]; [M_used][3]; [M_used]
+        PinnedBuf in_host, out_host;         // staging of the packed batch; of the results
+        std::vector<int64_t> pos;            // used pair -> stored pair, when the call has a pair_use mask
+    } twoview;
 };
 
 namespace {
@@ -2897,6 +2907,255 @@ int sfmba_resect(sfmba_handle* h, const double* x, const uint8_t* cam_select, co
     HIPCHK(h, download(h, cam_iters, pi + 2 * C, sizeof(int32_t) * C));
     HIPCHK(h, download(h, cam_rms_err, r.rms.p, sizeof(double) * C));
     return finish_with_ok_count(h, pi + 3 * C, C, counts, n_ok);
+}
+
+namespace {
+// ---- two-view geometry (sfmba_fundamental_ransac, sfmba_recover_pose; kernels: consumer_kernels.hpp, "Two-view geometry") ----
+struct TwoViewBatch { size_t E = 0, M = 0, Mu = 0; bool masked = false; int max_n = 0; };
+
+// The batch onto the device: the used pairs of every edge packed x1 y1 x2 y2 in stored order -> twoview.pairs, their runs
+// -> twoview.uptr; twoview.pos maps a used pair back to its stored place when there is a mask.
+int twoview_stage(sfmba_handle* h, const char* who, int64_t n_edges, const int64_t* edge_ptr, const double* pts1,
+                  const double* pts2, const uint8_t* pair_use, TwoViewBatch* bt) {
+    auto& t = h->twoview;
+    if (n_edges < 0 || !edge_ptr) return fail(h, -1, "%s: n_edges is negative or edge_ptr is NULL", who);
+    if (edge_ptr[0] != 0) return fail(h, -1, "%s: edge_ptr[0] must be 0", who);
+    for (int64_t e = 0; e < n_edges; ++e)
+        if (edge_ptr[e + 1] < edge_ptr[e]) return fail(h, -1, "%s: edge_ptr must ascend (edge %lld)", who, (long long)e);
+    const size_t E = (size_t)n_edges, M = (size_t)edge_ptr[n_edges];
+    if (M >= (size_t)1 << 31 || E >= (size_t)1 << 31) return fail(h, -1, "%s: the batch has 2^31 pairs or edges, or more", who);
+    if (M && (!pts1 || !pts2)) return fail(h, -1, "%s: pts1 or pts2 is NULL", who);
+    const size_t off_ptr = sizeof(double) * 4 * M;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, t.in_host.ensure(off_ptr + sizeof(int) * (E + 1), 0));
+    double* const pk = t.in_host.as<double>();
+    int* const up = reinterpret_cast<int*>(t.in_host.as<unsigned char>() + off_ptr);
+    t.pos.clear();
+    size_t u = 0;
+    int max_n = 0;
+    for (size_t e = 0; e < E; ++e) {
+        up[e] = (int)u;
+        for (size_t k = (size_t)edge_ptr[e]; k < (size_t)edge_ptr[e + 1]; ++k) {
+            if (pair_use && !pair_use[k]) continue;
+            pk[4 * u] = pts1[2 * k]; pk[4 * u + 1] = pts1[2 * k + 1]; pk[4 * u + 2] = pts2[2 * k]; pk[4 * u + 3] = pts2[2 * k + 1];
+            if (pair_use) t.pos.push_back((int64_t)k);
+            ++u;
+        }
+        max_n = std::max(max_n, (int)u - up[e]);
+    }
+    up[E] = (int)u;
+    CHK(ensure_all(h, {{&t.pairs, sizeof(double) * 4 * std::max<size_t>(u, 1)}, {&t.uptr, sizeof(int) * (E + 1)}}));
+    if (u) HIPCHK(h, hipMemcpyAsync(t.pairs.p, pk, sizeof(double) * 4 * u, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(t.uptr.p, up, sizeof(int) * (E + 1), hipMemcpyHostToDevice, h->stream));
+    bt->E = E; bt->M = M; bt->Mu = u; bt->masked = pair_use != nullptr; bt->max_n = max_n;
+    return 0;
+}
+
+// the events of profile = 1 round a call's launches
+struct TwoViewTimer {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~TwoViewTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    int start(sfmba_handle* h, bool on) {
+        if (!on) return 0;
+        HIPCHK(h, hipEventCreate(&a));
+        HIPCHK(h, hipEventCreate(&b));
+        HIPCHK(h, hipEventRecord(a, h->stream));
+        return 0;
+    }
+    int stop(sfmba_handle* h) {
+        if (a) HIPCHK(h, hipEventRecord(b, h->stream));
+        return 0;
+    }
+    int read(sfmba_handle* h, double* us) {                      // after the stream has been waited for
+        if (!us) return 0;
+        *us = 0.0;
+        if (!a) return 0;
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, a, b));
+        *us = 1e3 * (double)ms;
+        return 0;
+    }
+};
+
+// a per-pair result from its packed order in the staging (src) into the caller's stored order, `bytes` per pair; pairs
+// that took no part get the `bytes` at `fill`
+void twoview_scatter(const sfmba_handle* h, const TwoViewBatch& bt, const void* src, void* dst, size_t bytes, const void* fill) {
+    if (!dst) return;
+    if (!bt.masked) { memcpy(dst, src, bytes * bt.Mu); return; }
+    unsigned char* const d = static_cast<unsigned char*>(dst);
+    const unsigned char* const sp = static_cast<const unsigned char*>(src);
+    for (size_t k = 0; k < bt.M; ++k) memcpy(d + bytes * k, fill, bytes);
+    const auto& pos = h->twoview.pos;
+    for (size_t u = 0; u < bt.Mu; ++u) memcpy(d + bytes * (size_t)pos[u], sp + bytes * u, bytes);
+}
+
+// hypotheses of a workgroup's slice and the slices of an edge: about two workgroups per CU over the whole batch, a slice
+// not below kTwoViewMinSlice
+void twoview_slices(const sfmba_handle* h, size_t E, int H, int* hs, int* n_slices) {
+    const size_t want = (2 * (size_t)h->n_cu + E - 1) / std::max<size_t>(E, 1);
+    const int most = (H + kTwoViewMinSlice - 1) / kTwoViewMinSlice;
+    const int sl = (int)std::min<size_t>(std::max<size_t>(want, 1), (size_t)most);
+    *hs = (H + sl - 1) / sl;
+    *n_slices = (H + *hs - 1) / *hs;
+}
+}  // namespace
+
+void sfmba_default_ransac_options(sfmba_ransac_options* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->threshold = 1.0; o->confidence = 0.99; o->seed = 0; o->max_iters = 1000; o->refit = 0; o->profile = 0;
+}
+
+int sfmba_fundamental_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edge_ptr, const double* pts1, const double* pts2,
+                             const uint8_t* pair_use, const int32_t* samples, const sfmba_ransac_options* opt, double* F,
+                             double* F_refit, uint8_t* inlier_mask, int32_t* edge_inliers, int32_t* edge_best,
+                             uint8_t* edge_success, int32_t* edge_status, int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us) {
+    CHK(enter(h));
+    sfmba_ransac_options o;
+    if (opt) o = *opt; else sfmba_default_ransac_options(&o);
+    if (std::isnan(o.threshold) || std::isnan(o.confidence)) return fail(h, -1, "an option of sfmba_fundamental_ransac is NaN");
+    if (o.max_iters < 1) return fail(h, -1, "sfmba_fundamental_ransac: max_iters must be at least 1");
+    auto& t = h->twoview;
+    TwoViewBatch bt;
+    CHK(twoview_stage(h, "sfmba_fundamental_ransac", n_edges, edge_ptr, pts1, pts2, pair_use, &bt));
+    if (n_ok) *n_ok = 0;
+    if (kernel_us) *kernel_us = 0.0;
+    const size_t E = bt.E, H = (size_t)o.max_iters;
+    if (E == 0) return wait_stream(h);
+    int hs = 1, n_slices = 1;
+    twoview_slices(h, E, (int)H, &hs, &n_slices);
+    if (E * (size_t)n_slices >= (size_t)1 << 31) return fail(h, -1, "sfmba_fundamental_ransac: too many edges for one launch");
+    CHK(ensure_all(h, {{&t.slots, sizeof(double) * kTwoViewSlot * E * (size_t)n_slices},
+                       {&t.hyp, hyp_inliers ? sizeof(int) * E * H : 0}, {&t.samples, samples ? sizeof(int) * 8 * E * H : 0},
+                       {&t.F, sizeof(double) * 18 * E}, {&t.ints, sizeof(int) * 4 * E}, {&t.mask, std::max<size_t>(bt.Mu, 1)}}));
+    if (samples) {
+        const int* up = reinterpret_cast<const int*>(t.in_host.as<unsigned char>() + sizeof(double) * 4 * bt.M);
+        for (size_t e = 0; e < E; ++e) {
+            const int n = up[e + 1] - up[e];
+            if (n < 8) continue;                                 // (FEW_PAIRS: its samples are not read)
+            const int32_t* sp = samples + e * H * 8;
+            for (size_t k = 0; k < 8 * H; ++k)
+                if (sp[k] < 0 || sp[k] >= n)
+                    return fail(h, -1, "sfmba_fundamental_ransac: samples of edge %zu, hypothesis %zu: position %d is outside its %d used pairs",
+                                e, k / 8, (int)sp[k], n);
+        }
+        HIPCHK(h, hipMemcpyAsync(t.samples.p, samples, sizeof(int) * 8 * E * H, hipMemcpyHostToDevice, h->stream));
+    }
+    const FundIn in{t.pairs.as<double>(), t.uptr.as<int>(), samples ? t.samples.as<int>() : nullptr};
+    const FundOut out{t.F.as<double>(), t.F.as<double>() + 9 * E, t.mask.as<unsigned char>(), t.ints.as<int>()};
+    const size_t lds = sizeof(double) * 4 * (size_t)std::min(bt.max_n, kTwoViewLdsPairs);
+    {   // more than 64 KiB of LDS in all needs the opt-in, and the kernel's static part (about 8 KiB, above the 2 KiB that
+        // set_lds assumes) counts: opted in once per handle, whatever this call stages
+        const void* fn = reinterpret_cast<const void*>(k_fund_ransac);
+        if (std::find(h->lds_ready.begin(), h->lds_ready.end(), fn) == h->lds_ready.end()) {
+            HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * 4 * kTwoViewLdsPairs)));
+            h->lds_ready.push_back(fn);
+        }
+    }
+    TwoViewTimer timer;
+    CHK(timer.start(h, o.profile != 0));
+    hipLaunchKernelGGL(k_fund_ransac, dim3((unsigned)(E * (size_t)n_slices)), dim3(kTwoViewThreads), lds, h->stream, in, (int)H, hs,
+                       n_slices, (unsigned long long)o.seed, o.threshold, t.slots.as<double>(), hyp_inliers ? t.hyp.as<int>() : nullptr);
+    LAUNCHED(h);
+    hipLaunchKernelGGL(k_fund_finish, dim3((unsigned)E), dim3(kTwoViewThreads), 0, h->stream, in, n_slices, o.threshold, o.confidence,
+                       o.refit != 0 ? 1 : 0, (const double*)t.slots.as<double>(), out);
+    LAUNCHED(h);
+    CHK(timer.stop(h));
+    // the per-edge integers always come (n_ok); the mask through the staging when it has to be scattered
+    const size_t off_mask = sizeof(int) * 4 * E;
+    HIPCHK(h, t.out_host.ensure(off_mask + bt.Mu, 0));
+    int* const hi = t.out_host.as<int>();
+    unsigned char* const hm = t.out_host.as<unsigned char>() + off_mask;
+    HIPCHK(h, hipMemcpyAsync(hi, t.ints.p, sizeof(int) * 4 * E, hipMemcpyDeviceToHost, h->stream));
+    if (inlier_mask && bt.Mu) HIPCHK(h, hipMemcpyAsync(hm, t.mask.p, bt.Mu, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, download(h, F, t.F.p, sizeof(double) * 9 * E));
+    HIPCHK(h, download(h, F_refit, t.F.as<double>() + 9 * E, sizeof(double) * 9 * E));
+    HIPCHK(h, download(h, hyp_inliers, t.hyp.p, sizeof(int) * E * H));
+    CHK(wait_stream(h));
+    CHK(timer.read(h, kernel_us));
+    const uint8_t zero = 0;
+    twoview_scatter(h, bt, hm, inlier_mask, 1, &zero);
+    int64_t ok = 0;
+    for (size_t e = 0; e < E; ++e) {
+        if (edge_inliers) edge_inliers[e] = hi[4 * e];
+        if (edge_best) edge_best[e] = hi[4 * e + 1];
+        if (edge_status) edge_status[e] = hi[4 * e + 2];
+        if (edge_success) edge_success[e] = (uint8_t)hi[4 * e + 3];
+        ok += hi[4 * e + 2] == kFundOk ? 1 : 0;
+    }
+    if (n_ok) *n_ok = ok;
+    return 0;
+}
+
+void sfmba_default_pose_options(sfmba_pose_options* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->min_depth = 0.0; o->profile = 0;
+}
+
+int sfmba_recover_pose(sfmba_handle* h, int64_t n_edges, const int64_t* edge_ptr, const double* pts1, const double* pts2,
+                       const uint8_t* pair_use, const double* E_in, const double* K, const sfmba_pose_options* opt, double* R,
+                       double* t_out, uint8_t* front_mask, double* X, double* angle_deg, int32_t* edge_front,
+                       int32_t* edge_front_all, double* edge_sum_err, int32_t* edge_status, int64_t* n_ok, double* kernel_us) {
+    CHK(enter(h));
+    sfmba_pose_options o;
+    if (opt) o = *opt; else sfmba_default_pose_options(&o);
+    if (std::isnan(o.min_depth)) return fail(h, -1, "an option of sfmba_recover_pose is NaN");
+    if (!K) return fail(h, -1, "sfmba_recover_pose: K is NULL");
+    auto& t = h->twoview;
+    TwoViewBatch bt;
+    CHK(twoview_stage(h, "sfmba_recover_pose", n_edges, edge_ptr, pts1, pts2, pair_use, &bt));
+    if (n_ok) *n_ok = 0;
+    if (kernel_us) *kernel_us = 0.0;
+    const size_t E = bt.E, Mu = bt.Mu;
+    if (E == 0) return wait_stream(h);
+    if (!E_in) return fail(h, -1, "sfmba_recover_pose: E is NULL");
+    const size_t M1 = std::max<size_t>(Mu, 1);
+    CHK(ensure_all(h, {{&t.E, sizeof(double) * 9 * E}, {&t.Rt, sizeof(double) * 12 * E}, {&t.err, sizeof(double) * E},
+                       {&t.pose_ints, sizeof(int) * 6 * E}, {&t.mask, M1}, {&t.X, sizeof(double) * 3 * M1}, {&t.ang, sizeof(double) * M1}}));
+    // E through the staging of the results (pinned; nothing of this call is in it yet)
+    const size_t off_rt = 0, off_err = sizeof(double) * 12 * E, off_X = off_err + sizeof(double) * E,
+                 off_ang = off_X + sizeof(double) * 3 * Mu, off_int = off_ang + sizeof(double) * Mu, off_mask = off_int + sizeof(int) * 6 * E;
+    HIPCHK(h, t.out_host.ensure(off_mask + Mu, 0));
+    unsigned char* const st = t.out_host.as<unsigned char>();
+    memcpy(st, E_in, sizeof(double) * 9 * E);
+    HIPCHK(h, hipMemcpyAsync(t.E.p, st, sizeof(double) * 9 * E, hipMemcpyHostToDevice, h->stream));
+    KMat Km;
+    for (int k = 0; k < 9; ++k) Km.k[k] = K[k];
+    const PoseOut out{t.Rt.as<double>(), t.err.as<double>(), t.pose_ints.as<int>(), t.mask.as<unsigned char>(), t.X.as<double>(),
+                      t.ang.as<double>()};
+    TwoViewTimer timer;
+    CHK(timer.start(h, o.profile != 0));
+    hipLaunchKernelGGL(k_recover_pose, dim3((unsigned)E), dim3(kTwoViewThreads), 0, h->stream, (const double*)t.pairs.as<double>(),
+                       (const int*)t.uptr.as<int>(), (const double*)t.E.as<double>(), Km, o.min_depth, out);
+    LAUNCHED(h);
+    CHK(timer.stop(h));
+    HIPCHK(h, hipMemcpyAsync(st + off_rt, t.Rt.p, sizeof(double) * 12 * E, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(st + off_int, t.pose_ints.p, sizeof(int) * 6 * E, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, download(h, edge_sum_err, t.err.p, sizeof(double) * E));
+    if (X && Mu) HIPCHK(h, hipMemcpyAsync(st + off_X, t.X.p, sizeof(double) * 3 * Mu, hipMemcpyDeviceToHost, h->stream));
+    if (angle_deg && Mu) HIPCHK(h, hipMemcpyAsync(st + off_ang, t.ang.p, sizeof(double) * Mu, hipMemcpyDeviceToHost, h->stream));
+    if (front_mask && Mu) HIPCHK(h, hipMemcpyAsync(st + off_mask, t.mask.p, Mu, hipMemcpyDeviceToHost, h->stream));
+    CHK(wait_stream(h));
+    CHK(timer.read(h, kernel_us));
+    const double* rt = reinterpret_cast<const double*>(st + off_rt);
+    const int* hi = reinterpret_cast<const int*>(st + off_int);
+    const double nan3[3] = {NAN, NAN, NAN};
+    const uint8_t zero = 0;
+    twoview_scatter(h, bt, st + off_X, X, sizeof(double) * 3, nan3);
+    twoview_scatter(h, bt, st + off_ang, angle_deg, sizeof(double), nan3);
+    twoview_scatter(h, bt, st + off_mask, front_mask, 1, &zero);
+    int64_t ok = 0;
+    for (size_t e = 0; e < E; ++e) {
+        if (R) memcpy(R + 9 * e, rt + 12 * e, sizeof(double) * 9);
+        if (t_out) memcpy(t_out + 3 * e, rt + 12 * e + 9, sizeof(double) * 3);
+        if (edge_front) edge_front[e] = hi[6 * e];
+        if (edge_front_all) memcpy(edge_front_all + 4 * e, hi + 6 * e + 1, sizeof(int) * 4);
+        if (edge_status) edge_status[e] = hi[6 * e + 5];
+        ok += hi[6 * e + 5] == kPoseOk ? 1 : 0;
+    }
+    if (n_ok) *n_ok = ok;
+    return 0;
 }
 
 void sfmba_default_filter_options(sfmba_filter_options* o) {

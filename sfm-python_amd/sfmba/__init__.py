@@ -6,11 +6,13 @@ Public surface mirrors /root/reference/sfm_lite/bundle_adjustment.py and the sci
 from .api import (TERMINATION_MESSAGES, apply_bundle_adjustment, compute_residuals,
                   create_sparsity_matrix, get_backend, least_squares, pack_cameras_points,
                   project_points, unpack_cameras_points)
-from .backend import Backend, BackendError, ReprojectionStats, Resection, Triangulation
+from .backend import (Backend, BackendError, FundamentalEstimate, RelativePose, ReprojectionStats, Resection,
+                      Triangulation)
 from .bal import read_bal, write_bal
-from .extras import (calc_reproj_error, load_calibration_data, load_problem, prune_problem, refine_reconstruction,
-                     reproj_error, reprojection_stats, resect_cameras, save_problem, solve_pnp,
-                     total_mean_reproj_error, triangulate_points, triangulate_tracks)
+from .extras import (FM_RANSAC, calc_reproj_error, find_fundamental_mat, load_calibration_data, load_problem,
+                     prune_problem, recover_pose, refine_reconstruction, reproj_error, reprojection_stats, resect_cameras,
+                     save_problem, select_initial_pair, solve_pnp, total_mean_reproj_error, triangulate_points,
+                     triangulate_tracks)
 from .synthetic import (BAProblem, K_SCEAUX, drop_observations, growing_reconstruction, make_config,
                         make_problem, make_ring_problem)
 
@@ -22,4 +24,5 @@ __all__ = ["TERMINATION_MESSAGES", "apply_bundle_adjustment", "compute_residuals
            "load_problem", "reproj_error", "save_problem", "read_bal", "write_bal",
            "ReprojectionStats", "reprojection_stats", "total_mean_reproj_error", "prune_problem", "refine_reconstruction",
            "Triangulation", "triangulate_tracks", "triangulate_points",
-           "Resection", "resect_cameras", "solve_pnp"]
+           "Resection", "resect_cameras", "solve_pnp",
+           "FundamentalEstimate", "RelativePose", "FM_RANSAC", "find_fundamental_mat", "recover_pose", "select_initial_pair"]

@@ -24,6 +24,7 @@ SYMBOLS = (
     "sfmba_default_filter_options", "sfmba_reprojection_stats",
     "sfmba_default_triangulate_options", "sfmba_triangulate",
     "sfmba_default_resect_options", "sfmba_resect",
+    "sfmba_default_ransac_options", "sfmba_fundamental_ransac", "sfmba_default_pose_options", "sfmba_recover_pose",
 )
 
 
@@ -62,6 +63,15 @@ class TriangulateOptions(C.Structure):
 class ResectOptions(C.Structure):
     _fields_ = [("max_iter", C.c_int32), ("min_views", C.c_int32), ("start", C.c_int32), ("xtol", C.c_double),
                 ("min_depth", C.c_double), ("max_rms_px", C.c_double)]
+
+
+class RansacOptions(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("seed", C.c_uint64), ("max_iters", C.c_int32),
+                ("refit", C.c_int32), ("profile", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PoseOptions(C.Structure):
+    _fields_ = [("min_depth", C.c_double), ("profile", C.c_int32), ("reserved", C.c_int32)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -155,6 +165,17 @@ def load():
         lib.sfmba_default_resect_options.restype = None
         lib.sfmba_resect.argtypes = [P, P, P, P, C.POINTER(ResectOptions)] + [P] * 5 + [C.POINTER(C.c_int64)]
         lib.sfmba_resect.restype = C.c_int
+    if hasattr(lib, "sfmba_fundamental_ransac"):     # (likewise)
+        lib.sfmba_default_ransac_options.argtypes = [C.POINTER(RansacOptions)]
+        lib.sfmba_default_ransac_options.restype = None
+        lib.sfmba_fundamental_ransac.argtypes = ([P, C.c_int64] + [P] * 5 + [C.POINTER(RansacOptions)] + [P] * 8 +
+                                                 [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
+        lib.sfmba_fundamental_ransac.restype = C.c_int
+        lib.sfmba_default_pose_options.argtypes = [C.POINTER(PoseOptions)]
+        lib.sfmba_default_pose_options.restype = None
+        lib.sfmba_recover_pose.argtypes = ([P, C.c_int64] + [P] * 6 + [C.POINTER(PoseOptions)] + [P] * 9 +
+                                           [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
+        lib.sfmba_recover_pose.restype = C.c_int
     lib.sfmba_tr2d_solve.argtypes = [P, P, C.c_double, P]
     lib.sfmba_comm_get_unique_id.argtypes = [P]
     lib.sfmba_comm_init.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int64]

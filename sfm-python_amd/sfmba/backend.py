@@ -10,6 +10,70 @@ import numpy as np
 from . import _capi
 
 
+class FundamentalEstimate:
+    """What `Backend.fundamental_ransac` returns (include/sfmba.h: sfmba_fundamental_ransac), per edge of the batch:
+    ``F`` and ``F_refit`` (E, 3, 3), unit Frobenius norm, largest entry positive (``F_refit`` equals ``F`` unless
+    ``refit=1``); ``inliers``, ``best`` (the winning hypothesis), ``status`` (one of ``OK, FEW_PAIRS, DEGENERATE``) as
+    int32 (E), ``success`` (E, bool): inliers / used pairs >= confidence; ``inlier_mask`` (M, bool) over the stored pairs;
+    ``hyp_inliers`` (E, H) the count of every hypothesis, or None when not asked for; ``n_ok``; ``kernel_us``
+    (``profile=1``, else 0)."""
+
+    OK, FEW_PAIRS, DEGENERATE = 0, 1, 2
+
+    def __init__(self, F, F_refit, inlier_mask, inliers, best, success, status, hyp_inliers, n_ok, kernel_us, edge_ptr):
+        self.F, self.F_refit, self.inlier_mask = F, F_refit, inlier_mask
+        self.inliers, self.best, self.success, self.status = inliers, best, success, status
+        self.hyp_inliers, self.n_ok, self.kernel_us, self.edge_ptr = hyp_inliers, int(n_ok), float(kernel_us), edge_ptr
+
+    @property
+    def ok(self):
+        return self.status == self.OK
+
+    def __repr__(self):
+        return f"FundamentalEstimate(n_edges={len(self.status)}, n_ok={self.n_ok})"
+
+
+class RelativePose:
+    """What `Backend.recover_pose` returns (include/sfmba.h: sfmba_recover_pose), per edge: ``R`` (E, 3, 3) and ``t``
+    (E, 3), ``x2 = R x1 + t`` with ``|t| = 1``; ``front`` (E) the winner's pairs in front, ``front_all`` (E, 4) every
+    candidate's; ``sum_err`` (E) the reference's reprojection total; ``status`` (E) one of ``OK, FEW_PAIRS, DEGENERATE,
+    TIE``; per stored pair ``front_mask`` (M, bool), ``X`` (M, 3) and ``angle_deg`` (M), NaN where a pair took no part /
+    is not in front; ``n_ok``; ``kernel_us``."""
+
+    OK, FEW_PAIRS, DEGENERATE, TIE = 0, 1, 2, 3
+
+    def __init__(self, R, t, front_mask, X, angle_deg, front, front_all, sum_err, status, n_ok, kernel_us, edge_ptr):
+        self.R, self.t, self.front_mask, self.X, self.angle_deg = R, t, front_mask, X, angle_deg
+        self.front, self.front_all, self.sum_err, self.status = front, front_all, sum_err, status
+        self.n_ok, self.kernel_us, self.edge_ptr = int(n_ok), float(kernel_us), edge_ptr
+
+    @property
+    def ok(self):
+        return self.status == self.OK
+
+    def __repr__(self):
+        return f"RelativePose(n_edges={len(self.status)}, n_ok={self.n_ok})"
+
+
+def _edge_batch(pts1, pts2, edge_ptr, pair_use):
+    """The arrays of a batch of edges, checked: pts1, pts2 (M, 2) float64, edge_ptr (E + 1) int64 ascending from 0 to M
+    (None: one edge), the mask (M) uint8 or None."""
+    pts1, pts2 = _f64(pts1), _f64(pts2)
+    if pts1.ndim != 2 or pts1.shape[1] != 2 or pts2.shape != pts1.shape:
+        raise ValueError(f"pts1 and pts2 must both be (M, 2), got {pts1.shape} and {pts2.shape}")
+    M = pts1.shape[0]
+    if edge_ptr is None:
+        edge_ptr = np.array([0, M], dtype=np.int64)
+    edge_ptr = np.ascontiguousarray(edge_ptr, dtype=np.int64).ravel()
+    if edge_ptr.shape[0] < 1 or edge_ptr[0] != 0 or edge_ptr[-1] != M or np.any(np.diff(edge_ptr) < 0):
+        raise ValueError("edge_ptr must ascend from 0 to the number of pairs")
+    return pts1, pts2, edge_ptr, _mask(pair_use, M, "pair_use")
+
+
+def _opt_ptr(a):
+    return _capi.ptr(a) if a is not None else None
+
+
 class BackendError(RuntimeError):
     pass
 
@@ -418,6 +482,80 @@ class Backend:
             _capi.ptr(use) if use is not None else None, C.byref(opt), _capi.ptr(cameras), _capi.ptr(status),
             _capi.ptr(views), _capi.ptr(iters), _capi.ptr(rms), C.byref(n_ok)))
         return Resection(cameras, status, views, iters, rms, n_ok.value)
+
+    def fundamental_ransac(self, pts1, pts2, edge_ptr=None, pair_use=None, samples=None, want_hyp=False, **options):
+        """F by RANSAC for every edge of a batch of matched pixel pairs, the reference's
+        ``estimate_fundamental_matrix_ransac`` (include/sfmba.h: sfmba_fundamental_ransac).  ``pts1``, ``pts2`` (M, 2);
+        ``edge_ptr`` (E + 1) the edges' runs, None = one edge; ``pair_use`` (M) boolean, None = all; ``samples``
+        (E, H, 8) int32 positions among an edge's used pairs, None = drawn on the device from ``seed``.  ``options``:
+        fields of ``sfmba_ransac_options`` (threshold, confidence, seed, max_iters, refit, profile); with ``samples``
+        given, ``max_iters`` defaults to its H.  ``want_hyp``: also return the count of every hypothesis.  Needs no
+        problem.  -> :class:`FundamentalEstimate`."""
+        self._flush_pending()
+        pts1, pts2, edge_ptr, use = _edge_batch(pts1, pts2, edge_ptr, pair_use)
+        E, M = edge_ptr.shape[0] - 1, pts1.shape[0]
+        opt = _capi.RansacOptions()
+        self._lib.sfmba_default_ransac_options(C.byref(opt))
+        options = dict(options)
+        if "seed" in options:
+            seed = int(options.pop("seed"))
+            if not 0 <= seed < 2 ** 64:
+                raise ValueError("seed must fit 64 unsigned bits")
+            opt.seed = seed
+        if samples is not None:
+            samples = np.ascontiguousarray(samples, dtype=np.int32)
+            if samples.ndim == 2:
+                samples = samples[None]
+            if samples.ndim != 3 or samples.shape[0] != E or samples.shape[2] != 8 or samples.shape[1] < 1:
+                raise ValueError(f"samples must be (n_edges, H, 8) with n_edges = {E}, got {samples.shape}")
+            options.setdefault("max_iters", samples.shape[1])
+        _fill_options(opt, options, "RANSAC")
+        if opt.max_iters < 1:
+            raise ValueError("max_iters must be at least 1")
+        if samples is not None and samples.shape[1] != opt.max_iters:
+            raise ValueError(f"samples holds {samples.shape[1]} hypotheses per edge, max_iters is {opt.max_iters}")
+        H = int(opt.max_iters)
+        F, Fr = np.empty((E, 3, 3)), np.empty((E, 3, 3))
+        mask = np.empty(M, dtype=np.uint8)
+        inl, best, status = (np.empty(E, dtype=np.int32) for _ in range(3))
+        success = np.empty(E, dtype=np.uint8)
+        hyp = np.empty((E, H), dtype=np.int32) if want_hyp else None
+        n_ok, us = C.c_int64(), C.c_double()
+        self._check(self._lib.sfmba_fundamental_ransac(
+            self._h, E, _capi.ptr(edge_ptr), _capi.ptr(pts1), _capi.ptr(pts2), _opt_ptr(use), _opt_ptr(samples), C.byref(opt),
+            _capi.ptr(F), _capi.ptr(Fr), _capi.ptr(mask), _capi.ptr(inl), _capi.ptr(best), _capi.ptr(success),
+            _capi.ptr(status), _opt_ptr(hyp), C.byref(n_ok), C.byref(us)))
+        return FundamentalEstimate(F, Fr, mask.view(np.bool_), inl, best, success.view(np.bool_), status, hyp, n_ok.value,
+                                   us.value, edge_ptr)
+
+    def recover_pose(self, E, pts1, pts2, K, edge_ptr=None, pair_use=None, **options):
+        """R, t, the cheirality mask, the points and their ray angles for every edge of a batch, the reference's
+        ``recover_pose`` (include/sfmba.h: sfmba_recover_pose).  ``E`` (n_edges, 3, 3) or (3, 3); ``K`` (3, 3); the batch
+        as in :meth:`fundamental_ransac`.  ``options``: fields of ``sfmba_pose_options`` (min_depth, profile).  Needs no
+        problem.  -> :class:`RelativePose`."""
+        self._flush_pending()
+        pts1, pts2, edge_ptr, use = _edge_batch(pts1, pts2, edge_ptr, pair_use)
+        n, M = edge_ptr.shape[0] - 1, pts1.shape[0]
+        E = _f64(E)
+        if E.shape == (3, 3):
+            E = E[None]
+        E = _f64(E, (n, 3, 3), "E")
+        K = _f64(K, (3, 3), "K")
+        opt = _capi.PoseOptions()
+        self._lib.sfmba_default_pose_options(C.byref(opt))
+        _fill_options(opt, options, "pose")
+        R, t = np.empty((n, 3, 3)), np.empty((n, 3))
+        mask = np.empty(M, dtype=np.uint8)
+        X, ang = np.empty((M, 3)), np.empty(M)
+        front, status = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        front_all = np.empty((n, 4), dtype=np.int32)
+        err = np.empty(n)
+        n_ok, us = C.c_int64(), C.c_double()
+        self._check(self._lib.sfmba_recover_pose(
+            self._h, n, _capi.ptr(edge_ptr), _capi.ptr(pts1), _capi.ptr(pts2), _opt_ptr(use), _capi.ptr(E), _capi.ptr(K),
+            C.byref(opt), _capi.ptr(R), _capi.ptr(t), _capi.ptr(mask), _capi.ptr(X), _capi.ptr(ang), _capi.ptr(front),
+            _capi.ptr(front_all), _capi.ptr(err), _capi.ptr(status), C.byref(n_ok), C.byref(us)))
+        return RelativePose(R, t, mask.view(np.bool_), X, ang, front, front_all, err, status, n_ok.value, us.value, edge_ptr)
 
     def residual_jacobian(self, x):
         self._flush_pending()

@@ -240,6 +240,86 @@ def refine_reconstruction(x0, args, rounds=2, max_error_px=4.0, min_depth=0.0, m
     return result, (x, args), (obs_index, point_index), summaries
 
 
+FM_RANSAC = 8        # cv2.FM_RANSAC, the one method of the reference's teaching restatement
+
+
+def find_fundamental_mat(pts1, pts2, method=FM_RANSAC, ransacReprojThreshold=3.0, confidence=0.99, maxIters=1000, seed=0,
+                         device=0, backend=None):
+    """The two-line swap for ``cv2.findFundamentalMat(pts1, pts2, cv2.FM_RANSAC, thr, conf)`` (sfm.py:101) ->
+    ``(F (3, 3), mask (N, 1) uint8)`` as cv2 returns them; ``F`` is ``None`` when the pairs give no F.  One call of
+    :meth:`Backend.fundamental_ransac` with ``refit=1``: the F returned is the refit over all inliers of the best
+    hypothesis.  The score is the REFERENCE's (one-sided distance in image 2, strictly below the threshold), not cv2's
+    symmetric one; the samples are drawn on the device from ``seed``."""
+    if method != FM_RANSAC:
+        raise ValueError("only method=FM_RANSAC is implemented")
+    pts1, pts2 = np.asarray(pts1, dtype=np.float64), np.asarray(pts2, dtype=np.float64)
+    if pts1.ndim != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
+        raise ValueError(f"pts1 and pts2 must both be (N, 2), got {pts1.shape} and {pts2.shape}")
+    be = backend if backend is not None else api.get_backend(device)
+    est = be.fundamental_ransac(pts1, pts2, threshold=ransacReprojThreshold, confidence=confidence, max_iters=maxIters,
+                                seed=seed, refit=1)
+    mask = est.inlier_mask.astype(np.uint8).reshape(-1, 1)
+    return (est.F_refit[0].copy() if est.status[0] == est.OK else None), mask
+
+
+def recover_pose(E, pts1, pts2, K, device=0, backend=None):
+    """The two-line swap for ``cv2.recoverPose(E, pts1, pts2, K)`` (sfm.py:131) -> ``(n_front, R (3, 3), t (3, 1), mask
+    (N, 1) uint8 of 0 / 255)``: one call of :meth:`Backend.recover_pose`."""
+    pts1, pts2 = np.asarray(pts1, dtype=np.float64), np.asarray(pts2, dtype=np.float64)
+    if pts1.ndim != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
+        raise ValueError(f"pts1 and pts2 must both be (N, 2), got {pts1.shape} and {pts2.shape}")
+    if np.shape(E) != (3, 3) or np.shape(K) != (3, 3):
+        raise ValueError("E and K must be (3, 3)")
+    be = backend if backend is not None else api.get_backend(device)
+    pose = be.recover_pose(E, pts1, pts2, K)
+    return int(pose.front[0]), pose.R[0].copy(), pose.t[0].reshape(3, 1).copy(), pose.front_mask.astype(np.uint8).reshape(-1, 1) * 255
+
+
+def select_initial_pair(edges, K, min_angle=3, max_angle=60, device=0, backend=None, **ransac_options):
+    """The first-pair choice of ``SFM._initial_register`` (sfm.py:120-180) for a list ``edges`` of ``(pts1, pts2)``: one
+    :meth:`Backend.fundamental_ransac` call (``refit=1``) and one :meth:`Backend.recover_pose` call (``E = K^T F K``, over
+    each edge's inliers) for the whole list, then on the host the median of ``angle_deg`` over each edge's pairs in front.
+    -> ``(index, R, t, X, mask)``: the edge with the smallest median strictly inside ``(min_angle, max_angle)`` degrees
+    (the reference's ``3 < mid_angle < 60``) among the edges whose F and pose both came back ``OK``, its pose,
+    its points ``X`` (N, 3; NaN where not in front) and its front mask (N) -- or ``(None, None, None, None, None)``.
+
+    The reference's own angle code sums over the wrong axis (sfm.py:153-154 take ``axis=0`` on (N, 3) arrays, which mixes
+    the pairs); this is the per-pair angle between the two rays that it intends.  One more deviation: an edge whose pose
+    is a ``TIE`` (two candidates see equally many pairs in front) is passed over, where the reference takes whichever
+    candidate ``max`` meets first: an ambiguous pose is no start for a reconstruction."""
+    if not len(edges):
+        raise ValueError("edges is empty")
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError("K must be (3, 3)")
+    p1 = [np.asarray(e[0], dtype=np.float64) for e in edges]
+    p2 = [np.asarray(e[1], dtype=np.float64) for e in edges]
+    for a, b in zip(p1, p2):
+        if a.ndim != 2 or a.shape[1] != 2 or a.shape != b.shape:
+            raise ValueError(f"every edge must be a pair of (N, 2) arrays, got {a.shape} and {b.shape}")
+    ptr = np.concatenate([[0], np.cumsum([len(a) for a in p1])]).astype(np.int64)
+    pts1, pts2 = np.concatenate(p1), np.concatenate(p2)
+    be = backend if backend is not None else api.get_backend(device)
+    ransac_options.setdefault("refit", 1)
+    est = be.fundamental_ransac(pts1, pts2, edge_ptr=ptr, **ransac_options)
+    E = np.einsum("ji,ejk,kl->eil", K, est.F_refit, K)
+    pose = be.recover_pose(E, pts1, pts2, K, edge_ptr=ptr, pair_use=est.inlier_mask)
+    best, best_median = None, np.inf
+    for e in range(len(edges)):
+        sl = slice(int(ptr[e]), int(ptr[e + 1]))
+        front = pose.front_mask[sl]
+        if est.status[e] != est.OK or pose.status[e] != pose.OK or not front.any():
+            continue
+        median = float(np.median(pose.angle_deg[sl][front]))
+        if min_angle < median < max_angle and median < best_median:
+            best, best_median = e, median
+    if best is None:
+        return None, None, None, None, None
+    sl = slice(int(ptr[best]), int(ptr[best + 1]))
+    X = np.where(pose.front_mask[sl, None], pose.X[sl], np.nan)
+    return best, pose.R[best].copy(), pose.t[best].copy(), X, pose.front_mask[sl].copy()
+
+
 def load_calibration_data(txt_path):
     """3x3 whitespace-separated text -> ndarray, /root/reference/sfm_lite/utils.py:24-35."""
     K = np.array([[float(v) for v in line.split()] for line in open(txt_path) if line.strip()])

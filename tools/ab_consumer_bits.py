@@ -1,5 +1,5 @@
-"""Bit identity of the three consumers (reprojection statistics, triangulation, resection) between two builds of the
-library.  Usage: python tools/ab_consumer_bits.py LIB_A LIB_B [--out DIR]
+"""Bit identity of the consumers (reprojection statistics, triangulation, resection, and the two-view calls where both
+builds have them) between two builds of the library.  Usage: python tools/ab_consumer_bits.py LIB_A LIB_B [--out DIR]
 
 One fresh child process per library (SFMBA_LIB), each under its own time limit; the tool stops at the first child that
 does not exit cleanly.  A child runs the three calls over inputs that reach every form of the kernels -- the long-run,
@@ -32,6 +32,11 @@ def inputs():
     yield "camera_slices", ci.camera_slices_problem([1, 255, 256, 257, 1024, 1025])
 
 
+def kernel_constant_of(name):
+    from kernel_source import kernel_constant
+    return kernel_constant(name)
+
+
 def child(out_path):
     import sfmba
     from sfmba.backend import ReprojectionStats
@@ -62,6 +67,27 @@ def child(out_path):
                         for f in ("cameras", "status", "views", "iters", "rms_err"):
                             out[f"{key}/{f}"] = getattr(r, f)
                         out[f"{key}/n_ok"] = np.array([r.n_ok])
+    # the two-view calls: a batch that reaches the staged and the unstaged form, every status, a mask, drawn and given samples
+    if hasattr(be._lib, "sfmba_fundamental_ransac"):      # (an older build has neither)
+        import two_view_ref as tv
+        L = kernel_constant_of("kTwoViewLdsPairs")
+        rng = np.random.default_rng(6)
+        K = sfmba.K_SCEAUX
+        made = [tv.make_pairs(rng, n, K, noise=0.3, outliers=0.25) for n in (7, 8, 65, 1900, L + 1)]
+        ptr = np.concatenate([[0], np.cumsum([len(m[0]) for m in made])]).astype(np.int64)
+        p1, p2 = np.concatenate([m[0] for m in made]), np.concatenate([m[1] for m in made])
+        use = rng.random(len(p1)) < 0.9
+        smp = np.stack([tv.draw_samples(3, e, 40, 8) for e in range(len(made))])
+        for tag, kw in (("drawn", dict(max_iters=40, seed=3)), ("masked", dict(max_iters=40, seed=3, pair_use=use)), ("given", dict(samples=smp))):
+            est = be.fundamental_ransac(p1, p2, edge_ptr=ptr, threshold=1.0, refit=1, want_hyp=True, **kw)
+            for f in ("F", "F_refit", "inlier_mask", "inliers", "best", "success", "status", "hyp_inliers"):
+                out[f"two_view/64/ransac/{tag}/{f}"] = getattr(est, f)
+        Es = np.stack([tv.essential_from_pose(m[2], m[3]) for m in made])
+        Es[1] = 0.0
+        for tag, kw in (("all", {}), ("masked", dict(pair_use=use)), ("deep", dict(min_depth=6.0))):
+            pose = be.recover_pose(Es, p1, p2, K, edge_ptr=ptr, **kw)
+            for f in ("R", "t", "front_mask", "X", "angle_deg", "front", "front_all", "sum_err", "status"):
+                out[f"two_view/64/pose/{tag}/{f}"] = getattr(pose, f)
     be.close()
     np.savez(out_path, **{k.replace("/", "|"): v for k, v in out.items()})
 
@@ -92,6 +118,17 @@ def main():
             return 2
         files.append(np.load(path))
     a, b = files
+    only = [f for f in (a, b) if any(k.startswith("two_view|") for k in f.files)]
+    if len(only) == 1:                                           # one build has no two-view calls: nothing to compare them with
+        print("  (only one build has the two-view calls: their arrays are left out)")
+
+        class Without:
+            def __init__(self, f):
+                self.f, self.files = f, [k for k in f.files if not k.startswith("two_view|")]
+
+            def __getitem__(self, k):
+                return self.f[k]
+        a, b = Without(a), Without(b)
     print(f"A = {lib_a}\nB = {lib_b}")
     differ = [k for k in a.files if k not in b.files or a[k].dtype != b[k].dtype or a[k].tobytes() != b[k].tobytes()]
     differ += [k for k in b.files if k not in a.files]
