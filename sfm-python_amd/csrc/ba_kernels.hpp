@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "problem_tables.hpp"   // kWaveChunkCams, kWaveChunkRanges, dense_block_index: shared with the host's table build
 #include "tr2d.hpp"
 
 namespace sfmba {
@@ -809,7 +810,6 @@ struct CamMajor {
 constexpr int kCamThreads = 256;
 constexpr int kCamWaves = kCamThreads / 64;
 constexpr int kCamUnroll = 4;
-constexpr int kWaveChunkCams = 4, kWaveChunkRanges = 8;      // the XCD-aware chunk table (k_cam_schur_w, k_cam_blocks_w, k_cam_rhs_diag_w)
 
 // NV sums over the 64 lanes of a wave at the price of ~NV + 6 exchanges instead of 6 NV: a butterfly that HALVES the
 // values a lane carries at every step -- at mask m the lanes with bit m clear keep the lower half of their values, those
@@ -3193,9 +3193,6 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_rhs_diag_w(CamMajor cm, con
 // exact steps carried rounding noise along the seven gauge directions that no camera being fixed leaves open.)
 // ---------------------------------------------------------------------------------------------
 constexpr int kDenseMaxN = 128;                  // 6 C <= 128: C <= 21
-__host__ __device__ constexpr int dense_block_index(int a, int b, int C) {      // a <= b, row-major upper triangle
-    return a * C - a * (a - 1) / 2 + (b - a);
-}
 
 // blk[a][b] (6x6, row-major) = sum over the points p seen by cameras a and b (with multiplicity) of
 // W_a(p) Vinv_p W_b(p)^T,  W_c(p) = Jc^T Jp of camera c at point p.  The workgroup of a diagonal pair (a, a) also

@@ -31,6 +31,7 @@
 #include <thread>
 #include <vector>
 
+#include "problem_tables.hpp"
 #include "ba_kernels.hpp"
 #include "consumer_kernels.hpp"
 #include "tr2d.hpp"
@@ -117,68 +118,6 @@ struct PinnedBuf {
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
-// A few persistent host threads for set_problem's passes over the observation arrays (spawning threads per
-// call cost more than the passes themselves at a million observations).  run(parts, fn) calls fn(0..parts-1),
-// part 0 on the calling thread, and returns when all are done.
-class HostPool {
-public:
-    static constexpr int kMax = 16;
-    ~HostPool() {
-        { std::lock_guard<std::mutex> lk(m_); stop_ = true; ++gen_; }
-        cv_.notify_all();
-        for (auto& t : th_) t.join();
-    }
-    int parts_for(int64_t n) const {
-        const int hw = (int)std::thread::hardware_concurrency();
-        return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(kMax, hw > 0 ? hw : 1), n / 65536));
-    }
-    template <class Fn>
-    void run(int parts, Fn fn) {
-        if (parts <= 1) { fn(0); return; }
-        while ((int)th_.size() < parts - 1) {
-            const int id = (int)th_.size() + 1;
-            th_.emplace_back([this, id] { worker(id); });
-        }
-        std::function<void(int)> f = fn;
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            job_ = &f; job_parts_ = parts; pending_ = parts - 1; ++gen_;
-        }
-        cv_.notify_all();
-        fn(0);
-        std::unique_lock<std::mutex> lk(m_);
-        done_.wait(lk, [this] { return pending_ == 0; });
-        job_ = nullptr;
-    }
-private:
-    void worker(int id) {
-        unsigned long long seen = 0;
-        for (;;) {
-            std::function<void(int)>* f = nullptr;
-            {
-                std::unique_lock<std::mutex> lk(m_);
-                cv_.wait(lk, [&] { return gen_ != seen; });
-                seen = gen_;
-                if (stop_) return;
-                if (id >= job_parts_ || job_ == nullptr) continue;
-                f = job_;
-            }
-            (*f)(id);
-            {
-                std::lock_guard<std::mutex> lk(m_);
-                if (--pending_ == 0) done_.notify_one();
-            }
-        }
-    }
-    std::vector<std::thread> th_;
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    std::function<void(int)>* job_ = nullptr;
-    int job_parts_ = 0, pending_ = 0;
-    unsigned long long gen_ = 0;
-    bool stop_ = false;
-};
-
 // RCCL entry points, resolved at run time so that libsfmba.so has no load-time dependency on RCCL
 struct RcclApi {
     void* lib = nullptr;
@@ -207,10 +146,6 @@ RcclApi* rccl_api() {
         }
     }
     return api.lib ? &api : nullptr;
-}
-
-double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 // test / diagnostic hooks, set through sfmba_debug_option only (nothing reads the environment)
@@ -297,6 +232,13 @@ struct Forms {
 
 }  // namespace
 
+// the rows of the host's tables are uploaded as they are
+static_assert(sizeof(TableRow2) == sizeof(int2) && alignof(TableRow2) == alignof(int2) && offsetof(TableRow2, x) == offsetof(int2, x) &&
+              offsetof(TableRow2, y) == offsetof(int2, y), "TableRow2 is int2");
+static_assert(sizeof(TableRow4) == sizeof(int4) && alignof(TableRow4) == alignof(int4) && offsetof(TableRow4, x) == offsetof(int4, x) &&
+              offsetof(TableRow4, y) == offsetof(int4, y) && offsetof(TableRow4, z) == offsetof(int4, z) &&
+              offsetof(TableRow4, w) == offsetof(int4, w), "TableRow4 is int4");
+
 struct sfmba_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -310,7 +252,6 @@ struct sfmba_handle {
     int64_t N_total = 0;
     KMat K{};
     bool permuted = false;
-    std::vector<int64_t> order;              // sorted position -> caller's observation index
     int n_ranges = 0;
     bool f32 = false;                        // fp32 storage of uv, r, t1 and the Jacobian (arithmetic stays fp64)
     bool f32_next = false;                   // takes effect at the next sfmba_set_problem
@@ -339,8 +280,6 @@ struct sfmba_handle {
     // point-range boundaries, chunk 8 c + k on XCD k (see set_problem)
     DevView cam_chunks_b, cam_chunk_ptr_b;
     int n_chunks_b = 0;
-    std::vector<int4> host_chunks_b;
-    std::vector<int> host_chunk_ptr_b;
     DevBuf xa, xb, tabA, tabB, r, J, t1;     // ONE Jacobian / residual buffer set
     DevBuf rhsrec;                           // [P][kRhsRec]: what k_cam_rhs_diag gathers (written by k_prep)
     DevBuf V, Vinv, gp, e, recA, recB;       // rec: point records X Y Z | z (k_fill_rec), one per parameter vector
@@ -383,9 +322,7 @@ struct sfmba_handle {
     struct Stage { PinnedBuf uv, ci, pi, perm, ptr, uvf, tables, ci16, uv16; } stage;
     DevBuf ci16_dev, uv16_dev;               // packed upload of the observation arrays (k_unpack_obs)
     struct Prev { bool valid = false; bool f32 = false; bool packed = false; int64_t N = 0, P = 0; } prev;
-    std::vector<int2> host_ranges, host_wsteps, host_steps;
-    std::vector<int4> host_chunks;
-    std::vector<int> host_chunk_ptr;
+    ProblemTables tb;                        // what build_problem_tables() made of the arguments (problem_tables.hpp)
     HostPool pool;
     int64_t obs_reused = 0, obs_uploaded = 0;    // of the last sfmba_set_problem
     double* mbox = nullptr;                  // coherent pinned block the device posts the hand-off into (Mailbox)
@@ -593,11 +530,6 @@ void p2p_fill_args(sfmba_handle* h, P2pArgs& a) {
 // So cfg4 (1000 cameras / 100k points / 1M observations, fp64): pass A k_point_sweep_rc<FUSED> (sweep_rc, pcg_fused), pass B
 // k_cam_schur over the chunk list; cfg5 in fp32 storage (5000 / 1M / 10M): pass A k_rc_table32 + k_point_sweep_rc32 (sweep_rc_g,
 // mixed), pass B k_cam_schur_w on fp32 records over the XCD-aware table + k_cam_combine_w (xcd_b, mixed_b), rhs pass from rhsrec.
-struct ProblemFacts {                    // what only the build of the tables can tell
-    bool pixels_int16 = true;            // every pixel coordinate is an int16 integer
-    bool cam_multi = false;              // some camera's list was cut into several chunks
-    int64_t pair_entries = 0;            // length of the pair lists of the dense path
-};
 Forms decide_problem_forms(int64_t C, int64_t P, int64_t N, bool f32, int n_cu, const ProblemFacts& facts, const Debug& dbg) {
     const auto by_size = [](int option, bool fits) { return option == 1 || (option != 0 && fits); };     // 1 forces, 0 forbids
     Forms f;
@@ -1393,7 +1325,7 @@ int download_residuals(sfmba_handle* h, double* r_out) {
     if (!h->f32 && !h->permuted) { memcpy(r_out, h->h_x, bytes); return 0; }
     const float* sf = reinterpret_cast<const float*>(h->h_x);
     for (int64_t k = 0; k < h->N; ++k) {
-        const int64_t d = h->permuted ? h->order[k] : k;
+        const int64_t d = h->permuted ? h->tb.order[k] : k;
         r_out[2 * d] = h->f32 ? (double)sf[2 * k] : h->h_x[2 * k];
         r_out[2 * d + 1] = h->f32 ? (double)sf[2 * k + 1] : h->h_x[2 * k + 1];
     }
@@ -1941,32 +1873,17 @@ struct ProblemBuild {
     const size_t ldz = (size_t)ld;
     const bool f32 = h->f32_next;
     Forms plan;                              // the forms with the facts of the tables still assumed favourable
-    ProblemFacts facts;                      // ... and those facts as the phases find them
     std::vector<char> fixed;                 // [C] camera held still
-    int64_t n_cmp = 0, fdiff = 0;            // observations compared with / equal to the previous problem's
-    bool sorted = true;
-    const int parts = h->pool.parts_for(N);
-    const int64_t per = (N + parts - 1) / parts;
-    std::vector<int> hist;                   // [parts][C] camera counts, then scatter offsets
-    // what part t of the conversion pass found: first bad index, first changed observation, order broken, a pixel that is no int16
-    std::vector<int64_t> bad = std::vector<int64_t>((size_t)parts, -1), first_diff = std::vector<int64_t>((size_t)parts, N);
-    std::vector<char> unsorted = std::vector<char>((size_t)parts, 0), not16 = unsorted;
-    std::vector<int> cam_ptr, cov_ptr, cov_pt;
-    std::vector<int2> blk_ab;
-    // the converted arrays in pinned memory (h->stage)
-    double* uvs = nullptr; float* uvf = nullptr;
-    int *ci = nullptr, *pi = nullptr, *perm = nullptr, *ptr = nullptr;
-    unsigned short* ci16 = nullptr; short* uv16 = nullptr;
+    int64_t n_cmp = 0;                       // observations compared with the previous problem's
+    ProblemTables& tb = h->tb;               // the tables, the order, the facts and the re-used prefix (tb.fdiff)
+    StagedArrays st;                         // the converted arrays in pinned memory (h->stage)
     int64_t p_keep = 0;                      // run offsets that are unchanged on the device
     size_t tables_bytes = 0;
 
     int run();
-    // the phases, in order (the form decision sits between pair_lists and allocate)
+    // the phases, in order (the form decision sits between stage_and_build and allocate)
     int check_and_reset();
-    int convert_and_compare();      // ... and the point-major order
-    void convert(const int64_t* ord, int64_t n_compare, bool packed_prefix_ok);
-    void camera_major_sort();
-    void wave_ranges(), step_tables(), chunk_tables(), pair_lists();
+    int stage_and_build();          // pinned staging, then build_problem_tables()
     int allocate(), upload_and_zero(), enqueue_camera_major();
     hipError_t up(void* dst, const void* src, size_t elem, size_t from, size_t to) {
         if (to <= from) return hipSuccess;
@@ -2010,47 +1927,9 @@ int ProblemBuild::check_and_reset() {
     return 0;
 }
 
-// pass 1 (parallel): range check, order check, conversion with comparison, camera histogram
-void ProblemBuild::convert(const int64_t* ord, int64_t n_compare, bool packed_prefix_ok) {
-    h->pool.run(parts, [&](int t) {
-        const int64_t b = std::min<int64_t>(N, t * per), e = std::min<int64_t>(N, (t + 1) * per);
-        int* hc = hist.data() + (size_t)t * (size_t)C;
-        for (int64_t c = 0; c < C; ++c) hc[c] = 0;
-        int64_t fd = N;
-        for (int64_t k = b; k < e; ++k) {
-            const int64_t s = ord ? ord[k] : k;
-            const int64_t cv = cam[s], pv = pt[s];
-            if (cv < 0 || cv >= C || pv < 0 || pv >= P) { if (bad[t] < 0) bad[t] = s; continue; }
-            if (!ord && k > 0 && pv < pt[k - 1]) unsorted[t] = 1;
-            double u0, u1;
-            if (uv) { u0 = uv[2 * s]; u1 = uv[2 * s + 1]; }
-            else { u0 = (double)uv_i64[2 * s]; u1 = (double)uv_i64[2 * s + 1]; }          // as numpy promotes
-            if (!fixed[(size_t)cv]) ++hc[cv];
-            const bool same = k < n_compare && ci[k] == (int)cv && pi[k] == (int)pv && uvs[2 * k] == u0 && uvs[2 * k + 1] == u1;
-            if (ci16 && !(same && packed_prefix_ok)) {     // (an unchanged entry is packed already, if the previous call packed)
-                const bool in = std::fabs(u0) < 32768.0 && std::fabs(u1) < 32768.0;
-                const short q0 = in ? (short)u0 : (short)0, q1 = in ? (short)u1 : (short)0;
-                if (!in || (double)q0 != u0 || (double)q1 != u1) not16[t] = 1;
-                ci16[k] = (unsigned short)cv; uv16[2 * k] = q0; uv16[2 * k + 1] = q1;
-            }
-            if (same) continue;
-            if (fd == N) fd = k;
-            ci[k] = (int)cv; pi[k] = (int)pv; uvs[2 * k] = u0; uvs[2 * k + 1] = u1;
-            if (uvf) { uvf[2 * k] = (float)u0; uvf[2 * k + 1] = (float)u1; }    // integer pixels up to 2^24 are exact
-        }
-        first_diff[t] = fd;
-    });
-}
-
-// ---- incremental re-use ---------------------------------------------------------
-// The reference calls BA once per fused edge on a growing reconstruction (/root/reference/sfm_lite/sfm.py:59-71):
-// once every camera is registered, a new edge only appends points and their observations, so the argument
-// arrays of one call start with those of the previous call.  The converted arrays of the last problem stay in
-// pinned host memory and in HBM; this call compares as it converts, finds the first observation that differs
-// and uploads from there on only.  The structure tables are always rebuilt from the (complete) host arrays, by
-// the same code whatever was re-used: results are bitwise those of a fresh handle.
-// Then the point-major order: any order is accepted, the kernels want point-major.
-int ProblemBuild::convert_and_compare() {
+// The converted arrays of the last problem stay in pinned host memory and in HBM (incremental re-use, problem_tables.hpp):
+// the staging keeps the prefix this call is compared with when it grows.  Then the tables, from the host arrays alone.
+int ProblemBuild::stage_and_build() {
     auto& prev = h->prev;
     auto& sg = h->stage;
     n_cmp = (prev.valid && prev.f32 == f32) ? std::min(prev.N, N) : 0;
@@ -2063,251 +1942,37 @@ int ProblemBuild::convert_and_compare() {
     HIPCHK(h, sg.ptr.ensure(sizeof(int) * ((size_t)P + 1), 0));
     if (f32) HIPCHK(h, sg.uvf.ensure(sizeof(float) * 2 * ldz, sizeof(float) * 2 * keep_obs));
     const bool try_pack = plan.packed_upload;
-    const bool packed_prefix_ok = try_pack && prev.packed && n_cmp > 0;      // the staged prefix holds valid packed entries
     if (try_pack) {
         HIPCHK(h, sg.ci16.ensure(sizeof(unsigned short) * ldz, sizeof(unsigned short) * keep_obs));
         HIPCHK(h, sg.uv16.ensure(sizeof(short) * 2 * ldz, sizeof(short) * 2 * keep_obs));
     }
-    ci16 = try_pack ? sg.ci16.as<unsigned short>() : nullptr;
-    uv16 = try_pack ? sg.uv16.as<short>() : nullptr;
-    uvs = sg.uv.as<double>();
-    uvf = f32 ? sg.uvf.as<float>() : nullptr;
-    ci = sg.ci.as<int>(); pi = sg.pi.as<int>(); perm = sg.perm.as<int>(); ptr = sg.ptr.as<int>();
+    st.ci16 = try_pack ? sg.ci16.as<unsigned short>() : nullptr;
+    st.uv16 = try_pack ? sg.uv16.as<short>() : nullptr;
+    st.uvs = sg.uv.as<double>();
+    st.uvf = f32 ? sg.uvf.as<float>() : nullptr;
+    st.ci = sg.ci.as<int>(); st.pi = sg.pi.as<int>(); st.perm = sg.perm.as<int>(); st.ptr = sg.ptr.as<int>();
 
-    hist.assign((size_t)parts * (size_t)C, 0);
-    convert(nullptr, n_cmp, packed_prefix_ok);
-    for (int t = 0; t < parts; ++t) {       // (numpy's fancy indexing would raise IndexError in the reference)
-        const int64_t i = bad[t];
-        if (i < 0) continue;
+    ProblemInput in;
+    in.C = C; in.P = P; in.N = N; in.cam = cam; in.pt = pt; in.uv = uv; in.uv_i64 = uv_i64; in.fixed = fixed.data();
+    in.n_cmp = n_cmp;
+    in.packed_prefix_ok = try_pack && prev.packed && n_cmp > 0;      // the staged prefix holds valid packed entries
+    TablePlan tp;
+    tp.dense = plan.dense; tp.xcd_b = plan.xcd_b; tp.cm_device = plan.cm_device; tp.packed_upload = plan.packed_upload;
+    tp.cam_chunk_len = plan.cam_chunk_len;
+    tp.total_waves = (int64_t)h->n_cu * kWavesPerSweepBlock;
+    tp.parts = h->pool.parts_for(N);
+    tp.pair_parts = P >= 32768 ? 4 : 1;
+    if (!build_problem_tables(in, tp, st, h->pool, tb)) {       // (numpy's fancy indexing would raise IndexError in the reference)
+        const int64_t i = tb.bad;
         if (cam[i] < 0 || cam[i] >= C)
             return fail(h, -1, "camera_indices[%lld]=%lld out of range [0,%lld)", (long long)i, (long long)cam[i], (long long)C);
         return fail(h, -1, "point_indices[%lld]=%lld out of range [0,%lld)", (long long)i, (long long)pt[i], (long long)P);
     }
-    for (int t = 0; t < parts; ++t) sorted = sorted && !unsorted[t];
-    h->permuted = !sorted;
-    h->order.clear();
-    if (!sorted) {                       // No re-use on this path.
-        h->order.resize(N);
-        std::iota(h->order.begin(), h->order.end(), (int64_t)0);
-        std::stable_sort(h->order.begin(), h->order.end(), [&](int64_t a, int64_t b) { return pt[a] < pt[b]; });
-        convert(h->order.data(), 0, packed_prefix_ok);
-    }
-    fdiff = N;
-    for (int t = 0; t < parts; ++t) fdiff = std::min(fdiff, first_diff[t]);
-    fdiff = std::min(fdiff, n_cmp);      // nothing beyond the compared prefix is on the device
-    for (size_t k = (size_t)N; k < ldz; ++k) {                       // padding up to the next multiple of 256
-        ci[k] = 0; pi[k] = 0; uvs[2 * k] = 0.0; uvs[2 * k + 1] = 0.0;
-        if (uvf) { uvf[2 * k] = 0.f; uvf[2 * k + 1] = 0.f; }
-        if (ci16) { ci16[k] = 0; uv16[2 * k] = 0; uv16[2 * k + 1] = 0; }
-    }
-    for (char f : not16) facts.pixels_int16 = facts.pixels_int16 && !f;
+    h->permuted = !tb.sorted;
+    h->n_ranges = (int)tb.ranges.size(); h->n_steps = (int)tb.steps.size();
+    h->n_chunks = (int)tb.chunks.size(); h->n_chunks_b = (int)tb.chunks_b.size();
+    h->n_blk = (int)tb.blk_ab.size();
     return 0;
-}
-
-// camera-major order: stable counting sort of the positions by camera (per-part histograms, so that the parts scatter
-// independently and the order inside a camera stays the point-major one), and the run offsets of the points
-void ProblemBuild::camera_major_sort() {
-    cam_ptr.resize((size_t)C + 1);
-    int run = 0;
-    for (int64_t c = 0; c < C; ++c) {
-        cam_ptr[c] = run;
-        for (int t = 0; t < parts; ++t) { int& v = hist[(size_t)t * (size_t)C + c]; const int n = v; v = run; run += n; }
-    }
-    cam_ptr[C] = run;
-    // pass 2 (parallel): ptr[p] = first position whose point index is >= p (pi is non-decreasing): every run start k
-    // writes the entries (pi[k-1], pi[k]], so the parts touch disjoint pieces of ptr.
-    // The camera-major order itself is sorted on the DEVICE (k_cam_hist / k_cam_offsets / k_cam_scatter: the same stable
-    // order) unless the camera counters do not fit the LDS; the host then only needs the run offsets.
-    const bool on_host = !plan.cm_device;
-    h->pool.run(parts, [&](int t) {
-        const int64_t b = std::min<int64_t>(N, t * per), e = std::min<int64_t>(N, (t + 1) * per);
-        int* off = hist.data() + (size_t)t * (size_t)C;
-        for (int64_t k = b; k < e; ++k) {
-            const int lo = k == 0 ? -1 : pi[k - 1];
-            for (int q = lo + 1; q <= pi[k]; ++q) ptr[q] = (int)k;
-            if (on_host && !fixed[(size_t)ci[k]]) perm[off[ci[k]]++] = (int)k;
-        }
-    });
-    for (int64_t q = (int64_t)pi[N - 1] + 1; q <= P; ++q) ptr[q] = (int)N;
-    if (on_host)
-        for (size_t k = (size_t)cam_ptr[C]; k < ldz; ++k) perm[k] = 0;  // (shorter than N when cameras are held still)
-}
-
-// wave ranges: cut at point boundaries, >= T observations each
-void ProblemBuild::wave_ranges() {
-    const int64_t total_waves = (int64_t)h->n_cu * kWavesPerSweepBlock;
-    const int64_t T = std::max<int64_t>(64, (N + total_waves - 1) / total_waves);
-    std::vector<int2>& ranges = h->host_ranges;
-    ranges.clear();
-    int64_t start = 0;
-    for (int64_t p = 0; p < P; ++p) {
-        const int64_t endp = ptr[p + 1];
-        if (endp - start >= T || (p == P - 1 && endp > start)) {
-            ranges.push_back(make_int2((int)start, (int)endp));
-            start = endp;
-        }
-    }
-    h->n_ranges = (int)ranges.size();
-}
-
-// step table of the sweeps: per wave range, batches of <= 64 observations that end on a point
-// boundary; a point with more than 64 observations is one step of its own
-void ProblemBuild::step_tables() {
-    const std::vector<int2>& ranges = h->host_ranges;
-    std::vector<int2>& wsteps = h->host_wsteps;
-    std::vector<int2>& steps = h->host_steps;
-    wsteps.resize(ranges.size());
-    steps.clear();
-    // the ranges are independent: every worker walks a slice of them into its own list (the walk is a chain of
-    // dependent reads of pi / ptr -- 1.2-1.4 ms of a 3.6 ms call at 1M observations when one thread did all of it),
-    // the lists are concatenated in range order afterwards
-    const int sparts = (int)std::max<size_t>(1, std::min<size_t>((size_t)parts, ranges.size() / 64));
-    std::vector<std::vector<int2>> local((size_t)sparts);
-    const size_t rper = (ranges.size() + (size_t)sparts - 1) / (size_t)sparts;
-    h->pool.run(sparts, [&](int t) {
-        std::vector<int2>& out = local[(size_t)t];
-        const size_t w0 = std::min(ranges.size(), (size_t)t * rper), w1 = std::min(ranges.size(), w0 + rper);
-        out.reserve((w1 - w0) * 6);
-        for (size_t w = w0; w < w1; ++w) {
-            const int first = (int)out.size();                       // (relative to the slice; rebased below)
-            int64_t pos = ranges[w].x;
-            const int64_t end = ranges[w].y;
-            while (pos < end) {
-                const int64_t pfirst = pi[pos];
-                if (ptr[pfirst + 1] - pos > 64) {                    // long run (pos is always a run start)
-                    out.push_back(make_int2((int)pos, (int)(ptr[pfirst + 1] - pos)));
-                    pos = ptr[pfirst + 1];
-                    continue;
-                }
-                // largest run boundary <= pos + 64
-                int64_t lim = std::min<int64_t>(pos + 64, end), cut;
-                if (lim == end) cut = end;
-                else { const int64_t pl = pi[lim]; cut = (ptr[pl] == lim) ? lim : ptr[pl]; }   // lim inside a run -> its start
-                out.push_back(make_int2((int)pos, (int)(cut - pos)));
-                pos = cut;
-            }
-            wsteps[w] = make_int2(first, (int)out.size() - first);
-        }
-    });
-    size_t total = 0;
-    for (auto& v : local) total += v.size();
-    steps.reserve(total);
-    for (int t = 0; t < sparts; ++t) {
-        const int base = (int)steps.size();
-        const size_t w0 = std::min(ranges.size(), (size_t)t * rper), w1 = std::min(ranges.size(), w0 + rper);
-        for (size_t w = w0; w < w1; ++w) wsteps[w].x += base;
-        steps.insert(steps.end(), local[(size_t)t].begin(), local[(size_t)t].end());
-    }
-    h->n_steps = (int)steps.size();
-}
-
-// chunk table of the camera-major kernels: every camera gets at least one chunk (an empty one writes its
-// zeros), runs longer than the chunk length are cut; one 256-thread workgroup per chunk
-void ProblemBuild::chunk_tables() {
-    std::vector<int4>& chunks = h->host_chunks;
-    std::vector<int>& chunk_ptr = h->host_chunk_ptr;
-    chunks.clear();
-    chunk_ptr.resize((size_t)C + 1);
-    const int64_t chunk_len = plan.cam_chunk_len;
-    for (int64_t c = 0; c < C; ++c) {
-        chunk_ptr[c] = (int)chunks.size();
-        const int b = cam_ptr[c], e = cam_ptr[c + 1];
-        const int nch = std::max<int>(1, (int)((e - b + chunk_len - 1) / chunk_len));
-        if (nch > 1) facts.cam_multi = true;
-        for (int j = 0; j < nch; ++j)
-            chunks.push_back(make_int4((int)c, (int)std::min<int64_t>(e, b + j * chunk_len),
-                                       (int)std::min<int64_t>(e, b + (j + 1) * chunk_len), nch));
-    }
-    chunk_ptr[C] = (int)chunks.size();
-    h->n_chunks = (int)chunks.size();
-    // XCD-aware chunks for pass B of the Schur product (many points).  Every camera-major pass gathers one record
-    // per observation from a table of P x 48 bytes; workgroup i runs on XCD i mod 8 and each XCD has its own 4 MiB
-    // L2: with one chunk per camera every L2 sees the WHOLE table (48 MB at a million points).  A camera's list is
-    // ascending in the point index, so it is cut at the eight point-range boundaries P k / 8: chunk 8 c + k runs on
-    // XCD k and touches points of range k only, each L2 serves an eighth of the table (pass B at 5000 / 1M / 10M:
-    // 201 -> 134 us); the eight partial rows of a camera are added by k_cam_combine and the PCG tail runs behind
-    // it (k_pcg_tail).  Pass B only: the passes with 27 sums per workgroup (K3, rhs + preconditioner) lose more to
-    // eight times as many block reductions than they gain (208 -> 320 us, 188 -> 257 us).
-    std::vector<int4>& chunks_b = h->host_chunks_b;
-    chunks_b.clear();
-    h->host_chunk_ptr_b.clear();
-    if (plan.xcd_b) {
-        // row (8 g + k) 4 + j = camera 4 g + j, range k: the four waves of workgroup 8 g + k (XCD k) take the pieces of
-        // four cameras over the same point range (k_cam_schur_w); cameras behind the last one are padding (camera -1)
-        constexpr int kX = kWaveChunkRanges, kG = kWaveChunkCams;
-        static_assert(kX == 8, "one range per XCD");
-        const int64_t groups = (C + kG - 1) / kG;
-        chunks_b.assign((size_t)(groups * kX * kG), make_int4(-1, 0, 0, kX));
-        for (int64_t c = 0; c < C && !plan.cm_device; ++c) {       // (device-side sort: k_xcd_chunks fills the table)
-            const int b = cam_ptr[c], e = cam_ptr[c + 1];
-            int prev = b;
-            for (int k = 0; k < kX; ++k) {
-                int bound = e;
-                if (k + 1 < kX) {
-                    const int64_t p_hi = P * (int64_t)(k + 1) / kX;          // first point of the next range
-                    int lo = prev, hi = e;                                   // lower bound over pi[perm[.]] (ascending)
-                    while (lo < hi) { const int mid = (lo + hi) >> 1; if (pi[perm[mid]] < p_hi) lo = mid + 1; else hi = mid; }
-                    bound = lo;
-                }
-                chunks_b[(size_t)(((c / kG) * kX + k) * kG + c % kG)] = make_int4((int)c, prev, bound, kX);
-                prev = bound;
-            }
-        }
-    }
-    h->n_chunks_b = (int)chunks_b.size();
-}
-
-// few cameras: for every block pair (a <= b) the points seen by both cameras, with multiplicity (a point seen
-// m_a, m_b times contributes m_a m_b times); two counting passes over the runs.  The diagonal pairs' workgroups
-// also sum the reduced right-hand side of their camera, over the entries that pair an observation with itself.
-void ProblemBuild::pair_lists() {
-    if (!plan.dense) return;
-    const int nblk = (int)(C * (C + 1) / 2);
-    cov_ptr.assign((size_t)nblk + 1, 0);
-    // (unordered pairs i <= j: a pair of different cameras is one entry of its block, two observations of the same
-    // camera by the same point are two, an observation with itself one -- what the ordered double loop counted)
-    // Two passes over the points, count and fill; from 32k points on split over a few threads by contiguous point
-    // ranges: per-part counts per block, then part t's entries of a block follow part t - 1's -- ascending point order
-    // inside a block, whatever the number of parts.  (Below that size waking the pool costs more than the passes:
-    // measured at the SceauxCastle scale, 0.10 ms single-threaded against 0.13 ms on four threads.)
-    const int pp = P >= 32768 ? 4 : 1;
-    std::vector<int> cnt((size_t)pp * (size_t)nblk, 0);
-    const int64_t pper = (P + pp - 1) / pp;
-    auto each_pair = [&](int t, auto&& visit) {
-        const int64_t p0 = std::min<int64_t>(P, t * pper), p1 = std::min<int64_t>(P, p0 + pper);
-        for (int64_t p = p0; p < p1; ++p)
-            for (int i = ptr[p]; i < ptr[p + 1]; ++i)
-                for (int j = i; j < ptr[p + 1]; ++j) {
-                    const int a = std::min(ci[i], ci[j]), b = std::max(ci[i], ci[j]);
-                    if (fixed[(size_t)a] || fixed[(size_t)b]) continue;
-                    visit((int)p, dense_block_index(a, b, (int)C), i == j, a == b);
-                }
-    };
-    h->pool.run(pp, [&](int t) {
-        int* ct = cnt.data() + (size_t)t * (size_t)nblk;
-        each_pair(t, [&](int, int blk, bool self, bool same_cam) { ct[blk] += (self || !same_cam) ? 1 : 2; });
-    });
-    int64_t total = 0;
-    for (int blk = 0; blk < nblk; ++blk) {
-        cov_ptr[(size_t)blk] = (int)std::min<int64_t>(total, INT32_MAX);
-        for (int t = 0; t < pp; ++t) { int& v = cnt[(size_t)t * (size_t)nblk + blk]; const int n_e = v; v = (int)std::min<int64_t>(total, INT32_MAX); total += n_e; }
-    }
-    cov_ptr[(size_t)nblk] = (int)std::min<int64_t>(total, INT32_MAX);
-    facts.pair_entries = total;
-    if (total > ((int64_t)1 << 26)) return;                  // very long tracks: the pair lists would not pay (-> PCG)
-    cov_pt.resize((size_t)std::max<int64_t>(1, total));
-    h->pool.run(pp, [&](int t) {
-        int* fill = cnt.data() + (size_t)t * (size_t)nblk;
-        each_pair(t, [&](int p, int blk, bool self, bool same_cam) {
-            int& f = fill[blk];
-            cov_pt[(size_t)f++] = self ? ~p : p;                       // (~p: the term of the right-hand side)
-            if (!self && same_cam) cov_pt[(size_t)f++] = p;
-        });
-    });
-    blk_ab.resize((size_t)nblk);
-    for (int a = 0; a < (int)C; ++a)
-        for (int b = a; b < (int)C; ++b) blk_ab[(size_t)dense_block_index(a, b, (int)C)] = make_int2(a, b);
-    h->n_blk = nblk;
 }
 
 // device arrays: grow-only; the index / pixel arrays keep their re-used prefix when they grow
@@ -2315,28 +1980,28 @@ int ProblemBuild::allocate() {
     const Forms& f = h->forms;
     auto& sg = h->stage;
     const size_t esz = f32 ? sizeof(float) : sizeof(double);     // element size of the per-observation streams
-    const size_t keep = (size_t)fdiff;
+    const size_t keep = (size_t)tb.fdiff;
     HIPCHK(h, h->cam_idx.ensure_keep(sizeof(int) * ldz, sizeof(int) * keep));
     HIPCHK(h, h->pt_idx.ensure_keep(sizeof(int) * ldz, sizeof(int) * keep));
     HIPCHK(h, h->uv.ensure_keep(esz * 2 * ldz, esz * 2 * keep));
     // run offsets of the points before the first changed observation's point are unchanged
     // (entries up to the point of the last unchanged observation are determined by unchanged positions alone)
-    p_keep = keep == 0 ? 0 : std::min<int64_t>(std::min<int64_t>(h->prev.P, P), (int64_t)pi[fdiff - 1] + 1);
+    p_keep = keep == 0 ? 0 : std::min<int64_t>(std::min<int64_t>(h->prev.P, P), (int64_t)st.pi[tb.fdiff - 1] + 1);
     HIPCHK(h, h->pt_ptr.ensure_keep(sizeof(int) * ((size_t)P + 1), sizeof(int) * (size_t)p_keep));
     // the structure tables: one device buffer, one pinned staging buffer, one copy
     struct Piece { const void* src; size_t bytes; DevView* view; size_t off; };
     Piece pieces[11] = {
-        {cam_ptr.data(), sizeof(int) * cam_ptr.size(), &h->cam_ptr_dev, 0},
-        {h->host_ranges.data(), sizeof(int2) * h->host_ranges.size(), &h->ranges, 0},
-        {h->host_wsteps.data(), sizeof(int2) * h->host_wsteps.size(), &h->wsteps, 0},
-        {h->host_steps.data(), sizeof(int2) * h->host_steps.size(), &h->steps, 0},
-        {h->host_chunks.data(), sizeof(int4) * h->host_chunks.size(), &h->cam_chunks, 0},
-        {h->host_chunk_ptr.data(), sizeof(int) * h->host_chunk_ptr.size(), &h->cam_chunk_ptr, 0},
-        {cov_ptr.data(), f.dense ? sizeof(int) * cov_ptr.size() : 0, &h->cov_ptr, 0},
-        {cov_pt.data(), f.dense ? sizeof(int) * cov_pt.size() : 0, &h->cov_pt, 0},
-        {blk_ab.data(), f.dense ? sizeof(int2) * blk_ab.size() : 0, &h->blk_ab, 0},
-        {h->host_chunks_b.data(), sizeof(int4) * h->host_chunks_b.size(), &h->cam_chunks_b, 0},
-        {h->host_chunk_ptr_b.data(), sizeof(int) * h->host_chunk_ptr_b.size(), &h->cam_chunk_ptr_b, 0}};
+        {tb.cam_ptr.data(), sizeof(int) * tb.cam_ptr.size(), &h->cam_ptr_dev, 0},
+        {tb.ranges.data(), sizeof(int2) * tb.ranges.size(), &h->ranges, 0},
+        {tb.wsteps.data(), sizeof(int2) * tb.wsteps.size(), &h->wsteps, 0},
+        {tb.steps.data(), sizeof(int2) * tb.steps.size(), &h->steps, 0},
+        {tb.chunks.data(), sizeof(int4) * tb.chunks.size(), &h->cam_chunks, 0},
+        {tb.chunk_ptr.data(), sizeof(int) * tb.chunk_ptr.size(), &h->cam_chunk_ptr, 0},
+        {tb.cov_ptr.data(), f.dense ? sizeof(int) * tb.cov_ptr.size() : 0, &h->cov_ptr, 0},
+        {tb.cov_pt.data(), f.dense ? sizeof(int) * tb.cov_pt.size() : 0, &h->cov_pt, 0},
+        {tb.blk_ab.data(), f.dense ? sizeof(int2) * tb.blk_ab.size() : 0, &h->blk_ab, 0},
+        {tb.chunks_b.data(), sizeof(int4) * tb.chunks_b.size(), &h->cam_chunks_b, 0},
+        {tb.chunk_ptr_b.data(), sizeof(int) * tb.chunk_ptr_b.size(), &h->cam_chunk_ptr_b, 0}};
     tables_bytes = 0;
     for (auto& pc : pieces) { pc.off = tables_bytes; tables_bytes += (pc.bytes + 255) / 256 * 256; }
     HIPCHK(h, h->tables.ensure(tables_bytes + 256));
@@ -2349,9 +2014,9 @@ int ProblemBuild::allocate() {
     CHK(ensure_all(h, {
         {&h->xa, n8}, {&h->xb, n8}, {&h->tabA, cam_tab}, {&h->tabB, cam_tab}, {&h->r, esz * 2 * ldz}, {&h->J, esz * 12 * ldz},
         {&h->cm_perm, sizeof(int) * ldz}, {&h->cm_pt, sizeof(int) * ldz}, {&h->cm_uv, esz * 2 * ldz},
-        {&h->cam_partial, sizeof(double) * std::max<size_t>(27 * h->host_chunks.size(), 27 * h->host_chunks_b.size())},
+        {&h->cam_partial, sizeof(double) * std::max<size_t>(27 * tb.chunks.size(), 27 * tb.chunks_b.size())},
         {&h->recA, sizeof(double) * kRec * P}, {&h->recB, sizeof(double) * kRec * P},
-        {&h->rhsrec, f.use_rhsrec ? sizeof(double) * kRhsRec * P : 0}, {&h->Sblk, f.dense ? sizeof(double) * 36 * blk_ab.size() : 0},
+        {&h->rhsrec, f.use_rhsrec ? sizeof(double) * kRhsRec * P : 0}, {&h->Sblk, f.dense ? sizeof(double) * 36 * tb.blk_ab.size() : 0},
         {&h->t1, esz * 2 * ldz}, {&h->V, sizeof(double) * 6 * P}, {&h->Vinv, sizeof(double) * (kVinvInRec < 0 ? kVinvRow * P : 8)},
         {&h->gp, sizeof(double) * 3 * P + 16},                  // (+16: zeroed in 16-byte units)
         {&h->edge, sizeof(double) * 2 * kEdgeRow * (size_t)((N + 63) / 64)}, {&h->e, sizeof(double) * 3 * P},
@@ -2383,18 +2048,18 @@ int ProblemBuild::allocate() {
 // zero-initialised array in ONE launch
 int ProblemBuild::upload_and_zero() {
     const size_t esz = f32 ? sizeof(float) : sizeof(double);
-    const size_t keep = (size_t)fdiff;
+    const size_t keep = (size_t)tb.fdiff;
     if (h->forms.packed_upload) {
         HIPCHK(h, h->ci16_dev.ensure(sizeof(unsigned short) * ldz));
         HIPCHK(h, h->uv16_dev.ensure(sizeof(short) * 2 * ldz));
-        HIPCHK(h, up(h->ci16_dev.p, ci16, sizeof(unsigned short), keep, ldz));
-        HIPCHK(h, up(h->uv16_dev.p, uv16, 2 * sizeof(short), keep, ldz));
+        HIPCHK(h, up(h->ci16_dev.p, st.ci16, sizeof(unsigned short), keep, ldz));
+        HIPCHK(h, up(h->uv16_dev.p, st.uv16, 2 * sizeof(short), keep, ldz));
     } else {
-        HIPCHK(h, up(h->cam_idx.p, ci, sizeof(int), keep, ldz));
-        HIPCHK(h, up(h->pt_idx.p, pi, sizeof(int), keep, ldz));
-        HIPCHK(h, up(h->uv.p, f32 ? (const void*)uvf : (const void*)uvs, 2 * esz, keep, ldz));
+        HIPCHK(h, up(h->cam_idx.p, st.ci, sizeof(int), keep, ldz));
+        HIPCHK(h, up(h->pt_idx.p, st.pi, sizeof(int), keep, ldz));
+        HIPCHK(h, up(h->uv.p, f32 ? (const void*)st.uvf : (const void*)st.uvs, 2 * esz, keep, ldz));
     }
-    HIPCHK(h, up(h->pt_ptr.p, ptr, sizeof(int), (size_t)p_keep, (size_t)P + 1));
+    HIPCHK(h, up(h->pt_ptr.p, st.ptr, sizeof(int), (size_t)p_keep, (size_t)P + 1));
     if (h->forms.packed_upload && keep < ldz) {
         hipLaunchKernelGGL(k_unpack_obs, dim3((unsigned)((ldz - keep + 255) / 256)), dim3(256), 0, h->stream,
                            (const unsigned short*)h->ci16_dev.as<unsigned short>(), (const short2*)h->uv16_dev.as<short2>(),
@@ -2404,9 +2069,9 @@ int ProblemBuild::upload_and_zero() {
                            (const int*)h->pt_ptr.as<int>(), (int)P, (int)N, (int)ld, h->pt_idx.as<int>());
         LAUNCHED(h);
     }
-    h->obs_reused = fdiff;
-    h->obs_uploaded = ld - fdiff;
-    if (!(fdiff == N && n_cmp == N && h->prev.N == N && h->prev.P == P)) ++h->problem_gen;
+    h->obs_reused = tb.fdiff;
+    h->obs_uploaded = ld - tb.fdiff;
+    if (!(tb.fdiff == N && n_cmp == N && h->prev.N == N && h->prev.P == P)) ++h->problem_gen;
     HIPCHK(h, hipMemcpyAsync(h->tables.p, h->stage.tables.p, tables_bytes, hipMemcpyHostToDevice, h->stream));
     // zeroed: the exchange arena; V, g_p (points without observations are never written by the normal-block kernels:
     // their blocks must be 0) and p (... and their step is 0); r; the point records
@@ -2429,7 +2094,7 @@ int ProblemBuild::upload_and_zero() {
 // the camera-major copies of point index and pixel: sorted on the device, or gathered through the host's permutation
 int ProblemBuild::enqueue_camera_major() {
     if (!h->forms.cm_device) {
-        HIPCHK(h, hipMemcpyAsync(h->cm_perm.p, perm, sizeof(int) * ldz, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->cm_perm.p, st.perm, sizeof(int) * ldz, hipMemcpyHostToDevice, h->stream));
         hipLaunchKernelGGL(k_build_cam_major, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->cm_perm.as<int>(),
                            h->pt_idx.as<int>(), h->uv.as<double>(), f32 ? 1 : 0, (int)N, h->cm_pt.as<int>(),
                            h->cm_uv.as<double>());
@@ -2477,23 +2142,14 @@ int ProblemBuild::run() {
     h->solved = false;
     CHK(check_and_reset());
     plan = decide_problem_forms(C, P, N, f32, h->n_cu, ProblemFacts{}, h->dbg);
-    CHK(convert_and_compare());
-    const double tp1 = now_s();
-    camera_major_sort();
-    const double ts1 = now_s();
+    CHK(stage_and_build());
+    const double tp1 = tb.t_convert, ts1 = tb.t_sort, ts2 = tb.t_ranges, ts3 = tb.t_steps, tp2 = tb.t_end;
     for (int k = 0; k < 9; ++k) h->K.k[k] = K[k];
     h->f32 = f32;
     h->C = C; h->P = P; h->N = N; h->n = 6 * C + 3 * P;
     h->N_total = N;
     h->ld = ld;
-    wave_ranges();
-    const double ts2 = now_s();
-    step_tables();
-    const double ts3 = now_s();
-    chunk_tables();
-    pair_lists();
-    const double tp2 = now_s();
-    h->forms = decide_problem_forms(C, P, N, f32, h->n_cu, facts, h->dbg);      // THE decision: the facts are in
+    h->forms = decide_problem_forms(C, P, N, f32, h->n_cu, tb.facts, h->dbg);   // THE decision: the facts are in
     CHK(allocate());
     CHK(upload_and_zero());
     CHK(enqueue_camera_major());
@@ -2505,10 +2161,10 @@ int ProblemBuild::run() {
     if (timing)
         fprintf(stderr, "sfmba: set_problem  convert+compare %.2f ms  structure %.2f ms  allocate+enqueue %.2f ms  upload wait %.2f ms"
                         "  (%lld of %lld observations re-used)\n",
-                1e3 * (tp1 - tp0), 1e3 * (tp2 - tp1), 1e3 * (tp3 - tp2), 1e3 * (now_s() - tp3), (long long)fdiff, (long long)N);
+                1e3 * (tp1 - tp0), 1e3 * (tp2 - tp1), 1e3 * (tp3 - tp2), 1e3 * (now_s() - tp3), (long long)tb.fdiff, (long long)N);
     auto& prev = h->prev;
-    if (sorted) { prev.valid = true; prev.f32 = f32; prev.N = N; prev.P = P; }
-    prev.packed = sorted && h->forms.packed_upload;
+    if (tb.sorted) { prev.valid = true; prev.f32 = f32; prev.N = N; prev.P = P; }
+    prev.packed = tb.sorted && h->forms.packed_upload;
     h->have_problem = true;
     return 0;
 }
@@ -2700,7 +2356,7 @@ int stats_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
 
 // ---- what triangulation and resection share on the host ------------------------------------------------------------------
 // The masks of a call onto the device, both through pinned staging (stats.mask_host): obs_use [N] into stored order
-// (h->order: stored position -> caller's) -> stats.use, the select mask [n_sel] as it is -> select_dev; null: not
+// (h->tb.order: stored position -> caller's) -> stats.use, the select mask [n_sel] as it is -> select_dev; null: not
 // given.  *counts: room for n_counts ints behind them in the staging, for finish_with_ok_count.
 int stage_masks(sfmba_handle* h, const uint8_t* obs_use, const uint8_t* select, size_t n_sel, DevBuf& select_dev,
                 size_t n_counts, int** counts) {
@@ -2710,7 +2366,7 @@ int stage_masks(sfmba_handle* h, const uint8_t* obs_use, const uint8_t* select, 
     HIPCHK(h, s.mask_host.ensure(off_ok + sizeof(int) * n_counts, 0));
     unsigned char* const st = s.mask_host.as<unsigned char>();
     if (obs_use && N) {
-        for (size_t k = 0; k < N; ++k) st[k] = obs_use[h->permuted ? (size_t)h->order[k] : k] ? 1 : 0;
+        for (size_t k = 0; k < N; ++k) st[k] = obs_use[h->permuted ? (size_t)h->tb.order[k] : k] ? 1 : 0;
         HIPCHK(h, hipMemcpyAsync(s.use.p, st, N, hipMemcpyHostToDevice, h->stream));
     }
     if (select && n_sel) {
@@ -3209,7 +2865,7 @@ int sfmba_reprojection_stats(sfmba_handle* h, const double* x, const sfmba_filte
     CHK(wait_stream(h));
     if (want_ed || obs_keep) {
         for (size_t k = 0; k < N; ++k) {
-            const size_t d = h->permuted ? (size_t)h->order[k] : k;
+            const size_t d = h->permuted ? (size_t)h->tb.order[k] : k;
             if (obs_err) obs_err[d] = st_ed[2 * k];
             if (obs_depth) obs_depth[d] = st_ed[2 * k + 1];
             if (obs_keep) obs_keep[d] = st_keep[k];
@@ -3254,7 +2910,7 @@ int sfmba_residual_jacobian(sfmba_handle* h, const double* x, double* r_out, dou
     HIPCHK(h, hipMemcpyAsync(tp.data(), jp_rm.p, sizeof(double) * 6 * h->N, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int64_t k = 0; k < h->N; ++k) {
-        const int64_t d = h->permuted ? h->order[k] : k;
+        const int64_t d = h->permuted ? h->tb.order[k] : k;
         memcpy(Jc_out + 12 * d, tc.data() + 12 * k, sizeof(double) * 12);
         memcpy(Jp_out + 6 * d, tp.data() + 6 * k, sizeof(double) * 6);
     }
@@ -3332,7 +2988,7 @@ int sfmba_step_products(sfmba_handle* h, const double* x, const double* sg, cons
     if (si_out) HIPCHK(h, hipMemcpyAsync(si_out, h->si_cur, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int64_t k = 0; k < N; ++k) {
-        const int64_t d = h->permuted ? h->order[k] : k;
+        const int64_t d = h->permuted ? h->tb.order[k] : k;
         t1_out[2 * d] = t1[2 * k]; t1_out[2 * d + 1] = t1[2 * k + 1];
     }
     *g11_out = 0.0;                                             // the partial rows in the order the device sums them
