@@ -187,7 +187,11 @@ int64_t sfmba_p2p_calls(const sfmba_handle* h);      /* collectives served by th
  * transport).  Differences around a solve give launches / collectives per outer iteration (bench.py). */
 int  sfmba_get_counters(const sfmba_handle* h, int64_t* kernel_launches, int64_t* collectives);
 /* Which kernel form the current problem runs (the problem stage of the forms table): value = 0 / 1 for name =
- * "lds_tab", "lds_vec", "sweep_rc", "sweep_rc_g", "pcg_fused", "mixed", "jfree", "rc_cons", "dense". */
+ * "lds_tab", "lds_vec", "sweep_rc", "sweep_rc_g", "pcg_fused", "mixed", "jfree", "rc_cons", "dense", "cam_multi" (some
+ * camera has several chunks: k_cam_combine runs), "xcd_b" (pass B over the XCD-aware table), "rhsrec" (the rhs pass
+ * gathers the 128-byte records), "round_blocks"; and of the solve stage, as the next compute call decides it from the
+ * transport and the options of that moment: "xcd_cam" (K3 and the rhs pass one wave per chunk), "own_inverse" (the rhs
+ * pass inverts its camera's preconditioner block itself). */
 int  sfmba_get_form(sfmba_handle* h, const char* name, int32_t* value);
 /* PCG iterations of every outer iteration of the last completed sfmba_solve on this handle (the record the next
  * solve's speculative launches are sized from); returns the number of outer iterations, writes min(that, cap)
@@ -487,6 +491,22 @@ int  sfmba_schur_matvec(sfmba_handle* h, const double* x, const double* dc, cons
  * Single rank, 64-bit storage. */
 int  sfmba_step_products(sfmba_handle* h, const double* x, const double* sg, const double* dc, const double* dp_diag,
                          double* t1_out, double* g11_out, double* dp_out, double* sums_out, double* g_out, double* si_out);
+
+/* The reduced right-hand-side + preconditioner pass of an outer iteration, by the kernels the solver itself runs in the
+ * form the handle has decided (one workgroup per camera chunk with its own 6x6 inverse, or chunk sums combined and
+ * inverted by a launch behind it; point data from the point records and the inverse blocks, or from the 128-byte
+ * records; the wave-per-chunk form over the XCD-aware table).  At x, with J = [Jc | Jp] the Jacobian blocks of the
+ * observations, W_i = Jc_i^T Jp_i (6x3), V_p = sum_{i in p} Jp_i^T Jp_i, g_p = sum_{i in p} Jp_i^T r_i,
+ * U_c = sum_{i in c} Jc_i^T Jc_i, and the caller's diagonals dc (6C) and dp (3P):
+ *     Vinv_p = (V_p + diag(dp_p))^-1,      e_p = +Vinv_p g_p   (the gradient of the point, not its negative),
+ *     rhs_c  = -sum_{i in c} W_i e_p(i)    (6 per camera: the solver's reduced right-hand side is -g_c - rhs_c),
+ *     sd_c   = +sum_{i in c} W_i Vinv_p(i) W_i^T   (21 per camera: upper triangle, row-major),
+ *     minv_c = (U_c + diag(dc_c) - sd_c)^-1        (21 per camera: upper triangle, row-major; the values the PCG reads).
+ * x: 6C+3P.  rhs_out: 6C, sd_out and minv_out: 21C, camera by camera.  A camera without observations has rhs = sd = 0.
+ * Single rank, 64-bit storage, Schur-diagonal preconditioner (the default).  Leaves the handle as the other entries
+ * of this group do: a solve afterwards is the solve without the call. */
+int  sfmba_rhs_precond(sfmba_handle* h, const double* x, const double* dc, const double* dp, double* rhs_out,
+                       double* sd_out, double* minv_out);
 
 /* Few-camera path (6 n_cameras <= 128, the reference's own problem sizes): at x, with the diagonals dc (6C) and dp
  * (3P), form S = U + diag(dc) - W (V + diag(dp))^-1 W^T (S_out: (6C)^2 row-major, may be NULL) and solve S y = rhs

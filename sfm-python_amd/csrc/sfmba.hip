@@ -1614,10 +1614,13 @@ int sfmba_get_form(sfmba_handle* h, const char* name, int32_t* value) {
     CHK(enter(h));
     if (!name || !value) return fail(h, -1, "NULL argument");
     if (!h->have_problem) return fail(h, -1, "no problem set");
+    decide_solve_forms(h);                          // the solve stage as the next compute call would decide it
     const Forms& f = h->forms;
     const struct { const char* name; int value; } forms[] = {
         {"lds_tab", f.lds_tab}, {"lds_vec", f.lds_vec}, {"sweep_rc", f.sweep_rc}, {"sweep_rc_g", f.sweep_rc_g},
         {"pcg_fused", f.pcg_fused}, {"mixed", f.mixed}, {"jfree", f.jfree}, {"rc_cons", f.rc_cons}, {"dense", f.dense},
+        {"cam_multi", f.cam_multi}, {"xcd_b", f.xcd_b}, {"rhsrec", f.use_rhsrec}, {"round_blocks", f.round_blocks},
+        {"xcd_cam", f.xcd_cam}, {"own_inverse", f.own_inverse},
     };
     for (const auto& e : forms)
         if (strcmp(name, e.name) == 0) { *value = e.value; return 0; }
@@ -2997,6 +3000,38 @@ int sfmba_step_products(sfmba_handle* h, const double* x, const double* sg, cons
         sums_out[k] = 0.0;
         for (int b = 0; b < np2; ++b) sums_out[k] += part2[(size_t)b * kBacksubCols + k];
     }
+    return 0;
+}
+
+int sfmba_rhs_precond(sfmba_handle* h, const double* x, const double* dc, const double* dp, double* rhs_out, double* sd_out,
+                      double* minv_out) {
+    CHK(enter(h));
+    CHK(begin_compute(h, x));
+    if (!dc || !dp || !rhs_out || !sd_out || !minv_out) return fail(h, -1, "NULL argument");
+    if (h->f32) return fail(h, -1, "sfmba_rhs_precond returns the sums as formed from 64-bit blocks: 64-bit storage only");
+    if (!h->forms.one_rank) return fail(h, -1, "sfmba_rhs_precond is a single-rank entry");
+    if (!h->forms.precond) return fail(h, -1, "sfmba_rhs_precond needs the Schur-diagonal preconditioner (debug option precond)");
+    if (h->forms.round_blocks) return fail(h, -1, "sfmba_rhs_precond: blocks rounded to fp32 are not the blocks its header states");
+    const int64_t C = h->C, P = h->P;
+    CHK(linearise_at(h, x));
+    std::vector<double> planes(6 * C);
+    for (int64_t c = 0; c < C; ++c)
+        for (int k = 0; k < 6; ++k) planes[k * C + c] = dc[6 * c + k];
+    HIPCHK(h, hipMemcpyAsync(h->e.p, dp, sizeof(double) * 3 * P, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->Dc.p, planes.data(), sizeof(double) * 6 * C, hipMemcpyHostToDevice, h->stream));
+    // Vinv and e = Vinv g_p into the z half of the point records (and the 128-byte records of the form that gathers them)
+    CHK(launch_point_prep(h, nullptr, h->e.as<double>(), 0.0, h->rec + 3, h->x + 6 * C,
+                          h->forms.use_rhsrec ? h->rhsrec.as<double>() : (double*)nullptr));
+    CHK(launch_rhs_and_preconditioner(h));
+    std::vector<double> a(27 * C), m(21 * C);                   // acc | sd and Minv: plane-major over the cameras
+    HIPCHK(h, hipMemcpyAsync(a.data(), h->acc(), sizeof(double) * 27 * C, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(m.data(), h->Minv.p, sizeof(double) * 21 * C, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int64_t c = 0; c < C; ++c) {
+        for (int k = 0; k < 6; ++k) rhs_out[6 * c + k] = a[k * C + c];
+        for (int k = 0; k < 21; ++k) { sd_out[21 * c + k] = a[(6 + k) * C + c]; minv_out[21 * c + k] = m[k * C + c]; }
+    }
+    HIPCHK(h, hipMemsetAsync(h->acc(), 0, sizeof(double) * 6 * C, h->stream));
     return 0;
 }
 

@@ -607,6 +607,19 @@ class Backend:
                                                   _capi.ptr(si)))
         return {"t1": t1, "g11": g11.value, "dp": dp, "sums": sums, "g": g, "si": si}
 
+    def rhs_precond(self, x, dc, dp):
+        """The rhs + preconditioner pass in the form the handle has decided (include/sfmba.h: sfmba_rhs_precond)
+        -> (rhs (C, 6), sd (C, 21), minv (C, 21))."""
+        self._flush_pending()
+        x = _f64(x, (self.n_params,), "x")
+        dc, dp = _f64(dc).reshape(-1), _f64(dp).reshape(-1)
+        if dc.shape[0] != 6 * self.n_cameras or dp.shape[0] != 3 * self.n_points:
+            raise ValueError("dc must hold 6 C and dp 3 P entries")
+        rhs, sd, minv = np.empty((self.n_cameras, 6)), np.empty((self.n_cameras, 21)), np.empty((self.n_cameras, 21))
+        self._check(self._lib.sfmba_rhs_precond(self._h, _capi.ptr(x), _capi.ptr(dc), _capi.ptr(dp), _capi.ptr(rhs),
+                                                _capi.ptr(sd), _capi.ptr(minv)))
+        return rhs, sd, minv
+
     def dense_schur(self, x, dc, dp, rhs):
         """(S, y): the formed reduced camera matrix and the solution of S y = rhs by the in-LDS PCG run to the end."""
         self._flush_pending()

@@ -1,0 +1,673 @@
+"""Extended-precision references of the solver kernels' quantities and per-entry rounding-error bounds, shared by
+test_gpu_rc_consumers.py, test_gpu_entries.py and test_host_entry_bounds.py.
+
+An entry's bound is  k eps A:  A is the kernel's expression for the entry evaluated with every operand replaced by its
+absolute value (a cancelling difference is bounded by the sum of its terms), k the number of roundings on the entry's
+longest path, eps = 2^-52.  Everything here is numpy.longdouble (64-bit mantissa on x86-64: eleven bits below a double)
+and nothing is taken from a device.
+
+Counting conventions
+  * every multiplication, addition, division and square root is one rounding (the compiler contracts some pairs into
+    FMAs: fewer, never more); sin of the device's libm counts 2 (its documented 2 ulp);
+  * test_gpu_rc_consumers.py (T_ROUNDINGS .. CHOL_ROUNDINGS, _run_roundings; its header has the paths) forms its
+    reference from blocks FETCHED from the device, counts the roundings behind the fetched values on the longest path
+    only, and doubles k because the fetched operands carry K1's roundings of the same paths;
+  * the references of the classes below are formed from x alone.  r, Jc, Jp, and the sums that nest their abs-value
+    evaluations (U, g_c, V, g_p), count the longest path: a product of factors with k_a and k_b roundings has
+    max(k_a, k_b) + 1 (_mul_path), a sum max(k_a, k_b) + 1;
+  * the deeper quantities (rhs, sd, the inverse blocks, S v, S) take the Jacobian entries of their sums at their VALUES
+    -- an entry's own abs-value evaluation is 2.3 to 2.6 times the entry at the median, and nested through the four to
+    eight factors of sd or S v it puts every bound above the entry it bounds -- a residual u - uv as |u| + |uv|, and an
+    inverse with the first-order term of its input's error, |inv| A(input) |inv|.  A small entry's error is then no
+    longer within its own count times its value, so there the counts of BOTH factors of a product are added,
+    k_a + k_b + 1 (_mul: what (1 + k_a e)(1 + k_b e)(1 + e) gives to first order; 130 for an entry of Jp whose longest
+    path has 39).  With the longest path and values the fp64 oracle itself leaves such bounds (sd 1.9 times its
+    bound at 1123 cameras, V 1.2 times on the hand-built problem); with both factors counted it stays below 0.2;
+  * a sum over a run or a camera is counted by its structure: serial trips of a lane, the fold or DPP steps of the wave,
+    the waves of the workgroup, the combine rows (run_roundings_*, cam_roundings).
+"""
+import math
+import os
+import re
+
+import numpy as np
+
+from conftest import ROOT
+from kernel_source import kernel_constant
+
+LD = np.longdouble
+EPS = float(np.finfo(np.float64).eps)
+
+
+def extended_precision():
+    """The references need a longdouble that is wider than a double (x86-64: 64-bit mantissa)."""
+    return float(np.finfo(LD).eps) < 1e-18
+
+
+def source_constant(name):
+    """Value of `<name> = <digits>` (or `#define <name> <digits>`) in the library's sources, where kernel_constant's
+    pattern does not reach (a declaration of several constants, problem_tables.hpp, sfmba.hip)."""
+    for f in ("ba_kernels.hpp", "problem_tables.hpp", "sfmba.hip"):
+        src = open(os.path.join(ROOT, "sfm-python_amd", "csrc", f)).read()
+        m = re.search(r"\b%s = (\d+)\b" % name, src) or re.search(r"#define %s (\d+)" % name, src)
+        if m:
+            return int(m.group(1))
+    raise KeyError(name)
+
+
+# ---- what test_gpu_rc_consumers.py counts (see its header) --------------------------------------------------------------
+T_ROUNDINGS = {0: 7, 1: 18}
+T1_ROUNDINGS = {0: 10, 1: 19}
+CHOL_ROUNDINGS = 15          # chol3_inverse, longest path (inv[0]): l22 9, m22 10, m20 12, m20^2 13, two additions 15
+
+
+def _run_roundings(L):
+    return np.maximum(7, np.ceil(L / 64.0) + 6)
+
+
+def _cross_abs(a, b):
+    """|a x b| evaluated with absolute values: what bounds the rounding error of the cross product."""
+    return np.stack([a[:, 1] * b[:, 2] + a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] + a[:, 0] * b[:, 2],
+                     a[:, 0] * b[:, 1] + a[:, 1] * b[:, 0]], axis=1)
+
+
+def _row_form_abs(pb, x, u):
+    """The row form's expressions for j (N, 2, 3) and t = Jc u (N, 2) evaluated with every operand replaced by its absolute
+    value (and 1 / p_z by |1 / p_z| (sum |terms of p_z|) / |p_z|): gamma_n times this bounds the rounding error of n roundings."""
+    C, ci, pi = pb.n_cameras, np.asarray(pb.camera_indices), np.asarray(pb.point_indices)
+    K = np.abs(np.asarray(pb.K, dtype=LD))
+    cam, X = x[:6 * C].reshape(C, 6).astype(LD), x[6 * C:].reshape(-1, 3).astype(LD)
+    w, T = cam[:, :3], cam[:, 3:]
+    th2 = np.einsum("ci,ci->c", w, w)
+    th = np.sqrt(th2)
+    small = th < 1e-6
+    ths = np.where(small, 1.0, th)
+    a = np.where(small, 1.0, np.sin(ths) / ths)
+    b = np.where(small, 0.5, (1 - np.cos(ths)) / ths ** 2)
+    cc = np.where(small, 1.0 / 6, (ths - np.sin(ths)) / ths ** 3)
+    W = np.zeros((C, 3, 3), dtype=LD)
+    W[:, 0, 1], W[:, 0, 2], W[:, 1, 0], W[:, 1, 2], W[:, 2, 0], W[:, 2, 1] = -w[:, 2], w[:, 1], w[:, 2], -w[:, 0], -w[:, 1], w[:, 0]
+    R = np.eye(3, dtype=LD)[None] + a[:, None, None] * W + b[:, None, None] * np.einsum("cij,cjk->cik", W, W)
+    Ra = np.abs(R)[ci]
+    v, va = X[pi] - T[ci], np.abs(X[pi]) + np.abs(T[ci])
+    pz = np.einsum("nij,nj->ni", R[ci], v) @ np.asarray(pb.K, dtype=LD).T[:, 2]
+    pa = np.einsum("nij,nj->ni", Ra, va) @ K.T
+    iza = pa[:, 2] / pz ** 2
+    ja = np.empty((len(ci), 2, 3), dtype=LD)
+    for k in range(2):
+        pka = pa[:, k] * iza
+        ba = (K[k][None, :] + pka[:, None] * K[2][None, :]) * iza[:, None]
+        ja[:, k, :] = np.einsum("nm,nmi->ni", ba, Ra)
+    uw, uT, wa = np.abs(u[:, :3].astype(LD)), np.abs(u[:, 3:].astype(LD)), np.abs(w)
+    ca = _cross_abs(wa, uw)
+    aa = uw + np.abs(b)[:, None] * ca + np.abs(cc)[:, None] * _cross_abs(wa, ca)
+    ga = _cross_abs(va, aa[ci]) + uT[ci]
+    return ja, np.einsum("nki,ni->nk", ja, ga)
+
+
+def _inv3(A):
+    """(P, 3, 3) symmetric -> inverses, by cofactors in the arrays' own precision (numpy.linalg has no longdouble)."""
+    c = np.empty_like(A)
+    for i in range(3):
+        for j in range(3):
+            r, s = [k for k in range(3) if k != i], [k for k in range(3) if k != j]
+            c[:, j, i] = (-1) ** (i + j) * (A[:, r[0], s[0]] * A[:, r[1], s[1]] - A[:, r[0], s[1]] * A[:, r[1], s[0]])
+    det = np.einsum("pi,pi->p", A[:, 0, :], c[:, :, 0])
+    return c / det[:, None, None]
+
+
+# ---- helpers of the references formed from x ---------------------------------------------------------------------------
+def _mul(ka, kb):
+    """Roundings of a product whose factors carry ka and kb, both counted (the added count of the module's header)."""
+    return ka + kb + 1
+
+
+def _mul_path(ka, kb):
+    """The same on the longest path alone."""
+    return np.maximum(ka, kb) + 1
+
+
+def _add(ka, kb):
+    return np.maximum(ka, kb) + 1
+
+
+def _cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def _xabs(a, b):
+    """_cross_abs for arrays of any (broadcasting) shape."""
+    return np.stack([a[..., 1] * b[..., 2] + a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] + a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] + a[..., 1] * b[..., 0]], axis=-1)
+
+
+def _inv_spd(A):
+    """(B, n, n) symmetric positive definite -> inverses by Gauss-Jordan without pivoting, in the arrays' own precision."""
+    n = A.shape[1]
+    M = np.concatenate([A.copy(), np.broadcast_to(np.eye(n, dtype=A.dtype), A.shape).copy()], axis=2)
+    for j in range(n):
+        M[:, j, :] = M[:, j, :] / M[:, j, j][:, None]
+        for i in range(n):
+            if i != j:
+                M[:, i, :] = M[:, i, :] - M[:, i, j][:, None] * M[:, j, :][:, :]
+    return M[:, :, n:]
+
+
+def upper(M):
+    """(B, k, k) symmetric -> (B, k (k + 1) / 2) row-major upper triangle (the packed layout of the C-ABI)."""
+    iu = np.triu_indices(M.shape[1])
+    return M[:, iu[0], iu[1]]
+
+
+def _group_max(values, index, n):
+    out = np.zeros(n)
+    np.maximum.at(out, index, np.asarray(values, dtype=np.float64))
+    return out
+
+
+# ---- sums by their structure ---------------------------------------------------------------------------------------------
+TILE = 64                                            # K1: one wave per 64 consecutive observations of the point-major order
+SPD6_ROUNDINGS = 29          # spd6_inverse (k_cam_rhs_diag's own inverse and k_cam_prep_schur alike), longest path:
+#   Cholesky column by column, a product and a subtraction per earlier column, sqrt, reciprocal, scaling: L[5][5] after 26;
+#   M = L^-1 by forward substitution: 27 on M[5][0]; out[0] = sum_k M[k][0]^2: a product and an addition more: 29
+SIN_ROUNDINGS = 2            # sin of the device library
+
+
+def run_roundings_k1(L):
+    """V_p and g_p of k_resjac: the 7 FMA steps of seg_reduce_serial inside a tile, then one addition per further tile of
+    the run in point_edge_fixup -- a run of L observations touches at most ceil(L / 64) + 1 tiles."""
+    return 7 + np.ceil(np.asarray(L) / float(TILE))
+
+
+def run_roundings_sweep(L):
+    """y_p of pass A: a run of up to 64 observations lies inside one step (seg_reduce_serial, 7); a longer one is a step of
+    its own: ceil(L / 64) serial additions per lane, then wave_sum (4 DPP steps and 3 row totals: 7)."""
+    L = np.asarray(L)
+    return np.where(L <= 64, 7, np.ceil(L / 64.0) + 7)
+
+
+def cam_roundings(Lc, lanes, waves, chunk_len=None, per_wave=False, fold=6):
+    """Additions on the longest path of a camera's sum over its Lc observations in a camera-major pass: one per
+    observation of a lane (ceil(chunk / lanes) serial trips), the `fold` steps of the wave (wave_fold_sum 6, wave_sum 7),
+    the waves of the workgroup added in wave order, and the rows k_cam_combine adds for a camera of several chunks.
+    per_wave: the XCD-aware table -- one wave per chunk (a chunk holds at most all Lc observations), no workgroup sum, and
+    always the kWaveChunkRanges rows of k_cam_combine_w."""
+    Lc = np.asarray(Lc, dtype=np.float64)
+    if per_wave:
+        return np.ceil(Lc / 64.0) + fold + source_constant("kWaveChunkRanges")
+    nch = np.maximum(1, np.ceil(Lc / chunk_len))
+    return np.ceil(np.minimum(Lc, chunk_len) / lanes) + fold + waves + np.where(nch > 1, nch, 0)
+
+
+class Structure:
+    """How the camera-major passes cut and add a problem's sums under a set of debug options (the host's forms table:
+    decide_problem_forms / decide_solve_forms in sfmba.hip), and the additions that puts on a camera's longest path."""
+
+    def __init__(self, C, P, ci, pi, options=None):
+        o = dict(options or {})
+        N = len(ci)
+        self.Lc, self.Lp = np.bincount(ci, minlength=C), np.bincount(pi, minlength=P)
+        n_cu = 256                                   # (an MI355X; below two million observations the length is 4096 whatever it is)
+        self.chunk_len = o["cam_chunk"] if o.get("cam_chunk", 0) > 0 else max(4096, -(-N // (2 * n_cu)))
+        self.cam_multi = bool(np.any(self.Lc > self.chunk_len))
+        self.xcd_b = o.get("xcd_chunks", -1) == 1 or (o.get("xcd_chunks", -1) != 0 and P >= 250000)
+        self.xcd_cam = self.xcd_b and o.get("xcd_cam", -1) != 0
+        self.own_inverse = not self.cam_multi           # (one rank; the wave-per-chunk form of the rhs pass does not look at it)
+        ct, rt = kernel_constant("kCamThreads"), source_constant("SFMBA_RHS_THREADS")
+        if self.xcd_cam:                             # k_cam_blocks_w, k_cam_rhs_diag_w: wave_fold_sum, k_cam_combine_w
+            self.k3 = self.rhs = cam_roundings(self.Lc, 64, 0, per_wave=True)
+        else:                                        # k_cam_blocks (256 lanes), k_cam_rhs_diag (192 lanes), k_cam_combine
+            self.k3 = cam_roundings(self.Lc, ct, ct // 64, self.chunk_len)
+            self.rhs = cam_roundings(self.Lc, rt, rt // 64, self.chunk_len)
+        # pass B: k_cam_schur_w (wave_sum) over the XCD-aware table, else k_cam_schur over the chunk list
+        self.pass_b = cam_roundings(self.Lc, 64, 0, per_wave=True, fold=7) if self.xcd_b else cam_roundings(self.Lc, ct, ct // 64, self.chunk_len)
+
+
+# ---- references from x ---------------------------------------------------------------------------------------------------
+class Linearisation:
+    """r (N, 2), Jc (N, 2, 6), Jp (N, 2, 3) at x in longdouble by the analytic formulas of the oracle
+    (oracle/ba_oracle.py: jacobian_blocks), their abs-value evaluations (suffix a) as `observe` of ba_kernels.hpp orders the
+    operations, and the roundings of an entry (per observation: they depend on the camera's angle) -- k_* on the longest
+    path, ka_* with both factors of every product counted (the paths below give the added form: read k_a + k_b + 1 as
+    max(k_a, k_b) + 1 for k_*; on the hand-built problem r 34 | 67, Jp 39 | 130, Jc 47 | 167).
+
+    The camera table (cam_row_values), with t = |w|, h = t / 2; sin(t) / t passes the relative error of t on times
+    kappa(t) = |t cos t / sin t|:
+        t^2: 3;  t: sqrt, half the 3 and one more: 3;  a = sin(t) / t: 3 kappa + SIN_ROUNDINGS + 3 + 1 roundings of |a|,
+        the series of the small angles stays below that: 10 + 3 kappa.  kappa |a| = |cos t| stays finite where a
+        vanishes (t = pi), so a carries its error as e_a = 3 |cos t| + 7 |a| (10 |a| below 1e-4) instead of a count;
+        b = 0.5 (sin h / h)^2: twice that of sin h / h and the product: 13 + 6 max(1, kappa(h))
+        c: (t - sin t) / (t^2 t) with A = (t + |sin t|) / t^3 -- the error sin passes on, 3 |t cos t|, is below 3 A(numerator):
+           numerator 6, denominator 7, division 1 -- or the series to t^10 below 0.3 with A = sum |terms| (fifth power of
+           t^2 15, four products, the division, five additions: 25): 28 either way
+        R: off the diagonal -a w + b w w: (e_a + 2 |a|) |w| + (k_b + 3) b |w w|; on it 1 + b (w^2 - t^2): (k_b + 5) of the
+           second term and the last addition;  k_R = k_b + 6, and A(R) is raised to error / k_R where that is more (an
+           off-diagonal entry at t = pi)
+    One observation (observe<true>):
+        v = X - T: 1;  q = R v: k_R + 1 + 1, two additions: k_R + 4;  p = K q (K exact): k_q + 3;  iz = 1 / p_z: k_p + 1, with
+        A = A(p_z) / p_z^2;  u = p iz: k_p + k_iz + 1;  r = u - uv: k_u + 1
+        a = (K - u K_2) iz: (k_u + 2) + k_iz + 1;  j = a R, three terms: k_a + k_R + 1 + 2  -- Jp, and -Jp the T half of Jc
+        m = j x v: k_j + 1 + 1 + 1;  s = m x w: k_m + 2;  t = s x w: k_s + 2;  -(m - b s + c t): the larger of b + k_s + 1 and
+        c + k_t + 1 after two additions  -- the w half of Jc
+    Jcs, Jps, rs: what the sums of the methods below take for |Jc|, |Jp| and |r| (the module's header)."""
+
+    def __init__(self, C, P, ci, pi, uv, K, x):
+        if not extended_precision():
+            raise RuntimeError("numpy.longdouble is no wider than a double on this machine")
+        ci, pi = np.asarray(ci, dtype=np.int64), np.asarray(pi, dtype=np.int64)
+        self.C, self.P, self.N, self.ci, self.pi = C, P, len(ci), ci, pi
+        K = np.asarray(K, dtype=LD)
+        Ka = np.abs(K)
+        x = np.asarray(x, dtype=np.float64)
+        cam, X = x[:6 * C].reshape(C, 6).astype(LD), x[6 * C:].reshape(P, 3).astype(LD)
+        w, T = cam[:, :3], cam[:, 3:]
+        self.w, self.wa = w, np.abs(w)
+        th2 = np.einsum("ci,ci->c", w, w)
+        th = np.sqrt(th2)
+        zero = th == 0
+        ths = np.where(zero, LD(1), th)
+        half = ths / 2
+        a = np.where(zero, LD(1), np.sin(ths) / ths)
+        b = np.where(zero, LD(0.5), (np.sin(half) / half) ** 2 / 2)
+        coef = [LD((-1) ** n) / LD(math.factorial(2 * n + 3)) for n in range(14)]        # (t - sin t) / t^3 as a series
+        c_series, ca_series = sum(f * th2 ** n for n, f in enumerate(coef)), sum(abs(f) * th2 ** n for n, f in enumerate(coef[:6]))
+        c = np.where(th < 0.5, c_series, (ths - np.sin(ths)) / ths ** 3)
+        ca = np.where(th < 0.3, ca_series, (ths + np.abs(np.sin(ths))) / ths ** 3)       # (0.3: the device's own switch)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            sh = np.where(zero, 1.0, np.abs(np.sin(half) / half)).astype(np.float64)
+            k_b = 13 + 6 * np.where(ths < 1e-4, 1.0, np.maximum(1.0, np.abs(np.cos(half)).astype(np.float64) / sh))
+        e_a = np.where(ths < 1e-4, 10.0, 3 * np.abs(np.cos(ths)) + 7 * np.abs(a)).astype(np.float64)   # k_a |a|: finite at t = pi
+        k_c = np.full(C, 28.0)
+        Wx = np.zeros((C, 3, 3), dtype=LD)
+        Wx[:, 0, 1], Wx[:, 0, 2], Wx[:, 1, 0], Wx[:, 1, 2], Wx[:, 2, 0], Wx[:, 2, 1] = -w[:, 2], w[:, 1], w[:, 2], -w[:, 0], -w[:, 1], w[:, 0]
+        R = np.eye(3, dtype=LD)[None] + a[:, None, None] * Wx + b[:, None, None] * np.einsum("cij,cjk->cik", Wx, Wx)
+        Ra = np.abs(a)[:, None, None] * np.abs(Wx) + b[:, None, None] * np.einsum("ci,cj->cij", self.wa, self.wa)
+        ER = (e_a[:, None, None] + 2 * np.abs(a)[:, None, None]) * np.abs(Wx) + ((k_b + 3) * b)[:, None, None] * np.einsum("ci,cj->cij", self.wa, self.wa)
+        for i in range(3):
+            Ra[:, i, i] = 1 + b * (w[:, i] ** 2 + th2)
+            ER[:, i, i] = Ra[:, i, i] + (k_b + 5) * b * (w[:, i] ** 2 + th2)
+        k_R = k_b + 6
+        Ra = np.maximum(Ra, ER / k_R[:, None, None])         # (an entry that vanishes where a does keeps a's error)
+        self.b, self.c, self.ca, self.k_b, self.k_c, self.R = b, c, ca, k_b, k_c, R
+        uv = np.asarray(uv, dtype=np.float64).reshape(-1, 2).astype(LD)
+        # ---- one observation ----
+        Rn, Ran = R[ci], Ra[ci]
+        self.v, self.va = X[pi] - T[ci], np.abs(X[pi]) + np.abs(T[ci])
+        q, qa = np.einsum("nij,nj->ni", Rn, self.v), np.einsum("nij,nj->ni", Ran, self.va)
+        p, pa = q @ K.T, qa @ Ka.T
+        iz, iza = 1 / p[:, 2], pa[:, 2] / p[:, 2] ** 2
+        u, ua = p[:, :2] * iz[:, None], pa[:, :2] * iza[:, None]
+        self.r, self.ra = u - uv, ua + np.abs(uv)
+        A = (K[None, :2, :] - u[:, :, None] * K[None, 2:3, :]) * iz[:, None, None]
+        Aa = (Ka[None, :2, :] + ua[:, :, None] * Ka[None, 2:3, :]) * iza[:, None, None]
+        self.Jp, self.Jpa = np.einsum("nkm,nmi->nki", A, Rn), np.einsum("nkm,nmi->nki", Aa, Ran)
+        m, ma = _cross(self.Jp, self.v[:, None, :]), _xabs(self.Jpa, self.va[:, None, :])
+        wn, wan = w[ci][:, None, :], self.wa[ci][:, None, :]
+        s, sa = _cross(m, wn), _xabs(ma, wan)
+        t, ta = _cross(s, wn), _xabs(sa, wan)
+        bn, cn, can = b[ci][:, None, None], c[ci][:, None, None], ca[ci][:, None, None]
+        Jw, Jwa = -(m - bn * s + cn * t), ma + bn * sa + can * ta
+        self.Jc, self.Jca = np.concatenate([Jw, -self.Jp], axis=2), np.concatenate([Jwa, self.Jpa], axis=2)
+
+        def counts(mul):
+            """k of r, Jp and Jc by the docstring's paths with `mul` as the count of a product (Jc: the T half has
+            k_jp < k_jw, one count for the six columns)."""
+            kR = k_R[ci]
+            k_p = mul(kR, 1) + 2 + 3
+            k_iz = k_p + 1
+            k_u = mul(k_p, k_iz)
+            k_jp = mul(mul(k_u + 2, k_iz), kR) + 2
+            k_m = mul(k_jp, 1) + 1
+            return k_u + 1, k_jp, _add(_add(k_m, mul(k_b[ci], k_m + 2)), mul(k_c[ci], k_m + 4))
+        # The checks of r, Jc, Jp and of the sums over them that nest their abs-value evaluations (U, g_c, V, g_p): the
+        # longest path.  The deeper quantities, whose sums take the entries at their values: both factors counted.
+        self.k_r, self.k_jp, self.k_jc = counts(_mul_path)
+        self.ka_r, self.ka_jp, self.ka_jc = counts(_mul)
+        self.Jcs, self.Jps, self.rs = np.abs(self.Jc), np.abs(self.Jp), np.abs(u) + np.abs(uv)
+        self.Lp, self.Lc = np.bincount(pi, minlength=P), np.bincount(ci, minlength=C)
+
+    # ---- the normal equations' blocks --------------------------------------------------------------------------------------
+    def blocks(self, st, deep=False):
+        """U (C, 6, 6), g_c (C, 6), V (P, 3, 3), g_p (P, 3): values, abs-value evaluations and k per camera / point.
+        A term is a product of two entries and the row's second product added; the point sums by run_roundings_k1, the
+        camera sums by `st.k3` (K3 in the form `st` describes).  As checked (deep = False): the entries' own abs-value
+        evaluations nested, k on the longest path.  As operands of the deeper quantities (deep = True): the entries at
+        their values, the counts of both factors added (the module's header)."""
+        cache = self.__dict__.setdefault("_blocks", {})
+        if (id(st), deep) in cache:
+            return cache[id(st), deep]
+        C, P, ci, pi = self.C, self.P, self.ci, self.pi
+        mul = _mul if deep else _mul_path
+        Jca, Jpa, ra = (self.Jcs, self.Jps, self.rs) if deep else (self.Jca, self.Jpa, self.ra)
+        k_jc, k_jp, k_r = (self.ka_jc, self.ka_jp, self.ka_r) if deep else (self.k_jc, self.k_jp, self.k_r)
+        out = {}
+        for name, n, idx, A, Aa, kA, adds in (("U", C, ci, self.Jc, Jca, k_jc, st.k3),
+                                              ("V", P, pi, self.Jp, Jpa, k_jp, run_roundings_k1(self.Lp))):
+            val, ab = np.zeros((n, A.shape[2], A.shape[2]), dtype=LD), np.zeros((n, A.shape[2], A.shape[2]), dtype=LD)
+            np.add.at(val, idx, np.einsum("nki,nkj->nij", A, A))
+            np.add.at(ab, idx, np.einsum("nki,nkj->nij", Aa, Aa))
+            out[name], out[name + "a"], out["k_" + name] = val, ab, _group_max(mul(kA, kA) + 1, idx, n) + adds
+        for name, n, idx, A, Aa, kA, adds in (("gc", C, ci, self.Jc, Jca, k_jc, st.k3),
+                                              ("gp", P, pi, self.Jp, Jpa, k_jp, run_roundings_k1(self.Lp))):
+            val, ab = np.zeros((n, A.shape[2]), dtype=LD), np.zeros((n, A.shape[2]), dtype=LD)
+            np.add.at(val, idx, np.einsum("nki,nk->ni", A, self.r))
+            np.add.at(ab, idx, np.einsum("nki,nk->ni", Aa, ra))
+            out[name], out[name + "a"], out["k_" + name] = val, ab, _group_max(mul(kA, k_r) + 1, idx, n) + adds
+        cache[id(st), deep] = out
+        return out
+
+    def point_inverses(self, st, dp):
+        """Vinv = (V + diag dp)^-1 by chol3_inverse and e = Vinv g_p (k_point_prep).  The inverse's error: that of its input,
+        k_V + 1 roundings of A(V) + dp, and CHOL_ROUNDINGS of its own, both passed on by |Vinv| . |Vinv| (first order:
+        d(A^-1) = -A^-1 dA A^-1);  e: three products and two additions."""
+        b = self.blocks(st, deep=True)
+        D = np.einsum("pi,ij->pij", np.asarray(dp, dtype=np.float64).reshape(self.P, 3).astype(LD), np.eye(3, dtype=LD))
+        Vinv = _inv3(b["V"] + D)
+        aV = np.abs(Vinv)
+        out = {"Vinv": Vinv, "Vinva": np.einsum("pij,pjk,pkl->pil", aV, b["Va"] + D, aV), "k_Vinv": b["k_V"] + 1 + CHOL_ROUNDINGS}
+        out["e"], out["ea"] = np.einsum("pij,pj->pi", Vinv, b["gp"]), np.einsum("pij,pj->pi", out["Vinva"], b["gpa"])
+        out["k_e"] = _mul(out["k_Vinv"], b["k_gp"]) + 2
+        return out
+
+    # ---- the rhs + preconditioner pass ---------------------------------------------------------------------------------------
+    def rhs_pass(self, st, dc, dp):
+        """include/sfmba.h, sfmba_rhs_precond: rhs = -sum W e, sd = sum W Vinv W^T, minv = (U + diag dc - sd)^-1, as
+        k_cam_rhs_diag forms them:  s = Jp e (three terms), rhs -= Jc^T s (two terms, then the camera's sum: st.rhs);
+        h = Vinv Jp^T, G = Jp h (three terms each), m = G Jc (two terms), sd += Jc^T m (two terms).  The 6x6 inverse by
+        spd6_inverse from U - sd + dc (two additions): SPD6_ROUNDINGS of its own, like point_inverses."""
+        C, ci, pi = self.C, self.ci, self.pi
+        b, pv = self.blocks(st, deep=True), self.point_inverses(st, dp)
+        s, sa = np.einsum("nki,ni->nk", self.Jp, pv["e"][pi]), np.einsum("nki,ni->nk", self.Jps, pv["ea"][pi])
+        k_s = _mul(self.ka_jp, pv["k_e"][pi]) + 2
+        rhs, rhsa = np.zeros((C, 6), dtype=LD), np.zeros((C, 6), dtype=LD)
+        np.add.at(rhs, ci, -np.einsum("nki,nk->ni", self.Jc, s))
+        np.add.at(rhsa, ci, np.einsum("nki,nk->ni", self.Jcs, sa))
+        k_rhs = _group_max(_mul(self.ka_jc, k_s) + 1, ci, C) + st.rhs
+        h, ha = np.einsum("nij,nkj->nki", pv["Vinv"][pi], self.Jp), np.einsum("nij,nkj->nki", pv["Vinva"][pi], self.Jps)
+        k_h = _mul(pv["k_Vinv"][pi], self.ka_jp) + 2
+        G, Ga = np.einsum("nki,nli->nkl", self.Jp, h), np.einsum("nki,nli->nkl", self.Jps, ha)
+        k_G = _mul(self.ka_jp, k_h) + 2
+        m, ma = np.einsum("nkl,nlj->nkj", G, self.Jc), np.einsum("nkl,nlj->nkj", Ga, self.Jcs)
+        k_m = _mul(k_G, self.ka_jc) + 1
+        sd, sda = np.zeros((C, 6, 6), dtype=LD), np.zeros((C, 6, 6), dtype=LD)
+        np.add.at(sd, ci, np.einsum("nki,nkj->nij", self.Jc, m))
+        np.add.at(sda, ci, np.einsum("nki,nkj->nij", self.Jcs, ma))
+        k_sd = _group_max(_mul(self.ka_jc, k_m) + 1, ci, C) + st.rhs
+        D = np.einsum("ci,ij->cij", np.asarray(dc, dtype=np.float64).reshape(C, 6).astype(LD), np.eye(6, dtype=LD))
+        M = b["U"] + D - sd
+        Minv = _inv_spd(M)
+        aM = np.abs(Minv)
+        return {"rhs": rhs, "rhsa": rhsa, "k_rhs": k_rhs, "sd": sd, "sda": sda, "k_sd": k_sd, "M": M, "minv": Minv,
+                "minva": np.einsum("cij,cjk,ckl->cil", aM, b["Ua"] + np.abs(D) + sda, aM),
+                "k_minv": np.maximum(b["k_U"], k_sd) + 2 + SPD6_ROUNDINGS}
+
+    # ---- the implicit Schur product ------------------------------------------------------------------------------------------
+    def _a_prime(self, u):
+        """a' = u_w - b (w x u_w) + c (w x (w x u_w)) per camera (rc_put_au, k_rc_table, the prologue of pass B): the cross
+        products 2 and 4, the products with b and c, two additions."""
+        uw = u[:, :3]
+        c0, c0a = _cross(self.w, uw), _xabs(self.wa, np.abs(uw))
+        ap = uw - self.b[:, None] * c0 + self.c[:, None] * _cross(self.w, c0)
+        apa = np.abs(uw) + self.b[:, None] * c0a + self.ca[:, None] * _xabs(self.wa, c0a)
+        return ap, apa, _add(_mul(self.k_b, 2), _mul(self.k_c, 4)) + 1
+
+    def schur_product(self, st, dc, dp, v, pass_a):
+        """y = S v, S = U + diag dc - W (V + diag dp)^-1 W^T (include/sfmba.h: sfmba_schur_matvec).  The value from the blocks:
+        t = Jc v, z = Vinv sum Jp^T t, y = sum Jc^T (t - Jp z) + dc v.  The abs-value evaluation and k follow the kernels:
+        pass A (`pass_a` = "rc": k_point_sweep_rc, t_k = -j_k . (v x a' + v_T), three terms;  "stored": k_point_sweep,
+            t = Jc v, six terms added to 0):  y_p = sum j_k t_k (two terms, then the run: run_roundings_sweep),  z = Vinv y_p
+        pass B (k_cam_schur / k_cam_schur_w, exact blocks): h = z + v x a' + v_T,  u_k = -j_k . h,  q = sum_k u_k j_k,
+            sums of q x v and q over the camera (st.pass_b), the rotation Jacobian applied to the summed q x v like a';
+        the host adds dc v: two more."""
+        C, ci, pi = self.C, self.ci, self.pi
+        pv = self.point_inverses(st, dp)
+        vc, dcc = np.asarray(v, dtype=np.float64).reshape(C, 6).astype(LD), np.asarray(dc, dtype=np.float64).reshape(C, 6).astype(LD)
+        ap, apa, k_ap = self._a_prime(vc)
+        g = _cross(self.v, ap[ci]) + vc[ci, 3:]
+        ga = _xabs(self.va, apa[ci]) + np.abs(vc[ci, 3:])
+        k_g = _mul(1, k_ap[ci]) + 2
+        t = np.einsum("nki,ni->nk", self.Jc, vc[ci])
+        if pass_a == "rc":
+            ta, k_t = np.einsum("nki,ni->nk", self.Jps, ga), _mul(self.ka_jp, k_g) + 2
+        else:
+            ta, k_t = np.einsum("nki,ni->nk", self.Jcs, np.abs(vc[ci])), self.ka_jc + 1 + 6
+        yp, ypa = np.zeros((self.P, 3), dtype=LD), np.zeros((self.P, 3), dtype=LD)
+        np.add.at(yp, pi, np.einsum("nki,nk->ni", self.Jp, t))
+        np.add.at(ypa, pi, np.einsum("nki,nk->ni", self.Jps, ta))
+        k_yp = _group_max(_mul(self.ka_jp, k_t) + 2, pi, self.P) + run_roundings_sweep(self.Lp)
+        z, za = np.einsum("pij,pj->pi", pv["Vinv"], yp), np.einsum("pij,pj->pi", pv["Vinva"], ypa)
+        k_z = _mul(pv["k_Vinv"], k_yp) + 2
+        y = np.zeros((C, 6), dtype=LD)
+        np.add.at(y, ci, np.einsum("nki,nk->ni", self.Jc, t - np.einsum("nki,ni->nk", self.Jp, z[pi])))
+        y = y + dcc * vc
+        # pass B in its own form
+        ha = za[pi] + ga
+        k_h = np.maximum(k_z[pi], k_g) + 1
+        ua, k_u = np.einsum("nki,ni->nk", self.Jps, ha), _mul(self.ka_jp, k_h) + 2
+        qa, k_q = np.einsum("nk,nki->ni", ua, self.Jps), _mul(k_u, self.ka_jp) + 2
+        Ma, Sa = np.zeros((C, 3), dtype=LD), np.zeros((C, 3), dtype=LD)
+        np.add.at(Ma, ci, _xabs(qa, self.va))
+        np.add.at(Sa, ci, qa)
+        k_S = _group_max(k_q, ci, C) + st.pass_b
+        k_M = _group_max(_mul(k_q, 1) + 1, ci, C) + st.pass_b
+        c0a = _xabs(Ma, self.wa)
+        outa = np.concatenate([Ma + self.b[:, None] * c0a + self.ca[:, None] * _xabs(c0a, self.wa), Sa], axis=1)
+        k_w = _add(_add(k_M, _mul(self.k_b, k_M + 2)), _mul(self.k_c, k_M + 4))
+        k_y = np.concatenate([np.repeat(k_w[:, None], 3, axis=1), np.repeat(k_S[:, None], 3, axis=1)], axis=1) + 2
+        return {"y": y, "ya": outa + np.abs(dcc * vc), "k_y": k_y}
+
+    def dense_s(self, st, dc, dp):
+        """The explicit S = U + diag dc - sum_p W_a(p) Vinv_p W_b(p)^T (6 C x 6 C) as k_schur_blocks forms it: W = Jc^T Jp
+        (two terms), y = W Vinv (three terms), s += y W_b^T (three terms), the pair list's sum (one workgroup of 256 lanes:
+        serial trips, 6 fold steps, 4 waves), and the host's U + dc - s.  One k for all entries: the largest of each stage."""
+        C, P, ci, pi = self.C, self.P, self.ci, self.pi
+        b, pv = self.blocks(st, deep=True), self.point_inverses(st, dp)
+        W, Wa = np.einsum("nki,nkj->nij", self.Jc, self.Jp), np.einsum("nki,nkj->nij", self.Jcs, self.Jps)
+        Wm, Wma = np.zeros((C, P, 6, 3), dtype=LD), np.zeros((C, P, 6, 3), dtype=LD)
+        np.add.at(Wm, (ci, pi), W)
+        np.add.at(Wma, (ci, pi), Wa)
+        S = -np.einsum("apil,bpjl->aibj", np.einsum("apik,pkl->apil", Wm, pv["Vinv"]), Wm).reshape(6 * C, 6 * C)
+        Sa = np.einsum("apil,bpjl->aibj", np.einsum("apik,pkl->apil", Wma, pv["Vinva"]), Wma).reshape(6 * C, 6 * C)
+        dcc = np.asarray(dc, dtype=np.float64).reshape(-1).astype(LD)
+        for c in range(C):
+            S[6 * c:6 * c + 6, 6 * c:6 * c + 6] += b["U"][c]
+            Sa[6 * c:6 * c + 6, 6 * c:6 * c + 6] += b["Ua"][c]
+        S, Sa = S + np.diag(dcc), Sa + np.diag(np.abs(dcc))
+        k_W = float(np.max(_mul(self.ka_jc, self.ka_jp) + 1))
+        k_term = _mul(_mul(k_W, float(pv["k_Vinv"].max())) + 2, k_W) + 2
+        seen = (np.bincount(ci * P + pi, minlength=C * P).reshape(C, P)).astype(np.float64)
+        pairs = float((seen @ seen.T).max())                         # longest pair list, with multiplicity
+        k = max(k_term + math.ceil(pairs / 256.0) + 6 + 4, float(b["k_U"].max())) + 2
+        return {"S": S, "Sa": Sa, "k_S": k}
+
+
+# ---- the check itself -------------------------------------------------------------------------------------------------------
+def bound(k, A):
+    """k eps A, entry by entry (k: a scalar or one value per camera / point / observation, broadcast over the entry's block)."""
+    k = np.asarray(k, dtype=np.float64)
+    A = np.asarray(A)
+    return k.reshape(k.shape + (1,) * (A.ndim - k.ndim)) * EPS * A
+
+
+def ratio(got, ref, bnd):
+    """Largest |got - ref| / bound over the entries (entries with bound 0 -- structural zeros -- must be exact)."""
+    err = np.abs(np.asarray(got).astype(LD) - ref)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(bnd > 0, err / bnd, np.where(err == 0, 0.0, np.inf))
+    return float(q.max()) if q.size else 0.0
+
+
+def share_below(bnd, ref, level):
+    """Share of the non-zero entries of `ref` whose bound lies below level |ref| (what keeps a bound honest)."""
+    nz = ref != 0
+    return float(np.mean(bnd[nz] < level * np.abs(ref[nz]))) if nz.any() else 1.0
+
+
+def rel_max(a, b):
+    """The normwise figure of tests/test_gpu_parity.py (_rel)."""
+    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(1e-300, np.abs(np.asarray(b)).max()))
+
+
+# ---- the problems and cases of test_gpu_entries.py / test_host_entry_bounds.py ---------------------------------------------
+HAND_RUNS = (64, 63, 1, 65, 128, 256, 300)           # the first point runs: see hand_built
+HAND_CAMERAS = (0, 1, 191, 192, 193, 383, 384, 385, 577, 255, 256, 257, 511, 512, 513)
+
+
+def _problem(C, P, ci, pi, base, orc, seed, shift=(300.0, -200.0), noise=20.0):
+    """A BAProblem over the given structure with base's cameras, points and K: pixels = projections at x_true + noise."""
+    from sfmba.synthetic import BAProblem
+    rng = np.random.default_rng(seed)
+    args = (C, P, ci, pi, np.zeros((len(pi), 2)), base.K)
+    uv = orc.compute_residuals(base.x_true, *args).reshape(-1, 2) + np.asarray(shift) + rng.normal(0.0, noise, (len(pi), 2))
+    return BAProblem(C, P, ci, pi, uv, base.K, base.x0, base.x_true)
+
+
+def hand_built(orc):
+    """_hand_built of test_gpu_rc_consumers.py extended to the loop edges of K1, K3, the rhs pass and pass B.
+    15 cameras (one more than a multiple of kWaveChunkCams would be 13 or 17; every count below needs a camera of its own)
+    with HAND_CAMERAS observations: the trips of k_cam_rhs_diag's 192-lane pipeline (0, 1, 191 .. 193, 383 .. 385, 577) and the
+    two-per-lane trips of k_cam_blocks / four-per-lane trips of k_cam_schur (255 .. 257, 511 .. 513); 4610 observations.
+    Point runs in point-major order, tiles of 64: 64 (starts on a tile cut and ends on the next), 63, 1 (ends exactly on
+    the cut at 128), 65 (starts exactly on it), 128, 256 (from 321 to 577: the whole tiles 6, 7 and 8 lie inside it, so
+    point_edge_fixup adds several rows), 300, then runs of 1 .. 7 and one point without observations."""
+    import sfmba
+    counts = list(HAND_RUNS)
+    N = sum(HAND_CAMERAS)
+    cycle, k = (3, 5, 2, 7, 4, 1, 6), 0
+    while sum(counts) < N:
+        counts.append(min(cycle[k % len(cycle)], N - sum(counts)))
+        k += 1
+    counts.insert(40, 0)                                                      # a point nobody sees
+    P, C = len(counts), len(HAND_CAMERAS)
+    pi = np.repeat(np.arange(P), counts)
+    ci = np.random.default_rng(11).permutation(np.repeat(np.arange(C), HAND_CAMERAS))
+    return _problem(C, P, ci, pi, sfmba.make_problem(C, P, 4 * P, seed=4), orc, 7)
+
+
+def chunk_edge(orc):
+    """Three cameras with 4096, 4097 and 200 observations over 600 points: the default cam_chunk_len (4096) keeps the first
+    a single workgroup and cuts the second in two, whose rows k_cam_combine adds."""
+    import sfmba
+    C, P, per = 3, 600, (4096, 4097, 200)
+    N = sum(per)
+    pi = np.sort(np.arange(N) % P)
+    ci = np.random.default_rng(5).permutation(np.repeat(np.arange(C), per))
+    return _problem(C, P, ci, pi, sfmba.make_problem(C, P, 4 * P, seed=9), orc, 3)
+
+
+def theta_sweep():
+    """The small-angle fixture of tests/golden/residual_cases.npz -> (args, x)."""
+    from conftest import GOLDEN
+    g = np.load(os.path.join(GOLDEN, "residual_cases.npz"))
+    tags = [str(g[f"c{k:02d}_tag"]) for k in range(int(g["n_cases"]))]
+    pre = f"c{tags.index('theta_sweep'):02d}_"
+    C, P, _ = (int(v) for v in g[pre + "dims"])
+    return (C, P, g[pre + "ci"], g[pre + "pi"], g[pre + "uv"], g[pre + "K"]), g[pre + "x"]
+
+
+def lds_limit(doubles_per_camera):
+    """Largest camera count whose table of that many doubles per camera fits the dynamic LDS: kLdsDynMax of sfmba.hip, the
+    160 KiB of a workgroup less the 2 KiB the kernels' static arrays may take."""
+    src = open(os.path.join(ROOT, "sfm-python_amd", "csrc", "sfmba.hip")).read()
+    total = re.search(r"kLdsBytes = (\d+) \* (\d+);", src)
+    static = re.search(r"kLdsDynMax = kLdsBytes - (\d+);", src)
+    return (int(total.group(1)) * int(total.group(2)) - int(static.group(1))) // (8 * doubles_per_camera)
+
+
+def operands(lin, st, seed=0):
+    """dc, dp and v of a case, from the longdouble blocks alone: diagonals of the size of the blocks' own (V + diag dp is
+    then well conditioned for a point with one observation too, U + diag dc - sd for a camera with few)."""
+    b = lin.blocks(st, deep=True)
+    rng = np.random.default_rng(seed)
+    dp = np.asarray(np.einsum("pii->pi", b["V"]) + 1.0, dtype=np.float64).ravel() * rng.uniform(0.5, 2.0, size=3 * lin.P)
+    dc = np.asarray(0.1 * np.einsum("cii->ci", b["U"]) + 1e-3, dtype=np.float64).ravel() * rng.uniform(0.5, 2.0, size=6 * lin.C)
+    return dc, dp, rng.normal(size=6 * lin.C)
+
+
+_CACHE = {}
+
+
+def problem(name, orc):
+    """The named problem (built once per process) -> (args, x)."""
+    if name not in _CACHE:
+        import sfmba
+        if name == "hand_built":
+            pb = hand_built(orc)
+        elif name == "chunk_edge":
+            pb = chunk_edge(orc)
+        elif name == "theta_sweep":
+            _CACHE[name] = theta_sweep()
+            return _CACHE[name]
+        elif name.startswith("k1_"):
+            pb = sfmba.make_problem(int(name[3:]), 300, 3000, seed=int(name[3:]))
+        elif name.startswith("schur_"):
+            pb = sfmba.make_problem(int(name[6:]), 500, 8000, seed=int(name[6:]))
+        elif name.startswith("dense_"):
+            pb = sfmba.make_problem(int(name[6:]), 300, 2000, seed=int(name[6:]))
+        else:
+            raise KeyError(name)
+        _CACHE[name] = (pb.args, pb.x0)
+    return _CACHE[name]
+
+
+def linearisation(name, orc):
+    if ("lin", name) not in _CACHE:
+        args, x = problem(name, orc)
+        _CACHE["lin", name] = Linearisation(*args, x)
+    return _CACHE["lin", name]
+
+
+def structure(name, orc, options):
+    args, _ = problem(name, orc)
+    key = ("st", name, tuple(sorted(options.items())))
+    if key not in _CACHE:
+        _CACHE[key] = Structure(args[0], args[1], np.asarray(args[2]), np.asarray(args[3]), options)
+    return _CACHE[key]
+
+
+# name -> (problem, debug options, forms that form() must report)
+K1_CASES = {
+    "hand_built": ("hand_built", {}, {"lds_tab": 1}),
+    "theta_sweep": ("theta_sweep", {}, {"lds_tab": 1}),
+    "tab_lds0": ("hand_built", {"tab_lds": 0}, {"lds_tab": 0}),
+    "last_lds_table": ("k1_%d" % lds_limit(kernel_constant("kCamRow")), {}, {"lds_tab": 1}),
+    "first_l2_table": ("k1_%d" % (lds_limit(kernel_constant("kCamRow")) + 1), {}, {"lds_tab": 0}),
+}
+BLOCK_CASES = {
+    "default": ("hand_built", {}, {}),
+    "cam_chunk64": ("hand_built", {"cam_chunk": 64}, {}),
+    "xcd": ("hand_built", {"xcd_chunks": 1}, {}),
+    "chunk_edge": ("chunk_edge", {}, {}),
+}
+RHS_CASES = {
+    "default": ("hand_built", {}, {}),
+    "cam_chunk64": ("hand_built", {"cam_chunk": 64}, {}),
+    "rhsrec": ("hand_built", {"rhsrec": 1}, {}),
+    "xcd": ("hand_built", {"xcd_chunks": 1}, {}),
+    "xcd_pass_b_only": ("hand_built", {"xcd_chunks": 1, "xcd_cam": 0}, {}),
+}
+_VEC = lds_limit(6)
+SCHUR_CASES = {      # (..., pass A's form for the bound)
+    "sweep_rc": ("hand_built", {}, {"sweep_rc": 1, "sweep_rc_g": 0, "pcg_fused": 1}, "rc"),
+    "sweep_rc_g": ("hand_built", {"sweep_rc": 2}, {"sweep_rc": 0, "sweep_rc_g": 1}, "rc"),
+    "stored_lds_vec": ("hand_built", {"sweep_rc": 0}, {"sweep_rc": 0, "sweep_rc_g": 0, "lds_vec": 1}, "stored"),
+    "stored_l2_vec": ("hand_built", {"sweep_rc": 0, "vec_lds": 0}, {"sweep_rc": 0, "sweep_rc_g": 0, "lds_vec": 0}, "stored"),
+    "cam_chunk64": ("hand_built", {"cam_chunk": 64}, {"sweep_rc": 1}, "rc"),
+    "xcd": ("hand_built", {"xcd_chunks": 1}, {"sweep_rc": 1}, "rc"),
+    "fused_1024": ("schur_1024", {}, {"pcg_fused": 1, "sweep_rc": 1}, "rc"),
+    "unfused_1025": ("schur_1025", {}, {"pcg_fused": 0, "sweep_rc": 1}, "rc"),
+    "lds_table_1100": ("schur_%d" % kernel_constant("kRcMaxCams"), {}, {"sweep_rc": 1, "sweep_rc_g": 0}, "rc"),
+    "l2_table_1101": ("schur_%d" % (kernel_constant("kRcMaxCams") + 1), {}, {"sweep_rc": 0, "sweep_rc_g": 1}, "rc"),
+    "last_lds_vec": ("schur_%d" % _VEC, {"sweep_rc": 0}, {"sweep_rc": 0, "sweep_rc_g": 0, "lds_vec": 1}, "stored"),
+    "first_l2_vec": ("schur_%d" % (_VEC + 1), {"sweep_rc": 0}, {"sweep_rc": 0, "sweep_rc_g": 0, "lds_vec": 0}, "stored"),
+}
+DENSE_CAMERAS = kernel_constant("kDenseMaxN") // 6            # 21: the last camera count of the dense path
+
+# the conditions that keep the bounds honest: share of the entries whose bound lies below LEVEL |reference|
+SHARE = 0.99
+LEVEL, LEVEL_Y = 1e-9, 1e-8
+# The inverse preconditioner blocks: measured with the references alone on the hand-built problem, 97.7 % of the non-zero
+# entries of the packed triangles have their bound below 1e-9 |entry| (the others are entries of a block inverse that
+# cancel to a thousandth of their terms); asserted as at least SHARE_MINV.
+SHARE_MINV = 0.97

@@ -9,10 +9,9 @@ import math
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from entry_bounds import CHOL_ROUNDINGS, EPS, LD, T1_ROUNDINGS, T_ROUNDINGS, _cross_abs, _inv3, _row_form_abs, _run_roundings  # noqa: F401
 
-LD = np.longdouble
-EPS = float(np.finfo(np.float64).eps)
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -37,64 +36,7 @@ def orc():
 #   sums: products 2, then one addition per window of the lane's range, 6 (wave_sum), 16 (waves of the workgroup), and the
 #       workgroups' partial rows
 # k is TWICE the count: the reference is formed from the fetched blocks, which carry K1's roundings of the same paths.
-T_ROUNDINGS = {0: 7, 1: 18}
-T1_ROUNDINGS = {0: 10, 1: 19}
-CHOL_ROUNDINGS = 15
-
-
-def _run_roundings(L):
-    return np.maximum(7, np.ceil(L / 64.0) + 6)
-
-
-def _cross_abs(a, b):
-    """|a x b| evaluated with absolute values: what bounds the rounding error of the cross product."""
-    return np.stack([a[:, 1] * b[:, 2] + a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] + a[:, 0] * b[:, 2],
-                     a[:, 0] * b[:, 1] + a[:, 1] * b[:, 0]], axis=1)
-
-
-def _row_form_abs(pb, x, u):
-    """The row form's expressions for j (N, 2, 3) and t = Jc u (N, 2) evaluated with every operand replaced by its absolute
-    value (and 1 / p_z by |1 / p_z| (sum |terms of p_z|) / |p_z|): gamma_n times this bounds the rounding error of n roundings."""
-    C, ci, pi = pb.n_cameras, np.asarray(pb.camera_indices), np.asarray(pb.point_indices)
-    K = np.abs(np.asarray(pb.K, dtype=LD))
-    cam, X = x[:6 * C].reshape(C, 6).astype(LD), x[6 * C:].reshape(-1, 3).astype(LD)
-    w, T = cam[:, :3], cam[:, 3:]
-    th2 = np.einsum("ci,ci->c", w, w)
-    th = np.sqrt(th2)
-    small = th < 1e-6
-    ths = np.where(small, 1.0, th)
-    a = np.where(small, 1.0, np.sin(ths) / ths)
-    b = np.where(small, 0.5, (1 - np.cos(ths)) / ths ** 2)
-    cc = np.where(small, 1.0 / 6, (ths - np.sin(ths)) / ths ** 3)
-    W = np.zeros((C, 3, 3), dtype=LD)
-    W[:, 0, 1], W[:, 0, 2], W[:, 1, 0], W[:, 1, 2], W[:, 2, 0], W[:, 2, 1] = -w[:, 2], w[:, 1], w[:, 2], -w[:, 0], -w[:, 1], w[:, 0]
-    R = np.eye(3, dtype=LD)[None] + a[:, None, None] * W + b[:, None, None] * np.einsum("cij,cjk->cik", W, W)
-    Ra = np.abs(R)[ci]
-    v, va = X[pi] - T[ci], np.abs(X[pi]) + np.abs(T[ci])
-    pz = np.einsum("nij,nj->ni", R[ci], v) @ np.asarray(pb.K, dtype=LD).T[:, 2]
-    pa = np.einsum("nij,nj->ni", Ra, va) @ K.T
-    iza = pa[:, 2] / pz ** 2
-    ja = np.empty((len(ci), 2, 3), dtype=LD)
-    for k in range(2):
-        pka = pa[:, k] * iza
-        ba = (K[k][None, :] + pka[:, None] * K[2][None, :]) * iza[:, None]
-        ja[:, k, :] = np.einsum("nm,nmi->ni", ba, Ra)
-    uw, uT, wa = np.abs(u[:, :3].astype(LD)), np.abs(u[:, 3:].astype(LD)), np.abs(w)
-    ca = _cross_abs(wa, uw)
-    aa = uw + np.abs(b)[:, None] * ca + np.abs(cc)[:, None] * _cross_abs(wa, ca)
-    ga = _cross_abs(va, aa[ci]) + uT[ci]
-    return ja, np.einsum("nki,ni->nk", ja, ga)
-
-
-def _inv3(A):
-    """(P, 3, 3) symmetric -> inverses, by cofactors in the arrays' own precision (numpy.linalg has no longdouble)."""
-    c = np.empty_like(A)
-    for i in range(3):
-        for j in range(3):
-            r, s = [k for k in range(3) if k != i], [k for k in range(3) if k != j]
-            c[:, j, i] = (-1) ** (i + j) * (A[:, r[0], s[0]] * A[:, r[1], s[1]] - A[:, r[0], s[1]] * A[:, r[1], s[0]])
-    det = np.einsum("pi,pi->p", A[:, 0, :], c[:, :, 0])
-    return c / det[:, None, None]
+# (the constants, _run_roundings, _row_form_abs, _cross_abs and _inv3 live in tests/entry_bounds.py, shared with test_gpu_entries.py)
 
 
 class _Case:
