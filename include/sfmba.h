@@ -191,7 +191,8 @@ int  sfmba_get_counters(const sfmba_handle* h, int64_t* kernel_launches, int64_t
  * camera has several chunks: k_cam_combine runs), "xcd_b" (pass B over the XCD-aware table), "rhsrec" (the rhs pass
  * gathers the 128-byte records), "round_blocks"; and of the solve stage, as the next compute call decides it from the
  * transport and the options of that moment: "xcd_cam" (K3 and the rhs pass one wave per chunk), "own_inverse" (the rhs
- * pass inverts its camera's preconditioner block itself). */
+ * pass inverts its camera's preconditioner block itself).  "match_form" belongs to the descriptor set, not to the
+ * problem (sfmba_set_descriptors): 1 = form A, 2 = form B. */
 int  sfmba_get_form(sfmba_handle* h, const char* name, int32_t* value);
 /* PCG iterations of every outer iteration of the last completed sfmba_solve on this handle (the record the next
  * solve's speculative launches are sized from); returns the number of outer iterations, writes min(that, cap)
@@ -451,6 +452,62 @@ int  sfmba_recover_pose(sfmba_handle* h, int64_t n_edges, const int64_t* edge_pt
                         const sfmba_pose_options* opt, double* R, double* t, uint8_t* front_mask, double* X, double* angle_deg,
                         int32_t* edge_front, int32_t* edge_front_all, double* edge_sum_err, int32_t* edge_status,
                         int64_t* n_ok, double* kernel_us);
+
+/* ---- descriptor matching: 2 nearest neighbours and the ratio test for a batch of image pairs (sfm.py:94-96) -------- */
+/* What produces the pixel pairs of the two-view calls: for every ordered pair of images the reference runs
+ * BFMatcher(NORM_L2).knnMatch(desc_u, desc_v, k=2) and Lowe's test m.distance < 0.5 * n.distance.  Here a set of images'
+ * descriptors is put on the device once (sfmba_set_descriptors) and any number of batches of (query image, train image)
+ * edges are matched against it (sfmba_match_descriptors, one launch of k_match per batch).  Neither call needs
+ * sfmba_set_problem; both use buffers of their own, so fun, grad, the PCG record and a following solve are exactly what
+ * a fresh handle gives.  No atomics: same input, same bits.
+ *
+ * sfmba_set_descriptors: n_images images; image i owns rows img_ptr[i] .. img_ptr[i+1] - 1 of desc, (N, dim) row-major,
+ * uint8 (dtype 0) or float32 (dtype 1), 1 <= dim <= 512.  The set takes one of two forms, reported in form_out and by
+ * sfmba_get_form(h, "match_form", ..):
+ *   1, form A  every value is an integer in 0..255 and dim <= 256 (what cv2.SIFT emits): uint8 input of that width
+ *              always, float32 input when a pass over it on the device finds it so.  Stored as fp16; the dot products
+ *              are fp16 MFMAs with fp32 accumulation, in which every product and partial sum is an integer below 2^24;
+ *              d^2 = |a|^2 + |b|^2 - 2 a.b is formed in integers.  Distances are the exact integers.
+ *   2, form B  anything else.  Stored as fp32; dot products are fp32 MFMAs (an fp32 fma chain over k), norms and
+ *              |a|^2 + |b|^2 - 2 a.b are fp64, the top two are kept by that value; the two winners' distances are then
+ *              recomputed as sum (a - b)^2 in fp64 over the fp32 values, and these decide their order, the ratio test and
+ *              dist_sq.  A pair of candidates whose true distances differ by less than 4 dim 2^-24 |a| max|b| may come
+ *              out in the other order or lose the second place to the third.
+ * The buffers of a set are freed by the next sfmba_set_descriptors and by sfmba_destroy.
+ *
+ * sfmba_match_descriptors: edges (n_edges, 2) int32: query image u, train image v (u == v is allowed: every row's
+ * nearest neighbour is then itself at distance 0).  The outputs are per query row, the edges' query images one after
+ * another: query_ptr (n_edges + 1) with Q = query_ptr[n_edges] = the sum of the rows of the edges' query images.
+ *   order       the candidates of a query are ordered by (d^2, train index) lexicographically: the lower index wins an
+ *               exact tie.  A result depends neither on the tiles, the grid, nor the batch its edge is part of.
+ *   idx (Q,2)   the nearest and the second nearest train row (index within the train image); dist_sq (Q,2) their d^2
+ *   good (Q)    d1^2 < ratio^2 d2^2, strictly, in fp64, ratio^2 = ratio * ratio in fp64 (default ratio 0.5, sfm.py's).
+ *               For integer descriptors this is cv2's test on the float32 roots as long as correctly rounded float32
+ *               roots of distinct integers stay distinct (d^2 < 2^22 by our derivation; not verified against OpenCV).
+ *   too few     a train image with fewer than 2 rows or a query image with none: edge_status 1 (FEW), every idx -1,
+ *               dist_sq +inf, good 0 (the reference's `for m, n in matches` raises there); else edge_status 0
+ *   non-finite  a train row whose distance to the query is not finite is never a neighbour; a query left with fewer than
+ *               two neighbours gets idx -1 and dist_sq +inf for the missing ones and good 0
+ *   edge_good   the number of good queries of the edge;  n_ok: edges with status 0;  kernel_us: with profile = 1 the
+ *               HIP-event time of the launch, else 0.
+ * form: 0 the set's own form; 1 form A, -1 when the set does not qualify; 2 form B whatever the values (built from the
+ * set at the first such call); on integer data both forms give the same idx, dist_sq and good.
+ * Every output pointer may be NULL, and an array that is not asked for is not downloaded.  opt = NULL: the defaults.
+ * Returns -1 for a malformed img_ptr (not ascending from 0), an image id out of range, dim outside 1..512, a NaN or
+ * non-positive ratio, or a call made before sfmba_set_descriptors. */
+int  sfmba_set_descriptors(sfmba_handle* h, int64_t n_images, const int64_t* img_ptr /* n_images + 1, ascending from 0 */,
+                           const void* desc /* (N, dim) row-major */, int32_t dtype /* 0 uint8, 1 float32 */,
+                           int32_t dim /* 1..512 */, int32_t* form_out);
+typedef struct sfmba_match_options {
+    double  ratio;       /* Lowe's ratio (0.5) */
+    int32_t form;        /* 0 = the set's form, 1 = A, 2 = B (0) */
+    int32_t profile;     /* 1 = kernel_us is measured (0) */
+} sfmba_match_options;
+void sfmba_default_match_options(sfmba_match_options* opt);
+int  sfmba_match_descriptors(sfmba_handle* h, int64_t n_edges, const int32_t* edges /* (n_edges,2): query image, train image */,
+                             const sfmba_match_options* opt, int64_t* query_ptr /* n_edges + 1 */, int32_t* idx /* (Q,2) */,
+                             double* dist_sq /* (Q,2) */, uint8_t* good /* Q */, int32_t* edge_good, int32_t* edge_status,
+                             int64_t* n_ok, double* kernel_us);
 
 /* ---- least_squares(method='trf', x_scale='jac') (sfm.py:266-268) ---------------------------- */
 /* x_inout: x0 on entry, result.x on success (untouched on failure). */

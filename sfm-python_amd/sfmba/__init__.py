@@ -6,10 +6,11 @@ Public surface mirrors /root/reference/sfm_lite/bundle_adjustment.py and the sci
 from .api import (TERMINATION_MESSAGES, apply_bundle_adjustment, compute_residuals,
                   create_sparsity_matrix, get_backend, least_squares, pack_cameras_points,
                   project_points, unpack_cameras_points)
-from .backend import (Backend, BackendError, FundamentalEstimate, RelativePose, ReprojectionStats, Resection,
+from .backend import (Backend, BackendError, DescriptorMatches, FundamentalEstimate, RelativePose, ReprojectionStats, Resection,
                       Triangulation)
 from .bal import read_bal, write_bal
-from .extras import (FM_RANSAC, calc_reproj_error, find_fundamental_mat, load_calibration_data, load_problem,
+from .extras import (FM_RANSAC, DMatch, calc_reproj_error, find_fundamental_mat, knn_match, load_calibration_data,
+                     load_problem, match_descriptors, match_features,
                      prune_problem, recover_pose, refine_reconstruction, reproj_error, reprojection_stats, resect_cameras,
                      save_problem, select_initial_pair, solve_pnp, total_mean_reproj_error, triangulate_points,
                      triangulate_tracks)
@@ -25,4 +26,5 @@ __all__ = ["TERMINATION_MESSAGES", "apply_bundle_adjustment", "compute_residuals
            "ReprojectionStats", "reprojection_stats", "total_mean_reproj_error", "prune_problem", "refine_reconstruction",
            "Triangulation", "triangulate_tracks", "triangulate_points",
            "Resection", "resect_cameras", "solve_pnp",
-           "FundamentalEstimate", "RelativePose", "FM_RANSAC", "find_fundamental_mat", "recover_pose", "select_initial_pair"]
+           "FundamentalEstimate", "RelativePose", "FM_RANSAC", "find_fundamental_mat", "recover_pose", "select_initial_pair",
+           "DescriptorMatches", "DMatch", "knn_match", "match_descriptors", "match_features"]

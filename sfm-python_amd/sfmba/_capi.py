@@ -25,6 +25,7 @@ SYMBOLS = (
     "sfmba_default_triangulate_options", "sfmba_triangulate",
     "sfmba_default_resect_options", "sfmba_resect",
     "sfmba_default_ransac_options", "sfmba_fundamental_ransac", "sfmba_default_pose_options", "sfmba_recover_pose",
+    "sfmba_set_descriptors", "sfmba_default_match_options", "sfmba_match_descriptors",
 )
 
 
@@ -72,6 +73,10 @@ class RansacOptions(C.Structure):
 
 class PoseOptions(C.Structure):
     _fields_ = [("min_depth", C.c_double), ("profile", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MatchOptions(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("form", C.c_int32), ("profile", C.c_int32)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -179,6 +184,14 @@ def load():
         lib.sfmba_recover_pose.argtypes = ([P, C.c_int64] + [P] * 6 + [C.POINTER(PoseOptions)] + [P] * 9 +
                                            [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
         lib.sfmba_recover_pose.restype = C.c_int
+    if hasattr(lib, "sfmba_match_descriptors"):      # (likewise)
+        lib.sfmba_set_descriptors.argtypes = [P, C.c_int64, P, P, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+        lib.sfmba_set_descriptors.restype = C.c_int
+        lib.sfmba_default_match_options.argtypes = [C.POINTER(MatchOptions)]
+        lib.sfmba_default_match_options.restype = None
+        lib.sfmba_match_descriptors.argtypes = ([P, C.c_int64, P, C.POINTER(MatchOptions)] + [P] * 6 +
+                                                [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
+        lib.sfmba_match_descriptors.restype = C.c_int
     lib.sfmba_tr2d_solve.argtypes = [P, P, C.c_double, P]
     lib.sfmba_comm_get_unique_id.argtypes = [P]
     lib.sfmba_comm_init.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int64]

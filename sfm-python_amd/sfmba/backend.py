@@ -55,6 +55,83 @@ class RelativePose:
         return f"RelativePose(n_edges={len(self.status)}, n_ok={self.n_ok})"
 
 
+class DescriptorMatches:
+    """What `Backend.match_descriptors` returns (include/sfmba.h: sfmba_match_descriptors).  Per query row, the edges'
+    query images one after another (edge e owns ``query_ptr[e]:query_ptr[e + 1]``): ``idx`` (Q, 2) int32 the nearest and
+    second nearest train row (-1: none), ``dist_sq`` (Q, 2) their squared L2 distances (+inf: none), ``good`` (Q, bool)
+    Lowe's ratio test.  Per edge: ``edge_good`` the number of good queries, ``edge_status`` (``OK`` or ``FEW``: a train
+    image with fewer than two rows or an empty query image).  ``edges`` (E, 2) the batch; ``n_ok``; ``kernel_us``
+    (``profile=1``, else 0)."""
+
+    OK, FEW = 0, 1
+
+    def __init__(self, edges, query_ptr, idx, dist_sq, good, edge_good, edge_status, n_ok, kernel_us):
+        self.edges, self.query_ptr, self.idx, self.dist_sq, self.good = edges, query_ptr, idx, dist_sq, good
+        self.edge_good, self.edge_status, self.n_ok, self.kernel_us = edge_good, edge_status, int(n_ok), float(kernel_us)
+
+    def pairs(self, e):
+        """(k, 2) int array of (query index, train index) of the good queries of edge ``e`` in ascending query order:
+        the reference's ``good_pairs`` (sfm.py:96)."""
+        b, n = int(self.query_ptr[e]), int(self.query_ptr[e + 1])
+        q = np.flatnonzero(self.good[b:n])
+        return np.stack([q, self.idx[b:n, 0][q]], axis=1).astype(int)
+
+    def __repr__(self):
+        return f"DescriptorMatches(n_edges={len(self.edge_status)}, n_ok={self.n_ok})"
+
+
+def check_descriptors(descs):
+    """A list of (n_i, D) descriptor arrays, checked -> (desc (N, D) uint8 or float32, img_ptr (n + 1) int64).  All uint8:
+    kept as uint8; otherwise everything is converted to float32."""
+    if isinstance(descs, np.ndarray) and descs.ndim == 2:
+        raise ValueError("descs must be a list of (n_i, D) arrays, one per image, not one array")
+    arrs = [np.asarray(d) for d in descs]
+    for k, a in enumerate(arrs):
+        if a.ndim != 2:
+            raise ValueError(f"descriptors of image {k} must be (n, D), got shape {a.shape}")
+        if not (np.issubdtype(a.dtype, np.number) or a.dtype == np.bool_) or np.issubdtype(a.dtype, np.complexfloating):
+            raise ValueError(f"descriptors of image {k} have dtype {a.dtype}")
+    if not arrs:
+        return np.empty((0, 1), dtype=np.uint8), np.zeros(1, dtype=np.int64)
+    D = arrs[0].shape[1]
+    if any(a.shape[1] != D for a in arrs):
+        raise ValueError(f"all images must have the same descriptor length, got {sorted({a.shape[1] for a in arrs})}")
+    if not 1 <= D <= 512:
+        raise ValueError(f"descriptor length must be 1..512, got {D}")
+    dt = np.uint8 if all(a.dtype == np.uint8 for a in arrs) else np.float32
+    desc = np.ascontiguousarray(np.concatenate([a.astype(dt, copy=False) for a in arrs], axis=0))
+    ptr = np.concatenate([[0], np.cumsum([len(a) for a in arrs])]).astype(np.int64)
+    return desc, ptr
+
+
+def check_match_edges(edges, n_images):
+    """(E, 2) int32 of (query image, train image), checked against the number of images; None: all pairs u > v in the
+    order of the reference's ``product(nodes, repeat=2)`` (sfm.py:90)."""
+    if edges is None:
+        edges = [(u, v) for u in range(n_images) for v in range(n_images) if u > v]
+    e = np.asarray(edges)
+    if e.size == 0:
+        return np.empty((0, 2), dtype=np.int32)
+    if e.ndim == 1 and e.shape[0] == 2:
+        e = e[None]
+    if e.ndim != 2 or e.shape[1] != 2:
+        raise ValueError(f"edges must be (E, 2), got {e.shape}")
+    if not np.issubdtype(e.dtype, np.integer):
+        raise ValueError(f"edges must be integers, got {e.dtype}")
+    if e.min() < 0 or e.max() >= n_images:
+        raise ValueError(f"edges name image {int(e.max() if e.max() >= n_images else e.min())}, the set has {n_images}")
+    return np.ascontiguousarray(e, dtype=np.int32)
+
+
+def check_match_options(ratio=0.5, form=0, profile=0):
+    ratio = float(ratio)
+    if not ratio > 0.0:
+        raise ValueError(f"ratio must be positive, got {ratio}")
+    if form not in (0, 1, 2):
+        raise ValueError(f"form must be 0 (auto), 1 (A) or 2 (B), got {form!r}")
+    return ratio, int(form), int(bool(profile))
+
+
 def _edge_batch(pts1, pts2, edge_ptr, pair_use):
     """The arrays of a batch of edges, checked: pts1, pts2 (M, 2) float64, edge_ptr (E + 1) int64 ascending from 0 to M
     (None: one edge), the mask (M) uint8 or None."""
@@ -556,6 +633,41 @@ class Backend:
             C.byref(opt), _capi.ptr(R), _capi.ptr(t), _capi.ptr(mask), _capi.ptr(X), _capi.ptr(ang), _capi.ptr(front),
             _capi.ptr(front_all), _capi.ptr(err), _capi.ptr(status), C.byref(n_ok), C.byref(us)))
         return RelativePose(R, t, mask.view(np.bool_), X, ang, front, front_all, err, status, n_ok.value, us.value, edge_ptr)
+
+    def set_descriptors(self, descs):
+        """Put the descriptors of a set of images on the device: a list of (n_i, D) arrays, uint8 or anything that
+        converts to float32 (include/sfmba.h: sfmba_set_descriptors).  -> the form the set takes, 1 (A: integers 0..255,
+        exact) or 2 (B: general float32).  Needs no problem and leaves a set problem as it is."""
+        desc, ptr = check_descriptors(descs)
+        self._flush_pending()
+        form = C.c_int32()
+        self._check(self._lib.sfmba_set_descriptors(self._h, len(ptr) - 1, _capi.ptr(ptr), _capi.ptr(desc),
+                                                    0 if desc.dtype == np.uint8 else 1, desc.shape[1], C.byref(form)))
+        self.n_images, self._desc_rows = len(ptr) - 1, np.diff(ptr)
+        return int(form.value)
+
+    def match_descriptors(self, edges=None, ratio=0.5, form=0, profile=0):
+        """The two nearest train descriptors of every query descriptor and Lowe's ratio test for a batch of ``edges``
+        (E, 2) of (query image, train image) of the current set; None = all pairs u > v (include/sfmba.h:
+        sfmba_match_descriptors).  -> :class:`DescriptorMatches`."""
+        if getattr(self, "n_images", None) is None:
+            raise ValueError("call set_descriptors first")
+        edges = check_match_edges(edges, self.n_images)
+        opt = _capi.MatchOptions()
+        self._lib.sfmba_default_match_options(C.byref(opt))
+        opt.ratio, opt.form, opt.profile = check_match_options(ratio, form, profile)
+        self._flush_pending()
+        E = edges.shape[0]
+        Q = int(self._desc_rows[edges[:, 0]].sum()) if E else 0
+        qptr = np.empty(E + 1, dtype=np.int64)
+        idx, dist = np.empty((Q, 2), dtype=np.int32), np.empty((Q, 2))
+        good = np.empty(Q, dtype=np.uint8)
+        egood, status = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
+        n_ok, us = C.c_int64(), C.c_double()
+        self._check(self._lib.sfmba_match_descriptors(
+            self._h, E, _capi.ptr(edges), C.byref(opt), _capi.ptr(qptr), _capi.ptr(idx), _capi.ptr(dist), _capi.ptr(good),
+            _capi.ptr(egood), _capi.ptr(status), C.byref(n_ok), C.byref(us)))
+        return DescriptorMatches(edges, qptr, idx, dist, good.view(np.bool_), egood, status, n_ok.value, us.value)
 
     def residual_jacobian(self, x):
         self._flush_pending()

@@ -5,6 +5,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import api
+from .backend import check_descriptors, check_match_edges, check_match_options
 
 
 def reproj_error(point3ds, point2ds, K, R, tvec, device=0):
@@ -318,6 +319,91 @@ def select_initial_pair(edges, K, min_angle=3, max_angle=60, device=0, backend=N
     sl = slice(int(ptr[best]), int(ptr[best + 1]))
     X = np.where(pose.front_mask[sl, None], pose.X[sl], np.nan)
     return best, pose.R[best].copy(), pose.t[best].copy(), X, pose.front_mask[sl].copy()
+
+
+class DMatch:
+    """One neighbour of ``knn_match``: the fields of cv2.DMatch that the reference reads (sfm.py:96), ``distance`` the
+    float32 root of the squared distance."""
+    __slots__ = ("queryIdx", "trainIdx", "distance", "imgIdx")
+
+    def __init__(self, queryIdx, trainIdx, distance):
+        self.queryIdx, self.trainIdx, self.distance, self.imgIdx = int(queryIdx), int(trainIdx), float(distance), 0
+
+    def __repr__(self):
+        return f"DMatch(queryIdx={self.queryIdx}, trainIdx={self.trainIdx}, distance={self.distance})"
+
+
+def dmatch_lists(idx, dist_sq):
+    """idx (n, 2), dist_sq (n, 2) of one edge -> what ``knnMatch(.., k=2)`` returns: per query the list of its neighbours
+    that exist, nearest first."""
+    root = np.sqrt(np.asarray(dist_sq, dtype=np.float64)).astype(np.float32)
+    return [[DMatch(q, int(idx[q, k]), root[q, k]) for k in range(2) if idx[q, k] >= 0] for q in range(len(idx))]
+
+
+def knn_match(query, train, k=2, device=0, backend=None):
+    """The drop-in for ``cv2.BFMatcher(cv2.NORM_L2).knnMatch(query, train, k=2)`` (sfm.py:94): a list with, per query
+    descriptor, the list of its two nearest train descriptors as :class:`DMatch`.  A train set with fewer than two rows
+    gives empty lists."""
+    if k != 2:
+        raise ValueError("only k=2 is implemented")
+    check_descriptors([query, train])
+    be = backend if backend is not None else api.get_backend(device)
+    be.set_descriptors([query, train])
+    m = be.match_descriptors([(0, 1)])
+    return dmatch_lists(m.idx, m.dist_sq)
+
+
+def match_descriptors(descs, edges=None, ratio=0.5, form=0, profile=0, device=0, backend=None):
+    """Lines 94-96 of ``SFM._match_features`` for a whole graph in one device call: ``descs`` a list of (n_i, D) arrays,
+    ``edges`` (E, 2) of (query image, train image), None = all pairs u > v as the reference.  -> :class:`DescriptorMatches`;
+    ``.pairs(e)`` is the reference's ``good_pairs`` of edge e."""
+    _, ptr = check_descriptors(descs)
+    check_match_edges(edges, len(ptr) - 1)
+    check_match_options(ratio, form, profile)
+    be = backend if backend is not None else api.get_backend(device)
+    be.set_descriptors(descs)
+    return be.match_descriptors(edges, ratio=ratio, form=form, profile=profile)
+
+
+def match_features(descs, pts, K, min_matches=80, ratio=0.5, device=0, backend=None, **ransac_options):
+    """The whole of ``SFM._match_features`` (sfm.py:88-107) in two device calls: every pair u > v matched with the ratio
+    test, edges with at most 8 good pairs dropped, one :func:`Backend.fundamental_ransac` batch (``refit=1``) over the
+    rest, edges with more than ``min_matches`` inliers kept.  ``descs``: list of (n_i, D); ``pts``: list of (n_i, 2) pixel
+    positions of the same rows; the RANSAC defaults are those of :func:`find_fundamental_mat`.
+    -> list of ``(u, v, inlier_pairs (k, 2) of (row in u, row in v), F, E = K^T F K)``."""
+    _, ptr = check_descriptors(descs)
+    rows = np.diff(ptr)
+    pts = [np.asarray(p, dtype=np.float64) for p in pts]
+    if len(pts) != len(rows):
+        raise ValueError(f"{len(rows)} images have descriptors, {len(pts)} have pixels")
+    for k, p in enumerate(pts):
+        if p.shape != (rows[k], 2):
+            raise ValueError(f"pixels of image {k} must be ({rows[k]}, 2), got {p.shape}")
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError("K must be (3, 3)")
+    check_match_options(ratio)
+    be = backend if backend is not None else api.get_backend(device)
+    be.set_descriptors(descs)
+    m = be.match_descriptors(None, ratio=ratio)
+    cand = [(e, m.pairs(e)) for e in range(len(m.edges))]
+    cand = [(e, gp) for e, gp in cand if len(gp) > 8]
+    if not cand:
+        return []
+    p1 = [pts[m.edges[e, 0]][gp[:, 0]] for e, gp in cand]
+    p2 = [pts[m.edges[e, 1]][gp[:, 1]] for e, gp in cand]
+    eptr = np.concatenate([[0], np.cumsum([len(gp) for _, gp in cand])]).astype(np.int64)
+    opts = dict(threshold=3.0, confidence=0.99, max_iters=1000, seed=0, refit=1)
+    opts.update(ransac_options)
+    est = be.fundamental_ransac(np.concatenate(p1), np.concatenate(p2), edge_ptr=eptr, **opts)
+    out = []
+    for k, (e, gp) in enumerate(cand):
+        mask = est.inlier_mask[int(eptr[k]):int(eptr[k + 1])]
+        if est.status[k] != est.OK or int(mask.sum()) <= min_matches:
+            continue
+        F = est.F_refit[k].copy()
+        out.append((int(m.edges[e, 0]), int(m.edges[e, 1]), gp[mask], F, K.T @ F @ K))
+    return out
 
 
 def load_calibration_data(txt_path):
