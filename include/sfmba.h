@@ -366,6 +366,91 @@ int  sfmba_resect(sfmba_handle* h, const double* x, const uint8_t* cam_select /*
                   double* cam_out /* (C,6): omega, centre T, the BA model's parameters */, int32_t* cam_status,
                   int32_t* cam_views, int32_t* cam_iters, double* cam_rms_err, int64_t* n_ok);
 
+/* ---- robust resection: P3P inside RANSAC, then pose refinement over the inliers --------------------------------------- */
+/* sfmba_resect takes every used observation of a camera, so one wrong 2-D--3-D correspondence moves its DLT pose
+ * arbitrarily far.  This call is cv2.solvePnPRansac for every selected camera of the current problem at once: H = max_iters
+ * hypotheses per camera from three observations each (a minimal P3P solver), scored over all used observations, then
+ * sfmba_resect's refinement (start = 1) over the inliers of the best one.  No local optimisation inside the loop, no
+ * adaptive exit, and the mask is not recomputed after the refinement.
+ *
+ * A camera's "used observations" are numbered 0 .. n-1 in camera-major stored order (as in sfmba_resect); a masked call
+ * gives bit for bit what the problem without those observations gives.
+ *   samples     given: (C, H, 3) int32 positions among a camera's used observations; a position outside 0 .. n-1 (of a
+ *               selected camera with enough views) makes the call return -1, a sample with a repeated position is invalid:
+ *               its count is -1.  NULL: drawn by the counter-based rule of sfmba_fundamental_ransac with three draws,
+ *                 key = mix(seed ^ mix(c << 32 | h)), c the camera's index in the problem (not its rank among the selected)
+ *                 draw j = 0, 1, 2: k = mix(key + (j + 1) 0x9e3779b97f4a7c15) mod (n - j); then, for every earlier choice
+ *                 in ascending order, if (k >= choice) ++k
+ *   hypothesis  Grunert's P3P.  Unit rays j_i = K^-1 (u_i, v_i, 1) normalised; ca = j2.j3, cb = j1.j3, cg = j1.j2;
+ *               a2 = |P2 - P3|^2, b2 = |P1 - P3|^2, c2 = |P1 - P2|^2, p = (a2 - c2) / b2, q = (a2 + c2) / b2.  The quartic
+ *               in v = s3 / s1 (s_i the depth along ray i):
+ *                 A4 = (p - 1)^2 - 4 (c2 / b2) ca^2
+ *                 A3 = 4 [p (1 - p) cb - (1 - q) ca cg + 2 (c2 / b2) ca^2 cb]
+ *                 A2 = 2 [p^2 - 1 + 2 p^2 cb^2 + 2 ((b2 - c2) / b2) ca^2 - 4 q ca cb cg + 2 ((b2 - a2) / b2) cg^2]
+ *                 A1 = 4 [-p (1 + p) cb + 2 (a2 / b2) cg^2 cb - (1 - q) ca cg]
+ *                 A0 = (1 + p)^2 - 4 (a2 / b2) cg^2
+ *               Real roots in closed form: divided by A4 and depressed (v = y - b / 4), the largest real root z of the
+ *               resolvent cubic z^3 + 2 p' z^2 + (p'^2 - 4 r') z - q'^2 (Cardano for one real root, the trigonometric form
+ *               for three), the quadratics y^2 + s y + (p' + z - q' / s) / 2 and y^2 - s y + (p' + z + q' / s) / 2 with
+ *               s = sqrt z, then two Newton steps on the quartic; the roots in ascending order of v.
+ *               u = [(p - 1) v^2 - 2 p cb v + 1 + p] / (2 (cg - v ca)); a root counts when v > 0, u > 0 and everything is
+ *               finite.  s1 = sqrt(b2 / (1 + v^2 - 2 v cb)), s2 = u s1, s3 = v s1, Q_i = s_i j_i.  The pose aligns the two
+ *               triangles: frames e1 = (A2 - A1) / |.|, e3 = e1 x (A3 - A1) normalised, e2 = e3 x e1 for A = Q and A = P,
+ *               R = E_Q E_P^T, T = P1 - R^T Q1 -- the bundle-adjustment model x_cam = R (X - T).  At most four solutions,
+ *               numbered in ascending v; a repeated 3-D point, or a triple with |e1 x (P3 - P1)| <= 1e-9 |P3 - P1| (collinear),
+ *               has none.
+ *   score       of a solution: the used observations with |pi(K R (X - T)) - uv|^2 STRICTLY below threshold^2 and depth
+ *               > min_depth; a non-finite value is no inlier.  Of a hypothesis: the largest over its solutions, the lowest
+ *               solution among equals; 0 when it has no solution, -1 for an invalid sample.
+ *   best        the largest count, the lowest h among equals.  The mask is that of the best solution, evaluated once more,
+ *               and cam_inliers is counted FROM that mask: mask, count and the refinement's input agree by construction.
+ *   refinement  sfmba_resect's (k_resect, start = 1) from the best pose over the inliers, for every camera whose best
+ *               hypothesis has a finite solution and at least max(min_views, 4) inliers; max_iter, xtol, max_rms_px as
+ *               there.  refine = 0: no trial pose (k_resect gives the verdict and the rms error at the best pose itself).
+ *   verdict     first match wins (cam_status):
+ *                  -1 the camera was not selected
+ *                   1 FEW_VIEWS   fewer used observations than max(min_views, 4)
+ *                   2 DEGENERATE  no hypothesis with a finite solution and at least max(min_views, 4) inliers
+ *                   3 BEHIND / 4 HIGH_ERROR  k_resect's verdict over the inliers (also 2 for anything non-finite there)
+ *                   0 OK          otherwise
+ * cam_out (C,6): the refined pose (refine = 0: the best hypothesis' pose) for status 0, the camera of x otherwise.
+ * cam_hyp (C,6): the best hypothesis' pose (rotation vector, centre), unrefined, wherever it has a finite solution --
+ * DEGENERATE for want of inliers still reports it, with the count, h, solution and mask --, else the camera of x.
+ * inlier_mask (N, the caller's order): 0 for observations that took no part.  cam_views: used observations of a selected
+ * camera (else 0).  cam_best: h of the best hypothesis, -1 when no sample was valid (or there was no hypothesis);
+ * cam_best_sol: its solution, -1 when it has none.  cam_success: inliers / n >= confidence.  cam_iters, cam_rms_err:
+ * k_resect's, over the inliers, for every camera that reached it; else 0, NaN.  hyp_inliers (C,H): the count of every
+ * hypothesis (-1: invalid sample, not selected or FEW_VIEWS).  n_ok: cameras with status 0.  kernel_us: with profile = 1
+ * the HIP-event time of the call's launches, else 0.
+ *
+ * cam_select, obs_use, NULL outputs, opt = NULL and the return value -1 as for sfmba_resect, and also -1 for max_iters < 1.
+ * Pixels are read as stored (fp64 or fp32).  Every buffer is the call's own, sfmba_resect's or the statistics call's, so
+ * fun, grad, the PCG record and a following solve are exactly what a fresh handle gives; no atomics, sums in a fixed order:
+ * same input, same bits. */
+typedef struct sfmba_pnp_ransac_options {
+    double   threshold;   /* pixels (default 8.0, cv2.solvePnPRansac's) */
+    double   confidence;  /* cam_success = inliers / n >= confidence (0.99); there is no adaptive exit */
+    double   min_depth;   /* an inlier has depth above this (0.0) */
+    uint64_t seed;        /* of the drawn samples (0) */
+    int32_t  max_iters;   /* hypotheses per camera, H, at least 1 (256) */
+    int32_t  min_views;   /* used observations a camera needs, and inliers its best hypothesis needs; below 4 counts as 4 (6) */
+    int32_t  refine;      /* 1 = Gauss-Newton over the inliers from the best hypothesis' pose (1) */
+    int32_t  profile;     /* 1 = kernel_us is measured (0) */
+    int32_t  max_iter;    /* the refinement's trial poses, as sfmba_resect's max_iter (default 20) */
+    int32_t  reserved;
+    double   xtol;        /* as sfmba_resect's xtol (default 1e-10) */
+    double   max_rms_px;  /* as sfmba_resect's max_rms_px, over the inliers (default +inf) */
+} sfmba_pnp_ransac_options;
+void sfmba_default_pnp_ransac_options(sfmba_pnp_ransac_options* opt);
+int  sfmba_resect_ransac(sfmba_handle* h, const double* x, const uint8_t* cam_select /* C or NULL = all */,
+                         const uint8_t* obs_use /* N, caller's order, or NULL = all */,
+                         const int32_t* samples /* (C,H,3) or NULL = drawn */, const sfmba_pnp_ransac_options* opt,
+                         double* cam_out /* (C,6) */, double* cam_hyp /* (C,6) best hypothesis, unrefined */,
+                         uint8_t* inlier_mask /* N, caller's order */, int32_t* cam_status, int32_t* cam_views,
+                         int32_t* cam_inliers, int32_t* cam_best /* h */, int32_t* cam_best_sol, uint8_t* cam_success,
+                         int32_t* cam_iters, double* cam_rms_err /* over the inliers */, int32_t* hyp_inliers /* (C,H) */,
+                         int64_t* n_ok, double* kernel_us);
+
 /* ---- two-view geometry: F by RANSAC and pose recovery for a batch of edges (sfm.py:88-107, 120-180) -------------- */
 /* A batch of edges (image pairs) that is independent of the bundle-adjustment problem: neither call needs
  * sfmba_set_problem, both ignore sfmba_set_precision (pairs are always fp64) and any transport, and both use buffers of
@@ -529,6 +614,7 @@ int  sfmba_get_fun_grad(sfmba_handle* h, double* fun_out, double* grad_out);
  *        13 the per-observation sweep and 14 the per-point reduction of sfmba_reprojection_stats (default options),
  *        15 k_triangulate of sfmba_triangulate over every point and observation (default options),
  *        16 k_resect of sfmba_resect over every camera and observation (default options).
+ *        17 k_pnp_ransac + k_pnp_finish of sfmba_resect_ransac over every camera and observation (default options).
  * avg_us: average duration of one repetition. */
 int  sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t reps, double* avg_us);
 /* Normal-equation blocks at x: U (C,21 upper triangle row-major), V (P,6 upper), gc (C,6), gp (P,3). */

@@ -1825,4 +1825,466 @@ __global__ __launch_bounds__(kTwoViewThreads) void k_recover_pose(const double* 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Robust resection (sfmba_resect_ransac): P3P inside RANSAC per selected camera, over its used
+// observations in camera-major stored order, then k_resect (start = 1) over the inliers.
+//   k_pnp_gather   one workgroup per camera walks its slice of the permutation as k_resect does and compacts the used
+//                  observations by ballot prefix, in stored order, into packed correspondences X Y Z u v (40 bytes) with
+//                  their stored positions (the others' positions behind them) and their number; it also clears the
+//                  camera's part of the inlier mask.  No later kernel of the RANSAC chases entry -> stored position ->
+//                  point index -> point again, and k_resect walks the compacted positions as its permutation.
+//   k_pnp_ransac   grid over (camera, slice of hypotheses).  Every LANE draws and solves one hypothesis (Grunert's P3P:
+//                  the quartic in v = s3 / s1 by Ferrari through the largest root of the resolvent cubic, two Newton
+//                  steps, the pose by aligning the two triangles) and leaves its up to four poses in the wave's LDS slab;
+//                  the WAVE then scores them one after the other, the lanes striding the camera's correspondences
+//                  (staged in LDS up to kPnpLdsObs of them), counts by ballot / popcount.  A workgroup leaves the best
+//                  (count, h, solution, pose) of its slice in a slot of its own.
+//   k_pnp_finish   one workgroup per camera: best slot (largest count, lowest h), the mask of that pose in stored order
+//                  and the count FROM that mask, the pose as six parameters into the camera's row of the call's x, the
+//                  byte that selects the camera for k_resect, the integers.
+// No atomics: counts do not depend on the order, and the only sums are k_resect's, in its fixed order.
+// ---------------------------------------------------------------------------------------------
+constexpr int kPnpThreads = 256;
+constexpr int kPnpWaves = 4;
+constexpr int kPnpLdsObs = 1024;     // a camera of up to this many used observations is staged in LDS (40 KiB)
+constexpr int kPnpMinSlice = 64;     // fewest hypotheses of a workgroup's slice (one per lane of one wave)
+constexpr int kPnpSlot = 16;         // doubles of a slot: count, h, solution, R (9), T (3), unused
+constexpr int kPnpCorr = 5;          // doubles of a packed correspondence
+constexpr int kPnpPose = 12;         // R (9, row-major), T (3): x_cam = R (X - T)
+constexpr int kPnpSlabDoubles = 4 * kPnpPose * 64;               // a wave's slab: [solution][entry][lane]
+constexpr int kPnpOk = 0, kPnpFewViews = 1, kPnpDegenerate = 2, kPnpNotSelected = -1;
+
+// the counter-based sample rule of twoview_draw with three draws: a function of (seed, c, h) alone
+__device__ __forceinline__ void pnp_draw(unsigned long long seed, unsigned c, unsigned h, int n, int (&idx)[3]) {
+    const unsigned long long key = twoview_mix(seed ^ twoview_mix(((unsigned long long)c << 32) | (unsigned long long)h));
+    int k0 = (int)(twoview_mix(key + 0x9e3779b97f4a7c15ull) % (unsigned long long)n);
+    int k1 = (int)(twoview_mix(key + 2ull * 0x9e3779b97f4a7c15ull) % (unsigned long long)(n - 1));
+    if (k1 >= k0) ++k1;
+    const int lo = min(k0, k1), hi = max(k0, k1);
+    int k2 = (int)(twoview_mix(key + 3ull * 0x9e3779b97f4a7c15ull) % (unsigned long long)(n - 2));
+    if (k2 >= lo) ++k2;
+    if (k2 >= hi) ++k2;
+    idx[0] = k0; idx[1] = k1; idx[2] = k2;
+}
+
+__device__ __forceinline__ void pnp_order(double& a, double& b) {
+    if (a > b) { const double t = a; a = b; b = t; }
+}
+// unit vectors e1 = (A2 - A1) / |.|, e3 = e1 x (A3 - A1) normalised, e2 = e3 x e1, as E[3 k + i] = (e_k)_i; -> the sine of
+// the angle at A1 (a collinear triple: zero but for rounding)
+constexpr double kPnpCollinear = 1e-9;
+__device__ __forceinline__ double pnp_frame(const double* A1, const double* A2, const double* A3, double (&E)[9]) {
+    const double dx = A2[0] - A1[0], dy = A2[1] - A1[1], dz = A2[2] - A1[2];
+    const double n1 = sqrt(dx * dx + dy * dy + dz * dz);
+    E[0] = dx / n1; E[1] = dy / n1; E[2] = dz / n1;
+    const double fx = A3[0] - A1[0], fy = A3[1] - A1[1], fz = A3[2] - A1[2];
+    const double cx = E[1] * fz - E[2] * fy, cy = E[2] * fx - E[0] * fz, cz = E[0] * fy - E[1] * fx;
+    const double n3 = sqrt(cx * cx + cy * cy + cz * cz);
+    E[6] = cx / n3; E[7] = cy / n3; E[8] = cz / n3;
+    E[3] = E[7] * E[2] - E[8] * E[1]; E[4] = E[8] * E[0] - E[6] * E[2]; E[5] = E[6] * E[1] - E[7] * E[0];
+    return n3 / sqrt(fx * fx + fy * fy + fz * fz);
+}
+
+// Grunert's P3P by one lane: Pw the three points, px their pixels.  The solutions (at most four, ascending in v) go to
+// the wave's slab in dynamic LDS, smem[slab + (kPnpPose s + k) 64 + lane]; -> their number.  Anything non-finite is no
+// solution.  (LDS is addressed through smem and offsets: a pointer into it that reaches this code as a generic one
+// costs a null test per access.)
+__device__ __forceinline__ int pnp_p3p(const double (&Pw)[9], const double (&px)[6], const KMat& Kinv, int slab, int lane) {
+    extern __shared__ __align__(16) double smem[];
+    double j[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double u = px[2 * i], v = px[2 * i + 1];
+        const double x = Kinv.k[0] * u + Kinv.k[1] * v + Kinv.k[2], y = Kinv.k[3] * u + Kinv.k[4] * v + Kinv.k[5],
+                     z = Kinv.k[6] * u + Kinv.k[7] * v + Kinv.k[8];
+        const double nn = sqrt(x * x + y * y + z * z);
+        j[3 * i] = x / nn; j[3 * i + 1] = y / nn; j[3 * i + 2] = z / nn;
+    }
+    const double ca = j[3] * j[6] + j[4] * j[7] + j[5] * j[8], cb = j[0] * j[6] + j[1] * j[7] + j[2] * j[8],
+                 cg = j[0] * j[3] + j[1] * j[4] + j[2] * j[5];
+    auto dist2 = [&](int a, int b) {
+        const double x = Pw[3 * a] - Pw[3 * b], y = Pw[3 * a + 1] - Pw[3 * b + 1], z = Pw[3 * a + 2] - Pw[3 * b + 2];
+        return x * x + y * y + z * z;
+    };
+    const double a2 = dist2(1, 2), b2 = dist2(0, 2), c2 = dist2(0, 1);
+    const double p = (a2 - c2) / b2, q = (a2 + c2) / b2;
+    const double A4 = (p - 1.0) * (p - 1.0) - 4.0 * (c2 / b2) * ca * ca;
+    const double A3 = 4.0 * (p * (1.0 - p) * cb - (1.0 - q) * ca * cg + 2.0 * (c2 / b2) * ca * ca * cb);
+    const double A2 = 2.0 * (p * p - 1.0 + 2.0 * p * p * cb * cb + 2.0 * ((b2 - c2) / b2) * ca * ca - 4.0 * q * ca * cb * cg +
+                             2.0 * ((b2 - a2) / b2) * cg * cg);
+    const double A1 = 4.0 * (-p * (1.0 + p) * cb + 2.0 * (a2 / b2) * cg * cg * cb - (1.0 - q) * ca * cg);
+    const double A0 = (1.0 + p) * (1.0 + p) - 4.0 * (a2 / b2) * cg * cg;
+    const double b = A3 / A4, c = A2 / A4, d = A1 / A4, e = A0 / A4;
+    if (!(fabs(b) + fabs(c) + fabs(d) + fabs(e) < INFINITY)) return 0;
+    // depressed quartic y^4 + dp y^2 + dq y + dr with v = y - b / 4
+    const double dp = c - 0.375 * b * b;
+    const double dq = d - 0.5 * b * c + 0.125 * b * b * b;
+    const double dr = e - 0.25 * b * d + 0.0625 * b * b * c - (3.0 / 256.0) * b * b * b * b;
+    // resolvent cubic z^3 + 2 dp z^2 + (dp^2 - 4 dr) z - dq^2: its largest real root
+    const double B = 2.0 * dp, Cc = dp * dp - 4.0 * dr, D = -dq * dq;
+    const double P3 = Cc - B * B / 3.0;
+    const double Q3 = 2.0 * B * B * B / 27.0 - B * Cc / 3.0 + D;
+    const double disc = 0.25 * Q3 * Q3 + P3 * P3 * P3 / 27.0;
+    double w;
+    if (disc > 0.0) {
+        const double sq = sqrt(disc);
+        w = cbrt(-0.5 * Q3 + sq) + cbrt(-0.5 * Q3 - sq);
+    } else {
+        const double m = sqrt(-P3 / 3.0);
+        double arg = m > 0.0 ? 3.0 * Q3 / (2.0 * P3 * m) : 0.0;
+        arg = fmin(1.0, fmax(-1.0, arg));
+        w = 2.0 * m * cos(acos(arg) / 3.0);
+    }
+    const double z = w - B / 3.0;
+    if (!(z > 0.0)) return 0;
+    const double s = sqrt(z), qs = dq / s;
+    const double t1 = 0.5 * (dp + z - qs), t2 = 0.5 * (dp + z + qs);
+    const double d1 = z - 4.0 * t1, d2 = z - 4.0 * t2;
+    double r0 = INFINITY, r1 = INFINITY, r2 = INFINITY, r3 = INFINITY;
+    if (d1 >= 0.0) { const double rt = sqrt(d1); r0 = 0.5 * (-s - rt) - 0.25 * b; r1 = 0.5 * (-s + rt) - 0.25 * b; }
+    if (d2 >= 0.0) { const double rt = sqrt(d2); r2 = 0.5 * (s - rt) - 0.25 * b; r3 = 0.5 * (s + rt) - 0.25 * b; }
+    auto newton = [&](double v) {
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const double f = (((v + b) * v + c) * v + d) * v + e;
+            const double fp = ((4.0 * v + 3.0 * b) * v + 2.0 * c) * v + d;
+            v = v - f / fp;
+        }
+        return fabs(v) < INFINITY ? v : INFINITY;                // (a NaN as well)
+    };
+    r0 = newton(r0); r1 = newton(r1); r2 = newton(r2); r3 = newton(r3);
+    pnp_order(r0, r1); pnp_order(r2, r3); pnp_order(r0, r2); pnp_order(r1, r3); pnp_order(r1, r2);
+    double EP[9];
+    if (!(pnp_frame(&Pw[0], &Pw[3], &Pw[6], EP) > kPnpCollinear)) return 0;      // (a repeated point: NaN)
+    int ns = 0;
+    auto solution = [&](double v) {
+        const double u = ((p - 1.0) * v * v - 2.0 * p * cb * v + 1.0 + p) / (2.0 * (cg - v * ca));
+        if (!(v > 0.0 && u > 0.0 && u < INFINITY && v < INFINITY)) return;
+        const double s1 = sqrt(b2 / (1.0 + v * v - 2.0 * v * cb)), s2 = u * s1, s3 = v * s1;
+        const double Q[9] = {s1 * j[0], s1 * j[1], s1 * j[2], s2 * j[3], s2 * j[4], s2 * j[5], s3 * j[6], s3 * j[7], s3 * j[8]};
+        double EQ[9], R[9];
+        pnp_frame(&Q[0], &Q[3], &Q[6], EQ);
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) R[3 * i + k] = EQ[i] * EP[k] + EQ[3 + i] * EP[3 + k] + EQ[6 + i] * EP[6 + k];
+        const double T0 = Pw[0] - (R[0] * Q[0] + R[3] * Q[1] + R[6] * Q[2]), T1 = Pw[1] - (R[1] * Q[0] + R[4] * Q[1] + R[7] * Q[2]),
+                     T2 = Pw[2] - (R[2] * Q[0] + R[5] * Q[1] + R[8] * Q[2]);
+        double sum = fabs(T0) + fabs(T1) + fabs(T2);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) sum += fabs(R[k]);
+        if (!(sum < INFINITY)) return;
+        const int dst = slab + kPnpPose * ns * 64 + lane;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) smem[dst + 64 * k] = R[k];
+        smem[dst + 64 * 9] = T0; smem[dst + 64 * 10] = T1; smem[dst + 64 * 11] = T2;
+        ++ns;
+    };
+#pragma unroll 1
+    for (int i = 0; i < 4; ++i) solution(i == 0 ? r0 : (i == 1 ? r1 : (i == 2 ? r2 : r3)));   // (selects: an indexed array would live in scratch)
+    return ns;
+}
+
+// |pi(K R (X - T)) - uv|^2 of one correspondence at the pose ps (R | T); depth: the third entry of R (X - T)
+__device__ __forceinline__ double pnp_err2(const double (&ps)[kPnpPose], const KMat& K, double X, double Y, double Z, double u,
+                                           double v, double& depth) {
+    const double vx = X - ps[9], vy = Y - ps[10], vz = Z - ps[11];
+    const double qx = ps[0] * vx + ps[1] * vy + ps[2] * vz, qy = ps[3] * vx + ps[4] * vy + ps[5] * vz,
+                 qz = ps[6] * vx + ps[7] * vy + ps[8] * vz;
+    const double pxx = K.k[0] * qx + K.k[1] * qy + K.k[2] * qz, pyy = K.k[3] * qx + K.k[4] * qy + K.k[5] * qz,
+                 pzz = K.k[6] * qx + K.k[7] * qy + K.k[8] * qz;
+    const double iz = 1.0 / pzz;
+    const double rx = pxx * iz - u, ry = pyy * iz - v;
+    depth = qz;
+    return rx * rx + ry * ry;
+}
+// the score's test: squared error STRICTLY below thr2 and depth above min_depth; a non-finite value is no inlier
+__device__ __forceinline__ bool pnp_inlier(const double (&ps)[kPnpPose], const KMat& K, const double* __restrict__ o, double thr2,
+                                           double min_depth) {
+    double depth;
+    const double e2 = pnp_err2(ps, K, o[0], o[1], o[2], o[3], o[4], depth);
+    return e2 < thr2 && e2 < INFINITY && depth > min_depth;
+}
+
+struct PnpIn {
+    const double* __restrict__ corr;             // [N][5] packed per camera from cam_ptr[c] on
+    const int* __restrict__ cam_ptr;             // [C + 1]
+    const int* __restrict__ cn;                  // [C] used observations (0: not selected)
+    const int* __restrict__ samples;             // [C][H][3] positions among the used observations, or null: drawn
+};
+struct PnpScore { double thr2, min_depth; int need; };
+
+// the hypotheses h0 + 64 w + lane, + 256, ... < h1 of camera c, one per lane; the camera's correspondences are staged
+// in LDS behind the slabs (LDS_OBS) or read at go.  Leaves the wave's best (count, h, solution, pose) on every lane.
+template <bool LDS_OBS>
+__device__ __forceinline__ void pnp_slice(const double* __restrict__ go, const PnpIn& in, int c, int n, int H, int h0, int h1,
+                                          unsigned long long seed, const KMat& K, const KMat& Kinv, const PnpScore& sc,
+                                          int* __restrict__ hyp, int& bc, int& bh, int& bs, double (&bp)[kPnpPose]) {
+    extern __shared__ __align__(16) double smem[];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int slab = w * kPnpSlabDoubles;
+    const auto obs = [&](int k, double (&o)[kPnpCorr]) {
+#pragma unroll
+        for (int i = 0; i < kPnpCorr; ++i) o[i] = LDS_OBS ? smem[kPnpWaves * kPnpSlabDoubles + kPnpCorr * k + i] : go[(size_t)kPnpCorr * k + i];
+    };
+    bc = -2; bh = 0x7fffffff; bs = -1;
+#pragma unroll
+    for (int k = 0; k < kPnpPose; ++k) bp[k] = 0.0;
+#pragma unroll 1
+    for (int hb = h0 + 64 * w; hb < h1; hb += 64 * kPnpWaves) {  // uniform over the wave
+        const int h = hb + lane;
+        int ns = 0, hcount = -1, hsol = -1;
+        if (h < h1) {
+            int idx[3];
+            bool valid = true;
+            if (in.samples != nullptr) {
+                const int* __restrict__ sp = in.samples + ((size_t)c * (size_t)H + (size_t)h) * 3;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { idx[k] = sp[k]; valid = valid && idx[k] >= 0 && idx[k] < n; }
+                valid = valid && idx[0] != idx[1] && idx[0] != idx[2] && idx[1] != idx[2];
+            } else {
+                pnp_draw(seed, (unsigned)c, (unsigned)h, n, idx);
+            }
+            if (valid) {
+                double Pw[9], px[6];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    double o[kPnpCorr];
+                    obs(idx[k], o);
+                    Pw[3 * k] = o[0]; Pw[3 * k + 1] = o[1]; Pw[3 * k + 2] = o[2]; px[2 * k] = o[3]; px[2 * k + 1] = o[4];
+                }
+                hcount = 0;
+                ns = pnp_p3p(Pw, px, Kinv, slab, lane);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();                         // (one wave: its LDS operations execute in program order)
+        for (unsigned long long todo = __ballot(ns > 0); todo; todo &= todo - 1) {
+            const int l = __ffsll((long long)todo) - 1;
+            const int nl = __builtin_amdgcn_readlane(ns, l);
+#pragma unroll 1
+            for (int s = 0; s < nl; ++s) {
+                double ps[kPnpPose];
+#pragma unroll
+                for (int k = 0; k < kPnpPose; ++k) ps[k] = smem[slab + (kPnpPose * s + k) * 64 + l];
+                int cnt = 0;
+#pragma unroll 1
+                for (int k0 = 0; k0 < n; k0 += 64) {             // uniform over the wave: the ballot needs every lane
+                    const int k = k0 + lane;
+                    bool inl = false;
+                    if (k < n) {
+                        double o[kPnpCorr];
+                        obs(k, o);
+                        inl = pnp_inlier(ps, K, o, sc.thr2, sc.min_depth);
+                    }
+                    cnt += __popcll(__ballot(inl));
+                }
+                if (lane == l && (hsol < 0 || cnt > hcount)) { hcount = cnt; hsol = s; }   // the lowest solution of equal counts
+            }
+        }
+        if (h < h1 && hyp != nullptr) hyp[(size_t)c * (size_t)H + (size_t)h] = hcount;
+        // the round's best: the largest count, the lowest lane (h) among equals; rounds ascend in h
+        const int top = wave_reduce_xor(h < h1 ? hcount : -2, [](int a, int b) { return max(a, b); });
+        if (top > bc) {
+            const int lb = __ffsll((long long)__ballot(h < h1 && hcount == top)) - 1;
+            bc = top; bh = hb + lb; bs = __builtin_amdgcn_readlane(hsol, lb);
+            if (bs >= 0) {
+#pragma unroll
+                for (int k = 0; k < kPnpPose; ++k) bp[k] = smem[slab + (kPnpPose * bs + k) * 64 + lb];
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// dynamic LDS: the four waves' slabs, then the camera's correspondences when they fit
+__global__ __launch_bounds__(kPnpThreads) void k_pnp_ransac(PnpIn in, int H, int hs, int n_slices, unsigned long long seed,
+                                                            KMat K, KMat Kinv, PnpScore sc, double* __restrict__ slots,
+                                                            int* __restrict__ hyp) {
+    extern __shared__ __align__(16) double smem[];
+    __shared__ double wbest[kPnpWaves][kPnpSlot];
+    const int c = blockIdx.x / n_slices, sl = blockIdx.x - c * n_slices;
+    const int b = in.cam_ptr[c], n = in.cn[c];
+    const int h0 = sl * hs, h1 = min(H, h0 + hs);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    double* __restrict__ slot = slots + (size_t)blockIdx.x * kPnpSlot;
+    if (n < sc.need) {                                           // (uniform over the workgroup) no hypothesis
+        if (hyp != nullptr)
+            for (int h = h0 + (int)threadIdx.x; h < h1; h += kPnpThreads) hyp[(size_t)c * (size_t)H + (size_t)h] = -1;
+        if (threadIdx.x < kPnpSlot) slot[threadIdx.x] = threadIdx.x == 0 ? -2.0 : (threadIdx.x == 2 ? -1.0 : 0.0);
+        return;
+    }
+    const double* __restrict__ go = in.corr + (size_t)kPnpCorr * (size_t)b;
+    int bc, bh, bs;
+    double bp[kPnpPose];
+    if (n <= kPnpLdsObs) {
+        for (int k = threadIdx.x; k < kPnpCorr * n; k += kPnpThreads) smem[kPnpWaves * kPnpSlabDoubles + k] = go[k];
+        __syncthreads();
+        pnp_slice<true>(go, in, c, n, H, h0, h1, seed, K, Kinv, sc, hyp, bc, bh, bs, bp);
+    } else {
+        pnp_slice<false>(go, in, c, n, H, h0, h1, seed, K, Kinv, sc, hyp, bc, bh, bs, bp);
+    }
+    if (lane == 0) {
+        wbest[w][0] = (double)bc; wbest[w][1] = (double)bh; wbest[w][2] = (double)bs;
+#pragma unroll
+        for (int k = 0; k < kPnpPose; ++k) wbest[w][3 + k] = bp[k];
+        wbest[w][15] = 0.0;
+    }
+    __syncthreads();
+    if (threadIdx.x < kPnpSlot) {
+        int best = 0;
+        for (int k = 1; k < kPnpWaves; ++k)
+            if (wbest[k][0] > wbest[best][0] || (wbest[k][0] == wbest[best][0] && wbest[k][1] < wbest[best][1])) best = k;
+        slot[threadIdx.x] = wbest[best][threadIdx.x];
+    }
+}
+
+template <bool F32>
+__global__ __launch_bounds__(kPnpThreads) void k_pnp_gather(ResectIn in, int C, double* __restrict__ corr, int* __restrict__ cpos,
+                                                            int* __restrict__ cn, unsigned char* __restrict__ mask) {
+    __shared__ int wcnt[2 * kPnpWaves];
+    const int c = blockIdx.x;
+    const int b = in.cam_ptr[c], e = in.cam_ptr[c + 1];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const double* __restrict__ pts = in.x + 6 * (size_t)C;
+    const bool sel = in.select == nullptr || in.select[c] != 0;
+    const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    int base = 0, rest = 0;
+#pragma unroll 1
+    for (int j0 = b; j0 < e; j0 += kPnpThreads) {                // uniform over the workgroup
+        const int j = j0 + (int)threadIdx.x;
+        const int idx = j < e ? in.perm[j] : -1;
+        const bool on = idx >= 0 && sel && (in.use == nullptr || in.use[idx] != 0);
+        const bool out = idx >= 0 && !on;
+        if (idx >= 0) mask[idx] = 0;
+        const unsigned long long m = __ballot(on), mo = __ballot(out);
+        if (lane == 0) { wcnt[w] = __popcll(m); wcnt[kPnpWaves + w] = __popcll(mo); }
+        __syncthreads();
+        int off = base + __popcll(m & below), tot = 0, offo = rest + __popcll(mo & below), toto = 0;
+#pragma unroll
+        for (int k = 0; k < kPnpWaves; ++k) {
+            off += k < w ? wcnt[k] : 0; tot += wcnt[k];
+            offo += k < w ? wcnt[kPnpWaves + k] : 0; toto += wcnt[kPnpWaves + k];
+        }
+        // the observations that take no part fill the slice from its end: their mask byte stays 0, so k_resect, walking
+        // cpos as its permutation, meets the used ones first and in stored order -- thread for thread what it meets in the
+        // problem without the others
+        if (out) cpos[e - 1 - offo] = idx;
+        rest += toto;
+        if (on) {
+            const int p = in.pt_idx[idx];
+            const double2 q = load_pair(in.uv, F32, idx);
+            const double* __restrict__ Xp = pts + 3 * (size_t)p;
+            double* __restrict__ dst = corr + (size_t)kPnpCorr * (size_t)(b + off);
+            dst[0] = Xp[0]; dst[1] = Xp[1]; dst[2] = Xp[2]; dst[3] = q.x; dst[4] = q.y;
+            cpos[b + off] = idx;
+        }
+        base += tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) cn[c] = base;
+}
+
+// the rotation vector of R through the quaternion, the largest component first (as resect_pose_from_h ends)
+__device__ __forceinline__ void pnp_rotvec(const double* R, double* w) {
+    const double tr = R[0] + R[4] + R[8];
+    double qw, qx, qy, qz;
+    if (tr > 0.0) {
+        const double s = sqrt(tr + 1.0) * 2.0;
+        qw = 0.25 * s; qx = (R[7] - R[5]) / s; qy = (R[2] - R[6]) / s; qz = (R[3] - R[1]) / s;
+    } else if (R[0] > R[4] && R[0] > R[8]) {
+        const double s = sqrt(1.0 + R[0] - R[4] - R[8]) * 2.0;
+        qw = (R[7] - R[5]) / s; qx = 0.25 * s; qy = (R[1] + R[3]) / s; qz = (R[2] + R[6]) / s;
+    } else if (R[4] > R[8]) {
+        const double s = sqrt(1.0 + R[4] - R[0] - R[8]) * 2.0;
+        qw = (R[2] - R[6]) / s; qx = (R[1] + R[3]) / s; qy = 0.25 * s; qz = (R[5] + R[7]) / s;
+    } else {
+        const double s = sqrt(1.0 + R[8] - R[0] - R[4]) * 2.0;
+        qw = (R[3] - R[1]) / s; qx = (R[2] + R[6]) / s; qy = (R[5] + R[7]) / s; qz = 0.25 * s;
+    }
+    if (qw < 0.0) { qw = -qw; qx = -qx; qy = -qy; qz = -qz; }
+    const double n = sqrt(qx * qx + qy * qy + qz * qz);
+    const double f = n < 1e-12 ? 2.0 : 2.0 * atan2(n, qw) / n;
+    w[0] = qx * f; w[1] = qy * f; w[2] = qz * f;
+}
+
+struct PnpOut {
+    double* __restrict__ x;                      // the call's parameter vector: the best pose goes into the camera's row
+    double* __restrict__ hyp;                    // [C][6]
+    unsigned char* __restrict__ mask;            // [N] stored order
+    unsigned char* __restrict__ ok;              // [C] k_resect's select mask: RANSAC succeeded
+    int* __restrict__ ints;                      // [C][6] status, views, inliers, best h, best solution, success
+};
+
+__global__ __launch_bounds__(kPnpThreads) void k_pnp_finish(PnpIn in, const int* __restrict__ cpos,
+                                                            const unsigned char* __restrict__ select, int n_slices, KMat K,
+                                                            PnpScore sc, double confidence, const double* __restrict__ slots,
+                                                            PnpOut out) {
+    __shared__ double red[kPnpWaves];
+    __shared__ double sp[kPnpPose];
+    __shared__ int ctl[3];
+    const int c = blockIdx.x;
+    const int b = in.cam_ptr[c], n = in.cn[c];
+    const bool first = threadIdx.x == 0;
+    const bool sel = select == nullptr || select[c] != 0;
+    int* __restrict__ oi = out.ints + 6 * (size_t)c;
+    if (!sel || n < sc.need) {                                   // (uniform over the workgroup; k_pnp_gather cleared the mask)
+        if (first) {
+            oi[0] = sel ? kPnpFewViews : kPnpNotSelected; oi[1] = n; oi[2] = 0; oi[3] = -1; oi[4] = -1; oi[5] = 0;
+            out.ok[c] = 0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) out.hyp[6 * (size_t)c + k] = out.x[6 * (size_t)c + k];
+        }
+        return;
+    }
+    if (first) {
+        const double* __restrict__ sl = slots + (size_t)c * (size_t)n_slices * kPnpSlot;
+        int best = 0;
+        for (int k = 1; k < n_slices; ++k)                       // slots ascend in h: the first of equal counts has the lowest
+            if (sl[(size_t)k * kPnpSlot] > sl[(size_t)best * kPnpSlot]) best = k;
+        const double* __restrict__ bs = sl + (size_t)best * kPnpSlot;
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < kPnpPose; ++k) { sp[k] = bs[3 + k]; sum += fabs(bs[3 + k]); }
+        const bool any = bs[0] >= 0.0;                           // (below: no valid sample in any slot)
+        ctl[0] = (any && bs[2] >= 0.0 && sum < INFINITY) ? 1 : 0;
+        ctl[1] = any ? (int)bs[1] : -1;
+        ctl[2] = any ? (int)bs[2] : -1;
+    }
+    __syncthreads();
+    const bool has = ctl[0] != 0;
+    double ps[kPnpPose];
+#pragma unroll
+    for (int k = 0; k < kPnpPose; ++k) ps[k] = sp[k];
+    // The mask of the best pose, and the count FROM that mask: cam_inliers, cam_success, the status and k_resect's input
+    // all rest on this one evaluation (the count in the slot came from another copy of the expression).
+    const double* __restrict__ go = in.corr + (size_t)kPnpCorr * (size_t)b;
+    double cs[1] = {0.0};
+    for (int k = threadIdx.x; k < n; k += kPnpThreads) {
+        const bool inl = has && pnp_inlier(ps, K, go + (size_t)kPnpCorr * k, sc.thr2, sc.min_depth);
+        out.mask[cpos[b + k]] = inl ? 1 : 0;
+        cs[0] += inl ? 1.0 : 0.0;
+    }
+    block_sum<1>(cs, red);
+    if (first) {
+        const int cnt = (int)cs[0];
+        const bool ok = has && cnt >= sc.need;
+        oi[0] = ok ? kPnpOk : kPnpDegenerate; oi[1] = n; oi[2] = cnt; oi[3] = ctl[1]; oi[4] = ctl[2];
+        oi[5] = (has && (double)cnt / (double)n >= confidence) ? 1 : 0;
+        out.ok[c] = ok ? 1 : 0;
+        double prm[6];
+        if (has) {
+            pnp_rotvec(ps, prm);
+            prm[3] = ps[9]; prm[4] = ps[10]; prm[5] = ps[11];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) prm[k] = out.x[6 * (size_t)c + k];
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            out.hyp[6 * (size_t)c + k] = prm[k];
+            if (ok) out.x[6 * (size_t)c + k] = prm[k];
+        }
+    }
+}
+
 }  // namespace sfmba

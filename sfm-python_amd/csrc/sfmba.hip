@@ -419,6 +419,15 @@ struct sfmba_handle {
         PinnedBuf in_host, out_host;         // staging of the packed batch; of the results
         std::vector<int64_t> pos;            // used pair -> stored pair, when the call has a pair_use mask
     } twoview;
+    // sfmba_resect_ransac: works on stats.x, the camera-major permutation of the statistics call and stats.use as
+    // sfmba_resect does, on sfmba_resect's result arrays (k_resect runs last) and on buffers of its own
+    struct Pnp {
+        DevBuf select, ok, mask;             // [C] the caller's select mask; [C] RANSAC succeeded; [ld] inlier mask, stored order
+        DevBuf corr, cpos, cn;               // [N][5] packed X Y Z u v per camera; [N] their stored positions; [C] their number
+        DevBuf samples, slots, hyp;          // [C][H][3]; [C][slices][kPnpSlot]; [C][H]
+        DevBuf pose, ints;                   // [C][6] best hypothesis; [C][6] status, views, inliers, best h, best solution, success
+        PinnedBuf host;                      // staging of the results
+    } pnp;
     // sfmba_set_descriptors / sfmba_match_descriptors: the descriptor set in the form(s) the kernels read and the
     // buffers of a batch of edges; nothing of it is shared with the problem
     struct Match {
@@ -2517,15 +2526,17 @@ KMat inverse_k(const KMat& K) {
     return inv;
 }
 
-// x must be in stats.x and the permutation of stats_cam_perm(h) in place; use / select: the masks are on the device
-int launch_resect(sfmba_handle* h, const ResectOptions& opt, bool use, bool select) {
+// x must be in stats.x and the permutation of stats_cam_perm(h) in place; use / select: the masks on the device ([ld]
+// stored order / [C]), null: every observation / camera; perm: another order of the entries inside the cameras' slices
+// (null: the permutation itself)
+int launch_resect(sfmba_handle* h, const ResectOptions& opt, const unsigned char* use, const unsigned char* select,
+                  const int* perm = nullptr) {
     auto& s = h->stats;
     auto& r = h->resect;
     const size_t C = (size_t)h->C;
     if (C == 0) return 0;
-    const ResectIn in{s.cam_ptr.as<int>(), s.perm.as<int>(), h->pt_idx.as<int>(), h->uv.as<double>(),
-                      use ? s.use.as<unsigned char>() : nullptr, select ? r.select.as<unsigned char>() : nullptr,
-                      s.x.as<double>()};
+    const ResectIn in{s.cam_ptr.as<int>(), perm ? perm : s.perm.as<int>(), h->pt_idx.as<int>(), h->uv.as<double>(),
+                      use, select, s.x.as<double>()};
     const ResectOut out{r.cam.as<double>(), r.ints.as<int>(), r.ints.as<int>() + C, r.ints.as<int>() + 2 * C,
                         r.rms.as<double>(), r.ints.as<int>() + 3 * C};
     auto kern = h->f32 ? k_resect<true> : k_resect<false>;
@@ -2549,7 +2560,7 @@ int resect_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* a
     CHK(resect_allocate(h));
     CHK(upload_x(h, x, h->stats.x.as<double>()));
     CHK(stats_cam_perm(h));
-    return time_reps(h, reps, avg_us, [&] { return launch_resect(h, opt, false, false); });
+    return time_reps(h, reps, avg_us, [&] { return launch_resect(h, opt, nullptr, nullptr); });
 }
 }  // namespace
 
@@ -2576,7 +2587,8 @@ int sfmba_resect(sfmba_handle* h, const double* x, const uint8_t* cam_select, co
     CHK(upload_x(h, x, h->stats.x.as<double>()));
     CHK(stats_cam_perm(h));
     CHK(stage_masks(h, obs_use, cam_select, C, r.select, C, &counts));
-    CHK(launch_resect(h, resect_options(o), obs_use != nullptr, cam_select != nullptr));
+    CHK(launch_resect(h, resect_options(o), obs_use ? h->stats.use.as<unsigned char>() : nullptr,
+                      cam_select ? r.select.as<unsigned char>() : nullptr));
     const int* pi = r.ints.as<int>();
     HIPCHK(h, download(h, cam_out, r.cam.p, sizeof(double) * 6 * C));
     HIPCHK(h, download(h, cam_status, pi, sizeof(int32_t) * C));
@@ -2676,6 +2688,193 @@ void twoview_slices(const sfmba_handle* h, size_t E, int H, int* hs, int* n_slic
     *n_slices = (H + *hs - 1) / *hs;
 }
 }  // namespace
+
+namespace {
+// ---- robust resection (sfmba_resect_ransac; kernels: consumer_kernels.hpp, "Robust resection") ----------------------------
+struct PnpCall { int H, hs, n_slices; PnpScore sc; double confidence; unsigned long long seed; };
+
+PnpCall pnp_call(const sfmba_handle* h, const sfmba_pnp_ransac_options& o) {
+    PnpCall pc{};
+    pc.H = (int)o.max_iters;
+    // the slices of a camera by the rule of twoview_slices: about two workgroups per CU over the batch, and no slice below
+    // kPnpMinSlice hypotheses (H / kPnpMinSlice slices at the most, rounded down)
+    const size_t want = (2 * (size_t)h->n_cu + (size_t)h->C - 1) / std::max<size_t>((size_t)h->C, 1);
+    const int sl = (int)std::min<size_t>(std::max<size_t>(want, 1), (size_t)std::max(pc.H / kPnpMinSlice, 1));
+    pc.hs = (pc.H + sl - 1) / sl;
+    pc.n_slices = (pc.H + pc.hs - 1) / pc.hs;
+    pc.sc = PnpScore{o.threshold * o.threshold, o.min_depth, std::max((int)o.min_views, 4)};
+    pc.confidence = o.confidence;
+    pc.seed = (unsigned long long)o.seed;
+    return pc;
+}
+
+int pnp_allocate(sfmba_handle* h, const PnpCall& pc, bool samples, bool hyp) {
+    auto& q = h->pnp;
+    const size_t ldz = (size_t)h->ld, C = (size_t)h->C, H = (size_t)pc.H;
+    if (C * (size_t)pc.n_slices >= (size_t)1 << 31) return fail(h, -1, "sfmba_resect_ransac: too many cameras for one launch");
+    CHK(resect_allocate(h));
+    return ensure_all(h, {
+        {&q.select, C}, {&q.ok, C}, {&q.mask, ldz}, {&q.corr, sizeof(double) * kPnpCorr * ldz}, {&q.cpos, sizeof(int) * ldz},
+        {&q.cn, sizeof(int) * C}, {&q.samples, samples ? sizeof(int) * 3 * C * H : 0},
+        {&q.slots, sizeof(double) * kPnpSlot * C * (size_t)pc.n_slices}, {&q.hyp, hyp ? sizeof(int) * C * H : 0},
+        {&q.pose, sizeof(double) * 6 * C}, {&q.ints, sizeof(int) * 6 * C}});
+}
+
+PnpIn pnp_in(sfmba_handle* h, bool samples) {
+    auto& q = h->pnp;
+    return PnpIn{q.corr.as<double>(), h->stats.cam_ptr.as<int>(), q.cn.as<int>(), samples ? q.samples.as<int>() : nullptr};
+}
+
+// x must be in stats.x and the permutation of stats_cam_perm(h) in place; use / select: the masks are on the device
+int launch_pnp_gather(sfmba_handle* h, bool use, bool select) {
+    auto& s = h->stats;
+    auto& q = h->pnp;
+    const ResectIn in{s.cam_ptr.as<int>(), s.perm.as<int>(), h->pt_idx.as<int>(), h->uv.as<double>(),
+                      use ? s.use.as<unsigned char>() : nullptr, select ? q.select.as<unsigned char>() : nullptr,
+                      s.x.as<double>()};
+    auto kern = h->f32 ? k_pnp_gather<true> : k_pnp_gather<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)h->C), dim3(kPnpThreads), 0, h->stream, in, (int)h->C, q.corr.as<double>(),
+                       q.cpos.as<int>(), q.cn.as<int>(), q.mask.as<unsigned char>());
+    LAUNCHED(h);
+    return 0;
+}
+
+// k_pnp_ransac and k_pnp_finish behind k_pnp_gather
+int launch_pnp_ransac(sfmba_handle* h, const PnpCall& pc, bool samples, bool hyp, bool select) {
+    auto& q = h->pnp;
+    const size_t C = (size_t)h->C;
+    constexpr size_t lds = sizeof(double) * ((size_t)kPnpWaves * kPnpSlabDoubles + (size_t)kPnpCorr * kPnpLdsObs);
+    static_assert(lds + 1024 <= 160 * 1024, "slabs and staged correspondences must fit the LDS of a CU");
+    {   // more than 64 KiB of LDS needs the opt-in, once per handle
+        const void* fn = reinterpret_cast<const void*>(k_pnp_ransac);
+        if (std::find(h->lds_ready.begin(), h->lds_ready.end(), fn) == h->lds_ready.end()) {
+            HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            h->lds_ready.push_back(fn);
+        }
+    }
+    const PnpIn in = pnp_in(h, samples);
+    hipLaunchKernelGGL(k_pnp_ransac, dim3((unsigned)(C * (size_t)pc.n_slices)), dim3(kPnpThreads), lds, h->stream, in, pc.H, pc.hs,
+                       pc.n_slices, pc.seed, h->K, inverse_k(h->K), pc.sc, q.slots.as<double>(), hyp ? q.hyp.as<int>() : nullptr);
+    LAUNCHED(h);
+    const PnpOut out{h->stats.x.as<double>(), q.pose.as<double>(), q.mask.as<unsigned char>(), q.ok.as<unsigned char>(),
+                     q.ints.as<int>()};
+    hipLaunchKernelGGL(k_pnp_finish, dim3((unsigned)C), dim3(kPnpThreads), 0, h->stream, in, (const int*)q.cpos.as<int>(),
+                       (const unsigned char*)(select ? q.select.as<unsigned char>() : nullptr), pc.n_slices, h->K, pc.sc,
+                       pc.confidence, (const double*)q.slots.as<double>(), out);
+    LAUNCHED(h);
+    return 0;
+}
+
+// sfmba_time_kernel, which = 17: k_pnp_ransac + k_pnp_finish at x over every camera and observation, default options
+int pnp_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us) {
+    sfmba_pnp_ransac_options o;
+    sfmba_default_pnp_ransac_options(&o);
+    CHK(resect_check_single(h));
+    if (h->C == 0) { *avg_us = 0.0; return 0; }
+    const PnpCall pc = pnp_call(h, o);
+    CHK(pnp_allocate(h, pc, false, false));
+    CHK(upload_x(h, x, h->stats.x.as<double>()));
+    CHK(stats_cam_perm(h));
+    CHK(launch_pnp_gather(h, false, false));
+    return time_reps(h, reps, avg_us, [&] { return launch_pnp_ransac(h, pc, false, false, false); });
+}
+}  // namespace
+
+void sfmba_default_pnp_ransac_options(sfmba_pnp_ransac_options* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->threshold = 8.0; o->confidence = 0.99; o->min_depth = 0.0; o->seed = 0; o->max_iters = 256; o->min_views = 6;
+    o->refine = 1; o->profile = 0; o->max_iter = 20; o->xtol = 1e-10; o->max_rms_px = INFINITY;
+}
+
+int sfmba_resect_ransac(sfmba_handle* h, const double* x, const uint8_t* cam_select, const uint8_t* obs_use, const int32_t* samples,
+                        const sfmba_pnp_ransac_options* opt, double* cam_out, double* cam_hyp, uint8_t* inlier_mask,
+                        int32_t* cam_status, int32_t* cam_views, int32_t* cam_inliers, int32_t* cam_best, int32_t* cam_best_sol,
+                        uint8_t* cam_success, int32_t* cam_iters, double* cam_rms_err, int32_t* hyp_inliers, int64_t* n_ok,
+                        double* kernel_us) {
+    CHK(enter(h));
+    CHK(begin_compute(h, x));
+    sfmba_pnp_ransac_options o;
+    if (opt) o = *opt; else sfmba_default_pnp_ransac_options(&o);
+    if (std::isnan(o.threshold) || std::isnan(o.confidence) || std::isnan(o.min_depth) || std::isnan(o.xtol) || std::isnan(o.max_rms_px))
+        return fail(h, -1, "an option of sfmba_resect_ransac is NaN");
+    if (o.max_iters < 1) return fail(h, -1, "sfmba_resect_ransac: max_iters must be at least 1");
+    CHK(resect_check_single(h));
+    if (n_ok) *n_ok = 0;
+    if (kernel_us) *kernel_us = 0.0;
+    auto& q = h->pnp;
+    auto& r = h->resect;
+    const size_t C = (size_t)h->C, N = (size_t)h->N;
+    if (C == 0) return wait_stream(h);
+    const PnpCall pc = pnp_call(h, o);
+    const size_t H = (size_t)pc.H;
+    int* counts = nullptr;
+    CHK(pnp_allocate(h, pc, samples != nullptr, hyp_inliers != nullptr));
+    CHK(upload_x(h, x, h->stats.x.as<double>()));
+    CHK(stats_cam_perm(h));
+    CHK(stage_masks(h, obs_use, cam_select, C, q.select, 0, &counts));
+    // the results' staging: doubles first (pose, k_resect's pose and rms), then the integers (ours, k_resect's), the mask
+    const size_t off_ints = sizeof(double) * 13 * C, off_mask = off_ints + sizeof(int) * 10 * C;
+    HIPCHK(h, q.host.ensure(off_mask + N + 64, 0));
+    double* const hd = q.host.as<double>();
+    int* const hi = reinterpret_cast<int*>(q.host.as<unsigned char>() + off_ints);
+    unsigned char* const hm = q.host.as<unsigned char>() + off_mask;
+    TwoViewTimer timer;
+    CHK(timer.start(h, o.profile != 0));
+    CHK(launch_pnp_gather(h, obs_use != nullptr, cam_select != nullptr));
+    if (samples) {                                               // positions are checked against the cameras' counts
+        HIPCHK(h, hipMemcpyAsync(hi, q.cn.p, sizeof(int) * C, hipMemcpyDeviceToHost, h->stream));
+        CHK(wait_stream(h));
+        for (size_t c = 0; c < C; ++c) {
+            const int n = hi[c];
+            if (n < pc.sc.need) continue;                        // (not selected or FEW_VIEWS: its samples are not read)
+            const int32_t* sp = samples + c * H * 3;
+            for (size_t k = 0; k < 3 * H; ++k)
+                if (sp[k] < 0 || sp[k] >= n)
+                    return fail(h, -1, "sfmba_resect_ransac: samples of camera %zu, hypothesis %zu: position %d is outside its %d used observations",
+                                c, k / 3, (int)sp[k], n);
+        }
+        HIPCHK(h, hipMemcpyAsync(q.samples.p, samples, sizeof(int) * 3 * C * H, hipMemcpyHostToDevice, h->stream));
+    }
+    CHK(launch_pnp_ransac(h, pc, samples != nullptr, hyp_inliers != nullptr, cam_select != nullptr));
+    // the verdict and (refine = 1) the refinement: k_resect from the pose in x over the inlier mask, for the cameras that
+    // succeeded -- both masks were written by k_pnp_finish
+    ResectOptions ro{o.refine != 0 ? (int)o.max_iter : 0, (int)o.min_views, 1, o.xtol, o.min_depth, o.max_rms_px};
+    // (over the compacted positions of k_pnp_gather: a masked call sums in the order of the problem without the masked)
+    CHK(launch_resect(h, ro, q.mask.as<unsigned char>(), q.ok.as<unsigned char>(), q.cpos.as<int>()));
+    CHK(timer.stop(h));
+    HIPCHK(h, hipMemcpyAsync(hd, q.pose.p, sizeof(double) * 6 * C, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(hd + 6 * C, r.cam.p, sizeof(double) * 6 * C, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(hd + 12 * C, r.rms.p, sizeof(double) * C, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(hi, q.ints.p, sizeof(int) * 6 * C, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(hi + 6 * C, r.ints.p, sizeof(int) * 4 * C, hipMemcpyDeviceToHost, h->stream));
+    if (inlier_mask && N) HIPCHK(h, hipMemcpyAsync(hm, q.mask.p, N, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, download(h, hyp_inliers, q.hyp.p, sizeof(int) * C * H));
+    CHK(wait_stream(h));
+    CHK(timer.read(h, kernel_us));
+    if (inlier_mask)
+        for (size_t k = 0; k < N; ++k) inlier_mask[h->permuted ? (size_t)h->tb.order[k] : k] = hm[k];
+    const int* const ri = hi + 6 * C;                            // k_resect's status, views, iters, ok
+    int64_t ok = 0;
+    for (size_t c = 0; c < C; ++c) {
+        const int* pi = hi + 6 * c;
+        const bool refined = pi[0] == kPnpOk;                    // RANSAC succeeded: k_resect's verdict counts
+        const int status = refined ? ri[c] : pi[0];
+        if (cam_status) cam_status[c] = status;
+        if (cam_views) cam_views[c] = pi[1];
+        if (cam_inliers) cam_inliers[c] = pi[2];
+        if (cam_best) cam_best[c] = pi[3];
+        if (cam_best_sol) cam_best_sol[c] = pi[4];
+        if (cam_success) cam_success[c] = (uint8_t)pi[5];
+        if (cam_iters) cam_iters[c] = refined ? ri[2 * C + c] : 0;
+        if (cam_rms_err) cam_rms_err[c] = refined ? hd[12 * C + c] : NAN;
+        if (cam_hyp) memcpy(cam_hyp + 6 * c, hd + 6 * c, sizeof(double) * 6);
+        if (cam_out) memcpy(cam_out + 6 * c, status == kResOk ? hd + 6 * C + 6 * c : x + 6 * c, sizeof(double) * 6);
+        ok += status == kResOk ? 1 : 0;
+    }
+    if (n_ok) *n_ok = ok;
+    return 0;
+}
 
 void sfmba_default_ransac_options(sfmba_ransac_options* o) {
     if (!o) return;
@@ -3306,6 +3505,7 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
     if (which == 13 || which == 14) return stats_time_kernel(h, x, which, reps, avg_us);
     if (which == 15) return tri_time_kernel(h, x, reps, avg_us);
     if (which == 16) return resect_time_kernel(h, x, reps, avg_us);
+    if (which == 17) return pnp_time_kernel(h, x, reps, avg_us);
     int np = 0;
     CHK(linearise_at(h, x, which >= 2));
     if (which >= 2) {

@@ -7,12 +7,12 @@ from .api import (TERMINATION_MESSAGES, apply_bundle_adjustment, compute_residua
                   create_sparsity_matrix, get_backend, least_squares, pack_cameras_points,
                   project_points, unpack_cameras_points)
 from .backend import (Backend, BackendError, DescriptorMatches, FundamentalEstimate, RelativePose, ReprojectionStats, Resection,
-                      Triangulation)
+                      RobustResection, Triangulation)
 from .bal import read_bal, write_bal
 from .extras import (FM_RANSAC, DMatch, calc_reproj_error, find_fundamental_mat, knn_match, load_calibration_data,
                      load_problem, match_descriptors, match_features,
                      prune_problem, recover_pose, refine_reconstruction, reproj_error, reprojection_stats, resect_cameras,
-                     save_problem, select_initial_pair, solve_pnp, total_mean_reproj_error, triangulate_points,
+                     resect_cameras_ransac, save_problem, select_initial_pair, solve_pnp, solve_pnp_ransac, total_mean_reproj_error, triangulate_points,
                      triangulate_tracks)
 from .synthetic import (BAProblem, K_SCEAUX, drop_observations, growing_reconstruction, make_config,
                         make_problem, make_ring_problem)
@@ -26,5 +26,6 @@ __all__ = ["TERMINATION_MESSAGES", "apply_bundle_adjustment", "compute_residuals
            "ReprojectionStats", "reprojection_stats", "total_mean_reproj_error", "prune_problem", "refine_reconstruction",
            "Triangulation", "triangulate_tracks", "triangulate_points",
            "Resection", "resect_cameras", "solve_pnp",
+           "RobustResection", "resect_cameras_ransac", "solve_pnp_ransac",
            "FundamentalEstimate", "RelativePose", "FM_RANSAC", "find_fundamental_mat", "recover_pose", "select_initial_pair",
            "DescriptorMatches", "DMatch", "knn_match", "match_descriptors", "match_features"]

@@ -24,6 +24,7 @@ SYMBOLS = (
     "sfmba_default_filter_options", "sfmba_reprojection_stats",
     "sfmba_default_triangulate_options", "sfmba_triangulate",
     "sfmba_default_resect_options", "sfmba_resect",
+    "sfmba_default_pnp_ransac_options", "sfmba_resect_ransac",
     "sfmba_default_ransac_options", "sfmba_fundamental_ransac", "sfmba_default_pose_options", "sfmba_recover_pose",
     "sfmba_set_descriptors", "sfmba_default_match_options", "sfmba_match_descriptors",
 )
@@ -64,6 +65,12 @@ class TriangulateOptions(C.Structure):
 class ResectOptions(C.Structure):
     _fields_ = [("max_iter", C.c_int32), ("min_views", C.c_int32), ("start", C.c_int32), ("xtol", C.c_double),
                 ("min_depth", C.c_double), ("max_rms_px", C.c_double)]
+
+
+class PnpRansacOptions(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("min_depth", C.c_double), ("seed", C.c_uint64),
+                ("max_iters", C.c_int32), ("min_views", C.c_int32), ("refine", C.c_int32), ("profile", C.c_int32),
+                ("max_iter", C.c_int32), ("reserved", C.c_int32), ("xtol", C.c_double), ("max_rms_px", C.c_double)]
 
 
 class RansacOptions(C.Structure):
@@ -173,6 +180,12 @@ def load():
         lib.sfmba_default_resect_options.restype = None
         lib.sfmba_resect.argtypes = [P, P, P, P, C.POINTER(ResectOptions)] + [P] * 5 + [C.POINTER(C.c_int64)]
         lib.sfmba_resect.restype = C.c_int
+    if hasattr(lib, "sfmba_resect_ransac"):          # (likewise)
+        lib.sfmba_default_pnp_ransac_options.argtypes = [C.POINTER(PnpRansacOptions)]
+        lib.sfmba_default_pnp_ransac_options.restype = None
+        lib.sfmba_resect_ransac.argtypes = ([P] * 5 + [C.POINTER(PnpRansacOptions)] + [P] * 12 +
+                                            [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
+        lib.sfmba_resect_ransac.restype = C.c_int
     if hasattr(lib, "sfmba_fundamental_ransac"):     # (likewise)
         lib.sfmba_default_ransac_options.argtypes = [C.POINTER(RansacOptions)]
         lib.sfmba_default_ransac_options.restype = None

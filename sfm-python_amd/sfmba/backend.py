@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 
 import weakref
 
@@ -262,6 +263,42 @@ class Resection:
 
     def __repr__(self):
         return f"Resection(n_cameras={len(self.status)}, n_ok={self.n_ok})"
+
+
+@dataclasses.dataclass
+class RobustResection:
+    """What `Backend.resect_ransac` returns (include/sfmba.h: sfmba_resect_ransac).  ``cameras`` (C, 6): the refined pose
+    (rotation vector, centre) where ``status`` is 0, else the camera of ``x``; ``hyp`` (C, 6): the best hypothesis' pose,
+    unrefined; ``inlier_mask`` (N, bool) in the caller's observation order; ``status`` (C) one of the ``NOT_SELECTED ..
+    HIGH_ERROR`` codes; ``views``, ``inliers``, ``best`` (the winning hypothesis), ``best_sol`` (its solution), ``iters``
+    (C, int32); ``success`` (C, bool): inliers / views >= confidence; ``rms_err`` (C) over the inliers, NaN where the
+    camera did not get that far; ``hyp_inliers`` (C, H) the count of every hypothesis, or None when not asked for;
+    ``n_ok``; ``kernel_us`` (``profile=1``, else 0)."""
+
+    NOT_SELECTED, OK, FEW_VIEWS, DEGENERATE, BEHIND, HIGH_ERROR = -1, 0, 1, 2, 3, 4
+
+    cameras: np.ndarray
+    hyp: np.ndarray
+    inlier_mask: np.ndarray
+    status: np.ndarray
+    views: np.ndarray
+    inliers: np.ndarray
+    best: np.ndarray
+    best_sol: np.ndarray
+    success: np.ndarray
+    iters: np.ndarray
+    rms_err: np.ndarray
+    hyp_inliers: object
+    n_ok: int
+    kernel_us: float
+
+    @property
+    def ok(self):
+        """Boolean mask of the cameras that came back with a new pose."""
+        return self.status == self.OK
+
+    def __repr__(self):
+        return f"RobustResection(n_cameras={len(self.status)}, n_ok={self.n_ok})"
 
 
 class Backend:
@@ -559,6 +596,54 @@ class Backend:
             _capi.ptr(use) if use is not None else None, C.byref(opt), _capi.ptr(cameras), _capi.ptr(status),
             _capi.ptr(views), _capi.ptr(iters), _capi.ptr(rms), C.byref(n_ok)))
         return Resection(cameras, status, views, iters, rms, n_ok.value)
+
+    def resect_ransac(self, x, select=None, obs_use=None, samples=None, want_hyp=False, **options):
+        """Resect the selected cameras of the current problem robustly: ``max_iters`` P3P hypotheses per camera from three
+        of its used observations each, scored over all of them, then the refinement of :meth:`resect` over the inliers
+        of the best (include/sfmba.h: sfmba_resect_ransac).  ``select`` (C) and ``obs_use`` (N, the caller's order):
+        boolean masks, None = all; ``samples`` (C, H, 3) int32 positions among a camera's used observations (camera-major
+        stored order), None = drawn on the device from ``seed``.  ``options``: fields of ``sfmba_pnp_ransac_options``
+        (threshold, confidence, min_depth, seed, max_iters, min_views, refine, profile, max_iter, xtol, max_rms_px); with
+        ``samples`` given, ``max_iters`` defaults to its H.  ``want_hyp``: also return the count of every hypothesis.
+        -> :class:`RobustResection`."""
+        self._flush_pending()
+        x = _f64(x, (self.n_params,), "x")
+        opt = _capi.PnpRansacOptions()
+        self._lib.sfmba_default_pnp_ransac_options(C.byref(opt))
+        options = dict(options)
+        if "seed" in options:
+            seed = int(options.pop("seed"))
+            if not 0 <= seed < 2 ** 64:
+                raise ValueError("seed must fit 64 unsigned bits")
+            opt.seed = seed
+        Cn, N = self.n_cameras, self.n_obs
+        if samples is not None:
+            samples = np.ascontiguousarray(samples, dtype=np.int32)
+            if samples.ndim == 2:
+                samples = samples[None]
+            if samples.ndim != 3 or samples.shape[0] != Cn or samples.shape[2] != 3 or samples.shape[1] < 1:
+                raise ValueError(f"samples must be (n_cameras, H, 3) with n_cameras = {Cn}, got {samples.shape}")
+            options.setdefault("max_iters", samples.shape[1])
+        _fill_options(opt, options, "robust resection")
+        if opt.max_iters < 1:
+            raise ValueError("max_iters must be at least 1")
+        if samples is not None and samples.shape[1] != opt.max_iters:
+            raise ValueError(f"samples holds {samples.shape[1]} hypotheses per camera, max_iters is {opt.max_iters}")
+        H = int(opt.max_iters)
+        sel, use = _mask(select, Cn, "select"), _mask(obs_use, N, "obs_use")
+        cameras, hyp_pose = np.empty((Cn, 6)), np.empty((Cn, 6))
+        mask = np.zeros(N, dtype=np.uint8)
+        status, views, inl, best, sol, iters = (np.empty(Cn, dtype=np.int32) for _ in range(6))
+        success = np.zeros(Cn, dtype=np.uint8)
+        rms = np.empty(Cn)
+        hyp = np.empty((Cn, H), dtype=np.int32) if want_hyp else None
+        n_ok, us = C.c_int64(), C.c_double()
+        self._check(self._lib.sfmba_resect_ransac(
+            self._h, _capi.ptr(x), _opt_ptr(sel), _opt_ptr(use), _opt_ptr(samples), C.byref(opt), _capi.ptr(cameras),
+            _capi.ptr(hyp_pose), _capi.ptr(mask), _capi.ptr(status), _capi.ptr(views), _capi.ptr(inl), _capi.ptr(best),
+            _capi.ptr(sol), _capi.ptr(success), _capi.ptr(iters), _capi.ptr(rms), _opt_ptr(hyp), C.byref(n_ok), C.byref(us)))
+        return RobustResection(cameras, hyp_pose, mask.view(np.bool_), status, views, inl, best, sol, success.view(np.bool_),
+                               iters, rms, hyp, int(n_ok.value), float(us.value))
 
     def fundamental_ransac(self, pts1, pts2, edge_ptr=None, pair_use=None, samples=None, want_hyp=False, **options):
         """F by RANSAC for every edge of a batch of matched pixel pairs, the reference's

@@ -139,6 +139,44 @@ def solve_pnp(point3ds, point2ds, K, dist=None, device=0, backend=None, **option
     return True, w.reshape(3, 1).copy(), (-R @ T).reshape(3, 1)
 
 
+def resect_cameras_ransac(x, args, select=None, obs_use=None, samples=None, want_hyp=False, device=0, backend=None, **options):
+    """`Backend.resect_ransac` in one call on the reference's ``args`` tuple (sfm.py:268): every selected camera by P3P
+    inside RANSAC over its used observations, then the pose refinement of :func:`resect_cameras` over the inliers -- the
+    registration step that survives wrong 2-D--3-D correspondences.  ``options``: the fields of
+    ``sfmba_pnp_ransac_options``.  -> :class:`sfmba.RobustResection`."""
+    be = _backend_with_problem(args, device, backend)
+    return be.resect_ransac(x, select=select, obs_use=obs_use, samples=samples, want_hyp=want_hyp, **options)
+
+
+def solve_pnp_ransac(objectPoints, imagePoints, K, dist=None, iterationsCount=100, reprojectionError=8.0, confidence=0.99,
+                     seed=0, device=0, backend=None, **options):
+    """``cv2.solvePnPRansac(objectPoints, imagePoints, K, dist, iterationsCount=, reprojectionError=, confidence=)``:
+    ``(N, 3)`` points and ``(N, 2)`` pixels -> ``(retval, rvec (3, 1), tvec (3, 1), inliers (k, 1) int32)`` in OpenCV's
+    ``x_cam = R X + t`` convention, ``inliers`` the positions of the inlier correspondences.  A one-camera problem through
+    :func:`resect_cameras_ransac`: ``retval`` is ``status == OK``; a failure gives False, NaN poses and an empty
+    ``inliers``.  ``confidence`` only feeds ``cam_success`` (there is no adaptive exit: all ``iterationsCount`` hypotheses
+    run).  The device model has no lens distortion: a non-zero ``dist`` raises ValueError.  ``options``: further fields of
+    ``sfmba_pnp_ransac_options`` (min_views, refine, min_depth, max_iter, xtol, max_rms_px)."""
+    if dist is not None and np.any(np.asarray(dist, dtype=np.float64) != 0.0):
+        raise ValueError("solve_pnp_ransac supports no lens distortion: dist must be None or all zeros")
+    objectPoints = np.ascontiguousarray(objectPoints, dtype=np.float64)
+    imagePoints = np.ascontiguousarray(imagePoints, dtype=np.float64)
+    n = len(objectPoints)
+    if objectPoints.shape != (n, 3) or imagePoints.shape != (n, 2) or np.shape(K) != (3, 3):
+        raise ValueError("expected objectPoints (N,3), imagePoints (N,2), K (3,3)")
+    if int(iterationsCount) < 1:
+        raise ValueError("iterationsCount must be at least 1")
+    x = np.concatenate([np.zeros(6), objectPoints.ravel()])
+    res = resect_cameras_ransac(x, (1, n, np.zeros(n, dtype=np.int64), np.arange(n, dtype=np.int64), imagePoints, K),
+                                device=device, backend=backend, max_iters=int(iterationsCount),
+                                threshold=float(reprojectionError), confidence=float(confidence), seed=seed, **options)
+    if not res.ok[0]:
+        return False, np.full((3, 1), np.nan), np.full((3, 1), np.nan), np.zeros((0, 1), dtype=np.int32)
+    w, T = res.cameras[0, :3], res.cameras[0, 3:]
+    R = api._matrix_from_rotvec(w)
+    return True, w.reshape(3, 1).copy(), (-R @ T).reshape(3, 1), np.flatnonzero(res.inlier_mask).astype(np.int32).reshape(-1, 1)
+
+
 def _cameras_from_projection(M, K):
     """``[R | t] = K^-1 M`` -> (rotation vector, centre ``T = -R^T t``), the six camera parameters of the
     bundle-adjustment model.  Raises ValueError when ``R`` is not a rotation to within 1e-6."""

@@ -1,5 +1,5 @@
-"""Bit identity of the consumers (reprojection statistics, triangulation, resection, and the two-view calls where both
-builds have them) between two builds of the library.  Usage: python tools/ab_consumer_bits.py LIB_A LIB_B [--out DIR]
+"""Bit identity of the consumers (reprojection statistics, triangulation, resection, and the two-view calls and the robust
+resection where both builds have them) between two builds of the library.  Usage: python tools/ab_consumer_bits.py LIB_A LIB_B [--out DIR]
 
 One fresh child process per library (SFMBA_LIB), each under its own time limit; the tool stops at the first child that
 does not exit cleanly.  A child runs the three calls over inputs that reach every form of the kernels -- the long-run,
@@ -67,6 +67,13 @@ def child(out_path):
                         for f in ("cameras", "status", "views", "iters", "rms_err"):
                             out[f"{key}/{f}"] = getattr(r, f)
                         out[f"{key}/n_ok"] = np.array([r.n_ok])
+                if hasattr(be._lib, "sfmba_resect_ransac"):  # (an older build has it not) drawn samples, refined and not
+                    for refine in (0, 1):
+                        r = be.resect_ransac(x, select=csel, obs_use=use, want_hyp=True, max_iters=96, threshold=2.0, seed=4,
+                                             min_views=4, refine=refine)
+                        for f in ("cameras", "hyp", "inlier_mask", "status", "views", "inliers", "best", "best_sol", "success",
+                                  "iters", "rms_err", "hyp_inliers"):
+                            out[f"pnp/{name}/{bits}/{m}/refine{refine}/{f}"] = getattr(r, f)
     # the two-view calls: a batch that reaches the staged and the unstaged form, every status, a mask, drawn and given samples
     if hasattr(be._lib, "sfmba_fundamental_ransac"):      # (an older build has neither)
         import two_view_ref as tv
@@ -118,17 +125,18 @@ def main():
             return 2
         files.append(np.load(path))
     a, b = files
-    only = [f for f in (a, b) if any(k.startswith("two_view|") for k in f.files)]
-    if len(only) == 1:                                           # one build has no two-view calls: nothing to compare them with
-        print("  (only one build has the two-view calls: their arrays are left out)")
+    class Without:
+        def __init__(self, f, prefix):
+            self.f, self.files = f, [k for k in f.files if not k.startswith(prefix)]
 
-        class Without:
-            def __init__(self, f):
-                self.f, self.files = f, [k for k in f.files if not k.startswith("two_view|")]
+        def __getitem__(self, k):
+            return self.f[k]
 
-            def __getitem__(self, k):
-                return self.f[k]
-        a, b = Without(a), Without(b)
+    for prefix, what in (("two_view|", "the two-view calls"), ("pnp|", "the robust resection")):
+        only = [f for f in (a, b) if any(k.startswith(prefix) for k in f.files)]
+        if len(only) == 1:                                       # one build has not got the call: nothing to compare it with
+            print(f"  (only one build has {what}: its arrays are left out)")
+            a, b = Without(a, prefix), Without(b, prefix)
     print(f"A = {lib_a}\nB = {lib_b}")
     differ = [k for k in a.files if k not in b.files or a[k].dtype != b[k].dtype or a[k].tobytes() != b[k].tobytes()]
     differ += [k for k in b.files if k not in a.files]
