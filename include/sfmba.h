@@ -594,6 +594,49 @@ int  sfmba_match_descriptors(sfmba_handle* h, int64_t n_edges, const int32_t* ed
                              double* dist_sq /* (Q,2) */, uint8_t* good /* Q */, int32_t* edge_good, int32_t* edge_status,
                              int64_t* n_ok, double* kernel_us);
 
+/* ---- feature tracks: the connected components of the matches (sfm.py:109-117, graph.py:101-119) ------------------- */
+/* What turns the pair lists of the matched edges into the index arrays of a problem: which features of which images are
+ * the same 3-D point.  The vertices are the features that occur in a used pair, the edges are the used pairs, and a
+ * track is a connected component (the transitive closure of the matches, not the reference's one-hop sets, and
+ * independent of the order of edges and pairs).  Neither call needs sfmba_set_problem or sfmba_set_descriptors; both use
+ * buffers of their own, freed by the next sfmba_build_tracks and by sfmba_destroy, so fun, grad, the PCG record and a
+ * following solve are exactly what a fresh handle gives.
+ *
+ * Input: n_images images; image i owns the global feature ids img_ptr[i] .. img_ptr[i+1] - 1 (the convention of
+ * sfmba_set_descriptors), N = img_ptr[n_images] < 2^31.  edges (n_edges, 2) int32 of images (u, v), u != v, in either
+ * orientation and possibly repeated; edge e owns the pairs pair_ptr[e] .. pair_ptr[e+1] - 1 of pairs (M, 2) int32: row in
+ * u, row in v; a pair may be repeated.  pair_use (M) uint8 or NULL: a pair with 0 takes no part (it is still checked).
+ *
+ * A component becomes a track when it has at least min_length features and, with max_length > 0, at most max_length,
+ * and when it holds no two features of one image or conflicts = 1.  (A component has two features or more, so
+ * min_length 1 and 2 ask for the same.)  Tracks are numbered by ascending smallest global feature id; within a track the
+ * observations ascend by global feature id, that is by image and then by row.
+ *   feat_track (N)   the feature's track, or -1: in no used pair; -2: its component was dropped for its length; -3: its
+ *                    component was dropped for a conflict (also when the length fails as well)
+ *   counts (6)       components, tracks kept, dropped as too short, dropped as too long, dropped for a conflict (a
+ *                    component that also fails a length test counts here only), T = observations of the kept tracks
+ *   kernel_us        with profile = 1 the HIP-event time over all launches of the call, else 0
+ * sfmba_get_tracks returns the CSR of the last build: track_ptr (n_tracks + 1) int64, track_feat (T) global feature ids,
+ * track_image (T), n_tracks = counts[1]; any of them may be NULL.
+ * The result is a pure function of the input: the same bits whatever the grid, the schedule, or the order of edges and
+ * pairs.  Zero edges, zero pairs and a pair_use of zeros are valid: no track, feat_track all -1.
+ * Returns -1, before any kernel reads a pair, for img_ptr or pair_ptr not ascending from 0, an image id out of range,
+ * u == v, a row outside its image, N >= 2^31, min_length < 1, a non-zero max_length below min_length, conflicts other
+ * than 0 or 1, and for sfmba_get_tracks before a successful build. */
+typedef struct sfmba_track_options {
+    int32_t min_length;  /* fewest features of a track (2) */
+    int32_t max_length;  /* most features of a track, 0 = no limit (0) */
+    int32_t conflicts;   /* 0 = drop a component with two features of one image, 1 = keep it (0) */
+    int32_t profile;     /* 1 = kernel_us is measured (0) */
+} sfmba_track_options;
+void sfmba_default_track_options(sfmba_track_options* opt);
+int  sfmba_build_tracks(sfmba_handle* h, int64_t n_images, const int64_t* img_ptr /* n_images + 1, ascending from 0 */,
+                        int64_t n_edges, const int32_t* edges /* (n_edges,2) */, const int64_t* pair_ptr /* n_edges + 1 */,
+                        const int32_t* pairs /* (M,2) */, const uint8_t* pair_use /* M or NULL */,
+                        const sfmba_track_options* opt, int32_t* feat_track /* N or NULL */, int64_t* counts /* 6 or NULL */,
+                        double* kernel_us);
+int  sfmba_get_tracks(sfmba_handle* h, int64_t* track_ptr, int32_t* track_feat, int32_t* track_image);
+
 /* ---- least_squares(method='trf', x_scale='jac') (sfm.py:266-268) ---------------------------- */
 /* x_inout: x0 on entry, result.x on success (untouched on failure). */
 int  sfmba_solve(sfmba_handle* h, double* x_inout, const sfmba_options* opt, sfmba_result* out);

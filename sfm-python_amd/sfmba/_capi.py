@@ -27,6 +27,7 @@ SYMBOLS = (
     "sfmba_default_pnp_ransac_options", "sfmba_resect_ransac",
     "sfmba_default_ransac_options", "sfmba_fundamental_ransac", "sfmba_default_pose_options", "sfmba_recover_pose",
     "sfmba_set_descriptors", "sfmba_default_match_options", "sfmba_match_descriptors",
+    "sfmba_default_track_options", "sfmba_build_tracks", "sfmba_get_tracks",
 )
 
 
@@ -84,6 +85,10 @@ class PoseOptions(C.Structure):
 
 class MatchOptions(C.Structure):
     _fields_ = [("ratio", C.c_double), ("form", C.c_int32), ("profile", C.c_int32)]
+
+
+class TrackOptions(C.Structure):
+    _fields_ = [("min_length", C.c_int32), ("max_length", C.c_int32), ("conflicts", C.c_int32), ("profile", C.c_int32)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -205,6 +210,14 @@ def load():
         lib.sfmba_match_descriptors.argtypes = ([P, C.c_int64, P, C.POINTER(MatchOptions)] + [P] * 6 +
                                                 [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
         lib.sfmba_match_descriptors.restype = C.c_int
+    if hasattr(lib, "sfmba_build_tracks"):           # (likewise)
+        lib.sfmba_default_track_options.argtypes = [C.POINTER(TrackOptions)]
+        lib.sfmba_default_track_options.restype = None
+        lib.sfmba_build_tracks.argtypes = ([P, C.c_int64, P, C.c_int64] + [P] * 4 + [C.POINTER(TrackOptions), P, P,
+                                                                                   C.POINTER(C.c_double)])
+        lib.sfmba_build_tracks.restype = C.c_int
+        lib.sfmba_get_tracks.argtypes = [P] * 4
+        lib.sfmba_get_tracks.restype = C.c_int
     lib.sfmba_tr2d_solve.argtypes = [P, P, C.c_double, P]
     lib.sfmba_comm_get_unique_id.argtypes = [P]
     lib.sfmba_comm_init.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int64]

@@ -124,6 +124,114 @@ def check_match_edges(edges, n_images):
     return np.ascontiguousarray(e, dtype=np.int32)
 
 
+class Tracks:
+    """What `Backend.build_tracks` returns (include/sfmba.h: sfmba_build_tracks): the connected components of the used
+    match pairs.  ``feat_track`` (N) int32 per global feature id: its track, or ``UNMATCHED`` (in no used pair), ``SHORT``
+    (its component failed a length test), ``CONFLICT`` (its component holds two features of one image and was dropped).
+    The kept tracks as a CSR in point-major order: track t owns ``track_ptr[t]:track_ptr[t + 1]`` of ``track_feat``
+    (global feature ids, ascending), ``track_image`` and ``track_row`` (the row within the image).  ``counts``: a dict
+    of ``components``, ``tracks``, ``short``, ``long``, ``conflict``, ``observations``; ``n_tracks``; ``kernel_us``
+    (``profile=1``, else 0); ``img_ptr`` the input's."""
+
+    UNMATCHED, SHORT, CONFLICT = -1, -2, -3
+    COUNTS = ("components", "tracks", "short", "long", "conflict", "observations")
+
+    def __init__(self, img_ptr, feat_track, track_ptr, track_feat, track_image, counts, kernel_us):
+        self.img_ptr, self.feat_track, self.track_ptr = img_ptr, feat_track, track_ptr
+        self.track_feat, self.track_image = track_feat, track_image
+        self.track_row = (track_feat - img_ptr[track_image]).astype(np.int32)
+        self.counts = {k: int(v) for k, v in zip(self.COUNTS, counts)}
+        self.n_tracks, self.kernel_us = len(track_ptr) - 1, float(kernel_us)
+
+    def track_of(self, image, row):
+        """The track of feature ``row`` of ``image`` (or one of the negative states); arrays are taken element-wise."""
+        image, row = np.asarray(image), np.asarray(row)
+        if np.any(image < 0) or np.any(image >= len(self.img_ptr) - 1):
+            raise ValueError("image out of range")
+        if np.any(row < 0) or np.any(row >= self.img_ptr[image + 1] - self.img_ptr[image]):
+            raise ValueError("row outside its image")
+        t = self.feat_track[self.img_ptr[image] + row]
+        return int(t) if t.ndim == 0 else t
+
+    def problem(self, pts):
+        """The index arrays of a bundle-adjustment problem over the kept tracks: ``pts`` a list of (n_i, 2) pixel positions
+        of the images' features -> ``(n_points, camera_indices, point_indices, points_2d)`` with camera index = image id
+        and point index = track id, point-major as `set_problem` prefers."""
+        rows = np.diff(self.img_ptr)
+        if len(pts) != len(rows):
+            raise ValueError(f"{len(rows)} images, {len(pts)} pixel arrays")
+        pts = [np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in pts]
+        for k, a in enumerate(pts):
+            if a.shape[0] != rows[k]:
+                raise ValueError(f"pixels of image {k} must be ({rows[k]}, 2), got {a.shape}")
+        allpts = np.concatenate(pts, axis=0) if pts else np.empty((0, 2))
+        point_indices = np.repeat(np.arange(self.n_tracks, dtype=np.int32), np.diff(self.track_ptr))
+        return self.n_tracks, self.track_image.copy(), point_indices, np.ascontiguousarray(allpts[self.track_feat])
+
+    def __repr__(self):
+        return f"Tracks(n_tracks={self.n_tracks}, observations={self.counts['observations']})"
+
+
+def check_track_inputs(img_ptr, edges, pair_ptr, pairs, pair_use=None, min_length=2, max_length=0, conflicts=0, profile=0):
+    """The arguments of `Backend.build_tracks`, checked as sfmba_build_tracks checks them -> (img_ptr int64, edges (E, 2)
+    int32, pair_ptr int64, pairs (M, 2) int32, pair_use uint8 or None, options dict).  Raises ValueError."""
+    def ascending(a, name):
+        a = np.asarray(a)
+        if a.ndim != 1 or a.shape[0] < 1 or not (np.issubdtype(a.dtype, np.integer) or a.dtype == np.bool_):
+            raise ValueError(f"{name} must be a non-empty 1-D integer array")
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        if a[0] != 0 or np.any(np.diff(a) < 0):
+            raise ValueError(f"{name} must ascend from 0")
+        return a
+
+    def int_pairs(a, name):
+        a = np.asarray(a)
+        if a.size == 0:
+            return np.empty((0, 2), dtype=np.int32)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError(f"{name} must be (n, 2), got {a.shape}")
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{name} must be integers, got {a.dtype}")
+        if a.min() < -2**31 or a.max() >= 2**31:
+            raise ValueError(f"{name} does not fit int32")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    for name, v in (("min_length", min_length), ("max_length", max_length), ("conflicts", conflicts)):
+        if int(v) != v:
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    min_length, max_length, conflicts = int(min_length), int(max_length), int(conflicts)
+    if min_length < 1:
+        raise ValueError(f"min_length must be at least 1, got {min_length}")
+    if max_length < 0 or (max_length and max_length < min_length):
+        raise ValueError(f"max_length {max_length} is below min_length {min_length} (0 = no limit)")
+    if conflicts not in (0, 1):
+        raise ValueError(f"conflicts must be 0 (drop) or 1 (keep), got {conflicts}")
+    img_ptr, pair_ptr = ascending(img_ptr, "img_ptr"), ascending(pair_ptr, "pair_ptr")
+    n_images, N = len(img_ptr) - 1, int(img_ptr[-1])
+    if N >= 2**31:
+        raise ValueError(f"{N} features, the limit is 2^31 - 1")
+    edges, pairs = int_pairs(edges, "edges"), int_pairs(pairs, "pairs")
+    if len(edges) != len(pair_ptr) - 1:
+        raise ValueError(f"{len(edges)} edges, pair_ptr is for {len(pair_ptr) - 1}")
+    if len(pairs) != pair_ptr[-1]:
+        raise ValueError(f"{len(pairs)} pairs, pair_ptr ends at {int(pair_ptr[-1])}")
+    if len(edges):
+        if edges.min() < 0 or edges.max() >= n_images:
+            raise ValueError(f"edges name image {int(edges.max() if edges.max() >= n_images else edges.min())}, there are {n_images}")
+        same = np.flatnonzero(edges[:, 0] == edges[:, 1])
+        if len(same):
+            raise ValueError(f"edge {int(same[0])} joins image {int(edges[same[0], 0])} to itself")
+    if len(pairs):
+        rows = np.diff(img_ptr).astype(np.uint32)
+        limit = np.repeat(rows[edges], np.diff(pair_ptr), axis=0)            # (M, 2): rows of u, rows of v
+        bad = pairs.view(np.uint32) >= limit                                 # (unsigned: a negative row is a huge one)
+        if bad.any():
+            raise ValueError(f"pair {int(np.flatnonzero(bad.any(axis=1))[0])} names a row outside its image")
+    pair_use = _mask(pair_use, len(pairs), "pair_use")
+    return img_ptr, edges, pair_ptr, pairs, pair_use, dict(min_length=min_length, max_length=max_length,
+                                                           conflicts=conflicts, profile=int(bool(profile)))
+
+
 def check_match_options(ratio=0.5, form=0, profile=0):
     ratio = float(ratio)
     if not ratio > 0.0:
@@ -753,6 +861,28 @@ class Backend:
             self._h, E, _capi.ptr(edges), C.byref(opt), _capi.ptr(qptr), _capi.ptr(idx), _capi.ptr(dist), _capi.ptr(good),
             _capi.ptr(egood), _capi.ptr(status), C.byref(n_ok), C.byref(us)))
         return DescriptorMatches(edges, qptr, idx, dist, good.view(np.bool_), egood, status, n_ok.value, us.value)
+
+    def build_tracks(self, img_ptr, edges, pair_ptr, pairs, pair_use=None, **options):
+        """Feature tracks as the connected components of the used match pairs (include/sfmba.h: sfmba_build_tracks).
+        ``img_ptr`` (n + 1): image i owns the global feature ids ``img_ptr[i]:img_ptr[i + 1]``; ``edges`` (E, 2) images
+        (u, v); edge e owns ``pair_ptr[e]:pair_ptr[e + 1]`` of ``pairs`` (M, 2): row in u, row in v; ``pair_use`` (M) or
+        None.  Options: ``min_length`` (2), ``max_length`` (0 = none), ``conflicts`` (0 drop, 1 keep), ``profile``.
+        Needs no problem and no descriptors and leaves both as they are.  -> :class:`Tracks`."""
+        img_ptr, edges, pair_ptr, pairs, pair_use, options = check_track_inputs(img_ptr, edges, pair_ptr, pairs, pair_use,
+                                                                                **options)
+        opt = _capi.TrackOptions()
+        self._lib.sfmba_default_track_options(C.byref(opt))
+        _fill_options(opt, options, "track")
+        self._flush_pending()
+        feat_track = np.empty(int(img_ptr[-1]), dtype=np.int32)
+        counts, us = np.zeros(6, dtype=np.int64), C.c_double()
+        self._check(self._lib.sfmba_build_tracks(
+            self._h, len(img_ptr) - 1, _capi.ptr(img_ptr), len(edges), _capi.ptr(edges), _capi.ptr(pair_ptr), _capi.ptr(pairs),
+            _opt_ptr(pair_use), C.byref(opt), _capi.ptr(feat_track), _capi.ptr(counts), C.byref(us)))
+        track_ptr = np.empty(int(counts[1]) + 1, dtype=np.int64)
+        track_feat, track_image = np.empty(int(counts[5]), dtype=np.int32), np.empty(int(counts[5]), dtype=np.int32)
+        self._check(self._lib.sfmba_get_tracks(self._h, _capi.ptr(track_ptr), _capi.ptr(track_feat), _capi.ptr(track_image)))
+        return Tracks(img_ptr, feat_track, track_ptr, track_feat, track_image, counts, us.value)
 
     def residual_jacobian(self, x):
         self._flush_pending()

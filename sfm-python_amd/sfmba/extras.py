@@ -5,7 +5,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import api
-from .backend import check_descriptors, check_match_edges, check_match_options
+from .backend import check_descriptors, check_match_edges, check_match_options, check_track_inputs
 
 
 def reproj_error(point3ds, point2ds, K, R, tvec, device=0):
@@ -442,6 +442,29 @@ def match_features(descs, pts, K, min_matches=80, ratio=0.5, device=0, backend=N
         F = est.F_refit[k].copy()
         out.append((int(m.edges[e, 0]), int(m.edges[e, 1]), gp[mask], F, K.T @ F @ K))
     return out
+
+
+def build_tracks(matches, n_features, device=0, backend=None, **options):
+    """Feature tracks from the matched edges: what ``SFM._build_tracks`` (sfm.py:109-117) and the fusion bookkeeping of
+    graph.py decide, as the connected components of the matches.  ``matches``: the list :func:`match_features` returns,
+    ``(u, v, inlier_pairs, F, E)``, or plain ``(u, v, pairs)`` tuples, pairs (k, 2) of (row in u, row in v);
+    ``n_features``: the number of features of every image.  Options as :meth:`Backend.build_tracks`.
+    -> :class:`Tracks`; ``.problem(pts)`` gives the index arrays of ``set_problem``."""
+    n_features = np.asarray(n_features)
+    if n_features.ndim != 1 or (n_features.size and (not np.issubdtype(n_features.dtype, np.integer) or n_features.min() < 0)):
+        raise ValueError("n_features must be a 1-D array of non-negative integers, one per image")
+    img_ptr = np.concatenate([[0], np.cumsum(n_features, dtype=np.int64)]).astype(np.int64)
+    matches = list(matches)
+    for k, m in enumerate(matches):
+        if len(m) < 3:
+            raise ValueError(f"match {k} must be (u, v, pairs, ...)")
+    edges = np.array([(int(m[0]), int(m[1])) for m in matches], dtype=np.int64).reshape(-1, 2)
+    lists = [np.asarray(m[2]).reshape(-1, 2) if np.asarray(m[2]).size else np.empty((0, 2), dtype=np.int64) for m in matches]
+    pair_ptr = np.concatenate([[0], np.cumsum([len(p) for p in lists], dtype=np.int64)]).astype(np.int64)
+    pairs = np.concatenate(lists, axis=0) if lists else np.empty((0, 2), dtype=np.int64)
+    args = check_track_inputs(img_ptr, edges, pair_ptr, pairs, None, **options)
+    be = backend if backend is not None else api.get_backend(device)
+    return be.build_tracks(*args[:5], **args[5])
 
 
 def load_calibration_data(txt_path):
