@@ -2,7 +2,7 @@
 // None touches a buffer of the solver's.  What they share comes first: every helper is inlined
 // and keeps no state, so a call site compiles to what was written out there before.
 #pragma once
-#include "ba_kernels.hpp"
+#include "ba_device.hpp"
 
 namespace sfmba {
 

@@ -7,44 +7,21 @@
 // of forward-differenced, and the damped Gauss-Newton step of trf.py:480 is obtained from the Schur
 // complement on the cameras with block-Jacobi PCG (K4-K6) instead of LSMR on the full system.
 // Only scalars and 2x2 systems are handled on the host; every n- or m-vector stays in HBM.
-#include "../../include/sfmba.h"
+#include "handle.hpp"
 
-#include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
-#include <rccl/rccl.h>   // types only: librccl.so.1 is dlopen()ed by sfmba_comm_init
 #include <dlfcn.h>
 
-#include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <condition_variable>
-#include <functional>
-#include <initializer_list>
-#include <mutex>
-#include <numeric>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "problem_tables.hpp"
 #include "ba_kernels.hpp"
-#include "consumer_kernels.hpp"
-#include "match_kernels.hpp"
-#include "track_inputs.hpp"
-#include "track_kernels.hpp"
-#include "tr2d.hpp"
-
-using namespace sfmba;
 
 namespace {
-
-constexpr size_t kLdsBytes = 160 * 1024;       // gfx950: 160 KiB LDS per workgroup
-constexpr size_t kLdsDynMax = kLdsBytes - 2048; // dynamic part; every kernel here has <= 2 KiB static LDS (k_backsub: 1280 B)
 // Scalars at the end of the exchange arena (32 doubles):
 //   summed over ranks [0..11]: 0 sum r^2 | 1 G11 | 2 G12 | 3 G22 | 4..7 q5..q8 | 8..11 q1..q4 of the point
 //                              slice (grouped so that each phase all-reduces one contiguous run of fresh values)
@@ -66,60 +43,6 @@ constexpr int kStepSlot = 25, kSkipSlot = 30, kRadiusSlot = 31;
 constexpr int kPinCtrl = 40;             // a PcgCtrl (pcg_read)
 constexpr int kPinP2pErr = 62;           // the error word of the direct link at the end of a solve
 constexpr int kPointSlot[9] = {12, 8, 9, 10, 11, 4, 5, 6, 7};     // slot of q0..q8 of the point slice
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t ensure(size_t n) {
-        if (n <= bytes && p) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-        if (n == 0) n = 8;
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-    // grow-only like ensure(), but the first `keep` bytes survive a reallocation (device-to-device copy) and the new
-    // block has headroom, so that a problem that grows call by call does not reallocate every time
-    hipError_t ensure_keep(size_t n, size_t keep) {
-        if (n <= bytes && p) return hipSuccess;
-        if (keep == 0 || !p) return ensure(n + n / 2);
-        void* q = nullptr;
-        const size_t cap = n + n / 2;
-        hipError_t e = hipMalloc(&q, cap);
-        if (e != hipSuccess) return e;
-        e = hipMemcpy(q, p, std::min(keep, bytes), hipMemcpyDeviceToDevice);
-        (void)hipFree(p);
-        p = q; bytes = cap;
-        return e;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-// a piece of a larger device allocation (the structure tables of a problem share one buffer and one upload)
-struct DevView {
-    void* p = nullptr;
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-// pinned host memory, grow-only, optionally keeping a prefix across a reallocation
-struct PinnedBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-    hipError_t ensure(size_t n, size_t keep) {
-        if (n <= bytes && p) return hipSuccess;
-        void* q = nullptr;
-        const size_t cap = n + n / 2 + 64;
-        hipError_t e = hipHostMalloc(&q, cap, hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        if (p && keep) memcpy(q, p, std::min(keep, bytes));
-        if (p) (void)hipHostFree(p);
-        p = q; bytes = cap;
-        return hipSuccess;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
 
 // RCCL entry points, resolved at run time so that libsfmba.so has no load-time dependency on RCCL
 struct RcclApi {
@@ -151,87 +74,13 @@ RcclApi* rccl_api() {
     return api.lib ? &api : nullptr;
 }
 
-// test / diagnostic hooks, set through sfmba_debug_option only (nothing reads the environment)
-#define SFMBA_DEBUG_OPTIONS(X) \
-    X(pcg_fused, -1)      /* 0: two-kernel PCG although the fused launch would fit */ \
-    X(tab_lds, -1)        /* 0: camera table read from L2 although LDS would fit */ \
-    X(vec_lds, -1)        /* 0: camera vector read from L2 although LDS would fit */ \
-    X(sweep_rc, -1)       /* 0: pass A reads the stored Jacobian although the recomputing form would fit; 2: its table in global memory whatever the size */ \
-    X(dense, -1)          /* 0: PCG although the dense reduced-camera path would apply */ \
-    X(precond, -1)        /* 0: block-Jacobi preconditioner from U + Dc instead of the Schur diagonal */ \
-    X(pcg_local, -1)      /* 0: the fused PCG keeps its whole update in pass A's prologue */ \
-    X(xcd_chunks, -1)     /* 1 / 0: camera lists cut at the eight point-range boundaries (one chunk per XCD) whatever the size */ \
-    X(rhsrec, -1)         /* 1 / 0: the rhs + preconditioner pass gathers its own 128-byte records whatever the size */ \
-    X(cost_rider, -1)     /* 0: the trial cost is summed and posted by a k_finish launch of its own */ \
-    X(packed_upload, -1)  /* 0: the observation arrays are uploaded as int32 / fp64 although they would pack */ \
-    X(jfree, -1)          /* 1: the J-free iteration (measurement): K1 does not write the Jacobian, k_jdot and k_backsub recompute its blocks from the LDS camera table */ \
-    X(rc_consumers, -1)   /* 0: k_jdot and k_backsub read the stored Jacobian although their row form would apply; 1: the row form wherever it is legal, whatever the size */ \
-    X(cm_device, -1)      /* 0: the camera-major order is sorted on the host and its permutation uploaded */ \
-    X(pcg_inline, -1)     /* 0: sharded solves keep the collective of the product as a launch of its own */ \
-    X(xcd_cam, -1)        /* 0: K3 and the rhs pass keep the one-chunk-per-camera table where pass B takes the XCD-aware one */ \
-    X(pcg_skip_last, -1)  /* 0: the pass B behind the launch the record says is the last one is enqueued all the same; 2: only that pass B is left out */ \
-    X(pcg_mixed_b, -1)    /* 0: pass B keeps fp64 point records although pass A runs on fp32 operands */ \
-    X(pcg_mixed, -1)      /* 1 / 0: fp32 operands in the implicit Schur product whatever the storage mode */ \
-    X(pcg_split, -1)      /* 1: the local form with its tail in a kernel of its own (k_pcg_tail) on a single rank too; 0: sharded / multi-chunk solves keep the round-2 forms (whole update in every workgroup of pass A, or k_pcg_update) */ \
-    X(spec_scale, -1)     /* 0: k_update_scale is launched after the host has accepted the trial point */ \
-    X(start_handoff, -1)  /* 0: a solve starts with a blocking read-back of the cost and the scale sums */ \
-    X(early_download, -1) /* 0: the result is copied to the host behind the last launch of the solve */ \
-    X(cam_chunk, 0)       /* > 0: chunk length of the camera-major kernels */ \
-    X(pcg_guess_bias, 0)  /* added to the number of speculatively enqueued PCG iterations */ \
-    X(trace_pcg, 0) X(trace_stalls, 0) X(trace_timing, 0)   /* stderr diagnostics */ \
-    X(wait_deadline_s, 120) /* a hand-off that does not arrive within this many seconds fails the solve (-3) */ \
-    X(p2p_delay_ms, 0)    /* test: sleep this long before the first collective of a solve */ \
-    X(p2p_timeout_ms, 0)  /* test: > 0 overrides both time-outs of the direct all-reduce */
-struct Debug {
-#define X(name, init) int name = init;
-    SFMBA_DEBUG_OPTIONS(X)
-#undef X
-};
 // name -> member, from the same list: an option cannot exist without a setter
 const struct { const char* name; int Debug::*member; } kDebugOptions[] = {
 #define X(name, init) {#name, &Debug::name},
     SFMBA_DEBUG_OPTIONS(X)
 #undef X
 };
-
-// Which form of every kernel runs.  Two functions below the handle fill it and nothing else writes it:
-// decide_problem_forms (sfmba_set_problem) and decide_solve_forms (start of every compute call).
-struct Forms {
-    // ---- problem stage: frozen until the next sfmba_set_problem
-    bool packed_upload = false;              // observation arrays cross PCIe as uint16 / int16 (k_unpack_obs)
-    bool cm_device = false;                  // camera-major order sorted on the device
-    int64_t cam_chunk_len = 4096;            // chunk length of the camera-major kernels
-    bool lds_tab = true, lds_vec = true;     // camera table (K1, K2) / camera vector (sweeps) staged in LDS
-    bool sweep_rc = false;                   // pass A recomputes the blocks from an LDS table (k_point_sweep_rc)
-    bool sweep_rc_g = false;                 // ... from a table in global memory (more cameras than the LDS holds)
-    bool round_blocks = false;               // pass A applies stored fp32 blocks: the camera-major passes round theirs the same way
-    bool pcg_fused = false;                  // PCG update fused into the launch of pass A (v in LDS, C <= 1024)
-    // mixed-precision Schur product (ba_kernels.hpp: MixedPrep): fp32 operands, fp64 arithmetic
-    bool mixed = false;                      // pass A
-    bool mixed_b = false;                    // ... and pass B (fp32 point records)
-    bool jfree = false;                      // J-free iteration (needs the camera table in LDS)
-    bool rc_cons = false;                    // k_jdot / k_backsub in row form (k_jdot_rc, k_backsub_rc): the stored Jacobian is not read
-    bool dense = false;                      // reduced camera matrix formed and factorised (6 C <= kDenseMaxN) instead of PCG
-    bool xcd_b = false;                      // pass B takes the XCD-aware chunk table (every camera's list cut at eight point ranges)
-    bool use_rhsrec = false;                 // the rhs + preconditioner pass gathers its own 128-byte records (many points)
-    bool cam_multi = false;                  // some camera has more than one chunk: k_cam_combine runs
-    // ---- solve stage: from the above, the transport as it stands and the options read live
-    bool one_rank = true;                    // no transport: nothing is exchanged
-    bool dense_solve = false;                // dense, on one rank (sharded: the block pairs would need their own all-reduce)
-    bool precond = true;                     // Schur-diagonal preconditioner (false: block-Jacobi of U + Dc)
-    bool xcd_cam = false;                    // K3 and the rhs pass over the XCD-aware table too, one wave per chunk
-    bool cam_inline = false;                 // per-camera sums of K3 / the rhs pass all-reduced by the workgroup that forms them
-    bool own_inverse = false;                // the rhs pass inverts its camera's preconditioner block itself (RhsPrecond)
-    // where the product is reduced: inside pass B, camera by camera (CamExchange) / behind it, with the per-camera tail of
-    // the local form (k_p2p_pcg / k_pcg_tail); else by a collective and k_pcg_update or pass A's prologue
-    bool pcg_inline = false, pcg_split = false;
-    // per-camera bookkeeping in pass B or the tail: the fused form / the light update as a kernel of its own (> 1024 cameras)
-    bool pcg_local = false, pcg_local2 = false;
-    int skip_last = 0;                       // of the last speculative launch pair: 0 nothing is left out, 1 its pass B, 2 pass A too (FinalUpdate)
-    // hand-offs: no blocking one at the start; k_update_scale of the trial point enqueued before the verdict; (one rank) the
-    // trial cost and its post ride with K3; the result leaves on the copy stream as soon as the solve is decided
-    bool quick_start = false, spec_scale = false, cost_rider = true, early_download = false;
-};
+void decide_solve_forms(sfmba_handle* h);           // (defined with its table, below)
 
 }  // namespace
 
@@ -242,221 +91,9 @@ static_assert(sizeof(TableRow4) == sizeof(int4) && alignof(TableRow4) == alignof
               offsetof(TableRow4, y) == offsetof(int4, y) && offsetof(TableRow4, z) == offsetof(int4, z) &&
               offsetof(TableRow4, w) == offsetof(int4, w), "TableRow4 is int4");
 
-struct sfmba_handle {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::string err;
-    int n_cu = 256;
-
-    // problem
-    bool have_problem = false;
-    int64_t C = 0, P = 0, N = 0, ld = 0, n = 0;
-    int64_t N_total = 0;
-    KMat K{};
-    bool permuted = false;
-    int n_ranges = 0;
-    bool f32 = false;                        // fp32 storage of uv, r, t1 and the Jacobian (arithmetic stays fp64)
-    bool f32_next = false;                   // takes effect at the next sfmba_set_problem
-    std::vector<int64_t> fixed_next;         // sfmba_set_fixed_cameras: cameras held still from the next sfmba_set_problem on
-    int64_t n_fixed = 0;                     // ... of the current problem
-    Forms forms;                            // which kernel forms run (decide_problem_forms / decide_solve_forms)
-    DevBuf rctab;                            // [C][18], k_rc_table
-    DevBuf rt32, rec32, rctab32, rtd;        // [C][12], [P][8], [C][20] floats; [C][12] doubles
-    Origin origin{0.0, 0.0, 0.0};            // coordinates are rounded relative to it (set with every uploaded x)
-    DevView cov_ptr, cov_pt, blk_ab;         // dense path: per block pair (a <= b) the points both cameras see
-    DevBuf Sblk;
-    DevBuf tables;                           // ranges | wsteps | steps | chunk table | chunk offsets | pair lists: ONE upload
-    int n_blk = 0;
-    Debug dbg;                               // test / diagnostic hooks (sfmba_debug_option)
-
-    DevBuf cam_idx, pt_idx, pt_ptr, uv;
-    DevView ranges, wsteps, steps;
-    int n_steps = 0;
-    // camera-major order of the same observations (structure only): per-camera sums without atomics
-    DevBuf cm_perm, cm_pt, cm_uv, cam_partial;
-    DevBuf sort_hist, fixed_dev;             // device-side camera-major sort: [kSortSlices][C] counts -> offsets; held cameras
-    DevView cam_ptr_dev;                     // [C + 1]
-    DevView cam_chunks, cam_chunk_ptr;
-    int n_chunks = 0;
-    // a second chunk table for pass B of the Schur product alone (many points): every camera's list cut at the eight
-    // point-range boundaries, chunk 8 c + k on XCD k (see set_problem)
-    DevView cam_chunks_b, cam_chunk_ptr_b;
-    int n_chunks_b = 0;
-    DevBuf xa, xb, tabA, tabB, r, J, t1;     // ONE Jacobian / residual buffer set
-    DevBuf rhsrec;                           // [P][kRhsRec]: what k_cam_rhs_diag gathers (written by k_prep)
-    DevBuf V, Vinv, gp, e, recA, recB;       // rec: point records X Y Z | z (k_fill_rec), one per parameter vector
-    DevBuf edge;                             // pieces of the point rows cut by K1's tiles (PointBlocksOut)
-    DevBuf g, si, sg, p;                     // n-vectors; p = [dc | dp]
-    DevBuf g2, si2, sg2;                     // second set of g, si, sg: a speculative k_update_scale writes the trial
-                                             // point's there (see g_cur below)
-    DevBuf Dc, Minv, vecs, vtmp, vcm;               // camera-sized, plane-major [k][C]; vecs = 2 sets x (x r p s u)
-    DevBuf part, ctrl;
-    DevBuf arena_own;
-    double* arena = nullptr;                 // [acc 6C | sd 21C | Ugc 27C | 32 scalars]; acc | sd are plane-major [27][C]
-    int64_t arena_doubles = 0;
-    sfmba_allreduce_fn ar_fn = nullptr;
-    void* ar_ctx = nullptr;
-    sfmba_print_fn print_fn = nullptr;       // verbose = 2 lines go here (null: stdout of the C library)
-    void* print_ctx = nullptr;
-    ncclComm_t comm = nullptr;               // native RCCL communicator (sfmba_comm_init)
-    int64_t n_collectives = 0, n_launches = 0;
-    // direct all-reduce over peer-mapped staging buffers (k_p2p_allreduce); preferred over RCCL / the
-    // callback for every vector that fits a slot
-    struct P2p {
-        bool ready = false;
-        int rank = 0, world = 0;
-        int64_t stride = 0;                  // doubles per slot
-        void* own = nullptr;                 // this rank's staging buffer (flags, then data)
-        void* opened[kP2pMaxRanks] = {};     // peers' buffers as mapped here (null for own)
-        double* data[kP2pMaxRanks] = {};
-        unsigned long long* flags[kP2pMaxRanks] = {};
-        double* camdata[kP2pMaxRanks] = {};  // [2][W][6 C]: the product's per-camera exchange inside pass B (CamExchange)
-        unsigned* words = nullptr;           // [0] ticket, [1] error, [2..3] uint64 count of performed collectives
-        int64_t calls = 0;
-        bool first_in_solve = true;          // the next collective is the rendezvous of a solve (long timeout)
-        // agreed over the link itself at attach (every rank holds the same two values):
-        int shared_device = 1;               // ranks whose handle sits on the same physical GPU as this one's (rehearsals)
-        bool any_multi = false;              // some rank's shard has a camera of several chunks / the XCD-aware chunk table
-    } p2p;
-    double* h_scal = nullptr;                // pinned
-    // set_problem: converted arrays of the current problem in pinned memory (upload source, and what the next
-    // call is compared with), host copies of the structure tables, worker threads
-    struct Stage { PinnedBuf uv, ci, pi, perm, ptr, uvf, tables, ci16, uv16; } stage;
-    DevBuf ci16_dev, uv16_dev;               // packed upload of the observation arrays (k_unpack_obs)
-    struct Prev { bool valid = false; bool f32 = false; bool packed = false; int64_t N = 0, P = 0; } prev;
-    ProblemTables tb;                        // what build_problem_tables() made of the arguments (problem_tables.hpp)
-    HostPool pool;
-    int64_t obs_reused = 0, obs_uploaded = 0;    // of the last sfmba_set_problem
-    double* mbox = nullptr;                  // coherent pinned block the device posts the hand-off into (Mailbox)
-    double* mbox_dev = nullptr;              // its device-visible address
-    unsigned long long mbox_seq = 0;
-    Mailbox post{};                          // set while the launch that ends a hand-off is enqueued; else empty
-    double* h_x = nullptr;                   // pinned staging of the parameter vector
-    size_t h_x_doubles = 0;
-    // Large problems (>= 2M parameters): the result leaves the device while the solve still runs -- every trial point is
-    // copied to a pinned mirror of its buffer on a second stream, behind the launch that wrote it and beside the
-    // evaluation of that point, so that the accepted x of the LAST iteration is already on the host when the solve ends
-    // (24 MB = 0.45 ms at 3M parameters).  Not below that size: there the runtime performs the copy as a blit KERNEL,
-    // which shares the CUs with the residual + Jacobian kernel it overlaps (K1 30 -> 32 us at 306k parameters, 60 us
-    // under rocprofv3).  (Also tried there: the result in four chunks whose staging copies overlap the later chunks'
-    // DMA -- 145 us against 130-150 us for one copy + a four-thread staging copy: four blit launches, no gain.)
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_written = nullptr, ev_copied[2] = {nullptr, nullptr};
-    bool result_in_flight = false;           // a solve's early result copy (copy stream -> h_x) has not been waited for
-    PinnedBuf mirror[2];
-    unsigned long long mirror_tag[2] = {0, 0}, copy_count = 0, x_tag = 0;
-    bool mirror_on = false;
-    const double* skip = nullptr;         // device flag gating speculative trial launches (sfmba_solve); else null
-    double pcg_tol = 0.0; int pcg_cap = 0; // options of the running PCG (fused launch 0 writes the control block)
-    bool pcg_b_owed = false;              // the pass B behind the last enqueued pass A was left out (pcg_enqueue)
-    bool pcg_a_owed = false;              // ... and that pass A too: k_backsub does its update (FinalUpdate)
-    DevBuf pcg_part;                      // [4][C] partial dot products of the local form
-    int pcg_hint = 0;                     // largest PCG iteration count a solve on this handle has needed
-    std::vector<int> pcg_hist;            // PCG iterations of outer iteration k in the previous solve on this handle: the
-                                          // reference solves a slightly grown problem from a nearby start call after
-                                          // call (sfm.py:59-71), and the counts repeat; with a record the speculative
-                                          // batch is that count (+1 launch for the fused update), without the spare
-    int64_t hist_C = 0, hist_P = 0, hist_N = 0;   // the problem pcg_hist was recorded on
-    unsigned long long hist_sig = 0;         // ... and its content: problem generation + a checksum of the start vector
-    unsigned long long problem_gen = 0;      // raised by every sfmba_set_problem whose arrays differ from the previous ones
-    bool solved = false;
-    bool transport_dropped = false;          // sfmba_set_problem tore down an active transport: the next compute call
-                                             // fails until one is set up again (or single-rank use is acknowledged)
-    std::vector<const void*> lds_ready;      // kernels already opted in to 160 KiB dynamic LDS
-    int last_pcg_iters = 0;
-
-    double *x = nullptr, *x_new = nullptr;   // current / trial parameter vectors (alias xa/xb)
-    double *tab = nullptr, *tab_new = nullptr;
-    double *rec = nullptr, *rec_new = nullptr;   // point records of x / x_new (swapped together with them)
-    // gradient, column scale and D^2 g of the ACCEPTED point (alias g / si / sg or g2 / si2 / sg2) and the set a
-    // speculative k_update_scale fills for the trial point; swapped where x / tab / rec are, on acceptance only
-    double *g_cur = nullptr, *si_cur = nullptr, *sg_cur = nullptr;
-    double *g_new = nullptr, *si_new = nullptr, *sg_new = nullptr;
-
-    double* acc() const { return arena; }    // product of the implicit Schur complement / reduced rhs term (6C)
-    double* sd() const { return arena + 6 * C; }       // diagonal blocks of W Vinv W^T (Schur-diagonal preconditioner)
-    double* Ugc() const { return arena + 27 * C; }
-    double* scal() const { return arena + 54 * C; }
-    int pcg_L = 0;                           // launches (sweep+update pairs) since pcg_start
-    int red_bc = 1, red_grid = 2;            // block split of k_update_scale's reduction (cameras | points)
-    int scale_pts = 1;                       // points per thread of k_update_scale
-    double* partB() const { return part.as<double>() + (size_t)kPartRows * kNQ; }
-    bool pending_scale_sums = false;         // k_update_scale ran, its final sums ride with the next k_jdot
-    // sfmba_reprojection_stats: a parameter vector, camera table and result arrays of its own (grow-only), so that the
-    // solver's buffers -- x, tab, rec, r, J, the normal blocks -- are as the last solve left them after a statistics call
-    struct Stats {
-        DevBuf x, tab;                       // the call's parameter vector and its camera table
-        DevBuf ed, keep, keep_final;         // [ld] err | depth pairs; [ld] own test; [ld] own test and point kept
-        DevBuf pt_views, pt_d, pt_keep;      // [P]; [4][P] max err, sum err^2, min depth, angle; [P]
-        DevBuf cam_i, cam_d;                 // [2][C] views, behind; [2][C] sum err, max err
-        DevBuf part, sum;                    // [point workgroups][kStatsPart]; [kStatsPart]
-        DevBuf perm, cam_ptr, hist, cnt;     // camera-major permutation of ALL observations, built at the first call of a problem
-        unsigned long long perm_gen = 0;     // ... for the problem of this generation and size (0: none)
-        int64_t perm_N = -1, perm_C = -1;
-        PinnedBuf host;                      // staging of the per-observation downloads
-        // the masks of sfmba_triangulate / sfmba_resect (calls on a handle are serialised: one pair serves both)
-        DevBuf use;                          // [ld] obs_use in stored order
-        PinnedBuf mask_host;                 // staging of obs_use, of the select mask and of the OK counts
-    } stats;
-    // sfmba_triangulate: works on stats.x / stats.tab (the parameter vector and camera table of a call outside the
-    // solver), stats.use and on result arrays of its own
-    struct Tri {
-        DevBuf select;                       // [P]
-        DevBuf X, ints, dbl, ok_part;        // [P][3]; [3][P] status, views, iters; [2][P] rms err, angle; [workgroups]
-    } tri;
-    // sfmba_resect: works on stats.x (the parameter vector of a call outside the solver), the camera-major permutation
-    // of the statistics call, stats.use and on result arrays of its own
-    struct Resect {
-        DevBuf select;                       // [C]
-        DevBuf cam, ints, rms;               // [C][6]; [4][C] status, views, iters, ok; [C]
-    } resect;
-    // sfmba_fundamental_ransac / sfmba_recover_pose: a batch of edges that has nothing to do with the problem; every
-    // buffer is the two calls' own
-    struct TwoView {
-        DevBuf pairs, uptr, samples, E;      // [M_used][4] x1 y1 x2 y2; [n_edges + 1]; [n_edges][H][8]; [n_edges][9]
-        DevBuf slots, hyp;                   // [n_edges][slices][kTwoViewSlot]; [n_edges][H]
-        DevBuf F, ints, mask;                // [2][n_edges][9] F, F_refit; [n_edges][4]; [M_used]
-        DevBuf Rt, err, pose_ints, X, ang;   // [n_edges][12]; [n_edges]; [n_edges][6]; [M_used][3]; [M_used]
-        PinnedBuf in_host, out_host;         // staging of the packed batch; of the results
-        std::vector<int64_t> pos;            // used pair -> stored pair, when the call has a pair_use mask
-    } twoview;
-    // sfmba_resect_ransac: works on stats.x, the camera-major permutation of the statistics call and stats.use as
-    // sfmba_resect does, on sfmba_resect's result arrays (k_resect runs last) and on buffers of its own
-    struct Pnp {
-        DevBuf select, ok, mask;             // [C] the caller's select mask; [C] RANSAC succeeded; [ld] inlier mask, stored order
-        DevBuf corr, cpos, cn;               // [N][5] packed X Y Z u v per camera; [N] their stored positions; [C] their number
-        DevBuf samples, slots, hyp;          // [C][H][3]; [C][slices][kPnpSlot]; [C][H]
-        DevBuf pose, ints;                   // [C][6] best hypothesis; [C][6] status, views, inliers, best h, best solution, success
-        PinnedBuf host;                      // staging of the results
-    } pnp;
-    // sfmba_set_descriptors / sfmba_match_descriptors: the descriptor set in the form(s) the kernels read and the
-    // buffers of a batch of edges; nothing of it is shared with the problem
-    struct Match {
-        DevBuf raw, flag;                    // the caller's (N, dim) array as given; the verdict of k_match_check
-        DevBuf rows[2], norms[2];            // [form A, form B]: converted, padded rows; squared norms (fp32 / fp64)
-        bool have[2] = {false, false};
-        int row_bytes[2] = {0, 0}, n_chunk[2] = {1, 1};
-        DevBuf edges, wgs, idx, dist, good;  // [n_edges] MatchEdge; [workgroups] int2; [Q][2]; [Q][2]; [Q]
-        std::vector<int64_t> img_ptr;        // n_images + 1
-        std::vector<unsigned char> good_host;
-        int dim = 0, dtype = 0, form = 0;    // form: 0 no set, 1 A, 2 B (what the set qualifies for)
-    } match;
-    // sfmba_build_tracks / sfmba_get_tracks: the union-find forest, the component and track tables and the results of
-    // the last build; nothing of it is shared with the problem or with the descriptor set
-    struct Tracks {
-        DevBuf img_ptr, pairs;               // [n_images + 1] int; [Mu] int2 global feature ids
-        DevBuf parent, size, img, feat_track;        // [N] each (size: the component's number at a root after the first scan)
-        DevBuf members, cursor, comp_off;    // [members] feature ids by component; [components]; [components + 1]
-        DevBuf verdict, kept_len, track_id, track_off;       // [components] each
-        DevBuf track_ptr, track_feat, track_image;   // the CSR: [components + 1]; [members]; [members]
-        DevBuf sums, tot;                    // [scan workgroups][2]; [kTrackTotSlots]
-        bool built = false;
-        int64_t n_tracks = 0, T = 0;
-    } tracks;
-};
-
-namespace {
+namespace sfmba {
+constexpr size_t kLdsBytes = 160 * 1024;       // gfx950: 160 KiB LDS per workgroup
+const size_t kLdsDynMax = kLdsBytes - 2048;     // dynamic part; every kernel here has <= 2 KiB static LDS (k_backsub: 1280 B)
 
 int fail(sfmba_handle* h, int code, const char* fmt, ...) {
     char buf[512];
@@ -468,38 +105,10 @@ int fail(sfmba_handle* h, int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIPCHK(h, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e_ = (call);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return fail(h, e_ == hipErrorOutOfMemory ? -4 : -3, "%s failed: %s (%s:%d)", #call,  \
-                        hipGetErrorString(e_), __FILE__, __LINE__);                             \
-    } while (0)
-
-// after every kernel launch: count it (sfmba_get_counters) and pick up a launch failure
-#define LAUNCHED(h)                            \
-    do {                                       \
-        ++(h)->n_launches;                     \
-        HIPCHK(h, hipGetLastError());          \
-    } while (0)
-
-#define CHK(expr)                  \
-    do {                           \
-        int rc_ = (expr);          \
-        if (rc_ != 0) return rc_;  \
-    } while (0)
-
-// every buffer of the list at (at least) its size; 0: a form that is not taken needs no buffer
-struct SizedBuf { DevBuf* buf; size_t bytes; };
 int ensure_all(sfmba_handle* h, std::initializer_list<SizedBuf> sized) {
     for (const auto& b : sized)
         if (b.bytes) HIPCHK(h, b.buf->ensure(b.bytes));
     return 0;
-}
-
-// device -> host on the handle's stream; an array the caller did not ask for (null) is left out
-hipError_t download(sfmba_handle* h, void* dst, const void* src, size_t bytes) {
-    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
 }
 
 int enter(sfmba_handle* h) {
@@ -509,11 +118,157 @@ int enter(sfmba_handle* h) {
     return 0;
 }
 
+int opt_in_lds(sfmba_handle* h, const void* kernel, size_t bytes) {
+    if (std::find(h->lds_ready.begin(), h->lds_ready.end(), kernel) != h->lds_ready.end()) return 0;
+    HIPCHK(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    h->lds_ready.push_back(kernel);
+    return 0;
+}
+
+int launch_k_cam_table(sfmba_handle* h, const double* x, double* tab) {
+    hipLaunchKernelGGL(k_cam_table, dim3((unsigned)((h->C + 255) / 256)), dim3(256), 0, h->stream, x, (int)h->C, tab);
+    LAUNCHED(h);
+    return 0;
+}
+// the first two launches of the counting sort by camera (see k_cam_hist): sfmba_set_problem's and the statistics' own
+int launch_k_cam_hist(sfmba_handle* h, const unsigned char* fixed, int B, int per_slice, int* hist) {
+    const size_t lds = sizeof(int) * (size_t)h->C;
+    CHK(set_lds(h, k_cam_hist, lds));
+    hipLaunchKernelGGL(k_cam_hist, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(), fixed, (int)h->N, (int)h->C,
+                       per_slice, hist);
+    LAUNCHED(h);
+    return 0;
+}
+int launch_k_cam_offsets(sfmba_handle* h, const int* hist, const int* cam_ptr, int B, int* off) {
+    hipLaunchKernelGGL(k_cam_offsets, dim3((unsigned)((h->C + 255) / 256)), dim3(256), 0, h->stream, hist, cam_ptr, B, (int)h->C, off);
+    LAUNCHED(h);
+    return 0;
+}
+
+// `reps` back-to-back calls of `launch` on the handle's stream between two events -> average microseconds of one
+int time_reps(sfmba_handle* h, int32_t reps, double* avg_us, const std::function<int()>& launch) {
+    EventPair ev;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    CHK(ev.start(h, true));
+    for (int k = 0; k < reps; ++k) CHK(launch());
+    CHK(ev.stop(h));
+    HIPCHK(h, hipEventSynchronize(ev.b));
+    CHK(ev.read(h, avg_us));
+    *avg_us /= reps;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// Host/device hand-off: poll the stream instead of sleeping in hipStreamSynchronize.  The solver
+// hands control back to the host two to three times per outer iteration for ~30 us of GPU work each;
+// a blocking wait that parks the thread costs up to a millisecond per wake-up on an idle host.
+static void report_stall(const sfmba_handle* h, const char* where, double seconds) {   // trace_stalls: waits longer than 2 ms
+    if (h->dbg.trace_stalls && seconds > 2e-3) fprintf(stderr, "sfmba: waited %.2f ms in %s\n", 1e3 * seconds, where);
+}
+// `ev` null: the handle's stream; else one event of the copy stream
+int wait_stream(sfmba_handle* h, hipEvent_t ev) {
+    const char* what = ev ? "hipEventQuery" : "hipStreamQuery";
+    const double t0 = now_s();
+    for (;;) {
+        const hipError_t e = ev ? hipEventQuery(ev) : hipStreamQuery(h->stream);
+        if (e == hipSuccess) { report_stall(h, ev ? "wait_event" : "wait_stream", now_s() - t0); return 0; }
+        if (e != hipErrorNotReady) return fail(h, -3, "%s failed: %s", what, hipGetErrorString(e));
+        if (now_s() - t0 > 0.05) break;          // long wait: stop burning the core
+    }
+    if (ev) HIPCHK(h, hipEventSynchronize(ev));
+    else HIPCHK(h, hipStreamSynchronize(h->stream));
+    report_stall(h, ev ? "wait_event (blocking)" : "wait_stream (blocking)", now_s() - t0);
+    return 0;
+}
+
+// x crosses PCIe through a pinned staging buffer (an async copy from pageable memory is staged by the
+// runtime anyway, synchronously and in small pieces)
+static int ensure_h_x(sfmba_handle* h) {
+    const size_t need = (size_t)std::max<int64_t>(h->n, 2 * h->N);      // also stages the residual vector
+    if (h->h_x && h->h_x_doubles >= need) return 0;
+    if (h->h_x) { (void)hipHostFree(h->h_x); h->h_x = nullptr; h->h_x_doubles = 0; }
+    HIPCHK(h, hipHostMalloc((void**)&h->h_x, sizeof(double) * need, hipHostMallocDefault));
+    h->h_x_doubles = need;
+    return 0;
+}
+
+// pageable <-> pinned copy of a parameter vector: a few host threads from 1 MB on (one thread moves 2.4 MB in 85-115 us,
+// which was 9 % of a solve at 306k parameters).  `chunk_done(k, offset, bytes)` (optional) is called on the calling
+// thread, in chunk order, as soon as chunk k has arrived: the upload enqueues that chunk's DMA while the others are
+// still being copied.
+template <class Fn>
+static void staging_copy(sfmba_handle* h, void* dst, const void* src, size_t bytes, Fn chunk_done) {
+    const int parts = (int)std::min<size_t>(4, bytes >> 19);
+    if (parts <= 1) { memcpy(dst, src, bytes); chunk_done(0, (size_t)0, bytes); return; }
+    const size_t per = ((bytes + parts - 1) / parts + 63) & ~(size_t)63;
+    std::atomic<int> done[8];
+    for (auto& d : done) d.store(0, std::memory_order_relaxed);
+    h->pool.run(parts, [&](int t) {
+        const size_t b = std::min(bytes, (size_t)t * per), e = std::min(bytes, b + per);
+        if (e > b) memcpy(static_cast<char*>(dst) + b, static_cast<const char*>(src) + b, e - b);
+        if (t != 0) { done[t].store(1, std::memory_order_release); return; }
+        chunk_done(0, b, e - b);
+        for (int k = 1; k < parts; ++k) {
+            while (done[k].load(std::memory_order_acquire) == 0) { }
+            const size_t bk = std::min(bytes, (size_t)k * per), ek = std::min(bytes, bk + per);
+            chunk_done(k, bk, ek - bk);
+        }
+    });
+}
+static void staging_copy(sfmba_handle* h, void* dst, const void* src, size_t bytes) {
+    staging_copy(h, dst, src, bytes, [](int, size_t, size_t) {});
+}
+
+// `dst` null: the solver's current parameter vector h->x; else a buffer of the caller's (sfmba_reprojection_stats), which
+// leaves h->x and the origin of the fp32 operands alone
+int upload_x(sfmba_handle* h, const double* x_host, double* dst) {
+    CHK(ensure_h_x(h));
+    if (h->forms.mixed && !dst) {                    // origin of the fp32 operands: mean of (a sample of) this vector's points
+        const double* pts = x_host + 6 * h->C;
+        const int64_t stride = std::max<int64_t>(1, h->P / 1024);
+        double sx = 0.0, sy = 0.0, sz = 0.0;
+        int64_t cnt = 0;
+        for (int64_t q = 0; q < h->P; q += stride, ++cnt) { sx += pts[3 * q]; sy += pts[3 * q + 1]; sz += pts[3 * q + 2]; }
+        h->origin = Origin{sx / (double)cnt, sy / (double)cnt, sz / (double)cnt};
+        if (!std::isfinite(h->origin.x + h->origin.y + h->origin.z)) h->origin = Origin{0.0, 0.0, 0.0};
+    }
+    // The staging buffer's readers and writers on the stream: every call waits for its own before it returns (the solve
+    // for a post behind its upload and for the result's copy); synchronising an idle stream costs about 1 us and is kept.
+    // The early result copy of a solve runs on the copy stream: only a solve that failed leaves one behind.
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->result_in_flight && h->copy_stream) HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    h->result_in_flight = false;
+    const double t0 = now_s();
+    hipError_t err = hipSuccess;
+    staging_copy(h, h->h_x, x_host, sizeof(double) * h->n, [&](int, size_t off, size_t bytes) {
+        if (bytes == 0 || err != hipSuccess) return;
+        err = hipMemcpyAsync(reinterpret_cast<char*>(dst ? dst : h->x) + off, reinterpret_cast<const char*>(h->h_x) + off, bytes,
+                             hipMemcpyHostToDevice, h->stream);
+    });
+    HIPCHK(h, err);
+    if (h->dbg.trace_timing) fprintf(stderr, "sfmba: upload_x  staging copy + enqueue %.1f us\n", 1e6 * (now_s() - t0));
+    return 0;
+}
+
+// every compute entry: is the handle ready, and which forms does this call run (the solve stage of the decision)
+int begin_compute(sfmba_handle* h, const void* x) {
+    if (!h->have_problem) return fail(h, -1, "sfmba_set_problem has not been called");
+    if (h->transport_dropped)
+        return fail(h, -1, "sfmba_set_problem removed this handle's multi-rank transport (direct link / RCCL communicator / "
+                           "callback): set it up again for the new problem, or call sfmba_set_exchange(h, NULL, 0, NULL, NULL, 0) "
+                           "to solve the shard on its own");
+    if (!x) return fail(h, -1, "x is NULL");
+    decide_solve_forms(h);
+    return 0;
+}
+}  // namespace sfmba
+
+namespace {
+
 // All-reduce `count` doubles of the exchange arena in place over the ranks, on the handle's stream:
 // natively with RCCL when a communicator is set, else through the host callback, else a no-op.
 void p2p_release(sfmba_handle* h);
 void p2p_close_peers(sfmba_handle* h);
-bool multi_rank(const sfmba_handle* h) { return h->p2p.ready || h->comm != nullptr || h->ar_fn != nullptr; }
 const unsigned* p2p_error_word(const sfmba_handle* h) { return h->p2p.ready ? h->p2p.words + 1 : nullptr; }
 
 constexpr long long kP2pFirstTicks = 6000000000ll, kP2pSteadyTicks = 3000000000ll;      // 60 s, 30 s at 100 MHz
@@ -711,18 +466,6 @@ int exchange(sfmba_handle* h, double* ptr, int64_t count, int op, const int* can
     return 0;
 }
 
-// Dynamic LDS above 64 KiB needs the per-kernel opt-in; it is set ONCE per kernel (to the full
-// 160 KiB) because hipFuncSetAttribute costs tens of microseconds to a millisecond per call.
-template <class Kern>
-int set_lds(sfmba_handle* h, Kern k, size_t bytes) {
-    if (bytes <= 64 * 1024) return 0;
-    const void* fn = reinterpret_cast<const void*>(k);
-    if (std::find(h->lds_ready.begin(), h->lds_ready.end(), fn) != h->lds_ready.end()) return 0;
-    HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsDynMax));
-    h->lds_ready.push_back(fn);
-    return 0;
-}
-
 // inverse point blocks: an array of their own, or (record layout 2) a slot of the CURRENT parameter vector's point
 // records -- written by k_prep / k_point_prep for h->rec before every consumer of the iteration
 double* vinv_ptr(const sfmba_handle* h) { return kVinvInRec < 0 ? h->Vinv.as<double>() : h->rec + kVinvInRec; }
@@ -749,35 +492,7 @@ StepTable step_table(const sfmba_handle* h) {
     return StepTable{h->wsteps.as<int2>(), h->steps.as<int2>(), h->n_ranges};
 }
 
-int grid_1d(int64_t n, int block, int cap) {
-    int64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
-
-// Host/device hand-off: poll the stream instead of sleeping in hipStreamSynchronize.  The solver
-// hands control back to the host two to three times per outer iteration for ~30 us of GPU work each;
-// a blocking wait that parks the thread costs up to a millisecond per wake-up on an idle host.
-void report_stall(const sfmba_handle* h, const char* where, double seconds) {   // trace_stalls: waits longer than 2 ms
-    if (h->dbg.trace_stalls && seconds > 2e-3) fprintf(stderr, "sfmba: waited %.2f ms in %s\n", 1e3 * seconds, where);
-}
-
-// `ev` null: the handle's stream; else one event of the copy stream
-int wait_stream(sfmba_handle* h, hipEvent_t ev = nullptr) {
-    const char* what = ev ? "hipEventQuery" : "hipStreamQuery";
-    const double t0 = now_s();
-    for (;;) {
-        const hipError_t e = ev ? hipEventQuery(ev) : hipStreamQuery(h->stream);
-        if (e == hipSuccess) { report_stall(h, ev ? "wait_event" : "wait_stream", now_s() - t0); return 0; }
-        if (e != hipErrorNotReady) return fail(h, -3, "%s failed: %s", what, hipGetErrorString(e));
-        if (now_s() - t0 > 0.05) break;          // long wait: stop burning the core
-    }
-    if (ev) HIPCHK(h, hipEventSynchronize(ev));
-    else HIPCHK(h, hipStreamSynchronize(h->stream));
-    report_stall(h, ev ? "wait_event (blocking)" : "wait_stream (blocking)", now_s() - t0);
-    return 0;
-}
+double* partB(const sfmba_handle* h) { return h->part.as<double>() + (size_t)kPartRows * kNQ; }
 
 // The hand-off of an outer iteration: the device posts scalars + PCG control block into the mailbox and
 // raises its sequence number (post_mailbox); the host polls that word and nothing else: every
@@ -834,8 +549,7 @@ int launch_cam_table(sfmba_handle* h, const double* x, double* tab, double* rec,
         LAUNCHED(h);
         return 0;
     }
-    hipLaunchKernelGGL(k_cam_table, dim3((h->C + 255) / 256), dim3(256), 0, h->stream, x, (int)h->C, tab);
-    LAUNCHED(h);
+    CHK(launch_k_cam_table(h, x, tab));
     hipLaunchKernelGGL(k_fill_rec, dim3((unsigned)((3 * h->P + 255) / 256)), dim3(256), 0, h->stream, x + 6 * h->C, (int)h->P, rec);
     LAUNCHED(h);
     return 0;
@@ -1160,7 +874,7 @@ int launch_jdot(sfmba_handle* h, int* nparts) {
     auto run = [&](auto kern, size_t lds) -> int {
         CHK(set_lds(h, kern, lds));
         hipLaunchKernelGGL(kern, dim3(launch_grid), dim3(kSweepThreads), lds, h->stream, obs_arrays(h), sgc, sgp,
-                           (int)h->N, (int)h->C, h->t1.as<double>(), h->partB(), pb, rc);
+                           (int)h->N, (int)h->C, h->t1.as<double>(), partB(h), pb, rc);
         LAUNCHED(h);
         return 0;
     };
@@ -1169,7 +883,7 @@ int launch_jdot(sfmba_handle* h, int* nparts) {
         CHK(set_lds(h, k_jdot_rc, lds));
         hipLaunchKernelGGL(k_jdot_rc, dim3(launch_grid), dim3(kSweepThreads), lds, h->stream, (const int*)h->cam_idx.as<int>(),
                            (const int*)h->pt_idx.as<int>(), rc.camtab, rc.pts, h->K, sgc, sgp, (int)h->N, (int)h->C,
-                           h->t1.as<double>(), h->partB(), pb);
+                           h->t1.as<double>(), partB(h), pb);
         LAUNCHED(h);
     } else
     CHK(h->forms.jfree ? run(k_jdot<false, true>, sizeof(double) * kCamRow * (size_t)h->C)
@@ -1196,7 +910,7 @@ int launch_backsub(sfmba_handle* h, int* nparts, const double* planes = nullptr)
         }
         CHK(set_lds(h, kern, lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, h->ranges.as<int2>(), h->n_ranges, obs_arrays(h),
-                           step_planes, dc, vinv_ptr(h), h->gp.as<double>(), h->t1.as<double>(), dp, h->partB(),
+                           step_planes, dc, vinv_ptr(h), h->gp.as<double>(), h->t1.as<double>(), dp, partB(h),
                            (int)h->C, in_lds ? ctrl2 : (const PcgCtrl*)nullptr, in_lds ? h->pcg_L : 0, h->g_cur, h->si_cur, h->sg_cur, rc,
                            in_lds && h->pcg_a_owed && !planes ? FinalUpdate{h->pcg_part.as<double>(), h->vecs.as<double>(), h->ctrl.as<PcgCtrl>(), h->pcg_L - 1}
                                                    : FinalUpdate{});
@@ -1209,7 +923,7 @@ int launch_backsub(sfmba_handle* h, int* nparts, const double* planes = nullptr)
         hipLaunchKernelGGL(k_backsub_rc, dim3(grid), dim3(kSweepThreads), lds, h->stream, (const int2*)h->ranges.as<int2>(), h->n_ranges,
                            (const int*)h->cam_idx.as<int>(), (const int*)h->pt_idx.as<int>(), (const int*)h->pt_ptr.as<int>(),
                            rc.camtab, rc.pts, h->K, step_planes, dc, (const double*)vinv_ptr(h),
-                           (const double*)h->gp.as<double>(), (const double*)h->t1.as<double>(), dp, h->partB(), (int)h->C, ctrl2, h->pcg_L,
+                           (const double*)h->gp.as<double>(), (const double*)h->t1.as<double>(), dp, partB(h), (int)h->C, ctrl2, h->pcg_L,
                            (const double*)h->g_cur, (const double*)h->si_cur, (const double*)h->sg_cur,
                            h->pcg_a_owed && !planes ? FinalUpdate{h->pcg_part.as<double>(), h->vecs.as<double>(), h->ctrl.as<PcgCtrl>(), h->pcg_L - 1}
                                                     : FinalUpdate{});
@@ -1249,7 +963,7 @@ int launch_update_scale(sfmba_handle* h, int first, bool defer = false, bool spe
 // Final sums of k_backsub's partial rows (half B, kBacksubCols wide): G12, G22 -> slots 2, 3; q5..q8 of the
 // point slice -> 4..7 (the run the tail of the linear phase reduces over ranks); q5..q8 of the camera slice -> 21..24.
 Piggyback backsub_rider(sfmba_handle* h, int nparts) {
-    Piggyback pb{h->partB(), h->scal(), FinishJob{}, 1, kBacksubCols, 0};
+    Piggyback pb{partB(h), h->scal(), FinishJob{}, 1, kBacksubCols, 0};
     pb.job.row0[0] = 0; pb.job.nrows[0] = nparts;
     for (int k = 0; k < kFinishCols; ++k) { pb.job.slot[0][k] = -1; pb.job.slot[1][k] = -1; }
     for (int k = 0; k < 6; ++k) pb.job.slot[0][k] = 2 + k;
@@ -1281,75 +995,6 @@ int fetch_scalars(sfmba_handle* h) {
     return 0;
 }
 
-// x crosses PCIe through a pinned staging buffer (an async copy from pageable memory is staged by the
-// runtime anyway, synchronously and in small pieces)
-int ensure_h_x(sfmba_handle* h) {
-    const size_t need = (size_t)std::max<int64_t>(h->n, 2 * h->N);      // also stages the residual vector
-    if (h->h_x && h->h_x_doubles >= need) return 0;
-    if (h->h_x) { (void)hipHostFree(h->h_x); h->h_x = nullptr; h->h_x_doubles = 0; }
-    HIPCHK(h, hipHostMalloc((void**)&h->h_x, sizeof(double) * need, hipHostMallocDefault));
-    h->h_x_doubles = need;
-    return 0;
-}
-
-// pageable <-> pinned copy of a parameter vector: a few host threads from 1 MB on (one thread moves 2.4 MB in 85-115 us,
-// which was 9 % of a solve at 306k parameters).  `chunk_done(k, offset, bytes)` (optional) is called on the calling
-// thread, in chunk order, as soon as chunk k has arrived: the upload enqueues that chunk's DMA while the others are
-// still being copied.
-template <class Fn>
-void staging_copy(sfmba_handle* h, void* dst, const void* src, size_t bytes, Fn chunk_done) {
-    const int parts = (int)std::min<size_t>(4, bytes >> 19);
-    if (parts <= 1) { memcpy(dst, src, bytes); chunk_done(0, (size_t)0, bytes); return; }
-    const size_t per = ((bytes + parts - 1) / parts + 63) & ~(size_t)63;
-    std::atomic<int> done[8];
-    for (auto& d : done) d.store(0, std::memory_order_relaxed);
-    h->pool.run(parts, [&](int t) {
-        const size_t b = std::min(bytes, (size_t)t * per), e = std::min(bytes, b + per);
-        if (e > b) memcpy(static_cast<char*>(dst) + b, static_cast<const char*>(src) + b, e - b);
-        if (t != 0) { done[t].store(1, std::memory_order_release); return; }
-        chunk_done(0, b, e - b);
-        for (int k = 1; k < parts; ++k) {
-            while (done[k].load(std::memory_order_acquire) == 0) { }
-            const size_t bk = std::min(bytes, (size_t)k * per), ek = std::min(bytes, bk + per);
-            chunk_done(k, bk, ek - bk);
-        }
-    });
-}
-void staging_copy(sfmba_handle* h, void* dst, const void* src, size_t bytes) {
-    staging_copy(h, dst, src, bytes, [](int, size_t, size_t) {});
-}
-
-// `dst` null: the solver's current parameter vector h->x; else a buffer of the caller's (sfmba_reprojection_stats), which
-// leaves h->x and the origin of the fp32 operands alone
-int upload_x(sfmba_handle* h, const double* x_host, double* dst = nullptr) {
-    CHK(ensure_h_x(h));
-    if (h->forms.mixed && !dst) {                    // origin of the fp32 operands: mean of (a sample of) this vector's points
-        const double* pts = x_host + 6 * h->C;
-        const int64_t stride = std::max<int64_t>(1, h->P / 1024);
-        double sx = 0.0, sy = 0.0, sz = 0.0;
-        int64_t cnt = 0;
-        for (int64_t q = 0; q < h->P; q += stride, ++cnt) { sx += pts[3 * q]; sy += pts[3 * q + 1]; sz += pts[3 * q + 2]; }
-        h->origin = Origin{sx / (double)cnt, sy / (double)cnt, sz / (double)cnt};
-        if (!std::isfinite(h->origin.x + h->origin.y + h->origin.z)) h->origin = Origin{0.0, 0.0, 0.0};
-    }
-    // The staging buffer's readers and writers on the stream: every call waits for its own before it returns (the solve
-    // for a post behind its upload and for the result's copy); synchronising an idle stream costs about 1 us and is kept.
-    // The early result copy of a solve runs on the copy stream: only a solve that failed leaves one behind.
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->result_in_flight && h->copy_stream) HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-    h->result_in_flight = false;
-    const double t0 = now_s();
-    hipError_t err = hipSuccess;
-    staging_copy(h, h->h_x, x_host, sizeof(double) * h->n, [&](int, size_t off, size_t bytes) {
-        if (bytes == 0 || err != hipSuccess) return;
-        err = hipMemcpyAsync(reinterpret_cast<char*>(dst ? dst : h->x) + off, reinterpret_cast<const char*>(h->h_x) + off, bytes,
-                             hipMemcpyHostToDevice, h->stream);
-    });
-    HIPCHK(h, err);
-    if (h->dbg.trace_timing) fprintf(stderr, "sfmba: upload_x  staging copy + enqueue %.1f us\n", 1e6 * (now_s() - t0));
-    return 0;
-}
-
 // residual vector of the current buffer set into the caller's array (2N doubles, caller's observation
 // order), through the pinned staging buffer
 int download_residuals(sfmba_handle* h, double* r_out) {
@@ -1361,22 +1006,10 @@ int download_residuals(sfmba_handle* h, double* r_out) {
     if (!h->f32 && !h->permuted) { memcpy(r_out, h->h_x, bytes); return 0; }
     const float* sf = reinterpret_cast<const float*>(h->h_x);
     for (int64_t k = 0; k < h->N; ++k) {
-        const int64_t d = h->permuted ? h->tb.order[k] : k;
+        const size_t d = caller_position(h, (size_t)k);
         r_out[2 * d] = h->f32 ? (double)sf[2 * k] : h->h_x[2 * k];
         r_out[2 * d + 1] = h->f32 ? (double)sf[2 * k + 1] : h->h_x[2 * k + 1];
     }
-    return 0;
-}
-
-// every compute entry: is the handle ready, and which forms does this call run (the solve stage of the decision)
-int begin_compute(sfmba_handle* h, const void* x) {
-    if (!h->have_problem) return fail(h, -1, "sfmba_set_problem has not been called");
-    if (h->transport_dropped)
-        return fail(h, -1, "sfmba_set_problem removed this handle's multi-rank transport (direct link / RCCL communicator / "
-                           "callback): set it up again for the new problem, or call sfmba_set_exchange(h, NULL, 0, NULL, NULL, 0) "
-                           "to solve the shard on its own");
-    if (!x) return fail(h, -1, "x is NULL");
-    decide_solve_forms(h);
     return 0;
 }
 
@@ -1553,11 +1186,7 @@ void print_iter(sfmba_handle* h, int64_t it, int64_t nfev, double cost, bool hav
 
 }  // namespace
 
-// ==================================================================================================
-// C-ABI
-// ==================================================================================================
-
-extern "C" {
+// ==== C-ABI ===============================================================================================================
 
 void sfmba_default_options(sfmba_options* o) {
     if (!o) return;
@@ -2158,14 +1787,9 @@ int ProblemBuild::enqueue_camera_major() {
         fixed_dev = h->fixed_dev.as<unsigned char>();
     }
     const size_t lds = sizeof(int) * (size_t)C;
-    CHK(set_lds(h, k_cam_hist, lds));
     CHK(set_lds(h, k_cam_scatter, lds));
-    hipLaunchKernelGGL(k_cam_hist, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(), fixed_dev, (int)N, (int)C,
-                       per_slice, h->sort_hist.as<int>());
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_cam_offsets, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->sort_hist.as<int>(),
-                       (const int*)h->cam_ptr_dev.as<int>(), B, (int)C, sort_off);
-    LAUNCHED(h);
+    CHK(launch_k_cam_hist(h, fixed_dev, B, per_slice, h->sort_hist.as<int>()));
+    CHK(launch_k_cam_offsets(h, h->sort_hist.as<int>(), h->cam_ptr_dev.as<int>(), B, sort_off));
     hipLaunchKernelGGL(k_cam_scatter, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(), fixed_dev,
                        (const int*)h->pt_idx.as<int>(), (const double*)h->uv.as<double>(), f32 ? 1 : 0, (int)N, (int)C, per_slice,
                        key_bits, (const int*)sort_off, h->cm_pt.as<int>(), h->cm_uv.as<double>());
@@ -2248,1209 +1872,6 @@ int launch_point_prep(sfmba_handle* h, const double* si_pts, const double* e_in,
     return 0;
 }
 }  // namespace
-
-namespace {
-// ---- reprojection statistics (sfmba_reprojection_stats; kernels: consumer_kernels.hpp, "Reprojection statistics") ------
-int stats_allocate(sfmba_handle* h, int* pt_blocks) {
-    auto& s = h->stats;
-    const size_t ldz = (size_t)h->ld, P = (size_t)h->P, C = (size_t)h->C;
-    *pt_blocks = (int)std::max<size_t>(1, (P + kStatsPtThreads - 1) / kStatsPtThreads);
-    return ensure_all(h, {
-        {&s.x, sizeof(double) * (size_t)h->n}, {&s.tab, sizeof(double) * cam_table_doubles((int)C)},
-        {&s.ed, sizeof(double) * 2 * ldz}, {&s.keep, ldz}, {&s.keep_final, ldz},
-        {&s.pt_views, sizeof(int) * P}, {&s.pt_d, sizeof(double) * 4 * P}, {&s.pt_keep, P},
-        {&s.cam_i, sizeof(int) * 2 * C}, {&s.cam_d, sizeof(double) * 2 * C},
-        {&s.part, sizeof(double) * kStatsPart * (size_t)*pt_blocks}, {&s.sum, sizeof(double) * kStatsPart}});
-}
-
-// x into the call's own buffer, and its camera table
-int stats_prepare(sfmba_handle* h, const double* x) {
-    auto& s = h->stats;
-    CHK(upload_x(h, x, s.x.as<double>()));
-    hipLaunchKernelGGL(k_cam_table, dim3((unsigned)((h->C + 255) / 256)), dim3(256), 0, h->stream, (const double*)s.x.as<double>(),
-                       (int)h->C, s.tab.as<double>());
-    LAUNCHED(h);
-    return 0;
-}
-
-// the per-observation sweep: grid, workgroup and LDS of the residual-only sweep (launch_resjac)
-int launch_obs_stats(sfmba_handle* h, const StatsFilter& flt) {
-    auto& s = h->stats;
-    const bool lds_tab = h->forms.lds_tab;
-    const int grid = grid_1d(h->N, kSweepThreads, h->n_cu);
-    const size_t lds = lds_tab ? (size_t)h->C * kCamRow * sizeof(double) : sizeof(double) * kRowSlabDoubles * kWavesPerSweepBlock;
-    auto kern = lds_tab ? (h->f32 ? k_obs_stats<true, true> : k_obs_stats<true, false>)
-                        : (h->f32 ? k_obs_stats<false, true> : k_obs_stats<false, false>);
-    CHK(set_lds(h, kern, lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kSweepThreads), lds, h->stream, (const double*)s.tab.as<double>(),
-                       (const double*)(s.x.as<double>() + 6 * h->C), (const int*)h->cam_idx.as<int>(),
-                       (const int*)h->pt_idx.as<int>(), (const double*)h->uv.as<double>(), s.ed.as<double>(),
-                       s.keep.as<unsigned char>(), (int)h->N, (int)h->C, h->K, flt.max_err, flt.min_depth);
-    LAUNCHED(h);
-    return 0;
-}
-
-int launch_point_stats(sfmba_handle* h, const StatsFilter& flt, int pt_blocks) {
-    auto& s = h->stats;
-    double* d = s.pt_d.as<double>();
-    const size_t P = (size_t)h->P;
-    const PointStatsOut out{s.pt_views.as<int>(), d, d + P, d + 2 * P, d + 3 * P, s.pt_keep.as<unsigned char>()};
-    hipLaunchKernelGGL(k_point_stats, dim3(pt_blocks), dim3(kStatsPtThreads), 0, h->stream, (const int*)h->pt_ptr.as<int>(),
-                       (const int*)h->cam_idx.as<int>(), (const double*)s.tab.as<double>(),
-                       (const double*)(s.x.as<double>() + 6 * h->C), (const double*)s.ed.as<double>(),
-                       (const unsigned char*)s.keep.as<unsigned char>(), (int)h->P, flt, out,
-                       s.keep_final.as<unsigned char>(), s.part.as<double>());
-    LAUNCHED(h);
-    return 0;
-}
-
-int launch_stats_summary(sfmba_handle* h, int pt_blocks) {
-    auto& s = h->stats;
-    hipLaunchKernelGGL(k_stats_summary, dim3(1), dim3(256), 0, h->stream, (const double*)s.part.as<double>(), pt_blocks,
-                       s.sum.as<double>());
-    LAUNCHED(h);
-    return 0;
-}
-
-// The camera-major permutation of all observations of the current problem: built at the first call that asks for
-// per-camera figures and kept until the problem's arrays change (the solver's own lists leave out cameras held still
-// and, sorted on the device, come without the permutation).
-int stats_cam_perm(sfmba_handle* h) {
-    auto& s = h->stats;
-    const int64_t N = h->N, C = h->C;
-    if (s.perm_gen != 0 && s.perm_gen == h->problem_gen && s.perm_N == N && s.perm_C == C) return 0;
-    const size_t lds = sizeof(int) * (size_t)C;
-    if (lds > kLdsDynMax)
-        return fail(h, -1, "per-camera statistics sort with one LDS counter per camera: at most %d cameras", (int)(kLdsDynMax / sizeof(int)));
-    const int B = (int)std::min<int64_t>(kSortSlices, (N + 63) / 64);
-    const int per_slice = (int)(((N + B - 1) / B + 63) / 64 * 64);
-    int key_bits = 0;
-    while (((int64_t)1 << key_bits) < C) ++key_bits;
-    CHK(ensure_all(h, {{&s.hist, sizeof(int) * 2 * (size_t)B * (size_t)C},               // counts | offsets
-                       {&s.cnt, sizeof(int) * (size_t)C}, {&s.cam_ptr, sizeof(int) * ((size_t)C + 1)},
-                       {&s.perm, sizeof(int) * (size_t)h->ld}}));
-    int* off = s.hist.as<int>() + (size_t)B * (size_t)C;
-    const unsigned cblocks = (unsigned)((C + 255) / 256);
-    CHK(set_lds(h, k_cam_hist, lds));
-    CHK(set_lds(h, k_stats_cam_scatter, lds));
-    hipLaunchKernelGGL(k_cam_hist, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(),
-                       (const unsigned char*)nullptr, (int)N, (int)C, per_slice, s.hist.as<int>());
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_stats_cam_count, dim3(cblocks), dim3(256), 0, h->stream, (const int*)s.hist.as<int>(), B, (int)C,
-                       s.cnt.as<int>());
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_stats_cam_scan, dim3(1), dim3(1024), 0, h->stream, (const int*)s.cnt.as<int>(), (int)C, s.cam_ptr.as<int>());
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_cam_offsets, dim3(cblocks), dim3(256), 0, h->stream, (const int*)s.hist.as<int>(),
-                       (const int*)s.cam_ptr.as<int>(), B, (int)C, off);
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_stats_cam_scatter, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(), (int)N, (int)C,
-                       per_slice, key_bits, (const int*)off, s.perm.as<int>());
-    LAUNCHED(h);
-    s.perm_gen = h->problem_gen; s.perm_N = N; s.perm_C = C;
-    return 0;
-}
-
-int launch_cam_stats(sfmba_handle* h) {
-    auto& s = h->stats;
-    const size_t C = (size_t)h->C;
-    hipLaunchKernelGGL(k_cam_stats, dim3((unsigned)C), dim3(kCamThreads), 0, h->stream, (const int*)s.cam_ptr.as<int>(),
-                       (const int*)s.perm.as<int>(), (const double*)s.ed.as<double>(),
-                       (const unsigned char*)s.keep_final.as<unsigned char>(), s.cam_i.as<int>(), s.cam_d.as<double>(),
-                       s.cam_d.as<double>() + C, s.cam_i.as<int>() + C);
-    LAUNCHED(h);
-    return 0;
-}
-
-StatsFilter stats_filter(const sfmba_filter_options& o) {
-    return StatsFilter{o.max_error_px, o.min_depth, o.min_angle_deg, (int)o.min_views};
-}
-
-// `reps` back-to-back calls of `launch` on the handle's stream between two events -> average microseconds of one
-int time_reps(sfmba_handle* h, int32_t reps, double* avg_us, const std::function<int()>& launch) {
-    struct EventPair {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    HIPCHK(h, hipEventCreate(&ev.a));
-    HIPCHK(h, hipEventCreate(&ev.b));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventRecord(ev.a, h->stream));
-    for (int k = 0; k < reps; ++k) CHK(launch());
-    HIPCHK(h, hipEventRecord(ev.b, h->stream));
-    HIPCHK(h, hipEventSynchronize(ev.b));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, ev.a, ev.b));
-    *avg_us = 1e3 * (double)ms / reps;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// sfmba_time_kernel, which = 13 / 14: the per-observation sweep / the per-point reduction at x, default thresholds
-int stats_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t reps, double* avg_us) {
-    sfmba_filter_options o;
-    sfmba_default_filter_options(&o);
-    const StatsFilter flt = stats_filter(o);
-    int pt_blocks = 1;
-    CHK(stats_allocate(h, &pt_blocks));
-    CHK(stats_prepare(h, x));
-    CHK(launch_obs_stats(h, flt));                      // (the reduction's input)
-    return time_reps(h, reps, avg_us, [&] { return which == 13 ? launch_obs_stats(h, flt) : launch_point_stats(h, flt, pt_blocks); });
-}
-
-// ---- what triangulation and resection share on the host ------------------------------------------------------------------
-// The masks of a call onto the device, both through pinned staging (stats.mask_host): obs_use [N] into stored order
-// (h->tb.order: stored position -> caller's) -> stats.use, the select mask [n_sel] as it is -> select_dev; null: not
-// given.  *counts: room for n_counts ints behind them in the staging, for finish_with_ok_count.
-int stage_masks(sfmba_handle* h, const uint8_t* obs_use, const uint8_t* select, size_t n_sel, DevBuf& select_dev,
-                size_t n_counts, int** counts) {
-    auto& s = h->stats;
-    const size_t N = (size_t)h->N;
-    const size_t off_sel = (N + 63) / 64 * 64, off_ok = off_sel + (n_sel + 63) / 64 * 64;
-    HIPCHK(h, s.mask_host.ensure(off_ok + sizeof(int) * n_counts, 0));
-    unsigned char* const st = s.mask_host.as<unsigned char>();
-    if (obs_use && N) {
-        for (size_t k = 0; k < N; ++k) st[k] = obs_use[h->permuted ? (size_t)h->tb.order[k] : k] ? 1 : 0;
-        HIPCHK(h, hipMemcpyAsync(s.use.p, st, N, hipMemcpyHostToDevice, h->stream));
-    }
-    if (select && n_sel) {
-        for (size_t k = 0; k < n_sel; ++k) st[off_sel + k] = select[k] ? 1 : 0;
-        HIPCHK(h, hipMemcpyAsync(select_dev.p, st + off_sel, n_sel, hipMemcpyHostToDevice, h->stream));
-    }
-    *counts = reinterpret_cast<int*>(st + off_ok);
-    return 0;
-}
-
-// the end of such a call: the n OK counts at src (device) through `counts` (stage_masks), the stream waited for, their
-// sum -> *n_ok (null: not asked for)
-int finish_with_ok_count(sfmba_handle* h, const int* src, size_t n, int* counts, int64_t* n_ok) {
-    if (n_ok) HIPCHK(h, download(h, counts, src, sizeof(int) * n));
-    CHK(wait_stream(h));
-    if (n_ok) {
-        *n_ok = 0;
-        for (size_t k = 0; k < n; ++k) *n_ok += counts[k];
-    }
-    return 0;
-}
-
-// ---- triangulation (sfmba_triangulate; kernel: consumer_kernels.hpp, "Triangulation") ------------------------------------
-int tri_allocate(sfmba_handle* h, int* grid) {
-    auto& s = h->stats;
-    auto& t = h->tri;
-    const size_t ldz = (size_t)h->ld, P = (size_t)h->P;
-    *grid = grid_1d(h->P, kTriThreads, h->n_cu);
-    return ensure_all(h, {
-        {&s.x, sizeof(double) * (size_t)h->n}, {&s.tab, sizeof(double) * cam_table_doubles((int)h->C)},
-        {&s.use, ldz}, {&t.select, P}, {&t.X, sizeof(double) * 3 * P}, {&t.ints, sizeof(int) * 3 * P},
-        {&t.dbl, sizeof(double) * 2 * P}, {&t.ok_part, sizeof(int) * (size_t)*grid}});
-}
-
-TriOptions tri_options(const sfmba_triangulate_options& o) {
-    return TriOptions{(int)o.max_iter, (int)o.min_views, o.xtol, o.min_angle_deg, o.min_depth, o.max_error_px};
-}
-
-// the table of stats_prepare(h, x) must be in place; use / select: the masks are on the device
-int launch_triangulate(sfmba_handle* h, const TriOptions& opt, bool use, bool select, int grid) {
-    auto& s = h->stats;
-    auto& t = h->tri;
-    const size_t P = (size_t)h->P;
-    const bool lds_tab = h->forms.lds_tab;
-    const size_t lds = lds_tab ? (size_t)h->C * kCamRT * sizeof(double) : 0;
-    auto kern = lds_tab ? (h->f32 ? k_triangulate<true, true> : k_triangulate<true, false>)
-                        : (h->f32 ? k_triangulate<false, true> : k_triangulate<false, false>);
-    CHK(set_lds(h, kern, lds));
-    const TriIn in{h->pt_ptr.as<int>(), h->cam_idx.as<int>(), h->uv.as<double>(),
-                   use ? s.use.as<unsigned char>() : nullptr, select ? t.select.as<unsigned char>() : nullptr,
-                   s.x.as<double>() + 6 * h->C};
-    const TriOut out{t.X.as<double>(), t.ints.as<int>(), t.ints.as<int>() + P, t.ints.as<int>() + 2 * P,
-                     t.dbl.as<double>(), t.dbl.as<double>() + P, t.ok_part.as<int>()};
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kTriThreads), lds, h->stream, (const double*)s.tab.as<double>(), in, (int)h->P,
-                       (int)h->C, h->K, opt, out);
-    LAUNCHED(h);
-    return 0;
-}
-
-// sfmba_time_kernel, which = 15: k_triangulate at x over every point and observation, default options
-int tri_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us) {
-    sfmba_triangulate_options o;
-    sfmba_default_triangulate_options(&o);
-    const TriOptions opt = tri_options(o);
-    int grid = 1;
-    CHK(tri_allocate(h, &grid));
-    CHK(stats_prepare(h, x));
-    return time_reps(h, reps, avg_us, [&] { return launch_triangulate(h, opt, false, false, grid); });
-}
-}  // namespace
-
-void sfmba_default_triangulate_options(sfmba_triangulate_options* o) {
-    if (!o) return;
-    memset(o, 0, sizeof *o);
-    o->max_iter = 10; o->min_views = 2; o->xtol = 1e-10; o->min_angle_deg = 1.0; o->min_depth = 0.0; o->max_error_px = INFINITY;
-}
-
-int sfmba_triangulate(sfmba_handle* h, const double* x, const uint8_t* pt_select, const uint8_t* obs_use,
-                      const sfmba_triangulate_options* opt, double* X_out, int32_t* pt_status, int32_t* pt_views,
-                      int32_t* pt_iters, double* pt_rms_err, double* pt_angle_deg, int64_t* n_ok) {
-    CHK(enter(h));
-    CHK(begin_compute(h, x));
-    sfmba_triangulate_options o;
-    if (opt) o = *opt; else sfmba_default_triangulate_options(&o);
-    if (std::isnan(o.xtol) || std::isnan(o.min_angle_deg) || std::isnan(o.min_depth) || std::isnan(o.max_error_px))
-        return fail(h, -1, "an option of sfmba_triangulate is NaN");
-    auto& t = h->tri;
-    const size_t P = (size_t)h->P;
-    int grid = 1, *counts = nullptr;
-    CHK(tri_allocate(h, &grid));
-    CHK(stats_prepare(h, x));
-    CHK(stage_masks(h, obs_use, pt_select, P, t.select, (size_t)grid, &counts));
-    CHK(launch_triangulate(h, tri_options(o), obs_use != nullptr, pt_select != nullptr, grid));
-    const int* pi = t.ints.as<int>();
-    HIPCHK(h, download(h, X_out, t.X.p, sizeof(double) * 3 * P));
-    HIPCHK(h, download(h, pt_status, pi, sizeof(int32_t) * P));
-    HIPCHK(h, download(h, pt_views, pi + P, sizeof(int32_t) * P));
-    HIPCHK(h, download(h, pt_iters, pi + 2 * P, sizeof(int32_t) * P));
-    HIPCHK(h, download(h, pt_rms_err, t.dbl.p, sizeof(double) * P));
-    HIPCHK(h, download(h, pt_angle_deg, t.dbl.as<double>() + P, sizeof(double) * P));
-    return finish_with_ok_count(h, t.ok_part.as<int>(), (size_t)grid, counts, n_ok);
-}
-
-namespace {
-// ---- resection (sfmba_resect; kernel: consumer_kernels.hpp, "Resection") ----------------------------------------------------
-int resect_allocate(sfmba_handle* h) {
-    auto& r = h->resect;
-    const size_t ldz = (size_t)h->ld, C = (size_t)h->C;
-    return ensure_all(h, {
-        {&h->stats.x, sizeof(double) * (size_t)h->n}, {&h->stats.use, ldz}, {&r.select, C}, {&r.cam, sizeof(double) * 6 * C},
-        {&r.ints, sizeof(int) * 4 * C}, {&r.rms, sizeof(double) * C}});
-}
-
-ResectOptions resect_options(const sfmba_resect_options& o) {
-    return ResectOptions{(int)o.max_iter, (int)o.min_views, o.start != 0 ? 1 : 0, o.xtol, o.min_depth, o.max_rms_px};
-}
-
-// K^-1 by the adjugate (the pixels of the linear stage are normalised with it)
-KMat inverse_k(const KMat& K) {
-    const double* k = K.k;
-    const double c00 = k[4] * k[8] - k[5] * k[7], c01 = k[5] * k[6] - k[3] * k[8], c02 = k[3] * k[7] - k[4] * k[6];
-    const double det = k[0] * c00 + k[1] * c01 + k[2] * c02;
-    KMat inv;
-    inv.k[0] = c00 / det; inv.k[1] = (k[2] * k[7] - k[1] * k[8]) / det; inv.k[2] = (k[1] * k[5] - k[2] * k[4]) / det;
-    inv.k[3] = c01 / det; inv.k[4] = (k[0] * k[8] - k[2] * k[6]) / det; inv.k[5] = (k[2] * k[3] - k[0] * k[5]) / det;
-    inv.k[6] = c02 / det; inv.k[7] = (k[1] * k[6] - k[0] * k[7]) / det; inv.k[8] = (k[0] * k[4] - k[1] * k[3]) / det;
-    return inv;
-}
-
-// x must be in stats.x and the permutation of stats_cam_perm(h) in place; use / select: the masks on the device ([ld]
-// stored order / [C]), null: every observation / camera; perm: another order of the entries inside the cameras' slices
-// (null: the permutation itself)
-int launch_resect(sfmba_handle* h, const ResectOptions& opt, const unsigned char* use, const unsigned char* select,
-                  const int* perm = nullptr) {
-    auto& s = h->stats;
-    auto& r = h->resect;
-    const size_t C = (size_t)h->C;
-    if (C == 0) return 0;
-    const ResectIn in{s.cam_ptr.as<int>(), perm ? perm : s.perm.as<int>(), h->pt_idx.as<int>(), h->uv.as<double>(),
-                      use, select, s.x.as<double>()};
-    const ResectOut out{r.cam.as<double>(), r.ints.as<int>(), r.ints.as<int>() + C, r.ints.as<int>() + 2 * C,
-                        r.rms.as<double>(), r.ints.as<int>() + 3 * C};
-    auto kern = h->f32 ? k_resect<true> : k_resect<false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)C), dim3(kCamThreads), 0, h->stream, in, (int)h->C, h->K, inverse_k(h->K), opt, out);
-    LAUNCHED(h);
-    return 0;
-}
-
-int resect_check_single(sfmba_handle* h) {
-    if (multi_rank(h) || h->N_total != h->N)
-        return fail(h, -1, "sfmba_resect needs every observation of a camera: this handle holds a shard of the problem");
-    return 0;
-}
-
-// sfmba_time_kernel, which = 16: k_resect at x over every camera and observation, default options
-int resect_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us) {
-    sfmba_resect_options o;
-    sfmba_default_resect_options(&o);
-    const ResectOptions opt = resect_options(o);
-    CHK(resect_check_single(h));
-    CHK(resect_allocate(h));
-    CHK(upload_x(h, x, h->stats.x.as<double>()));
-    CHK(stats_cam_perm(h));
-    return time_reps(h, reps, avg_us, [&] { return launch_resect(h, opt, nullptr, nullptr); });
-}
-}  // namespace
-
-void sfmba_default_resect_options(sfmba_resect_options* o) {
-    if (!o) return;
-    memset(o, 0, sizeof *o);
-    o->max_iter = 20; o->min_views = 6; o->start = 0; o->xtol = 1e-10; o->min_depth = 0.0; o->max_rms_px = INFINITY;
-}
-
-int sfmba_resect(sfmba_handle* h, const double* x, const uint8_t* cam_select, const uint8_t* obs_use,
-                 const sfmba_resect_options* opt, double* cam_out, int32_t* cam_status, int32_t* cam_views,
-                 int32_t* cam_iters, double* cam_rms_err, int64_t* n_ok) {
-    CHK(enter(h));
-    CHK(begin_compute(h, x));
-    sfmba_resect_options o;
-    if (opt) o = *opt; else sfmba_default_resect_options(&o);
-    if (std::isnan(o.xtol) || std::isnan(o.min_depth) || std::isnan(o.max_rms_px))
-        return fail(h, -1, "an option of sfmba_resect is NaN");
-    CHK(resect_check_single(h));
-    auto& r = h->resect;
-    const size_t C = (size_t)h->C;
-    int* counts = nullptr;
-    CHK(resect_allocate(h));
-    CHK(upload_x(h, x, h->stats.x.as<double>()));
-    CHK(stats_cam_perm(h));
-    CHK(stage_masks(h, obs_use, cam_select, C, r.select, C, &counts));
-    CHK(launch_resect(h, resect_options(o), obs_use ? h->stats.use.as<unsigned char>() : nullptr,
-                      cam_select ? r.select.as<unsigned char>() : nullptr));
-    const int* pi = r.ints.as<int>();
-    HIPCHK(h, download(h, cam_out, r.cam.p, sizeof(double) * 6 * C));
-    HIPCHK(h, download(h, cam_status, pi, sizeof(int32_t) * C));
-    HIPCHK(h, download(h, cam_views, pi + C, sizeof(int32_t) * C));
-    HIPCHK(h, download(h, cam_iters, pi + 2 * C, sizeof(int32_t) * C));
-    HIPCHK(h, download(h, cam_rms_err, r.rms.p, sizeof(double) * C));
-    return finish_with_ok_count(h, pi + 3 * C, C, counts, n_ok);
-}
-
-namespace {
-// ---- two-view geometry (sfmba_fundamental_ransac, sfmba_recover_pose; kernels: consumer_kernels.hpp, "Two-view geometry") ----
-struct TwoViewBatch { size_t E = 0, M = 0, Mu = 0; bool masked = false; int max_n = 0; };
-
-// The batch onto the device: the used pairs of every edge packed x1 y1 x2 y2 in stored order -> twoview.pairs, their runs
-// -> twoview.uptr; twoview.pos maps a used pair back to its stored place when there is a mask.
-int twoview_stage(sfmba_handle* h, const char* who, int64_t n_edges, const int64_t* edge_ptr, const double* pts1,
-                  const double* pts2, const uint8_t* pair_use, TwoViewBatch* bt) {
-    auto& t = h->twoview;
-    if (n_edges < 0 || !edge_ptr) return fail(h, -1, "%s: n_edges is negative or edge_ptr is NULL", who);
-    if (edge_ptr[0] != 0) return fail(h, -1, "%s: edge_ptr[0] must be 0", who);
-    for (int64_t e = 0; e < n_edges; ++e)
-        if (edge_ptr[e + 1] < edge_ptr[e]) return fail(h, -1, "%s: edge_ptr must ascend (edge %lld)", who, (long long)e);
-    const size_t E = (size_t)n_edges, M = (size_t)edge_ptr[n_edges];
-    if (M >= (size_t)1 << 31 || E >= (size_t)1 << 31) return fail(h, -1, "%s: the batch has 2^31 pairs or edges, or more", who);
-    if (M && (!pts1 || !pts2)) return fail(h, -1, "%s: pts1 or pts2 is NULL", who);
-    const size_t off_ptr = sizeof(double) * 4 * M;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, t.in_host.ensure(off_ptr + sizeof(int) * (E + 1), 0));
-    double* const pk = t.in_host.as<double>();
-    int* const up = reinterpret_cast<int*>(t.in_host.as<unsigned char>() + off_ptr);
-    t.pos.clear();
-    size_t u = 0;
-    int max_n = 0;
-    for (size_t e = 0; e < E; ++e) {
-        up[e] = (int)u;
-        for (size_t k = (size_t)edge_ptr[e]; k < (size_t)edge_ptr[e + 1]; ++k) {
-            if (pair_use && !pair_use[k]) continue;
-            pk[4 * u] = pts1[2 * k]; pk[4 * u + 1] = pts1[2 * k + 1]; pk[4 * u + 2] = pts2[2 * k]; pk[4 * u + 3] = pts2[2 * k + 1];
-            if (pair_use) t.pos.push_back((int64_t)k);
-            ++u;
-        }
-        max_n = std::max(max_n, (int)u - up[e]);
-    }
-    up[E] = (int)u;
-    CHK(ensure_all(h, {{&t.pairs, sizeof(double) * 4 * std::max<size_t>(u, 1)}, {&t.uptr, sizeof(int) * (E + 1)}}));
-    if (u) HIPCHK(h, hipMemcpyAsync(t.pairs.p, pk, sizeof(double) * 4 * u, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(t.uptr.p, up, sizeof(int) * (E + 1), hipMemcpyHostToDevice, h->stream));
-    bt->E = E; bt->M = M; bt->Mu = u; bt->masked = pair_use != nullptr; bt->max_n = max_n;
-    return 0;
-}
-
-// the events of profile = 1 round a call's launches
-struct TwoViewTimer {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~TwoViewTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    int start(sfmba_handle* h, bool on) {
-        if (!on) return 0;
-        HIPCHK(h, hipEventCreate(&a));
-        HIPCHK(h, hipEventCreate(&b));
-        HIPCHK(h, hipEventRecord(a, h->stream));
-        return 0;
-    }
-    int stop(sfmba_handle* h) {
-        if (a) HIPCHK(h, hipEventRecord(b, h->stream));
-        return 0;
-    }
-    int read(sfmba_handle* h, double* us) {                      // after the stream has been waited for
-        if (!us) return 0;
-        *us = 0.0;
-        if (!a) return 0;
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, a, b));
-        *us = 1e3 * (double)ms;
-        return 0;
-    }
-};
-
-// a per-pair result from its packed order in the staging (src) into the caller's stored order, `bytes` per pair; pairs
-// that took no part get the `bytes` at `fill`
-void twoview_scatter(const sfmba_handle* h, const TwoViewBatch& bt, const void* src, void* dst, size_t bytes, const void* fill) {
-    if (!dst) return;
-    if (!bt.masked) { memcpy(dst, src, bytes * bt.Mu); return; }
-    unsigned char* const d = static_cast<unsigned char*>(dst);
-    const unsigned char* const sp = static_cast<const unsigned char*>(src);
-    for (size_t k = 0; k < bt.M; ++k) memcpy(d + bytes * k, fill, bytes);
-    const auto& pos = h->twoview.pos;
-    for (size_t u = 0; u < bt.Mu; ++u) memcpy(d + bytes * (size_t)pos[u], sp + bytes * u, bytes);
-}
-
-// hypotheses of a workgroup's slice and the slices of an edge: about two workgroups per CU over the whole batch, a slice
-// not below kTwoViewMinSlice
-void twoview_slices(const sfmba_handle* h, size_t E, int H, int* hs, int* n_slices) {
-    const size_t want = (2 * (size_t)h->n_cu + E - 1) / std::max<size_t>(E, 1);
-    const int most = (H + kTwoViewMinSlice - 1) / kTwoViewMinSlice;
-    const int sl = (int)std::min<size_t>(std::max<size_t>(want, 1), (size_t)most);
-    *hs = (H + sl - 1) / sl;
-    *n_slices = (H + *hs - 1) / *hs;
-}
-}  // namespace
-
-namespace {
-// ---- robust resection (sfmba_resect_ransac; kernels: consumer_kernels.hpp, "Robust resection") ----------------------------
-struct PnpCall { int H, hs, n_slices; PnpScore sc; double confidence; unsigned long long seed; };
-
-PnpCall pnp_call(const sfmba_handle* h, const sfmba_pnp_ransac_options& o) {
-    PnpCall pc{};
-    pc.H = (int)o.max_iters;
-    // the slices of a camera by the rule of twoview_slices: about two workgroups per CU over the batch, and no slice below
-    // kPnpMinSlice hypotheses (H / kPnpMinSlice slices at the most, rounded down)
-    const size_t want = (2 * (size_t)h->n_cu + (size_t)h->C - 1) / std::max<size_t>((size_t)h->C, 1);
-    const int sl = (int)std::min<size_t>(std::max<size_t>(want, 1), (size_t)std::max(pc.H / kPnpMinSlice, 1));
-    pc.hs = (pc.H + sl - 1) / sl;
-    pc.n_slices = (pc.H + pc.hs - 1) / pc.hs;
-    pc.sc = PnpScore{o.threshold * o.threshold, o.min_depth, std::max((int)o.min_views, 4)};
-    pc.confidence = o.confidence;
-    pc.seed = (unsigned long long)o.seed;
-    return pc;
-}
-
-int pnp_allocate(sfmba_handle* h, const PnpCall& pc, bool samples, bool hyp) {
-    auto& q = h->pnp;
-    const size_t ldz = (size_t)h->ld, C = (size_t)h->C, H = (size_t)pc.H;
-    if (C * (size_t)pc.n_slices >= (size_t)1 << 31) return fail(h, -1, "sfmba_resect_ransac: too many cameras for one launch");
-    CHK(resect_allocate(h));
-    return ensure_all(h, {
-        {&q.select, C}, {&q.ok, C}, {&q.mask, ldz}, {&q.corr, sizeof(double) * kPnpCorr * ldz}, {&q.cpos, sizeof(int) * ldz},
-        {&q.cn, sizeof(int) * C}, {&q.samples, samples ? sizeof(int) * 3 * C * H : 0},
-        {&q.slots, sizeof(double) * kPnpSlot * C * (size_t)pc.n_slices}, {&q.hyp, hyp ? sizeof(int) * C * H : 0},
-        {&q.pose, sizeof(double) * 6 * C}, {&q.ints, sizeof(int) * 6 * C}});
-}
-
-PnpIn pnp_in(sfmba_handle* h, bool samples) {
-    auto& q = h->pnp;
-    return PnpIn{q.corr.as<double>(), h->stats.cam_ptr.as<int>(), q.cn.as<int>(), samples ? q.samples.as<int>() : nullptr};
-}
-
-// x must be in stats.x and the permutation of stats_cam_perm(h) in place; use / select: the masks are on the device
-int launch_pnp_gather(sfmba_handle* h, bool use, bool select) {
-    auto& s = h->stats;
-    auto& q = h->pnp;
-    const ResectIn in{s.cam_ptr.as<int>(), s.perm.as<int>(), h->pt_idx.as<int>(), h->uv.as<double>(),
-                      use ? s.use.as<unsigned char>() : nullptr, select ? q.select.as<unsigned char>() : nullptr,
-                      s.x.as<double>()};
-    auto kern = h->f32 ? k_pnp_gather<true> : k_pnp_gather<false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)h->C), dim3(kPnpThreads), 0, h->stream, in, (int)h->C, q.corr.as<double>(),
-                       q.cpos.as<int>(), q.cn.as<int>(), q.mask.as<unsigned char>());
-    LAUNCHED(h);
-    return 0;
-}
-
-// k_pnp_ransac and k_pnp_finish behind k_pnp_gather
-int launch_pnp_ransac(sfmba_handle* h, const PnpCall& pc, bool samples, bool hyp, bool select) {
-    auto& q = h->pnp;
-    const size_t C = (size_t)h->C;
-    constexpr size_t lds = sizeof(double) * ((size_t)kPnpWaves * kPnpSlabDoubles + (size_t)kPnpCorr * kPnpLdsObs);
-    static_assert(lds + 1024 <= 160 * 1024, "slabs and staged correspondences must fit the LDS of a CU");
-    {   // more than 64 KiB of LDS needs the opt-in, once per handle
-        const void* fn = reinterpret_cast<const void*>(k_pnp_ransac);
-        if (std::find(h->lds_ready.begin(), h->lds_ready.end(), fn) == h->lds_ready.end()) {
-            HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            h->lds_ready.push_back(fn);
-        }
-    }
-    const PnpIn in = pnp_in(h, samples);
-    hipLaunchKernelGGL(k_pnp_ransac, dim3((unsigned)(C * (size_t)pc.n_slices)), dim3(kPnpThreads), lds, h->stream, in, pc.H, pc.hs,
-                       pc.n_slices, pc.seed, h->K, inverse_k(h->K), pc.sc, q.slots.as<double>(), hyp ? q.hyp.as<int>() : nullptr);
-    LAUNCHED(h);
-    const PnpOut out{h->stats.x.as<double>(), q.pose.as<double>(), q.mask.as<unsigned char>(), q.ok.as<unsigned char>(),
-                     q.ints.as<int>()};
-    hipLaunchKernelGGL(k_pnp_finish, dim3((unsigned)C), dim3(kPnpThreads), 0, h->stream, in, (const int*)q.cpos.as<int>(),
-                       (const unsigned char*)(select ? q.select.as<unsigned char>() : nullptr), pc.n_slices, h->K, pc.sc,
-                       pc.confidence, (const double*)q.slots.as<double>(), out);
-    LAUNCHED(h);
-    return 0;
-}
-
-// sfmba_time_kernel, which = 17: k_pnp_ransac + k_pnp_finish at x over every camera and observation, default options
-int pnp_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us) {
-    sfmba_pnp_ransac_options o;
-    sfmba_default_pnp_ransac_options(&o);
-    CHK(resect_check_single(h));
-    if (h->C == 0) { *avg_us = 0.0; return 0; }
-    const PnpCall pc = pnp_call(h, o);
-    CHK(pnp_allocate(h, pc, false, false));
-    CHK(upload_x(h, x, h->stats.x.as<double>()));
-    CHK(stats_cam_perm(h));
-    CHK(launch_pnp_gather(h, false, false));
-    return time_reps(h, reps, avg_us, [&] { return launch_pnp_ransac(h, pc, false, false, false); });
-}
-}  // namespace
-
-void sfmba_default_pnp_ransac_options(sfmba_pnp_ransac_options* o) {
-    if (!o) return;
-    memset(o, 0, sizeof *o);
-    o->threshold = 8.0; o->confidence = 0.99; o->min_depth = 0.0; o->seed = 0; o->max_iters = 256; o->min_views = 6;
-    o->refine = 1; o->profile = 0; o->max_iter = 20; o->xtol = 1e-10; o->max_rms_px = INFINITY;
-}
-
-int sfmba_resect_ransac(sfmba_handle* h, const double* x, const uint8_t* cam_select, const uint8_t* obs_use, const int32_t* samples,
-                        const sfmba_pnp_ransac_options* opt, double* cam_out, double* cam_hyp, uint8_t* inlier_mask,
-                        int32_t* cam_status, int32_t* cam_views, int32_t* cam_inliers, int32_t* cam_best, int32_t* cam_best_sol,
-                        uint8_t* cam_success, int32_t* cam_iters, double* cam_rms_err, int32_t* hyp_inliers, int64_t* n_ok,
-                        double* kernel_us) {
-    CHK(enter(h));
-    CHK(begin_compute(h, x));
-    sfmba_pnp_ransac_options o;
-    if (opt) o = *opt; else sfmba_default_pnp_ransac_options(&o);
-    if (std::isnan(o.threshold) || std::isnan(o.confidence) || std::isnan(o.min_depth) || std::isnan(o.xtol) || std::isnan(o.max_rms_px))
-        return fail(h, -1, "an option of sfmba_resect_ransac is NaN");
-    if (o.max_iters < 1) return fail(h, -1, "sfmba_resect_ransac: max_iters must be at least 1");
-    CHK(resect_check_single(h));
-    if (n_ok) *n_ok = 0;
-    if (kernel_us) *kernel_us = 0.0;
-    auto& q = h->pnp;
-    auto& r = h->resect;
-    const size_t C = (size_t)h->C, N = (size_t)h->N;
-    if (C == 0) return wait_stream(h);
-    const PnpCall pc = pnp_call(h, o);
-    const size_t H = (size_t)pc.H;
-    int* counts = nullptr;
-    CHK(pnp_allocate(h, pc, samples != nullptr, hyp_inliers != nullptr));
-    CHK(upload_x(h, x, h->stats.x.as<double>()));
-    CHK(stats_cam_perm(h));
-    CHK(stage_masks(h, obs_use, cam_select, C, q.select, 0, &counts));
-    // the results' staging: doubles first (pose, k_resect's pose and rms), then the integers (ours, k_resect's), the mask
-    const size_t off_ints = sizeof(double) * 13 * C, off_mask = off_ints + sizeof(int) * 10 * C;
-    HIPCHK(h, q.host.ensure(off_mask + N + 64, 0));
-    double* const hd = q.host.as<double>();
-    int* const hi = reinterpret_cast<int*>(q.host.as<unsigned char>() + off_ints);
-    unsigned char* const hm = q.host.as<unsigned char>() + off_mask;
-    TwoViewTimer timer;
-    CHK(timer.start(h, o.profile != 0));
-    CHK(launch_pnp_gather(h, obs_use != nullptr, cam_select != nullptr));
-    if (samples) {                                               // positions are checked against the cameras' counts
-        HIPCHK(h, hipMemcpyAsync(hi, q.cn.p, sizeof(int) * C, hipMemcpyDeviceToHost, h->stream));
-        CHK(wait_stream(h));
-        for (size_t c = 0; c < C; ++c) {
-            const int n = hi[c];
-            if (n < pc.sc.need) continue;                        // (not selected or FEW_VIEWS: its samples are not read)
-            const int32_t* sp = samples + c * H * 3;
-            for (size_t k = 0; k < 3 * H; ++k)
-                if (sp[k] < 0 || sp[k] >= n)
-                    return fail(h, -1, "sfmba_resect_ransac: samples of camera %zu, hypothesis %zu: position %d is outside its %d used observations",
-                                c, k / 3, (int)sp[k], n);
-        }
-        HIPCHK(h, hipMemcpyAsync(q.samples.p, samples, sizeof(int) * 3 * C * H, hipMemcpyHostToDevice, h->stream));
-    }
-    CHK(launch_pnp_ransac(h, pc, samples != nullptr, hyp_inliers != nullptr, cam_select != nullptr));
-    // the verdict and (refine = 1) the refinement: k_resect from the pose in x over the inlier mask, for the cameras that
-    // succeeded -- both masks were written by k_pnp_finish
-    ResectOptions ro{o.refine != 0 ? (int)o.max_iter : 0, (int)o.min_views, 1, o.xtol, o.min_depth, o.max_rms_px};
-    // (over the compacted positions of k_pnp_gather: a masked call sums in the order of the problem without the masked)
-    CHK(launch_resect(h, ro, q.mask.as<unsigned char>(), q.ok.as<unsigned char>(), q.cpos.as<int>()));
-    CHK(timer.stop(h));
-    HIPCHK(h, hipMemcpyAsync(hd, q.pose.p, sizeof(double) * 6 * C, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(hd + 6 * C, r.cam.p, sizeof(double) * 6 * C, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(hd + 12 * C, r.rms.p, sizeof(double) * C, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(hi, q.ints.p, sizeof(int) * 6 * C, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(hi + 6 * C, r.ints.p, sizeof(int) * 4 * C, hipMemcpyDeviceToHost, h->stream));
-    if (inlier_mask && N) HIPCHK(h, hipMemcpyAsync(hm, q.mask.p, N, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, download(h, hyp_inliers, q.hyp.p, sizeof(int) * C * H));
-    CHK(wait_stream(h));
-    CHK(timer.read(h, kernel_us));
-    if (inlier_mask)
-        for (size_t k = 0; k < N; ++k) inlier_mask[h->permuted ? (size_t)h->tb.order[k] : k] = hm[k];
-    const int* const ri = hi + 6 * C;                            // k_resect's status, views, iters, ok
-    int64_t ok = 0;
-    for (size_t c = 0; c < C; ++c) {
-        const int* pi = hi + 6 * c;
-        const bool refined = pi[0] == kPnpOk;                    // RANSAC succeeded: k_resect's verdict counts
-        const int status = refined ? ri[c] : pi[0];
-        if (cam_status) cam_status[c] = status;
-        if (cam_views) cam_views[c] = pi[1];
-        if (cam_inliers) cam_inliers[c] = pi[2];
-        if (cam_best) cam_best[c] = pi[3];
-        if (cam_best_sol) cam_best_sol[c] = pi[4];
-        if (cam_success) cam_success[c] = (uint8_t)pi[5];
-        if (cam_iters) cam_iters[c] = refined ? ri[2 * C + c] : 0;
-        if (cam_rms_err) cam_rms_err[c] = refined ? hd[12 * C + c] : NAN;
-        if (cam_hyp) memcpy(cam_hyp + 6 * c, hd + 6 * c, sizeof(double) * 6);
-        if (cam_out) memcpy(cam_out + 6 * c, status == kResOk ? hd + 6 * C + 6 * c : x + 6 * c, sizeof(double) * 6);
-        ok += status == kResOk ? 1 : 0;
-    }
-    if (n_ok) *n_ok = ok;
-    return 0;
-}
-
-void sfmba_default_ransac_options(sfmba_ransac_options* o) {
-    if (!o) return;
-    memset(o, 0, sizeof *o);
-    o->threshold = 1.0; o->confidence = 0.99; o->seed = 0; o->max_iters = 1000; o->refit = 0; o->profile = 0;
-}
-
-int sfmba_fundamental_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edge_ptr, const double* pts1, const double* pts2,
-                             const uint8_t* pair_use, const int32_t* samples, const sfmba_ransac_options* opt, double* F,
-                             double* F_refit, uint8_t* inlier_mask, int32_t* edge_inliers, int32_t* edge_best,
-                             uint8_t* edge_success, int32_t* edge_status, int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us) {
-    CHK(enter(h));
-    sfmba_ransac_options o;
-    if (opt) o = *opt; else sfmba_default_ransac_options(&o);
-    if (std::isnan(o.threshold) || std::isnan(o.confidence)) return fail(h, -1, "an option of sfmba_fundamental_ransac is NaN");
-    if (o.max_iters < 1) return fail(h, -1, "sfmba_fundamental_ransac: max_iters must be at least 1");
-    auto& t = h->twoview;
-    TwoViewBatch bt;
-    CHK(twoview_stage(h, "sfmba_fundamental_ransac", n_edges, edge_ptr, pts1, pts2, pair_use, &bt));
-    if (n_ok) *n_ok = 0;
-    if (kernel_us) *kernel_us = 0.0;
-    const size_t E = bt.E, H = (size_t)o.max_iters;
-    if (E == 0) return wait_stream(h);
-    int hs = 1, n_slices = 1;
-    twoview_slices(h, E, (int)H, &hs, &n_slices);
-    if (E * (size_t)n_slices >= (size_t)1 << 31) return fail(h, -1, "sfmba_fundamental_ransac: too many edges for one launch");
-    CHK(ensure_all(h, {{&t.slots, sizeof(double) * kTwoViewSlot * E * (size_t)n_slices},
-                       {&t.hyp, hyp_inliers ? sizeof(int) * E * H : 0}, {&t.samples, samples ? sizeof(int) * 8 * E * H : 0},
-                       {&t.F, sizeof(double) * 18 * E}, {&t.ints, sizeof(int) * 4 * E}, {&t.mask, std::max<size_t>(bt.Mu, 1)}}));
-    if (samples) {
-        const int* up = reinterpret_cast<const int*>(t.in_host.as<unsigned char>() + sizeof(double) * 4 * bt.M);
-        for (size_t e = 0; e < E; ++e) {
-            const int n = up[e + 1] - up[e];
-            if (n < 8) continue;                                 // (FEW_PAIRS: its samples are not read)
-            const int32_t* sp = samples + e * H * 8;
-            for (size_t k = 0; k < 8 * H; ++k)
-                if (sp[k] < 0 || sp[k] >= n)
-                    return fail(h, -1, "sfmba_fundamental_ransac: samples of edge %zu, hypothesis %zu: position %d is outside its %d used pairs",
-                                e, k / 8, (int)sp[k], n);
-        }
-        HIPCHK(h, hipMemcpyAsync(t.samples.p, samples, sizeof(int) * 8 * E * H, hipMemcpyHostToDevice, h->stream));
-    }
-    const FundIn in{t.pairs.as<double>(), t.uptr.as<int>(), samples ? t.samples.as<int>() : nullptr};
-    const FundOut out{t.F.as<double>(), t.F.as<double>() + 9 * E, t.mask.as<unsigned char>(), t.ints.as<int>()};
-    const size_t lds = sizeof(double) * 4 * (size_t)std::min(bt.max_n, kTwoViewLdsPairs);
-    {   // more than 64 KiB of LDS in all needs the opt-in, and the kernel's static part (about 8 KiB, above the 2 KiB that
-        // set_lds assumes) counts: opted in once per handle, whatever this call stages
-        const void* fn = reinterpret_cast<const void*>(k_fund_ransac);
-        if (std::find(h->lds_ready.begin(), h->lds_ready.end(), fn) == h->lds_ready.end()) {
-            HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * 4 * kTwoViewLdsPairs)));
-            h->lds_ready.push_back(fn);
-        }
-    }
-    TwoViewTimer timer;
-    CHK(timer.start(h, o.profile != 0));
-    hipLaunchKernelGGL(k_fund_ransac, dim3((unsigned)(E * (size_t)n_slices)), dim3(kTwoViewThreads), lds, h->stream, in, (int)H, hs,
-                       n_slices, (unsigned long long)o.seed, o.threshold, t.slots.as<double>(), hyp_inliers ? t.hyp.as<int>() : nullptr);
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_fund_finish, dim3((unsigned)E), dim3(kTwoViewThreads), 0, h->stream, in, n_slices, o.threshold, o.confidence,
-                       o.refit != 0 ? 1 : 0, (const double*)t.slots.as<double>(), out);
-    LAUNCHED(h);
-    CHK(timer.stop(h));
-    // the per-edge integers always come (n_ok); the mask through the staging when it has to be scattered
-    const size_t off_mask = sizeof(int) * 4 * E;
-    HIPCHK(h, t.out_host.ensure(off_mask + bt.Mu, 0));
-    int* const hi = t.out_host.as<int>();
-    unsigned char* const hm = t.out_host.as<unsigned char>() + off_mask;
-    HIPCHK(h, hipMemcpyAsync(hi, t.ints.p, sizeof(int) * 4 * E, hipMemcpyDeviceToHost, h->stream));
-    if (inlier_mask && bt.Mu) HIPCHK(h, hipMemcpyAsync(hm, t.mask.p, bt.Mu, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, download(h, F, t.F.p, sizeof(double) * 9 * E));
-    HIPCHK(h, download(h, F_refit, t.F.as<double>() + 9 * E, sizeof(double) * 9 * E));
-    HIPCHK(h, download(h, hyp_inliers, t.hyp.p, sizeof(int) * E * H));
-    CHK(wait_stream(h));
-    CHK(timer.read(h, kernel_us));
-    const uint8_t zero = 0;
-    twoview_scatter(h, bt, hm, inlier_mask, 1, &zero);
-    int64_t ok = 0;
-    for (size_t e = 0; e < E; ++e) {
-        if (edge_inliers) edge_inliers[e] = hi[4 * e];
-        if (edge_best) edge_best[e] = hi[4 * e + 1];
-        if (edge_status) edge_status[e] = hi[4 * e + 2];
-        if (edge_success) edge_success[e] = (uint8_t)hi[4 * e + 3];
-        ok += hi[4 * e + 2] == kFundOk ? 1 : 0;
-    }
-    if (n_ok) *n_ok = ok;
-    return 0;
-}
-
-void sfmba_default_pose_options(sfmba_pose_options* o) {
-    if (!o) return;
-    memset(o, 0, sizeof *o);
-    o->min_depth = 0.0; o->profile = 0;
-}
-
-int sfmba_recover_pose(sfmba_handle* h, int64_t n_edges, const int64_t* edge_ptr, const double* pts1, const double* pts2,
-                       const uint8_t* pair_use, const double* E_in, const double* K, const sfmba_pose_options* opt, double* R,
-                       double* t_out, uint8_t* front_mask, double* X, double* angle_deg, int32_t* edge_front,
-                       int32_t* edge_front_all, double* edge_sum_err, int32_t* edge_status, int64_t* n_ok, double* kernel_us) {
-    CHK(enter(h));
-    sfmba_pose_options o;
-    if (opt) o = *opt; else sfmba_default_pose_options(&o);
-    if (std::isnan(o.min_depth)) return fail(h, -1, "an option of sfmba_recover_pose is NaN");
-    if (!K) return fail(h, -1, "sfmba_recover_pose: K is NULL");
-    auto& t = h->twoview;
-    TwoViewBatch bt;
-    CHK(twoview_stage(h, "sfmba_recover_pose", n_edges, edge_ptr, pts1, pts2, pair_use, &bt));
-    if (n_ok) *n_ok = 0;
-    if (kernel_us) *kernel_us = 0.0;
-    const size_t E = bt.E, Mu = bt.Mu;
-    if (E == 0) return wait_stream(h);
-    if (!E_in) return fail(h, -1, "sfmba_recover_pose: E is NULL");
-    const size_t M1 = std::max<size_t>(Mu, 1);
-    CHK(ensure_all(h, {{&t.E, sizeof(double) * 9 * E}, {&t.Rt, sizeof(double) * 12 * E}, {&t.err, sizeof(double) * E},
-                       {&t.pose_ints, sizeof(int) * 6 * E}, {&t.mask, M1}, {&t.X, sizeof(double) * 3 * M1}, {&t.ang, sizeof(double) * M1}}));
-    // E through the staging of the results (pinned; nothing of this call is in it yet)
-    const size_t off_rt = 0, off_err = sizeof(double) * 12 * E, off_X = off_err + sizeof(double) * E,
-                 off_ang = off_X + sizeof(double) * 3 * Mu, off_int = off_ang + sizeof(double) * Mu, off_mask = off_int + sizeof(int) * 6 * E;
-    HIPCHK(h, t.out_host.ensure(off_mask + Mu, 0));
-    unsigned char* const st = t.out_host.as<unsigned char>();
-    memcpy(st, E_in, sizeof(double) * 9 * E);
-    HIPCHK(h, hipMemcpyAsync(t.E.p, st, sizeof(double) * 9 * E, hipMemcpyHostToDevice, h->stream));
-    KMat Km;
-    for (int k = 0; k < 9; ++k) Km.k[k] = K[k];
-    const PoseOut out{t.Rt.as<double>(), t.err.as<double>(), t.pose_ints.as<int>(), t.mask.as<unsigned char>(), t.X.as<double>(),
-                      t.ang.as<double>()};
-    TwoViewTimer timer;
-    CHK(timer.start(h, o.profile != 0));
-    hipLaunchKernelGGL(k_recover_pose, dim3((unsigned)E), dim3(kTwoViewThreads), 0, h->stream, (const double*)t.pairs.as<double>(),
-                       (const int*)t.uptr.as<int>(), (const double*)t.E.as<double>(), Km, o.min_depth, out);
-    LAUNCHED(h);
-    CHK(timer.stop(h));
-    HIPCHK(h, hipMemcpyAsync(st + off_rt, t.Rt.p, sizeof(double) * 12 * E, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(st + off_int, t.pose_ints.p, sizeof(int) * 6 * E, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, download(h, edge_sum_err, t.err.p, sizeof(double) * E));
-    if (X && Mu) HIPCHK(h, hipMemcpyAsync(st + off_X, t.X.p, sizeof(double) * 3 * Mu, hipMemcpyDeviceToHost, h->stream));
-    if (angle_deg && Mu) HIPCHK(h, hipMemcpyAsync(st + off_ang, t.ang.p, sizeof(double) * Mu, hipMemcpyDeviceToHost, h->stream));
-    if (front_mask && Mu) HIPCHK(h, hipMemcpyAsync(st + off_mask, t.mask.p, Mu, hipMemcpyDeviceToHost, h->stream));
-    CHK(wait_stream(h));
-    CHK(timer.read(h, kernel_us));
-    const double* rt = reinterpret_cast<const double*>(st + off_rt);
-    const int* hi = reinterpret_cast<const int*>(st + off_int);
-    const double nan3[3] = {NAN, NAN, NAN};
-    const uint8_t zero = 0;
-    twoview_scatter(h, bt, st + off_X, X, sizeof(double) * 3, nan3);
-    twoview_scatter(h, bt, st + off_ang, angle_deg, sizeof(double), nan3);
-    twoview_scatter(h, bt, st + off_mask, front_mask, 1, &zero);
-    int64_t ok = 0;
-    for (size_t e = 0; e < E; ++e) {
-        if (R) memcpy(R + 9 * e, rt + 12 * e, sizeof(double) * 9);
-        if (t_out) memcpy(t_out + 3 * e, rt + 12 * e + 9, sizeof(double) * 3);
-        if (edge_front) edge_front[e] = hi[6 * e];
-        if (edge_front_all) memcpy(edge_front_all + 4 * e, hi + 6 * e + 1, sizeof(int) * 4);
-        if (edge_status) edge_status[e] = hi[6 * e + 5];
-        ok += hi[6 * e + 5] == kPoseOk ? 1 : 0;
-    }
-    if (n_ok) *n_ok = ok;
-    return 0;
-}
-
-namespace {
-// ---- descriptor matching (sfmba_set_descriptors, sfmba_match_descriptors; kernels: match_kernels.hpp) ----
-void match_release(sfmba_handle* h) {
-    auto& m = h->match;
-    for (DevBuf* b : {&m.raw, &m.rows[0], &m.rows[1], &m.norms[0], &m.norms[1]})
-        if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->bytes = 0; }
-    m.have[0] = m.have[1] = false;
-    m.form = 0;
-    m.img_ptr.clear();
-}
-
-extern "C++" {
-template <bool FB, int NG>
-int match_launch(sfmba_handle* h, size_t n_wg, int f, double ratio2) {
-    auto& m = h->match;
-    const size_t lds = 2 * match_tile_bytes(32 * NG);
-    const void* fn = reinterpret_cast<const void*>(k_match<FB, NG>);
-    if (lds > 65536 && std::find(h->lds_ready.begin(), h->lds_ready.end(), fn) == h->lds_ready.end()) {
-        HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        h->lds_ready.push_back(fn);
-    }
-    hipLaunchKernelGGL((k_match<FB, NG>), dim3((unsigned)n_wg), dim3(kMatchThreads), lds, h->stream,
-                       (const unsigned char*)m.rows[f].as<unsigned char>(), (const void*)m.norms[f].p,
-                       (const MatchEdge*)m.edges.as<MatchEdge>(), (const int2*)m.wgs.as<int2>(), m.n_chunk[f], ratio2,
-                       m.idx.as<int>(), m.dist.as<double>(), m.good.as<unsigned char>());
-    LAUNCHED(h);
-    return 0;
-}
-}  // extern "C++"
-
-// the set in form f (0 = A, 1 = B) from the raw array on the device
-int match_convert(sfmba_handle* h, int f) {
-    auto& m = h->match;
-    if (m.have[f]) return 0;
-    const size_t N = (size_t)m.img_ptr.back();
-    const int D = m.dim;
-    const int bytes = (f == 0 ? 2 : 4) * D;                      // of a row; in 32-byte groups, their number one the kernel is built for
-    int ng = kMatchGroups;
-#define X(n) if (32 * n >= bytes && n < ng) ng = n;
-    MATCH_FOR_EACH_NG(X)
-#undef X
-    m.row_bytes[f] = 32 * ng;
-    m.n_chunk[f] = (bytes + kMatchRowBytes - 1) / kMatchRowBytes;      // (more than one: form B beyond 128 values, full rows)
-    const size_t stride = (size_t)m.row_bytes[f] * (size_t)m.n_chunk[f];
-    CHK(ensure_all(h, {{&m.rows[f], std::max<size_t>(stride * N, 16)}, {&m.norms[f], std::max<size_t>(8 * N, 16)}}));
-    if (N) {
-        const unsigned grid = (unsigned)((N + 255) / 256);
-        if (f == 0)
-            hipLaunchKernelGGL(k_match_convert<false>, dim3(grid), dim3(256), 0, h->stream, (const void*)m.raw.p, m.dtype, N, D,
-                               (int)stride, m.rows[0].as<unsigned char>(), m.norms[0].p);
-        else
-            hipLaunchKernelGGL(k_match_convert<true>, dim3(grid), dim3(256), 0, h->stream, (const void*)m.raw.p, m.dtype, N, D,
-                               (int)stride, m.rows[1].as<unsigned char>(), m.norms[1].p);
-        LAUNCHED(h);
-    }
-    m.have[f] = true;
-    return 0;
-}
-}  // namespace
-
-int sfmba_set_descriptors(sfmba_handle* h, int64_t n_images, const int64_t* img_ptr, const void* desc, int32_t dtype,
-                          int32_t dim, int32_t* form_out) {
-    CHK(enter(h));
-    if (n_images < 0 || !img_ptr) return fail(h, -1, "sfmba_set_descriptors: n_images is negative or img_ptr is NULL");
-    if (n_images >= ((int64_t)1 << 31)) return fail(h, -1, "sfmba_set_descriptors: too many images");
-    if (dim < 1 || dim > kMatchMaxDim) return fail(h, -1, "sfmba_set_descriptors: dim must be 1..%d, got %d", kMatchMaxDim, (int)dim);
-    if (dtype != 0 && dtype != 1) return fail(h, -1, "sfmba_set_descriptors: dtype must be 0 (uint8) or 1 (float32)");
-    if (img_ptr[0] != 0) return fail(h, -1, "sfmba_set_descriptors: img_ptr[0] must be 0");
-    for (int64_t i = 0; i < n_images; ++i) {
-        if (img_ptr[i + 1] < img_ptr[i]) return fail(h, -1, "sfmba_set_descriptors: img_ptr must ascend (image %lld)", (long long)i);
-        if (img_ptr[i + 1] - img_ptr[i] >= ((int64_t)1 << 30))
-            return fail(h, -1, "sfmba_set_descriptors: image %lld has 2^30 descriptors or more", (long long)i);
-    }
-    const size_t N = (size_t)img_ptr[n_images];
-    if (N && !desc) return fail(h, -1, "sfmba_set_descriptors: desc is NULL");
-    auto& m = h->match;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    match_release(h);
-    m.img_ptr.assign(img_ptr, img_ptr + n_images + 1);
-    m.dim = dim; m.dtype = dtype;
-    const size_t raw_bytes = N * (size_t)dim * (dtype ? 4 : 1);
-    CHK(ensure_all(h, {{&m.raw, std::max<size_t>(raw_bytes, 16)}, {&m.flag, sizeof(int)}}));
-    if (raw_bytes) HIPCHK(h, hipMemcpyAsync(m.raw.p, desc, raw_bytes, hipMemcpyHostToDevice, h->stream));
-    // form A: integers 0..255 whose padded row fits one LDS row of fp16
-    bool integer = dim <= kMatchRowBytes / 2;
-    if (integer && dtype == 1 && N) {
-        int flag = 0;
-        HIPCHK(h, hipMemsetAsync(m.flag.p, 0, sizeof(int), h->stream));
-        const size_t n = N * (size_t)dim;
-        const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)h->n_cu * 8);
-        hipLaunchKernelGGL(k_match_check, dim3(grid), dim3(256), 0, h->stream, (const float*)m.raw.as<float>(), n, m.flag.as<int>());
-        LAUNCHED(h);
-        HIPCHK(h, hipMemcpyAsync(&flag, m.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        integer = flag == 0;
-    }
-    m.form = integer ? 1 : 2;
-    const int rc = match_convert(h, m.form - 1);
-    if (rc != 0) { match_release(h); return rc; }
-    const int rw = wait_stream(h);
-    if (rw != 0) { match_release(h); return rw; }
-    if (form_out) *form_out = m.form;
-    return 0;
-}
-
-void sfmba_default_match_options(sfmba_match_options* o) {
-    if (!o) return;
-    memset(o, 0, sizeof *o);
-    o->ratio = 0.5; o->form = 0; o->profile = 0;
-}
-
-int sfmba_match_descriptors(sfmba_handle* h, int64_t n_edges, const int32_t* edges, const sfmba_match_options* opt,
-                            int64_t* query_ptr, int32_t* idx, double* dist_sq, uint8_t* good, int32_t* edge_good,
-                            int32_t* edge_status, int64_t* n_ok, double* kernel_us) {
-    CHK(enter(h));
-    sfmba_match_options o;
-    if (opt) o = *opt; else sfmba_default_match_options(&o);
-    if (!(o.ratio > 0.0)) return fail(h, -1, "sfmba_match_descriptors: ratio must be positive, got %g", o.ratio);
-    if (o.form < 0 || o.form > 2) return fail(h, -1, "sfmba_match_descriptors: form must be 0, 1 or 2");
-    auto& m = h->match;
-    if (!m.form) return fail(h, -1, "sfmba_match_descriptors: call sfmba_set_descriptors first");
-    if (n_edges < 0 || (n_edges && !edges)) return fail(h, -1, "sfmba_match_descriptors: n_edges is negative or edges is NULL");
-    if (o.form == 1 && m.form != 1)
-        return fail(h, -1, "sfmba_match_descriptors: form A asked for, but the descriptors are not integers 0..255 of dim <= %d",
-                    kMatchRowBytes / 2);
-    const int f = o.form == 2 ? 1 : m.form - 1;
-    const int64_t n_images = (int64_t)m.img_ptr.size() - 1;
-    const size_t E = (size_t)n_edges;
-    if (n_ok) *n_ok = 0;
-    if (kernel_us) *kernel_us = 0.0;
-    std::vector<MatchEdge> ed(E);
-    std::vector<int2> wgs;
-    std::vector<int32_t> status(E);
-    size_t Q = 0;
-    for (size_t e = 0; e < E; ++e) {
-        const int64_t u = edges[2 * e], v = edges[2 * e + 1];
-        if (u < 0 || u >= n_images || v < 0 || v >= n_images)
-            return fail(h, -1, "sfmba_match_descriptors: edge %zu names image %lld, the set has %lld", e,
-                        (long long)(u < 0 || u >= n_images ? u : v), (long long)n_images);
-        MatchEdge& d = ed[e];
-        d.qrow = m.img_ptr[u]; d.trow = m.img_ptr[v]; d.out = (long long)Q;
-        d.nq = (int)(m.img_ptr[u + 1] - m.img_ptr[u]); d.nt = (int)(m.img_ptr[v + 1] - m.img_ptr[v]);
-        status[e] = d.nq < 1 || d.nt < 2 ? 1 : 0;
-        if (query_ptr) query_ptr[e] = (int64_t)Q;
-        if (!status[e])
-            for (int q0 = 0; q0 < d.nq; q0 += MATCH_TQ) wgs.push_back(make_int2((int)e, q0));
-        Q += (size_t)d.nq;
-    }
-    if (query_ptr) query_ptr[E] = (int64_t)Q;
-    if (Q >= (size_t)1 << 30 || wgs.size() >= (size_t)1 << 31)
-        return fail(h, -1, "sfmba_match_descriptors: the batch has 2^30 queries or more");
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    CHK(match_convert(h, f));
-    if (!wgs.empty()) {
-        CHK(ensure_all(h, {{&m.edges, sizeof(MatchEdge) * E}, {&m.wgs, sizeof(int2) * wgs.size()}, {&m.idx, sizeof(int) * 2 * Q},
-                           {&m.dist, sizeof(double) * 2 * Q}, {&m.good, Q}}));
-        HIPCHK(h, hipMemcpyAsync(m.edges.p, ed.data(), sizeof(MatchEdge) * E, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(m.wgs.p, wgs.data(), sizeof(int2) * wgs.size(), hipMemcpyHostToDevice, h->stream));
-        const double ratio2 = o.ratio * o.ratio;
-        TwoViewTimer timer;
-        CHK(timer.start(h, o.profile != 0));
-        switch ((f ? 100 : 0) + m.row_bytes[f] / 32) {
-#define X(n) case n: CHK((match_launch<false, n>(h, wgs.size(), f, ratio2))); break; \
-             case 100 + n: CHK((match_launch<true, n>(h, wgs.size(), f, ratio2))); break;
-            MATCH_FOR_EACH_NG(X)
-#undef X
-            default: return fail(h, -3, "sfmba_match_descriptors: no kernel for rows of %d bytes", m.row_bytes[f]);
-        }
-        CHK(timer.stop(h));
-        if (!good && edge_good) m.good_host.resize(Q);
-        HIPCHK(h, download(h, idx, m.idx.p, sizeof(int) * 2 * Q));
-        HIPCHK(h, download(h, dist_sq, m.dist.p, sizeof(double) * 2 * Q));
-        HIPCHK(h, download(h, good ? good : (edge_good ? m.good_host.data() : nullptr), m.good.p, Q));
-        CHK(wait_stream(h));
-        CHK(timer.read(h, kernel_us));
-    }
-    // edges with too few rows: the device wrote nothing of theirs
-    const unsigned char* gsrc = good ? good : m.good_host.data();
-    int64_t ok = 0;
-    for (size_t e = 0; e < E; ++e) {
-        const size_t b = (size_t)ed[e].out, n = (size_t)ed[e].nq;
-        if (status[e]) {
-            if (idx) std::fill(idx + 2 * b, idx + 2 * (b + n), -1);
-            if (dist_sq) std::fill(dist_sq + 2 * b, dist_sq + 2 * (b + n), (double)INFINITY);
-            if (good) std::fill(good + b, good + b + n, (uint8_t)0);
-        }
-        if (edge_good) {
-            int32_t c = 0;
-            if (!status[e]) for (size_t k = b; k < b + n; ++k) c += gsrc[k] ? 1 : 0;
-            edge_good[e] = c;
-        }
-        if (edge_status) edge_status[e] = status[e];
-        ok += status[e] == 0 ? 1 : 0;
-    }
-    if (n_ok) *n_ok = ok;
-    return 0;
-}
-
-namespace {
-// ---- feature tracks (sfmba_build_tracks, sfmba_get_tracks; kernels: track_kernels.hpp, checks: track_inputs.hpp) ----
-void track_release(sfmba_handle* h) {
-    auto& t = h->tracks;
-    for (DevBuf* b : {&t.img_ptr, &t.pairs, &t.parent, &t.size, &t.img, &t.feat_track, &t.members, &t.cursor, &t.comp_off,
-                      &t.verdict, &t.kept_len, &t.track_id, &t.track_off, &t.track_ptr, &t.track_feat, &t.track_image,
-                      &t.sums, &t.tot})
-        if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->bytes = 0; }
-    t.built = false;
-    t.n_tracks = t.T = 0;
-}
-
-extern "C++" {
-// the three launches of one scan over `n_max` entries at the most
-template <class Src>
-int track_scan(sfmba_handle* h, const Src& src, size_t n_max, int slot) {
-    auto& t = h->tracks;
-    const unsigned nb = (unsigned)std::max<size_t>((n_max + kTrackScanItems - 1) / kTrackScanItems, 1);
-    hipLaunchKernelGGL(k_track_scan_reduce<Src>, dim3(nb), dim3(kTrackBlock), 0, h->stream, src, t.sums.as<long long>());
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_track_scan_sums, dim3(1), dim3(kTrackBlock), 0, h->stream, t.sums.as<long long>(), nb,
-                       t.tot.as<long long>(), slot);
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_track_scan_apply<Src>, dim3(nb), dim3(kTrackBlock), 0, h->stream, src, (const long long*)t.sums.as<long long>());
-    LAUNCHED(h);
-    return 0;
-}
-}  // extern "C++"
-}  // namespace
-
-void sfmba_default_track_options(sfmba_track_options* o) {
-    if (!o) return;
-    memset(o, 0, sizeof *o);
-    o->min_length = 2; o->max_length = 0; o->conflicts = 0; o->profile = 0;
-}
-
-int sfmba_build_tracks(sfmba_handle* h, int64_t n_images, const int64_t* img_ptr, int64_t n_edges, const int32_t* edges,
-                       const int64_t* pair_ptr, const int32_t* pairs, const uint8_t* pair_use, const sfmba_track_options* opt,
-                       int32_t* feat_track, int64_t* counts, double* kernel_us) {
-    CHK(enter(h));
-    sfmba_track_options o;
-    if (opt) o = *opt; else sfmba_default_track_options(&o);
-    TrackBatch bt;
-    std::string why;
-    if (track_check_inputs(n_images, img_ptr, n_edges, edges, pair_ptr, pairs, pair_use, o.min_length, o.max_length,
-                           o.conflicts, true, &bt, &why) != 0)
-        return fail(h, -1, "%s", why.c_str());
-    if (n_images >= ((int64_t)1 << 31) - 1) return fail(h, -1, "sfmba_build_tracks: too many images");
-    const size_t N = (size_t)bt.N, Mu = (size_t)bt.Mu;
-    if ((Mu + kTrackBlock - 1) / kTrackBlock >= (size_t)1 << 31) return fail(h, -1, "sfmba_build_tracks: 2^39 used pairs or more");
-    auto& t = h->tracks;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    track_release(h);
-    if (kernel_us) *kernel_us = 0.0;
-    if (counts) std::fill(counts, counts + 6, (int64_t)0);
-    if (Mu == 0) {                                               // no used pair: no component, every feature unmatched
-        if (feat_track) std::fill(feat_track, feat_track + N, (int32_t)kTrackUnmatched);
-        t.built = true;
-        return 0;
-    }
-    // a component has two members or more and every member is an end of a used pair
-    const size_t comps = std::min(N / 2, Mu), memb = std::min(N, 2 * Mu);
-    const size_t nb = std::max<size_t>((N + kTrackScanItems - 1) / kTrackScanItems, 1);
-    CHK(ensure_all(h, {{&t.img_ptr, sizeof(int) * (size_t)(n_images + 1)}, {&t.pairs, sizeof(int2) * Mu},
-                       {&t.parent, sizeof(int) * N}, {&t.size, sizeof(int) * N}, {&t.img, sizeof(int) * N},
-                       {&t.feat_track, sizeof(int) * N}, {&t.members, sizeof(int) * memb}, {&t.cursor, sizeof(int) * comps},
-                       {&t.comp_off, sizeof(long long) * (comps + 1)}, {&t.verdict, sizeof(int) * comps},
-                       {&t.kept_len, sizeof(int) * comps}, {&t.track_id, sizeof(int) * comps},
-                       {&t.track_off, sizeof(long long) * comps}, {&t.track_ptr, sizeof(long long) * (comps + 1)},
-                       {&t.track_feat, sizeof(int) * memb}, {&t.track_image, sizeof(int) * memb},
-                       {&t.sums, sizeof(long long) * 2 * nb}, {&t.tot, sizeof(long long) * kTrackTotSlots}}));
-    std::vector<int> ptr32((size_t)n_images + 1);
-    for (int64_t i = 0; i <= n_images; ++i) ptr32[(size_t)i] = (int)img_ptr[i];
-    HIPCHK(h, hipMemcpyAsync(t.img_ptr.p, ptr32.data(), sizeof(int) * ptr32.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(t.pairs.p, bt.packed.data(), sizeof(int2) * Mu, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));                  // (both sources are pageable and die with this call)
-    TwoViewTimer timer;
-    CHK(timer.start(h, o.profile != 0));
-    HIPCHK(h, hipMemsetAsync(t.tot.p, 0, sizeof(long long) * kTrackTotSlots, h->stream));
-    HIPCHK(h, hipMemsetAsync(t.cursor.p, 0, sizeof(int) * comps, h->stream));
-    const unsigned gN = (unsigned)((N + kTrackBlock - 1) / kTrackBlock);
-    int* const parent = t.parent.as<int>();
-    int* const size = t.size.as<int>();
-    long long* const tot = t.tot.as<long long>();
-    hipLaunchKernelGGL(k_track_init, dim3(gN), dim3(kTrackBlock), 0, h->stream, (int)N, (const int*)t.img_ptr.as<int>(),
-                       (int)n_images, parent, size, t.img.as<int>(), t.feat_track.as<int>());
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_track_union, dim3((unsigned)((Mu + kTrackBlock - 1) / kTrackBlock)), dim3(kTrackBlock), 0, h->stream,
-                       (long long)Mu, (const int2*)t.pairs.as<int2>(), parent);
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_track_flatten, dim3(gN), dim3(kTrackBlock), 0, h->stream, (int)N, parent, size);
-    LAUNCHED(h);
-    CHK(track_scan(h, TrackCompSrc{parent, size, (int)N, t.comp_off.as<long long>(), tot}, N, kTrackTotComps));
-    hipLaunchKernelGGL(k_track_fill, dim3(gN), dim3(kTrackBlock), 0, h->stream, (int)N, (const int*)parent, (const int*)size,
-                       (const long long*)t.comp_off.as<long long>(), t.cursor.as<int>(), t.members.as<int>());
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_track_sort, dim3((unsigned)((comps + kTrackBlock - 1) / kTrackBlock)), dim3(kTrackBlock), 0, h->stream,
-                       (const long long*)t.comp_off.as<long long>(), t.members.as<int>(), (const int*)t.img.as<int>(),
-                       o.min_length, o.max_length, o.conflicts, t.verdict.as<int>(), t.kept_len.as<int>(), tot);
-    LAUNCHED(h);
-    CHK(track_scan(h, TrackKeepSrc{t.kept_len.as<int>(), t.track_id.as<int>(), t.track_off.as<long long>(), tot}, comps,
-                   kTrackTotKept));
-    hipLaunchKernelGGL(k_track_write, dim3((unsigned)((memb + kTrackBlock - 1) / kTrackBlock)), dim3(kTrackBlock), 0, h->stream,
-                       (const int*)t.members.as<int>(), (const int*)parent, (const int*)size,
-                       (const long long*)t.comp_off.as<long long>(), (const int*)t.verdict.as<int>(),
-                       (const int*)t.track_id.as<int>(), (const long long*)t.track_off.as<long long>(),
-                       (const int*)t.img.as<int>(), (const long long*)tot, t.feat_track.as<int>(),
-                       t.track_ptr.as<long long>(), t.track_feat.as<int>(), t.track_image.as<int>());
-    LAUNCHED(h);
-    CHK(timer.stop(h));
-    long long totals[kTrackTotSlots];
-    HIPCHK(h, download(h, totals, tot, sizeof totals));
-    HIPCHK(h, download(h, feat_track, t.feat_track.p, sizeof(int) * N));
-    CHK(wait_stream(h));
-    CHK(timer.read(h, kernel_us));
-    t.n_tracks = totals[kTrackTotKept];
-    t.T = totals[kTrackTotObs];
-    t.built = true;
-    if (counts) {
-        counts[0] = totals[kTrackTotComps]; counts[1] = totals[kTrackTotKept]; counts[2] = totals[kTrackTotShort];
-        counts[3] = totals[kTrackTotLong]; counts[4] = totals[kTrackTotConflict]; counts[5] = totals[kTrackTotObs];
-    }
-    return 0;
-}
-
-int sfmba_get_tracks(sfmba_handle* h, int64_t* track_ptr, int32_t* track_feat, int32_t* track_image) {
-    CHK(enter(h));
-    auto& t = h->tracks;
-    if (!t.built) return fail(h, -1, "sfmba_get_tracks: no tracks built (call sfmba_build_tracks first)");
-    if (t.n_tracks == 0) {
-        if (track_ptr) track_ptr[0] = 0;
-        return 0;
-    }
-    static_assert(sizeof(long long) == sizeof(int64_t), "track_ptr is downloaded as it is");
-    HIPCHK(h, download(h, track_ptr, t.track_ptr.p, sizeof(int64_t) * (size_t)(t.n_tracks + 1)));
-    HIPCHK(h, download(h, track_feat, t.track_feat.p, sizeof(int32_t) * (size_t)t.T));
-    HIPCHK(h, download(h, track_image, t.track_image.p, sizeof(int32_t) * (size_t)t.T));
-    CHK(wait_stream(h));
-    return 0;
-}
-
-void sfmba_default_filter_options(sfmba_filter_options* o) {
-    if (!o) return;
-    memset(o, 0, sizeof *o);
-    o->max_error_px = INFINITY; o->min_depth = -INFINITY; o->min_angle_deg = 0.0; o->min_views = 0;
-}
-
-int sfmba_reprojection_stats(sfmba_handle* h, const double* x, const sfmba_filter_options* opt, double* obs_err,
-                             double* obs_depth, uint8_t* obs_keep, int32_t* pt_views, double* pt_max_err, double* pt_sum_err2,
-                             double* pt_min_depth, double* pt_max_angle_deg, uint8_t* pt_keep, int32_t* cam_views,
-                             double* cam_sum_err, double* cam_max_err, int32_t* cam_behind, sfmba_stats_summary* summary) {
-    CHK(enter(h));
-    CHK(begin_compute(h, x));
-    sfmba_filter_options o;
-    if (opt) o = *opt; else sfmba_default_filter_options(&o);
-    if (std::isnan(o.max_error_px) || std::isnan(o.min_depth) || std::isnan(o.min_angle_deg))
-        return fail(h, -1, "a threshold of the filter options is NaN");
-    const StatsFilter flt = stats_filter(o);
-    auto& s = h->stats;
-    const size_t N = (size_t)h->N, P = (size_t)h->P, C = (size_t)h->C;
-    const bool want_cam = cam_views || cam_sum_err || cam_max_err || cam_behind;
-    int pt_blocks = 1;
-    CHK(stats_allocate(h, &pt_blocks));
-    CHK(stats_prepare(h, x));
-    if (want_cam) CHK(stats_cam_perm(h));
-    CHK(launch_obs_stats(h, flt));
-    CHK(launch_point_stats(h, flt, pt_blocks));
-    if (summary) CHK(launch_stats_summary(h, pt_blocks));
-    if (want_cam) CHK(launch_cam_stats(h));
-    // downloads: only what was asked for; the per-observation arrays through pinned staging, then into the caller's order
-    const bool want_ed = obs_err || obs_depth;
-    if (want_ed || obs_keep) HIPCHK(h, s.host.ensure(17 * N + 64, 0));
-    double* const st_ed = s.host.as<double>();
-    unsigned char* const st_keep = s.host.as<unsigned char>() + 16 * N;
-    if (want_ed) HIPCHK(h, download(h, st_ed, s.ed.p, 16 * N));
-    if (obs_keep) HIPCHK(h, download(h, st_keep, s.keep_final.p, N));
-    const double* pd = s.pt_d.as<double>();
-    HIPCHK(h, download(h, pt_views, s.pt_views.p, sizeof(int32_t) * P));
-    HIPCHK(h, download(h, pt_max_err, pd, sizeof(double) * P));
-    HIPCHK(h, download(h, pt_sum_err2, pd + P, sizeof(double) * P));
-    HIPCHK(h, download(h, pt_min_depth, pd + 2 * P, sizeof(double) * P));
-    HIPCHK(h, download(h, pt_max_angle_deg, pd + 3 * P, sizeof(double) * P));
-    HIPCHK(h, download(h, pt_keep, s.pt_keep.p, P));
-    HIPCHK(h, download(h, cam_views, s.cam_i.p, sizeof(int32_t) * C));
-    HIPCHK(h, download(h, cam_behind, s.cam_i.as<int>() + C, sizeof(int32_t) * C));
-    HIPCHK(h, download(h, cam_sum_err, s.cam_d.p, sizeof(double) * C));
-    HIPCHK(h, download(h, cam_max_err, s.cam_d.as<double>() + C, sizeof(double) * C));
-    double sums[kStatsPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (summary) HIPCHK(h, download(h, sums, s.sum.p, sizeof sums));
-    CHK(wait_stream(h));
-    if (want_ed || obs_keep) {
-        for (size_t k = 0; k < N; ++k) {
-            const size_t d = h->permuted ? (size_t)h->tb.order[k] : k;
-            if (obs_err) obs_err[d] = st_ed[2 * k];
-            if (obs_depth) obs_depth[d] = st_ed[2 * k + 1];
-            if (obs_keep) obs_keep[d] = st_keep[k];
-        }
-    }
-    if (summary) {
-        summary->n_obs = h->N;
-        summary->n_points_kept = (int64_t)sums[0]; summary->n_obs_kept = (int64_t)sums[1]; summary->n_behind = (int64_t)sums[2];
-        summary->sum_err = sums[3]; summary->sum_err2 = sums[4]; summary->max_err = sums[5];
-    }
-    return 0;
-}
 
 int sfmba_residuals(sfmba_handle* h, const double* x, double* r_out) {
     CHK(enter(h));
@@ -3551,10 +1972,10 @@ int sfmba_step_products(sfmba_handle* h, const double* x, const double* sg, cons
     int np1 = 0, np2 = 0;
     CHK(launch_jdot(h, &np1));
     std::vector<double> part1((size_t)np1), t1((size_t)2 * N);
-    HIPCHK(h, hipMemcpyAsync(part1.data(), h->partB(), sizeof(double) * np1, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(part1.data(), partB(h), sizeof(double) * np1, hipMemcpyDeviceToHost, h->stream));
     CHK(launch_backsub(h, &np2, h->vtmp.as<double>()));
     std::vector<double> part2((size_t)np2 * kBacksubCols);
-    HIPCHK(h, hipMemcpyAsync(part2.data(), h->partB(), sizeof(double) * part2.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(part2.data(), partB(h), sizeof(double) * part2.size(), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(t1.data(), h->t1.p, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(dp_out, h->p.as<double>() + 6 * C, sizeof(double) * 3 * P, hipMemcpyDeviceToHost, h->stream));
     if (g_out) HIPCHK(h, hipMemcpyAsync(g_out, h->g_cur, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
@@ -3887,13 +2308,13 @@ int Solve::linear_phase() {
         // slots 1..12 over the ranks when an accepted step left fresh q1..q4 (8..11, sums) and max|g| (12, a
         // maximum by the mask), G11 alone otherwise.  Slots 2..7 (G12, G22, q5..q8 of the previous iteration)
         // are summed once more along the way; nothing reads them before k_backsub's sums rewrite them.
-        const Piggyback pb = sum_rider(h, h->partB(), np, kG11Slot);
+        const Piggyback pb = sum_rider(h, partB(h), np, kG11Slot);
         static_assert(kMaxSlot == 12 && kG11Slot == 1, "mask below assumes the maximum sits at the end of the run");
         CHK(p2p_allreduce(h, sc + kG11Slot, scale_sums_rode ? kMaxSlot : 1, 0, nullptr,
                           scale_sums_rode ? 1ull << (kMaxSlot - 1) : 0ull, &pb));
         ++h->n_collectives;
     } else if (!f.one_rank) {
-        CHK(launch_finish(h, sum_rider(h, h->partB(), np, kG11Slot), h->skip, h->post));
+        CHK(launch_finish(h, sum_rider(h, partB(h), np, kG11Slot), h->skip, h->post));
         if (scale_sums_rode) CHK(exchange_linearise(h));        // q1..q4, max|g| of the accepted point
         CHK(exchange(h, sc + kG11Slot, 1, 0));
     }
@@ -3903,7 +2324,7 @@ int Solve::linear_phase() {
                            h->V.as<double>(), h->gp.as<double>(), h->si_cur, (int)C, (int)P, bc,
                            h->Dc.as<double>(), (f.precond ? (double*)nullptr : h->Minv.as<double>()),
                            vinv_ptr(h), h->rec + 3,
-                           f.one_rank ? (const double*)h->partB() : (const double*)nullptr, np, opt.pcg_tol,
+                           f.one_rank ? (const double*)partB(h) : (const double*)nullptr, np, opt.pcg_tol,
                            std::max(opt.pcg_tol, opt.pcg_tol_max), (const double*)(h->x + 6 * C),
                            (f.use_rhsrec && !f.dense_solve) ? h->rhsrec.as<double>() : (double*)nullptr,   // (read by k_cam_rhs_diag only)
                            f.dense_solve ? MixedPrep{nullptr, nullptr, nullptr, nullptr, Origin{0.0, 0.0, 0.0}} : mixed_prep(h, h->tab));
@@ -4290,5 +2711,3 @@ int sfmba_get_fun_grad(sfmba_handle* h, double* fun_out, double* grad_out) {
 int sfmba_tr2d_solve(const double* B3, const double* g2, double Delta, double* p2) {
     return solve_trust_region_2d(B3, g2, Delta, p2) ? 1 : 0;
 }
-
-}  // extern "C"

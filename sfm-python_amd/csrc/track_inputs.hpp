@@ -1,4 +1,4 @@
-// Validation of the arguments of sfmba_build_tracks, without a device: plain C++ that sfmba.hip calls before any kernel
+// Validation of the arguments of sfmba_build_tracks, without a device: plain C++ that tracks.hip calls before any kernel
 // reads a pair, and that tests/host/track_inputs_check.cpp runs as a stand-alone program under the host sanitizers.
 // DESIGN.md section 23.
 #pragma once
