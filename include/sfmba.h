@@ -637,6 +637,62 @@ int  sfmba_build_tracks(sfmba_handle* h, int64_t n_images, const int64_t* img_pt
                         double* kernel_us);
 int  sfmba_get_tracks(sfmba_handle* h, int64_t* track_ptr, int32_t* track_feat, int32_t* track_image);
 
+/* ---- view planning and problem assembly: the bookkeeping of an incremental reconstruction (sfm.py:59-71, 182-241) ---- */
+/* Every round of the loop of SFM.construct asks which unregistered images see enough triangulated points (_select_edge,
+ * over Node.pts3d_pts2d, graph.py:46-54) and what the index arrays of the problem over a given set of cameras and
+ * tracks are (Graph.pt3ds_pt2ds, graph.py:186-191).  Both are sweeps over what the last successful sfmba_build_tracks
+ * left on the device; n_images and n_tracks below are that build's (n_tracks = counts[1]) and are compared with it.
+ * The calls read the tracks' tables and write buffers of their own: the tracks, the descriptor set, the problem, fun,
+ * grad and a following solve are exactly what they are without these calls.  A mask entry is set when it is not 0.
+ * The results are pure functions of the tracks and the masks: the same bits from call to call.
+ *
+ * sfmba_plan_views: cam_reg (n_images) uint8, the image is registered; trk_known (n_tracks) uint8, the track has a 3-D
+ * point.  Outputs, each may be NULL:
+ *   trk_reg_views (n_tracks) int32  the registered images among the views of track t
+ *   img_tracks (n_images) int32     the features of image i that lie in a kept track
+ *   img_known (n_images) int32      of those, the ones whose track is known: len(feat2point_index) of graph.py:46-54,
+ *                                   the quantity _select_edge scores with
+ *   img_gain (n_images) int32       the features of i whose track is not known and has trk_reg_views[t] - cam_reg[i] >= 1:
+ *                                   the tracks that become (or already are) two-view once i is registered
+ *   totals (3) int64                registered images, known tracks, tracks with trk_known == 0 and trk_reg_views >= 2
+ *   kernel_us                       with profile = 1 the HIP-event time over the launches of the call, else 0
+ *
+ * sfmba_assemble_problem: cam_use (n_images), trk_use (n_tracks).  Observation k of track t is used when trk_use[t] and
+ * cam_use[track_image[k]]; a track is in the sub-problem when it has at least min_views used observations; an image is
+ * in it when cam_use is set and it has at least one used observation of such a track.  counts (3): cameras, points,
+ * observations of the sub-problem.  sfmba_get_assembled then returns it (two calls because the sizes are not known
+ * before the first); any pointer may be NULL:
+ *   cam_of (cameras) int32          image id per sub-camera, ascending
+ *   pt_of (points) int32            track id per sub-point, ascending
+ *   camera_indices, point_indices   (observations) int64, renumbered through cam_of and pt_of: what sfmba_set_problem takes
+ *   obs_feat (observations) int32   global feature id
+ *   points_2d (observations, 2)     the pixels of obs_feat, gathered on the device from the table of sfmba_set_keypoints
+ * in point-major order, ascending by feature id within a point, as the tracks' CSR is.
+ *
+ * sfmba_set_keypoints: the pixel positions pts (N, 2) fp64 of all features, once, with the img_ptr convention of
+ * sfmba_set_descriptors.  Needs no tracks.  The table is compared with the tracks' img_ptr where points_2d is asked for,
+ * and a sfmba_build_tracks with another img_ptr drops it.
+ *
+ * Return -1, with a message that starts with the function's name: sfmba_plan_views, sfmba_assemble_problem and
+ * sfmba_get_assembled before a successful sfmba_build_tracks ("... sfmba_build_tracks first"); a mask of another length
+ * than the build's or NULL; min_views < 1; sfmba_get_assembled before sfmba_assemble_problem on the current tracks, or
+ * with points_2d and no (or another img_ptr's) keypoint table; img_ptr not ascending from 0, N >= 2^31 or a pixel that
+ * is not finite for sfmba_set_keypoints. */
+typedef struct sfmba_plan_options {
+    int32_t min_views;   /* fewest used observations of a track of the sub-problem (2); sfmba_plan_views ignores it */
+    int32_t profile;     /* 1 = kernel_us is measured (0) */
+} sfmba_plan_options;
+void sfmba_default_plan_options(sfmba_plan_options* opt);
+int  sfmba_set_keypoints(sfmba_handle* h, int64_t n_images, const int64_t* img_ptr /* n_images + 1, ascending from 0 */,
+                         const double* pts /* (N,2) */);
+int  sfmba_plan_views(sfmba_handle* h, int64_t n_images, const uint8_t* cam_reg, int64_t n_tracks, const uint8_t* trk_known,
+                      const sfmba_plan_options* opt, int32_t* trk_reg_views, int32_t* img_tracks, int32_t* img_known,
+                      int32_t* img_gain, int64_t* totals /* 3 or NULL */, double* kernel_us);
+int  sfmba_assemble_problem(sfmba_handle* h, int64_t n_images, const uint8_t* cam_use, int64_t n_tracks, const uint8_t* trk_use,
+                            const sfmba_plan_options* opt, int64_t* counts /* 3 or NULL */, double* kernel_us);
+int  sfmba_get_assembled(sfmba_handle* h, int32_t* cam_of, int32_t* pt_of, int64_t* camera_indices, int64_t* point_indices,
+                         int32_t* obs_feat, double* points_2d);
+
 /* ---- least_squares(method='trf', x_scale='jac') (sfm.py:266-268) ---------------------------- */
 /* x_inout: x0 on entry, result.x on success (untouched on failure). */
 int  sfmba_solve(sfmba_handle* h, double* x_inout, const sfmba_options* opt, sfmba_result* out);

@@ -1,5 +1,6 @@
 // handle.hpp -- the handle behind include/sfmba.h and what the library's sources share on the host (internal, host only).
-// sfmba.hip defines every function declared here; consumers.hip, match.hip and tracks.hip hold their stages.
+// sfmba.hip defines every function declared here but one (launch_k_track_scan_sums: tracks.hip); consumers.hip, match.hip,
+// tracks.hip and plan.hip hold their stages.
 #pragma once
 #include "../../include/sfmba.h"
 #include <hip/hip_runtime.h>
@@ -362,7 +363,25 @@ struct sfmba_handle {
         DevBuf sums, tot;                    // [scan workgroups][2]; [kTrackTotSlots]
         bool built = false;
         int64_t n_tracks = 0, T = 0;
+        // what the plan stage reads of the last build besides the tables: its sizes and its img_ptr
+        int64_t n_images = 0, N = 0;
+        std::vector<int64_t> img_ptr_host;
     } tracks;
+    // sfmba_plan_views / sfmba_assemble_problem / sfmba_get_assembled / sfmba_set_keypoints: they read the tables of
+    // `tracks` and write buffers of their own (grow-only), so the tracks, the problem and a solve stay as they are
+    struct Plan {
+        DevBuf cam_mask, trk_mask;           // [n_images], [n_tracks]: the masks of the running call
+        DevBuf trk_views, img_out;           // [n_tracks]; [3][n_images] tracks, known, gain
+        DevBuf kept, pt_id, obs_off, pt_of;  // [n_tracks] used observations of a track of the sub-problem or 0; its number; its first observation; sub-point -> track
+        DevBuf present, cam_id, cam_of;      // [n_images] in the sub-problem; its number; sub-camera -> image
+        DevBuf ci, pi, of, p2d;              // [T] camera_indices, point_indices (64-bit), obs_feat; [T][2] gathered pixels
+        DevBuf sums, tot;                    // [scan workgroups][2]; [kPlanTotSlots]
+        DevBuf kp;                           // [N][2] the keypoint table of sfmba_set_keypoints
+        std::vector<int64_t> kp_img_ptr;     // ... and its img_ptr
+        bool have_kp = false;
+        bool assembled = false;              // counts and the buffers hold a sub-problem of the current tracks
+        int64_t counts[3] = {0, 0, 0};       // cameras, points, observations
+    } plan;
 };
 
 namespace sfmba {
@@ -404,6 +423,9 @@ int stats_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
 int tri_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us);
 int resect_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us);
 int pnp_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us);
+// the middle launch of the scan of track_scan.hpp, compiled in tracks.hip, for the plan stage: `block` and `items` are the
+// caller's kTrackBlock and kTrackScanItems, refused (-3) when they are not the ones the kernel was compiled with
+int launch_k_track_scan_sums(sfmba_handle* h, long long* sums, unsigned nb, long long* tot, int slot, int block, int items);
 
 // device -> host on the handle's stream; an array the caller did not ask for (null) is left out
 inline hipError_t download(sfmba_handle* h, void* dst, const void* src, size_t bytes) {

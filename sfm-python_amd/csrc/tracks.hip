@@ -30,6 +30,15 @@ int track_scan(sfmba_handle* h, const Src& src, size_t n_max, int slot) {
 }
 }  // namespace
 
+int sfmba::launch_k_track_scan_sums(sfmba_handle* h, long long* sums, unsigned nb, long long* tot, int slot, int block, int items) {
+    if (block != kTrackBlock || items != kTrackScanItems)
+        return fail(h, -3, "launch_k_track_scan_sums: the caller scans %d entries with %d threads, the kernel %d with %d", items,
+                    block, kTrackScanItems, kTrackBlock);
+    hipLaunchKernelGGL(k_track_scan_sums, dim3(1), dim3(kTrackBlock), 0, h->stream, sums, nb, tot, slot);
+    LAUNCHED(h);
+    return 0;
+}
+
 void sfmba_default_track_options(sfmba_track_options* o) {
     if (!o) return;
     memset(o, 0, sizeof *o);
@@ -53,6 +62,11 @@ int sfmba_build_tracks(sfmba_handle* h, int64_t n_images, const int64_t* img_ptr
     auto& t = h->tracks;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     track_release(h);
+    // the plan stage: a sub-problem assembled over the previous tracks is gone, and so is a keypoint table of another img_ptr
+    t.n_images = n_images; t.N = bt.N;
+    t.img_ptr_host.assign(img_ptr, img_ptr + n_images + 1);
+    h->plan.assembled = false;
+    if (h->plan.have_kp && h->plan.kp_img_ptr != t.img_ptr_host) h->plan.have_kp = false;
     if (kernel_us) *kernel_us = 0.0;
     if (counts) std::fill(counts, counts + 6, (int64_t)0);
     if (Mu == 0) {                                               // no used pair: no component, every feature unmatched

@@ -28,6 +28,7 @@ SYMBOLS = (
     "sfmba_default_ransac_options", "sfmba_fundamental_ransac", "sfmba_default_pose_options", "sfmba_recover_pose",
     "sfmba_set_descriptors", "sfmba_default_match_options", "sfmba_match_descriptors",
     "sfmba_default_track_options", "sfmba_build_tracks", "sfmba_get_tracks",
+    "sfmba_default_plan_options", "sfmba_set_keypoints", "sfmba_plan_views", "sfmba_assemble_problem", "sfmba_get_assembled",
 )
 
 
@@ -89,6 +90,10 @@ class MatchOptions(C.Structure):
 
 class TrackOptions(C.Structure):
     _fields_ = [("min_length", C.c_int32), ("max_length", C.c_int32), ("conflicts", C.c_int32), ("profile", C.c_int32)]
+
+
+class PlanOptions(C.Structure):
+    _fields_ = [("min_views", C.c_int32), ("profile", C.c_int32)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -218,6 +223,17 @@ def load():
         lib.sfmba_build_tracks.restype = C.c_int
         lib.sfmba_get_tracks.argtypes = [P] * 4
         lib.sfmba_get_tracks.restype = C.c_int
+    if hasattr(lib, "sfmba_plan_views"):             # (likewise)
+        lib.sfmba_default_plan_options.argtypes = [C.POINTER(PlanOptions)]
+        lib.sfmba_default_plan_options.restype = None
+        lib.sfmba_set_keypoints.argtypes = [P, C.c_int64, P, P]
+        lib.sfmba_set_keypoints.restype = C.c_int
+        lib.sfmba_plan_views.argtypes = [P, C.c_int64, P, C.c_int64, P, C.POINTER(PlanOptions)] + [P] * 5 + [C.POINTER(C.c_double)]
+        lib.sfmba_plan_views.restype = C.c_int
+        lib.sfmba_assemble_problem.argtypes = [P, C.c_int64, P, C.c_int64, P, C.POINTER(PlanOptions), P, C.POINTER(C.c_double)]
+        lib.sfmba_assemble_problem.restype = C.c_int
+        lib.sfmba_get_assembled.argtypes = [P] * 7
+        lib.sfmba_get_assembled.restype = C.c_int
     lib.sfmba_tr2d_solve.argtypes = [P, P, C.c_double, P]
     lib.sfmba_comm_get_unique_id.argtypes = [P]
     lib.sfmba_comm_init.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int64]

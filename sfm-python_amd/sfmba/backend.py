@@ -232,6 +232,118 @@ def check_track_inputs(img_ptr, edges, pair_ptr, pairs, pair_use=None, min_lengt
                                                            conflicts=conflicts, profile=int(bool(profile)))
 
 
+def check_plan_inputs(n_images=None, n_tracks=None, cam_mask=None, trk_mask=None, min_views=2, keypoints=None, img_ptr=None):
+    """The arguments of `Backend.plan_views`, `Backend.assemble_problem` and `Backend.set_keypoints`, checked as the C side
+    checks them (csrc/plan_inputs.hpp) -> ``(cam_mask uint8, trk_mask uint8, min_views, pts (N, 2) float64, kp_ptr int64)``.
+    ``n_images`` / ``n_tracks``: the sizes of the last build, None = no masks to check; ``keypoints``: a list of (n_i, 2)
+    pixel arrays, one per image, None = none to check; ``img_ptr``: the tracks' img_ptr the keypoints must agree with.
+    Raises ValueError."""
+    cam = trk = pts = kp_ptr = None
+    if int(min_views) != min_views:
+        raise ValueError(f"min_views must be an integer, got {min_views!r}")
+    min_views = int(min_views)
+    if min_views < 1:
+        raise ValueError(f"min_views must be at least 1, got {min_views}")
+    if n_images is not None:
+        for name, a, n in (("image", cam_mask, int(n_images)), ("track", trk_mask, int(n_tracks))):
+            if a is None:
+                raise ValueError(f"the {name} mask is missing")
+            if np.asarray(a).ndim != 1:
+                raise ValueError(f"the {name} mask must be 1-D, got shape {np.asarray(a).shape}")
+        cam, trk = _mask(cam_mask, int(n_images), "the image mask"), _mask(trk_mask, int(n_tracks), "the track mask")
+    if keypoints is not None:
+        if isinstance(keypoints, np.ndarray) and keypoints.ndim == 2:
+            raise ValueError("keypoints must be a list of (n_i, 2) arrays, one per image, not one array")
+        arrs = [np.asarray(p, dtype=np.float64) for p in keypoints]
+        for k, a in enumerate(arrs):
+            if a.ndim != 2 or a.shape[1] != 2:
+                if a.size:
+                    raise ValueError(f"pixels of image {k} must be (n, 2), got shape {a.shape}")
+                arrs[k] = a.reshape(0, 2)
+            if not np.all(np.isfinite(a)):
+                raise ValueError(f"a pixel of image {k} is not finite")
+        kp_ptr = np.concatenate([[0], np.cumsum([len(a) for a in arrs])]).astype(np.int64)
+        if kp_ptr[-1] >= 2**31:
+            raise ValueError(f"{int(kp_ptr[-1])} features, the limit is 2^31 - 1")
+        if img_ptr is not None:
+            img_ptr = np.asarray(img_ptr, dtype=np.int64).ravel()
+            if img_ptr.shape[0] < 1 or img_ptr[0] != 0 or np.any(np.diff(img_ptr) < 0):
+                raise ValueError("img_ptr must ascend from 0")
+            if not np.array_equal(img_ptr, kp_ptr):
+                raise ValueError("the keypoints' row counts differ from the tracks' img_ptr")
+        pts = np.ascontiguousarray(np.concatenate(arrs, axis=0) if arrs else np.empty((0, 2)))
+    return cam, trk, min_views, pts, kp_ptr
+
+
+class ViewPlan:
+    """What `Backend.plan_views` returns (include/sfmba.h: sfmba_plan_views): the counts a view selection needs.
+    ``cam_reg`` (n_images, bool) and ``trk_known`` (n_tracks, bool): the masks given; ``trk_reg_views`` (n_tracks, int32)
+    registered images among a track's views; ``img_tracks``, ``img_known``, ``img_gain`` (n_images, int32): an image's
+    features in a kept track, those of a known track (``len(feat2point_index)`` of graph.py:46-54), and those of an
+    unknown track that another registered image sees; ``totals``: a dict of ``registered`` images, ``known`` tracks and
+    tracks ``ready`` to be triangulated (unknown, two registered views or more); ``kernel_us`` (``profile=1``, else 0)."""
+
+    def __init__(self, cam_reg, trk_known, trk_reg_views, img_tracks, img_known, img_gain, totals, kernel_us):
+        self.cam_reg, self.trk_known, self.trk_reg_views = cam_reg, trk_known, trk_reg_views
+        self.img_tracks, self.img_known, self.img_gain = img_tracks, img_known, img_gain
+        self.totals = dict(zip(("registered", "known", "ready"), (int(v) for v in totals)))
+        self.kernel_us = float(kernel_us)
+
+    def candidates(self, min_known=7):
+        """The unregistered images with ``img_known >= min_known``, by ``img_known`` descending, ties to the lower id."""
+        idx = np.flatnonzero(~self.cam_reg & (self.img_known >= min_known))
+        return idx[np.lexsort((idx, -self.img_known[idx].astype(np.int64)))]
+
+    def edge_scores(self, edges, n_pairs):
+        """``min(img_known[u], img_known[v]) / n_pairs`` for ``edges`` (E, 2): the score of ``_select_edge`` (sfm.py:195)
+        with the known tracks of the transitive closure in place of ``Node.pts3d_pts2d``."""
+        edges = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+        n_pairs = np.asarray(n_pairs, dtype=np.float64).reshape(-1)
+        if n_pairs.shape[0] != edges.shape[0]:
+            raise ValueError(f"{edges.shape[0]} edges, {n_pairs.shape[0]} pair counts")
+        return np.minimum(self.img_known[edges[:, 0]], self.img_known[edges[:, 1]]) / n_pairs
+
+    def __repr__(self):
+        return f"ViewPlan({', '.join(f'{k}={v}' for k, v in self.totals.items())})"
+
+
+class SubProblem:
+    """What `Backend.assemble_problem` returns (include/sfmba.h: sfmba_assemble_problem, sfmba_get_assembled): the
+    bundle-adjustment problem over a set of images and tracks.  ``cam_of`` (n_cameras, int32) image id per camera and
+    ``pt_of`` (n_points, int32) track id per point, both ascending; ``camera_indices``, ``point_indices`` (n_obs, int64)
+    renumbered through them; ``obs_feat`` (n_obs, int32) global feature ids; ``points_2d`` (n_obs, 2) their pixels, or
+    None when the back end holds no keypoints; point-major, ascending by feature id within a point.  ``counts``: a dict
+    of ``cameras``, ``points``, ``observations``; ``kernel_us`` (``profile=1``, else 0)."""
+
+    def __init__(self, cam_of, pt_of, camera_indices, point_indices, obs_feat, points_2d, kernel_us):
+        self.cam_of, self.pt_of, self.camera_indices, self.point_indices = cam_of, pt_of, camera_indices, point_indices
+        self.obs_feat, self.points_2d, self.kernel_us = obs_feat, points_2d, float(kernel_us)
+        self.n_cameras, self.n_points, self.n_obs = len(cam_of), len(pt_of), len(obs_feat)
+        self.counts = dict(cameras=self.n_cameras, points=self.n_points, observations=self.n_obs)
+
+    def args(self, K):
+        """The tuple of `set_problem` and of ``least_squares(..., args=)``."""
+        if self.points_2d is None:
+            raise ValueError("the sub-problem has no pixels: call set_keypoints before assemble_problem")
+        return (self.n_cameras, self.n_points, self.camera_indices, self.point_indices, self.points_2d, K)
+
+    def gather(self, cameras, points):
+        """``cameras`` (n_images, 6) and ``points`` (n_tracks, 3) -> the parameter vector ``x`` of the sub-problem."""
+        cameras, points = np.asarray(cameras, dtype=np.float64), np.asarray(points, dtype=np.float64)
+        return np.concatenate([cameras[self.cam_of].ravel(), points[self.pt_of].ravel()])
+
+    def scatter(self, x, cameras, points):
+        """The cameras and points of ``x`` written back into ``cameras`` (n_images, 6) and ``points`` (n_tracks, 3)."""
+        x = np.asarray(x, dtype=np.float64).ravel()
+        if x.shape[0] != 6 * self.n_cameras + 3 * self.n_points:
+            raise ValueError(f"x has {x.shape[0]} entries, expected {6 * self.n_cameras + 3 * self.n_points}")
+        cameras[self.cam_of] = x[:6 * self.n_cameras].reshape(-1, 6)
+        points[self.pt_of] = x[6 * self.n_cameras:].reshape(-1, 3)
+
+    def __repr__(self):
+        return f"SubProblem(cameras={self.n_cameras}, points={self.n_points}, observations={self.n_obs})"
+
+
 def check_match_options(ratio=0.5, form=0, profile=0):
     ratio = float(ratio)
     if not ratio > 0.0:
@@ -882,7 +994,65 @@ class Backend:
         track_ptr = np.empty(int(counts[1]) + 1, dtype=np.int64)
         track_feat, track_image = np.empty(int(counts[5]), dtype=np.int32), np.empty(int(counts[5]), dtype=np.int32)
         self._check(self._lib.sfmba_get_tracks(self._h, _capi.ptr(track_ptr), _capi.ptr(track_feat), _capi.ptr(track_image)))
+        self._plan_dims = (len(img_ptr) - 1, int(counts[1]))               # what the masks of the plan stage are checked against
+        if getattr(self, "_kp_ptr", None) is not None and not np.array_equal(self._kp_ptr, img_ptr):
+            self._kp_ptr = None                                          # (the library dropped the table too)
         return Tracks(img_ptr, feat_track, track_ptr, track_feat, track_image, counts, us.value)
+
+    def set_keypoints(self, pts_list):
+        """Put the pixel positions of all features on the device, once: a list of (n_i, 2) arrays, one per image, rows as
+        the tracks' feature rows (include/sfmba.h: sfmba_set_keypoints).  `assemble_problem` gathers ``points_2d`` from
+        it.  Needs no tracks and no problem and leaves both as they are."""
+        _, _, _, pts, ptr = check_plan_inputs(keypoints=pts_list)
+        self._flush_pending()
+        self._check(self._lib.sfmba_set_keypoints(self._h, len(ptr) - 1, _capi.ptr(ptr), _capi.ptr(pts)))
+        self._kp_ptr = ptr
+
+    def _plan_sizes(self):
+        dims = getattr(self, "_plan_dims", None)
+        if dims is None:
+            raise ValueError("call build_tracks first")
+        return dims
+
+    def plan_views(self, cam_reg, trk_known, profile=0):
+        """The counts a view selection needs, from the tracks of the last `build_tracks` (include/sfmba.h:
+        sfmba_plan_views).  ``cam_reg`` (n_images): the image is registered; ``trk_known`` (n_tracks): the track has a 3-D
+        point.  -> :class:`ViewPlan`."""
+        n_images, n_tracks = self._plan_sizes()
+        cam, trk, _, _, _ = check_plan_inputs(n_images, n_tracks, cam_reg, trk_known)
+        opt = _capi.PlanOptions()
+        self._lib.sfmba_default_plan_options(C.byref(opt))
+        opt.profile = int(bool(profile))
+        self._flush_pending()
+        views = np.empty(n_tracks, dtype=np.int32)
+        img_tracks, img_known, img_gain = (np.empty(n_images, dtype=np.int32) for _ in range(3))
+        totals, us = np.zeros(3, dtype=np.int64), C.c_double()
+        self._check(self._lib.sfmba_plan_views(self._h, n_images, _capi.ptr(cam), n_tracks, _capi.ptr(trk), C.byref(opt),
+                                               _capi.ptr(views), _capi.ptr(img_tracks), _capi.ptr(img_known),
+                                               _capi.ptr(img_gain), _capi.ptr(totals), C.byref(us)))
+        return ViewPlan(cam.view(np.bool_), trk.view(np.bool_), views, img_tracks, img_known, img_gain, totals, us.value)
+
+    def assemble_problem(self, cam_use, trk_use, min_views=2, profile=0):
+        """The problem over the images of ``cam_use`` (n_images) and the tracks of ``trk_use`` (n_tracks), from the
+        tracks of the last `build_tracks`: the tracks with at least ``min_views`` observations in used images, the used
+        images that see one of them, renumbered index arrays and -- after `set_keypoints` -- the pixels (include/sfmba.h:
+        sfmba_assemble_problem, sfmba_get_assembled).  -> :class:`SubProblem`."""
+        n_images, n_tracks = self._plan_sizes()
+        cam, trk, min_views, _, _ = check_plan_inputs(n_images, n_tracks, cam_use, trk_use, min_views)
+        opt = _capi.PlanOptions()
+        self._lib.sfmba_default_plan_options(C.byref(opt))
+        opt.min_views, opt.profile = min_views, int(bool(profile))
+        self._flush_pending()
+        counts, us = np.zeros(3, dtype=np.int64), C.c_double()
+        self._check(self._lib.sfmba_assemble_problem(self._h, n_images, _capi.ptr(cam), n_tracks, _capi.ptr(trk), C.byref(opt),
+                                                     _capi.ptr(counts), C.byref(us)))
+        Cn, Pn, Nn = (int(v) for v in counts)
+        cam_of, pt_of = np.empty(Cn, dtype=np.int32), np.empty(Pn, dtype=np.int32)
+        ci, pi, of = np.empty(Nn, dtype=np.int64), np.empty(Nn, dtype=np.int64), np.empty(Nn, dtype=np.int32)
+        uv = np.empty((Nn, 2)) if getattr(self, "_kp_ptr", None) is not None else None
+        self._check(self._lib.sfmba_get_assembled(self._h, _capi.ptr(cam_of), _capi.ptr(pt_of), _capi.ptr(ci), _capi.ptr(pi),
+                                                  _capi.ptr(of), _opt_ptr(uv)))
+        return SubProblem(cam_of, pt_of, ci, pi, of, uv, us.value)
 
     def residual_jacobian(self, x):
         self._flush_pending()

@@ -467,6 +467,238 @@ def build_tracks(matches, n_features, device=0, backend=None, **options):
     return be.build_tracks(*args[:5], **args[5])
 
 
+class Reconstruction:
+    """What :func:`reconstruct` returns.  ``registered`` (n_images, bool); ``cameras`` (n_images, 6): rotation vector and
+    centre, the bundle-adjustment model's parameters, NaN where not registered; ``points`` (n_tracks, 3), NaN where
+    unknown; ``known`` (n_tracks, bool); ``rounds``: one dict per round with ``tried`` and ``registered`` (image ids),
+    ``failed`` (image -> why: the verdict of its resection, "few_views", "degenerate", "behind" or "high_error", or
+    "absent" when none of its features lies in a track of the round's problem), ``points_added``, ``n_obs``
+    (observations of the round's solve) and ``rmse_before`` / ``rmse_after`` of that solve (None when the round had no
+    solve), with ``record_state=True`` also ``registered_before`` and ``known_before``, copies of the two masks the
+    round started from; when images are left unregistered at the end, a closing entry that tried nothing and whose
+    ``failed`` says "few_known" (fewer than ``min_known`` known tracks) or "not_grown" (its resection failed and the
+    number of its known tracks has not grown since); ``tracks``: the :class:`Tracks`;
+    ``problem()`` -> ``(x, args)`` of the final set, ``args`` the tuple of ``least_squares``, with ``cam_of`` / ``pt_of``
+    (image id per camera, track id per point of that problem) and ``obs_feat`` as attributes."""
+
+    def __init__(self, registered, cameras, points, known, rounds, tracks, x, args, cam_of, pt_of, obs_feat):
+        self.registered, self.cameras, self.points, self.known = registered, cameras, points, known
+        self.rounds, self.tracks = rounds, tracks
+        self._x, self._args, self.cam_of, self.pt_of, self.obs_feat = x, args, cam_of, pt_of, obs_feat
+
+    def problem(self):
+        return self._x.copy(), self._args
+
+    def __repr__(self):
+        return (f"Reconstruction(registered={int(self.registered.sum())}/{len(self.registered)}, "
+                f"known={int(self.known.sum())}/{len(self.known)}, rounds={len(self.rounds)})")
+
+
+_RESECT_VERDICTS = {1: "few_views", 2: "degenerate", 3: "behind", 4: "high_error"}
+
+
+def _initial_edge(matches, pts, K, init, be):
+    """-> (u, v, pts of u, pts of v, E) of the first pair: camera u at the identity, v from E's pose."""
+    if init is None:
+        index = select_initial_pair([(pts[m[0]][np.asarray(m[2])[:, 0]], pts[m[1]][np.asarray(m[2])[:, 1]]) for m in matches], K,
+                                    backend=be)[0]
+        if index is None:
+            raise ValueError("no edge qualifies as the initial pair (select_initial_pair)")
+        init = (matches[index][0], matches[index][1])
+    u, v = int(init[0]), int(init[1])
+    for m in matches:
+        if len(m) < 5:
+            continue
+        pairs = np.asarray(m[2]).reshape(-1, 2)
+        if (int(m[0]), int(m[1])) == (u, v):
+            return u, v, pts[u][pairs[:, 0]], pts[v][pairs[:, 1]], np.asarray(m[4], dtype=np.float64)
+        if (int(m[0]), int(m[1])) == (v, u):                      # the same edge the other way round: x_u^T E^T x_v = 0
+            return u, v, pts[u][pairs[:, 1]], pts[v][pairs[:, 0]], np.asarray(m[4], dtype=np.float64).T
+    raise ValueError(f"init = ({u}, {v}) is no edge of `matches` with an essential matrix")
+
+
+def reconstruct(matches, pts, K, tracks=None, init=None, batch=1, min_known=7, filter=True, fix_first=False, ftol=1e-10,
+                ransac_options=None, triangulate_options=None, filter_options=None, filter_rounds=2, max_rounds=None,
+                record_state=False, device=0, backend=None):
+    """Incremental reconstruction, the loop of ``SFM.construct`` (sfm.py:59-71, 182-241) camera by camera on one
+    :class:`Backend`: `plan_views` chooses the next images, `assemble_problem` cuts the growing problem out of the tracks,
+    `resect_ransac` registers, `triangulate` adds points, bundle adjustment and (``filter=True``)
+    :func:`refine_reconstruction` clean up.  DESIGN.md section 25.
+
+    ``matches``: what :func:`match_features` returns, ``(u, v, pairs, F, E)``; ``pts``: list of (n_i, 2) pixel arrays;
+    ``tracks``: the :class:`Tracks` of the last `build_tracks` on ``backend`` over these matches (None: built here);
+    ``init``: ``(u, v)``, an edge of ``matches`` -- u is put at the identity, v at the pose of the edge's ``E`` -- or None:
+    :func:`select_initial_pair`.  Every round takes the ``batch`` best unregistered images (0 = all) that see at least
+    ``min_known`` known tracks (7: the reference's ``> 6``); an image whose resection failed is tried again only after
+    that number has grown.  An observation of a new camera that its RANSAC pose leaves out is dropped for good, and a
+    new point must triangulate within ``max_error_px`` of the trim (unless ``triangulate_options`` says otherwise).
+    ``ransac_options``, ``triangulate_options``: fields of the two calls' option structures;
+    ``filter_options``: ``max_error_px`` (4), ``min_depth`` (0), ``min_angle_deg`` (2), ``min_views`` (2) of the trim
+    and of the final pass; ``fix_first=True`` holds camera u still in every solve (the reference holds nothing).
+    -> :class:`Reconstruction`."""
+    be = backend if backend is not None else api.get_backend(device)
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError("K must be (3, 3)")
+    if int(batch) != batch or batch < 0:
+        raise ValueError(f"batch must be a non-negative integer, got {batch!r}")
+    matches = list(matches)
+    pts = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 2) for p in pts]
+    n_images = len(pts)
+    ransac_options, triangulate_options = dict(ransac_options or {}), dict(triangulate_options or {})
+    thr = dict(max_error_px=4.0, min_depth=0.0, min_angle_deg=2.0, min_views=2)
+    unknown = set(filter_options or {}) - set(thr)
+    if unknown:
+        raise TypeError(f"unknown filter option(s) {sorted(unknown)} (known: {sorted(thr)})")
+    thr.update(filter_options or {})
+    if not filter:
+        thr = dict(max_error_px=np.inf, min_depth=-np.inf, min_angle_deg=0.0, min_views=0)
+    # a new point must pass the pixel threshold of the trim as well: bundle adjustment is a plain least squares, and
+    # one track with a wrong observation bends the cameras until good observations fail the trim that follows it
+    triangulate_options.setdefault("max_error_px", thr["max_error_px"])
+    if tracks is None:
+        tracks = build_tracks(matches, [len(p) for p in pts], backend=be)
+    elif getattr(be, "_plan_dims", None) != (n_images, tracks.n_tracks):
+        raise ValueError("`tracks` is not the result of the last build_tracks on this back end")
+    if len(tracks.img_ptr) - 1 != n_images or any(len(p) != n for p, n in zip(pts, np.diff(tracks.img_ptr))):
+        raise ValueError("`pts` does not have the tracks' number of features per image")
+    be.set_keypoints(pts)
+    be.set_precision(64)
+    n_tracks, N = tracks.n_tracks, int(tracks.img_ptr[-1])
+    registered, known = np.zeros(n_images, dtype=bool), np.zeros(n_tracks, dtype=bool)
+    cameras, points = np.full((n_images, 6), np.nan), np.full((n_tracks, 3), np.nan)
+    feat_ok = np.ones(N, dtype=bool)                             # False: the observation of this feature was dropped for good
+    all_tracks = np.ones(n_tracks, dtype=bool)
+    rounds = []
+
+    def start(sub):                                              # the sub-problem on the handle, and its parameter vector
+        be.set_fixed_cameras(())
+        be.set_problem(*sub.args(K))
+        return np.nan_to_num(sub.gather(cameras, points), nan=0.0)
+
+    def take_points(sub, tri):
+        new = sub.pt_of[tri.ok]
+        points[new], known[new] = tri.points[tri.ok], True
+        return len(new)
+
+    # ---- the initial pair
+    u, v, p1, p2, E = _initial_edge(matches, pts, K, init, be)
+    pose = be.recover_pose(E, p1, p2, K)
+    if pose.status[0] != pose.OK:                                # (a TIE is no start for a reconstruction: select_initial_pair)
+        raise ValueError(f"the pose of the initial pair ({u}, {v}) could not be recovered (status {int(pose.status[0])})")
+    R, t = pose.R[0].reshape(3, 3), pose.t[0].reshape(3)
+    cameras[u] = 0.0
+    cameras[v] = np.concatenate([api._rotvec_from_matrix(R), -R.T @ t])
+    registered[[u, v]] = True
+    sub = be.assemble_problem(registered, all_tracks, min_views=2)
+    if sub.n_obs == 0:
+        raise ValueError(f"images {u} and {v} share no track")
+    take_points(sub, be.triangulate(start(sub), **triangulate_options))
+
+    # ---- the rounds
+    tried_known = np.full(n_images, -1, dtype=np.int64)          # img_known at an image's last failed resection
+    for _ in range(int(max_rounds) if max_rounds is not None else 2 * n_images + 2):
+        plan = be.plan_views(registered, known)
+        cand = plan.candidates(min_known)
+        cand = cand[plan.img_known[cand] > tried_known[cand]]
+        if batch:
+            cand = cand[:int(batch)]
+        if len(cand) == 0:
+            left = np.flatnonzero(~registered)
+            if len(left):
+                rounds.append(dict(tried=[], registered=[], points_added=0, n_obs=0, rmse_before=None, rmse_after=None,
+                                   failed={int(i): "few_known" if plan.img_known[i] < min_known else "not_grown" for i in left}))
+            break
+        use = registered.copy()
+        use[cand] = True
+        sub = be.assemble_problem(use, all_tracks, min_views=2)
+        x = start(sub)
+        obs_ok = feat_ok[sub.obs_feat]
+        resect_use = known[sub.pt_of][sub.point_indices] & obs_ok
+        rr = be.resect_ransac(x, select=np.isin(sub.cam_of, cand), obs_use=resect_use, **ransac_options)
+        info = dict(tried=[int(i) for i in cand], registered=[], failed={}, points_added=0, n_obs=0, rmse_before=None,
+                    rmse_after=None)
+        if record_state:
+            info["registered_before"], info["known_before"] = plan.cam_reg.copy(), plan.trk_known.copy()
+        position = {int(i): c for c, i in enumerate(sub.cam_of)}
+        for i in (int(i) for i in cand):
+            c = position.get(i)
+            if c is not None and rr.ok[c]:
+                cameras[i], registered[i] = rr.cameras[c], True
+                info["registered"].append(i)
+            else:
+                tried_known[i] = plan.img_known[i]
+                info["failed"][i] = "absent" if c is None else _RESECT_VERDICTS.get(int(rr.status[c]), str(int(rr.status[c])))
+        rounds.append(info)
+        if not info["registered"]:
+            break
+        # what a new camera's pose does not agree with is a wrong 2-D--3-D match: dropped for good
+        new_cam = np.isin(sub.cam_of, info["registered"])
+        feat_ok[sub.obs_feat[resect_use & new_cam[sub.camera_indices] & ~rr.inlier_mask]] = False
+        obs_ok = feat_ok[sub.obs_feat]
+        x = np.nan_to_num(sub.gather(cameras, points), nan=0.0)
+        tri = be.triangulate(x, select=~known[sub.pt_of], obs_use=registered[sub.cam_of][sub.camera_indices] & obs_ok,
+                             **triangulate_options)
+        info["points_added"] = take_points(sub, tri)
+        # bundle adjustment over the registered cameras and the known tracks, without the observations dropped so far
+        x, args, cam_of, pt_of, obs_feat = _final_set(be, registered, known, feat_ok, cameras, points, K)
+        info["n_obs"] = len(obs_feat)
+        for k in range(max(int(filter_rounds), 1) if filter else 1):
+            kw = dict(ftol=ftol)
+            if fix_first:
+                kw["jac_sparsity"] = api.create_sparsity_matrix(args[0], args[1], len(obs_feat), args[2], args[3],
+                                                                fixed_camera_indices=(int(np.flatnonzero(cam_of == u)[0]),))
+            if not filter:
+                result = api.least_squares(api.compute_residuals, x, x_scale="jac", method="trf", args=args, backend=be, **kw)
+                x = result.x
+            else:
+                pidx = np.asarray(args[3])
+                result, (x, args), (oi, pi), _ = refine_reconstruction(x, args, rounds=1, backend=be, **thr, **kw)
+                lost_pt = np.ones(len(pt_of), dtype=bool)
+                lost_pt[pi] = False
+                lost_obs = np.ones(len(obs_feat), dtype=bool)
+                lost_obs[oi] = False
+                # an observation that went while its point stayed failed its own test: dropped for good; a track
+                # that went loses its point and may be triangulated again
+                feat_ok[obs_feat[lost_obs & ~lost_pt[pidx]]] = False
+                known[pt_of[lost_pt]] = False
+                points[pt_of[lost_pt]] = np.nan
+                pt_of, obs_feat = pt_of[pi], obs_feat[oi]
+            if k == 0:
+                info["rmse_before"] = float(result.rmse0)
+            info["rmse_after"] = float(result.rmse)
+            if not filter or not (lost_pt.any() or lost_obs.any()):
+                break
+        cameras[cam_of] = x[:6 * len(cam_of)].reshape(-1, 6)
+        points[pt_of] = x[6 * len(cam_of):].reshape(-1, 3)
+
+    # ---- what the result contains: one statistics pass with the same thresholds
+    x, args, cam_of, pt_of, obs_feat = _final_set(be, registered, known, feat_ok, cameras, points, K)
+    if len(obs_feat):
+        be.set_fixed_cameras(())
+        be.set_problem(*args)
+        st = be.reprojection_stats(x, want=("obs", "points"), **thr)
+        if st.n_obs_kept < st.n_obs or st.n_points_kept < args[1]:
+            lost = pt_of[~st.pt_keep]
+            known[lost], points[lost] = False, np.nan
+            x, args, oi, pi = prune_problem(x, args, st.obs_keep, st.pt_keep)
+            pt_of, obs_feat = pt_of[pi], obs_feat[oi]
+    return Reconstruction(registered, cameras, points, known, rounds, tracks, x, args, cam_of, pt_of, obs_feat)
+
+
+def _final_set(be, registered, known, feat_ok, cameras, points, K):
+    """The problem over the registered cameras and the known tracks without the dropped observations ->
+    ``(x, args, cam_of, pt_of, obs_feat)``; a track left with fewer than two observations goes (its point stays known)."""
+    sub = be.assemble_problem(registered, known, min_views=2)
+    x, args = sub.gather(cameras, points), sub.args(K)
+    keep = feat_ok[sub.obs_feat]
+    if keep.all():
+        return x, args, sub.cam_of, sub.pt_of, sub.obs_feat
+    pt_keep = np.bincount(sub.point_indices[keep], minlength=sub.n_points) >= 2
+    x, args, oi, pi = prune_problem(x, args, keep, pt_keep)
+    return x, args, sub.cam_of, sub.pt_of[pi], sub.obs_feat[oi]
+
+
 def load_calibration_data(txt_path):
     """3x3 whitespace-separated text -> ndarray, /root/reference/sfm_lite/utils.py:24-35."""
     K = np.array([[float(v) for v in line.split()] for line in open(txt_path) if line.strip()])
