@@ -106,10 +106,14 @@ __device__ __forceinline__ void store_pair(double* __restrict__ base, int f32, i
 
 // The table buffer holds three views of the same data: rows [C][17] (K1, K2, the camera-major passes), the
 // compact [C][12] = R | T that the recomputing Schur pass stages in LDS, and w, b, c plane-major [5][C] for its
-// one-thread-per-camera prologue.
+// one-thread-per-camera prologue.  Between the last two a fourth, compact [C][12] = M | T with M = K R (the intrinsics
+// carried through the rotation once per camera; 16-byte aligned for every C): what the fp64 row-form kernels stage
+// instead of R | T, since the projection and the rows of d r/d X need R only as K R:
+//     p = M v,   j_k = (M_k - (p_k / p_z) M_3) / p_z.
 constexpr int kCamRT = 12, kCamWbc = 5;
 __host__ __device__ constexpr size_t cam_rt_offset(int C) { return (size_t)C * kCamRow; }
-__host__ __device__ constexpr size_t cam_wbc_offset(int C) { return cam_rt_offset(C) + (size_t)C * kCamRT; }
+__host__ __device__ constexpr size_t cam_mt_offset(int C) { return cam_rt_offset(C) + (size_t)C * kCamRT; }
+__host__ __device__ constexpr size_t cam_wbc_offset(int C) { return cam_mt_offset(C) + (size_t)C * kCamRT; }
 __host__ __device__ constexpr size_t cam_table_doubles(int C) { return cam_wbc_offset(C) + (size_t)C * kCamWbc; }
 // the 17 entries of one camera's row: R (9), T (3), w (3), b, c  (t may be global or LDS)
 __device__ __forceinline__ void cam_row_values(const double* __restrict__ prm, double* __restrict__ t) {

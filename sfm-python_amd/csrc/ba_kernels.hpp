@@ -193,25 +193,41 @@ __device__ __forceinline__ size_t jaddr_f32(int i, int m) {       // in float4 u
 // bundle_adjustment.py:25, which the reference rebuilds per OBSERVATION), and the coefficients of the
 // right Jacobian Jr = I - b [w]x + c [w]x^2 used by d r / d w.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void cam_table_row(const double* __restrict__ prm, double* __restrict__ tab, int C, int c) {
-    double* __restrict__ t = tab + (size_t)c * kCamRow;
+__device__ __forceinline__ void cam_table_row(const double* __restrict__ prm, const KMat& K, double* __restrict__ tab, int C,
+                                              int c) {
+    // The row in registers, then the views.  One camera per lane: the rows of a wave lie 144 / 96 bytes apart, every store
+    // instruction touches 64 lines whatever its width, and the camera blocks are the critical path of k_step_table -- so
+    // the three row-major views go out as 16-byte stores (9 + 6 + 6 instead of 18 + 12 + 12 of 8 bytes).
+    double t[kCamRow];
     t[kCamTab] = 0.0;
     cam_row_values(prm, t);
-    double* __restrict__ rt = tab + cam_rt_offset(C) + (size_t)c * kCamRT;
+    double m[kCamRT];                                                            // M = K R | T (see ba_device.hpp)
 #pragma unroll
-    for (int k = 0; k < kCamRT; ++k) rt[k] = t[k];
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) m[3 * i + j] = K.k[3 * i] * t[j] + K.k[3 * i + 1] * t[3 + j] + K.k[3 * i + 2] * t[6 + j];
+    }
+#pragma unroll
+    for (int k = 9; k < kCamRT; ++k) m[k] = t[k];
+    double* __restrict__ row = tab + (size_t)c * kCamRow;
+    double* __restrict__ rt = tab + cam_rt_offset(C) + (size_t)c * kCamRT;
+    double* __restrict__ mt = tab + cam_mt_offset(C) + (size_t)c * kCamRT;
+#pragma unroll
+    for (int k = 0; k < kCamRow; k += 2) st16(row + k, t[k], t[k + 1]);
+#pragma unroll
+    for (int k = 0; k < kCamRT; k += 2) { st16(rt + k, t[k], t[k + 1]); st16(mt + k, m[k], m[k + 1]); }
     double* __restrict__ wbc = tab + cam_wbc_offset(C);
 #pragma unroll
     for (int k = 0; k < kCamWbc; ++k) wbc[(size_t)k * C + c] = t[12 + k];
 }
 
-__global__ void k_cam_table(const double* __restrict__ xc, int C, double* __restrict__ tab) {
+__global__ void k_cam_table(const double* __restrict__ xc, int C, KMat K, double* __restrict__ tab) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     double prm[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) prm[k] = xc[6 * (size_t)c + k];
-    cam_table_row(prm, tab, C, c);
+    cam_table_row(prm, K, tab, C, c);
 }
 
 // Delta < 0 stands for "first iteration of a solve": the radius is |x0 * scale_inv| (SCIPY trf.py:428), 1 when that is
@@ -253,7 +269,7 @@ __global__ __launch_bounds__(256) void k_step_table(const double* __restrict__ x
                                                     const double* __restrict__ sg,
                                                     const double* __restrict__ p, double c1, double c2,
                                                     const double* __restrict__ coef,
-                                                    int C, int64_t n, int bc, double* __restrict__ x_new,
+                                                    int C, int64_t n, int bc, KMat K, double* __restrict__ x_new,
                                                     double* __restrict__ tab, double* __restrict__ rec_new,
                                                     const double* __restrict__ skip) {
     if (skip != nullptr && *skip != 0.0) return;   // speculative launch cancelled by k_tr_step
@@ -268,7 +284,7 @@ __global__ __launch_bounds__(256) void k_step_table(const double* __restrict__ x
             prm[k] = x[e] + c1 * sg[e] + c2 * p[e];
             x_new[e] = prm[k];
         }
-        cam_table_row(prm, tab, C, c);
+        cam_table_row(prm, K, tab, C, c);
         return;
     }
     const int64_t n6 = 6 * (int64_t)C;
@@ -295,7 +311,7 @@ __global__ void k_fill_rec(const double* __restrict__ pts, int P, double* __rest
 
 // k_cam_table and k_fill_rec of a freshly uploaded parameter vector as ONE launch: blocks [0, bc) take one camera per
 // thread, the remaining blocks the point coordinates (the split of k_step_table)
-__global__ __launch_bounds__(256) void k_cam_table_rec(const double* __restrict__ x, int C, int P, int bc,
+__global__ __launch_bounds__(256) void k_cam_table_rec(const double* __restrict__ x, int C, int P, int bc, KMat K,
                                                        double* __restrict__ tab, double* __restrict__ rec) {
     if ((int)blockIdx.x < bc) {
         const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -303,7 +319,7 @@ __global__ __launch_bounds__(256) void k_cam_table_rec(const double* __restrict_
         double prm[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) prm[k] = x[6 * (size_t)c + k];
-        cam_table_row(prm, tab, C, c);
+        cam_table_row(prm, K, tab, C, c);
         return;
     }
     const int q = ((int)blockIdx.x - bc) * blockDim.x + threadIdx.x;
@@ -1797,13 +1813,75 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep(
 //     row k of d r/d w . u_w = -(j_k x v) . a',   a' = u_w - b (w x u_w) + c (w x (w x u_w))
 //     (Jc u)_k = -j_k . g,   g = v x a' + u_T,          y_p = sum_i Jp_i^T (Jc_i u),   z_p = Vinv_p y_p
 // (the identity (m x w).u = m.(w x u) moves the rotation Jacobian from the observation to the camera), so the
-// LDS table holds 18 doubles per camera, R | T | a' | u_T, 144 KB at 1000 cameras: R | T copied from the compact
-// view of the camera table, a' and u_T built per launch from u by one thread per camera.  Per observation: 8 B of
-// indices from HBM, 144 B from LDS, ~90 flop -- against 104 B from HBM for the form that reads J.
+// LDS table holds 18 doubles per camera, M | T | a' | u_T with M = K R, 144 KB at 1000 cameras: M | T copied from its
+// compact view of the camera table, a' and u_T built per launch from u by one thread per camera.  Per observation: 8 B
+// of indices from HBM, 144 B from LDS, ~60 flop -- against 104 B from HBM for the form that reads J.  (R enters the
+// projection and the rows j_k only as K R; with R in the row, carrying K through it per observation was 50 of ~90 flop.)
 constexpr int kRcRow = 18;
 constexpr int kRcMaxCams = 1100;          // 18 doubles x C within the 160 KiB LDS (FUSED additionally needs C <= 1024)
 
-// The table of the recomputing pass A in global memory (GTAB): R | T | a' | u_T per camera, 18 doubles, for the vector
+// The rows of d r/d X of one observation from its camera's M = K R and v = X - T:
+//     p = M v,   j_k = (M_k - (p_k / p_z) M_3) / p_z       (= row k of A R with A = d pi/d p K)
+// ONE expression for pass A, the exact-block branch of pass B and the row-form consumers: the two passes apply the same
+// bits of j, so that the product stays that of one symmetric matrix.
+__device__ __forceinline__ void kr_rows(const double (&M)[9], double vx, double vy, double vz, double* __restrict__ j) {
+    const double px = M[0] * vx + M[1] * vy + M[2] * vz;
+    const double py = M[3] * vx + M[4] * vy + M[5] * vz;
+    const double pz = M[6] * vx + M[7] * vy + M[8] * vz;
+    const double iz = 1.0 / pz;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double pk = (k == 0 ? px : py) * iz;
+        j[3 * k + 0] = (M[3 * k + 0] - pk * M[6]) * iz;
+        j[3 * k + 1] = (M[3 * k + 1] - pk * M[7]) * iz;
+        j[3 * k + 2] = (M[3 * k + 2] - pk * M[8]) * iz;
+    }
+}
+// The table prologue of the row-form kernels in two halves.  w, b, c of a camera depend on nothing the launch computes:
+// a kernel whose vector u is only known behind a block reduction (the PCG step in the prologue of the fused pass A, the
+// FinalUpdate of k_backsub_rc) requests them BEFORE it, next to the loads of the reduction itself, and only FMAs and LDS
+// writes follow it.
+struct RcWbc { double wx, wy, wz, b, cc; };
+__device__ __forceinline__ RcWbc rc_load_wbc(const double* __restrict__ wbc, int C, int cam) {
+    return {wbc[cam], wbc[(size_t)C + cam], wbc[2 * (size_t)C + cam], wbc[3 * (size_t)C + cam], wbc[4 * (size_t)C + cam]};
+}
+// a' and u_T of camera `cam` from its six entries u, into the camera's row of the table
+__device__ __forceinline__ void rc_put_au(const RcWbc& q, int cam, const double* u, double* __restrict__ tab) {
+    const double wx = q.wx, wy = q.wy, wz = q.wz, b = q.b, cc = q.cc;
+    const double c0 = wy * u[2] - wz * u[1], c1 = wz * u[0] - wx * u[2], c2 = wx * u[1] - wy * u[0];   // w x u_w
+    const double d0 = wy * c2 - wz * c1, d1 = wz * c0 - wx * c2, d2 = wx * c1 - wy * c0;               // w x (w x u_w)
+    double* __restrict__ row = tab + (size_t)kRcRow * cam;
+    row[12] = u[0] - b * c0 + cc * d0; row[13] = u[1] - b * c1 + cc * d1; row[14] = u[2] - b * c2 + cc * d2;
+    row[15] = u[3]; row[16] = u[4]; row[17] = u[5];
+}
+__device__ __forceinline__ void rc_put_au(const double* __restrict__ wbc, int C, int cam, const double* u,
+                                          double* __restrict__ tab) {
+    rc_put_au(rc_load_wbc(wbc, C, cam), cam, u, tab);
+}
+// M | T of every camera into the table: 6 x 16 bytes per camera, coalesced; ends with the barrier
+__device__ __forceinline__ void rc_stage_mt(const double* __restrict__ mt, int C, double* __restrict__ tab_lds) {
+    for (int e = threadIdx.x; e < C * (kCamRT / 2); e += blockDim.x) {
+        const int cam = e / (kCamRT / 2), k = e - cam * (kCamRT / 2);
+        reinterpret_cast<double2*>(tab_lds + (size_t)kRcRow * cam)[k] = reinterpret_cast<const double2*>(mt)[e];
+    }
+    __syncthreads();
+}
+// One observation from its camera's row M | T | a' | u_T (nine 16-byte pieces) and its point: j (2x3 row-major) and
+// t_k = (Jc u)_k = -j_k . (v x a' + u_T).
+__device__ __forceinline__ void rc_row_products(const double2* __restrict__ row, double X, double Y, double Z,
+                                                double* __restrict__ j, double* __restrict__ t) {
+    const double2 m01 = row[0], m23 = row[1], m45 = row[2], m67 = row[3], m8t = row[4], t12 = row[5];
+    const double2 a01 = row[6], a2u = row[7], u12 = row[8];
+    const double M[9] = {m01.x, m01.y, m23.x, m23.y, m45.x, m45.y, m67.x, m67.y, m8t.x};
+    const double vx = X - m8t.y, vy = Y - t12.x, vz = Z - t12.y;
+    kr_rows(M, vx, vy, vz, j);
+    const double ax = a01.x, ay = a01.y, az = a2u.x;
+    const double g0 = vy * az - vz * ay + a2u.y, g1 = vz * ax - vx * az + u12.x, g2 = vx * ay - vy * ax + u12.y;   // v x a' + u_T
+#pragma unroll
+    for (int k = 0; k < 2; ++k) t[k] = -(j[3 * k] * g0 + j[3 * k + 1] * g1 + j[3 * k + 2] * g2);
+}
+
+// The table of the recomputing pass A in global memory (GTAB): M | T | a' | u_T per camera, 18 doubles, for the vector
 // u of the current PCG iterate (u_planes: plane-major [6][C]; with ctrl2 the base of the vector sets, as in the sweep).
 __global__ __launch_bounds__(256) void k_rc_table(const double* __restrict__ camtab, const double* __restrict__ u_planes,
                                                   const PcgCtrl* __restrict__ ctrl2, int L, int C,
@@ -1815,20 +1893,14 @@ __global__ __launch_bounds__(256) void k_rc_table(const double* __restrict__ cam
     }
     const int cam = blockIdx.x * blockDim.x + threadIdx.x;
     if (cam >= C) return;
-    const double* __restrict__ rt = camtab + cam_rt_offset(C) + (size_t)kCamRT * cam;
-    const double* __restrict__ wbc = camtab + cam_wbc_offset(C);
+    const double* __restrict__ mt = camtab + cam_mt_offset(C) + (size_t)kCamRT * cam;
     double* __restrict__ row = rctab + (size_t)kRcRow * cam;
 #pragma unroll
-    for (int k = 0; k < kCamRT; ++k) row[k] = rt[k];
+    for (int k = 0; k < kCamRT; ++k) row[k] = mt[k];
     double u[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) u[k] = u_planes[(size_t)k * C + cam];
-    const double wx = wbc[cam], wy = wbc[(size_t)C + cam], wz = wbc[2 * (size_t)C + cam];
-    const double b = wbc[3 * (size_t)C + cam], cc = wbc[4 * (size_t)C + cam];
-    const double c0 = wy * u[2] - wz * u[1], c1 = wz * u[0] - wx * u[2], c2 = wx * u[1] - wy * u[0];   // w x u_w
-    const double d0 = wy * c2 - wz * c1, d1 = wz * c0 - wx * c2, d2 = wx * c1 - wy * c0;               // w x (w x u_w)
-    row[12] = u[0] - b * c0 + cc * d0; row[13] = u[1] - b * c1 + cc * d1; row[14] = u[2] - b * c2 + cc * d2;
-    row[15] = u[3]; row[16] = u[4]; row[17] = u[5];
+    rc_put_au(camtab + cam_wbc_offset(C), C, cam, u, rctab);
 }
 
 // the same table with fp32 operands (mixed-precision product): [C][20] float = R | T - o (from rt32) | a' | u_T . .
@@ -1896,18 +1968,11 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep_rc(
     int c = 0, p = 0, cn = 0, pn = 0;
     if (cur.y <= 64 && lane < cur.y) { c = cam_idx[cur.x + lane]; p = pt_idx[cur.x + lane]; }
     if (nxt.y <= 64 && lane < nxt.y) { cn = cam_idx[nxt.x + lane]; pn = pt_idx[nxt.x + lane]; }
-    const double* __restrict__ rt = camtab + cam_rt_offset(C);                    // compact [C][12] = R | T
     const double* __restrict__ wbc = camtab + cam_wbc_offset(C);                  // w, b, c plane-major [5][C]
-    auto put_au = [&](int cam, const double* u) {          // a' and u_T of camera `cam` from its u (6)
-        const double wx = wbc[cam], wy = wbc[(size_t)C + cam], wz = wbc[2 * (size_t)C + cam];
-        const double b = wbc[3 * (size_t)C + cam], cc = wbc[4 * (size_t)C + cam];
-        const double c0 = wy * u[2] - wz * u[1], c1 = wz * u[0] - wx * u[2], c2 = wx * u[1] - wy * u[0];   // w x u_w
-        const double d0 = wy * c2 - wz * c1, d1 = wz * c0 - wx * c2, d2 = wx * c1 - wy * c0;               // w x (w x u_w)
-        double* __restrict__ row = smem + (size_t)kRcRow * cam;
-        row[12] = u[0] - b * c0 + cc * d0; row[13] = u[1] - b * c1 + cc * d1; row[14] = u[2] - b * c2 + cc * d2;
-        row[15] = u[3]; row[16] = u[4]; row[17] = u[5];
-    };
+    auto put_au = [&](int cam, const double* u) { rc_put_au(wbc, C, cam, u, smem); };
     if (FUSED) {
+        // (w, b, c requested before the update's reduction, as k_backsub_rc does: five more doubles live across it, and
+        // this kernel, at its 128 registers, spills 36 bytes per lane -- left behind the reduction)
         double uu[6];
         if (!pcg_fused_update(pf, acc, C, L, uu)) return;
         if ((int)threadIdx.x < C) put_au(threadIdx.x, uu);
@@ -1926,13 +1991,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep_rc(
             }
         }
     }
-    if (!GTAB) {
-        for (int e = threadIdx.x; e < C * (kCamRT / 2); e += blockDim.x) {     // R | T: 6 x 16 bytes per camera, coalesced
-            const int cam = e / (kCamRT / 2), k = e - cam * (kCamRT / 2);
-            reinterpret_cast<double2*>(smem + (size_t)kRcRow * cam)[k] = reinterpret_cast<const double2*>(rt)[e];
-        }
-        __syncthreads();
-    }
+    if (!GTAB) rc_stage_mt(camtab + cam_mt_offset(C), C, smem);           // compact [C][12] = M | T
     const double* __restrict__ table = GTAB ? rctab : smem;
     // GTAB: the rows of a step are gathered through the wave's LDS slab (rows_request, see k_resjac); a point with more
     // than 64 observations reads its rows from global memory as before
@@ -1941,34 +2000,11 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep_rc(
 
     // y contribution of one observation from its camera row (nine 16-byte pieces) and its point X
     auto contrib = [&](const double2* __restrict__ row, double X, double Y, double Z, double* y) {
-        const double2 r01 = row[0], r23 = row[1], r45 = row[2], r67 = row[3], r8t = row[4], t12 = row[5];
-        const double2 a01 = row[6], a2u = row[7], u12 = row[8];
-        const double R0 = r01.x, R1 = r01.y, R2 = r23.x, R3 = r23.y, R4 = r45.x, R5 = r45.y, R6 = r67.x, R7 = r67.y,
-                     R8 = r8t.x;
-        const double vx = X - r8t.y, vy = Y - t12.x, vz = Z - t12.y;
-        const double qx = R0 * vx + R1 * vy + R2 * vz;
-        const double qy = R3 * vx + R4 * vy + R5 * vz;
-        const double qz = R6 * vx + R7 * vy + R8 * vz;
-        const double px = K.k[0] * qx + K.k[1] * qy + K.k[2] * qz;
-        const double py = K.k[3] * qx + K.k[4] * qy + K.k[5] * qz;
-        const double pz = K.k[6] * qx + K.k[7] * qy + K.k[8] * qz;
-        const double iz = 1.0 / pz;
-        // g = v x a' + u_T
-        const double ax = a01.x, ay = a01.y, az = a2u.x;
-        const double g0 = vy * az - vz * ay + a2u.y, g1 = vz * ax - vx * az + u12.x, g2 = vx * ay - vy * ax + u12.y;
+        double j[6], t[2];
+        rc_row_products(row, X, Y, Z, j, t);
         y[0] = 0.0; y[1] = 0.0; y[2] = 0.0;
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const double pk = (k == 0 ? px : py) * iz;
-            const double b0 = (K.k[3 * k + 0] - pk * K.k[6]) * iz;
-            const double b1 = (K.k[3 * k + 1] - pk * K.k[7]) * iz;
-            const double b2 = (K.k[3 * k + 2] - pk * K.k[8]) * iz;
-            const double j0 = b0 * R0 + b1 * R3 + b2 * R6;            // row k of A R
-            const double j1 = b0 * R1 + b1 * R4 + b2 * R7;
-            const double j2 = b0 * R2 + b1 * R5 + b2 * R8;
-            const double tk = -(j0 * g0 + j1 * g1 + j2 * g2);        // (Jc u)_k
-            y[0] += j0 * tk; y[1] += j1 * tk; y[2] += j2 * tk;
-        }
+        for (int k = 0; k < 2; ++k) { y[0] += j[3 * k] * t[k]; y[1] += j[3 * k + 1] * t[k]; y[2] += j[3 * k + 2] * t[k]; }
     };
     auto row_of = [&](int cc) { return reinterpret_cast<const double2*>(table + (size_t)kRcRow * cc); };
 
@@ -2384,6 +2420,13 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur(CamMajor cm, const do
 #pragma unroll
         for (int k = 0; k < 3; ++k) { ap[k] = (double)(float)ap[k]; vT[k] = (double)(float)vT[k]; }
     }
+    // The fp64 product takes its rows j_k from M = K R (kr_rows), as pass A does: the same bits in both passes
+    constexpr bool KR = MODE == 0 && !ROUND && !MIXED;
+    double Mk[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (KR) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Mk[k] = camtab[cam_mt_offset(C) + (size_t)ch.x * kCamRT + k];      // wave-uniform: scalar loads
+    }
     double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k0 = ch.y + (int)threadIdx.x; k0 < ch.z; k0 += kCamThreads * kCamUnroll) {      // see k_cam_blocks
         int p[kCamUnroll];
@@ -2430,13 +2473,28 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur(CamMajor cm, const do
                 for (int q = 0; q < 6; ++q) a[q] += jc[q] * u0 + jc[6 + q] * u1;
             } else {
                 const double vx = X[u][0] - t[9], vy = X[u][1] - t[10], vz = X[u][2] - t[11];
-                const double qx = t[0] * vx + t[1] * vy + t[2] * vz;
-                const double qy = t[3] * vx + t[4] * vy + t[5] * vz;
-                const double qz = t[6] * vx + t[7] * vy + t[8] * vz;
-                const double px = K.k[0] * qx + K.k[1] * qy + K.k[2] * qz;
-                const double py = K.k[3] * qx + K.k[4] * qy + K.k[5] * qz;
-                const double pz = K.k[6] * qx + K.k[7] * qy + K.k[8] * qz;
-                const double iz = 1.0 / pz;
+                double j[6];
+                if (KR) {
+                    kr_rows(Mk, vx, vy, vz, j);
+                } else {
+                    const double qx = t[0] * vx + t[1] * vy + t[2] * vz;
+                    const double qy = t[3] * vx + t[4] * vy + t[5] * vz;
+                    const double qz = t[6] * vx + t[7] * vy + t[8] * vz;
+                    const double px = K.k[0] * qx + K.k[1] * qy + K.k[2] * qz;
+                    const double py = K.k[3] * qx + K.k[4] * qy + K.k[5] * qz;
+                    const double pz = K.k[6] * qx + K.k[7] * qy + K.k[8] * qz;
+                    const double iz = 1.0 / pz;
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const double pk = (k == 0 ? px : py) * iz;
+                        const double b0 = (K.k[3 * k + 0] - pk * K.k[6]) * iz;
+                        const double b1 = (K.k[3 * k + 1] - pk * K.k[7]) * iz;
+                        const double b2 = (K.k[3 * k + 2] - pk * K.k[8]) * iz;
+                        j[3 * k + 0] = b0 * t[0] + b1 * t[3] + b2 * t[6];
+                        j[3 * k + 1] = b0 * t[1] + b1 * t[4] + b2 * t[7];
+                        j[3 * k + 2] = b0 * t[2] + b1 * t[5] + b2 * t[8];
+                    }
+                }
                 double h0 = z[u][0], h1 = z[u][1], h2 = z[u][2];
                 if (MODE == 0) {
                     h0 += vy * ap[2] - vz * ap[1] + vT[0];
@@ -2446,13 +2504,7 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur(CamMajor cm, const do
                 double s0 = 0.0, s1 = 0.0, s2 = 0.0;             // q = sum_k u_k j_k
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
-                    const double pk = (k == 0 ? px : py) * iz;
-                    const double b0 = (K.k[3 * k + 0] - pk * K.k[6]) * iz;
-                    const double b1 = (K.k[3 * k + 1] - pk * K.k[7]) * iz;
-                    const double b2 = (K.k[3 * k + 2] - pk * K.k[8]) * iz;
-                    const double j0 = b0 * t[0] + b1 * t[3] + b2 * t[6];
-                    const double j1 = b0 * t[1] + b1 * t[4] + b2 * t[7];
-                    const double j2 = b0 * t[2] + b1 * t[5] + b2 * t[8];
+                    const double j0 = j[3 * k], j1 = j[3 * k + 1], j2 = j[3 * k + 2];
                     const double uk = -(j0 * h0 + j1 * h1 + j2 * h2);
                     s0 += uk * j0; s1 += uk * j1; s2 += uk * j2;
                 }
@@ -2578,6 +2630,11 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur_w(CamMajor cm, const 
 #pragma unroll
         for (int k = 0; k < 3; ++k) { ap[k] = (double)(float)ap[k]; vT[k] = (double)(float)vT[k]; }
     }
+    double Mk[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // fp64 operands: the rows from M = K R, as in k_cam_schur
+    if (!MIXED) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Mk[k] = camtab[cam_mt_offset(C) + (size_t)ch.x * kCamRT + k];
+    }
     double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k0 = ch.y + lane; k0 < ch.z; k0 += 64 * kCamUnroll) {
         int p[kCamUnroll];
@@ -2606,26 +2663,35 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur_w(CamMajor cm, const 
         for (int u = 0; u < kCamUnroll; ++u) {
             if (p[u] < 0) continue;
             const double vx = X[u][0] - t[9], vy = X[u][1] - t[10], vz = X[u][2] - t[11];
-            const double qx = t[0] * vx + t[1] * vy + t[2] * vz;
-            const double qy = t[3] * vx + t[4] * vy + t[5] * vz;
-            const double qz = t[6] * vx + t[7] * vy + t[8] * vz;
-            const double px = K.k[0] * qx + K.k[1] * qy + K.k[2] * qz;
-            const double py = K.k[3] * qx + K.k[4] * qy + K.k[5] * qz;
-            const double pz = K.k[6] * qx + K.k[7] * qy + K.k[8] * qz;
-            const double iz = 1.0 / pz;
+            double j[6];
+            if (!MIXED) {
+                kr_rows(Mk, vx, vy, vz, j);
+            } else {
+                const double qx = t[0] * vx + t[1] * vy + t[2] * vz;
+                const double qy = t[3] * vx + t[4] * vy + t[5] * vz;
+                const double qz = t[6] * vx + t[7] * vy + t[8] * vz;
+                const double px = K.k[0] * qx + K.k[1] * qy + K.k[2] * qz;
+                const double py = K.k[3] * qx + K.k[4] * qy + K.k[5] * qz;
+                const double pz = K.k[6] * qx + K.k[7] * qy + K.k[8] * qz;
+                const double iz = 1.0 / pz;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const double pk = (k == 0 ? px : py) * iz;
+                    const double b0 = (K.k[3 * k + 0] - pk * K.k[6]) * iz;
+                    const double b1 = (K.k[3 * k + 1] - pk * K.k[7]) * iz;
+                    const double b2 = (K.k[3 * k + 2] - pk * K.k[8]) * iz;
+                    j[3 * k + 0] = b0 * t[0] + b1 * t[3] + b2 * t[6];
+                    j[3 * k + 1] = b0 * t[1] + b1 * t[4] + b2 * t[7];
+                    j[3 * k + 2] = b0 * t[2] + b1 * t[5] + b2 * t[8];
+                }
+            }
             const double h0 = z[u][0] + vy * ap[2] - vz * ap[1] + vT[0];
             const double h1 = z[u][1] + vz * ap[0] - vx * ap[2] + vT[1];
             const double h2 = z[u][2] + vx * ap[1] - vy * ap[0] + vT[2];
             double s0 = 0.0, s1 = 0.0, s2 = 0.0;             // q = sum_k u_k j_k
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                const double pk = (k == 0 ? px : py) * iz;
-                const double b0 = (K.k[3 * k + 0] - pk * K.k[6]) * iz;
-                const double b1 = (K.k[3 * k + 1] - pk * K.k[7]) * iz;
-                const double b2 = (K.k[3 * k + 2] - pk * K.k[8]) * iz;
-                const double j0 = b0 * t[0] + b1 * t[3] + b2 * t[6];
-                const double j1 = b0 * t[1] + b1 * t[4] + b2 * t[7];
-                const double j2 = b0 * t[2] + b1 * t[5] + b2 * t[8];
+                const double j0 = j[3 * k], j1 = j[3 * k + 1], j2 = j[3 * k + 2];
                 const double uk = -(j0 * h0 + j1 * h1 + j2 * h2);
                 s0 += uk * j0; s1 += uk * j1; s2 += uk * j2;
             }
@@ -3524,10 +3590,13 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub(
         pos += n_take;
     }
     {   // camera slice (dc is camera-major like x), a few elements per workgroup so that none straggles;
-        // after the sweep, so that its four sums are not live across it
+        // after the sweep, so that its four sums are not live across it.  (More than one trip only where a workgroup's
+        // share exceeds its threads: fewer than six observations per camera.)
         const int per = (6 * C + (int)gridDim.x - 1) / (int)gridDim.x;
-        const int e = (int)blockIdx.x * per + (int)threadIdx.x;
-        if ((int)threadIdx.x < per && e < 6 * C) dots(qs + 4, (size_t)e, vv[e]);
+        for (int t = threadIdx.x; t < per; t += blockDim.x) {
+            const int e = (int)blockIdx.x * per + t;
+            if (e < 6 * C) dots(qs + 4, (size_t)e, vv[e]);
+        }
     }
     double row[kBacksubCols];
     row[0] = wave_sum(g12);
@@ -3548,62 +3617,13 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub(
 
 // ---------------------------------------------------------------------------------------------
 // k_jdot and k_backsub in ROW FORM (Forms::rc_cons): the two products with the whole Jacobian, J (D^2 g) and J p, taken
-// the way pass A (k_point_sweep_rc) takes Jc u -- from the LDS table R | T | a' | u_T of the vector's camera slice and the
+// the way pass A (k_point_sweep_rc) takes Jc u -- from the LDS table M | T | a' | u_T of the vector's camera slice and the
 // point, without the stored blocks (96 of the 120 bytes those kernels read per observation):
-//     j_k = row k of d r / d X (the same expressions as observe<true>: the same bits as the stored point block),
+//     j_k = row k of d r / d X (kr_rows, from M = K R: equal to the stored point block up to rounding),
 //     (Jc u)_k = -j_k . (v x a' + u_T),       (J [u; w])_k = (Jc u)_k + j_k . w_p.
 // 64-bit storage only: with 32-bit storage the consumers have to apply the stored, rounded blocks.
 // ---------------------------------------------------------------------------------------------
-// a' and u_T of camera `cam` from its six entries u (put_au of pass A)
-__device__ __forceinline__ void rc_put_au(const double* __restrict__ wbc, int C, int cam, const double* u,
-                                          double* __restrict__ tab_lds) {
-    const double wx = wbc[cam], wy = wbc[(size_t)C + cam], wz = wbc[2 * (size_t)C + cam];
-    const double b = wbc[3 * (size_t)C + cam], cc = wbc[4 * (size_t)C + cam];
-    const double c0 = wy * u[2] - wz * u[1], c1 = wz * u[0] - wx * u[2], c2 = wx * u[1] - wy * u[0];   // w x u_w
-    const double d0 = wy * c2 - wz * c1, d1 = wz * c0 - wx * c2, d2 = wx * c1 - wy * c0;               // w x (w x u_w)
-    double* __restrict__ row = tab_lds + (size_t)kRcRow * cam;
-    row[12] = u[0] - b * c0 + cc * d0; row[13] = u[1] - b * c1 + cc * d1; row[14] = u[2] - b * c2 + cc * d2;
-    row[15] = u[3]; row[16] = u[4]; row[17] = u[5];
-}
-// R | T of every camera into the table: 6 x 16 bytes per camera, coalesced; ends with the barrier
-__device__ __forceinline__ void rc_stage_rt(const double* __restrict__ rt, int C, double* __restrict__ tab_lds) {
-    for (int e = threadIdx.x; e < C * (kCamRT / 2); e += blockDim.x) {
-        const int cam = e / (kCamRT / 2), k = e - cam * (kCamRT / 2);
-        reinterpret_cast<double2*>(tab_lds + (size_t)kRcRow * cam)[k] = reinterpret_cast<const double2*>(rt)[e];
-    }
-    __syncthreads();
-}
-// One observation from its camera's row (nine 16-byte pieces) and its point: j (2x3 row-major) and t_k = (Jc u)_k.
-// The arithmetic of `contrib` in k_point_sweep_rc.
-__device__ __forceinline__ void rc_row_products(const double2* __restrict__ row, const KMat& K, double X, double Y, double Z,
-                                                double* __restrict__ j, double* __restrict__ t) {
-    const double2 r01 = row[0], r23 = row[1], r45 = row[2], r67 = row[3], r8t = row[4], t12 = row[5];
-    const double2 a01 = row[6], a2u = row[7], u12 = row[8];
-    const double R0 = r01.x, R1 = r01.y, R2 = r23.x, R3 = r23.y, R4 = r45.x, R5 = r45.y, R6 = r67.x, R7 = r67.y,
-                 R8 = r8t.x;
-    const double vx = X - r8t.y, vy = Y - t12.x, vz = Z - t12.y;
-    const double qx = R0 * vx + R1 * vy + R2 * vz;
-    const double qy = R3 * vx + R4 * vy + R5 * vz;
-    const double qz = R6 * vx + R7 * vy + R8 * vz;
-    const double px = K.k[0] * qx + K.k[1] * qy + K.k[2] * qz;
-    const double py = K.k[3] * qx + K.k[4] * qy + K.k[5] * qz;
-    const double pz = K.k[6] * qx + K.k[7] * qy + K.k[8] * qz;
-    const double iz = 1.0 / pz;
-    const double ax = a01.x, ay = a01.y, az = a2u.x;
-    const double g0 = vy * az - vz * ay + a2u.y, g1 = vz * ax - vx * az + u12.x, g2 = vx * ay - vy * ax + u12.y;   // v x a' + u_T
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const double pk = (k == 0 ? px : py) * iz;
-        const double b0 = (K.k[3 * k + 0] - pk * K.k[6]) * iz;
-        const double b1 = (K.k[3 * k + 1] - pk * K.k[7]) * iz;
-        const double b2 = (K.k[3 * k + 2] - pk * K.k[8]) * iz;
-        const double j0 = b0 * R0 + b1 * R3 + b2 * R6;            // row k of A R
-        const double j1 = b0 * R1 + b1 * R4 + b2 * R7;
-        const double j2 = b0 * R2 + b1 * R5 + b2 * R8;
-        j[3 * k + 0] = j0; j[3 * k + 1] = j1; j[3 * k + 2] = j2;
-        t[k] = -(j0 * g0 + j1 * g1 + j2 * g2);
-    }
-}
+// (rc_put_au, rc_stage_mt and rc_row_products: beside pass A, which shares them)
 
 // k_jdot in row form: t1 = J (D^2 g), sum |t1|^2.  Same grid, rider workgroup and part[block] as k_jdot.
 __global__ __launch_bounds__(kSweepThreads) void k_jdot_rc(
@@ -3624,7 +3644,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_jdot_rc(
         const double u[6] = {u01.x, u01.y, u23.x, u23.y, u45.x, u45.y};
         rc_put_au(camtab + cam_wbc_offset(C), C, cam, u, smem);
     }
-    rc_stage_rt(camtab + cam_rt_offset(C), C, smem);
+    rc_stage_mt(camtab + cam_mt_offset(C), C, smem);
     double acc = 0.0;
     while (i < N) {
         const int in = i + stride;
@@ -3634,7 +3654,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_jdot_rc(
         const double* __restrict__ b = sgp + 3 * (size_t)p;
         const double X = Xp[0], Y = Xp[1], Z = Xp[2], b0 = b[0], b1 = b[1], b2 = b[2];
         double j[6], t[2];
-        rc_row_products(reinterpret_cast<const double2*>(smem + (size_t)kRcRow * c), K, X, Y, Z, j, t);
+        rc_row_products(reinterpret_cast<const double2*>(smem + (size_t)kRcRow * c), X, Y, Z, j, t);
         const double t0 = t[0] + (j[0] * b0 + j[1] * b1 + j[2] * b2);
         const double t1v = t[1] + (j[3] * b0 + j[4] * b1 + j[5] * b2);
         reinterpret_cast<double2*>(t1)[i] = make_double2(t0, t1v);
@@ -3673,12 +3693,14 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
         const PcgCtrl ci = fu.ctrl2[fu.L & 1];
         PcgCtrl co = ci;
         double xe[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, pe[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        RcWbc q = {0.0, 0.0, 0.0, 0.0, 0.0};
         if (cam < C) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
                 xe[k] = fu.vecs[kPcgX * n6 + (size_t)k * C + cam];
                 pe[k] = fu.vecs[kPcgP * n6 + (size_t)k * C + cam];
             }
+            q = rc_load_wbc(wbc, C, cam);                                 // in flight under the reduction, like x and p
         }
         if (ci.done == 0) alpha = pcg_local_step(fu.part, C, ci, co);     // (else: finished earlier than the record says)
         if (blockIdx.x == 0 && threadIdx.x == 0) fu.ctrl2[(fu.L + 1) & 1] = co;
@@ -3691,7 +3713,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
                 u[k] = add ? fma(alpha, pe[k], xe[k]) : xe[k];
                 if (blockIdx.x == 0) dc[6 * cam + k] = u[k];              // (the step vector only: see k_backsub)
             }
-            rc_put_au(wbc, C, cam, u, smem);
+            rc_put_au(q, cam, u, smem);
         }
     } else {
         if (ctrl2 != nullptr)                      // dc_planes = base of the PCG vector sets: take x of the final set
@@ -3706,7 +3728,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
             rc_put_au(wbc, C, cam, u, smem);
         }
     }
-    rc_stage_rt(camtab + cam_rt_offset(C), C, smem);
+    rc_stage_mt(camtab + cam_mt_offset(C), C, smem);
     const int wg = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     int pos = 0, end = 0;
@@ -3714,7 +3736,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
     double g12 = 0.0, g22 = 0.0;
     double qs[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};       // q5..q8: [0..3] points, [4..7] cameras
     auto products = [&](int j, double X, double Y, double Z, double* jp, double* t) {      // observation j, its point
-        rc_row_products(reinterpret_cast<const double2*>(smem + (size_t)kRcRow * cam_idx[j]), K, X, Y, Z, jp, t);
+        rc_row_products(reinterpret_cast<const double2*>(smem + (size_t)kRcRow * cam_idx[j]), X, Y, Z, jp, t);
     };
     // point entries: g is g_p itself and D^2 g = g / s^2 exactly as k_update_scale formed it
     auto point_dots = [&](int p, const double* s3, double z0, double z1, double z2) {
@@ -3796,8 +3818,9 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
     {   // camera slice, a few elements per workgroup so that none straggles; after the sweep, so that its four sums
         // are not live across it.  Element e = 6 cam + k of the step, formed as the prologue formed it.
         const int per = (n6 + (int)gridDim.x - 1) / (int)gridDim.x;
-        const int e = (int)blockIdx.x * per + (int)threadIdx.x;
-        if ((int)threadIdx.x < per && e < n6) {
+        for (int t = threadIdx.x; t < per; t += blockDim.x) {   // (more than one trip: see k_backsub)
+            const int e = (int)blockIdx.x * per + t;
+            if (e >= n6) break;
             const int cam = e / 6, k = e - 6 * cam;
             double pe;
             if (final_update) {

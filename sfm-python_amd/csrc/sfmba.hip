@@ -126,7 +126,7 @@ int opt_in_lds(sfmba_handle* h, const void* kernel, size_t bytes) {
 }
 
 int launch_k_cam_table(sfmba_handle* h, const double* x, double* tab) {
-    hipLaunchKernelGGL(k_cam_table, dim3((unsigned)((h->C + 255) / 256)), dim3(256), 0, h->stream, x, (int)h->C, tab);
+    hipLaunchKernelGGL(k_cam_table, dim3((unsigned)((h->C + 255) / 256)), dim3(256), 0, h->stream, x, (int)h->C, h->K, tab);
     LAUNCHED(h);
     return 0;
 }
@@ -545,7 +545,7 @@ int launch_cam_table(sfmba_handle* h, const double* x, double* tab, double* rec,
     if (one_launch) {
         const int bc = (int)((h->C + 255) / 256);
         hipLaunchKernelGGL(k_cam_table_rec, dim3((unsigned)(bc + (3 * h->P + 255) / 256)), dim3(256), 0, h->stream, x,
-                           (int)h->C, (int)h->P, bc, tab, rec);
+                           (int)h->C, (int)h->P, bc, h->K, tab, rec);
         LAUNCHED(h);
         return 0;
     }
@@ -2370,7 +2370,7 @@ int Solve::tail() {
 int Solve::enqueue_trial(const double* coef_dev, double c1, double c2) {
     const int bc = (int)((C + 255) / 256);
     hipLaunchKernelGGL(k_step_table, dim3(bc + grid_1d(3 * P, 256, 2048)), dim3(256), 0, h->stream, h->x,
-                       h->sg_cur, h->p.as<double>(), c1, c2, coef_dev, (int)C, n, bc, h->x_new,
+                       h->sg_cur, h->p.as<double>(), c1, c2, coef_dev, (int)C, n, bc, h->K, h->x_new,
                        h->tab_new, h->rec_new, h->skip);
     LAUNCHED(h);
     if (h->mirror_on) {                                         // x_new to its host mirror, beside the evaluation below
