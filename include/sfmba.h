@@ -526,6 +526,53 @@ int  sfmba_fundamental_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* e
                               const sfmba_ransac_options* opt, double* F, double* F_refit, uint8_t* inlier_mask,
                               int32_t* edge_inliers, int32_t* edge_best, uint8_t* edge_success, int32_t* edge_status,
                               int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us);
+/* sfmba_homography_ransac: a homography x2 ~ H x1 by RANSAC for every edge, H = max_iters hypotheses each, without early
+ * exit: the sibling of sfmba_fundamental_ransac (what cv2.findHomography(.., cv2.RANSAC) estimates before its refinement).
+ * The batch (n_edges, edge_ptr, pts1, pts2, pair_use, "used pairs") and sfmba_ransac_options are those of the F call;
+ * a batch with a mask gives bit for bit what the batch with those pairs removed gives.  No atomics, sums in a fixed
+ * order: same input, same bits.  Buffers are shared with the F call and grow only; neither call changes what the other,
+ * or a following solve, computes.
+ *   hypothesis  four used pairs: each image's four points minus their column means, over ONE scale, the standard
+ *               deviation of all 8 coordinates together (np.std(pts), the normalisation of the F call); T1 and T2 are the
+ *               matrices that do this, T = [[1/s, 0, -mx/s], [0, 1/s, -my/s], [0, 0, 1]].  A normalised pair (x, y) -> (u, v)
+ *               gives the two rows
+ *                 [-x, -y, -1,  0,  0,  0, u x, u y, u]
+ *                 [ 0,  0,  0, -x, -y, -1, v x, v y, v]
+ *               of the 8 x 9 matrix A, the four first rows before the four second rows; h = the eigenvector of the
+ *               smallest eigenvalue of A^T A (the cyclic Jacobi of the F call: pairs (0,1), (0,2), .., (7,8), until the
+ *               off-diagonal part is 1e-40 of the diagonal, at most 30 sweeps), Hn = h as 3 x 3 row-major; then
+ *               H = T2^-1 Hn T1 with T2^-1 = [[s2, 0, m2x], [0, s2, m2y], [0, 0, 1]] in closed form.
+ *   score       q = H (x1, y1, 1); d2 = (q0/q2 - x2)^2 + (q1/q2 - y2)^2; the pair is an inlier when d2 is finite and
+ *               STRICTLY below threshold^2.  One-sided in image 2, as cv2.findHomography's and as the F call's.
+ *   best        the largest inlier count, the lowest h among equals
+ *   samples     given: (n_edges, H, 4) int32 positions among the used pairs; a position outside 0 .. n-1 makes the call
+ *               return -1, a sample with a repeated position is invalid: its count is -1.  NULL: drawn by the counter-based
+ *               rule of the F call with four draws: key = mix(seed ^ mix(e << 32 | h)); draw j = 0..3:
+ *               k = mix(key + (j + 1) 0x9e3779b97f4a7c15) mod (n - j); then, for every earlier choice c in ascending
+ *               order of c, if (k >= c) ++k
+ *   finish      inlier_mask and edge_inliers are evaluated once more from the best H (one place decides count, success,
+ *               status and the refit's pairs).
+ *   refit = 1   H_refit: the same estimate over ALL inliers of the best hypothesis: means and scale over the inliers,
+ *               both rows of every inlier, the 45 sums of A^T A in a fixed order, the same Jacobi, denormalised.  When the
+ *               result is not finite, H_refit is a copy of H.  refit_mask and edge_refit_inliers: the used pairs scored
+ *               against H_refit AS RETURNED (unit norm) with the expression of the score.
+ *               refit = 0, or a status other than 0: H_refit, refit_mask and edge_refit_inliers are copies of H,
+ *               inlier_mask and edge_inliers.
+ * Hm and H_refit (n_edges,9) have unit Frobenius norm and their entry of largest magnitude (the first of equals)
+ * positive.  inlier_mask, refit_mask (M): 0 for pairs that took no part.  edge_inliers, edge_best: count and h of the best
+ * hypothesis.  edge_success: inliers / n >= confidence.  edge_status: 0 OK; 1 FEW_PAIRS (n < 4): count 0, best -1, empty
+ * masks, every hyp_inliers entry -1; 2 DEGENERATE (no hypothesis with a finite H and at least 4 inliers): both H are zero,
+ * the count, h and mask of the best hypothesis are still reported (best -1 and an empty mask when no sample was valid).
+ * hyp_inliers (n_edges,H): the count of every hypothesis (-1: invalid sample, or FEW_PAIRS).  n_ok: edges with status 0.
+ * kernel_us: with profile = 1 the HIP-event time of the call's launches, else 0.  Every output pointer may be NULL.
+ * Returns -1 for a malformed batch, a NaN option, max_iters < 1 or a sample position outside 0 .. n-1.
+ * Not done here: the LM refinement cv2 runs after its RANSAC, a symmetric transfer error, the orientation / collinearity
+ * pre-test of a sample, the decomposition of H into poses, adaptive exit. */
+int  sfmba_homography_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edge_ptr, const double* pts1, const double* pts2,
+                             const uint8_t* pair_use /* M or NULL = all */, const int32_t* samples /* (n_edges,H,4) or NULL = drawn */,
+                             const sfmba_ransac_options* opt, double* Hm, double* H_refit, uint8_t* inlier_mask,
+                             uint8_t* refit_mask, int32_t* edge_inliers, int32_t* edge_refit_inliers, int32_t* edge_best,
+                             uint8_t* edge_success, int32_t* edge_status, int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us);
 typedef struct sfmba_pose_options {
     double  min_depth;   /* a pair is in front when both depths are above this (0.0) */
     int32_t profile;     /* 1 = kernel_us is measured (0) */

@@ -1181,6 +1181,9 @@ __global__ __launch_bounds__(kCamThreads) void k_resect(ResectIn in, int C, KMat
 //                   A workgroup leaves the best (count, h, F) of its slice in a slot of its own.
 //   k_fund_finish   one workgroup per edge: best slot (largest count, lowest h), the mask of that F, the refit over all
 //                   its inliers (sums by block_sum, the 9x9 Jacobi by wave 0), unit norm and sign.
+//   k_homog_ransac, k_homog_finish   the same two for a homography (sfmba_homography_ransac): four
+//                   sampled pairs, the DLT's eight rows, the same Jacobi, T2^-1 Hn T1, the transfer distance in image 2;
+//                   the finish adds the mask and count of the refit.
 //   k_recover_pose  one workgroup per edge: wave 0 decomposes E into the four (R, t), every pair is triangulated against
 //                   each (two-view DLT, smallest_eigenvector4) and counted in front; thread 0 decides; a second pass
 //                   writes the winner's points, mask, ray angles and the summed reprojection error.
@@ -1190,7 +1193,7 @@ constexpr int kTwoViewThreads = 256;
 constexpr int kTwoViewWaves = 4;
 constexpr int kTwoViewLdsPairs = 4096;   // an edge of up to this many used pairs is staged in LDS (128 KiB of the 160)
 constexpr int kTwoViewMinSlice = 8;      // fewest hypotheses of a workgroup's slice (two per wave)
-constexpr int kTwoViewSlot = 12;         // doubles of a slot: count, h, F (9), unused
+constexpr int kTwoViewSlot = 12;         // doubles of a slot: count, h, F or H (9), unused
 constexpr int kJacobiLdsSweeps = 30;     // cap of the sweeps of jacobi_lds (a 9x9 converges in 5..9)
 constexpr int kFundOk = 0, kFundFewPairs = 1, kFundDegenerate = 2;
 constexpr int kPoseOk = 0, kPoseFewPairs = 1, kPoseDegenerate = 2, kPoseTie = 3;
@@ -1233,18 +1236,20 @@ __device__ __forceinline__ void jacobi_lds(volatile double* A, volatile double* 
     }
 }
 
-// the counter-based sample rule (include/sfmba.h): eight distinct positions among n >= 8, a function of (seed, e, h) alone
+// the counter-based sample rule (include/sfmba.h): S distinct positions among n >= S, a function of (seed, e, h) alone
 __host__ __device__ __forceinline__ unsigned long long twoview_mix(unsigned long long z) {
     z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
     z ^= z >> 27; z *= 0x94d049bb133111ebull;
     z ^= z >> 31;
     return z;
 }
-__device__ __forceinline__ void twoview_draw(unsigned long long seed, unsigned e, unsigned h, int n, int (&idx)[8]) {
+// (S = 8 for F, S = 4 for a homography)
+template <int S>
+__device__ __forceinline__ void twoview_draw(unsigned long long seed, unsigned e, unsigned h, int n, int (&idx)[S]) {
     const unsigned long long key = twoview_mix(seed ^ twoview_mix(((unsigned long long)e << 32) | (unsigned long long)h));
-    int srt[8];                                                  // the earlier choices, ascending
+    int srt[S];                                                  // the earlier choices, ascending
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < S; ++j) {
         int k = (int)(twoview_mix(key + (unsigned long long)(j + 1) * 0x9e3779b97f4a7c15ull) % (unsigned long long)(n - j));
 #pragma unroll
         for (int i = 0; i < j; ++i) if (k >= srt[i]) ++k;
@@ -1322,7 +1327,7 @@ __device__ __forceinline__ void fund_unit(double (&F)[9]) {
 struct FundIn {
     const double* __restrict__ pairs;            // [M_used][4] x1 y1 x2 y2
     const int* __restrict__ uptr;                // [n_edges + 1] runs of used pairs
-    const int* __restrict__ samples;             // [n_edges][H][8] positions among the used pairs, or null: drawn
+    const int* __restrict__ samples;             // [n_edges][H][8] (F) or [n_edges][H][4] (H) positions among the used pairs, or null: drawn
 };
 
 // the hypotheses h0 + w, h0 + w + 4, ... < h1 of edge e by wave w; P: the edge's pairs (LDS or global)
@@ -1617,6 +1622,368 @@ __global__ __launch_bounds__(kTwoViewThreads) void k_fund_finish(FundIn in, int 
 #pragma unroll
             for (int k = 0; k < 9; ++k) out.F_refit[9 * (size_t)e + k] = sum < INFINITY ? Fr[k] : Fu[k];
         }
+    }
+}
+
+// ---- sfmba_homography_ransac: the F pair's grid, slices, staging, slots and finish, with a
+// four-pair DLT homography as the hypothesis and the transfer distance in image 2 as the score ----
+constexpr int kHomogOk = 0, kHomogFewPairs = 1, kHomogDegenerate = 2;
+
+// the two DLT rows of one normalised pair (x, y) -> (u, v)
+__device__ __forceinline__ void homog_rows(double x, double y, double u, double v, double (&r0)[9], double (&r1)[9]) {
+    r0[0] = -x; r0[1] = -y; r0[2] = -1.0; r0[3] = 0.0; r0[4] = 0.0; r0[5] = 0.0; r0[6] = u * x; r0[7] = u * y; r0[8] = u;
+    r1[0] = 0.0; r1[1] = 0.0; r1[2] = 0.0; r1[3] = -x; r1[4] = -y; r1[5] = -1.0; r1[6] = v * x; r1[7] = v * y; r1[8] = v;
+}
+// After jacobi_lds<9>: Hn = the eigenvector of the smallest eigenvalue, then T2^-1 Hn T1 with T1 = [[1/s1, 0, -m1x/s1],
+// [0, 1/s1, -m1y/s1], [0, 0, 1]] and T2^-1 = [[s2, 0, m2x], [0, s2, m2y], [0, 0, 1]].  Every lane of the calling wave
+// leaves with the same H.
+__device__ __forceinline__ void homog_from_jacobi(const volatile double* A, const volatile double* V, double m1x, double m1y,
+                                                  double s1, double m2x, double m2y, double s2, double (&Hm)[9]) {
+    int lo = 0;
+    double least = A[0];
+#pragma unroll
+    for (int k = 1; k < 9; ++k) { const double d = A[10 * k]; if (d < least) { least = d; lo = k; } }
+    double Hn[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Hn[k] = V[9 * k + lo];
+    const double a1 = 1.0 / s1, b1 = -m1x / s1, c1 = -m1y / s1;
+    double G[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        G[3 * i] = Hn[3 * i] * a1; G[3 * i + 1] = Hn[3 * i + 1] * a1;
+        G[3 * i + 2] = Hn[3 * i] * b1 + Hn[3 * i + 1] * c1 + Hn[3 * i + 2];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        Hm[j] = s2 * G[j] + m2x * G[6 + j]; Hm[3 + j] = s2 * G[3 + j] + m2y * G[6 + j];
+        Hm[6 + j] = G[6 + j];
+    }
+}
+// the score: the squared distance of x2 from the transferred H x1, one-sided, strictly below the squared threshold; a
+// non-finite distance is no inlier (NaN compares false; +inf < thr2 is false)
+__device__ __forceinline__ bool homog_inlier(const double (&Hm)[9], double x1, double y1, double x2, double y2, double thr2) {
+    const double q0 = Hm[0] * x1 + Hm[1] * y1 + Hm[2], q1 = Hm[3] * x1 + Hm[4] * y1 + Hm[5], q2 = Hm[6] * x1 + Hm[7] * y1 + Hm[8];
+    const double dx = q0 / q2 - x2, dy = q1 / q2 - y2;
+    const double d2 = dx * dx + dy * dy;
+    return d2 < thr2 && d2 < INFINITY;
+}
+
+// the hypotheses h0 + w, h0 + w + 4, ... < h1 of edge e by wave w; P: the edge's pairs (LDS or global); in.samples [.][H][4]
+__device__ __forceinline__ void homog_slice(const double* P, const FundIn& in, int e, int n, int H, int h0, int h1,
+                                            unsigned long long seed, double thr2, volatile double* A, volatile double* V,
+                                            volatile double* R, int* __restrict__ hyp, int& bc, int& bh, double (&bH)[9]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const double2* __restrict__ P2 = reinterpret_cast<const double2*>(P);
+    bc = -1; bh = 0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) bH[k] = 0.0;
+#pragma unroll 1
+    for (int h = h0 + w; h < h1; h += kTwoViewWaves) {
+        int idx[4];
+        bool valid = true;
+        if (in.samples != nullptr) {
+            const int* __restrict__ sp = in.samples + ((size_t)e * (size_t)H + (size_t)h) * 4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { idx[j] = sp[j]; valid = valid && idx[j] >= 0 && idx[j] < n; }
+#pragma unroll
+            for (int j = 1; j < 4; ++j)
+#pragma unroll
+                for (int i = 0; i < j; ++i) valid = valid && idx[i] != idx[j];
+        } else {
+            twoview_draw(seed, (unsigned)e, (unsigned)h, n, idx);
+        }
+        if (!valid) {                                            // (uniform over the wave)
+            if (lane == 0 && hyp != nullptr) hyp[(size_t)e * (size_t)H + (size_t)h] = -1;
+            continue;
+        }
+        double x1[4], y1[4], x2[4], y2[4];
+        double m1x = 0.0, m1y = 0.0, m2x = 0.0, m2y = 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double2 qa = P2[2 * idx[j]], qb = P2[2 * idx[j] + 1];
+            x1[j] = qa.x; y1[j] = qa.y; x2[j] = qb.x; y2[j] = qb.y;
+            m1x += qa.x; m1y += qa.y; m2x += qb.x; m2y += qb.y;
+        }
+        const double g1 = (m1x + m1y) / 8.0, g2 = (m2x + m2y) / 8.0;       // np.std: about the mean of all 8 coordinates
+        m1x /= 4.0; m1y /= 4.0; m2x /= 4.0; m2y /= 4.0;
+        double q1 = 0.0, q2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            q1 += (x1[j] - g1) * (x1[j] - g1) + (y1[j] - g1) * (y1[j] - g1);
+            q2 += (x2[j] - g2) * (x2[j] - g2) + (y2[j] - g2) * (y2[j] - g2);
+        }
+        const double s1 = sqrt(q1 / 8.0), s2 = sqrt(q2 / 8.0);
+        // the eight rows through LDS (lane 0 stores them: the four first rows, then the four second rows), then lane
+        // i < 9 sums row i of A^T A over the rows 0..7
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            double r0[9], r1[9];
+            homog_rows((x1[j] - m1x) / s1, (y1[j] - m1y) / s1, (x2[j] - m2x) / s2, (y2[j] - m2y) / s2, r0, r1);
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i) { R[9 * j + i] = r0[i]; R[9 * (4 + j) + i] = r1[i]; }
+            }
+        }
+        if (lane < 9) {
+            double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const double ri = R[9 * j + lane];
+#pragma unroll
+                for (int c = 0; c < 9; ++c) acc[c] += ri * R[9 * j + c];
+            }
+#pragma unroll
+            for (int c = 0; c < 9; ++c) { A[9 * lane + c] = acc[c]; V[9 * lane + c] = c == lane ? 1.0 : 0.0; }
+        }
+        jacobi_lds<9>(A, V, lane);
+        double Hm[9];
+        homog_from_jacobi(A, V, m1x, m1y, s1, m2x, m2y, s2, Hm);
+        int cnt = 0;
+#pragma unroll 1
+        for (int k0 = 0; k0 < n; k0 += 64) {                     // uniform over the wave: the ballot needs every lane
+            const int k = k0 + lane;
+            bool inl = false;
+            if (k < n) { const double2 qa = P2[2 * k], qb = P2[2 * k + 1]; inl = homog_inlier(Hm, qa.x, qa.y, qb.x, qb.y, thr2); }
+            cnt += __popcll(__ballot(inl));
+        }
+        if (lane == 0 && hyp != nullptr) hyp[(size_t)e * (size_t)H + (size_t)h] = cnt;
+        if (cnt > bc) {                                          // (h ascends: the lowest h of equal counts stays)
+            bc = cnt; bh = h;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) bH[k] = Hm[k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(kTwoViewThreads) void k_homog_ransac(FundIn in, int H, int hs, int n_slices, unsigned long long seed,
+                                                                  double thr2, double* __restrict__ slots, int* __restrict__ hyp) {
+    extern __shared__ __align__(16) double smem[];
+    __shared__ double jA[kTwoViewWaves][81], jV[kTwoViewWaves][81], jR[kTwoViewWaves][72];
+    __shared__ double wbest[kTwoViewWaves][kTwoViewSlot];
+    const int e = blockIdx.x / n_slices, sl = blockIdx.x - e * n_slices;
+    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
+    const int h0 = sl * hs, h1 = min(H, h0 + hs);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    double* __restrict__ slot = slots + (size_t)blockIdx.x * kTwoViewSlot;
+    if (n < 4) {                                                 // (uniform over the workgroup) FEW_PAIRS: no hypothesis
+        if (hyp != nullptr)
+            for (int h = h0 + (int)threadIdx.x; h < h1; h += kTwoViewThreads) hyp[(size_t)e * (size_t)H + (size_t)h] = -1;
+        if (threadIdx.x == 0) {
+            slot[0] = -1.0; slot[1] = 0.0;
+#pragma unroll
+            for (int k = 2; k < kTwoViewSlot; ++k) slot[k] = 0.0;
+        }
+        return;
+    }
+    const double* __restrict__ gp = in.pairs + 4 * (size_t)b;
+    int bc, bh;
+    double bH[9];
+    if (n <= kTwoViewLdsPairs) {
+        stage_table(gp, 4 * n, smem);
+        homog_slice(smem, in, e, n, H, h0, h1, seed, thr2, jA[w], jV[w], jR[w], hyp, bc, bh, bH);
+    } else {
+        homog_slice(gp, in, e, n, H, h0, h1, seed, thr2, jA[w], jV[w], jR[w], hyp, bc, bh, bH);
+    }
+    if (lane == 0) {
+        wbest[w][0] = (double)bc; wbest[w][1] = (double)bh;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wbest[w][2 + k] = bH[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int best = 0;
+        for (int k = 1; k < kTwoViewWaves; ++k)
+            if (wbest[k][0] > wbest[best][0] || (wbest[k][0] == wbest[best][0] && wbest[k][1] < wbest[best][1])) best = k;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) slot[k] = wbest[best][k];
+        slot[11] = 0.0;
+    }
+}
+
+// fund_ata_rows with both DLT rows of a pair: rows I0 .. I1 - 1 of the upper triangle of A^T A over the pairs of the mask mk
+// (its own stores), thread t taking pairs t, t + 256, ..., a pair's first row before its second; thread 0 stores them (and
+// their mirror) into A
+template <int I0, int I1>
+__device__ __forceinline__ void homog_ata_rows(const double2* __restrict__ P2, int n, const unsigned char* mk, double m1x,
+                                               double m1y, double s1, double m2x, double m2y, double s2, double* red, double* A) {
+    constexpr int NS = sym<9>(I1 - 1, 8) - sym<9>(I0, I0) + 1, Q0 = sym<9>(I0, I0);
+    double s[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) s[q] = 0.0;
+#pragma unroll 1
+    for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+        const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+        if (!mk[k]) continue;
+        double r0[9], r1[9];
+        homog_rows((qa.x - m1x) / s1, (qa.y - m1y) / s1, (qb.x - m2x) / s2, (qb.y - m2y) / s2, r0, r1);
+#pragma unroll
+        for (int i = I0; i < I1; ++i)
+#pragma unroll
+            for (int c = i; c < 9; ++c) { s[sym<9>(i, c) - Q0] += r0[i] * r0[c]; s[sym<9>(i, c) - Q0] += r1[i] * r1[c]; }
+    }
+    block_sum<NS>(s, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = I0; i < I1; ++i)
+#pragma unroll
+            for (int c = i; c < 9; ++c) { A[9 * i + c] = s[sym<9>(i, c) - Q0]; A[9 * c + i] = s[sym<9>(i, c) - Q0]; }
+    }
+}
+
+struct HomogOut {
+    double* __restrict__ Hm;                     // [E][9]
+    double* __restrict__ H_refit;                // [E][9]
+    unsigned char* __restrict__ mask;            // [M_used] of the best hypothesis
+    unsigned char* __restrict__ refit_mask;      // [M_used] of H_refit
+    int* __restrict__ ints;                      // [E][5] inliers, best h, status, success, refit inliers
+};
+
+__global__ __launch_bounds__(kTwoViewThreads) void k_homog_finish(FundIn in, int n_slices, double thr2, double confidence, int refit,
+                                                                  const double* __restrict__ slots, HomogOut out) {
+    __shared__ double red[kTwoViewWaves * 18];
+    __shared__ double jA[81], jV[81];
+    __shared__ double sH[9], sm[9];
+    __shared__ int ctl[2];
+    const int e = blockIdx.x;
+    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
+    const bool first = threadIdx.x == 0;
+    const double2* __restrict__ P2 = reinterpret_cast<const double2*>(in.pairs + 4 * (size_t)b);
+    int* __restrict__ oi = out.ints + 5 * (size_t)e;
+    if (first) {
+        const double* __restrict__ sl = slots + (size_t)e * (size_t)n_slices * kTwoViewSlot;
+        int best = 0;
+        for (int k = 1; k < n_slices; ++k)                       // slots ascend in h: the first of equal counts has the lowest
+            if (sl[(size_t)k * kTwoViewSlot] > sl[(size_t)best * kTwoViewSlot]) best = k;
+        const double* __restrict__ bs = sl + (size_t)best * kTwoViewSlot;
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { sH[k] = bs[2 + k]; sum += fabs(bs[2 + k]); }
+        ctl[0] = n < 4 ? kHomogFewPairs : (sum < INFINITY ? kHomogOk : kHomogDegenerate);
+        ctl[1] = bs[0] >= 0.0 ? (int)bs[1] : -1;                 // (-1: no valid sample in any slot)
+    }
+    __syncthreads();
+    const unsigned char* mk = out.mask + (size_t)b;              // a thread reads back only what it stored itself
+    if (ctl[0] == kHomogFewPairs) {                              // (uniform over the workgroup)
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) { out.mask[(size_t)b + k] = 0; out.refit_mask[(size_t)b + k] = 0; }
+        if (threadIdx.x < 9) { out.Hm[9 * (size_t)e + threadIdx.x] = 0.0; out.H_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
+        if (first) { oi[0] = 0; oi[1] = -1; oi[2] = kHomogFewPairs; oi[3] = 0; oi[4] = 0; }
+        return;
+    }
+    // The mask of the best H, and the count FROM that mask, as in k_fund_finish: everything below rests on this one
+    // evaluation.  refit_mask starts as its copy (refit = 0 and DEGENERATE leave it so).
+    double Hb[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Hb[k] = sH[k];
+    {
+        double c[1] = {0.0};
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+            const bool inl = ctl[1] >= 0 && homog_inlier(Hb, qa.x, qa.y, qb.x, qb.y, thr2);
+            out.mask[(size_t)b + k] = inl ? 1 : 0;
+            out.refit_mask[(size_t)b + k] = inl ? 1 : 0;
+            c[0] += inl ? 1.0 : 0.0;
+        }
+        block_sum<1>(c, red);
+        if (first) {
+            const int cnt = (int)c[0];
+            if (ctl[0] == kHomogOk && cnt < 4) ctl[0] = kHomogDegenerate;
+            sm[8] = (double)cnt;
+            // (DEGENERATE still reports the count, h and mask of its best hypothesis; only H is withheld)
+            oi[0] = cnt; oi[1] = ctl[1]; oi[2] = ctl[0];
+            oi[3] = (ctl[1] >= 0 && (double)cnt / (double)n >= confidence) ? 1 : 0;
+            oi[4] = cnt;
+        }
+        __syncthreads();
+    }
+    const int status = ctl[0], cnt = (int)sm[8];
+    if (status != kHomogOk) {
+        if (threadIdx.x < 9) { out.Hm[9 * (size_t)e + threadIdx.x] = 0.0; out.H_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
+        return;
+    }
+    double Hu[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Hu[k] = Hb[k];
+    fund_unit(Hu);
+    if (first) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) out.Hm[9 * (size_t)e + k] = Hu[k];
+    }
+    if (!refit) {
+        if (first) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) out.H_refit[9 * (size_t)e + k] = Hu[k];
+        }
+        return;
+    }
+    // the same estimate over the cnt >= 4 inliers: thread t takes pairs t, t + 256, ...
+    {
+        double v[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+            if (mk[k]) { v[0] += qa.x; v[1] += qa.y; v[2] += qb.x; v[3] += qb.y; }
+        }
+        block_sum<4>(v, red);
+        if (first) {
+            const double c = (double)cnt;
+            sm[0] = v[0] / c; sm[1] = v[1] / c; sm[2] = v[2] / c; sm[3] = v[3] / c;
+            sm[4] = (v[0] + v[1]) / (2.0 * c); sm[5] = (v[2] + v[3]) / (2.0 * c);
+        }
+        __syncthreads();
+    }
+    const double m1x = sm[0], m1y = sm[1], m2x = sm[2], m2y = sm[3];
+    {
+        const double g1 = sm[4], g2 = sm[5];
+        double v[2] = {0.0, 0.0};
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+            if (mk[k]) {
+                v[0] += (qa.x - g1) * (qa.x - g1) + (qa.y - g1) * (qa.y - g1);
+                v[1] += (qb.x - g2) * (qb.x - g2) + (qb.y - g2) * (qb.y - g2);
+            }
+        }
+        block_sum<2>(v, red);
+        if (first) { sm[6] = sqrt(v[0] / (2.0 * (double)cnt)); sm[7] = sqrt(v[1] / (2.0 * (double)cnt)); }
+        __syncthreads();
+    }
+    const double s1 = sm[6], s2 = sm[7];
+    // the 45 sums in three passes (rows 0-1, 2-4, 5-8 of the upper triangle), as k_fund_finish takes them
+    homog_ata_rows<0, 2>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
+    homog_ata_rows<2, 5>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
+    homog_ata_rows<5, 9>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
+    if (first)
+        for (int k = 0; k < 81; ++k) jV[k] = (k % 10) == 0 ? 1.0 : 0.0;
+    if (threadIdx.x < 64) {                                      // wave 0: thread 0's stores above are its own
+        jacobi_lds<9>(jA, jV, (int)threadIdx.x);
+        double Hr[9];
+        homog_from_jacobi(jA, jV, m1x, m1y, s1, m2x, m2y, s2, Hr);
+        fund_unit(Hr);
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) sum += fabs(Hr[k]);
+        if (first) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const double v = sum < INFINITY ? Hr[k] : Hu[k];
+                out.H_refit[9 * (size_t)e + k] = v;
+                sH[k] = v;
+            }
+        }
+    }
+    __syncthreads();
+    // refit_mask and its count: the used pairs against H_refit as it is returned, the same expression
+    {
+        double Hr[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Hr[k] = sH[k];
+        double c[1] = {0.0};
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+            const bool inl = homog_inlier(Hr, qa.x, qa.y, qb.x, qb.y, thr2);
+            out.refit_mask[(size_t)b + k] = inl ? 1 : 0;
+            c[0] += inl ? 1.0 : 0.0;
+        }
+        block_sum<1>(c, red);
+        if (first) oi[4] = (int)c[0];
     }
 }
 

@@ -385,6 +385,60 @@ int check_samples(sfmba_handle* h, const int32_t* samples, size_t batch, size_t 
     return 0;
 }
 
+// What sfmba_fundamental_ransac (S = 8 positions a sample) and sfmba_homography_ransac (S = 4) do alike before their finish
+// kernels: options, the batch onto the device, the slices, slots / counts / samples buffers, the caller's samples
+// checked and uploaded, the LDS opt-in, and the launch of the RANSAC kernel (the two have one signature; `score` is its threshold argument).
+using TwoViewRansacKernel = void (*)(FundIn, int, int, int, unsigned long long, double, double*, int*);
+struct TwoViewRansac {
+    TwoViewRansacKernel kern = nullptr;
+    sfmba_ransac_options o;
+    TwoViewBatch bt;
+    size_t E = 0, H = 0;
+    int hs = 1, n_slices = 1;
+    FundIn in{};
+};
+
+// (E = 0 on return: the batch has no edge and nothing was launched)
+int twoview_ransac_begin(sfmba_handle* h, const char* who, TwoViewRansacKernel kern, int S, int64_t n_edges, const int64_t* edge_ptr, const double* pts1,
+                         const double* pts2, const uint8_t* pair_use, const int32_t* samples, const sfmba_ransac_options* opt,
+                         bool hyp, int64_t* n_ok, double* kernel_us, TwoViewRansac* c) {
+    if (opt) c->o = *opt; else sfmba_default_ransac_options(&c->o);
+    if (std::isnan(c->o.threshold) || std::isnan(c->o.confidence)) return fail(h, -1, "an option of %s is NaN", who);
+    if (c->o.max_iters < 1) return fail(h, -1, "%s: max_iters must be at least 1", who);
+    auto& t = h->twoview;
+    CHK(twoview_stage(h, who, n_edges, edge_ptr, pts1, pts2, pair_use, &c->bt));
+    if (n_ok) *n_ok = 0;
+    if (kernel_us) *kernel_us = 0.0;
+    const size_t E = c->bt.E, H = (size_t)c->o.max_iters;
+    c->H = H;
+    if (E == 0) return 0;
+    ransac_slices(h->n_cu, E, (int)H, kTwoViewMinSlice, true, &c->hs, &c->n_slices);
+    if (E * (size_t)c->n_slices >= (size_t)1 << 31) return fail(h, -1, "%s: too many edges for one launch", who);
+    CHK(ensure_all(h, {{&t.slots, sizeof(double) * kTwoViewSlot * E * (size_t)c->n_slices}, {&t.hyp, hyp ? sizeof(int) * E * H : 0},
+                       {&t.samples, samples ? sizeof(int) * (size_t)S * E * H : 0}}));
+    if (samples) {
+        const int* up = reinterpret_cast<const int*>(t.in_host.as<unsigned char>() + sizeof(double) * 4 * c->bt.M);
+        CHK(check_samples(h, samples, E, H, (size_t)S, [&](size_t e) { return up[e + 1] - up[e]; }, S,   // (below: FEW_PAIRS)
+                          who, "edge", "pairs"));
+        HIPCHK(h, hipMemcpyAsync(t.samples.p, samples, sizeof(int) * (size_t)S * E * H, hipMemcpyHostToDevice, h->stream));
+    }
+    // the kernel's static LDS (about 8 KiB, above the 2 KiB that set_lds assumes) counts: opted in whatever this call stages
+    CHK(opt_in_lds(h, reinterpret_cast<const void*>(kern), sizeof(double) * 4 * kTwoViewLdsPairs));
+    c->kern = kern;
+    c->in = FundIn{t.pairs.as<double>(), t.uptr.as<int>(), samples ? t.samples.as<int>() : nullptr};
+    c->E = E;
+    return 0;
+}
+
+int launch_twoview_ransac(sfmba_handle* h, const TwoViewRansac& c, double score, bool hyp) {
+    auto& t = h->twoview;
+    const size_t lds = sizeof(double) * 4 * (size_t)std::min(c.bt.max_n, kTwoViewLdsPairs);
+    hipLaunchKernelGGL(c.kern, dim3((unsigned)(c.E * (size_t)c.n_slices)), dim3(kTwoViewThreads), lds, h->stream, c.in, (int)c.H, c.hs,
+                       c.n_slices, (unsigned long long)c.o.seed, score, t.slots.as<double>(), hyp ? t.hyp.as<int>() : nullptr);
+    LAUNCHED(h);
+    return 0;
+}
+
 // ---- robust resection (sfmba_resect_ransac; kernels: consumer_kernels.hpp, "Robust resection") ----------------------------
 struct PnpCall { int H, hs, n_slices; PnpScore sc; double confidence; unsigned long long seed; };
 
@@ -551,40 +605,20 @@ int sfmba_fundamental_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* ed
                              double* F_refit, uint8_t* inlier_mask, int32_t* edge_inliers, int32_t* edge_best,
                              uint8_t* edge_success, int32_t* edge_status, int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us) {
     CHK(enter(h));
-    sfmba_ransac_options o;
-    if (opt) o = *opt; else sfmba_default_ransac_options(&o);
-    if (std::isnan(o.threshold) || std::isnan(o.confidence)) return fail(h, -1, "an option of sfmba_fundamental_ransac is NaN");
-    if (o.max_iters < 1) return fail(h, -1, "sfmba_fundamental_ransac: max_iters must be at least 1");
+    TwoViewRansac c;
+    CHK(twoview_ransac_begin(h, "sfmba_fundamental_ransac", k_fund_ransac, 8, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
+                             hyp_inliers != nullptr, n_ok, kernel_us, &c));
+    if (c.E == 0) return wait_stream(h);
     auto& t = h->twoview;
-    TwoViewBatch bt;
-    CHK(twoview_stage(h, "sfmba_fundamental_ransac", n_edges, edge_ptr, pts1, pts2, pair_use, &bt));
-    if (n_ok) *n_ok = 0;
-    if (kernel_us) *kernel_us = 0.0;
-    const size_t E = bt.E, H = (size_t)o.max_iters;
-    if (E == 0) return wait_stream(h);
-    int hs = 1, n_slices = 1;
-    ransac_slices(h->n_cu, E, (int)H, kTwoViewMinSlice, true, &hs, &n_slices);
-    if (E * (size_t)n_slices >= (size_t)1 << 31) return fail(h, -1, "sfmba_fundamental_ransac: too many edges for one launch");
-    CHK(ensure_all(h, {{&t.slots, sizeof(double) * kTwoViewSlot * E * (size_t)n_slices},
-                       {&t.hyp, hyp_inliers ? sizeof(int) * E * H : 0}, {&t.samples, samples ? sizeof(int) * 8 * E * H : 0},
-                       {&t.F, sizeof(double) * 18 * E}, {&t.ints, sizeof(int) * 4 * E}, {&t.mask, std::max<size_t>(bt.Mu, 1)}}));
-    if (samples) {
-        const int* up = reinterpret_cast<const int*>(t.in_host.as<unsigned char>() + sizeof(double) * 4 * bt.M);
-        CHK(check_samples(h, samples, E, H, 8, [&](size_t e) { return up[e + 1] - up[e]; }, 8,   // (below: FEW_PAIRS)
-                          "sfmba_fundamental_ransac", "edge", "pairs"));
-        HIPCHK(h, hipMemcpyAsync(t.samples.p, samples, sizeof(int) * 8 * E * H, hipMemcpyHostToDevice, h->stream));
-    }
-    const FundIn in{t.pairs.as<double>(), t.uptr.as<int>(), samples ? t.samples.as<int>() : nullptr};
+    const sfmba_ransac_options& o = c.o;
+    const TwoViewBatch& bt = c.bt;
+    const size_t E = c.E, H = c.H;
+    CHK(ensure_all(h, {{&t.F, sizeof(double) * 18 * E}, {&t.ints, sizeof(int) * 4 * E}, {&t.mask, std::max<size_t>(bt.Mu, 1)}}));
     const FundOut out{t.F.as<double>(), t.F.as<double>() + 9 * E, t.mask.as<unsigned char>(), t.ints.as<int>()};
-    const size_t lds = sizeof(double) * 4 * (size_t)std::min(bt.max_n, kTwoViewLdsPairs);
-    // the kernel's static LDS (about 8 KiB, above the 2 KiB that set_lds assumes) counts: opted in whatever this call stages
-    CHK(opt_in_lds(h, reinterpret_cast<const void*>(k_fund_ransac), sizeof(double) * 4 * kTwoViewLdsPairs));
     EventPair timer;
     CHK(timer.start(h, o.profile != 0));
-    hipLaunchKernelGGL(k_fund_ransac, dim3((unsigned)(E * (size_t)n_slices)), dim3(kTwoViewThreads), lds, h->stream, in, (int)H, hs,
-                       n_slices, (unsigned long long)o.seed, o.threshold, t.slots.as<double>(), hyp_inliers ? t.hyp.as<int>() : nullptr);
-    LAUNCHED(h);
-    hipLaunchKernelGGL(k_fund_finish, dim3((unsigned)E), dim3(kTwoViewThreads), 0, h->stream, in, n_slices, o.threshold, o.confidence,
+    CHK(launch_twoview_ransac(h, c, o.threshold, hyp_inliers != nullptr));
+    hipLaunchKernelGGL(k_fund_finish, dim3((unsigned)E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, o.threshold, o.confidence,
                        o.refit != 0 ? 1 : 0, (const double*)t.slots.as<double>(), out);
     LAUNCHED(h);
     CHK(timer.stop(h));
@@ -609,6 +643,61 @@ int sfmba_fundamental_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* ed
         if (edge_status) edge_status[e] = hi[4 * e + 2];
         if (edge_success) edge_success[e] = (uint8_t)hi[4 * e + 3];
         ok += hi[4 * e + 2] == kFundOk ? 1 : 0;
+    }
+    if (n_ok) *n_ok = ok;
+    return 0;
+}
+
+// The F call with k_homog_ransac / k_homog_finish and samples of four positions: twoview.F holds H and H_refit, twoview.mask
+// both masks, twoview.ints five integers per edge.
+int sfmba_homography_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edge_ptr, const double* pts1, const double* pts2,
+                            const uint8_t* pair_use, const int32_t* samples, const sfmba_ransac_options* opt, double* Hm,
+                            double* H_refit, uint8_t* inlier_mask, uint8_t* refit_mask, int32_t* edge_inliers,
+                            int32_t* edge_refit_inliers, int32_t* edge_best, uint8_t* edge_success, int32_t* edge_status,
+                            int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us) {
+    CHK(enter(h));
+    TwoViewRansac c;
+    CHK(twoview_ransac_begin(h, "sfmba_homography_ransac", k_homog_ransac, 4, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
+                             hyp_inliers != nullptr, n_ok, kernel_us, &c));
+    if (c.E == 0) return wait_stream(h);
+    auto& t = h->twoview;
+    const sfmba_ransac_options& o = c.o;
+    const TwoViewBatch& bt = c.bt;
+    const size_t E = c.E, H = c.H, Mu = bt.Mu;
+    CHK(ensure_all(h, {{&t.F, sizeof(double) * 18 * E}, {&t.ints, sizeof(int) * 5 * E}, {&t.mask, 2 * std::max<size_t>(Mu, 1)}}));
+    const HomogOut out{t.F.as<double>(), t.F.as<double>() + 9 * E, t.mask.as<unsigned char>(), t.mask.as<unsigned char>() + Mu,
+                       t.ints.as<int>()};
+    const double thr2 = o.threshold * o.threshold;
+    EventPair timer;
+    CHK(timer.start(h, o.profile != 0));
+    CHK(launch_twoview_ransac(h, c, thr2, hyp_inliers != nullptr));
+    hipLaunchKernelGGL(k_homog_finish, dim3((unsigned)E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, thr2, o.confidence,
+                       o.refit != 0 ? 1 : 0, (const double*)t.slots.as<double>(), out);
+    LAUNCHED(h);
+    CHK(timer.stop(h));
+    // the per-edge integers always come (n_ok); the masks through the staging when they have to be scattered
+    const size_t off_mask = sizeof(int) * 5 * E;
+    HIPCHK(h, t.out_host.ensure(off_mask + 2 * Mu, 0));
+    int* const hi = t.out_host.as<int>();
+    unsigned char* const hm = t.out_host.as<unsigned char>() + off_mask;
+    HIPCHK(h, hipMemcpyAsync(hi, t.ints.p, sizeof(int) * 5 * E, hipMemcpyDeviceToHost, h->stream));
+    if ((inlier_mask || refit_mask) && Mu) HIPCHK(h, hipMemcpyAsync(hm, t.mask.p, 2 * Mu, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, download(h, Hm, t.F.p, sizeof(double) * 9 * E));
+    HIPCHK(h, download(h, H_refit, t.F.as<double>() + 9 * E, sizeof(double) * 9 * E));
+    HIPCHK(h, download(h, hyp_inliers, t.hyp.p, sizeof(int) * E * H));
+    CHK(wait_stream(h));
+    CHK(timer.read(h, kernel_us));
+    const uint8_t zero = 0;
+    twoview_scatter(h, bt, hm, inlier_mask, 1, &zero);
+    twoview_scatter(h, bt, hm + Mu, refit_mask, 1, &zero);
+    int64_t ok = 0;
+    for (size_t e = 0; e < E; ++e) {
+        if (edge_inliers) edge_inliers[e] = hi[5 * e];
+        if (edge_best) edge_best[e] = hi[5 * e + 1];
+        if (edge_status) edge_status[e] = hi[5 * e + 2];
+        if (edge_success) edge_success[e] = (uint8_t)hi[5 * e + 3];
+        if (edge_refit_inliers) edge_refit_inliers[e] = hi[5 * e + 4];
+        ok += hi[5 * e + 2] == kHomogOk ? 1 : 0;
     }
     if (n_ok) *n_ok = ok;
     return 0;

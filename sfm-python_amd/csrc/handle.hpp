@@ -321,12 +321,12 @@ struct sfmba_handle {
         DevBuf select;                       // [C]
         DevBuf cam, ints, rms;               // [C][6]; [4][C] status, views, iters, ok; [C]
     } resect;
-    // sfmba_fundamental_ransac / sfmba_recover_pose: a batch of edges that has nothing to do with the problem; every
-    // buffer is the two calls' own
+    // sfmba_fundamental_ransac / sfmba_homography_ransac / sfmba_recover_pose: a batch of edges that has nothing to do
+    // with the problem; every buffer is the three calls' own
     struct TwoView {
-        DevBuf pairs, uptr, samples, E;      // [M_used][4] x1 y1 x2 y2; [n_edges + 1]; [n_edges][H][8]; [n_edges][9]
+        DevBuf pairs, uptr, samples, E;      // [M_used][4] x1 y1 x2 y2; [n_edges + 1]; [n_edges][H][8 (F) or 4 (H)]; [n_edges][9]
         DevBuf slots, hyp;                   // [n_edges][slices][kTwoViewSlot]; [n_edges][H]
-        DevBuf F, ints, mask;                // [2][n_edges][9] F, F_refit; [n_edges][4]; [M_used]
+        DevBuf F, ints, mask;                // [2][n_edges][9] F, F_refit (H, H_refit); [n_edges][4 (F) or 5 (H)]; [M_used] ([2][M_used] for H)
         DevBuf Rt, err, pose_ints, X, ang;   // [n_edges][12]; [n_edges]; [n_edges][6]; [M_used][3]; [M_used]
         PinnedBuf in_host, out_host;         // staging of the packed batch; of the results
         std::vector<int64_t> pos;            // used pair -> stored pair, when the call has a pair_use mask

@@ -34,6 +34,30 @@ class FundamentalEstimate:
         return f"FundamentalEstimate(n_edges={len(self.status)}, n_ok={self.n_ok})"
 
 
+class HomographyEstimate:
+    """What `Backend.homography_ransac` returns (include/sfmba.h: sfmba_homography_ransac), per edge of the batch:
+    ``H`` and ``H_refit`` (E, 3, 3), ``x2 ~ H x1``, unit Frobenius norm, largest entry positive (``H_refit`` equals ``H``
+    unless ``refit=1``); ``inliers``, ``refit_inliers``, ``best`` (the winning hypothesis), ``status`` (one of ``OK,
+    FEW_PAIRS, DEGENERATE``) as int32 (E), ``success`` (E, bool): inliers / used pairs >= confidence; ``inlier_mask`` (of
+    ``H``) and ``refit_mask`` (of ``H_refit``) (M, bool) over the stored pairs; ``hyp_inliers`` (E, H) the count of every
+    hypothesis, or None when not asked for; ``n_ok``; ``kernel_us`` (``profile=1``, else 0)."""
+
+    OK, FEW_PAIRS, DEGENERATE = 0, 1, 2
+
+    def __init__(self, H, H_refit, inlier_mask, refit_mask, inliers, refit_inliers, best, success, status, hyp_inliers, n_ok,
+                 kernel_us, edge_ptr):
+        self.H, self.H_refit, self.inlier_mask, self.refit_mask = H, H_refit, inlier_mask, refit_mask
+        self.inliers, self.refit_inliers, self.best, self.success, self.status = inliers, refit_inliers, best, success, status
+        self.hyp_inliers, self.n_ok, self.kernel_us, self.edge_ptr = hyp_inliers, int(n_ok), float(kernel_us), edge_ptr
+
+    @property
+    def ok(self):
+        return self.status == self.OK
+
+    def __repr__(self):
+        return f"HomographyEstimate(n_edges={len(self.status)}, n_ok={self.n_ok})"
+
+
 class RelativePose:
     """What `Backend.recover_pose` returns (include/sfmba.h: sfmba_recover_pose), per edge: ``R`` (E, 3, 3) and ``t``
     (E, 3), ``x2 = R x1 + t`` with ``|t| = 1``; ``front`` (E) the winner's pairs in front, ``front_all`` (E, 4) every
@@ -366,6 +390,17 @@ def _edge_batch(pts1, pts2, edge_ptr, pair_use):
     if edge_ptr.shape[0] < 1 or edge_ptr[0] != 0 or edge_ptr[-1] != M or np.any(np.diff(edge_ptr) < 0):
         raise ValueError("edge_ptr must ascend from 0 to the number of pairs")
     return pts1, pts2, edge_ptr, _mask(pair_use, M, "pair_use")
+
+
+def _homography_samples(samples, n_edges):
+    """The caller's sample sets of `Backend.homography_ransac`, checked: (n_edges, H, 4) integers with H >= 1 -> int32,
+    C-contiguous; None stays None."""
+    if samples is None:
+        return None
+    samples = np.asarray(samples)
+    if samples.dtype.kind not in "iu" or samples.ndim != 3 or samples.shape[0] != n_edges or samples.shape[2] != 4 or samples.shape[1] < 1:
+        raise ValueError(f"samples must be (n_edges, H, 4) int32 with n_edges = {n_edges}, got {samples.dtype} {samples.shape}")
+    return np.ascontiguousarray(samples, dtype=np.int32)
 
 
 def _opt_ptr(a):
@@ -909,6 +944,45 @@ class Backend:
             _capi.ptr(status), _opt_ptr(hyp), C.byref(n_ok), C.byref(us)))
         return FundamentalEstimate(F, Fr, mask.view(np.bool_), inl, best, success.view(np.bool_), status, hyp, n_ok.value,
                                    us.value, edge_ptr)
+
+    def homography_ransac(self, pts1, pts2, edge_ptr=None, pair_use=None, samples=None, want_hyp=False, **options):
+        """A homography ``x2 ~ H x1`` by RANSAC for every edge of a batch of matched pixel pairs (include/sfmba.h:
+        sfmba_homography_ransac), the sibling of :meth:`fundamental_ransac`: the same batch arguments and the same
+        ``options`` (fields of ``sfmba_ransac_options``); ``samples`` (E, H, 4) int32 positions among an edge's used
+        pairs, None = drawn on the device from ``seed``; with ``samples`` given, ``max_iters`` defaults to its H.
+        ``want_hyp``: also return the count of every hypothesis.  Needs no problem.  -> :class:`HomographyEstimate`."""
+        pts1, pts2, edge_ptr, use = _edge_batch(pts1, pts2, edge_ptr, pair_use)
+        E, M = edge_ptr.shape[0] - 1, pts1.shape[0]
+        samples = _homography_samples(samples, E)
+        self._flush_pending()
+        opt = _capi.RansacOptions()
+        self._lib.sfmba_default_ransac_options(C.byref(opt))
+        options = dict(options)
+        if "seed" in options:
+            seed = int(options.pop("seed"))
+            if not 0 <= seed < 2 ** 64:
+                raise ValueError("seed must fit 64 unsigned bits")
+            opt.seed = seed
+        if samples is not None:
+            options.setdefault("max_iters", samples.shape[1])
+        _fill_options(opt, options, "RANSAC")
+        if opt.max_iters < 1:
+            raise ValueError("max_iters must be at least 1")
+        if samples is not None and samples.shape[1] != opt.max_iters:
+            raise ValueError(f"samples holds {samples.shape[1]} hypotheses per edge, max_iters is {opt.max_iters}")
+        H = int(opt.max_iters)
+        Hm, Hr = np.empty((E, 3, 3)), np.empty((E, 3, 3))
+        mask, rmask = np.empty(M, dtype=np.uint8), np.empty(M, dtype=np.uint8)
+        inl, rinl, best, status = (np.empty(E, dtype=np.int32) for _ in range(4))
+        success = np.empty(E, dtype=np.uint8)
+        hyp = np.empty((E, H), dtype=np.int32) if want_hyp else None
+        n_ok, us = C.c_int64(), C.c_double()
+        self._check(self._lib.sfmba_homography_ransac(
+            self._h, E, _capi.ptr(edge_ptr), _capi.ptr(pts1), _capi.ptr(pts2), _opt_ptr(use), _opt_ptr(samples), C.byref(opt),
+            _capi.ptr(Hm), _capi.ptr(Hr), _capi.ptr(mask), _capi.ptr(rmask), _capi.ptr(inl), _capi.ptr(rinl), _capi.ptr(best),
+            _capi.ptr(success), _capi.ptr(status), _opt_ptr(hyp), C.byref(n_ok), C.byref(us)))
+        return HomographyEstimate(Hm, Hr, mask.view(np.bool_), rmask.view(np.bool_), inl, rinl, best, success.view(np.bool_),
+                                  status, hyp, n_ok.value, us.value, edge_ptr)
 
     def recover_pose(self, E, pts1, pts2, K, edge_ptr=None, pair_use=None, **options):
         """R, t, the cheirality mask, the points and their ray angles for every edge of a batch, the reference's
