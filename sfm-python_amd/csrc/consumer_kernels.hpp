@@ -1174,16 +1174,18 @@ __global__ __launch_bounds__(kCamThreads) void k_resect(ResectIn in, int C, KMat
 // Two-view geometry (sfmba_fundamental_ransac, sfmba_recover_pose).  A batch of edges (image
 // pairs), each a run of used pixel pairs x1 y1 x2 y2 (32 bytes, packed by the host in stored order); nothing of a
 // bundle-adjustment problem is read.
-//   k_fund_ransac   grid over (edge, slice of hypotheses); a wave takes one hypothesis at a time: eight sampled pairs ->
-//                   the reference's estimate_fundamental_matrix (one-scale normalisation, A^T A of the eight rows, its
-//                   smallest eigenvector by jacobi_lds<9>, rank 2 by a 3x3 Jacobi in registers, T2^T F T1), then the
-//                   lanes stride the edge's pairs and count |x2^T F x1| / |(F x1)_xy| < threshold by ballot / popcount.
-//                   A workgroup leaves the best (count, h, F) of its slice in a slot of its own.
-//   k_fund_finish   one workgroup per edge: best slot (largest count, lowest h), the mask of that F, the refit over all
-//                   its inliers (sums by block_sum, the 9x9 Jacobi by wave 0), unit norm and sign.
-//   k_homog_ransac, k_homog_finish   the same two for a homography (sfmba_homography_ransac): four
-//                   sampled pairs, the DLT's eight rows, the same Jacobi, T2^-1 Hn T1, the transfer distance in image 2;
-//                   the finish adds the mask and count of the refit.
+// The RANSAC and its finish are written once over a model (FundModel, HomogModel: what a model supplies is listed above
+// them); the four kernels are that code with a model bound:
+//   k_fund_ransac, k_homog_ransac   twoview_ransac<M>: grid over (edge, slice of hypotheses); a wave takes one hypothesis
+//                   at a time (twoview_slice<M>): M::S sampled pairs (ransac_sample) -> one-scale normalisation, A^T A of
+//                   the model's eight rows, its smallest eigenvector by jacobi_lds<9>, M::from_jacobi (F, the reference's
+//                   estimate_fundamental_matrix: rank 2 by a 3x3 Jacobi in registers, T2^T F T1; H: T2^-1 Hn T1), then
+//                   the lanes stride the edge's pairs and count M::inlier (F: |x2^T F x1| / |(F x1)_xy| < threshold; H:
+//                   the squared transfer distance in image 2) by ballot / popcount.  A workgroup leaves the best (count,
+//                   h, matrix) of its slice in a slot of its own.
+//   k_fund_finish, k_homog_finish   twoview_finish<M>: one workgroup per edge: best slot (largest count, lowest h), the
+//                   mask of that matrix, the refit over all its inliers (sums by block_sum, the 9x9 Jacobi by wave 0),
+//                   unit norm and sign; a model with kRefitMask (H) adds the mask and count of the refit.
 //   k_recover_pose  one workgroup per edge: wave 0 decomposes E into the four (R, t), every pair is triangulated against
 //                   each (two-view DLT, smallest_eigenvector4) and counted in front; thread 0 decides; a second pass
 //                   writes the winner's points, mask, ray angles and the summed reprojection error.
@@ -1261,59 +1263,143 @@ __device__ __forceinline__ void twoview_draw(unsigned long long seed, unsigned e
     }
 }
 
-// the row of construct_matrix_A of one normalised pair
-__device__ __forceinline__ void fund_row(double x1, double y1, double x2, double y2, double (&r)[9]) {
-    r[0] = x2 * x1; r[1] = x2 * y1; r[2] = x2; r[3] = y2 * x1; r[4] = y2 * y1; r[5] = y2; r[6] = x1; r[7] = y1; r[8] = 1.0;
-}
-// After jacobi_lds<9>: f = the eigenvector of the smallest eigenvalue, rank 2 forced by removing the smallest singular
-// direction (F <- F - (F v3) v3^T, v3 the smallest eigenvector of F^T F), then T2^T F T1 with T = [[1/s, 0, -mx/s],
-// [0, 1/s, -my/s], [0, 0, 1]].  Every lane of the calling wave leaves with the same F.
-__device__ __forceinline__ void fund_from_jacobi(const volatile double* A, const volatile double* V, double m1x, double m1y,
-                                                 double s1, double m2x, double m2y, double s2, double (&F)[9]) {
-    int lo = 0;
-    double least = A[0];
+// The S positions of hypothesis h of item b (an edge, a camera) among its n >= S entries: the caller's (samples
+// [batch][H][S]; false when one lies outside 0 .. n - 1 or two are equal) or, samples null, drawn by twoview_draw
+template <int S>
+__device__ __forceinline__ bool ransac_sample(const int* __restrict__ samples, int b, int H, int h, int n, unsigned long long seed,
+                                              int (&idx)[S]) {
+    bool valid = true;
+    if (samples != nullptr) {
+        const int* __restrict__ sp = samples + ((size_t)b * (size_t)H + (size_t)h) * S;
 #pragma unroll
-    for (int k = 1; k < 9; ++k) { const double d = A[10 * k]; if (d < least) { least = d; lo = k; } }
+        for (int j = 0; j < S; ++j) { idx[j] = sp[j]; valid = valid && idx[j] >= 0 && idx[j] < n; }
 #pragma unroll
-    for (int k = 0; k < 9; ++k) F[k] = V[9 * k + lo];
-    double a[6], w[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+        for (int j = 1; j < S; ++j)
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = i; j < 3; ++j) a[sym<3>(i, j)] = F[i] * F[j] + F[3 + i] * F[3 + j] + F[6 + i] * F[6 + j];
-    jacobi_sweeps<3>(a, w);
-    // (the columns as values behind an empty statement: without it the compiler selects an ADDRESS by the comparisons
-    // below and reads the column from scratch memory)
-    double w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4], w5 = w[5], w6 = w[6], w7 = w[7], w8 = w[8];
-    asm volatile("" : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3), "+v"(w4), "+v"(w5), "+v"(w6), "+v"(w7), "+v"(w8));
-    double l3 = a[0], v0 = w0, v1 = w3, v2 = w6;
-    if (a[3] < l3) { l3 = a[3]; v0 = w1; v1 = w4; v2 = w7; }
-    if (a[5] < l3) { l3 = a[5]; v0 = w2; v1 = w5; v2 = w8; }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const double fv = F[3 * i] * v0 + F[3 * i + 1] * v1 + F[3 * i + 2] * v2;
-        F[3 * i] -= fv * v0; F[3 * i + 1] -= fv * v1; F[3 * i + 2] -= fv * v2;
+            for (int i = 0; i < j; ++i) valid = valid && idx[i] != idx[j];
+    } else {
+        twoview_draw(seed, (unsigned)b, (unsigned)h, n, idx);
     }
-    const double a1 = 1.0 / s1, b1 = -m1x / s1, c1 = -m1y / s1, a2 = 1.0 / s2, b2 = -m2x / s2, c2 = -m2y / s2;
-    double G[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        G[3 * i] = F[3 * i] * a1; G[3 * i + 1] = F[3 * i + 1] * a1;
-        G[3 * i + 2] = F[3 * i] * b1 + F[3 * i + 1] * c1 + F[3 * i + 2];
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        F[j] = a2 * G[j]; F[3 + j] = a2 * G[3 + j];
-        F[6 + j] = b2 * G[j] + c2 * G[3 + j] + G[6 + j];
-    }
+    return valid;
 }
-// the reference's score: the distance of x2 from the line F x1, one-sided, strictly below the threshold; a non-finite
-// distance is no inlier (NaN compares false; +inf < thr is false)
-__device__ __forceinline__ bool fund_inlier(const double (&F)[9], double x1, double y1, double x2, double y2, double thr) {
-    const double l0 = F[0] * x1 + F[1] * y1 + F[2], l1 = F[3] * x1 + F[4] * y1 + F[5], l2 = F[6] * x1 + F[7] * y1 + F[8];
-    const double d = fabs(x2 * l0 + y2 * l1 + l2) / sqrt(l0 * l0 + l1 * l1);
-    return d < thr && d < INFINITY;
-}
+
+// ---- The model of a two-view RANSAC: what twoview_slice, twoview_ransac, twoview_ata_rows and twoview_finish below ask of
+// an estimator.  A model is a 3x3 matrix, the null vector of a 9-column system of normalised pairs:
+//   S            pairs of a sample, and the fewest inliers of an estimate
+//   kRefitMask   whether the finish also returns the mask and count of the refit (a second mask, a fifth integer per edge)
+//   kOk, kFewPairs, kDegenerate   its status values
+//   kRows, rows  the rows a normalised pair gives the system (kRows * S = 8).  Pair j of a sample stores row q at
+//                S q + j of the wave's R (F: j; H: the four first rows, then the four second rows); the refit adds a
+//                pair's rows to the sums of A^T A in the order q = 0, 1
+//   from_jacobi after jacobi_lds<9>: the matrix in pixel coordinates, the same on every lane of the calling wave
+//   inlier       the one-sided score of a pixel pair against the matrix, strictly below `score` (the host's argument:
+//                the threshold for F, its square for H); a non-finite distance is no inlier
+constexpr int kHomogOk = 0, kHomogFewPairs = 1, kHomogDegenerate = 2;
+
+// the reference's estimate_fundamental_matrix: eight pairs, a row of construct_matrix_A each, the distance to the epipolar line
+struct FundModel {
+    static constexpr int S = 8;
+    static constexpr bool kRefitMask = false;
+    static constexpr int kOk = kFundOk, kFewPairs = kFundFewPairs, kDegenerate = kFundDegenerate;
+
+    static constexpr int kRows = 1;
+    static __device__ __forceinline__ void rows(double x1, double y1, double x2, double y2, double (&r)[1][9]) {
+        r[0][0] = x2 * x1; r[0][1] = x2 * y1; r[0][2] = x2; r[0][3] = y2 * x1; r[0][4] = y2 * y1; r[0][5] = y2; r[0][6] = x1; r[0][7] = y1; r[0][8] = 1.0;
+    }
+    // f = the eigenvector of the smallest eigenvalue, rank 2 forced by removing the smallest singular direction
+    // (F <- F - (F v3) v3^T, v3 the smallest eigenvector of F^T F), then T2^T F T1 with T = [[1/s, 0, -mx/s],
+    // [0, 1/s, -my/s], [0, 0, 1]]
+    static __device__ __forceinline__ void from_jacobi(const volatile double* A, const volatile double* V, double m1x, double m1y,
+                                                       double s1, double m2x, double m2y, double s2, double (&F)[9]) {
+        int lo = 0;
+        double least = A[0];
+#pragma unroll
+        for (int k = 1; k < 9; ++k) { const double d = A[10 * k]; if (d < least) { least = d; lo = k; } }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) F[k] = V[9 * k + lo];
+        double a[6], w[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = i; j < 3; ++j) a[sym<3>(i, j)] = F[i] * F[j] + F[3 + i] * F[3 + j] + F[6 + i] * F[6 + j];
+        jacobi_sweeps<3>(a, w);
+        // (the columns as values behind an empty statement: without it the compiler selects an ADDRESS by the comparisons
+        // below and reads the column from scratch memory)
+        double w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4], w5 = w[5], w6 = w[6], w7 = w[7], w8 = w[8];
+        asm volatile("" : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3), "+v"(w4), "+v"(w5), "+v"(w6), "+v"(w7), "+v"(w8));
+        double l3 = a[0], v0 = w0, v1 = w3, v2 = w6;
+        if (a[3] < l3) { l3 = a[3]; v0 = w1; v1 = w4; v2 = w7; }
+        if (a[5] < l3) { l3 = a[5]; v0 = w2; v1 = w5; v2 = w8; }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double fv = F[3 * i] * v0 + F[3 * i + 1] * v1 + F[3 * i + 2] * v2;
+            F[3 * i] -= fv * v0; F[3 * i + 1] -= fv * v1; F[3 * i + 2] -= fv * v2;
+        }
+        const double a1 = 1.0 / s1, b1 = -m1x / s1, c1 = -m1y / s1, a2 = 1.0 / s2, b2 = -m2x / s2, c2 = -m2y / s2;
+        double G[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            G[3 * i] = F[3 * i] * a1; G[3 * i + 1] = F[3 * i + 1] * a1;
+            G[3 * i + 2] = F[3 * i] * b1 + F[3 * i + 1] * c1 + F[3 * i + 2];
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            F[j] = a2 * G[j]; F[3 + j] = a2 * G[3 + j];
+            F[6 + j] = b2 * G[j] + c2 * G[3 + j] + G[6 + j];
+        }
+    }
+    // the reference's score: the distance of x2 from the line F x1 (NaN compares false; +inf < thr is false)
+    static __device__ __forceinline__ bool inlier(const double (&F)[9], double x1, double y1, double x2, double y2, double thr) {
+        const double l0 = F[0] * x1 + F[1] * y1 + F[2], l1 = F[3] * x1 + F[4] * y1 + F[5], l2 = F[6] * x1 + F[7] * y1 + F[8];
+        const double d = fabs(x2 * l0 + y2 * l1 + l2) / sqrt(l0 * l0 + l1 * l1);
+        return d < thr && d < INFINITY;
+    }
+};
+
+// a four-pair DLT homography x2 ~ H x1 (sfmba_homography_ransac): two rows a pair, the transfer distance in image 2
+struct HomogModel {
+    static constexpr int S = 4;
+    static constexpr bool kRefitMask = true;
+    static constexpr int kOk = kHomogOk, kFewPairs = kHomogFewPairs, kDegenerate = kHomogDegenerate;
+
+    static constexpr int kRows = 2;
+    static __device__ __forceinline__ void rows(double x, double y, double u, double v, double (&r)[2][9]) {
+        r[0][0] = -x; r[0][1] = -y; r[0][2] = -1.0; r[0][3] = 0.0; r[0][4] = 0.0; r[0][5] = 0.0; r[0][6] = u * x; r[0][7] = u * y; r[0][8] = u;
+        r[1][0] = 0.0; r[1][1] = 0.0; r[1][2] = 0.0; r[1][3] = -x; r[1][4] = -y; r[1][5] = -1.0; r[1][6] = v * x; r[1][7] = v * y; r[1][8] = v;
+    }
+    // Hn = the eigenvector of the smallest eigenvalue, then T2^-1 Hn T1 with T1 = [[1/s1, 0, -m1x/s1], [0, 1/s1, -m1y/s1],
+    // [0, 0, 1]] and T2^-1 = [[s2, 0, m2x], [0, s2, m2y], [0, 0, 1]]
+    static __device__ __forceinline__ void from_jacobi(const volatile double* A, const volatile double* V, double m1x, double m1y,
+                                                       double s1, double m2x, double m2y, double s2, double (&Hm)[9]) {
+        int lo = 0;
+        double least = A[0];
+#pragma unroll
+        for (int k = 1; k < 9; ++k) { const double d = A[10 * k]; if (d < least) { least = d; lo = k; } }
+        double Hn[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Hn[k] = V[9 * k + lo];
+        const double a1 = 1.0 / s1, b1 = -m1x / s1, c1 = -m1y / s1;
+        double G[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            G[3 * i] = Hn[3 * i] * a1; G[3 * i + 1] = Hn[3 * i + 1] * a1;
+            G[3 * i + 2] = Hn[3 * i] * b1 + Hn[3 * i + 1] * c1 + Hn[3 * i + 2];
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            Hm[j] = s2 * G[j] + m2x * G[6 + j]; Hm[3 + j] = s2 * G[3 + j] + m2y * G[6 + j];
+            Hm[6 + j] = G[6 + j];
+        }
+    }
+    // the squared distance of x2 from the transferred H x1 (NaN compares false; +inf < thr2 is false)
+    static __device__ __forceinline__ bool inlier(const double (&Hm)[9], double x1, double y1, double x2, double y2, double thr2) {
+        const double q0 = Hm[0] * x1 + Hm[1] * y1 + Hm[2], q1 = Hm[3] * x1 + Hm[4] * y1 + Hm[5], q2 = Hm[6] * x1 + Hm[7] * y1 + Hm[8];
+        const double dx = q0 / q2 - x2, dy = q1 / q2 - y2;
+        const double d2 = dx * dx + dy * dy;
+        return d2 < thr2 && d2 < INFINITY;
+    }
+};
+
 // unit Frobenius norm, the entry of largest magnitude (the first of equals) positive
 __device__ __forceinline__ void fund_unit(double (&F)[9]) {
     double ss = 0.0, big = 0.0, sgn = 1.0;
@@ -1327,62 +1413,54 @@ __device__ __forceinline__ void fund_unit(double (&F)[9]) {
 struct FundIn {
     const double* __restrict__ pairs;            // [M_used][4] x1 y1 x2 y2
     const int* __restrict__ uptr;                // [n_edges + 1] runs of used pairs
-    const int* __restrict__ samples;             // [n_edges][H][8] (F) or [n_edges][H][4] (H) positions among the used pairs, or null: drawn
+    const int* __restrict__ samples;             // [n_edges][H][S] positions among the used pairs, or null: drawn
 };
 
 // the hypotheses h0 + w, h0 + w + 4, ... < h1 of edge e by wave w; P: the edge's pairs (LDS or global)
-__device__ __forceinline__ void fund_slice(const double* P, const FundIn& in, int e, int n, int H, int h0, int h1,
-                                           unsigned long long seed, double thr, volatile double* A, volatile double* V,
-                                           volatile double* R, int* __restrict__ hyp, int& bc, int& bh, double (&bF)[9]) {
+template <class M>
+__device__ __forceinline__ void twoview_slice(const double* P, const int* __restrict__ samples, int e, int n, int H, int h0, int h1,
+                                              unsigned long long seed, double score, volatile double* A, volatile double* V,
+                                              volatile double* R, int* __restrict__ hyp, int& bc, int& bh, double (&bM)[9]) {
+    constexpr int S = M::S;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const double2* __restrict__ P2 = reinterpret_cast<const double2*>(P);
     bc = -1; bh = 0x7fffffff;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) bF[k] = 0.0;
+    for (int k = 0; k < 9; ++k) bM[k] = 0.0;
 #pragma unroll 1
     for (int h = h0 + w; h < h1; h += kTwoViewWaves) {
-        int idx[8];
-        bool valid = true;
-        if (in.samples != nullptr) {
-            const int* __restrict__ sp = in.samples + ((size_t)e * (size_t)H + (size_t)h) * 8;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { idx[j] = sp[j]; valid = valid && idx[j] >= 0 && idx[j] < n; }
-#pragma unroll
-            for (int j = 1; j < 8; ++j)
-#pragma unroll
-                for (int i = 0; i < j; ++i) valid = valid && idx[i] != idx[j];
-        } else {
-            twoview_draw(seed, (unsigned)e, (unsigned)h, n, idx);
-        }
-        if (!valid) {                                            // (uniform over the wave)
+        int idx[S];
+        if (!ransac_sample(samples, e, H, h, n, seed, idx)) {    // (uniform over the wave)
             if (lane == 0 && hyp != nullptr) hyp[(size_t)e * (size_t)H + (size_t)h] = -1;
             continue;
         }
-        double x1[8], y1[8], x2[8], y2[8];
+        double x1[S], y1[S], x2[S], y2[S];
         double m1x = 0.0, m1y = 0.0, m2x = 0.0, m2y = 0.0;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = 0; j < S; ++j) {
             const double2 qa = P2[2 * idx[j]], qb = P2[2 * idx[j] + 1];
             x1[j] = qa.x; y1[j] = qa.y; x2[j] = qb.x; y2[j] = qb.y;
             m1x += qa.x; m1y += qa.y; m2x += qb.x; m2y += qb.y;
         }
-        const double g1 = (m1x + m1y) / 16.0, g2 = (m2x + m2y) / 16.0;     // np.std: about the mean of all 16 coordinates
-        m1x /= 8.0; m1y /= 8.0; m2x /= 8.0; m2y /= 8.0;
+        const double g1 = (m1x + m1y) / (2.0 * S), g2 = (m2x + m2y) / (2.0 * S);   // np.std: about the mean of all 2 S coordinates
+        m1x /= (double)S; m1y /= (double)S; m2x /= (double)S; m2y /= (double)S;
         double q1 = 0.0, q2 = 0.0;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = 0; j < S; ++j) {
             q1 += (x1[j] - g1) * (x1[j] - g1) + (y1[j] - g1) * (y1[j] - g1);
             q2 += (x2[j] - g2) * (x2[j] - g2) + (y2[j] - g2) * (y2[j] - g2);
         }
-        const double s1 = sqrt(q1 / 16.0), s2 = sqrt(q2 / 16.0);
+        const double s1 = sqrt(q1 / (2.0 * S)), s2 = sqrt(q2 / (2.0 * S));
         // the eight rows through LDS (lane 0 stores them), then lane i < 9 sums row i of A^T A over the rows 0..7
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            double r[9];
-            fund_row((x1[j] - m1x) / s1, (y1[j] - m1y) / s1, (x2[j] - m2x) / s2, (y2[j] - m2y) / s2, r);
+        for (int j = 0; j < S; ++j) {
+            double r[M::kRows][9];
+            M::rows((x1[j] - m1x) / s1, (y1[j] - m1y) / s1, (x2[j] - m2x) / s2, (y2[j] - m2y) / s2, r);
             if (lane == 0) {
 #pragma unroll
-                for (int i = 0; i < 9; ++i) R[9 * j + i] = r[i];
+                for (int i = 0; i < 9; ++i)
+#pragma unroll
+                    for (int q = 0; q < M::kRows; ++q) R[9 * (S * q + j) + i] = r[q][i];
             }
         }
         if (lane < 9) {
@@ -1397,36 +1475,40 @@ __device__ __forceinline__ void fund_slice(const double* P, const FundIn& in, in
             for (int c = 0; c < 9; ++c) { A[9 * lane + c] = acc[c]; V[9 * lane + c] = c == lane ? 1.0 : 0.0; }
         }
         jacobi_lds<9>(A, V, lane);
-        double F[9];
-        fund_from_jacobi(A, V, m1x, m1y, s1, m2x, m2y, s2, F);
+        double Mh[9];
+        M::from_jacobi(A, V, m1x, m1y, s1, m2x, m2y, s2, Mh);
         int cnt = 0;
 #pragma unroll 1
         for (int k0 = 0; k0 < n; k0 += 64) {                     // uniform over the wave: the ballot needs every lane
             const int k = k0 + lane;
             bool inl = false;
-            if (k < n) { const double2 qa = P2[2 * k], qb = P2[2 * k + 1]; inl = fund_inlier(F, qa.x, qa.y, qb.x, qb.y, thr); }
+            if (k < n) { const double2 qa = P2[2 * k], qb = P2[2 * k + 1]; inl = M::inlier(Mh, qa.x, qa.y, qb.x, qb.y, score); }
             cnt += __popcll(__ballot(inl));
         }
         if (lane == 0 && hyp != nullptr) hyp[(size_t)e * (size_t)H + (size_t)h] = cnt;
         if (cnt > bc) {                                          // (h ascends: the lowest h of equal counts stays)
             bc = cnt; bh = h;
 #pragma unroll
-            for (int k = 0; k < 9; ++k) bF[k] = F[k];
+            for (int k = 0; k < 9; ++k) bM[k] = Mh[k];
         }
     }
 }
 
-__global__ __launch_bounds__(kTwoViewThreads) void k_fund_ransac(FundIn in, int H, int hs, int n_slices, unsigned long long seed,
-                                                                 double thr, double* __restrict__ slots, int* __restrict__ hyp) {
+// grid over (edge, slice of hypotheses): the best (count, h, matrix) of the workgroup's slice into its slot.  (This body
+// and twoview_finish take plain pointers: the kernels' own parameters carry __restrict__, and saying it again here moves
+// their code away from what it was as one function)
+template <class M>
+__device__ __forceinline__ void twoview_ransac(const double* pairs, const int* uptr, const int* samples, int H, int hs, int n_slices,
+                                               unsigned long long seed, double score, double* slots, int* hyp) {
     extern __shared__ __align__(16) double smem[];
     __shared__ double jA[kTwoViewWaves][81], jV[kTwoViewWaves][81], jR[kTwoViewWaves][72];
     __shared__ double wbest[kTwoViewWaves][kTwoViewSlot];
     const int e = blockIdx.x / n_slices, sl = blockIdx.x - e * n_slices;
-    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
+    const int b = uptr[e], n = uptr[e + 1] - b;
     const int h0 = sl * hs, h1 = min(H, h0 + hs);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     double* __restrict__ slot = slots + (size_t)blockIdx.x * kTwoViewSlot;
-    if (n < 8) {                                                 // (uniform over the workgroup) FEW_PAIRS: no hypothesis
+    if (n < M::S) {                                              // (uniform over the workgroup) FEW_PAIRS: no hypothesis
         if (hyp != nullptr)
             for (int h = h0 + (int)threadIdx.x; h < h1; h += kTwoViewThreads) hyp[(size_t)e * (size_t)H + (size_t)h] = -1;
         if (threadIdx.x == 0) {
@@ -1436,19 +1518,19 @@ __global__ __launch_bounds__(kTwoViewThreads) void k_fund_ransac(FundIn in, int 
         }
         return;
     }
-    const double* __restrict__ gp = in.pairs + 4 * (size_t)b;
+    const double* __restrict__ gp = pairs + 4 * (size_t)b;
     int bc, bh;
-    double bF[9];
+    double bM[9];
     if (n <= kTwoViewLdsPairs) {
         stage_table(gp, 4 * n, smem);
-        fund_slice(smem, in, e, n, H, h0, h1, seed, thr, jA[w], jV[w], jR[w], hyp, bc, bh, bF);
+        twoview_slice<M>(smem, samples, e, n, H, h0, h1, seed, score, jA[w], jV[w], jR[w], hyp, bc, bh, bM);
     } else {
-        fund_slice(gp, in, e, n, H, h0, h1, seed, thr, jA[w], jV[w], jR[w], hyp, bc, bh, bF);
+        twoview_slice<M>(gp, samples, e, n, H, h0, h1, seed, score, jA[w], jV[w], jR[w], hyp, bc, bh, bM);
     }
     if (lane == 0) {
         wbest[w][0] = (double)bc; wbest[w][1] = (double)bh;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) wbest[w][2 + k] = bF[k];
+        for (int k = 0; k < 9; ++k) wbest[w][2 + k] = bM[k];
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1463,9 +1545,9 @@ __global__ __launch_bounds__(kTwoViewThreads) void k_fund_ransac(FundIn in, int 
 
 // rows I0 .. I1 - 1 of the upper triangle of A^T A over the pairs of the mask mk (its own stores), thread t taking pairs t, t + 256, ...; thread 0
 // stores them (and their mirror) into A
-template <int I0, int I1>
-__device__ __forceinline__ void fund_ata_rows(const double2* __restrict__ P2, int n, const unsigned char* mk, double m1x,
-                                              double m1y, double s1, double m2x, double m2y, double s2, double* red, double* A) {
+template <class M, int I0, int I1>
+__device__ __forceinline__ void twoview_ata_rows(const double2* __restrict__ P2, int n, const unsigned char* mk, double m1x,
+                                                 double m1y, double s1, double m2x, double m2y, double s2, double* red, double* A) {
     constexpr int NS = sym<9>(I1 - 1, 8) - sym<9>(I0, I0) + 1, Q0 = sym<9>(I0, I0);
     double s[NS];
 #pragma unroll
@@ -1474,12 +1556,14 @@ __device__ __forceinline__ void fund_ata_rows(const double2* __restrict__ P2, in
     for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
         const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
         if (!mk[k]) continue;
-        double r[9];
-        fund_row((qa.x - m1x) / s1, (qa.y - m1y) / s1, (qb.x - m2x) / s2, (qb.y - m2y) / s2, r);
+        double r[M::kRows][9];
+        M::rows((qa.x - m1x) / s1, (qa.y - m1y) / s1, (qb.x - m2x) / s2, (qb.y - m2y) / s2, r);
 #pragma unroll
         for (int i = I0; i < I1; ++i)
 #pragma unroll
-            for (int c = i; c < 9; ++c) s[sym<9>(i, c) - Q0] += r[i] * r[c];
+            for (int c = i; c < 9; ++c)
+#pragma unroll
+                for (int q = 0; q < M::kRows; ++q) s[sym<9>(i, c) - Q0] += r[q][i] * r[q][c];
     }
     block_sum<NS>(s, red);
     if (threadIdx.x == 0) {
@@ -1490,23 +1574,23 @@ __device__ __forceinline__ void fund_ata_rows(const double2* __restrict__ P2, in
     }
 }
 
-struct FundOut {
-    double* __restrict__ F;                      // [E][9]
-    double* __restrict__ F_refit;                // [E][9]
-    unsigned char* __restrict__ mask;            // [M_used]
-    int* __restrict__ ints;                      // [E][4] inliers, best h, status, success
-};
-
-__global__ __launch_bounds__(kTwoViewThreads) void k_fund_finish(FundIn in, int n_slices, double thr, double confidence, int refit,
-                                                                 const double* __restrict__ slots, FundOut out) {
+// One workgroup per edge: best slot (largest count, lowest h), the mask of that matrix, the refit over all its inliers
+// (sums by block_sum, the 9x9 Jacobi by wave 0), unit norm and sign; with M::kRefitMask one more pass over the pairs for the
+// mask and count of the refit.  oM, oM_refit [E][9]; omask, orefit_mask [M_used]; oints [E][4 or 5] inliers, best h, status,
+// success, refit inliers.
+template <class M>
+__device__ __forceinline__ void twoview_finish(const double* pairs, const int* uptr, int n_slices, double score, double confidence,
+                                               int refit, const double* slots, double* oM, double* oM_refit, unsigned char* omask,
+                                               unsigned char* orefit_mask, int* oints) {
     __shared__ double red[kTwoViewWaves * 18];
     __shared__ double jA[81], jV[81];
-    __shared__ double sF[9], sm[9];
+    __shared__ double sM[9], sm[9];
     __shared__ int ctl[2];
     const int e = blockIdx.x;
-    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
+    const int b = uptr[e], n = uptr[e + 1] - b;
     const bool first = threadIdx.x == 0;
-    const double2* __restrict__ P2 = reinterpret_cast<const double2*>(in.pairs + 4 * (size_t)b);
+    const double2* __restrict__ P2 = reinterpret_cast<const double2*>(pairs + 4 * (size_t)b);
+    int* __restrict__ oi = oints + (M::kRefitMask ? 5 : 4) * (size_t)e;
     if (first) {
         const double* __restrict__ sl = slots + (size_t)e * (size_t)n_slices * kTwoViewSlot;
         int best = 0;
@@ -1515,65 +1599,73 @@ __global__ __launch_bounds__(kTwoViewThreads) void k_fund_finish(FundIn in, int 
         const double* __restrict__ bs = sl + (size_t)best * kTwoViewSlot;
         double sum = 0.0;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) { sF[k] = bs[2 + k]; sum += fabs(bs[2 + k]); }
-        ctl[0] = n < 8 ? kFundFewPairs : (sum < INFINITY ? kFundOk : kFundDegenerate);
+        for (int k = 0; k < 9; ++k) { sM[k] = bs[2 + k]; sum += fabs(bs[2 + k]); }
+        ctl[0] = n < M::S ? M::kFewPairs : (sum < INFINITY ? M::kOk : M::kDegenerate);
         ctl[1] = bs[0] >= 0.0 ? (int)bs[1] : -1;                 // (-1: no valid sample in any slot)
     }
     __syncthreads();
-    const unsigned char* mk = out.mask + (size_t)b;              // a thread reads back only what it stored itself
-    if (ctl[0] == kFundFewPairs) {                               // (uniform over the workgroup)
-        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) out.mask[(size_t)b + k] = 0;
-        if (threadIdx.x < 9) { out.F[9 * (size_t)e + threadIdx.x] = 0.0; out.F_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
-        if (first) { int* __restrict__ oi = out.ints + 4 * (size_t)e; oi[0] = 0; oi[1] = -1; oi[2] = kFundFewPairs; oi[3] = 0; }
+    const unsigned char* mk = omask + (size_t)b;                 // a thread reads back only what it stored itself
+    if (ctl[0] == M::kFewPairs) {                                // (uniform over the workgroup)
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            omask[(size_t)b + k] = 0;
+            if constexpr (M::kRefitMask) orefit_mask[(size_t)b + k] = 0;
+        }
+        if (threadIdx.x < 9) { oM[9 * (size_t)e + threadIdx.x] = 0.0; oM_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
+        if (first) {
+            oi[0] = 0; oi[1] = -1; oi[2] = M::kFewPairs; oi[3] = 0;
+            if constexpr (M::kRefitMask) oi[4] = 0;
+        }
         return;
     }
-    // The mask of the best F, and the count FROM that mask: edge_inliers, edge_success, the status and the refit below all
-    // rest on this one evaluation (the count in the slot came from another copy of the expression, which the compiler may
-    // have contracted differently for a pair within an ulp of the threshold).
-    double F[9];
+    // The mask of the best matrix, and the count FROM that mask: edge_inliers, edge_success, the status and the refit below
+    // all rest on this one evaluation (the count in the slot came from another copy of the expression, which the compiler may
+    // have contracted differently for a pair within an ulp of the threshold).  A refit mask starts as its copy (refit = 0
+    // and DEGENERATE leave it so).
+    double Mb[9];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) F[k] = sF[k];
+    for (int k = 0; k < 9; ++k) Mb[k] = sM[k];
     {
         double c[1] = {0.0};
         for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
             const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
-            const bool inl = ctl[1] >= 0 && fund_inlier(F, qa.x, qa.y, qb.x, qb.y, thr);
-            out.mask[(size_t)b + k] = inl ? 1 : 0;
+            const bool inl = ctl[1] >= 0 && M::inlier(Mb, qa.x, qa.y, qb.x, qb.y, score);
+            omask[(size_t)b + k] = inl ? 1 : 0;
+            if constexpr (M::kRefitMask) orefit_mask[(size_t)b + k] = inl ? 1 : 0;
             c[0] += inl ? 1.0 : 0.0;
         }
         block_sum<1>(c, red);
         if (first) {
             const int cnt = (int)c[0];
-            if (ctl[0] == kFundOk && cnt < 8) ctl[0] = kFundDegenerate;
+            if (ctl[0] == M::kOk && cnt < M::S) ctl[0] = M::kDegenerate;
             sm[8] = (double)cnt;
-            int* __restrict__ oi = out.ints + 4 * (size_t)e;
-            // (DEGENERATE still reports the count, h and mask of its best hypothesis; only F is withheld)
+            // (DEGENERATE still reports the count, h and mask of its best hypothesis; only the matrix is withheld)
             oi[0] = cnt; oi[1] = ctl[1]; oi[2] = ctl[0];
             oi[3] = (ctl[1] >= 0 && (double)cnt / (double)n >= confidence) ? 1 : 0;
+            if constexpr (M::kRefitMask) oi[4] = cnt;
         }
         __syncthreads();
     }
     const int status = ctl[0], cnt = (int)sm[8];
-    if (status != kFundOk) {
-        if (threadIdx.x < 9) { out.F[9 * (size_t)e + threadIdx.x] = 0.0; out.F_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
+    if (status != M::kOk) {
+        if (threadIdx.x < 9) { oM[9 * (size_t)e + threadIdx.x] = 0.0; oM_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
         return;
     }
-    double Fu[9];
+    double Mu[9];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) Fu[k] = F[k];
-    fund_unit(Fu);
+    for (int k = 0; k < 9; ++k) Mu[k] = Mb[k];
+    fund_unit(Mu);
     if (first) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) out.F[9 * (size_t)e + k] = Fu[k];
+        for (int k = 0; k < 9; ++k) oM[9 * (size_t)e + k] = Mu[k];
     }
     if (!refit) {
         if (first) {
 #pragma unroll
-            for (int k = 0; k < 9; ++k) out.F_refit[9 * (size_t)e + k] = Fu[k];
+            for (int k = 0; k < 9; ++k) oM_refit[9 * (size_t)e + k] = Mu[k];
         }
         return;
     }
-    // the reference's estimate_fundamental_matrix over the cnt >= 8 inliers: thread t takes pairs t, t + 256, ...
+    // the same estimate over the cnt >= S inliers: thread t takes pairs t, t + 256, ...
     {
         double v[4] = {0.0, 0.0, 0.0, 0.0};
         for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
@@ -1605,231 +1697,53 @@ __global__ __launch_bounds__(kTwoViewThreads) void k_fund_finish(FundIn in, int 
     }
     const double s1 = sm[6], s2 = sm[7];
     // the 45 sums in three passes (rows 0-1, 2-4, 5-8 of the upper triangle): all of them at once in registers spilled
-    fund_ata_rows<0, 2>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
-    fund_ata_rows<2, 5>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
-    fund_ata_rows<5, 9>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
+    twoview_ata_rows<M, 0, 2>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
+    twoview_ata_rows<M, 2, 5>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
+    twoview_ata_rows<M, 5, 9>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
     if (first)
         for (int k = 0; k < 81; ++k) jV[k] = (k % 10) == 0 ? 1.0 : 0.0;
     if (threadIdx.x < 64) {                                      // wave 0: thread 0's stores above are its own
         jacobi_lds<9>(jA, jV, (int)threadIdx.x);
-        double Fr[9];
-        fund_from_jacobi(jA, jV, m1x, m1y, s1, m2x, m2y, s2, Fr);
-        fund_unit(Fr);
+        double Mr[9];
+        M::from_jacobi(jA, jV, m1x, m1y, s1, m2x, m2y, s2, Mr);
+        fund_unit(Mr);
         double sum = 0.0;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) sum += fabs(Fr[k]);
+        for (int k = 0; k < 9; ++k) sum += fabs(Mr[k]);
         if (first) {
 #pragma unroll
-            for (int k = 0; k < 9; ++k) out.F_refit[9 * (size_t)e + k] = sum < INFINITY ? Fr[k] : Fu[k];
-        }
-    }
-}
-
-// ---- sfmba_homography_ransac: the F pair's grid, slices, staging, slots and finish, with a
-// four-pair DLT homography as the hypothesis and the transfer distance in image 2 as the score ----
-constexpr int kHomogOk = 0, kHomogFewPairs = 1, kHomogDegenerate = 2;
-
-// the two DLT rows of one normalised pair (x, y) -> (u, v)
-__device__ __forceinline__ void homog_rows(double x, double y, double u, double v, double (&r0)[9], double (&r1)[9]) {
-    r0[0] = -x; r0[1] = -y; r0[2] = -1.0; r0[3] = 0.0; r0[4] = 0.0; r0[5] = 0.0; r0[6] = u * x; r0[7] = u * y; r0[8] = u;
-    r1[0] = 0.0; r1[1] = 0.0; r1[2] = 0.0; r1[3] = -x; r1[4] = -y; r1[5] = -1.0; r1[6] = v * x; r1[7] = v * y; r1[8] = v;
-}
-// After jacobi_lds<9>: Hn = the eigenvector of the smallest eigenvalue, then T2^-1 Hn T1 with T1 = [[1/s1, 0, -m1x/s1],
-// [0, 1/s1, -m1y/s1], [0, 0, 1]] and T2^-1 = [[s2, 0, m2x], [0, s2, m2y], [0, 0, 1]].  Every lane of the calling wave
-// leaves with the same H.
-__device__ __forceinline__ void homog_from_jacobi(const volatile double* A, const volatile double* V, double m1x, double m1y,
-                                                  double s1, double m2x, double m2y, double s2, double (&Hm)[9]) {
-    int lo = 0;
-    double least = A[0];
-#pragma unroll
-    for (int k = 1; k < 9; ++k) { const double d = A[10 * k]; if (d < least) { least = d; lo = k; } }
-    double Hn[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Hn[k] = V[9 * k + lo];
-    const double a1 = 1.0 / s1, b1 = -m1x / s1, c1 = -m1y / s1;
-    double G[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        G[3 * i] = Hn[3 * i] * a1; G[3 * i + 1] = Hn[3 * i + 1] * a1;
-        G[3 * i + 2] = Hn[3 * i] * b1 + Hn[3 * i + 1] * c1 + Hn[3 * i + 2];
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        Hm[j] = s2 * G[j] + m2x * G[6 + j]; Hm[3 + j] = s2 * G[3 + j] + m2y * G[6 + j];
-        Hm[6 + j] = G[6 + j];
-    }
-}
-// the score: the squared distance of x2 from the transferred H x1, one-sided, strictly below the squared threshold; a
-// non-finite distance is no inlier (NaN compares false; +inf < thr2 is false)
-__device__ __forceinline__ bool homog_inlier(const double (&Hm)[9], double x1, double y1, double x2, double y2, double thr2) {
-    const double q0 = Hm[0] * x1 + Hm[1] * y1 + Hm[2], q1 = Hm[3] * x1 + Hm[4] * y1 + Hm[5], q2 = Hm[6] * x1 + Hm[7] * y1 + Hm[8];
-    const double dx = q0 / q2 - x2, dy = q1 / q2 - y2;
-    const double d2 = dx * dx + dy * dy;
-    return d2 < thr2 && d2 < INFINITY;
-}
-
-// the hypotheses h0 + w, h0 + w + 4, ... < h1 of edge e by wave w; P: the edge's pairs (LDS or global); in.samples [.][H][4]
-__device__ __forceinline__ void homog_slice(const double* P, const FundIn& in, int e, int n, int H, int h0, int h1,
-                                            unsigned long long seed, double thr2, volatile double* A, volatile double* V,
-                                            volatile double* R, int* __restrict__ hyp, int& bc, int& bh, double (&bH)[9]) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const double2* __restrict__ P2 = reinterpret_cast<const double2*>(P);
-    bc = -1; bh = 0x7fffffff;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) bH[k] = 0.0;
-#pragma unroll 1
-    for (int h = h0 + w; h < h1; h += kTwoViewWaves) {
-        int idx[4];
-        bool valid = true;
-        if (in.samples != nullptr) {
-            const int* __restrict__ sp = in.samples + ((size_t)e * (size_t)H + (size_t)h) * 4;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { idx[j] = sp[j]; valid = valid && idx[j] >= 0 && idx[j] < n; }
-#pragma unroll
-            for (int j = 1; j < 4; ++j)
-#pragma unroll
-                for (int i = 0; i < j; ++i) valid = valid && idx[i] != idx[j];
-        } else {
-            twoview_draw(seed, (unsigned)e, (unsigned)h, n, idx);
-        }
-        if (!valid) {                                            // (uniform over the wave)
-            if (lane == 0 && hyp != nullptr) hyp[(size_t)e * (size_t)H + (size_t)h] = -1;
-            continue;
-        }
-        double x1[4], y1[4], x2[4], y2[4];
-        double m1x = 0.0, m1y = 0.0, m2x = 0.0, m2y = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double2 qa = P2[2 * idx[j]], qb = P2[2 * idx[j] + 1];
-            x1[j] = qa.x; y1[j] = qa.y; x2[j] = qb.x; y2[j] = qb.y;
-            m1x += qa.x; m1y += qa.y; m2x += qb.x; m2y += qb.y;
-        }
-        const double g1 = (m1x + m1y) / 8.0, g2 = (m2x + m2y) / 8.0;       // np.std: about the mean of all 8 coordinates
-        m1x /= 4.0; m1y /= 4.0; m2x /= 4.0; m2y /= 4.0;
-        double q1 = 0.0, q2 = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            q1 += (x1[j] - g1) * (x1[j] - g1) + (y1[j] - g1) * (y1[j] - g1);
-            q2 += (x2[j] - g2) * (x2[j] - g2) + (y2[j] - g2) * (y2[j] - g2);
-        }
-        const double s1 = sqrt(q1 / 8.0), s2 = sqrt(q2 / 8.0);
-        // the eight rows through LDS (lane 0 stores them: the four first rows, then the four second rows), then lane
-        // i < 9 sums row i of A^T A over the rows 0..7
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            double r0[9], r1[9];
-            homog_rows((x1[j] - m1x) / s1, (y1[j] - m1y) / s1, (x2[j] - m2x) / s2, (y2[j] - m2y) / s2, r0, r1);
-            if (lane == 0) {
-#pragma unroll
-                for (int i = 0; i < 9; ++i) { R[9 * j + i] = r0[i]; R[9 * (4 + j) + i] = r1[i]; }
+            for (int k = 0; k < 9; ++k) {
+                const double v = sum < INFINITY ? Mr[k] : Mu[k];
+                oM_refit[9 * (size_t)e + k] = v;
+                if constexpr (M::kRefitMask) sM[k] = v;
             }
         }
-        if (lane < 9) {
-            double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    }
+    if constexpr (M::kRefitMask) {
+        __syncthreads();
+        // refit_mask and its count: the used pairs against the refit as it is returned, the same expression
+        double Mr[9];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const double ri = R[9 * j + lane];
-#pragma unroll
-                for (int c = 0; c < 9; ++c) acc[c] += ri * R[9 * j + c];
-            }
-#pragma unroll
-            for (int c = 0; c < 9; ++c) { A[9 * lane + c] = acc[c]; V[9 * lane + c] = c == lane ? 1.0 : 0.0; }
+        for (int k = 0; k < 9; ++k) Mr[k] = sM[k];
+        double c[1] = {0.0};
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+            const bool inl = M::inlier(Mr, qa.x, qa.y, qb.x, qb.y, score);
+            orefit_mask[(size_t)b + k] = inl ? 1 : 0;
+            c[0] += inl ? 1.0 : 0.0;
         }
-        jacobi_lds<9>(A, V, lane);
-        double Hm[9];
-        homog_from_jacobi(A, V, m1x, m1y, s1, m2x, m2y, s2, Hm);
-        int cnt = 0;
-#pragma unroll 1
-        for (int k0 = 0; k0 < n; k0 += 64) {                     // uniform over the wave: the ballot needs every lane
-            const int k = k0 + lane;
-            bool inl = false;
-            if (k < n) { const double2 qa = P2[2 * k], qb = P2[2 * k + 1]; inl = homog_inlier(Hm, qa.x, qa.y, qb.x, qb.y, thr2); }
-            cnt += __popcll(__ballot(inl));
-        }
-        if (lane == 0 && hyp != nullptr) hyp[(size_t)e * (size_t)H + (size_t)h] = cnt;
-        if (cnt > bc) {                                          // (h ascends: the lowest h of equal counts stays)
-            bc = cnt; bh = h;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) bH[k] = Hm[k];
-        }
+        block_sum<1>(c, red);
+        if (first) oi[4] = (int)c[0];
     }
 }
 
-__global__ __launch_bounds__(kTwoViewThreads) void k_homog_ransac(FundIn in, int H, int hs, int n_slices, unsigned long long seed,
-                                                                  double thr2, double* __restrict__ slots, int* __restrict__ hyp) {
-    extern __shared__ __align__(16) double smem[];
-    __shared__ double jA[kTwoViewWaves][81], jV[kTwoViewWaves][81], jR[kTwoViewWaves][72];
-    __shared__ double wbest[kTwoViewWaves][kTwoViewSlot];
-    const int e = blockIdx.x / n_slices, sl = blockIdx.x - e * n_slices;
-    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
-    const int h0 = sl * hs, h1 = min(H, h0 + hs);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    double* __restrict__ slot = slots + (size_t)blockIdx.x * kTwoViewSlot;
-    if (n < 4) {                                                 // (uniform over the workgroup) FEW_PAIRS: no hypothesis
-        if (hyp != nullptr)
-            for (int h = h0 + (int)threadIdx.x; h < h1; h += kTwoViewThreads) hyp[(size_t)e * (size_t)H + (size_t)h] = -1;
-        if (threadIdx.x == 0) {
-            slot[0] = -1.0; slot[1] = 0.0;
-#pragma unroll
-            for (int k = 2; k < kTwoViewSlot; ++k) slot[k] = 0.0;
-        }
-        return;
-    }
-    const double* __restrict__ gp = in.pairs + 4 * (size_t)b;
-    int bc, bh;
-    double bH[9];
-    if (n <= kTwoViewLdsPairs) {
-        stage_table(gp, 4 * n, smem);
-        homog_slice(smem, in, e, n, H, h0, h1, seed, thr2, jA[w], jV[w], jR[w], hyp, bc, bh, bH);
-    } else {
-        homog_slice(gp, in, e, n, H, h0, h1, seed, thr2, jA[w], jV[w], jR[w], hyp, bc, bh, bH);
-    }
-    if (lane == 0) {
-        wbest[w][0] = (double)bc; wbest[w][1] = (double)bh;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) wbest[w][2 + k] = bH[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int best = 0;
-        for (int k = 1; k < kTwoViewWaves; ++k)
-            if (wbest[k][0] > wbest[best][0] || (wbest[k][0] == wbest[best][0] && wbest[k][1] < wbest[best][1])) best = k;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) slot[k] = wbest[best][k];
-        slot[11] = 0.0;
-    }
-}
-
-// fund_ata_rows with both DLT rows of a pair: rows I0 .. I1 - 1 of the upper triangle of A^T A over the pairs of the mask mk
-// (its own stores), thread t taking pairs t, t + 256, ..., a pair's first row before its second; thread 0 stores them (and
-// their mirror) into A
-template <int I0, int I1>
-__device__ __forceinline__ void homog_ata_rows(const double2* __restrict__ P2, int n, const unsigned char* mk, double m1x,
-                                               double m1y, double s1, double m2x, double m2y, double s2, double* red, double* A) {
-    constexpr int NS = sym<9>(I1 - 1, 8) - sym<9>(I0, I0) + 1, Q0 = sym<9>(I0, I0);
-    double s[NS];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) s[q] = 0.0;
-#pragma unroll 1
-    for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
-        const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
-        if (!mk[k]) continue;
-        double r0[9], r1[9];
-        homog_rows((qa.x - m1x) / s1, (qa.y - m1y) / s1, (qb.x - m2x) / s2, (qb.y - m2y) / s2, r0, r1);
-#pragma unroll
-        for (int i = I0; i < I1; ++i)
-#pragma unroll
-            for (int c = i; c < 9; ++c) { s[sym<9>(i, c) - Q0] += r0[i] * r0[c]; s[sym<9>(i, c) - Q0] += r1[i] * r1[c]; }
-    }
-    block_sum<NS>(s, red);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = I0; i < I1; ++i)
-#pragma unroll
-            for (int c = i; c < 9; ++c) { A[9 * i + c] = s[sym<9>(i, c) - Q0]; A[9 * c + i] = s[sym<9>(i, c) - Q0]; }
-    }
-}
-
+// ---- the kernels of the two models (their names and arguments are what the host and the profiles know) ----
+struct FundOut {
+    double* __restrict__ F;                      // [E][9]
+    double* __restrict__ F_refit;                // [E][9]
+    unsigned char* __restrict__ mask;            // [M_used]
+    int* __restrict__ ints;                      // [E][4] inliers, best h, status, success
+};
 struct HomogOut {
     double* __restrict__ Hm;                     // [E][9]
     double* __restrict__ H_refit;                // [E][9]
@@ -1838,153 +1752,22 @@ struct HomogOut {
     int* __restrict__ ints;                      // [E][5] inliers, best h, status, success, refit inliers
 };
 
+__global__ __launch_bounds__(kTwoViewThreads) void k_fund_ransac(FundIn in, int H, int hs, int n_slices, unsigned long long seed,
+                                                                 double thr, double* __restrict__ slots, int* __restrict__ hyp) {
+    twoview_ransac<FundModel>(in.pairs, in.uptr, in.samples, H, hs, n_slices, seed, thr, slots, hyp);
+}
+__global__ __launch_bounds__(kTwoViewThreads) void k_fund_finish(FundIn in, int n_slices, double thr, double confidence, int refit,
+                                                                 const double* __restrict__ slots, FundOut out) {
+    twoview_finish<FundModel>(in.pairs, in.uptr, n_slices, thr, confidence, refit, slots, out.F, out.F_refit, out.mask, nullptr, out.ints);
+}
+__global__ __launch_bounds__(kTwoViewThreads) void k_homog_ransac(FundIn in, int H, int hs, int n_slices, unsigned long long seed,
+                                                                  double thr2, double* __restrict__ slots, int* __restrict__ hyp) {
+    twoview_ransac<HomogModel>(in.pairs, in.uptr, in.samples, H, hs, n_slices, seed, thr2, slots, hyp);
+}
 __global__ __launch_bounds__(kTwoViewThreads) void k_homog_finish(FundIn in, int n_slices, double thr2, double confidence, int refit,
                                                                   const double* __restrict__ slots, HomogOut out) {
-    __shared__ double red[kTwoViewWaves * 18];
-    __shared__ double jA[81], jV[81];
-    __shared__ double sH[9], sm[9];
-    __shared__ int ctl[2];
-    const int e = blockIdx.x;
-    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
-    const bool first = threadIdx.x == 0;
-    const double2* __restrict__ P2 = reinterpret_cast<const double2*>(in.pairs + 4 * (size_t)b);
-    int* __restrict__ oi = out.ints + 5 * (size_t)e;
-    if (first) {
-        const double* __restrict__ sl = slots + (size_t)e * (size_t)n_slices * kTwoViewSlot;
-        int best = 0;
-        for (int k = 1; k < n_slices; ++k)                       // slots ascend in h: the first of equal counts has the lowest
-            if (sl[(size_t)k * kTwoViewSlot] > sl[(size_t)best * kTwoViewSlot]) best = k;
-        const double* __restrict__ bs = sl + (size_t)best * kTwoViewSlot;
-        double sum = 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { sH[k] = bs[2 + k]; sum += fabs(bs[2 + k]); }
-        ctl[0] = n < 4 ? kHomogFewPairs : (sum < INFINITY ? kHomogOk : kHomogDegenerate);
-        ctl[1] = bs[0] >= 0.0 ? (int)bs[1] : -1;                 // (-1: no valid sample in any slot)
-    }
-    __syncthreads();
-    const unsigned char* mk = out.mask + (size_t)b;              // a thread reads back only what it stored itself
-    if (ctl[0] == kHomogFewPairs) {                              // (uniform over the workgroup)
-        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) { out.mask[(size_t)b + k] = 0; out.refit_mask[(size_t)b + k] = 0; }
-        if (threadIdx.x < 9) { out.Hm[9 * (size_t)e + threadIdx.x] = 0.0; out.H_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
-        if (first) { oi[0] = 0; oi[1] = -1; oi[2] = kHomogFewPairs; oi[3] = 0; oi[4] = 0; }
-        return;
-    }
-    // The mask of the best H, and the count FROM that mask, as in k_fund_finish: everything below rests on this one
-    // evaluation.  refit_mask starts as its copy (refit = 0 and DEGENERATE leave it so).
-    double Hb[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Hb[k] = sH[k];
-    {
-        double c[1] = {0.0};
-        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
-            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
-            const bool inl = ctl[1] >= 0 && homog_inlier(Hb, qa.x, qa.y, qb.x, qb.y, thr2);
-            out.mask[(size_t)b + k] = inl ? 1 : 0;
-            out.refit_mask[(size_t)b + k] = inl ? 1 : 0;
-            c[0] += inl ? 1.0 : 0.0;
-        }
-        block_sum<1>(c, red);
-        if (first) {
-            const int cnt = (int)c[0];
-            if (ctl[0] == kHomogOk && cnt < 4) ctl[0] = kHomogDegenerate;
-            sm[8] = (double)cnt;
-            // (DEGENERATE still reports the count, h and mask of its best hypothesis; only H is withheld)
-            oi[0] = cnt; oi[1] = ctl[1]; oi[2] = ctl[0];
-            oi[3] = (ctl[1] >= 0 && (double)cnt / (double)n >= confidence) ? 1 : 0;
-            oi[4] = cnt;
-        }
-        __syncthreads();
-    }
-    const int status = ctl[0], cnt = (int)sm[8];
-    if (status != kHomogOk) {
-        if (threadIdx.x < 9) { out.Hm[9 * (size_t)e + threadIdx.x] = 0.0; out.H_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
-        return;
-    }
-    double Hu[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Hu[k] = Hb[k];
-    fund_unit(Hu);
-    if (first) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) out.Hm[9 * (size_t)e + k] = Hu[k];
-    }
-    if (!refit) {
-        if (first) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) out.H_refit[9 * (size_t)e + k] = Hu[k];
-        }
-        return;
-    }
-    // the same estimate over the cnt >= 4 inliers: thread t takes pairs t, t + 256, ...
-    {
-        double v[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
-            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
-            if (mk[k]) { v[0] += qa.x; v[1] += qa.y; v[2] += qb.x; v[3] += qb.y; }
-        }
-        block_sum<4>(v, red);
-        if (first) {
-            const double c = (double)cnt;
-            sm[0] = v[0] / c; sm[1] = v[1] / c; sm[2] = v[2] / c; sm[3] = v[3] / c;
-            sm[4] = (v[0] + v[1]) / (2.0 * c); sm[5] = (v[2] + v[3]) / (2.0 * c);
-        }
-        __syncthreads();
-    }
-    const double m1x = sm[0], m1y = sm[1], m2x = sm[2], m2y = sm[3];
-    {
-        const double g1 = sm[4], g2 = sm[5];
-        double v[2] = {0.0, 0.0};
-        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
-            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
-            if (mk[k]) {
-                v[0] += (qa.x - g1) * (qa.x - g1) + (qa.y - g1) * (qa.y - g1);
-                v[1] += (qb.x - g2) * (qb.x - g2) + (qb.y - g2) * (qb.y - g2);
-            }
-        }
-        block_sum<2>(v, red);
-        if (first) { sm[6] = sqrt(v[0] / (2.0 * (double)cnt)); sm[7] = sqrt(v[1] / (2.0 * (double)cnt)); }
-        __syncthreads();
-    }
-    const double s1 = sm[6], s2 = sm[7];
-    // the 45 sums in three passes (rows 0-1, 2-4, 5-8 of the upper triangle), as k_fund_finish takes them
-    homog_ata_rows<0, 2>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
-    homog_ata_rows<2, 5>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
-    homog_ata_rows<5, 9>(P2, n, mk, m1x, m1y, s1, m2x, m2y, s2, red, jA);
-    if (first)
-        for (int k = 0; k < 81; ++k) jV[k] = (k % 10) == 0 ? 1.0 : 0.0;
-    if (threadIdx.x < 64) {                                      // wave 0: thread 0's stores above are its own
-        jacobi_lds<9>(jA, jV, (int)threadIdx.x);
-        double Hr[9];
-        homog_from_jacobi(jA, jV, m1x, m1y, s1, m2x, m2y, s2, Hr);
-        fund_unit(Hr);
-        double sum = 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) sum += fabs(Hr[k]);
-        if (first) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                const double v = sum < INFINITY ? Hr[k] : Hu[k];
-                out.H_refit[9 * (size_t)e + k] = v;
-                sH[k] = v;
-            }
-        }
-    }
-    __syncthreads();
-    // refit_mask and its count: the used pairs against H_refit as it is returned, the same expression
-    {
-        double Hr[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Hr[k] = sH[k];
-        double c[1] = {0.0};
-        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
-            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
-            const bool inl = homog_inlier(Hr, qa.x, qa.y, qb.x, qb.y, thr2);
-            out.refit_mask[(size_t)b + k] = inl ? 1 : 0;
-            c[0] += inl ? 1.0 : 0.0;
-        }
-        block_sum<1>(c, red);
-        if (first) oi[4] = (int)c[0];
-    }
+    twoview_finish<HomogModel>(in.pairs, in.uptr, n_slices, thr2, confidence, refit, slots, out.Hm, out.H_refit, out.mask, out.refit_mask,
+                               out.ints);
 }
 
 // ---- sfmba_recover_pose ----
@@ -2221,19 +2004,6 @@ constexpr int kPnpPose = 12;         // R (9, row-major), T (3): x_cam = R (X - 
 constexpr int kPnpSlabDoubles = 4 * kPnpPose * 64;               // a wave's slab: [solution][entry][lane]
 constexpr int kPnpOk = 0, kPnpFewViews = 1, kPnpDegenerate = 2, kPnpNotSelected = -1;
 
-// the counter-based sample rule of twoview_draw with three draws: a function of (seed, c, h) alone
-__device__ __forceinline__ void pnp_draw(unsigned long long seed, unsigned c, unsigned h, int n, int (&idx)[3]) {
-    const unsigned long long key = twoview_mix(seed ^ twoview_mix(((unsigned long long)c << 32) | (unsigned long long)h));
-    int k0 = (int)(twoview_mix(key + 0x9e3779b97f4a7c15ull) % (unsigned long long)n);
-    int k1 = (int)(twoview_mix(key + 2ull * 0x9e3779b97f4a7c15ull) % (unsigned long long)(n - 1));
-    if (k1 >= k0) ++k1;
-    const int lo = min(k0, k1), hi = max(k0, k1);
-    int k2 = (int)(twoview_mix(key + 3ull * 0x9e3779b97f4a7c15ull) % (unsigned long long)(n - 2));
-    if (k2 >= lo) ++k2;
-    if (k2 >= hi) ++k2;
-    idx[0] = k0; idx[1] = k1; idx[2] = k2;
-}
-
 __device__ __forceinline__ void pnp_order(double& a, double& b) {
     if (a > b) { const double t = a; a = b; b = t; }
 }
@@ -2403,15 +2173,7 @@ __device__ __forceinline__ void pnp_slice(const double* __restrict__ go, const P
         int ns = 0, hcount = -1, hsol = -1;
         if (h < h1) {
             int idx[3];
-            bool valid = true;
-            if (in.samples != nullptr) {
-                const int* __restrict__ sp = in.samples + ((size_t)c * (size_t)H + (size_t)h) * 3;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { idx[k] = sp[k]; valid = valid && idx[k] >= 0 && idx[k] < n; }
-                valid = valid && idx[0] != idx[1] && idx[0] != idx[2] && idx[1] != idx[2];
-            } else {
-                pnp_draw(seed, (unsigned)c, (unsigned)h, n, idx);
-            }
+            const bool valid = ransac_sample(in.samples, c, H, h, n, seed, idx);
             if (valid) {
                 double Pw[9], px[6];
 #pragma unroll

@@ -439,6 +439,63 @@ int launch_twoview_ransac(sfmba_handle* h, const TwoViewRansac& c, double score,
     return 0;
 }
 
+// the caller's arrays of a two-view RANSAC call (any may be null): the model and its refit [E][9], the masks [M] (the
+// second: of the refit, a model with two), the per-edge integers in the kernel's order with success as bytes
+struct TwoViewResults {
+    double *M, *M_refit;
+    uint8_t* mask[2];
+    int32_t *inliers, *best, *status;
+    uint8_t* success;
+    int32_t *refit_inliers, *hyp;
+    int64_t* n_ok;
+    double* kernel_us;
+};
+
+// What the two calls do alike after twoview_ransac_begin: the result buffers (twoview.F the model and its refit,
+// twoview.mask n_masks masks, twoview.ints n_ints integers per edge), the RANSAC launch and `finish` (the model's finish
+// kernel on these buffers) between the event pair, the downloads, the masks scattered, the integers handed out.
+template <class Finish>
+int twoview_ransac_end(sfmba_handle* h, const TwoViewRansac& c, double score, size_t n_ints, size_t n_masks, int ok_status,
+                       const TwoViewResults& r, Finish finish) {
+    if (c.E == 0) return wait_stream(h);
+    auto& t = h->twoview;
+    const TwoViewBatch& bt = c.bt;
+    const size_t E = c.E, H = c.H, Mu = bt.Mu;
+    CHK(ensure_all(h, {{&t.F, sizeof(double) * 18 * E}, {&t.ints, sizeof(int) * n_ints * E}, {&t.mask, n_masks * std::max<size_t>(Mu, 1)}}));
+    EventPair timer;
+    CHK(timer.start(h, c.o.profile != 0));
+    CHK(launch_twoview_ransac(h, c, score, r.hyp != nullptr));
+    finish(t.F.as<double>(), t.mask.as<unsigned char>(), t.ints.as<int>(), score);
+    LAUNCHED(h);
+    CHK(timer.stop(h));
+    // the per-edge integers always come (n_ok); the masks through the staging when they have to be scattered
+    const size_t off_mask = sizeof(int) * n_ints * E;
+    HIPCHK(h, t.out_host.ensure(off_mask + n_masks * Mu, 0));
+    int* const hi = t.out_host.as<int>();
+    unsigned char* const hm = t.out_host.as<unsigned char>() + off_mask;
+    HIPCHK(h, hipMemcpyAsync(hi, t.ints.p, sizeof(int) * n_ints * E, hipMemcpyDeviceToHost, h->stream));
+    if ((r.mask[0] || r.mask[1]) && Mu) HIPCHK(h, hipMemcpyAsync(hm, t.mask.p, n_masks * Mu, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, download(h, r.M, t.F.p, sizeof(double) * 9 * E));
+    HIPCHK(h, download(h, r.M_refit, t.F.as<double>() + 9 * E, sizeof(double) * 9 * E));
+    HIPCHK(h, download(h, r.hyp, t.hyp.p, sizeof(int) * E * H));
+    CHK(wait_stream(h));
+    CHK(timer.read(h, r.kernel_us));
+    const uint8_t zero = 0;
+    for (size_t m = 0; m < n_masks; ++m) twoview_scatter(h, bt, hm + m * Mu, r.mask[m], 1, &zero);
+    int64_t ok = 0;
+    for (size_t e = 0; e < E; ++e) {
+        const int* const ei = hi + n_ints * e;
+        if (r.inliers) r.inliers[e] = ei[0];
+        if (r.best) r.best[e] = ei[1];
+        if (r.status) r.status[e] = ei[2];
+        if (r.success) r.success[e] = (uint8_t)ei[3];
+        if (r.refit_inliers) r.refit_inliers[e] = ei[4];
+        ok += ei[2] == ok_status ? 1 : 0;
+    }
+    if (r.n_ok) *r.n_ok = ok;
+    return 0;
+}
+
 // ---- robust resection (sfmba_resect_ransac; kernels: consumer_kernels.hpp, "Robust resection") ----------------------------
 struct PnpCall { int H, hs, n_slices; PnpScore sc; double confidence; unsigned long long seed; };
 
@@ -608,44 +665,12 @@ int sfmba_fundamental_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* ed
     TwoViewRansac c;
     CHK(twoview_ransac_begin(h, "sfmba_fundamental_ransac", k_fund_ransac, 8, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
                              hyp_inliers != nullptr, n_ok, kernel_us, &c));
-    if (c.E == 0) return wait_stream(h);
-    auto& t = h->twoview;
-    const sfmba_ransac_options& o = c.o;
-    const TwoViewBatch& bt = c.bt;
-    const size_t E = c.E, H = c.H;
-    CHK(ensure_all(h, {{&t.F, sizeof(double) * 18 * E}, {&t.ints, sizeof(int) * 4 * E}, {&t.mask, std::max<size_t>(bt.Mu, 1)}}));
-    const FundOut out{t.F.as<double>(), t.F.as<double>() + 9 * E, t.mask.as<unsigned char>(), t.ints.as<int>()};
-    EventPair timer;
-    CHK(timer.start(h, o.profile != 0));
-    CHK(launch_twoview_ransac(h, c, o.threshold, hyp_inliers != nullptr));
-    hipLaunchKernelGGL(k_fund_finish, dim3((unsigned)E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, o.threshold, o.confidence,
-                       o.refit != 0 ? 1 : 0, (const double*)t.slots.as<double>(), out);
-    LAUNCHED(h);
-    CHK(timer.stop(h));
-    // the per-edge integers always come (n_ok); the mask through the staging when it has to be scattered
-    const size_t off_mask = sizeof(int) * 4 * E;
-    HIPCHK(h, t.out_host.ensure(off_mask + bt.Mu, 0));
-    int* const hi = t.out_host.as<int>();
-    unsigned char* const hm = t.out_host.as<unsigned char>() + off_mask;
-    HIPCHK(h, hipMemcpyAsync(hi, t.ints.p, sizeof(int) * 4 * E, hipMemcpyDeviceToHost, h->stream));
-    if (inlier_mask && bt.Mu) HIPCHK(h, hipMemcpyAsync(hm, t.mask.p, bt.Mu, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, download(h, F, t.F.p, sizeof(double) * 9 * E));
-    HIPCHK(h, download(h, F_refit, t.F.as<double>() + 9 * E, sizeof(double) * 9 * E));
-    HIPCHK(h, download(h, hyp_inliers, t.hyp.p, sizeof(int) * E * H));
-    CHK(wait_stream(h));
-    CHK(timer.read(h, kernel_us));
-    const uint8_t zero = 0;
-    twoview_scatter(h, bt, hm, inlier_mask, 1, &zero);
-    int64_t ok = 0;
-    for (size_t e = 0; e < E; ++e) {
-        if (edge_inliers) edge_inliers[e] = hi[4 * e];
-        if (edge_best) edge_best[e] = hi[4 * e + 1];
-        if (edge_status) edge_status[e] = hi[4 * e + 2];
-        if (edge_success) edge_success[e] = (uint8_t)hi[4 * e + 3];
-        ok += hi[4 * e + 2] == kFundOk ? 1 : 0;
-    }
-    if (n_ok) *n_ok = ok;
-    return 0;
+    const TwoViewResults r{F, F_refit, {inlier_mask, nullptr}, edge_inliers, edge_best, edge_status, edge_success, nullptr, hyp_inliers,
+                           n_ok, kernel_us};
+    return twoview_ransac_end(h, c, c.o.threshold, 4, 1, kFundOk, r, [&](double* M, unsigned char* mask, int* ints, double score) {
+        hipLaunchKernelGGL(k_fund_finish, dim3((unsigned)c.E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, score, c.o.confidence,
+                           c.o.refit != 0 ? 1 : 0, (const double*)h->twoview.slots.as<double>(), FundOut{M, M + 9 * c.E, mask, ints});
+    });
 }
 
 // The F call with k_homog_ransac / k_homog_finish and samples of four positions: twoview.F holds H and H_refit, twoview.mask
@@ -659,48 +684,13 @@ int sfmba_homography_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edg
     TwoViewRansac c;
     CHK(twoview_ransac_begin(h, "sfmba_homography_ransac", k_homog_ransac, 4, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
                              hyp_inliers != nullptr, n_ok, kernel_us, &c));
-    if (c.E == 0) return wait_stream(h);
-    auto& t = h->twoview;
-    const sfmba_ransac_options& o = c.o;
-    const TwoViewBatch& bt = c.bt;
-    const size_t E = c.E, H = c.H, Mu = bt.Mu;
-    CHK(ensure_all(h, {{&t.F, sizeof(double) * 18 * E}, {&t.ints, sizeof(int) * 5 * E}, {&t.mask, 2 * std::max<size_t>(Mu, 1)}}));
-    const HomogOut out{t.F.as<double>(), t.F.as<double>() + 9 * E, t.mask.as<unsigned char>(), t.mask.as<unsigned char>() + Mu,
-                       t.ints.as<int>()};
-    const double thr2 = o.threshold * o.threshold;
-    EventPair timer;
-    CHK(timer.start(h, o.profile != 0));
-    CHK(launch_twoview_ransac(h, c, thr2, hyp_inliers != nullptr));
-    hipLaunchKernelGGL(k_homog_finish, dim3((unsigned)E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, thr2, o.confidence,
-                       o.refit != 0 ? 1 : 0, (const double*)t.slots.as<double>(), out);
-    LAUNCHED(h);
-    CHK(timer.stop(h));
-    // the per-edge integers always come (n_ok); the masks through the staging when they have to be scattered
-    const size_t off_mask = sizeof(int) * 5 * E;
-    HIPCHK(h, t.out_host.ensure(off_mask + 2 * Mu, 0));
-    int* const hi = t.out_host.as<int>();
-    unsigned char* const hm = t.out_host.as<unsigned char>() + off_mask;
-    HIPCHK(h, hipMemcpyAsync(hi, t.ints.p, sizeof(int) * 5 * E, hipMemcpyDeviceToHost, h->stream));
-    if ((inlier_mask || refit_mask) && Mu) HIPCHK(h, hipMemcpyAsync(hm, t.mask.p, 2 * Mu, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, download(h, Hm, t.F.p, sizeof(double) * 9 * E));
-    HIPCHK(h, download(h, H_refit, t.F.as<double>() + 9 * E, sizeof(double) * 9 * E));
-    HIPCHK(h, download(h, hyp_inliers, t.hyp.p, sizeof(int) * E * H));
-    CHK(wait_stream(h));
-    CHK(timer.read(h, kernel_us));
-    const uint8_t zero = 0;
-    twoview_scatter(h, bt, hm, inlier_mask, 1, &zero);
-    twoview_scatter(h, bt, hm + Mu, refit_mask, 1, &zero);
-    int64_t ok = 0;
-    for (size_t e = 0; e < E; ++e) {
-        if (edge_inliers) edge_inliers[e] = hi[5 * e];
-        if (edge_best) edge_best[e] = hi[5 * e + 1];
-        if (edge_status) edge_status[e] = hi[5 * e + 2];
-        if (edge_success) edge_success[e] = (uint8_t)hi[5 * e + 3];
-        if (edge_refit_inliers) edge_refit_inliers[e] = hi[5 * e + 4];
-        ok += hi[5 * e + 2] == kHomogOk ? 1 : 0;
-    }
-    if (n_ok) *n_ok = ok;
-    return 0;
+    const TwoViewResults r{Hm, H_refit, {inlier_mask, refit_mask}, edge_inliers, edge_best, edge_status, edge_success, edge_refit_inliers,
+                           hyp_inliers, n_ok, kernel_us};
+    return twoview_ransac_end(h, c, c.o.threshold * c.o.threshold, 5, 2, kHomogOk, r, [&](double* M, unsigned char* mask, int* ints, double score) {
+        hipLaunchKernelGGL(k_homog_finish, dim3((unsigned)c.E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, score, c.o.confidence,
+                           c.o.refit != 0 ? 1 : 0, (const double*)h->twoview.slots.as<double>(),
+                           HomogOut{M, M + 9 * c.E, mask, mask + c.bt.Mu, ints});
+    });
 }
 
 void sfmba_default_pose_options(sfmba_pose_options* o) {

@@ -392,15 +392,48 @@ def _edge_batch(pts1, pts2, edge_ptr, pair_use):
     return pts1, pts2, edge_ptr, _mask(pair_use, M, "pair_use")
 
 
-def _homography_samples(samples, n_edges):
-    """The caller's sample sets of `Backend.homography_ransac`, checked: (n_edges, H, 4) integers with H >= 1 -> int32,
-    C-contiguous; None stays None."""
-    if samples is None:
-        return None
-    samples = np.asarray(samples)
-    if samples.dtype.kind not in "iu" or samples.ndim != 3 or samples.shape[0] != n_edges or samples.shape[2] != 4 or samples.shape[1] < 1:
-        raise ValueError(f"samples must be (n_edges, H, 4) int32 with n_edges = {n_edges}, got {samples.dtype} {samples.shape}")
-    return np.ascontiguousarray(samples, dtype=np.int32)
+def _ransac_prologue(opt, options, samples, batch, S, batch_name, item, what, then_flush=None):
+    """The keyword options and the caller's sample sets of a RANSAC call, checked: the options into ``opt`` (a ctypes
+    structure holding the defaults; ``what`` names the call in an error text) -> the samples as (batch, H, S) int32,
+    C-contiguous, None staying None.  ``seed`` must fit 64 unsigned bits; with samples given ``max_iters`` defaults to
+    their H and must equal it.  The samples are converted to int32 and (H, S) stands for a batch of one, checked after the
+    seed; with ``then_flush`` (`Backend.homography_ransac`) they must come as three axes of an integer type and are
+    checked first, and ``then_flush()`` runs before any other check."""
+    strict = then_flush is not None
+
+    def shaped(s):
+        if s is None:
+            return None
+        if strict:
+            s = np.asarray(s)
+            right, kind, got = s.dtype.kind in "iu" and s.ndim == 3, " int32", f"{s.dtype} {s.shape}"
+        else:
+            s = np.ascontiguousarray(s, dtype=np.int32)
+            s = s[None] if s.ndim == 2 else s
+            right, kind, got = s.ndim == 3, "", f"{s.shape}"
+        if not right or s.shape[0] != batch or s.shape[2] != S or s.shape[1] < 1:
+            raise ValueError(f"samples must be ({batch_name}, H, {S}){kind} with {batch_name} = {batch}, got {got}")
+        return np.ascontiguousarray(s, dtype=np.int32)
+
+    if strict:
+        samples = shaped(samples)
+        then_flush()
+    options = dict(options)
+    if "seed" in options:
+        seed = int(options.pop("seed"))
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must fit 64 unsigned bits")
+        opt.seed = seed
+    if not strict:
+        samples = shaped(samples)
+    if samples is not None:
+        options.setdefault("max_iters", samples.shape[1])
+    _fill_options(opt, options, what)
+    if opt.max_iters < 1:
+        raise ValueError("max_iters must be at least 1")
+    if samples is not None and samples.shape[1] != opt.max_iters:
+        raise ValueError(f"samples holds {samples.shape[1]} hypotheses per {item}, max_iters is {opt.max_iters}")
+    return samples
 
 
 def _opt_ptr(a):
@@ -865,25 +898,8 @@ class Backend:
         x = _f64(x, (self.n_params,), "x")
         opt = _capi.PnpRansacOptions()
         self._lib.sfmba_default_pnp_ransac_options(C.byref(opt))
-        options = dict(options)
-        if "seed" in options:
-            seed = int(options.pop("seed"))
-            if not 0 <= seed < 2 ** 64:
-                raise ValueError("seed must fit 64 unsigned bits")
-            opt.seed = seed
         Cn, N = self.n_cameras, self.n_obs
-        if samples is not None:
-            samples = np.ascontiguousarray(samples, dtype=np.int32)
-            if samples.ndim == 2:
-                samples = samples[None]
-            if samples.ndim != 3 or samples.shape[0] != Cn or samples.shape[2] != 3 or samples.shape[1] < 1:
-                raise ValueError(f"samples must be (n_cameras, H, 3) with n_cameras = {Cn}, got {samples.shape}")
-            options.setdefault("max_iters", samples.shape[1])
-        _fill_options(opt, options, "robust resection")
-        if opt.max_iters < 1:
-            raise ValueError("max_iters must be at least 1")
-        if samples is not None and samples.shape[1] != opt.max_iters:
-            raise ValueError(f"samples holds {samples.shape[1]} hypotheses per camera, max_iters is {opt.max_iters}")
+        samples = _ransac_prologue(opt, options, samples, Cn, 3, "n_cameras", "camera", "robust resection")
         H = int(opt.max_iters)
         sel, use = _mask(select, Cn, "select"), _mask(obs_use, N, "obs_use")
         cameras, hyp_pose = np.empty((Cn, 6)), np.empty((Cn, 6))
@@ -913,24 +929,7 @@ class Backend:
         E, M = edge_ptr.shape[0] - 1, pts1.shape[0]
         opt = _capi.RansacOptions()
         self._lib.sfmba_default_ransac_options(C.byref(opt))
-        options = dict(options)
-        if "seed" in options:
-            seed = int(options.pop("seed"))
-            if not 0 <= seed < 2 ** 64:
-                raise ValueError("seed must fit 64 unsigned bits")
-            opt.seed = seed
-        if samples is not None:
-            samples = np.ascontiguousarray(samples, dtype=np.int32)
-            if samples.ndim == 2:
-                samples = samples[None]
-            if samples.ndim != 3 or samples.shape[0] != E or samples.shape[2] != 8 or samples.shape[1] < 1:
-                raise ValueError(f"samples must be (n_edges, H, 8) with n_edges = {E}, got {samples.shape}")
-            options.setdefault("max_iters", samples.shape[1])
-        _fill_options(opt, options, "RANSAC")
-        if opt.max_iters < 1:
-            raise ValueError("max_iters must be at least 1")
-        if samples is not None and samples.shape[1] != opt.max_iters:
-            raise ValueError(f"samples holds {samples.shape[1]} hypotheses per edge, max_iters is {opt.max_iters}")
+        samples = _ransac_prologue(opt, options, samples, E, 8, "n_edges", "edge", "RANSAC")
         H = int(opt.max_iters)
         F, Fr = np.empty((E, 3, 3)), np.empty((E, 3, 3))
         mask = np.empty(M, dtype=np.uint8)
@@ -953,23 +952,9 @@ class Backend:
         ``want_hyp``: also return the count of every hypothesis.  Needs no problem.  -> :class:`HomographyEstimate`."""
         pts1, pts2, edge_ptr, use = _edge_batch(pts1, pts2, edge_ptr, pair_use)
         E, M = edge_ptr.shape[0] - 1, pts1.shape[0]
-        samples = _homography_samples(samples, E)
-        self._flush_pending()
         opt = _capi.RansacOptions()
         self._lib.sfmba_default_ransac_options(C.byref(opt))
-        options = dict(options)
-        if "seed" in options:
-            seed = int(options.pop("seed"))
-            if not 0 <= seed < 2 ** 64:
-                raise ValueError("seed must fit 64 unsigned bits")
-            opt.seed = seed
-        if samples is not None:
-            options.setdefault("max_iters", samples.shape[1])
-        _fill_options(opt, options, "RANSAC")
-        if opt.max_iters < 1:
-            raise ValueError("max_iters must be at least 1")
-        if samples is not None and samples.shape[1] != opt.max_iters:
-            raise ValueError(f"samples holds {samples.shape[1]} hypotheses per edge, max_iters is {opt.max_iters}")
+        samples = _ransac_prologue(opt, options, samples, E, 4, "n_edges", "edge", "RANSAC", then_flush=self._flush_pending)
         H = int(opt.max_iters)
         Hm, Hr = np.empty((E, 3, 3)), np.empty((E, 3, 3))
         mask, rmask = np.empty(M, dtype=np.uint8), np.empty(M, dtype=np.uint8)

@@ -1,5 +1,5 @@
-"""Bit identity of the consumers (reprojection statistics, triangulation, resection, and the two-view calls and the robust
-resection where both builds have them) between two builds of the library.  Usage: python tools/ab_consumer_bits.py LIB_A LIB_B [--out DIR]
+"""Bit identity of the consumers (reprojection statistics, triangulation, resection, and the two-view calls -- F, homography,
+pose -- and the robust resection where both builds have them) between two builds of the library.  Usage: python tools/ab_consumer_bits.py LIB_A LIB_B [--out DIR]
 
 One fresh child process per library (SFMBA_LIB), each under its own time limit; the tool stops at the first child that
 does not exit cleanly.  A child runs the three calls over inputs that reach every form of the kernels -- the long-run,
@@ -89,7 +89,14 @@ def child(out_path):
             est = be.fundamental_ransac(p1, p2, edge_ptr=ptr, threshold=1.0, refit=1, want_hyp=True, **kw)
             for f in ("F", "F_refit", "inlier_mask", "inliers", "best", "success", "status", "hyp_inliers"):
                 out[f"two_view/64/ransac/{tag}/{f}"] = getattr(est, f)
-        Es = np.stack([tv.essential_from_pose(m[2], m[3]) for m in made])
+        if hasattr(be._lib, "sfmba_homography_ransac"):   # the same batch and options through the homography model
+            import homography_ref as hr
+            smp4 = np.stack([hr.draw_samples4(3, e, 40, int(ptr[e + 1] - ptr[e])) for e in range(len(made))])
+            for tag, kw in (("drawn", dict(max_iters=40, seed=3)), ("masked", dict(max_iters=40, seed=3, pair_use=use)), ("given", dict(samples=smp4))):
+                est = be.homography_ransac(p1, p2, edge_ptr=ptr, threshold=1.0, refit=1, want_hyp=True, **kw)
+                for f in ("H", "H_refit", "inlier_mask", "refit_mask", "inliers", "refit_inliers", "best", "success", "status", "hyp_inliers"):
+                    out[f"two_view/64/homography/{tag}/{f}"] = getattr(est, f)
+        Es =np.stack([tv.essential_from_pose(m[2], m[3]) for m in made])
         Es[1] = 0.0
         for tag, kw in (("all", {}), ("masked", dict(pair_use=use)), ("deep", dict(min_depth=6.0))):
             pose = be.recover_pose(Es, p1, p2, K, edge_ptr=ptr, **kw)
