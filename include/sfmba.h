@@ -573,6 +573,69 @@ int  sfmba_homography_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* ed
                              const sfmba_ransac_options* opt, double* Hm, double* H_refit, uint8_t* inlier_mask,
                              uint8_t* refit_mask, int32_t* edge_inliers, int32_t* edge_refit_inliers, int32_t* edge_best,
                              uint8_t* edge_success, int32_t* edge_status, int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us);
+/* sfmba_essential_ransac: the essential matrix x2^T E x1 = 0 (x in camera coordinates) by five-point RANSAC for every edge,
+ * H = max_iters hypotheses each, without early exit: the calibrated sibling of sfmba_fundamental_ransac (what
+ * cv2.findEssentialMat(pts1, pts2, K, cv2.RANSAC) estimates).  The batch (n_edges, edge_ptr, pts1, pts2, pair_use, "used
+ * pairs") and sfmba_ransac_options are those of the F call; K (9, row-major) is ONE camera matrix for the whole batch and
+ * both images.  A batch with a mask gives bit for bit what the batch with those pairs removed gives; edge e of a batch
+ * gives what the one-edge batch gives.  No atomics, sums in a fixed order: same input, same bits.  Buffers are shared
+ * with the F and H calls and grow only; no call changes what another, or a following solve, computes.
+ *   hypothesis  five used pairs.  A pixel (x, y) goes to camera coordinates by q = K^-1 (x, y, 1), (q0/q2, q1/q2) (K^-1 in
+ *               closed form by cofactors); nothing else is normalised.  A pair gives the row of construct_matrix_A of the
+ *               F call, [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1], of the 5 x 9 matrix A.  The eigenvectors of the
+ *               four smallest eigenvalues of A^T A (the cyclic Jacobi of the F call, the same order of pairs and the same
+ *               caps), by ascending eigenvalue, the lower column first among equals, are X, Y, Z, W (3 x 3 row-major), and
+ *               E = x X + y Y + z Z + W.  A sample whose rows have no rank 5 -- the fifth-smallest eigenvalue is not above
+ *               1e-12 times the largest, as for five collinear points -- has no candidate: 0 roots, count 0.
+ *   constraints det E = 0 and the nine entries (row-major) of 2 E E^T E - tr(E E^T) E = 0: ten cubics in x, y, z, written
+ *               as a 10 x 20 matrix over the monomials in Nister's order
+ *                 x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1
+ *               Gauss-Jordan elimination with partial pivoting (the first row of equal magnitudes) makes the left 10 x 10
+ *               block the identity.  With <m> the reduced row of monomial m, the three differences <x^2z> - z <x^2>,
+ *               <y^2z> - z <y^2>, <xyz> - z <xy> hold only x, y and 1 times polynomials in z: B(z) (x, y, 1)^T = 0, B 3 x 3
+ *               with columns of degree 3, 3, 4.  det B(z) has degree 10.
+ *   roots       EVERY real root z of det B(z): a zero leading coefficient lowers the degree; the roots of the derivatives
+ *               of every order, found from the highest down, cut the interval of the Cauchy bound 1 + max |c_k / c_n| into
+ *               stretches on which the next polynomial is monotonic; a sign change over a stretch is one root, found by
+ *               Newton steps inside a bracket that is bisected when a step leaves it or shrinks by less than half (at most
+ *               100 steps).  A simple real root is never missed.  A non-finite coefficient: no root.
+ *   candidates  one per root, by ascending z (0 to 10): (x, y, 1) is the null vector of B(z), the cross product of the two
+ *               rows of B(z) whose product is the longest (rows 0 1, then 0 2, then 1 2 among equals) divided by its last
+ *               entry; E = x X + y Y + z Z + W; F_pix = K^-T E K^-1.
+ *   score       the F call's, applied to F_pix: |x2^T F x1| / sqrt(l0^2 + l1^2) with l = F x1, in pixels, one-sided in image
+ *               2, STRICTLY below threshold; a non-finite distance is no inlier.  Counts are comparable with the F and H
+ *               calls'.  The count of a hypothesis is its best candidate's, the lower z among equals; a hypothesis with no
+ *               real root or no finite candidate counts 0.
+ *   best        the largest count, the lowest h among equals
+ *   samples     given: (n_edges, H, 5) int32 positions among the used pairs; a position outside 0 .. n-1 makes the call
+ *               return -1, a sample with a repeated position is invalid: its count is -1.  NULL: drawn by the counter-based
+ *               rule of the F call with five draws.
+ *   polish      the best candidate of the best hypothesis once more, in homogeneous coordinates: v = its parts along X, Y, Z,
+ *               W at unit length; two Gauss-Newton steps on the ten cubics c(v) = 0 with the step kept orthogonal to v,
+ *               (J^T J + v v^T) d = -J^T c, v <- (v + d) / |v + d|; E = v0 X + v1 Y + v2 Z + v3 W and its F_pix.  (The four
+ *               null vectors share one eigenvalue, so their basis is whatever the eigensolver returns, and the chart W = 1
+ *               loses digits when the solution has a small W part in it.)  A step that is not finite leaves the candidate.
+ *   finish      inlier_mask and edge_inliers are evaluated once more from the bits of the polished F_pix; hyp_inliers
+ *               holds the counts before the polish.
+ * E (n_edges,9): the best candidate's E with unit Frobenius norm and its entry of largest magnitude (the first of equals)
+ * positive -- [t]x R has two largest entries of nearly equal magnitude, so compare E up to sign.  inlier_mask (M): 0 for pairs
+ * that took no part.  edge_inliers, edge_best, edge_best_root: count, h and candidate number (by ascending z) of the best
+ * hypothesis.  edge_success: inliers / n >= confidence.  edge_status: 0 OK; 1 FEW_PAIRS (n < 5): count 0, best -1, root -1, empty
+ * mask; 2 DEGENERATE (no hypothesis with a finite E and at least 5 inliers): E is zero, the count, h, root and mask of the best
+ * hypothesis are still reported (-1, -1 and an empty mask when no sample was valid; root -1 when it had no real root).
+ * hyp_inliers, hyp_roots (n_edges,H): the count and the number of real roots of every hypothesis (-1: invalid sample, or
+ * FEW_PAIRS).  n_ok: edges with status 0.  kernel_us: with profile = 1 the HIP-event time of the call's launches, else 0.
+ * Every output pointer may be NULL.
+ * Returns -1 for a malformed batch, a NaN option, max_iters < 1, a sample position outside 0 .. n-1, a NULL, non-finite or
+ * singular K, and opt->refit != 0.
+ * Not done here: a refit or local optimisation over the inliers (a linear eight-point refit would bring the planar
+ * degeneracy back), adaptive exit, different intrinsics for the two images, cv2's Sampson score, making a planar first
+ * pair usable (all points in one plane leave a two-fold ambiguity). */
+int  sfmba_essential_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edge_ptr, const double* pts1, const double* pts2,
+                            const uint8_t* pair_use /* M or NULL = all */, const int32_t* samples /* (n_edges,H,5) or NULL = drawn */,
+                            const double* K, const sfmba_ransac_options* opt, double* E, uint8_t* inlier_mask,
+                            int32_t* edge_inliers, int32_t* edge_best, int32_t* edge_best_root, uint8_t* edge_success,
+                            int32_t* edge_status, int32_t* hyp_inliers, int32_t* hyp_roots, int64_t* n_ok, double* kernel_us);
 typedef struct sfmba_pose_options {
     double  min_depth;   /* a pair is in front when both depths are above this (0.0) */
     int32_t profile;     /* 1 = kernel_us is measured (0) */

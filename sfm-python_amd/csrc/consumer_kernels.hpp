@@ -1770,6 +1770,555 @@ __global__ __launch_bounds__(kTwoViewThreads) void k_homog_finish(FundIn in, int
                                out.ints);
 }
 
+// ---- sfmba_essential_ransac (include/sfmba.h): the calibrated model, five pairs a sample ----
+// k_ess_ransac   the grid, slots and wave-per-hypothesis loop of twoview_ransac.  A hypothesis: five pairs in camera
+//                coordinates (K^-1), A^T A of their FundModel::rows, jacobi_lds<9>, the four eigenvectors of the smallest
+//                eigenvalues X Y Z W; the ten cubic constraints on E = xX + yY + zZ + W, one coefficient per lane and round
+//                (200 of them); Gauss-Jordan with partial pivoting, one entry per lane and round; B(z), its cofactor
+//                polynomials and det B(z) by lanes over the coefficients; every real root of det B(z) by the tower of its
+//                derivatives (ess_real_roots), an interval per lane; a candidate (E, F_pix) per lane; then ONE pass over
+//                the edge's pairs: a lane loads a pair and tests it against every candidate.
+// k_ess_finish   one workgroup per edge: best slot, the mask and count from its F_pix, status, E by fund_unit.
+// Everything a wave indexes at run time is in its table of kEssWaveDoubles doubles of LDS (the map below): no scratch.
+constexpr int kEssS = 5;                  // pairs of a sample, and the fewest inliers of an estimate
+constexpr int kEssSlot = 24;              // doubles of a slot: count, h, root, F_pix (9), E (9), unused (3)
+constexpr int kEssMaxRoots = 10;
+constexpr int kEssRootIters = 100;        // cap of the safeguarded Newton steps of one root (a bisection at the worst: 2^-100)
+constexpr double kEssRankTol = 1e-12;     // a sample's A^T A has rank 5 when its fifth-smallest eigenvalue is above this times the largest
+constexpr int kEssOk = 0, kEssFewPairs = 1, kEssDegenerate = 2;
+// a wave's table, in doubles
+constexpr int kEssOffA = 0;               // [9][9] A^T A, its diagonal the eigenvalues after jacobi_lds
+constexpr int kEssOffV = 81;              // [9][9] eigenvectors in columns
+constexpr int kEssOffR = 162;             // [5][9] rows of the sample
+constexpr int kEssOffB = 207;             // [4][9] X Y Z W
+constexpr int kEssOffSys = 243;           // [10][20] the constraints in Nister's monomial order
+constexpr int kEssOffBz = 443;            // [3][3][5] B(z), ascending powers
+constexpr int kEssOffP = 488;             // [3][8] the cofactor polynomials of rows 0 and 1
+constexpr int kEssOffC = 512;             // [11] det B(z), ascending powers
+constexpr int kEssOffG = 523;             // [11] the derivative of the current level
+constexpr int kEssOffRoots = 534;         // [2][10] roots of the previous and of the current level
+constexpr int kEssOffF = 554;             // [10][9] F_pix of the candidates
+constexpr int kEssOffE = 644;             // [10][9] E of the candidates
+constexpr int kEssOffM = 736;             // [10][20] the constraints as they were before the elimination (ess_polish)
+constexpr int kEssWaveDoubles = 936;
+constexpr int kEssPolishSteps = 2;
+static_assert(kEssOffE + 9 * kEssMaxRoots <= kEssOffM && kEssOffM + 200 <= kEssWaveDoubles, "a wave's table holds its candidates");
+static_assert(sizeof(double) * (4 * kTwoViewLdsPairs + kTwoViewWaves * (kEssWaveDoubles + kEssSlot)) <= 160 * 1024,
+              "staged pairs and the waves' tables must fit the LDS of a CU");
+
+// Nister's order x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1 as triples a <= b <= c of
+// variable numbers (x y z 1 = 0 1 2 3), six bits a monomial, ten monomials a word
+constexpr unsigned long long ess_mono_word(int first) {
+    constexpr int mono[20][3] = {{0, 0, 0}, {1, 1, 1}, {0, 0, 1}, {0, 1, 1}, {0, 0, 2}, {0, 0, 3}, {1, 1, 2}, {1, 1, 3}, {0, 1, 2}, {0, 1, 3},
+                                 {0, 2, 2}, {0, 2, 3}, {0, 3, 3}, {1, 2, 2}, {1, 2, 3}, {1, 3, 3}, {2, 2, 2}, {2, 2, 3}, {2, 3, 3}, {3, 3, 3}};
+    unsigned long long v = 0;
+    for (int m = 0; m < 10; ++m)
+        v |= (unsigned long long)(mono[first + m][0] | (mono[first + m][1] << 2) | (mono[first + m][2] << 4)) << (6 * m);
+    return v;
+}
+constexpr unsigned long long kEssMonoLo = ess_mono_word(0), kEssMonoHi = ess_mono_word(10);
+
+// (the waves' tables through pointers that say LDS: a volatile access through a generic pointer is a flat one with a 64-bit
+// address of its own, and this code has hundreds)
+typedef __attribute__((address_space(3))) volatile double EssLds;
+
+// the trilinear forms of the constraints: det(P row 0, Q row 1, R row 2), and entry (i, j) of 2 P Q^T R - tr(P Q^T) R
+__device__ __forceinline__ double ess_det3(const EssLds* P, const EssLds* Q, const EssLds* R) {
+    return P[0] * (Q[4] * R[8] - Q[5] * R[7]) - P[1] * (Q[3] * R[8] - Q[5] * R[6]) + P[2] * (Q[3] * R[7] - Q[4] * R[6]);
+}
+__device__ __forceinline__ double ess_trace3(const EssLds* P, const EssLds* Q, const EssLds* R, int i, int j) {
+    double acc = 0.0, tr = 0.0;
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {
+        const double s = P[3 * i] * Q[3 * l] + P[3 * i + 1] * Q[3 * l + 1] + P[3 * i + 2] * Q[3 * l + 2];
+        acc += s * R[3 * l + j];
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) tr += P[k] * Q[k];
+    return 2.0 * acc - tr * R[3 * i + j];
+}
+
+// p(x) and p'(x) of the polynomial g of degree L (ascending powers, LDS)
+__device__ __forceinline__ void ess_horner(const EssLds* g, int L, double x, double& p, double& dp) {
+    p = g[L]; dp = 0.0;
+#pragma unroll 1
+    for (int j = L - 1; j >= 0; --j) { dp = dp * x + p; p = p * x + g[j]; }
+}
+
+// Every real root of c (degree <= 10, ascending powers, in T + kEssOffC) by ONE wave, ascending, into T + kEssOffRoots
+// + 10 * half (half = n & 1); -> their number.  The tower of derivatives: level L = 1 .. n takes g = c^(n - L) / (n - L)!, of degree L;
+// the roots of level L - 1 are its critical points and cut [-R, R] (R the Cauchy bound of c, which holds every root of
+// every derivative) into at most L intervals, on each of which g is monotonic: lane i takes interval i, and a sign change
+// is one root, found by Newton steps that a bisection safeguards.  A simple real root is never missed: it lies alone between
+// two critical points and changes the sign there.  A critical point that is a root itself (a double root) counts once.
+__device__ __forceinline__ int ess_real_roots(EssLds* T, int lane, int& half) {
+    const EssLds* c = T + kEssOffC;
+    EssLds* g = T + kEssOffG;
+    int n = -1;
+    double sum = 0.0;
+#pragma unroll
+    for (int k = 0; k <= 10; ++k) { const double v = c[k]; sum += fabs(v); if (v != 0.0) n = k; }
+    half = n & 1;
+    if (!(sum < INFINITY) || n < 1) return 0;                   // (uniform over the wave)
+    const double cn = c[n];
+    double R = 0.0;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) { const double q = fabs(c[k] / cn); if (k < n && q > R) R = q; }
+    R = fmin(1.0 + R, 1e150);
+    int m = 0;
+#pragma unroll 1
+    for (int L = 1; L <= n; ++L) {
+        const int k = n - L;
+        const EssLds* prev = T + kEssOffRoots + 10 * ((L - 1) & 1);
+        EssLds* next = T + kEssOffRoots + 10 * (L & 1);
+        if (lane <= L) {                                         // g_j = c_(j + k) binom(j + k, k): exact integers
+            double b = 1.0;
+            for (int i = 1; i <= k; ++i) b = b * (double)(lane + i) / (double)i;
+            g[lane] = c[lane + k] * b;
+        }
+        bool found = false;
+        double root = 0.0;
+        if (lane <= m) {
+            double a = lane == 0 ? -R : prev[lane - 1], bb = lane == m ? R : prev[lane];
+            double fa, fb, d;
+            ess_horner(g, L, a, fa, d);
+            ess_horner(g, L, bb, fb, d);
+            if (fa == 0.0) { found = true; root = a; }           // (its left neighbour leaves it to this interval)
+            else if (fb != 0.0 && ((fa < 0.0) != (fb < 0.0)) && fa == fa && fb == fb) {
+                const bool neg_a = fa < 0.0;
+                double x = 0.5 * a + 0.5 * bb, dxo = bb - a;
+                found = true;
+#pragma unroll 1
+                for (int it = 0; it < kEssRootIters; ++it) {
+                    double p, dp;
+                    ess_horner(g, L, x, p, dp);
+                    if (p == 0.0) break;
+                    if ((p < 0.0) == neg_a) a = x; else bb = x;
+                    double dx = p / dp, xn = x - dx;
+                    if (!(xn > a && xn < bb) || !(fabs(2.0 * dx) < fabs(dxo))) { xn = 0.5 * a + 0.5 * bb; dx = x - xn; }
+                    dxo = dx;
+                    if (!(xn > a && xn < bb) || xn == x) break;  // the bracket is two neighbouring doubles, or the step is nothing
+                    x = xn;
+                }
+                root = x;
+            }
+        }
+        const unsigned long long have = __ballot(found);
+        if (found) next[__popcll(have & ((1ull << lane) - 1ull))] = root;
+        m = __popcll(have);
+    }
+    return m;
+}
+
+// The candidate Ec of the wave's table once more, in homogeneous coordinates: v = (<X, Ec>, <Y, Ec>, <Z, Ec>, <W, Ec>) of unit
+// length, kEssPolishSteps Gauss-Newton steps on the ten cubics c(v) = 0 with the step kept orthogonal to v,
+// (J^T J + v v^T) d = -J^T c, v <- (v + d) / |v + d|; E = v0 X + v1 Y + v2 Z + v3 W.  The chart w = 1 loses digits when the
+// solution has a small W part in the basis that the eigensolver happened to return; this form does not.  The same on every
+// lane (everything it reads is the wave's own).
+__device__ __forceinline__ void ess_polish(const EssLds* T, const EssLds* Ec, double (&Em)[9]) {
+    const EssLds* Bs = T + kEssOffB;
+    const EssLds* M0 = T + kEssOffM;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { const double ei = Ec[i]; v0 += Bs[i] * ei; v1 += Bs[9 + i] * ei; v2 += Bs[18 + i] * ei; v3 += Bs[27 + i] * ei; }
+    {
+        const double nv = sqrt(v0 * v0 + v1 * v1 + v2 * v2 + v3 * v3);
+        v0 /= nv; v1 /= nv; v2 /= nv; v3 /= nv;
+    }
+#pragma unroll 1
+    for (int step = 0; step < kEssPolishSteps; ++step) {
+        // the normal equations, upper triangle a[i][j], and the right-hand side a[i][4]
+        double a[4][5] = {{v0 * v0, v0 * v1, v0 * v2, v0 * v3, 0.0}, {0.0, v1 * v1, v1 * v2, v1 * v3, 0.0},
+                          {0.0, 0.0, v2 * v2, v2 * v3, 0.0}, {0.0, 0.0, 0.0, v3 * v3, 0.0}};
+#pragma unroll 1
+        for (int q = 0; q < 10; ++q) {
+            double c = 0.0, j0 = 0.0, j1 = 0.0, j2 = 0.0, j3 = 0.0;
+#pragma unroll 1
+            for (int m = 0; m < 20; ++m) {
+                const int code = (int)((m < 10 ? kEssMonoLo >> (6 * m) : kEssMonoHi >> (6 * (m - 10))) & 63ull);
+                const int ia = code & 3, ib = (code >> 2) & 3, ic = code >> 4;
+                const double xa = ia == 0 ? v0 : (ia == 1 ? v1 : (ia == 2 ? v2 : v3));
+                const double xb = ib == 0 ? v0 : (ib == 1 ? v1 : (ib == 2 ? v2 : v3));
+                const double xc = ic == 0 ? v0 : (ic == 1 ? v1 : (ic == 2 ? v2 : v3));
+                const double k = M0[20 * q + m], da = k * xb * xc, db = k * xa * xc, dc = k * xa * xb;
+                c += da * xa;
+                j0 += (ia == 0 ? da : 0.0) + (ib == 0 ? db : 0.0) + (ic == 0 ? dc : 0.0);
+                j1 += (ia == 1 ? da : 0.0) + (ib == 1 ? db : 0.0) + (ic == 1 ? dc : 0.0);
+                j2 += (ia == 2 ? da : 0.0) + (ib == 2 ? db : 0.0) + (ic == 2 ? dc : 0.0);
+                j3 += (ia == 3 ? da : 0.0) + (ib == 3 ? db : 0.0) + (ic == 3 ? dc : 0.0);
+            }
+            a[0][0] += j0 * j0; a[0][1] += j0 * j1; a[0][2] += j0 * j2; a[0][3] += j0 * j3; a[0][4] -= j0 * c;
+            a[1][1] += j1 * j1; a[1][2] += j1 * j2; a[1][3] += j1 * j3; a[1][4] -= j1 * c;
+            a[2][2] += j2 * j2; a[2][3] += j2 * j3; a[2][4] -= j2 * c;
+            a[3][3] += j3 * j3; a[3][4] -= j3 * c;
+        }
+        a[1][0] = a[0][1]; a[2][0] = a[0][2]; a[3][0] = a[0][3]; a[2][1] = a[1][2]; a[3][1] = a[1][3]; a[3][2] = a[2][3];
+        // positive definite: elimination without pivoting, then back-substitution
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = i + 1; r < 4; ++r) {
+                const double f = a[r][i] / a[i][i];
+#pragma unroll
+                for (int cc = i; cc < 5; ++cc) a[r][cc] -= f * a[i][cc];
+            }
+        const double d3 = a[3][4] / a[3][3];
+        const double d2 = (a[2][4] - a[2][3] * d3) / a[2][2];
+        const double d1 = (a[1][4] - a[1][2] * d2 - a[1][3] * d3) / a[1][1];
+        const double d0 = (a[0][4] - a[0][1] * d1 - a[0][2] * d2 - a[0][3] * d3) / a[0][0];
+        v0 += d0; v1 += d1; v2 += d2; v3 += d3;
+        const double nv = sqrt(v0 * v0 + v1 * v1 + v2 * v2 + v3 * v3);
+        v0 /= nv; v1 /= nv; v2 /= nv; v3 /= nv;
+    }
+    double sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { Em[i] = v0 * Bs[i] + v1 * Bs[9 + i] + v2 * Bs[18 + i] + v3 * Bs[27 + i]; sum += fabs(Em[i]); }
+    if (!(sum < INFINITY)) {                                     // (uniform) a step that went nowhere: the candidate as it was
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Em[i] = Ec[i];
+    }
+}
+
+// the hypotheses h0 + w, h0 + w + 4, ... < h1 of edge e by wave w; P: the edge's pairs (LDS or global); T: the wave's table
+__device__ __forceinline__ void ess_slice(const double* P, const int* __restrict__ samples, int e, int n, int H, int h0, int h1,
+                                          unsigned long long seed, double thr, const KMat& Ki, volatile double* Tg,
+                                          int* __restrict__ hyp, int* __restrict__ hyp_roots, int& bc, int& bh, int& br,
+                                          double (&bF)[9], double (&bE)[9]) {
+    constexpr int S = kEssS;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const double2* __restrict__ P2 = reinterpret_cast<const double2*>(P);
+    EssLds* T = (EssLds*)Tg;
+    EssLds* A = T + kEssOffA;
+    EssLds* V = T + kEssOffV;
+    EssLds* R = T + kEssOffR;
+    EssLds* Bs = T + kEssOffB;
+    EssLds* sys = T + kEssOffSys;
+    EssLds* Bz = T + kEssOffBz;
+    EssLds* Pc = T + kEssOffP;
+    EssLds* cF = T + kEssOffF;
+    EssLds* cE = T + kEssOffE;
+    bc = -1; bh = 0x7fffffff; br = -1;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { bF[k] = 0.0; bE[k] = 0.0; }
+#pragma unroll 1
+    for (int h = h0 + w; h < h1; h += kTwoViewWaves) {
+        const size_t at = (size_t)e * (size_t)H + (size_t)h;
+        int idx[S];
+        if (!ransac_sample(samples, e, H, h, n, seed, idx)) {    // (uniform over the wave)
+            if (lane == 0 && hyp != nullptr) hyp[at] = -1;
+            if (lane == 0 && hyp_roots != nullptr) hyp_roots[at] = -1;
+            continue;
+        }
+        // the five rows in camera coordinates through LDS (lane 0 stores them), then lane i < 9 sums row i of A^T A
+#pragma unroll
+        for (int j = 0; j < S; ++j) {
+            const double2 qa = P2[2 * idx[j]], qb = P2[2 * idx[j] + 1];
+            const double w1 = Ki.k[6] * qa.x + Ki.k[7] * qa.y + Ki.k[8], w2 = Ki.k[6] * qb.x + Ki.k[7] * qb.y + Ki.k[8];
+            double r[1][9];
+            FundModel::rows((Ki.k[0] * qa.x + Ki.k[1] * qa.y + Ki.k[2]) / w1, (Ki.k[3] * qa.x + Ki.k[4] * qa.y + Ki.k[5]) / w1,
+                            (Ki.k[0] * qb.x + Ki.k[1] * qb.y + Ki.k[2]) / w2, (Ki.k[3] * qb.x + Ki.k[4] * qb.y + Ki.k[5]) / w2, r);
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i) R[9 * j + i] = r[0][i];
+            }
+        }
+        if (lane < 9) {
+            double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int j = 0; j < S; ++j) {
+                const double ri = R[9 * j + lane];
+#pragma unroll
+                for (int c = 0; c < 9; ++c) acc[c] += ri * R[9 * j + c];
+            }
+#pragma unroll
+            for (int c = 0; c < 9; ++c) { A[9 * lane + c] = acc[c]; V[9 * lane + c] = c == lane ? 1.0 : 0.0; }
+        }
+        jacobi_lds<9>(Tg + kEssOffA, Tg + kEssOffV, lane);
+        // X Y Z W: the columns of the four smallest eigenvalues, ascending, the lower column first among equals.  The fifth
+        // eigenvalue says whether the five rows have rank 5: a sample without it (collinear points) has no candidate
+        bool rank5;
+        {
+            const int r = lane < 36 ? lane / 9 : 4, i = lane < 36 ? lane - 9 * r : 0;
+            double d[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) d[k] = Tg[kEssOffA + 10 * k];    // (read as jacobi_lds wrote them: through the generic pointer)
+            int col = 0;
+            double fifth = 0.0, most = d[0];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                int rank = 0;
+#pragma unroll
+                for (int j = 0; j < 9; ++j) rank += (d[j] < d[k] || (d[j] == d[k] && j < k)) ? 1 : 0;
+                if (rank == r) col = k;
+                if (rank == 4) fifth = d[k];
+                most = d[k] > most ? d[k] : most;
+            }
+            rank5 = fifth > kEssRankTol * most;                  // (the same on every lane; false for a NaN)
+            if (lane < 36) Bs[lane] = Tg[kEssOffV + 9 * i + col];
+        }
+        // the 200 coefficients: entry t = 20 eq + m is the coefficient of monomial m in constraint eq (0: det E; 1 + 3 i + j:
+        // entry (i, j) of 2 E E^T E - tr(E E^T) E), the sum of the trilinear form over the six orders of the monomial's three
+        // variables over the number of orders that coincide
+#pragma unroll 1
+        for (int t = lane; t < 200; t += 64) {
+            const int eq = t / 20, m = t - 20 * eq;
+            const int code = (int)((m < 10 ? kEssMonoLo >> (6 * m) : kEssMonoHi >> (6 * (m - 10))) & 63ull);
+            const int a = code & 3, b = (code >> 2) & 3, c = code >> 4;
+            const double mult = (a == b && b == c) ? 6.0 : ((a == b || b == c) ? 2.0 : 1.0);
+            const int ij = eq > 0 ? eq - 1 : 0, i = ij / 3, j = ij - 3 * i;
+            double s = 0.0;
+#pragma unroll 1
+            for (int p = 0; p < 6; ++p) {
+                const int first = p < 2 ? a : (p < 4 ? b : c);
+                const int second = p == 0 ? b : (p == 1 ? c : (p == 2 ? a : (p == 3 ? c : (p == 4 ? a : b))));
+                const int third = a + b + c - first - second;
+                const EssLds* Pm = Bs + 9 * first;
+                const EssLds* Qm = Bs + 9 * second;
+                const EssLds* Rm = Bs + 9 * third;
+                s += eq == 0 ? ess_det3(Pm, Qm, Rm) : ess_trace3(Pm, Qm, Rm, i, j);
+            }
+            sys[t] = s / mult;
+            T[kEssOffM + t] = s / mult;
+        }
+        // Gauss-Jordan on the left 10 x 10 block with partial pivoting (the first of equal magnitudes); lane = 20 r3 + j
+        // takes column j of the rows r3, r3 + 3, r3 + 6, r3 + 9
+        {
+            const int r3 = lane / 20, j = lane - 20 * r3;
+#pragma unroll 1
+            for (int c = 0; c < 10; ++c) {
+                int p = c;
+                double big = fabs(sys[21 * c]);
+                for (int r = c + 1; r < 10; ++r) { const double v = fabs(sys[20 * r + c]); if (v > big) { big = v; p = r; } }
+                if (lane < 20) { const double u = sys[20 * c + lane], v = sys[20 * p + lane]; sys[20 * c + lane] = v; sys[20 * p + lane] = u; }
+                const double piv = sys[21 * c];
+                if (lane < 20) sys[20 * c + lane] = sys[20 * c + lane] / piv;
+                if (lane < 60) {
+                    const double pj = sys[20 * c + j];
+                    double f[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) { const int r = r3 + 3 * q; f[q] = (r < 10 && r != c) ? sys[20 * r + c] : 0.0; }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) { const int r = r3 + 3 * q; if (r < 10 && r != c) sys[20 * r + j] = sys[20 * r + j] - f[q] * pj; }
+                }
+            }
+        }
+        // B(z): row q from the rows 4 + 2 q and 5 + 2 q of the system, (row 4 + 2 q) - z (row 5 + 2 q); column 0 1 2 the
+        // coefficient of x, y, 1 (the right-hand columns 10.., 13.., 16..), of degree 3, 3, 4
+        if (lane < 45) {
+            const int q = lane / 15, rest = lane - 15 * q, col = rest / 5, d = rest - 5 * col;
+            const int D = col == 2 ? 3 : 2, base = 10 + 3 * col;
+            const EssLds* ra = sys + 20 * (4 + 2 * q);
+            const EssLds* rb = ra + 20;
+            const double va = d <= D ? ra[base + D - d] : 0.0, vb = (d >= 1 && d - 1 <= D) ? rb[base + D - d + 1] : 0.0;
+            Bz[lane] = va - vb;
+        }
+        // (p0, p1, p2) = row 0 x row 1 of B(z) as polynomials (degrees 7, 7, 6); det B(z) = p0 b20 + p1 b21 + p2 b22
+        if (lane < 24) {
+            const int q = lane >> 3, k = lane & 7;
+            const int eu = q == 0 ? 1 : (q == 1 ? 2 : 0), ev = q == 0 ? 5 : (q == 1 ? 3 : 4);
+            const int es = q == 0 ? 2 : (q == 1 ? 0 : 1), et = q == 0 ? 4 : (q == 1 ? 5 : 3);
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < 5; ++i)
+                if (k - i >= 0 && k - i < 5) s += Bz[5 * eu + i] * Bz[5 * ev + k - i] - Bz[5 * es + i] * Bz[5 * et + k - i];
+            Pc[lane] = s;
+        }
+        if (lane < 11) {
+            double s = 0.0;
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    if (lane - i >= 0 && lane - i < 5) s += Pc[8 * q + i] * Bz[5 * (6 + q) + lane - i];
+            T[kEssOffC + lane] = s;
+        }
+        int half = 0;
+        const int nr = rank5 ? ess_real_roots(T, lane, half) : 0;
+        // a candidate per root, ascending z: (x, y, 1) the null vector of B(z) as the cross product of two of its rows, the
+        // pair whose product is the longest (the first of equals); E = xX + yY + zZ + W; F_pix = K^-T E K^-1
+        const EssLds* roots = T + kEssOffRoots + 10 * half;
+        if (lane < nr) {
+            const double z = roots[lane];
+            double b[9];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) b[q] = (((Bz[5 * q + 4] * z + Bz[5 * q + 3]) * z + Bz[5 * q + 2]) * z + Bz[5 * q + 1]) * z + Bz[5 * q];
+            const double n0[3] = {b[1] * b[5] - b[2] * b[4], b[2] * b[3] - b[0] * b[5], b[0] * b[4] - b[1] * b[3]};
+            const double n1[3] = {b[1] * b[8] - b[2] * b[7], b[2] * b[6] - b[0] * b[8], b[0] * b[7] - b[1] * b[6]};
+            const double n2[3] = {b[4] * b[8] - b[5] * b[7], b[5] * b[6] - b[3] * b[8], b[3] * b[7] - b[4] * b[6]};
+            const double l0 = n0[0] * n0[0] + n0[1] * n0[1] + n0[2] * n0[2], l1 = n1[0] * n1[0] + n1[1] * n1[1] + n1[2] * n1[2],
+                         l2 = n2[0] * n2[0] + n2[1] * n2[1] + n2[2] * n2[2];
+            double vx = n0[0], vy = n0[1], vw = n0[2], best = l0;
+            if (l1 > best) { vx = n1[0]; vy = n1[1]; vw = n1[2]; best = l1; }
+            if (l2 > best) { vx = n2[0]; vy = n2[1]; vw = n2[2]; }
+            const double x = vx / vw, y = vy / vw;
+            double Em[9], G[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) Em[k] = x * Bs[k] + y * Bs[9 + k] + z * Bs[18 + k] + Bs[27 + k];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) G[3 * i + j] = Em[3 * i] * Ki.k[j] + Em[3 * i + 1] * Ki.k[3 + j] + Em[3 * i + 2] * Ki.k[6 + j];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) cF[9 * lane + 3 * i + j] = Ki.k[i] * G[j] + Ki.k[3 + i] * G[3 + j] + Ki.k[6 + i] * G[6 + j];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) cE[9 * lane + k] = Em[k];
+        }
+        // one pass over the pairs: a lane loads a pair and tests it against every candidate; lane c keeps the count of candidate c
+        int mine = 0;
+#pragma unroll 1
+        for (int k0 = 0; k0 < n; k0 += 64) {                     // uniform over the wave: the ballot needs every lane
+            const int k = k0 + lane;
+            double2 qa = make_double2(0.0, 0.0), qb = make_double2(0.0, 0.0);
+            if (k < n) { qa = P2[2 * k]; qb = P2[2 * k + 1]; }
+#pragma unroll 1
+            for (int c = 0; c < nr; ++c) {
+                double Fc[9];
+#pragma unroll
+                for (int q = 0; q < 9; ++q) Fc[q] = cF[9 * c + q];
+                const bool inl = k < n && FundModel::inlier(Fc, qa.x, qa.y, qb.x, qb.y, thr);
+                const int pop = __popcll(__ballot(inl));
+                mine += lane == c ? pop : 0;
+            }
+        }
+        int cb = -1, best = 0;
+#pragma unroll 1
+        for (int c = 0; c < nr; ++c) {
+            const int v = __shfl(mine, c);
+            if (cb < 0 || v > best) { best = v; cb = c; }        // (z ascends: the lowest of equal counts stays)
+        }
+        if (lane == 0 && hyp != nullptr) hyp[at] = best;
+        if (lane == 0 && hyp_roots != nullptr) hyp_roots[at] = nr;
+        if (best > bc) {                                         // (h ascends: the lowest h of equal counts stays)
+            bc = best; bh = h; br = cb;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) { bF[k] = 0.0; bE[k] = 0.0; }
+            if (cb >= 0) {                                       // the wave's best so far is kept polished (the edge's best always is one)
+                double G[9];
+                ess_polish(T, cE + 9 * cb, bE);
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) G[3 * i + j] = bE[3 * i] * Ki.k[j] + bE[3 * i + 1] * Ki.k[3 + j] + bE[3 * i + 2] * Ki.k[6 + j];
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) bF[3 * i + j] = Ki.k[i] * G[j] + Ki.k[3 + i] * G[3 + j] + Ki.k[6 + i] * G[6 + j];
+            }
+        }
+    }
+}
+
+struct EssOut {
+    double* __restrict__ E;                      // [E][9]
+    unsigned char* __restrict__ mask;            // [M_used]
+    int* __restrict__ ints;                      // [E][5] inliers, best h, status, success, best root
+};
+
+__global__ __launch_bounds__(kTwoViewThreads) void k_ess_ransac(FundIn in, int H, int hs, int n_slices, unsigned long long seed, double thr,
+                                                                KMat Ki, double* __restrict__ slots, int* __restrict__ hyp,
+                                                                int* __restrict__ hyp_roots) {
+    extern __shared__ __align__(16) double smem[];
+    __shared__ double tab[kTwoViewWaves][kEssWaveDoubles];
+    __shared__ double wbest[kTwoViewWaves][kEssSlot];
+    const int e = blockIdx.x / n_slices, sl = blockIdx.x - e * n_slices;
+    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
+    const int h0 = sl * hs, h1 = min(H, h0 + hs);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    double* __restrict__ slot = slots + (size_t)blockIdx.x * kEssSlot;
+    if (n < kEssS) {                                             // (uniform over the workgroup) FEW_PAIRS: no hypothesis
+        for (int h = h0 + (int)threadIdx.x; h < h1; h += kTwoViewThreads) {
+            if (hyp != nullptr) hyp[(size_t)e * (size_t)H + (size_t)h] = -1;
+            if (hyp_roots != nullptr) hyp_roots[(size_t)e * (size_t)H + (size_t)h] = -1;
+        }
+        if (threadIdx.x < kEssSlot) slot[threadIdx.x] = threadIdx.x == 0 || threadIdx.x == 2 ? -1.0 : 0.0;
+        return;
+    }
+    const double* __restrict__ gp = in.pairs + 4 * (size_t)b;
+    int bc, bh, br;
+    double bF[9], bE[9];
+    if (n <= kTwoViewLdsPairs) {
+        stage_table(gp, 4 * n, smem);
+        ess_slice(smem, in.samples, e, n, H, h0, h1, seed, thr, Ki, tab[w], hyp, hyp_roots, bc, bh, br, bF, bE);
+    } else {
+        ess_slice(gp, in.samples, e, n, H, h0, h1, seed, thr, Ki, tab[w], hyp, hyp_roots, bc, bh, br, bF, bE);
+    }
+    if (lane == 0) {
+        wbest[w][0] = (double)bc; wbest[w][1] = (double)bh; wbest[w][2] = (double)br;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { wbest[w][3 + k] = bF[k]; wbest[w][12 + k] = bE[k]; }
+        wbest[w][21] = 0.0; wbest[w][22] = 0.0; wbest[w][23] = 0.0;
+    }
+    __syncthreads();
+    if (threadIdx.x < kEssSlot) {
+        int best = 0;
+        for (int k = 1; k < kTwoViewWaves; ++k)
+            if (wbest[k][0] > wbest[best][0] || (wbest[k][0] == wbest[best][0] && wbest[k][1] < wbest[best][1])) best = k;
+        slot[threadIdx.x] = wbest[best][threadIdx.x];
+    }
+}
+
+// One workgroup per edge: the best slot (largest count, lowest h), the mask of its F_pix and the count FROM that mask (as
+// twoview_finish does), status, success, E by fund_unit.
+__global__ __launch_bounds__(kTwoViewThreads) void k_ess_finish(FundIn in, int n_slices, double thr, double confidence,
+                                                                const double* __restrict__ slots, EssOut out) {
+    __shared__ double red[kTwoViewWaves];
+    __shared__ double sF[9], sE[9];
+    __shared__ int ctl[3];
+    const int e = blockIdx.x;
+    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
+    const bool first = threadIdx.x == 0;
+    const double2* __restrict__ P2 = reinterpret_cast<const double2*>(in.pairs + 4 * (size_t)b);
+    int* __restrict__ oi = out.ints + 5 * (size_t)e;
+    if (first) {
+        const double* __restrict__ sl = slots + (size_t)e * (size_t)n_slices * kEssSlot;
+        int best = 0;
+        for (int k = 1; k < n_slices; ++k)                       // slots ascend in h: the first of equal counts has the lowest
+            if (sl[(size_t)k * kEssSlot] > sl[(size_t)best * kEssSlot]) best = k;
+        const double* __restrict__ bs = sl + (size_t)best * kEssSlot;
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { sF[k] = bs[3 + k]; sE[k] = bs[12 + k]; sum += fabs(bs[3 + k]) + fabs(bs[12 + k]); }
+        ctl[0] = n < kEssS ? kEssFewPairs : ((sum < INFINITY && bs[2] >= 0.0) ? kEssOk : kEssDegenerate);
+        ctl[1] = bs[0] >= 0.0 ? (int)bs[1] : -1;                 // (-1: no valid sample in any slot)
+        ctl[2] = bs[0] >= 0.0 ? (int)bs[2] : -1;
+    }
+    __syncthreads();
+    if (ctl[0] == kEssFewPairs) {                                // (uniform over the workgroup)
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) out.mask[(size_t)b + k] = 0;
+        if (threadIdx.x < 9) out.E[9 * (size_t)e + threadIdx.x] = 0.0;
+        if (first) { oi[0] = 0; oi[1] = -1; oi[2] = kEssFewPairs; oi[3] = 0; oi[4] = -1; }
+        return;
+    }
+    double Fb[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Fb[k] = sF[k];
+    double c[1] = {0.0};
+    for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+        const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+        const bool inl = ctl[1] >= 0 && FundModel::inlier(Fb, qa.x, qa.y, qb.x, qb.y, thr);
+        out.mask[(size_t)b + k] = inl ? 1 : 0;
+        c[0] += inl ? 1.0 : 0.0;
+    }
+    block_sum<1>(c, red);
+    if (first) {
+        const int cnt = (int)c[0];
+        int status = ctl[0];
+        if (status == kEssOk && cnt < kEssS) status = kEssDegenerate;
+        // (DEGENERATE still reports the count, h, root and mask of its best hypothesis; only the matrix is withheld)
+        oi[0] = cnt; oi[1] = ctl[1]; oi[2] = status;
+        oi[3] = (ctl[1] >= 0 && (double)cnt / (double)n >= confidence) ? 1 : 0;
+        oi[4] = ctl[2];
+        double Eu[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Eu[k] = sE[k];
+        fund_unit(Eu);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) out.E[9 * (size_t)e + k] = status == kEssOk ? Eu[k] : 0.0;
+    }
+}
+
 // ---- sfmba_recover_pose ----
 struct PoseOut {
     double* __restrict__ Rt;                     // [E][12] R (9), t (3)

@@ -390,7 +390,9 @@ int check_samples(sfmba_handle* h, const int32_t* samples, size_t batch, size_t 
 // checked and uploaded, the LDS opt-in, and the launch of the RANSAC kernel (the two have one signature; `score` is its threshold argument).
 using TwoViewRansacKernel = void (*)(FundIn, int, int, int, unsigned long long, double, double*, int*);
 struct TwoViewRansac {
-    TwoViewRansacKernel kern = nullptr;
+    TwoViewRansacKernel kern = nullptr;          // null (the essential call): `finish` launches both kernels
+    size_t slot_doubles = kTwoViewSlot;          // of a slot of the RANSAC kernel
+    size_t hyp_arrays = 1;                       // per-hypothesis integer arrays [n_edges][H] in twoview.hyp, one behind the other
     sfmba_ransac_options o;
     TwoViewBatch bt;
     size_t E = 0, H = 0;
@@ -399,7 +401,7 @@ struct TwoViewRansac {
 };
 
 // (E = 0 on return: the batch has no edge and nothing was launched)
-int twoview_ransac_begin(sfmba_handle* h, const char* who, TwoViewRansacKernel kern, int S, int64_t n_edges, const int64_t* edge_ptr, const double* pts1,
+int twoview_ransac_begin(sfmba_handle* h, const char* who, TwoViewRansacKernel kern, const void* lds_kernel, int S, int64_t n_edges, const int64_t* edge_ptr, const double* pts1,
                          const double* pts2, const uint8_t* pair_use, const int32_t* samples, const sfmba_ransac_options* opt,
                          bool hyp, int64_t* n_ok, double* kernel_us, TwoViewRansac* c) {
     if (opt) c->o = *opt; else sfmba_default_ransac_options(&c->o);
@@ -414,7 +416,8 @@ int twoview_ransac_begin(sfmba_handle* h, const char* who, TwoViewRansacKernel k
     if (E == 0) return 0;
     ransac_slices(h->n_cu, E, (int)H, kTwoViewMinSlice, true, &c->hs, &c->n_slices);
     if (E * (size_t)c->n_slices >= (size_t)1 << 31) return fail(h, -1, "%s: too many edges for one launch", who);
-    CHK(ensure_all(h, {{&t.slots, sizeof(double) * kTwoViewSlot * E * (size_t)c->n_slices}, {&t.hyp, hyp ? sizeof(int) * E * H : 0},
+    CHK(ensure_all(h, {{&t.slots, sizeof(double) * c->slot_doubles * E * (size_t)c->n_slices},
+                       {&t.hyp, hyp ? sizeof(int) * c->hyp_arrays * E * H : 0},
                        {&t.samples, samples ? sizeof(int) * (size_t)S * E * H : 0}}));
     if (samples) {
         const int* up = reinterpret_cast<const int*>(t.in_host.as<unsigned char>() + sizeof(double) * 4 * c->bt.M);
@@ -423,7 +426,7 @@ int twoview_ransac_begin(sfmba_handle* h, const char* who, TwoViewRansacKernel k
         HIPCHK(h, hipMemcpyAsync(t.samples.p, samples, sizeof(int) * (size_t)S * E * H, hipMemcpyHostToDevice, h->stream));
     }
     // the kernel's static LDS (about 8 KiB, above the 2 KiB that set_lds assumes) counts: opted in whatever this call stages
-    CHK(opt_in_lds(h, reinterpret_cast<const void*>(kern), sizeof(double) * 4 * kTwoViewLdsPairs));
+    CHK(opt_in_lds(h, lds_kernel, sizeof(double) * 4 * kTwoViewLdsPairs));
     c->kern = kern;
     c->in = FundIn{t.pairs.as<double>(), t.uptr.as<int>(), samples ? t.samples.as<int>() : nullptr};
     c->E = E;
@@ -446,9 +449,10 @@ struct TwoViewResults {
     uint8_t* mask[2];
     int32_t *inliers, *best, *status;
     uint8_t* success;
-    int32_t *refit_inliers, *hyp;
+    int32_t *refit_inliers, *hyp;                // (refit_inliers: the fifth integer of an edge, whatever the model keeps there)
     int64_t* n_ok;
     double* kernel_us;
+    int32_t* hyp2 = nullptr;                     // the second per-hypothesis array of a call with two
 };
 
 // What the two calls do alike after twoview_ransac_begin: the result buffers (twoview.F the model and its refit,
@@ -464,7 +468,7 @@ int twoview_ransac_end(sfmba_handle* h, const TwoViewRansac& c, double score, si
     CHK(ensure_all(h, {{&t.F, sizeof(double) * 18 * E}, {&t.ints, sizeof(int) * n_ints * E}, {&t.mask, n_masks * std::max<size_t>(Mu, 1)}}));
     EventPair timer;
     CHK(timer.start(h, c.o.profile != 0));
-    CHK(launch_twoview_ransac(h, c, score, r.hyp != nullptr));
+    if (c.kern) CHK(launch_twoview_ransac(h, c, score, r.hyp != nullptr));
     finish(t.F.as<double>(), t.mask.as<unsigned char>(), t.ints.as<int>(), score);
     LAUNCHED(h);
     CHK(timer.stop(h));
@@ -478,6 +482,7 @@ int twoview_ransac_end(sfmba_handle* h, const TwoViewRansac& c, double score, si
     HIPCHK(h, download(h, r.M, t.F.p, sizeof(double) * 9 * E));
     HIPCHK(h, download(h, r.M_refit, t.F.as<double>() + 9 * E, sizeof(double) * 9 * E));
     HIPCHK(h, download(h, r.hyp, t.hyp.p, sizeof(int) * E * H));
+    if (r.hyp2) HIPCHK(h, download(h, r.hyp2, t.hyp.as<int>() + E * H, sizeof(int) * E * H));
     CHK(wait_stream(h));
     CHK(timer.read(h, r.kernel_us));
     const uint8_t zero = 0;
@@ -663,7 +668,7 @@ int sfmba_fundamental_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* ed
                              uint8_t* edge_success, int32_t* edge_status, int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us) {
     CHK(enter(h));
     TwoViewRansac c;
-    CHK(twoview_ransac_begin(h, "sfmba_fundamental_ransac", k_fund_ransac, 8, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
+    CHK(twoview_ransac_begin(h, "sfmba_fundamental_ransac", k_fund_ransac, reinterpret_cast<const void*>(k_fund_ransac), 8, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
                              hyp_inliers != nullptr, n_ok, kernel_us, &c));
     const TwoViewResults r{F, F_refit, {inlier_mask, nullptr}, edge_inliers, edge_best, edge_status, edge_success, nullptr, hyp_inliers,
                            n_ok, kernel_us};
@@ -682,7 +687,7 @@ int sfmba_homography_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edg
                             int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us) {
     CHK(enter(h));
     TwoViewRansac c;
-    CHK(twoview_ransac_begin(h, "sfmba_homography_ransac", k_homog_ransac, 4, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
+    CHK(twoview_ransac_begin(h, "sfmba_homography_ransac", k_homog_ransac, reinterpret_cast<const void*>(k_homog_ransac), 4, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
                              hyp_inliers != nullptr, n_ok, kernel_us, &c));
     const TwoViewResults r{Hm, H_refit, {inlier_mask, refit_mask}, edge_inliers, edge_best, edge_status, edge_success, edge_refit_inliers,
                            hyp_inliers, n_ok, kernel_us};
@@ -690,6 +695,41 @@ int sfmba_homography_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edg
         hipLaunchKernelGGL(k_homog_finish, dim3((unsigned)c.E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, score, c.o.confidence,
                            c.o.refit != 0 ? 1 : 0, (const double*)h->twoview.slots.as<double>(),
                            HomogOut{M, M + 9 * c.E, mask, mask + c.bt.Mu, ints});
+    });
+}
+
+// The F call with k_ess_ransac / k_ess_finish and samples of five positions: twoview.F holds E, twoview.ints five integers
+// per edge (the fifth: the root of the best candidate), twoview.hyp the counts and, behind them, the root counts.
+int sfmba_essential_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edge_ptr, const double* pts1, const double* pts2,
+                           const uint8_t* pair_use, const int32_t* samples, const double* K, const sfmba_ransac_options* opt,
+                           double* E_out, uint8_t* inlier_mask, int32_t* edge_inliers, int32_t* edge_best, int32_t* edge_best_root,
+                           uint8_t* edge_success, int32_t* edge_status, int32_t* hyp_inliers, int32_t* hyp_roots, int64_t* n_ok,
+                           double* kernel_us) {
+    CHK(enter(h));
+    if (!K) return fail(h, -1, "sfmba_essential_ransac: K is NULL");
+    KMat Km;
+    for (int k = 0; k < 9; ++k) Km.k[k] = K[k];
+    const KMat Ki = inverse_k(Km);
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(K[k]) || !std::isfinite(Ki.k[k])) return fail(h, -1, "sfmba_essential_ransac: K is not finite or is singular");
+    if (opt && opt->refit != 0) return fail(h, -1, "sfmba_essential_ransac: refit must be 0 (there is no refit of an essential matrix)");
+    TwoViewRansac c;
+    c.slot_doubles = kEssSlot;
+    c.hyp_arrays = 2;
+    const bool hyp = hyp_inliers != nullptr || hyp_roots != nullptr;
+    CHK(twoview_ransac_begin(h, "sfmba_essential_ransac", nullptr, reinterpret_cast<const void*>(k_ess_ransac), kEssS, n_edges, edge_ptr,
+                             pts1, pts2, pair_use, samples, opt, hyp, n_ok, kernel_us, &c));
+    const TwoViewResults r{E_out, nullptr, {inlier_mask, nullptr}, edge_inliers, edge_best, edge_status, edge_success, edge_best_root,
+                           hyp_inliers, n_ok, kernel_us, hyp_roots};
+    return twoview_ransac_end(h, c, c.o.threshold, 5, 1, kEssOk, r, [&](double* M, unsigned char* mask, int* ints, double score) {
+        auto& t = h->twoview;
+        int* const hy = hyp ? t.hyp.as<int>() : nullptr;
+        const size_t lds = sizeof(double) * 4 * (size_t)std::min(c.bt.max_n, kTwoViewLdsPairs);
+        hipLaunchKernelGGL(k_ess_ransac, dim3((unsigned)(c.E * (size_t)c.n_slices)), dim3(kTwoViewThreads), lds, h->stream, c.in, (int)c.H,
+                           c.hs, c.n_slices, (unsigned long long)c.o.seed, score, Ki, t.slots.as<double>(), hy,
+                           hy ? hy + c.E * c.H : nullptr);
+        hipLaunchKernelGGL(k_ess_finish, dim3((unsigned)c.E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, score, c.o.confidence,
+                           (const double*)t.slots.as<double>(), EssOut{M, mask, ints});
     });
 }
 

@@ -58,6 +58,30 @@ class HomographyEstimate:
         return f"HomographyEstimate(n_edges={len(self.status)}, n_ok={self.n_ok})"
 
 
+class EssentialEstimate:
+    """What `Backend.essential_ransac` returns (include/sfmba.h: sfmba_essential_ransac), per edge of the batch: ``E``
+    (n_edges, 3, 3), unit Frobenius norm, largest entry positive (compare up to sign); ``inliers``, ``best`` (the winning
+    hypothesis), ``best_root`` (its candidate, by ascending z), ``status`` (one of ``OK, FEW_PAIRS, DEGENERATE``) as int32
+    (n_edges), ``success`` (n_edges, bool): inliers / used pairs >= confidence; ``inlier_mask`` (M, bool) over the stored
+    pairs; ``hyp_inliers`` and ``hyp_roots`` (n_edges, H) the count and the number of real roots of every hypothesis, or
+    None when not asked for; ``n_ok``; ``kernel_us`` (``profile=1``, else 0)."""
+
+    OK, FEW_PAIRS, DEGENERATE = 0, 1, 2
+
+    def __init__(self, E, inlier_mask, inliers, best, best_root, success, status, hyp_inliers, hyp_roots, n_ok, kernel_us, edge_ptr):
+        self.E, self.inlier_mask = E, inlier_mask
+        self.inliers, self.best, self.best_root, self.success, self.status = inliers, best, best_root, success, status
+        self.hyp_inliers, self.hyp_roots = hyp_inliers, hyp_roots
+        self.n_ok, self.kernel_us, self.edge_ptr = int(n_ok), float(kernel_us), edge_ptr
+
+    @property
+    def ok(self):
+        return self.status == self.OK
+
+    def __repr__(self):
+        return f"EssentialEstimate(n_edges={len(self.status)}, n_ok={self.n_ok})"
+
+
 class RelativePose:
     """What `Backend.recover_pose` returns (include/sfmba.h: sfmba_recover_pose), per edge: ``R`` (E, 3, 3) and ``t``
     (E, 3), ``x2 = R x1 + t`` with ``|t| = 1``; ``front`` (E) the winner's pairs in front, ``front_all`` (E, 4) every
@@ -434,6 +458,23 @@ def _ransac_prologue(opt, options, samples, batch, S, batch_name, item, what, th
     if samples is not None and samples.shape[1] != opt.max_iters:
         raise ValueError(f"samples holds {samples.shape[1]} hypotheses per {item}, max_iters is {opt.max_iters}")
     return samples
+
+
+def check_essential_args(K, options):
+    """``K`` of `Backend.essential_ransac` as (3, 3) float64, finite and invertible, and its ``options`` without a refit:
+    there is no refit of an essential matrix (include/sfmba.h: sfmba_essential_ransac, "Not done here")."""
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError(f"K must be (3, 3), got {K.shape}")
+    if not np.all(np.isfinite(K)):
+        raise ValueError("K must be finite")
+    with np.errstate(all="ignore"):
+        invertible = float(np.linalg.det(K)) != 0.0 and bool(np.all(np.isfinite(np.linalg.inv(K))))
+    if not invertible:
+        raise ValueError("K must be invertible")
+    if int(options.get("refit", 0)) != 0:
+        raise ValueError("refit must be 0: an essential matrix has no refit")
+    return K
 
 
 def _opt_ptr(a):
@@ -968,6 +1009,34 @@ class Backend:
             _capi.ptr(success), _capi.ptr(status), _opt_ptr(hyp), C.byref(n_ok), C.byref(us)))
         return HomographyEstimate(Hm, Hr, mask.view(np.bool_), rmask.view(np.bool_), inl, rinl, best, success.view(np.bool_),
                                   status, hyp, n_ok.value, us.value, edge_ptr)
+
+    def essential_ransac(self, pts1, pts2, K, edge_ptr=None, pair_use=None, samples=None, want_hyp=False, **options):
+        """The essential matrix by five-point RANSAC for every edge of a batch of matched pixel pairs (include/sfmba.h:
+        sfmba_essential_ransac), the calibrated sibling of :meth:`fundamental_ransac`: the same batch arguments and the
+        same ``options`` (fields of ``sfmba_ransac_options``; ``refit`` must stay 0); ``K`` (3, 3) the one camera matrix of
+        both images; ``samples`` (E, H, 5) int32 positions among an edge's used pairs, None = drawn on the device from
+        ``seed``; with ``samples`` given, ``max_iters`` defaults to its H.  ``want_hyp``: also return the count and the
+        number of real roots of every hypothesis.  Needs no problem.  -> :class:`EssentialEstimate`."""
+        pts1, pts2, edge_ptr, use = _edge_batch(pts1, pts2, edge_ptr, pair_use)
+        K = check_essential_args(K, options)
+        E, M = edge_ptr.shape[0] - 1, pts1.shape[0]
+        opt = _capi.RansacOptions()
+        self._lib.sfmba_default_ransac_options(C.byref(opt))
+        samples = _ransac_prologue(opt, options, samples, E, 5, "n_edges", "edge", "RANSAC", then_flush=self._flush_pending)
+        H = int(opt.max_iters)
+        Em = np.empty((E, 3, 3))
+        mask = np.empty(M, dtype=np.uint8)
+        inl, best, root, status = (np.empty(E, dtype=np.int32) for _ in range(4))
+        success = np.empty(E, dtype=np.uint8)
+        hyp = np.empty((E, H), dtype=np.int32) if want_hyp else None
+        hyp_roots = np.empty((E, H), dtype=np.int32) if want_hyp else None
+        n_ok, us = C.c_int64(), C.c_double()
+        self._check(self._lib.sfmba_essential_ransac(
+            self._h, E, _capi.ptr(edge_ptr), _capi.ptr(pts1), _capi.ptr(pts2), _opt_ptr(use), _opt_ptr(samples), _capi.ptr(K),
+            C.byref(opt), _capi.ptr(Em), _capi.ptr(mask), _capi.ptr(inl), _capi.ptr(best), _capi.ptr(root), _capi.ptr(success),
+            _capi.ptr(status), _opt_ptr(hyp), _opt_ptr(hyp_roots), C.byref(n_ok), C.byref(us)))
+        return EssentialEstimate(Em, mask.view(np.bool_), inl, best, root, success.view(np.bool_), status, hyp, hyp_roots,
+                                 n_ok.value, us.value, edge_ptr)
 
     def recover_pose(self, E, pts1, pts2, K, edge_ptr=None, pair_use=None, **options):
         """R, t, the cheirality mask, the points and their ray angles for every edge of a batch, the reference's

@@ -5,7 +5,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import api
-from .backend import check_descriptors, check_match_edges, check_match_options, check_track_inputs
+from .backend import check_descriptors, check_essential_args, check_match_edges, check_match_options, check_track_inputs
 
 
 def reproj_error(point3ds, point2ds, K, R, tvec, device=0):
@@ -347,7 +347,31 @@ def find_homography(srcPoints, dstPoints, method=RANSAC, ransacReprojThreshold=3
     return H, mask
 
 
-def select_initial_pair(edges, K, min_angle=3, max_angle=60, device=0, backend=None, max_homography_ratio=None, **ransac_options):
+def find_essential_mat(points1, points2, cameraMatrix, method=RANSAC, prob=0.999, threshold=1.0, maxIters=1000, seed=0, device=0,
+                       backend=None):
+    """The swap for ``cv2.findEssentialMat(points1, points2, cameraMatrix, cv2.RANSAC, prob, threshold)`` -> ``(E (3, 3),
+    mask (N, 1) uint8)``; ``E`` is ``None`` when the pairs give no essential matrix.  One call of
+    :meth:`Backend.essential_ransac`: ``E`` is the best five-point candidate itself (unit norm; there is no refit), ``mask``
+    its inliers.  The score is the F call's one-sided distance in image 2 in pixels, not cv2's Sampson distance; ``prob`` only
+    decides ``success`` of the batch call, every one of the ``maxIters`` hypotheses is scored."""
+    if method != RANSAC:
+        raise ValueError("only method=RANSAC is implemented")
+    p1, p2 = np.asarray(points1, dtype=np.float64), np.asarray(points2, dtype=np.float64)
+    if p1.ndim == 3 and p1.shape[1] == 1:                         # cv2's (N, 1, 2)
+        p1 = p1[:, 0]
+    if p2.ndim == 3 and p2.shape[1] == 1:
+        p2 = p2[:, 0]
+    if p1.ndim != 2 or p1.shape[1] != 2 or p1.shape != p2.shape:
+        raise ValueError(f"points1 and points2 must both be (N, 2), got {p1.shape} and {p2.shape}")
+    Km = check_essential_args(cameraMatrix, {})
+    be = backend if backend is not None else api.get_backend(device)
+    est = be.essential_ransac(p1, p2, Km, threshold=threshold, confidence=prob, max_iters=maxIters, seed=seed)
+    mask = est.inlier_mask.astype(np.uint8).reshape(-1, 1)
+    return (est.E[0].copy() if est.status[0] == est.OK else None), mask
+
+
+def select_initial_pair(edges, K, min_angle=3, max_angle=60, device=0, backend=None, max_homography_ratio=None,
+                        two_view="fundamental", **ransac_options):
     """The first-pair choice of ``SFM._initial_register`` (sfm.py:120-180) for a list ``edges`` of ``(pts1, pts2)``: one
     :meth:`Backend.fundamental_ransac` call (``refit=1``) and one :meth:`Backend.recover_pose` call (``E = K^T F K``, over
     each edge's inliers) for the whole list, then on the host the median of ``angle_deg`` over each edge's pairs in front.
@@ -367,7 +391,13 @@ def select_initial_pair(edges, K, min_angle=3, max_angle=60, device=0, backend=N
     noise makes it, and its median angle is a small number that often lands inside the window.  Prototyped in numpy on the
     CPU (300 pairs, 0.3 px noise, 25 % outliers, threshold 1 px, 100 hypotheses, one generator at one seed), the ratio was
     0.92-0.98 on four planar edges, 0.91-1.00 on four pure-rotation edges and 0.02-0.04 on four general edges (the 4-6
-    pairs a four-point H always fits); COLMAP's customary value is 0.8."""
+    pairs a four-point H always fits); COLMAP's customary value is 0.8.
+
+    ``two_view``: ``"fundamental"`` (the default) makes exactly the calls above.  With ``"essential"`` one
+    :meth:`Backend.essential_ransac` call takes the place of the F call (``refit`` is not passed on) and its ``E`` goes to
+    :meth:`Backend.recover_pose` as it is; the homography gate then compares against the E count."""
+    if two_view not in ("fundamental", "essential"):
+        raise ValueError(f"two_view must be 'fundamental' or 'essential', got {two_view!r}")
     if max_homography_ratio is not None and not float(max_homography_ratio) >= 0.0:
         raise ValueError(f"max_homography_ratio must be None or a non-negative number, got {max_homography_ratio!r}")
     if not len(edges):
@@ -383,9 +413,14 @@ def select_initial_pair(edges, K, min_angle=3, max_angle=60, device=0, backend=N
     ptr = np.concatenate([[0], np.cumsum([len(a) for a in p1])]).astype(np.int64)
     pts1, pts2 = np.concatenate(p1), np.concatenate(p2)
     be = backend if backend is not None else api.get_backend(device)
-    ransac_options.setdefault("refit", 1)
-    est = be.fundamental_ransac(pts1, pts2, edge_ptr=ptr, **ransac_options)
-    E = np.einsum("ji,ejk,kl->eil", K, est.F_refit, K)
+    if two_view == "essential":
+        check_essential_args(K, ransac_options)
+        est = be.essential_ransac(pts1, pts2, K, edge_ptr=ptr, **ransac_options)
+        E = est.E
+    else:
+        ransac_options.setdefault("refit", 1)
+        est = be.fundamental_ransac(pts1, pts2, edge_ptr=ptr, **ransac_options)
+        E = np.einsum("ji,ejk,kl->eil", K, est.F_refit, K)
     pose = be.recover_pose(E, pts1, pts2, K, edge_ptr=ptr, pair_use=est.inlier_mask)
     planar = np.zeros(len(edges), dtype=bool)
     if max_homography_ratio is not None:
