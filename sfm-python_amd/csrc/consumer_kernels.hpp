@@ -1174,18 +1174,18 @@ __global__ __launch_bounds__(kCamThreads) void k_resect(ResectIn in, int C, KMat
 // Two-view geometry (sfmba_fundamental_ransac, sfmba_recover_pose).  A batch of edges (image
 // pairs), each a run of used pixel pairs x1 y1 x2 y2 (32 bytes, packed by the host in stored order); nothing of a
 // bundle-adjustment problem is read.
-// The RANSAC and its finish are written once over a model (FundModel, HomogModel: what a model supplies is listed above
-// them); the four kernels are that code with a model bound:
-//   k_fund_ransac, k_homog_ransac   twoview_ransac<M>: grid over (edge, slice of hypotheses); a wave takes one hypothesis
-//                   at a time (twoview_slice<M>): M::S sampled pairs (ransac_sample) -> one-scale normalisation, A^T A of
-//                   the model's eight rows, its smallest eigenvector by jacobi_lds<9>, M::from_jacobi (F, the reference's
-//                   estimate_fundamental_matrix: rank 2 by a 3x3 Jacobi in registers, T2^T F T1; H: T2^-1 Hn T1), then
-//                   the lanes stride the edge's pairs and count M::inlier (F: |x2^T F x1| / |(F x1)_xy| < threshold; H:
-//                   the squared transfer distance in image 2) by ballot / popcount.  A workgroup leaves the best (count,
-//                   h, matrix) of its slice in a slot of its own.
-//   k_fund_finish, k_homog_finish   twoview_finish<M>: one workgroup per edge: best slot (largest count, lowest h), the
-//                   mask of that matrix, the refit over all its inliers (sums by block_sum, the 9x9 Jacobi by wave 0),
-//                   unit norm and sign; a model with kRefitMask (H) adds the mask and count of the refit.
+// The grid, slots and ties of the RANSAC are the shell's (below); F and H put into it what is written
+// once over a model (FundModel, HomogModel: what a model supplies is listed above them); then the finish of an edge:
+//   k_fund_ransac, k_homog_ransac   twoview_ransac<M> binds twoview_slice<M>: a wave takes one hypothesis at a time, M::S
+//                   sampled pairs (ransac_sample) -> one-scale normalisation, A^T A of the model's eight rows, its smallest
+//                   eigenvector by jacobi_lds<9>, M::from_jacobi (F, the reference's estimate_fundamental_matrix: rank 2 by
+//                   a 3x3 Jacobi in registers, T2^T F T1; H: T2^-1 Hn T1), then the lanes stride the edge's pairs and count
+//                   M::inlier (F: |x2^T F x1| / |(F x1)_xy| < threshold; H: the squared transfer distance in image 2) by
+//                   ballot / popcount.
+//   k_fund_finish, k_homog_finish   twoview_finish<M>: one workgroup per edge: twoview_verdict (best slot, the mask of that
+//                   matrix and the count from it, status; k_ess_finish shares it), then unit norm and sign and the refit
+//                   over all inliers (sums by block_sum, the 9x9 Jacobi by wave 0); a model with kRefitMask (H) adds the
+//                   mask and count of the refit.
 //   k_recover_pose  one workgroup per edge: wave 0 decomposes E into the four (R, t), every pair is triangulated against
 //                   each (two-view DLT, smallest_eigenvector4) and counted in front; thread 0 decides; a second pass
 //                   writes the winner's points, mask, ray angles and the summed reprojection error.
@@ -1195,7 +1195,8 @@ constexpr int kTwoViewThreads = 256;
 constexpr int kTwoViewWaves = 4;
 constexpr int kTwoViewLdsPairs = 4096;   // an edge of up to this many used pairs is staged in LDS (128 KiB of the 160)
 constexpr int kTwoViewMinSlice = 8;      // fewest hypotheses of a workgroup's slice (two per wave)
-constexpr int kTwoViewSlot = 12;         // doubles of a slot: count, h, F or H (9), unused
+constexpr int kRansacHead = 3;           // doubles of a slot before its payload: count, h, one auxiliary integer (the shell, below)
+constexpr int kTwoViewSlot = kRansacHead + 9;    // doubles of a slot: the payload is F or H
 constexpr int kJacobiLdsSweeps = 30;     // cap of the sweeps of jacobi_lds (a 9x9 converges in 5..9)
 constexpr int kFundOk = 0, kFundFewPairs = 1, kFundDegenerate = 2;
 constexpr int kPoseOk = 0, kPoseFewPairs = 1, kPoseDegenerate = 2, kPoseTie = 3;
@@ -1283,7 +1284,72 @@ __device__ __forceinline__ bool ransac_sample(const int* __restrict__ samples, i
     return valid;
 }
 
-// ---- The model of a two-view RANSAC: what twoview_slice, twoview_ransac, twoview_ata_rows and twoview_finish below ask of
+// ---- The shell of the two-view RANSAC kernels (F, H, E).  A grid over (edge, slice of its H hypotheses): a workgroup leaves
+// the best of the hypotheses [h0, h1) of one edge in a slot of its own: count, h, one auxiliary integer (E: the root), P doubles.
+// THE RULE every caller-visible tie rests on: the largest count wins, among equal counts the lowest h.  A slice meets its
+// hypotheses in ascending h and replaces the wave's best only by a strictly larger count; waves: ransac_better; slots ascend
+// in h, so the first of equal counts is the one (ransac_best_slot).  A family supplies a slice function (twoview_slice<M>,
+// ess_slice: untouched by the shell, their loops are sensitive to anything live across them) and a kernel that binds it:
+// ransac_block; too few pairs: ransac_no_hypothesis per array, ransac_empty_slot; else the slice over staged or global pairs,
+// the wave's best packed into a RansacBest, ransac_store.
+constexpr int kRansacNone = -1;          // count and auxiliary integer of no hypothesis
+
+template <int P> struct RansacBest { int count = kRansacNone, h = 0x7fffffff, aux = kRansacNone; double v[P] = {}; };
+
+__device__ __forceinline__ bool ransac_better(double count, double h, double than_count, double than_h) {
+    return count > than_count || (count == than_count && h < than_h);
+}
+
+struct RansacBlock { int item, h0, h1; };
+__device__ __forceinline__ RansacBlock ransac_block(int H, int hs, int n_slices) {
+    const int item = blockIdx.x / n_slices, sl = blockIdx.x - item * n_slices;
+    return RansacBlock{item, sl * hs, min(H, sl * hs + hs)};
+}
+
+// -1 into the workgroup's part of a per-hypothesis array [batch][H] (null: not asked for)
+__device__ __forceinline__ void ransac_no_hypothesis(const RansacBlock& rb, int H, int* hyp) {
+    if (hyp != nullptr)
+        for (int h = rb.h0 + (int)threadIdx.x; h < rb.h1; h += kTwoViewThreads) hyp[(size_t)rb.item * (size_t)H + (size_t)h] = -1;
+}
+
+template <int P>
+__device__ __forceinline__ void ransac_empty_slot(double* slots) {
+    constexpr int kSlot = kRansacHead + P;
+    if (threadIdx.x < kSlot) slots[(size_t)blockIdx.x * kSlot + threadIdx.x] = threadIdx.x == 0 || threadIdx.x == 2 ? (double)kRansacNone : 0.0;
+}
+
+// the waves' bests through LDS into the workgroup's slot: thread t stores entry t of the winner
+template <int P>
+__device__ __forceinline__ void ransac_store(const RansacBest<P>& best, double* slots) {
+    constexpr int kSlot = kRansacHead + P;
+    __shared__ double wbest[kTwoViewWaves][kSlot];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) {
+        wbest[w][0] = (double)best.count; wbest[w][1] = (double)best.h; wbest[w][2] = (double)best.aux;
+#pragma unroll
+        for (int k = 0; k < P; ++k) wbest[w][kRansacHead + k] = best.v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kSlot) {
+        int win = 0;
+        for (int k = 1; k < kTwoViewWaves; ++k)
+            if (ransac_better(wbest[k][0], wbest[k][1], wbest[win][0], wbest[win][1])) win = k;
+        slots[(size_t)blockIdx.x * kSlot + threadIdx.x] = wbest[win][threadIdx.x];
+    }
+}
+
+// the winner among the n_slices slots of an item (see THE RULE)
+template <int P>
+__device__ __forceinline__ const double* ransac_best_slot(const double* slots, int item, int n_slices) {
+    constexpr int kSlot = kRansacHead + P;
+    const double* __restrict__ sl = slots + (size_t)item * (size_t)n_slices * kSlot;
+    int best = 0;
+    for (int k = 1; k < n_slices; ++k)
+        if (sl[(size_t)k * kSlot] > sl[(size_t)best * kSlot]) best = k;
+    return sl + (size_t)best * kSlot;
+}
+
+// ---- The model of a two-view RANSAC: what twoview_slice, twoview_verdict, twoview_ata_rows and twoview_finish below ask of
 // an estimator.  A model is a 3x3 matrix, the null vector of a 9-column system of normalised pairs:
 //   S            pairs of a sample, and the fewest inliers of an estimate
 //   kRefitMask   whether the finish also returns the mask and count of the refit (a second mask, a fifth integer per edge)
@@ -1494,53 +1560,29 @@ __device__ __forceinline__ void twoview_slice(const double* P, const int* __rest
     }
 }
 
-// grid over (edge, slice of hypotheses): the best (count, h, matrix) of the workgroup's slice into its slot.  (This body
-// and twoview_finish take plain pointers: the kernels' own parameters carry __restrict__, and saying it again here moves
-// their code away from what it was as one function)
+// The F / H binding of the shell.  (This body and twoview_finish take plain pointers: the kernels' own
+// parameters carry __restrict__, and saying it again here moves their code away from what it was as one function)
 template <class M>
 __device__ __forceinline__ void twoview_ransac(const double* pairs, const int* uptr, const int* samples, int H, int hs, int n_slices,
                                                unsigned long long seed, double score, double* slots, int* hyp) {
     extern __shared__ __align__(16) double smem[];
     __shared__ double jA[kTwoViewWaves][81], jV[kTwoViewWaves][81], jR[kTwoViewWaves][72];
-    __shared__ double wbest[kTwoViewWaves][kTwoViewSlot];
-    const int e = blockIdx.x / n_slices, sl = blockIdx.x - e * n_slices;
-    const int b = uptr[e], n = uptr[e + 1] - b;
-    const int h0 = sl * hs, h1 = min(H, h0 + hs);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    double* __restrict__ slot = slots + (size_t)blockIdx.x * kTwoViewSlot;
-    if (n < M::S) {                                              // (uniform over the workgroup) FEW_PAIRS: no hypothesis
-        if (hyp != nullptr)
-            for (int h = h0 + (int)threadIdx.x; h < h1; h += kTwoViewThreads) hyp[(size_t)e * (size_t)H + (size_t)h] = -1;
-        if (threadIdx.x == 0) {
-            slot[0] = -1.0; slot[1] = 0.0;
-#pragma unroll
-            for (int k = 2; k < kTwoViewSlot; ++k) slot[k] = 0.0;
-        }
-        return;
-    }
+    const RansacBlock rb = ransac_block(H, hs, n_slices);
+    const int b = uptr[rb.item], n = uptr[rb.item + 1] - b, w = threadIdx.x >> 6;
     const double* __restrict__ gp = pairs + 4 * (size_t)b;
+    if (n < M::S) { ransac_no_hypothesis(rb, H, hyp); ransac_empty_slot<9>(slots); return; }    // (uniform) FEW_PAIRS: no hypothesis
     int bc, bh;
     double bM[9];
     if (n <= kTwoViewLdsPairs) {
         stage_table(gp, 4 * n, smem);
-        twoview_slice<M>(smem, samples, e, n, H, h0, h1, seed, score, jA[w], jV[w], jR[w], hyp, bc, bh, bM);
+        twoview_slice<M>(smem, samples, rb.item, n, H, rb.h0, rb.h1, seed, score, jA[w], jV[w], jR[w], hyp, bc, bh, bM);
     } else {
-        twoview_slice<M>(gp, samples, e, n, H, h0, h1, seed, score, jA[w], jV[w], jR[w], hyp, bc, bh, bM);
+        twoview_slice<M>(gp, samples, rb.item, n, H, rb.h0, rb.h1, seed, score, jA[w], jV[w], jR[w], hyp, bc, bh, bM);
     }
-    if (lane == 0) {
-        wbest[w][0] = (double)bc; wbest[w][1] = (double)bh;
+    RansacBest<9> best{bc, bh};
 #pragma unroll
-        for (int k = 0; k < 9; ++k) wbest[w][2 + k] = bM[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int best = 0;
-        for (int k = 1; k < kTwoViewWaves; ++k)
-            if (wbest[k][0] > wbest[best][0] || (wbest[k][0] == wbest[best][0] && wbest[k][1] < wbest[best][1])) best = k;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) slot[k] = wbest[best][k];
-        slot[11] = 0.0;
-    }
+    for (int k = 0; k < 9; ++k) best.v[k] = bM[k];
+    ransac_store(best, slots);
 }
 
 // rows I0 .. I1 - 1 of the upper triangle of A^T A over the pairs of the mask mk (its own stores), thread t taking pairs t, t + 256, ...; thread 0
@@ -1574,79 +1616,87 @@ __device__ __forceinline__ void twoview_ata_rows(const double2* __restrict__ P2,
     }
 }
 
-// One workgroup per edge: best slot (largest count, lowest h), the mask of that matrix, the refit over all its inliers
-// (sums by block_sum, the 9x9 Jacobi by wave 0), unit norm and sign; with M::kRefitMask one more pass over the pairs for the
-// mask and count of the refit.  oM, oM_refit [E][9]; omask, orefit_mask [M_used]; oints [E][4 or 5] inliers, best h, status,
-// success, refit inliers.
+// The verdict of an edge, the first half of its finish kernel: the best of its slots, the mask of that slot's matrix (the
+// first nine doubles of the payload) and the count FROM that mask, status, success, oi[0..3] = inliers, best h, status,
+// success (with M::kRefitMask the refit's mask and count oi[4] start as copies: refit = 0 and DEGENERATE leave them so).  Of a
+// model it asks S, the status values, kRefitMask and inlier.
+struct TwoViewVerdict { int status, cnt, aux; };
+template <class M, int P>
+__device__ __forceinline__ TwoViewVerdict twoview_verdict(const double2* P2, int e, size_t b, int n, int n_slices, double score,
+                                                          double confidence, const double* slots, unsigned char* omask,
+                                                          unsigned char* orefit_mask, int* oi, double (&pay)[P]) {
+    __shared__ double red[kTwoViewWaves];
+    __shared__ double sp[P];
+    __shared__ int ctl[4];                                       // status, best h, auxiliary integer, count
+    const bool first = threadIdx.x == 0;
+    if (first) {
+        const double* __restrict__ bs = ransac_best_slot<P>(slots, e, n_slices);
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < P; ++k) { sp[k] = bs[kRansacHead + k]; sum += fabs(bs[kRansacHead + k]); }
+        ctl[0] = n < M::S ? M::kFewPairs : (sum < INFINITY ? M::kOk : M::kDegenerate);
+        ctl[1] = bs[0] >= 0.0 ? (int)bs[1] : -1;                 // (-1: no valid sample in any slot)
+        ctl[2] = bs[0] >= 0.0 ? (int)bs[2] : -1;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < P; ++k) pay[k] = sp[k];
+    if (ctl[0] == M::kFewPairs) {                                // (uniform over the workgroup)
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            omask[b + k] = 0;
+            if constexpr (M::kRefitMask) orefit_mask[b + k] = 0;
+        }
+        if (first) {
+            oi[0] = 0; oi[1] = -1; oi[2] = M::kFewPairs; oi[3] = 0;
+            if constexpr (M::kRefitMask) oi[4] = 0;
+        }
+        return TwoViewVerdict{M::kFewPairs, 0, -1};
+    }
+    // edge_inliers, edge_success, the status and a refit all rest on this one evaluation (the count in the slot came from another
+    // copy of the expression, which the compiler may have contracted differently for a pair within an ulp of the threshold)
+    double Mb[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Mb[k] = pay[k];
+    double c[1] = {0.0};
+    for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+        const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
+        const bool inl = ctl[1] >= 0 && M::inlier(Mb, qa.x, qa.y, qb.x, qb.y, score);
+        omask[b + k] = inl ? 1 : 0;
+        if constexpr (M::kRefitMask) orefit_mask[b + k] = inl ? 1 : 0;
+        c[0] += inl ? 1.0 : 0.0;
+    }
+    block_sum<1>(c, red);
+    if (first) {
+        const int cnt = (int)c[0];
+        if (ctl[0] == M::kOk && cnt < M::S) ctl[0] = M::kDegenerate;
+        ctl[3] = cnt;
+        // (DEGENERATE still reports the count, h and mask of its best hypothesis; only the matrix is withheld)
+        oi[0] = cnt; oi[1] = ctl[1]; oi[2] = ctl[0];
+        oi[3] = (ctl[1] >= 0 && (double)cnt / (double)n >= confidence) ? 1 : 0;
+        if constexpr (M::kRefitMask) oi[4] = cnt;
+    }
+    __syncthreads();
+    return TwoViewVerdict{ctl[0], ctl[3], ctl[2]};
+}
+
+// One workgroup per edge: the verdict, the matrix with unit norm and sign, the refit, with M::kRefitMask its mask and count.
+// oM, oM_refit [E][9]; omask, orefit_mask [M_used]; oints [E][4 or 5] inliers, best h, status, success, refit inliers.
 template <class M>
 __device__ __forceinline__ void twoview_finish(const double* pairs, const int* uptr, int n_slices, double score, double confidence,
                                                int refit, const double* slots, double* oM, double* oM_refit, unsigned char* omask,
                                                unsigned char* orefit_mask, int* oints) {
     __shared__ double red[kTwoViewWaves * 18];
     __shared__ double jA[81], jV[81];
-    __shared__ double sM[9], sm[9];
-    __shared__ int ctl[2];
+    __shared__ double sM[9], sm[8];
     const int e = blockIdx.x;
     const int b = uptr[e], n = uptr[e + 1] - b;
     const bool first = threadIdx.x == 0;
     const double2* __restrict__ P2 = reinterpret_cast<const double2*>(pairs + 4 * (size_t)b);
     int* __restrict__ oi = oints + (M::kRefitMask ? 5 : 4) * (size_t)e;
-    if (first) {
-        const double* __restrict__ sl = slots + (size_t)e * (size_t)n_slices * kTwoViewSlot;
-        int best = 0;
-        for (int k = 1; k < n_slices; ++k)                       // slots ascend in h: the first of equal counts has the lowest
-            if (sl[(size_t)k * kTwoViewSlot] > sl[(size_t)best * kTwoViewSlot]) best = k;
-        const double* __restrict__ bs = sl + (size_t)best * kTwoViewSlot;
-        double sum = 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { sM[k] = bs[2 + k]; sum += fabs(bs[2 + k]); }
-        ctl[0] = n < M::S ? M::kFewPairs : (sum < INFINITY ? M::kOk : M::kDegenerate);
-        ctl[1] = bs[0] >= 0.0 ? (int)bs[1] : -1;                 // (-1: no valid sample in any slot)
-    }
-    __syncthreads();
     const unsigned char* mk = omask + (size_t)b;                 // a thread reads back only what it stored itself
-    if (ctl[0] == M::kFewPairs) {                                // (uniform over the workgroup)
-        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
-            omask[(size_t)b + k] = 0;
-            if constexpr (M::kRefitMask) orefit_mask[(size_t)b + k] = 0;
-        }
-        if (threadIdx.x < 9) { oM[9 * (size_t)e + threadIdx.x] = 0.0; oM_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
-        if (first) {
-            oi[0] = 0; oi[1] = -1; oi[2] = M::kFewPairs; oi[3] = 0;
-            if constexpr (M::kRefitMask) oi[4] = 0;
-        }
-        return;
-    }
-    // The mask of the best matrix, and the count FROM that mask: edge_inliers, edge_success, the status and the refit below
-    // all rest on this one evaluation (the count in the slot came from another copy of the expression, which the compiler may
-    // have contracted differently for a pair within an ulp of the threshold).  A refit mask starts as its copy (refit = 0
-    // and DEGENERATE leave it so).
     double Mb[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Mb[k] = sM[k];
-    {
-        double c[1] = {0.0};
-        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
-            const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
-            const bool inl = ctl[1] >= 0 && M::inlier(Mb, qa.x, qa.y, qb.x, qb.y, score);
-            omask[(size_t)b + k] = inl ? 1 : 0;
-            if constexpr (M::kRefitMask) orefit_mask[(size_t)b + k] = inl ? 1 : 0;
-            c[0] += inl ? 1.0 : 0.0;
-        }
-        block_sum<1>(c, red);
-        if (first) {
-            const int cnt = (int)c[0];
-            if (ctl[0] == M::kOk && cnt < M::S) ctl[0] = M::kDegenerate;
-            sm[8] = (double)cnt;
-            // (DEGENERATE still reports the count, h and mask of its best hypothesis; only the matrix is withheld)
-            oi[0] = cnt; oi[1] = ctl[1]; oi[2] = ctl[0];
-            oi[3] = (ctl[1] >= 0 && (double)cnt / (double)n >= confidence) ? 1 : 0;
-            if constexpr (M::kRefitMask) oi[4] = cnt;
-        }
-        __syncthreads();
-    }
-    const int status = ctl[0], cnt = (int)sm[8];
-    if (status != M::kOk) {
+    const TwoViewVerdict vd = twoview_verdict<M>(P2, e, (size_t)b, n, n_slices, score, confidence, slots, omask, orefit_mask, oi, Mb);
+    if (vd.status != M::kOk) {
         if (threadIdx.x < 9) { oM[9 * (size_t)e + threadIdx.x] = 0.0; oM_refit[9 * (size_t)e + threadIdx.x] = 0.0; }
         return;
     }
@@ -1674,7 +1724,7 @@ __device__ __forceinline__ void twoview_finish(const double* pairs, const int* u
         }
         block_sum<4>(v, red);
         if (first) {
-            const double c = (double)cnt;
+            const double c = (double)vd.cnt;
             sm[0] = v[0] / c; sm[1] = v[1] / c; sm[2] = v[2] / c; sm[3] = v[3] / c;
             sm[4] = (v[0] + v[1]) / (2.0 * c); sm[5] = (v[2] + v[3]) / (2.0 * c);
         }
@@ -1692,7 +1742,7 @@ __device__ __forceinline__ void twoview_finish(const double* pairs, const int* u
             }
         }
         block_sum<2>(v, red);
-        if (first) { sm[6] = sqrt(v[0] / (2.0 * (double)cnt)); sm[7] = sqrt(v[1] / (2.0 * (double)cnt)); }
+        if (first) { sm[6] = sqrt(v[0] / (2.0 * (double)vd.cnt)); sm[7] = sqrt(v[1] / (2.0 * (double)vd.cnt)); }
         __syncthreads();
     }
     const double s1 = sm[6], s2 = sm[7];
@@ -1771,17 +1821,18 @@ __global__ __launch_bounds__(kTwoViewThreads) void k_homog_finish(FundIn in, int
 }
 
 // ---- sfmba_essential_ransac (include/sfmba.h): the calibrated model, five pairs a sample ----
-// k_ess_ransac   the grid, slots and wave-per-hypothesis loop of twoview_ransac.  A hypothesis: five pairs in camera
+// k_ess_ransac   binds ess_slice to the shell, a wave per hypothesis.  A hypothesis: five pairs in camera
 //                coordinates (K^-1), A^T A of their FundModel::rows, jacobi_lds<9>, the four eigenvectors of the smallest
 //                eigenvalues X Y Z W; the ten cubic constraints on E = xX + yY + zZ + W, one coefficient per lane and round
 //                (200 of them); Gauss-Jordan with partial pivoting, one entry per lane and round; B(z), its cofactor
 //                polynomials and det B(z) by lanes over the coefficients; every real root of det B(z) by the tower of its
 //                derivatives (ess_real_roots), an interval per lane; a candidate (E, F_pix) per lane; then ONE pass over
 //                the edge's pairs: a lane loads a pair and tests it against every candidate.
-// k_ess_finish   one workgroup per edge: best slot, the mask and count from its F_pix, status, E by fund_unit.
+// k_ess_finish   one workgroup per edge: twoview_verdict on the slot's F_pix, then the root, the status and E by fund_unit.
 // Everything a wave indexes at run time is in its table of kEssWaveDoubles doubles of LDS (the map below): no scratch.
 constexpr int kEssS = 5;                  // pairs of a sample, and the fewest inliers of an estimate
-constexpr int kEssSlot = 24;              // doubles of a slot: count, h, root, F_pix (9), E (9), unused (3)
+constexpr int kEssPayload = 18;           // of a slot (its auxiliary integer: the root): F_pix (9), E (9)
+constexpr int kEssSlot = kRansacHead + kEssPayload;
 constexpr int kEssMaxRoots = 10;
 constexpr int kEssRootIters = 100;        // cap of the safeguarded Newton steps of one root (a bisection at the worst: 2^-100)
 constexpr double kEssRankTol = 1e-12;     // a sample's A^T A has rank 5 when its fifth-smallest eigenvalue is above this times the largest
@@ -2221,98 +2272,44 @@ __global__ __launch_bounds__(kTwoViewThreads) void k_ess_ransac(FundIn in, int H
                                                                 int* __restrict__ hyp_roots) {
     extern __shared__ __align__(16) double smem[];
     __shared__ double tab[kTwoViewWaves][kEssWaveDoubles];
-    __shared__ double wbest[kTwoViewWaves][kEssSlot];
-    const int e = blockIdx.x / n_slices, sl = blockIdx.x - e * n_slices;
-    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
-    const int h0 = sl * hs, h1 = min(H, h0 + hs);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    double* __restrict__ slot = slots + (size_t)blockIdx.x * kEssSlot;
-    if (n < kEssS) {                                             // (uniform over the workgroup) FEW_PAIRS: no hypothesis
-        for (int h = h0 + (int)threadIdx.x; h < h1; h += kTwoViewThreads) {
-            if (hyp != nullptr) hyp[(size_t)e * (size_t)H + (size_t)h] = -1;
-            if (hyp_roots != nullptr) hyp_roots[(size_t)e * (size_t)H + (size_t)h] = -1;
-        }
-        if (threadIdx.x < kEssSlot) slot[threadIdx.x] = threadIdx.x == 0 || threadIdx.x == 2 ? -1.0 : 0.0;
-        return;
-    }
+    const RansacBlock rb = ransac_block(H, hs, n_slices);
+    const int b = in.uptr[rb.item], n = in.uptr[rb.item + 1] - b, w = threadIdx.x >> 6;
     const double* __restrict__ gp = in.pairs + 4 * (size_t)b;
+    if (n < kEssS) { ransac_no_hypothesis(rb, H, hyp); ransac_no_hypothesis(rb, H, hyp_roots); ransac_empty_slot<kEssPayload>(slots); return; }   // (uniform) FEW_PAIRS
     int bc, bh, br;
     double bF[9], bE[9];
     if (n <= kTwoViewLdsPairs) {
         stage_table(gp, 4 * n, smem);
-        ess_slice(smem, in.samples, e, n, H, h0, h1, seed, thr, Ki, tab[w], hyp, hyp_roots, bc, bh, br, bF, bE);
+        ess_slice(smem, in.samples, rb.item, n, H, rb.h0, rb.h1, seed, thr, Ki, tab[w], hyp, hyp_roots, bc, bh, br, bF, bE);
     } else {
-        ess_slice(gp, in.samples, e, n, H, h0, h1, seed, thr, Ki, tab[w], hyp, hyp_roots, bc, bh, br, bF, bE);
+        ess_slice(gp, in.samples, rb.item, n, H, rb.h0, rb.h1, seed, thr, Ki, tab[w], hyp, hyp_roots, bc, bh, br, bF, bE);
     }
-    if (lane == 0) {
-        wbest[w][0] = (double)bc; wbest[w][1] = (double)bh; wbest[w][2] = (double)br;
+    RansacBest<kEssPayload> best{bc, bh, br};
 #pragma unroll
-        for (int k = 0; k < 9; ++k) { wbest[w][3 + k] = bF[k]; wbest[w][12 + k] = bE[k]; }
-        wbest[w][21] = 0.0; wbest[w][22] = 0.0; wbest[w][23] = 0.0;
-    }
-    __syncthreads();
-    if (threadIdx.x < kEssSlot) {
-        int best = 0;
-        for (int k = 1; k < kTwoViewWaves; ++k)
-            if (wbest[k][0] > wbest[best][0] || (wbest[k][0] == wbest[best][0] && wbest[k][1] < wbest[best][1])) best = k;
-        slot[threadIdx.x] = wbest[best][threadIdx.x];
-    }
+    for (int k = 0; k < 9; ++k) { best.v[k] = bF[k]; best.v[9 + k] = bE[k]; }
+    ransac_store(best, slots);
 }
 
-// One workgroup per edge: the best slot (largest count, lowest h), the mask of its F_pix and the count FROM that mask (as
-// twoview_finish does), status, success, E by fund_unit.
+// what twoview_verdict asks of a model: E is scored as F, by its F_pix (the first nine doubles of the payload)
+struct EssVerdict : FundModel { static constexpr int S = kEssS; };
+static_assert(kEssOk == kFundOk && kEssFewPairs == kFundFewPairs && kEssDegenerate == kFundDegenerate, "EssVerdict reports F's status values");
+
+// One workgroup per edge: twoview_verdict, then what is E's own: the status also needs a root (the fifth integer), E by fund_unit.
 __global__ __launch_bounds__(kTwoViewThreads) void k_ess_finish(FundIn in, int n_slices, double thr, double confidence,
                                                                 const double* __restrict__ slots, EssOut out) {
-    __shared__ double red[kTwoViewWaves];
-    __shared__ double sF[9], sE[9];
-    __shared__ int ctl[3];
     const int e = blockIdx.x;
     const int b = in.uptr[e], n = in.uptr[e + 1] - b;
-    const bool first = threadIdx.x == 0;
     const double2* __restrict__ P2 = reinterpret_cast<const double2*>(in.pairs + 4 * (size_t)b);
     int* __restrict__ oi = out.ints + 5 * (size_t)e;
-    if (first) {
-        const double* __restrict__ sl = slots + (size_t)e * (size_t)n_slices * kEssSlot;
-        int best = 0;
-        for (int k = 1; k < n_slices; ++k)                       // slots ascend in h: the first of equal counts has the lowest
-            if (sl[(size_t)k * kEssSlot] > sl[(size_t)best * kEssSlot]) best = k;
-        const double* __restrict__ bs = sl + (size_t)best * kEssSlot;
-        double sum = 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { sF[k] = bs[3 + k]; sE[k] = bs[12 + k]; sum += fabs(bs[3 + k]) + fabs(bs[12 + k]); }
-        ctl[0] = n < kEssS ? kEssFewPairs : ((sum < INFINITY && bs[2] >= 0.0) ? kEssOk : kEssDegenerate);
-        ctl[1] = bs[0] >= 0.0 ? (int)bs[1] : -1;                 // (-1: no valid sample in any slot)
-        ctl[2] = bs[0] >= 0.0 ? (int)bs[2] : -1;
-    }
-    __syncthreads();
-    if (ctl[0] == kEssFewPairs) {                                // (uniform over the workgroup)
-        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) out.mask[(size_t)b + k] = 0;
-        if (threadIdx.x < 9) out.E[9 * (size_t)e + threadIdx.x] = 0.0;
-        if (first) { oi[0] = 0; oi[1] = -1; oi[2] = kEssFewPairs; oi[3] = 0; oi[4] = -1; }
-        return;
-    }
-    double Fb[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Fb[k] = sF[k];
-    double c[1] = {0.0};
-    for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
-        const double2 qa = P2[2 * k], qb = P2[2 * k + 1];
-        const bool inl = ctl[1] >= 0 && FundModel::inlier(Fb, qa.x, qa.y, qb.x, qb.y, thr);
-        out.mask[(size_t)b + k] = inl ? 1 : 0;
-        c[0] += inl ? 1.0 : 0.0;
-    }
-    block_sum<1>(c, red);
-    if (first) {
-        const int cnt = (int)c[0];
-        int status = ctl[0];
-        if (status == kEssOk && cnt < kEssS) status = kEssDegenerate;
+    double pay[kEssPayload];
+    const TwoViewVerdict vd = twoview_verdict<EssVerdict>(P2, e, (size_t)b, n, n_slices, thr, confidence, slots, out.mask, nullptr, oi, pay);
+    if (threadIdx.x == 0) {
         // (DEGENERATE still reports the count, h, root and mask of its best hypothesis; only the matrix is withheld)
-        oi[0] = cnt; oi[1] = ctl[1]; oi[2] = status;
-        oi[3] = (ctl[1] >= 0 && (double)cnt / (double)n >= confidence) ? 1 : 0;
-        oi[4] = ctl[2];
+        const int status = vd.status == kEssOk && vd.aux < 0 ? kEssDegenerate : vd.status;
+        oi[2] = status; oi[4] = vd.aux;
         double Eu[9];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) Eu[k] = sE[k];
+        for (int k = 0; k < 9; ++k) Eu[k] = pay[9 + k];
         fund_unit(Eu);
 #pragma unroll
         for (int k = 0; k < 9; ++k) out.E[9 * (size_t)e + k] = status == kEssOk ? Eu[k] : 0.0;

@@ -385,12 +385,10 @@ int check_samples(sfmba_handle* h, const int32_t* samples, size_t batch, size_t 
     return 0;
 }
 
-// What sfmba_fundamental_ransac (S = 8 positions a sample) and sfmba_homography_ransac (S = 4) do alike before their finish
-// kernels: options, the batch onto the device, the slices, slots / counts / samples buffers, the caller's samples
-// checked and uploaded, the LDS opt-in, and the launch of the RANSAC kernel (the two have one signature; `score` is its threshold argument).
-using TwoViewRansacKernel = void (*)(FundIn, int, int, int, unsigned long long, double, double*, int*);
+// What sfmba_fundamental_ransac (S = 8 positions a sample), sfmba_homography_ransac (S = 4) and sfmba_essential_ransac (S = 5)
+// do alike before their kernels: options, the batch onto the device, the slices, slots / counts / samples buffers, the
+// caller's samples checked and uploaded, the LDS opt-in of the RANSAC kernel.
 struct TwoViewRansac {
-    TwoViewRansacKernel kern = nullptr;          // null (the essential call): `finish` launches both kernels
     size_t slot_doubles = kTwoViewSlot;          // of a slot of the RANSAC kernel
     size_t hyp_arrays = 1;                       // per-hypothesis integer arrays [n_edges][H] in twoview.hyp, one behind the other
     sfmba_ransac_options o;
@@ -401,7 +399,7 @@ struct TwoViewRansac {
 };
 
 // (E = 0 on return: the batch has no edge and nothing was launched)
-int twoview_ransac_begin(sfmba_handle* h, const char* who, TwoViewRansacKernel kern, const void* lds_kernel, int S, int64_t n_edges, const int64_t* edge_ptr, const double* pts1,
+int twoview_ransac_begin(sfmba_handle* h, const char* who, const void* lds_kernel, int S, int64_t n_edges, const int64_t* edge_ptr, const double* pts1,
                          const double* pts2, const uint8_t* pair_use, const int32_t* samples, const sfmba_ransac_options* opt,
                          bool hyp, int64_t* n_ok, double* kernel_us, TwoViewRansac* c) {
     if (opt) c->o = *opt; else sfmba_default_ransac_options(&c->o);
@@ -427,17 +425,17 @@ int twoview_ransac_begin(sfmba_handle* h, const char* who, TwoViewRansacKernel k
     }
     // the kernel's static LDS (about 8 KiB, above the 2 KiB that set_lds assumes) counts: opted in whatever this call stages
     CHK(opt_in_lds(h, lds_kernel, sizeof(double) * 4 * kTwoViewLdsPairs));
-    c->kern = kern;
     c->in = FundIn{t.pairs.as<double>(), t.uptr.as<int>(), samples ? t.samples.as<int>() : nullptr};
     c->E = E;
     return 0;
 }
 
-int launch_twoview_ransac(sfmba_handle* h, const TwoViewRansac& c, double score, bool hyp) {
-    auto& t = h->twoview;
+// a model's RANSAC kernel over the (edge, slice) grid: the arguments the kernels begin with alike, then the model's `own`
+template <class Kern, class... Own>
+int launch_twoview_ransac(sfmba_handle* h, const TwoViewRansac& c, Kern kern, double score, Own... own) {
     const size_t lds = sizeof(double) * 4 * (size_t)std::min(c.bt.max_n, kTwoViewLdsPairs);
-    hipLaunchKernelGGL(c.kern, dim3((unsigned)(c.E * (size_t)c.n_slices)), dim3(kTwoViewThreads), lds, h->stream, c.in, (int)c.H, c.hs,
-                       c.n_slices, (unsigned long long)c.o.seed, score, t.slots.as<double>(), hyp ? t.hyp.as<int>() : nullptr);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(c.E * (size_t)c.n_slices)), dim3(kTwoViewThreads), lds, h->stream, c.in, (int)c.H, c.hs,
+                       c.n_slices, (unsigned long long)c.o.seed, score, own...);
     LAUNCHED(h);
     return 0;
 }
@@ -455,12 +453,12 @@ struct TwoViewResults {
     int32_t* hyp2 = nullptr;                     // the second per-hypothesis array of a call with two
 };
 
-// What the two calls do alike after twoview_ransac_begin: the result buffers (twoview.F the model and its refit,
-// twoview.mask n_masks masks, twoview.ints n_ints integers per edge), the RANSAC launch and `finish` (the model's finish
-// kernel on these buffers) between the event pair, the downloads, the masks scattered, the integers handed out.
-template <class Finish>
+// What the three calls do alike after twoview_ransac_begin: the result buffers (twoview.F the model and its refit,
+// twoview.mask n_masks masks, twoview.ints n_ints integers per edge), `launch` (the model's RANSAC and finish kernels on
+// these buffers) between the event pair, the downloads, the masks scattered, the integers handed out.
+template <class Launch>
 int twoview_ransac_end(sfmba_handle* h, const TwoViewRansac& c, double score, size_t n_ints, size_t n_masks, int ok_status,
-                       const TwoViewResults& r, Finish finish) {
+                       const TwoViewResults& r, Launch launch) {
     if (c.E == 0) return wait_stream(h);
     auto& t = h->twoview;
     const TwoViewBatch& bt = c.bt;
@@ -468,9 +466,7 @@ int twoview_ransac_end(sfmba_handle* h, const TwoViewRansac& c, double score, si
     CHK(ensure_all(h, {{&t.F, sizeof(double) * 18 * E}, {&t.ints, sizeof(int) * n_ints * E}, {&t.mask, n_masks * std::max<size_t>(Mu, 1)}}));
     EventPair timer;
     CHK(timer.start(h, c.o.profile != 0));
-    if (c.kern) CHK(launch_twoview_ransac(h, c, score, r.hyp != nullptr));
-    finish(t.F.as<double>(), t.mask.as<unsigned char>(), t.ints.as<int>(), score);
-    LAUNCHED(h);
+    CHK(launch(t.F.as<double>(), t.mask.as<unsigned char>(), t.ints.as<int>(), score));
     CHK(timer.stop(h));
     // the per-edge integers always come (n_ok); the masks through the staging when they have to be scattered
     const size_t off_mask = sizeof(int) * n_ints * E;
@@ -668,13 +664,17 @@ int sfmba_fundamental_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* ed
                              uint8_t* edge_success, int32_t* edge_status, int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us) {
     CHK(enter(h));
     TwoViewRansac c;
-    CHK(twoview_ransac_begin(h, "sfmba_fundamental_ransac", k_fund_ransac, reinterpret_cast<const void*>(k_fund_ransac), 8, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
+    CHK(twoview_ransac_begin(h, "sfmba_fundamental_ransac", reinterpret_cast<const void*>(k_fund_ransac), 8, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
                              hyp_inliers != nullptr, n_ok, kernel_us, &c));
     const TwoViewResults r{F, F_refit, {inlier_mask, nullptr}, edge_inliers, edge_best, edge_status, edge_success, nullptr, hyp_inliers,
                            n_ok, kernel_us};
     return twoview_ransac_end(h, c, c.o.threshold, 4, 1, kFundOk, r, [&](double* M, unsigned char* mask, int* ints, double score) {
+        auto& t = h->twoview;
+        CHK(launch_twoview_ransac(h, c, k_fund_ransac, score, t.slots.as<double>(), hyp_inliers ? t.hyp.as<int>() : nullptr));
         hipLaunchKernelGGL(k_fund_finish, dim3((unsigned)c.E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, score, c.o.confidence,
-                           c.o.refit != 0 ? 1 : 0, (const double*)h->twoview.slots.as<double>(), FundOut{M, M + 9 * c.E, mask, ints});
+                           c.o.refit != 0 ? 1 : 0, (const double*)t.slots.as<double>(), FundOut{M, M + 9 * c.E, mask, ints});
+        LAUNCHED(h);
+        return 0;
     });
 }
 
@@ -687,14 +687,17 @@ int sfmba_homography_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edg
                             int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us) {
     CHK(enter(h));
     TwoViewRansac c;
-    CHK(twoview_ransac_begin(h, "sfmba_homography_ransac", k_homog_ransac, reinterpret_cast<const void*>(k_homog_ransac), 4, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
+    CHK(twoview_ransac_begin(h, "sfmba_homography_ransac", reinterpret_cast<const void*>(k_homog_ransac), 4, n_edges, edge_ptr, pts1, pts2, pair_use, samples, opt,
                              hyp_inliers != nullptr, n_ok, kernel_us, &c));
     const TwoViewResults r{Hm, H_refit, {inlier_mask, refit_mask}, edge_inliers, edge_best, edge_status, edge_success, edge_refit_inliers,
                            hyp_inliers, n_ok, kernel_us};
     return twoview_ransac_end(h, c, c.o.threshold * c.o.threshold, 5, 2, kHomogOk, r, [&](double* M, unsigned char* mask, int* ints, double score) {
+        auto& t = h->twoview;
+        CHK(launch_twoview_ransac(h, c, k_homog_ransac, score, t.slots.as<double>(), hyp_inliers ? t.hyp.as<int>() : nullptr));
         hipLaunchKernelGGL(k_homog_finish, dim3((unsigned)c.E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, score, c.o.confidence,
-                           c.o.refit != 0 ? 1 : 0, (const double*)h->twoview.slots.as<double>(),
-                           HomogOut{M, M + 9 * c.E, mask, mask + c.bt.Mu, ints});
+                           c.o.refit != 0 ? 1 : 0, (const double*)t.slots.as<double>(), HomogOut{M, M + 9 * c.E, mask, mask + c.bt.Mu, ints});
+        LAUNCHED(h);
+        return 0;
     });
 }
 
@@ -717,19 +720,18 @@ int sfmba_essential_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edge
     c.slot_doubles = kEssSlot;
     c.hyp_arrays = 2;
     const bool hyp = hyp_inliers != nullptr || hyp_roots != nullptr;
-    CHK(twoview_ransac_begin(h, "sfmba_essential_ransac", nullptr, reinterpret_cast<const void*>(k_ess_ransac), kEssS, n_edges, edge_ptr,
+    CHK(twoview_ransac_begin(h, "sfmba_essential_ransac", reinterpret_cast<const void*>(k_ess_ransac), kEssS, n_edges, edge_ptr,
                              pts1, pts2, pair_use, samples, opt, hyp, n_ok, kernel_us, &c));
     const TwoViewResults r{E_out, nullptr, {inlier_mask, nullptr}, edge_inliers, edge_best, edge_status, edge_success, edge_best_root,
                            hyp_inliers, n_ok, kernel_us, hyp_roots};
     return twoview_ransac_end(h, c, c.o.threshold, 5, 1, kEssOk, r, [&](double* M, unsigned char* mask, int* ints, double score) {
         auto& t = h->twoview;
         int* const hy = hyp ? t.hyp.as<int>() : nullptr;
-        const size_t lds = sizeof(double) * 4 * (size_t)std::min(c.bt.max_n, kTwoViewLdsPairs);
-        hipLaunchKernelGGL(k_ess_ransac, dim3((unsigned)(c.E * (size_t)c.n_slices)), dim3(kTwoViewThreads), lds, h->stream, c.in, (int)c.H,
-                           c.hs, c.n_slices, (unsigned long long)c.o.seed, score, Ki, t.slots.as<double>(), hy,
-                           hy ? hy + c.E * c.H : nullptr);
+        CHK(launch_twoview_ransac(h, c, k_ess_ransac, score, Ki, t.slots.as<double>(), hy, hy ? hy + c.E * c.H : nullptr));
         hipLaunchKernelGGL(k_ess_finish, dim3((unsigned)c.E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, score, c.o.confidence,
                            (const double*)t.slots.as<double>(), EssOut{M, mask, ints});
+        LAUNCHED(h);
+        return 0;
     });
 }
 

@@ -23,6 +23,7 @@ import pytest
 import essential_ref as er
 import two_view_ref as tv
 from conftest import ROOT
+from kernel_source import kernel_constant
 
 pytestmark = pytest.mark.gpu
 
@@ -165,6 +166,37 @@ def test_statuses_repeated_samples_and_degenerate_input(be):
         assert w.hyp_inliers[e].tobytes() == many.hyp_inliers[0].tobytes() and w.hyp_roots[e].tobytes() == many.hyp_roots[0].tobytes()
         assert w.E[e].tobytes() == many.E[0].tobytes() and w.best[e] == many.best[0] and w.best_root[e] == many.best_root[0]
         assert w.inlier_mask[40 * e:40 * e + 40].tobytes() == many.inlier_mask.tobytes()
+
+
+def test_hypothesis_counts_and_the_choice_between_slots(be):
+    """Equal counts planted in two waves of one slice, in a later slice and in the last slot: the lowest h wins, and what
+    it returns is what that sample returns alone.  One edge of 40 noise-free pairs, ten of them outliers; the planted
+    sample is five clean pairs (the restatement: 4 real roots, 30 inliers), every other hypothesis a sample with an
+    outlier (7 inliers)."""
+    minslice = kernel_constant("kTwoViewMinSlice")
+    H = 8 * minslice + 1                                         # nine slices of a one-edge batch on any grid
+    rng = np.random.default_rng(2713)
+    a, b, _, _, _, bad = er.scene(rng, 40, K, "general", noise=0.0, outliers=0.25)
+    clean, dirty = np.flatnonzero(~bad), np.flatnonzero(bad)
+    planted, filler = clean[:5].astype(np.int32), np.concatenate([clean[5:9], dirty[:1]]).astype(np.int32)
+    ref = er.ransac_edge(a, b, K, np.stack([planted, filler]), er.THRESHOLD, margin=er.MARGIN)
+    assert ref["roots"][0] > 0 and ref["hyp"][0] > ref["hyp"][1] >= 0 and not ref["near"].any()    # (else nothing below is a test)
+    alone = be.essential_ransac(a, b, K, samples=planted[None, None], threshold=er.THRESHOLD, want_hyp=True)
+    assert alone.status[0] == alone.OK and alone.hyp_inliers[0, 0] == ref["hyp"][0] and alone.best_root[0] >= 0
+
+    def run(at):
+        smp = np.tile(filler, (H, 1))
+        smp[at] = planted
+        est = be.essential_ransac(a, b, K, samples=smp[None], threshold=er.THRESHOLD, want_hyp=True)
+        assert np.all(est.hyp_inliers[0][at] == ref["hyp"][0]) and np.all(np.delete(est.hyp_inliers[0], at) == ref["hyp"][1])
+        assert np.all(est.hyp_roots[0][at] == alone.hyp_roots[0, 0])
+        for name in ("E", "best_root", "inlier_mask", "inliers", "status", "success"):
+            assert getattr(est, name).tobytes() == getattr(alone, name).tobytes(), (name, at)
+        return est
+
+    # h = 13 is met by an earlier wave of its slice than h = 10
+    assert run([13, 10, 5 * minslice + 2, H - 1]).best[0] == 10
+    assert run([H - 1]).best[0] == H - 1
 
 
 def test_mask_batch_and_repeat_give_the_same_bits(be):

@@ -1,5 +1,5 @@
 """Bit identity of the consumers (reprojection statistics, triangulation, resection, and the two-view calls -- F, homography,
-pose -- and the robust resection where both builds have them) between two builds of the library.  Usage: python tools/ab_consumer_bits.py LIB_A LIB_B [--out DIR]
+essential, pose -- and the robust resection where both builds have them) between two builds of the library.  Usage: python tools/ab_consumer_bits.py LIB_A LIB_B [--out DIR]
 
 One fresh child process per library (SFMBA_LIB), each under its own time limit; the tool stops at the first child that
 does not exit cleanly.  A child runs the three calls over inputs that reach every form of the kernels -- the long-run,
@@ -96,7 +96,18 @@ def child(out_path):
                 est = be.homography_ransac(p1, p2, edge_ptr=ptr, threshold=1.0, refit=1, want_hyp=True, **kw)
                 for f in ("H", "H_refit", "inlier_mask", "refit_mask", "inliers", "refit_inliers", "best", "success", "status", "hyp_inliers"):
                     out[f"two_view/64/homography/{tag}/{f}"] = getattr(est, f)
-        Es =np.stack([tv.essential_from_pose(m[2], m[3]) for m in made])
+        if hasattr(be._lib, "sfmba_essential_ransac"):    # the same batch behind an edge of 4 pairs (FEW_PAIRS for five-pair samples)
+            import essential_ref as er
+            few = tv.make_pairs(rng, 4, K, noise=0.3)
+            eptr = np.concatenate([[0], 4 + ptr]).astype(np.int64)
+            e1, e2, euse = np.concatenate([few[0], p1]), np.concatenate([few[1], p2]), np.concatenate([np.ones(4, dtype=bool), use])
+            sizes = np.diff(eptr)
+            smp5 = np.stack([er.draw_samples5(3, e, 40, int(n)) if n >= 5 else np.zeros((40, 5), dtype=np.int32) for e, n in enumerate(sizes)])
+            for tag, kw in (("drawn", dict(max_iters=40, seed=3)), ("masked", dict(max_iters=40, seed=3, pair_use=euse)), ("given", dict(samples=smp5))):
+                est = be.essential_ransac(e1, e2, K, edge_ptr=eptr, threshold=1.0, want_hyp=True, **kw)
+                for f in ("E", "inlier_mask", "inliers", "best", "best_root", "success", "status", "hyp_inliers", "hyp_roots"):
+                    out[f"two_view/64/essential/{tag}/{f}"] = getattr(est, f)
+        Es = np.stack([tv.essential_from_pose(m[2], m[3]) for m in made])
         Es[1] = 0.0
         for tag, kw in (("all", {}), ("masked", dict(pair_use=use)), ("deep", dict(min_depth=6.0))):
             pose = be.recover_pose(Es, p1, p2, K, edge_ptr=ptr, **kw)
