@@ -187,7 +187,8 @@ int64_t sfmba_p2p_calls(const sfmba_handle* h);      /* collectives served by th
  * transport).  Differences around a solve give launches / collectives per outer iteration (bench.py). */
 int  sfmba_get_counters(const sfmba_handle* h, int64_t* kernel_launches, int64_t* collectives);
 /* Which kernel form the current problem runs (the problem stage of the forms table): value = 0 / 1 for name =
- * "lds_tab", "lds_vec", "sweep_rc", "sweep_rc_g", "pcg_fused", "mixed", "jfree", "rc_cons", "dense", "cam_multi" (some
+ * "lds_tab", "lds_vec", "sweep_rc", "sweep_rc_g", "pcg_fused", "mixed", "mixed_b" (pass B reads the fp32 point records
+ * too), "jfree", "rc_cons", "dense", "cam_multi" (some
  * camera has several chunks: k_cam_combine runs), "xcd_b" (pass B over the XCD-aware table), "rhsrec" (the rhs pass
  * gathers the 128-byte records), "round_blocks"; and of the solve stage, as the next compute call decides it from the
  * transport and the options of that moment: "xcd_cam" (K3 and the rhs pass one wave per chunk), "own_inverse" (the rhs
@@ -855,10 +856,20 @@ int  sfmba_step_products(sfmba_handle* h, const double* x, const double* sg, con
  *     sd_c   = +sum_{i in c} W_i Vinv_p(i) W_i^T   (21 per camera: upper triangle, row-major),
  *     minv_c = (U_c + diag(dc_c) - sd_c)^-1        (21 per camera: upper triangle, row-major; the values the PCG reads).
  * x: 6C+3P.  rhs_out: 6C, sd_out and minv_out: 21C, camera by camera.  A camera without observations has rhs = sd = 0.
- * Single rank, 64-bit storage, Schur-diagonal preconditioner (the default).  Leaves the handle as the other entries
+ * Single rank, Schur-diagonal preconditioner (the default); 64-bit storage, or 32-bit storage with a recomputing pass A
+ * (form "round_blocks" 0: the pass then reads nothing rounded but the pixels, as float32 values, behind g_p; with the
+ * stored fp32 Jacobian it rounds its blocks and the call returns -1).  Leaves the handle as the other entries
  * of this group do: a solve afterwards is the solve without the call. */
 int  sfmba_rhs_precond(sfmba_handle* h, const double* x, const double* dc, const double* dp, double* rhs_out,
                        double* sd_out, double* minv_out);
+
+/* The fp32 operands of the mixed-precision Schur product (debug option "pcg_mixed"; the default with 32-bit storage) as
+ * they stand after the last sfmba_schur_matvec: origin (3) the point the coordinates are rounded relative to,
+ * rt32 (12 C floats: R row-major | T - origin per camera), rec32 (8 P floats per point: X - origin | z of the last
+ * pass A | two unused floats; the z slots of a point without observations are never written), rtd (12 C doubles: the
+ * values of rt32 as pass B reads them).  Any output may be NULL.  Returns -1 when the problem does not run the mixed
+ * form (sfmba_get_form(h, "mixed")).  Copies only: launches nothing and changes nothing on the handle. */
+int  sfmba_get_mixed_operands(sfmba_handle* h, double* origin, float* rt32, float* rec32, double* rtd);
 
 /* Few-camera path (6 n_cameras <= 128, the reference's own problem sizes): at x, with the diagonals dc (6C) and dp
  * (3P), form S = U + diag(dc) - W (V + diag(dp))^-1 W^T (S_out: (6C)^2 row-major, may be NULL) and solve S y = rhs

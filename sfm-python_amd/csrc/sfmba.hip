@@ -1288,7 +1288,7 @@ int sfmba_get_form(sfmba_handle* h, const char* name, int32_t* value) {
     const Forms& f = h->forms;
     const struct { const char* name; int value; } forms[] = {
         {"lds_tab", f.lds_tab}, {"lds_vec", f.lds_vec}, {"sweep_rc", f.sweep_rc}, {"sweep_rc_g", f.sweep_rc_g},
-        {"pcg_fused", f.pcg_fused}, {"mixed", f.mixed}, {"jfree", f.jfree}, {"rc_cons", f.rc_cons}, {"dense", f.dense},
+        {"pcg_fused", f.pcg_fused}, {"mixed", f.mixed}, {"mixed_b", f.mixed_b}, {"jfree", f.jfree}, {"rc_cons", f.rc_cons}, {"dense", f.dense},
         {"cam_multi", f.cam_multi}, {"xcd_b", f.xcd_b}, {"rhsrec", f.use_rhsrec}, {"round_blocks", f.round_blocks},
         {"xcd_cam", f.xcd_cam}, {"own_inverse", f.own_inverse},
     };
@@ -1999,7 +1999,8 @@ int sfmba_rhs_precond(sfmba_handle* h, const double* x, const double* dc, const 
     CHK(enter(h));
     CHK(begin_compute(h, x));
     if (!dc || !dp || !rhs_out || !sd_out || !minv_out) return fail(h, -1, "NULL argument");
-    if (h->f32) return fail(h, -1, "sfmba_rhs_precond returns the sums as formed from 64-bit blocks: 64-bit storage only");
+    // (32-bit storage with a recomputing pass A: the pass forms its blocks in fp64 from the camera table and the fp64 point
+    // records and reads nothing rounded but the pixels behind g_p; with the stored Jacobian it rounds them: refused below)
     if (!h->forms.one_rank) return fail(h, -1, "sfmba_rhs_precond is a single-rank entry");
     if (!h->forms.precond) return fail(h, -1, "sfmba_rhs_precond needs the Schur-diagonal preconditioner (debug option precond)");
     if (h->forms.round_blocks) return fail(h, -1, "sfmba_rhs_precond: blocks rounded to fp32 are not the blocks its header states");
@@ -2023,6 +2024,19 @@ int sfmba_rhs_precond(sfmba_handle* h, const double* x, const double* dc, const 
         for (int k = 0; k < 21; ++k) { sd_out[21 * c + k] = a[(6 + k) * C + c]; minv_out[21 * c + k] = m[k * C + c]; }
     }
     HIPCHK(h, hipMemsetAsync(h->acc(), 0, sizeof(double) * 6 * C, h->stream));
+    return 0;
+}
+
+int sfmba_get_mixed_operands(sfmba_handle* h, double* origin, float* rt32, float* rec32, double* rtd) {
+    CHK(enter(h));
+    if (!h->have_problem) return fail(h, -1, "sfmba_set_problem has not been called");
+    if (!h->forms.mixed) return fail(h, -1, "sfmba_get_mixed_operands: the problem does not run the mixed-precision product (form \"mixed\")");
+    const size_t C = (size_t)h->C, P = (size_t)h->P;
+    if (rt32) HIPCHK(h, hipMemcpyAsync(rt32, h->rt32.p, sizeof(float) * kRt32 * C, hipMemcpyDeviceToHost, h->stream));
+    if (rec32) HIPCHK(h, hipMemcpyAsync(rec32, h->rec32.p, sizeof(float) * kRec32 * P, hipMemcpyDeviceToHost, h->stream));
+    if (rtd) HIPCHK(h, hipMemcpyAsync(rtd, h->rtd.p, sizeof(double) * kRt32 * C, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (origin) { origin[0] = h->origin.x; origin[1] = h->origin.y; origin[2] = h->origin.z; }
     return 0;
 }
 

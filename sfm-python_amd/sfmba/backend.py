@@ -1245,6 +1245,19 @@ class Backend:
                                                 _capi.ptr(sd), _capi.ptr(minv)))
         return rhs, sd, minv
 
+    def mixed_operands(self):
+        """The fp32 operands of the mixed-precision Schur product as the last `schur_matvec` left them (include/sfmba.h:
+        sfmba_get_mixed_operands) -> dict(origin (3), rt32 (C, 12) float32, rec32 (P, 8) float32, rtd (C, 12) float64).
+        Raises ValueError when the problem does not run the mixed form."""
+        self._flush_pending()
+        origin = np.empty(3)
+        rt32 = np.empty((self.n_cameras, 12), dtype=np.float32)
+        rec32 = np.empty((self.n_points, 8), dtype=np.float32)
+        rtd = np.empty((self.n_cameras, 12))
+        self._check(self._lib.sfmba_get_mixed_operands(self._h, _capi.ptr(origin), _capi.ptr(rt32), _capi.ptr(rec32),
+                                                       _capi.ptr(rtd)))
+        return {"origin": origin, "rt32": rt32, "rec32": rec32, "rtd": rtd}
+
     def dense_schur(self, x, dc, dp, rhs):
         """(S, y): the formed reduced camera matrix and the solution of S y = rhs by the in-LDS PCG run to the end."""
         self._flush_pending()

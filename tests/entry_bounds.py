@@ -289,7 +289,7 @@ class Linearisation:
             ER[:, i, i] = Ra[:, i, i] + (k_b + 5) * b * (w[:, i] ** 2 + th2)
         k_R = k_b + 6
         Ra = np.maximum(Ra, ER / k_R[:, None, None])         # (an entry that vanishes where a does keeps a's error)
-        self.b, self.c, self.ca, self.k_b, self.k_c, self.R = b, c, ca, k_b, k_c, R
+        self.b, self.c, self.ca, self.k_b, self.k_c, self.R, self.Ra, self.k_R = b, c, ca, k_b, k_c, R, Ra, k_R
         uv = np.asarray(uv, dtype=np.float64).reshape(-1, 2).astype(LD)
         # ---- one observation ----
         Rn, Ran = R[ci], Ra[ci]

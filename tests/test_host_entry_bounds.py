@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import entry_bounds as eb
+import entry_bounds32 as e32
 
 pytestmark = pytest.mark.skipif(not eb.extended_precision(), reason="numpy.longdouble is no wider than a double on this machine")
 
@@ -145,6 +146,210 @@ def test_fp32_rounding_of_the_smallest_entries_is_rejected_entry_by_entry_and_ac
         print(f"{q}: {int(small.sum())} entries rounded to fp32: err/bound {worst:.3g}, normwise {eb.rel_max(spoilt, np.asarray(ref, dtype=np.float64)):.3g}")
         assert worst > 1.0, q                                                          # the per-entry check rejects it
         assert eb.rel_max(spoilt, np.asarray(ref, dtype=np.float64)) < normwise, q     # test_gpu_parity.py's check accepts it
+
+
+# ---- fp32 storage and the mixed-precision product (tests/entry_bounds32.py, test_gpu_entries32.py) -----------------------------
+def _host_fetch(orc, name, cases=None):
+    """What test_gpu_entries32.py fetches from the device, emulated for a case: the operands rounded from x, V of the
+    longdouble blocks as doubles, the blocks of the fp64 oracle at the pixels the storage mode holds."""
+    args, x, lin, st, (dc, dp, v), options, forms, bits = e32.case(name, orc, cases)
+    ops = e32.operands_from_x(lin, x, v)
+    uv = np.asarray(args[4], dtype=np.float64)
+    if bits == 32:
+        uv = uv.astype(np.float32).astype(np.float64)
+    r, Jc, Jp = orc.jacobian_blocks(x, args[0], args[1], args[2], args[3], uv, args[5])
+    V = np.asarray(lin.blocks(st)["V"], dtype=np.float64)
+    return args, x, lin, st, (dc, dp, v), forms, ops, V, (r, Jc, Jp)
+
+
+@pytest.mark.parametrize("name", list(e32.MIXED_CASES))
+def test_mixed_cases_tie_entries_and_the_fp64_oracle(orc, name):
+    """Every array of every mixed case: tie entries within TIE_CAP (none in the emulated a', which is not fetched); the
+    same operand roundings followed by plain double arithmetic lie inside every bound, and y meets SHARE / LEVEL_Y."""
+    args, x, lin, st, (dc, dp, v), forms, ops, V, (_, _, Jp) = _host_fetch(orc, name)
+    assert not ops["a_tie"].any(), name
+    rt32 = e32.fl32(ops["rt"])
+    ok, tie_rt = e32.accepted32(rt32, ops["rt"], ops["rt_bnd"])
+    assert ok.all() and np.array_equal(rt32[:, 9:], ops["T32"]), name
+    mixed_b = forms["mixed_b"] == 1
+    kw = dict(mixed_b=mixed_b, a32=ops["a32"], uT32=ops["uT32"])
+    ref = e32.mixed_product(lin, st, args[5], dc, dp, v, rt32, ops["X32"], V, **kw)
+    o64 = e32.mixed_product(lin, st, args[5], dc, dp, v, rt32, ops["X32"], V, dt=np.float64, rows64=Jp, **kw)
+    seen, A, B = lin.Lp > 0, ref["a"], ref["b"]
+    bz = eb.bound(A["k_z"], A["za"])
+    ok, tie_z = e32.accepted32(e32.fl32(o64["a"]["z"])[seen], A["z"][seen], bz[seen])
+    assert ok.all(), name
+    assert eb.ratio(o64["a"]["z"][seen], A["z"][seen], bz[seen]) <= 1.0, name
+    by = eb.bound(B["k_y"], B["ya"])
+    q, s = eb.ratio(o64["b"]["y"], B["y"], by), eb.share_below(by, B["y"], eb.LEVEL_Y)
+    print(f"{name}: tie share rt32 {tie_rt.mean():.2e}, z32 {tie_z.mean():.2e}; fp64 oracle err/bound of y {q:.3f}, share below "
+          f"{eb.LEVEL_Y:g} |ref| {s:.4f} (k_z {A['k_z'].min():.0f}..{A['k_z'].max():.0f}, k_y {B['k_y'].min():.0f}..{B['k_y'].max():.0f})")
+    assert tie_rt.mean() <= e32.TIE_CAP and tie_z.mean() <= e32.TIE_CAP, name
+    assert q <= 1.0 and s >= eb.SHARE, (name, q, s)
+
+
+@pytest.mark.parametrize("name", list(eb.K1_CASES))
+def test_k1_fp32_stores_tie_entries_and_the_fp64_oracle(orc, name):
+    problem, _, _ = eb.K1_CASES[name]
+    args, x = eb.problem(problem, orc)
+    lin = e32.linearisation32(problem, orc, 32)
+    uv32 = np.asarray(args[4], dtype=np.float64).astype(np.float32).astype(np.float64)
+    o = dict(zip(("r", "Jc", "Jp"), orc.jacobian_blocks(x, args[0], args[1], args[2], args[3], uv32, args[5])))
+    for what, ref, k, A in (("r", lin.r, lin.k_r, lin.ra), ("Jc", lin.Jc, lin.k_jc, lin.Jca), ("Jp", lin.Jp, lin.k_jp, lin.Jpa)):
+        ok, tie = e32.accepted32(e32.fl32(o[what].reshape(ref.shape)), ref, eb.bound(k, A))
+        print(f"{name}: {what} tie share {tie.mean():.2e} ({int(tie.sum())} of {tie.size})")
+        assert ok.all() and tie.mean() <= e32.TIE_CAP, (name, what, tie.mean())
+
+
+@pytest.mark.parametrize("name", list(eb.RHS_CASES))
+def test_rhs_cases_at_the_pixels_of_fp32_storage(orc, name):
+    problem, options, _ = eb.RHS_CASES[name]
+    lin, st = e32.linearisation32(problem, orc, 32), eb.structure(problem, orc, options)
+    dc, dp, _ = eb.operands(lin, st)
+    ref = lin.rhs_pass(st, dc, dp)
+    _share(name, "rhs", ref["rhs"], ref["k_rhs"], ref["rhsa"])
+    _share(name, "sd", eb.upper(ref["sd"]), ref["k_sd"], eb.upper(ref["sda"]))
+    _share(name, "minv", eb.upper(ref["minv"]), ref["k_minv"], eb.upper(ref["minva"]), share=eb.SHARE_MINV)
+
+
+@pytest.mark.parametrize("name", list(e32.STORED_CASES))
+def test_stored_fp32_jacobian_cases(orc, name):
+    args, x, lin, st, (dc, dp, v), forms, ops, V, (_, Jc, Jp) = _host_fetch(orc, name, e32.STORED_CASES)
+    Jc32, Jp32 = Jc.astype(np.float32), Jp.astype(np.float32)
+    ref = e32.stored_product(lin, st, Jc32, Jp32, V, dc, dp, v)
+    o64 = e32.stored_product(lin, st, Jc32, Jp32, V, dc, dp, v, dt=np.float64)
+    by = eb.bound(ref["k_y"], ref["ya"])
+    q, s = eb.ratio(o64["y"], ref["y"], by), eb.share_below(by, ref["y"], eb.LEVEL_Y)
+    print(f"{name}: fp64 oracle err/bound of y {q:.3f}, share below {eb.LEVEL_Y:g} |ref| {s:.4f}")
+    assert q <= 1.0 and s >= eb.SHARE, (name, q, s)
+
+
+def test_pass_b_in_its_own_form_is_the_schur_product(orc):
+    """entry_bounds32.pass_b fed with the fp64 quantities of x is entry_bounds' schur_product: value and abs-value evaluation."""
+    st, lin = eb.structure("hand_built", orc, {}), eb.linearisation("hand_built", orc)
+    dc, dp, v = eb.operands(lin, st)
+    s, pv = lin.schur_product(st, dc, dp, v, "rc"), lin.point_inverses(st, dp)
+    vc = v.reshape(lin.C, 6).astype(eb.LD)
+    ap, apa, k_ap = lin._a_prime(vc)
+    yp = np.zeros((lin.P, 3), dtype=eb.LD)
+    np.add.at(yp, lin.pi, np.einsum("nki,nk->ni", lin.Jp, np.einsum("nki,ni->nk", lin.Jc, vc[lin.ci])))
+    z = np.einsum("pij,pj->pi", pv["Vinv"], yp)
+    B = e32.pass_b(lin, st, lin.Jp, lin.Jps, lin.ka_jp, lin.v, lin.va, 1, ap, apa, k_ap, vc[:, 3:], z, np.abs(z), 0.0, dc, v)
+    assert np.abs(np.asarray(B["y"] - s["y"], dtype=np.float64)).max() <= 1e-16 * float(np.abs(s["y"]).max())
+    assert np.all(B["k_y"] <= s["k_y"]) and np.all(B["ya"] <= s["ya"] * (1 + 1e-15))
+
+
+def test_planted_errors_are_rejected_entry_by_entry_and_accepted_by_the_normwise_window(orc):
+    """What the 1e-13 < rel < 1e-6 window of test_mixed_precision_schur_product (and the 1e-6 of test_fp32_storage_mode)
+    cannot tell from the contract "fp32 operands, fp64 arithmetic", planted into the fp64 oracle's values of the
+    hand-built case: each is rejected by the check of test_gpu_entries32.py and accepted by the window it replaces."""
+    args, x, lin, st, (dc, dp, v), forms, ops, V, (_, Jc, _) = _host_fetch(orc, "default")
+    K, F32 = args[5], np.float32
+    rt32 = e32.fl32(ops["rt"])
+    exact = eb.linearisation("hand_built", orc).schur_product(st, dc, dp, v, "rc")["y"]       # the old test's reference: fp64, x
+
+    def window(y, ref=exact):
+        return 1e-13 < eb.rel_max(np.asarray(y, dtype=np.float64), np.asarray(ref, dtype=np.float64)) < 1e-6
+
+    def product(dt, **kw):
+        a = dict(mixed_b=True, a32=ops["a32"], uT32=ops["uT32"], rt32=rt32, dc=dc)
+        a.update(kw)
+        rt, d = a.pop("rt32"), a.pop("dc")
+        return e32.mixed_product(lin, st, K, d, dp, v, rt, ops["X32"], V, dt=dt, **a)
+
+    clean = product(np.float64)
+    z32 = e32.fl32(clean["a"]["z"])
+    ref = product(eb.LD, z32=z32)
+    B = ref["b"]
+    by = eb.bound(B["k_y"], B["ya"])
+    assert eb.ratio(clean["b"]["y"], B["y"], by) <= 1.0 and window(clean["b"]["y"])
+    seen, A = lin.Lp > 0, ref["a"]
+    bz = eb.bound(A["k_z"], A["za"])
+    assert e32.accepted32(z32[seen], A["z"][seen], bz[seen])[0].all()
+
+    # 1. one product of pass B formed in fp32: s0 += u_k j_0 of one observation
+    u, j = clean["b"]["u"], clean["rows"].j
+    n = int(np.flatnonzero(lin.ci == int(np.argmax(lin.Lc)))[0])
+    c = int(lin.ci[n])
+    spoilt = np.array(clean["b"]["y"], dtype=np.float64)
+    spoilt[c, 3] -= float(F32(u[n, 0] * j[n, 0, 0])) - u[n, 0] * j[n, 0, 0]
+    assert spoilt[c, 3] != clean["b"]["y"][c, 3]
+    q = eb.ratio(spoilt, B["y"], by)
+    print(f"one fp32 product in pass B: err/bound {q:.3g}")
+    assert q > 1.0 and window(spoilt)
+
+    # 2. z rounded twice
+    z2 = (z32.astype(np.float64) * (1 + 2.0 ** -24)).astype(F32)
+    ok = e32.accepted32(z2[seen], A["z"][seen], bz[seen])[0]
+    print(f"z rounded twice: {int((~ok).sum())} of {ok.size} entries of z32 rejected")
+    assert not ok.all() and window(product(np.float64, z32=z2)["b"]["y"])
+
+    # 3. T rounded absolutely instead of relative to the origin (the unshifted scene)
+    T = x[:6 * lin.C].reshape(lin.C, 6)[:, 3:]
+    rt_abs = rt32.copy()
+    rt_abs[:, 9:] = (T.astype(F32).astype(np.float64) - ops["origin"]).astype(F32)
+    ok = e32.accepted32(rt_abs, ops["rt"], ops["rt_bnd"])[0]
+    print(f"T rounded absolutely: {int((~ok).sum())} of {3 * lin.C} entries of T - o rejected")
+    assert not ok.all() and window(product(np.float64, rt32=rt_abs)["b"]["y"])
+
+    # 4. the smallest hundredth of the stored Jc entries one ulp32 off
+    lin32 = e32.linearisation32("hand_built", orc, 32)
+    stored = Jc.astype(F32)
+    mag = np.abs(stored)
+    small = (mag > 0) & (mag <= np.quantile(mag[mag > 0], 0.01))
+    off = np.where(small, np.nextafter(stored, F32(np.inf)), stored)
+    bj = eb.bound(lin32.k_jc, lin32.Jca)
+    assert e32.accepted32(stored, lin32.Jc, bj)[0].all()
+    ok = e32.accepted32(off, lin32.Jc, bj)[0]
+    print(f"stored Jc one ulp32 off: {int((~ok).sum())} of {int(small.sum())} perturbed entries rejected")
+    assert (~ok).sum() == small.sum() and eb.rel_max(off.astype(np.float64), Jc) < 1e-6
+
+    # 5. one observation of a camera's last chunk dropped -- on a product whose largest entry belongs to ANOTHER camera (one
+    # strongly damped camera, as a trust-region step with one poorly scaled camera has it): the window is blind to the rest
+    c = int(np.argmax(lin.Lc))
+    last = int(np.flatnonzero(lin.ci == c)[-1])
+    rows = np.abs(np.asarray(exact, dtype=np.float64)).max(axis=1)
+    rows[c] = 0.0
+    other = int(np.argmax(rows))
+    dcs = np.array(dc, dtype=np.float64).reshape(lin.C, 6)
+    dcs[other] *= 1e5
+    exact_s = eb.linearisation("hand_built", orc).schur_product(st, dcs.ravel(), dp, v, "rc")["y"]
+    full, dropped = product(eb.LD, z32=z32, dc=dcs), product(np.float64, z32=z32, dc=dcs, drop=last)
+    Bs = full["b"]
+    q = eb.ratio(dropped["b"]["y"], Bs["y"], eb.bound(Bs["k_y"], Bs["ya"]))
+    print(f"one observation of camera {c} dropped: err/bound {q:.3g}, normwise "
+          f"{eb.rel_max(np.asarray(dropped['b']['y'], dtype=np.float64), np.asarray(exact_s, dtype=np.float64)):.3g}")
+    assert q > 1.0 and window(dropped["b"]["y"], exact_s)
+
+
+def test_origin_replica_arguments():
+    """The Python replica of upload_x's origin: the sample's stride, and a non-finite point in the sample gives 0."""
+    C, P = 2, 10
+    x = np.arange(6 * C + 3 * P, dtype=np.float64)
+    pts = x[6 * C:].reshape(P, 3)
+    assert np.array_equal(e32.origin_of(x, C, P), np.array([sum(pts[:, k].tolist()) / P for k in range(3)]))
+    for bad in (np.inf, -np.inf, np.nan):
+        y = x.copy()
+        y[6 * C + 3 * 4 + 1] = bad
+        assert np.array_equal(e32.origin_of(y, C, P), np.zeros(3))
+    P = 2500                                                 # stride 2: the odd points are not read
+    x = np.concatenate([np.zeros(6 * C), np.random.default_rng(0).normal(size=3 * P)])
+    y = x.copy()
+    y[6 * C + 3::6] = np.nan
+    o = e32.origin_of(x, C, P)
+    assert np.array_equal(e32.origin_of(y, C, P), o) and np.allclose(o, x[6 * C:].reshape(P, 3)[::2].mean(axis=0), atol=1e-14)
+    assert np.array_equal(e32.origin_of(np.zeros(6 * C), C, 0), np.zeros(3))
+
+
+def test_fl32_interval_reports_the_tie_entries():
+    one, up = np.float32(1.0), np.nextafter(np.float32(1.0), np.float32(2.0))
+    mid = (eb.LD(one) + eb.LD(up)) / 2
+    ref = np.array([eb.LD(1.0), mid * (1 - eb.LD(1e-12)), mid * (1 + eb.LD(1e-12)), mid * (1 - eb.LD(1e-9))])
+    lo, hi, tie = e32.fl32_interval(ref, np.full(4, 1e-11))
+    assert tie.tolist() == [False, True, True, False] and lo.tolist() == [one, one, one, one] and hi.tolist() == [one, up, up, one]
+    ok, _ = e32.accepted32(np.array([1.0, float(up), 1.0, float(up)]), ref, np.full(4, 1e-11))
+    assert ok.tolist() == [True, True, True, False]
+    assert not e32.accepted32(np.array([1.0 + 1e-12]), ref[:1], np.full(1, 1e-11))[0][0]      # not a float32 value
 
 
 def test_relative_error_the_entry_check_lets_through(orc):
