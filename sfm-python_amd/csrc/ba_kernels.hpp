@@ -712,52 +712,37 @@ __host__ __device__ constexpr size_t cam_slots_k3(int world, int C) { return (si
 __host__ __device__ constexpr size_t cam_slots_rhs(int world, int C) { return cam_slots_k3(world, C) + (size_t)world * 27 * C; }
 __host__ __device__ constexpr size_t cam_slots_total(int world, int C) { return cam_slots_rhs(world, C) + (size_t)world * 27 * C; }
 
-// K3: U_c = sum Jc^T Jc (21, packed upper triangle), g_c = sum Jc^T r (6) of one camera chunk.
-// A camera with a single chunk stores straight into Ugc[c][27]; otherwise the chunk's 27 sums go to
-// partial[chunk][27] and k_cam_combine adds them.
-template <bool F32>
-__global__ __launch_bounds__(kCamThreads) void k_cam_blocks(CamMajor cm, const double* __restrict__ camtab,
-                                                            const double* __restrict__ rec, KMat K,
-                                                            double* __restrict__ Ugc, double* __restrict__ partial,
-                                                            const double* __restrict__ skip, int n_chunks,
-                                                            const int* __restrict__ pt_idx, int N, PointBlocksOut pb,
-                                                            Piggyback fin, Mailbox mb, CamExchange cx) {
-    __shared__ double red[kCamWaves][27];
-    // One more rider (fin.part != null: the FIRST workgroup of the grid): the sum of the cost partials the residual
-    // launch in front of this one left, and the hand-off post behind it -- k_finish's work without its launch; the host
-    // has the trial cost while this launch is still building the blocks it speculates on.
-    const int bid = (int)blockIdx.x - (fin.part != nullptr ? 1 : 0);        // (the FIRST workgroup: dispatched at once)
-    if (bid < 0) {
-        if (!(skip != nullptr && *skip != 0.0)) { finish_in_block(fin); __syncthreads(); }
-        if (mb.host != nullptr && threadIdx.x < 64) post_mailbox(mb);      // (also when the trial was cancelled)
-        return;
-    }
-    if (skip != nullptr && *skip != 0.0) return;   // speculative launch cancelled by k_tr_step
-    if (bid >= n_chunks) {                         // riders: the point rows K1's tiles cut (see k_resjac)
-        point_edge_fixup((bid - n_chunks) * kCamThreads + (int)threadIdx.x, pt_idx, N, pb);
-        return;
-    }
-    const int4 ch = cm.chunks[bid];
-    double t[kCamTab];
-#pragma unroll
-    for (int k = 0; k < kCamTab; ++k) t[k] = camtab[(size_t)ch.x * kCamRow + k];      // wave-uniform: scalar loads
-    double a[27];
-#pragma unroll
-    for (int q = 0; q < 27; ++q) a[q] = 0.0;
-    // kU observations per lane and trip, all index loads first, then all gathers (kU = 2 here: with 27 sums in
-    // registers a deeper unroll pushes the kernel past 128 VGPRs, i.e. below four workgroups per CU, and 1000
-    // camera workgroups then take two rounds)
+// The rider of a K3 launch in its FIRST workgroup (fin.part != null; bid < 0 there), for both forms of the kernel: the sum
+// of the cost partials the residual launch in front of this one left, and the hand-off post behind it -- k_finish's work
+// without its launch; the host has the trial cost while this launch is still building the blocks it speculates on.
+// (The tests that pick the riders stay in the kernels, each with its own return: merged into one returned flag, the
+// riders' stores lay on a path to the chunk-record load of the wave form, which then was no scalar load any more.)
+__device__ __forceinline__ void cam_blocks_first_rider(const double* __restrict__ skip, const Piggyback& fin, const Mailbox& mb) {
+    if (!(skip != nullptr && *skip != 0.0)) { finish_in_block(fin); __syncthreads(); }
+    if (mb.host != nullptr && threadIdx.x < 64) post_mailbox(mb);          // (also when the trial was cancelled)
+}
+
+// The observation loop of K3: a[0..20] += Jc^T Jc (packed upper triangle), a[21..26] += Jc^T r over the observations
+// first, first + STRIDE, ... < end of one camera (row t), the blocks recomputed from the gathered point.
+// kU observations per lane and trip, all index loads first, then all gathers (kU = 2 here: with 27 sums in
+// registers a deeper unroll pushes the kernel past 128 VGPRs, i.e. below four workgroups per CU, and 1000
+// camera workgroups then take two rounds).  The chunk's bounds come by value and the arrays as plain pointers: handed
+// over as references to the chunk record, the wave-uniform scalar loads of the wave form turned into vector loads.
+template <bool F32, int STRIDE>
+__device__ __forceinline__ void cam_blocks_sweep(const int* __restrict__ pt, const double* __restrict__ uvs,
+                                                 const double* __restrict__ rec, const KMat& K, const double* __restrict__ t,
+                                                 int first, int end, double (&a)[27]) {
     constexpr int kU = 2;
-    for (int k0 = ch.y + (int)threadIdx.x; k0 < ch.z; k0 += kCamThreads * kU) {
+    for (int k0 = first; k0 < end; k0 += STRIDE * kU) {
         int p[kU];
         double2 uv[kU];
         double X[kU][3];
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-            const int k = k0 + u * kCamThreads;
+            const int k = k0 + u * STRIDE;
             p[u] = -1;
             uv[u] = make_double2(0.0, 0.0);
-            if (k < ch.z) { p[u] = cm.pt[k]; uv[u] = load_pair(cm.uv, F32, k); }
+            if (k < end) { p[u] = pt[k]; uv[u] = load_pair(uvs, F32, k); }
         }
 #pragma unroll
         for (int u = 0; u < kU; ++u) {                    // two 16-byte loads of the point's record: X Y | Z .
@@ -779,6 +764,34 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_blocks(CamMajor cm, const d
             for (int i = 0; i < 6; ++i) a[21 + i] += jc[i] * rx + jc[6 + i] * ry;
         }
     }
+}
+
+// K3: U_c = sum Jc^T Jc (21, packed upper triangle), g_c = sum Jc^T r (6) of one camera chunk.
+// A camera with a single chunk stores straight into Ugc[c][27]; otherwise the chunk's 27 sums go to
+// partial[chunk][27] and k_cam_combine adds them.
+template <bool F32>
+__global__ __launch_bounds__(kCamThreads) void k_cam_blocks(CamMajor cm, const double* __restrict__ camtab,
+                                                            const double* __restrict__ rec, KMat K,
+                                                            double* __restrict__ Ugc, double* __restrict__ partial,
+                                                            const double* __restrict__ skip, int n_chunks,
+                                                            const int* __restrict__ pt_idx, int N, PointBlocksOut pb,
+                                                            Piggyback fin, Mailbox mb, CamExchange cx) {
+    __shared__ double red[kCamWaves][27];
+    const int bid = (int)blockIdx.x - (fin.part != nullptr ? 1 : 0);        // (the FIRST workgroup: dispatched at once)
+    if (bid < 0) { cam_blocks_first_rider(skip, fin, mb); return; }
+    if (skip != nullptr && *skip != 0.0) return;   // speculative launch cancelled by k_tr_step
+    if (bid >= n_chunks) {                         // riders: the point rows K1's tiles cut (see k_resjac)
+        point_edge_fixup((bid - n_chunks) * kCamThreads + (int)threadIdx.x, pt_idx, N, pb);
+        return;
+    }
+    const int4 ch = cm.chunks[bid];
+    double t[kCamTab];
+#pragma unroll
+    for (int k = 0; k < kCamTab; ++k) t[k] = camtab[(size_t)ch.x * kCamRow + k];      // wave-uniform: scalar loads
+    double a[27];
+#pragma unroll
+    for (int q = 0; q < 27; ++q) a[q] = 0.0;
+    cam_blocks_sweep<F32, kCamThreads>(cm.pt, cm.uv, rec, K, t, ch.y + (int)threadIdx.x, ch.z, a);
     double s = cam_block_total<27>(a, red);
     if (threadIdx.x < 27) {
         if (cx.world > 1) s = cam_exchange_value(cx, cam_slots_k3(cx.world, cx.C), 27, threadIdx.x, cx.C, ch.x, s, 3u);
@@ -802,11 +815,7 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_blocks_w(CamMajor cm, const
                                                               const int* __restrict__ pt_idx, int N, PointBlocksOut pb,
                                                               Piggyback fin, Mailbox mb) {
     const int bid = (int)blockIdx.x - (fin.part != nullptr ? 1 : 0);        // (the FIRST workgroup: dispatched at once)
-    if (bid < 0) {
-        if (!(skip != nullptr && *skip != 0.0)) { finish_in_block(fin); __syncthreads(); }
-        if (mb.host != nullptr && threadIdx.x < 64) post_mailbox(mb);      // (also when the trial was cancelled)
-        return;
-    }
+    if (bid < 0) { cam_blocks_first_rider(skip, fin, mb); return; }
     if (skip != nullptr && *skip != 0.0) return;   // speculative launch cancelled by k_tr_step
     if (bid >= n_wgs) {                            // riders: the point rows K1's tiles cut (see k_resjac)
         point_edge_fixup((bid - n_wgs) * kCamThreads + (int)threadIdx.x, pt_idx, N, pb);
@@ -822,38 +831,7 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_blocks_w(CamMajor cm, const
     double a[27];
 #pragma unroll
     for (int n = 0; n < 27; ++n) a[n] = 0.0;
-    constexpr int kU = 2;
-    for (int k0 = ch.y + lane; k0 < ch.z; k0 += 64 * kU) {
-        int p[kU];
-        double2 uv[kU];
-        double X[kU][3];
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const int k = k0 + u * 64;
-            p[u] = -1;
-            uv[u] = make_double2(0.0, 0.0);
-            if (k < ch.z) { p[u] = cm.pt[k]; uv[u] = load_pair(cm.uv, F32, k); }
-        }
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const double2* __restrict__ rp = reinterpret_cast<const double2*>(rec + (size_t)kRec * (p[u] < 0 ? 0 : p[u]));
-            const double2 xy = rp[0], zz = rp[1];
-            X[u][0] = xy.x; X[u][1] = xy.y; X[u][2] = zz.x;
-        }
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            if (p[u] < 0) continue;
-            double jc[12], jp[6], rx, ry;
-            observe<true>(t, X[u][0], X[u][1], X[u][2], uv[u].x, uv[u].y, K, rx, ry, jc, jp);
-            int n = 0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i)
-#pragma unroll
-                for (int j = i; j < 6; ++j) a[n++] += jc[i] * jc[j] + jc[6 + i] * jc[6 + j];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) a[21 + i] += jc[i] * rx + jc[6 + i] * ry;
-        }
-    }
+    cam_blocks_sweep<F32, 64>(cm.pt, cm.uv, rec, K, t, ch.y + lane, ch.z, a);
     const int col = wave_fold_sum<27>(a, lane);
     if (col >= 0) partial[(size_t)q * 27 + col] = a[0];
 }
@@ -1837,6 +1815,14 @@ __device__ __forceinline__ void kr_rows(const double (&M)[9], double vx, double 
         j[3 * k + 2] = (M[3 * k + 2] - pk * M[8]) * iz;
     }
 }
+// a' = u_w - b (w x u_w) + c (w x (w x u_w)): the rotation part u_w of a camera vector carried through the transposed
+// right Jacobian, once per camera instead of once per observation.  ONE expression for the fp32 tables of pass A
+// and the prologues of pass B; rc_put_au (whose text k_backsub_rc's schedule depends on) must agree with it term by term.
+__device__ __forceinline__ void cam_aprime(double wx, double wy, double wz, double b, double c, const double* u, double* ap) {
+    const double c0 = wy * u[2] - wz * u[1], c1 = wz * u[0] - wx * u[2], c2 = wx * u[1] - wy * u[0];   // w x u_w
+    const double d0 = wy * c2 - wz * c1, d1 = wz * c0 - wx * c2, d2 = wx * c1 - wy * c0;               // w x (w x u_w)
+    ap[0] = u[0] - b * c0 + c * d0; ap[1] = u[1] - b * c1 + c * d1; ap[2] = u[2] - b * c2 + c * d2;
+}
 // The table prologue of the row-form kernels in two halves.  w, b, c of a camera depend on nothing the launch computes:
 // a kernel whose vector u is only known behind a block reduction (the PCG step in the prologue of the fused pass A, the
 // FinalUpdate of k_backsub_rc) requests them BEFORE it, next to the loads of the reduction itself, and only FMAs and LDS
@@ -1847,7 +1833,7 @@ __device__ __forceinline__ RcWbc rc_load_wbc(const double* __restrict__ wbc, int
 }
 // a' and u_T of camera `cam` from its six entries u, into the camera's row of the table
 __device__ __forceinline__ void rc_put_au(const RcWbc& q, int cam, const double* u, double* __restrict__ tab) {
-    const double wx = q.wx, wy = q.wy, wz = q.wz, b = q.b, cc = q.cc;
+    const double wx = q.wx, wy = q.wy, wz = q.wz, b = q.b, cc = q.cc;                                   // (must agree with cam_aprime)
     const double c0 = wy * u[2] - wz * u[1], c1 = wz * u[0] - wx * u[2], c2 = wx * u[1] - wy * u[0];   // w x u_w
     const double d0 = wy * c2 - wz * c1, d1 = wz * c0 - wx * c2, d2 = wx * c1 - wy * c0;               // w x (w x u_w)
     double* __restrict__ row = tab + (size_t)kRcRow * cam;
@@ -1921,12 +1907,9 @@ __global__ __launch_bounds__(256) void k_rc_table32(const double* __restrict__ c
     double u[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) u[k] = u_planes[(size_t)k * C + cam];
-    const double wx = wbc[cam], wy = wbc[(size_t)C + cam], wz = wbc[2 * (size_t)C + cam];
-    const double b = wbc[3 * (size_t)C + cam], cc = wbc[4 * (size_t)C + cam];
-    const double c0 = wy * u[2] - wz * u[1], c1 = wz * u[0] - wx * u[2], c2 = wx * u[1] - wy * u[0];   // w x u_w
-    const double d0 = wy * c2 - wz * c1, d1 = wz * c0 - wx * c2, d2 = wx * c1 - wy * c0;               // w x (w x u_w)
-    row[3] = make_float4((float)(u[0] - b * c0 + cc * d0), (float)(u[1] - b * c1 + cc * d1), (float)(u[2] - b * c2 + cc * d2),
-                         (float)u[3]);
+    double ap[3];
+    cam_aprime(wbc[cam], wbc[(size_t)C + cam], wbc[2 * (size_t)C + cam], wbc[3 * (size_t)C + cam], wbc[4 * (size_t)C + cam], u, ap);
+    row[3] = make_float4((float)ap[0], (float)ap[1], (float)ap[2], (float)u[3]);
     row[4] = make_float4((float)u[4], (float)u[5], 0.f, 0.f);
 }
 // five LDS-DMA pieces per 80-byte row (rows_request with the fp32 table)
@@ -2124,13 +2107,10 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep_rc32(
     if (s + 2 < s_end) nn = st.steps[s + 2];
     const double* __restrict__ wbc = camtab + cam_wbc_offset(C);                  // w, b, c plane-major [5][C]
     auto put_au = [&](int cam, const double* u) {          // a' and u_T of camera `cam` from its u (6), rounded to fp32
-        const double wx = wbc[cam], wy = wbc[(size_t)C + cam], wz = wbc[2 * (size_t)C + cam];
-        const double b = wbc[3 * (size_t)C + cam], cc = wbc[4 * (size_t)C + cam];
-        const double c0 = wy * u[2] - wz * u[1], c1 = wz * u[0] - wx * u[2], c2 = wx * u[1] - wy * u[0];   // w x u_w
-        const double d0 = wy * c2 - wz * c1, d1 = wz * c0 - wx * c2, d2 = wx * c1 - wy * c0;               // w x (w x u_w)
+        double ap[3];
+        cam_aprime(wbc[cam], wbc[(size_t)C + cam], wbc[2 * (size_t)C + cam], wbc[3 * (size_t)C + cam], wbc[4 * (size_t)C + cam], u, ap);
         float4* __restrict__ row = reinterpret_cast<float4*>(smem + (size_t)kRc32Row * cam);
-        row[3] = make_float4((float)(u[0] - b * c0 + cc * d0), (float)(u[1] - b * c1 + cc * d1),
-                             (float)(u[2] - b * c2 + cc * d2), (float)u[3]);
+        row[3] = make_float4((float)ap[0], (float)ap[1], (float)ap[2], (float)u[3]);
         row[4] = make_float4((float)u[4], (float)u[5], 0.f, 0.f);
     };
     if (FUSED) {
@@ -2168,6 +2148,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep_rc32(
     float* const slab = smem + (size_t)(threadIdx.x >> 6) * kRow32SlabFloats;
 
     // y contribution of one observation from its camera row (five 16-byte pieces) and its point X - o
+    // (the rows j0 j1 j2 must agree term by term with the MIXED rows of k_cam_schur and k_cam_schur_w, pass B of the same product)
     auto contrib = [&](const float4* __restrict__ row, float X, float Y, float Z, double* y) {
         const float4 f0 = row[0], f1 = row[1], f2 = row[2], f3 = row[3], f4 = row[4];
         const double R0 = f0.x, R1 = f0.y, R2 = f0.z, R3 = f0.w, R4 = f1.x, R5 = f1.y, R6 = f1.z, R7 = f1.w, R8 = f2.x;
@@ -2377,6 +2358,41 @@ struct PcgLocal {
 // MIXED (MODE 0, exact-block form): the operands of the mixed-precision product -- R, T - o, a', u_T rounded to fp32
 // exactly as pass A's table holds them, the point and z from its 32-byte fp32 record (`rec` then points at rec32).
 struct MixedB { const double* __restrict__ rtd; };      // [C][12] = R | T - o, fp32 values held as doubles
+
+// The recomputed blocks of one observation as fp32 storage holds them (pass A applied the STORED blocks): d r/d w and
+// d r/d X rounded to float, d r/d T = -d r/d X rebuilt from the rounded entries.  ONE expression for pass B on stored
+// blocks and both forms of the rhs pass.
+__device__ __forceinline__ void round_blocks_as_stored(double* __restrict__ jc, double* __restrict__ jp) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { jc[q] = (double)(float)jc[q]; jc[6 + q] = (double)(float)jc[6 + q]; }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) jp[q] = (double)(float)jp[q];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { jc[3 + q] = -jp[q]; jc[9 + q] = -jp[3 + q]; }
+}
+// Exact blocks, one observation: with the rows j, v = X - T and h (= z, or z + v x a' + v_T) the two residual-space
+// values are u_k = -j_k . h;  q = sum_k u_k j_k;  a[0..2] += q x v,  a[3..5] += q.
+__device__ __forceinline__ void cam_exact_accumulate(const double* __restrict__ j, double vx, double vy, double vz,
+                                                     double h0, double h1, double h2, double (&a)[6]) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;             // q = sum_k u_k j_k
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double j0 = j[3 * k], j1 = j[3 * k + 1], j2 = j[3 * k + 2];
+        const double uk = -(j0 * h0 + j1 * h1 + j2 * h2);
+        s0 += uk * j0; s1 += uk * j1; s2 += uk * j2;
+    }
+    a[0] += s1 * vz - s2 * vy; a[1] += s2 * vx - s0 * vz; a[2] += s0 * vy - s1 * vx;       // q x v
+    a[3] += s0; a[4] += s1; a[5] += s2;
+}
+// r = -(M - b (M x w) + c ((M x w) x w)): the rotation Jacobian applied ONCE to the summed M = sum q x v (it is linear
+// in M) instead of per observation; t = the camera's row (w at 12, b, c at 15, 16)
+__device__ __forceinline__ void cam_rotate_back(const double* __restrict__ t, const double* __restrict__ m, double* __restrict__ r) {
+    const double wx = t[12], wy = t[13], wz = t[14];
+    const double m0 = m[0], m1 = m[1], m2 = m[2];
+    const double c0 = m1 * wz - m2 * wy, c1 = m2 * wx - m0 * wz, c2 = m0 * wy - m1 * wx;          // M x w
+    const double d0 = c1 * wz - c2 * wy, d1 = c2 * wx - c0 * wz, d2 = c0 * wy - c1 * wx;          // (M x w) x w
+    r[0] = -(m0 - t[15] * c0 + t[16] * d0); r[1] = -(m1 - t[15] * c1 + t[16] * d1); r[2] = -(m2 - t[15] * c2 + t[16] * d2);
+}
 template <int MODE, bool ROUND, bool MIXED = false>
 __global__ __launch_bounds__(kCamThreads) void k_cam_schur(CamMajor cm, const double* __restrict__ camtab,
                                                            const double* __restrict__ rec, KMat K,
@@ -2407,12 +2423,7 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur(CamMajor cm, const do
     // -- the rotation Jacobian is applied ONCE per workgroup to the summed M instead of per observation (it is
     // linear in M): ~100 flop per observation instead of ~200.  a[0..2] = sum q x v, a[3..5] = sum q.
     double ap[3] = {0.0, 0.0, 0.0};
-    if (MODE == 0 && !ROUND) {
-        const double wx = t[12], wy = t[13], wz = t[14];
-        const double c0 = wy * vc[2] - wz * vc[1], c1 = wz * vc[0] - wx * vc[2], c2 = wx * vc[1] - wy * vc[0];
-        const double d0 = wy * c2 - wz * c1, d1 = wz * c0 - wx * c2, d2 = wx * c1 - wy * c0;
-        ap[0] = vc[0] - t[15] * c0 + t[16] * d0; ap[1] = vc[1] - t[15] * c1 + t[16] * d1; ap[2] = vc[2] - t[15] * c2 + t[16] * d2;
-    }
+    if (MODE == 0 && !ROUND) cam_aprime(t[12], t[13], t[14], t[15], t[16], vc, ap);
     double vT[3] = {vc[3], vc[4], vc[5]};                  // the translation part of the camera vector as the sweep uses it
     if (MIXED) {
 #pragma unroll
@@ -2428,6 +2439,12 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur(CamMajor cm, const do
         for (int k = 0; k < 9; ++k) Mk[k] = camtab[cam_mt_offset(C) + (size_t)ch.x * kCamRT + k];      // wave-uniform: scalar loads
     }
     double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // The loop is written here and in k_cam_schur_w, each from the shared pieces (kr_rows, round_blocks_as_stored,
+    // cam_exact_accumulate): as ONE helper over the stride it cost both wave kernels and the mixed form of this one one to
+    // two VGPRs, and the record load as a helper turned the exec-masked gathers into clamped ones.  The MIXED rows
+    // (q = R v, p = K q, b, j = b R) stay written out here, in k_cam_schur_w and in `contrib` of k_point_sweep_rc32 and
+    // must agree term by term: as a helper they cost k_cam_schur_w<true> six more scalar spills and this kernel's scalar
+    // loads their widths.
     for (int k0 = ch.y + (int)threadIdx.x; k0 < ch.z; k0 += kCamThreads * kCamUnroll) {      // see k_cam_blocks
         int p[kCamUnroll];
         double X[kCamUnroll][3], z[kCamUnroll][3];
@@ -2457,12 +2474,7 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur(CamMajor cm, const do
             if (ROUND) {
                 double jc[12], jp[6], rx, ry;
                 observe<true>(t, X[u][0], X[u][1], X[u][2], 0.0, 0.0, K, rx, ry, jc, jp);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) { jc[q] = (double)(float)jc[q]; jc[6 + q] = (double)(float)jc[6 + q]; }
-#pragma unroll
-                for (int q = 0; q < 6; ++q) jp[q] = (double)(float)jp[q];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) { jc[3 + q] = -jp[q]; jc[9 + q] = -jp[3 + q]; }
+                round_blocks_as_stored(jc, jp);
                 double u0 = -(jp[0] * z[u][0] + jp[1] * z[u][1] + jp[2] * z[u][2]);
                 double u1 = -(jp[3] * z[u][0] + jp[4] * z[u][1] + jp[5] * z[u][2]);
                 if (MODE == 0) {
@@ -2501,15 +2513,7 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur(CamMajor cm, const do
                     h1 += vz * ap[0] - vx * ap[2] + vT[1];
                     h2 += vx * ap[1] - vy * ap[0] + vT[2];
                 }
-                double s0 = 0.0, s1 = 0.0, s2 = 0.0;             // q = sum_k u_k j_k
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const double j0 = j[3 * k], j1 = j[3 * k + 1], j2 = j[3 * k + 2];
-                    const double uk = -(j0 * h0 + j1 * h1 + j2 * h2);
-                    s0 += uk * j0; s1 += uk * j1; s2 += uk * j2;
-                }
-                a[0] += s1 * vz - s2 * vy; a[1] += s2 * vx - s0 * vz; a[2] += s0 * vy - s1 * vx;       // q x v
-                a[3] += s0; a[4] += s1; a[5] += s2;
+                cam_exact_accumulate(j, vx, vy, vz, h0, h1, h2, a);
             }
         }
     }
@@ -2538,13 +2542,9 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur(CamMajor cm, const do
         if (threadIdx.x < 6) tot[threadIdx.x] = s;
         __syncthreads();
         if (threadIdx.x < 3) {
-            const double wx = t[12], wy = t[13], wz = t[14];
-            const double m0 = tot[0], m1 = tot[1], m2 = tot[2];
-            const double c0 = m1 * wz - m2 * wy, c1 = m2 * wx - m0 * wz, c2 = m0 * wy - m1 * wx;          // M x w
-            const double d0 = c1 * wz - c2 * wy, d1 = c2 * wx - c0 * wz, d2 = c0 * wy - c1 * wx;          // (M x w) x w
-            const double r0 = -(m0 - t[15] * c0 + t[16] * d0), r1 = -(m1 - t[15] * c1 + t[16] * d1),
-                         r2 = -(m2 - t[15] * c2 + t[16] * d2);
-            out = threadIdx.x == 0 ? r0 : (threadIdx.x == 1 ? r1 : r2);
+            double r[3];
+            cam_rotate_back(t, tot, r);
+            out = threadIdx.x == 0 ? r[0] : (threadIdx.x == 1 ? r[1] : r[2]);
         } else if (threadIdx.x < 6) {
             out = -tot[threadIdx.x];
         }
@@ -2617,12 +2617,7 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur_w(CamMajor cm, const 
 #pragma unroll
     for (int k = 0; k < 6; ++k) vc[k] = vin[(size_t)k * C + ch.x];
     double ap[3];
-    {
-        const double wx = t[12], wy = t[13], wz = t[14];
-        const double c0 = wy * vc[2] - wz * vc[1], c1 = wz * vc[0] - wx * vc[2], c2 = wx * vc[1] - wy * vc[0];
-        const double d0 = wy * c2 - wz * c1, d1 = wz * c0 - wx * c2, d2 = wx * c1 - wy * c0;
-        ap[0] = vc[0] - t[15] * c0 + t[16] * d0; ap[1] = vc[1] - t[15] * c1 + t[16] * d1; ap[2] = vc[2] - t[15] * c2 + t[16] * d2;
-    }
+    cam_aprime(t[12], t[13], t[14], t[15], t[16], vc, ap);
     double vT[3] = {vc[3], vc[4], vc[5]};
     if (MIXED) {
 #pragma unroll
@@ -2646,13 +2641,13 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur_w(CamMajor cm, const 
         }
 #pragma unroll
         for (int u = 0; u < kCamUnroll; ++u) {
-            if (MIXED) {
+            if (MIXED) {                                  // the point's fp32 record: X Y Z z0 | z1 z2, one 32-byte sector
                 const float* __restrict__ rp = reinterpret_cast<const float*>(rec) + (size_t)kRec32 * (p[u] < 0 ? 0 : p[u]);
                 const float4 r0 = *reinterpret_cast<const float4*>(rp);
                 const float2 r1 = *reinterpret_cast<const float2*>(rp + 4);
                 X[u][0] = r0.x; X[u][1] = r0.y; X[u][2] = r0.z;
                 z[u][0] = r0.w; z[u][1] = r1.x; z[u][2] = r1.y;
-            } else {
+            } else {                                      // the point's record: X Y | Z z0 | z1 z2, three 16-byte loads
                 const double2* __restrict__ rp = reinterpret_cast<const double2*>(rec + (size_t)kRec * (p[u] < 0 ? 0 : p[u]));
                 const double2 r0 = rp[0], r1 = rp[1], r2 = rp[2];
                 X[u][0] = r0.x; X[u][1] = r0.y; X[u][2] = r1.x;
@@ -2666,7 +2661,7 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur_w(CamMajor cm, const 
             double j[6];
             if (!MIXED) {
                 kr_rows(Mk, vx, vy, vz, j);
-            } else {
+            } else {                                      // (as in k_cam_schur: must agree term by term)
                 const double qx = t[0] * vx + t[1] * vy + t[2] * vz;
                 const double qy = t[3] * vx + t[4] * vy + t[5] * vz;
                 const double qz = t[6] * vx + t[7] * vy + t[8] * vz;
@@ -2685,30 +2680,19 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_schur_w(CamMajor cm, const 
                     j[3 * k + 2] = b0 * t[2] + b1 * t[5] + b2 * t[8];
                 }
             }
+            // (h summed term by term onto z; k_cam_schur adds z to (v x a' + v_T): each form keeps the bits it has always had)
             const double h0 = z[u][0] + vy * ap[2] - vz * ap[1] + vT[0];
             const double h1 = z[u][1] + vz * ap[0] - vx * ap[2] + vT[1];
             const double h2 = z[u][2] + vx * ap[1] - vy * ap[0] + vT[2];
-            double s0 = 0.0, s1 = 0.0, s2 = 0.0;             // q = sum_k u_k j_k
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const double j0 = j[3 * k], j1 = j[3 * k + 1], j2 = j[3 * k + 2];
-                const double uk = -(j0 * h0 + j1 * h1 + j2 * h2);
-                s0 += uk * j0; s1 += uk * j1; s2 += uk * j2;
-            }
-            a[0] += s1 * vz - s2 * vy; a[1] += s2 * vx - s0 * vz; a[2] += s0 * vy - s1 * vx;       // q x v
-            a[3] += s0; a[4] += s1; a[5] += s2;
+            cam_exact_accumulate(j, vx, vy, vz, h0, h1, h2, a);
         }
     }
 #pragma unroll
     for (int k = 0; k < 6; ++k) a[k] = wave_sum(a[k]);        // on every lane
     if (lane < 6) {
-        const double wx = t[12], wy = t[13], wz = t[14];
-        const double m0 = a[0], m1 = a[1], m2 = a[2];
-        const double c0 = m1 * wz - m2 * wy, c1 = m2 * wx - m0 * wz, c2 = m0 * wy - m1 * wx;          // M x w
-        const double d0 = c1 * wz - c2 * wy, d1 = c2 * wx - c0 * wz, d2 = c0 * wy - c1 * wx;          // (M x w) x w
-        const double r0 = -(m0 - t[15] * c0 + t[16] * d0), r1 = -(m1 - t[15] * c1 + t[16] * d1),
-                     r2 = -(m2 - t[15] * c2 + t[16] * d2);
-        const double out = lane == 0 ? r0 : (lane == 1 ? r1 : (lane == 2 ? r2 : (lane == 3 ? -a[3] : (lane == 4 ? -a[4] : -a[5]))));
+        double r[3];
+        cam_rotate_back(t, a, r);
+        const double out = lane == 0 ? r[0] : (lane == 1 ? r[1] : (lane == 2 ? r[2] : (lane == 3 ? -a[3] : (lane == 4 ? -a[4] : -a[5]))));
         partial[(size_t)q * 6 + lane] = out;
     }
 }
@@ -2750,6 +2734,83 @@ struct RhsPrecond {
     const double* __restrict__ Dc;
     double* __restrict__ Minv;
 };
+// What the rhs pass gathers for point pidx (< 0: point 0, never used): X, e and the packed Vinv -- one 128-byte record
+// per observation (kRhsRec) when k_prep has written them (rhsrec != null), else the two gathers
+__device__ __forceinline__ void rhs_gather(const double* __restrict__ rhsrec, const double* __restrict__ rec,
+                                           const double* __restrict__ Vinv, int pidx, double* Xo, double* eo, double* vo) {
+    const size_t pp = (size_t)(pidx < 0 ? 0 : pidx);
+    const double2* __restrict__ rp = reinterpret_cast<const double2*>(rhsrec != nullptr ? rhsrec + kRhsRec * pp : rec + kRec * pp);
+    const double2* __restrict__ vp = rhsrec != nullptr ? rp + 4 : reinterpret_cast<const double2*>(Vinv + kVinvRow * pp);
+    const double2 r0 = rp[0], r1 = rp[1], r2 = rp[2], v0 = vp[0], v1 = vp[1], v2 = vp[2];
+    Xo[0] = r0.x; Xo[1] = r0.y; Xo[2] = r1.x;
+    eo[0] = r1.y; eo[1] = r2.x; eo[2] = r2.y;
+    vo[0] = v0.x; vo[1] = v0.y; vo[2] = v1.x; vo[3] = v1.y; vo[4] = v2.x; vo[5] = v2.y;
+}
+// One observation of the rhs pass: a[0..5] -= W e, a[6..26] += W Vinv W^T (packed upper).  W = Jc^T Jp has rank two (the
+// two residual rows), so neither W nor W Vinv is formed:
+//     -W e          = -Jc^T (Jp e)
+//     W Vinv W^T    = Jc^T G Jc,   G = Jp Vinv Jp^T  (2 x 2, symmetric)
+// 111 multiply-adds per observation instead of 171, and no 6 x 3 temporaries in registers
+__device__ __forceinline__ void rhs_accumulate(const double* __restrict__ jc, const double* __restrict__ jp,
+                                               const double* __restrict__ e, const double* __restrict__ vi, double (&a)[27]) {
+    const double s0 = jp[0] * e[0] + jp[1] * e[1] + jp[2] * e[2];
+    const double s1 = jp[3] * e[0] + jp[4] * e[1] + jp[5] * e[2];
+    const double h00 = vi[0] * jp[0] + vi[1] * jp[1] + vi[2] * jp[2];      // Vinv jp_0 (Vinv packed upper)
+    const double h01 = vi[1] * jp[0] + vi[3] * jp[1] + vi[4] * jp[2];
+    const double h02 = vi[2] * jp[0] + vi[4] * jp[1] + vi[5] * jp[2];
+    const double h10 = vi[0] * jp[3] + vi[1] * jp[4] + vi[2] * jp[5];      // Vinv jp_1
+    const double h11 = vi[1] * jp[3] + vi[3] * jp[4] + vi[4] * jp[5];
+    const double h12 = vi[2] * jp[3] + vi[4] * jp[4] + vi[5] * jp[5];
+    const double g00 = jp[0] * h00 + jp[1] * h01 + jp[2] * h02;
+    const double g01 = jp[0] * h10 + jp[1] * h11 + jp[2] * h12;
+    const double g11 = jp[3] * h10 + jp[4] * h11 + jp[5] * h12;
+    double m0[6], m1[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        a[i] -= jc[i] * s0 + jc[6 + i] * s1;
+        m0[i] = g00 * jc[i] + g01 * jc[6 + i];
+        m1[i] = g01 * jc[i] + g11 * jc[6 + i];
+    }
+    int n = 6;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) a[n++] += jc[i] * m0[j] + jc[6 + i] * m1[j];
+}
+// The observation loop of the rhs pass over the observations lane0, lane0 + STRIDE, ... of [first, end) of one camera
+// (lane0 = first + the lane's index among the STRIDE; the trip count is uniform over them).
+// One observation per lane and trip (27 sums + two rows of a 6x3 block pair in registers: no room to unroll), software
+// pipelined: the 1000 camera workgroups of a launch start together and walk in lockstep, so a trip whose index load,
+// record gather and arithmetic follow each other costs the two latencies SIX times per launch (a camera's ~1000
+// observations / 192 lanes) with nothing to hide them behind -- 33 us at cfg4, of which 13 are arithmetic.  Here the
+// index is fetched two trips ahead and the record (120 of its 128 bytes: X | e | Vinv) one trip ahead, i.e. requested
+// before the current trip's ~250 instructions issue.  Same observations per lane in the same order: same bits.
+template <bool ROUND, int STRIDE>
+__device__ __forceinline__ void cam_rhs_sweep(const int* __restrict__ pt, const double* __restrict__ rhsrec,
+                                              const double* __restrict__ rec, const double* __restrict__ Vinv, const KMat& K,
+                                              const double* __restrict__ t, int first, int lane0, int end, double (&a)[27]) {
+    int p_cur = lane0 < end ? pt[lane0] : -1;
+    int p_nxt = lane0 + STRIDE < end ? pt[lane0 + STRIDE] : -1;
+    double X[3], e[3], vi[6];
+    rhs_gather(rhsrec, rec, Vinv, p_cur, X, e, vi);
+    for (int k0 = first; k0 < end; k0 += STRIDE) {
+        const int k2 = k0 + (lane0 - first) + 2 * STRIDE;
+        const int p_n2 = k2 < end ? pt[k2] : -1;
+        double Xn[3], en[3], vn[6];
+        rhs_gather(rhsrec, rec, Vinv, p_nxt, Xn, en, vn);
+        if (p_cur >= 0) {
+            double jc[12], jp[6], rx, ry;
+            observe<true>(t, X[0], X[1], X[2], 0.0, 0.0, K, rx, ry, jc, jp);
+            if (ROUND) round_blocks_as_stored(jc, jp);            // as stored in fp32 (see k_cam_schur)
+            rhs_accumulate(jc, jp, e, vi, a);
+        }
+        p_cur = p_nxt; p_nxt = p_n2;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { X[q] = Xn[q]; e[q] = en[q]; }
+#pragma unroll
+        for (int q = 0; q < 6; ++q) vi[q] = vn[q];
+    }
+}
 template <bool ROUND>
 __global__ __launch_bounds__(kRhsThreads) void k_cam_rhs_diag(CamMajor cm, const double* __restrict__ camtab,
                                                               const double* __restrict__ rec,
@@ -2764,77 +2825,7 @@ __global__ __launch_bounds__(kRhsThreads) void k_cam_rhs_diag(CamMajor cm, const
     double a[27];
 #pragma unroll
     for (int q = 0; q < 27; ++q) a[q] = 0.0;
-    // One observation per lane and trip (27 sums + two rows of a 6x3 block pair in registers: no room to unroll), software
-    // pipelined: the 1000 camera workgroups of a launch start together and walk in lockstep, so a trip whose index load,
-    // record gather and arithmetic follow each other costs the two latencies SIX times per launch (a camera's ~1000
-    // observations / 192 lanes) with nothing to hide them behind -- 33 us at cfg4, of which 13 are arithmetic.  Here the
-    // index is fetched two trips ahead and the record (120 of its 128 bytes: X | e | Vinv) one trip ahead, i.e. requested
-    // before the current trip's ~250 instructions issue.  Same observations per lane in the same order: same bits.
-    auto gather = [&](int pidx, double* Xo, double* eo, double* vo) {
-        const size_t pp = (size_t)(pidx < 0 ? 0 : pidx);
-        // one 128-byte record per observation (kRhsRec) when k_prep has written them, else the two gathers
-        const double2* __restrict__ rp = reinterpret_cast<const double2*>(rhsrec != nullptr ? rhsrec + kRhsRec * pp : rec + kRec * pp);
-        const double2* __restrict__ vp = rhsrec != nullptr ? rp + 4 : reinterpret_cast<const double2*>(Vinv + kVinvRow * pp);
-        const double2 r0 = rp[0], r1 = rp[1], r2 = rp[2], v0 = vp[0], v1 = vp[1], v2 = vp[2];
-        Xo[0] = r0.x; Xo[1] = r0.y; Xo[2] = r1.x;
-        eo[0] = r1.y; eo[1] = r2.x; eo[2] = r2.y;
-        vo[0] = v0.x; vo[1] = v0.y; vo[2] = v1.x; vo[3] = v1.y; vo[4] = v2.x; vo[5] = v2.y;
-    };
-    const int k_first = ch.y + (int)threadIdx.x;
-    int p_cur = k_first < ch.z ? cm.pt[k_first] : -1;
-    int p_nxt = k_first + kRhsThreads < ch.z ? cm.pt[k_first + kRhsThreads] : -1;
-    double X[3], e[3], vi[6];
-    gather(p_cur, X, e, vi);
-    for (int k0 = ch.y; k0 < ch.z; k0 += kRhsThreads) {            // (workgroup-uniform trip count)
-        const int k2 = k0 + (int)threadIdx.x + 2 * kRhsThreads;
-        const int p_n2 = k2 < ch.z ? cm.pt[k2] : -1;
-        double Xn[3], en[3], vn[6];
-        gather(p_nxt, Xn, en, vn);
-        if (p_cur >= 0) {
-            double jc[12], jp[6], rx, ry;
-            observe<true>(t, X[0], X[1], X[2], 0.0, 0.0, K, rx, ry, jc, jp);
-            if (ROUND) {                           // as stored in fp32 (see k_cam_schur)
-#pragma unroll
-                for (int q = 0; q < 3; ++q) { jc[q] = (double)(float)jc[q]; jc[6 + q] = (double)(float)jc[6 + q]; }
-#pragma unroll
-                for (int q = 0; q < 6; ++q) jp[q] = (double)(float)jp[q];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) { jc[3 + q] = -jp[q]; jc[9 + q] = -jp[3 + q]; }
-            }
-            // W = Jc^T Jp has rank two (the two residual rows), so neither W nor W Vinv is formed:
-            //     -W e          = -Jc^T (Jp e)
-            //     W Vinv W^T    = Jc^T G Jc,   G = Jp Vinv Jp^T  (2 x 2, symmetric)
-            // 111 multiply-adds per observation instead of 171, and no 6 x 3 temporaries in registers
-            const double s0 = jp[0] * e[0] + jp[1] * e[1] + jp[2] * e[2];
-            const double s1 = jp[3] * e[0] + jp[4] * e[1] + jp[5] * e[2];
-            const double h00 = vi[0] * jp[0] + vi[1] * jp[1] + vi[2] * jp[2];      // Vinv jp_0 (Vinv packed upper)
-            const double h01 = vi[1] * jp[0] + vi[3] * jp[1] + vi[4] * jp[2];
-            const double h02 = vi[2] * jp[0] + vi[4] * jp[1] + vi[5] * jp[2];
-            const double h10 = vi[0] * jp[3] + vi[1] * jp[4] + vi[2] * jp[5];      // Vinv jp_1
-            const double h11 = vi[1] * jp[3] + vi[3] * jp[4] + vi[4] * jp[5];
-            const double h12 = vi[2] * jp[3] + vi[4] * jp[4] + vi[5] * jp[5];
-            const double g00 = jp[0] * h00 + jp[1] * h01 + jp[2] * h02;
-            const double g01 = jp[0] * h10 + jp[1] * h11 + jp[2] * h12;
-            const double g11 = jp[3] * h10 + jp[4] * h11 + jp[5] * h12;
-            double m0[6], m1[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                a[i] -= jc[i] * s0 + jc[6 + i] * s1;
-                m0[i] = g00 * jc[i] + g01 * jc[6 + i];
-                m1[i] = g01 * jc[i] + g11 * jc[6 + i];
-            }
-            int n = 6;
-#pragma unroll
-            for (int i = 0; i < 6; ++i)
-#pragma unroll
-                for (int j = i; j < 6; ++j) a[n++] += jc[i] * m0[j] + jc[6 + i] * m1[j];
-        }
-        p_cur = p_nxt; p_nxt = p_n2;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) { X[q] = Xn[q]; e[q] = en[q]; }
-#pragma unroll
-        for (int q = 0; q < 6; ++q) vi[q] = vn[q];
-    }
+    cam_rhs_sweep<ROUND, kRhsThreads>(cm.pt, rhsrec, rec, Vinv, K, t, ch.y, ch.y + (int)threadIdx.x, ch.z, a);
     double s = cam_block_total<27, kRhsThreads / 64>(a, red);
     if (threadIdx.x < 27) {
         if (cx.world > 1) s = cam_exchange_value(cx, cam_slots_rhs(cx.world, C), 27, threadIdx.x, C, ch.x, s, 4u);
@@ -2884,66 +2875,7 @@ __global__ __launch_bounds__(kCamThreads) void k_cam_rhs_diag_w(CamMajor cm, con
     double a[27];
 #pragma unroll
     for (int n = 0; n < 27; ++n) a[n] = 0.0;
-    auto gather = [&](int pidx, double* Xo, double* eo, double* vo) {
-        const size_t pp = (size_t)(pidx < 0 ? 0 : pidx);
-        const double2* __restrict__ rp = reinterpret_cast<const double2*>(rhsrec != nullptr ? rhsrec + kRhsRec * pp : rec + kRec * pp);
-        const double2* __restrict__ vp = rhsrec != nullptr ? rp + 4 : reinterpret_cast<const double2*>(Vinv + kVinvRow * pp);
-        const double2 r0 = rp[0], r1 = rp[1], r2 = rp[2], v0 = vp[0], v1 = vp[1], v2 = vp[2];
-        Xo[0] = r0.x; Xo[1] = r0.y; Xo[2] = r1.x;
-        eo[0] = r1.y; eo[1] = r2.x; eo[2] = r2.y;
-        vo[0] = v0.x; vo[1] = v0.y; vo[2] = v1.x; vo[3] = v1.y; vo[4] = v2.x; vo[5] = v2.y;
-    };
-    const int k_first = ch.y + lane;
-    int p_cur = k_first < ch.z ? cm.pt[k_first] : -1;
-    int p_nxt = k_first + 64 < ch.z ? cm.pt[k_first + 64] : -1;
-    double X[3], e[3], vi[6];
-    gather(p_cur, X, e, vi);
-    for (int k0 = ch.y; k0 < ch.z; k0 += 64) {                     // (wave-uniform trip count; software pipelined as k_cam_rhs_diag)
-        const int k2 = k0 + lane + 128;
-        const int p_n2 = k2 < ch.z ? cm.pt[k2] : -1;
-        double Xn[3], en[3], vn[6];
-        gather(p_nxt, Xn, en, vn);
-        if (p_cur >= 0) {
-            double jc[12], jp[6], rx, ry;
-            observe<true>(t, X[0], X[1], X[2], 0.0, 0.0, K, rx, ry, jc, jp);
-            if (ROUND) {                           // as stored in fp32 (see k_cam_schur)
-#pragma unroll
-                for (int n = 0; n < 3; ++n) { jc[n] = (double)(float)jc[n]; jc[6 + n] = (double)(float)jc[6 + n]; }
-#pragma unroll
-                for (int n = 0; n < 6; ++n) jp[n] = (double)(float)jp[n];
-#pragma unroll
-                for (int n = 0; n < 3; ++n) { jc[3 + n] = -jp[n]; jc[9 + n] = -jp[3 + n]; }
-            }
-            const double s0 = jp[0] * e[0] + jp[1] * e[1] + jp[2] * e[2];
-            const double s1 = jp[3] * e[0] + jp[4] * e[1] + jp[5] * e[2];
-            const double h00 = vi[0] * jp[0] + vi[1] * jp[1] + vi[2] * jp[2];      // Vinv jp_0 (Vinv packed upper)
-            const double h01 = vi[1] * jp[0] + vi[3] * jp[1] + vi[4] * jp[2];
-            const double h02 = vi[2] * jp[0] + vi[4] * jp[1] + vi[5] * jp[2];
-            const double h10 = vi[0] * jp[3] + vi[1] * jp[4] + vi[2] * jp[5];      // Vinv jp_1
-            const double h11 = vi[1] * jp[3] + vi[3] * jp[4] + vi[4] * jp[5];
-            const double h12 = vi[2] * jp[3] + vi[4] * jp[4] + vi[5] * jp[5];
-            const double g00 = jp[0] * h00 + jp[1] * h01 + jp[2] * h02;
-            const double g01 = jp[0] * h10 + jp[1] * h11 + jp[2] * h12;
-            const double g11 = jp[3] * h10 + jp[4] * h11 + jp[5] * h12;
-            double m0[6], m1[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                a[i] -= jc[i] * s0 + jc[6 + i] * s1;
-                m0[i] = g00 * jc[i] + g01 * jc[6 + i];
-                m1[i] = g01 * jc[i] + g11 * jc[6 + i];
-            }
-            int n = 6;
-#pragma unroll
-            for (int i = 0; i < 6; ++i)
-#pragma unroll
-                for (int j = i; j < 6; ++j) a[n++] += jc[i] * m0[j] + jc[6 + i] * m1[j];
-        }
-        p_cur = p_nxt; p_nxt = p_n2;
-#pragma unroll
-        for (int n = 0; n < 3; ++n) { X[n] = Xn[n]; e[n] = en[n]; }
-#pragma unroll
-        for (int n = 0; n < 6; ++n) vi[n] = vn[n];
-    }
+    cam_rhs_sweep<ROUND, 64>(cm.pt, rhsrec, rec, Vinv, K, t, ch.y, ch.y + lane, ch.z, a);
     const int col = wave_fold_sum<27>(a, lane);
     if (col >= 0) partial[(size_t)q * 27 + col] = a[0];
 }

@@ -3,7 +3,11 @@ Usage: python tools/compare_kernel_asm.py PARENT.s NEW.s   (each sfm-python_amd/
 
 A kernel's text runs from its label to its .Lfunc_end; the function's number inside block labels (.LBB<number>_<block>, and
 the same in the loop comments) depends on how many kernels precede it in the file and is ignored, as is the padding
-before a comment.  Exit status 1 when a kernel of the parent differs or is missing."""
+before a comment.  For a kernel that differs, the opcodes whose counts differ are listed as `opcode parent->new` (the
+first word of every instruction line; labels, directives and comments are not counted): a kernel whose listed opcodes
+are compares, selects, moves, waits and branches only does the same memory and floating-point work.
+Exit status 1 when a kernel of the parent differs or is missing."""
+import collections
 import re
 import sys
 
@@ -22,6 +26,11 @@ def kernels(path):
     return out
 
 
+def opcodes(lines):
+    words = (ln.split(";")[0].split() for ln in lines)
+    return collections.Counter(w[0] for w in words if w and not w[0].startswith(".") and not w[0].endswith(":"))
+
+
 def main():
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
     differ = [k for k in a if k not in b or a[k] != b[k]]
@@ -29,6 +38,11 @@ def main():
           f"{len([k for k in b if k not in a])} new")
     for k in differ:
         print("  differs:", k)
+        if k in b:
+            ha, hb = opcodes(a[k]), opcodes(b[k])
+            changed = [f"{op} {ha[op]}->{hb[op]}" for op in sorted(set(ha) | set(hb)) if ha[op] != hb[op]]
+            print(f"    {sum(ha.values())} -> {sum(hb.values())} instructions; opcode counts that differ:",
+                  ", ".join(changed) if changed else "none (order or operands only)")
     for k in b:
         if k not in a:
             print("  new:", k)
