@@ -192,7 +192,10 @@ int  sfmba_get_counters(const sfmba_handle* h, int64_t* kernel_launches, int64_t
  * camera has several chunks: k_cam_combine runs), "xcd_b" (pass B over the XCD-aware table), "rhsrec" (the rhs pass
  * gathers the 128-byte records), "round_blocks"; and of the solve stage, as the next compute call decides it from the
  * transport and the options of that moment: "xcd_cam" (K3 and the rhs pass one wave per chunk), "own_inverse" (the rhs
- * pass inverts its camera's preconditioner block itself).  "match_form" belongs to the descriptor set, not to the
+ * pass inverts its camera's preconditioner block itself), "one_rank", "precond" (Schur-diagonal preconditioner),
+ * "dense_solve", "pcg_local" / "pcg_local2" (per-camera bookkeeping of the PCG in pass B or its tail: fused form /
+ * k_pcg_update_local), "pcg_split" (k_pcg_tail), "skip_last" (0, 1, 2: what of the last speculative launch pair is left
+ * out), "quick_start", "spec_scale", "cost_rider".  "match_form" belongs to the descriptor set, not to the
  * problem (sfmba_set_descriptors): 1 = form A, 2 = form B. */
 int  sfmba_get_form(sfmba_handle* h, const char* name, int32_t* value);
 /* PCG iterations of every outer iteration of the last completed sfmba_solve on this handle (the record the next
@@ -870,6 +873,30 @@ int  sfmba_rhs_precond(sfmba_handle* h, const double* x, const double* dc, const
  * values of rt32 as pass B reads them).  Any output may be NULL.  Returns -1 when the problem does not run the mixed
  * form (sfmba_get_form(h, "mixed")).  Copies only: launches nothing and changes nothing on the handle. */
 int  sfmba_get_mixed_operands(sfmba_handle* h, double* origin, float* rt32, float* rec32, double* rtd);
+
+/* What the LAST outer iteration of the last sfmba_solve left on the handle, valid until the next operation that computes
+ * on it.  A solve with max_nfev = 1 runs the linear phase and the device-decided trial of iteration 0 and returns x0, so
+ * the state is that of one outer iteration at x0; max_nfev = 2 leaves iteration 1 (at the point the solve returns) when
+ * the first step was accepted.  n = 6C + 3P.  Every output may be NULL; all are in the caller's layout:
+ *   scalars (32)   the exchange scalars on the device: 0 sum r^2 of the last evaluated point, 1 G11, 2 G12, 3 G22,
+ *                  4..7 q5..q8 and 8..11 q1..q4 of the point slice, 12 max|g_p|, 13 reg, 14 |g_h|^2 (the next forcing
+ *                  term's memory), 15 eta, 16..24 q0..q8 of the camera slice, 25..29 c1, c2, predicted reduction, |step_h|,
+ *                  |step| as the device decided them, 30 the skip flag, 31 the radius the device used
+ *   ctrl (8)       the PCG control block the solve ended on: rz, rz0, tol2, rz_prev, alpha_prev, iters, max_iters, done
+ *   si, g, sg      (n each) column scale, gradient and D^2 g of the point the solve returns
+ *   si2, g2, sg2   (n each) the other buffer set: with "spec_scale", those of the last trial point
+ *   Dc (6C), Minv (21C: upper triangles, the values the PCG read), Vinv (6P: upper triangles), e (3P)
+ *   pcg_x, pcg_r   (6C each) iterate and residual the PCG ended on, from the vector set the control block names
+ *   p (n)          the step [dc | dp];   x_new (n) the last trial point
+ * An output the solve's form does not keep is refused: the call returns -1 and the message names the output.  Minv:
+ * not on the dense path (its inverses live in LDS).  e: only on the dense path or with the 128-byte records ("rhsrec");
+ * elsewhere pass A has overwritten it with its z.  pcg_r: not on the dense path and not in the local forms (their r
+ * lags one update behind).  pcg_x: not when k_backsub's prologue did the last update (the final x is dc of p only).
+ * Returns -1 without a completed solve.  Waits for the stream and copies: launches nothing and changes nothing on the
+ * handle. */
+int  sfmba_get_iteration_state(sfmba_handle* h, double* scalars, double* ctrl, double* si, double* g, double* sg,
+                               double* si2, double* g2, double* sg2, double* Dc, double* Minv, double* Vinv, double* e,
+                               double* pcg_x, double* pcg_r, double* p, double* x_new);
 
 /* Few-camera path (6 n_cameras <= 128, the reference's own problem sizes): at x, with the diagonals dc (6C) and dp
  * (3P), form S = U + diag(dc) - W (V + diag(dp))^-1 W^T (S_out: (6C)^2 row-major, may be NULL) and solve S y = rhs

@@ -1291,6 +1291,9 @@ int sfmba_get_form(sfmba_handle* h, const char* name, int32_t* value) {
         {"pcg_fused", f.pcg_fused}, {"mixed", f.mixed}, {"mixed_b", f.mixed_b}, {"jfree", f.jfree}, {"rc_cons", f.rc_cons}, {"dense", f.dense},
         {"cam_multi", f.cam_multi}, {"xcd_b", f.xcd_b}, {"rhsrec", f.use_rhsrec}, {"round_blocks", f.round_blocks},
         {"xcd_cam", f.xcd_cam}, {"own_inverse", f.own_inverse},
+        {"one_rank", f.one_rank}, {"precond", f.precond}, {"dense_solve", f.dense_solve}, {"pcg_local", f.pcg_local},
+        {"pcg_local2", f.pcg_local2}, {"pcg_split", f.pcg_split}, {"skip_last", f.skip_last}, {"quick_start", f.quick_start},
+        {"spec_scale", f.spec_scale}, {"cost_rider", f.cost_rider},
     };
     for (const auto& e : forms)
         if (strcmp(name, e.name) == 0) { *value = e.value; return 0; }
@@ -2706,6 +2709,62 @@ int sfmba_solve_from(sfmba_handle* h, const double* x0, double* x_out, const sfm
         h->err = msg;
     }
     return rc;
+}
+
+// Test entry: the state the last outer iteration of the last solve left on the handle (include/sfmba.h).  Copies only.
+int sfmba_get_iteration_state(sfmba_handle* h, double* scalars, double* ctrl, double* si, double* g, double* sg,
+                              double* si2, double* g2, double* sg2, double* Dc, double* Minv, double* Vinv, double* e,
+                              double* pcg_x, double* pcg_r, double* p, double* x_new) {
+    CHK(enter(h));
+    if (!h->have_problem || !h->solved) return fail(h, -1, "sfmba_get_iteration_state: no completed sfmba_solve on this handle");
+    const Forms& f = h->forms;
+    const bool local = f.pcg_local || f.pcg_local2;
+    if (Minv && f.dense_solve) return fail(h, -1, "sfmba_get_iteration_state: Minv is not kept on the dense path (the inverses live in LDS)");
+    if (e && !f.dense_solve && !f.use_rhsrec) return fail(h, -1, "sfmba_get_iteration_state: e is not kept (pass A has overwritten it with its z)");
+    if (pcg_r && (f.dense_solve || local)) return fail(h, -1, "sfmba_get_iteration_state: pcg_r is not kept (%s)", f.dense_solve ? "the dense path holds r in LDS" : "the local form's r lags one update behind");
+    if (pcg_x && h->pcg_a_owed) return fail(h, -1, "sfmba_get_iteration_state: pcg_x is not kept (k_backsub's prologue did the last update: the final x is dc of p)");
+    const size_t C = (size_t)h->C, P = (size_t)h->P, n = (size_t)h->n, n6 = 6 * C;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    auto fetch = [&](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost); };
+    PcgCtrl hc{};
+    HIPCHK(h, fetch(&hc, h->ctrl.as<PcgCtrl>() + (h->pcg_L & 1), sizeof hc));
+    if (scalars) HIPCHK(h, fetch(scalars, h->scal(), sizeof(double) * kScalSlots));
+    if (ctrl) {
+        const double c8[8] = {hc.rz, hc.rz0, hc.tol2, hc.rz_prev, hc.alpha_prev, (double)hc.iters, (double)hc.max_iters, (double)hc.done};
+        memcpy(ctrl, c8, sizeof c8);
+    }
+    const struct { double* dst; const double* src; } whole[] = {{si, h->si_cur}, {g, h->g_cur}, {sg, h->sg_cur}, {si2, h->si_new},
+                                                                {g2, h->g_new}, {sg2, h->sg_new}, {p, h->p.as<double>()}, {x_new, h->x_new}};
+    for (const auto& w : whole)
+        if (w.dst) HIPCHK(h, fetch(w.dst, w.src, sizeof(double) * n));
+    std::vector<double> buf;
+    auto planes = [&](double* dst, const double* src, size_t rows) -> int {        // plane-major [rows][C] -> [C][rows]
+        if (!dst) return 0;
+        buf.resize(rows * C);
+        HIPCHK(h, fetch(buf.data(), src, sizeof(double) * rows * C));
+        for (size_t c = 0; c < C; ++c)
+            for (size_t k = 0; k < rows; ++k) dst[rows * c + k] = buf[k * C + c];
+        return 0;
+    };
+    auto records = [&](double* dst, const double* src, size_t stride, size_t width) -> int {    // [P][stride] -> [P][width]
+        if (!dst) return 0;
+        buf.resize(stride * P);
+        HIPCHK(h, fetch(buf.data(), src, sizeof(double) * (stride * (P - 1) + width)));
+        for (size_t q = 0; q < P; ++q)
+            for (size_t k = 0; k < width; ++k) dst[width * q + k] = buf[stride * q + k];
+        return 0;
+    };
+    CHK(planes(Dc, h->Dc.as<double>(), 6));
+    CHK(planes(Minv, h->Minv.as<double>(), 21));
+    if (P > 0) {
+        CHK(records(Vinv, vinv_ptr(h), kVinvRow, 6));
+        if (f.dense_solve) CHK(records(e, h->rec + 3, kRec, 3));
+        else CHK(records(e, h->rhsrec.as<double>() + 3, kRhsRec, 3));
+    }
+    const double* set = h->vecs.as<double>() + (size_t)(hc.iters & 1) * kPcgVecs * n6;      // (k_transpose, k_backsub: x of the final set)
+    CHK(planes(pcg_x, set + kPcgX * n6, 6));
+    CHK(planes(pcg_r, set + kPcgR * n6, 6));
+    return 0;
 }
 
 int sfmba_get_fun_grad(sfmba_handle* h, double* fun_out, double* grad_out) {

@@ -21,7 +21,7 @@ SYMBOLS = (
     "sfmba_comm_destroy", "sfmba_set_precision", "sfmba_p2p_export", "sfmba_p2p_attach", "sfmba_p2p_detach",
     "sfmba_p2p_calls", "sfmba_tr2d_solve", "sfmba_debug_option", "sfmba_set_print", "sfmba_get_counters", "sfmba_problem_reuse", "sfmba_dense_schur",
     "sfmba_get_pcg_history", "sfmba_set_fixed_cameras", "sfmba_step_products", "sfmba_get_form", "sfmba_rhs_precond",
-    "sfmba_get_mixed_operands", "sfmba_default_filter_options", "sfmba_reprojection_stats",
+    "sfmba_get_mixed_operands", "sfmba_get_iteration_state", "sfmba_default_filter_options", "sfmba_reprojection_stats",
     "sfmba_default_triangulate_options", "sfmba_triangulate",
     "sfmba_default_resect_options", "sfmba_resect",
     "sfmba_default_pnp_ransac_options", "sfmba_resect_ransac",
@@ -179,6 +179,9 @@ def load():
     if hasattr(lib, "sfmba_get_mixed_operands"):     # (likewise)
         lib.sfmba_get_mixed_operands.argtypes = [P] * 5
         lib.sfmba_get_mixed_operands.restype = C.c_int
+    if hasattr(lib, "sfmba_get_iteration_state"):    # (likewise)
+        lib.sfmba_get_iteration_state.argtypes = [P] * 17
+        lib.sfmba_get_iteration_state.restype = C.c_int
     if hasattr(lib, "sfmba_reprojection_stats"):     # (likewise)
         lib.sfmba_default_filter_options.argtypes = [C.POINTER(FilterOptions)]
         lib.sfmba_default_filter_options.restype = None

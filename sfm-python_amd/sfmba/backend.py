@@ -1258,6 +1258,30 @@ class Backend:
                                                        _capi.ptr(rtd)))
         return {"origin": origin, "rt32": rt32, "rec32": rec32, "rtd": rtd}
 
+    ITERATION_STATE = ("scalars", "ctrl", "si", "g", "sg", "si2", "g2", "sg2", "Dc", "Minv", "Vinv", "e", "pcg_x", "pcg_r",
+                       "p", "x_new")
+
+    def iteration_state(self, skip=()):
+        """What the last outer iteration of the last `solve` left on the handle (include/sfmba.h:
+        sfmba_get_iteration_state) -> dict of ITERATION_STATE without the names of ``skip``: scalars (32), ctrl (dict:
+        rz, rz0, tol2, rz_prev, alpha_prev, iters, max_iters, done), si, g, sg, si2, g2, sg2, p, x_new (n), Dc (C, 6),
+        Minv (C, 21), Vinv (P, 6), e (P, 3), pcg_x, pcg_r (C, 6).  An output the solve's form does not keep has to be in
+        ``skip``: asking for it raises ValueError.  Copies only."""
+        unknown = set(skip) - set(self.ITERATION_STATE)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        self._flush_pending()
+        nc, npt, n = self.n_cameras, self.n_points, self.n_params
+        shapes = {"scalars": (32,), "ctrl": (8,), "Dc": (nc, 6), "Minv": (nc, 21), "Vinv": (npt, 6), "e": (npt, 3),
+                  "pcg_x": (nc, 6), "pcg_r": (nc, 6)}
+        out = {name: np.empty(shapes.get(name, (n,))) for name in self.ITERATION_STATE if name not in skip}
+        self._check(self._lib.sfmba_get_iteration_state(self._h, *[_opt_ptr(out.get(name)) for name in self.ITERATION_STATE]))
+        if "ctrl" in out:
+            c = out["ctrl"]
+            out["ctrl"] = {"rz": float(c[0]), "rz0": float(c[1]), "tol2": float(c[2]), "rz_prev": float(c[3]),
+                           "alpha_prev": float(c[4]), "iters": int(c[5]), "max_iters": int(c[6]), "done": int(c[7])}
+        return out
+
     def dense_schur(self, x, dc, dp, rhs):
         """(S, y): the formed reduced camera matrix and the solution of S y = rhs by the in-LDS PCG run to the end."""
         self._flush_pending()
