@@ -844,7 +844,13 @@ int  sfmba_schur_matvec(sfmba_handle* h, const double* x, const double* dc, cons
  * the column scale are those of x, D^2 g of the cameras is sg, and D^2 g of the points is g_p * scale_p^2 as the solver has it.
  * x, sg: 6C+3P; dc: 6C; dp_diag: 3P.  t1_out: 2N in the caller's observation order; dp_out: 3P; sums_out: 10;
  * g_out, si_out (6C+3P, either may be NULL): the gradient and the inverse column scale the sums were formed with.
- * Single rank, 64-bit storage. */
+ * Single rank; 64-bit or 32-bit storage.  In 32-bit storage the fp32 OPERANDS of the two kernels are the stored Jacobian
+ * blocks Jc, Jp (the float32 values sfmba_residual_jacobian returns; with the J-free iteration, debug option jfree, the
+ * blocks are recomputed in fp64 and nothing of J is rounded) and the stored t1; everything formed from them is fp64:
+ *   t1_out holds the stored float32 values of t1 exactly (each widened to a double);
+ *   *g11_out is the sum of the squares of the UNROUNDED fp64 t1, which k_jdot sums before it stores;
+ *   the sum t1.t2 of sums_out is formed by k_backsub with the STORED (rounded) t1 it reads back.
+ * Leaves the handle as the other entries of this group do: a solve afterwards is the solve without the call. */
 int  sfmba_step_products(sfmba_handle* h, const double* x, const double* sg, const double* dc, const double* dp_diag,
                          double* t1_out, double* g11_out, double* dp_out, double* sums_out, double* g_out, double* si_out);
 

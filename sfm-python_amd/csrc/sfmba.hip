@@ -1960,7 +1960,6 @@ int sfmba_step_products(sfmba_handle* h, const double* x, const double* sg, cons
     CHK(enter(h));
     CHK(begin_compute(h, x));
     if (!sg || !dc || !dp_diag || !t1_out || !g11_out || !dp_out || !sums_out) return fail(h, -1, "NULL argument");
-    if (h->f32) return fail(h, -1, "sfmba_step_products returns t1 as stored: 64-bit storage only");
     if (!h->forms.one_rank) return fail(h, -1, "sfmba_step_products is a single-rank entry");
     const int64_t C = h->C, P = h->P, N = h->N;
     CHK(linearise_at(h, x));
@@ -1974,19 +1973,22 @@ int sfmba_step_products(sfmba_handle* h, const double* x, const double* sg, cons
     CHK(launch_point_prep(h, nullptr, h->e.as<double>(), 0.0, nullptr, nullptr, nullptr));
     int np1 = 0, np2 = 0;
     CHK(launch_jdot(h, &np1));
-    std::vector<double> part1((size_t)np1), t1((size_t)2 * N);
+    std::vector<double> part1((size_t)np1), t1(h->f32 ? 0 : (size_t)2 * N);
+    std::vector<float> t1f(h->f32 ? (size_t)2 * N : 0);        // 32-bit storage: t1 holds 2N floats, widened below
     HIPCHK(h, hipMemcpyAsync(part1.data(), partB(h), sizeof(double) * np1, hipMemcpyDeviceToHost, h->stream));
     CHK(launch_backsub(h, &np2, h->vtmp.as<double>()));
     std::vector<double> part2((size_t)np2 * kBacksubCols);
     HIPCHK(h, hipMemcpyAsync(part2.data(), partB(h), sizeof(double) * part2.size(), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(t1.data(), h->t1.p, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, h->stream));
+    if (h->f32) HIPCHK(h, hipMemcpyAsync(t1f.data(), h->t1.p, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, h->stream));
+    else HIPCHK(h, hipMemcpyAsync(t1.data(), h->t1.p, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(dp_out, h->p.as<double>() + 6 * C, sizeof(double) * 3 * P, hipMemcpyDeviceToHost, h->stream));
     if (g_out) HIPCHK(h, hipMemcpyAsync(g_out, h->g_cur, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     if (si_out) HIPCHK(h, hipMemcpyAsync(si_out, h->si_cur, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int64_t k = 0; k < N; ++k) {
         const int64_t d = h->permuted ? h->tb.order[k] : k;
-        t1_out[2 * d] = t1[2 * k]; t1_out[2 * d + 1] = t1[2 * k + 1];
+        if (h->f32) { t1_out[2 * d] = (double)t1f[2 * k]; t1_out[2 * d + 1] = (double)t1f[2 * k + 1]; }
+        else { t1_out[2 * d] = t1[2 * k]; t1_out[2 * d + 1] = t1[2 * k + 1]; }
     }
     *g11_out = 0.0;                                             // the partial rows in the order the device sums them
     for (int b = 0; b < np1; ++b) *g11_out += part1[b];

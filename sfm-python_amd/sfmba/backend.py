@@ -1216,7 +1216,8 @@ class Backend:
 
     def step_products(self, x, sg, dc, dp_diag):
         """k_jdot and k_backsub in the selected form (include/sfmba.h: sfmba_step_products)
-        -> dict(t1 (N, 2), g11, dp (P, 3), sums (10), g, si)."""
+        -> dict(t1 (N, 2), g11, dp (P, 3), sums (10), g, si).  Both storage modes: with 32-bit storage t1 holds the
+        stored float32 values exactly, g11 is the sum of the unrounded squares and sums[0] = t1.t2 uses the stored t1."""
         self._flush_pending()
         x = _f64(x, (self.n_params,), "x")
         sg = _f64(sg, (self.n_params,), "sg")

@@ -4,12 +4,11 @@ The forms table takes the row form from 65536 observations on; the problems here
 they ask for it with rc_consumers = 1 -- "wherever it is legal" -- and check through the form query that it ran.
 Entry by entry against extended-precision numpy (both forms), whole solves against the stored-Jacobian form and the
 oracle, the FinalUpdate hand-over of replayed records, and the sharded forms on a world of one."""
-import math
-
 import numpy as np
 import pytest
 
 from entry_bounds import CHOL_ROUNDINGS, EPS, LD, T1_ROUNDINGS, T_ROUNDINGS, _cross_abs, _inv3, _row_form_abs, _run_roundings  # noqa: F401
+from step_products_ref import _Case, _check_entries, rc_hand_built as _hand_built  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -36,109 +35,8 @@ def orc():
 #   sums: products 2, then one addition per window of the lane's range, 6 (wave_sum), 16 (waves of the workgroup), and the
 #       workgroups' partial rows
 # k is TWICE the count: the reference is formed from the fetched blocks, which carry K1's roundings of the same paths.
-# (the constants, _run_roundings, _row_form_abs, _cross_abs and _inv3 live in tests/entry_bounds.py, shared with test_gpu_entries.py)
-
-
-class _Case:
-    """Reference values of sfmba_step_products in longdouble from the fetched blocks, and what bounds the entries' errors."""
-
-    def __init__(self, be, pb, seed=0):
-        C, P, N = pb.n_cameras, pb.n_points, len(pb.camera_indices)
-        ci, pi = np.asarray(pb.camera_indices), np.asarray(pb.point_indices)
-        rng = np.random.default_rng(seed)
-        self.pb, self.C, self.P, self.N, self.ci, self.pi = pb, C, P, N, ci, pi
-        self.sg = rng.normal(size=6 * C + 3 * P)
-        self.dc = 1e-2 * rng.normal(size=6 * C)
-        r, Jc, Jp = be.residual_jacobian(pb.x0)
-        r, Jc, Jp = r.reshape(N, 2).astype(LD), Jc.astype(LD), Jp.astype(LD)
-        V = np.zeros((P, 3, 3), dtype=LD)
-        np.add.at(V, pi, np.einsum("nki,nkj->nij", Jp, Jp))
-        # a diagonal of the size of V's own: V + diag is well conditioned, also for a point with one observation (V singular)
-        self.diag = np.asarray(np.einsum("pii->pi", V) + 1.0, dtype=np.float64).ravel() * rng.uniform(0.5, 2.0, size=3 * P)
-        self.L = np.bincount(pi, minlength=P)
-        self.seen = self.L > 0
-        sgc, sgp, dc = self.sg[:6 * C].reshape(C, 6).astype(LD), self.sg[6 * C:].reshape(P, 3).astype(LD), self.dc.reshape(C, 6).astype(LD)
-        aJc, aJp = np.abs(Jc), np.abs(Jp)
-        self.t1 = np.einsum("nki,ni->nk", Jc, sgc[ci]) + np.einsum("nki,ni->nk", Jp, sgp[pi])
-        t = np.einsum("nki,ni->nk", Jc, dc[ci])
-        ja1, ta1 = _row_form_abs(pb, pb.x0, sgc)
-        ja2, ta2 = _row_form_abs(pb, pb.x0, dc)
-        # sum |terms| of t1 and of t = Jc dc, per form
-        self.S_t1 = {0: np.einsum("nki,ni->nk", aJc, np.abs(sgc[ci])) + np.einsum("nki,ni->nk", aJp, np.abs(sgp[pi])),
-                     1: ta1 + np.einsum("nki,ni->nk", ja1, np.abs(sgp[pi]))}
-        S_t = {0: np.einsum("nki,ni->nk", aJc, np.abs(dc[ci])), 1: ta2}
-        aj = {0: aJp, 1: ja2}
-        gp, y = np.zeros((P, 3), dtype=LD), np.zeros((P, 3), dtype=LD)
-        np.add.at(gp, pi, np.einsum("nki,nk->ni", Jp, r))
-        np.add.at(y, pi, np.einsum("nki,nk->ni", Jp, t))
-        A = V + np.einsum("pi,ij->pij", self.diag.reshape(P, 3).astype(LD), np.eye(3, dtype=LD))
-        Ainv = _inv3(A)
-        self.dp = np.einsum("pij,pj->pi", Ainv, -gp - y)
-        aInv = np.abs(Ainv)
-        ga, aA = np.zeros((P, 3), dtype=LD), np.abs(A)
-        np.add.at(ga, pi, np.einsum("nki,nk->ni", aJp, np.abs(r)))
-        s_run = _run_roundings(self.L)
-        self.k_t1, self.B_t1, self.S_dp, self.k_dp, self.B_dp, self.B_t2 = {}, {}, {}, {}, {}, {}
-        self.t2 = t + np.einsum("nki,ni->nk", Jp, self.dp[pi])
-        for form in (0, 1):
-            self.k_t1[form] = 2 * T1_ROUNDINGS[form]
-            self.B_t1[form] = self.k_t1[form] * EPS * self.S_t1[form]
-            ya = np.zeros((P, 3), dtype=LD)
-            np.add.at(ya, pi, np.einsum("nki,nk->ni", aj[form], S_t[form]))
-            # sum |terms| of dp: |Vinv| (sum |jp r| + sum |jp t|), and the inverse's own error |Vinv| |V + diag| |Vinv| |b|
-            self.S_dp[form] = np.einsum("pij,pj->pi", aInv, ga + ya) + \
-                np.einsum("pij,pjk,pkl,pl->pi", aInv, aA, aInv, np.abs(gp) + np.abs(y))
-            self.k_dp[form] = 2 * (T_ROUNDINGS[form] + 2 + s_run + 4 + CHOL_ROUNDINGS + 2 + s_run)
-            self.B_dp[form] = self.k_dp[form][:, None] * EPS * self.S_dp[form]
-            self.B_t2[form] = 2 * (T_ROUNDINGS[form] + 4) * EPS * (S_t[form] + np.einsum("nki,ni->nk", aj[form], np.abs(self.dp[pi]))) + \
-                np.einsum("nki,ni->nk", aj[form], self.B_dp[form][pi])
-
-    def sums(self, out, form):
-        """-> (reference of g11 and the ten sums, their bounds) with the gradient and the scale the device formed them with."""
-        C, P, N = self.C, self.P, self.N
-        g, si = out["g"].astype(LD), out["si"].astype(LD)
-        gpt, spt = g[6 * C:].reshape(P, 3)[self.seen], si[6 * C:].reshape(P, 3)[self.seen]
-        dp, Bdp = self.dp[self.seen], self.B_dp[form][self.seen]
-        dc, gc, sc, sgc = self.dc.astype(LD), g[:6 * C], si[:6 * C], self.sg[:6 * C].astype(LD)
-        # additions on the way of a sum: one per window of a lane's range (ranges are cut at max(64, N / 4096) observations,
-        # a window completes at least one run), the run trips of the longest point, 6 + 16 in the workgroup, <= 256 partial rows
-        n_add = 2 + max(64, math.ceil(N / 4096)) + math.ceil(self.L.max() / 64) + 6 + 16 + min(256, math.ceil(N / 1024))
-        t1, t2, B1, B2 = self.t1, self.t2, self.B_t1[form], self.B_t2[form]
-        ref = [np.sum(t1 * t1), np.sum(t1 * t2), np.sum(t2 * t2),
-               np.sum(gpt * dp), np.sum((dp * spt) ** 2), np.sum(gpt / spt ** 2 * dp), np.sum(dp * dp),
-               np.sum(gc * dc), np.sum((dc * sc) ** 2), np.sum(sgc * dc), np.sum(dc * dc)]
-        e = 2 * n_add * EPS
-        bound = [np.sum((2 * np.abs(t1) + B1) * B1) + e * np.sum(t1 * t1),
-                 np.sum(B1 * np.abs(t2) + np.abs(t1) * B2 + B1 * B2) + e * np.sum(np.abs(t1 * t2)),
-                 np.sum((2 * np.abs(t2) + B2) * B2) + e * np.sum(t2 * t2),
-                 np.sum(np.abs(gpt) * Bdp) + e * np.sum(np.abs(gpt * dp)),
-                 np.sum(spt ** 2 * (2 * np.abs(dp) + Bdp) * Bdp) + (e + 4 * EPS) * np.sum((dp * spt) ** 2),
-                 np.sum(np.abs(gpt) / spt ** 2 * Bdp) + (e + 6 * EPS) * np.sum(np.abs(gpt / spt ** 2 * dp)),
-                 np.sum((2 * np.abs(dp) + Bdp) * Bdp) + e * np.sum(dp * dp),
-                 e * np.sum(np.abs(gc * dc)), (e + 4 * EPS) * np.sum((dc * sc) ** 2), e * np.sum(np.abs(sgc * dc)), e * np.sum(dc * dc)]
-        return np.array(ref, dtype=LD), np.array(bound, dtype=LD)
-
-
-def _check_entries(be, pb, form, case, tag):
-    out = be.step_products(pb.x0, case.sg, case.dc, case.diag)
-    seen = case.seen                                 # (an unobserved point has no run: nothing produces its dp)
-    err_t1 = np.abs(out["t1"].astype(LD) - case.t1)
-    err_dp = np.abs(out["dp"].astype(LD) - case.dp)[seen]
-    ref, bound = case.sums(out, form)
-    got = np.concatenate([[out["g11"]], out["sums"]]).astype(LD)
-    err_s = np.abs(got - ref)
-    print(f"{tag} form {form}: t1 err/bound {float((err_t1 / case.B_t1[form]).max()):.3f} (k = {case.k_t1[form]}), "
-          f"dp {float((err_dp / case.B_dp[form][seen]).max()):.3f} (k = {int(case.k_dp[form].min())}..{int(case.k_dp[form].max())}), "
-          f"sums {np.array2string(np.asarray(err_s / bound, dtype=np.float64), precision=3)}")
-    assert np.all(np.isfinite(out["t1"])) and np.all(np.isfinite(out["dp"][seen])) and np.all(np.isfinite(got.astype(np.float64)))
-    assert np.all(err_t1 <= case.B_t1[form]), tag
-    assert np.all(err_dp <= case.B_dp[form][seen]), tag
-    assert np.all(err_s <= bound), (tag, err_s / bound)
-    # the bounds mean something: they sit nine digits below all but a hundredth of the entries (and all of the sums)
-    assert np.mean(case.B_t1[form] < 1e-9 * np.abs(case.t1)) >= 0.99, tag
-    assert np.mean(case.B_dp[form][seen] < 1e-9 * np.abs(case.dp[seen])) >= 0.99, tag
-    assert np.all(bound < 1e-9 * np.abs(ref)), tag
-    return out
+# (the constants, _run_roundings, _row_form_abs, _cross_abs and _inv3 live in tests/entry_bounds.py, shared with test_gpu_entries.py;
+# _Case, _check_entries and the hand-built problem in tests/step_products_ref.py, shared with test_gpu_step_products.py)
 
 
 def _both_forms(pb, tag, fixed=(), expect_row_form=1):
@@ -157,21 +55,6 @@ def _both_forms(pb, tag, fixed=(), expect_row_form=1):
         finally:
             be.close()
     return outs
-
-
-def _hand_built(orc):
-    """8 cameras, 40 points: 21 points of 3 observations (0..62), a run of 5 that starts on lane 63 of the first window, a
-    point with 200 observations (more than a window: the long-run path), 8 points with one observation, 9 with four."""
-    import sfmba
-    from sfmba.synthetic import BAProblem
-    base = sfmba.make_problem(8, 40, 400, seed=4)
-    counts = [3] * 21 + [5] + [200] + [1] * 8 + [4] * 9
-    pi = np.repeat(np.arange(40), counts)
-    ci = (np.arange(len(pi)) * 3 + pi) % 8
-    args = (8, 40, ci, pi, np.zeros((len(pi), 2)), base.K)
-    rng = np.random.default_rng(7)
-    uv = orc.compute_residuals(base.x_true, *args).reshape(-1, 2) + rng.normal(0.0, 0.5, (len(pi), 2))
-    return BAProblem(8, 40, ci, pi, uv, base.K, base.x0, base.x_true)
 
 
 CASES = ("tiny", "medium", "hand_built", "gaps", "held_camera")

@@ -7,7 +7,8 @@ five function evaluations, on the hand-built problem of tests/entry_bounds.py.  
 of that file's case tables and of tests/entry_bounds32.py's (cam_chunk, rhsrec, xcd_chunks, xcd_cam, pcg_mixed,
 pcg_mixed_b, and sweep_rc / vec_lds, which also decide pcg_fused and round_blocks) and with precond = 0, and writes every returned array to
 DIR/solver_bits_<a|b>.npz (DIR: a fresh temporary folder unless --out names one).  An entry that a form refuses
-(step_products in 32-bit storage, rhs_precond on stored fp32 blocks) is recorded by its message and listed in the report.
+(rhs_precond on stored fp32 blocks; step_products in 32-bit storage by a library older than its fp32 form, against which
+the newer one then shows those arrays as differing) is recorded by its message and listed in the report.
 The parent compares the two files byte for byte."""
 import os
 import subprocess
