@@ -1157,6 +1157,58 @@ __device__ __forceinline__ void recompute_blocks(const Recompute& rc, const doub
     observe<true>(tl, Xp[0], Xp[1], Xp[2], 0.0, 0.0, rc.K, rx, ry, jc, jp);
 }
 
+// ---- pieces shared by the point-major kernels (pass A, k_jdot, k_backsub; stored and row form) ----
+// z = Vinv y: the packed symmetric 3x3 block vi = (00 01 02 11 12 22) times a vector; entry k (a constant where it is used):
+//     k = 0: vi[0] y0 + vi[1] y1 + vi[2] y2,   k = 1: vi[1] y0 + vi[3] y1 + vi[4] y2,   k = 2: vi[2] y0 + vi[4] y1 + vi[5] y2
+__device__ __forceinline__ double vinv_row(const double* vi, const double* y, int k) {
+    return vi[k] * y[0] + vi[k == 0 ? 1 : 2 + k] * y[1] + vi[k == 0 ? 2 : 3 + k] * y[2];
+}
+// pass A's result z_p = Vinv_p y_p, entries 3..5 of the point's fp64 record.  Entry by entry into the record, not through
+// a three-vector: the sweeps' schedules have each store behind its own products, and the record's address formed once.
+__device__ __forceinline__ void store_z64(double* __restrict__ rec, const double* vi, const double* y) {
+    rec[3] = vinv_row(vi, y, 0);
+    rec[4] = vinv_row(vi, y, 1);
+    rec[5] = vinv_row(vi, y, 2);
+}
+// Inside the two-kernel PCG (ctrl2 != null) `vin` is the base of the ping-pong vector sets: the control block of launch L
+// (written by the previous update) says which set is current; `vin` moves to that set's vector `plane`.  False when the
+// solve is finished (grid-uniform): the launch has nothing to do.
+__device__ __forceinline__ bool pcg_current_set(const PcgCtrl* __restrict__ ctrl2, int L, int plane, int n6,
+                                                const double* __restrict__& vin) {
+    if (ctrl2 != nullptr) {
+        const PcgCtrl* __restrict__ ctrl = ctrl2 + (L & 1);
+        if (ctrl->done != 0) return false;
+        vin += (size_t)((ctrl->iters & 1) * kPcgVecs + plane) * n6;
+    }
+    return true;
+}
+// the six entries of camera `cam` out of a plane-major vector [6][C]
+__device__ __forceinline__ void cam_gather6(const double* __restrict__ planes, int C, int cam, double* u) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) u[k] = planes[(size_t)k * C + cam];
+}
+// (t0, t1) = Jc_i v_c: the 2x6 camera block times camera c's row of a camera-major vector (48-byte rows, 16-byte aligned
+// in LDS and in global memory: three 128-bit reads)
+__device__ __forceinline__ void cam_row_dot(const double* __restrict__ vv, int c, const double* jc, double& t0, double& t1) {
+    const double2* a2 = reinterpret_cast<const double2*>(vv + 6 * c);
+    const double2 a01 = a2[0], a23 = a2[1], a45 = a2[2];
+    const double a[6] = {a01.x, a01.y, a23.x, a23.y, a45.x, a45.y};
+    t0 = 0.0; t1 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { t0 += jc[k] * a[k]; t1 += jc[6 + k] * a[k]; }
+}
+// part[block] = sum |t1|^2 of the workgroup, waves added in fixed order
+__device__ __forceinline__ void jdot_block_sum(double acc, double* red, double* __restrict__ part, int n_waves) {
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int k = 0; k < n_waves; ++k) s += red[k];
+        part[blockIdx.x] = s;
+    }
+}
+
 template <bool LDS_VEC, bool JFREE = false>
 __global__ __launch_bounds__(kSweepThreads) void k_jdot(ObsArrays o, const double* __restrict__ sgc,
                                                         const double* __restrict__ sgp, int N, int C,
@@ -1166,7 +1218,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_jdot(ObsArrays o, const doubl
     extern __shared__ __align__(16) double smem[];
     __shared__ double red[kWavesPerSweepBlock];
     const int nwork = pb.part != nullptr ? (int)gridDim.x - 1 : (int)gridDim.x;
-    if ((int)blockIdx.x == nwork) { finish_in_block(pb); return; }      // rider block: another kernel's sums
+    if ((int)blockIdx.x == nwork) { finish_in_block(pb); return; }      // rider block: another kernel's sums (as k_jdot_rc)
     if (LDS_VEC) {
         for (int i = threadIdx.x; i < 6 * C; i += blockDim.x) smem[i] = sgc[i];
         __syncthreads();
@@ -1178,26 +1230,15 @@ __global__ __launch_bounds__(kSweepThreads) void k_jdot(ObsArrays o, const doubl
         double jc[12], jp[6];
         if (JFREE) recompute_blocks(rc, smem, o.cam_idx[i], o.pt_idx[i], jc, jp);
         else load_blocks(o, i, jc, jp);
-        const double2* a2 = reinterpret_cast<const double2*>(vc + 6 * o.cam_idx[i]);    // 16-byte aligned rows
-        const double2 a01 = a2[0], a23 = a2[1], a45 = a2[2];
-        const double a[6] = {a01.x, a01.y, a23.x, a23.y, a45.x, a45.y};
+        double t0, t1v;
+        cam_row_dot(vc, o.cam_idx[i], jc, t0, t1v);
         const double* b = sgp + 3 * (size_t)o.pt_idx[i];
-        double t0 = 0.0, t1v = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { t0 += jc[k] * a[k]; t1v += jc[6 + k] * a[k]; }
 #pragma unroll
         for (int k = 0; k < 3; ++k) { t0 += jp[k] * b[k]; t1v += jp[3 + k] * b[k]; }
         store_pair(t1, o.f32, i, t0, t1v);
         acc += t0 * t0 + t1v * t1v;
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s += red[k];
-        part[blockIdx.x] = s;
-    }
+    jdot_block_sum(acc, red, part, (int)(blockDim.x >> 6));
 }
 
 // Regularisation of the damped Gauss-Newton step from the 1-D Cauchy problem along -g_h
@@ -1708,12 +1749,8 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep(
             for (int k = 0; k < 6; ++k) smem[6 * threadIdx.x + k] = uu[k];
         }
         __syncthreads();
-    } else if (ctrl2 != nullptr) {
-        // inside the two-kernel PCG: `vin` is the base of the ping-pong vector sets; the control block of this
-        // launch (written by the previous k_pcg_update) says which set is current
-        const PcgCtrl* __restrict__ ctrl = ctrl2 + (L & 1);
-        if (ctrl->done != 0) return;                         // grid-uniform
-        vin += (size_t)((ctrl->iters & 1) * kPcgVecs + (LDS_VEC ? kPcgU : kPcgUcm)) * n6;
+    } else if (!pcg_current_set(ctrl2, L, LDS_VEC ? kPcgU : kPcgUcm, n6, vin)) {
+        return;
     }
     if (LDS_VEC && !FUSED) {
         for (int e = threadIdx.x; e < n6; e += blockDim.x) {       // e = k*C + c (plane-major global, coalesced)
@@ -1724,14 +1761,6 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep(
     }
     // v: LDS table, or the camera-major copy [C][6] in global memory (L2) when 6 C doubles exceed the LDS
     const double* __restrict__ vv = LDS_VEC ? smem : vin;
-    auto jcv = [&](const double* jc, int cc, double& t0, double& t1) {    // rows of 48 bytes, 16-byte aligned
-        const double2* a2 = reinterpret_cast<const double2*>(vv + 6 * cc);
-        const double2 a01 = a2[0], a23 = a2[1], a45 = a2[2];
-        const double a[6] = {a01.x, a01.y, a23.x, a23.y, a45.x, a45.y};
-        t0 = 0.0; t1 = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { t0 += jc[k] * a[k]; t1 += jc[6 + k] * a[k]; }
-    };
 
     while (s < s_end) {
         // ---- request the next step's indices ---------------------------------------------------
@@ -1749,17 +1778,12 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep(
             for (int j = cur.x + lane; j < run_end; j += 64) {
                 load_blocks(o, j, jc, jp);
                 double t0, t1;
-                jcv(jc, o.cam_idx[j], t0, t1);
+                cam_row_dot(vv, o.cam_idx[j], jc, t0, t1);
                 y[0] += jp[0] * t0 + jp[3] * t1; y[1] += jp[1] * t0 + jp[4] * t1;
                 y[2] += jp[2] * t0 + jp[5] * t1;
             }
             y[0] = wave_sum(y[0]); y[1] = wave_sum(y[1]); y[2] = wave_sum(y[2]);
-            if (lane == 0) {
-                const double* vi = Vinv + kVinvRow * (size_t)pp;
-                zout[(size_t)kRec * pp + 3] = vi[0] * y[0] + vi[1] * y[1] + vi[2] * y[2];
-                zout[(size_t)kRec * pp + 4] = vi[1] * y[0] + vi[3] * y[1] + vi[4] * y[2];
-                zout[(size_t)kRec * pp + 5] = vi[2] * y[0] + vi[4] * y[1] + vi[5] * y[2];
-            }
+            if (lane == 0) store_z64(zout + (size_t)kRec * pp, Vinv + kVinvRow * (size_t)pp, y);
         } else {
             const bool act = lane < cur.y;
             double vi[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -1768,18 +1792,14 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep(
 #pragma unroll                                     // every lane of a run reads its point's block: no dependent
                 for (int k = 0; k < 6; ++k) vi[k] = Vinv[kVinvRow * (size_t)p + k];       // gather after the reduction
                 double t0, t1;
-                jcv(jc, c, t0, t1);
+                cam_row_dot(vv, c, jc, t0, t1);
                 y[0] = jp[0] * t0 + jp[3] * t1; y[1] = jp[1] * t0 + jp[4] * t1;
                 y[2] = jp[2] * t0 + jp[5] * t1;
             }
             const int key = act ? p : -1 - lane;                  // run key = point index
             seg_reduce_serial<3>(y, key, lane);
             const int prev = lane_below(key, lane);
-            if (act && (lane == 0 || prev != key)) {              // first lane of the point's run
-                zout[(size_t)kRec * p + 3] = vi[0] * y[0] + vi[1] * y[1] + vi[2] * y[2];
-                zout[(size_t)kRec * p + 4] = vi[1] * y[0] + vi[3] * y[1] + vi[4] * y[2];
-                zout[(size_t)kRec * p + 5] = vi[2] * y[0] + vi[4] * y[1] + vi[5] * y[2];
-            }
+            if (act && (lane == 0 || prev != key)) store_z64(zout + (size_t)kRec * p, vi, y);     // first lane of the point's run
         }
         cur = nxt; i = in_; c = cn; p = pn;
         ++s;
@@ -1872,8 +1892,8 @@ __device__ __forceinline__ void rc_row_products(const double2* __restrict__ row,
 __global__ __launch_bounds__(256) void k_rc_table(const double* __restrict__ camtab, const double* __restrict__ u_planes,
                                                   const PcgCtrl* __restrict__ ctrl2, int L, int C,
                                                   double* __restrict__ rctab) {
-    if (ctrl2 != nullptr) {
-        const PcgCtrl* __restrict__ ctrl = ctrl2 + (L & 1);
+    if (ctrl2 != nullptr) {                                   // pcg_current_set, written out: through the helper the
+        const PcgCtrl* __restrict__ ctrl = ctrl2 + (L & 1);   // offset takes one more scalar multiply here
         if (ctrl->done != 0) return;                          // grid-uniform
         u_planes += (size_t)((ctrl->iters & 1) * kPcgVecs + kPcgU) * 6 * C;
     }
@@ -1884,17 +1904,24 @@ __global__ __launch_bounds__(256) void k_rc_table(const double* __restrict__ cam
 #pragma unroll
     for (int k = 0; k < kCamRT; ++k) row[k] = mt[k];
     double u[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) u[k] = u_planes[(size_t)k * C + cam];
+    cam_gather6(u_planes, C, cam, u);
     rc_put_au(camtab + cam_wbc_offset(C), C, cam, u, rctab);
 }
 
+// a' and u_T of camera `cam` from its six entries u, rounded to fp32, into the camera's row of the fp32 table
+__device__ __forceinline__ void rc32_put_au(const double* __restrict__ wbc, int C, int cam, const double* u, float* __restrict__ tab) {
+    double ap[3];
+    cam_aprime(wbc[cam], wbc[(size_t)C + cam], wbc[2 * (size_t)C + cam], wbc[3 * (size_t)C + cam], wbc[4 * (size_t)C + cam], u, ap);
+    float4* __restrict__ row = reinterpret_cast<float4*>(tab + (size_t)kRc32Row * cam);
+    row[3] = make_float4((float)ap[0], (float)ap[1], (float)ap[2], (float)u[3]);
+    row[4] = make_float4((float)u[4], (float)u[5], 0.f, 0.f);
+}
 // the same table with fp32 operands (mixed-precision product): [C][20] float = R | T - o (from rt32) | a' | u_T . .
 __global__ __launch_bounds__(256) void k_rc_table32(const double* __restrict__ camtab, const float* __restrict__ rt32,
                                                     const double* __restrict__ u_planes, const PcgCtrl* __restrict__ ctrl2,
                                                     int L, int C, float* __restrict__ rctab32) {
-    if (ctrl2 != nullptr) {
-        const PcgCtrl* __restrict__ ctrl = ctrl2 + (L & 1);
+    if (ctrl2 != nullptr) {                                   // pcg_current_set, written out: through the helper the
+        const PcgCtrl* __restrict__ ctrl = ctrl2 + (L & 1);   // offset takes one more scalar multiply here
         if (ctrl->done != 0) return;                          // grid-uniform
         u_planes += (size_t)((ctrl->iters & 1) * kPcgVecs + kPcgU) * 6 * C;
     }
@@ -1903,14 +1930,9 @@ __global__ __launch_bounds__(256) void k_rc_table32(const double* __restrict__ c
     const float4* __restrict__ src = reinterpret_cast<const float4*>(rt32 + (size_t)kRt32 * cam);
     float4* __restrict__ row = reinterpret_cast<float4*>(rctab32 + (size_t)kRc32Row * cam);
     row[0] = src[0]; row[1] = src[1]; row[2] = src[2];
-    const double* __restrict__ wbc = camtab + cam_wbc_offset(C);
     double u[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) u[k] = u_planes[(size_t)k * C + cam];
-    double ap[3];
-    cam_aprime(wbc[cam], wbc[(size_t)C + cam], wbc[2 * (size_t)C + cam], wbc[3 * (size_t)C + cam], wbc[4 * (size_t)C + cam], u, ap);
-    row[3] = make_float4((float)ap[0], (float)ap[1], (float)ap[2], (float)u[3]);
-    row[4] = make_float4((float)u[4], (float)u[5], 0.f, 0.f);
+    cam_gather6(u_planes, C, cam, u);
+    rc32_put_au(camtab + cam_wbc_offset(C), C, cam, u, rctab32);
 }
 // five LDS-DMA pieces per 80-byte row (rows_request with the fp32 table)
 __device__ __forceinline__ void rows_request32(const float* __restrict__ table, int cam, int lane, float* slab) {
@@ -1960,16 +1982,11 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep_rc(
         if (!pcg_fused_update(pf, acc, C, L, uu)) return;
         if ((int)threadIdx.x < C) put_au(threadIdx.x, uu);
     } else {
-        if (ctrl2 != nullptr) {                               // two-kernel PCG: vin = base of the vector sets
-            const PcgCtrl* __restrict__ ctrl = ctrl2 + (L & 1);
-            if (ctrl->done != 0) return;                      // grid-uniform
-            vin += (size_t)((ctrl->iters & 1) * kPcgVecs + kPcgU) * n6;
-        }
+        if (!pcg_current_set(ctrl2, L, kPcgU, n6, vin)) return;           // two-kernel PCG: vin = base of the vector sets
         if (!GTAB) {
             for (int cam = threadIdx.x; cam < C; cam += blockDim.x) {     // vin: plane-major [6][C]
                 double u[6];
-#pragma unroll
-                for (int k = 0; k < 6; ++k) u[k] = vin[(size_t)k * C + cam];
+                cam_gather6(vin, C, cam, u);
                 put_au(cam, u);
             }
         }
@@ -2052,23 +2069,14 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep_rc(
                 y[0] += w[0]; y[1] += w[1]; y[2] += w[2];
             }
             y[0] = wave_sum(y[0]); y[1] = wave_sum(y[1]); y[2] = wave_sum(y[2]);
-            if (lane == 0) {
-                const double* vl = Vinv + kVinvRow * (size_t)pp;
-                zout[(size_t)kRec * pp + 3] = vl[0] * y[0] + vl[1] * y[1] + vl[2] * y[2];
-                zout[(size_t)kRec * pp + 4] = vl[1] * y[0] + vl[3] * y[1] + vl[4] * y[2];
-                zout[(size_t)kRec * pp + 5] = vl[2] * y[0] + vl[4] * y[1] + vl[5] * y[2];
-            }
+            if (lane == 0) store_z64(zout + (size_t)kRec * pp, Vinv + kVinvRow * (size_t)pp, y);
         } else {
             const bool act = lane < cur.y;
             if (!GTAB && act) contrib(row_of(c), X[0], X[1], X[2], y);
             const int key = act ? p : -1 - lane;
             seg_reduce_serial<3>(y, key, lane);
             const int prev = lane_below(key, lane);
-            if (act && (lane == 0 || prev != key)) {
-                zout[(size_t)kRec * p + 3] = vi[0] * y[0] + vi[1] * y[1] + vi[2] * y[2];
-                zout[(size_t)kRec * p + 4] = vi[1] * y[0] + vi[3] * y[1] + vi[4] * y[2];
-                zout[(size_t)kRec * p + 5] = vi[2] * y[0] + vi[4] * y[1] + vi[5] * y[2];
-            }
+            if (act && (lane == 0 || prev != key)) store_z64(zout + (size_t)kRec * p, vi, y);
         }
         cur = nxt; nxt = nn; nn = n3;
         c = cn; p = pn; cn = c2; pn = p2;
@@ -2106,28 +2114,18 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep_rc32(
     if (s + 1 < s_end) nxt = st.steps[s + 1];
     if (s + 2 < s_end) nn = st.steps[s + 2];
     const double* __restrict__ wbc = camtab + cam_wbc_offset(C);                  // w, b, c plane-major [5][C]
-    auto put_au = [&](int cam, const double* u) {          // a' and u_T of camera `cam` from its u (6), rounded to fp32
-        double ap[3];
-        cam_aprime(wbc[cam], wbc[(size_t)C + cam], wbc[2 * (size_t)C + cam], wbc[3 * (size_t)C + cam], wbc[4 * (size_t)C + cam], u, ap);
-        float4* __restrict__ row = reinterpret_cast<float4*>(smem + (size_t)kRc32Row * cam);
-        row[3] = make_float4((float)ap[0], (float)ap[1], (float)ap[2], (float)u[3]);
-        row[4] = make_float4((float)u[4], (float)u[5], 0.f, 0.f);
-    };
+    auto put_au = [&](int cam, const double* u) { rc32_put_au(wbc, C, cam, u, smem); };
     if (FUSED) {
         double uu[6];
         if (!pcg_fused_update(pf, acc, C, L, uu)) return;
         if ((int)threadIdx.x < C) put_au(threadIdx.x, uu);
     } else {
-        if (ctrl2 != nullptr) {                               // two-kernel PCG: vin = base of the vector sets
-            const PcgCtrl* __restrict__ ctrl = ctrl2 + (L & 1);
-            if (ctrl->done != 0) return;                      // grid-uniform
-            vin += (size_t)((ctrl->iters & 1) * kPcgVecs + kPcgU) * n6;
-        }
+        if (!pcg_current_set(ctrl2, L, kPcgU, n6, vin)) return;           // two-kernel PCG: vin = base of the vector sets
         if (!GTAB) {
             for (int cam = threadIdx.x; cam < C; cam += blockDim.x) {     // vin: plane-major [6][C]
                 double u[6];
-#pragma unroll
-                for (int k = 0; k < 6; ++k) u[k] = vin[(size_t)k * C + cam];
+#pragma unroll                                      // cam_gather6, written out: through the helper
+                for (int k = 0; k < 6; ++k) u[k] = vin[(size_t)k * C + cam];      // <false, false, false> takes two more VGPRs
                 put_au(cam, u);
             }
         }
@@ -2180,15 +2178,11 @@ __global__ __launch_bounds__(kSweepThreads) void k_point_sweep_rc32(
     auto row_of = [&](int cc) { return reinterpret_cast<const float4*>(table + (size_t)kRc32Row * cc); };
     auto store_z = [&](int pp, const double* vv, const double* y) {
         if (Z64) {
-            double* __restrict__ zd = zout64 + (size_t)kRec * pp;
-            zd[3] = vv[0] * y[0] + vv[1] * y[1] + vv[2] * y[2];
-            zd[4] = vv[1] * y[0] + vv[3] * y[1] + vv[4] * y[2];
-            zd[5] = vv[2] * y[0] + vv[4] * y[1] + vv[5] * y[2];
+            store_z64(zout64 + (size_t)kRec * pp, vv, y);
         } else {
             float* __restrict__ zp = rec32 + (size_t)kRec32 * pp;
-            zp[3] = (float)(vv[0] * y[0] + vv[1] * y[1] + vv[2] * y[2]);
-            *reinterpret_cast<float2*>(zp + 4) = make_float2((float)(vv[1] * y[0] + vv[3] * y[1] + vv[4] * y[2]),
-                                                             (float)(vv[2] * y[0] + vv[4] * y[1] + vv[5] * y[2]));
+            zp[3] = (float)vinv_row(vv, y, 0);
+            *reinterpret_cast<float2*>(zp + 4) = make_float2((float)vinv_row(vv, y, 1), (float)vinv_row(vv, y, 2));
         }
     };
     auto load_point = [&](bool on, int pp, float* X, double* vi) {
@@ -3364,6 +3358,40 @@ struct FinalUpdate {
     PcgCtrl* __restrict__ ctrl2;
     int L;                               // the launch of pass A that was left out
 };
+// ---- pieces shared by k_backsub and its row form k_backsub_rc ----
+// The window of 64 observations at `pos`: lane's observation i, its point p and the point's run [sb, se); the first
+// n_take lanes hold runs that end inside the window (0: one point with more observations than the window holds).
+struct BacksubWindow { int i, p, sb, se, n_take; };
+__device__ __forceinline__ BacksubWindow backsub_window(const int* __restrict__ pt_idx, const int* __restrict__ pt_ptr,
+                                                        int pos, int end, int lane) {
+    const int i = pos + lane;
+    const bool in = i < end;
+    const int p = in ? pt_idx[i] : pt_idx[pos];
+    const int sb = pt_ptr[p], se = pt_ptr[p + 1];
+    const bool complete = in && (se <= pos + 64);
+    return {i, p, sb, se, (int)__popcll(__ballot(complete))};
+}
+// dp of a run, from the lane at its head to every lane of the run
+__device__ __forceinline__ void backsub_from_head(bool act, int lane, const BacksubWindow& w, double& z0, double& z1, double& z2) {
+    const int head = act ? lane - (w.i - w.sb) : lane;
+    z0 = __shfl(z0, head); z1 = __shfl(z1, head); z2 = __shfl(z2, head);
+}
+// dp_p = Vinv_p (-g_p - y), stored
+__device__ __forceinline__ void backsub_solve_point(const double* __restrict__ Vinv, const double* __restrict__ gp,
+                                                    double* __restrict__ dp, int p, const double* y,
+                                                    double& z0, double& z1, double& z2) {
+    const double* vi = Vinv + kVinvRow * (size_t)p;
+    const double b[3] = {-gp[3 * (size_t)p] - y[0], -gp[3 * (size_t)p + 1] - y[1], -gp[3 * (size_t)p + 2] - y[2]};
+    z0 = vinv_row(vi, b, 0); z1 = vinv_row(vi, b, 1); z2 = vinv_row(vi, b, 2);
+    dp[3 * (size_t)p] = z0; dp[3 * (size_t)p + 1] = z1; dp[3 * (size_t)p + 2] = z2;
+}
+// camera entries of q5..q8: element e of the parameter vector, step pe
+__device__ __forceinline__ void backsub_cam_dots(const double* __restrict__ gvec, const double* __restrict__ si,
+                                                 const double* __restrict__ sg, size_t e, double pe, double* q) {
+    const double s = si[e];
+    q[0] += gvec[e] * pe; q[1] += (pe * s) * (pe * s); q[2] += sg[e] * pe; q[3] += pe * pe;
+}
+
 template <bool LDS_VEC, bool JFREE = false>
 __global__ __launch_bounds__(kSweepThreads) void k_backsub(
     const int2* __restrict__ ranges, int n_ranges, ObsArrays o, const double* __restrict__ dc_planes,
@@ -3375,6 +3403,8 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub(
     extern __shared__ __align__(16) double smem[];
     __shared__ double red[kBacksubCols * kWavesPerSweepBlock];
     if (LDS_VEC && fu.part != nullptr) {
+        // (the same prologue stands in k_backsub_rc up to the LDS write; its fma(alpha, pe, xe) and this xe + alpha * pe are
+        // the same v_fma_f64 under -ffp-contract=fast)
         const int n6 = 6 * C, cam = threadIdx.x;
         const PcgCtrl ci = fu.ctrl2[fu.L & 1];
         PcgCtrl co = ci;
@@ -3429,22 +3459,9 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub(
     };
     double g12 = 0.0, g22 = 0.0;
     double qs[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};       // q5..q8: [0..3] points, [4..7] cameras
-    auto dots = [&](double* q, size_t e, double pe) {              // element e of the parameter vector, step pe
-        const double s = si[e];
-        q[0] += gvec[e] * pe; q[1] += (pe * s) * (pe * s); q[2] += sg[e] * pe; q[3] += pe * pe;
-    };
-
-    auto jcv = [&](const double* jc, int c, double& t0, double& t1v) {
-        // 48-byte rows, 16-byte aligned in both placements: three 128-bit reads
-        const double2* a2 = reinterpret_cast<const double2*>(vv + 6 * c);
-        const double2 a01 = a2[0], a23 = a2[1], a45 = a2[2];
-        const double a[6] = {a01.x, a01.y, a23.x, a23.y, a45.x, a45.y};
-        t0 = 0.0; t1v = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { t0 += jc[k] * a[k]; t1v += jc[6 + k] * a[k]; }
-    };
     // point entries: g is g_p itself and D^2 g = g / s^2 exactly as k_update_scale formed it, so only the
-    // three scale entries have to be fetched
+    // three scale entries have to be fetched  (the same text stands in k_backsub_rc: as a helper it changes that kernel's
+    // schedule, 112 VGPRs for 122 and 61 more instructions)
     auto point_dots = [&](int p, const double* s3, double z0, double z1, double z2) {
         const double z[3] = {z0, z1, z2};
 #pragma unroll
@@ -3452,15 +3469,6 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub(
             const double s_ = s3[k], ge = gp[3 * (size_t)p + k], pe = z[k];
             qs[0] += ge * pe; qs[1] += (pe * s_) * (pe * s_); qs[2] += (ge / (s_ * s_)) * pe; qs[3] += pe * pe;
         }
-    };
-    auto solve_point = [&](int p, const double* y, double& z0, double& z1, double& z2) {
-        const double* vi = Vinv + kVinvRow * (size_t)p;
-        const double b0 = -gp[3 * (size_t)p] - y[0], b1 = -gp[3 * (size_t)p + 1] - y[1],
-                     b2 = -gp[3 * (size_t)p + 2] - y[2];
-        z0 = vi[0] * b0 + vi[1] * b1 + vi[2] * b2;
-        z1 = vi[1] * b0 + vi[3] * b1 + vi[4] * b2;
-        z2 = vi[2] * b0 + vi[4] * b1 + vi[5] * b2;
-        dp[3 * (size_t)p] = z0; dp[3 * (size_t)p + 1] = z1; dp[3 * (size_t)p + 2] = z2;
     };
     auto gram = [&](int i, const double* jp, double t0, double t1v, double z0, double z1, double z2) {
         const double a0 = t0 + jp[0] * z0 + jp[1] * z1 + jp[2] * z2;
@@ -3471,32 +3479,28 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub(
     };
 
     while (pos < end) {
-        const int i = pos + lane;
-        const bool in = i < end;
-        const int p = in ? o.pt_idx[i] : o.pt_idx[pos];
-        const int sb = o.pt_ptr[p], se = o.pt_ptr[p + 1];
-        const bool complete = in && (se <= pos + 64);
-        const int n_take = __popcll(__ballot(complete));
+        const BacksubWindow w = backsub_window(o.pt_idx, o.pt_ptr, pos, end, lane);
+        const int i = w.i, p = w.p, sb = w.sb, n_take = w.n_take;
         double jc[12], jp[6];
         if (n_take == 0) {
-            const int run_end = __shfl(se, 0);
+            const int run_end = __shfl(w.se, 0);
             const int pp = __shfl(p, 0);
             double y[3] = {0.0, 0.0, 0.0};
             for (int j = pos + lane; j < run_end; j += 64) {
                 blocks_of(j, pp, jc, jp);
                 double t0, t1v;
-                jcv(jc, o.cam_idx[j], t0, t1v);
+                cam_row_dot(vv, o.cam_idx[j], jc, t0, t1v);
                 y[0] += jp[0] * t0 + jp[3] * t1v; y[1] += jp[1] * t0 + jp[4] * t1v;
                 y[2] += jp[2] * t0 + jp[5] * t1v;
             }
             y[0] = wave_sum(y[0]); y[1] = wave_sum(y[1]); y[2] = wave_sum(y[2]);
             double z0, z1, z2;
-            solve_point(pp, y, z0, z1, z2);              // every lane writes the same values
+            backsub_solve_point(Vinv, gp, dp, pp, y, z0, z1, z2);              // every lane writes the same values
             if (lane == 0) point_dots(pp, si + 6 * (size_t)C + 3 * (size_t)pp, z0, z1, z2);
             for (int j = pos + lane; j < run_end; j += 64) {
                 blocks_of(j, pp, jc, jp);
                 double t0, t1v;
-                jcv(jc, o.cam_idx[j], t0, t1v);
+                cam_row_dot(vv, o.cam_idx[j], jc, t0, t1v);
                 gram(j, jp, t0, t1v, z0, z1, z2);
             }
             pos = run_end;
@@ -3510,14 +3514,13 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub(
             blocks_of(i, p, jc, jp);
 #pragma unroll
             for (int k = 0; k < 3; ++k) s3[k] = si[6 * (size_t)C + 3 * (size_t)p + k];
-            jcv(jc, o.cam_idx[i], t0, t1v);
+            cam_row_dot(vv, o.cam_idx[i], jc, t0, t1v);
             y[0] = jp[0] * t0 + jp[3] * t1v; y[1] = jp[1] * t0 + jp[4] * t1v;
             y[2] = jp[2] * t0 + jp[5] * t1v;
         }
         seg_reduce_serial<3>(y, act ? sb : -1 - lane, lane);
-        if (act && i == sb) { solve_point(p, y, z0, z1, z2); point_dots(p, s3, z0, z1, z2); }
-        const int head = act ? lane - (i - sb) : lane;
-        z0 = __shfl(z0, head); z1 = __shfl(z1, head); z2 = __shfl(z2, head);
+        if (act && i == sb) { backsub_solve_point(Vinv, gp, dp, p, y, z0, z1, z2); point_dots(p, s3, z0, z1, z2); }
+        backsub_from_head(act, lane, w, z0, z1, z2);
         if (act) gram(i, jp, t0, t1v, z0, z1, z2);
         pos += n_take;
     }
@@ -3527,9 +3530,10 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub(
         const int per = (6 * C + (int)gridDim.x - 1) / (int)gridDim.x;
         for (int t = threadIdx.x; t < per; t += blockDim.x) {
             const int e = (int)blockIdx.x * per + t;
-            if (e < 6 * C) dots(qs + 4, (size_t)e, vv[e]);
+            if (e < 6 * C) backsub_cam_dots(gvec, si, sg, (size_t)e, vv[e], qs + 4);
         }
     }
+    // (the same block-sum tail stands in k_backsub_rc: as a helper it costs that kernel two VGPRs)
     double row[kBacksubCols];
     row[0] = wave_sum(g12);
     row[1] = wave_sum(g22);
@@ -3565,7 +3569,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_jdot_rc(
     extern __shared__ __align__(16) double smem[];
     __shared__ double red[kWavesPerSweepBlock];
     const int nwork = pb.part != nullptr ? (int)gridDim.x - 1 : (int)gridDim.x;
-    if ((int)blockIdx.x == nwork) { finish_in_block(pb); return; }      // rider block: another kernel's sums
+    if ((int)blockIdx.x == nwork) { finish_in_block(pb); return; }      // rider block: another kernel's sums (as k_jdot)
     const int stride = nwork * (int)blockDim.x;
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     int c = 0, p = 0;
@@ -3593,14 +3597,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_jdot_rc(
         acc += t0 * t0 + t1v * t1v;
         i = in; c = cn; p = pn;
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s += red[k];
-        part[blockIdx.x] = s;
-    }
+    jdot_block_sum(acc, red, part, (int)(blockDim.x >> 6));
 }
 
 // k_backsub in row form: everything k_backsub<true> does (the FinalUpdate prologue included; its comment applies), with the
@@ -3642,7 +3639,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
             double u[6];
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
-                u[k] = add ? fma(alpha, pe[k], xe[k]) : xe[k];
+                u[k] = add ? fma(alpha, pe[k], xe[k]) : xe[k];                // (k_backsub's xe + alpha * pe: the same v_fma_f64)
                 if (blockIdx.x == 0) dc[6 * cam + k] = u[k];              // (the step vector only: see k_backsub)
             }
             rc_put_au(q, cam, u, smem);
@@ -3670,7 +3667,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
     auto products = [&](int j, double X, double Y, double Z, double* jp, double* t) {      // observation j, its point
         rc_row_products(reinterpret_cast<const double2*>(smem + (size_t)kRcRow * cam_idx[j]), X, Y, Z, jp, t);
     };
-    // point entries: g is g_p itself and D^2 g = g / s^2 exactly as k_update_scale formed it
+    // point entries: g is g_p itself and D^2 g = g / s^2 exactly as k_update_scale formed it (k_backsub's point_dots)
     auto point_dots = [&](int p, const double* s3, double z0, double z1, double z2) {
         const double z[3] = {z0, z1, z2};
 #pragma unroll
@@ -3678,15 +3675,6 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
             const double s_ = s3[k], ge = gp[3 * (size_t)p + k], pe = z[k];
             qs[0] += ge * pe; qs[1] += (pe * s_) * (pe * s_); qs[2] += (ge / (s_ * s_)) * pe; qs[3] += pe * pe;
         }
-    };
-    auto solve_point = [&](int p, const double* y, double& z0, double& z1, double& z2) {
-        const double* vi = Vinv + kVinvRow * (size_t)p;
-        const double b0 = -gp[3 * (size_t)p] - y[0], b1 = -gp[3 * (size_t)p + 1] - y[1],
-                     b2 = -gp[3 * (size_t)p + 2] - y[2];
-        z0 = vi[0] * b0 + vi[1] * b1 + vi[2] * b2;
-        z1 = vi[1] * b0 + vi[3] * b1 + vi[4] * b2;
-        z2 = vi[2] * b0 + vi[4] * b1 + vi[5] * b2;
-        dp[3 * (size_t)p] = z0; dp[3 * (size_t)p + 1] = z1; dp[3 * (size_t)p + 2] = z2;
     };
     auto gram = [&](int i, const double* jp, const double* t, double z0, double z1, double z2) {
         const double a0 = t[0] + jp[0] * z0 + jp[1] * z1 + jp[2] * z2;
@@ -3697,15 +3685,11 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
     };
 
     while (pos < end) {
-        const int i = pos + lane;
-        const bool in = i < end;
-        const int p = in ? pt_idx[i] : pt_idx[pos];
-        const int sb = pt_ptr[p], se = pt_ptr[p + 1];
-        const bool complete = in && (se <= pos + 64);
-        const int n_take = __popcll(__ballot(complete));
+        const BacksubWindow w = backsub_window(pt_idx, pt_ptr, pos, end, lane);
+        const int i = w.i, p = w.p, sb = w.sb, n_take = w.n_take;
         double jp[6], t[2];
         if (n_take == 0) {                             // one point with more observations than the window holds
-            const int run_end = __shfl(se, 0);
+            const int run_end = __shfl(w.se, 0);
             const int pp = __shfl(p, 0);
             const double* __restrict__ Xp = pts + 3 * (size_t)pp;
             const double X = Xp[0], Y = Xp[1], Z = Xp[2];
@@ -3717,7 +3701,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
             }
             y[0] = wave_sum(y[0]); y[1] = wave_sum(y[1]); y[2] = wave_sum(y[2]);
             double z0, z1, z2;
-            solve_point(pp, y, z0, z1, z2);              // every lane writes the same values
+            backsub_solve_point(Vinv, gp, dp, pp, y, z0, z1, z2);              // every lane writes the same values
             if (lane == 0) point_dots(pp, si + 6 * (size_t)C + 3 * (size_t)pp, z0, z1, z2);
             for (int j = pos + lane; j < run_end; j += 64) {
                 products(j, X, Y, Z, jp, t);
@@ -3741,9 +3725,8 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
             y[2] = jp[2] * t[0] + jp[5] * t[1];
         }
         seg_reduce_serial<3>(y, act ? sb : -1 - lane, lane);
-        if (act && i == sb) { solve_point(p, y, z0, z1, z2); point_dots(p, s3, z0, z1, z2); }
-        const int head = act ? lane - (i - sb) : lane;
-        z0 = __shfl(z0, head); z1 = __shfl(z1, head); z2 = __shfl(z2, head);
+        if (act && i == sb) { backsub_solve_point(Vinv, gp, dp, p, y, z0, z1, z2); point_dots(p, s3, z0, z1, z2); }
+        backsub_from_head(act, lane, w, z0, z1, z2);
         if (act) gram(i, jp, t, z0, z1, z2);
         pos += n_take;
     }
@@ -3761,11 +3744,10 @@ __global__ __launch_bounds__(kSweepThreads) void k_backsub_rc(
             } else {
                 pe = dc_planes[(size_t)k * C + cam];
             }
-            const double s = si[e];
-            qs[4] += gvec[e] * pe; qs[5] += (pe * s) * (pe * s); qs[6] += sg[e] * pe; qs[7] += pe * pe;
+            backsub_cam_dots(gvec, si, sg, (size_t)e, pe, qs + 4);
         }
     }
-    double row[kBacksubCols];
+    double row[kBacksubCols];                           // (k_backsub's block-sum tail)
     row[0] = wave_sum(g12);
     row[1] = wave_sum(g22);
 #pragma unroll

@@ -310,6 +310,7 @@ MIXED_CASES = {
     "xcd": ("hand_built", 32, {"xcd_chunks": 1}, dict(_M, xcd_b=1)),
     "mixed_b0": ("hand_built", 32, {"pcg_mixed_b": 0}, dict(_M, mixed_b=0)),
     "mixed_b0_xcd": ("hand_built", 32, {"pcg_mixed_b": 0, "xcd_chunks": 1}, dict(_M, mixed_b=0, xcd_b=1)),
+    "mixed_b0_sweep_rc_g": ("hand_built", 32, {"pcg_mixed_b": 0, "sweep_rc": 2}, dict(_M, mixed_b=0, sweep_rc=0, sweep_rc_g=1)),
     "fp64_storage": ("hand_built", 64, {"pcg_mixed": 1}, _M),
     "fused_1024": ("schur_1024", 32, {}, _M),
     "unfused_1025": ("schur_1025", 32, {}, dict(_M, pcg_fused=0)),

@@ -35,6 +35,9 @@ def cases():
                     seen.add((bits, tuple(sorted(options.items()))))
     for bits in (64, 32):                                         # rhs without the preconditioner: k_cam_schur<1, *>
         seen.update({(bits, (("precond", 0),)), (bits, (("precond", 0), ("sweep_rc", 0)))})
+    seen.add((64, (("rc_consumers", 1),)))                        # k_jdot_rc, k_backsub_rc: step_products and the solve
+    for bits in (64, 32):                                         # k_jdot<false, true>, k_backsub<false, true>
+        seen.add((bits, (("jfree", 1),)))
     for bits, options in sorted(seen):
         yield f"{bits}|" + (",".join(f"{k}={v}" for k, v in options) or "default"), bits, dict(options)
 
