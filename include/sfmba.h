@@ -816,6 +816,60 @@ int  sfmba_solve_from(sfmba_handle* h, const double* x0, double* x_out, const sf
 /* After a successful sfmba_solve: result.fun (2N) and result.grad (6C+3P); either may be NULL. */
 int  sfmba_get_fun_grad(sfmba_handle* h, double* fun_out, double* grad_out);
 
+/* ---- covariance of a solution: camera and point blocks ------------------------------------------ */
+/* How well the solution x is determined.  With r(x) the 2N residuals of sfmba_residuals, J = d r/d x from the analytic
+ * blocks of the solver, D the set of HELD camera parameters and F its complement (every point parameter is free):
+ *   U = J_F^T J_F,  V_p = sum Jp^T Jp (3x3 per point),  W_p = J_F^T Jp,  S = U - sum_p W_p V_p^-1 W_p^T.
+ * kind = 0 (marginal):    Sigma_cc = sigma^2 S^-1 on F (rows and columns in D are zero),
+ *                         Sigma_pp(p) = sigma^2 (V_p^-1 + V_p^-1 W_p^T S^-1 W_p V_p^-1).
+ * kind = 1 (conditional): sigma^2 (U_cc|F)^-1 per camera with the points held, sigma^2 V_p^-1 per point with the cameras
+ *                         held: cheap, available at every size, and optimistic.
+ * sigma^2 = opt.sigma2 if > 0, else sum r^2 / dof with dof = 2N - (free parameters of observed cameras) - 3 (observed
+ * points); dof <= 0: sigma^2 = 1 (info.dof says so).  No damping and no x_scale: the undamped J^T J at the caller's x.
+ *
+ * The held set D is the union of (1) all six parameters of every camera the problem holds (sfmba_set_fixed_cameras),
+ * (2) the call's `hold` list: n_hold indices in [0, 6C), each one camera parameter (6 c + k: k = 0..2 the rotation vector,
+ * 3..5 T), (3) with opt.gauge = 1 (default), ONLY when n_hold == 0 and the problem holds fewer than two cameras, the
+ * usual "first camera plus one baseline coordinate": g0 = the held camera if there is one, else camera 0; g1 = the
+ * observed camera with the largest |T - T_g0| at x (ties: lowest index); all six parameters of g0 and the one T
+ * coordinate of g1 with the largest |T_g1 - T_g0| component (ties: lowest axis).  opt.gauge = 0 adds nothing: with nothing
+ * held S has seven null directions and the call reports RANK_DEFICIENT.  A camera without observations is treated as held
+ * and its blocks are NaN; a point without observations is skipped (pt_status = 3, NaN blocks).  held_out (6C bytes): 0 free,
+ * 1 held, 2 unobserved.
+ *
+ * Rank is decided in the factorisations.  Cameras: a Cholesky pivot d_k <= opt.rank_tol S_kk (default 1e-10) ends the call
+ * with info.status = 1 and info.bad_param = k.  Points: a point whose 3x3 Cholesky has a pivot <= opt.point_tol max diag V_p
+ * (default 1e-12) gets pt_status = 1 (a single-view or otherwise undetermined point); any such point ends the call with
+ * info.status = 2, info.n_bad_points and info.bad_point (the first).  After either, every matrix is NaN while pt_status and
+ * held_out are valid, so the caller can trim the problem and call again.  A rank failure returns 0.
+ *
+ * Outputs (any may be NULL; an array that is not asked for is not downloaded, and the point sweep runs only when pt_cov or
+ * pt_sigma is asked for): cam_cov (C,6,6) the diagonal blocks; cam_full (6C,6C) (kind = 1: block diagonal); cam_sigma
+ * (C,2) sqrt of the largest eigenvalue of the rotation and of the T block; pt_cov (P,3,3); pt_sigma (P) sqrt of the largest
+ * eigenvalue; pt_status (P) 0 fine, 1 undetermined, 3 no observation.  info.cost = 0.5 sum r^2; info.min_pivot_rel the
+ * smallest d_k / S_kk met; info.kernel_us the device time of the call's kernels with opt.profile = 1.
+ *
+ * Returns -1 when no problem is set or x is NULL, an option is NaN or negative, a hold index is out of range or repeated,
+ * the handle is sharded (a shard's covariance is not the problem's), the storage is fp32, or kind = 0 and the problem is
+ * not on the dense form (6 C > 128, or its pair lists were not built); kind = 1 is limited only as the per-camera pass of
+ * sfmba_reprojection_stats is.  The call works on buffers of its own: fun and grad of the last solve and the record the
+ * next solve starts from are as they were.  Same input, same bits: no atomics; every sum runs in a fixed order. */
+typedef struct sfmba_covariance_options {
+    int32_t kind, gauge;
+    double  sigma2, rank_tol, point_tol;
+    int32_t profile, reserved;
+} sfmba_covariance_options;
+typedef struct sfmba_covariance_info {
+    int32_t status, g0, g1, g1_axis, n_free, n_held, bad_param, reserved;
+    int64_t dof, n_bad_points, bad_point;
+    double  sigma2, cost, min_pivot_rel, kernel_us;
+} sfmba_covariance_info;
+void sfmba_default_covariance_options(sfmba_covariance_options* opt);
+int  sfmba_covariance(sfmba_handle* h, const double* x, const int32_t* hold, int32_t n_hold,
+                      const sfmba_covariance_options* opt, double* cam_cov /*(C,6,6)*/, double* cam_full /*(6C,6C) or NULL*/,
+                      double* cam_sigma /*(C,2)*/, double* pt_cov /*(P,3,3)*/, double* pt_sigma /*P*/,
+                      int32_t* pt_status /*P*/, uint8_t* held_out /*6C*/, sfmba_covariance_info* info);
+
 /* ---- measurement / test entry points -------------------------------------------------------- */
 /* `reps` back-to-back launches of one kernel at x, bracketed by HIP events on the handle's stream.
  * which: 0 residual+Jacobian sweep (with the point blocks V_p, g_p it leaves behind), 1 residual-only sweep,
@@ -828,6 +882,7 @@ int  sfmba_get_fun_grad(sfmba_handle* h, double* fun_out, double* grad_out);
  *        15 k_triangulate of sfmba_triangulate over every point and observation (default options),
  *        16 k_resect of sfmba_resect over every camera and observation (default options).
  *        17 k_pnp_ransac + k_pnp_finish of sfmba_resect_ransac over every camera and observation (default options).
+ *        18 the kernels of sfmba_covariance with the default options, point sweep included (kind = 1 above 21 cameras).
  * avg_us: average duration of one repetition. */
 int  sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t reps, double* avg_us);
 /* Normal-equation blocks at x: U (C,21 upper triangle row-major), V (P,6 upper), gc (C,6), gp (P,3). */
@@ -927,6 +982,7 @@ int  sfmba_tr2d_solve(const double* B3, const double* g2, double Delta, double* 
  *   "pcg_split"         1: the per-camera tail of the local form in a kernel of its own (k_pcg_tail) on one rank too;
  *                       0: sharded / multi-chunk solves keep the general prologue or k_pcg_update
  *   "precond"           0: block-Jacobi preconditioner from U + D instead of the Schur-diagonal blocks
+ *   "cov_lds"           0: the point sweep of sfmba_covariance reads Sigma_cc from L2 instead of staging it in LDS
  *   "cam_chunk"      P  > 0: chunk length of the camera-major kernels (forces multi-chunk cameras + k_cam_combine)
  *   "xcd_chunks"     P  1 / 0: pass B's camera lists cut at the eight point-range boundaries (one piece per XCD) whatever
  *                       the problem size (default: from 250k points on)

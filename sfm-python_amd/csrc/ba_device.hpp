@@ -15,6 +15,9 @@ constexpr int kWavesPerSweepBlock = kSweepThreads / 64;
 struct KMat { double k[9]; };
 struct Origin { double x, y, z; };   // of the fp32 operands (MixedPrep)
 constexpr int kP2pMaxRanks = 16;    // of the direct all-reduce (P2pArgs)
+// two constants of the dense path for the units that do not include ba_kernels.hpp (covariance.hip); they stay defined
+// there, where the tests read them, and ba_kernels.hpp holds the pairs together
+namespace restated { constexpr int kDenseMaxN = 128; constexpr int kDenseThreads = 512; }
 
 // Cross-lane moves that stay in the VALU (DPP row shifts, v_readlane) instead of going through the LDS pipe
 // as ds_bpermute does; row_shl:N makes lane i read lane i+N of its 16-lane row (0 when that leaves the row).

@@ -2970,6 +2970,7 @@ __global__ __launch_bounds__(kCamThreads) void k_schur_blocks(const int* __restr
 // iterations and outcome like the implicit PCG does (1 converged, 2 iteration cap, 3 breakdown: x is the last good
 // iterate).  Every sum has a fixed order: same input, same bits.
 constexpr int kDenseThreads = 512, kDenseLanes = 4;      // (1024 x 8: 128 registers per lane, spills; 256 x 2: slower)
+static_assert(restated::kDenseMaxN == kDenseMaxN && restated::kDenseThreads == kDenseThreads, "ba_device.hpp restates them");
 __device__ __forceinline__ double dense_rcp(double d) {         // v_rcp_f64 + one Newton step
     const double y = __builtin_amdgcn_rcp(d);
     return fma(fma(-d, y, 1.0), y, y);

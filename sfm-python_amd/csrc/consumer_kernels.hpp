@@ -3,6 +3,7 @@
 // and keeps no state, so a call site compiles to what was written out there before.
 #pragma once
 #include "ba_device.hpp"
+#include "consumer_device.hpp"   // for_each_long_run, the register Jacobi: shared with cov_kernels.hpp
 
 namespace sfmba {
 
@@ -20,20 +21,9 @@ __device__ __forceinline__ double cam_depth(const double* tl, double X, double Y
 // k_obs_stats, tri_load_row and k_resect write them out.  k_obs_stats also keeps its own staging loop: with stage_table
 // its instructions are the same but for register numbers, and two of four timing windows fell 1-2 % outside the parent's.)
 
-// A lane takes a run shorter than kStatsLongTrack; the runs it leaves (is_long) are taken by the whole wave afterwards,
-// one after the other: run(q, b, e, X, Y, Z) with lane q's run [b, e) and point on every lane.  Uniform over the wave.
+// where the lane / wave split of a point-major sweep switches over (for_each_long_run, consumer_device.hpp)
 constexpr int kStatsLongTrack = 32;
-template <class Run>
-__device__ __forceinline__ void for_each_long_run(bool is_long, int b, int e, double X, double Y, double Z, Run run) {
-    unsigned long long todo = __ballot(is_long);
-    while (todo) {
-        const int q = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const int qb = __shfl(b, q), qe = __shfl(e, q);
-        const double qX = __shfl(X, q), qY = __shfl(Y, q), qZ = __shfl(Z, q);
-        run(q, qb, qe, qX, qY, qZ);
-    }
-}
+static_assert(restated::kStatsLongTrack == kStatsLongTrack, "consumer_device.hpp restates it for cov_kernels.hpp");
 
 // The widest angle between the rays X - T of the used observations of a run, tracked as the pair (|a x b|, a . b) and
 // compared by the sign of sin(theta1 - theta2) = s1 d2 - d1 s2 (both angles in [0, pi]); atan2 once per run (per lane in
@@ -96,65 +86,6 @@ __device__ __forceinline__ double widest_angle_wave(int b, int e, int lane, doub
         }
     }
     return wave_max(atan2(sb, db));
-}
-
-// Cyclic Jacobi on a symmetric N x N matrix in registers, upper triangle row by row: sym<N>(i, j) is entry (i, j)'s place
-template <int N>
-__host__ __device__ constexpr int sym(int i, int j) {
-    return i <= j ? N * i - i * (i - 1) / 2 + (j - i) : N * j - j * (j - 1) / 2 + (i - j);
-}
-// the rotation that annihilates a_pq (theta^2 = inf: t = 0; a zero pair: the identity, without a branch round live state)
-__device__ __forceinline__ void jacobi_cs(double app, double aqq, double apq, double& t, double& c, double& s) {
-    const double theta = (aqq - app) / (2.0 * apq);
-    t = apq == 0.0 ? 0.0 : copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    c = 1.0 / sqrt(t * t + 1.0);
-    s = t * c;
-}
-// one rotation in the (P, Q) plane: a <- G^T a G, v <- v G
-template <int N, int P, int Q>
-__device__ __forceinline__ void jacobi_rotate(double (&a)[N * (N + 1) / 2], double (&v)[N * N]) {
-    const double apq = a[sym<N>(P, Q)];
-    double t, c, s;
-    jacobi_cs(a[sym<N>(P, P)], a[sym<N>(Q, Q)], apq, t, c, s);
-    a[sym<N>(P, P)] -= t * apq;
-    a[sym<N>(Q, Q)] += t * apq;
-    a[sym<N>(P, Q)] = 0.0;
-#pragma unroll
-    for (int r = 0; r < N; ++r) {
-        if (r != P && r != Q) {
-            const double arp = a[sym<N>(r, P)], arq = a[sym<N>(r, Q)];
-            a[sym<N>(r, P)] = c * arp - s * arq;
-            a[sym<N>(r, Q)] = s * arp + c * arq;
-        }
-        const double vrp = v[N * r + P], vrq = v[N * r + Q];
-        v[N * r + P] = c * vrp - s * vrq;
-        v[N * r + Q] = s * vrp + c * vrq;
-    }
-}
-// the rotations of one sweep: (0, 1), (0, 2), ..., (0, N - 1), (1, 2), ..., (N - 2, N - 1)
-template <int N, int P = 0, int Q = 1>
-__device__ __forceinline__ void jacobi_rotate_all(double (&a)[N * (N + 1) / 2], double (&v)[N * N]) {
-    jacobi_rotate<N, P, Q>(a, v);
-    if constexpr (Q + 1 < N) jacobi_rotate_all<N, P, Q + 1>(a, v);
-    else if constexpr (P + 2 < N) jacobi_rotate_all<N, P + 1, P + 2>(a, v);
-}
-// a <- eigenvalues on the diagonal, v (I on entry) <- eigenvectors in its columns: sweeps until the off-diagonal part is
-// 1e-40 of the diagonal (a sweep squares that ratio) or has vanished
-constexpr int kJacobiRegSweeps = 12;  // cap of the sweeps of a register matrix (a 4x4 converges in 4..7)
-template <int N>
-__device__ __forceinline__ void jacobi_sweeps(double (&a)[N * (N + 1) / 2], double (&v)[N * N]) {
-#pragma unroll 1
-    for (int sweep = 0; sweep < kJacobiRegSweeps; ++sweep) {
-        double off = 0.0, dia = 0.0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-#pragma unroll
-            for (int j = i + 1; j < N; ++j) off += fabs(a[sym<N>(i, j)]);
-            dia += fabs(a[sym<N>(i, i)]);
-        }
-        if (!(off > 1e-40 * dia)) break;                         // (a NaN ends the loop too)
-        jacobi_rotate_all<N>(a, v);
-    }
 }
 
 // The damped Gauss-Newton refinements (a point in k_triangulate, a pose in k_resect): the damping after an accepted

@@ -66,7 +66,8 @@ int launch_stats_summary(sfmba_handle* h, int pt_blocks) {
 // The camera-major permutation of all observations of the current problem: built at the first call that asks for
 // per-camera figures and kept until the problem's arrays change (the solver's own lists leave out cameras held still
 // and, sorted on the device, come without the permutation).
-int stats_cam_perm(sfmba_handle* h) {
+}  // namespace
+int sfmba::stats_cam_perm(sfmba_handle* h) {
     auto& s = h->stats;
     const int64_t N = h->N, C = h->C;
     if (s.perm_gen != 0 && s.perm_gen == h->problem_gen && s.perm_N == N && s.perm_C == C) return 0;
@@ -96,6 +97,7 @@ int stats_cam_perm(sfmba_handle* h) {
     s.perm_gen = h->problem_gen; s.perm_N = N; s.perm_C = C;
     return 0;
 }
+namespace {
 
 int launch_cam_stats(sfmba_handle* h) {
     auto& s = h->stats;

@@ -18,6 +18,7 @@
 
 namespace sfmba {
 extern const size_t kLdsDynMax;                // dynamic LDS a workgroup may ask for (sfmba.hip, where the tests read it)
+extern const int kRecStride, kVinvStride;      // doubles per point record / inverse point block as k_schur_blocks reads them (sfmba.hip)
 
 struct DevBuf {
     void* p = nullptr;
@@ -99,6 +100,7 @@ struct PinnedBuf {
     X(spec_scale, -1)     /* 0: k_update_scale is launched after the host has accepted the trial point */ \
     X(start_handoff, -1)  /* 0: a solve starts with a blocking read-back of the cost and the scale sums */ \
     X(early_download, -1) /* 0: the result is copied to the host behind the last launch of the solve */ \
+    X(cov_lds, -1)        /* 0: the point sweep of sfmba_covariance reads Sigma_cc from L2 instead of staging it in LDS */ \
     X(cam_chunk, 0)       /* > 0: chunk length of the camera-major kernels */ \
     X(pcg_guess_bias, 0)  /* added to the number of speculatively enqueued PCG iterations */ \
     X(trace_pcg, 0) X(trace_stalls, 0) X(trace_timing, 0)   /* stderr diagnostics */ \
@@ -171,6 +173,7 @@ struct sfmba_handle {
     bool f32_next = false;                   // takes effect at the next sfmba_set_problem
     std::vector<int64_t> fixed_next;         // sfmba_set_fixed_cameras: cameras held still from the next sfmba_set_problem on
     int64_t n_fixed = 0;                     // ... of the current problem
+    std::vector<char> fixed_cur;             // [C] camera held still in the current problem
     Forms forms;                            // which kernel forms run (decide_problem_forms / decide_solve_forms)
     DevBuf rctab;                            // [C][18], k_rc_table
     DevBuf rt32, rec32, rctab32, rtd;        // [C][12], [P][8], [C][20] floats; [C][12] doubles
@@ -382,6 +385,16 @@ struct sfmba_handle {
         bool assembled = false;              // counts and the buffers hold a sub-problem of the current tracks
         int64_t counts[3] = {0, 0, 0};       // cameras, points, observations
     } plan;
+    // sfmba_covariance: works on stats.x / stats.tab and the camera-major permutation of the statistics call (kind = 1 and
+    // the U blocks) and on buffers of its own, so the solver's buffers stay as the last solve left them
+    struct Cov {
+        DevBuf rec, Vinv, Sblk, U;           // [P][kRecStride] X Y Z 0 0 0; [P][kVinvStride]; [n_blk][36]; [C][21]
+        DevBuf pt_cost, pt_status, held;     // [P] sum r^2 of the point's run; [P]; [6 C]
+        DevBuf scal, ints;                   // [kCovScal] doubles, [kCovInts] ints: the sums, sigma^2, pivots, failures
+        DevBuf full, cam_cov, cam_sigma, cam_piv;    // [6C][6C]; [C][36]; [C][2]; [C][2] min relative pivot, failing parameter
+        DevBuf pt_cov, pt_sigma;             // [P][9]; [P]
+        PinnedBuf host;                      // staging of the mask and of the small read-backs
+    } cov;
 };
 
 namespace sfmba {
@@ -423,6 +436,11 @@ int stats_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
 int tri_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us);
 int resect_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us);
 int pnp_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us);
+int cov_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us);                      // 18 (covariance.hip)
+// k_schur_blocks over the problem's pair lists at zero damping: blocks of W Vinv W^T -> Sblk [n_blk][36] (no rhs term)
+int launch_k_schur_blocks(sfmba_handle* h, const double* tab, const double* rec, const double* Vinv, double* Sblk);
+// the camera-major permutation of ALL observations (stats.perm / stats.cam_ptr), built once per problem (consumers.hip)
+int stats_cam_perm(sfmba_handle* h);
 // the middle launch of the scan of track_scan.hpp, compiled in tracks.hip, for the plan stage: `block` and `items` are the
 // caller's kTrackBlock and kTrackScanItems, refused (-3) when they are not the ones the kernel was compiled with
 int launch_k_track_scan_sums(sfmba_handle* h, long long* sums, unsigned nb, long long* tot, int slot, int block, int items);

@@ -94,6 +94,7 @@ static_assert(sizeof(TableRow4) == sizeof(int4) && alignof(TableRow4) == alignof
 namespace sfmba {
 constexpr size_t kLdsBytes = 160 * 1024;       // gfx950: 160 KiB LDS per workgroup
 const size_t kLdsDynMax = kLdsBytes - 2048;     // dynamic part; every kernel here has <= 2 KiB static LDS (k_backsub: 1280 B)
+const int kRecStride = kRec, kVinvStride = kVinvRow;
 
 int fail(sfmba_handle* h, int code, const char* fmt, ...) {
     char buf[512];
@@ -136,6 +137,13 @@ int launch_k_cam_hist(sfmba_handle* h, const unsigned char* fixed, int B, int pe
     CHK(set_lds(h, k_cam_hist, lds));
     hipLaunchKernelGGL(k_cam_hist, dim3(B), dim3(64), lds, h->stream, (const int*)h->cam_idx.as<int>(), fixed, (int)h->N, (int)h->C,
                        per_slice, hist);
+    LAUNCHED(h);
+    return 0;
+}
+int launch_k_schur_blocks(sfmba_handle* h, const double* tab, const double* rec, const double* Vinv, double* Sblk) {
+    hipLaunchKernelGGL(k_schur_blocks, dim3(h->n_blk), dim3(kCamThreads), 0, h->stream, (const int*)h->cov_ptr.as<int>(),
+                       (const int*)h->cov_pt.as<int>(), (const int2*)h->blk_ab.as<int2>(), tab, rec, Vinv, h->K, (int)h->C, Sblk,
+                       (double*)nullptr);
     LAUNCHED(h);
     return 0;
 }
@@ -1589,6 +1597,7 @@ int ProblemBuild::check_and_reset() {
     }
     h->n_fixed = 0;
     for (char f : fixed) h->n_fixed += f;
+    h->fixed_cur.assign(fixed.begin(), fixed.end());
     // A new problem returns the handle to single-process operation: every transport (direct link, RCCL
     // communicator, callback) is torn down and has to be set up again after this call (include/sfmba.h).  The
     // staging buffer of the direct link stays allocated until sfmba_p2p_detach / _export / _destroy, because
@@ -2101,6 +2110,7 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
     if (which == 15) return tri_time_kernel(h, x, reps, avg_us);
     if (which == 16) return resect_time_kernel(h, x, reps, avg_us);
     if (which == 17) return pnp_time_kernel(h, x, reps, avg_us);
+    if (which == 18) return cov_time_kernel(h, x, reps, avg_us);
     int np = 0;
     CHK(linearise_at(h, x, which >= 2));
     if (which >= 2) {

@@ -30,6 +30,7 @@ SYMBOLS = (
     "sfmba_set_descriptors", "sfmba_default_match_options", "sfmba_match_descriptors",
     "sfmba_default_track_options", "sfmba_build_tracks", "sfmba_get_tracks",
     "sfmba_default_plan_options", "sfmba_set_keypoints", "sfmba_plan_views", "sfmba_assemble_problem", "sfmba_get_assembled",
+    "sfmba_default_covariance_options", "sfmba_covariance",
 )
 
 
@@ -95,6 +96,18 @@ class TrackOptions(C.Structure):
 
 class PlanOptions(C.Structure):
     _fields_ = [("min_views", C.c_int32), ("profile", C.c_int32)]
+
+
+class CovarianceOptions(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("gauge", C.c_int32), ("sigma2", C.c_double), ("rank_tol", C.c_double),
+                ("point_tol", C.c_double), ("profile", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CovarianceInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("g0", C.c_int32), ("g1", C.c_int32), ("g1_axis", C.c_int32), ("n_free", C.c_int32),
+                ("n_held", C.c_int32), ("bad_param", C.c_int32), ("reserved", C.c_int32), ("dof", C.c_int64),
+                ("n_bad_points", C.c_int64), ("bad_point", C.c_int64), ("sigma2", C.c_double), ("cost", C.c_double),
+                ("min_pivot_rel", C.c_double), ("kernel_us", C.c_double)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
@@ -249,6 +262,12 @@ def load():
         lib.sfmba_assemble_problem.restype = C.c_int
         lib.sfmba_get_assembled.argtypes = [P] * 7
         lib.sfmba_get_assembled.restype = C.c_int
+    if hasattr(lib, "sfmba_covariance"):             # (likewise)
+        lib.sfmba_default_covariance_options.argtypes = [C.POINTER(CovarianceOptions)]
+        lib.sfmba_default_covariance_options.restype = None
+        lib.sfmba_covariance.argtypes = ([P, P, P, C.c_int32, C.POINTER(CovarianceOptions)] + [P] * 7 +
+                                         [C.POINTER(CovarianceInfo)])
+        lib.sfmba_covariance.restype = C.c_int
     lib.sfmba_tr2d_solve.argtypes = [P, P, C.c_double, P]
     lib.sfmba_comm_get_unique_id.argtypes = [P]
     lib.sfmba_comm_init.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int64]

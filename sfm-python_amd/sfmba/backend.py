@@ -552,6 +552,34 @@ class ReprojectionStats:
         return "ReprojectionStats(" + ", ".join(f"{k}={v!r}" for k, v in self.summary().items()) + ")"
 
 
+class Covariance:
+    """What `Backend.covariance` returns (include/sfmba.h: sfmba_covariance).  ``cam_cov`` (C,6,6), ``cam_full`` (6C,6C) or
+    None, ``cam_sigma`` (C,2), ``pt_cov`` (P,3,3) / ``pt_sigma`` (P) or None, ``pt_status`` (P: 0 fine, 1 undetermined,
+    3 no observation), ``held`` (6C: 0 free, 1 held, 2 unobserved), ``sigma2``, ``dof``, ``cost``, ``status`` (0 fine, 1
+    rank deficient cameras, 2 undetermined points), ``gauge`` = (g0, g1, axis) of the default gauge or -1s, ``bad_param``,
+    ``n_bad_points``, ``bad_point``, ``min_pivot_rel``, ``kernel_us``.  After a rank failure every matrix is NaN."""
+
+    STATUS = {0: "ok", 1: "rank deficient", 2: "undetermined points"}
+
+    def __init__(self, arrays, info):
+        for name in ("cam_cov", "cam_full", "cam_sigma", "pt_cov", "pt_sigma", "pt_status", "held"):
+            setattr(self, name, arrays.get(name))
+        self.sigma2, self.cost, self.dof, self.status = float(info.sigma2), float(info.cost), int(info.dof), int(info.status)
+        self.gauge = (int(info.g0), int(info.g1), int(info.g1_axis))
+        self.n_free, self.n_held, self.bad_param = int(info.n_free), int(info.n_held), int(info.bad_param)
+        self.n_bad_points, self.bad_point = int(info.n_bad_points), int(info.bad_point)
+        self.min_pivot_rel, self.kernel_us = float(info.min_pivot_rel), float(info.kernel_us)
+
+    @property
+    def ok(self):
+        return self.status == 0
+
+    def __repr__(self):
+        return (f"Covariance(status={self.STATUS.get(self.status, self.status)!r}, sigma2={self.sigma2:.6g}, dof={self.dof}, "
+                f"gauge={self.gauge}, n_free={self.n_free}, n_held={self.n_held}, min_pivot_rel={self.min_pivot_rel:.3g}, "
+                f"bad_param={self.bad_param}, n_bad_points={self.n_bad_points})")
+
+
 class Triangulation:
     """What `Backend.triangulate` returns (include/sfmba.h: sfmba_triangulate).  ``points`` (P, 3): the new point where
     ``status`` is 0, else the point of ``x``; ``status`` (P) one of the ``Triangulation.OK .. HIGH_ERROR`` codes, -1 for a
@@ -879,6 +907,41 @@ class Backend:
             if name in arrays:
                 arrays[name] = arrays[name].view(np.bool_)
         return ReprojectionStats(arrays, summary)
+
+    def covariance(self, x, hold=None, kind="marginal", gauge="auto", sigma2=None, want_full=False, want_points=True,
+                   **options):
+        """Covariance blocks of the solution ``x`` of the current problem (include/sfmba.h: sfmba_covariance).  ``kind``:
+        "marginal" (sigma^2 S^-1 and the point blocks that go with it; at most 21 cameras) or "conditional" (each block with
+        everything else held; any size).  ``hold``: camera parameters to hold, as indices 6 c + k or (camera, component)
+        pairs; ``gauge``: "auto" holds the first camera and one baseline coordinate when nothing else fixes the gauge,
+        "none" adds nothing.  ``sigma2`` None: sum r^2 / dof.  ``options``: rank_tol, point_tol, profile.
+        -> :class:`Covariance`."""
+        self._flush_pending()
+        x = _f64(x, (self.n_params,), "x")
+        kinds, gauges = {"marginal": 0, "conditional": 1, 0: 0, 1: 1}, {"auto": 1, "none": 0, True: 1, False: 0, None: 0}
+        if kind not in kinds or gauge not in gauges:
+            raise ValueError("kind is 'marginal' or 'conditional', gauge is 'auto' or 'none'")
+        opt = _capi.CovarianceOptions()
+        self._lib.sfmba_default_covariance_options(C.byref(opt))
+        _fill_options(opt, options, "covariance")
+        opt.kind, opt.gauge, opt.sigma2 = kinds[kind], gauges[gauge], 0.0 if sigma2 is None else float(sigma2)
+        hold_idx = []
+        for q in (() if hold is None else hold):
+            hold_idx.append(6 * int(q[0]) + int(q[1]) if np.ndim(q) else int(q))
+        hold_arr = np.ascontiguousarray(hold_idx, dtype=np.int32)
+        Cn, P = self.n_cameras, self.n_points
+        arrays = {"cam_cov": np.empty((Cn, 6, 6)), "cam_sigma": np.empty((Cn, 2)), "pt_status": np.empty(P, dtype=np.int32),
+                  "held": np.empty(6 * Cn, dtype=np.uint8)}
+        if want_full:
+            arrays["cam_full"] = np.empty((6 * Cn, 6 * Cn))
+        if want_points:
+            arrays["pt_cov"], arrays["pt_sigma"] = np.empty((P, 3, 3)), np.empty(P)
+        info = _capi.CovarianceInfo()
+        ptrs = [_capi.ptr(arrays[k]) if k in arrays else None
+                for k in ("cam_cov", "cam_full", "cam_sigma", "pt_cov", "pt_sigma", "pt_status", "held")]
+        self._check(self._lib.sfmba_covariance(self._h, _capi.ptr(x), _capi.ptr(hold_arr) if len(hold_arr) else None,
+                                               len(hold_arr), C.byref(opt), *ptrs, C.byref(info)))
+        return Covariance(arrays, info)
 
     def triangulate(self, x, select=None, obs_use=None, **options):
         """Triangulate the selected points of the current problem from their used observations and the cameras of ``x``:

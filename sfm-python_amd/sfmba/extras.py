@@ -51,6 +51,20 @@ def reprojection_stats(x, args, max_error_px=np.inf, min_depth=-np.inf, min_angl
                                  min_views=min_views, want=want)
 
 
+def covariance(x, n_cameras, n_points, camera_indices, point_indices, points_2d, K, fixed_camera_indices=(), device=0,
+               backend=None, **kw):
+    """Camera and point covariance blocks of a bundle-adjustment solution ``x`` on the arguments of the reference's
+    ``least_squares`` call (`Backend.covariance`; include/sfmba.h: sfmba_covariance).  ``fixed_camera_indices``: cameras the
+    problem holds still, as ``create_sparsity_matrix`` takes them; ``kw``: ``hold`` (indices 6 c + k or (camera, component)
+    pairs), ``kind``, ``gauge``, ``sigma2``, ``want_full``, ``want_points``, ``rank_tol``, ``point_tol``, ``profile``.
+    ``backend``: a :class:`Backend` to run on instead of the calling thread's own (``device`` is then ignored)."""
+    be = backend if backend is not None else api.get_backend(device)
+    be.set_precision(64)
+    be.set_fixed_cameras(fixed_camera_indices)
+    be.set_problem(n_cameras, n_points, camera_indices, point_indices, points_2d, K)
+    return be.covariance(x, **kw)
+
+
 def total_mean_reproj_error(x, args, device=0, backend=None):
     """Mean L2 reprojection error over all observations at ``x``: the figure the reference accumulates after every fused
     edge with one ``calc_reproj_error`` call per observation (sfm.py:234-241), here from one sweep.

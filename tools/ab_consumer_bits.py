@@ -1,5 +1,5 @@
 """Bit identity of the consumers (reprojection statistics, triangulation, resection, and the two-view calls -- F, homography,
-essential, pose -- and the robust resection where both builds have them) between two builds of the library.  Usage: python tools/ab_consumer_bits.py LIB_A LIB_B [--out DIR]
+essential, pose -- the robust resection and the covariance call where both builds have them) between two builds of the library.  Usage: python tools/ab_consumer_bits.py LIB_A LIB_B [--out DIR]
 
 One fresh child process per library (SFMBA_LIB), each under its own time limit; the tool stops at the first child that
 does not exit cleanly.  A child runs the three calls over inputs that reach every form of the kernels -- the long-run,
@@ -113,6 +113,19 @@ def child(out_path):
             pose = be.recover_pose(Es, p1, p2, K, edge_ptr=ptr, **kw)
             for f in ("R", "t", "front_mask", "X", "angle_deg", "front", "front_all", "sum_err", "status"):
                 out[f"two_view/64/pose/{tag}/{f}"] = getattr(pose, f)
+    # the covariance call: marginal at 11 and 21 cameras (lane and wave form of the point sweep), conditional at 40
+    if hasattr(be._lib, "sfmba_covariance"):              # (an older build has it not)
+        import covariance_ref as cr
+        for name in ("c11_dup", "c21", "grid21", "cond40"):
+            c = cr.case(name)
+            be.set_precision(64)
+            be.set_fixed_cameras(c["fixed"])
+            be.set_problem(*c["args"])
+            for kind in (("conditional",) if c["kind"] else ("marginal", "conditional")):
+                cov = be.covariance(c["x"], kind=kind, want_full=True)
+                for f in ("cam_cov", "cam_full", "cam_sigma", "pt_cov", "pt_sigma", "pt_status", "held"):
+                    out[f"cov/{name}/{kind}/{f}"] = getattr(cov, f)
+                out[f"cov/{name}/{kind}/info"] = np.array([cov.sigma2, cov.cost, cov.min_pivot_rel, cov.dof, cov.status], dtype=np.float64)
     be.close()
     np.savez(out_path, **{k.replace("/", "|"): v for k, v in out.items()})
 
@@ -150,7 +163,7 @@ def main():
         def __getitem__(self, k):
             return self.f[k]
 
-    for prefix, what in (("two_view|", "the two-view calls"), ("pnp|", "the robust resection")):
+    for prefix, what in (("two_view|", "the two-view calls"), ("pnp|", "the robust resection"), ("cov|", "the covariance call")):
         only = [f for f in (a, b) if any(k.startswith(prefix) for k in f.files)]
         if len(only) == 1:                                       # one build has not got the call: nothing to compare it with
             print(f"  (only one build has {what}: its arrays are left out)")
