@@ -577,6 +577,65 @@ int  sfmba_homography_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* ed
                              const sfmba_ransac_options* opt, double* Hm, double* H_refit, uint8_t* inlier_mask,
                              uint8_t* refit_mask, int32_t* edge_inliers, int32_t* edge_refit_inliers, int32_t* edge_best,
                              uint8_t* edge_success, int32_t* edge_status, int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us);
+/* sfmba_similarity_ransac: a similarity dst ~ s R src + t between two sets of 3-D points by RANSAC, H = max_iters hypotheses
+ * per set, without early exit: what relates two reconstructions (each lives in its own 7-dof gauge), or a reconstruction to
+ * positions known from outside.  A batch of n_sets SETS plays the part of the edges: set_ptr (n_sets + 1) ascending from 0 to
+ * M, src and dst (M,3) row-major, pair_use (M) or NULL = all; "used pairs" are those of the mask in stored order, n of them in
+ * a set.  sfmba_ransac_options are those of the F call; threshold is a DISTANCE IN THE UNITS OF dst (the default 1.0 means
+ * nothing here: pass one).  A batch with a mask gives bit for bit what the batch with those pairs removed gives; set e of a
+ * batch is a one-set batch given that set's samples.  No atomics, sums in a fixed order: same input, same bits.  Buffers are
+ * shared with the two-view calls and grow only; no call changes what another, or a following solve, computes.
+ *   hypothesis  three used pairs a_k -> b_k (k = 0, 1, 2 in the sample's order), Horn's closed form (J. Opt. Soc. Am. A 4,
+ *               1987): the means am, bm (sum / 3); the centred a'_k = a_k - am, b'_k = b_k - bm; the nine sums
+ *               S_ij = sum_k a'_k,i b'_k,j and saa = sum_k |a'_k|^2, accumulated in the order k = 0, 1, 2; the symmetric
+ *                 N = [ Sxx+Syy+Szz  Syz-Szy       Szx-Sxz       Sxy-Syx     ]
+ *                     [ .            Sxx-Syy-Szz   Sxy+Syx       Szx+Sxz     ]
+ *                     [ .            .            -Sxx+Syy-Szz   Syz+Szy     ]
+ *                     [ .            .             .            -Sxx-Syy+Szz ];
+ *               q = (w, x, y, z) the eigenvector of N's largest eigenvalue l1 (cyclic Jacobi on -N in registers, pairs
+ *               (0,1), (0,2), .., (2,3), until the off-diagonal part is 1e-40 of the diagonal, at most 12 sweeps), divided
+ *               by its norm; R the rotation of q,
+ *                 [ w2+x2-y2-z2  2(xy-wz)     2(xz+wy)    ]
+ *                 [ 2(xy+wz)     w2-x2+y2-z2  2(yz-wx)    ]
+ *                 [ 2(xz-wy)     2(yz+wx)     w2-x2-y2+z2 ], always proper: there is no reflection case;
+ *               s = sum_k b'_k . (R a'_k) / saa, evaluated as sum_ij R_ji S_ij / saa; t = bm - s R am.  With this s it is
+ *               Umeyama's least-squares estimate whenever that has det > 0.
+ *               NO SOLUTION (the sample is valid, its count is 0): l1 - l2 is not above 1e-9 (l1 - l4), l1 >= l2 >= l3 >= l4
+ *               the eigenvalues of N -- a collinear or repeated triple, the rotation about the line is free --, or saa or s
+ *               is not positive, or anything of (s, R, t) is not finite.
+ *   score       d2 = |s R a + t - b|^2 of a used pair; an inlier when d2 is finite and STRICTLY below threshold^2.
+ *               One-sided, in the frame and units of dst.
+ *   best        the largest inlier count, the lowest h among equals
+ *   samples     given: (n_sets, H, 3) int32 positions among the used pairs; a position outside 0 .. n-1 makes the call
+ *               return -1, a sample with a repeated position is invalid: its count is -1.  NULL: drawn by the counter-based
+ *               rule of the F call with three draws: key = mix(seed ^ mix(e << 32 | h)), e the set's position in the batch;
+ *               draw j = 0..2: k = mix(key + (j + 1) 0x9e3779b97f4a7c15) mod (n - j); then, for every earlier choice c in
+ *               ascending order of c, if (k >= c) ++k
+ *   finish      inlier_mask and set_inliers are evaluated once more from the best (s, R, t) (one place decides count,
+ *               success, status and the refit's pairs).
+ *   refit = 1   sim_refit: the same estimate over ALL inliers of the best hypothesis: the means over the inliers first,
+ *               then S_ij and saa about them, each a sum in a fixed order; the same N, Jacobi, R, s, t.  When that has no
+ *               solution, sim_refit is a copy of sim.  refit_mask and set_refit_inliers: the used pairs scored against
+ *               sim_refit AS RETURNED with the expression of the score.
+ *               refit = 0, or a status other than 0: sim_refit, refit_mask and set_refit_inliers are copies of sim,
+ *               inlier_mask and set_inliers.
+ * sim and sim_refit (n_sets,13): s, R (9, row-major), t (3).  inlier_mask, refit_mask (M): 0 for pairs that took no part.
+ * set_inliers, set_best: count and h of the best hypothesis.  set_success: inliers / n >= confidence.  set_status: 0 OK;
+ * 1 FEW_PAIRS (n < 3): count 0, best -1, empty masks, every hyp_inliers entry -1; 2 DEGENERATE (no hypothesis with a
+ * solution and at least 3 inliers): both similarities are zero, the count, h and mask of the best hypothesis are still
+ * reported (count 0 and an empty mask when the best sample had no solution; best -1 when no sample was valid).  A
+ * triple whose two triangles are similar fits its own similarity exactly, so a set without a common one can still be OK
+ * with a count of a handful (a mirrored copy: every triangle is congruent to its image, and a mirror image of a plane is a
+ * rotation of it): the caller decides how many inliers are enough.  hyp_inliers (n_sets,H): the count of every hypothesis (-1: invalid
+ * sample, or FEW_PAIRS).  n_ok: sets with status 0.  kernel_us: with profile = 1 the HIP-event time of the call's launches,
+ * else 0.  Every output pointer may be NULL, and an array that is not asked for is not downloaded.
+ * Returns -1 for a malformed batch, a NaN option, max_iters < 1 or a sample position outside 0 .. n-1.
+ * Not done here: adaptive exit, local optimisation of the best hypothesis, a reflection model, a robust weight in the refit. */
+int  sfmba_similarity_ransac(sfmba_handle* h, int64_t n_sets, const int64_t* set_ptr, const double* src, const double* dst,
+                             const uint8_t* pair_use /* M or NULL = all */, const int32_t* samples /* (n_sets,H,3) or NULL = drawn */,
+                             const sfmba_ransac_options* opt, double* sim /* (n_sets,13) */, double* sim_refit, uint8_t* inlier_mask,
+                             uint8_t* refit_mask, int32_t* set_inliers, int32_t* set_refit_inliers, int32_t* set_best,
+                             uint8_t* set_success, int32_t* set_status, int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us);
 /* sfmba_essential_ransac: the essential matrix x2^T E x1 = 0 (x in camera coordinates) by five-point RANSAC for every edge,
  * H = max_iters hypotheses each, without early exit: the calibrated sibling of sfmba_fundamental_ransac (what
  * cv2.findEssentialMat(pts1, pts2, K, cv2.RANSAC) estimates).  The batch (n_edges, edge_ptr, pts1, pts2, pair_use, "used

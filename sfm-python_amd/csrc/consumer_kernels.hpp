@@ -2452,6 +2452,312 @@ __global__ __launch_bounds__(kTwoViewThreads) void k_recover_pose(const double* 
     }
 }
 
+// ---- sfmba_similarity_ransac (include/sfmba.h): dst ~ s R src + t between two 3-D point sets ----
+// A batch of SETS plays the part of the edges: each a run of used pairs sx sy sz dx dy dz (48 bytes, packed by the host in
+// stored order); nothing of a bundle-adjustment problem is read.  The fifth model of the shell, in the form of k_pnp_ransac:
+//   k_sim_ransac   grid over (set, slice of its hypotheses).  Every LANE draws three pairs (ransac_sample<3>) and solves its
+//                  own hypothesis by Horn's closed form (sim_from_sums: the 4x4 matrix N of the nine centred sums, the
+//                  quaternion of its largest eigenvalue by smallest_eigenvector4 on -N, R, s, t), then the wave walks the
+//                  set's pairs with ONE index: every lane reads the same address (LDS broadcasts it without a conflict; past
+//                  kSimLdsPairs the pairs are read at their global address, the same on every lane) and counts the inliers
+//                  of its own (s, R, t) in a register.  No slab, no readlane / ballot loop per hypothesis, and 64 lanes
+//                  busy however few pairs the set has.  The wave's best of a round is the largest count, the lowest lane
+//                  among equals; rounds ascend in h.
+//   k_sim_finish   one workgroup per set, the sequence of twoview_verdict: best slot, the mask of that similarity in stored
+//                  order and the count FROM that mask, status; refit = 1: means, then the nine centred sums and |a'|^2 over
+//                  the inliers (block_sum, a fixed order), the same sim_from_sums by thread 0, the refit's mask and count.
+// No atomics; sums in a fixed order; counts do not depend on the order.
+constexpr int kSimLdsPairs = 3072;        // a set of up to this many used pairs is staged in LDS: 144 KiB of the 160, beside
+                                          // the 512 bytes of ransac_store; the launch asks for the largest set's 48 n bytes
+                                          // only, so sets of up to 1706 pairs (80 KiB) leave room for two workgroups a CU
+constexpr int kSimMinSlice = 64;          // fewest hypotheses of a workgroup's slice (one per lane of one wave)
+constexpr int kSimPair = 6;               // doubles of a packed pair
+constexpr int kSimPayload = 13;           // of a slot: s, R (9, row-major), t (3)
+constexpr int kSimOk = 0, kSimFewPairs = 1, kSimDegenerate = 2;
+constexpr double kSimEigenGap = 1e-9;     // the rotation is determined when l1 - l2 of N is above this times l1 - l4
+static_assert(sizeof(double) * kSimPair * kSimLdsPairs + sizeof(double) * kTwoViewWaves * (kRansacHead + kSimPayload) <= 160 * 1024,
+              "the staged pairs and ransac_store's table fit the LDS of a CU");
+
+// Horn (1987) from the sums of a set of pairs a -> b: S[3 i + j] = sum a'_i b'_j and saa = sum |a'|^2 about the means am,
+// bm.  m <- s, R, t; false (m is then not to be used): the two largest eigenvalues of N are not kSimEigenGap of the spread
+// apart (a collinear or repeated set: the rotation about the line is free), saa or s is not positive, anything non-finite.
+__device__ __forceinline__ bool sim_from_sums(const double (&S)[9], double saa, const double (&am)[3], const double (&bm)[3],
+                                              double (&m)[kSimPayload]) {
+    double a[10];                                                // -N, upper triangle row by row
+    a[0] = -(S[0] + S[4] + S[8]); a[1] = -(S[5] - S[7]); a[2] = -(S[6] - S[2]); a[3] = -(S[1] - S[3]);
+    a[4] = -(S[0] - S[4] - S[8]); a[5] = -(S[1] + S[3]); a[6] = -(S[6] + S[2]);
+    a[7] = -(S[4] - S[0] - S[8]); a[8] = -(S[5] + S[7]);
+    a[9] = -(S[8] - S[0] - S[4]);
+    double qw, qx, qy, qz;
+    smallest_eigenvector4(a, qw, qx, qy, qz);
+    // the eigenvalues of -N are on a's diagonal: the smallest, the second smallest and the largest
+    const double l01 = fmin(a[0], a[4]), h01 = fmax(a[0], a[4]), l23 = fmin(a[7], a[9]), h23 = fmax(a[7], a[9]);
+    const double lo = fmin(l01, l23), hi = fmax(h01, h23), second = fmin(fmax(l01, l23), fmin(h01, h23));
+    if (!(second - lo > kSimEigenGap * (hi - lo))) return false;
+    const double nq = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
+    qw /= nq; qx /= nq; qy /= nq; qz /= nq;
+    double* R = m + 1;
+    R[0] = qw * qw + qx * qx - qy * qy - qz * qz; R[1] = 2.0 * (qx * qy - qw * qz); R[2] = 2.0 * (qx * qz + qw * qy);
+    R[3] = 2.0 * (qx * qy + qw * qz); R[4] = qw * qw - qx * qx + qy * qy - qz * qz; R[5] = 2.0 * (qy * qz - qw * qx);
+    R[6] = 2.0 * (qx * qz - qw * qy); R[7] = 2.0 * (qy * qz + qw * qx); R[8] = qw * qw - qx * qx - qy * qy + qz * qz;
+    // sum b' . (R a') = sum_ij R_ji S_ij
+    const double num = R[0] * S[0] + R[1] * S[3] + R[2] * S[6] + R[3] * S[1] + R[4] * S[4] + R[5] * S[7] + R[6] * S[2] + R[7] * S[5] +
+                       R[8] * S[8];
+    const double s = num / saa;
+    if (!(saa > 0.0) || !(s > 0.0)) return false;
+    m[0] = s;
+    m[10] = bm[0] - s * (R[0] * am[0] + R[1] * am[1] + R[2] * am[2]);
+    m[11] = bm[1] - s * (R[3] * am[0] + R[4] * am[1] + R[5] * am[2]);
+    m[12] = bm[2] - s * (R[6] * am[0] + R[7] * am[1] + R[8] * am[2]);
+    double sum = 0.0;
+#pragma unroll
+    for (int k = 0; k < kSimPayload; ++k) sum += fabs(m[k]);
+    return sum < INFINITY;
+}
+
+// the score's test: |s R a + t - b|^2 STRICTLY below thr2; a non-finite value is no inlier
+__device__ __forceinline__ bool sim_inlier(const double (&m)[kSimPayload], const double (&o)[kSimPair], double thr2) {
+    const double px = m[1] * o[0] + m[2] * o[1] + m[3] * o[2], py = m[4] * o[0] + m[5] * o[1] + m[6] * o[2],
+                 pz = m[7] * o[0] + m[8] * o[1] + m[9] * o[2];
+    const double dx = m[0] * px + m[10] - o[3], dy = m[0] * py + m[11] - o[4], dz = m[0] * pz + m[12] - o[5];
+    const double d2 = dx * dx + dy * dy + dz * dz;
+    return d2 < thr2 && d2 < INFINITY;
+}
+
+// pair k of the set: staged at the head of the dynamic LDS (addressed through smem, see pnp_p3p) or at g2
+template <bool LDS_PAIRS>
+__device__ __forceinline__ void sim_pair(const double2* __restrict__ g2, int k, double (&o)[kSimPair]) {
+    extern __shared__ __align__(16) double smem[];
+    double2 q0, q1, q2;
+    if constexpr (LDS_PAIRS) {
+        const double2* s2 = reinterpret_cast<const double2*>(smem);
+        q0 = s2[3 * k]; q1 = s2[3 * k + 1]; q2 = s2[3 * k + 2];
+    } else {
+        q0 = g2[3 * (size_t)k]; q1 = g2[3 * (size_t)k + 1]; q2 = g2[3 * (size_t)k + 2];
+    }
+    o[0] = q0.x; o[1] = q0.y; o[2] = q1.x; o[3] = q1.y; o[4] = q2.x; o[5] = q2.y;
+}
+
+// the hypotheses h0 + 64 w + lane, + 256, ... < h1 of set e, one per lane; leaves the wave's best on every lane
+template <bool LDS_PAIRS>
+__device__ __forceinline__ void sim_slice(const double* __restrict__ gp, const int* __restrict__ samples, int e, int n, int H, int h0,
+                                          int h1, unsigned long long seed, double thr2, int* __restrict__ hyp,
+                                          RansacBest<kSimPayload>& best) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const double2* __restrict__ g2 = reinterpret_cast<const double2*>(gp);
+#pragma unroll 1
+    for (int hb = h0 + 64 * w; hb < h1; hb += 64 * kTwoViewWaves) {   // uniform over the wave
+        const int h = hb + lane;
+        int hcount = -2;                                         // (a lane past h1: below every hypothesis)
+        bool solved = false;
+        double m[kSimPayload];
+        if (h < h1) {
+            int idx[3];
+            hcount = kRansacNone;
+            if (ransac_sample(samples, e, H, h, n, seed, idx)) {
+                double a[9], b[9];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    double o[kSimPair];
+                    sim_pair<LDS_PAIRS>(g2, idx[j], o);
+                    a[3 * j] = o[0]; a[3 * j + 1] = o[1]; a[3 * j + 2] = o[2]; b[3 * j] = o[3]; b[3 * j + 1] = o[4]; b[3 * j + 2] = o[5];
+                }
+                double am[3], bm[3], S[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, saa = 0.0;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) { am[i] = (a[i] + a[3 + i] + a[6 + i]) / 3.0; bm[i] = (b[i] + b[3 + i] + b[6 + i]) / 3.0; }
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const double ac[3] = {a[3 * k] - am[0], a[3 * k + 1] - am[1], a[3 * k + 2] - am[2]};
+                    const double bc[3] = {b[3 * k] - bm[0], b[3 * k + 1] - bm[1], b[3 * k + 2] - bm[2]};
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) S[3 * i + j] += ac[i] * bc[j];
+                    saa += ac[0] * ac[0] + ac[1] * ac[1] + ac[2] * ac[2];
+                }
+                solved = sim_from_sums(S, saa, am, bm, m);
+                hcount = 0;                                      // a valid sample; without a solution it stays 0
+            }
+        }
+        if (!solved) {
+#pragma unroll
+            for (int k = 0; k < kSimPayload; ++k) m[k] = 0.0;
+        }
+        if (__ballot(solved)) {                                  // (uniform over the wave)
+            int cnt = 0;
+#pragma unroll 4
+            for (int k = 0; k < n; ++k) {                        // one index for the wave: every lane reads the same pair
+                double o[kSimPair];
+                sim_pair<LDS_PAIRS>(g2, k, o);
+                cnt += sim_inlier(m, o, thr2) ? 1 : 0;
+            }
+            if (solved) hcount = cnt;
+        }
+        if (h < h1 && hyp != nullptr) hyp[(size_t)e * (size_t)H + (size_t)h] = hcount;
+        // the round's best: the largest count, the lowest lane (h) among equals; rounds ascend in h
+        const int top = wave_reduce_xor(hcount, [](int x, int y) { return max(x, y); });
+        if (top > best.count) {
+            const int lb = __ffsll((long long)__ballot(hcount == top)) - 1;
+            best.count = top; best.h = hb + lb;
+#pragma unroll
+            for (int k = 0; k < kSimPayload; ++k) best.v[k] = __shfl(m[k], lb);
+        }
+    }
+}
+
+// dynamic LDS: the set's pairs when they fit (the host sizes it by the largest set of the batch, kSimLdsPairs at the most)
+__global__ __launch_bounds__(kTwoViewThreads) void k_sim_ransac(FundIn in, int H, int hs, int n_slices, unsigned long long seed,
+                                                                double thr2, double* __restrict__ slots, int* __restrict__ hyp) {
+    extern __shared__ __align__(16) double smem[];
+    const RansacBlock rb = ransac_block(H, hs, n_slices);
+    const int b = in.uptr[rb.item], n = in.uptr[rb.item + 1] - b;
+    const double* __restrict__ gp = in.pairs + kSimPair * (size_t)b;
+    if (n < 3) { ransac_no_hypothesis(rb, H, hyp); ransac_empty_slot<kSimPayload>(slots); return; }   // (uniform) FEW_PAIRS
+    RansacBest<kSimPayload> best;
+    if (n <= kSimLdsPairs) {
+        stage_table(gp, kSimPair * n, smem);
+        sim_slice<true>(gp, in.samples, rb.item, n, H, rb.h0, rb.h1, seed, thr2, hyp, best);
+    } else {
+        sim_slice<false>(gp, in.samples, rb.item, n, H, rb.h0, rb.h1, seed, thr2, hyp, best);
+    }
+    ransac_store(best, slots);
+}
+
+struct SimOut {
+    double* __restrict__ sim;                    // [E][13] s, R, t of the best hypothesis
+    double* __restrict__ sim_refit;              // [E][13]
+    unsigned char* __restrict__ mask;            // [M_used] of the best hypothesis
+    unsigned char* __restrict__ refit_mask;      // [M_used] of sim_refit
+    int* __restrict__ ints;                      // [E][5] inliers, best h, status, success, refit inliers
+};
+
+__global__ __launch_bounds__(kTwoViewThreads) void k_sim_finish(FundIn in, int n_slices, double thr2, double confidence, int refit,
+                                                                const double* __restrict__ slots, SimOut out) {
+    __shared__ double red[kTwoViewWaves * 10];
+    __shared__ double sp[kSimPayload], sm[6];
+    __shared__ int ctl[4];                                       // status, best h, has a similarity, count
+    const int e = blockIdx.x;
+    const int b = in.uptr[e], n = in.uptr[e + 1] - b;
+    const bool first = threadIdx.x == 0;
+    const double2* __restrict__ g2 = reinterpret_cast<const double2*>(in.pairs + kSimPair * (size_t)b);
+    int* __restrict__ oi = out.ints + 5 * (size_t)e;
+    double* __restrict__ om = out.sim + kSimPayload * (size_t)e;
+    double* __restrict__ orf = out.sim_refit + kSimPayload * (size_t)e;
+    unsigned char* __restrict__ mk = out.mask + (size_t)b;       // a thread reads back only what it stored itself
+    unsigned char* __restrict__ rmk = out.refit_mask + (size_t)b;
+    if (n < 3) {                                                 // (uniform over the workgroup) FEW_PAIRS
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) { mk[k] = 0; rmk[k] = 0; }
+        if (threadIdx.x < kSimPayload) { om[threadIdx.x] = 0.0; orf[threadIdx.x] = 0.0; }
+        if (first) { oi[0] = 0; oi[1] = -1; oi[2] = kSimFewPairs; oi[3] = 0; oi[4] = 0; }
+        return;
+    }
+    if (first) {
+        const double* __restrict__ bs = ransac_best_slot<kSimPayload>(slots, e, n_slices);
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < kSimPayload; ++k) { sp[k] = bs[kRansacHead + k]; sum += fabs(bs[kRansacHead + k]); }
+        ctl[1] = bs[0] >= 0.0 ? (int)bs[1] : -1;                 // (-1: no valid sample in any slot)
+        ctl[2] = (bs[0] >= 0.0 && sum < INFINITY && bs[kRansacHead] > 0.0) ? 1 : 0;      // (s = 0: a sample without a solution)
+    }
+    __syncthreads();
+    const bool has = ctl[2] != 0;
+    double mb[kSimPayload];
+#pragma unroll
+    for (int k = 0; k < kSimPayload; ++k) mb[k] = sp[k];
+    // set_inliers, set_success, the status and the refit's pairs all rest on this one evaluation (the count in the slot came
+    // from another copy of the expression)
+    double c[1] = {0.0};
+    for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+        double o[kSimPair];
+        sim_pair<false>(g2, k, o);
+        const bool inl = has && sim_inlier(mb, o, thr2);
+        mk[k] = inl ? 1 : 0; rmk[k] = inl ? 1 : 0;
+        c[0] += inl ? 1.0 : 0.0;
+    }
+    block_sum<1>(c, red);
+    if (first) {
+        const int cnt = (int)c[0];
+        ctl[0] = (has && cnt >= 3) ? kSimOk : kSimDegenerate;
+        ctl[3] = cnt;
+        // (DEGENERATE still reports the count, h and mask of its best hypothesis; only the similarity is withheld)
+        oi[0] = cnt; oi[1] = ctl[1]; oi[2] = ctl[0];
+        oi[3] = (ctl[1] >= 0 && (double)cnt / (double)n >= confidence) ? 1 : 0;
+        oi[4] = cnt;
+    }
+    __syncthreads();
+    if (ctl[0] != kSimOk) {
+        if (threadIdx.x < kSimPayload) { om[threadIdx.x] = 0.0; orf[threadIdx.x] = 0.0; }
+        return;
+    }
+    if (threadIdx.x < kSimPayload) om[threadIdx.x] = sp[threadIdx.x];
+    if (!refit) {
+        if (threadIdx.x < kSimPayload) orf[threadIdx.x] = sp[threadIdx.x];
+        return;
+    }
+    // the same estimate over the cnt >= 3 inliers: thread t takes pairs t, t + 256, ...; the means first
+    const double cnt = (double)ctl[3];
+    {
+        double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            double o[kSimPair];
+            sim_pair<false>(g2, k, o);
+            if (mk[k]) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) v[i] += o[i];
+            }
+        }
+        block_sum<6>(v, red);
+        if (first) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) sm[i] = v[i] / cnt;
+        }
+        __syncthreads();
+    }
+    {
+        const double am[3] = {sm[0], sm[1], sm[2]}, bm[3] = {sm[3], sm[4], sm[5]};
+        double v[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};          // S (9), sum |a'|^2
+        for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+            double o[kSimPair];
+            sim_pair<false>(g2, k, o);
+            if (mk[k]) {
+                const double ac[3] = {o[0] - am[0], o[1] - am[1], o[2] - am[2]}, bc[3] = {o[3] - bm[0], o[4] - bm[1], o[5] - bm[2]};
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) v[3 * i + j] += ac[i] * bc[j];
+                v[9] += ac[0] * ac[0] + ac[1] * ac[1] + ac[2] * ac[2];
+            }
+        }
+        block_sum<10>(v, red);
+        if (first) {
+            const double S[9] = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]};
+            double mr[kSimPayload];
+            const bool ok = sim_from_sums(S, v[9], am, bm, mr);
+#pragma unroll
+            for (int k = 0; k < kSimPayload; ++k) {              // (no solution: a copy of the best)
+                const double r = ok ? mr[k] : sp[k];
+                orf[k] = r;
+                sp[k] = r;
+            }
+        }
+        __syncthreads();
+    }
+    // refit_mask and its count: the used pairs against the refit as it is returned, the same expression
+    double mr[kSimPayload];
+#pragma unroll
+    for (int k = 0; k < kSimPayload; ++k) mr[k] = sp[k];
+    double cr[1] = {0.0};
+    for (int k = threadIdx.x; k < n; k += kTwoViewThreads) {
+        double o[kSimPair];
+        sim_pair<false>(g2, k, o);
+        const bool inl = sim_inlier(mr, o, thr2);
+        rmk[k] = inl ? 1 : 0;
+        cr[0] += inl ? 1.0 : 0.0;
+    }
+    block_sum<1>(cr, red);
+    if (first) oi[4] = (int)cr[0];
+}
+
 // ---------------------------------------------------------------------------------------------
 // Robust resection (sfmba_resect_ransac): P3P inside RANSAC per selected camera, over its used
 // observations in camera-major stored order, then k_resect (start = 1) over the inliers.

@@ -312,9 +312,10 @@ namespace {
 struct TwoViewBatch { size_t E = 0, M = 0, Mu = 0; bool masked = false; int max_n = 0; };
 
 // The batch onto the device: the used pairs of every edge packed x1 y1 x2 y2 in stored order -> twoview.pairs, their runs
-// -> twoview.uptr; twoview.pos maps a used pair back to its stored place when there is a mask.
+// -> twoview.uptr; twoview.pos maps a used pair back to its stored place when there is a mask.  dim: the coordinates of a
+// point (2: pixels; 3: the sets of sfmba_similarity_ransac, packed sx sy sz dx dy dz).
 int twoview_stage(sfmba_handle* h, const char* who, int64_t n_edges, const int64_t* edge_ptr, const double* pts1,
-                  const double* pts2, const uint8_t* pair_use, TwoViewBatch* bt) {
+                  const double* pts2, const uint8_t* pair_use, TwoViewBatch* bt, size_t dim = 2) {
     auto& t = h->twoview;
     if (n_edges < 0 || !edge_ptr) return fail(h, -1, "%s: n_edges is negative or edge_ptr is NULL", who);
     if (edge_ptr[0] != 0) return fail(h, -1, "%s: edge_ptr[0] must be 0", who);
@@ -323,7 +324,7 @@ int twoview_stage(sfmba_handle* h, const char* who, int64_t n_edges, const int64
     const size_t E = (size_t)n_edges, M = (size_t)edge_ptr[n_edges];
     if (M >= (size_t)1 << 31 || E >= (size_t)1 << 31) return fail(h, -1, "%s: the batch has 2^31 pairs or edges, or more", who);
     if (M && (!pts1 || !pts2)) return fail(h, -1, "%s: pts1 or pts2 is NULL", who);
-    const size_t off_ptr = sizeof(double) * 4 * M;
+    const size_t off_ptr = sizeof(double) * 2 * dim * M;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, t.in_host.ensure(off_ptr + sizeof(int) * (E + 1), 0));
     double* const pk = t.in_host.as<double>();
@@ -335,15 +336,15 @@ int twoview_stage(sfmba_handle* h, const char* who, int64_t n_edges, const int64
         up[e] = (int)u;
         for (size_t k = (size_t)edge_ptr[e]; k < (size_t)edge_ptr[e + 1]; ++k) {
             if (pair_use && !pair_use[k]) continue;
-            pk[4 * u] = pts1[2 * k]; pk[4 * u + 1] = pts1[2 * k + 1]; pk[4 * u + 2] = pts2[2 * k]; pk[4 * u + 3] = pts2[2 * k + 1];
+            for (size_t i = 0; i < dim; ++i) { pk[2 * dim * u + i] = pts1[dim * k + i]; pk[2 * dim * u + dim + i] = pts2[dim * k + i]; }
             if (pair_use) t.pos.push_back((int64_t)k);
             ++u;
         }
         max_n = std::max(max_n, (int)u - up[e]);
     }
     up[E] = (int)u;
-    CHK(ensure_all(h, {{&t.pairs, sizeof(double) * 4 * std::max<size_t>(u, 1)}, {&t.uptr, sizeof(int) * (E + 1)}}));
-    if (u) HIPCHK(h, hipMemcpyAsync(t.pairs.p, pk, sizeof(double) * 4 * u, hipMemcpyHostToDevice, h->stream));
+    CHK(ensure_all(h, {{&t.pairs, sizeof(double) * 2 * dim * std::max<size_t>(u, 1)}, {&t.uptr, sizeof(int) * (E + 1)}}));
+    if (u) HIPCHK(h, hipMemcpyAsync(t.pairs.p, pk, sizeof(double) * 2 * dim * u, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(t.uptr.p, up, sizeof(int) * (E + 1), hipMemcpyHostToDevice, h->stream));
     bt->E = E; bt->M = M; bt->Mu = u; bt->masked = pair_use != nullptr; bt->max_n = max_n;
     return 0;
@@ -393,6 +394,10 @@ int check_samples(sfmba_handle* h, const int32_t* samples, size_t batch, size_t 
 struct TwoViewRansac {
     size_t slot_doubles = kTwoViewSlot;          // of a slot of the RANSAC kernel
     size_t hyp_arrays = 1;                       // per-hypothesis integer arrays [n_edges][H] in twoview.hyp, one behind the other
+    size_t dim = 2;                              // coordinates of a point of a pair (3: sfmba_similarity_ransac)
+    size_t model_doubles = 9;                    // of the model and of its refit in twoview.F
+    int min_slice = kTwoViewMinSlice, lds_pairs = kTwoViewLdsPairs;      // of the RANSAC kernel
+    const char* item = "edge";                   // what an entry of the batch is called in an error text
     sfmba_ransac_options o;
     TwoViewBatch bt;
     size_t E = 0, H = 0;
@@ -408,25 +413,25 @@ int twoview_ransac_begin(sfmba_handle* h, const char* who, const void* lds_kerne
     if (std::isnan(c->o.threshold) || std::isnan(c->o.confidence)) return fail(h, -1, "an option of %s is NaN", who);
     if (c->o.max_iters < 1) return fail(h, -1, "%s: max_iters must be at least 1", who);
     auto& t = h->twoview;
-    CHK(twoview_stage(h, who, n_edges, edge_ptr, pts1, pts2, pair_use, &c->bt));
+    CHK(twoview_stage(h, who, n_edges, edge_ptr, pts1, pts2, pair_use, &c->bt, c->dim));
     if (n_ok) *n_ok = 0;
     if (kernel_us) *kernel_us = 0.0;
     const size_t E = c->bt.E, H = (size_t)c->o.max_iters;
     c->H = H;
     if (E == 0) return 0;
-    ransac_slices(h->n_cu, E, (int)H, kTwoViewMinSlice, true, &c->hs, &c->n_slices);
+    ransac_slices(h->n_cu, E, (int)H, c->min_slice, true, &c->hs, &c->n_slices);
     if (E * (size_t)c->n_slices >= (size_t)1 << 31) return fail(h, -1, "%s: too many edges for one launch", who);
     CHK(ensure_all(h, {{&t.slots, sizeof(double) * c->slot_doubles * E * (size_t)c->n_slices},
                        {&t.hyp, hyp ? sizeof(int) * c->hyp_arrays * E * H : 0},
                        {&t.samples, samples ? sizeof(int) * (size_t)S * E * H : 0}}));
     if (samples) {
-        const int* up = reinterpret_cast<const int*>(t.in_host.as<unsigned char>() + sizeof(double) * 4 * c->bt.M);
+        const int* up = reinterpret_cast<const int*>(t.in_host.as<unsigned char>() + sizeof(double) * 2 * c->dim * c->bt.M);
         CHK(check_samples(h, samples, E, H, (size_t)S, [&](size_t e) { return up[e + 1] - up[e]; }, S,   // (below: FEW_PAIRS)
-                          who, "edge", "pairs"));
+                          who, c->item, "pairs"));
         HIPCHK(h, hipMemcpyAsync(t.samples.p, samples, sizeof(int) * (size_t)S * E * H, hipMemcpyHostToDevice, h->stream));
     }
     // the kernel's static LDS (about 8 KiB, above the 2 KiB that set_lds assumes) counts: opted in whatever this call stages
-    CHK(opt_in_lds(h, lds_kernel, sizeof(double) * 4 * kTwoViewLdsPairs));
+    CHK(opt_in_lds(h, lds_kernel, sizeof(double) * 2 * c->dim * (size_t)c->lds_pairs));
     c->in = FundIn{t.pairs.as<double>(), t.uptr.as<int>(), samples ? t.samples.as<int>() : nullptr};
     c->E = E;
     return 0;
@@ -435,7 +440,7 @@ int twoview_ransac_begin(sfmba_handle* h, const char* who, const void* lds_kerne
 // a model's RANSAC kernel over the (edge, slice) grid: the arguments the kernels begin with alike, then the model's `own`
 template <class Kern, class... Own>
 int launch_twoview_ransac(sfmba_handle* h, const TwoViewRansac& c, Kern kern, double score, Own... own) {
-    const size_t lds = sizeof(double) * 4 * (size_t)std::min(c.bt.max_n, kTwoViewLdsPairs);
+    const size_t lds = sizeof(double) * 2 * c.dim * (size_t)std::min(c.bt.max_n, c.lds_pairs);
     hipLaunchKernelGGL(kern, dim3((unsigned)(c.E * (size_t)c.n_slices)), dim3(kTwoViewThreads), lds, h->stream, c.in, (int)c.H, c.hs,
                        c.n_slices, (unsigned long long)c.o.seed, score, own...);
     LAUNCHED(h);
@@ -465,7 +470,8 @@ int twoview_ransac_end(sfmba_handle* h, const TwoViewRansac& c, double score, si
     auto& t = h->twoview;
     const TwoViewBatch& bt = c.bt;
     const size_t E = c.E, H = c.H, Mu = bt.Mu;
-    CHK(ensure_all(h, {{&t.F, sizeof(double) * 18 * E}, {&t.ints, sizeof(int) * n_ints * E}, {&t.mask, n_masks * std::max<size_t>(Mu, 1)}}));
+    const size_t P = c.model_doubles;
+    CHK(ensure_all(h, {{&t.F, sizeof(double) * 2 * P * E}, {&t.ints, sizeof(int) * n_ints * E}, {&t.mask, n_masks * std::max<size_t>(Mu, 1)}}));
     EventPair timer;
     CHK(timer.start(h, c.o.profile != 0));
     CHK(launch(t.F.as<double>(), t.mask.as<unsigned char>(), t.ints.as<int>(), score));
@@ -477,8 +483,8 @@ int twoview_ransac_end(sfmba_handle* h, const TwoViewRansac& c, double score, si
     unsigned char* const hm = t.out_host.as<unsigned char>() + off_mask;
     HIPCHK(h, hipMemcpyAsync(hi, t.ints.p, sizeof(int) * n_ints * E, hipMemcpyDeviceToHost, h->stream));
     if ((r.mask[0] || r.mask[1]) && Mu) HIPCHK(h, hipMemcpyAsync(hm, t.mask.p, n_masks * Mu, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, download(h, r.M, t.F.p, sizeof(double) * 9 * E));
-    HIPCHK(h, download(h, r.M_refit, t.F.as<double>() + 9 * E, sizeof(double) * 9 * E));
+    HIPCHK(h, download(h, r.M, t.F.p, sizeof(double) * P * E));
+    HIPCHK(h, download(h, r.M_refit, t.F.as<double>() + P * E, sizeof(double) * P * E));
     HIPCHK(h, download(h, r.hyp, t.hyp.p, sizeof(int) * E * H));
     if (r.hyp2) HIPCHK(h, download(h, r.hyp2, t.hyp.as<int>() + E * H, sizeof(int) * E * H));
     CHK(wait_stream(h));
@@ -698,6 +704,36 @@ int sfmba_homography_ransac(sfmba_handle* h, int64_t n_edges, const int64_t* edg
         CHK(launch_twoview_ransac(h, c, k_homog_ransac, score, t.slots.as<double>(), hyp_inliers ? t.hyp.as<int>() : nullptr));
         hipLaunchKernelGGL(k_homog_finish, dim3((unsigned)c.E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, score, c.o.confidence,
                            c.o.refit != 0 ? 1 : 0, (const double*)t.slots.as<double>(), HomogOut{M, M + 9 * c.E, mask, mask + c.bt.Mu, ints});
+        LAUNCHED(h);
+        return 0;
+    });
+}
+
+// The H call with k_sim_ransac / k_sim_finish over sets of 3-D pairs (six doubles a pair) and samples of three positions:
+// twoview.F holds sim and sim_refit, 13 doubles each.
+int sfmba_similarity_ransac(sfmba_handle* h, int64_t n_sets, const int64_t* set_ptr, const double* src, const double* dst,
+                            const uint8_t* pair_use, const int32_t* samples, const sfmba_ransac_options* opt, double* sim,
+                            double* sim_refit, uint8_t* inlier_mask, uint8_t* refit_mask, int32_t* set_inliers,
+                            int32_t* set_refit_inliers, int32_t* set_best, uint8_t* set_success, int32_t* set_status,
+                            int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us) {
+    CHK(enter(h));
+    TwoViewRansac c;
+    c.slot_doubles = kRansacHead + kSimPayload;
+    c.dim = 3;
+    c.model_doubles = kSimPayload;
+    c.min_slice = kSimMinSlice;
+    c.lds_pairs = kSimLdsPairs;
+    c.item = "set";
+    CHK(twoview_ransac_begin(h, "sfmba_similarity_ransac", reinterpret_cast<const void*>(k_sim_ransac), 3, n_sets, set_ptr, src, dst, pair_use, samples, opt,
+                             hyp_inliers != nullptr, n_ok, kernel_us, &c));
+    const TwoViewResults r{sim, sim_refit, {inlier_mask, refit_mask}, set_inliers, set_best, set_status, set_success, set_refit_inliers,
+                           hyp_inliers, n_ok, kernel_us};
+    return twoview_ransac_end(h, c, c.o.threshold * c.o.threshold, 5, 2, kSimOk, r, [&](double* M, unsigned char* mask, int* ints, double score) {
+        auto& t = h->twoview;
+        CHK(launch_twoview_ransac(h, c, k_sim_ransac, score, t.slots.as<double>(), hyp_inliers ? t.hyp.as<int>() : nullptr));
+        hipLaunchKernelGGL(k_sim_finish, dim3((unsigned)c.E), dim3(kTwoViewThreads), 0, h->stream, c.in, c.n_slices, score, c.o.confidence,
+                           c.o.refit != 0 ? 1 : 0, (const double*)t.slots.as<double>(),
+                           SimOut{M, M + kSimPayload * c.E, mask, mask + c.bt.Mu, ints});
         LAUNCHED(h);
         return 0;
     });

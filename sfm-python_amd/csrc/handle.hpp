@@ -325,7 +325,8 @@ struct sfmba_handle {
         DevBuf cam, ints, rms;               // [C][6]; [4][C] status, views, iters, ok; [C]
     } resect;
     // sfmba_fundamental_ransac / sfmba_homography_ransac / sfmba_recover_pose: a batch of edges that has nothing to do
-    // with the problem; every buffer is the three calls' own
+    // with the problem; every buffer is the three calls' own.  sfmba_similarity_ransac shares them: pairs [M_used][6]
+    // sx sy sz dx dy dz, samples [n_sets][H][3], slots of 16 doubles, F [2][n_sets][13], ints [n_sets][5], mask [2][M_used]
     struct TwoView {
         DevBuf pairs, uptr, samples, E;      // [M_used][4] x1 y1 x2 y2; [n_edges + 1]; [n_edges][H][8 (F) or 4 (H)]; [n_edges][9]
         DevBuf slots, hyp;                   // [n_edges][slices][kTwoViewSlot]; [n_edges][H]

@@ -7,11 +7,11 @@ from .api import (TERMINATION_MESSAGES, apply_bundle_adjustment, compute_residua
                   create_sparsity_matrix, get_backend, least_squares, pack_cameras_points,
                   project_points, unpack_cameras_points)
 from .backend import (Backend, BackendError, Covariance, DescriptorMatches, EssentialEstimate, FundamentalEstimate, HomographyEstimate, RelativePose, ReprojectionStats, Resection,
-                      RobustResection, SubProblem, Tracks, Triangulation, ViewPlan, check_plan_inputs,
-                      check_track_inputs)
+                      RobustResection, SimilarityEstimate, SubProblem, Tracks, Triangulation, ViewPlan, check_plan_inputs,
+                      check_similarity_inputs, check_track_inputs)
 from .bal import read_bal, write_bal
-from .extras import (FM_RANSAC, RANSAC, DMatch, Reconstruction, build_tracks, calc_reproj_error, covariance, find_essential_mat, find_fundamental_mat, find_homography, knn_match, load_calibration_data,
-                     load_problem, match_descriptors, match_features,
+from .extras import (FM_RANSAC, RANSAC, DMatch, Reconstruction, align_reconstruction, apply_similarity, build_tracks, calc_reproj_error, covariance, find_essential_mat, find_fundamental_mat, find_homography, knn_match, load_calibration_data,
+                     load_problem, match_descriptors, match_features, estimate_similarity, merge_reconstructions,
                      prune_problem, reconstruct, recover_pose, refine_reconstruction, reproj_error, reprojection_stats, resect_cameras,
                      resect_cameras_ransac, save_problem, select_initial_pair, solve_pnp, solve_pnp_ransac, total_mean_reproj_error, triangulate_points,
                      triangulate_tracks)
@@ -34,4 +34,6 @@ __all__ = ["TERMINATION_MESSAGES", "apply_bundle_adjustment", "compute_residuals
            "DescriptorMatches", "DMatch", "knn_match", "match_descriptors", "match_features",
            "Tracks", "build_tracks", "check_track_inputs",
            "ViewPlan", "SubProblem", "check_plan_inputs", "Reconstruction", "reconstruct",
-           "Covariance", "covariance"]
+           "Covariance", "covariance",
+           "SimilarityEstimate", "check_similarity_inputs", "estimate_similarity", "apply_similarity", "align_reconstruction",
+           "merge_reconstructions"]

@@ -26,7 +26,7 @@ SYMBOLS = (
     "sfmba_default_resect_options", "sfmba_resect",
     "sfmba_default_pnp_ransac_options", "sfmba_resect_ransac",
     "sfmba_default_ransac_options", "sfmba_fundamental_ransac", "sfmba_default_pose_options", "sfmba_recover_pose",
-    "sfmba_homography_ransac", "sfmba_essential_ransac",
+    "sfmba_homography_ransac", "sfmba_essential_ransac", "sfmba_similarity_ransac",
     "sfmba_set_descriptors", "sfmba_default_match_options", "sfmba_match_descriptors",
     "sfmba_default_track_options", "sfmba_build_tracks", "sfmba_get_tracks",
     "sfmba_default_plan_options", "sfmba_set_keypoints", "sfmba_plan_views", "sfmba_assemble_problem", "sfmba_get_assembled",
@@ -231,6 +231,10 @@ def load():
         lib.sfmba_homography_ransac.argtypes = ([P, C.c_int64] + [P] * 5 + [C.POINTER(RansacOptions)] + [P] * 10 +
                                                 [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
         lib.sfmba_homography_ransac.restype = C.c_int
+    if hasattr(lib, "sfmba_similarity_ransac"):      # (likewise)
+        lib.sfmba_similarity_ransac.argtypes = ([P, C.c_int64] + [P] * 5 + [C.POINTER(RansacOptions)] + [P] * 10 +
+                                                [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
+        lib.sfmba_similarity_ransac.restype = C.c_int
     if hasattr(lib, "sfmba_essential_ransac"):       # (likewise)
         lib.sfmba_essential_ransac.argtypes = ([P, C.c_int64] + [P] * 6 + [C.POINTER(RansacOptions)] + [P] * 9 +
                                                [C.POINTER(C.c_int64), C.POINTER(C.c_double)])

@@ -58,6 +58,35 @@ class HomographyEstimate:
         return f"HomographyEstimate(n_edges={len(self.status)}, n_ok={self.n_ok})"
 
 
+class SimilarityEstimate:
+    """What `Backend.similarity_ransac` returns (include/sfmba.h: sfmba_similarity_ransac), per set of the batch:
+    ``dst ~ scale R src + t`` with ``scale`` (E), ``R`` (E, 3, 3), ``t`` (E, 3) of the best hypothesis and ``scale_refit``,
+    ``R_refit``, ``t_refit`` of the estimate over all its inliers (copies unless ``refit=1``); ``inliers``,
+    ``refit_inliers``, ``best`` (the winning hypothesis), ``status`` (one of ``OK, FEW_PAIRS, DEGENERATE``) as int32 (E),
+    ``success`` (E, bool): inliers / used pairs >= confidence; ``inlier_mask`` (of the best hypothesis) and ``refit_mask``
+    (of the refit) (M, bool) over the stored pairs; ``hyp_inliers`` (E, H) the count of every hypothesis, or None when not
+    asked for; ``n_ok``; ``kernel_us`` (``profile=1``, else 0); ``set_ptr``.  A status OK says only that three or more
+    pairs agree: how many inliers are enough is the caller's decision."""
+
+    OK, FEW_PAIRS, DEGENERATE = 0, 1, 2
+
+    def __init__(self, sim, sim_refit, inlier_mask, refit_mask, inliers, refit_inliers, best, success, status, hyp_inliers, n_ok,
+                 kernel_us, set_ptr):
+        self.scale, self.R, self.t = sim[:, 0].copy(), sim[:, 1:10].reshape(-1, 3, 3).copy(), sim[:, 10:13].copy()
+        self.scale_refit, self.R_refit, self.t_refit = (sim_refit[:, 0].copy(), sim_refit[:, 1:10].reshape(-1, 3, 3).copy(),
+                                                        sim_refit[:, 10:13].copy())
+        self.inlier_mask, self.refit_mask = inlier_mask, refit_mask
+        self.inliers, self.refit_inliers, self.best, self.success, self.status = inliers, refit_inliers, best, success, status
+        self.hyp_inliers, self.n_ok, self.kernel_us, self.set_ptr = hyp_inliers, int(n_ok), float(kernel_us), set_ptr
+
+    @property
+    def ok(self):
+        return self.status == self.OK
+
+    def __repr__(self):
+        return f"SimilarityEstimate(n_sets={len(self.status)}, n_ok={self.n_ok})"
+
+
 class EssentialEstimate:
     """What `Backend.essential_ransac` returns (include/sfmba.h: sfmba_essential_ransac), per edge of the batch: ``E``
     (n_edges, 3, 3), unit Frobenius norm, largest entry positive (compare up to sign); ``inliers``, ``best`` (the winning
@@ -401,19 +430,35 @@ def check_match_options(ratio=0.5, form=0, profile=0):
     return ratio, int(form), int(bool(profile))
 
 
-def _edge_batch(pts1, pts2, edge_ptr, pair_use):
-    """The arrays of a batch of edges, checked: pts1, pts2 (M, 2) float64, edge_ptr (E + 1) int64 ascending from 0 to M
-    (None: one edge), the mask (M) uint8 or None."""
+def _edge_batch(pts1, pts2, edge_ptr, pair_use, dim=2, names=("pts1", "pts2", "edge_ptr")):
+    """The arrays of a batch of edges, checked: pts1, pts2 (M, dim) float64, edge_ptr (E + 1) int64 ascending from 0 to M
+    (None: one edge), the mask (M) uint8 or None.  (dim = 3 and the names of `similarity_ransac`: a batch of sets.)"""
     pts1, pts2 = _f64(pts1), _f64(pts2)
-    if pts1.ndim != 2 or pts1.shape[1] != 2 or pts2.shape != pts1.shape:
-        raise ValueError(f"pts1 and pts2 must both be (M, 2), got {pts1.shape} and {pts2.shape}")
+    if pts1.ndim != 2 or pts1.shape[1] != dim or pts2.shape != pts1.shape:
+        raise ValueError(f"{names[0]} and {names[1]} must both be (M, {dim}), got {pts1.shape} and {pts2.shape}")
     M = pts1.shape[0]
     if edge_ptr is None:
         edge_ptr = np.array([0, M], dtype=np.int64)
     edge_ptr = np.ascontiguousarray(edge_ptr, dtype=np.int64).ravel()
     if edge_ptr.shape[0] < 1 or edge_ptr[0] != 0 or edge_ptr[-1] != M or np.any(np.diff(edge_ptr) < 0):
-        raise ValueError("edge_ptr must ascend from 0 to the number of pairs")
+        raise ValueError(f"{names[2]} must ascend from 0 to the number of pairs")
     return pts1, pts2, edge_ptr, _mask(pair_use, M, "pair_use")
+
+
+def check_similarity_inputs(src, dst, set_ptr=None, pair_use=None, samples=None, **options):
+    """The arguments of `Backend.similarity_ransac`, checked without a device -> ``(src, dst, set_ptr, pair_use, samples,
+    options)``: ``src``, ``dst`` (M, 3) float64; ``set_ptr`` (E + 1) int64 ascending from 0 to M (None: one set);
+    ``pair_use`` (M) uint8 or None; ``samples`` (E, H, 3) int32 or None ((H, 3) stands for one set); ``options`` a
+    `_capi.RansacOptions` holding the library's defaults (threshold 1.0, confidence 0.99, seed 0, max_iters 1000 or the
+    samples' H, refit 0, profile 0) overridden by the keywords.  Raises ``ValueError`` for a wrong shape, a
+    non-ascending ``set_ptr``, a NaN option, ``max_iters < 1`` or samples that disagree with it, ``TypeError`` for an
+    unknown keyword.  (Whether a sample position lies inside its set depends on the mask: the library checks it.)"""
+    src, dst, set_ptr, use = _edge_batch(src, dst, set_ptr, pair_use, dim=3, names=("src", "dst", "set_ptr"))
+    opt = _capi.RansacOptions(threshold=1.0, confidence=0.99, seed=0, max_iters=1000, refit=0, profile=0)
+    samples = _ransac_prologue(opt, options, samples, set_ptr.shape[0] - 1, 3, "n_sets", "set", "similarity RANSAC")
+    if np.isnan(opt.threshold) or np.isnan(opt.confidence):
+        raise ValueError("an option of the similarity RANSAC is NaN")
+    return src, dst, set_ptr, use, samples, opt
 
 
 def _ransac_prologue(opt, options, samples, batch, S, batch_name, item, what, then_flush=None):
@@ -1072,6 +1117,29 @@ class Backend:
             _capi.ptr(success), _capi.ptr(status), _opt_ptr(hyp), C.byref(n_ok), C.byref(us)))
         return HomographyEstimate(Hm, Hr, mask.view(np.bool_), rmask.view(np.bool_), inl, rinl, best, success.view(np.bool_),
                                   status, hyp, n_ok.value, us.value, edge_ptr)
+
+    def similarity_ransac(self, src, dst, set_ptr=None, pair_use=None, samples=None, want_hyp=False, **options):
+        """A similarity ``dst ~ s R src + t`` by RANSAC for every set of a batch of 3-D point pairs (include/sfmba.h:
+        sfmba_similarity_ransac), the fifth model of the family: ``src``, ``dst`` (M, 3); ``set_ptr`` (E + 1) the sets'
+        runs, None = one set; ``pair_use`` (M) boolean, None = all; ``samples`` (E, H, 3) int32 positions among a set's used
+        pairs, None = drawn on the device from ``seed``; ``options``: fields of ``sfmba_ransac_options`` -- ``threshold``
+        is a distance in the units of ``dst``, so pass one --; with ``samples`` given, ``max_iters`` defaults to its H.
+        ``want_hyp``: also return the count of every hypothesis.  Needs no problem.  -> :class:`SimilarityEstimate`."""
+        src, dst, set_ptr, use, samples, opt = check_similarity_inputs(src, dst, set_ptr, pair_use, samples, **options)
+        self._flush_pending()
+        E, M, H = set_ptr.shape[0] - 1, src.shape[0], int(opt.max_iters)
+        sim, simr = np.empty((E, 13)), np.empty((E, 13))
+        mask, rmask = np.empty(M, dtype=np.uint8), np.empty(M, dtype=np.uint8)
+        inl, rinl, best, status = (np.empty(E, dtype=np.int32) for _ in range(4))
+        success = np.empty(E, dtype=np.uint8)
+        hyp = np.empty((E, H), dtype=np.int32) if want_hyp else None
+        n_ok, us = C.c_int64(), C.c_double()
+        self._check(self._lib.sfmba_similarity_ransac(
+            self._h, E, _capi.ptr(set_ptr), _capi.ptr(src), _capi.ptr(dst), _opt_ptr(use), _opt_ptr(samples), C.byref(opt),
+            _capi.ptr(sim), _capi.ptr(simr), _capi.ptr(mask), _capi.ptr(rmask), _capi.ptr(inl), _capi.ptr(rinl), _capi.ptr(best),
+            _capi.ptr(success), _capi.ptr(status), _opt_ptr(hyp), C.byref(n_ok), C.byref(us)))
+        return SimilarityEstimate(sim, simr, mask.view(np.bool_), rmask.view(np.bool_), inl, rinl, best, success.view(np.bool_),
+                                  status, hyp, n_ok.value, us.value, set_ptr)
 
     def essential_ransac(self, pts1, pts2, K, edge_ptr=None, pair_use=None, samples=None, want_hyp=False, **options):
         """The essential matrix by five-point RANSAC for every edge of a batch of matched pixel pairs (include/sfmba.h:

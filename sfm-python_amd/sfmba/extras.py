@@ -586,9 +586,174 @@ class Reconstruction:
     def problem(self):
         return self._x.copy(), self._args
 
+    def transformed(self, s, R, t):
+        """A new :class:`Reconstruction` in the frame ``X' = s R X + t``: ``cameras``, ``points`` and the ``x`` of
+        ``problem()`` mapped by :func:`apply_similarity` (reprojections do not change), NaN rows staying NaN; masks,
+        ``rounds``, ``tracks`` and the problem's ``args`` are shared with this one."""
+        s, R, t = _similarity_args(s, R, t)
+        cameras, points = _map_cameras(self.cameras, s, R, t), _map_points(self.points, s, R, t)
+        x = apply_similarity(self._x, len(self.cam_of), s, R, t)
+        return Reconstruction(self.registered.copy(), cameras, points, self.known.copy(), list(self.rounds), self.tracks, x,
+                              self._args, self.cam_of, self.pt_of, self.obs_feat)
+
     def __repr__(self):
         return (f"Reconstruction(registered={int(self.registered.sum())}/{len(self.registered)}, "
                 f"known={int(self.known.sum())}/{len(self.known)}, rounds={len(self.rounds)})")
+
+
+# ---- similarities: one reconstruction against another, or against positions known from outside (DESIGN.md section 29) ----
+def _similarity_args(s, R, t):
+    s, R, t = float(s), np.asarray(R, dtype=np.float64), np.asarray(t, dtype=np.float64).reshape(-1)
+    if R.shape != (3, 3) or t.shape != (3,):
+        raise ValueError(f"R must be (3, 3) and t (3,), got {R.shape} and {t.shape}")
+    return s, R, t
+
+
+def _map_points(points, s, R, t):
+    return s * (np.asarray(points, dtype=np.float64) @ R.T) + t
+
+
+def _map_cameras(cameras, s, R, t):
+    """(n, 6) rotation vector | centre under X' = s R X + t: the centre maps as a point, the rotation R_c becomes
+    R_c R^T (x_cam = R_c (X - T) is then scaled by s, which a projection does not see); a NaN row stays NaN."""
+    out = np.array(cameras, dtype=np.float64).reshape(-1, 6)
+    for row in out:
+        if np.isfinite(row).all():
+            row[:3] = api._rotvec_from_matrix(api._matrix_from_rotvec(row[:3]) @ R.T)
+    out[:, 3:] = _map_points(out[:, 3:], s, R, t)
+    return out
+
+
+def apply_similarity(x, n_cameras, s, R, t):
+    """The parameter vector ``x`` (``n_cameras`` rows of rotation vector | centre, then the points) in the frame
+    ``X' = s R X + t`` -> a new vector: points become ``s R X + t``, centres ``s R T + t``, rotations ``R_c R^T``, so every
+    reprojection is what it was.  NumPy on the host: an elementwise map does not earn an upload, a launch and a
+    download."""
+    s, R, t = _similarity_args(s, R, t)
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    n = int(n_cameras)
+    if n < 0 or 6 * n > x.shape[0] or (x.shape[0] - 6 * n) % 3:
+        raise ValueError(f"x has {x.shape[0]} entries: not {n} cameras and whole points")
+    return np.concatenate([_map_cameras(x[:6 * n].reshape(n, 6), s, R, t).ravel(),
+                           _map_points(x[6 * n:].reshape(-1, 3), s, R, t).ravel()])
+
+
+def _similarity_threshold(dst, threshold):
+    """``threshold`` of the similarity calls; None: 0.02 x the median distance of the ``dst`` points from their
+    coordinate-wise median (a convenience computed in NumPy: two per cent of the cloud's typical radius)."""
+    if threshold is not None:
+        return float(threshold)
+    dst = np.asarray(dst, dtype=np.float64).reshape(-1, 3)
+    if len(dst) == 0:
+        return 1.0
+    return 0.02 * float(np.median(np.linalg.norm(dst - np.median(dst, axis=0), axis=1)))
+
+
+def estimate_similarity(src, dst, threshold=None, min_inliers=6, max_iters=1000, confidence=0.99, seed=0, refit=True,
+                        pair_use=None, device=0, backend=None):
+    """``dst ~ s R src + t`` between two (N, 3) point sets by RANSAC -> ``(s, R (3, 3), t (3,), mask (N,) bool)``: one call
+    of :meth:`Backend.similarity_ransac`.  With ``refit=True`` the estimate over all inliers of the best hypothesis and ITS
+    mask, else the best three-point hypothesis and its mask.  ``(None, None, None, mask)`` when the status is not OK or the
+    mask holds fewer than ``min_inliers`` pairs: a triple whose two triangles happen to be similar fits its own similarity
+    exactly (every triple of a mirrored copy does), so a handful of inliers says nothing.  ``threshold``: a distance in the units of ``dst``; None = 0.02 x the median distance of the used ``dst``
+    points from their coordinate-wise median, a convenience computed in NumPy.  ``confidence`` only decides ``success``
+    of the batch call; every one of the ``max_iters`` hypotheses is scored."""
+    dst = np.asarray(dst, dtype=np.float64)
+    used = dst.reshape(-1, 3) if pair_use is None else dst.reshape(-1, 3)[np.asarray(pair_use).ravel() != 0]
+    be = backend if backend is not None else api.get_backend(device)
+    est = be.similarity_ransac(src, dst, pair_use=pair_use, threshold=_similarity_threshold(used, threshold), confidence=confidence,
+                               max_iters=max_iters, seed=seed, refit=1 if refit else 0)
+    mask, count = (est.refit_mask, est.refit_inliers[0]) if refit else (est.inlier_mask, est.inliers[0])
+    if est.status[0] != est.OK or count < int(min_inliers):
+        return None, None, None, mask
+    if refit:
+        return float(est.scale_refit[0]), est.R_refit[0], est.t_refit[0], mask
+    return float(est.scale[0]), est.R[0], est.t[0], mask
+
+
+def _robust_similarity(be, src, dst, threshold, min_inliers, ransac, what):
+    """The refit of one `similarity_ransac` over src -> dst, or ``ValueError`` naming ``what`` the pairs are."""
+    if len(src) < int(min_inliers):
+        raise ValueError(f"{len(src)} {what}: fewer than min_inliers = {int(min_inliers)}")
+    ransac = dict(ransac)
+    ransac["refit"] = 1
+    est = be.similarity_ransac(src, dst, threshold=_similarity_threshold(dst, threshold), **ransac)
+    if est.status[0] != est.OK or est.refit_inliers[0] < int(min_inliers):
+        raise ValueError(f"no similarity with min_inliers = {int(min_inliers)} inliers among the {len(src)} {what} "
+                         f"(status {int(est.status[0])}, {int(est.refit_inliers[0])} inliers)")
+    return est
+
+
+def align_reconstruction(rec, centres, threshold=None, min_inliers=6, device=0, backend=None, **ransac):
+    """Put a :class:`Reconstruction` into the frame of camera positions known from outside (GPS, a survey, ground truth)
+    -> ``(Reconstruction, SimilarityEstimate)``.  ``centres``: (n_images, 3), NaN rows where unknown; the correspondences
+    are the registered images with a known position, camera centre -> position, in ascending image order (the estimate's
+    masks run over them: ``np.flatnonzero(rec.registered & np.isfinite(centres).all(axis=1))``).  One
+    :meth:`Backend.similarity_ransac` with ``refit=1`` (``ransac``: its other options; ``threshold`` as in
+    :func:`estimate_similarity`), then :meth:`Reconstruction.transformed` by the refit.  ``ValueError`` when there are
+    fewer than ``min_inliers`` correspondences, or fewer than ``min_inliers`` inliers."""
+    centres = np.asarray(centres, dtype=np.float64)
+    if centres.shape != (len(rec.registered), 3):
+        raise ValueError(f"centres must be ({len(rec.registered)}, 3), got {centres.shape}")
+    be = backend if backend is not None else api.get_backend(device)
+    corr = rec.registered & np.isfinite(centres).all(axis=1)
+    est = _robust_similarity(be, rec.cameras[corr, 3:6], centres[corr], threshold, min_inliers, ransac,
+                             "registered images with a known position")
+    return rec.transformed(est.scale_refit[0], est.R_refit[0], est.t_refit[0]), est
+
+
+def merge_reconstructions(a, b, K, threshold=None, min_inliers=10, filter_options=None, device=0, backend=None, **ransac):
+    """Join two reconstructions over the same :class:`Tracks` (say, two runs of :func:`reconstruct` from different
+    ``init=`` pairs that each left images over) -> ``(Reconstruction, SimilarityEstimate)`` in a's frame.  Both must carry
+    the ``Tracks`` of the last `build_tracks` on the back end, whose key points must be set (`reconstruct` leaves them so).
+    The correspondences are the tracks known in both, b's point -> a's point, in ascending track order (the estimate's
+    masks run over them); one :meth:`Backend.similarity_ransac` with ``refit=1`` (``ransac``: its other options;
+    ``threshold`` as in :func:`estimate_similarity`, in a's units) maps b into a's frame.  ``registered`` and ``known``
+    are the unions; where both have a camera or a point, a's is kept.  The problem is assembled with
+    ``Backend.assemble_problem(registered, known, min_views=2)`` and one `reprojection_stats` pass with the trim's
+    thresholds (``filter_options``: the keys and defaults of :func:`reconstruct`) prunes observations and points as the
+    closing pass of `reconstruct` does.  NO solve is run: ``refine_reconstruction(*merged.problem())`` is the caller's
+    next line.  Of ``a`` and ``b`` only ``registered``, ``cameras``, ``points``, ``known`` and ``tracks`` are read
+    (observations that their own runs had dropped come back and face the closing pass again).  ``rounds`` of the result
+    is ``a.rounds + b.rounds`` plus a closing dict with ``merged=True``, ``inliers`` and ``scale``.  ``ValueError`` for
+    different tracks, fewer than ``min_inliers`` shared tracks or fewer than ``min_inliers`` inliers."""
+    be = backend if backend is not None else api.get_backend(device)
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError("K must be (3, 3)")
+    tracks = a.tracks
+    if b.tracks is not tracks and not (b.tracks.n_tracks == tracks.n_tracks and np.array_equal(b.tracks.img_ptr, tracks.img_ptr) and
+                                       np.array_equal(b.tracks.feat_track, tracks.feat_track)):
+        raise ValueError("the two reconstructions do not carry the same tracks")
+    n_images = len(tracks.img_ptr) - 1
+    if getattr(be, "_plan_dims", None) != (n_images, tracks.n_tracks):
+        raise ValueError("the reconstructions' tracks are not the result of the last build_tracks on this back end")
+    thr = dict(max_error_px=4.0, min_depth=0.0, min_angle_deg=2.0, min_views=2)
+    unknown = set(filter_options or {}) - set(thr)
+    if unknown:
+        raise TypeError(f"unknown filter option(s) {sorted(unknown)} (known: {sorted(thr)})")
+    thr.update(filter_options or {})
+    both = a.known & b.known
+    est = _robust_similarity(be, b.points[both], a.points[both], threshold, min_inliers, ransac, "tracks known in both")
+    s, R, t = _similarity_args(est.scale_refit[0], est.R_refit[0], est.t_refit[0])
+    registered, known = a.registered | b.registered, a.known | b.known
+    cameras = np.where(a.registered[:, None], a.cameras, _map_cameras(b.cameras, s, R, t))
+    points = np.where(a.known[:, None], a.points, _map_points(b.points, s, R, t))
+    cameras[~registered], points[~known] = np.nan, np.nan
+    be.set_precision(64)
+    sub = be.assemble_problem(registered, known, min_views=2)
+    x, args, pt_of, obs_feat = sub.gather(cameras, points), sub.args(K), sub.pt_of, sub.obs_feat
+    if len(obs_feat):
+        be.set_fixed_cameras(())
+        be.set_problem(*args)
+        st = be.reprojection_stats(x, want=("obs", "points"), **thr)
+        if st.n_obs_kept < st.n_obs or st.n_points_kept < args[1]:
+            lost = pt_of[~st.pt_keep]
+            known[lost], points[lost] = False, np.nan
+            x, args, oi, pi = prune_problem(x, args, st.obs_keep, st.pt_keep)
+            pt_of, obs_feat = pt_of[pi], obs_feat[oi]
+    rounds = list(a.rounds) + list(b.rounds) + [dict(merged=True, inliers=int(est.refit_inliers[0]), scale=s)]
+    return Reconstruction(registered, cameras, points, known, rounds, tracks, x, args, sub.cam_of, pt_of, obs_feat), est
 
 
 _RESECT_VERDICTS = {1: "few_views", 2: "degenerate", 3: "behind", 4: "high_error"}
