@@ -12,28 +12,6 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFMBA_LIB") or os.path.join(_HERE, "libsfmba.so")   # SFMBA_LIB: diagnostic builds
 
-# every symbol include/sfmba.h declares (tests check the library exports each of them)
-SYMBOLS = (
-    "sfmba_create", "sfmba_destroy", "sfmba_last_error", "sfmba_default_options", "sfmba_set_stream",
-    "sfmba_set_problem", "sfmba_set_problem_i64", "sfmba_exchange_doubles", "sfmba_set_exchange", "sfmba_residuals",
-    "sfmba_residual_jacobian", "sfmba_solve", "sfmba_solve_from", "sfmba_get_fun_grad", "sfmba_time_kernel",
-    "sfmba_normal_blocks", "sfmba_schur_matvec", "sfmba_comm_get_unique_id", "sfmba_comm_init",
-    "sfmba_comm_destroy", "sfmba_set_precision", "sfmba_p2p_export", "sfmba_p2p_attach", "sfmba_p2p_detach",
-    "sfmba_p2p_calls", "sfmba_tr2d_solve", "sfmba_debug_option", "sfmba_set_print", "sfmba_get_counters", "sfmba_problem_reuse", "sfmba_dense_schur",
-    "sfmba_get_pcg_history", "sfmba_set_fixed_cameras", "sfmba_step_products", "sfmba_get_form", "sfmba_rhs_precond",
-    "sfmba_get_mixed_operands", "sfmba_get_iteration_state", "sfmba_default_filter_options", "sfmba_reprojection_stats",
-    "sfmba_default_triangulate_options", "sfmba_triangulate",
-    "sfmba_default_resect_options", "sfmba_resect",
-    "sfmba_default_pnp_ransac_options", "sfmba_resect_ransac",
-    "sfmba_default_ransac_options", "sfmba_fundamental_ransac", "sfmba_default_pose_options", "sfmba_recover_pose",
-    "sfmba_homography_ransac", "sfmba_essential_ransac", "sfmba_similarity_ransac",
-    "sfmba_set_descriptors", "sfmba_default_match_options", "sfmba_match_descriptors",
-    "sfmba_default_track_options", "sfmba_build_tracks", "sfmba_get_tracks",
-    "sfmba_default_plan_options", "sfmba_set_keypoints", "sfmba_plan_views", "sfmba_assemble_problem", "sfmba_get_assembled",
-    "sfmba_default_covariance_options", "sfmba_covariance",
-)
-
-
 class Options(C.Structure):
     _fields_ = [("ftol", C.c_double), ("xtol", C.c_double), ("gtol", C.c_double),
                 ("max_nfev", C.c_int64), ("verbose", C.c_int32), ("max_iter", C.c_int32),
@@ -113,6 +91,81 @@ class CovarianceInfo(C.Structure):
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
 PRINT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
 
+P, INT, I32, I64, F64, STR, REF = C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.c_double, C.c_char_p, C.POINTER
+
+# Every function include/sfmba.h declares, in its order: name -> (restype, argtypes).  P is any data pointer, REF(S) a
+# pointer to an option, result or info structure or to a scalar passed with byref.  tests/test_host_cabi.py holds every
+# entry, and every structure above, to the header.
+SIGNATURES = {
+    "sfmba_create": (INT, [REF(P), INT]),
+    "sfmba_destroy": (None, [P]),
+    "sfmba_last_error": (STR, [P]),
+    "sfmba_default_options": (None, [REF(Options)]),
+    "sfmba_set_print": (INT, [P, PRINT_FN, P]),
+    "sfmba_set_stream": (INT, [P, P]),
+    "sfmba_set_precision": (INT, [P, I32]),
+    "sfmba_set_problem": (INT, [P, I64, I64, I64, P, P, P, P]),
+    "sfmba_problem_reuse": (INT, [P, REF(I64), REF(I64)]),
+    "sfmba_set_problem_i64": (INT, [P, I64, I64, I64, P, P, P, P]),
+    "sfmba_set_fixed_cameras": (INT, [P, P, I64]),
+    "sfmba_exchange_doubles": (I64, [I64]),
+    "sfmba_set_exchange": (INT, [P, P, I64, ALLREDUCE_FN, P, I64]),
+    "sfmba_comm_get_unique_id": (INT, [P]),
+    "sfmba_comm_init": (INT, [P, P, I32, I32, I64]),
+    "sfmba_comm_destroy": (INT, [P]),
+    "sfmba_p2p_export": (INT, [P, I32, P]),
+    "sfmba_p2p_attach": (INT, [P, P, I32, I32]),
+    "sfmba_p2p_detach": (INT, [P]),
+    "sfmba_p2p_calls": (I64, [P]),
+    "sfmba_get_counters": (INT, [P, REF(I64), REF(I64)]),
+    "sfmba_get_form": (INT, [P, STR, REF(I32)]),
+    "sfmba_get_pcg_history": (I32, [P, P, I32]),
+    "sfmba_residuals": (INT, [P, P, P]),
+    "sfmba_residual_jacobian": (INT, [P, P, P, P, P]),
+    "sfmba_default_filter_options": (None, [REF(FilterOptions)]),
+    "sfmba_reprojection_stats": (INT, [P, P, REF(FilterOptions)] + [P] * 13 + [REF(StatsSummary)]),
+    "sfmba_default_triangulate_options": (None, [REF(TriangulateOptions)]),
+    "sfmba_triangulate": (INT, [P, P, P, P, REF(TriangulateOptions)] + [P] * 6 + [REF(I64)]),
+    "sfmba_default_resect_options": (None, [REF(ResectOptions)]),
+    "sfmba_resect": (INT, [P, P, P, P, REF(ResectOptions)] + [P] * 5 + [REF(I64)]),
+    "sfmba_default_pnp_ransac_options": (None, [REF(PnpRansacOptions)]),
+    "sfmba_resect_ransac": (INT, [P] * 5 + [REF(PnpRansacOptions)] + [P] * 12 + [REF(I64), REF(F64)]),
+    "sfmba_default_ransac_options": (None, [REF(RansacOptions)]),
+    "sfmba_fundamental_ransac": (INT, [P, I64] + [P] * 5 + [REF(RansacOptions)] + [P] * 8 + [REF(I64), REF(F64)]),
+    "sfmba_homography_ransac": (INT, [P, I64] + [P] * 5 + [REF(RansacOptions)] + [P] * 10 + [REF(I64), REF(F64)]),
+    "sfmba_similarity_ransac": (INT, [P, I64] + [P] * 5 + [REF(RansacOptions)] + [P] * 10 + [REF(I64), REF(F64)]),
+    "sfmba_essential_ransac": (INT, [P, I64] + [P] * 6 + [REF(RansacOptions)] + [P] * 9 + [REF(I64), REF(F64)]),
+    "sfmba_default_pose_options": (None, [REF(PoseOptions)]),
+    "sfmba_recover_pose": (INT, [P, I64] + [P] * 6 + [REF(PoseOptions)] + [P] * 9 + [REF(I64), REF(F64)]),
+    "sfmba_set_descriptors": (INT, [P, I64, P, P, I32, I32, REF(I32)]),
+    "sfmba_default_match_options": (None, [REF(MatchOptions)]),
+    "sfmba_match_descriptors": (INT, [P, I64, P, REF(MatchOptions)] + [P] * 6 + [REF(I64), REF(F64)]),
+    "sfmba_default_track_options": (None, [REF(TrackOptions)]),
+    "sfmba_build_tracks": (INT, [P, I64, P, I64, P, P, P, P, REF(TrackOptions), P, P, REF(F64)]),
+    "sfmba_get_tracks": (INT, [P, P, P, P]),
+    "sfmba_default_plan_options": (None, [REF(PlanOptions)]),
+    "sfmba_set_keypoints": (INT, [P, I64, P, P]),
+    "sfmba_plan_views": (INT, [P, I64, P, I64, P, REF(PlanOptions)] + [P] * 5 + [REF(F64)]),
+    "sfmba_assemble_problem": (INT, [P, I64, P, I64, P, REF(PlanOptions), P, REF(F64)]),
+    "sfmba_get_assembled": (INT, [P] * 7),
+    "sfmba_solve": (INT, [P, P, REF(Options), REF(Result)]),
+    "sfmba_solve_from": (INT, [P, P, P, REF(Options), REF(Result)]),
+    "sfmba_get_fun_grad": (INT, [P, P, P]),
+    "sfmba_default_covariance_options": (None, [REF(CovarianceOptions)]),
+    "sfmba_covariance": (INT, [P, P, P, I32, REF(CovarianceOptions)] + [P] * 7 + [REF(CovarianceInfo)]),
+    "sfmba_time_kernel": (INT, [P, P, I32, I32, REF(F64)]),
+    "sfmba_normal_blocks": (INT, [P] * 6),
+    "sfmba_schur_matvec": (INT, [P] * 6),
+    "sfmba_step_products": (INT, [P] * 11),
+    "sfmba_rhs_precond": (INT, [P] * 7),
+    "sfmba_get_mixed_operands": (INT, [P] * 5),
+    "sfmba_get_iteration_state": (INT, [P] * 17),
+    "sfmba_dense_schur": (INT, [P] * 7),
+    "sfmba_tr2d_solve": (INT, [P, P, F64, P]),
+    "sfmba_debug_option": (INT, [P, STR, I64]),
+}
+SYMBOLS = tuple(SIGNATURES)     # (tests check the library exports each of them)
+
 _lib = None
 
 
@@ -156,149 +209,10 @@ def load():
             "make -C sfm-python_amd).  sfmba has no CPU fallback.")
     _share_hip_runtime_with_torch()
     lib = C.CDLL(LIB_PATH)
-    P = C.c_void_p
-    lib.sfmba_create.argtypes = [C.POINTER(P), C.c_int]
-    lib.sfmba_create.restype = C.c_int
-    lib.sfmba_destroy.argtypes = [P]
-    lib.sfmba_destroy.restype = None
-    lib.sfmba_last_error.argtypes = [P]
-    lib.sfmba_last_error.restype = C.c_char_p
-    lib.sfmba_default_options.argtypes = [C.POINTER(Options)]
-    lib.sfmba_default_options.restype = None
-    lib.sfmba_set_stream.argtypes = [P, P]
-    lib.sfmba_set_problem.argtypes = [P, C.c_int64, C.c_int64, C.c_int64, P, P, P, P]
-    lib.sfmba_set_problem_i64.argtypes = [P, C.c_int64, C.c_int64, C.c_int64, P, P, P, P]
-    lib.sfmba_exchange_doubles.argtypes = [C.c_int64]
-    lib.sfmba_exchange_doubles.restype = C.c_int64
-    lib.sfmba_set_exchange.argtypes = [P, P, C.c_int64, ALLREDUCE_FN, P, C.c_int64]
-    lib.sfmba_residuals.argtypes = [P, P, P]
-    lib.sfmba_residual_jacobian.argtypes = [P, P, P, P, P]
-    lib.sfmba_solve.argtypes = [P, P, C.POINTER(Options), C.POINTER(Result)]
-    lib.sfmba_solve_from.argtypes = [P, P, P, C.POINTER(Options), C.POINTER(Result)]
-    lib.sfmba_get_fun_grad.argtypes = [P, P, P]
-    lib.sfmba_time_kernel.argtypes = [P, P, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
-    lib.sfmba_normal_blocks.argtypes = [P, P, P, P, P, P]
-    lib.sfmba_schur_matvec.argtypes = [P, P, P, P, P, P]
-    lib.sfmba_dense_schur.argtypes = [P, P, P, P, P, P, P]
-    lib.sfmba_dense_schur.restype = C.c_int
-    if hasattr(lib, "sfmba_step_products"):     # (an older build given through SFMBA_LIB for an A/B run has neither)
-        lib.sfmba_step_products.argtypes = [P] * 11
-        lib.sfmba_step_products.restype = C.c_int
-        lib.sfmba_get_form.argtypes = [P, C.c_char_p, C.POINTER(C.c_int32)]
-        lib.sfmba_get_form.restype = C.c_int
-    if hasattr(lib, "sfmba_rhs_precond"):            # (likewise)
-        lib.sfmba_rhs_precond.argtypes = [P] * 7
-        lib.sfmba_rhs_precond.restype = C.c_int
-    if hasattr(lib, "sfmba_get_mixed_operands"):     # (likewise)
-        lib.sfmba_get_mixed_operands.argtypes = [P] * 5
-        lib.sfmba_get_mixed_operands.restype = C.c_int
-    if hasattr(lib, "sfmba_get_iteration_state"):    # (likewise)
-        lib.sfmba_get_iteration_state.argtypes = [P] * 17
-        lib.sfmba_get_iteration_state.restype = C.c_int
-    if hasattr(lib, "sfmba_reprojection_stats"):     # (likewise)
-        lib.sfmba_default_filter_options.argtypes = [C.POINTER(FilterOptions)]
-        lib.sfmba_default_filter_options.restype = None
-        lib.sfmba_reprojection_stats.argtypes = [P, P, C.POINTER(FilterOptions)] + [P] * 13 + [C.POINTER(StatsSummary)]
-        lib.sfmba_reprojection_stats.restype = C.c_int
-    if hasattr(lib, "sfmba_triangulate"):            # (likewise)
-        lib.sfmba_default_triangulate_options.argtypes = [C.POINTER(TriangulateOptions)]
-        lib.sfmba_default_triangulate_options.restype = None
-        lib.sfmba_triangulate.argtypes = [P, P, P, P, C.POINTER(TriangulateOptions)] + [P] * 6 + [C.POINTER(C.c_int64)]
-        lib.sfmba_triangulate.restype = C.c_int
-    if hasattr(lib, "sfmba_resect"):                 # (likewise)
-        lib.sfmba_default_resect_options.argtypes = [C.POINTER(ResectOptions)]
-        lib.sfmba_default_resect_options.restype = None
-        lib.sfmba_resect.argtypes = [P, P, P, P, C.POINTER(ResectOptions)] + [P] * 5 + [C.POINTER(C.c_int64)]
-        lib.sfmba_resect.restype = C.c_int
-    if hasattr(lib, "sfmba_resect_ransac"):          # (likewise)
-        lib.sfmba_default_pnp_ransac_options.argtypes = [C.POINTER(PnpRansacOptions)]
-        lib.sfmba_default_pnp_ransac_options.restype = None
-        lib.sfmba_resect_ransac.argtypes = ([P] * 5 + [C.POINTER(PnpRansacOptions)] + [P] * 12 +
-                                            [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
-        lib.sfmba_resect_ransac.restype = C.c_int
-    if hasattr(lib, "sfmba_fundamental_ransac"):     # (likewise)
-        lib.sfmba_default_ransac_options.argtypes = [C.POINTER(RansacOptions)]
-        lib.sfmba_default_ransac_options.restype = None
-        lib.sfmba_fundamental_ransac.argtypes = ([P, C.c_int64] + [P] * 5 + [C.POINTER(RansacOptions)] + [P] * 8 +
-                                                 [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
-        lib.sfmba_fundamental_ransac.restype = C.c_int
-        lib.sfmba_default_pose_options.argtypes = [C.POINTER(PoseOptions)]
-        lib.sfmba_default_pose_options.restype = None
-        lib.sfmba_recover_pose.argtypes = ([P, C.c_int64] + [P] * 6 + [C.POINTER(PoseOptions)] + [P] * 9 +
-                                           [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
-        lib.sfmba_recover_pose.restype = C.c_int
-    if hasattr(lib, "sfmba_homography_ransac"):      # (likewise)
-        lib.sfmba_homography_ransac.argtypes = ([P, C.c_int64] + [P] * 5 + [C.POINTER(RansacOptions)] + [P] * 10 +
-                                                [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
-        lib.sfmba_homography_ransac.restype = C.c_int
-    if hasattr(lib, "sfmba_similarity_ransac"):      # (likewise)
-        lib.sfmba_similarity_ransac.argtypes = ([P, C.c_int64] + [P] * 5 + [C.POINTER(RansacOptions)] + [P] * 10 +
-                                                [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
-        lib.sfmba_similarity_ransac.restype = C.c_int
-    if hasattr(lib, "sfmba_essential_ransac"):       # (likewise)
-        lib.sfmba_essential_ransac.argtypes = ([P, C.c_int64] + [P] * 6 + [C.POINTER(RansacOptions)] + [P] * 9 +
-                                               [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
-        lib.sfmba_essential_ransac.restype = C.c_int
-    if hasattr(lib, "sfmba_match_descriptors"):      # (likewise)
-        lib.sfmba_set_descriptors.argtypes = [P, C.c_int64, P, P, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-        lib.sfmba_set_descriptors.restype = C.c_int
-        lib.sfmba_default_match_options.argtypes = [C.POINTER(MatchOptions)]
-        lib.sfmba_default_match_options.restype = None
-        lib.sfmba_match_descriptors.argtypes = ([P, C.c_int64, P, C.POINTER(MatchOptions)] + [P] * 6 +
-                                                [C.POINTER(C.c_int64), C.POINTER(C.c_double)])
-        lib.sfmba_match_descriptors.restype = C.c_int
-    if hasattr(lib, "sfmba_build_tracks"):           # (likewise)
-        lib.sfmba_default_track_options.argtypes = [C.POINTER(TrackOptions)]
-        lib.sfmba_default_track_options.restype = None
-        lib.sfmba_build_tracks.argtypes = ([P, C.c_int64, P, C.c_int64] + [P] * 4 + [C.POINTER(TrackOptions), P, P,
-                                                                                   C.POINTER(C.c_double)])
-        lib.sfmba_build_tracks.restype = C.c_int
-        lib.sfmba_get_tracks.argtypes = [P] * 4
-        lib.sfmba_get_tracks.restype = C.c_int
-    if hasattr(lib, "sfmba_plan_views"):             # (likewise)
-        lib.sfmba_default_plan_options.argtypes = [C.POINTER(PlanOptions)]
-        lib.sfmba_default_plan_options.restype = None
-        lib.sfmba_set_keypoints.argtypes = [P, C.c_int64, P, P]
-        lib.sfmba_set_keypoints.restype = C.c_int
-        lib.sfmba_plan_views.argtypes = [P, C.c_int64, P, C.c_int64, P, C.POINTER(PlanOptions)] + [P] * 5 + [C.POINTER(C.c_double)]
-        lib.sfmba_plan_views.restype = C.c_int
-        lib.sfmba_assemble_problem.argtypes = [P, C.c_int64, P, C.c_int64, P, C.POINTER(PlanOptions), P, C.POINTER(C.c_double)]
-        lib.sfmba_assemble_problem.restype = C.c_int
-        lib.sfmba_get_assembled.argtypes = [P] * 7
-        lib.sfmba_get_assembled.restype = C.c_int
-    if hasattr(lib, "sfmba_covariance"):             # (likewise)
-        lib.sfmba_default_covariance_options.argtypes = [C.POINTER(CovarianceOptions)]
-        lib.sfmba_default_covariance_options.restype = None
-        lib.sfmba_covariance.argtypes = ([P, P, P, C.c_int32, C.POINTER(CovarianceOptions)] + [P] * 7 +
-                                         [C.POINTER(CovarianceInfo)])
-        lib.sfmba_covariance.restype = C.c_int
-    lib.sfmba_tr2d_solve.argtypes = [P, P, C.c_double, P]
-    lib.sfmba_comm_get_unique_id.argtypes = [P]
-    lib.sfmba_comm_init.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int64]
-    lib.sfmba_comm_destroy.argtypes = [P]
-    lib.sfmba_set_precision.argtypes = [P, C.c_int32]
-    lib.sfmba_p2p_export.argtypes = [P, C.c_int32, P]
-    lib.sfmba_p2p_attach.argtypes = [P, P, C.c_int32, C.c_int32]
-    lib.sfmba_p2p_detach.argtypes = [P]
-    lib.sfmba_debug_option.argtypes = [P, C.c_char_p, C.c_int64]
-    lib.sfmba_problem_reuse.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.sfmba_problem_reuse.restype = C.c_int
-    lib.sfmba_get_counters.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.sfmba_get_counters.restype = C.c_int
-    lib.sfmba_get_pcg_history.argtypes = [P, P, C.c_int32]
-    lib.sfmba_get_pcg_history.restype = C.c_int32
-    lib.sfmba_set_print.argtypes = [P, PRINT_FN, P]
-    lib.sfmba_set_print.restype = C.c_int
-    lib.sfmba_set_fixed_cameras.argtypes = [P, P, C.c_int64]
-    lib.sfmba_set_fixed_cameras.restype = C.c_int
-    lib.sfmba_p2p_calls.argtypes = [P]
-    lib.sfmba_p2p_calls.restype = C.c_int64
-    for name in ("sfmba_set_stream", "sfmba_set_problem", "sfmba_set_problem_i64", "sfmba_set_exchange", "sfmba_residuals",
-                 "sfmba_residual_jacobian", "sfmba_solve", "sfmba_solve_from", "sfmba_get_fun_grad", "sfmba_time_kernel",
-                 "sfmba_normal_blocks", "sfmba_schur_matvec", "sfmba_tr2d_solve", "sfmba_comm_get_unique_id",
-                 "sfmba_comm_init", "sfmba_comm_destroy", "sfmba_set_precision", "sfmba_p2p_export",
-                 "sfmba_p2p_attach", "sfmba_p2p_detach", "sfmba_debug_option"):
-        getattr(lib, name).restype = C.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if hasattr(lib, name):      # (an older build given through SFMBA_LIB for an A/B run lacks the newer functions)
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

@@ -32,8 +32,128 @@ def test_library_exports_every_declared_symbol(lib):
         assert hasattr(lib, name), name
 
 
-def test_struct_layouts_match_header():
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+            "double": ctypes.c_double, "void": None}
+
+
+def _parse_header(text):
+    """include/sfmba.h (or a piece of it) without its comments -> (prototypes {name: (ret, [arg types])}, callback typedefs
+    in the same form, structures {name: [(field type, field name)]}).  A type is its text without ``const`` and blanks."""
+    text = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
+
+    def ctype(decl):                                    # "const double* x" -> "double*"
+        return re.sub(r"\bconst\b|\s+", "", decl)
+
+    def args(s):
+        return [ctype(re.fullmatch(r"(.*?)\w+", a.strip(), flags=re.S).group(1)) for a in s.split(",")]
+
+    protos = {m.group(2): (ctype(m.group(1)), args(m.group(3)))
+              for m in re.finditer(r"((?:const\s+)?\w+[\s*]+)(sfmba_\w+)\s*\(([^()]*)\)\s*;", text)}
+    callbacks = {m.group(2): (ctype(m.group(1)), args(m.group(3)))
+                 for m in re.finditer(r"typedef\s+(\w+)\s*\(\s*\*\s*(sfmba_\w+)\s*\)\s*\(([^()]*)\)\s*;", text)}
+    structs = {}
+    for m in re.finditer(r"typedef\s+struct\s+(sfmba_\w+)\s*\{(.*?)\}\s*\1\s*;", text, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in m.group(2).split(";"))):
+            kind, names = re.fullmatch(r"(\w+)\s+(.*)", decl, flags=re.S).groups()
+            fields += [(kind, n.strip()) for n in names.split(",")]
+        structs[m.group(1)] = fields
+    return protos, callbacks, structs
+
+
+def _bound_structure(name):
+    """The ctypes.Structure of `_capi` for a structure of the header: sfmba_pnp_ransac_options -> PnpRansacOptions."""
     from sfmba import _capi
+    return getattr(_capi, "".join(w.capitalize() for w in name.split("_")[1:]), None)
+
+
+def _kind_matches(kind, ct):
+    """Does the ctypes type ``ct`` pass what the header declares as ``kind``?"""
+    from sfmba import _capi
+    if kind in ("sfmba_allreduce_fn", "sfmba_print_fn"):
+        return ct is {"sfmba_allreduce_fn": _capi.ALLREDUCE_FN, "sfmba_print_fn": _capi.PRINT_FN}[kind]
+    if not kind.endswith("*"):
+        return kind in _SCALARS and ct is _SCALARS[kind]
+    if ct is ctypes.c_void_p:
+        return True
+    if ct is ctypes.c_char_p:
+        return kind == "char*"
+    if not (isinstance(ct, type) and issubclass(ct, ctypes._Pointer)):
+        return False
+    target = kind[:-1]                                  # POINTER(S): S is that very structure, or that very scalar
+    if target.startswith("sfmba_") and target != "sfmba_handle*":
+        return _bound_structure(target) is not None and ct._type_ is _bound_structure(target)
+    return ct._type_ is (ctypes.c_void_p if target.endswith("*") else _SCALARS.get(target, "unknown"))
+
+
+def _signature_mismatches(protos, table):
+    """One line for every way a parsed prototype and its entry of the table ``{name: (restype, argtypes)}`` disagree."""
+    out = []
+    for name, (ret, kinds) in protos.items():
+        if name not in table:
+            out.append(f"{name}: not in the table")
+            continue
+        restype, argtypes = table[name]
+        if not _kind_matches(ret, restype):
+            out.append(f"{name}: returns {ret}, restype is {restype}")
+        if len(kinds) != len(argtypes):
+            out.append(f"{name}: {len(kinds)} arguments, argtypes has {len(argtypes)}")
+            continue
+        out += [f"{name}: argument {k} is {kind}, argtypes has {ct}"
+                for k, (kind, ct) in enumerate(zip(kinds, argtypes)) if not _kind_matches(kind, ct)]
+    return out
+
+
+def _header_text():
+    with open(os.path.join(ROOT, "include", "sfmba.h")) as f:
+        return f.read()
+
+
+def test_signature_table_matches_header():
+    """Every prototype of include/sfmba.h against `_capi.SIGNATURES`: the same functions, and for each the number of
+    arguments, the kind of every position and the return type; the two callback typedefs against the CFUNCTYPEs."""
+    from sfmba import _capi
+    protos, callbacks, _ = _parse_header(_header_text())
+    assert len(protos) >= 66
+    assert set(protos) == set(_capi.SIGNATURES) and _capi.SYMBOLS == tuple(_capi.SIGNATURES)
+    assert _signature_mismatches(protos, _capi.SIGNATURES) == []
+    assert set(callbacks) == {"sfmba_allreduce_fn", "sfmba_print_fn"}
+    cfuncs = {name: (fn._restype_, list(fn._argtypes_))
+              for name, fn in (("sfmba_allreduce_fn", _capi.ALLREDUCE_FN), ("sfmba_print_fn", _capi.PRINT_FN))}
+    assert _signature_mismatches(callbacks, cfuncs) == []
+
+
+def test_signature_comparer_reports_a_doctored_prototype():
+    """The comparer fails when it should: a prototype of today's header with an argument removed, and one with an int64_t
+    turned into int32_t, are each reported (and the prototype as it stands is not)."""
+    from sfmba import _capi
+    real = "int  sfmba_comm_init(sfmba_handle* h, const void* id128, int32_t rank, int32_t world,\n" \
+           "                     int64_t n_obs_total);"
+    assert real in _header_text()
+    assert _signature_mismatches(_parse_header(real)[0], _capi.SIGNATURES) == []
+    shorter, narrower = real.replace(" int32_t world,", ""), real.replace("int64_t n_obs_total", "int32_t n_obs_total")
+    assert shorter != real and narrower != real
+    assert _signature_mismatches(_parse_header(shorter)[0], _capi.SIGNATURES) == [
+        "sfmba_comm_init: 4 arguments, argtypes has 5"]
+    assert _signature_mismatches(_parse_header(narrower)[0], _capi.SIGNATURES) == [
+        f"sfmba_comm_init: argument 4 is int32_t, argtypes has {ctypes.c_int64}"]
+
+
+def test_struct_layouts_match_header():
+    """Every structure of include/sfmba.h against its ctypes.Structure, field by field: names, order and types, the
+    ``reserved`` fields included."""
+    from sfmba import _capi
+    _, _, structs = _parse_header(_header_text())
+    assert len(structs) >= 14
+    for name, fields in structs.items():
+        cls = _bound_structure(name)
+        assert cls is not None and issubclass(cls, ctypes.Structure), name
+        assert [f[0] for f in cls._fields_] == [n for _, n in fields], name
+        for (kind, field), (_, ct) in zip(fields, cls._fields_):
+            assert _kind_matches(kind, ct), f"{name}.{field}: header says {kind}, the Structure has {ct}"
+    bound = {_bound_structure(name) for name in structs}
+    assert {v for v in vars(_capi).values() if isinstance(v, type) and issubclass(v, ctypes.Structure)
+            and v is not ctypes.Structure} == bound
     assert ctypes.sizeof(_capi.Options) == 80
     assert ctypes.sizeof(_capi.Result) == 128
 

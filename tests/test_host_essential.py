@@ -73,7 +73,7 @@ def test_python_layer_rejects_bad_arguments():
 
     def _samples(samples, n_edges):                               # as Backend.essential_ransac hands them over
         return _ransac_prologue(_capi.RansacOptions(max_iters=1000), {}, samples, n_edges, 5, "n_edges", "edge", "RANSAC",
-                                then_flush=lambda: None)
+                                strict=True)
     assert _samples(None, 3) is None
     good = _samples(np.zeros((2, 7, 5), dtype=np.int64), 2)
     assert good.dtype == np.int32 and good.shape == (2, 7, 5) and good.flags.c_contiguous

@@ -74,7 +74,7 @@ def test_python_layer_rejects_bad_arguments():
 
     def _homography_samples(samples, n_edges):                   # as Backend.homography_ransac hands them over
         return _ransac_prologue(_capi.RansacOptions(max_iters=1000), {}, samples, n_edges, 4, "n_edges", "edge", "RANSAC",
-                                then_flush=lambda: None)
+                                strict=True)
     assert _homography_samples(None, 3) is None
     good = _homography_samples(np.zeros((2, 5, 4), dtype=np.int64), 2)
     assert good.dtype == np.int32 and good.shape == (2, 5, 4) and good.flags.c_contiguous
