@@ -455,6 +455,88 @@ int  sfmba_resect_ransac(sfmba_handle* h, const double* x, const uint8_t* cam_se
                          int32_t* cam_iters, double* cam_rms_err /* over the inliers */, int32_t* hyp_inliers /* (C,H) */,
                          int64_t* n_ok, double* kernel_us);
 
+/* ---- robust triangulation: view-pair RANSAC over each track, then sfmba_triangulate over the inliers ---------------- */
+/* sfmba_triangulate takes every used observation of a point, so one wrong match in a track -- tracks are the transitive
+ * closure of the matches -- bends its DLT point or fails its verdict, and all the good observations of the track are lost
+ * with it.  This call triangulates every selected point of the current problem from PAIRS of its used observations, scores
+ * each pair's point over all of them, and hands the inliers of the best to sfmba_triangulate's kernel: the caller gets a
+ * per-observation mask, drops one observation and keeps the point.  No local optimisation inside the loop, no adaptive
+ * exit, no caller-supplied pairs, and the mask is not recomputed after the refinement.
+ *
+ * A point's "used observations" are numbered 0 .. n-1 in stored (point-major) order among the used; the hypotheses, their
+ * counts, the best, the mask and X_hyp of a masked call are bit for bit what the problem without those observations gives.
+ * (So are the outputs of the refinement -- X_out, pt_iters, pt_rms_err, pt_angle_deg -- for every point with fewer than 32
+ * STORED observations: k_triangulate adds such a run in stored order, a longer one lane by lane of a wave from its stored
+ * positions, which a mask shifts; there the two agree as two refinements that stop on xtol do.)
+ *   hypotheses  M = n (n - 1) / 2, H = max_pairs.  M <= H: every pair (i < j) in lexicographic order -- (0,1), (0,2), ..,
+ *               (0,n-1), (1,2), .., (n-2,n-1) --, h = 0 .. M-1; a hypothesis h >= M does not exist (hyp_inliers: -1).
+ *               M > H: H hypotheses, hypothesis h the pair (first draw, second draw) of the counter-based rule of
+ *               sfmba_fundamental_ransac with two draws:
+ *                 key = mix(seed ^ mix(p << 32 | h)), p the point's index in the problem (not its rank among the selected)
+ *                 draw j = 0, 1: k = mix(key + (j + 1) 0x9e3779b97f4a7c15) mod (n - j); second draw: if (k >= first) ++k
+ *               Two hypotheses may name the same pair.
+ *   point       of a pair (a, b), in this order: the two-view case of sfmba_triangulate's linear stage -- rows u M3 - M1,
+ *               v M3 - M2 of a, then of b, with M = K R [I | -T] in pixel units, A^T A as ten sums, its smallest eigenvector
+ *               w by the same cyclic Jacobi rotations, X = w[:3] / w[3]: cv2.triangulatePoints of the two views.  It is
+ *               VALID when X is finite, |w[3]| > 1e-12 |w|, the depth of X (third component of R (X - T)) is above
+ *               min_depth in a and in b, and the angle between the rays X - T_a and X - T_b, atan2(|r_a x r_b|, r_a . r_b)
+ *               in degrees, is at least min_pair_angle_deg.
+ *   score       the used observations with |pi(K R (X - T)) - uv|^2 STRICTLY below threshold^2 and depth above min_depth;
+ *               a non-finite value is no inlier; the pair's own two views are scored like any other.  A pair whose point
+ *               is not valid scores 0.
+ *   best        the largest count, the lowest h among equals (all counts 0: h = 0).  The mask is that of the best
+ *               hypothesis, evaluated once more -- all zero when its point is not valid --, and pt_inliers is counted
+ *               FROM that mask: mask, count and the refinement's input agree by construction.
+ *   refinement  sfmba_triangulate's kernel (k_triangulate, unchanged) with the inlier mask as its obs_use and, as its
+ *               pt_select, the points whose best hypothesis is valid with at least max(2, min_views) inliers: the n-view
+ *               DLT over the inliers, Gauss-Newton and the verdict with max_iter, xtol, min_angle_deg, min_depth and
+ *               max_error_px as there.  refine = 0: max_iter = 0 (the n-view DLT over the inliers and its verdict).
+ *   verdict     first match wins (pt_status):
+ *                  -1 the point was not selected
+ *                   1 FEW_VIEWS     fewer used observations than max(2, min_views)
+ *                   6 NO_CONSENSUS  no valid best hypothesis with at least max(2, min_views) inliers
+ *                   2 AT_INFINITY / 3 BEHIND / 4 LOW_ANGLE / 5 HIGH_ERROR  k_triangulate's verdict over the inliers
+ *                   0 OK            otherwise
+ * X_out (P,3): the refined point for status 0, the point of x otherwise.  X_hyp (P,3): the best hypothesis' point wherever
+ * it is valid -- NO_CONSENSUS for want of inliers still reports it, with the count, h and mask --, else the point of x.
+ * inlier_mask (N, the caller's order): 0 for observations that took no part.  pt_views: used observations of a selected
+ * point (else 0).  pt_inliers: the count of the mask.  pt_best: h of the best hypothesis; -1: not selected or FEW_VIEWS.
+ * pt_iters, pt_rms_err, pt_angle_deg: k_triangulate's, over the inliers, for every point that reached it and got past
+ * AT_INFINITY; else 0, NaN, NaN.  hyp_inliers (P,H): the count of every hypothesis (-1: it does not exist, or the point is
+ * not selected or FEW_VIEWS).  n_ok: points with status 0.  kernel_us: with profile = 1 the HIP-event time of the call's
+ * launches, else 0.
+ *
+ * pt_select, obs_use, NULL outputs and opt = NULL as for sfmba_triangulate.  Returns -1 when no problem is set, x is NULL,
+ * an option is NaN, max_pairs < 1, hyp_inliers is asked for with P * H >= 2^31, or the handle waits for its transport.  As
+ * sfmba_triangulate: on a sharded handle the call describes the LOCAL shard only (p is the local index); pixels are read
+ * as stored (fp64 or fp32); every buffer is the call's own, sfmba_triangulate's or the statistics call's, so fun, grad, the
+ * PCG record and a following solve are exactly what a fresh handle gives; no atomics, sums in a fixed order, a point's
+ * results depend on nothing but its own inputs: same input, same bits. */
+typedef struct sfmba_tri_ransac_options {
+    double   threshold;          /* pixels (default 4.0) */
+    double   min_depth;          /* an inlier, and a pair's point in its two views, has depth above this; the verdict's too (0.0) */
+    double   min_pair_angle_deg; /* smallest angle between the two rays of a hypothesis (1.0) */
+    uint64_t seed;               /* of the drawn pairs (0) */
+    int32_t  max_pairs;          /* hypotheses per point, H, at least 1; a point with at most H pairs takes them all (64) */
+    int32_t  min_views;          /* used observations a point needs, and inliers its best hypothesis needs; below 2 counts as 2 (2) */
+    int32_t  refine;             /* 1 = Gauss-Newton over the inliers after their n-view DLT (1) */
+    int32_t  profile;            /* 1 = kernel_us is measured (0) */
+    int32_t  max_iter;           /* the refinement's trial points, as sfmba_triangulate's max_iter (default 10) */
+    int32_t  reserved;
+    double   xtol;               /* as sfmba_triangulate's xtol (default 1e-10) */
+    double   min_angle_deg;      /* as sfmba_triangulate's min_angle_deg, over the inliers (default 1.0) */
+    double   max_error_px;       /* as sfmba_triangulate's max_error_px, over the inliers (default +inf) */
+} sfmba_tri_ransac_options;
+void sfmba_default_tri_ransac_options(sfmba_tri_ransac_options* opt);
+int  sfmba_triangulate_ransac(sfmba_handle* h, const double* x, const uint8_t* pt_select /* P or NULL = all */,
+                              const uint8_t* obs_use /* N, caller's order, or NULL = all */,
+                              const sfmba_tri_ransac_options* opt,
+                              double* X_out /* (P,3) */, double* X_hyp /* (P,3) best hypothesis, unrefined */,
+                              uint8_t* inlier_mask /* N, caller's order */, int32_t* pt_status, int32_t* pt_views,
+                              int32_t* pt_inliers, int32_t* pt_best /* h */, int32_t* pt_iters,
+                              double* pt_rms_err /* over the inliers */, double* pt_angle_deg, int32_t* hyp_inliers /* (P,H) */,
+                              int64_t* n_ok, double* kernel_us);
+
 /* ---- two-view geometry: F by RANSAC and pose recovery for a batch of edges (sfm.py:88-107, 120-180) -------------- */
 /* A batch of edges (image pairs) that is independent of the bundle-adjustment problem: neither call needs
  * sfmba_set_problem, both ignore sfmba_set_precision (pairs are always fp64) and any transport, and both use buffers of
@@ -942,6 +1024,8 @@ int  sfmba_covariance(sfmba_handle* h, const double* x, const int32_t* hold, int
  *        16 k_resect of sfmba_resect over every camera and observation (default options).
  *        17 k_pnp_ransac + k_pnp_finish of sfmba_resect_ransac over every camera and observation (default options).
  *        18 the kernels of sfmba_covariance with the default options, point sweep included (kind = 1 above 21 cameras).
+ *        19 the kernels of sfmba_triangulate_ransac (k_tri_ransac, then k_triangulate over its mask) at the default
+ *           options over every point and observation.
  * avg_us: average duration of one repetition. */
 int  sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t reps, double* avg_us);
 /* Normal-equation blocks at x: U (C,21 upper triangle row-major), V (P,6 upper), gc (C,6), gp (P,3). */

@@ -4,6 +4,15 @@
 #pragma once
 #include "ba_device.hpp"
 #include "consumer_device.hpp"   // for_each_long_run, the register Jacobi: shared with cov_kernels.hpp
+#include "tri_pairs.hpp"         // the pair numbering of k_tri_ransac, host and device
+
+// The workgroup scan of the feature tracks (track_scan.hpp), for k_tri_ransac.  Its three sizes as track_kernels.hpp
+// defines them (plan_kernels.hpp restates them likewise); only track_block_scan is used here, no launch of the scan.
+constexpr int kTrackBlock = 256;
+constexpr int kTrackScanPerThread = 4;
+constexpr int kTrackScanItems = 1024;
+static_assert(kTrackScanItems == kTrackBlock * kTrackScanPerThread, "a thread scans kTrackScanPerThread consecutive entries");
+#include "track_scan.hpp"
 
 namespace sfmba {
 
@@ -466,6 +475,29 @@ __device__ __forceinline__ void tri_load_row(const double* __restrict__ rt, int 
     for (int k = kCamRT; k < kCamRow; ++k) tl[k] = 0.0;
 }
 
+// a += the two DLT rows of the observation stored at k: the body of the n-view pass below and of the two-view
+// hypotheses of k_tri_ransac
+template <bool F32>
+__device__ __forceinline__ void tri_dlt_rows(const double* __restrict__ rt, const TriIn& in, int k, const KMat& K, double (&a)[10]) {
+    double tl[kCamRow];
+    tri_load_row(rt, in.cam_idx[k], tl);
+    const double2 px = load_pair(in.uv, F32, k);
+    double m[12];                                                // M = K R [I | -T], row-major 3x4
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) m[4 * i + j] = K.k[3 * i] * tl[j] + K.k[3 * i + 1] * tl[3 + j] + K.k[3 * i + 2] * tl[6 + j];
+        m[4 * i + 3] = -(m[4 * i] * tl[9] + m[4 * i + 1] * tl[10] + m[4 * i + 2] * tl[11]);
+    }
+    double ru[4], rv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { ru[j] = px.x * m[8 + j] - m[j]; rv[j] = px.y * m[8 + j] - m[4 + j]; }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = i; j < 4; ++j) a[sym<4>(i, j)] += ru[i] * ru[j] + rv[i] * rv[j];
+}
+
 // the linear stage's pass: a += the two DLT rows of every used observation; used = their number
 template <bool F32, bool WAVE>
 __device__ __forceinline__ void tri_dlt_pass(const double* __restrict__ rt, const TriIn& in, int b, int e, int lane,
@@ -476,23 +508,7 @@ __device__ __forceinline__ void tri_dlt_pass(const double* __restrict__ rt, cons
 #pragma unroll 1
     for (int k = WAVE ? b + lane : b; k < e; k += WAVE ? 64 : 1) {
         if (in.use != nullptr && !in.use[k]) continue;
-        double tl[kCamRow];
-        tri_load_row(rt, in.cam_idx[k], tl);
-        const double2 px = load_pair(in.uv, F32, k);
-        double m[12];                                            // M = K R [I | -T], row-major 3x4
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) m[4 * i + j] = K.k[3 * i] * tl[j] + K.k[3 * i + 1] * tl[3 + j] + K.k[3 * i + 2] * tl[6 + j];
-            m[4 * i + 3] = -(m[4 * i] * tl[9] + m[4 * i + 1] * tl[10] + m[4 * i + 2] * tl[11]);
-        }
-        double ru[4], rv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { ru[j] = px.x * m[8 + j] - m[j]; rv[j] = px.y * m[8 + j] - m[4 + j]; }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = i; j < 4; ++j) a[sym<4>(i, j)] += ru[i] * ru[j] + rv[i] * rv[j];
+        tri_dlt_rows<F32>(rt, in, k, K, a);
         ++used;
     }
     if (WAVE) {
@@ -3195,6 +3211,260 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_finish(PnpIn in, const int*
         for (int k = 0; k < 6; ++k) {
             out.hyp[6 * (size_t)c + k] = prm[k];
             if (ok) out.x[6 * (size_t)c + k] = prm[k];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Robust triangulation (sfmba_triangulate_ransac): per selected point, hypotheses from PAIRS of its
+// used observations -- all of them in lexicographic order while there are at most H (tri_pair_unrank), else H drawn by the
+// counter rule with two draws (ransac_sample<2>) --, each the two-view case of the n-view DLT above (tri_dlt_rows twice,
+// smallest_eigenvector4) and scored over every used observation of the point; the largest count wins, the lowest h among
+// equals; the best is evaluated once more for the mask.  k_triangulate then runs over the mask (launch_triangulate).
+//   k_tri_ransac   a workgroup takes kTriRansacThreads consecutive points, one per thread.  SHORT runs (fewer than
+//                  kStatsLongTrack stored observations): the points' hypothesis numbers m_p are scanned over the
+//                  workgroup (track_block_scan) and the hypotheses handed out ONE PER LANE in rounds of the workgroup's
+//                  width -- a lane finds its point by bisection of the prefix array in LDS --, so a wave is full whatever
+//                  the mix of track lengths (a lane per point would wait for the longest track with the Jacobi state idle
+//                  in 63 lanes, a wave per point wastes it below 12 views).  A lane leaves its count in LDS; after
+//                  a round the point's own thread walks its piece of the round in ascending h and keeps the first
+//                  largest, then evaluates that hypothesis again: X_hyp, the mask in stored order, the count from the mask.
+//                  LONG runs are taken by the wave afterwards, one after the other (for_each_long_run): lanes are
+//                  hypotheses, every lane walks the same observations (uniform addresses), the wave's best by a maximum
+//                  and a ballot, the mask by lanes striding the run.
+// A hypothesis is computed by one lane from the point's own inputs in both forms and counts are integers: a point's
+// results do not depend on its chunk, round, wave or neighbours.  No atomics.
+// ---------------------------------------------------------------------------------------------
+constexpr int kTriRansacThreads = 256;
+static_assert(kTriRansacThreads == kTrackBlock, "track_block_scan scans a workgroup of kTrackBlock threads");
+static_assert((long long)kTriRansacThreads * (kStatsLongTrack - 1) * (kStatsLongTrack - 2) / 2 < (1ll << 31),
+              "the hypotheses of a chunk's short runs are numbered with an int");
+constexpr int kTriNoConsensus = 6;
+constexpr size_t kTriRansacStaticLds = 4096;     // room for k_tri_ransac's static LDS (prefix, used counts, a round's counts, the scan's sums)
+struct TriRansacOptions { int H, need; double thr2, min_depth, min_pair_angle_deg; unsigned long long seed; };
+struct TriRansacOut {
+    double* __restrict__ X_hyp;                  // [P][3]
+    unsigned char* __restrict__ mask;            // [N] stored order; ZERO on entry: only a valid best hypothesis writes its run
+    unsigned char* __restrict__ ok;              // [P] the best count reaches the need: k_triangulate's select
+    int* __restrict__ status;                    // [P] -1, FEW_VIEWS, NO_CONSENSUS, or 0: k_triangulate's verdict counts
+    int* __restrict__ views;
+    int* __restrict__ inliers;
+    int* __restrict__ best;
+    int* __restrict__ hyp;                       // [P][H], -1 on entry, or null
+};
+struct TriRansacResult { int status, views, inliers, best; double X, Y, Z; };
+
+// stored position of the i-th used observation of the run [b, e)
+__device__ __forceinline__ int tri_used_position(const TriIn& in, int b, int e, int i) {
+    if (in.use == nullptr) return b + i;
+    int k = b;
+#pragma unroll 1
+    for (; k < e; ++k)
+        if (in.use[k] && i-- == 0) break;
+    return k;
+}
+
+// The point of the observations stored at ka and kb (in this order): false when it is not valid -- not finite,
+// |w3| <= 1e-12 |w|, a depth of the two at most min_depth, or the angle between the two rays below the limit.
+template <bool F32>
+__device__ __forceinline__ bool tri_pair_point(const double* __restrict__ rt, const TriIn& in, const KMat& K, int ka, int kb,
+                                               const TriRansacOptions& o, double& X, double& Y, double& Z) {
+    constexpr double kDeg = 57.295779513082320877;
+    double a[10];
+#pragma unroll
+    for (int q = 0; q < 10; ++q) a[q] = 0.0;
+    tri_dlt_rows<F32>(rt, in, ka, K, a);
+    tri_dlt_rows<F32>(rt, in, kb, K, a);
+    double w0, w1, w2, w3;
+    smallest_eigenvector4(a, w0, w1, w2, w3);
+    const double nw = sqrt(w0 * w0 + w1 * w1 + w2 * w2 + w3 * w3);
+    X = w0 / w3; Y = w1 / w3; Z = w2 / w3;
+    if (!(fabs(w3) > 1e-12 * nw)) return false;                  // (false for a NaN as well)
+    if (!(fabs(X) + fabs(Y) + fabs(Z) < INFINITY)) return false;
+    const double* __restrict__ ra = rt + (size_t)in.cam_idx[ka] * kCamRT;
+    const double* __restrict__ rb = rt + (size_t)in.cam_idx[kb] * kCamRT;
+    if (!(cam_depth(ra, X, Y, Z) > o.min_depth && cam_depth(rb, X, Y, Z) > o.min_depth)) return false;
+    const double ax = X - ra[9], ay = Y - ra[10], az = Z - ra[11], bx = X - rb[9], by = Y - rb[10], bz = Z - rb[11];
+    const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+    const double ang = kDeg * atan2(sqrt(cx * cx + cy * cy + cz * cz), ax * bx + ay * by + az * bz);
+    return ang >= o.min_pair_angle_deg;
+}
+
+// used observations of [b, e), every step-th from b + first, with squared error strictly below thr2 and depth above
+// min_depth at (X, Y, Z); WRITE: each one's verdict into mask
+template <bool F32, bool WRITE>
+__device__ __forceinline__ int tri_count_inliers(const double* __restrict__ rt, const TriIn& in, const KMat& K, int b, int e,
+                                                 int first, int step, double X, double Y, double Z, const TriRansacOptions& o,
+                                                 unsigned char* __restrict__ mask) {
+    int count = 0;
+#pragma unroll 1
+    for (int k = b + first; k < e; k += step) {
+        if (in.use != nullptr && !in.use[k]) continue;
+        double tl[kCamRow];
+        tri_load_row(rt, in.cam_idx[k], tl);
+        const double2 px = load_pair(in.uv, F32, k);
+        double rx, ry;
+        observe<false>(tl, X, Y, Z, px.x, px.y, K, rx, ry, nullptr, nullptr);
+        const bool inl = rx * rx + ry * ry < o.thr2 && cam_depth(tl, X, Y, Z) > o.min_depth;     // (a NaN: no inlier)
+        if (WRITE) mask[k] = inl ? 1 : 0;
+        count += inl ? 1 : 0;
+    }
+    return count;
+}
+
+// the pair of hypothesis h of point p with n used observations in [b, e): stored positions, in the hypothesis' order
+__device__ __forceinline__ void tri_hypothesis_pair(const TriIn& in, const TriRansacOptions& o, int p, int b, int e, int n, int h,
+                                                    int& ka, int& kb) {
+    int i, j;
+    if (tri_pair_count(n) <= (long long)o.H) {
+        tri_pair_unrank(n, h, i, j);
+    } else {
+        int idx[2];
+        ransac_sample<2>(nullptr, p, o.H, h, n, o.seed, idx);
+        i = idx[0]; j = idx[1];
+    }
+    ka = tri_used_position(in, b, e, i);
+    kb = tri_used_position(in, b, e, j);
+}
+
+// count of hypothesis h (0: its point is not valid)
+template <bool F32>
+__device__ __forceinline__ int tri_hypothesis(const double* __restrict__ rt, const TriIn& in, const KMat& K,
+                                              const TriRansacOptions& o, int p, int b, int e, int n, int h) {
+    int ka, kb;
+    tri_hypothesis_pair(in, o, p, b, e, n, h, ka, kb);
+    double X, Y, Z;
+    if (!tri_pair_point<F32>(rt, in, K, ka, kb, o, X, Y, Z)) return 0;
+    return tri_count_inliers<F32, false>(rt, in, K, b, e, 0, 1, X, Y, Z, o, nullptr);
+}
+
+// hypotheses of a point with n used observations (0: fewer than the need)
+__device__ __forceinline__ int tri_hypotheses(const TriRansacOptions& o, int n) {
+    return n < o.need ? 0 : (int)min(tri_pair_count(n), (long long)o.H);
+}
+
+template <bool LDS_TAB, bool F32>
+__global__ __launch_bounds__(kTriRansacThreads) void k_tri_ransac(const double* __restrict__ camtab, TriIn in, int P, int C, KMat K,
+                                                                  TriRansacOptions o, TriRansacOut out) {
+    extern __shared__ __align__(16) double smem[];
+    __shared__ int pre[kTriRansacThreads + 1];                   // exclusive scan of the chunk's hypothesis numbers
+    __shared__ int nus[kTriRansacThreads];                       // used observations of the chunk's points
+    __shared__ int cnt[kTriRansacThreads];                       // the counts of a round
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    const double* __restrict__ rt_global = camtab + cam_rt_offset(C);
+    if (LDS_TAB) stage_table(rt_global, C * kCamRT, smem);
+    const double* __restrict__ rt = LDS_TAB ? smem : rt_global;
+    for (int base = blockIdx.x * kTriRansacThreads; base < P; base += gridDim.x * kTriRansacThreads) {     // uniform over the workgroup
+        const int p = base + tid;
+        int b = 0, e = 0;
+        double X0 = 0.0, Y0 = 0.0, Z0 = 0.0;
+        bool sel = false;
+        if (p < P) {
+            b = in.pt_ptr[p]; e = in.pt_ptr[p + 1];
+            X0 = in.pts[3 * (size_t)p]; Y0 = in.pts[3 * (size_t)p + 1]; Z0 = in.pts[3 * (size_t)p + 2];
+            sel = in.select == nullptr || in.select[p] != 0;
+        }
+        const bool is_long = sel && e - b >= kStatsLongTrack;
+        TriRansacResult r;
+        r.status = kTriNotSelected; r.views = 0; r.inliers = 0; r.best = -1;
+        r.X = X0; r.Y = Y0; r.Z = Z0;
+        // ---- short runs: one hypothesis per lane
+        int n = 0;
+        if (sel && !is_long) {
+            n = e - b;
+            if (in.use != nullptr) {
+                n = 0;
+                for (int k = b; k < e; ++k) n += in.use[k] ? 1 : 0;
+            }
+            r.views = n;
+            r.status = kTriFewViews;
+        }
+        const int m = sel && !is_long ? tri_hypotheses(o, n) : 0;
+        long long c_ex, s_ex, c_tot, s_tot;
+        track_block_scan(m ? 1 : 0, m, c_ex, s_ex, c_tot, s_tot);
+        const int mine = (int)s_ex, total = (int)s_tot;
+        pre[tid] = mine;
+        nus[tid] = n;
+        if (tid == 0) pre[kTriRansacThreads] = total;
+        __syncthreads();
+        int bc = -1, bh = 0;                                     // the point's best so far: count, h
+        for (int r0 = 0; r0 < total; r0 += kTriRansacThreads) {  // (uniform over the workgroup)
+            const int g = r0 + tid;
+            int c = 0;
+            if (g < total) {
+                int lo = 0, hi = kTriRansacThreads;              // pre[lo] <= g < pre[hi]: the last lo has hypotheses
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (pre[mid] <= g) lo = mid; else hi = mid;
+                }
+                const int q = base + lo, h = g - pre[lo];
+                c = tri_hypothesis<F32>(rt, in, K, o, q, in.pt_ptr[q], in.pt_ptr[q + 1], nus[lo], h);
+                if (out.hyp != nullptr) out.hyp[(size_t)q * (size_t)o.H + (size_t)h] = c;
+            }
+            cnt[tid] = c;
+            __syncthreads();
+            const int g0 = max(mine, r0), g1 = min(mine + m, r0 + kTriRansacThreads);
+            for (int k = g0; k < g1; ++k) {                      // ascending h: only a larger count replaces
+                const int ck = cnt[k - r0];
+                if (ck > bc) { bc = ck; bh = k - mine; }
+            }
+            __syncthreads();
+        }
+        if (m > 0) {
+            int ka, kb;
+            tri_hypothesis_pair(in, o, p, b, e, n, bh, ka, kb);
+            double X, Y, Z;
+            const bool valid = tri_pair_point<F32>(rt, in, K, ka, kb, o, X, Y, Z);
+            r.best = bh;
+            if (valid) {
+                r.inliers = tri_count_inliers<F32, true>(rt, in, K, b, e, 0, 1, X, Y, Z, o, out.mask);
+                r.X = X; r.Y = Y; r.Z = Z;
+            }
+            r.status = valid && r.inliers >= o.need ? kTriOk : kTriNoConsensus;
+        }
+        // ---- long runs: the wave, lanes are hypotheses
+        for_each_long_run(is_long, b, e, X0, Y0, Z0, [&](int ql, int qb, int qe, double qX, double qY, double qZ) {
+            const int q = base + (tid - lane) + ql;
+            TriRansacResult w;
+            w.status = kTriFewViews; w.inliers = 0; w.best = -1;
+            w.X = qX; w.Y = qY; w.Z = qZ;
+            int nq = qe - qb;
+            if (in.use != nullptr) {
+                nq = 0;
+                for (int k = qb + lane; k < qe; k += 64) nq += in.use[k] ? 1 : 0;
+                nq = wave_isum(nq);
+            }
+            w.views = nq;
+            const int mq = tri_hypotheses(o, nq);
+            if (mq > 0) {
+                int wc = -1, wh = 0;
+                for (int hb = 0; hb < mq; hb += 64) {
+                    const int h = hb + lane;
+                    int c = -2;
+                    if (h < mq) {
+                        c = tri_hypothesis<F32>(rt, in, K, o, q, qb, qe, nq, h);
+                        if (out.hyp != nullptr) out.hyp[(size_t)q * (size_t)o.H + (size_t)h] = c;
+                    }
+                    const int top = wave_reduce_xor(c, [](int x, int y) { return max(x, y); });
+                    if (top > wc) { wc = top; wh = hb + __ffsll((long long)__ballot(c == top)) - 1; }
+                }
+                int ka, kb;
+                tri_hypothesis_pair(in, o, q, qb, qe, nq, wh, ka, kb);
+                double X, Y, Z;
+                const bool valid = tri_pair_point<F32>(rt, in, K, ka, kb, o, X, Y, Z);    // (every lane alike)
+                w.best = wh;
+                if (valid) {
+                    w.inliers = wave_isum(tri_count_inliers<F32, true>(rt, in, K, qb, qe, lane, 64, X, Y, Z, o, out.mask));
+                    w.X = X; w.Y = Y; w.Z = Z;
+                }
+                w.status = valid && w.inliers >= o.need ? kTriOk : kTriNoConsensus;
+            }
+            if (lane == ql) r = w;
+        });
+        if (p < P) {
+            out.X_hyp[3 * (size_t)p] = r.X; out.X_hyp[3 * (size_t)p + 1] = r.Y; out.X_hyp[3 * (size_t)p + 2] = r.Z;
+            out.status[p] = r.status; out.views[p] = r.views; out.inliers[p] = r.inliers; out.best[p] = r.best;
+            out.ok[p] = r.status == kTriOk ? 1 : 0;
         }
     }
 }

@@ -1,5 +1,5 @@
 // consumers.hip -- host code of the consumers of a solved scene (kernels: consumer_kernels.hpp): reprojection statistics,
-// triangulation, resection, robust resection and two-view geometry.  None touches a buffer of the solver's.
+// triangulation, robust triangulation, resection, robust resection and two-view geometry.  None touches a buffer of the solver's.
 #include "handle.hpp"
 #include "consumer_kernels.hpp"
 
@@ -165,8 +165,8 @@ TriOptions tri_options(const sfmba_triangulate_options& o) {
     return TriOptions{(int)o.max_iter, (int)o.min_views, o.xtol, o.min_angle_deg, o.min_depth, o.max_error_px};
 }
 
-// the table of stats_prepare(h, x) must be in place; use / select: the masks are on the device
-int launch_triangulate(sfmba_handle* h, const TriOptions& opt, bool use, bool select, int grid) {
+// the table of stats_prepare(h, x) must be in place; use [ld, stored order] / select [P]: masks on the device, null: all
+int launch_triangulate(sfmba_handle* h, const TriOptions& opt, const unsigned char* use, const unsigned char* select, int grid) {
     auto& s = h->stats;
     auto& t = h->tri;
     const size_t P = (size_t)h->P;
@@ -176,8 +176,7 @@ int launch_triangulate(sfmba_handle* h, const TriOptions& opt, bool use, bool se
                         : (h->f32 ? k_triangulate<false, true> : k_triangulate<false, false>);
     CHK(set_lds(h, kern, lds));
     const TriIn in{h->pt_ptr.as<int>(), h->cam_idx.as<int>(), h->uv.as<double>(),
-                   use ? s.use.as<unsigned char>() : nullptr, select ? t.select.as<unsigned char>() : nullptr,
-                   s.x.as<double>() + 6 * h->C};
+                   use, select, s.x.as<double>() + 6 * h->C};
     const TriOut out{t.X.as<double>(), t.ints.as<int>(), t.ints.as<int>() + P, t.ints.as<int>() + 2 * P,
                      t.dbl.as<double>(), t.dbl.as<double>() + P, t.ok_part.as<int>()};
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kTriThreads), lds, h->stream, (const double*)s.tab.as<double>(), in, (int)h->P,
@@ -209,7 +208,8 @@ int sfmba_triangulate(sfmba_handle* h, const double* x, const uint8_t* pt_select
     CHK(tri_allocate(h, &grid));
     CHK(stats_prepare(h, x));
     CHK(stage_masks(h, obs_use, pt_select, P, t.select, (size_t)grid, &counts));
-    CHK(launch_triangulate(h, tri_options(o), obs_use != nullptr, pt_select != nullptr, grid));
+    CHK(launch_triangulate(h, tri_options(o), obs_use ? h->stats.use.as<unsigned char>() : nullptr,
+                           pt_select ? t.select.as<unsigned char>() : nullptr, grid));
     const int* pi = t.ints.as<int>();
     HIPCHK(h, download(h, X_out, t.X.p, sizeof(double) * 3 * P));
     HIPCHK(h, download(h, pt_status, pi, sizeof(int32_t) * P));
@@ -218,6 +218,132 @@ int sfmba_triangulate(sfmba_handle* h, const double* x, const uint8_t* pt_select
     HIPCHK(h, download(h, pt_rms_err, t.dbl.p, sizeof(double) * P));
     HIPCHK(h, download(h, pt_angle_deg, t.dbl.as<double>() + P, sizeof(double) * P));
     return finish_with_ok_count(h, t.ok_part.as<int>(), (size_t)grid, counts, n_ok);
+}
+
+namespace {
+// ---- robust triangulation (sfmba_triangulate_ransac; kernel: consumer_kernels.hpp, "Robust triangulation") ---------------
+TriRansacOptions tri_ransac_options(const sfmba_tri_ransac_options& o) {
+    return TriRansacOptions{(int)o.max_pairs, std::max((int)o.min_views, 2), o.threshold * o.threshold, o.min_depth,
+                            o.min_pair_angle_deg, (unsigned long long)o.seed};
+}
+
+// sfmba_triangulate's buffers (k_triangulate runs last) and the call's own
+int tri_ransac_allocate(sfmba_handle* h, int H, bool hyp, int* grid, int* tri_grid) {
+    auto& q = h->tri_ransac;
+    const size_t ldz = (size_t)h->ld, P = (size_t)h->P;
+    *grid = grid_1d(h->P, kTriRansacThreads, h->n_cu);
+    CHK(tri_allocate(h, tri_grid));
+    return ensure_all(h, {{&q.mask, ldz}, {&q.ok, P}, {&q.X_hyp, sizeof(double) * 3 * P}, {&q.ints, sizeof(int) * 4 * P},
+                          {&q.hyp, hyp ? sizeof(int) * P * (size_t)H : 0}});
+}
+
+// what k_tri_ransac finds in place: a mask of zeros (only a valid best hypothesis writes its run), counts of -1
+int tri_ransac_clear(sfmba_handle* h, int H, bool hyp) {
+    auto& q = h->tri_ransac;
+    if (h->ld) HIPCHK(h, hipMemsetAsync(q.mask.p, 0, (size_t)h->ld, h->stream));
+    if (hyp && h->P) HIPCHK(h, hipMemsetAsync(q.hyp.p, 0xff, sizeof(int) * (size_t)h->P * (size_t)H, h->stream));
+    return 0;
+}
+
+// k_tri_ransac, then k_triangulate over its mask for the points whose best count reaches the need.  The table of
+// stats_prepare(h, x) and the cleared buffers must be in place; use / select: the caller's masks are on the device
+int launch_tri_ransac(sfmba_handle* h, const TriRansacOptions& ro, const TriOptions& to, bool use, bool select, bool hyp, int grid,
+                      int tri_grid) {
+    auto& s = h->stats;
+    auto& q = h->tri_ransac;
+    const size_t P = (size_t)h->P;
+    const bool lds_tab = h->forms.lds_tab;
+    const size_t lds = lds_tab ? (size_t)h->C * kCamRT * sizeof(double) : 0;
+    auto kern = lds_tab ? (h->f32 ? k_tri_ransac<true, true> : k_tri_ransac<true, false>)
+                        : (h->f32 ? k_tri_ransac<false, true> : k_tri_ransac<false, false>);
+    // About 3 KiB of static LDS (kTriRansacStaticLds bounds it) stand beside the table: the opt-in is asked for as soon as
+    // the two together pass 64 KiB, and leaves that room below the 160 KiB of a CU.
+    static_assert(sizeof(int) * (3 * kTriRansacThreads + 1) + 2 * sizeof(long long) * (kTrackBlock / 64) <= kTriRansacStaticLds, "");
+    if (lds + kTriRansacStaticLds > 64 * 1024)
+        CHK(opt_in_lds(h, reinterpret_cast<const void*>(kern), kLdsDynMax + 2048 - kTriRansacStaticLds));
+    const TriIn in{h->pt_ptr.as<int>(), h->cam_idx.as<int>(), h->uv.as<double>(), use ? s.use.as<unsigned char>() : nullptr,
+                   select ? h->tri.select.as<unsigned char>() : nullptr, s.x.as<double>() + 6 * h->C};
+    int* const qi = q.ints.as<int>();
+    const TriRansacOut out{q.X_hyp.as<double>(), q.mask.as<unsigned char>(), q.ok.as<unsigned char>(), qi, qi + P, qi + 2 * P,
+                           qi + 3 * P, hyp ? q.hyp.as<int>() : nullptr};
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kTriRansacThreads), lds, h->stream, (const double*)s.tab.as<double>(), in, (int)h->P,
+                       (int)h->C, h->K, ro, out);
+    LAUNCHED(h);
+    return launch_triangulate(h, to, q.mask.as<unsigned char>(), q.ok.as<unsigned char>(), tri_grid);
+}
+
+}  // namespace
+
+void sfmba_default_tri_ransac_options(sfmba_tri_ransac_options* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->threshold = 4.0; o->min_depth = 0.0; o->min_pair_angle_deg = 1.0; o->seed = 0; o->max_pairs = 64; o->min_views = 2;
+    o->refine = 1; o->profile = 0; o->max_iter = 10; o->xtol = 1e-10; o->min_angle_deg = 1.0; o->max_error_px = INFINITY;
+}
+
+int sfmba_triangulate_ransac(sfmba_handle* h, const double* x, const uint8_t* pt_select, const uint8_t* obs_use,
+                             const sfmba_tri_ransac_options* opt, double* X_out, double* X_hyp, uint8_t* inlier_mask,
+                             int32_t* pt_status, int32_t* pt_views, int32_t* pt_inliers, int32_t* pt_best, int32_t* pt_iters,
+                             double* pt_rms_err, double* pt_angle_deg, int32_t* hyp_inliers, int64_t* n_ok, double* kernel_us) {
+    CHK(enter(h));
+    CHK(begin_compute(h, x));
+    sfmba_tri_ransac_options o;
+    if (opt) o = *opt; else sfmba_default_tri_ransac_options(&o);
+    if (std::isnan(o.threshold) || std::isnan(o.min_depth) || std::isnan(o.min_pair_angle_deg) || std::isnan(o.xtol) ||
+        std::isnan(o.min_angle_deg) || std::isnan(o.max_error_px))
+        return fail(h, -1, "an option of sfmba_triangulate_ransac is NaN");
+    if (o.max_pairs < 1) return fail(h, -1, "sfmba_triangulate_ransac: max_pairs must be at least 1");
+    const size_t P = (size_t)h->P, N = (size_t)h->N, H = (size_t)o.max_pairs;
+    if (hyp_inliers && P * H >= (size_t)1 << 31)
+        return fail(h, -1, "sfmba_triangulate_ransac: hyp_inliers of %zu points x %zu pairs passes 2^31 entries", P, H);
+    if (n_ok) *n_ok = 0;
+    if (kernel_us) *kernel_us = 0.0;
+    auto& t = h->tri;
+    auto& q = h->tri_ransac;
+    const TriRansacOptions ro = tri_ransac_options(o);
+    const TriOptions to{o.refine != 0 ? (int)o.max_iter : 0, (int)o.min_views, o.xtol, o.min_angle_deg, o.min_depth, o.max_error_px};
+    int grid = 1, tri_grid = 1, *counts = nullptr;
+    CHK(tri_ransac_allocate(h, ro.H, hyp_inliers != nullptr, &grid, &tri_grid));
+    CHK(stats_prepare(h, x));
+    CHK(stage_masks(h, obs_use, pt_select, P, t.select, 0, &counts));
+    // the staging of what the host combines: status, views, inliers, best | k_triangulate's status; the mask
+    const size_t off_mask = sizeof(int) * 5 * P;
+    HIPCHK(h, q.host.ensure(off_mask + N + 64, 0));
+    int* const hi = q.host.as<int>();
+    unsigned char* const hm = q.host.as<unsigned char>() + off_mask;
+    EventPair timer;
+    CHK(timer.start(h, o.profile != 0));
+    CHK(tri_ransac_clear(h, ro.H, hyp_inliers != nullptr));
+    CHK(launch_tri_ransac(h, ro, to, obs_use != nullptr, pt_select != nullptr, hyp_inliers != nullptr, grid, tri_grid));
+    CHK(timer.stop(h));
+    // k_triangulate leaves the point of x, 0, NaN, NaN wherever it did not run or gave no new point: those four as they are
+    const int* ti = t.ints.as<int>();
+    HIPCHK(h, download(h, X_out, t.X.p, sizeof(double) * 3 * P));
+    HIPCHK(h, download(h, X_hyp, q.X_hyp.p, sizeof(double) * 3 * P));
+    HIPCHK(h, download(h, pt_iters, ti + 2 * P, sizeof(int32_t) * P));
+    HIPCHK(h, download(h, pt_rms_err, t.dbl.p, sizeof(double) * P));
+    HIPCHK(h, download(h, pt_angle_deg, t.dbl.as<double>() + P, sizeof(double) * P));
+    HIPCHK(h, download(h, hyp_inliers, q.hyp.p, sizeof(int32_t) * P * H));
+    if (P) {
+        HIPCHK(h, hipMemcpyAsync(hi, q.ints.p, sizeof(int) * 4 * P, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(hi + 4 * P, ti, sizeof(int) * P, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (inlier_mask && N) HIPCHK(h, hipMemcpyAsync(hm, q.mask.p, N, hipMemcpyDeviceToHost, h->stream));
+    CHK(wait_stream(h));
+    CHK(timer.read(h, kernel_us));
+    if (inlier_mask)
+        for (size_t k = 0; k < N; ++k) inlier_mask[caller_position(h, k)] = hm[k];
+    int64_t ok = 0;
+    for (size_t p = 0; p < P; ++p) {
+        const int status = hi[p] == kTriOk ? hi[4 * P + p] : hi[p];      // RANSAC found a consensus: k_triangulate's verdict counts
+        if (pt_status) pt_status[p] = status;
+        if (pt_views) pt_views[p] = hi[P + p];
+        if (pt_inliers) pt_inliers[p] = hi[2 * P + p];
+        if (pt_best) pt_best[p] = hi[3 * P + p];
+        ok += status == kTriOk ? 1 : 0;
+    }
+    if (n_ok) *n_ok = ok;
+    return 0;
 }
 
 namespace {
@@ -929,7 +1055,7 @@ int sfmba::tri_time_kernel(sfmba_handle* h, const double* x, int32_t reps, doubl
     int grid = 1;
     CHK(tri_allocate(h, &grid));
     CHK(stats_prepare(h, x));
-    return time_reps(h, reps, avg_us, [&] { return launch_triangulate(h, opt, false, false, grid); });
+    return time_reps(h, reps, avg_us, [&] { return launch_triangulate(h, opt, nullptr, nullptr, grid); });
 }
 
 // sfmba_time_kernel, which = 16: k_resect at x over every camera and observation, default options
@@ -956,4 +1082,17 @@ int sfmba::pnp_time_kernel(sfmba_handle* h, const double* x, int32_t reps, doubl
     CHK(stats_cam_perm(h));
     CHK(launch_pnp_gather(h, false, false));
     return time_reps(h, reps, avg_us, [&] { return launch_pnp_ransac(h, pc, false, false, false); });
+}
+
+// sfmba_time_kernel, which = 19: k_tri_ransac + k_triangulate over its mask at x, every point and observation, default options
+int sfmba::tri_ransac_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us) {
+    sfmba_tri_ransac_options o;
+    sfmba_default_tri_ransac_options(&o);
+    const TriRansacOptions ro = tri_ransac_options(o);
+    const TriOptions to{(int)o.max_iter, (int)o.min_views, o.xtol, o.min_angle_deg, o.min_depth, o.max_error_px};
+    int grid = 1, tri_grid = 1;
+    CHK(tri_ransac_allocate(h, ro.H, false, &grid, &tri_grid));
+    CHK(stats_prepare(h, x));
+    CHK(tri_ransac_clear(h, ro.H, false));
+    return time_reps(h, reps, avg_us, [&] { return launch_tri_ransac(h, ro, to, false, false, false, grid, tri_grid); });
 }

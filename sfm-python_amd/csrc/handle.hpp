@@ -318,6 +318,13 @@ struct sfmba_handle {
         DevBuf select;                       // [P]
         DevBuf X, ints, dbl, ok_part;        // [P][3]; [3][P] status, views, iters; [2][P] rms err, angle; [workgroups]
     } tri;
+    // sfmba_triangulate_ransac: works on stats.x / stats.tab and stats.use as sfmba_triangulate does, on
+    // sfmba_triangulate's select mask and result arrays (k_triangulate runs last) and on buffers of its own
+    struct TriRansac {
+        DevBuf mask, ok;                     // [ld] inlier mask, stored order; [P] the best count reaches the need
+        DevBuf X_hyp, ints, hyp;             // [P][3]; [4][P] status, views, inliers, best h; [P][H]
+        PinnedBuf host;                      // staging of the integers and the mask
+    } tri_ransac;
     // sfmba_resect: works on stats.x (the parameter vector of a call outside the solver), the camera-major permutation
     // of the statistics call, stats.use and on result arrays of its own
     struct Resect {
@@ -438,6 +445,7 @@ int tri_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_
 int resect_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us);
 int pnp_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us);
 int cov_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us);                      // 18 (covariance.hip)
+int tri_ransac_time_kernel(sfmba_handle* h, const double* x, int32_t reps, double* avg_us);               // 19 (consumers.hip)
 // k_schur_blocks over the problem's pair lists at zero damping: blocks of W Vinv W^T -> Sblk [n_blk][36] (no rhs term)
 int launch_k_schur_blocks(sfmba_handle* h, const double* tab, const double* rec, const double* Vinv, double* Sblk);
 // the camera-major permutation of ALL observations (stats.perm / stats.cam_ptr), built once per problem (consumers.hip)

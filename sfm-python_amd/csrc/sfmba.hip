@@ -93,7 +93,7 @@ static_assert(sizeof(TableRow4) == sizeof(int4) && alignof(TableRow4) == alignof
 
 namespace sfmba {
 constexpr size_t kLdsBytes = 160 * 1024;       // gfx950: 160 KiB LDS per workgroup
-const size_t kLdsDynMax = kLdsBytes - 2048;     // dynamic part; every kernel here has <= 2 KiB static LDS (k_backsub: 1280 B)
+const size_t kLdsDynMax = kLdsBytes - 2048;     // dynamic part; every kernel that asks for it has <= 2 KiB static LDS (k_backsub: 1280 B); k_tri_ransac (3152 B) asks for less: launch_tri_ransac
 const int kRecStride = kRec, kVinvStride = kVinvRow;
 
 int fail(sfmba_handle* h, int code, const char* fmt, ...) {
@@ -2111,6 +2111,7 @@ int sfmba_time_kernel(sfmba_handle* h, const double* x, int32_t which, int32_t r
     if (which == 16) return resect_time_kernel(h, x, reps, avg_us);
     if (which == 17) return pnp_time_kernel(h, x, reps, avg_us);
     if (which == 18) return cov_time_kernel(h, x, reps, avg_us);
+    if (which == 19) return tri_ransac_time_kernel(h, x, reps, avg_us);
     int np = 0;
     CHK(linearise_at(h, x, which >= 2));
     if (which >= 2) {

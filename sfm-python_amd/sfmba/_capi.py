@@ -55,6 +55,13 @@ class PnpRansacOptions(C.Structure):
                 ("max_iter", C.c_int32), ("reserved", C.c_int32), ("xtol", C.c_double), ("max_rms_px", C.c_double)]
 
 
+class TriRansacOptions(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("min_depth", C.c_double), ("min_pair_angle_deg", C.c_double), ("seed", C.c_uint64),
+                ("max_pairs", C.c_int32), ("min_views", C.c_int32), ("refine", C.c_int32), ("profile", C.c_int32),
+                ("max_iter", C.c_int32), ("reserved", C.c_int32), ("xtol", C.c_double), ("min_angle_deg", C.c_double),
+                ("max_error_px", C.c_double)]
+
+
 class RansacOptions(C.Structure):
     _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("seed", C.c_uint64), ("max_iters", C.c_int32),
                 ("refit", C.c_int32), ("profile", C.c_int32), ("reserved", C.c_int32)]
@@ -130,6 +137,8 @@ SIGNATURES = {
     "sfmba_resect": (INT, [P, P, P, P, REF(ResectOptions)] + [P] * 5 + [REF(I64)]),
     "sfmba_default_pnp_ransac_options": (None, [REF(PnpRansacOptions)]),
     "sfmba_resect_ransac": (INT, [P] * 5 + [REF(PnpRansacOptions)] + [P] * 12 + [REF(I64), REF(F64)]),
+    "sfmba_default_tri_ransac_options": (None, [REF(TriRansacOptions)]),
+    "sfmba_triangulate_ransac": (INT, [P] * 4 + [REF(TriRansacOptions)] + [P] * 11 + [REF(I64), REF(F64)]),
     "sfmba_default_ransac_options": (None, [REF(RansacOptions)]),
     "sfmba_fundamental_ransac": (INT, [P, I64] + [P] * 5 + [REF(RansacOptions)] + [P] * 8 + [REF(I64), REF(F64)]),
     "sfmba_homography_ransac": (INT, [P, I64] + [P] * 5 + [REF(RansacOptions)] + [P] * 10 + [REF(I64), REF(F64)]),

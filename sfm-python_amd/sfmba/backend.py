@@ -11,8 +11,8 @@ from .checks import (_edge_batch, _f64, _fill_options, _mask, _opt_ptr, _ransac_
                      check_descriptors, check_essential_args, check_match_edges, check_match_options, check_plan_inputs,
                      check_similarity_inputs, check_track_inputs)
 from .results import (Covariance, DescriptorMatches, EssentialEstimate, FundamentalEstimate,  # noqa: F401 (likewise)
-                      HomographyEstimate, RelativePose, ReprojectionStats, Resection, RobustResection, SimilarityEstimate,
-                      SubProblem, Tracks, Triangulation, ViewPlan)
+                      HomographyEstimate, RelativePose, ReprojectionStats, Resection, RobustResection, RobustTriangulation,
+                      SimilarityEstimate, SubProblem, Tracks, Triangulation, ViewPlan)
 
 
 class BackendError(RuntimeError):
@@ -342,6 +342,44 @@ class Backend:
             _capi.ptr(use) if use is not None else None, C.byref(opt), _capi.ptr(points), _capi.ptr(status),
             _capi.ptr(views), _capi.ptr(iters), _capi.ptr(rms), _capi.ptr(ang), C.byref(n_ok)))
         return Triangulation(points, status, views, iters, rms, ang, n_ok.value)
+
+    def triangulate_ransac(self, x, select=None, obs_use=None, want_hyp=False, **options):
+        """Triangulate the selected points of the current problem robustly: hypotheses from pairs of a point's used
+        observations (all pairs while there are at most ``max_pairs``, else that many drawn on the device from ``seed``),
+        scored over all of them, then :meth:`triangulate` over the inliers of the best (include/sfmba.h:
+        sfmba_triangulate_ransac).  ``select`` (P) and ``obs_use`` (N, the caller's order): boolean masks, None = all.
+        ``options``: fields of ``sfmba_tri_ransac_options`` (threshold, min_depth, min_pair_angle_deg, seed, max_pairs,
+        min_views, refine, profile, max_iter, xtol, min_angle_deg, max_error_px).  ``want_hyp``: also return the count of
+        every hypothesis.  -> :class:`RobustTriangulation`."""
+        self._flush_pending()
+        x = _f64(x, (self.n_params,), "x")
+        opt = _capi.TriRansacOptions()
+        self._lib.sfmba_default_tri_ransac_options(C.byref(opt))
+        options = dict(options)
+        if "seed" in options:
+            seed = int(options.pop("seed"))
+            if not 0 <= seed < 2 ** 64:
+                raise ValueError("seed must fit 64 unsigned bits")
+            opt.seed = seed
+        _fill_options(opt, options, "robust triangulation")
+        if opt.max_pairs < 1:
+            raise ValueError("max_pairs must be at least 1")
+        P, N, H = self.n_points, self.n_obs, int(opt.max_pairs)
+        if want_hyp and P * H >= 2 ** 31:
+            raise ValueError(f"hyp_inliers of {P} points x {H} pairs passes 2^31 entries")
+        sel, use = _mask(select, P, "select"), _mask(obs_use, N, "obs_use")
+        points, hyp_points = np.empty((P, 3)), np.empty((P, 3))
+        mask = np.zeros(N, dtype=np.uint8)
+        status, views, inl, best, iters = (np.empty(P, dtype=np.int32) for _ in range(5))
+        rms, ang = np.empty(P), np.empty(P)
+        hyp = np.empty((P, H), dtype=np.int32) if want_hyp else None
+        n_ok, us = C.c_int64(), C.c_double()
+        self._check(self._lib.sfmba_triangulate_ransac(
+            self._h, _capi.ptr(x), _opt_ptr(sel), _opt_ptr(use), C.byref(opt), _capi.ptr(points), _capi.ptr(hyp_points),
+            _capi.ptr(mask), _capi.ptr(status), _capi.ptr(views), _capi.ptr(inl), _capi.ptr(best), _capi.ptr(iters),
+            _capi.ptr(rms), _capi.ptr(ang), _opt_ptr(hyp), C.byref(n_ok), C.byref(us)))
+        return RobustTriangulation(points, status, views, iters, rms, ang, int(n_ok.value), hyp_points,
+                                   mask.view(np.bool_), inl, best, hyp, float(us.value))
 
     def resect(self, x, select=None, obs_use=None, **options):
         """Resect the selected cameras of the current problem from their used observations and the points of ``x``:

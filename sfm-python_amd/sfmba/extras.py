@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import api
+from . import _capi, api
 from .backend import check_descriptors, check_essential_args, check_match_edges, check_match_options, check_track_inputs
 
 
@@ -119,6 +119,15 @@ def triangulate_tracks(x, args, select=None, obs_use=None, device=0, backend=Non
     -> :class:`sfmba.Triangulation`."""
     be = _backend_with_problem(args, device, backend)
     return be.triangulate(x, select=select, obs_use=obs_use, **options)
+
+
+def triangulate_tracks_ransac(x, args, select=None, obs_use=None, want_hyp=False, device=0, backend=None, **options):
+    """`Backend.triangulate_ransac` in one call on the reference's ``args`` tuple (sfm.py:268): every selected point by a
+    RANSAC over pairs of its used observations, then :func:`triangulate_tracks` over the inliers of the best pair --
+    one wrong observation costs a track that observation, not the point.  ``options``: the fields of
+    ``sfmba_tri_ransac_options``.  -> :class:`RobustTriangulation`."""
+    be = _backend_with_problem(args, device, backend)
+    return be.triangulate_ransac(x, select=select, obs_use=obs_use, want_hyp=want_hyp, **options)
 
 
 def resect_cameras(x, args, select=None, obs_use=None, device=0, backend=None, **options):
@@ -781,7 +790,7 @@ def _initial_edge(matches, pts, K, init, be, init_options=None):
 
 def reconstruct(matches, pts, K, tracks=None, init=None, batch=1, min_known=7, filter=True, fix_first=False, ftol=1e-10,
                 ransac_options=None, triangulate_options=None, filter_options=None, filter_rounds=2, max_rounds=None,
-                record_state=False, device=0, backend=None, init_options=None):
+                record_state=False, device=0, backend=None, init_options=None, robust_triangulation=False):
     """Incremental reconstruction, the loop of ``SFM.construct`` (sfm.py:59-71, 182-241) camera by camera on one
     :class:`Backend`: `plan_views` chooses the next images, `assemble_problem` cuts the growing problem out of the tracks,
     `resect_ransac` registers, `triangulate` adds points, bundle adjustment and (``filter=True``)
@@ -798,6 +807,10 @@ def reconstruct(matches, pts, K, tracks=None, init=None, batch=1, min_known=7, f
     ``ransac_options``, ``triangulate_options``: fields of the two calls' option structures;
     ``filter_options``: ``max_error_px`` (4), ``min_depth`` (0), ``min_angle_deg`` (2), ``min_views`` (2) of the trim
     and of the final pass; ``fix_first=True`` holds camera u still in every solve (the reference holds nothing).
+    ``robust_triangulation=True``: the rounds add points with `triangulate_ransac` -- a track with a wrong observation
+    comes back with its point and that observation is dropped for good, as after `resect_ransac`, where `triangulate`
+    would refuse the whole track round after round; ``triangulate_options`` may then name the fields of
+    ``sfmba_tri_ransac_options`` as well, and ``threshold`` defaults to ``max_error_px`` of the trim (4 without one).
     -> :class:`Reconstruction`."""
     be = backend if backend is not None else api.get_backend(device)
     K = np.asarray(K, dtype=np.float64)
@@ -819,6 +832,12 @@ def reconstruct(matches, pts, K, tracks=None, init=None, batch=1, min_known=7, f
     # a new point must pass the pixel threshold of the trim as well: bundle adjustment is a plain least squares, and
     # one track with a wrong observation bends the cameras until good observations fail the trim that follows it
     triangulate_options.setdefault("max_error_px", thr["max_error_px"])
+    robust_options = None
+    if robust_triangulation:
+        robust_options = dict(triangulate_options)
+        robust_options.setdefault("threshold", thr["max_error_px"] if np.isfinite(thr["max_error_px"]) else 4.0)
+        plain = {f[0] for f in _capi.TriangulateOptions._fields_}
+        triangulate_options = {k: v for k, v in triangulate_options.items() if k in plain}      # (the initial pair's call)
     if tracks is None:
         tracks = build_tracks(matches, [len(p) for p in pts], backend=be)
     elif getattr(be, "_plan_dims", None) != (n_images, tracks.n_tracks):
@@ -900,8 +919,14 @@ def reconstruct(matches, pts, K, tracks=None, init=None, batch=1, min_known=7, f
         feat_ok[sub.obs_feat[resect_use & new_cam[sub.camera_indices] & ~rr.inlier_mask]] = False
         obs_ok = feat_ok[sub.obs_feat]
         x = np.nan_to_num(sub.gather(cameras, points), nan=0.0)
-        tri = be.triangulate(x, select=~known[sub.pt_of], obs_use=registered[sub.cam_of][sub.camera_indices] & obs_ok,
-                             **triangulate_options)
+        if robust_triangulation:
+            tri_use = registered[sub.cam_of][sub.camera_indices] & obs_ok
+            tri = be.triangulate_ransac(x, select=~known[sub.pt_of], obs_use=tri_use, **robust_options)
+            # what the point of a new track does not agree with is a wrong match in the track: dropped for good
+            feat_ok[sub.obs_feat[tri_use & tri.ok[sub.point_indices] & ~tri.inlier_mask]] = False
+        else:
+            tri = be.triangulate(x, select=~known[sub.pt_of], obs_use=registered[sub.cam_of][sub.camera_indices] & obs_ok,
+                                 **triangulate_options)
         info["points_added"] = take_points(sub, tri)
         # bundle adjustment over the registered cameras and the known tracks, without the observations dropped so far
         x, args, cam_of, pt_of, obs_feat = _final_set(be, registered, known, feat_ok, cameras, points, K)

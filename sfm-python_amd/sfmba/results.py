@@ -346,6 +346,26 @@ class Triangulation:
         return f"Triangulation(n_points={len(self.status)}, n_ok={self.n_ok})"
 
 
+class RobustTriangulation(Triangulation):
+    """What `Backend.triangulate_ransac` returns (include/sfmba.h: sfmba_triangulate_ransac): the fields of
+    :class:`Triangulation` -- ``points`` the refined point where ``status`` is 0, ``views`` the used observations,
+    ``iters``, ``rms_err`` and ``angle_deg`` those of the refinement over the inliers -- and ``hyp`` (P, 3) the best
+    hypothesis' point, unrefined; ``inlier_mask`` (N, bool) in the caller's observation order; ``inliers``, ``best`` (the
+    winning hypothesis) (P, int32); ``hyp_inliers`` (P, H) the count of every hypothesis, or None when not asked for;
+    ``kernel_us`` (``profile=1``, else 0).  ``status`` may also be ``NO_CONSENSUS``."""
+
+    NO_CONSENSUS = 6
+
+    def __init__(self, points, status, views, iters, rms_err, angle_deg, n_ok, hyp, inlier_mask, inliers, best,
+                 hyp_inliers, kernel_us=0.0):
+        super().__init__(points, status, views, iters, rms_err, angle_deg, n_ok)
+        self.hyp, self.inlier_mask, self.inliers, self.best = hyp, inlier_mask, inliers, best
+        self.hyp_inliers, self.kernel_us = hyp_inliers, float(kernel_us)
+
+    def __repr__(self):
+        return f"RobustTriangulation(n_points={len(self.status)}, n_ok={self.n_ok})"
+
+
 class Resection:
     """What `Backend.resect` returns (include/sfmba.h: sfmba_resect).  ``cameras`` (C, 6): the new pose (rotation vector,
     centre -- the bundle-adjustment model's parameters) where ``status`` is 0, else the camera of ``x``; ``status`` (C)
